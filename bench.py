@@ -4,6 +4,13 @@
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1 launched under
 torch.distributed.run, one rank per GPU. Prints ONE JSON line on rank 0.
 
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the outputs
+(`--dump-outputs DIR`) and the line. Everything else the benchmark measures (roofline replays,
+latency / TTFA, other batch sizes and configurations, EOS mix, CPU baseline) runs with `--full`.
+`--dump-outputs DIR` writes what rank 0's last timed step handed back — every utterance's PCM, float32
+(rows, samples) — as DIR/pcm.npy; above 64 MB, a fixed seeded sample of it instead (pcm_sample.npy and
+its flat indices, pcm_sample_index.npy). Inputs are seeded: the same arguments give the same inputs.
+
 A "step" = one non-streaming synthesis (prefill → generate → decode, the reference's
 `synthesize_with_timing`, lib.rs:425-501 / benches/e2e_bench.rs:207-262) of this rank's batch of
 utterances: synthetic 512-token prompts, CustomVoice prefill, eos_token_id = None and a fixed frame
@@ -12,7 +19,7 @@ count so the work is identical across engines, default sampling (temperature 0.9
 Weak scaling: every GPU gets `--batch` utterances (config[3] of BASELINE.json: 64 utterances over 8
 GPUs = 8 per GPU); value = frames of ALL ranks / max-over-ranks time.
 
-Extra objects: "roofline" (frac = the whole captured frame against the HBM roof, measured by this
+Extra objects (--full): "roofline" (frac = the whole captured frame against the HBM roof, measured by this
 run; the GEMV family alone — isolated replay, and inside the graph from the committed rocprof table —
 in sub-objects that say which is which) and "cpu_baseline" (the
 C oracle = port of the reference's candle-CPU F32 path, timed on this host's cores on a bounded
@@ -22,6 +29,7 @@ import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -30,6 +38,7 @@ sys.path.insert(0, ROOT)
 # Figures that cannot be taken from inside the run (rocprofv3 kernel tables, PMC passes) come from files committed under
 # profiles/ for THIS round only: an older round's profile is never substituted silently — the field is null instead.
 PROFILE_ROUND = "r6"
+DUMP_LIMIT = 64 << 20      # bytes --dump-outputs may write in all
 
 
 def committed_rocprof_table(avg_bytes_per_launch, model, batch):
@@ -59,6 +68,20 @@ def committed_rocprof_table(avg_bytes_per_launch, model, batch):
     return None
 
 
+def dump_outputs(path, pcm):
+    """pcm: (rows, samples) float32, what the timed path returned to its caller. Whole when it fits in DUMP_LIMIT, else a
+    fixed, seeded sample of its elements (sorted, duplicates removed) with their flat indices as float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if pcm.nbytes <= DUMP_LIMIT - 4096:       # (room for the .npy headers)
+        np.save(os.path.join(path, "pcm.npy"), pcm)
+        return
+    n = (DUMP_LIMIT - 4096) // (4 + 8)
+    idx = np.unique(np.random.default_rng(0).integers(0, pcm.size, size=n))
+    np.save(os.path.join(path, "pcm_sample.npy"), pcm.reshape(-1)[idx])
+    np.save(os.path.join(path, "pcm_sample_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -79,10 +102,15 @@ def main():
     ap.add_argument("--cpu-frames-single", type=int, default=8, help="frames of the single-thread CPU-baseline sample (~8 s)")
     ap.add_argument("--profile-frames", type=int, default=6)
     ap.add_argument("--ttfa-reps", type=int, default=5)
-    ap.add_argument("--headline-only", action="store_true", help="only the timed steps: no roofline replays, latency / TTFA, other batches, other configurations, "
-                    "EOS mix or CPU baseline (the command the committed rocprofv3 kernel table is taken from)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline replays, latency / TTFA, other batches, other configurations, "
+                    "EOS mix and CPU baseline (a plain run does set-up, warm-up, the timed steps, --dump-outputs and the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the PCM of rank 0's last timed step to DIR/*.npy (float32, at most 64 MB)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: only the timed steps and the frame roofline: no roofline replays, latency / TTFA, "
+                    "other batches, other configurations, EOS mix or CPU baseline. Without --full every run is headline-only")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the BASELINE.json side configurations (greedy, x-vector, 4k-token VoiceDesign, 0.6B single utterance)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.headline_only:
         args.no_cpu_baseline = True; args.no_other_configs = True; args.also_batches = ""; args.ttfa_reps = 0
 
@@ -91,8 +119,9 @@ def main():
     same_gpu = os.environ.get("Q3_DP_TEST_SAME_GPU") == "1"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become N ranks ourselves (one process per GPU), never a silent world = 1
-        n_vis = torch.cuda.device_count()
-        if n_vis < args.gpus and not same_gpu:
+        # (this process only launches and waits: it touches no GPU in the same-GPU test mode, and it is never replaced)
+        n_vis = args.gpus if same_gpu else torch.cuda.device_count()
+        if n_vis < args.gpus:
             raise SystemExit(f"bench.py: --gpus {args.gpus} requested but only {n_vis} GPU(s) are visible")
         import socket
         with socket.socket() as so:
@@ -100,7 +129,10 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execvp(sys.executable, cmd)
+        import signal
+        child = subprocess.Popen(cmd)
+        signal.signal(signal.SIGTERM, lambda *_: child.terminate())      # a time limit on this process reaches the ranks
+        raise SystemExit(child.wait())
     import qwen3_tts_rs_amd as q
     from qwen3_tts_rs_amd import dp, synth
 
@@ -157,6 +189,7 @@ def main():
 
     submit_path = [0, 0, 0, 0]    # (path, packets per frame, packets without acquire / release fence) of the timed sessions: q3_session_submit_info / _fences
     phase_ms = []       # (create, run, close) wall per step: the timed step is all three
+    last_samples = []   # samples per row of the latest step (what --dump-outputs writes of the pinned rows)
     # the samples of every utterance land in host memory inside the timed step, as `synthesize` returns them
     # (lib.rs:718-784): one pinned buffer per row, reused step after step (allocated once, outside the timing, like a
     # server's output ring)
@@ -173,7 +206,9 @@ def main():
         s = model.session(utts, opts)
         tb = time.perf_counter()
         try:
-            return s.run_timing_only(use_graph=use_graph, pcm_out=pcm_out)
+            t = s.run_timing_only(use_graph=use_graph, pcm_out=pcm_out)
+            last_samples[:] = s.last_samples
+            return t
         finally:
             tc = time.perf_counter()
             try:
@@ -238,6 +273,11 @@ def main():
         finish()
         return
 
+    if args.dump_outputs:      # before any --full leg: those reuse the pinned rows
+        n_s = set(last_samples)
+        assert len(n_s) == 1, f"rows of the last step hold different sample counts: {last_samples}"
+        dump_outputs(args.dump_outputs, pinned[len(utts)][:, :n_s.pop()].numpy().copy())
+
     ms_per_step = elapsed / args.steps * 1000.0
     fps = frames_total / elapsed
     audio_s_per_utt = args.frames * cfg.samples_per_frame / 24000.0
@@ -246,6 +286,33 @@ def main():
     stage = {"prefill_ms": float(np.mean([t.prefill_ms for t in timings])),
              "generation_ms": float(np.mean([t.generation_ms for t in timings])),
              "decode_ms": float(np.mean([t.decode_ms for t in timings]))}
+    out = {
+        "metric": "acoustic_frames_per_sec", "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": f"Qwen3-TTS-{args.model} synthetic weights; {B} utterances/GPU x {world} GPU(s), "
+                               f"{args.prompt_tokens}-token prompts, {args.workload} prefill, {args.frames} frames each "
+                               f"(eos off), {args.sampling} sampling, non-streaming prefill+generate+decode",
+                   "utterances_per_gpu": B, "frames_per_utterance": args.frames, "parallelism": f"dp{world}",
+                   "weights": "bf16", "activations_kv": "f32",
+                   "kv": "f32, in place (2x the bytes of the reference GPU path's bf16 cache, kv_cache.rs:234-310: the parity contract is the CPU F32 path)",
+                   "hip_graph": use_graph,
+                   "frame_submit": {0: "eager launches", 1: "hipGraphLaunch", 2: "own AQL queue, HIP's fences on every packet",
+                                    3: "own AQL queue, no fences (probe: invalid)",
+                                    4: "captured frame replayed on the library's own AQL queue; boundaries between write-through kernels without agent-scope fences"}.get(submit_path[0], str(submit_path[0])),
+                   "frame_packets": submit_path[1], "frame_packets_without_acquire_release_fence": submit_path[2:4], "prefill": args.workload, "sampling": args.sampling,
+                   "pcm_copy_out": True},      # every utterance's samples are copied to (pinned) host memory inside the timed step
+        "rtf": rtf_job, "rtf_per_utterance": rtf_utt, "stage_ms": stage, "step_wall_ms": step_wall, "step_phase_ms_create_run_close": phase_ms[-args.steps:],
+        "weights_load_s": load_s, "weight_broadcast": {"bytes": bcast_bytes, "seconds": bcast_s,
+                                                        "gbps": (bcast_bytes / bcast_s / 1e9) if bcast_s > 0 else None,
+                                                        "expected": "one RCCL broadcast of the 4.4 GB arena from rank 0: ~30 ms per-link bound on xGMI (~150 GB/s), "
+                                                                    "more on the first call (communicator set-up); steady state has no collective (DESIGN 6)"},
+        "rccl": rccl,
+    }
+    if not args.full:      # a plain run: the headline line and nothing else
+        print(json.dumps(out), flush=True)
+        finish()
+        return
 
     # (measured right behind the timed steps; round 6 saw 2496-2578 frames/s from this leg box to box, 2558-2587 from the same loop
     #  alone in a process, tools/dev/eos_mix_ab.py — profiles/r6_eos_mix_staged_ab.txt)
@@ -513,29 +580,7 @@ def main():
         except Exception as e:
             cpu = {"value": None, "unit": "frames/s", "cores": min(os.cpu_count() or 1, 32), "kind": "port", "sample": f"failed: {e}"}
 
-    out = {
-        "metric": "acoustic_frames_per_sec", "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": f"Qwen3-TTS-{args.model} synthetic weights; {B} utterances/GPU x {world} GPU(s), "
-                               f"{args.prompt_tokens}-token prompts, {args.workload} prefill, {args.frames} frames each "
-                               f"(eos off), {args.sampling} sampling, non-streaming prefill+generate+decode",
-                   "utterances_per_gpu": B, "frames_per_utterance": args.frames, "parallelism": f"dp{world}",
-                   "weights": "bf16", "activations_kv": "f32",
-                   "kv": "f32, in place (2x the bytes of the reference GPU path's bf16 cache, kv_cache.rs:234-310: the parity contract is the CPU F32 path)",
-                   "hip_graph": use_graph,
-                   "frame_submit": {0: "eager launches", 1: "hipGraphLaunch", 2: "own AQL queue, HIP's fences on every packet",
-                                    3: "own AQL queue, no fences (probe: invalid)",
-                                    4: "captured frame replayed on the library's own AQL queue; boundaries between write-through kernels without agent-scope fences"}.get(submit_path[0], str(submit_path[0])),
-                   "frame_packets": submit_path[1], "frame_packets_without_acquire_release_fence": submit_path[2:4], "prefill": args.workload, "sampling": args.sampling,
-                   "pcm_copy_out": True},      # every utterance's samples are copied to (pinned) host memory inside the timed step
-        "rtf": rtf_job, "rtf_per_utterance": rtf_utt, "stage_ms": stage, "step_wall_ms": step_wall, "step_phase_ms_create_run_close": phase_ms[-args.steps:], "latency": lat,
-        "weights_load_s": load_s, "weight_broadcast": {"bytes": bcast_bytes, "seconds": bcast_s,
-                                                        "gbps": (bcast_bytes / bcast_s / 1e9) if bcast_s > 0 else None,
-                                                        "expected": "one RCCL broadcast of the 4.4 GB arena from rank 0: ~30 ms per-link bound on xGMI (~150 GB/s), "
-                                                                    "more on the first call (communicator set-up); steady state has no collective (DESIGN 6)"},
-        "roofline": roofline, "cpu_baseline": cpu, "other_batches": wide, "other_configs": others, "eos_mix": eos_mix, "rccl": rccl,
-    }
+    out.update({"latency": lat, "roofline": roofline, "cpu_baseline": cpu, "other_batches": wide, "other_configs": others, "eos_mix": eos_mix})
     print(json.dumps(out), flush=True)
     finish()
 

@@ -41,6 +41,7 @@ import torch
 import torch.nn.functional as F
 import qwen3_tts_rs_amd as q
 from qwen3_tts_rs_amd import synth
+import golden_io
 from common import manifest_handle, synthetic_prompt
 
 from transformers.models.qwen3_omni_moe import modeling_qwen3_omni_moe as M
@@ -193,7 +194,7 @@ def main():
     out["talker_last_hidden"] = hn.numpy()
     out["talker_logits"] = F.linear(hn, W["talker.codec_head.weight"].reshape(cfg.codec_vocab, cfg.hidden)).numpy()
 
-    np.savez_compressed(OUT, **out)
+    golden_io.save(OUT, **out)
     print("wrote", OUT, {k: v.shape for k, v in out.items()})
     mimi_fixture()
 

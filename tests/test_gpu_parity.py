@@ -911,7 +911,7 @@ def test_bench_two_ranks_same_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--model", "tiny", "--steps", "1", "--warmup", "1", "--frames", "12",
-                        "--batch", "2", "--also-batches", "", "--no-cpu-baseline", "--no-other-configs", "--ttfa-reps", "1", "--prompt-tokens", "16"],
+                        "--batch", "2", "--full", "--also-batches", "", "--no-cpu-baseline", "--no-other-configs", "--ttfa-reps", "1", "--prompt-tokens", "16"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -924,24 +924,30 @@ def test_bench_two_ranks_same_gpu():
 
 @pytest.mark.gpu
 def test_bench_eight_ranks_same_gpu():
-    """8-rank rehearsal of the driver's SCALE run: `bench.py --gpus 8` spawns eight ranks itself, all on
-    cuda:0 over gloo (Q3_DP_TEST_SAME_GPU=1; RCCL refuses several ranks per device), tiny model. Arena broadcast to seven
-    non-root ranks, their finalize, barriers, max-over-ranks timing, sum of frames over ranks, eight entries in
-    rccl.ranks_seen, every rank leaves with exit code 0."""
+    """8-rank run of the driver's SCALE flow: `bench.py --gpus 8` spawns eight ranks itself, tiny model.
+    Arena broadcast to seven non-root ranks, their finalize, barriers, max-over-ranks timing, sum of frames over ranks,
+    eight entries in rccl.ranks_seen, every rank leaves with exit code 0. It needs eight GPUs, one rank per device over
+    RCCL: eight ranks sharing one device (the same-GPU mode of the two-rank test) would keep nine processes on one card
+    at once."""
     import json, subprocess, sys
+    n_dev = _lib.lib.q3_device_count()
+    if n_dev < 8:
+        pytest.skip(f"needs 8 GPUs, found {n_dev}")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ); env["Q3_DP_TEST_SAME_GPU"] = "1"; env["MASTER_ADDR"] = "127.0.0.1"
+    env = dict(os.environ); env["MASTER_ADDR"] = "127.0.0.1"
+    env.pop("Q3_DP_TEST_SAME_GPU", None)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--model", "tiny", "--steps", "2", "--warmup", "1", "--frames", "12",
-                        "--batch", "2", "--also-batches", "", "--no-cpu-baseline", "--no-other-configs", "--ttfa-reps", "1", "--prompt-tokens", "16"],
+                        "--batch", "2", "--full", "--also-batches", "", "--no-cpu-baseline", "--no-other-configs", "--ttfa-reps", "1", "--prompt-tokens", "16"],
                        capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     out = json.loads(lines[0])
     assert out["n_gpus"] == 8 and out["scaling"] == "weak" and out["value"] > 0
-    assert out["rccl"]["world"] == 8 and sorted(x[0] for x in out["rccl"]["ranks_seen"]) == list(range(8)) and out["rccl"]["same_gpu_test_mode"] is True
+    assert out["rccl"]["world"] == 8 and sorted(x[0] for x in out["rccl"]["ranks_seen"]) == list(range(8)) and out["rccl"]["same_gpu_test_mode"] is False
+    assert out["rccl"]["backend"] == "nccl" and sorted(x[1] for x in out["rccl"]["ranks_seen"]) == list(range(8))
     assert out["config"]["utterances_per_gpu"] == 2 and out["weight_broadcast"]["bytes"] > 0
     # weak scaling bookkeeping: 8 ranks x 2 utterances x 12 frames x 2 steps over the max-over-ranks time
     assert abs(out["value"] * out["ms_per_step"] / 1000.0 - 8 * 2 * 12) < 1e-6 * 8 * 2 * 12

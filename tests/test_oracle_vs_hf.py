@@ -9,6 +9,7 @@ import os
 import numpy as np
 
 import qwen3_tts_rs_amd as q
+import golden_io
 import oracle as O
 from common import oracle_model, synthetic_prompt
 
@@ -21,7 +22,7 @@ def _rel(a, b):
 
 
 def test_decoder_stages_match_hf_code2wav_and_mimi_rvq():
-    fx = np.load(FX)
+    fx = golden_io.load(FX)
     cfg = q.tiny()
     om = oracle_model(cfg, seed=SEED, which=2)
     pcm, taps = om.decode(fx["codes"], taps=True)
@@ -42,7 +43,7 @@ def test_decoder_stages_match_hf_code2wav_and_mimi_rvq():
 def test_trans_conv_trim_rule_vs_hf_module():
     """Documented difference 1: HF's CausalTransConvNet trims k - s samples at BOTH ends, the reference at the right end
     only (causal_trans_conv.rs:76-99). Oracle == reference rule; HF module output == the same signal without its first r samples."""
-    fx = np.load(FX)
+    fx = golden_io.load(FX)
     cfg = q.tiny()
     x = np.ascontiguousarray(fx["transconv_blk0_input"])                       # [cin][L] after SnakeBeta
     cin, L = x.shape; r = cfg.dec_up_rates[0]; cout = cin // 2
@@ -60,7 +61,7 @@ def test_trans_conv_trim_rule_vs_hf_module():
 
 
 def test_talker_layers_match_hf_qwen3_decoder_layer():
-    fx = np.load(FX)
+    fx = golden_io.load(FX)
     cfg = q.tiny()
     om = oracle_model(cfg, seed=SEED, which=1)
     utt = q.Utterance(synthetic_prompt(9, 3), q.Speaker.Ryan, q.Language.English, seed=1)
