@@ -279,6 +279,30 @@ q3_status q3_batcher_fetch(q3_batcher* b, int64_t ticket, uint32_t* codes_host, 
  * "improved overlap mode"). */
 q3_status q3_session_set_stream_mode(q3_session* s, int mode);
 
+/* ---------------- streaming text input: a row's text arrives while it speaks ----------------
+ * Qwen3-TTS reads its text one token per frame after the prefill ("trailing text", lib.rs:508-519, 613-619): frame f of a row
+ * depends on the text only through trailing token f. A row OPENED before q3_session_prefill takes the rest of its text in pieces
+ * (q3_session_append_text); a frame whose trailing token has not arrived yet is not committed — the row is HELD in it (no
+ * token, counter or state of the row moves) while the other rows go on — and runs as if it had never waited once the token is
+ * there. tts_eos, then tts_pad follow the append that closes the text (last != 0). For any feeding schedule an open row's codes
+ * and PCM equal those of the same request with its whole text. q3_session_generate never replays a frame in which
+ * no row can commit; q3_session_next_chunk / _row return *n_samples = 0, *done = 0 while a whole chunk is not possible yet;
+ * q3_session_run refuses a session with an open row. q3_session_prefill_len / Q3_GET_TRAILING report the trailing rows present.
+ * No reference counterpart (the reference takes the whole text per call). */
+/* Open row b: before q3_session_prefill, not in a ragged first batch nor a debug / profiling session. The request must carry at
+ * least one text token (the prefill consumes it); an ICL request at least n_ref + 1 - n_ref_text, and a max_length within the
+ * session's frame budget (its length cap max(75, 6 n_text) is resolved when the text closes). */
+q3_status q3_session_open_text(q3_session* s, int b);
+/* Append n text tokens to open row b; last != 0 closes its text. Waits for the session's frames in flight, projects the tokens on
+ * the session stream (one fixed path: a token's row does not depend on how it was fed) and publishes them. Text beyond the row's
+ * slot (1024 rows, or the session's prompt budget + 1024) is refused with Q3_UNSUPPORTED; an append after the close with
+ * Q3_INVALID_ARG; appends to a row that has ended (EOS / max_length) are accepted and ignored. */
+q3_status q3_session_append_text(q3_session* s, int b, const uint32_t* ids, int n, int last);
+/* Row b: text tokens received (n_text), frames committed, frames it can still commit with the text it has (0 when held or
+ * done), whether its text is closed; frames_replayed = frames the session has replayed, all rows. Any pointer may be NULL. */
+q3_status q3_session_text_state(q3_session* s, int b, int* n_text, int* frames_committed, int* frames_runnable, int* closed,
+                                int* frames_replayed);
+
 /* ---------------- stage-level entry points (parity tests; the reference's
  * tests/reference_validation.rs stages) ---------------- */
 enum {

@@ -119,6 +119,9 @@ SYMBOLS = {
     "q3_session_submit_info": (c_int, [c_void_p, P(c_int), P(c_int)]),
     "q3_session_submit_fences": (c_int, [c_void_p, P(c_int), P(c_int)]),
     "q3_session_set_stream_mode": (c_int, [c_void_p, c_int]),
+    "q3_session_open_text": (c_int, [c_void_p, c_int]),
+    "q3_session_append_text": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int]),
+    "q3_session_text_state": (c_int, [c_void_p, c_int, P(c_int), P(c_int), P(c_int), P(c_int), P(c_int)]),
     "q3_model_config": (c_int, [c_void_p, P(CConfig)]),
     "q3_config_default": (c_int, [c_int, P(CConfig)]),
     "q3_config_from_json": (c_int, [c_char_p, P(CConfig), P(c_int)]),

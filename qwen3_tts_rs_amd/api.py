@@ -250,6 +250,25 @@ class Session:
     def prefill(self):
         check(lib.q3_session_prefill(self._h))
 
+    # ---- streaming text input ----
+    def open_text(self, b: int):
+        """Row b takes the rest of its text in pieces (append_text); before prefill. Its utterance carries the first ids."""
+        check(lib.q3_session_open_text(self._h, int(b)))
+
+    def append_text(self, b: int, ids: Sequence[int], last: bool = False):
+        """Append token ids to open row b; last=True closes its text (tts_eos follows)."""
+        t = np.ascontiguousarray(list(ids), dtype=np.uint32)
+        check(lib.q3_session_append_text(self._h, int(b), t.ctypes.data_as(ctypes.c_void_p) if t.size else None, int(t.size),
+                                         1 if last else 0))
+
+    def text_state(self, b: int = 0) -> dict:
+        """n_text (tokens received), frames_committed, frames_runnable (what the text allows now), closed, frames_replayed
+        (frames the session replayed, all rows)."""
+        v = [ctypes.c_int() for _ in range(5)]
+        check(lib.q3_session_text_state(self._h, int(b), *[ctypes.byref(x) for x in v]))
+        return {"n_text": v[0].value, "frames_committed": v[1].value, "frames_runnable": v[2].value,
+                "closed": bool(v[3].value), "frames_replayed": v[4].value}
+
     def generate(self, n_frames: int, use_graph: bool = True):
         check(lib.q3_session_generate(self._h, int(n_frames), 1 if use_graph else 0))
 
@@ -467,6 +486,54 @@ class StreamingSession:
         if c is None:
             raise StopIteration
         return c
+
+
+class TextStreamingSession:
+    """StreamingSession whose text arrives in pieces (q3_session_open_text / q3_session_append_text): `push` token
+    ids as they come, `finish` once the text is complete; `next_chunk` returns the next AudioBuffer, or None while the text does
+    not reach a whole chunk yet. The concatenated chunks equal those of StreamingSession over the whole text."""
+
+    def __init__(self, model: "Qwen3TTS", utt: Utterance, options: SynthesisOptions, continuous: bool = False):
+        self._s = Session(model, [utt], options)
+        if continuous:
+            check(lib.q3_session_set_stream_mode(self._s._h, 1))
+        self._s.open_text(0)
+        self._done = False
+        self._finished = False
+        self._spf = model.config.samples_per_frame
+        self._chunk = options.chunk_frames if options.chunk_frames > 0 else 10
+
+    def push(self, ids: Sequence[int]):
+        self._s.append_text(0, ids, last=False)
+
+    def finish(self, ids: Sequence[int] = ()):
+        if not self._finished:
+            self._s.append_text(0, ids, last=True)
+            self._finished = True
+
+    def next_chunk(self) -> Optional[AudioBuffer]:
+        if self._done:
+            return None
+        buf = np.zeros(self._chunk * self._spf, dtype=np.float32)
+        n = ctypes.c_size_t(); d = ctypes.c_int()
+        check(lib.q3_session_next_chunk(self._s._h, buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(n), ctypes.byref(d)))
+        if d.value:
+            self._done = True
+        if n.value == 0:
+            return None
+        return AudioBuffer(buf[:n.value].copy())
+
+    def text_state(self) -> dict:
+        return self._s.text_state(0)
+
+    def frames_generated(self) -> int:
+        return self._s.frames(0)[0]
+
+    def is_done(self) -> bool:
+        return self._done
+
+    def close(self):
+        self._s.close()
 
 
 class ModelType(enum.Enum):    # config.rs:176-194
@@ -762,6 +829,14 @@ class Qwen3TTS:
                                           continuous: bool = False) -> StreamingSession:
         """synthesize_voice_design_streaming (lib.rs:1095-1128)."""
         return StreamingSession(self, Utterance(text_ids, language=language, instruct_ids=instruct_ids), options or SynthesisOptions(), continuous)
+
+    def synthesize_streaming_text(self, first_ids, speaker: Speaker, language: Language, options=None,
+                                  continuous: bool = False) -> "TextStreamingSession":
+        """Streaming TEXT input: speech starts from the first token ids while the rest of the text is still
+        being written (an LLM -> TTS pipeline). `push` more ids as they arrive, `finish` when the text is complete; the audio
+        equals synthesize_streaming over the whole text. Token ids, not text: re-tokenizing a growing string can change ids
+        already sent, and that is the caller's business."""
+        return TextStreamingSession(self, Utterance(list(first_ids), speaker, language), options or SynthesisOptions(), continuous)
 
     def synthesize_voice_clone_debug(self, text_ids, prompt, language: Language, options=None):
         """synthesize_voice_clone_debug (lib.rs:897-1046): (AudioBuffer, FrameCodes) for a VoiceClonePrompt."""

@@ -53,6 +53,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--xvector-npy", default=None, help="speaker embedding [hidden] f32 (.npy) for voice cloning")
     ap.add_argument("--ref-codes-bin", default=None, help="reference codec frames (codes_*.bin) for ICL voice cloning")
     ap.add_argument("--streaming", action="store_true", help="stream chunks (reports time to first audio)")
+    ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
+                    help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
+                         "first token to the first audio; writes the same WAV as without the flag)")
     ap.add_argument("--no-eos", action="store_true", help="disable EOS (fixed-length runs on synthetic weights)")
     return ap
 
@@ -132,6 +135,34 @@ def compare_with_reference(reference_dir: str, seed: int, num_frames: int, codes
 
 def max_frames_from_args(a) -> int:
     return int(a.duration * 12.5) if a.duration is not None else a.frames
+
+
+def feed_tokens(model, utt, opts, ids, n_feed):
+    """The text through the open-text path n_feed tokens at a time, frames generated between the pieces as far as
+    the text allows: (samples, codes, ms from the first token to the first chunk's audio). The codes are those of the whole-text
+    run, and the samples its whole-utterance decode."""
+    import dataclasses
+    t0 = time.time(); ttfa = None
+    chunk = opts.chunk_frames if opts.chunk_frames > 0 else 10
+    s = model.session([dataclasses.replace(utt, text_ids=list(ids[:n_feed]))], opts)
+    try:
+        s.open_text(0); s.prefill()
+        pos, closed = n_feed, False
+        while True:
+            if pos < len(ids):
+                s.append_text(0, ids[pos:pos + n_feed]); pos += n_feed
+            elif not closed:
+                s.append_text(0, [], last=True); closed = True
+            s.generate(opts.max_length)                 # as many frames as the text received so far allows
+            n, done = s.frames(0)
+            if ttfa is None and n > 0 and (n >= chunk or done):
+                s.decode(0, 0, min(n, chunk))
+                ttfa = (time.time() - t0) * 1000.0
+            if done:
+                break
+        return s.decode(0), s.codes(0), (ttfa if ttfa is not None else (time.time() - t0) * 1000.0)
+    finally:
+        s.close()
 
 
 def main(argv=None) -> int:
@@ -220,6 +251,10 @@ def main(argv=None) -> int:
         samples = np.concatenate(chunks) if chunks else np.zeros(0, np.float32)
         codes = ss._s.codes(0); ss._s.close()
         timing = None
+    elif a.feed_tokens > 0:
+        samples, codes, ttfa = feed_tokens(model, utt, opts, ids, a.feed_tokens)
+        timing = None
+        print(f"Fed {len(ids)} tokens {a.feed_tokens} at a time: first token to first audio {ttfa:.1f} ms")
     else:
         s = model.session([utt], opts)
         audio, timing = s.run()

@@ -48,6 +48,8 @@ q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limi
     HIPC(hipMemcpyAsync(s->trail_len + b, &hv[1], 4, hipMemcpyHostToDevice, s->stream));
     HIPC(hipMemcpyAsync(s->pad_row + b, &hv[2], 4, hipMemcpyHostToDevice, s->stream));
     HIPC(hipMemcpyAsync(s->limit + b, &hv[3], 4, hipMemcpyHostToDevice, s->stream));
+    static const int text_closed = 0x7fffffff;        // an opened row (q3_session_open_text) gets an ordinary closed request
+    if (s->text_ready) HIPC(hipMemcpyAsync(s->text_ready + b, &text_closed, 4, hipMemcpyHostToDevice, s->stream));
     const SampleRow srow = sample_row(sq.req.opts);
     HIPC(hipMemcpyAsync(s->sample_rows + b, &srow, sizeof srow, hipMemcpyHostToDevice, s->stream));
     HIPC(sync_frames(s));

@@ -361,6 +361,14 @@ struct SeqInfo {
     // `start_run` (0, or the session's frame count when the row was swapped in: q3_session_replace)
     int start_run = 0, limit = 0, stream_pos = 0;
     bool idle = false;      // frozen by session_idle_row: holds one page (the one its frozen position lies in), takes no more
+    int max_length_req = 0; // the request's own max_length (an ICL row's length cap is applied to it: `limit`)
+    // open text (q3_session_open_text): the row's text arrives in pieces (q3_session_append_text). Its trailing
+    // rows live in the row's replacement slot (trail_base), n_trail of them so far; `ready` = frames the text allows (INT_MAX
+    // once closed) = text_ready[b] on the device; `committed` = frames the row has committed (the device frame_idx, predicted
+    // by the host between two reads). An opened row's frames are counted from `committed`, never from frames_run - start_run.
+    bool opened = false, text_closed = true;
+    std::vector<uint32_t> text_all;       // every text token received so far (the request's own first)
+    int n_trail = 0, ready = 0x7fffffff, committed = 0;
 };
 
 struct ProfAcc { double ms = 0; double bytes = 0; long launches = 0; };
@@ -397,6 +405,10 @@ struct q3_session {
     uint32_t* ids_dev = nullptr; int *tr_dev = nullptr, *ci_dev = nullptr; float *proj_e = nullptr, *proj_h = nullptr;
     uint32_t* ref_codes_dev = nullptr;
     int *trail_base = nullptr, *trail_len = nullptr, *pad_row = nullptr;
+    // open text rows: text_ready[b] (SampleArgs::text_ready; nullptr until a row is opened — the frame's kernels then
+    // take their closed-text paths) and the scratch of the one projection path appended tokens take (8-row GEMV groups)
+    int* text_ready = nullptr;
+    uint32_t* app_ids = nullptr; float *app_e = nullptr, *app_h = nullptr, *app_out = nullptr;
     uint32_t* tok = nullptr; uint8_t* seen = nullptr; int *frame_idx = nullptr, *pos = nullptr, *token_count = nullptr;
     float* U = nullptr; uint32_t* codes = nullptr;
     float* logits_hist = nullptr; float* cp_logits_hist = nullptr; bool debug = false;
@@ -456,7 +468,8 @@ Q3_HIDDEN q3_status kv_reserve_frames(q3_session* s, int frames);
 Q3_HIDDEN void kv_release_row(q3_session* s, int b);
 Q3_HIDDEN LmDims talker_dims(const q3_config& c);
 Q3_HIDDEN LmDims cp_dims(const q3_config& c);
-Q3_HIDDEN q3_status talker_step(q3_session* s, const int* pos_dev, int pos_static, bool with_head, int rows_per_seq = 1);
+Q3_HIDDEN q3_status talker_step(q3_session* s, const int* pos_dev, int pos_static, bool with_head, int rows_per_seq = 1,
+                                const int* text_ready = nullptr);
 Q3_HIDDEN SampleRow sample_row(const q3_options& o);
 Q3_HIDDEN void request_shape(const q3_request& r, int* prefill_len, int* limit);
 Q3_HIDDEN long row_worst_units(int prefill_len, int limit, bool bf16);

@@ -121,6 +121,10 @@ hipError_t launch_fused_residual_rmsnorm_bf16(const uint16_t* x, const uint16_t*
 // y = rms_norm(x) * w   (rows = batch)
 hipError_t launch_rmsnorm(const float* x, int ldx, const float* w, float* y, int ldy, int rows, int cols, float eps,
                           hipStream_t st);
+// the same for the talker's final norm of a frame in a session with open text rows: row b is skipped (y keeps its old
+// contents) while it is HELD, frame_idx[b] >= text_ready[b] (see SampleArgs::text_ready)
+hipError_t launch_rmsnorm_hold(const float* x, int ldx, const float* w, float* y, int ldy, int rows, int cols, float eps,
+                               const int* frame_idx, const int* text_ready, hipStream_t st);
 
 // ---- attention decode ----
 struct AttnArgs {
@@ -256,6 +260,7 @@ struct FrameEmbedArgs {
     uint32_t* codes; const int* frame_idx; int max_frames;
     const float* text_rows; const int* trail_base; const int* trail_len; const int* pad_row;   // per-seq
     float* out; int H; int B; int n_acoustic;
+    const int* text_ready = nullptr;     // nullable: a HELD sequence (frame_idx >= text_ready, SampleArgs::text_ready) records no codes
 };
 hipError_t launch_frame_embed(const FrameEmbedArgs& a, hipStream_t st);
 
@@ -289,6 +294,10 @@ struct SampleArgs {
     int top_k; float top_p; int use_top_p;
     float rep_pen, rep_inv; int use_rep;
     int eos_id; int min_new_tokens; int codec_eos; int use_suppress;
+    // open text (q3_session_open_text; nullable, advance != 0 only): text_ready[b] = frames sequence b's text allows so far
+    // (INT_MAX once its text is closed). A sequence with frame_idx >= text_ready is HELD: it writes nothing — no token, no
+    // penalty mark, no counter — and runs the same frame again once its next text token has arrived
+    const int* text_ready;
 };
 hipError_t launch_sample(const SampleArgs& a, hipStream_t st);
 

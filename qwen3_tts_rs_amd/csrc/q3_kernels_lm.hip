@@ -288,6 +288,29 @@ hipError_t launch_rmsnorm(const float* x, int ldx, const float* w, float* y, int
     return hipGetLastError();
 }
 
+// k_rmsnorm for the talker's final norm (-> LASTH) of a frame of a session with open text rows: a HELD row (frame_idx >=
+// text_ready, SampleArgs::text_ready) keeps its old output row — the code predictor's conditioning when the row resumes.
+// The whole workgroup leaves together, before the barrier of the reduction.
+__global__ __launch_bounds__(256) void k_rmsnorm_hold(const float* x, int ldx, const float* w, float* y, int ldy, int cols,
+                                                      float eps, const int* frame_idx, const int* text_ready) {
+    __shared__ float red[4];
+    if (frame_idx[blockIdx.x] >= text_ready[blockIdx.x]) return;
+    const float* xr = x + (size_t)blockIdx.x * ldx;
+    float* yr = y + (size_t)blockIdx.x * ldy;
+    float ss = 0.0f;
+    for (int c = threadIdx.x; c < cols; c += 256) { const float v = xr[c]; ss += v * v; }
+    ss = block_sum_256(ss, red);
+    const float den = sqrtf(ss / (float)cols + eps);
+    for (int c = threadIdx.x; c < cols; c += 256) yr[c] = xr[c] / den * w[c];
+}
+
+hipError_t launch_rmsnorm_hold(const float* x, int ldx, const float* w, float* y, int ldy, int rows, int cols, float eps,
+                               const int* frame_idx, const int* text_ready, hipStream_t st) {
+    if (!frame_idx || !text_ready) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rmsnorm_hold, dim3(rows), dim3(256), 0, st, x, ldx, w, y, ldy, cols, eps, frame_idx, text_ready);
+    return hipGetLastError();
+}
+
 // The reference's only hand-written kernel, re-done for wave64: pass 1 s = x + r (stored, rounded to
 // T), Σ s² accumulated from the unrounded f32; wave shuffle + LDS cross-wave reduce; pass 2 re-reads
 // the rounded s. Output = (normed, sum). f32 math: s / sqrt(mean+eps) * w (CPU form, fused_ops.rs:59-67).
@@ -1305,6 +1328,7 @@ __global__ __launch_bounds__(256) void k_frame_embed(FrameEmbedArgs a) {
     const int f = a.frame_idx[b];
     const uint32_t tok = a.tok[b];
     const int tlen = a.trail_len[b], tbase = a.trail_base[b], prow = a.pad_row[b];
+    const int ready = a.text_ready ? a.text_ready[b] : 0x7fffffff;
     constexpr int LPT = 16;                                   // logits per thread kept in registers (vocab <= 4096)
     float lv[LPT];
     const float* lg = a.cp_logits_last + (size_t)b * a.cp_vocab;
@@ -1336,7 +1360,11 @@ __global__ __launch_bounds__(256) void k_frame_embed(FrameEmbedArgs a) {
     } else {
         last = block_argmax_first(lg, a.cp_vocab, red_v, red_i);
     }
-    if (tid == 0 && blockIdx.y == 0 && live) {
+    // A HELD sequence (open text, frame_idx >= text_ready: FrameEmbedArgs::text_ready) records nothing for frame f. The code
+    // predictor's gathers of this frame did write codes 1..14 into slot f, but from the LASTH and tok the held row keeps
+    // (k_rmsnorm_hold, k_sample) through row-independent kernels: the values it stored are the ones the resumed frame stores again.
+    // The next talker input below is built and thrown away like the rest of a held row's frame (K/V at pos, logits).
+    if (tid == 0 && blockIdx.y == 0 && live && f < ready) {
         frame[0] = tok;
         frame[a.n_acoustic] = (uint32_t)last;
     }
@@ -1402,10 +1430,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     // (round 5) what only the last lines of the kernel need — this step's uniform draw (two dependent loads), the counters it
     // advances — is requested NOW by the one thread that uses it: at the end of the kernel each of these was a memory round
     // trip of its own on the frame's critical path (the read-modify-write of pos / frame_idx included)
-    float u_pre = 0.0f; int fi_pre = 0, lim_pre = 0x7fffffff, pos_pre = 0;
+    float u_pre = 0.0f; int fi_pre = 0, lim_pre = 0x7fffffff, pos_pre = 0, ready_pre = 0x7fffffff;
     if (tid == 0) {
         if (a.u) u_pre = a.u[(size_t)b * a.u_stride + (a.draw_idx ? a.draw_idx[b] : 0)];      // (also in greedy mode: the row options that say so are still in flight)
-        if (a.advance) { fi_pre = a.frame_idx[b]; pos_pre = a.pos[b]; if (a.limit) lim_pre = a.limit[b]; }
+        if (a.advance) { fi_pre = a.frame_idx[b]; pos_pre = a.pos[b]; if (a.limit) lim_pre = a.limit[b]; if (a.text_ready) ready_pre = a.text_ready[b]; }
     }
     int n_sort = 2; while (n_sort < V) n_sort <<= 1;
 
@@ -1628,7 +1656,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
         __syncthreads();
         pick = s_pick;
     }
-    if (tid == 0) {
+    // A HELD sequence (SampleArgs::text_ready) writes nothing: it must resume with the token, penalty mask and counters it had.
+    // (The check comes before the limit freeze below, which still writes tok / seen: harmless for a row that has ended.)
+    const bool held = a.text_ready && a.advance && fi_pre >= ready_pre;
+    if (tid == 0 && !held) {
         a.tok[b] = (uint32_t)pick;
         if (seen && pick < V) seen[pick] = 1;
         const bool frozen = a.advance && a.limit && fi_pre >= lim_pre;      // SampleArgs::limit

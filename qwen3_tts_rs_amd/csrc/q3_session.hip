@@ -71,7 +71,7 @@ q3_status kv_reserve_frames(q3_session* s, int frames) {
     for (int b = 0; b < s->B; ++b) {
         const SeqInfo& q = s->seq[(size_t)b];
         if (q.idle) continue;
-        int upto = s->frames_run - q.start_run + frames;
+        int upto = (q.opened ? q.committed : s->frames_run - q.start_run) + frames;      // (a held row rewrites its current position)
         if (upto > q.limit) upto = q.limit;
         if (upto < 0) upto = 0;
         Q3C(kv_reserve_row(s, b, q.prefill_len + upto + 1));
@@ -233,7 +233,7 @@ LmDims cp_dims(const q3_config& c) { return LmDims{c.cp_hidden, c.cp_inter, c.cp
 
 // talker layers on the contents of tb.X at position pos (device array or static); with_head: final
 // norm → LASTH and codec_head → LOGITS (talker.rs:716-736)
-q3_status talker_step(q3_session* s, const int* pos_dev, int pos_static, bool with_head, int rows_per_seq) {
+q3_status talker_step(q3_session* s, const int* pos_dev, int pos_static, bool with_head, int rows_per_seq, const int* text_ready) {
     const q3_model* m = s->m; const q3_config& c = m->cfg;
     const LmDims d = talker_dims(c);
     for (int i = 0; i < c.n_layers; ++i)
@@ -241,7 +241,11 @@ q3_status talker_step(q3_session* s, const int* pos_dev, int pos_static, bool wi
                      s->paged ? nullptr : s->vcache + (size_t)i * s->kv_layer_stride,
                      s->max_seq, pos_dev, pos_static, s->n_splits, rows_per_seq, false, nullptr, s->paged ? i : -1));
     if (with_head) {
-        // final norm of each sequence's LAST row of the step
+        // final norm of each sequence's LAST row of the step (a frame with open text rows: held rows keep their LASTH)
+        if (text_ready)
+            HIPC(launch_rmsnorm_hold(s->tb.X + (size_t)(rows_per_seq - 1) * c.hidden, rows_per_seq * c.hidden, m->norm, s->LASTH, c.hidden, s->B,
+                                     c.hidden, c.rms_eps, s->frame_idx, text_ready, s->stream));
+        else
         HIPC(launch_rmsnorm(s->tb.X + (size_t)(rows_per_seq - 1) * c.hidden, rows_per_seq * c.hidden, m->norm, s->LASTH, c.hidden, s->B,
                             c.hidden, c.rms_eps, s->stream));
         LinArgs h;
@@ -391,14 +395,15 @@ static q3_status frame_launch(q3_session* s) {
     f.codes = s->codes; f.frame_idx = s->frame_idx; f.max_frames = s->max_frames;
     f.text_rows = s->rows; f.trail_base = s->trail_base; f.trail_len = s->trail_len; f.pad_row = s->pad_row;
     f.out = s->tb.X; f.H = c.hidden; f.B = s->B; f.n_acoustic = c.n_groups - 1;
+    f.text_ready = s->text_ready;            // null unless a row was opened
     HIPC(launch_frame_embed(f, s->stream));
     if (s->debug && s->cp_logits_hist) {
         // capture is host-indexed: only valid outside graph replay (debug sessions never use graphs)
         HIPC(hipMemcpyAsync(s->cp_logits_hist + (size_t)s->frames_run * 15 * s->B * c.cp_vocab, s->CP_LOGITS,
                             (size_t)15 * s->B * c.cp_vocab * 4, hipMemcpyDeviceToDevice, s->stream));
     }
-    Q3C(talker_step(s, s->pos, 0, true));
-    SampleArgs a; fill_sample_args(s, a); a.advance = 1;
+    Q3C(talker_step(s, s->pos, 0, true, 1, s->text_ready));
+    SampleArgs a; fill_sample_args(s, a); a.advance = 1; a.text_ready = s->text_ready;
     HIPC(launch_sample(a, s->stream));
     return Q3_OK;
 }
@@ -497,7 +502,7 @@ q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int fra
             return set_err(Q3_INVALID_ARG, "bad token id arrays");
         if (r.mode == Q3_MODE_VOICE_CLONE && !r.xvector) return set_err(Q3_INVALID_ARG, "voice clone needs an x-vector");
         SeqInfo& q = s->seq[b];
-        q.req = r;
+        q.req = r; q.max_length_req = r.opts.max_length;
         q.text.assign(r.text_ids, r.text_ids + r.n_text);
         for (uint32_t id : q.text) if (id >= (uint32_t)c.text_vocab) return set_err(Q3_INVALID_ARG, "text id %u out of range", id);
         if (r.mode == Q3_MODE_VOICE_DESIGN) q.instruct.assign(r.instruct_ids, r.instruct_ids + r.n_instruct);
@@ -710,6 +715,7 @@ extern "C" q3_status q3_session_set_kv_dtype(q3_session* s, int dtype) {
 extern "C" q3_status q3_session_set_debug(q3_session* s, int capture) {
     if (!s) return set_err(Q3_INVALID_ARG, "null session");
     if (s->prefilled) return set_err(Q3_INVALID_ARG, "set_debug must be called before prefill");
+    if (capture && s->text_ready) return set_err(Q3_UNSUPPORTED, "set_debug: the session has open text rows");
     s->debug = capture != 0;
     if (s->debug && !s->logits_hist) {
         const q3_config& c = s->m->cfg;
@@ -721,6 +727,7 @@ extern "C" q3_status q3_session_set_debug(q3_session* s, int capture) {
 }
 extern "C" q3_status q3_session_set_profile(q3_session* s, int enable) {
     if (!s) return set_err(Q3_INVALID_ARG, "null session");
+    if (enable && s->text_ready) return set_err(Q3_UNSUPPORTED, "set_profile: the session has open text rows");
     s->profile = enable != 0;
     return Q3_OK;
 }
@@ -773,6 +780,165 @@ static q3_status text_project(q3_session* s, const uint32_t* ids_dev, int n, flo
     }
     if (er != hipSuccess) st = set_err(Q3_HIP_ERROR, "text projection: %s", hipGetErrorString(er));
     return st;
+}
+
+// ---- open text rows (q3_session_open_text / q3_session_append_text) ----
+// An opened row's trailing text rows live in its replacement slot (rows repl_base + b * row_cap ..), contiguous as k_frame_embed
+// indexes them; frame f of the row may commit only once trailing row f is there (text_ready[b] > f), else the row is HELD.
+static int slot_row0(const q3_session* s, int b) { return s->repl_base + b * s->row_cap; }
+// trailing text ids of an opened row so far: its text minus what the prefill consumes (text[0]; ICL: the first n_ref + 1 of
+// [ref_text, text], talker.rs:656-708), without tts_eos
+static void open_trailing_ids(const SeqInfo& q, std::vector<uint32_t>& out) {
+    out.clear();
+    if (q.icl) {
+        const size_t n_icl = q.ref_codes.size() / 16 + 1;
+        std::vector<uint32_t> all(q.ref_text);
+        all.insert(all.end(), q.text_all.begin(), q.text_all.end());
+        if (all.size() > n_icl) out.assign(all.begin() + (ptrdiff_t)n_icl, all.end());
+    } else if (q.text_all.size() > 1) {
+        out.assign(q.text_all.begin() + 1, q.text_all.end());
+    }
+}
+// host view of an opened row's text: trailing rows present, what the frame reads (+ tts_eos once closed), frames allowed
+static void open_counts(SeqInfo& q) {
+    std::vector<uint32_t> t; open_trailing_ids(q, t);
+    q.n_trail = (int)t.size();
+    q.trailing_len = q.n_trail + (q.text_closed ? 1 : 0);
+    q.ready = q.text_closed ? 0x7fffffff : q.n_trail;
+    if (q.icl && q.text_closed) {       // the ICL length cap (lib.rs:913-929) over the whole text, resolved at close
+        int cap = 6 * (int)q.text_all.size(); if (cap < 75) cap = 75;
+        q.limit = q.max_length_req < cap ? q.max_length_req : cap;
+    }
+}
+// Appended text rows take ONE projection path whatever a call carries: 8-row GEMV groups, the unused rows of the last group
+// padded in scratch. (text_project picks two GEMMs from 48 rows on, and at 1.7B the two sum in different orders: a token's bits
+// would depend on what it was projected with.) Rows [dst, dst + n) of row b's slot; queued on the session stream.
+static q3_status project_appended(q3_session* s, int b, const std::vector<uint32_t>& ids, int dst) {
+    const q3_model* m = s->m; const q3_config& c = m->cfg;
+    const int TD = c.text_dim, H = c.hidden, n = (int)ids.size(), row0 = slot_row0(s, b);
+    if (n <= 0) return Q3_OK;
+    std::vector<uint32_t> padded((size_t)(n + 7) / 8 * 8);       // lives until the synchronisation below
+    for (size_t i = 0; i < padded.size(); ++i) padded[i] = ids[i < (size_t)n ? i : (size_t)n - 1];
+    hipError_t er = hipSuccess;
+    for (int r0 = 0; r0 < n && er == hipSuccess; r0 += 8) {
+        const int k = (n - r0) < 8 ? (n - r0) : 8;
+        er = hipMemcpyAsync(s->app_ids, padded.data() + r0, 8 * 4, hipMemcpyHostToDevice, s->stream);
+        if (er == hipSuccess) er = launch_gather_rows_bf16(m->text_emb, s->app_ids, s->app_e, 8, TD, s->stream);
+        if (er != hipSuccess) break;
+        LinArgs a;
+        a.N = TD; a.K = TD; set_w(a, m->fc1w, 8, TD, TD); a.x = s->app_e; a.ldx = TD; a.bias = m->fc1b; a.y = s->app_h; a.ldy = TD; a.M = 8; a.epi = EPI_SILU;
+        er = launch_linear(a, s->stream);
+        if (er != hipSuccess) break;
+        LinArgs b2;
+        b2.N = H; b2.K = TD; set_w(b2, m->fc2w, 8, H, TD); b2.x = s->app_h; b2.ldx = TD; b2.bias = m->fc2b; b2.y = s->app_out; b2.ldy = H; b2.M = 8; b2.epi = EPI_NONE;
+        er = launch_linear(b2, s->stream);
+        if (er == hipSuccess)
+            er = hipMemcpyAsync(s->rows + (size_t)(row0 + dst + r0) * H, s->app_out, (size_t)k * H * 4, hipMemcpyDeviceToDevice, s->stream);
+    }
+    const hipError_t es = sync_frames(s);
+    if (er == hipSuccess) er = es;
+    if (er != hipSuccess) return set_err(Q3_HIP_ERROR, "appended text projection: %s", hipGetErrorString(er));
+    return Q3_OK;
+}
+// what the frame reads of an opened row — trail_len, text_ready, limit — published on the session stream, landed on return
+static q3_status publish_text(q3_session* s, int b) {
+    const SeqInfo& q = s->seq[(size_t)b];
+    const int v[3] = {q.trailing_len, q.ready, q.limit};
+    HIPC(hipMemcpyAsync(s->trail_len + b, &v[0], 4, hipMemcpyHostToDevice, s->stream));
+    HIPC(hipMemcpyAsync(s->text_ready + b, &v[1], 4, hipMemcpyHostToDevice, s->stream));
+    HIPC(hipMemcpyAsync(s->limit + b, &v[2], 4, hipMemcpyHostToDevice, s->stream));
+    HIPC(sync_frames(s));
+    return Q3_OK;
+}
+static bool any_open_text(const q3_session* s) { for (const auto& q : s->seq) if (q.opened && !q.text_closed) return true; return false; }
+
+extern "C" q3_status q3_session_open_text(q3_session* s, int b) {
+    if (!s) return set_err(Q3_INVALID_ARG, "null session");
+    if (b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_open_text: bad sequence index %d", b);
+    if (s->prefilled) return set_err(Q3_INVALID_ARG, "q3_session_open_text: rows are opened before q3_session_prefill");
+    if (!s->ragged.empty()) return set_err(Q3_UNSUPPORTED, "q3_session_open_text: not in a ragged first batch (rows of different prefill lengths)");
+    if (s->debug || s->profile) return set_err(Q3_UNSUPPORTED, "q3_session_open_text: not on debug / profiling sessions");
+    SeqInfo& q = s->seq[(size_t)b];
+    if (q.opened) return Q3_OK;
+    if (q.text.empty()) return set_err(Q3_INVALID_ARG, "q3_session_open_text: row %d has no text token (an open row needs one at creation: the prefill consumes it)", b);
+    if (q.icl) {
+        const int n_ref = (int)(q.ref_codes.size() / 16), need = n_ref + 1 - (int)q.ref_text.size();
+        if ((int)q.text.size() < need)
+            return set_err(Q3_INVALID_ARG, "q3_session_open_text: ICL row %d needs at least %d target text tokens at creation (%d given), so that tts_eos falls after the ICL block", b, need, (int)q.text.size());
+        if (q.max_length_req > s->max_frames)
+            return set_err(Q3_UNSUPPORTED, "q3_session_open_text: ICL row %d asks for max_length %d beyond the session's frame budget %d (its length cap is resolved when the text closes; q3_session_create_reserved)", b, q.max_length_req, s->max_frames);
+    }
+    HIPC(hipSetDevice(s->m->device));
+    if (!s->text_ready) {
+        const q3_config& c = s->m->cfg;
+        HIPC(s->pool.alloc(&s->text_ready, (size_t)s->B));
+        HIPC(s->pool.alloc(&s->app_ids, 8)); HIPC(s->pool.alloc(&s->app_e, (size_t)8 * c.text_dim));
+        HIPC(s->pool.alloc(&s->app_h, (size_t)8 * c.text_dim)); HIPC(s->pool.alloc(&s->app_out, (size_t)8 * c.hidden));
+        const std::vector<int> closed((size_t)s->B, 0x7fffffff);
+        HIPC(q3_hipMemcpy(s->text_ready, closed.data(), (size_t)s->B * 4, hipMemcpyHostToDevice));
+    }
+    q.opened = true; q.text_closed = false; q.text_all = q.text; q.committed = 0;
+    if (q.icl) q.limit = q.max_length_req;          // until the text closes (open_counts)
+    open_counts(q);
+    if (q.n_trail + 1 > s->row_cap) { q.opened = false; q.text_closed = true; return set_err(Q3_UNSUPPORTED, "q3_session_open_text: %d trailing text rows exceed the row's slot (%d)", q.n_trail + 1, s->row_cap); }
+    HIPC(q3_hipMemcpy(s->limit + b, &q.limit, 4, hipMemcpyHostToDevice));
+    return Q3_OK;
+}
+
+static q3_status refresh_codes(q3_session* s);
+extern "C" q3_status q3_session_append_text(q3_session* s, int b, const uint32_t* ids, int n, int last) {
+    if (!s) return set_err(Q3_INVALID_ARG, "null session");
+    if (b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_append_text: bad sequence index %d", b);
+    if (n < 0 || (n > 0 && !ids)) return set_err(Q3_INVALID_ARG, "q3_session_append_text: bad token id array");
+    SeqInfo& q = s->seq[(size_t)b];
+    if (!q.opened) return set_err(Q3_INVALID_ARG, "q3_session_append_text: row %d is not open (q3_session_open_text, before the prefill)", b);
+    if (q.text_closed) return set_err(Q3_INVALID_ARG, "q3_session_append_text: row %d's text is already closed", b);
+    const q3_config& c = s->m->cfg;
+    for (int i = 0; i < n; ++i) if (ids[i] >= (uint32_t)c.text_vocab) return set_err(Q3_INVALID_ARG, "text id %u out of range", ids[i]);
+    if (q.n_trail + n + 1 > s->row_cap) return set_err(Q3_UNSUPPORTED, "q3_session_append_text: %d trailing text rows exceed the row's slot (%d)", q.n_trail + n + 1, s->row_cap);
+    if (!s->prefilled) {                 // the prefill projects whatever has arrived by then
+        q.text_all.insert(q.text_all.end(), ids, ids + n);
+        if (last) q.text_closed = true;
+        open_counts(q);
+        return Q3_OK;
+    }
+    HIPC(hipSetDevice(s->m->device));
+    HIPC(sync_frames(s));                // no frame in flight while the row's text changes (q3_session_replace does the same)
+    Q3C(refresh_codes(s));
+    if (q.done) { q.text_all.insert(q.text_all.end(), ids, ids + n); if (last) q.text_closed = true; return Q3_OK; }   // ended (EOS / max_length): accepted, ignored
+    std::vector<uint32_t> rows(ids, ids + n);
+    if (last) rows.push_back(TTS_EOS);
+    const int dst = q.n_trail;
+    Q3C(project_appended(s, b, rows, dst));      // rows beyond trail_len: no frame reads them before publish_text
+    q.text_all.insert(q.text_all.end(), ids, ids + n);
+    if (last) q.text_closed = true;
+    open_counts(q);
+    Q3C(publish_text(s, b));
+    s->codes_host_valid = false;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_session_text_state(q3_session* s, int b, int* n_text, int* frames_committed, int* frames_runnable, int* closed,
+                                           int* frames_replayed) {
+    if (!s) return set_err(Q3_INVALID_ARG, "null session");
+    if (b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_text_state: bad sequence index %d", b);
+    const SeqInfo& q = s->seq[(size_t)b];
+    int committed = 0, runnable = 0;
+    if (s->prefilled) {
+        HIPC(hipSetDevice(s->m->device));
+        Q3C(refresh_codes(s));
+        committed = q.opened ? q.committed : std::min(std::max(s->frames_run - q.start_run, 0), q.limit);
+        runnable = q.done ? 0 : (q.opened ? std::min(q.ready, q.limit) : q.limit) - committed;
+        if (runnable < 0) runnable = 0;
+    } else {
+        runnable = q.opened ? std::min(q.ready, q.limit) : q.limit;
+    }
+    if (n_text) *n_text = (int)(q.opened ? q.text_all.size() : q.text.size());
+    if (frames_committed) *frames_committed = committed;
+    if (frames_runnable) *frames_runnable = runnable;
+    if (closed) *closed = q.text_closed ? 1 : 0;
+    if (frames_replayed) *frames_replayed = s->frames_run;
+    return Q3_OK;
 }
 
 // run_prefill_layers (talker.rs:823-841) for long prompts: chunks of up to 128 positions per sequence go through every
@@ -946,6 +1112,7 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
         q.pad_row = r_pad;
         if (q.icl) q.trail_base = n_text_all > n_icl ? r_text + n_icl : r_pad;       // talker.rs:692-708
         else q.trail_base = n_text > 1 ? r_text + 1 : r_eos;          // build_trailing_text (lib.rs:508-519)
+        if (q.opened) { q.trail_base = slot_row0(s, b); open_counts(q); }      // open text: trailing rows in the row's slot (below)
         trail_base[b] = q.trail_base; trail_len[b] = q.trailing_len; pad_row[b] = q.pad_row;
         // prefill positions (talker.rs:451-491 / 511-564 / 585-627)
         int* tr = &text_row[(size_t)b * S]; int* ci = &codec_id[(size_t)b * S];
@@ -998,6 +1165,24 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
                                      s->ref_codes_dev ? s->ref_codes_dev + ref_off[b] : nullptr, m->cp_embs_dev);
         if (e != hipSuccess) st = set_err(Q3_HIP_ERROR, "prefill assembly: %s", hipGetErrorString(e));
     }
+    std::vector<int> ready_v, limit_v;
+    if (st == Q3_OK && s->text_ready) {
+        // open rows: the trailing rows received so far (+ tts_eos if the text closed before the prefill) go through the appended
+        // rows' projection path, whatever arrived when; text_ready / limit of every row published with the rest
+        for (int b = 0; b < B && st == Q3_OK; ++b) {
+            const SeqInfo& q = s->seq[b];
+            if (!q.opened) continue;
+            std::vector<uint32_t> t; open_trailing_ids(q, t);
+            if (q.text_closed) t.push_back(TTS_EOS);
+            st = project_appended(s, b, t, 0);
+        }
+        for (int b = 0; b < B; ++b) { ready_v.push_back(s->seq[b].ready); limit_v.push_back(s->seq[b].limit); }
+        if (st == Q3_OK) {
+            hipError_t e = hipMemcpyAsync(s->text_ready, ready_v.data(), B * 4, hipMemcpyHostToDevice, s->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(s->limit, limit_v.data(), B * 4, hipMemcpyHostToDevice, s->stream);
+            if (e != hipSuccess) st = set_err(Q3_HIP_ERROR, "prefill: open text state: %s", hipGetErrorString(e));
+        }
+    }
     if (st != Q3_OK) { (void)sync_frames(s); return st; }
     // 2. run_prefill_layers (talker.rs:823-841): causal attention ⇒ token-by-token decode steps
     //    and the GEMV kernels take up to 16 rows for the price of one, so each weight pass carries a CHUNK of
@@ -1049,8 +1234,14 @@ static q3_status refresh_codes(q3_session* s) {
     if (s->codes_host_valid) return Q3_OK;
     HIPC(sync_frames(s));
     s->codes_host.resize((size_t)s->B * s->max_frames * 16);
+    if (s->text_ready) {          // opened rows (a held row ran frames it did not commit): their count is the device frame_idx
+        std::vector<int> fi((size_t)s->B);
+        HIPC(q3_hipMemcpy(fi.data(), s->frame_idx, s->B * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < s->B; ++b) if (s->seq[b].opened) s->seq[b].committed = fi[(size_t)b];
+    }
+    auto ran_of = [s](const SeqInfo& q) { return q.opened ? q.committed : s->frames_run - q.start_run; };
     for (int b = 0; b < s->B; ++b) {
-        int ran = s->frames_run - s->seq[b].start_run;
+        int ran = ran_of(s->seq[b]);
         if (ran > s->seq[b].limit) ran = s->seq[b].limit;
         if (ran > 0)
             HIPC(q3_hipMemcpy(&s->codes_host[(size_t)b * s->max_frames * 16], s->codes + (size_t)b * s->max_frames * 16,
@@ -1060,7 +1251,7 @@ static q3_status refresh_codes(q3_session* s) {
     HIPC(q3_hipMemcpy(tok.data(), s->tok, s->B * 4, hipMemcpyDeviceToHost));
     for (int b = 0; b < s->B; ++b) {
         SeqInfo& q = s->seq[b];
-        int n = s->frames_run - q.start_run; bool done = false;      // frames this row has run (rows swapped in later started later)
+        int n = ran_of(q); bool done = false;      // frames this row has run (rows swapped in later started later)
         if (n > q.limit) n = q.limit;
         if (n < 0) n = 0;
         const int eos = q.req.opts.eos_token_id;                     // per row (SampleRow)
@@ -1079,10 +1270,21 @@ static q3_status refresh_codes(q3_session* s) {
 
 static bool all_done(q3_session* s) { for (auto& q : s->seq) if (!q.done) return false; return true; }
 // frames the session still has to run for its longest-remaining row (lockstep sessions: max_frames - frames_run)
+// An opened row can commit frames up to what its text allows; a held or finished one none.
+static int row_capacity(const q3_session* s, const SeqInfo& q) {
+    if (!q.opened) return q.limit - (s->frames_run - q.start_run);
+    if (q.done) return 0;
+    return std::min(q.ready, q.limit) - q.committed;
+}
 static int session_remaining(const q3_session* s) {
     int r = 0;
-    for (const auto& q : s->seq) { const int left = q.limit - (s->frames_run - q.start_run); if (left > r) r = left; }
+    for (const auto& q : s->seq) { const int left = row_capacity(s, q); if (left > r) r = left; }
     return r;
+}
+// n more frames were handed to the device: what each opened row commits of them (k_sample holds it at text_ready, freezes it at limit)
+static void open_rows_ran(q3_session* s, int n) {
+    for (auto& q : s->seq)
+        if (q.opened) { const int stop = std::max(q.committed, std::min(q.ready, q.limit)); q.committed = std::min(q.committed + n, stop); }
 }
 
 // Which kernels of the frame keep to the activation-transport rule of q3_kernels.h (write-through + drained stores, L1-bypassing
@@ -1185,12 +1387,12 @@ static q3_status frames_enqueue(q3_session* s, int n) {
     if (s->aql) {
         std::string why; int handed = 0;
         const bool ok = q3::aql_submit(s->aql, n, &why, &handed);
-        s->frames_run += handed;
+        s->frames_run += handed; open_rows_ran(s, handed);
         if (!ok) { s->aql_failed = true; s->codes_host_valid = false; return set_err(Q3_HIP_ERROR, "AQL frame submission: %s", why.c_str()); }
     } else {
         if (!s->graph_exec) return set_err(Q3_INVALID_ARG, "frames_enqueue: no captured frame");
         for (int i = 0; i < n; ++i) HIPC(hipGraphLaunch(s->graph_exec, s->stream));
-        s->frames_run += n;
+        s->frames_run += n; open_rows_ran(s, n);
     }
     s->codes_host_valid = false;
     return Q3_OK;
@@ -1203,6 +1405,9 @@ extern "C" q3_status q3_session_generate(q3_session* s, int n_frames, int use_gr
     HIPC(hipSetDevice(s->m->device));
     if (s->debug || s->profile) use_graph = 0;
     int todo = n_frames;
+    // open rows: no frame is replayed in which no row can commit — a burst is the most frames any row's text (or limit) allows,
+    // nothing when every live row is held or done
+    if (s->text_ready) Q3C(refresh_codes(s));
     { const int left = session_remaining(s); if (todo > left) todo = left; }
     if (todo <= 0) return Q3_OK;
     Q3C(kv_reserve_frames(s, todo));        // paged KV: every page these frames can reach, before the first of them is queued
@@ -1224,11 +1429,12 @@ extern "C" q3_status q3_session_generate(q3_session* s, int n_frames, int use_gr
         for (int i = 0; i < burst; ++i) {
             if (use_graph) HIPC(hipGraphLaunch(s->graph_exec, s->stream));
             else Q3C(frame_launch(s));
-            s->frames_run += 1;
+            s->frames_run += 1; open_rows_ran(s, 1);
         }
         todo -= burst;
         s->codes_host_valid = false;
         if (eos_on) { Q3C(refresh_codes(s)); if (all_done(s)) break; }
+        if (s->text_ready) { const int left = session_remaining(s); if (todo > left) todo = left; }
     }
     HIPC(sync_frames(s));
     if (s->profile && !s->prof_events.empty()) {
@@ -1253,12 +1459,15 @@ extern "C" q3_status q3_session_next_chunk_row(q3_session* s, int b, float* pcm_
     Q3C(refresh_codes(s));
     SeqInfo& q = s->seq[b];
     const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
-    while (!q.done && q.n_frames - q.stream_pos < chunk && session_remaining(s) > 0) {
+    // (an opened row waits for its own text: it stops generating when it is held)
+    while (!q.done && q.n_frames - q.stream_pos < chunk && (q.opened ? row_capacity(s, q) : session_remaining(s)) > 0) {
         Q3C(q3_session_generate(s, chunk - (q.n_frames - q.stream_pos), 1));
         Q3C(refresh_codes(s));
     }
     int avail = q.n_frames - q.stream_pos;
     if (avail > chunk) avail = chunk;
+    // an opened row whose text does not reach a whole chunk yet: nothing now (chunk boundaries stay those of the closed run)
+    if (q.opened && !q.done && avail < chunk) { if (n_samples) *n_samples = 0; if (done) *done = 0; return Q3_OK; }
     if (avail <= 0) { if (n_samples) *n_samples = 0; if (done) *done = 1; return Q3_OK; }
     const int spf = samples_per_frame(s->m->cfg);
     if (s->stream_mode == 1 && !q.icl) {
@@ -1357,6 +1566,7 @@ extern "C" q3_status q3_session_decode(q3_session* s, int b, int f0, int f1, flo
 // splitting the chip between the two (Q3_DECODE_CUS below) costs the frames more than the vocoder takes.
 extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_host, const size_t* cap, size_t* n_samples, q3_timing* timing) {
     if (!s) return set_err(Q3_INVALID_ARG, "null session");
+    if (any_open_text(s)) return set_err(Q3_UNSUPPORTED, "q3_session_run: a row's text is still open (q3_session_append_text with last != 0 closes it; or drive the session with q3_session_generate)");
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const auto t0 = clk::now();
@@ -1559,6 +1769,9 @@ extern "C" q3_status q3_session_next_chunk(q3_session* s, float* pcm_host, size_
     }
     int avail = q.n_frames - s->stream_pos;
     if (avail > chunk) avail = chunk;
+    // open text that does not reach a whole chunk yet: nothing now (the loop above stopped at the held frame; chunk boundaries
+    // stay those of the closed run). Read-ahead below never goes past what the text allows (session_remaining).
+    if (q.opened && !q.done && avail < chunk) { if (n_samples) *n_samples = 0; if (done) *done = 0; return Q3_OK; }
     if (avail <= 0) { if (n_samples) *n_samples = 0; if (done) *done = 1; return Q3_OK; }
     const bool chunk_done = q.done && s->stream_pos + avail >= q.n_frames;
     // Read-ahead: the frames of the NEXT chunk are enqueued (graph replays, no host wait) while this chunk is vocoded

@@ -54,6 +54,9 @@ pub mod ffi {
         pub fn q3_session_next_chunk_row(s: *mut c_void, b: i32, pcm: *mut f32, cap: usize, n: *mut usize, done: *mut i32) -> i32;
         pub fn q3_session_create_reserved(m: *mut c_void, reqs: *const Q3Request, batch: i32, frame_budget: i32, prompt_budget: i32, out: *mut *mut c_void) -> i32;
         pub fn q3_session_replace(s: *mut c_void, b: i32, req: *const Q3Request) -> i32;
+        pub fn q3_session_open_text(s: *mut c_void, b: i32) -> i32;
+        pub fn q3_session_append_text(s: *mut c_void, b: i32, ids: *const u32, n: i32, last: i32) -> i32;
+        pub fn q3_session_text_state(s: *mut c_void, b: i32, n_text: *mut i32, frames_committed: *mut i32, frames_runnable: *mut i32, closed: *mut i32, frames_replayed: *mut i32) -> i32;
         pub fn q3_batcher_create(m: *mut c_void, slots: i32, frame_budget: i32, prompt_budget: i32, out: *mut *mut c_void) -> i32;
         pub fn q3_batcher_free(b: *mut c_void);
         pub fn q3_batcher_submit(b: *mut c_void, req: *const Q3Request, want_pcm: i32, ticket: *mut i64) -> i32;
