@@ -349,6 +349,37 @@ q3_status q3_fused_residual_rmsnorm(int device, int dtype, const void* x_host, c
  * (candle Linear, transformer.rs:224-227): x [M][K] f32, w [N][K] bf16 */
 q3_status q3_linear(int device, const float* x_host, const uint16_t* w_bf16_host, const float* bias_host,
                     int M, int N, int K, float* y_host);
+/* Test API: ONE launch of the GEMV family with every argument of the engine's dispatcher spelled out. All arrays are host
+ * arrays. x [M][ldx] (ldx >= K, ldx % 4 == 0); w / w2 row-major bf16 [N][K] (w2: the SwiGLU "up" matrix, else NULL);
+ * bias [N], norm_w [K] (fused input RMSNorm with eps) and resid [M][ldr] may be NULL; epi 0 none / 1 + resid / 2 SiLU /
+ * 3 SwiGLU; tiled -1 = the engine's choice, 1 = 16-row tiles, 2 = 4-row tiles, 0 = row-major first-generation kernel;
+ * ksplit 1, or 2 = the K range over two workgroups (the entry zeroes the M x N result first); use_ws != 0 and M > 16: the
+ * wide-session GEMM's workspace is passed. y [M_alloc][ldy] (M_alloc >= M, ldy >= N) is uploaded whole before the launch and
+ * copied back whole after it, so the caller sees what lies around the result. zero_n > 0 (% 4 == 0): zero_buf
+ * [zero_n + zero_guard] is uploaded, its first zero_n floats are the launch's clearing side job, and it is copied back.
+ * A launch the dispatcher refuses returns Q3_UNSUPPORTED (never another kernel) and leaves y / zero_buf as they were. */
+typedef struct q3_linear_ex_args {
+    int M, N, K, ldx, ldy, ldr, M_alloc;
+    int epi, tiled, ksplit, use_ws, zero_n, zero_guard;
+    float eps;
+    const float* x; const uint16_t* w; const uint16_t* w2;
+    const float* bias; const float* norm_w; const float* resid;
+    float* y; float* zero_buf;
+} q3_linear_ex_args;
+q3_status q3_linear_ex(int device, const q3_linear_ex_args* args);
+/* Test API: one decode-attention step (per-head q/k RMSNorm, rotate-half RoPE at pos, K/V append, GQA attention) over a
+ * contiguous cache. variant 0 = the one-launch kernel (+ the split merge when n_splits > 1), 1 = the three-launch path,
+ * 2 = the code predictor's kernel (every pos equal, < 16; n_splits 1; Q3_UNSUPPORTED otherwise). pos [B]; qkv
+ * [B][(nh + 2 nkv) * 128]; q_norm_w / k_norm_w [128]; rope_cos / rope_sin [max_seq][64]; kcache / vcache
+ * [B][nkv][max_seq][128] in and out; out [B][nh * 128]. nh / nkv is 1, 2 or 4; n_splits <= 64. */
+typedef struct q3_attn_step_args {
+    int variant, B, nh, nkv, n_splits, max_seq;
+    float eps; int reserved;
+    const int* pos; const float* qkv; const float* q_norm_w; const float* k_norm_w;
+    const float* rope_cos; const float* rope_sin;
+    float* kcache; float* vcache; float* out;
+} q3_attn_step_args;
+q3_status q3_attn_step(int device, const q3_attn_step_args* args);
 /* Qwen3TTS::decode_codes (lib.rs:881-890) / Decoder12Hz::decode (decoder_12hz.rs:411-505):
  * frames [n][16] u32 → n*1920 f32 samples. taps (optional, [Q3_DEC_N] host pointers or NULL)
  * receive stage outputs for the stage-by-stage validation the reference does in

@@ -52,6 +52,18 @@ class CMimiConfig(ctypes.Structure):     # q3_mimi_config (mimi::Config::v0_1(So
                 ("norm_eps", ctypes.c_float), ("rope_theta", ctypes.c_float)]
 
 
+class CLinearEx(ctypes.Structure):       # q3_linear_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("M", "N", "K", "ldx", "ldy", "ldr", "M_alloc", "epi", "tiled", "ksplit", "use_ws",
+                                              "zero_n", "zero_guard")] + [("eps", ctypes.c_float)] + \
+               [(n, ctypes.c_void_p) for n in ("x", "w", "w2", "bias", "norm_w", "resid", "y", "zero_buf")]
+
+
+class CAttnStep(ctypes.Structure):       # q3_attn_step_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("variant", "B", "nh", "nkv", "n_splits", "max_seq")] + \
+               [("eps", ctypes.c_float), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("pos", "qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache", "out")]
+
+
 class CTiming(ctypes.Structure):
     _fields_ = [("prefill_ms", ctypes.c_double), ("generation_ms", ctypes.c_double), ("decode_ms", ctypes.c_double),
                 ("generation_frames", ctypes.c_int32)]
@@ -108,6 +120,8 @@ SYMBOLS = {
     "q3_rng_next": (ctypes.c_float, [P(ctypes.c_uint64)]),
     "q3_fused_residual_rmsnorm": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]),
     "q3_linear": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "q3_linear_ex": (c_int, [c_int, P(CLinearEx)]),
+    "q3_attn_step": (c_int, [c_int, P(CAttnStep)]),
     "q3_decode_codes": (c_int, [c_void_p, c_void_p, c_int, c_void_p, P(c_void_p)]),
     "q3_codes_to_tensor": (None, [c_void_p, c_int, c_void_p]),
     "q3_session_set_profile": (c_int, [c_void_p, c_int]),

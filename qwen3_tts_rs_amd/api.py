@@ -970,6 +970,73 @@ def linear(x: np.ndarray, w_bf16: np.ndarray, bias: Optional[np.ndarray] = None,
     return y
 
 
+def linear_ex(x: np.ndarray, w_bf16: np.ndarray, *, w2_bf16: Optional[np.ndarray] = None, bias: Optional[np.ndarray] = None,
+              norm_w: Optional[np.ndarray] = None, eps: float = 1e-6, resid: Optional[np.ndarray] = None, epi: int = 0,
+              tiled: int = -1, ksplit: int = 1, use_ws: bool = True, y: Optional[np.ndarray] = None, M: Optional[int] = None,
+              zero_buf: Optional[np.ndarray] = None, zero_n: int = 0, device: int = 0) -> np.ndarray:
+    """q3_linear_ex: one launch of the GEMV family with the dispatcher's arguments spelled out (parity tests). x [M][ldx] and
+    resid [M][ldr] carry their pitches as their second dimension, K and N are those of w [N][K]. y ([M_alloc][ldy] f32, C order)
+    is uploaded, written in place and returned whole; zero_buf ([zero_n + guard] f32) likewise. Raises Q3Error (status 7) when
+    the dispatcher refuses the arguments."""
+    def f32(a):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+        return a
+    w = np.ascontiguousarray(w_bf16, dtype=np.uint16); N, K = w.shape
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    M = x.shape[0] if M is None else M
+    assert x.ndim == 2 and x.shape[0] >= M
+    if y is None:
+        y = np.zeros((M, N), dtype=np.float32)
+    f32(y); assert y.ndim == 2
+    a = _lib.CLinearEx()
+    a.M, a.N, a.K, a.ldx, a.ldy, a.M_alloc = M, N, K, x.shape[1], y.shape[1], y.shape[0]
+    a.epi, a.tiled, a.ksplit, a.use_ws, a.eps = epi, tiled, ksplit, 1 if use_ws else 0, eps
+    keep = [x, w, y]
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    a.x, a.w, a.y = ptr(x), ptr(w), ptr(y)
+    if w2_bf16 is not None:
+        w2 = np.ascontiguousarray(w2_bf16, dtype=np.uint16); assert w2.shape == w.shape
+        keep.append(w2); a.w2 = ptr(w2)
+    if bias is not None:
+        b = np.ascontiguousarray(bias, dtype=np.float32); assert b.shape == (N,)
+        keep.append(b); a.bias = ptr(b)
+    if norm_w is not None:
+        nw = np.ascontiguousarray(norm_w, dtype=np.float32); assert nw.shape == (K,)
+        keep.append(nw); a.norm_w = ptr(nw)
+    if resid is not None:
+        r = np.ascontiguousarray(resid, dtype=np.float32); assert r.ndim == 2 and r.shape[0] >= M
+        keep.append(r); a.resid = ptr(r); a.ldr = r.shape[1]
+    if zero_buf is not None:
+        f32(zero_buf); assert zero_buf.ndim == 1 and zero_buf.size >= zero_n
+        a.zero_buf = ptr(zero_buf); a.zero_n = zero_n; a.zero_guard = zero_buf.size - zero_n
+    check(lib.q3_linear_ex(device, ctypes.byref(a)))
+    return y
+
+
+def attn_step(variant: int, qkv: np.ndarray, pos, q_norm_w: np.ndarray, k_norm_w: np.ndarray, eps: float, rope_cos: np.ndarray,
+              rope_sin: np.ndarray, kcache: np.ndarray, vcache: np.ndarray, nh: int, nkv: int, n_splits: int, device: int = 0):
+    """q3_attn_step: one decode-attention step over a contiguous cache [B][nkv][max_seq][128] (parity tests). variant 0 = the
+    one-launch kernel (+ merge), 1 = the three-launch path, 2 = the code predictor's kernel. Returns (out [B][nh*128], kcache,
+    vcache) — the caches are copies of the arguments with the new position appended."""
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32); B = qkv.shape[0]
+    assert qkv.shape == (B, (nh + 2 * nkv) * 128)
+    kc = np.array(kcache, dtype=np.float32, order="C"); vc = np.array(vcache, dtype=np.float32, order="C")
+    max_seq = kc.shape[2]
+    assert kc.shape == (B, nkv, max_seq, 128) and vc.shape == kc.shape
+    pos = np.ascontiguousarray(pos, dtype=np.int32); assert pos.shape == (B,)
+    qw = np.ascontiguousarray(q_norm_w, dtype=np.float32); kw = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    rc = np.ascontiguousarray(rope_cos, dtype=np.float32); rs = np.ascontiguousarray(rope_sin, dtype=np.float32)
+    assert qw.shape == (128,) and kw.shape == (128,) and rc.shape == (max_seq, 64) and rs.shape == (max_seq, 64)
+    out = np.zeros((B, nh * 128), dtype=np.float32)
+    a = _lib.CAttnStep()
+    a.variant, a.B, a.nh, a.nkv, a.n_splits, a.max_seq, a.eps = variant, B, nh, nkv, n_splits, max_seq, eps
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    a.pos, a.qkv, a.q_norm_w, a.k_norm_w, a.rope_cos, a.rope_sin = ptr(pos), ptr(qkv), ptr(qw), ptr(kw), ptr(rc), ptr(rs)
+    a.kcache, a.vcache, a.out = ptr(kc), ptr(vc), ptr(out)
+    check(lib.q3_attn_step(device, ctypes.byref(a)))
+    return out, kc, vc
+
+
 def sample(logits: np.ndarray, u: np.ndarray, options: SynthesisOptions, seen: Optional[np.ndarray] = None,
            token_count: int = -1, device: int = 0) -> np.ndarray:
     """apply_generation_penalties + sample on the GPU (token_count < 0: plain `sample`, sampling.rs:140)."""

@@ -186,6 +186,116 @@ extern "C" q3_status q3_linear(int device, const float* x_host, const uint16_t* 
     return Q3_OK;
 }
 
+// One launch_linear call through a complete LinArgs (op-level tests of every GEMV family: tests/test_gpu_linear_paths.py).
+// A launch the dispatcher refuses comes back as a status — never another kernel in its place — and leaves the host y alone.
+extern "C" q3_status q3_linear_ex(int device, const q3_linear_ex_args* p) {
+    if (!p || !p->x || !p->w || !p->y) return set_err(Q3_INVALID_ARG, "q3_linear_ex: null argument");
+    const int M = p->M, N = p->N, K = p->K;
+    if (M < 1 || M > Q3_MAX_BATCH || N < 1 || K < 8 || K % 8) return set_err(Q3_INVALID_ARG, "q3_linear_ex: bad shape (1 <= M <= %d, K a multiple of 8)", Q3_MAX_BATCH);
+    if (p->ldx < K || p->ldx % 4 || p->ldy < N || p->M_alloc < M) return set_err(Q3_INVALID_ARG, "q3_linear_ex: bad pitch (ldx >= K, ldx %% 4 == 0, ldy >= N, M_alloc >= M)");
+    if (p->epi < EPI_NONE || p->epi > EPI_SWIGLU || p->tiled < -1 || p->tiled > 2 || p->ksplit < 1) return set_err(Q3_INVALID_ARG, "q3_linear_ex: epi 0..3, tiled -1..2, ksplit >= 1");
+    if (p->epi == EPI_SWIGLU && !p->w2) return set_err(Q3_INVALID_ARG, "q3_linear_ex: SwiGLU needs a second matrix");
+    if (p->epi == EPI_RESID && (!p->resid || p->ldr < N)) return set_err(Q3_INVALID_ARG, "q3_linear_ex: residual epilogue needs resid with ldr >= N");
+    if (p->zero_n < 0 || p->zero_n % 4 || p->zero_guard < 0 || (p->zero_n > 0 && !p->zero_buf)) return set_err(Q3_INVALID_ARG, "q3_linear_ex: zero_n must be a multiple of 4 with a buffer");
+    int mode = p->tiled;
+    if (mode < 0) mode = (M <= 16 && N < 4096 && !short_k_wide(N, K) && (M <= 2 || (N <= 1024 && M <= 8))) ? 2 : 1;      // pick_mode
+    if (mode == 0 && p->ksplit != 1) return set_err(Q3_UNSUPPORTED, "q3_linear_ex: the row-major kernel has no split-K form");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const int nmat = p->epi == EPI_SWIGLU ? 2 : 1;
+    const size_t welems = mode == 0 ? (size_t)N * K : tiled_elems(mode, N, K);
+    uint16_t* w; float *x, *y, *b = nullptr, *nw = nullptr, *res = nullptr, *zb = nullptr, *ws = nullptr;
+    HIPC(pool.alloc(&w, welems * nmat));
+    for (int i = 0; i < nmat; ++i) {
+        const uint16_t* src = i ? p->w2 : p->w;
+        if (mode == 0) HIPC(q3_hipMemcpy(w + (size_t)i * welems, src, welems * 2, hipMemcpyHostToDevice));
+        else {
+            std::vector<uint16_t> wt(welems);
+            retile_bf16(src, N, K, wt.data(), mode);
+            HIPC(q3_hipMemcpy(w + (size_t)i * welems, wt.data(), welems * 2, hipMemcpyHostToDevice));
+        }
+    }
+    const size_t xn = (size_t)M * p->ldx, yn = (size_t)p->M_alloc * p->ldy;
+    HIPC(pool.alloc(&x, xn)); HIPC(q3_hipMemcpy(x, p->x, xn * 4, hipMemcpyHostToDevice));
+    HIPC(pool.alloc(&y, yn)); HIPC(q3_hipMemcpy(y, p->y, yn * 4, hipMemcpyHostToDevice));
+    if (p->bias) { HIPC(pool.alloc(&b, (size_t)N)); HIPC(q3_hipMemcpy(b, p->bias, (size_t)N * 4, hipMemcpyHostToDevice)); }
+    if (p->norm_w) { HIPC(pool.alloc(&nw, (size_t)K)); HIPC(q3_hipMemcpy(nw, p->norm_w, (size_t)K * 4, hipMemcpyHostToDevice)); }
+    if (p->epi == EPI_RESID) { HIPC(pool.alloc(&res, (size_t)M * p->ldr)); HIPC(q3_hipMemcpy(res, p->resid, (size_t)M * p->ldr * 4, hipMemcpyHostToDevice)); }
+    const size_t zn = (size_t)p->zero_n + p->zero_guard;
+    if (p->zero_n > 0) { HIPC(pool.alloc(&zb, zn)); HIPC(q3_hipMemcpy(zb, p->zero_buf, zn * 4, hipMemcpyHostToDevice)); }
+    size_t ws_bytes = 0;
+    if (p->use_ws && M > 16) {      // outside the GEMM's shapes the workspace is still passed: the dispatcher itself must fall back to k_gemv_wide
+        if (N >= 128 && K >= 128) ws_bytes = gemm_wide_ws_bytes(M, N, K, p->epi);
+        HIPC(pool.alloc(&ws, (ws_bytes ? ws_bytes : 256) / 4));
+    }
+    // split-K adds into y: zeros under the M x N result only, so that the caller's sentinels around it survive
+    if (p->ksplit == 2) for (int m = 0; m < M; ++m) HIPC(q3_null_stream_memset(y + (size_t)m * p->ldy, (size_t)N * 4, m == M - 1));
+    LinArgs a;
+    a.W = w; a.W2 = nmat == 2 ? w + welems : nullptr; a.x = x; a.ldx = p->ldx; a.norm_w = nw; a.eps = p->eps; a.bias = b;
+    a.resid = res; a.ldr = res ? p->ldr : 0; a.y = y; a.ldy = p->ldy; a.M = M; a.N = N; a.K = K; a.epi = p->epi;
+    a.tiled = mode; a.Kpad = mode == 0 ? K : kpad_for(mode, K); a.ksplit = p->ksplit;
+    a.zero = zb; a.zero_n = zb ? p->zero_n : 0; a.ws = ws; a.ws_bytes = ws_bytes;
+    HIPC(q3_hipDeviceSynchronize());
+    const hipError_t e = launch_linear(a, 0);
+    if (e == hipErrorInvalidValue || e == hipErrorNotSupported) {
+        (void)hipGetLastError();
+        return set_err(Q3_UNSUPPORTED, "q3_linear_ex: launch_linear refused M=%d N=%d K=%d epi=%d norm=%d tiled=%d ksplit=%d (%s)", M, N, K, p->epi, nw ? 1 : 0,
+                       mode, p->ksplit, hipGetErrorString(e));
+    }
+    HIPC(e);
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->y, y, yn * 4, hipMemcpyDeviceToHost));
+    if (zb) HIPC(q3_hipMemcpy(p->zero_buf, zb, zn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+// One decode-attention step over a contiguous cache (tests/test_gpu_attention_op.py): q/k-norm + RoPE + append + GQA attention
+// through the one-launch kernel (+ merge), the three-launch path, or the code predictor's single-wave kernel.
+extern "C" q3_status q3_attn_step(int device, const q3_attn_step_args* p) {
+    if (!p || !p->pos || !p->qkv || !p->q_norm_w || !p->k_norm_w || !p->rope_cos || !p->rope_sin || !p->kcache || !p->vcache || !p->out)
+        return set_err(Q3_INVALID_ARG, "q3_attn_step: null argument");
+    const int B = p->B, nh = p->nh, nkv = p->nkv;
+    if (p->variant < 0 || p->variant > 2) return set_err(Q3_INVALID_ARG, "q3_attn_step: variant 0..2");
+    if (B < 1 || B > Q3_MAX_BATCH || nkv < 1 || nh < nkv || nh > 64 || nh % nkv || p->max_seq < 1 || p->n_splits < 1 || p->n_splits > MAX_SPLITS)
+        return set_err(Q3_INVALID_ARG, "q3_attn_step: bad shape");
+    const int nrep = nh / nkv;
+    if (nrep != 1 && nrep != 2 && nrep != 4) return set_err(Q3_UNSUPPORTED, "q3_attn_step: heads / kv heads must be 1, 2 or 4");
+    for (int b = 0; b < B; ++b) if (p->pos[b] < 0 || p->pos[b] >= p->max_seq) return set_err(Q3_INVALID_ARG, "q3_attn_step: pos[%d] = %d outside the cache (%d)", b, p->pos[b], p->max_seq);
+    if (p->variant == 2) for (int b = 1; b < B; ++b) if (p->pos[b] != p->pos[0]) return set_err(Q3_INVALID_ARG, "q3_attn_step: variant 2 takes one position for every row");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const int ld_qkv = (nh + 2 * nkv) * HEAD_DIM, QD = nh * HEAD_DIM;
+    const size_t cn = (size_t)B * nkv * p->max_seq * HEAD_DIM, rn = (size_t)p->max_seq * 64;
+    int* pos; float *qkv, *qw, *kw, *rc, *rs, *kv, *qbuf, *part, *out;
+    HIPC(pool.alloc(&pos, (size_t)B)); HIPC(pool.alloc(&qkv, (size_t)B * ld_qkv)); HIPC(pool.alloc(&qw, (size_t)HEAD_DIM)); HIPC(pool.alloc(&kw, (size_t)HEAD_DIM));
+    HIPC(pool.alloc(&rc, rn)); HIPC(pool.alloc(&rs, rn)); HIPC(pool.alloc(&kv, 2 * cn));       // K and V in one block: their distance fits every kernel's 32-bit form
+    HIPC(pool.alloc(&qbuf, (size_t)B * QD)); HIPC(pool.alloc(&part, (size_t)B * nh * p->n_splits * PART_STRIDE)); HIPC(pool.alloc(&out, (size_t)B * QD));
+    HIPC(q3_hipMemcpy(pos, p->pos, (size_t)B * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(qkv, p->qkv, (size_t)B * ld_qkv * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(qw, p->q_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kw, p->k_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(rc, p->rope_cos, rn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(rs, p->rope_sin, rn * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(kv, p->kcache, cn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kv + cn, p->vcache, cn * 4, hipMemcpyHostToDevice));
+    AttnArgs t{};
+    t.qkv = qkv; t.ld_qkv = ld_qkv; t.q_norm_w = qw; t.k_norm_w = kw; t.eps = p->eps; t.rope_cos = rc; t.rope_sin = rs;
+    t.pos_dev = p->variant == 2 ? nullptr : pos; t.pos_static = p->variant == 2 ? p->pos[0] : 0;
+    t.kcache = kv; t.vcache = kv + cn; t.max_seq = p->max_seq; t.qbuf = qbuf; t.part = part; t.out = out; t.ld_out = QD;
+    t.B = B; t.nh = nh; t.nkv = nkv; t.n_splits = p->n_splits; t.rows_per_seq = 1;
+    if (p->variant == 2 && !attn_cp_ok(t)) return set_err(Q3_UNSUPPORTED, "q3_attn_step: arguments outside launch_attn_cp (one split, position < 16, max_seq < 256)");
+    HIPC(q3_hipDeviceSynchronize());
+    if (p->variant == 0) {
+        HIPC(launch_attn_fused(t, 0));
+        if (p->n_splits > 1) HIPC(launch_attn_merge(t, 0));
+    } else if (p->variant == 1) {
+        HIPC(launch_qknorm_rope_kv(t, 0));
+        HIPC(launch_attn_decode(t, 0));
+        HIPC(launch_attn_merge(t, 0));
+    } else HIPC(launch_attn_cp(t, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->out, out, (size_t)B * QD * 4, hipMemcpyDeviceToHost));
+    HIPC(q3_hipMemcpy(p->kcache, kv, cn * 4, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(p->vcache, kv + cn, cn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
 #ifdef Q3_TRACE
 // development builds only (not declared in include/q3tts.h): arm the per-node stamp buffer BEFORE the first
 // q3_session_generate (the captured graph keeps the slice pointers), then read the stamps of the last replayed frame.

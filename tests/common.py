@@ -38,6 +38,21 @@ def model_pair(cfg, seed=synth.DEFAULT_SEED, device=0):
     return gm, om
 
 
+def gqa_config(ratio):
+    """q.tiny() at another heads / kv-heads ratio, talker and code predictor alike (tiny itself is 2): the 1 and 4 of
+    q3_model_create's accepted ratios, which no other config of the suite has"""
+    cfg = q.tiny()
+    if ratio == 1:
+        cfg.n_heads = cfg.n_kv_heads = cfg.cp_heads = cfg.cp_kv_heads = 2
+    elif ratio == 4:
+        cfg.n_heads = cfg.cp_heads = 4
+        cfg.n_kv_heads = cfg.cp_kv_heads = 1
+    else:
+        assert ratio == 2
+    cfg.name = f"tiny_gqa{ratio}"
+    return cfg
+
+
 from qwen3_tts_rs_amd.synth import synthetic_prompt      # noqa: E402,F401 — the benchmark's prompt generator lives in the package (bench.py uses it)
 
 

@@ -1,6 +1,7 @@
 """ctypes wrapper of the CPU oracle (oracle/libq3oracle.so) — TEST INFRASTRUCTURE. Imported only by
 tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg."""
 import ctypes
+import weakref
 import os
 import subprocess
 
@@ -135,6 +136,7 @@ class OracleModel:
         self.cfg = cfg
         oc = to_oconfig(cfg)
         self.h = olib.q3o_model_new(ctypes.byref(oc))
+        self._sessions = weakref.WeakSet()      # q3o_session_free reads the model: sessions still open are closed before it goes
 
     def set_tensor(self, name, arr, dtype):
         """arr: f32 array, or uint16 bf16 bits (dtype 1) — upconverted exactly to f32."""
@@ -150,6 +152,8 @@ class OracleModel:
 
     def close(self):
         if self.h:
+            for s in list(getattr(self, "_sessions", ())):      # e.g. left open by a test that failed midway
+                s.close()
             olib.q3o_model_free(self.h); self.h = None
 
     __del__ = close
@@ -224,6 +228,7 @@ class OracleSession:
         self.h = olib.q3o_session_new(model.h, ctypes.byref(r))
         if not self.h:
             raise RuntimeError(err())
+        model._sessions.add(self)
 
     def close(self):
         if self.h:

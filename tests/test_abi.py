@@ -106,6 +106,20 @@ def test_no_cpu_fallback():
         assert e.status == 5
     else:
         raise AssertionError("q3_linear succeeded without a GPU")
+    try:
+        q.linear_ex(np.zeros((1, 8), np.float32), np.zeros((8, 8), np.uint16))
+    except _lib.Q3Error as e:
+        assert e.status == 5
+    else:
+        raise AssertionError("q3_linear_ex succeeded without a GPU")
+    try:
+        q.attn_step(0, np.zeros((1, 4 * 128), np.float32), [0], np.ones(128, np.float32), np.ones(128, np.float32), 1e-6,
+                    np.ones((4, 64), np.float32), np.zeros((4, 64), np.float32), np.zeros((1, 1, 4, 128), np.float32),
+                    np.zeros((1, 1, 4, 128), np.float32), 2, 1, 1)
+    except _lib.Q3Error as e:
+        assert e.status == 5
+    else:
+        raise AssertionError("q3_attn_step succeeded without a GPU")
 
 
 def test_speaker_language_tables():
@@ -171,6 +185,10 @@ def test_null_handles_return_status_not_crash():
         lambda: L.q3_model_load(b"/nonexistent", -1, ctypes.byref(null), ctypes.byref(i)),
         lambda: L.q3_wav_read(b"/nonexistent.wav", None, 0, None, None),
         lambda: L.q3_resample(None, 1, 16000, 24000, None, 0, None),
+        lambda: L.q3_linear_ex(0, None),
+        lambda: L.q3_linear_ex(0, ctypes.byref(_lib.CLinearEx())),
+        lambda: L.q3_attn_step(0, None),
+        lambda: L.q3_attn_step(0, ctypes.byref(_lib.CAttnStep())),
     ]
     for k, f in enumerate(calls):
         st = f()

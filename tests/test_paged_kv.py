@@ -10,7 +10,7 @@ import pytest
 
 import qwen3_tts_rs_amd as q
 from qwen3_tts_rs_amd import _lib, api
-from common import model_pair, synthetic_prompt
+from common import model_pair, synthetic_prompt, gqa_config
 
 pytestmark = pytest.mark.gpu
 
@@ -37,8 +37,31 @@ def _run(model, utts, frames, graph, monkeypatch, contiguous):
     return out, pcm
 
 
-@pytest.mark.parametrize("kind,B,frames", [("custom", 3, 300), ("custom", 1, 140), ("design200", 2, 150), ("design600", 1, 40), ("design1100", 1, 30)])
-def test_paged_equals_contiguous_bit_for_bit(gm, kind, B, frames, monkeypatch):
+@pytest.fixture(scope="module")
+def gqa_models():
+    """models at heads / kv-heads ratios 1 and 4 (common.gqa_config), built on first use"""
+    made = {}
+
+    def get(ratio):
+        if ratio not in made:
+            made[ratio] = q.Qwen3TTS.from_synthetic(gqa_config(ratio), device=0, seed=1234)
+        return made[ratio]
+    yield get
+    for m in made.values():
+        m.close()
+
+
+# the last column is the heads / kv-heads ratio: 2 = the tiny config; 1 and 4 reach the paged instances of k_attn_fused (scalar- and
+# vector-loaded page-table rows) and the chunked prefill over pages at NREP = 1 / 4
+@pytest.mark.parametrize("kind,B,frames,ratio", [
+    pytest.param("custom", 3, 300, 2, id="custom-3-300"), pytest.param("custom", 1, 140, 2, id="custom-1-140"),
+    pytest.param("design200", 2, 150, 2, id="design200-2-150"), pytest.param("design600", 1, 40, 2, id="design600-1-40"),
+    pytest.param("design1100", 1, 30, 2, id="design1100-1-30"),
+    pytest.param("custom", 3, 140, 1, id="gqa1-custom-3-140"), pytest.param("design200", 2, 40, 1, id="gqa1-design200-2-40"),
+    pytest.param("design1100", 1, 30, 1, id="gqa1-design1100-1-30"),
+    pytest.param("custom", 3, 140, 4, id="gqa4-custom-3-140"), pytest.param("design200", 2, 40, 4, id="gqa4-design200-2-40"),
+    pytest.param("design1100", 1, 30, 4, id="gqa4-design1100-1-30")])
+def test_paged_equals_contiguous_bit_for_bit(gm, gqa_models, kind, B, frames, ratio, monkeypatch):
     """Same sessions with paged and with contiguous KV: identical codes. 300 frames cross two page boundaries inside the
     captured frame; a 200-token instruct prompt fills page 0 and 1 in the chunked prefill, 600 tokens go through the GEMM
     prefill (bf16x3 planes built from pages) and end in page 4; 1100 tokens make the row longer than 8 pages (the vector-loaded
@@ -49,6 +72,8 @@ def test_paged_equals_contiguous_bit_for_bit(gm, kind, B, frames, monkeypatch):
         n = int(kind[6:])
         return q.Utterance(synthetic_prompt(9, i), language=q.Language.German, instruct_ids=synthetic_prompt(n, 50 + i), seed=40 + i)
     utts = [utt(i) for i in range(B)]
+    if ratio != 2:
+        gm = gqa_models(ratio)
     info0 = gm.kv_pool_info()
     assert info0["page_positions"] == 128 and info0["pages_in_use"] == 0
     for graph in (True, False):
@@ -162,12 +187,8 @@ def test_replace_relinks_pages(monkeypatch):
         m.close()
 
 
-def test_bf16_kv_session_mode(gm):
-    """Opt-in bf16 K/V (q3_session_set_kv_dtype; the reference GPU path's cache dtype, kv_cache.rs:234-310): the prompt is prefilled
-    in f32 pages and converted once into pages of the bf16 pool, decode steps append / read bf16. Not bit-comparable with the F32
-    oracle by construction, so the checks are: teacher-forced hidden states within bf16 distance of the f32 session's (crossing a
-    page boundary), deterministic free runs, a swap into a bf16 session equal to the request's own bf16 batch-1 run, and every
-    page of both pools returned."""
+def _bf16_teacher_forced(gm):
+    """20 teacher-forced steps across a page boundary, f32 and bf16 K/V: (hidden states per mode, the two utterances, options)"""
     cfg = gm.config
     opts = q.SynthesisOptions(max_length=150, eos_token_id=None, seed=7)
     utts = [q.Utterance(synthetic_prompt(12, i), language=q.Language.German, instruct_ids=synthetic_prompt(110, 50 + i), seed=40 + i) for i in range(2)]   # 119 positions: page 0 nearly full
@@ -181,6 +202,24 @@ def test_bf16_kv_session_mode(gm):
     scale = float(np.abs(hs[False]).max())
     err = float(np.abs(hs[True] - hs[False]).max())
     assert 0 < err <= 4e-2 * scale, (err, scale)             # bf16 K/V: 8 mantissa bits on every cached key and value; not zero (the mode is really on)
+    return utts, opts
+
+
+@pytest.mark.parametrize("ratio", [1, 4])
+def test_bf16_kv_teacher_forced_gqa_ratios(gqa_models, ratio):
+    """the teacher-forced part of test_bf16_kv_session_mode at heads / kv-heads ratios 1 and 4: the bf16 instances of k_attn_fused"""
+    m = gqa_models(ratio)
+    _bf16_teacher_forced(m)
+    assert m.kv_pool_info()["pages_in_use"] == 0
+
+
+def test_bf16_kv_session_mode(gm):
+    """Opt-in bf16 K/V (q3_session_set_kv_dtype; the reference GPU path's cache dtype, kv_cache.rs:234-310): the prompt is prefilled
+    in f32 pages and converted once into pages of the bf16 pool, decode steps append / read bf16. Not bit-comparable with the F32
+    oracle by construction, so the checks are: teacher-forced hidden states within bf16 distance of the f32 session's (crossing a
+    page boundary), deterministic free runs, a swap into a bf16 session equal to the request's own bf16 batch-1 run, and every
+    page of both pools returned."""
+    utts, opts = _bf16_teacher_forced(gm)
     runs = []
     for _ in range(2):
         s = gm.session(utts, opts, kv_bf16=True); s.prefill(); s.generate(150)
