@@ -231,6 +231,12 @@ q3_status q3_session_next_chunk(q3_session* s, float* pcm_host, size_t cap, size
  * advance in lockstep, so the first row asked generates the chunk's frames for all of them and the others only run their
  * vocoder. An error leaves the row's position untouched: the call can be repeated (lib.rs:1775-1781). */
 q3_status q3_session_next_chunk_row(q3_session* s, int b, float* pcm_host, size_t cap, size_t* n_samples, int* done);
+/* q3_session_next_chunk_row for every row in one call: generates until every live row has a chunk (or ends, or is held by
+ * open text), then decodes all rows' chunks together. pcm_host / cap / n_samples / done are arrays of one entry per row.
+ * n_samples[b] = 0 with done[b] = 0 means "nothing yet" (held row), with done[b] = 1 "finished". Chunk boundaries and
+ * samples are those of q3_session_next_chunk_row; in stream mode 1 the rows that are not ICL share one pass of a codec stream
+ * the session owns (below), so a chunk costs O(chunk) and the launch count does not grow with the rows. */
+q3_status q3_session_next_chunks(q3_session* s, float* const* pcm_host, const size_t* cap, size_t* n_samples, int* done);
 /* Continuous batching: replace row b of a PREFILLED session — normally one whose sequence has ended (q3_session_frames:
  * done; fetch its codes / PCM first) — by a new request, which then starts at its frame 0 while the other rows go on. The
  * reference keeps all per-utterance state per call (KV caches, SamplingContext, penalty mask, trailing text:
@@ -388,6 +394,24 @@ enum { Q3_DEC_QUANT = 0, Q3_DEC_PRECONV = 1, Q3_DEC_PRETRANS = 2, Q3_DEC_UP0 = 3
        Q3_DEC_INIT = 5, Q3_DEC_BLK0 = 6, Q3_DEC_BLK1 = 7, Q3_DEC_BLK2 = 8, Q3_DEC_BLK3 = 9, Q3_DEC_N = 10 };
 q3_status q3_decode_codes(q3_model* m, const uint32_t* frames_host, int n_frames, float* pcm_host,
                           float** taps_host);
+/* ---------------- codec stream: the vocoder with per-row state, many rows per decode pass ----------------
+ * A codec stream keeps, for each of its `rows`, what the vocoder's front needs to go on from where the row stopped (the
+ * pre-transformer's K / V, its output latent, two columns of pre_conv history): a push costs O(new frames), not O(frames so
+ * far), and ONE pass of launches serves every row pushed in the call. Row state (about 68 KB per frame at the production
+ * decoder shape) is allocated when a row is first pushed; Q3_OOM when the device refuses it. No reference counterpart. */
+typedef struct q3_codec_stream q3_codec_stream;
+q3_status q3_codec_stream_create(q3_model* m, int rows, int max_frames, q3_codec_stream** out);
+void      q3_codec_stream_free(q3_codec_stream* cs);
+q3_status q3_codec_stream_reset(q3_codec_stream* cs, int row);          /* row starts over at frame 0 */
+q3_status q3_codec_stream_pos(q3_codec_stream* cs, int row, int* n_frames);
+/* append n_frames[i] frames ([n][16] u32, host) to row rows[i] and decode them, all rows in one pass:
+ * pcm_host[i] receives n_frames[i] * samples_per_frame f32 samples — the same bits as those frames in
+ * q3_decode_codes over everything the row has been given so far. A row out of range or listed twice, a push past
+ * max_frames, a null pointer or a cap[i] below the samples is Q3_INVALID_ARG and changes no row; n_frames[i] = 0 is a
+ * no-op for that row. A push that fails on the device after those checks (Q3_HIP_ERROR) leaves the rows it carried at
+ * frame 0: their state is not trusted half-written, push them again from their first frame. */
+q3_status q3_codec_stream_push(q3_codec_stream* cs, int n_rows, const int* rows, const uint32_t* const* frames_host,
+                               const int* n_frames, float* const* pcm_host, const size_t* cap);
 /* codes_to_tensor (lib.rs:1417-1431): [n][16] u32 → [16][n] i64 (host helper) */
 void      q3_codes_to_tensor(const uint32_t* frames, int n_frames, int64_t* out);
 

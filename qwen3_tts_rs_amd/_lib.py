@@ -102,6 +102,12 @@ SYMBOLS = {
     "q3_session_run": (c_int, [c_void_p, c_int, P(c_void_p), P(ctypes.c_size_t), P(ctypes.c_size_t), P(CTiming)]),
     "q3_session_next_chunk": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, P(ctypes.c_size_t), P(c_int)]),
     "q3_session_next_chunk_row": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_size_t, P(ctypes.c_size_t), P(c_int)]),
+    "q3_session_next_chunks": (c_int, [c_void_p, P(c_void_p), P(ctypes.c_size_t), P(ctypes.c_size_t), P(c_int)]),
+    "q3_codec_stream_create": (c_int, [c_void_p, c_int, c_int, P(c_void_p)]),
+    "q3_codec_stream_free": (None, [c_void_p]),
+    "q3_codec_stream_reset": (c_int, [c_void_p, c_int]),
+    "q3_codec_stream_pos": (c_int, [c_void_p, c_int, P(c_int)]),
+    "q3_codec_stream_push": (c_int, [c_void_p, c_int, P(c_int), P(c_void_p), P(c_int), P(c_void_p), P(ctypes.c_size_t)]),
     "q3_session_replace": (c_int, [c_void_p, c_int, c_void_p]),
     "q3_batcher_create": (c_int, [c_void_p, c_int, c_int, c_int, P(c_void_p)]),
     "q3_batcher_free": (None, [c_void_p]),

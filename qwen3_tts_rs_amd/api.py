@@ -247,6 +247,17 @@ class Session:
         check(lib.q3_session_next_chunk_row(self._h, int(b), buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(n), ctypes.byref(d)))
         return (AudioBuffer(buf[:n.value].copy()) if n.value else None), bool(d.value)
 
+    def next_chunks(self) -> List[Tuple[Optional[AudioBuffer], bool]]:
+        """next_chunk_row for every row in one call (q3_session_next_chunks): one (chunk or None, done) per row. In continuous
+        stream mode the rows' chunks are vocoded together, from per-row decoder state."""
+        B = self.B; spf = self.model.config.samples_per_frame
+        bufs = [np.zeros(max(self.options.chunk_frames, 1) * spf, dtype=np.float32) for _ in range(B)]
+        ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data_as(ctypes.c_void_p) for b in bufs])
+        caps = (ctypes.c_size_t * B)(*[b.size for b in bufs])
+        n = (ctypes.c_size_t * B)(); d = (ctypes.c_int * B)()
+        check(lib.q3_session_next_chunks(self._h, ptrs, caps, n, d))
+        return [((AudioBuffer(bufs[b][:n[b]].copy()) if n[b] else None), bool(d[b])) for b in range(B)]
+
     def prefill(self):
         check(lib.q3_session_prefill(self._h))
 
@@ -862,12 +873,55 @@ class Qwen3TTS:
         check(lib.q3_decode_codes(self._h, c.ctypes.data_as(ctypes.c_void_p), c.shape[0], out.ctypes.data_as(ctypes.c_void_p), tp))
         return AudioBuffer(out)
 
+    def codec_stream(self, rows: int, max_frames: int) -> "CodecStream":
+        """The vocoder with per-row state (q3_codec_stream_*): frames are appended to rows and decoded as they come, many rows
+        per pass; a row's samples are those of decode_codes over everything it has been given."""
+        return CodecStream(self, rows, max_frames)
+
     def frame_embed(self, sem_token: int, codes15, text_add: np.ndarray) -> np.ndarray:
         c = np.ascontiguousarray(codes15, dtype=np.uint32); t = np.ascontiguousarray(text_add, dtype=np.float32)
         out = np.zeros(self.config.hidden, dtype=np.float32)
         check(lib.q3_frame_embed(self._h, int(sem_token), c.ctypes.data_as(ctypes.c_void_p), t.ctypes.data_as(ctypes.c_void_p),
                                  out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+
+class CodecStream:
+    def __init__(self, model: "Qwen3TTS", rows: int, max_frames: int):
+        self.model = model; self.rows = int(rows); self.max_frames = int(max_frames)
+        self._h = ctypes.c_void_p()
+        check(lib.q3_codec_stream_create(model._h, self.rows, self.max_frames, ctypes.byref(self._h)))
+
+    def push(self, frames: dict) -> dict:
+        """{row: codes [n][16]} -> {row: samples [n * samples_per_frame]}: every row of the call in one decode pass."""
+        return self._push_lists(list(frames.keys()), list(frames.values()))
+
+    def _push_lists(self, rows: Sequence[int], codes: Sequence[np.ndarray], cap: Optional[Sequence[int]] = None) -> dict:
+        """push with the rows as given (a row may be listed twice: the call is then refused); cap overrides the buffer sizes."""
+        n = len(rows); spf = self.model.config.samples_per_frame
+        cs = [np.ascontiguousarray(c, dtype=np.uint32).reshape(-1, 16) for c in codes]
+        outs = [np.zeros(c.shape[0] * spf, dtype=np.float32) for c in cs]
+        r = (ctypes.c_int * n)(*[int(x) for x in rows])
+        fp = (ctypes.c_void_p * n)(*[c.ctypes.data_as(ctypes.c_void_p) for c in cs])
+        nf = (ctypes.c_int * n)(*[c.shape[0] for c in cs])
+        op = (ctypes.c_void_p * n)(*[o.ctypes.data_as(ctypes.c_void_p) for o in outs])
+        cp = (ctypes.c_size_t * n)(*[int(x) for x in (cap if cap is not None else [o.size for o in outs])])
+        check(lib.q3_codec_stream_push(self._h, n, r, fp, nf, op, cp))
+        return {int(rows[i]): outs[i] for i in range(n)}
+
+    def reset(self, row: int):
+        check(lib.q3_codec_stream_reset(self._h, int(row)))
+
+    def pos(self, row: int) -> int:
+        n = ctypes.c_int()
+        check(lib.q3_codec_stream_pos(self._h, int(row), ctypes.byref(n)))
+        return n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.q3_codec_stream_free(self._h); self._h = None
+
+    __del__ = close
 
 
 def pcm16(samples: np.ndarray) -> np.ndarray:

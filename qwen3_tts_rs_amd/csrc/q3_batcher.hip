@@ -63,6 +63,7 @@ q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limi
         q.req.ref_text_ids = q.ref_text.data(); q.req.xvector = q.xvec.empty() ? nullptr : q.xvec.data();
     }
     if (b == 0) s->stream_pos = 0;       // q3_session_next_chunk (the row-0 streaming call) starts over with the new utterance too
+    if (s->cstream) codec_stream_reset(s->cstream, b);      // q3_session_next_chunks: the row's vocoder state belonged to the old utterance
     s->codes_host_valid = false;
     return Q3_OK;
 }

@@ -105,15 +105,19 @@ q3_status codec_reserve(const q3_model* m, CodecWS& ws, int T, int Tf) {
     HIPC(dev_malloc((void**)&ws.frames, (size_t)Tf * 16 * 4));
     size_t total_up = up; for (int b = 0; b < 4; ++b) total_up *= c.dec_up_rates[b];
     HIPC(dev_malloc((void**)&ws.pcm, (size_t)T * total_up * 4));
-    // RoPE table of the pre-transformer (decoder_12hz.rs:541-553), host libm
-    std::vector<float> cs((size_t)Tf * 32), sn((size_t)Tf * 32);
+    Q3C(codec_rope_table(c, Tf, ws.cs, ws.sn));
+    ws.cap_frames = T; ws.cap_front = Tf;
+    return Q3_OK;
+}
+// RoPE table of the pre-transformer (decoder_12hz.rs:541-553) for positions [0, n), host libm: cs / sn = device [n][32]
+q3_status codec_rope_table(const q3_config& c, int n, float* cs_dev, float* sn_dev) {
+    std::vector<float> cs((size_t)n * 32), sn((size_t)n * 32);
     for (int i = 0; i < 32; ++i) {
         const float inv = 1.0f / powf(c.dec_theta, (float)(2 * i) / (float)c.dec_head_dim);
-        for (int t = 0; t < Tf; ++t) { const float f = (float)t * inv; cs[(size_t)t * 32 + i] = cosf(f); sn[(size_t)t * 32 + i] = sinf(f); }
+        for (int t = 0; t < n; ++t) { const float f = (float)t * inv; cs[(size_t)t * 32 + i] = cosf(f); sn[(size_t)t * 32 + i] = sinf(f); }
     }
-    HIPC(q3_hipMemcpy(ws.cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
-    HIPC(q3_hipMemcpy(ws.sn, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
-    ws.cap_frames = T; ws.cap_front = Tf;
+    HIPC(q3_hipMemcpy(cs_dev, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(sn_dev, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
     return Q3_OK;
 }
 
@@ -127,7 +131,14 @@ static const void* packed_of(const float* w) { return tl_codec_model ? tl_codec_
 // bf16 planes per operand in the vocoder's matrix-core convs (q3_model_set_codec_planes): only codec_decode_dev sets 2,
 // for its own launches — the encoders that share the kernels (speaker / speech tokenizer) always run the exact products
 static thread_local int tl_codec_planes = 3;
-struct CodecPlanesScope { explicit CodecPlanesScope(int p) { tl_codec_planes = p; } ~CodecPlanesScope() { tl_codec_planes = 3; } };
+// what one decode sets for the launch helpers below: the model (packed weights) and the planes of ITS launches
+CodecScope::CodecScope(const q3_model* m) {
+    // Q3_CODEC_PLANES=2|3: A/B aid, overrides q3_model_set_codec_planes for the vocoder only (never the encoders)
+    static const int env_planes = [] { const char* e = getenv("Q3_CODEC_PLANES"); const int v = e ? atoi(e) : 0; return (v == 2 || v == 3) ? v : 0; }();
+    planes = env_planes ? env_planes : m->codec_planes;
+    tl_codec_model = m; tl_codec_planes = planes;
+}
+CodecScope::~CodecScope() { tl_codec_planes = 3; }
 static hipError_t conv1(const float* x, const float* w, const float* b, float* y, int cin, int cout, int L, hipStream_t st,
                         const float* resid = nullptr, const float* scale = nullptr, int act = 0,
                         const float* sa = nullptr, const float* sib = nullptr) {
@@ -142,40 +153,39 @@ static hipError_t convk(const float* x, const float* w, const float* b, float* y
     return launch_conv1d(a, st);
 }
 
-// frames already on device in ws.frames; result in ws.pcm. taps: host pointers or nullptr.
-// c0 = 0: whole-utterance decode, ws.pcm = [T*spf]. c0 > 0 (segment decode): the front (quantiser, pre_conv,
-// pre-transformer: everything with unbounded left context, and cheap) runs over all T frames, the convolutional
-// stack only over frames [c0, T), and ws.pcm = [(T-c0)*spf]; samples of frames >= c0 + CODEC_CTX_FRAMES are
-// identical to the whole-utterance decode (every kernel sums each output in a position-independent order).
-q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st, float** taps, int c0) {
+static q3_status tap_out(float** taps, int id, const float* dev, size_t n, hipStream_t st) {
+    if (taps && taps[id]) { HIPC(hipStreamSynchronize(st)); HIPC(q3_hipMemcpy(taps[id], dev, n * 4, hipMemcpyDeviceToHost)); }
+    return Q3_OK;
+}
+// The pipeline in its four stages. codec_decode_dev runs them over one utterance; the codec stream (q3_codec_stream.hip) runs
+// the same launches over the new columns of several rows, with its own positions and attention between q|k|v and the o projection.
+// D1 quantiser: ws.frames [T][16] → quantized in ws.bufB [Q][T] (E1 = A[0..256T), E2 = A[256T..512T))
+q3_status codec_front_quant(const q3_model* m, CodecWS& ws, int T, hipStream_t st) {
     const q3_config& c = m->cfg;
-    tl_codec_model = m;
-    // Q3_CODEC_PLANES=2|3: A/B aid, overrides q3_model_set_codec_planes for the vocoder only (never the encoders)
-    static const int env_planes = [] { const char* e = getenv("Q3_CODEC_PLANES"); const int v = e ? atoi(e) : 0; return (v == 2 || v == 3) ? v : 0; }();
-    const int NPL = env_planes ? env_planes : m->codec_planes;
-    const CodecPlanesScope planes_scope(NPL);
-    const int CD = c.dec_cb_dim, Q = c.dec_q_dim, LAT = c.dec_latent, DH = c.dec_hidden, QD = c.dec_heads * c.dec_head_dim, DI = c.dec_inter;
-    auto TAP = [&](int id, const float* dev, size_t n) -> q3_status {
-        if (taps && taps[id]) { HIPC(hipStreamSynchronize(st)); HIPC(q3_hipMemcpy(taps[id], dev, n * 4, hipMemcpyDeviceToHost)); }
-        return Q3_OK;
-    };
-    float *A = ws.bufA, *B = ws.bufB, *C = ws.bufC, *D = ws.bufD, *E = ws.bufE;
-    // D1 quantiser: E1 = A[0..256T), E2 = A[256T..512T) → quantized in B [Q][T]
+    const int CD = c.dec_cb_dim, Q = c.dec_q_dim;
+    float *A = ws.bufA, *B = ws.bufB;
     float* e1 = A; float* e2 = A + (size_t)CD * T;
     HIPC(launch_rvq_embed(ws.frames, T, m->first_cb, m->rest_cbs_dev, e1, e2, CD, c.dec_cb_size, st));
     HIPC(conv1(e1, m->first_proj, nullptr, B, CD, Q, T, st));
     HIPC(conv1(e2, m->rest_proj, nullptr, B, CD, Q, T, st, B));
-    Q3C(TAP(Q3_DEC_QUANT, B, (size_t)Q * T));
-    // D2 pre_conv → C [LAT][T]
-    HIPC(convk(B, m->pre_w, m->pre_b, C, Q, LAT, T, 3, 1, st));
-    Q3C(TAP(Q3_DEC_PRECONV, C, (size_t)LAT * T));
-    // D3 pre-transformer. hidden Hd = D [DH][T]
-    float* Hd = D;
+    return Q3_OK;
+}
+// D2 pre_conv (k = 3, causal): x [Q][L] → y [LAT][L]
+q3_status codec_front_preconv(const q3_model* m, const float* x, float* y, int L, hipStream_t st) {
+    HIPC(convk(x, m->pre_w, m->pre_b, y, m->cfg.dec_q_dim, m->cfg.dec_latent, L, 3, 1, st));
+    return Q3_OK;
+}
+// D3 pre-transformer: ws.bufC [LAT][T] → ws.bufC [LAT][T]. rope_attn(l, q, k, v, ao) rotates q / k ([QD][T] each, q | k | v | ao
+// back to back in ws.bufA) and leaves the attention output in ao.
+q3_status codec_front_transformer(const q3_model* m, CodecWS& ws, int T, hipStream_t st, const CodecAttnFn& rope_attn) {
+    const q3_config& c = m->cfg;
+    const int LAT = c.dec_latent, DH = c.dec_hidden, QD = c.dec_heads * c.dec_head_dim, DI = c.dec_inter;
+    float *A = ws.bufA, *B = ws.bufB, *C = ws.bufC, *D = ws.bufD, *E = ws.bufE;
+    float* Hd = D;                                   // hidden [DH][T]
     HIPC(conv1(C, m->inp_w, m->inp_b, Hd, LAT, DH, T, st));
     float* Nn = E;                                   // [DH][T]
     float* q = A; float* k = A + (size_t)QD * T; float* v = A + (size_t)2 * QD * T; float* ao = A + (size_t)3 * QD * T;
     float* g = B; float* u = B + (size_t)DI * T;
-    const float scale = (float)pow((double)c.dec_head_dim, -0.5);
     for (int l = 0; l < c.dec_layers; ++l) {
         const DecLayerW& L = m->dl[l];
         HIPC(launch_rmsnorm_c(Hd, L.in_ln, Nn, DH, T, c.dec_eps, st));
@@ -199,8 +209,7 @@ q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st
             HIPC(conv1(Nn, L.k, nullptr, k, DH, QD, T, st));
             HIPC(conv1(Nn, L.v, nullptr, v, DH, QD, T, st));
         }
-        HIPC(launch_rope_c(q, k, ws.cs, ws.sn, c.dec_heads, c.dec_head_dim, T, st));
-        HIPC(launch_attn_c(q, k, v, ao, c.dec_heads, c.dec_head_dim, T, scale, st));
+        Q3C(rope_attn(l, q, k, v, ao));
         HIPC(conv1(ao, L.o, nullptr, Hd, QD, DH, T, st, Hd, L.attn_scale));
         HIPC(launch_rmsnorm_c(Hd, L.post_ln, Nn, DH, T, c.dec_eps, st));
         if (!no_fuse_qkv && adjacent(L.gate, L.up, DI, DH)) {
@@ -214,14 +223,16 @@ q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st
     }
     HIPC(launch_rmsnorm_c(Hd, m->dec_norm, Nn, DH, T, c.dec_eps, st));
     HIPC(conv1(Nn, m->outp_w, m->outp_b, C, DH, LAT, T, st));      // C [LAT][T]
-    Q3C(TAP(Q3_DEC_PRETRANS, C, (size_t)LAT * T));
-    // D4 upsample stages: cur in C (segment decode: the latent columns [c0, T) copied out to F)
-    float* cur = C; float* o1 = A; float* o2 = B;
-    int L = T;
-    if (c0 > 0) {
-        HIPC(launch_copy_rows(C + c0, T, ws.bufF, T - c0, LAT, T - c0, st));
-        cur = ws.bufF; L = T - c0;
-    }
+    return Q3_OK;
+}
+// D4-D9, the convolutional stack: latent cur [LAT][L] (ws.bufC or ws.bufF) → ws.pcm [L*spf]
+q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, int L, hipStream_t st, float** taps, const CodecScope& scope) {
+    const int NPL = scope.planes;
+    const q3_config& c = m->cfg;
+    const int LAT = c.dec_latent;
+    auto TAP = [&](int id, const float* dev, size_t n) -> q3_status { return tap_out(taps, id, dev, n, st); };
+    float *A = ws.bufA, *B = ws.bufB, *C = ws.bufC;
+    // D4 upsample stages
     for (int i = 0; i < 2; ++i) {
         const UpW& U = m->up[i];
         float* upo = (cur == C) ? A : C;            // transconv output [LAT][L*r]
@@ -237,7 +248,6 @@ q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st
         cur = upo;
         Q3C(TAP(Q3_DEC_UP0 + i, cur, (size_t)LAT * L));
     }
-    (void)o1; (void)o2;
     // D5-D9. SnakeBeta is applied by the PRODUCER's epilogue (each element activated once, not once per
     // consuming output-channel tile): every tensor below exists as "raw" (residual / tap) and/or "act"
     // (= snake of the next consumer).
@@ -295,6 +305,37 @@ q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st
     // D9 final conv on the activated tensor + clamp
     HIPC(convk(xact, m->fin_w, m->fin_b, ws.pcm, Cc, 1, L, 7, 1, st, nullptr, nullptr, 2));
     return Q3_OK;
+}
+
+// frames already on device in ws.frames; result in ws.pcm. taps: host pointers or nullptr.
+// c0 = 0: whole-utterance decode, ws.pcm = [T*spf]. c0 > 0 (segment decode): the front (quantiser, pre_conv,
+// pre-transformer: everything with unbounded left context, and cheap) runs over all T frames, the convolutional
+// stack only over frames [c0, T), and ws.pcm = [(T-c0)*spf]; samples of frames >= c0 + CODEC_CTX_FRAMES are
+// identical to the whole-utterance decode (every kernel sums each output in a position-independent order).
+q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st, float** taps, int c0) {
+    const q3_config& c = m->cfg;
+    const CodecScope scope(m);
+    const int Q = c.dec_q_dim, LAT = c.dec_latent;
+    float *B = ws.bufB, *C = ws.bufC;
+    Q3C(codec_front_quant(m, ws, T, st));
+    Q3C(tap_out(taps, Q3_DEC_QUANT, B, (size_t)Q * T, st));
+    Q3C(codec_front_preconv(m, B, C, T, st));
+    Q3C(tap_out(taps, Q3_DEC_PRECONV, C, (size_t)LAT * T, st));
+    const float scale = (float)pow((double)c.dec_head_dim, -0.5);
+    Q3C(codec_front_transformer(m, ws, T, st, [&](int, float* q, float* k, float* v, float* ao) -> q3_status {
+        HIPC(launch_rope_c(q, k, ws.cs, ws.sn, c.dec_heads, c.dec_head_dim, T, st));
+        HIPC(launch_attn_c(q, k, v, ao, c.dec_heads, c.dec_head_dim, T, scale, st));
+        return Q3_OK;
+    }));
+    Q3C(tap_out(taps, Q3_DEC_PRETRANS, C, (size_t)LAT * T, st));
+    // the stack's input: the latent in C (segment decode: the latent columns [c0, T) copied out to F)
+    float* cur = C;
+    int L = T;
+    if (c0 > 0) {
+        HIPC(launch_copy_rows(C + c0, T, ws.bufF, T - c0, LAT, T - c0, st));
+        cur = ws.bufF; L = T - c0;
+    }
+    return codec_stack_dev(m, ws, cur, L, st, taps, scope);
 }
 
 extern "C" q3_status q3_decode_codes(q3_model* m, const uint32_t* frames_host, int n_frames, float* pcm_host, float** taps_host) {

@@ -2,6 +2,7 @@
 // Round 6: q3_engine.hip (3 800 lines: model, arena, KV pool, session, graph capture, batcher, test entry points) was split into
 //   q3_model.hip     errors, synthetic tensors, the weight manifest / arena, q3_model_* (create, set_tensor, finalize, KV pool API)
 //   q3_codec_run.hip device-memory cache, the vocoder pipeline (codec_decode_dev) and q3_decode_codes
+//   q3_codec_stream.hip the codec stream: the vocoder with per-row state, many rows per pass
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
 //                    streaming chunks, q3_session_run / decode / get
 //   q3_batcher.hip   continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
@@ -27,6 +28,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <string>
 #include <thread>
@@ -419,6 +421,7 @@ struct q3_session {
     q3::AqlProgram* aql = nullptr; int aql_mode = 0; bool aql_tried = false, aql_failed = false;
     bool precapture = false;       // q3_session_prefill captures the frame while the prompt's kernels run (set by the callers that will replay it)
     CodecWS cws;
+    q3_codec_stream* cstream = nullptr;   // q3_session_next_chunks, stream mode 1: per-row vocoder state (created on the first call)
     // overlapped segment decode (q3_session_run): vocoder segments run on their own stream while the frame loop continues
     hipStream_t dec_stream = nullptr; hipEvent_t dec_ev = nullptr;
     std::vector<CodecWS> par_ws; std::vector<hipStream_t> par_streams;     // q3_session_run: utterances vocoded side by side
@@ -461,6 +464,22 @@ Q3_HIDDEN void retile_bf16(const uint16_t* src, int N, int K, uint16_t* dst, int
 Q3_HIDDEN q3_status codec_reserve(const q3_model* m, CodecWS& ws, int T, int Tf = 0);
 Q3_HIDDEN int samples_per_frame(const q3_config& c);
 Q3_HIDDEN q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st, float** taps, int c0 = 0);
+// the stages of codec_decode_dev, for the codec stream (q3_codec_stream.hip). A CodecScope must be alive on the calling thread
+// while they run: it names the model (packed weights) and the bf16 planes (q3_model_set_codec_planes) of their launches.
+struct Q3_HIDDEN CodecScope { int planes; explicit CodecScope(const q3_model* m); ~CodecScope(); CodecScope(const CodecScope&) = delete; };
+using CodecAttnFn = std::function<q3_status(int layer, float* q, float* k, float* v, float* ao)>;
+Q3_HIDDEN q3_status codec_rope_table(const q3_config& c, int n, float* cs_dev, float* sn_dev);
+Q3_HIDDEN q3_status codec_front_quant(const q3_model* m, CodecWS& ws, int T, hipStream_t st);
+Q3_HIDDEN q3_status codec_front_preconv(const q3_model* m, const float* x, float* y, int L, hipStream_t st);
+Q3_HIDDEN q3_status codec_front_transformer(const q3_model* m, CodecWS& ws, int T, hipStream_t st, const CodecAttnFn& rope_attn);
+Q3_HIDDEN q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, int L, hipStream_t st, float** taps, const CodecScope& scope);
+// q3_codec_stream.hip
+// n new frames of one row, codes on the host OR the device; the first `skip` of them only catch the row's state up (no samples)
+struct CsPush { int row; int n; int skip; const uint32_t* host; const uint32_t* dev; float* pcm_host; };
+Q3_HIDDEN q3_status codec_stream_create(q3_model* m, int rows, int max_frames, hipStream_t st, q3_codec_stream** out);
+Q3_HIDDEN q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& pushes);
+Q3_HIDDEN int codec_stream_pos(const q3_codec_stream* cs, int row);
+Q3_HIDDEN void codec_stream_reset(q3_codec_stream* cs, int row);
 // q3_session.hip
 Q3_HIDDEN hipError_t sync_frames(q3_session* s);
 Q3_HIDDEN q3_status kv_reserve_row(q3_session* s, int b, int n_pos);

@@ -342,6 +342,16 @@ hipError_t launch_rmsnorm_c(const float* x, const float* w, float* y, int C, int
 hipError_t launch_rope_c(float* q, float* k, const float* cs, const float* sn, int nh, int hd, int L, hipStream_t st);
 hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* o, int nh, int hd, int L, float scale,
                          hipStream_t st);
+// codec stream (q3_codec_stream.hip): the front over the new columns of several rows, K / V from per-row caches
+struct AttnCsRow { const float* kv; int a0, e, qcol; };      // row cache [layer][K | V][QD][cap]; new frames [a0, e) at columns qcol ..
+struct ColCopy { const float* src; float* dst; int sp, dp; }; // one column: dst[c * dp] = src ? src[c * sp] : 0
+struct SegCopy { unsigned long long src, dst, n; };           // one run of floats
+hipError_t launch_rope_c_pos(float* q, float* k, const float* cs, const float* sn, const int* pos, int nh, int hd, int L, hipStream_t st);
+hipError_t launch_attn_cs(const float* q, float* o, const AttnCsRow* rows, int n_rows, int max_tiles, size_t layer_off, int nh, int hd,
+                          int N, int cap, float scale, hipStream_t st);
+hipError_t launch_copy_cols(const ColCopy* d, int n, int C, size_t src_off, size_t dst_off, hipStream_t st);
+hipError_t launch_copy_segs(const float* src, float* dst, const SegCopy* segs, int n_segs, size_t max_n, hipStream_t st);
+hipError_t launch_gather_frames(const uint32_t* const* src, uint32_t* dst, int n, hipStream_t st);
 hipError_t launch_silu_mul(const float* g, const float* u, float* y, int64_t n, hipStream_t st);
 hipError_t launch_rvq_embed(const uint32_t* frames, int n_frames, const float* first_cb, const float* const* rest_cbs,
                             float* first_out, float* rest_out, int cb_dim, int cb_size, hipStream_t st);

@@ -1273,6 +1273,60 @@ hipError_t launch_rope_c(float* q, float* k, const float* cs, const float* sn, i
     hipLaunchKernelGGL(k_rope_c, dim3((L + 255) / 256, nh * hd / 2, 2), dim3(256), 0, st, q, k, cs, sn, hd, L);
     return hipGetLastError();
 }
+// the same with the position of column t taken from pos[t] (codec stream: the columns of several rows side by side)
+__global__ __launch_bounds__(256) void k_rope_c_pos(float* q, float* k, const float* cs, const float* sn, const int* __restrict__ pos, int hd, int L) {
+    const int half = hd / 2;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int hi = blockIdx.y;                 // h*half + i
+    if (t >= L) return;
+    const int h = hi / half, i = hi % half, tp = pos[t];
+    const float c = cs[(size_t)tp * half + i], s = sn[(size_t)tp * half + i];
+    float* p = blockIdx.z == 0 ? q : k;
+    const size_t i1 = ((size_t)h * hd + i) * L + t, i2 = ((size_t)h * hd + i + half) * L + t;
+    const float x1 = p[i1], x2 = p[i2];
+    p[i1] = add_rn(mul_rn(x1, c), mul_rn(-x2, s));
+    p[i2] = add_rn(mul_rn(x2, c), mul_rn(x1, s));
+}
+hipError_t launch_rope_c_pos(float* q, float* k, const float* cs, const float* sn, const int* pos, int nh, int hd, int L, hipStream_t st) {
+    hipLaunchKernelGGL(k_rope_c_pos, dim3((L + 255) / 256, nh * hd / 2, 2), dim3(256), 0, st, q, k, cs, sn, pos, hd, L);
+    return hipGetLastError();
+}
+
+// ---- codec stream: descriptor-driven moves between the concatenated [C][n] tensors of a push and the rows' caches ----
+// column j of the list: dst[c * dp] = src ? src[c * sp] : 0 for c < C. One launch moves the columns of every row (K | V of a
+// layer into the caches, latent columns out of them, the pre_conv input with each row's two history columns).
+__global__ __launch_bounds__(256) void k_copy_cols(const ColCopy* __restrict__ d, int n, int C, size_t src_off, size_t dst_off) {
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63), c = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (j >= n || c >= C) return;
+    const ColCopy e = d[j];
+    e.dst[dst_off + (size_t)c * e.dp] = e.src ? e.src[src_off + (size_t)c * e.sp] : 0.0f;
+}
+hipError_t launch_copy_cols(const ColCopy* d, int n, int C, size_t src_off, size_t dst_off, hipStream_t st) {
+    if (n <= 0 || C <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_copy_cols, dim3((n + 63) / 64, (C + 3) / 4), dim3(256), 0, st, d, n, C, src_off, dst_off);
+    return hipGetLastError();
+}
+// segment s of the list: dst[s.dst + i] = src[s.src + i] for i < s.n (the wanted samples of every row into one staging buffer)
+__global__ __launch_bounds__(256) void k_copy_segs(const float* __restrict__ src, float* __restrict__ dst, const SegCopy* __restrict__ segs) {
+    const SegCopy s = segs[blockIdx.y];
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < s.n) dst[s.dst + i] = src[s.src + i];
+}
+hipError_t launch_copy_segs(const float* src, float* dst, const SegCopy* segs, int n_segs, size_t max_n, hipStream_t st) {
+    if (n_segs <= 0 || max_n == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_copy_segs, dim3((unsigned)((max_n + 255) / 256), n_segs), dim3(256), 0, st, src, dst, segs);
+    return hipGetLastError();
+}
+// frame j of the list ([16] codes) to dst[j][16]: the new frames of every row, from wherever each row keeps them on the device
+__global__ __launch_bounds__(256) void k_gather_frames(const uint32_t* const* __restrict__ src, uint32_t* __restrict__ dst, int n) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < n * 16) dst[t] = src[t >> 4][t & 15];
+}
+hipError_t launch_gather_frames(const uint32_t* const* src, uint32_t* dst, int n, hipStream_t st) {
+    if (n <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gather_frames, dim3((n * 16 + 255) / 256), dim3(256), 0, st, src, dst, n);
+    return hipGetLastError();
+}
 
 // causal MHA over [nh*hd][L] tensors, hd == 64: one wave per (query i, head h); lane = key index
 // inside a 64-key chunk for QKᵀ/softmax, lane = output dim for the accumulator.
@@ -1328,20 +1382,27 @@ typedef __attribute__((ext_vector_type(16))) float f32x16a_t;
 // merged in wave order at the end — a fixed order per query, so prefix decodes still reproduce the whole-utterance bits.
 // One wave per tile walked up to 20 key tiles alone: 95 us per layer at 640 frames.
 constexpr int ATC_NW = 4;
-__global__ __launch_bounds__(64 * ATC_NW) void k_attn_c_mfma(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                             float* __restrict__ o, int L, float scale) {
+// One (query tile qt, head h) of that kernel. CS = false is the whole-utterance decode: q / k / v / o are [nh*64][L] and every
+// pitch is L. CS = true is the codec stream (k_attn_cs): the queries are the NEW columns of a row — q and o have pitch qp and
+// hold query i at column i - qoff — while k and v are the row's cache of pitch kp, valid up to the row's end L; lanes whose
+// query lies before the row's first new frame qlo load zeros and store nothing. Only the addressing differs: the tile
+// alignment, the key-tile walk of each wave and the merge are the same statements, so a query gets the same bits.
+template <bool CS>
+__device__ __forceinline__ void attn_c_tile(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                            float* __restrict__ o, const int qp, const int kp, const int L, const int qt, const int h,
+                                            const int qlo, const int qoff, const float scale) {
     constexpr int VP = 33;
     __shared__ float vs_all[ATC_NW][64 * VP];                                  // per wave: V patch, then its partial O
     __shared__ float s_m[ATC_NW][32], s_l[ATC_NW][32];
     const int lane = threadIdx.x & 63, li = lane & 31, lk = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float* vs = vs_all[wave];
-    const int qt = (int)gridDim.x - 1 - (int)blockIdx.x, h = blockIdx.y;      // longest (last) query tiles first
     const int i0 = qt * 32, i = i0 + li;
-    const size_t hb = (size_t)h * 64 * L;
+    const size_t hb = (size_t)h * 64 * kp, hq = (size_t)h * 64 * qp;
+    const bool mine = i < L && (!CS || i >= qlo);                              // this lane's query is one the launch computes
     float qb[32];                                                              // B operand of step s: Q[i][d = 2s + lk]
 #pragma unroll
-    for (int s = 0; s < 32; ++s) qb[s] = i < L ? q[hb + (size_t)(2 * s + lk) * L + i] : 0.0f;
+    for (int s = 0; s < 32; ++s) qb[s] = mine ? q[hq + (size_t)(2 * s + lk) * qp + (i - qoff)] : 0.0f;
     f32x16a_t oacc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -1354,13 +1415,13 @@ __global__ __launch_bounds__(64 * ATC_NW) void k_attn_c_mfma(const float* __rest
         // V tile -> LDS (rows d, columns key); issued first so that it overlaps the score MFMAs
         float vr[32];
 #pragma unroll
-        for (int s = 0; s < 32; ++s) vr[s] = jok ? v[hb + (size_t)(2 * s + lk) * L + j] : 0.0f;
+        for (int s = 0; s < 32; ++s) vr[s] = jok ? v[hb + (size_t)(2 * s + lk) * kp + j] : 0.0f;
         f32x16a_t sacc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sacc[r] = 0.0f;
         float ka[32];
 #pragma unroll
-        for (int s = 0; s < 32; ++s) ka[s] = jok ? k[hb + (size_t)(2 * s + lk) * L + j] : 0.0f;
+        for (int s = 0; s < 32; ++s) ka[s] = jok ? k[hb + (size_t)(2 * s + lk) * kp + j] : 0.0f;
 #pragma unroll
         for (int s = 0; s < 32; ++s) sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[s], qb[s], sacc, 0, 0, 0);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      // the previous tile's patch reads are done
@@ -1406,7 +1467,7 @@ __global__ __launch_bounds__(64 * ATC_NW) void k_attn_c_mfma(const float* __rest
     if (lk == 0) { s_m[wave][li] = m; s_l[wave][li] = lw; }
     __syncthreads();
     // merge in wave order: thread (w', lane) handles d = w' * 16 + (lane >> 5) * 8 .. +8 of query li
-    if (i < L) {
+    if (mine) {
         float M = -INFINITY;
 #pragma unroll
         for (int w = 0; w < ATC_NW; ++w) M = fmaxf(M, s_m[w][li]);
@@ -1419,9 +1480,29 @@ __global__ __launch_bounds__(64 * ATC_NW) void k_attn_c_mfma(const float* __rest
             float acc = 0.0f;
 #pragma unroll
             for (int w = 0; w < ATC_NW; ++w) acc += vs_all[w][d * VP + li] * wg[w];
-            o[hb + (size_t)d * L + i] = acc / den;
+            o[hq + (size_t)d * qp + (i - qoff)] = acc / den;
         }
     }
+}
+__global__ __launch_bounds__(64 * ATC_NW) void k_attn_c_mfma(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                             float* __restrict__ o, int L, float scale) {
+    attn_c_tile<false>(q, k, v, o, L, L, L, (int)gridDim.x - 1 - (int)blockIdx.x, blockIdx.y, 0, 0, scale);      // longest (last) query tiles first
+}
+// Codec stream: the new columns of several rows against each row's K/V cache, grid (query tile, head, row). Row r's queries are
+// its frames [a0, e) (columns qcol .. of q / o, pitch N); its keys and values are frames [0, e) of its cache [layer][K | V][QD][cap].
+__global__ __launch_bounds__(64 * ATC_NW) void k_attn_cs(const float* __restrict__ q, float* __restrict__ o, const AttnCsRow* __restrict__ rows,
+                                                         size_t layer_off, int N, int cap, int QD, float scale) {
+    const AttnCsRow r = rows[blockIdx.z];
+    const int t0 = r.a0 >> 5, nt = ((r.e - 1) >> 5) - t0 + 1;                 // 32-query tiles at ABSOLUTE multiples of 32
+    if ((int)blockIdx.x >= nt) return;
+    const float* kc = r.kv + layer_off;
+    attn_c_tile<true>(q, kc, kc + (size_t)QD * cap, o, N, cap, r.e, t0 + nt - 1 - (int)blockIdx.x, blockIdx.y, r.a0, r.a0 - r.qcol, scale);
+}
+hipError_t launch_attn_cs(const float* q, float* o, const AttnCsRow* rows, int n_rows, int max_tiles, size_t layer_off, int nh, int hd,
+                          int N, int cap, float scale, hipStream_t st) {
+    if (hd != 64 || n_rows <= 0 || max_tiles <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_attn_cs, dim3(max_tiles, nh, n_rows), dim3(64 * ATC_NW), 0, st, q, o, rows, layer_off, N, cap, nh * hd, scale);
+    return hipGetLastError();
 }
 hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* o, int nh, int hd, int L, float scale,
                          hipStream_t st) {

@@ -685,6 +685,7 @@ q3_session::~q3_session() {
     if (graph) (void)hipGraphDestroy(graph);
     for (auto& ev : prof_pool) (void)hipEventDestroy(ev);
     for (auto st : par_streams) (void)hipStreamDestroy(st);
+    if (cstream) q3_codec_stream_free(cstream);          // (drops its own reference to the model: ours is still held)
     cws.release(); seg_ws.release();
     for (auto& w : par_ws) w.release();
     if (dec_ev) (void)hipEventDestroy(dec_ev);
@@ -1448,6 +1449,7 @@ extern "C" q3_status q3_session_generate(q3_session* s, int n_frames, int use_gr
 }
 
 static q3_status decode_range_on(q3_session* s, int b, int f0, int f1, hipStream_t st, float* pcm_host, size_t cap, size_t* n_samples);
+static q3_status chunk_decode_row(q3_session* s, int b, int avail, float* pcm_host, size_t cap, size_t* n_samples);
 
 // Streaming with several sequences in one session: the next chunk of row b (StreamingSession::next_chunk, lib.rs:1650-1759,
 // one per row). Rows advance in lockstep, so asking row after row costs the frames once: the first call generates them for
@@ -1469,6 +1471,15 @@ extern "C" q3_status q3_session_next_chunk_row(q3_session* s, int b, float* pcm_
     // an opened row whose text does not reach a whole chunk yet: nothing now (chunk boundaries stay those of the closed run)
     if (q.opened && !q.done && avail < chunk) { if (n_samples) *n_samples = 0; if (done) *done = 0; return Q3_OK; }
     if (avail <= 0) { if (n_samples) *n_samples = 0; if (done) *done = 1; return Q3_OK; }
+    Q3C(chunk_decode_row(s, b, avail, pcm_host, cap, n_samples));
+    q.stream_pos += avail;
+    if (done) *done = (q.done && q.stream_pos >= q.n_frames) ? 1 : 0;
+    return Q3_OK;
+}
+// the vocoder pass of one row's chunk: frames [stream_pos, stream_pos + avail) of row b in the session's stream mode
+static q3_status chunk_decode_row(q3_session* s, int b, int avail, float* pcm_host, size_t cap, size_t* n_samples) {
+    SeqInfo& q = s->seq[b];
+    const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
     const int spf = samples_per_frame(s->m->cfg);
     if (s->stream_mode == 1 && !q.icl) {
         // continuous mode (q3_session_set_stream_mode): left context re-run, sample-exact with the whole-utterance decode
@@ -1485,8 +1496,66 @@ extern "C" q3_status q3_session_next_chunk_row(q3_session* s, int b, float* pcm_
     } else {
         Q3C(decode_range_on(s, b, q.stream_pos, q.stream_pos + avail, s->stream, pcm_host, cap, n_samples));
     }
-    q.stream_pos += avail;
-    if (done) *done = (q.done && q.stream_pos >= q.n_frames) ? 1 : 0;
+    return Q3_OK;
+}
+
+// q3_session_next_chunk_row for every row in one call. The frames come first, exactly as the per-row calls in row order would
+// ask for them (generation does not depend on how it is cut into bursts, and a row's chunk is `chunk` frames until it ends and
+// the rest then: the boundaries are the per-row calls'). Then one vocoder pass: in stream mode 1 every row that is not ICL
+// goes through the session's codec stream (q3_codec_stream.hip) in ONE push — a chunk costs its own frames, not the utterance
+// so far, and the launches do not multiply with the rows; ICL rows and stream mode 0 keep the per-row context-free decode.
+extern "C" q3_status q3_session_next_chunks(q3_session* s, float* const* pcm_host, const size_t* cap, size_t* n_samples, int* done) {
+    if (!s) return set_err(Q3_INVALID_ARG, "null session");
+    if (!n_samples || !done) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks: n_samples and done are required");
+    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks: the model has no device");
+    HIPC(hipSetDevice(s->m->device));
+    if (!s->prefilled) Q3C(q3_session_prefill(s));
+    Q3C(refresh_codes(s));
+    const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
+    const int spf = samples_per_frame(s->m->cfg);
+    for (int b = 0; b < s->B; ++b) {
+        SeqInfo& q = s->seq[b];
+        while (!q.done && q.n_frames - q.stream_pos < chunk && (q.opened ? row_capacity(s, q) : session_remaining(s)) > 0) {
+            Q3C(q3_session_generate(s, chunk - (q.n_frames - q.stream_pos), 1));
+            Q3C(refresh_codes(s));
+        }
+    }
+    // what every row gets; refused as a whole before any row moves
+    std::vector<int> avail((size_t)s->B, 0);
+    std::vector<char> held((size_t)s->B, 0);
+    for (int b = 0; b < s->B; ++b) {
+        const SeqInfo& q = s->seq[b];
+        int a = std::min(q.n_frames - q.stream_pos, chunk);
+        held[(size_t)b] = q.opened && !q.done && a < chunk;          // an opened row whose text does not reach a whole chunk yet: nothing now
+        if (a < 0 || held[(size_t)b]) a = 0;
+        avail[(size_t)b] = a;
+        if (a > 0 && pcm_host && pcm_host[b] && (!cap || cap[b] < (size_t)a * spf))
+            return set_err(Q3_INVALID_ARG, "q3_session_next_chunks: pcm buffer of row %d too small", b);
+    }
+    std::vector<CsPush> pushes;
+    for (int b = 0; b < s->B; ++b) {
+        SeqInfo& q = s->seq[b];
+        const int a = avail[(size_t)b];
+        n_samples[b] = (size_t)a * spf;
+        if (a <= 0) continue;
+        if (s->stream_mode == 1 && !q.icl) {
+            if (!s->cstream) Q3C(codec_stream_create(s->m, s->B, s->max_frames, s->stream, &s->cstream));
+            // the row's state follows the row: behind it (q3_session_next_chunk_row moved the row on) the push catches up,
+            // ahead of it (another utterance's) it starts over
+            if (codec_stream_pos(s->cstream, b) > q.stream_pos) codec_stream_reset(s->cstream, b);
+            const int sp = codec_stream_pos(s->cstream, b);
+            pushes.push_back({b, q.stream_pos + a - sp, q.stream_pos - sp, nullptr, s->codes + ((size_t)b * s->max_frames + sp) * 16,
+                              pcm_host ? pcm_host[b] : nullptr});
+        } else {
+            Q3C(chunk_decode_row(s, b, a, pcm_host ? pcm_host[b] : nullptr, cap ? cap[b] : 0, nullptr));
+        }
+    }
+    if (!pushes.empty()) Q3C(codec_stream_push(s->cstream, pushes));
+    for (int b = 0; b < s->B; ++b) {
+        SeqInfo& q = s->seq[b];
+        q.stream_pos += avail[(size_t)b];
+        done[b] = held[(size_t)b] ? 0 : (avail[(size_t)b] <= 0 || (q.done && q.stream_pos >= q.n_frames)) ? 1 : 0;
+    }
     return Q3_OK;
 }
 

@@ -52,6 +52,13 @@ pub mod ffi {
         pub fn q3_session_run(s: *mut c_void, use_graph: i32, pcm: *mut *mut f32, cap: *const usize, n: *mut usize, t: *mut Q3Timing) -> i32;
         pub fn q3_session_next_chunk(s: *mut c_void, pcm: *mut f32, cap: usize, n: *mut usize, done: *mut i32) -> i32;
         pub fn q3_session_next_chunk_row(s: *mut c_void, b: i32, pcm: *mut f32, cap: usize, n: *mut usize, done: *mut i32) -> i32;
+        pub fn q3_session_next_chunks(s: *mut c_void, pcm: *const *mut f32, cap: *const usize, n: *mut usize, done: *mut i32) -> i32;
+        pub fn q3_codec_stream_create(m: *mut c_void, rows: i32, max_frames: i32, out: *mut *mut c_void) -> i32;
+        pub fn q3_codec_stream_free(cs: *mut c_void);
+        pub fn q3_codec_stream_reset(cs: *mut c_void, row: i32) -> i32;
+        pub fn q3_codec_stream_pos(cs: *mut c_void, row: i32, n_frames: *mut i32) -> i32;
+        pub fn q3_codec_stream_push(cs: *mut c_void, n_rows: i32, rows: *const i32, frames: *const *const u32, n_frames: *const i32,
+                                    pcm: *const *mut f32, cap: *const usize) -> i32;
         pub fn q3_session_create_reserved(m: *mut c_void, reqs: *const Q3Request, batch: i32, frame_budget: i32, prompt_budget: i32, out: *mut *mut c_void) -> i32;
         pub fn q3_session_replace(s: *mut c_void, b: i32, req: *const Q3Request) -> i32;
         pub fn q3_session_open_text(s: *mut c_void, b: i32) -> i32;
