@@ -277,6 +277,24 @@ q3_status q3_batcher_poll(q3_batcher* b, int64_t ticket, int* state, int* n_fram
 /* Copy a finished ticket's results out ([n_frames][16] u32; n_samples f32) and release it. A FAILED ticket returns its
  * status (message in q3_last_error) and is released too. */
 q3_status q3_batcher_fetch(q3_batcher* b, int64_t ticket, uint32_t* codes_host, int cap_frames, float* pcm_host, size_t cap_samples);
+/* Streamed tickets: the audio is delivered while the request runs. q3_batcher_submit_streamed queues like q3_batcher_submit
+ * (rows of any prompt kind; an ICL request whose n_ref + max_length exceeds frame_budget + prompt_budget is Q3_UNSUPPORTED).
+ * At the end of every q3_batcher_step the frames of that step go to the batcher's decode worker as ONE job over every streamed
+ * row, which pushes them through a block-allocated codec stream (one stream row per slot, q3_codec_stream_create_blocked;
+ * Q3_BAT_STREAM_BLOCK_FRAMES, default 128, and Q3_BAT_STREAM_MAX_BLOCKS, default 0 = no limit, are read by q3_batcher_create);
+ * the step does not wait for it. The concatenation of what q3_batcher_read returns for a ticket is, bit for bit, the PCM the
+ * same request gives with want_pcm = 1; its codes are the same too.
+ * q3_batcher_read never blocks: it copies up to cap_samples (any count) of the ticket's samples that have landed and were not
+ * read yet; *done = 1 once the ticket has finished and its last sample has been read (0 samples, done 0 before the first step).
+ * An unknown ticket or one not submitted as streamed is Q3_INVALID_ARG; a FAILED ticket returns its status — a push the
+ * stream refused (Q3_OOM under the block limit) or that failed fails the tickets it could not serve, each with its message,
+ * and the others neither lose nor repeat a sample.
+ * q3_batcher_fetch on a streamed ticket waits for its outstanding jobs, returns the codes and releases it (unread samples are
+ * dropped); a non-null pcm_host is Q3_INVALID_ARG. q3_batcher_poll reports the samples that have landed.
+ * q3_batcher_stream_info: the block figures of that stream as of the last job (q3_codec_stream_info). */
+q3_status q3_batcher_submit_streamed(q3_batcher* b, const q3_request* req, int64_t* ticket);
+q3_status q3_batcher_read(q3_batcher* b, int64_t ticket, float* pcm_host, size_t cap_samples, size_t* n_samples, int* done);
+q3_status q3_batcher_stream_info(q3_batcher* b, int* block_frames, size_t* block_bytes, int* blocks_total, int* blocks_in_use, int* blocks_peak);
 
 /* Chunk decode mode of q3_session_next_chunk. 0 (default) = each chunk decoded as an independent utterance, exactly
  * as the reference does (lib.rs:1755-1758: audible seams, every chunk restarts from zero padding). 1 = continuous:
@@ -412,6 +430,19 @@ q3_status q3_codec_stream_pos(q3_codec_stream* cs, int row, int* n_frames);
  * frame 0: their state is not trusted half-written, push them again from their first frame. */
 q3_status q3_codec_stream_push(q3_codec_stream* cs, int n_rows, const int* rows, const uint32_t* const* frames_host,
                                const int* n_frames, float* const* pcm_host, const size_t* cap);
+/* Block-allocated state: a row's K / V and latent live in blocks of block_frames frames (a positive multiple of 32, otherwise
+ * Q3_INVALID_ARG), taken from the stream's free list when a push reaches them and returned by q3_codec_stream_reset and the free of
+ * the stream — a row holds what its frames need, not max_frames. max_blocks bounds the blocks in use (0 = no bound): a push that
+ * would exceed it is refused as a whole with Q3_OOM before any row's state or position changes. Same samples, bit for bit. */
+q3_status q3_codec_stream_create_blocked(q3_model* m, int rows, int max_frames, int block_frames, int max_blocks, q3_codec_stream** out);
+/* block figures (any pointer may be NULL): frames and bytes per block, blocks allocated so far, in use now, and the most that
+ * were ever in use at once. A stream of q3_codec_stream_create reports block_frames 0 (and zeros). */
+q3_status q3_codec_stream_info(q3_codec_stream* cs, int* block_frames, size_t* block_bytes, int* blocks_total, int* blocks_in_use,
+                               int* blocks_peak);
+/* state-only frames: the front runs over n_frames frames of a row at frame 0 (any other position: Q3_INVALID_ARG) and fills its
+ * caches; no stack runs, no samples. Later pushes to the row give the samples of q3_decode_codes(primed | pushed) with the
+ * first n_frames * samples_per_frame cut — a voice-clone prompt's reference frames (lib.rs:1022-1041). */
+q3_status q3_codec_stream_prime(q3_codec_stream* cs, int row, const uint32_t* frames_host, int n_frames);
 /* codes_to_tensor (lib.rs:1417-1431): [n][16] u32 → [16][n] i64 (host helper) */
 void      q3_codes_to_tensor(const uint32_t* frames, int n_frames, int64_t* out);
 

@@ -104,6 +104,9 @@ SYMBOLS = {
     "q3_session_next_chunk_row": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_size_t, P(ctypes.c_size_t), P(c_int)]),
     "q3_session_next_chunks": (c_int, [c_void_p, P(c_void_p), P(ctypes.c_size_t), P(ctypes.c_size_t), P(c_int)]),
     "q3_codec_stream_create": (c_int, [c_void_p, c_int, c_int, P(c_void_p)]),
+    "q3_codec_stream_create_blocked": (c_int, [c_void_p, c_int, c_int, c_int, c_int, P(c_void_p)]),
+    "q3_codec_stream_info": (c_int, [c_void_p, P(c_int), P(ctypes.c_size_t), P(c_int), P(c_int), P(c_int)]),
+    "q3_codec_stream_prime": (c_int, [c_void_p, c_int, c_void_p, c_int]),
     "q3_codec_stream_free": (None, [c_void_p]),
     "q3_codec_stream_reset": (c_int, [c_void_p, c_int]),
     "q3_codec_stream_pos": (c_int, [c_void_p, c_int, P(c_int)]),
@@ -112,6 +115,9 @@ SYMBOLS = {
     "q3_batcher_create": (c_int, [c_void_p, c_int, c_int, c_int, P(c_void_p)]),
     "q3_batcher_free": (None, [c_void_p]),
     "q3_batcher_submit": (c_int, [c_void_p, c_void_p, c_int, P(ctypes.c_int64)]),
+    "q3_batcher_submit_streamed": (c_int, [c_void_p, c_void_p, P(ctypes.c_int64)]),
+    "q3_batcher_read": (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_size_t, P(ctypes.c_size_t), P(c_int)]),
+    "q3_batcher_stream_info": (c_int, [c_void_p, P(c_int), P(ctypes.c_size_t), P(c_int), P(c_int), P(c_int)]),
     "q3_batcher_step": (c_int, [c_void_p, c_int, c_int, P(c_int), P(c_int), P(c_int)]),
     "q3_batcher_poll": (c_int, [c_void_p, ctypes.c_int64, P(c_int), P(c_int), P(ctypes.c_size_t)]),
     "q3_batcher_fetch": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, ctypes.c_size_t]),

@@ -413,6 +413,7 @@ class Batcher:
         h = ctypes.c_void_p()
         check(lib.q3_batcher_create(model._h, int(slots), int(frame_budget), int(prompt_budget), ctypes.byref(h)))
         self._h = h
+        self._streamed = set()                      # tickets of submit_streamed (their samples leave through read, not fetch)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -428,6 +429,32 @@ class Batcher:
         check(lib.q3_batcher_submit(self._h, ctypes.byref(r), 1 if want_pcm else 0, ctypes.byref(t)))
         return int(t.value)
 
+    def submit_streamed(self, utt: Utterance) -> int:
+        """Queue one request whose audio is delivered while it runs (`read`); returns its ticket."""
+        keep = []
+        r = CRequest(); fill_request(r, utt, self.options, keep)
+        t = ctypes.c_int64()
+        check(lib.q3_batcher_submit_streamed(self._h, ctypes.byref(r), ctypes.byref(t)))
+        self._streamed.add(int(t.value))
+        return int(t.value)
+
+    def read(self, ticket: int, max_samples: Optional[int] = None) -> Tuple[np.ndarray, bool]:
+        """(samples of a streamed ticket that have landed and were not read yet — at most max_samples —, done). Never blocks;
+        done is True once the ticket has finished and its last sample has been read. A failed ticket raises its error."""
+        if max_samples is None:
+            max_samples = max(self.poll(ticket)[2], 1)      # every landed sample (more may land before the read: they come next time)
+        buf = np.zeros(int(max_samples), np.float32)
+        n = ctypes.c_size_t(); d = ctypes.c_int()
+        check(lib.q3_batcher_read(self._h, int(ticket), buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(n), ctypes.byref(d)))
+        return buf[:n.value].copy(), bool(d.value)
+
+    def stream_info(self) -> dict:
+        """Block figures of the streamed tickets' codec stream (as CodecStream.info), as of the last decode job."""
+        bf = ctypes.c_int(); bb = ctypes.c_size_t(); tot = ctypes.c_int(); use = ctypes.c_int(); peak = ctypes.c_int()
+        check(lib.q3_batcher_stream_info(self._h, ctypes.byref(bf), ctypes.byref(bb), ctypes.byref(tot), ctypes.byref(use), ctypes.byref(peak)))
+        return {"block_frames": bf.value, "block_bytes": bb.value, "blocks_total": tot.value, "blocks_in_use": use.value,
+                "blocks_peak": peak.value}
+
     def step(self, n_frames: int = 32, use_graph: bool = True) -> Tuple[int, int, int]:
         """One scheduling round: (rows running, requests queued, tickets finished in this call)."""
         a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
@@ -442,9 +469,12 @@ class Batcher:
     def fetch(self, ticket: int) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """(codes [n][16] u32, PCM or None) of a finished ticket, which is released; a failed ticket raises its error."""
         st, n, ns = self.poll(ticket)
+        if int(ticket) in self._streamed:
+            ns = 0                                    # a streamed ticket's samples go through read
         codes = np.zeros((n, 16), np.uint32); pcm = np.zeros(ns, np.float32)
         check(lib.q3_batcher_fetch(self._h, int(ticket), codes.ctypes.data_as(ctypes.c_void_p), n,
                                    pcm.ctypes.data_as(ctypes.c_void_p) if ns else None, ns))
+        self._streamed.discard(int(ticket))          # released by the library (a call that raised above keeps it)
         return codes, (pcm if ns else None)
 
     def run_all(self, utts: Sequence[Utterance], want_pcm: bool = True, poll_frames: int = 32, use_graph: bool = True):
@@ -832,6 +862,39 @@ class Qwen3TTS:
             s.close()
         return codes, pcm, frames, wall
 
+    def synthesize_continuous_streaming(self, utts: Sequence[Utterance], options=None, slots: int = 8, poll_frames: int = 10,
+                                        on_audio=None, use_graph: bool = True):
+        """Continuous batching with streamed audio (Batcher.submit_streamed): every request's samples are handed to
+        on_audio(index, samples, done) as they land — after each step of poll_frames frames —, `done` with a request's last
+        piece (which may be empty). The pieces of a request concatenate to the PCM synthesize_continuous gives it. Returns
+        the codes per request."""
+        o = options or SynthesisOptions()
+        utts = list(utts)
+        budget = max((u.max_length if u.max_length is not None else (u.options or o).max_length) for u in utts)
+        prompt = max((0 if u.instruct_ids is None else len(u.instruct_ids)) + (0 if u.ref_codes is None else int(np.asarray(u.ref_codes).reshape(-1, 16).shape[0])) + 16 for u in utts)
+        bt = Batcher(self, slots=min(slots, max(len(utts), 1)), frame_budget=budget, prompt_budget=prompt, options=o)
+        try:
+            tickets = [bt.submit_streamed(u) for u in utts]
+            open_ = set(range(len(utts)))
+
+            def drain():
+                for i in sorted(open_):
+                    samples, done = bt.read(tickets[i])
+                    if samples.size or done:
+                        if on_audio is not None:
+                            on_audio(i, samples, done)
+                    if done:
+                        open_.discard(i)
+            while True:
+                running, queued, _ = bt.step(poll_frames, use_graph)
+                drain()
+                if running == 0 and queued == 0:
+                    break
+            drain()                                  # (the step that found nothing running waited for the last samples)
+            return [bt.fetch(t)[0] for t in tickets]
+        finally:
+            bt.close()
+
     def synthesize_streaming(self, text_ids, speaker: Speaker, language: Language, options=None,
                              continuous: bool = False) -> StreamingSession:
         return StreamingSession(self, Utterance(text_ids, speaker, language), options or SynthesisOptions(), continuous)
@@ -873,10 +936,11 @@ class Qwen3TTS:
         check(lib.q3_decode_codes(self._h, c.ctypes.data_as(ctypes.c_void_p), c.shape[0], out.ctypes.data_as(ctypes.c_void_p), tp))
         return AudioBuffer(out)
 
-    def codec_stream(self, rows: int, max_frames: int) -> "CodecStream":
+    def codec_stream(self, rows: int, max_frames: int, block_frames: int = 0, max_blocks: int = 0) -> "CodecStream":
         """The vocoder with per-row state (q3_codec_stream_*): frames are appended to rows and decoded as they come, many rows
-        per pass; a row's samples are those of decode_codes over everything it has been given."""
-        return CodecStream(self, rows, max_frames)
+        per pass; a row's samples are those of decode_codes over everything it has been given. block_frames > 0 (a multiple of
+        32): the state is allocated in blocks of that many frames as a row grows, at most max_blocks of them (0 = no bound)."""
+        return CodecStream(self, rows, max_frames, block_frames, max_blocks)
 
     def frame_embed(self, sem_token: int, codes15, text_add: np.ndarray) -> np.ndarray:
         c = np.ascontiguousarray(codes15, dtype=np.uint32); t = np.ascontiguousarray(text_add, dtype=np.float32)
@@ -887,10 +951,26 @@ class Qwen3TTS:
 
 
 class CodecStream:
-    def __init__(self, model: "Qwen3TTS", rows: int, max_frames: int):
+    def __init__(self, model: "Qwen3TTS", rows: int, max_frames: int, block_frames: int = 0, max_blocks: int = 0):
         self.model = model; self.rows = int(rows); self.max_frames = int(max_frames)
         self._h = ctypes.c_void_p()
-        check(lib.q3_codec_stream_create(model._h, self.rows, self.max_frames, ctypes.byref(self._h)))
+        if block_frames or max_blocks:
+            check(lib.q3_codec_stream_create_blocked(model._h, self.rows, self.max_frames, int(block_frames), int(max_blocks),
+                                                     ctypes.byref(self._h)))
+        else:
+            check(lib.q3_codec_stream_create(model._h, self.rows, self.max_frames, ctypes.byref(self._h)))
+
+    def prime(self, row: int, codes: np.ndarray):
+        """State-only frames for a row at frame 0 (a voice-clone prompt's reference codes): the caches are filled, no samples."""
+        c = np.ascontiguousarray(codes, dtype=np.uint32).reshape(-1, 16)
+        check(lib.q3_codec_stream_prime(self._h, int(row), c.ctypes.data_as(ctypes.c_void_p), c.shape[0]))
+
+    def info(self) -> dict:
+        """Block figures: block_frames (0 = whole-row state), block_bytes, blocks_total, blocks_in_use, blocks_peak."""
+        bf = ctypes.c_int(); bb = ctypes.c_size_t(); tot = ctypes.c_int(); use = ctypes.c_int(); peak = ctypes.c_int()
+        check(lib.q3_codec_stream_info(self._h, ctypes.byref(bf), ctypes.byref(bb), ctypes.byref(tot), ctypes.byref(use), ctypes.byref(peak)))
+        return {"block_frames": bf.value, "block_bytes": bb.value, "blocks_total": tot.value, "blocks_in_use": use.value,
+                "blocks_peak": peak.value}
 
     def push(self, frames: dict) -> dict:
         """{row: codes [n][16]} -> {row: samples [n * samples_per_frame]}: every row of the call in one decode pass."""

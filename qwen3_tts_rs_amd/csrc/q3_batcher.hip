@@ -129,7 +129,18 @@ struct BatTicket {
     q3_status st = Q3_OK; std::string err;
     // vocoded by the batcher's decode worker (below): queued / running there until dec_done; the row it ran in is long refilled
     bool decoding = false; std::atomic<bool> dec_done{false}; q3_status dec_st = Q3_OK; std::string dec_err;
+    // A streamed ticket (q3_batcher_submit_streamed): its frames go to the worker step by step (StreamPart), its samples land in
+    // spcm and leave through q3_batcher_read. The host thread owns streamed / s_pushed / s_ended; the worker owns s_all / s_deliv;
+    // s_pending, spcm, s_read, s_failed, s_st and s_err are shared under the worker's mutex.
+    bool streamed = false, s_started = false, s_ended = false; int s_pushed = 0;          // frames handed to the worker so far; the row has been collected
+    int s_pending = 0; std::vector<float> spcm; size_t s_read = 0;     // parts queued or running; landed samples; samples read
+    bool s_failed = false; q3_status s_st = Q3_OK; std::string s_err;
+    std::vector<uint32_t> s_all; int s_deliv = 0;                      // reference | generated frames seen so far; frames whose samples landed
 };
+// frames [f0, f0 + n) of a streamed ticket for the stream row of its slot: `first` resets the row (and primes it with the ticket's
+// reference frames), `last` gives the row's blocks back once the samples have landed
+struct StreamPart { BatTicket* t; int row; std::vector<uint32_t> frames; bool first, last; };
+struct DecJob { BatTicket* whole = nullptr; std::vector<StreamPart> parts; };      // a whole-ticket decode OR one step's stream parts
 struct q3_batcher {
     q3_model* m = nullptr; int slots = 0, frame_budget = 0, prompt_budget = 0, chunk_frames = 0;
     q3_session* s = nullptr;
@@ -148,6 +159,9 @@ struct q3_batcher {
         int64_t id = -1; std::thread thr; q3_session* side = nullptr; q3_status st = Q3_OK; std::string err; int limit = 0;
     } stage;
     std::unique_ptr<struct BatDecoder> dec;           // the decode worker of finished rows (below)
+    // streamed tickets: the parts of the step in progress (one job at its end), the stream's shape (environment, read at create)
+    std::vector<StreamPart> sparts; int n_streamed = 0;
+    int s_block_frames = 128, s_max_blocks = 0;
 };
 // Round 6: a finished row's vocoder no longer stalls the session either. bat_collect used to decode the row's samples on the session's
 // own stream before the row could be refilled — every live row stood still for ~20 ms per 640 frames. The codes are on the host
@@ -155,17 +169,45 @@ struct q3_batcher {
 // idled and refilled at once, and the ticket counts as RUNNING until its samples have landed (poll; fetch waits for them). Same
 // kernels on the same codes as q3_session_decode: the same samples. ICL rows (reference frames prepended and cut, lib.rs:1022-1041)
 // and Q3_BAT_SYNC_DECODE=1 keep the synchronous decode.
+// Streamed tickets use the same worker, stream and queue: at the end of a step its frames are on the host and go in as ONE job
+// that covers every streamed row; the worker pushes them through a block-allocated codec stream (q3_codec_stream.hip, one stream
+// row per slot) and the samples land in the tickets' buffers. Jobs run in order, so the last part of a slot's previous owner
+// precedes the first part of its next one.
 struct BatDecoder {
-    std::thread thr; std::mutex mu; std::condition_variable cv, cv_done; std::deque<BatTicket*> q; bool stop = false;
+    std::thread thr; std::mutex mu; std::condition_variable cv, cv_done; std::deque<DecJob> q; bool stop = false;
     hipStream_t stream = nullptr; CodecWS ws;
+    q3_codec_stream* cs = nullptr;                    // the streamed tickets' vocoder state (created by the first stream job)
+    int info_bf = 0, info_total = 0, info_use = 0, info_peak = 0; size_t info_bytes = 0;      // its figures after the last job (under mu)
+    // Q3_BAT_STREAM_STATS=1 (development aid): what the worker did, printed when the batcher is freed
+    long st_jobs = 0, st_pushes = 0, st_frames = 0, st_depth_sum = 0; int st_depth_max = 0; double st_busy_ms = 0;
 };
 static void decoder_main(q3_batcher* b);
-static void decoder_push(q3_batcher* b, BatTicket* t) {
+static void decoder_enqueue(q3_batcher* b, DecJob&& j) {
     BatDecoder& d = *b->dec;
     std::lock_guard<std::mutex> g(d.mu);
     if (!d.thr.joinable()) d.thr = std::thread(decoder_main, b);
-    d.q.push_back(t);
+    for (StreamPart& p : j.parts) p.t->s_pending++;
+    d.q.push_back(std::move(j));
+    d.st_depth_sum += (long)d.q.size(); if ((int)d.q.size() > d.st_depth_max) d.st_depth_max = (int)d.q.size();
     d.cv.notify_one();
+}
+static void decoder_push(q3_batcher* b, BatTicket* t) { DecJob j; j.whole = t; decoder_enqueue(b, std::move(j)); }
+// the parts gathered since the last flush become one job; the step does not wait for it
+static void stream_flush(q3_batcher* b) {
+    if (b->sparts.empty()) return;
+    DecJob j; j.parts = std::move(b->sparts); b->sparts.clear();
+    decoder_enqueue(b, std::move(j));
+}
+// a collected streamed ticket whose parts have all been served is DONE (or FAILED with the worker's reason)
+static void stream_settle(q3_batcher* b, BatTicket& t, bool wait) {
+    if (!t.streamed) return;
+    stream_flush(b);
+    BatDecoder& d = *b->dec;
+    std::unique_lock<std::mutex> lk(d.mu);
+    if (wait) d.cv_done.wait(lk, [&] { return t.s_pending == 0; });
+    if (t.state != Q3_TICKET_RUNNING || t.row >= 0) return;
+    if (t.s_failed) { t.state = Q3_TICKET_FAILED; t.st = t.s_st; t.err = t.s_err; }
+    else if (t.s_ended && t.s_pending == 0) t.state = Q3_TICKET_DONE;
 }
 static void ticket_wait_decode(q3_batcher* b, BatTicket& t) {
     if (!t.decoding) return;
@@ -185,7 +227,12 @@ static void decoder_stop(q3_batcher* b) {
         d.stop = true; d.cv.notify_all();
     }
     if (d.thr.joinable()) d.thr.join();
-    if (d.stream) { (void)hipStreamSynchronize(d.stream); (void)hipStreamDestroy(d.stream); d.stream = nullptr; }
+    if (d.st_jobs > 0 && getenv("Q3_BAT_STREAM_STATS"))
+        fprintf(stderr, "[q3 batcher stream] %ld stream jobs (one per step), %ld pushes, %ld frames through the front, worker busy %.1f ms (%.2f ms per job), "
+                        "queue depth at enqueue: max %d\n", d.st_jobs, d.st_pushes, d.st_frames, d.st_busy_ms, d.st_busy_ms / d.st_jobs, d.st_depth_max);
+    if (d.stream) (void)hipStreamSynchronize(d.stream);
+    if (d.cs) { q3_codec_stream_free(d.cs); d.cs = nullptr; }
+    if (d.stream) { (void)hipStreamDestroy(d.stream); d.stream = nullptr; }
     d.ws.release();
 }
 static q3_status decoder_run(q3_batcher* b, BatTicket& t) {
@@ -201,16 +248,101 @@ static q3_status decoder_run(q3_batcher* b, BatTicket& t) {
     HIPC(hipStreamSynchronize(d.stream));
     return Q3_OK;
 }
+// One step's parts of the streamed tickets. Parts are pushed together, a row at most once per push (a slot whose owner changed
+// inside the step has two parts: the push is cut there). A row's push starts at the stream row's position: normally the part's
+// own frames; after a failed push put the row back to frame 0, everything from the ticket's first (reference) frame, with `skip`
+// set to what was already delivered — no sample is lost or repeated. A joint push that is refused or fails is repeated row by
+// row, and the tickets whose own push fails are FAILED with its message.
+static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
+    BatDecoder& d = *b->dec;
+    const auto t_job = std::chrono::steady_clock::now();
+    const q3_model* m = b->m;
+    const int spf = samples_per_frame(m->cfg);
+    q3_status st0 = hipSetDevice(m->device) == hipSuccess ? Q3_OK : set_err(Q3_HIP_ERROR, "hipSetDevice");
+    if (st0 == Q3_OK && !d.stream && hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking) != hipSuccess) st0 = set_err(Q3_HIP_ERROR, "hipStreamCreateWithFlags");
+    if (st0 == Q3_OK && !d.cs)
+        st0 = codec_stream_create(b->m, b->slots, b->frame_budget + b->prompt_budget, d.stream, &d.cs, b->s_block_frames, b->s_max_blocks);
+    auto fail = [&](BatTicket& t, q3_status st, const char* msg) {
+        std::lock_guard<std::mutex> g(d.mu);
+        if (!t.s_failed) { t.s_failed = true; t.s_st = st; t.s_err = msg; }
+    };
+    struct Out { StreamPart* p; int n_new; std::vector<float> pcm; };
+    auto is_failed = [&](BatTicket& t) { std::lock_guard<std::mutex> g(d.mu); return t.s_failed; };
+    // the samples of a served part land; a failed ticket's row and a finished one's give their blocks back
+    auto land = [&](Out& o) {
+        BatTicket& t = *o.p->t;
+        t.s_deliv += o.n_new;
+        std::lock_guard<std::mutex> g(d.mu);
+        t.spcm.insert(t.spcm.end(), o.pcm.begin(), o.pcm.end());
+    };
+    size_t i = 0;
+    while (i < parts.size()) {
+        // the next group: parts up to the first repeated row
+        std::vector<Out> grp; std::vector<char> seen((size_t)b->slots, 0);
+        for (; i < parts.size() && !seen[(size_t)parts[i].row]; ++i) {
+            StreamPart& p = parts[i]; BatTicket& t = *p.t;
+            seen[(size_t)p.row] = 1;
+            if (st0 != Q3_OK) { fail(t, st0, q3_last_error()); continue; }
+            if (p.first) { codec_stream_reset(d.cs, p.row); t.s_all = t.req.ref_codes; t.s_deliv = 0; }
+            if (is_failed(t)) continue;
+            t.s_all.insert(t.s_all.end(), p.frames.begin(), p.frames.end());
+            grp.push_back({&p, (int)(p.frames.size() / 16), {}});
+        }
+        auto push_of = [&](Out& o) {
+            BatTicket& t = *o.p->t;
+            const int n_ref = (int)(t.req.ref_codes.size() / 16), sp = codec_stream_pos(d.cs, o.p->row);
+            o.pcm.resize((size_t)o.n_new * spf);
+            return CsPush{o.p->row, n_ref + t.s_deliv + o.n_new - sp, n_ref + t.s_deliv - sp, t.s_all.data() + (size_t)sp * 16, nullptr, o.pcm.data()};
+        };
+        std::vector<CsPush> P;
+        for (Out& o : grp) if (o.n_new > 0) P.push_back(push_of(o));
+        bool joint_ok = true;
+        if (!P.empty()) { joint_ok = codec_stream_push(d.cs, P) == Q3_OK; d.st_pushes++; for (const CsPush& p : P) d.st_frames += p.n; }
+        // A refused joint push (Q3_OOM under max_blocks) is repeated row by row, the rows that need no new block first and then the
+        // others by the blocks they already hold, fewest first: under a block limit the ticket that fails is the one whose row
+        // holds the most — a long ticket does not starve a short one that arrived after it took the last free block.
+        if (!joint_ok)
+            std::stable_sort(grp.begin(), grp.end(), [&](const Out& x, const Out& y) {
+                auto key = [&](const Out& o) {
+                    if (o.n_new <= 0) return std::make_pair(0, 0);
+                    int held = 0, need = 0;
+                    codec_stream_blocks(d.cs, o.p->row, (int)(o.p->t->req.ref_codes.size() / 16) + o.p->t->s_deliv + o.n_new, &held, &need);
+                    return std::make_pair(need > 0 ? 1 : 0, need > 0 ? held : 0);
+                };
+                return key(x) < key(y);
+            });
+        for (Out& o : grp) {
+            BatTicket& t = *o.p->t;
+            if (!joint_ok && o.n_new > 0) {            // alone: this row's own push decides about this ticket
+                const q3_status st = codec_stream_push(d.cs, {push_of(o)});
+                if (st != Q3_OK) { fail(t, st, q3_last_error()); codec_stream_reset(d.cs, o.p->row); continue; }
+            }
+            land(o);
+            if (o.p->last) codec_stream_reset(d.cs, o.p->row);
+        }
+    }
+    int bf = 0, tot = 0, use = 0, peak = 0; size_t bytes = 0;
+    if (d.cs) (void)q3_codec_stream_info(d.cs, &bf, &bytes, &tot, &use, &peak);
+    {
+        std::lock_guard<std::mutex> g(d.mu);
+        d.info_bf = bf; d.info_bytes = bytes; d.info_total = tot; d.info_use = use; d.info_peak = peak;
+        for (StreamPart& p : parts) p.t->s_pending--;
+        d.st_jobs++; d.st_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_job).count();
+    }
+    d.cv_done.notify_all();
+}
 static void decoder_main(q3_batcher* b) {
     BatDecoder& d = *b->dec;
     for (;;) {
-        BatTicket* t = nullptr;
+        DecJob job;
         {
             std::unique_lock<std::mutex> lk(d.mu);
             d.cv.wait(lk, [&] { return d.stop || !d.q.empty(); });
             if (d.q.empty()) return;                 // stop, and nothing left to decode
-            t = d.q.front(); d.q.pop_front();
+            job = std::move(d.q.front()); d.q.pop_front();
         }
+        if (!job.whole) { decoder_stream_job(b, job.parts); continue; }
+        BatTicket* t = job.whole;
         const q3_status st = decoder_run(b, *t);
         t->dec_st = st;
         if (st != Q3_OK) t->dec_err = q3_last_error();
@@ -278,6 +410,17 @@ extern "C" q3_status q3_batcher_create(q3_model* m, int slots, int frame_budget,
     b->m = m; b->slots = slots; b->frame_budget = frame_budget; b->prompt_budget = prompt_budget;
     b->owner.assign(slots, -1); b->commit.assign(slots, 0);
     b->dec.reset(new BatDecoder());
+    // the streamed tickets' codec stream: frames per block (a multiple of 32, default 128) and the block limit (default none)
+    if (const char* e = getenv("Q3_BAT_STREAM_BLOCK_FRAMES")) {
+        const int v = atoi(e);
+        if (v < 32 || v % 32 != 0) return set_err(Q3_INVALID_ARG, "Q3_BAT_STREAM_BLOCK_FRAMES=%s: not a positive multiple of 32", e);
+        b->s_block_frames = v;
+    }
+    if (const char* e = getenv("Q3_BAT_STREAM_MAX_BLOCKS")) {
+        const int v = atoi(e);
+        if (v < 0) return set_err(Q3_INVALID_ARG, "Q3_BAT_STREAM_MAX_BLOCKS=%s: negative", e);
+        b->s_max_blocks = v;
+    }
     *out = b.release();
     return Q3_OK;
 }
@@ -288,13 +431,26 @@ extern "C" void q3_batcher_free(q3_batcher* b) {
     if (b->s) q3_session_free(b->s);
     delete b;
 }
+static q3_status batcher_submit(q3_batcher* b, const q3_request* req, int want_pcm, bool streamed, int64_t* ticket);
 extern "C" q3_status q3_batcher_submit(q3_batcher* b, const q3_request* req, int want_pcm, int64_t* ticket) {
     if (!b || !req || !ticket) return set_err(Q3_INVALID_ARG, "q3_batcher_submit: null argument");
+    return batcher_submit(b, req, want_pcm, false, ticket);
+}
+extern "C" q3_status q3_batcher_submit_streamed(q3_batcher* b, const q3_request* req, int64_t* ticket) {
+    if (!b || !req || !ticket) return set_err(Q3_INVALID_ARG, "q3_batcher_submit_streamed: null argument");
+    if (b->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_batcher_submit_streamed: the model has no device (manifest-only): the vocoder runs on the GPU");
+    if (req->n_ref > 0 && req->ref_codes && (long)req->n_ref + req->opts.max_length > (long)b->frame_budget + b->prompt_budget)
+        return set_err(Q3_UNSUPPORTED, "q3_batcher_submit_streamed: %d reference frames + max_length %d exceed the stream's %d frames (frame_budget + prompt_budget)",
+                       req->n_ref, req->opts.max_length, b->frame_budget + b->prompt_budget);
+    return batcher_submit(b, req, 0, true, ticket);
+}
+static q3_status batcher_submit(q3_batcher* b, const q3_request* req, int want_pcm, bool streamed, int64_t* ticket) {
     if (req->opts.max_length < 1 || req->opts.max_length > b->frame_budget)
         return set_err(Q3_UNSUPPORTED, "q3_batcher_submit: max_length %d outside 1..%d (the batcher's frame budget)", req->opts.max_length, b->frame_budget);
     if (req->n_text < 0 || req->n_instruct < 0 || req->n_ref < 0 || req->n_ref_text < 0) return set_err(Q3_INVALID_ARG, "q3_batcher_submit: negative length");
     std::unique_ptr<BatTicket> t(new BatTicket());
-    t->req.own(*req, b->m->cfg.hidden); t->want_pcm = want_pcm != 0;
+    t->req.own(*req, b->m->cfg.hidden); t->want_pcm = want_pcm != 0; t->streamed = streamed;
+    if (streamed) b->n_streamed++;
     const int64_t id = b->next_id++;
     b->t[id] = std::move(t);
     b->queue.push_back(id);
@@ -304,6 +460,24 @@ extern "C" q3_status q3_batcher_submit(q3_batcher* b, const q3_request* req, int
 
 static void bat_fail(BatTicket& t, q3_status st) { t.state = Q3_TICKET_FAILED; t.st = st; t.err = q3_last_error(); t.row = -1; }
 
+// frames [t.s_pushed, n_total) of a streamed ticket's row (frames = the row's codes from frame 0) join the parts of this step
+static void stream_part(q3_batcher* b, BatTicket& t, int row, const uint32_t* frames, int n_total, bool last) {
+    if (n_total < t.s_pushed) {
+        // frames past the row's end would have gone to the worker (samples nobody should hear): a row's frame count never shrinks
+        // (refresh_codes cuts at the EOS before a frame is handed over), so this is a broken invariant — the ticket fails, loudly
+        std::lock_guard<std::mutex> g(b->dec->mu);
+        if (!t.s_failed) {
+            t.s_failed = true; t.s_st = Q3_INVALID_ARG;
+            t.s_err = "streamed ticket: " + std::to_string(t.s_pushed) + " frames were handed to the vocoder, the row ended at " + std::to_string(n_total);
+        }
+        n_total = t.s_pushed;
+    }
+    if (!last && n_total == t.s_pushed) return;
+    StreamPart p{&t, row, {}, !t.s_started, last};
+    p.frames.assign(frames + (size_t)t.s_pushed * 16, frames + (size_t)n_total * 16);
+    t.s_started = true; t.s_pushed = n_total;
+    b->sparts.push_back(std::move(p));
+}
 // the row's sequence has ended: keep its codes (and PCM), free the row
 static q3_status bat_collect(q3_batcher* b, int row) {
     BatTicket& t = *b->t[b->owner[row]];
@@ -312,6 +486,11 @@ static q3_status bat_collect(q3_batcher* b, int row) {
     t.codes.resize((size_t)n * 16); t.n_frames = n;
     if (n > 0) Q3C(q3_session_codes(b->s, row, t.codes.data(), n, &n));
     bool async = false;
+    if (t.streamed) {
+        // its last part: the frames up to its end that no step has handed over yet; DONE once the worker has served it
+        stream_part(b, t, row, t.codes.data(), n, true);
+        t.s_ended = true; async = true;
+    } else
     if (t.want_pcm && n > 0) {
         static const bool sync_decode = getenv("Q3_BAT_SYNC_DECODE") != nullptr;
         t.pcm.resize((size_t)n * samples_per_frame(b->m->cfg));
@@ -502,13 +681,35 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
         }
         if (busy == 0 && collected == 0) break;          // nothing runs and nothing is waiting for a row
     }
+    // Streamed tickets: the frames of this step come to the host and go to the decode worker as ONE job over every streamed row
+    // (a row that ended inside the step has its part already, up to its end: bat_collect). The step does not wait for the job.
+    // A ticket the worker could not serve (a refused or failed push) gives up its row here.
+    if (b->n_streamed > 0) {
+        for (int r = 0; r < b->slots; ++r) {
+            if (b->owner[r] < 0) continue;
+            BatTicket& t = *b->t[b->owner[r]];
+            if (!t.streamed) continue;
+            bool failed; { std::lock_guard<std::mutex> g(b->dec->mu); failed = t.s_failed; }
+            if (failed) {
+                t.state = Q3_TICKET_FAILED; t.st = t.s_st; t.err = t.s_err; t.row = -1;
+                b->owner[r] = -1; b->commit[r] = 0;
+                Q3C(session_idle_row(b->s, r));
+                finished++;
+                continue;
+            }
+            int n = 0, done = 0;
+            Q3C(q3_session_frames(b->s, r, &n, &done));        // (one read-back serves every row: the session's host copy of the codes)
+            if (n > t.s_pushed) stream_part(b, t, r, &b->s->codes_host[(size_t)r * b->s->max_frames * 16], n, false);
+        }
+        stream_flush(b);
+    }
     Q3C(fill());                                   // the next step starts with full rows
     int running = 0;
     for (int r = 0; r < b->slots; ++r) running += b->owner[r] >= 0 ? 1 : 0;
     // Nothing runs and nothing waits: the rows that just ended may still be with the decode worker. Their samples are waited for
     // HERE, so that a host loop that stops on "running == 0 && queued == 0" finds every ticket DONE, as it always did.
     if (running == 0 && b->queue.empty())
-        for (auto& kv : b->t) ticket_wait_decode(b, *kv.second);
+        for (auto& kv : b->t) { ticket_wait_decode(b, *kv.second); stream_settle(b, *kv.second, true); }
     if (n_running) *n_running = running;
     if (n_queued) *n_queued = (int)b->queue.size();
     if (n_finished) *n_finished = finished;
@@ -521,6 +722,7 @@ extern "C" q3_status q3_batcher_poll(q3_batcher* b, int64_t ticket, int* state, 
     if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_poll: unknown ticket %lld", (long long)ticket);
     BatTicket& t = *it->second;
     if (t.decoding && t.dec_done.load()) ticket_wait_decode(b, t);      // its samples have landed: DONE (or FAILED) from here on
+    stream_settle(b, t, false);
     if (state) *state = t.state;                                         // a ticket still being vocoded reads RUNNING
     int nf = t.n_frames;
     if (t.state == Q3_TICKET_RUNNING && b->s && t.row >= 0) {       // frames run so far (an EOS inside them is only looked at when the row is collected)
@@ -529,6 +731,7 @@ extern "C" q3_status q3_batcher_poll(q3_batcher* b, int64_t ticket, int* state, 
     }
     if (n_frames) *n_frames = nf;
     if (n_samples) *n_samples = t.pcm.size();         // (of a ticket still being vocoded: the samples it WILL hold — the size q3_batcher_fetch wants)
+    if (n_samples && t.streamed) { std::lock_guard<std::mutex> g(b->dec->mu); *n_samples = t.spcm.size(); }      // streamed: the samples that have landed
     return Q3_OK;
 }
 
@@ -538,8 +741,15 @@ extern "C" q3_status q3_batcher_fetch(q3_batcher* b, int64_t ticket, uint32_t* c
     if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_fetch: unknown ticket %lld", (long long)ticket);
     BatTicket& t = *it->second;
     ticket_wait_decode(b, t);                         // a row that ended but is still being vocoded: wait for its samples
+    if (t.streamed) {
+        // a ticket the worker may still hold parts of is not released under it: a finished (or failed) one waits for them
+        if (t.row < 0) stream_settle(b, t, true);      // (a FAILED one too: the queue may still hold parts that name it)
+        if (t.state == Q3_TICKET_DONE && pcm_host)
+            return set_err(Q3_INVALID_ARG, "q3_batcher_fetch: ticket %lld is streamed: its samples go through q3_batcher_read", (long long)ticket);
+    }
     if (t.state == Q3_TICKET_FAILED) {
         const q3_status st = t.st; const std::string err = t.err;
+        if (t.streamed) b->n_streamed--;
         b->t.erase(it);
         return set_err(st, "%s", err.c_str());
     }
@@ -552,7 +762,42 @@ extern "C" q3_status q3_batcher_fetch(q3_batcher* b, int64_t ticket, uint32_t* c
         if (cap_samples < t.pcm.size()) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
         memcpy(pcm_host, t.pcm.data(), t.pcm.size() * 4);
     }
+    if (t.streamed) b->n_streamed--;
     b->t.erase(it);
     return Q3_OK;
 }
 
+
+extern "C" q3_status q3_batcher_read(q3_batcher* b, int64_t ticket, float* pcm_host, size_t cap_samples, size_t* n_samples, int* done) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_read: null batcher");
+    if (!n_samples || !done || (cap_samples > 0 && !pcm_host)) return set_err(Q3_INVALID_ARG, "q3_batcher_read: null argument");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_read: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_read: ticket %lld was not submitted as streamed (its samples come with q3_batcher_fetch)", (long long)ticket);
+    *n_samples = 0; *done = 0;
+    stream_settle(b, t, false);
+    if (t.state == Q3_TICKET_FAILED) return set_err(t.st, "%s", t.err.c_str());
+    std::lock_guard<std::mutex> g(b->dec->mu);
+    size_t n = t.spcm.size() - t.s_read;
+    if (n > cap_samples) n = cap_samples;
+    if (n > 0) memcpy(pcm_host, t.spcm.data() + t.s_read, n * 4);
+    t.s_read += n;
+    *n_samples = n;
+    *done = (t.state == Q3_TICKET_DONE && t.s_read == t.spcm.size()) ? 1 : 0;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_stream_info(q3_batcher* b, int* block_frames, size_t* block_bytes, int* blocks_total, int* blocks_in_use, int* blocks_peak) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_stream_info: null batcher");
+    BatDecoder& d = *b->dec;
+    std::lock_guard<std::mutex> g(d.mu);
+    // the stream's own figures (q3_codec_stream_info after the last job); before the first stream job there is no stream: the
+    // block size the batcher will ask for, and zeros
+    if (block_frames) *block_frames = d.info_bf ? d.info_bf : b->s_block_frames;
+    if (block_bytes) *block_bytes = d.info_bytes;
+    if (blocks_total) *blocks_total = d.info_total;
+    if (blocks_in_use) *blocks_in_use = d.info_use;
+    if (blocks_peak) *blocks_peak = d.info_peak;
+    return Q3_OK;
+}

@@ -10,11 +10,19 @@
 // row's tail) reaches the context columns' outputs alone, which are dropped. That is the argument codec_decode_dev(..., c0)
 // rests on, for several rows. A row still inside its first CODEC_CTX_FRAMES frames needs the zero padding of every inner layer,
 // which no neighbour can stand in for: it runs the stack on its own [0, e).
+//
+// A BLOCKED stream (q3_codec_stream_create_blocked) keeps K | V and the latent of a row in blocks of bf frames (bf % 32 == 0), one
+// block = [layer][K | V][QD][bf] followed by [LAT][bf], taken from the stream's free list when a push reaches them and given back
+// at reset: a row holds what its frames need, not max_frames. Frame f of a row is column f % bf of its block f / bf. Blocks are
+// never cleared: every kernel reads a frame only below the row's position. The launches are the same ones with block-aware
+// descriptors, and the attention is the third instance of attn_c_tile (k_attn_cb), which differs in addressing only.
 #include "q3_engine.h"
 
-struct CsRow { int pos = 0; float* kv = nullptr; float* lat = nullptr; float* hist = nullptr; };
+struct CsRow { int pos = 0; float* kv = nullptr; float* lat = nullptr; float* hist = nullptr; std::vector<float*> blocks; };
 struct q3_codec_stream {
     q3_model* m = nullptr; int R = 0, cap = 0;
+    int bf = 0, max_blocks = 0;                              // blocked stream: frames per block (0 = whole-row state), block limit (0 = none)
+    std::vector<float*> free_blocks; int blocks_total = 0, blocks_in_use = 0, blocks_peak = 0;
     hipStream_t st = nullptr; bool owns_stream = false;
     std::vector<CsRow> rows;
     CodecWS ws;
@@ -28,7 +36,12 @@ static size_t kv_floats(const q3_codec_stream* cs) {
     return (size_t)c.dec_layers * 2 * c.dec_heads * c.dec_head_dim * cs->cap;
 }
 
-q3_status codec_stream_create(q3_model* m, int rows, int max_frames, hipStream_t st, q3_codec_stream** out) {
+static size_t block_floats(const q3_codec_stream* cs) {
+    const q3_config& c = cs->m->cfg;
+    return ((size_t)c.dec_layers * 2 * c.dec_heads * c.dec_head_dim + c.dec_latent) * cs->bf;
+}
+
+q3_status codec_stream_create(q3_model* m, int rows, int max_frames, hipStream_t st, q3_codec_stream** out, int block_frames, int max_blocks) {
     if (!m || !m->finalized) return set_err(Q3_INVALID_ARG, "model not finalized");
     if (!out || rows < 1 || max_frames < 1) return set_err(Q3_INVALID_ARG, "q3_codec_stream_create: rows and max_frames must be positive");
     if (m->device < 0) return set_err(Q3_INVALID_ARG, "q3_codec_stream_create: the model has no device (manifest-only): the vocoder runs on the GPU");
@@ -36,6 +49,7 @@ q3_status codec_stream_create(q3_model* m, int rows, int max_frames, hipStream_t
     HIPC(hipSetDevice(m->device));
     std::unique_ptr<q3_codec_stream> cs(new q3_codec_stream());
     cs->m = m; cs->R = rows; cs->cap = max_frames; cs->rows.resize(rows);
+    cs->bf = block_frames; cs->max_blocks = max_blocks;
     m->refs.fetch_add(1);
     auto fail = [&](q3_status s) { q3_codec_stream_free(cs.release()); return s; };
     if (st) cs->st = st;
@@ -57,12 +71,29 @@ extern "C" q3_status q3_codec_stream_create(q3_model* m, int rows, int max_frame
     return codec_stream_create(m, rows, max_frames, nullptr, out);
 }
 
+extern "C" q3_status q3_codec_stream_create_blocked(q3_model* m, int rows, int max_frames, int block_frames, int max_blocks, q3_codec_stream** out) {
+    if (block_frames < 32 || block_frames % 32 != 0)
+        return set_err(Q3_INVALID_ARG, "q3_codec_stream_create_blocked: block_frames %d is not a positive multiple of 32 (a 32-key attention tile must lie inside one block)", block_frames);
+    if (max_blocks < 0) return set_err(Q3_INVALID_ARG, "q3_codec_stream_create_blocked: negative max_blocks");
+    return codec_stream_create(m, rows, max_frames, nullptr, out, block_frames, max_blocks);
+}
+extern "C" q3_status q3_codec_stream_info(q3_codec_stream* cs, int* block_frames, size_t* block_bytes, int* blocks_total, int* blocks_in_use, int* blocks_peak) {
+    if (!cs) return set_err(Q3_INVALID_ARG, "q3_codec_stream_info: null stream");
+    if (block_frames) *block_frames = cs->bf;
+    if (block_bytes) *block_bytes = block_floats(cs) * 4;
+    if (blocks_total) *blocks_total = cs->blocks_total;
+    if (blocks_in_use) *blocks_in_use = cs->blocks_in_use;
+    if (blocks_peak) *blocks_peak = cs->blocks_peak;
+    return Q3_OK;
+}
+
 extern "C" void q3_codec_stream_free(q3_codec_stream* cs) {
     if (!cs) return;
     q3_model* m = cs->m;
     (void)hipSetDevice(m->device);
     if (cs->st) (void)hipStreamSynchronize(cs->st);
-    for (CsRow& r : cs->rows) { dev_free(r.kv); dev_free(r.lat); dev_free(r.hist); }
+    for (CsRow& r : cs->rows) { dev_free(r.kv); dev_free(r.lat); dev_free(r.hist); for (float* b : r.blocks) dev_free(b); }
+    for (float* b : cs->free_blocks) dev_free(b);
     cs->ws.release();
     dev_free(cs->cs); dev_free(cs->sn); dev_free(cs->desc); dev_free(cs->stage);
     if (cs->stage_host) (void)hipHostFree(cs->stage_host);
@@ -72,7 +103,20 @@ extern "C" void q3_codec_stream_free(q3_codec_stream* cs) {
 }
 
 int codec_stream_pos(const q3_codec_stream* cs, int row) { return cs->rows[row].pos; }
-void codec_stream_reset(q3_codec_stream* cs, int row) { cs->rows[row].pos = 0; }      // the caches are only read below pos
+// blocked stream: the blocks row holds, and how many more it takes to reach frame `upto` (0 / 0 on an unblocked stream)
+void codec_stream_blocks(const q3_codec_stream* cs, int row, int upto, int* held, int* need) {
+    const CsRow& r = cs->rows[row];
+    *held = (int)r.blocks.size();
+    *need = cs->bf ? std::max(0, (upto + cs->bf - 1) / cs->bf - *held) : 0;
+}
+// the caches are only read below pos; a blocked row's blocks go back to the free list (no push is in flight: each ends with a wait)
+void codec_stream_reset(q3_codec_stream* cs, int row) {
+    CsRow& r = cs->rows[row];
+    r.pos = 0;
+    cs->blocks_in_use -= (int)r.blocks.size();
+    cs->free_blocks.insert(cs->free_blocks.end(), r.blocks.begin(), r.blocks.end());
+    r.blocks.clear();
+}
 
 extern "C" q3_status q3_codec_stream_reset(q3_codec_stream* cs, int row) {
     if (!cs || row < 0 || row >= cs->R) return set_err(Q3_INVALID_ARG, "q3_codec_stream_reset: bad row");
@@ -112,10 +156,54 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
     const int Q = c.dec_q_dim, LAT = c.dec_latent, QD = c.dec_heads * c.dec_head_dim, cap = cs->cap, spf = samples_per_frame(c);
     const int nP = (int)P.size();
     const bool on_dev = P[0].dev != nullptr;
+    const int bf = cs->bf, kp = bf ? bf : cap;              // pitch of a row's K / V / latent columns
+    const size_t lat_off = (size_t)c.dec_layers * 2 * QD * bf;      // blocked: the latent inside a block
+    // A push that returns before its rows' positions move (a workspace, staging or descriptor allocation that fails below) gives the
+    // blocks it took back: a row never holds more than ceil(pos / bf), whatever the way out.
+    struct Untake {
+        q3_codec_stream* cs; const std::vector<CsPush>& P; bool armed = true;
+        ~Untake() {
+            if (!armed || !cs->bf) return;
+            for (const CsPush& p : P) {
+                CsRow& r = cs->rows[p.row];
+                while ((int)r.blocks.size() > (r.pos + cs->bf - 1) / cs->bf) { cs->free_blocks.push_back(r.blocks.back()); r.blocks.pop_back(); cs->blocks_in_use--; }
+            }
+        }
+    } untake{cs, P};
+    if (bf) {
+        // the blocks this push reaches: all of them or none, before anything changes
+        int need = 0;
+        for (const CsPush& p : P) {
+            const CsRow& r = cs->rows[p.row];
+            need += std::max(0, (r.pos + p.n + bf - 1) / bf - (int)r.blocks.size());
+        }
+        if (cs->max_blocks > 0 && cs->blocks_in_use + need > cs->max_blocks)
+            return set_err(Q3_OOM, "codec stream: block pool exhausted: the push needs %d more block(s) of %d frames, %d of %d are in use",
+                           need, bf, cs->blocks_in_use, cs->max_blocks);
+        while ((int)cs->free_blocks.size() < need) {
+            float* b = nullptr;
+            if (dev_malloc((void**)&b, block_floats(cs) * 4) != hipSuccess) {
+                (void)hipGetLastError();
+                return set_err(Q3_OOM, "codec stream: block %d (%zu KB each)", cs->blocks_total, block_floats(cs) * 4 >> 10);
+            }
+            cs->free_blocks.push_back(b); cs->blocks_total++;
+        }
+        for (const CsPush& p : P) {
+            CsRow& r = cs->rows[p.row];
+            if (!r.hist && dev_malloc((void**)&r.hist, (size_t)Q * 2 * 4) != hipSuccess) {
+                (void)hipGetLastError(); r.hist = nullptr;
+                return set_err(Q3_OOM, "codec stream: history columns of row %d", p.row);
+            }
+        }
+        for (const CsPush& p : P) {
+            CsRow& r = cs->rows[p.row];
+            while ((int)r.blocks.size() * bf < r.pos + p.n) { r.blocks.push_back(cs->free_blocks.back()); cs->free_blocks.pop_back(); cs->blocks_in_use++; }
+        }
+    }
     // row state on first use
     for (const CsPush& p : P) {
         CsRow& r = cs->rows[p.row];
-        if (r.kv) continue;
+        if (bf || r.kv) continue;
         if (dev_malloc((void**)&r.kv, kv_floats(cs) * 4) != hipSuccess || dev_malloc((void**)&r.lat, (size_t)LAT * cap * 4) != hipSuccess ||
             dev_malloc((void**)&r.hist, (size_t)Q * 2 * 4) != hipSuccess) {
             (void)hipGetLastError();
@@ -166,14 +254,20 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
     // descriptors
     std::vector<int> pos(N);
     std::vector<AttnCsRow> arows(nP);
-    std::vector<ColCopy> xin(Np), hist(2 * nP), compact(N), kvsc(N), latsc(N), latg(Lc);
+    std::vector<ColCopy> xin(Np), hist(2 * nP), compact(N), kvsc(N), latsc(N), latg(Lc), solog;
     std::vector<SegCopy> segs;
+    std::vector<AttnCbRow> brows(bf ? nP : 0);
+    std::vector<const float*> tabs;                         // blocked: the block lists of the pushed rows, back to back
+    // frame f of a row: its K column of layer 0 (the layer and V are offsets of the copy / the kernel) and its latent column
+    auto kv_col = [&](const CsRow& r, int f) { return bf ? r.blocks[f / bf] + f % bf : r.kv + f; };
+    auto lat_col = [&](const CsRow& r, int f) { return bf ? r.blocks[f / bf] + lat_off + f % bf : r.lat + f; };
     std::vector<const uint32_t*> fsrc(on_dev ? N : 0);
     std::vector<uint32_t> fhost(on_dev ? 0 : (size_t)N * 16);
     for (int i = 0; i < nP; ++i) {
         const CsRow& r = cs->rows[P[i].row];
         const int f0 = r.pos, n = P[i].n, x0 = col0[i] + 2 * i;      // x0: the row's first column in the pre_conv input
         arows[i] = {r.kv, f0, f0 + n, col0[i]};
+        if (bf) { brows[i] = {(int)tabs.size(), f0, f0 + n, col0[i]}; tabs.insert(tabs.end(), r.blocks.begin(), r.blocks.end()); }
         // pre_conv input: the two columns before f0 (zeros before the row's frame 0: the causal pad), then the new ones
         for (int h = 0; h < 2; ++h) xin[x0 + h] = {f0 - 2 + h >= 0 ? r.hist + h : nullptr, A + x0 + h, 2, Np};
         // ... whose last two columns are the next push's history
@@ -183,8 +277,8 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
             pos[col] = f0 + j;
             xin[x0 + 2 + j] = {B + col, A + x0 + 2 + j, N, Np};
             compact[col] = {B + x0 + 2 + j, C + col, Np, N};
-            kvsc[col] = {knew + col, r.kv + f0 + j, N, cap};
-            latsc[col] = {C + col, r.lat + f0 + j, N, cap};
+            kvsc[col] = {knew + col, kv_col(r, f0 + j), N, kp};
+            latsc[col] = {C + col, lat_col(r, f0 + j), N, kp};
             if (on_dev) fsrc[col] = P[i].dev + (size_t)j * 16;
             else memcpy(&fhost[(size_t)col * 16], P[i].host + (size_t)j * 16, 64);
         }
@@ -194,17 +288,23 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
         for (int i : conc) {
             const CsRow& r = cs->rows[P[i].row];
             const int a0 = r.pos + P[i].skip, c0 = a0 - CODEC_CTX_FRAMES, len = P[i].n - P[i].skip + CODEC_CTX_FRAMES;
-            for (int j = 0; j < len; ++j) latg[l0 + j] = {r.lat + c0 + j, F + l0 + j, cap, Lc};
+            for (int j = 0; j < len; ++j) latg[l0 + j] = {lat_col(r, c0 + j), F + l0 + j, kp, Lc};
             segs.push_back({(unsigned long long)(l0 + CODEC_CTX_FRAMES) * spf, (unsigned long long)out0[i] * spf, (unsigned long long)(P[i].n - P[i].skip) * spf});
             l0 += len;
         }
-        for (int i : solo)
+        for (int i : solo) {
+            // blocked: the row's latent [0, e) is gathered column by column (e may lie past a block edge)
+            const CsRow& r = cs->rows[P[i].row];
+            const int e = r.pos + P[i].n;
+            if (bf) for (int f = 0; f < e; ++f) solog.push_back({lat_col(r, f), F + f, kp, e});
             segs.push_back({(unsigned long long)(cs->rows[P[i].row].pos + P[i].skip) * spf, (unsigned long long)out0[i] * spf,
                             (unsigned long long)(P[i].n - P[i].skip) * spf});
+        }
     }
     DescBlock db;
     const size_t o_pos = db.add(pos), o_arows = db.add(arows), o_xin = db.add(xin), o_hist = db.add(hist), o_compact = db.add(compact),
-                 o_kvsc = db.add(kvsc), o_latsc = db.add(latsc), o_latg = db.add(latg), o_segs = db.add(segs), o_fsrc = db.add(fsrc);
+                 o_kvsc = db.add(kvsc), o_latsc = db.add(latsc), o_latg = db.add(latg), o_segs = db.add(segs), o_fsrc = db.add(fsrc),
+                 o_brows = db.add(brows), o_tabs = db.add(tabs), o_solog = db.add(solog);
     if (db.host.size() > cs->desc_cap) {
         HIPC(hipStreamSynchronize(st));
         dev_free(cs->desc); cs->desc = nullptr; cs->desc_cap = 0;
@@ -220,7 +320,7 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
         ~Failed() {
             if (!armed) return;
             (void)hipStreamSynchronize(cs->st);
-            for (const CsPush& p : P) cs->rows[p.row].pos = 0;
+            for (const CsPush& p : P) codec_stream_reset(cs, p.row);
         }
     } failed{cs, P};
     HIPC(q3_hipMemcpy(cs->desc, db.host.data(), db.host.size(), hipMemcpyHostToDevice));
@@ -237,10 +337,11 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
     HIPC(launch_copy_cols((const ColCopy*)D(o_compact), N, LAT, 0, 0, st));            // C [LAT][N]: the history columns' outputs dropped
     const float scale = (float)pow((double)c.dec_head_dim, -0.5);
     Q3C(codec_front_transformer(m, ws, N, st, [&](int l, float* q, float* k, float*, float* ao) -> q3_status {
-        const size_t layer_off = (size_t)l * 2 * QD * cap;
+        const size_t layer_off = (size_t)l * 2 * QD * kp;
         HIPC(launch_rope_c_pos(q, k, cs->cs, cs->sn, (const int*)D(o_pos), c.dec_heads, c.dec_head_dim, N, st));
         HIPC(launch_copy_cols((const ColCopy*)D(o_kvsc), N, 2 * QD, 0, layer_off, st));
-        HIPC(launch_attn_cs(q, ao, (const AttnCsRow*)D(o_arows), nP, max_tiles, layer_off, c.dec_heads, c.dec_head_dim, N, cap, scale, st));
+        if (bf) HIPC(launch_attn_cb(q, ao, (const AttnCbRow*)D(o_brows), (const float* const*)D(o_tabs), nP, max_tiles, layer_off, c.dec_heads, c.dec_head_dim, N, bf, scale, st));
+        else HIPC(launch_attn_cs(q, ao, (const AttnCsRow*)D(o_arows), nP, max_tiles, layer_off, c.dec_heads, c.dec_head_dim, N, cap, scale, st));
         return Q3_OK;
     }));
     HIPC(launch_copy_cols((const ColCopy*)D(o_latsc), N, LAT, 0, 0, st));
@@ -252,10 +353,11 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
         Q3C(codec_stack_dev(m, ws, F, Lc, st, nullptr, scope));
         HIPC(launch_copy_segs(ws.pcm, cs->stage, dsegs, (int)conc.size(), max_n, st));
     }
-    for (size_t k = 0; k < solo.size(); ++k) {
+    for (size_t k = 0, g0 = 0; k < solo.size(); ++k) {
         const int i = solo[k]; const CsRow& r = cs->rows[P[i].row];
         const int e = r.pos + P[i].n;
-        HIPC(launch_copy_rows(r.lat, cap, F, e, LAT, e, st));
+        if (bf) { HIPC(launch_copy_cols((const ColCopy*)D(o_solog) + g0, e, LAT, 0, 0, st)); g0 += (size_t)e; }
+        else HIPC(launch_copy_rows(r.lat, cap, F, e, LAT, e, st));
         Q3C(codec_stack_dev(m, ws, F, e, st, nullptr, scope));
         HIPC(launch_copy_segs(ws.pcm, cs->stage, dsegs + conc.size() + k, 1, (size_t)(P[i].n - P[i].skip) * spf, st));
     }
@@ -265,7 +367,8 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
         if (P[i].pcm_host) memcpy(P[i].pcm_host, cs->stage_host + (size_t)out0[i] * spf, (size_t)(P[i].n - P[i].skip) * spf * 4);
         cs->rows[P[i].row].pos += P[i].n;
     }
-    failed.armed = false;
+    failed.armed = false; untake.armed = false;
+    cs->blocks_peak = std::max(cs->blocks_peak, cs->blocks_in_use);
     return Q3_OK;
 }
 
@@ -295,4 +398,18 @@ extern "C" q3_status q3_codec_stream_push(q3_codec_stream* cs, int n_rows, const
         P.push_back({r, n, 0, frames_host[i], nullptr, pcm_host[i]});
     }
     return codec_stream_push(cs, P);
+}
+
+extern "C" q3_status q3_codec_stream_prime(q3_codec_stream* cs, int row, const uint32_t* frames_host, int n_frames) {
+    if (!cs) return set_err(Q3_INVALID_ARG, "q3_codec_stream_prime: null stream");
+    if (row < 0 || row >= cs->R) return set_err(Q3_INVALID_ARG, "q3_codec_stream_prime: row %d out of range (%d rows)", row, cs->R);
+    if (cs->rows[row].pos != 0) return set_err(Q3_INVALID_ARG, "q3_codec_stream_prime: row %d is at frame %d, state-only frames come first", row, cs->rows[row].pos);
+    if (n_frames < 0 || (n_frames > 0 && !frames_host)) return set_err(Q3_INVALID_ARG, "q3_codec_stream_prime: bad frames argument");
+    if (n_frames > cs->cap) return set_err(Q3_INVALID_ARG, "q3_codec_stream_prime: %d frames, the stream holds %d", n_frames, cs->cap);
+    for (int f = 0; f < n_frames; ++f)
+        for (int g = 1; g < 16; ++g)
+            if (frames_host[(size_t)f * 16 + g] >= (uint32_t)cs->m->cfg.dec_cb_size)
+                return set_err(Q3_INVALID_ARG, "code %u out of range for codebook %d (row %d, frame %d)", frames_host[(size_t)f * 16 + g], g, row, f);
+    // a push whose frames are all `skip`: the front fills the caches, no stack runs and there are no samples
+    return codec_stream_push(cs, {CsPush{row, n_frames, n_frames, frames_host, nullptr, nullptr}});
 }

@@ -476,9 +476,12 @@ Q3_HIDDEN q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, 
 // q3_codec_stream.hip
 // n new frames of one row, codes on the host OR the device; the first `skip` of them only catch the row's state up (no samples)
 struct CsPush { int row; int n; int skip; const uint32_t* host; const uint32_t* dev; float* pcm_host; };
-Q3_HIDDEN q3_status codec_stream_create(q3_model* m, int rows, int max_frames, hipStream_t st, q3_codec_stream** out);
+// block_frames > 0: block-allocated state (a multiple of 32), at most max_blocks blocks (0 = no limit)
+Q3_HIDDEN q3_status codec_stream_create(q3_model* m, int rows, int max_frames, hipStream_t st, q3_codec_stream** out, int block_frames = 0,
+                                        int max_blocks = 0);
 Q3_HIDDEN q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& pushes);
 Q3_HIDDEN int codec_stream_pos(const q3_codec_stream* cs, int row);
+Q3_HIDDEN void codec_stream_blocks(const q3_codec_stream* cs, int row, int upto, int* held, int* need);
 Q3_HIDDEN void codec_stream_reset(q3_codec_stream* cs, int row);
 // q3_session.hip
 Q3_HIDDEN hipError_t sync_frames(q3_session* s);

@@ -344,11 +344,14 @@ hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* 
                          hipStream_t st);
 // codec stream (q3_codec_stream.hip): the front over the new columns of several rows, K / V from per-row caches
 struct AttnCsRow { const float* kv; int a0, e, qcol; };      // row cache [layer][K | V][QD][cap]; new frames [a0, e) at columns qcol ..
+struct AttnCbRow { int tab0, a0, e, qcol; };                  // as AttnCsRow, the cache being the block list tabs[tab0 ..] (block-allocated stream)
 struct ColCopy { const float* src; float* dst; int sp, dp; }; // one column: dst[c * dp] = src ? src[c * sp] : 0
 struct SegCopy { unsigned long long src, dst, n; };           // one run of floats
 hipError_t launch_rope_c_pos(float* q, float* k, const float* cs, const float* sn, const int* pos, int nh, int hd, int L, hipStream_t st);
 hipError_t launch_attn_cs(const float* q, float* o, const AttnCsRow* rows, int n_rows, int max_tiles, size_t layer_off, int nh, int hd,
                           int N, int cap, float scale, hipStream_t st);
+hipError_t launch_attn_cb(const float* q, float* o, const AttnCbRow* rows, const float* const* tabs, int n_rows, int max_tiles, size_t layer_off,
+                          int nh, int hd, int N, int bf, float scale, hipStream_t st);
 hipError_t launch_copy_cols(const ColCopy* d, int n, int C, size_t src_off, size_t dst_off, hipStream_t st);
 hipError_t launch_copy_segs(const float* src, float* dst, const SegCopy* segs, int n_segs, size_t max_n, hipStream_t st);
 hipError_t launch_gather_frames(const uint32_t* const* src, uint32_t* dst, int n, hipStream_t st);

@@ -1387,10 +1387,14 @@ constexpr int ATC_NW = 4;
 // hold query i at column i - qoff — while k and v are the row's cache of pitch kp, valid up to the row's end L; lanes whose
 // query lies before the row's first new frame qlo load zeros and store nothing. Only the addressing differs: the tile
 // alignment, the key-tile walk of each wave and the merge are the same statements, so a query gets the same bits.
-template <bool CS>
+// BLK = true (with CS) is the block-allocated codec stream (k_attn_cb): the row's cache is a list of blocks of kp frames each,
+// [layer][K | V][QD][kp]; a 32-key tile lies inside one block (kp % 32 == 0), so the tile's K and V base come from the row's
+// block table tab (+ boff to the layer, + voff from K to V) and the key's column is its frame inside the block. k and v are unused.
+template <bool CS, bool BLK = false>
 __device__ __forceinline__ void attn_c_tile(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                             float* __restrict__ o, const int qp, const int kp, const int L, const int qt, const int h,
-                                            const int qlo, const int qoff, const float scale) {
+                                            const int qlo, const int qoff, const float scale,
+                                            const float* const* __restrict__ tab = nullptr, const size_t boff = 0, const size_t voff = 0) {
     constexpr int VP = 33;
     __shared__ float vs_all[ATC_NW][64 * VP];                                  // per wave: V patch, then its partial O
     __shared__ float s_m[ATC_NW][32], s_l[ATC_NW][32];
@@ -1412,16 +1416,18 @@ __device__ __forceinline__ void attn_c_tile(const float* __restrict__ q, const f
     for (int j0 = 32 * wave; j0 <= i0; j0 += 32 * ATC_NW) {
         const int j = j0 + li;
         const bool jok = j < L;
+        const float* kt = k; const float* vt = v; int jc = j;                  // the tile's K and V base, this lane's key column
+        if (BLK) { kt = tab[j0 / kp] + boff; vt = kt + voff; jc = j0 % kp + li; }
         // V tile -> LDS (rows d, columns key); issued first so that it overlaps the score MFMAs
         float vr[32];
 #pragma unroll
-        for (int s = 0; s < 32; ++s) vr[s] = jok ? v[hb + (size_t)(2 * s + lk) * kp + j] : 0.0f;
+        for (int s = 0; s < 32; ++s) vr[s] = jok ? vt[hb + (size_t)(2 * s + lk) * kp + jc] : 0.0f;
         f32x16a_t sacc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sacc[r] = 0.0f;
         float ka[32];
 #pragma unroll
-        for (int s = 0; s < 32; ++s) ka[s] = jok ? k[hb + (size_t)(2 * s + lk) * kp + j] : 0.0f;
+        for (int s = 0; s < 32; ++s) ka[s] = jok ? kt[hb + (size_t)(2 * s + lk) * kp + jc] : 0.0f;
 #pragma unroll
         for (int s = 0; s < 32; ++s) sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[s], qb[s], sacc, 0, 0, 0);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      // the previous tile's patch reads are done
@@ -1502,6 +1508,22 @@ hipError_t launch_attn_cs(const float* q, float* o, const AttnCsRow* rows, int n
                           int N, int cap, float scale, hipStream_t st) {
     if (hd != 64 || n_rows <= 0 || max_tiles <= 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_attn_cs, dim3(max_tiles, nh, n_rows), dim3(64 * ATC_NW), 0, st, q, o, rows, layer_off, N, cap, nh * hd, scale);
+    return hipGetLastError();
+}
+// Block-allocated codec stream: as k_attn_cs, the row's cache being its block list tabs[tab0 ..] of bf frames per block
+// ([layer][K | V][QD][bf] in each block; layer_off = layer * 2 * QD * bf).
+__global__ __launch_bounds__(64 * ATC_NW) void k_attn_cb(const float* __restrict__ q, float* __restrict__ o, const AttnCbRow* __restrict__ rows,
+                                                         const float* const* __restrict__ tabs, size_t layer_off, int N, int bf, int QD, float scale) {
+    const AttnCbRow r = rows[blockIdx.z];
+    const int t0 = r.a0 >> 5, nt = ((r.e - 1) >> 5) - t0 + 1;                 // 32-query tiles at ABSOLUTE multiples of 32
+    if ((int)blockIdx.x >= nt) return;
+    attn_c_tile<true, true>(q, nullptr, nullptr, o, N, bf, r.e, t0 + nt - 1 - (int)blockIdx.x, blockIdx.y, r.a0, r.a0 - r.qcol, scale,
+                            tabs + r.tab0, layer_off, (size_t)QD * bf);
+}
+hipError_t launch_attn_cb(const float* q, float* o, const AttnCbRow* rows, const float* const* tabs, int n_rows, int max_tiles, size_t layer_off,
+                          int nh, int hd, int N, int bf, float scale, hipStream_t st) {
+    if (hd != 64 || n_rows <= 0 || max_tiles <= 0 || bf <= 0 || bf % 32 != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_attn_cb, dim3(max_tiles, nh, n_rows), dim3(64 * ATC_NW), 0, st, q, o, rows, tabs, layer_off, N, bf, nh * hd, scale);
     return hipGetLastError();
 }
 hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* o, int nh, int hd, int L, float scale,

@@ -54,6 +54,9 @@ pub mod ffi {
         pub fn q3_session_next_chunk_row(s: *mut c_void, b: i32, pcm: *mut f32, cap: usize, n: *mut usize, done: *mut i32) -> i32;
         pub fn q3_session_next_chunks(s: *mut c_void, pcm: *const *mut f32, cap: *const usize, n: *mut usize, done: *mut i32) -> i32;
         pub fn q3_codec_stream_create(m: *mut c_void, rows: i32, max_frames: i32, out: *mut *mut c_void) -> i32;
+        pub fn q3_codec_stream_create_blocked(m: *mut c_void, rows: i32, max_frames: i32, block_frames: i32, max_blocks: i32, out: *mut *mut c_void) -> i32;
+        pub fn q3_codec_stream_info(cs: *mut c_void, block_frames: *mut i32, block_bytes: *mut usize, blocks_total: *mut i32, blocks_in_use: *mut i32, blocks_peak: *mut i32) -> i32;
+        pub fn q3_codec_stream_prime(cs: *mut c_void, row: i32, frames: *const u32, n_frames: i32) -> i32;
         pub fn q3_codec_stream_free(cs: *mut c_void);
         pub fn q3_codec_stream_reset(cs: *mut c_void, row: i32) -> i32;
         pub fn q3_codec_stream_pos(cs: *mut c_void, row: i32, n_frames: *mut i32) -> i32;
@@ -67,6 +70,9 @@ pub mod ffi {
         pub fn q3_batcher_create(m: *mut c_void, slots: i32, frame_budget: i32, prompt_budget: i32, out: *mut *mut c_void) -> i32;
         pub fn q3_batcher_free(b: *mut c_void);
         pub fn q3_batcher_submit(b: *mut c_void, req: *const Q3Request, want_pcm: i32, ticket: *mut i64) -> i32;
+        pub fn q3_batcher_submit_streamed(b: *mut c_void, req: *const Q3Request, ticket: *mut i64) -> i32;
+        pub fn q3_batcher_read(b: *mut c_void, ticket: i64, pcm: *mut f32, cap_samples: usize, n_samples: *mut usize, done: *mut i32) -> i32;
+        pub fn q3_batcher_stream_info(b: *mut c_void, block_frames: *mut i32, block_bytes: *mut usize, blocks_total: *mut i32, blocks_in_use: *mut i32, blocks_peak: *mut i32) -> i32;
         pub fn q3_batcher_step(b: *mut c_void, n_frames: i32, use_graph: i32, n_running: *mut i32, n_queued: *mut i32, n_finished: *mut i32) -> i32;
         pub fn q3_batcher_poll(b: *mut c_void, ticket: i64, state: *mut i32, n_frames: *mut i32, n_samples: *mut usize) -> i32;
         pub fn q3_batcher_fetch(b: *mut c_void, ticket: i64, codes: *mut u32, cap_frames: i32, pcm: *mut f32, cap_samples: usize) -> i32;
