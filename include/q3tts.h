@@ -295,6 +295,34 @@ q3_status q3_batcher_fetch(q3_batcher* b, int64_t ticket, uint32_t* codes_host, 
 q3_status q3_batcher_submit_streamed(q3_batcher* b, const q3_request* req, int64_t* ticket);
 q3_status q3_batcher_read(q3_batcher* b, int64_t ticket, float* pcm_host, size_t cap_samples, size_t* n_samples, int* done);
 q3_status q3_batcher_stream_info(q3_batcher* b, int* block_frames, size_t* block_bytes, int* blocks_total, int* blocks_in_use, int* blocks_peak);
+/* Open tickets: the text arrives in pieces while the request waits or speaks (streamed text in, beside the streamed audio out).
+ * q3_batcher_submit_open queues like q3_batcher_submit / _submit_streamed, chosen by `want`, with the ticket's text open. The
+ * request carries what q3_session_open_text asks for — at least one text token; an ICL request at least n_ref + 1 - n_ref_text
+ * target tokens and a max_length within frame_budget —, else Q3_INVALID_ARG / Q3_UNSUPPORTED here. Admission under a page limit
+ * counts prompt + max_length; an ICL ticket's length cap max(75, 6 n_text) is resolved when its text closes.
+ * q3_batcher_append_text is host-only: it validates and records and never touches the device. The tokens become visible to the
+ * frames, in arrival order, at the next FLUSH: at the start of every piece of q3_batcher_step, with no frame in flight, the
+ * pending tokens of all running open tickets are projected together (groups of eight across rows, each through the one path of
+ * q3_session_append_text: a token's row has the same bits) and published together, with one synchronisation. It works in every
+ * state of the ticket: queued (the tokens are part of the request when its side session is created), staged on the prefill
+ * worker (applied by the first flush after the row is entered) and running. last != 0 closes the text. After a close, or for a
+ * ticket not submitted open: Q3_INVALID_ARG; text beyond the row's slot (prompt_budget + 1024 rows, one of them taken):
+ * Q3_UNSUPPORTED, nothing of that call is taken and the ticket goes on; for a ticket that has ended: accepted and ignored.
+ * A row whose text is exhausted is HELD: it keeps its slot, counts in n_running, and a step in which every row is
+ * held replays no frame. For any feeding schedule a ticket's codes and PCM equal those of the closed request.
+ * q3_batcher_text_state: the fields of q3_session_text_state (tokens the next flush will publish included); for a queued ticket
+ * frames_committed is 0 and frames_runnable what its text allows.
+ * q3_batcher_cancel gives a ticket's place back, synchronously (call it between steps). Queued: it leaves the queue. Running: its
+ * row is collected with the frames it has committed and is free for the next step. The ticket reads Q3_TICKET_CANCELLED;
+ * q3_batcher_fetch returns its [n][16] codes — with want_pcm their decode, the first n * 1920 samples of the full run — and
+ * releases it; a streamed ticket's q3_batcher_read delivers every sample of the committed frames, then done = 1. DONE / FAILED /
+ * CANCELLED tickets: Q3_OK, nothing happens; an unknown ticket: Q3_INVALID_ARG. The other rows keep their bits. */
+enum { Q3_TICKET_CANCELLED = 4 };
+enum { Q3_WANT_CODES = 0, Q3_WANT_PCM = 1, Q3_WANT_STREAM = 2 };
+q3_status q3_batcher_submit_open(q3_batcher* b, const q3_request* req, int want, int64_t* ticket);
+q3_status q3_batcher_append_text(q3_batcher* b, int64_t ticket, const uint32_t* ids, int n, int last);
+q3_status q3_batcher_text_state(q3_batcher* b, int64_t ticket, int* n_text, int* frames_committed, int* frames_runnable, int* closed);
+q3_status q3_batcher_cancel(q3_batcher* b, int64_t ticket);
 
 /* Chunk decode mode of q3_session_next_chunk. 0 (default) = each chunk decoded as an independent utterance, exactly
  * as the reference does (lib.rs:1755-1758: audible seams, every chunk restarts from zero padding). 1 = continuous:

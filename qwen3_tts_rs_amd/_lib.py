@@ -118,6 +118,10 @@ SYMBOLS = {
     "q3_batcher_submit_streamed": (c_int, [c_void_p, c_void_p, P(ctypes.c_int64)]),
     "q3_batcher_read": (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_size_t, P(ctypes.c_size_t), P(c_int)]),
     "q3_batcher_stream_info": (c_int, [c_void_p, P(c_int), P(ctypes.c_size_t), P(c_int), P(c_int), P(c_int)]),
+    "q3_batcher_submit_open": (c_int, [c_void_p, c_void_p, c_int, P(ctypes.c_int64)]),
+    "q3_batcher_append_text": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_int]),
+    "q3_batcher_text_state": (c_int, [c_void_p, ctypes.c_int64, P(c_int), P(c_int), P(c_int), P(c_int)]),
+    "q3_batcher_cancel": (c_int, [c_void_p, ctypes.c_int64]),
     "q3_batcher_step": (c_int, [c_void_p, c_int, c_int, P(c_int), P(c_int), P(c_int)]),
     "q3_batcher_poll": (c_int, [c_void_p, ctypes.c_int64, P(c_int), P(c_int), P(ctypes.c_size_t)]),
     "q3_batcher_fetch": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, ctypes.c_size_t]),

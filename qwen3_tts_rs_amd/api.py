@@ -402,6 +402,8 @@ class Batcher:
     one session; `step` fills free rows, runs a few frames of the shared frame graph and collects finished rows. The
     scheduling loop is native — this class only marshals requests and results."""
     QUEUED, RUNNING, DONE, FAILED = 0, 1, 2, 3
+    CANCELLED = 4
+    _WANT = {"codes": 0, "pcm": 1, "stream": 2}
 
     def __init__(self, model: "Qwen3TTS", slots: int = 8, frame_budget: int = 2048, prompt_budget: int = 0,
                  options: Optional[SynthesisOptions] = None):
@@ -437,6 +439,37 @@ class Batcher:
         check(lib.q3_batcher_submit_streamed(self._h, ctypes.byref(r), ctypes.byref(t)))
         self._streamed.add(int(t.value))
         return int(t.value)
+
+    def submit_open(self, utt: Utterance, want: str = "stream") -> int:
+        """Queue one request whose text arrives in pieces (`append_text`); the utterance carries the first ids. want: "stream"
+        (samples through `read`), "pcm" or "codes" (through `fetch`). Returns its ticket."""
+        if want not in self._WANT:
+            raise ValueError(f"want must be one of {sorted(self._WANT)}, not {want!r}")
+        keep = []
+        r = CRequest(); fill_request(r, utt, self.options, keep)
+        t = ctypes.c_int64()
+        check(lib.q3_batcher_submit_open(self._h, ctypes.byref(r), self._WANT[want], ctypes.byref(t)))
+        if want == "stream":
+            self._streamed.add(int(t.value))
+        return int(t.value)
+
+    def append_text(self, ticket: int, ids: Sequence[int], last: bool = False):
+        """Append token ids to an open ticket, in any state (queued, being prefilled, running); last=True closes its text. Host
+        only: the frames see the tokens from the next `step` on."""
+        t = np.ascontiguousarray(list(ids), dtype=np.uint32)
+        check(lib.q3_batcher_append_text(self._h, int(ticket), t.ctypes.data_as(ctypes.c_void_p) if t.size else None, int(t.size),
+                                         1 if last else 0))
+
+    def text_state(self, ticket: int) -> dict:
+        """n_text (tokens received), frames_committed, frames_runnable (what the text allows now), closed."""
+        v = [ctypes.c_int() for _ in range(4)]
+        check(lib.q3_batcher_text_state(self._h, int(ticket), *[ctypes.byref(x) for x in v]))
+        return {"n_text": v[0].value, "frames_committed": v[1].value, "frames_runnable": v[2].value, "closed": bool(v[3].value)}
+
+    def cancel(self, ticket: int):
+        """Give a ticket's place back (between steps): a queued one leaves the queue, a running one keeps the frames it has
+        committed (`fetch` / `read` deliver them) and frees its row. The ticket reads CANCELLED."""
+        check(lib.q3_batcher_cancel(self._h, int(ticket)))
 
     def read(self, ticket: int, max_samples: Optional[int] = None) -> Tuple[np.ndarray, bool]:
         """(samples of a streamed ticket that have landed and were not read yet — at most max_samples —, done). Never blocks;

@@ -42,20 +42,34 @@ q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limi
     HIPC(d2d(s->U + (size_t)b * (s->max_frames + 2), side->U + (size_t)j * (side->max_frames + 2),
              (size_t)((side->max_frames < s->max_frames ? side->max_frames : s->max_frames) + 2) * 4));
     const int row0 = s->repl_base + b * s->row_cap;
-    HIPC(d2d(s->rows + (size_t)row0 * H, side->rows + (size_t)sq.row_base * H, (size_t)sq.n_rows * H * 4));
-    const int hv[4] = {row0 + (sq.trail_base - sq.row_base), sq.trailing_len, row0 + (sq.pad_row - sq.row_base), limit};
+    int hv[4] = {row0 + (sq.trail_base - sq.row_base), sq.trailing_len, row0 + (sq.pad_row - sq.row_base), limit};
+    if (sq.opened) {
+        // An open row (q3_batcher_submit_open) keeps the layout q3_session_open_text gives it: its trailing rows from the first row
+        // of the slot on, so that later text (session_append_many) lands behind them; the one prompt row the frames still read,
+        // tts_pad, goes to the slot's last row. Nothing else of the prompt's rows is read after the prefill.
+        if (!s->text_ready) return set_err(Q3_INVALID_ARG, "transplant_row: an open row needs the session's hold path (session_text_enable)");
+        hv[0] = row0; hv[2] = row0 + s->row_cap - 1;
+        if (sq.trailing_len > 0) HIPC(d2d(s->rows + (size_t)row0 * H, side->rows + (size_t)sq.trail_base * H, (size_t)sq.trailing_len * H * 4));
+        HIPC(d2d(s->rows + (size_t)hv[2] * H, side->rows + (size_t)sq.pad_row * H, (size_t)H * 4));
+    } else
+        HIPC(d2d(s->rows + (size_t)row0 * H, side->rows + (size_t)sq.row_base * H, (size_t)sq.n_rows * H * 4));
     HIPC(hipMemcpyAsync(s->trail_base + b, &hv[0], 4, hipMemcpyHostToDevice, s->stream));
     HIPC(hipMemcpyAsync(s->trail_len + b, &hv[1], 4, hipMemcpyHostToDevice, s->stream));
     HIPC(hipMemcpyAsync(s->pad_row + b, &hv[2], 4, hipMemcpyHostToDevice, s->stream));
     HIPC(hipMemcpyAsync(s->limit + b, &hv[3], 4, hipMemcpyHostToDevice, s->stream));
-    static const int text_closed = 0x7fffffff;        // an opened row (q3_session_open_text) gets an ordinary closed request
-    if (s->text_ready) HIPC(hipMemcpyAsync(s->text_ready + b, &text_closed, 4, hipMemcpyHostToDevice, s->stream));
+    // frames the row's text allows: everything for a closed request (also in a row that was open before), the side row's own
+    // count for an open one
+    const int ready = sq.opened ? sq.ready : 0x7fffffff;
+    if (s->text_ready) HIPC(hipMemcpyAsync(s->text_ready + b, &ready, 4, hipMemcpyHostToDevice, s->stream));
     const SampleRow srow = sample_row(sq.req.opts);
     HIPC(hipMemcpyAsync(s->sample_rows + b, &srow, sizeof srow, hipMemcpyHostToDevice, s->stream));
     HIPC(sync_frames(s));
     SeqInfo nq = sq;
     nq.row_base = row0; nq.trail_base = hv[0]; nq.pad_row = hv[2];
     nq.start_run = s->frames_run; nq.limit = limit; nq.n_frames = 0; nq.done = false; nq.stream_pos = 0; nq.req.opts.max_length = limit; nq.idle = false;
+    // (opened, text_closed, text_all, n_trail, ready came along with sq) an open ICL row resolves its length cap against the
+    // request's own max_length when its text closes (open_counts): the side session was created with the session's frame budget
+    if (sq.opened) { nq.committed = 0; nq.max_length_req = limit; }
     s->seq[(size_t)b] = nq;
     {   // the request's arrays live in the row's own vectors (the caller's pointers need not outlive the call)
         SeqInfo& q = s->seq[(size_t)b];
@@ -73,6 +87,7 @@ q3_status transplant_check(q3_session* s, q3_session* side, int j, int limit_req
     if (side->opts.chunk_frames != s->opts.chunk_frames) return set_err(Q3_UNSUPPORTED, "q3_session_replace: chunk_frames is a property of the session");
     const int limit = limit_req < sq.limit ? limit_req : sq.limit;
     if (sq.n_rows > s->row_cap) return set_err(Q3_UNSUPPORTED, "q3_session_replace: the request's %d text rows exceed the session's slot (%d rows: 1024, or the longest text of the original batch)", sq.n_rows, s->row_cap);
+    if (sq.opened && sq.trailing_len + 1 > s->row_cap - 1) return set_err(Q3_UNSUPPORTED, "q3_session_replace: the open request's %d trailing text rows exceed the session's slot (%d rows)", sq.trailing_len + 1, s->row_cap - 1);
     if (s->paged != side->paged) return set_err(Q3_UNSUPPORTED, "q3_session_replace: the sessions disagree on KV paging");
     if (s->kv_bf16 != s->kv_in_bf16) return set_err(Q3_UNSUPPORTED, "q3_session_replace: the session's K/V conversion has not happened yet");
     // max_seq bounds a row in both layouts: the captured frame was specialised for it (key splits, the page-table form of the
@@ -82,7 +97,16 @@ q3_status transplant_check(q3_session* s, q3_session* side, int j, int limit_req
     return Q3_OK;
 }
 
-extern "C" q3_status q3_session_replace(q3_session* s, int b, const q3_request* req) {
+// a one-row side session takes the request with its text open (and already closed again, if the close came before the prefill)
+static q3_status side_open_text(q3_session* side, bool closed) {
+    Q3C(q3_session_open_text(side, 0));
+    if (closed) Q3C(q3_session_append_text(side, 0, nullptr, 0, 1));
+    return Q3_OK;
+}
+static q3_status session_replace(q3_session* s, int b, const q3_request* req, bool open_text, bool closed);
+extern "C" q3_status q3_session_replace(q3_session* s, int b, const q3_request* req) { return session_replace(s, b, req, false, false); }
+// open_text: the batcher's open tickets (the public call installs a closed request)
+static q3_status session_replace(q3_session* s, int b, const q3_request* req, bool open_text, bool closed) {
     if (!s || !req || b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_replace: bad argument");
     if (!s->prefilled) return set_err(Q3_INVALID_ARG, "q3_session_replace: session not prefilled");
     if (s->debug || s->profile) return set_err(Q3_UNSUPPORTED, "q3_session_replace: not on debug / profiling sessions");
@@ -98,9 +122,11 @@ extern "C" q3_status q3_session_replace(q3_session* s, int b, const q3_request* 
         if (timing) fprintf(stderr, "[q3 replace] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count());
     };
     q3_session* side_raw = nullptr;
-    Q3C(session_create(s->m, &r, 1, 0, 0, &side_raw, s->stream));      // on the host's stream: its frames and this prefill are serial anyway
+    // (an open request: with the host's frame budget — an ICL row's length cap, which would size the side session, is not known yet)
+    Q3C(session_create(s->m, &r, 1, open_text ? s->max_frames : 0, 0, &side_raw, s->stream));      // on the host's stream: its frames and this prefill are serial anyway
     std::unique_ptr<q3_session> side(side_raw);
     side->kv_bf16 = s->kv_bf16;                        // the side session prefills in f32 and converts, as the host session did
+    if (open_text) Q3C(side_open_text(side.get(), closed));
     lap("create");
     // (sampling options are per row — SampleRow —, resolved by the side session: an ICL request's repetition-penalty floor and
     // length cap, lib.rs:913-929, come along)
@@ -136,6 +162,11 @@ struct BatTicket {
     int s_pending = 0; std::vector<float> spcm; size_t s_read = 0;     // parts queued or running; landed samples; samples read
     bool s_failed = false; q3_status s_st = Q3_OK; std::string s_err;
     std::vector<uint32_t> s_all; int s_deliv = 0;                      // reference | generated frames seen so far; frames whose samples landed
+    // An open ticket (q3_batcher_submit_open): text_all = every token received so far (q3_batcher_append_text only records), closed =
+    // the host has closed the text. n_taken / close_taken = what the ticket's row — or the side session that is being prefilled
+    // for it — already holds; the rest goes in with the next flush of q3_batcher_step. Host thread only.
+    bool open = false, closed = false, close_taken = false; std::vector<uint32_t> text_all; size_t n_taken = 0;
+    bool cancelled = false;                             // q3_batcher_cancel took its row (or its place in the queue)
 };
 // frames [f0, f0 + n) of a streamed ticket for the stream row of its slot: `first` resets the row (and primes it with the ticket's
 // reference frames), `last` gives the row's blocks back once the samples have landed
@@ -162,6 +193,9 @@ struct q3_batcher {
     // streamed tickets: the parts of the step in progress (one job at its end), the stream's shape (environment, read at create)
     std::vector<StreamPart> sparts; int n_streamed = 0;
     int s_block_frames = 128, s_max_blocks = 0;
+    bool want_text = false;                           // an open ticket was submitted: the session runs the frame with the hold kernels
+    // Q3_BAT_TEXT_STATS=1 (development aid): what the text flushes did, printed when the batcher is freed
+    long tx_flushes = 0, tx_tokens = 0, tx_steps = 0; double tx_ms = 0;
 };
 // Round 6: a finished row's vocoder no longer stalls the session either. bat_collect used to decode the row's samples on the session's
 // own stream before the row could be refilled — every live row stood still for ~20 ms per 640 frames. The codes are on the host
@@ -207,7 +241,7 @@ static void stream_settle(q3_batcher* b, BatTicket& t, bool wait) {
     if (wait) d.cv_done.wait(lk, [&] { return t.s_pending == 0; });
     if (t.state != Q3_TICKET_RUNNING || t.row >= 0) return;
     if (t.s_failed) { t.state = Q3_TICKET_FAILED; t.st = t.s_st; t.err = t.s_err; }
-    else if (t.s_ended && t.s_pending == 0) t.state = Q3_TICKET_DONE;
+    else if (t.s_ended && t.s_pending == 0) t.state = t.cancelled ? Q3_TICKET_CANCELLED : Q3_TICKET_DONE;
 }
 static void ticket_wait_decode(q3_batcher* b, BatTicket& t) {
     if (!t.decoding) return;
@@ -218,7 +252,7 @@ static void ticket_wait_decode(q3_batcher* b, BatTicket& t) {
     }
     t.decoding = false;
     if (t.dec_st != Q3_OK) { t.state = Q3_TICKET_FAILED; t.st = t.dec_st; t.err = t.dec_err; t.pcm.clear(); }
-    else t.state = Q3_TICKET_DONE;
+    else t.state = t.cancelled ? Q3_TICKET_CANCELLED : Q3_TICKET_DONE;
 }
 static void decoder_stop(q3_batcher* b) {
     BatDecoder& d = *b->dec;
@@ -364,7 +398,8 @@ static void stage_drop(q3_batcher* b) {
 // request occupies yet)
 static q3_status session_idle_row(q3_session* s, int b) {
     SeqInfo& q = s->seq[b];
-    int ran = s->frames_run - q.start_run; if (ran < 0) ran = 0; if (ran > q.limit) ran = q.limit;
+    int ran = q.opened ? q.committed : s->frames_run - q.start_run;      // (a held row replayed frames it did not commit)
+    if (ran < 0) ran = 0; if (ran > q.limit) ran = q.limit;
     q.limit = ran;
     HIPC(sync_frames(s));          // no frame in flight while the row's limit and pages change
     HIPC(q3_hipMemcpy(s->limit + b, &q.limit, sizeof(int), hipMemcpyHostToDevice));
@@ -427,6 +462,9 @@ extern "C" q3_status q3_batcher_create(q3_model* m, int slots, int frame_budget,
 extern "C" void q3_batcher_free(q3_batcher* b) {
     if (!b) return;
     stage_drop(b);
+    if (b->tx_steps > 0 && getenv("Q3_BAT_TEXT_STATS"))
+        fprintf(stderr, "[q3 batcher text] %ld flushes in %ld steps, %ld tokens, %.3f ms in flushes (%.4f ms per step)\n", b->tx_flushes, b->tx_steps, b->tx_tokens,
+                b->tx_ms, b->tx_ms / b->tx_steps);
     if (b->dec) decoder_stop(b);                       // finishes what is queued (tickets nobody will fetch included), then ends the worker
     if (b->s) q3_session_free(b->s);
     delete b;
@@ -455,6 +493,96 @@ static q3_status batcher_submit(q3_batcher* b, const q3_request* req, int want_p
     b->t[id] = std::move(t);
     b->queue.push_back(id);
     *ticket = id;
+    return Q3_OK;
+}
+
+// ---- open tickets: the text arrives in pieces ----
+// trailing text rows of a text of n_text tokens: what the prefill does not consume (open_trailing_ids of q3_session.hip)
+static int ticket_n_trail(const BatTicket& t, size_t n_text) {
+    const q3_request& r = t.req.r;
+    const bool icl = r.mode == Q3_MODE_VOICE_CLONE && r.n_ref > 0 && r.ref_codes && r.ref_text_ids;
+    if (!icl) return n_text > 1 ? (int)n_text - 1 : 0;
+    const long all = (long)r.n_ref_text + (long)n_text, n_icl = (long)r.n_ref + 1;
+    return all > n_icl ? (int)(all - n_icl) : 0;
+}
+// the frame limit of an open ticket with the text it has: its max_length, for an ICL ticket whose text is closed the length cap too
+static int ticket_limit(const BatTicket& t) {
+    const q3_request& r = t.req.r;
+    const bool icl = r.mode == Q3_MODE_VOICE_CLONE && r.n_ref > 0 && r.ref_codes && r.ref_text_ids;
+    int lim = r.opts.max_length;
+    if (icl && t.closed) { int cap = 6 * (int)t.text_all.size(); if (cap < 75) cap = 75; if (lim > cap) lim = cap; }
+    return lim;
+}
+// text rows a slot of the batcher's session takes from an open ticket (its last row holds tts_pad: transplant_row)
+static int batcher_text_cap(const q3_batcher* b) { return (b->prompt_budget > 16 ? b->prompt_budget : 16) + 1024 - 1; }
+
+extern "C" q3_status q3_batcher_submit_open(q3_batcher* b, const q3_request* req, int want, int64_t* ticket) {
+    if (!b || !req || !ticket) return set_err(Q3_INVALID_ARG, "q3_batcher_submit_open: null argument");
+    if (want != Q3_WANT_CODES && want != Q3_WANT_PCM && want != Q3_WANT_STREAM) return set_err(Q3_INVALID_ARG, "q3_batcher_submit_open: want %d is none of Q3_WANT_CODES / _PCM / _STREAM", want);
+    if (b->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_batcher_submit_open: the model has no device (manifest-only)");
+    // what q3_session_open_text asks of the row (the side session is opened when the ticket reaches the head of the queue)
+    if (req->n_text < 1 || !req->text_ids)
+        return set_err(Q3_INVALID_ARG, "q3_session_open_text: the request has no text token (an open row needs one at creation: the prefill consumes it)");
+    for (int i = 0; i < req->n_text; ++i) if (req->text_ids[i] >= (uint32_t)b->m->cfg.text_vocab) return set_err(Q3_INVALID_ARG, "text id %u out of range", req->text_ids[i]);
+    if (req->mode == Q3_MODE_VOICE_CLONE && req->n_ref > 0 && req->ref_codes && req->ref_text_ids) {
+        const int need = req->n_ref + 1 - req->n_ref_text;
+        if (req->n_text < need)
+            return set_err(Q3_INVALID_ARG, "q3_session_open_text: the ICL request needs at least %d target text tokens at creation (%d given), so that tts_eos falls after the ICL block", need, req->n_text);
+        if (req->opts.max_length > b->frame_budget)
+            return set_err(Q3_UNSUPPORTED, "q3_session_open_text: the ICL request asks for max_length %d beyond the frame budget %d (its length cap is resolved when the text closes)", req->opts.max_length, b->frame_budget);
+    }
+    int64_t id = 0;
+    if (want == Q3_WANT_STREAM) Q3C(q3_batcher_submit_streamed(b, req, &id));
+    else Q3C(batcher_submit(b, req, want == Q3_WANT_PCM, false, &id));
+    BatTicket& t = *b->t[id];
+    t.open = true; t.text_all = t.req.text;
+    if (ticket_n_trail(t, t.text_all.size()) + 1 > batcher_text_cap(b)) {
+        b->queue.pop_back(); if (t.streamed) b->n_streamed--; b->t.erase(id);
+        return set_err(Q3_UNSUPPORTED, "q3_batcher_submit_open: the text exceeds the row's slot (%d rows)", batcher_text_cap(b));
+    }
+    b->want_text = true;
+    *ticket = id;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_append_text(q3_batcher* b, int64_t ticket, const uint32_t* ids, int n, int last) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_append_text: null batcher");
+    if (n < 0 || (n > 0 && !ids)) return set_err(Q3_INVALID_ARG, "q3_batcher_append_text: bad token id array");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_append_text: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.open) return set_err(Q3_INVALID_ARG, "q3_batcher_append_text: ticket %lld was not submitted open (q3_batcher_submit_open)", (long long)ticket);
+    if (t.closed) return set_err(Q3_INVALID_ARG, "q3_batcher_append_text: ticket %lld's text is already closed", (long long)ticket);
+    for (int i = 0; i < n; ++i) if (ids[i] >= (uint32_t)b->m->cfg.text_vocab) return set_err(Q3_INVALID_ARG, "text id %u out of range", ids[i]);
+    const int rows = ticket_n_trail(t, t.text_all.size() + (size_t)n) + 1;
+    if (rows > batcher_text_cap(b)) return set_err(Q3_UNSUPPORTED, "q3_batcher_append_text: %d trailing text rows exceed the row's slot (%d)", rows, batcher_text_cap(b));
+    // recorded only: the frames see it after the next flush (q3_batcher_step). A ticket that has ended takes it and ignores it.
+    t.text_all.insert(t.text_all.end(), ids, ids + n);
+    if (last) t.closed = true;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_text_state(q3_batcher* b, int64_t ticket, int* n_text, int* frames_committed, int* frames_runnable, int* closed) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_text_state: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_text_state: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    int committed = 0, runnable = 0;
+    // what the text received so far allows (tokens the next flush will publish included), as q3_session_text_state counts
+    const int lim = t.open ? ticket_limit(t) : 0;
+    const int allowed = !t.open ? 0 : t.closed ? lim : std::min(lim, ticket_n_trail(t, t.text_all.size()));
+    if (t.state == Q3_TICKET_QUEUED) runnable = t.open ? allowed : t.req.r.opts.max_length;
+    else if (t.row >= 0 && b->s) {
+        int done = 0;
+        Q3C(q3_session_frames(b->s, t.row, nullptr, &done));
+        committed = session_row_committed(b->s, t.row);
+        runnable = done ? 0 : (t.open ? allowed : b->s->seq[(size_t)t.row].limit) - committed;
+        if (runnable < 0) runnable = 0;
+    } else committed = t.n_frames;
+    if (n_text) *n_text = (int)(t.open ? t.text_all.size() : t.req.text.size());
+    if (frames_committed) *frames_committed = committed;
+    if (frames_runnable) *frames_runnable = runnable;
+    if (closed) *closed = (!t.open || t.closed) ? 1 : 0;
     return Q3_OK;
 }
 
@@ -505,7 +633,7 @@ static q3_status bat_collect(q3_batcher* b, int row) {
             t.pcm.resize(ns);
         }
     }
-    t.state = async ? Q3_TICKET_RUNNING : Q3_TICKET_DONE; t.row = -1;
+    t.state = async ? Q3_TICKET_RUNNING : t.cancelled ? Q3_TICKET_CANCELLED : Q3_TICKET_DONE; t.row = -1;
     b->owner[row] = -1; b->commit[row] = 0;
     // the device freezes a row at its frame limit, not at EOS: idle it now so that it stops advancing — and taking pages — while
     // the queue is empty or waits for room; its pages but one go back to the pool
@@ -543,15 +671,20 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
         for (int r = 0; r < b->slots; ++r) Q3C(session_idle_row(s, r));
     }
     if (!b->s) { if (n_running) *n_running = 0; if (n_queued) *n_queued = 0; if (n_finished) *n_finished = finished; return Q3_OK; }
+    // the first open ticket switches the hold path on: text_ready and the append scratch; a frame captured before is captured
+    // again by the next q3_session_generate (nothing is in flight between two steps). Never for a batcher without open tickets.
+    if (b->want_text && !b->s->text_ready) Q3C(session_text_enable(b->s));
+    if (b->want_text) b->tx_steps++;
     // Admission under a page limit (q3_model_kv_pool_limit): a request enters a row only if its WORST CASE (prompt + max_length
     // positions; row_worst_units) fits beside what the running rows may still come to hold and what everything else on the model
     // holds now — so a page shortage shows up here, as a request that waits in the queue (rows are running: room will come) or
     // fails on its ticket (it cannot fit even alone), never in the middle of a generation where it would stop every row.
     auto held_units = [&](int r) -> long { return (long)b->s->kv_rows[(size_t)r].size() * (b->s->kv_in_bf16 ? 1 : 2); };
-    auto admit = [&](const q3_request& rq, long* units_out, bool* wait) -> bool {
+    auto admit = [&](const q3_request& rq, bool open, long* units_out, bool* wait) -> bool {
         *wait = false; *units_out = 0;
         if (!b->s->paged) return true;
         int S = 0, lim = 0; request_shape(rq, &S, &lim);
+        if (open) lim = rq.opts.max_length;          // an open ICL ticket's length cap is not known before its text closes
         const long units = row_worst_units(S, lim, b->s->kv_bf16);
         *units_out = units;
         long mine = 0, claimed = 0; int running = 0;
@@ -574,7 +707,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
                 const int64_t id = b->queue.front();
                 BatTicket& t = *b->t[id];
                 long units = 0; bool wait = false;
-                if (!admit(t.req.r, &units, &wait)) {
+                if (!admit(t.req.r, t.open, &units, &wait)) {
                     if (wait) return Q3_OK;          // FIFO: the head of the queue waits for running rows to end
                     b->queue.erase(b->queue.begin());
                     if (b->stage.id == id) stage_drop(b);      // (a limit set after it was prefilled ahead) its side session goes with it
@@ -597,6 +730,12 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
                         if (st == Q3_OK) st = transplant_row(b->s, r, b->stage.side, 0, b->stage.limit);
                     }
                     stage_drop(b);
+                } else if (t.open) {
+                    // with the text it has at this moment; what arrives later goes in with the flushes
+                    q3_request rq = t.req.r;
+                    rq.text_ids = t.text_all.data(); rq.n_text = (int32_t)t.text_all.size();
+                    t.n_taken = t.text_all.size(); t.close_taken = t.closed;
+                    st = session_replace(b->s, r, &rq, true, t.closed);
                 } else
                     st = q3_session_replace(b->s, r, &t.req.r);
                 if (st != Q3_OK) { bat_fail(t, st); finished++; continue; }     // does not fit: the ticket carries the reason; try the next one
@@ -608,7 +747,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
     };
     // the head of the queue starts its prefill on the worker (see q3_batcher::Stage); called with frames about to be queued
     auto stage_begin = [&]() {
-        static const bool off = getenv("Q3_BAT_NO_STAGE") != nullptr;
+        const bool off = getenv("Q3_BAT_NO_STAGE") != nullptr;      // (read per step: a test flips it between two batchers)
         if (off || b->stage.id >= 0 || b->queue.empty() || b->s->debug || b->s->profile) return;
         // not while this thread may still CAPTURE the host session's frame (the first graph step): one thing less to go wrong
         // (captures are in relaxed mode and repeated when invalidated: q3_session.hip frame_capture)
@@ -621,17 +760,25 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
         BatTicket& t = *b->t[id];
         q3_request rq = t.req.r;                     // (arrays owned by the ticket, which lives until it is fetched)
         rq.opts.chunk_frames = b->chunk_frames;
+        // an open ticket is staged with a copy of the text it has now (q3_batcher_append_text may grow the ticket's own while the
+        // worker reads); what arrives later is applied by the first flush after the transplant
+        const bool open = t.open, closed = t.closed;
+        std::vector<uint32_t> text_now;
+        if (open) { text_now = t.text_all; t.n_taken = text_now.size(); t.close_taken = closed; }
         const int limit_req = rq.opts.max_length;
         if (limit_req < 1 || limit_req > b->s->max_frames) return;      // the synchronous path reports it on the ticket
         rq.opts.max_length = b->s->max_frames;       // the side session draws the row's PCG stream with the host session's stride
         b->stage.id = id; b->stage.st = Q3_OK; b->stage.err.clear(); b->stage.side = nullptr; b->stage.limit = 0;
         q3_batcher* bp = b;
         try {
-        b->stage.thr = std::thread([bp, rq, limit_req]() {
+        b->stage.thr = std::thread([bp, rq, limit_req, open, closed, text_now]() {
             q3_batcher::Stage& g = bp->stage;
             q3_session* side = nullptr;
+            q3_request rw = rq;
+            if (open) { rw.text_ids = text_now.data(); rw.n_text = (int32_t)text_now.size(); }
             q3_status st = hipSetDevice(bp->m->device) == hipSuccess ? Q3_OK : set_err(Q3_HIP_ERROR, "hipSetDevice");
-            if (st == Q3_OK) st = session_create(bp->m, &rq, 1, 0, 0, &side);          // a stream of its own: runs beside the frames
+            if (st == Q3_OK) st = session_create(bp->m, &rw, 1, open ? bp->s->max_frames : 0, 0, &side);          // a stream of its own: runs beside the frames
+            if (st == Q3_OK && open) st = side_open_text(side, closed);
             if (st == Q3_OK) { side->kv_bf16 = bp->s->kv_bf16; st = transplant_check(bp->s, side, 0, limit_req, &g.limit); }
             if (st == Q3_OK) st = q3_session_prefill(side);                            // ends with a synchronisation of that stream
             g.side = side; g.st = st;
@@ -642,13 +789,37 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
     // Run in pieces that end where the next row reaches its frame limit: that row is collected and refilled at once instead of
     // idling to the end of the step (a row that ends on EOS is noticed at q3_session_generate's 32-frame check or at the
     // end of the piece)
+    // The text flush, at the start of every piece (nothing is in flight): what q3_batcher_append_text recorded for the running
+    // open tickets since their last flush — tickets that were queued or staged meanwhile included — goes to the device in one
+    // session_append_many: projected together, published together, one synchronisation.
+    auto flush_text = [&]() -> q3_status {
+        if (!b->want_text) return Q3_OK;
+        std::vector<TextPiece> pieces;
+        for (int r = 0; r < b->slots; ++r) {
+            if (b->owner[r] < 0) continue;
+            BatTicket& t = *b->t[b->owner[r]];
+            if (!t.open || (t.n_taken == t.text_all.size() && t.close_taken == t.closed)) continue;
+            pieces.push_back({r, t.text_all.data() + t.n_taken, (int)(t.text_all.size() - t.n_taken), t.closed});
+        }
+        if (pieces.empty()) return Q3_OK;
+        const auto t0 = std::chrono::steady_clock::now();
+        Q3C(session_append_many(b->s, pieces));
+        for (const TextPiece& p : pieces) {
+            BatTicket& t = *b->t[b->owner[p.b]];
+            b->tx_tokens += p.n; t.n_taken = t.text_all.size(); t.close_taken = t.closed;
+        }
+        b->tx_flushes++; b->tx_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return Q3_OK;
+    };
     for (int left = n_frames; left > 0;) {
         Q3C(fill());
+        Q3C(flush_text());
         int piece = left, busy = 0;
         for (int r = 0; r < b->slots; ++r) {
             if (b->owner[r] < 0) continue;
-            const SeqInfo& q = b->s->seq[r];
-            const int rem = q.limit - (b->s->frames_run - q.start_run);
+            // (an open row's progress is what it has COMMITTED, not frames_run - start_run: it may have been held; a held row —
+            // nothing runnable with the text it has — does not make the piece busy)
+            const int rem = session_row_remaining(b->s, r);
             if (rem > 0) { busy++; if (rem < piece) piece = rem; }
         }
         if (busy > 0) {
@@ -673,7 +844,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
             {   // a row without a live EOS id ends exactly at its frame limit, which the host knows: no device read-back (a
                 // synchronisation and nine blocking copies per step) while no row can have ended
                 const SeqInfo& q = b->s->seq[r];
-                if (q.req.opts.eos_token_id < 0 && b->s->frames_run - q.start_run < q.limit) continue;
+                if (q.req.opts.eos_token_id < 0 && session_row_committed(b->s, r) < q.limit) continue;
             }
             int n = 0, done = 0;
             Q3C(q3_session_frames(b->s, r, &n, &done));
@@ -716,6 +887,37 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
     return Q3_OK;
 }
 
+// A ticket whose client went away gives its place back. Synchronous: between two steps nothing of the session is in flight.
+// Queued: it leaves the queue (a side session staged for it is dropped with its pages). Running: its row is collected with the
+// frames it has committed — the codes, and their samples: every layer of the vocoder is causal, so they are the first n * 1920
+// samples of what the full run would have given; a streamed ticket's last part goes to the worker with last = true, which gives
+// the slot's blocks back —, idled, and free for the next fill. The samples are waited for here, so the ticket reads CANCELLED on return.
+extern "C" q3_status q3_batcher_cancel(q3_batcher* b, int64_t ticket) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_cancel: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_cancel: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (t.state == Q3_TICKET_QUEUED) {
+        b->queue.erase(std::remove(b->queue.begin(), b->queue.end(), ticket), b->queue.end());
+        if (b->stage.id == ticket) stage_drop(b);
+        t.cancelled = true; t.state = Q3_TICKET_CANCELLED; t.n_frames = 0; t.s_ended = true;
+        return Q3_OK;
+    }
+    if (t.state != Q3_TICKET_RUNNING || t.row < 0) return Q3_OK;      // DONE / FAILED / CANCELLED, or ended and with the decode worker: nothing to take back
+    const int row = t.row;
+    t.cancelled = true;
+    const q3_status st = bat_collect(b, row);
+    if (st != Q3_OK) {           // the row could not be read: the ticket fails, the row is given up all the same
+        bat_fail(t, st); t.decoding = false;
+        b->owner[row] = -1; b->commit[row] = 0;
+        (void)session_idle_row(b->s, row);
+        return set_err(st, "%s", t.err.c_str());
+    }
+    ticket_wait_decode(b, t);
+    stream_settle(b, t, true);
+    return Q3_OK;
+}
+
 extern "C" q3_status q3_batcher_poll(q3_batcher* b, int64_t ticket, int* state, int* n_frames, size_t* n_samples) {
     if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_poll: null batcher");
     auto it = b->t.find(ticket);
@@ -726,8 +928,7 @@ extern "C" q3_status q3_batcher_poll(q3_batcher* b, int64_t ticket, int* state, 
     if (state) *state = t.state;                                         // a ticket still being vocoded reads RUNNING
     int nf = t.n_frames;
     if (t.state == Q3_TICKET_RUNNING && b->s && t.row >= 0) {       // frames run so far (an EOS inside them is only looked at when the row is collected)
-        const SeqInfo& q = b->s->seq[t.row];
-        nf = b->s->frames_run - q.start_run; if (nf > q.limit) nf = q.limit; if (nf < 0) nf = 0;
+        nf = session_row_committed(b->s, t.row);      // (an open row: the frames it committed — it may have been held)
     }
     if (n_frames) *n_frames = nf;
     if (n_samples) *n_samples = t.pcm.size();         // (of a ticket still being vocoded: the samples it WILL hold — the size q3_batcher_fetch wants)
@@ -744,7 +945,7 @@ extern "C" q3_status q3_batcher_fetch(q3_batcher* b, int64_t ticket, uint32_t* c
     if (t.streamed) {
         // a ticket the worker may still hold parts of is not released under it: a finished (or failed) one waits for them
         if (t.row < 0) stream_settle(b, t, true);      // (a FAILED one too: the queue may still hold parts that name it)
-        if (t.state == Q3_TICKET_DONE && pcm_host)
+        if ((t.state == Q3_TICKET_DONE || t.state == Q3_TICKET_CANCELLED) && pcm_host)
             return set_err(Q3_INVALID_ARG, "q3_batcher_fetch: ticket %lld is streamed: its samples go through q3_batcher_read", (long long)ticket);
     }
     if (t.state == Q3_TICKET_FAILED) {
@@ -753,7 +954,7 @@ extern "C" q3_status q3_batcher_fetch(q3_batcher* b, int64_t ticket, uint32_t* c
         b->t.erase(it);
         return set_err(st, "%s", err.c_str());
     }
-    if (t.state != Q3_TICKET_DONE) return set_err(Q3_INVALID_ARG, "q3_batcher_fetch: ticket %lld has not finished", (long long)ticket);
+    if (t.state != Q3_TICKET_DONE && t.state != Q3_TICKET_CANCELLED) return set_err(Q3_INVALID_ARG, "q3_batcher_fetch: ticket %lld has not finished", (long long)ticket);
     if (codes_host) {
         if (cap_frames < t.n_frames) return set_err(Q3_INVALID_ARG, "codes buffer too small (%d < %d frames)", cap_frames, t.n_frames);
         memcpy(codes_host, t.codes.data(), t.codes.size() * 4);
@@ -784,7 +985,7 @@ extern "C" q3_status q3_batcher_read(q3_batcher* b, int64_t ticket, float* pcm_h
     if (n > 0) memcpy(pcm_host, t.spcm.data() + t.s_read, n * 4);
     t.s_read += n;
     *n_samples = n;
-    *done = (t.state == Q3_TICKET_DONE && t.s_read == t.spcm.size()) ? 1 : 0;
+    *done = ((t.state == Q3_TICKET_DONE || t.state == Q3_TICKET_CANCELLED) && t.s_read == t.spcm.size()) ? 1 : 0;
     return Q3_OK;
 }
 

@@ -411,6 +411,7 @@ struct q3_session {
     // take their closed-text paths) and the scratch of the one projection path appended tokens take (8-row GEMV groups)
     int* text_ready = nullptr;
     uint32_t* app_ids = nullptr; float *app_e = nullptr, *app_h = nullptr, *app_out = nullptr;
+    int* flush_buf = nullptr; size_t flush_cap = 0;       // the batcher's text flush (session_append_many): [ids | destination rows | entries to publish]
     uint32_t* tok = nullptr; uint8_t* seen = nullptr; int *frame_idx = nullptr, *pos = nullptr, *token_count = nullptr;
     float* U = nullptr; uint32_t* codes = nullptr;
     float* logits_hist = nullptr; float* cp_logits_hist = nullptr; bool debug = false;
@@ -501,6 +502,12 @@ Q3_HIDDEN q3_status session_create(q3_model* m, const q3_request* reqs, int batc
 Q3_HIDDEN q3_status lm_layer(q3_session* s, const LmDims& d, const LayerW& w, LmBuf& b, float* kc, float* vc, int max_seq,
                              const int* pos_dev, int pos_static, int n_splits, int rows_per_seq = 1, bool skip_qkv = false,
                              const CpGatherArgs* fold = nullptr, int paged_layer = -1);
+// open text through the batcher: switch the hold path on; one flush over many rows; a row's progress
+struct TextPiece { int b; const uint32_t* ids; int n; bool last; };      // n tokens for open row b; last: its text closes
+Q3_HIDDEN q3_status session_text_enable(q3_session* s);
+Q3_HIDDEN q3_status session_append_many(q3_session* s, const std::vector<TextPiece>& pieces);
+Q3_HIDDEN int session_row_remaining(const q3_session* s, int b);
+Q3_HIDDEN int session_row_committed(const q3_session* s, int b);
 // q3_batcher.hip
 Q3_HIDDEN q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limit);
 Q3_HIDDEN q3_status transplant_check(q3_session* s, q3_session* side, int j, int limit_req, int* limit_out);

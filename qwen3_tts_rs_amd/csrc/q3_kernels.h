@@ -231,6 +231,10 @@ hipError_t launch_assemble_rows(const float* rows, const int* text_row, const ui
                                 const float* xvec, float* out, int n, int H, hipStream_t st,
                                 const uint32_t* ref_codes = nullptr, const uint16_t* const* cp_embs = nullptr);   // codec_id <= -3: ICL ref frame -3-id
 hipError_t launch_copy_rows(const float* src, int lds, float* dst, int ldd, int rows, int cols, hipStream_t st);
+// text flush of the batcher: rows[dst_row[r]][0..cols) = src[r][0..cols) for the n_src source rows whose dst_row[r] >= 0 (device
+// list; the caller bounds every index), then n entries {b, trail_len, text_ready, limit} written to the per-row arrays
+hipError_t launch_scatter_rows(const float* src, const int* dst_row, float* rows, int n_src, int cols, hipStream_t st);
+hipError_t launch_publish_text(const int* ent, int n, int* trail_len, int* text_ready, int* limit, hipStream_t st);
 
 struct CpGatherArgs {
     int pass;                        // 0..15

@@ -1274,6 +1274,33 @@ hipError_t launch_copy_rows(const float* src, int lds, float* dst, int ldd, int 
     return hipGetLastError();
 }
 
+// Row scatter of the batcher's text flush: source row r of a projection group goes to row dst_row[r] of `rows`, the
+// destinations read from a device list (-1 = a padding row of the group: skipped). One group's rows belong to different
+// session rows' slots, so there is no common stride a k_copy_rows could use.
+__global__ __launch_bounds__(256) void k_scatter_rows(const float* src, const int* dst_row, float* rows, int cols) {
+    const size_t r = blockIdx.x;
+    const int d = dst_row[r];
+    if (d < 0) return;
+    for (int c = threadIdx.x; c < cols; c += 256) rows[(size_t)d * cols + c] = src[r * cols + c];
+}
+hipError_t launch_scatter_rows(const float* src, const int* dst_row, float* rows, int n_src, int cols, hipStream_t st) {
+    if (n_src <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_scatter_rows, dim3(n_src), dim3(256), 0, st, src, dst_row, rows, cols);
+    return hipGetLastError();
+}
+// ... and what the frame reads of the rows it announces, in one launch behind the scatters: n entries {b, trail_len, text_ready, limit}
+__global__ __launch_bounds__(64) void k_publish_text(const int* ent, int n, int* trail_len, int* text_ready, int* limit) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int b = ent[4 * i];
+    trail_len[b] = ent[4 * i + 1]; text_ready[b] = ent[4 * i + 2]; limit[b] = ent[4 * i + 3];
+}
+hipError_t launch_publish_text(const int* ent, int n, int* trail_len, int* text_ready, int* limit, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_publish_text, dim3((n + 63) / 64), dim3(64), 0, st, ent, n, trail_len, text_ready, limit);
+    return hipGetLastError();
+}
+
 // Code-predictor input of pass p (code_predictor.rs:337-345, 386-396): pass 0 = talker hidden,
 // pass 1 = semantic embedding, pass p>=2 = embedding (table p-2) of argmax(previous pass logits);
 // the argmax'd code is also recorded as codes[b][frame][p-1].

@@ -814,9 +814,23 @@ static void open_counts(SeqInfo& q) {
 // Appended text rows take ONE projection path whatever a call carries: 8-row GEMV groups, the unused rows of the last group
 // padded in scratch. (text_project picks two GEMMs from 48 rows on, and at 1.7B the two sum in different orders: a token's bits
 // would depend on what it was projected with.) Rows [dst, dst + n) of row b's slot; queued on the session stream.
-static q3_status project_appended(q3_session* s, int b, const std::vector<uint32_t>& ids, int dst) {
+// One group: 8 ids on the device -> app_out[8][H]. q3_session_append_text and the batcher's flush (session_append_many) both come
+// through here, so a token's row has the same bits whichever of the two received it.
+static hipError_t project_group(q3_session* s, const uint32_t* ids_dev) {
     const q3_model* m = s->m; const q3_config& c = m->cfg;
-    const int TD = c.text_dim, H = c.hidden, n = (int)ids.size(), row0 = slot_row0(s, b);
+    const int TD = c.text_dim, H = c.hidden;
+    hipError_t er = launch_gather_rows_bf16(m->text_emb, ids_dev, s->app_e, 8, TD, s->stream);
+    if (er != hipSuccess) return er;
+    LinArgs a;
+    a.N = TD; a.K = TD; set_w(a, m->fc1w, 8, TD, TD); a.x = s->app_e; a.ldx = TD; a.bias = m->fc1b; a.y = s->app_h; a.ldy = TD; a.M = 8; a.epi = EPI_SILU;
+    er = launch_linear(a, s->stream);
+    if (er != hipSuccess) return er;
+    LinArgs b2;
+    b2.N = H; b2.K = TD; set_w(b2, m->fc2w, 8, H, TD); b2.x = s->app_h; b2.ldx = TD; b2.bias = m->fc2b; b2.y = s->app_out; b2.ldy = H; b2.M = 8; b2.epi = EPI_NONE;
+    return launch_linear(b2, s->stream);
+}
+static q3_status project_appended(q3_session* s, int b, const std::vector<uint32_t>& ids, int dst) {
+    const int H = s->m->cfg.hidden, n = (int)ids.size(), row0 = slot_row0(s, b);
     if (n <= 0) return Q3_OK;
     std::vector<uint32_t> padded((size_t)(n + 7) / 8 * 8);       // lives until the synchronisation below
     for (size_t i = 0; i < padded.size(); ++i) padded[i] = ids[i < (size_t)n ? i : (size_t)n - 1];
@@ -824,15 +838,7 @@ static q3_status project_appended(q3_session* s, int b, const std::vector<uint32
     for (int r0 = 0; r0 < n && er == hipSuccess; r0 += 8) {
         const int k = (n - r0) < 8 ? (n - r0) : 8;
         er = hipMemcpyAsync(s->app_ids, padded.data() + r0, 8 * 4, hipMemcpyHostToDevice, s->stream);
-        if (er == hipSuccess) er = launch_gather_rows_bf16(m->text_emb, s->app_ids, s->app_e, 8, TD, s->stream);
-        if (er != hipSuccess) break;
-        LinArgs a;
-        a.N = TD; a.K = TD; set_w(a, m->fc1w, 8, TD, TD); a.x = s->app_e; a.ldx = TD; a.bias = m->fc1b; a.y = s->app_h; a.ldy = TD; a.M = 8; a.epi = EPI_SILU;
-        er = launch_linear(a, s->stream);
-        if (er != hipSuccess) break;
-        LinArgs b2;
-        b2.N = H; b2.K = TD; set_w(b2, m->fc2w, 8, H, TD); b2.x = s->app_h; b2.ldx = TD; b2.bias = m->fc2b; b2.y = s->app_out; b2.ldy = H; b2.M = 8; b2.epi = EPI_NONE;
-        er = launch_linear(b2, s->stream);
+        if (er == hipSuccess) er = project_group(s, s->app_ids);
         if (er == hipSuccess)
             er = hipMemcpyAsync(s->rows + (size_t)(row0 + dst + r0) * H, s->app_out, (size_t)k * H * 4, hipMemcpyDeviceToDevice, s->stream);
     }
@@ -853,6 +859,18 @@ static q3_status publish_text(q3_session* s, int b) {
 }
 static bool any_open_text(const q3_session* s) { for (const auto& q : s->seq) if (q.opened && !q.text_closed) return true; return false; }
 
+// text_ready (every row closed) and the scratch of the appended rows' projection path, once per session
+static q3_status alloc_text_state(q3_session* s) {
+    if (s->text_ready) return Q3_OK;
+    const q3_config& c = s->m->cfg;
+    HIPC(s->pool.alloc(&s->text_ready, (size_t)s->B));
+    HIPC(s->pool.alloc(&s->app_ids, 8)); HIPC(s->pool.alloc(&s->app_e, (size_t)8 * c.text_dim));
+    HIPC(s->pool.alloc(&s->app_h, (size_t)8 * c.text_dim)); HIPC(s->pool.alloc(&s->app_out, (size_t)8 * c.hidden));
+    const std::vector<int> closed((size_t)s->B, 0x7fffffff);
+    HIPC(q3_hipMemcpy(s->text_ready, closed.data(), (size_t)s->B * 4, hipMemcpyHostToDevice));
+    return Q3_OK;
+}
+
 extern "C" q3_status q3_session_open_text(q3_session* s, int b) {
     if (!s) return set_err(Q3_INVALID_ARG, "null session");
     if (b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_open_text: bad sequence index %d", b);
@@ -870,14 +888,7 @@ extern "C" q3_status q3_session_open_text(q3_session* s, int b) {
             return set_err(Q3_UNSUPPORTED, "q3_session_open_text: ICL row %d asks for max_length %d beyond the session's frame budget %d (its length cap is resolved when the text closes; q3_session_create_reserved)", b, q.max_length_req, s->max_frames);
     }
     HIPC(hipSetDevice(s->m->device));
-    if (!s->text_ready) {
-        const q3_config& c = s->m->cfg;
-        HIPC(s->pool.alloc(&s->text_ready, (size_t)s->B));
-        HIPC(s->pool.alloc(&s->app_ids, 8)); HIPC(s->pool.alloc(&s->app_e, (size_t)8 * c.text_dim));
-        HIPC(s->pool.alloc(&s->app_h, (size_t)8 * c.text_dim)); HIPC(s->pool.alloc(&s->app_out, (size_t)8 * c.hidden));
-        const std::vector<int> closed((size_t)s->B, 0x7fffffff);
-        HIPC(q3_hipMemcpy(s->text_ready, closed.data(), (size_t)s->B * 4, hipMemcpyHostToDevice));
-    }
+    Q3C(alloc_text_state(s));
     q.opened = true; q.text_closed = false; q.text_all = q.text; q.committed = 0;
     if (q.icl) q.limit = q.max_length_req;          // until the text closes (open_counts)
     open_counts(q);
@@ -1286,6 +1297,83 @@ static int session_remaining(const q3_session* s) {
 static void open_rows_ran(q3_session* s, int n) {
     for (auto& q : s->seq)
         if (q.opened) { const int stop = std::max(q.committed, std::min(q.ready, q.limit)); q.committed = std::min(q.committed + n, stop); }
+}
+
+// ---- open text through the batcher (q3_batcher_submit_open) ----
+// The hold path of a session that was created without an open row: text_ready and the append scratch are allocated, and a frame
+// that was captured without the hold kernels is dropped — the next q3_session_generate captures it again, once. The caller has
+// nothing of the session in flight.
+q3_status session_text_enable(q3_session* s) {
+    if (s->text_ready) return Q3_OK;
+    if (s->debug || s->profile) return set_err(Q3_UNSUPPORTED, "open text: not on debug / profiling sessions");
+    HIPC(hipSetDevice(s->m->device));
+    HIPC(sync_frames(s));
+    Q3C(alloc_text_state(s));
+    if (s->aql) { q3::aql_program_destroy(s->aql); s->aql = nullptr; }
+    s->aql_mode = 0; s->aql_tried = false;
+    if (s->graph_exec) { (void)hipGraphExecDestroy(s->graph_exec); s->graph_exec = nullptr; }
+    if (s->graph) { (void)hipGraphDestroy(s->graph); s->graph = nullptr; }
+    return Q3_OK;
+}
+// frames row b can still commit with the text (and limit) it has; its committed count (the host's view: exact between two reads)
+int session_row_remaining(const q3_session* s, int b) { const int r = row_capacity(s, s->seq[(size_t)b]); return r > 0 ? r : 0; }
+int session_row_committed(const q3_session* s, int b) {
+    const SeqInfo& q = s->seq[(size_t)b];
+    int n = q.opened ? q.committed : s->frames_run - q.start_run;
+    if (n > q.limit) n = q.limit;
+    return n > 0 ? n : 0;
+}
+// The text flush: the pieces of ANY number of open rows are projected together and published together, with ONE
+// synchronisation at the end (q3_session_append_text drains, projects and synchronises per call and row). The tokens (+ tts_eos
+// of a row that closes) are packed across rows into groups of eight, the last padded with its last id as project_appended pads;
+// every group takes project_group, and k_scatter_rows sends its rows to the slots they belong to. The caller has nothing of the
+// session in flight. All or nothing: a piece that is refused leaves every row as it was.
+q3_status session_append_many(q3_session* s, const std::vector<TextPiece>& pieces) {
+    if (pieces.empty()) return Q3_OK;
+    if (!s->text_ready) return set_err(Q3_INVALID_ARG, "text flush: the session has no open text state");
+    const q3_config& c = s->m->cfg;
+    for (const TextPiece& p : pieces) {
+        if (p.b < 0 || p.b >= s->B || p.n < 0 || (p.n > 0 && !p.ids)) return set_err(Q3_INVALID_ARG, "text flush: bad piece");
+        const SeqInfo& q = s->seq[(size_t)p.b];
+        if (!q.opened || q.text_closed) return set_err(Q3_INVALID_ARG, "text flush: row %d is not open", p.b);
+        for (int i = 0; i < p.n; ++i) if (p.ids[i] >= (uint32_t)c.text_vocab) return set_err(Q3_INVALID_ARG, "text id %u out of range", p.ids[i]);
+        // (the last row of a transplanted open row's slot holds its tts_pad row: transplant_row)
+        if (q.n_trail + p.n + 1 > s->row_cap - 1) return set_err(Q3_UNSUPPORTED, "text flush: %d trailing text rows exceed the row's slot (%d)", q.n_trail + p.n + 1, s->row_cap - 1);
+    }
+    HIPC(hipSetDevice(s->m->device));
+    std::vector<int> ids, dst, pub;
+    for (const TextPiece& p : pieces) {
+        SeqInfo& q = s->seq[(size_t)p.b];
+        const int row0 = q.trail_base + q.n_trail;
+        for (int i = 0; i < p.n; ++i) { ids.push_back((int)p.ids[i]); dst.push_back(row0 + i); }
+        if (p.last) { ids.push_back((int)TTS_EOS); dst.push_back(row0 + p.n); }
+        q.text_all.insert(q.text_all.end(), p.ids, p.ids + p.n);
+        if (p.last) q.text_closed = true;
+        open_counts(q);
+        const int e[4] = {p.b, q.trailing_len, q.ready, q.limit};
+        pub.insert(pub.end(), e, e + 4);
+    }
+    while (ids.size() % 8 != 0) { ids.push_back(ids.back()); dst.push_back(-1); }
+    const size_t n_src = ids.size(), n_pub = pub.size() / 4;
+    // one upload: [ids | destinations | entries to publish]; the buffer grows by doubling and lives as long as the session
+    std::vector<int> up(ids); up.insert(up.end(), dst.begin(), dst.end()); up.insert(up.end(), pub.begin(), pub.end());
+    if (up.size() > s->flush_cap) {
+        size_t cap = s->flush_cap ? s->flush_cap : 256;
+        while (cap < up.size()) cap *= 2;
+        HIPC(s->pool.alloc(&s->flush_buf, cap));
+        s->flush_cap = cap;
+    }
+    hipError_t er = hipMemcpyAsync(s->flush_buf, up.data(), up.size() * 4, hipMemcpyHostToDevice, s->stream);      // (`up` lives until the synchronisation below)
+    for (size_t g = 0; g < n_src && er == hipSuccess; g += 8) {
+        er = project_group(s, (const uint32_t*)s->flush_buf + g);
+        if (er == hipSuccess) er = launch_scatter_rows(s->app_out, s->flush_buf + n_src + g, s->rows, 8, c.hidden, s->stream);
+    }
+    if (er == hipSuccess) er = launch_publish_text(s->flush_buf + 2 * n_src, (int)n_pub, s->trail_len, s->text_ready, s->limit, s->stream);
+    const hipError_t es = sync_frames(s);
+    if (er == hipSuccess) er = es;
+    s->codes_host_valid = false;
+    if (er != hipSuccess) return set_err(Q3_HIP_ERROR, "text flush: %s", hipGetErrorString(er));
+    return Q3_OK;
 }
 
 // Which kernels of the frame keep to the activation-transport rule of q3_kernels.h (write-through + drained stores, L1-bypassing

@@ -73,6 +73,10 @@ pub mod ffi {
         pub fn q3_batcher_submit_streamed(b: *mut c_void, req: *const Q3Request, ticket: *mut i64) -> i32;
         pub fn q3_batcher_read(b: *mut c_void, ticket: i64, pcm: *mut f32, cap_samples: usize, n_samples: *mut usize, done: *mut i32) -> i32;
         pub fn q3_batcher_stream_info(b: *mut c_void, block_frames: *mut i32, block_bytes: *mut usize, blocks_total: *mut i32, blocks_in_use: *mut i32, blocks_peak: *mut i32) -> i32;
+        pub fn q3_batcher_submit_open(b: *mut c_void, req: *const Q3Request, want: i32, ticket: *mut i64) -> i32;
+        pub fn q3_batcher_append_text(b: *mut c_void, ticket: i64, ids: *const u32, n: i32, last: i32) -> i32;
+        pub fn q3_batcher_text_state(b: *mut c_void, ticket: i64, n_text: *mut i32, frames_committed: *mut i32, frames_runnable: *mut i32, closed: *mut i32) -> i32;
+        pub fn q3_batcher_cancel(b: *mut c_void, ticket: i64) -> i32;
         pub fn q3_batcher_step(b: *mut c_void, n_frames: i32, use_graph: i32, n_running: *mut i32, n_queued: *mut i32, n_finished: *mut i32) -> i32;
         pub fn q3_batcher_poll(b: *mut c_void, ticket: i64, state: *mut i32, n_frames: *mut i32, n_samples: *mut usize) -> i32;
         pub fn q3_batcher_fetch(b: *mut c_void, ticket: i64, codes: *mut u32, cap_frames: i32, pcm: *mut f32, cap_samples: usize) -> i32;
