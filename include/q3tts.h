@@ -173,6 +173,27 @@ q3_status q3_model_kv_pool_trim(q3_model* m, size_t* bytes_freed);
  * decodes started after the call; anything but 2 or 3 is Q3_INVALID_ARG. */
 q3_status q3_model_set_codec_planes(q3_model* m, int planes);
 q3_status q3_model_kv_pool_info(q3_model* m, int* page_positions, size_t* page_bytes, int* pages_total, int* pages_in_use, int* pages_peak);
+/* Prefix cache (opt-in, off by default; no reference counterpart: the reference builds its KV cache per call, kv_cache.rs:234-310,
+ * and prefills the whole VoiceDesign prompt [instruct N][role 3][codec 5][first text 1] every time, talker.rs:585-627). Under
+ * causal attention the K/V of the instruct positions depend on the instruct tokens only, so the pages a prefill filled for them
+ * are kept and LINKED into the rows of later requests with the same instruction: the prefill then starts at the first position
+ * that is not cached. Blocks of 128 positions (one KV page), keyed by a chain hash over the token ids (ids stored and compared);
+ * a lookup is a longest-prefix match in pages. A hit is invisible except in time: first logits, codes and PCM are bit for bit
+ * those of the same request in the same session shape with the cache off.
+ * q3_model_prefix_cache: capacity in pages; 0 = off, which also drops every cached page (one a running row holds stays that
+ * row's). Cached pages are f32 pages of the model's pool and count against q3_model_kv_pool_limit once, however many rows share
+ * them; loading weights again (q3_model_set_tensor, q3_model_mark_loaded, q3_model_finalize) drops every cached page; pages only the cache holds are given up (least recently used first) before a request fails with Q3_KV_OVERFLOW, and the
+ * batcher's admission treats them as free. They pin their slabs against q3_model_kv_pool_trim until the cache is cleared.
+ * Not used by debug / profiling sessions, with Q3_KV_CONTIGUOUS=1, for instructions shorter than one page, or for prompts that
+ * are not VoiceDesign (ICL, x-vector, CustomVoice).
+ * q3_model_prefix_cache_info: capacity, pages cached, how many of those a row holds too, and counters since the model was created
+ * (lookups = eligible rows prefilled, hit_positions = prompt positions not computed again); any pointer may be NULL.
+ * q3_session_prefix_info: positions of row b's prompt that came from the cache (after prefill; rows that entered through
+ * q3_session_replace or the batcher report their own). */
+q3_status q3_model_prefix_cache(q3_model* m, int max_pages);
+q3_status q3_model_prefix_cache_info(q3_model* m, int* max_pages, int* pages_cached, int* pages_shared, long long* lookups,
+                                     long long* hit_positions, long long* evictions);
+q3_status q3_session_prefix_info(q3_session* s, int b, int* reused_positions);
 /* Verify every tensor is present ("Missing weight: <name>"), derive codebooks
  * (decoder_12hz.rs:189-225) and RoPE tables. */
 q3_status q3_model_finalize(q3_model* m);

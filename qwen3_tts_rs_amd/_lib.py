@@ -87,6 +87,9 @@ SYMBOLS = {
     "q3_model_set_codec_planes": (c_int, [c_void_p, c_int]),
     "q3_model_kv_pool_trim": (c_int, [c_void_p, P(ctypes.c_size_t)]),
     "q3_model_kv_pool_info": (c_int, [c_void_p, P(c_int), P(ctypes.c_size_t), P(c_int), P(c_int), P(c_int)]),
+    "q3_model_prefix_cache": (c_int, [c_void_p, c_int]),
+    "q3_model_prefix_cache_info": (c_int, [c_void_p, P(c_int), P(c_int), P(c_int), P(ctypes.c_longlong), P(ctypes.c_longlong), P(ctypes.c_longlong)]),
+    "q3_session_prefix_info": (c_int, [c_void_p, c_int, P(c_int)]),
     "q3_model_mark_loaded": (c_int, [c_void_p]),
     "q3_model_finalize": (c_int, [c_void_p]),
     "q3_synth_fill": (c_int, [ctypes.c_uint64, c_char_p, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int64, c_void_p]),

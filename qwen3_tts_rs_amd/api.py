@@ -339,6 +339,12 @@ class Session:
         check(lib.q3_session_prefill_len(self._h, b, ctypes.byref(p), ctypes.byref(t)))
         return p.value, t.value
 
+    def prefix_info(self, b: int = 0) -> int:
+        """Positions of row b's prompt whose K/V came from the model's prefix cache (q3_session_prefix_info; after prefill)."""
+        n = ctypes.c_int()
+        check(lib.q3_session_prefix_info(self._h, int(b), ctypes.byref(n)))
+        return n.value
+
     def get(self, what: int, shape, b: int = 0, dtype=np.float32) -> np.ndarray:
         out = np.zeros(shape, dtype=dtype)
         check(lib.q3_session_get(self._h, what, b, out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
@@ -551,6 +557,9 @@ class StreamingSession:
 
     def is_done(self) -> bool:
         return self._done
+
+    def close(self):
+        self._s.close()
 
     def __iter__(self):
         return self
@@ -778,6 +787,21 @@ class Qwen3TTS:
         pp = ctypes.c_int(); pb = ctypes.c_size_t(); tot = ctypes.c_int(); use = ctypes.c_int(); peak = ctypes.c_int()
         check(lib.q3_model_kv_pool_info(self._h, ctypes.byref(pp), ctypes.byref(pb), ctypes.byref(tot), ctypes.byref(use), ctypes.byref(peak)))
         return {"page_positions": pp.value, "page_bytes": pb.value, "pages_total": tot.value, "pages_in_use": use.value, "pages_peak": peak.value}
+
+    def prefix_cache(self, max_pages: int):
+        """Capacity of the model's prefix cache in KV pages of 128 positions (q3_model_prefix_cache); 0 = off (the default), which
+        also drops every cached page. With it on, the prefilled K/V pages of a VoiceDesign instruction are linked into later requests
+        that carry the same instruction, and their prefill starts at the first position that is not cached — same bits, less time."""
+        check(lib.q3_model_prefix_cache(self._h, int(max_pages)))
+
+    def prefix_cache_info(self) -> dict:
+        """Capacity, occupancy and counters of the prefix cache (q3_model_prefix_cache_info). pages_shared: cached pages a row
+        holds too; hit_positions: prompt positions that were not computed again."""
+        mx = ctypes.c_int(); n = ctypes.c_int(); sh = ctypes.c_int()
+        lk = ctypes.c_longlong(); hp = ctypes.c_longlong(); ev = ctypes.c_longlong()
+        check(lib.q3_model_prefix_cache_info(self._h, ctypes.byref(mx), ctypes.byref(n), ctypes.byref(sh), ctypes.byref(lk), ctypes.byref(hp), ctypes.byref(ev)))
+        return {"max_pages": mx.value, "pages_cached": n.value, "pages_shared": sh.value, "lookups": lk.value,
+                "hit_positions": hp.value, "evictions": ev.value}
 
     def arena(self) -> Tuple[int, int]:
         p = ctypes.c_void_p(); n = ctypes.c_size_t()

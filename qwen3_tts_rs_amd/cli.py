@@ -56,6 +56,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
                     help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
                          "first token to the first audio; writes the same WAV as without the flag)")
+    ap.add_argument("--prefix-cache", type=int, default=0, metavar="PAGES",
+                    help="keep up to PAGES KV pages (128 positions each) of prefilled --instruct prompts for later requests of this model (0 = off)")
     ap.add_argument("--no-eos", action="store_true", help="disable EOS (fixed-length runs on synthetic weights)")
     return ap
 
@@ -211,6 +213,8 @@ def main(argv=None) -> int:
         model = q.Qwen3TTS.from_pretrained(a.model_dir, device=dev)
     print(f"Loaded model in {time.time() - t0:.2f}s ({model.config.name}, type {model.model_type.name if model.model_type else 'unknown'}, "
           f"tokenizer: {tok.kind if tok else 'none (--token-ids)'})")
+    if a.prefix_cache > 0:
+        model.prefix_cache(a.prefix_cache)
     ids = [int(x) for x in a.token_ids.split(",")] if a.token_ids else tok.encode(a.text)
     opts = q.SynthesisOptions(max_length=frames, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
                               repetition_penalty=a.repetition_penalty, seed=a.seed)

@@ -1,6 +1,7 @@
 // q3_batcher.hip — continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
-// (one of the five units of the engine: q3_engine.h says which holds what)
+// (one of the units of the engine: q3_engine.h says which holds what)
 #include "q3_engine.h"
+#include "q3_prefix_cache.h"
 #include <condition_variable>
 #include <deque>
 
@@ -33,6 +34,11 @@ q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limi
     }
     auto d2d = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s->stream); };
     HIPC(d2d(s->LASTH + (size_t)b * H, side->LASTH + (size_t)j * H, (size_t)H * 4));
+    // the row's first logits (Q3_GET_LOGITS after the prefill; the next frame overwrites every row's)
+    HIPC(d2d(s->LOGITS + (size_t)b * c.codec_vocab, side->LOGITS + (size_t)j * c.codec_vocab, (size_t)c.codec_vocab * 4));
+    // a one-length session that prefilled its rows in groups (prefix cache): its own prompt embeddings were never assembled
+    if (s->regrouped && S == s->prefill_len)
+        HIPC(d2d(s->embeds + (size_t)b * S * H, side->embeds + (size_t)j * S * H, (size_t)S * H * 4));
     HIPC(d2d(s->tok + b, side->tok + j, 4));
     HIPC(d2d(s->seen + (size_t)b * c.codec_vocab, side->seen + (size_t)j * c.codec_vocab, (size_t)c.codec_vocab));
     HIPC(d2d(s->token_count + b, side->token_count + j, 4));
@@ -693,9 +699,12 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
             mine += h;
             if (b->owner[r] >= 0) { claimed += std::max(b->commit[r], h); running++; } else claimed += h;
         }
+        // pages only the prefix cache holds are reclaimable (kv_take evicts them before a row's request fails): they do not stand
+        // in a request's way. A request is never discounted for the pages it hopes to find cached.
+        const long reclaim = 2L * prefix_reclaimable(b->m);
         std::lock_guard<std::mutex> g(b->m->kv_budget.mu);
         if (b->m->kv_budget.limit <= 0) return true;
-        const long others = b->m->kv_budget.used - mine;
+        const long others = std::max(0L, b->m->kv_budget.used - mine - reclaim);
         if (others + claimed + units <= b->m->kv_budget.limit) return true;
         *wait = running > 0;
         return false;

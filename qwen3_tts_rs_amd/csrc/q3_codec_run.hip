@@ -1,5 +1,5 @@
 // q3_codec_run.hip — the device-memory cache, the vocoder pipeline (codec_decode_dev) and q3_decode_codes
-// (one of the five units of the engine: q3_engine.h says which holds what)
+// (one of the units of the engine: q3_engine.h says which holds what)
 #include "q3_engine.h"
 
 // ------------------------------------------------------------------------------------------------

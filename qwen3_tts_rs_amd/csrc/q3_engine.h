@@ -1,6 +1,7 @@
 // q3_engine.h — what the translation units of the engine share (not part of the C ABI; include/q3tts.h is).
 // Round 6: q3_engine.hip (3 800 lines: model, arena, KV pool, session, graph capture, batcher, test entry points) was split into
 //   q3_model.hip     errors, synthetic tensors, the weight manifest / arena, q3_model_* (create, set_tensor, finalize, KV pool API)
+//   q3_prefix_cache.hip the prefix cache: prefilled instruct pages shared across requests (q3_prefix_cache.h)
 //   q3_codec_run.hip device-memory cache, the vocoder pipeline (codec_decode_dev) and q3_decode_codes
 //   q3_codec_stream.hip the codec stream: the vocoder with per-row state, many rows per pass
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
@@ -170,11 +171,27 @@ struct KvPool {
         if (budget->used > budget->peak) budget->peak = budget->used;      // limit is an admission bound, not a hard allocator wall)
         return hipSuccess;
     }
+    // Shared pages (the prefix cache, q3_prefix_cache.h): `shared[p]` = how many holders page p has, kept only while there is
+    // more than one — a page without an entry has exactly one. share() adds a holder; give() takes one away and returns the page
+    // to the free list when the last one goes. A shared page is counted ONCE in in_use and in the budget: by take(), until then.
+    std::unordered_map<float*, int> shared;
+    void share(float* p) {
+        std::lock_guard<std::mutex> g(mu);
+        auto it = shared.find(p);
+        if (it == shared.end()) shared.emplace(p, 2); else it->second += 1;
+    }
+    bool is_shared(float* p) { std::lock_guard<std::mutex> g(mu); return shared.count(p) != 0; }
+    bool is_shared_locked(float* p) const { return shared.count(p) != 0; }      // the caller holds mu (one lock for a scan over many pages)
     void give(std::vector<float*>& pages) {
         std::lock_guard<std::mutex> g(mu);
-        for (float* p : pages) free_pages.push_back(p);
-        in_use -= (int)pages.size();
-        { std::lock_guard<std::mutex> gb(budget->mu); budget->used -= (long)pages.size() * unit; }
+        int freed = 0;
+        for (float* p : pages) {
+            auto it = shared.find(p);
+            if (it != shared.end()) { if (--it->second <= 1) shared.erase(it); continue; }      // another holder keeps it
+            free_pages.push_back(p); ++freed;
+        }
+        in_use -= freed;
+        { std::lock_guard<std::mutex> gb(budget->mu); budget->used -= (long)freed * unit; }
         pages.clear();
     }
     // slabs none of whose pages is held go back to the device (q3_model_kv_pool_trim); returns the bytes freed
@@ -206,6 +223,7 @@ struct KvPool {
     ~KvPool() { for (void* s : slabs) (void)hipFree(s); }
 };
 
+struct PrefixCache;
 struct q3_model {
     q3_config cfg{};
     int device = 0;
@@ -213,6 +231,7 @@ struct q3_model {
     KvBudget kv_budget;    // one limit / occupancy for both pools below, in half-f32-page units
     KvPool kv_pool;
     KvPool kv_pool16;      // pages of bf16 sessions (q3_session_set_kv_dtype): the same geometry with 2-byte elements
+    PrefixCache* prefix = nullptr;      // prefilled instruct pages shared across requests (q3_prefix_cache.h; created with a device model, off until sized)
     // sessions hold pages, streams and weights of their model: the handle itself is ONE reference and every live session another;
     // whoever drops the count to zero destroys the model (q3_model_free with sessions still alive only gives up the handle's
     // reference — a host that tears down in the wrong order must not crash — and nobody touches *m after its own decrement)
@@ -362,6 +381,7 @@ struct SeqInfo {
     // rows end at different frames: a row generates at most `limit` frames (its own max_length) counted from session frame
     // `start_run` (0, or the session's frame count when the row was swapped in: q3_session_replace)
     int start_run = 0, limit = 0, stream_pos = 0;
+    int reused = 0;         // prompt positions whose K/V pages came from the model's prefix cache (q3_session_prefix_info)
     bool idle = false;      // frozen by session_idle_row: holds one page (the one its frozen position lies in), takes no more
     int max_length_req = 0; // the request's own max_length (an ICL row's length cap is applied to it: `limit`)
     // open text (q3_session_open_text): the row's text arrives in pieces (q3_session_append_text). Its trailing
@@ -398,6 +418,8 @@ struct q3_session {
     // idle rows, these are the real requests; q3_session_prefill prefills them in groups of equal prefill length and moves each
     // row in (transplant_row), exactly as a continuous-batching swap would
     std::vector<BatReq> ragged;
+    bool regrouped = false;               // prefix cache: a one-length session whose rows were prefilled in groups (prefix_regroup); transplant_row then also fills embeds
+    bool prefix_common = false;           // prefix cache: rows that hit differently stay in this session (a group prefill_ragged formed)
     int kv_overflow_row = -1;             // the row whose page request the pool refused (kv_reserve_row): the batcher fails that row alone
     // bf16 K/V (opt-in, q3_session_set_kv_dtype; the reference GPU path's cache dtype): the prompt is prefilled into f32 pages
     // as always, converted once into pages of the bf16 pool (kv_in_bf16 from then on), and the decode attention reads / appends bf16
@@ -508,6 +530,7 @@ Q3_HIDDEN q3_status session_text_enable(q3_session* s);
 Q3_HIDDEN q3_status session_append_many(q3_session* s, const std::vector<TextPiece>& pieces);
 Q3_HIDDEN int session_row_remaining(const q3_session* s, int b);
 Q3_HIDDEN int session_row_committed(const q3_session* s, int b);
+// q3_prefix_cache.hip: see q3_prefix_cache.h
 // q3_batcher.hip
 Q3_HIDDEN q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limit);
 Q3_HIDDEN q3_status transplant_check(q3_session* s, q3_session* side, int j, int limit_req, int* limit_out);

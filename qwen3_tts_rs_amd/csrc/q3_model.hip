@@ -1,6 +1,7 @@
 // q3_model.hip — errors, synthetic tensors, the weight manifest and arena, q3_model_* (create / set_tensor / finalize / KV pool API)
-// (one of the five units of the engine: q3_engine.h says which holds what)
+// (one of the units of the engine: q3_engine.h says which holds what)
 #include "q3_engine.h"
+#include "q3_prefix_cache.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -292,6 +293,7 @@ extern "C" q3_status q3_model_create(const q3_config* cfg, int device, q3_model*
     build_manifest(m.get());
     HIPC(hipMalloc((void**)&m->arena, m->arena_bytes));
     HIPC(hipMemset(m->arena, 0, m->arena_bytes));
+    m->prefix = new PrefixCache();
     *out = m.release();
     return Q3_OK;
 }
@@ -307,6 +309,7 @@ void model_destroy(q3_model* m) {
     hipFree(m->arena); hipFree(m->rope_cos); hipFree(m->rope_sin); hipFree(m->derived); hipFree(m->wpk_arena);
     hipFree((void*)m->rest_cbs_dev); hipFree((void*)m->cp_embs_dev); hipFree(m->proj_tabs); hipFree(m->qkv0_tabs);
     for (hipStream_t st : m->idle_streams) (void)hipStreamDestroy(st);
+    delete m->prefix;
     delete m;
 }
 
@@ -345,6 +348,7 @@ extern "C" q3_status q3_model_kv_pool_info(q3_model* m, int* page_positions, siz
 }
 // Slabs of either pool none of whose pages is held go back to the device (a server that has seen one very long prompt need not
 // keep its ~1 GB slabs for the model's lifetime). Safe beside running sessions: held pages pin their slab.
+// Pages the prefix cache holds are held pages: they pin their slabs until the cache is cleared (q3_model_prefix_cache(m, 0)).
 extern "C" q3_status q3_model_kv_pool_trim(q3_model* m, size_t* bytes_freed) {
     if (!m || m->device < 0) return set_err(Q3_INVALID_ARG, "q3_model_kv_pool_trim: no device model");
     HIPC(hipSetDevice(m->device));
@@ -453,6 +457,7 @@ extern "C" q3_status q3_model_set_tensor(q3_model* m, const char* name, int dtyp
     HIPC(q3_hipMemcpy(m->arena + s.offset, src, up_bytes, hipMemcpyHostToDevice));
     s.loaded = true;
     m->finalized = false;
+    prefix_clear(m);      // K/V cached for the old weights must not be linked again
     return Q3_OK;
 }
 
@@ -465,6 +470,7 @@ extern "C" q3_status q3_model_arena(q3_model* m, void** dev_ptr, size_t* bytes) 
 extern "C" q3_status q3_model_mark_loaded(q3_model* m) {
     if (!m) return set_err(Q3_INVALID_ARG, "null model");
     for (auto& s : m->slots) s.loaded = true;
+    prefix_clear(m);      // the arena was written behind our back
     return Q3_OK;
 }
 
@@ -501,6 +507,7 @@ extern "C" q3_status q3_model_finalize(q3_model* m) {
     for (auto& s : m->slots)
         if (!s.loaded) return set_err(Q3_MISSING_WEIGHT, "Missing weight: %s", s.name.c_str());
     HIPC(hipSetDevice(m->device));
+    prefix_clear(m);
     const q3_config& c = m->cfg;
     m->text_emb = P<uint16_t>(m, "talker.model.text_embedding.weight");
     m->fc1w = PT(m, "talker.text_projection.linear_fc1.weight");

@@ -1,6 +1,7 @@
 // q3_session.hip — sessions: KV paging, talker / code-predictor step, frame capture and submission, prefill, generate, streaming, run / decode / get
-// (one of the five units of the engine: q3_engine.h says which holds what)
+// (one of the units of the engine: q3_engine.h says which holds what)
 #include "q3_engine.h"
+#include "q3_prefix_cache.h"
 
 // Everything this session has in flight has landed: the frames on the library's own AQL queue (q3_aql.cpp; not ordered with any
 // HIP stream) and whatever rides the session's stream. Every host-side wait of the engine goes through here.
@@ -53,7 +54,7 @@ q3_status kv_reserve_row(q3_session* s, int b, int n_pos) {
     const int need = (n_pos + KV_PAGE_POS - 1) / KV_PAGE_POS, have = (int)row.size();
     if (need <= have) return Q3_OK;
     KvPool& pool = s->kv_in_bf16 ? s->m->kv_pool16 : s->m->kv_pool;
-    if (pool.take(need - have, row) != hipSuccess)
+    if (kv_take(s->m, pool, need - have, row) != hipSuccess)      // (reclaims pages only the prefix cache holds before it gives up)
     {
         s->kv_overflow_row = b;
         return set_err(Q3_KV_OVERFLOW, "KV page pool exhausted: row %d needs %d more %s page(s) of %d positions (budget: %ld of %ld half-pages in use)",
@@ -83,7 +84,8 @@ void kv_release_row(q3_session* s, int b) {        // the caller has drained eve
 }
 
 // bf16 sessions: every row's f32 pages -> as many pages of the bf16 pool (k_kv_pages_to_bf16), the table rewritten, the f32
-// pages returned. The caller has drained the stream; this drains it again before the f32 pages go back.
+// pages returned (a page the prefix cache also holds stays the cache's: KvPool::give). The caller has drained the stream; this
+// drains it again before the f32 pages go back.
 static q3_status kv_convert_to_bf16(q3_session* s) {
     if (!s->paged) return set_err(Q3_UNSUPPORTED, "bf16 K/V needs the paged cache");
     const q3_config& c = s->m->cfg;
@@ -91,7 +93,7 @@ static q3_status kv_convert_to_bf16(q3_session* s) {
     q3_status st = Q3_OK;
     for (int b = 0; b < s->B && st == Q3_OK; ++b) {
         const int n = (int)s->kv_rows[(size_t)b].size();
-        if (s->m->kv_pool16.take(n, fresh[(size_t)b]) != hipSuccess) { st = set_err(Q3_KV_OVERFLOW, "KV page pool (bf16) exhausted: row %d needs %d page(s)", b, n); break; }
+        if (kv_take(s->m, s->m->kv_pool16, n, fresh[(size_t)b]) != hipSuccess) { st = set_err(Q3_KV_OVERFLOW, "KV page pool (bf16) exhausted: row %d needs %d page(s)", b, n); break; }
         for (int i = 0; i < n; ++i) { src.push_back((unsigned long long)s->kv_rows[(size_t)b][(size_t)i]); dst.push_back((unsigned long long)fresh[(size_t)b][(size_t)i]); }
     }
     if (st != Q3_OK) { for (auto& f : fresh) if (!f.empty()) s->m->kv_pool16.give(f); return st; }
@@ -957,15 +959,23 @@ extern "C" q3_status q3_session_text_state(q3_session* s, int b, int* n_text, in
 // layer as GEMMs over the decode path's tiled weight image + a query-blocked causal attention (q3_kernels_prefill.hip).
 // Leaves the KV cache filled for positions [0, S) and LASTH / LOGITS of the last position, like the chunked decode-step
 // schedule it replaces for S >= 48.
-static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head) {      // positions [0, S) of the S_all-position prompts
+// positions per sequence per GEMM pass (prefill_gemm below)
+static int prefill_gemm_chunk(int B) {
+    static const int rows_env = [] { const char* e = getenv("Q3_PREFILL_ROWS"); return e ? atoi(e) : 4224; }();
+    const int C = rows_env / B;
+    return C < 128 ? 128 : (C / 128) * 128;
+}
+// P0 > 0: positions [0, P0) are already in the rows' pages (linked from the prefix cache) and are not computed again. The passes
+// keep the cuts of the run from 0 — the same chunks, and inside the chunk P0 lies in the same query blocks (prefix_usable_pages rounds P0
+// to a block boundary of that chunk) — so every position from P0 on sees the arithmetic of the uncached run.
+static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, int P0 = 0) {      // positions [P0, S) of the S_all-position prompts
     const q3_model* m = s->m; const q3_config& c = m->cfg;
     const LmDims d = talker_dims(c);
     const int B = s->B, H = d.H, QD = d.nh * HEAD_DIM, KD = d.nkv * HEAD_DIM, I = d.I;
     // positions per sequence per pass: up to 4224 activation rows per launch (a whole 4k-position prompt in one pass:
     // 33 M-tiles x N/128 workgroups per GEMM, 520 attention workgroups; 2048-row passes: 113 ms instead of 99 for the
     // 4105-position prefill of the 1.7B model), at least one 128-row tile per sequence
-    static const int rows_env = [] { const char* e = getenv("Q3_PREFILL_ROWS"); return e ? atoi(e) : 4224; }();
-    int C = rows_env / B; C = C < 128 ? 128 : (C / 128) * 128;
+    const int C = prefill_gemm_chunk(B);
     const int max_rows = B * (S < C ? S : C);
     struct SyncedPool : DevPool { hipStream_t st; explicit SyncedPool(hipStream_t s_) : st(s_) {} ~SyncedPool() { (void)hipStreamSynchronize(st); } };
     SyncedPool tmp(s->stream);       // on EVERY return path the stream is drained before the blocks go back to the cache
@@ -1004,8 +1014,11 @@ static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head) {
     float* SKW = nullptr; size_t skw_bytes = 0;
     if (planes && max_rows <= 1024) { skw_bytes = (size_t)8 * max_rows * (QD + 2 * KD > 2 * I / 4 ? QD + 2 * KD : 2 * I / 4) * sizeof(float); HIPC(tmp.alloc(&SKW, skw_bytes / sizeof(float))); }
     int ch = 0;
-    for (int t0 = 0; t0 < S; t0 += C) {
-        ch = (S - t0) < C ? (S - t0) : C;
+    for (int c0 = 0; c0 < S; c0 += C) {
+        const int c1 = (S - c0) < C ? S : c0 + C;                // the chunk [c0, c1) of the run from 0
+        if (c1 <= P0) continue;
+        const int t0 = c0 > P0 ? c0 : P0;
+        ch = c1 - t0;
         const int rows = B * ch;
         for (int b = 0; b < B; ++b)
             HIPC(launch_copy_rows(s->embeds + ((size_t)b * S_all + t0) * H, H, X + (size_t)b * ch * H, H, ch, H, s->stream));
@@ -1058,6 +1071,132 @@ static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head) {
     return Q3_OK;
 }
 
+// Which kernels prefill an S-position prompt: the GEMM passes over [0, Sg) (or none), the decode-step schedule over the rest.
+// The GEMM path works in 128-position tiles and its grids are sized to fill the chip in whole rounds (4096
+// positions: 256 / 512 / 1536 workgroups of 256 CUs' worth); a few positions past the last full tile would cost every
+// GEMM another round (4105 positions, one sequence: +9 ... +50 % per GEMM). Up to Q3_PREFILL_TAIL (default 32)
+// trailing positions of a >= 1024-position prompt therefore go through the decode-step schedule instead (about
+// 1 ms per 16 rows at 4k context), which appends to the same KV cache. The rule looks at the PROMPT only — never at the
+// batch — so which kernels compute a given position does not depend on how many sequences are prefilled together
+// (a batch pays ceil(B * r / 16) passes for it; positions below the cut always take the GEMM, whose bits are
+// batch-invariant; the decode-step kernels pick their tiling by the row count of a pass, like any decode step).
+static bool prefill_cut_of(const q3_model* m, int S, int* Sg) {
+    static const int gemm_min = [] { const char* e = getenv("Q3_PREFILL_GEMM_MIN"); return e ? atoi(e) : 48; }();   // 0 disables the GEMM path
+    static const int tail_max = [] { const char* e = getenv("Q3_PREFILL_TAIL"); return e ? atoi(e) : 32; }();
+    *Sg = 0;
+    if (gemm_min <= 0 || S < gemm_min || !d_nh_ok(m->cfg)) return false;
+    const int r = S % 128;
+    *Sg = (S >= 1024 && r > 0 && r <= tail_max) ? S - r : S;
+    return true;
+}
+static bool prefill_cut(const q3_session* s, int S, int* Sg) {
+    *Sg = 0;
+    return !s->no_chunk && !s->debug && prefill_cut_of(s->m, S, Sg);
+}
+static int prefill_step_chunk(const q3_session* s) { return s->no_chunk ? 1 : (16 / s->B > 0 ? 16 / s->B : 1); }
+
+// ---- prefix cache (q3_prefix_cache.h): what a session asks of it ----
+// Eligible: the instruct positions of a VoiceDesign row, in whole pages — the only prompt positions whose input is a pure
+// function of the cache key. Never for debug / profile / no_chunk sessions or contiguous K/V.
+static bool prefix_session_ok(const q3_session* s) { return prefix_on(s->m) && s->paged && !s->debug && !s->profile && !s->no_chunk; }
+static int prefix_eligible_pages(const SeqInfo& q) { return q.req.mode == Q3_MODE_VOICE_DESIGN ? (int)q.instruct.size() / KV_PAGE_POS : 0; }
+// The regime of this session's prefill: everything besides the token ids that decides the BITS of a cached position.
+//   GEMM path: which attention kernel the prompt length selects (below 256 positions / bf16x3 / bf16x3 with key halves). With
+//   key halves a query block's half boundary comes from the block's last position. At GQA ratio 2 a block is 128 rows = one
+//   page, chunks start at multiples of 128, and every eligible page is a whole block: its last position is the page's, whatever
+//   the prompt length or the chunk length — prompts of different lengths share pages. At ratio 1 a block is 256 rows: the block
+//   a cached page lies in can end with the prompt or the chunk, and chunks of an odd number of pages shift the blocks, so Sg
+//   and, when there is more than one chunk, the chunk length are part of the regime there.
+//   Decode-step path (no GEMM geometry for the model): session width, key splits and prompt length.
+static PrefixRegime prefix_regime_of(const q3_model* m, int B, int S, int n_splits) {
+    PrefixRegime rg; int Sg = 0;
+    if (prefill_cut_of(m, S, &Sg)) {
+        const int C = prefill_gemm_chunk(B);
+        const char* x3e = getenv("Q3_PREFILL_ATTN_X3");
+        rg.v[0] = 1; rg.v[1] = Sg >= 1024 ? 2 : (Sg >= 256 ? 1 : 0);
+        const bool wide_blk = 256 / (m->cfg.n_heads / m->cfg.n_kv_heads) > KV_PAGE_POS;      // blocks of more than one page
+        rg.v[2] = (rg.v[1] == 2 && wide_blk) ? Sg : 0; rg.v[3] = (rg.v[1] == 2 && wide_blk && Sg > C) ? C : 0;
+        rg.v[4] = (x3e && atoi(x3e) == 0) ? 1 : 0;
+    } else { rg.v[0] = 2; rg.v[1] = B; rg.v[2] = n_splits; rg.v[3] = S; }
+    return rg;
+}
+static PrefixRegime prefix_regime(const q3_session* s) { return prefix_regime_of(s->m, s->B, s->prefill_len, s->n_splits); }
+// How many of `pages` cached pages a row may link so that the rest of the prompt is computed with the cuts of the uncached run.
+//   GEMM path: the passes start at a block boundary of the chunk the first uncached position lies in (blocks are 256 / ratio
+//   rows with the bf16x3 attention, 128 / ratio below 256 positions; chunks start at multiples of the chunk length). When every
+//   GEMM position is cached no pass runs and nothing is rounded.
+//   Decode-step path: the passes of 16 / B positions start at a multiple of that.
+static int prefix_usable_pages_of(const q3_model* m, int B, int S, int pages) {
+    int Sg = 0; const int P = pages * KV_PAGE_POS;
+    if (prefill_cut_of(m, S, &Sg)) {
+        if (P >= Sg) return Sg / KV_PAGE_POS;
+        const int C = prefill_gemm_chunk(B), nrep = m->cfg.n_heads / m->cfg.n_kv_heads;
+        const int blk = (Sg >= 256 ? 256 : 128) / nrep, c0 = (P / C) * C;
+        const int P1 = c0 + ((P - c0) / blk) * blk;
+        return P1 / KV_PAGE_POS;      // (blk < 128 never occurs: the GEMM path takes ratios 1 and 2 only)
+    }
+    const int ch = 16 / B > 0 ? 16 / B : 1;      // prefill_step_chunk of a session the cache serves (never no_chunk)
+    int g = ch, r = KV_PAGE_POS; while (r) { const int t = g % r; g = r; r = t; }      // gcd(chunk, 128)
+    const int step = KV_PAGE_POS / g * ch;
+    return (P / step) * step / KV_PAGE_POS;
+}
+static int prefix_usable_pages(const q3_session* s, int pages) { return prefix_usable_pages_of(s->m, s->B, s->prefill_len, pages); }
+
+static q3_status prefill_ragged(q3_session* s);
+// Looks every row up and links what the session can use. Returns the number of positions the session's rows skip (the same for
+// every row: rows of one batched prefill run through the same passes), or -1 when the rows hit differently and the session
+// should prefill them in groups instead (prefill_ragged: each group a side session of its own width).
+static int prefix_link(q3_session* s, q3_status* st) {
+    *st = Q3_OK;
+    const int B = s->B; q3_model* m = s->m;
+    const PrefixRegime rg = prefix_regime(s);
+    int kmin = 0x7fffffff, kmax = 0; bool opened = false;      // in pages the session can USE (chains of 9 and 8 pages both use 8 at ratio 1)
+    for (int b = 0; b < B; ++b) {
+        const SeqInfo& q = s->seq[(size_t)b];
+        const int el = prefix_eligible_pages(q);
+        const int k = (el > 0 && s->kv_rows[(size_t)b].empty()) ? prefix_usable_pages(s, prefix_peek(m, rg, q.instruct.data(), el)) : 0;
+        kmin = std::min(kmin, k); kmax = std::max(kmax, k); opened = opened || q.opened;
+    }
+    if (kmin != kmax && !opened && !s->prefix_common) return -1;
+    // (rows with open text, and the groups prefill_ragged has already formed, stay together: every row links what the row with
+    // the shortest chain can — the bits of this session shape with the cache off)
+    const int pages = kmin;
+    bool short_of = false;
+    for (int b = 0; b < B; ++b) {
+        const SeqInfo& q = s->seq[(size_t)b];
+        if (prefix_eligible_pages(q) < 1) continue;
+        const int got = prefix_acquire(m, rg, q.instruct.data(), pages, s->kv_rows[(size_t)b]);      // (counts the lookup, also of a miss)
+        short_of = short_of || got < pages;
+    }
+    if (pages < 1) return 0;
+    if (short_of) {      // a block went between the two looks (another thread's eviction): this prefill runs from 0
+        for (int b = 0; b < B; ++b) if (!s->kv_rows[(size_t)b].empty()) m->kv_pool.give(s->kv_rows[(size_t)b]);
+        return 0;
+    }
+    for (int b = 0; b < B; ++b) {
+        std::vector<float*>& row = s->kv_rows[(size_t)b];
+        const hipError_t e = hipMemcpyAsync(s->kv_table + (size_t)b * KV_MAX_PAGES, row.data(), row.size() * 8, hipMemcpyHostToDevice, s->stream);
+        if (e != hipSuccess) { *st = set_err(Q3_HIP_ERROR, "prefix cache: page table: %s", hipGetErrorString(e)); return 0; }
+        s->seq[(size_t)b].reused = pages * KV_PAGE_POS;
+    }
+    return pages * KV_PAGE_POS;
+}
+// the rows of a one-length session as a ragged batch (prefix_link said -1): requests rebuilt from the rows' own copies
+static void prefix_regroup(q3_session* s) {
+    s->regrouped = true;      // transplant_row also brings each row's prompt embeddings (Q3_GET_PREFILL_EMBEDS stays valid)
+    s->ragged.resize((size_t)s->B);
+    for (int b = 0; b < s->B; ++b) {
+        const SeqInfo& q = s->seq[(size_t)b];
+        q3_request r = q.req;
+        r.text_ids = q.text.data(); r.n_text = (int32_t)q.text.size();
+        r.instruct_ids = q.instruct.empty() ? nullptr : q.instruct.data(); r.n_instruct = (int32_t)q.instruct.size();
+        r.ref_codes = q.ref_codes.empty() ? nullptr : q.ref_codes.data(); r.n_ref = (int32_t)(q.ref_codes.size() / 16);
+        r.ref_text_ids = q.ref_text.empty() ? nullptr : q.ref_text.data(); r.n_ref_text = (int32_t)q.ref_text.size();
+        r.xvector = q.xvec.empty() ? nullptr : q.xvec.data();
+        s->ragged[(size_t)b].own(r, s->m->cfg.hidden);
+    }
+}
+
 // q3_session_prefill of a ragged first batch (session_create_any): the idle rows never run — every row's state comes from a side
 // session. Rows are grouped by prefill length in row order; a group of G rows is one batched side prefill.
 static q3_status prefill_ragged(q3_session* s) {
@@ -1066,13 +1205,26 @@ static q3_status prefill_ragged(q3_session* s) {
     s->kv_in_bf16 = s->kv_bf16;                          // the idle rows hold no pages: nothing to convert
     s->prefilled = true; s->frames_run = 0; s->codes_host_valid = false;      // transplant_row stamps rows with start_run = frames_run
     std::vector<char> placed((size_t)B, 0);
+    // prefix cache: rows of one length that would reuse different numbers of cached pages go into different groups (a batched
+    // prefill runs all its rows through the same passes). The look is a plan only: each side session looks again and links.
+    std::vector<int> hit((size_t)B, 0);
+    // The plan takes the regime and the rounding of a one-row group (the width of a group is not known before the groups are);
+    // where those depend on the width — the decode-step path, several chunks at ratio 1 — a group may link less than planned:
+    // its side session links what its shortest chain allows (prefix_common), which keeps the bits right and only costs hits.
+    if (prefix_session_ok(s))
+        for (int b = 0; b < B; ++b) {
+            const q3_request& r = s->ragged[(size_t)b].r;
+            const int el = r.mode == Q3_MODE_VOICE_DESIGN ? r.n_instruct / KV_PAGE_POS : 0;
+            int S = 0, Lb = 0; request_shape(r, &S, &Lb);
+            if (el > 0) hit[(size_t)b] = prefix_usable_pages_of(s->m, 1, S, prefix_peek(s->m, prefix_regime_of(s->m, 1, S, s->n_splits), r.instruct_ids, el));
+        }
     for (int b0 = 0; b0 < B; ++b0) {
         if (placed[(size_t)b0]) continue;
         int S0 = 0, L = 0; request_shape(s->ragged[(size_t)b0].r, &S0, &L);
         std::vector<int> rows; std::vector<q3_request> reqs; std::vector<int> limits;
         for (int b = b0; b < B; ++b) {
             int S = 0, Lb = 0; request_shape(s->ragged[(size_t)b].r, &S, &Lb);
-            if (placed[(size_t)b] || S != S0) continue;
+            if (placed[(size_t)b] || S != S0 || hit[(size_t)b] != hit[(size_t)b0]) continue;
             q3_request r = s->ragged[(size_t)b].r;
             // the row's RESOLVED limit (an ICL row's max_length is capped at max(75, 6 * n_text), talker.rs:646-710 / lib.rs:897-1046) is
             // what session_create_any sized max_frames for — the raw max_length of an ICL row may well exceed it
@@ -1084,7 +1236,7 @@ static q3_status prefill_ragged(q3_session* s) {
         q3_session* side_raw = nullptr;
         q3_status st = session_create(s->m, reqs.data(), (int)reqs.size(), 0, 0, &side_raw, s->stream);
         std::unique_ptr<q3_session> side(side_raw);
-        if (st == Q3_OK) { side->kv_bf16 = s->kv_bf16; }
+        if (st == Q3_OK) { side->kv_bf16 = s->kv_bf16; side->prefix_common = true; }
         std::vector<int> lim(rows.size(), 0);
         for (size_t j = 0; j < rows.size() && st == Q3_OK; ++j) st = transplant_check(s, side.get(), (int)j, limits[j], &lim[j]);
         if (st == Q3_OK) st = q3_session_prefill(side.get());
@@ -1104,6 +1256,23 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
     HIPC(hipSetDevice(m->device));
     if (!s->ragged.empty()) return prefill_ragged(s);
     const int B = s->B, H = c.hidden, S = s->prefill_len;
+    // prefix cache: the rows link the cached pages of their instructions and the prompt is computed from position P0 on
+    const bool cached = prefix_session_ok(s);
+    int P0 = 0;
+    if (cached) {
+        // a prefill that failed after linking (a later row's Q3_KV_OVERFLOW) left pages in the rows: they go back first, so that
+        // this attempt links again instead of computing [0, P) into pages the cache and other rows hold
+        bool leftover = false;
+        for (int b = 0; b < B; ++b) leftover = leftover || !s->kv_rows[(size_t)b].empty();
+        if (leftover) {
+            HIPC(sync_frames(s));
+            for (int b = 0; b < B; ++b) { kv_release_row(s, b); s->seq[(size_t)b].reused = 0; }
+        }
+        q3_status lst = Q3_OK;
+        P0 = prefix_link(s, &lst);
+        Q3C(lst);
+        if (P0 < 0) { prefix_regroup(s); return prefill_ragged(s); }      // rows that hit differently: each group keeps the bits of its own run
+    }
     for (int b = 0; b < B; ++b) Q3C(kv_reserve_row(s, b, S + 1));      // paged KV: the prompt's positions and the first frame's
     // 1. ids to project, per sequence: [instruct…, IM_START, ASSISTANT, NEWLINE, TTS_PAD, TTS_BOS, text…, TTS_EOS]
     std::vector<uint32_t> ids; ids.reserve(s->n_rows_total);
@@ -1200,23 +1369,12 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
     //    and the GEMV kernels take up to 16 rows for the price of one, so each weight pass carries a CHUNK of
     //    16/B consecutive positions per sequence (q3_kernels.h AttnArgs::rows_per_seq). Bit-identical to the
     //    one-position-at-a-time schedule (rows are independent in the GEMV; attention sees the same K/V).
-    static const int gemm_min = [] { const char* e = getenv("Q3_PREFILL_GEMM_MIN"); return e ? atoi(e) : 48; }();   // 0 disables the GEMM path
-    const bool tiles_ok = (d_nh_ok(c));
-    const int chunk = s->no_chunk ? 1 : (16 / B > 0 ? 16 / B : 1);
-    // The GEMM path works in 128-position tiles and its grids are sized to fill the chip in whole rounds (4096
-    // positions: 256 / 512 / 1536 workgroups of 256 CUs' worth); a few positions past the last full tile would cost every
-    // GEMM another round (4105 positions, one sequence: +9 ... +50 % per GEMM). Up to Q3_PREFILL_TAIL (default 32)
-    // trailing positions of a >= 1024-position prompt therefore go through the decode-step schedule below instead (about
-    // 1 ms per 16 rows at 4k context), which appends to the same KV cache. The rule looks at the PROMPT only — never at the
-    // batch — so which kernels compute a given position does not depend on how many sequences are prefilled together
-    // (a batch pays ceil(B * r / 16) passes for it; positions below the cut always take the GEMM, whose bits are
-    // batch-invariant; the decode-step kernels pick their tiling by the row count of a pass, like any decode step).
-    static const int tail_max = [] { const char* e = getenv("Q3_PREFILL_TAIL"); return e ? atoi(e) : 32; }();
-    int t_begin = 0;
-    if (!s->no_chunk && !s->debug && gemm_min > 0 && S >= gemm_min && tiles_ok) {
-        const int r = S % 128;
-        const int Sg = (S >= 1024 && r > 0 && r <= tail_max) ? S - r : S;
-        Q3C(prefill_gemm(s, S, Sg, Sg == S));
+    //    Long prompts run their first Sg positions as GEMM passes and only a short tail here (prefill_cut). Positions below P0
+    //    are in linked pages already: neither schedule computes them again.
+    const int chunk = prefill_step_chunk(s);
+    int t_begin = P0, Sg = 0;
+    if (prefill_cut(s, S, &Sg)) {
+        if (P0 < Sg) Q3C(prefill_gemm(s, S, Sg, Sg == S, P0));
         t_begin = Sg;
     }
     for (int t0 = t_begin; t0 < S; t0 += chunk) {
@@ -1237,6 +1395,14 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
     // (bf16-KV sessions capture later: which attention kernel the frame holds depends on the conversion below.)
     if (s->precapture && !s->kv_bf16 && !s->debug && !s->profile) Q3C(frame_capture(s, true));
     HIPC(sync_frames(s));
+    if (cached) {      // the stream is drained: the rows' eligible pages that are not cached yet get a second holder, the cache (no copy)
+        const PrefixRegime rg = prefix_regime(s);
+        for (int b = 0; b < B; ++b) {
+            const SeqInfo& q = s->seq[(size_t)b];
+            const int el = prefix_eligible_pages(q);
+            if (el > 0 && (int)s->kv_rows[(size_t)b].size() >= el) prefix_insert(s->m, rg, q.instruct.data(), el, s->kv_rows[(size_t)b].data());
+        }
+    }
     if (s->kv_bf16 && !s->kv_in_bf16) Q3C(kv_convert_to_bf16(s));       // the prompt's K/V moves into pages of the bf16 pool, once
     s->prefilled = true; s->frames_run = 0; s->codes_host_valid = false;
     return Q3_OK;

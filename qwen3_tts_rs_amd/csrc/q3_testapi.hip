@@ -1,5 +1,5 @@
 // q3_testapi.hip — low-level entry points of the parity tests, submission / profiling read-outs, bench.py roofline replays
-// (one of the five units of the engine: q3_engine.h says which holds what)
+// (one of the units of the engine: q3_engine.h says which holds what)
 #include "q3_engine.h"
 
 extern "C" q3_status q3_talker_step(q3_session* s, const float* embeds_host, float* hidden_host, float* logits_host) {

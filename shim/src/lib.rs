@@ -45,6 +45,9 @@ pub mod ffi {
         pub fn q3_model_kv_pool_trim(m: *mut c_void, bytes_freed: *mut usize) -> i32;
         pub fn q3_model_set_codec_planes(m: *mut c_void, planes: i32) -> i32;
         pub fn q3_model_kv_pool_info(m: *mut c_void, page_positions: *mut i32, page_bytes: *mut usize, pages_total: *mut i32, pages_in_use: *mut i32, pages_peak: *mut i32) -> i32;
+        pub fn q3_model_prefix_cache(m: *mut c_void, max_pages: i32) -> i32;
+        pub fn q3_model_prefix_cache_info(m: *mut c_void, max_pages: *mut i32, pages_cached: *mut i32, pages_shared: *mut i32, lookups: *mut i64, hit_positions: *mut i64, evictions: *mut i64) -> i32;
+        pub fn q3_session_prefix_info(s: *mut c_void, b: i32, reused_positions: *mut i32) -> i32;
         pub fn q3_codes_to_tensor(frames: *const u32, n_frames: i32, out: *mut i64);
         pub fn q3_session_create(m: *mut c_void, reqs: *const Q3Request, batch: i32, out: *mut *mut c_void) -> i32;
         pub fn q3_session_prefill(s: *mut c_void) -> i32;
@@ -276,6 +279,16 @@ impl Qwen3TTS {
     /// bails on overflow (kv_cache.rs:293-300); here a request that needs a page beyond the cap fails with the same error before
     /// anything runs.
     pub fn set_kv_pool_limit(&self, max_pages: i32) -> Result<()> { check(unsafe { q3_model_kv_pool_limit(self.model, max_pages) }) }
+    /// Capacity of the prefix cache in KV pages (0 = off, the default): the prefilled pages of a VoiceDesign instruction are linked
+    /// into later requests with the same instruction instead of being computed again. No reference counterpart (the reference
+    /// prefills the whole prompt per call, talker.rs:585-627); the output bits do not depend on it.
+    pub fn set_prefix_cache(&self, max_pages: i32) -> Result<()> { check(unsafe { q3_model_prefix_cache(self.model, max_pages) }) }
+    /// (capacity, pages cached, cached pages a row holds too, lookups, prompt positions reused, evictions)
+    pub fn prefix_cache_info(&self) -> Result<(i32, i32, i32, i64, i64, i64)> {
+        let (mut mx, mut n, mut sh, mut lk, mut hp, mut ev) = (0i32, 0i32, 0i32, 0i64, 0i64, 0i64);
+        check(unsafe { q3_model_prefix_cache_info(self.model, &mut mx, &mut n, &mut sh, &mut lk, &mut hp, &mut ev) })?;
+        Ok((mx, n, sh, lk, hp, ev))
+    }
     /// Slabs of the KV page pool none of whose pages is held go back to the device; returns the bytes freed.
     pub fn kv_pool_trim(&self) -> Result<usize> {
         let mut n: usize = 0;
