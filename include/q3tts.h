@@ -492,6 +492,57 @@ q3_status q3_codec_stream_info(q3_codec_stream* cs, int* block_frames, size_t* b
  * caches; no stack runs, no samples. Later pushes to the row give the samples of q3_decode_codes(primed | pushed) with the
  * first n_frames * samples_per_frame cut — a voice-clone prompt's reference frames (lib.rs:1022-1041). */
 q3_status q3_codec_stream_prime(q3_codec_stream* cs, int row, const uint32_t* frames_host, int n_frames);
+/* ---------------- output stage: streamed audio at a requested sample rate, f32 or PCM16 ----------------
+ * A stage has `rows` independent rows; each has an output rate, an output format, the last 128 input samples it still needs and a
+ * count of what it has consumed. Its input is the engine's 24 kHz mono f32. ONE launch serves every row of a push, whatever their
+ * rates, formats and positions. The filter is q3_resample's (the 128-tap Blackman-Harris²-windowed sinc of audio/resample.rs:83-97
+ * at 0.95 x the lower Nyquist): with L / M = sample_rate / 24000 in lowest terms, output i sits at input time i M / L and is the
+ * dot product of row (i M) mod L of a table taps[L][128] — q3_resample's weights in f64, rounded to f32 — with inputs c - 63 ..
+ * c + 64, c = floor(i M / L); f32 products summed in an order that does not depend on how the input was cut into pushes.
+ * Rates: 4000..96000 Hz with L <= 320 (8000, 11025, 12000, 16000, 22050, 32000, 44100, 48000 among them), else Q3_UNSUPPORTED
+ * before the device is touched. 24000 Hz is a copy: no filter, nothing held back, the bits of the 24 kHz path.
+ * Streaming rule: after n_in input samples in total a row has returned every output i with floor(i M / L) + 64 <= n_in - 1 (the
+ * first push returns about 64 L / M samples fewer than it was given: 2.7 ms); a push with last != 0 returns the rest, up to
+ * llround(n_in * sample_rate / 24000) samples in total, against zeros beyond the end — q3_resample's n_out and edge handling.
+ * The row then takes no more samples until q3_pcm_stage_set / _reset restarts it (a further flush returns 0 samples).
+ * Q3_PCM_S16: q3_pcm16_from_f32's rule on the device (clamp to +-1, x 32767.0f, truncation toward zero, NaN -> 0); the copy to
+ * the host carries 2 bytes per sample. No reference counterpart (nearest: audio::resample / save_wav, whole clips on the host). */
+enum { Q3_PCM_F32 = 0, Q3_PCM_S16 = 1 };
+typedef struct q3_pcm_stage q3_pcm_stage;
+/* max_push_samples: the most 24 kHz samples one row takes in one push */
+q3_status q3_pcm_stage_create(int device, int rows, size_t max_push_samples, q3_pcm_stage** out);
+void      q3_pcm_stage_free(q3_pcm_stage* ps);
+q3_status q3_pcm_stage_set(q3_pcm_stage* ps, int row, uint32_t sample_rate, int format);   /* also restarts the row */
+q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row);                                   /* row starts over at sample 0 */
+/* n_in[i] samples (host) for row rows[i], all rows in one pass; last (may be NULL = none) flushes a row. out_host[i] receives
+ * n_samples[i] samples in the row's format (float or int16_t), at most cap_samples[i]. A null argument, a row out of range or
+ * listed twice, n_in[i] above max_push_samples, samples for a flushed row or a cap below what the push returns
+ * (q3_pcm_stage_bound) is Q3_INVALID_ARG and changes no row; so does a push that fails on the device. */
+q3_status q3_pcm_stage_push(q3_pcm_stage* ps, int n_rows, const int* rows, const float* const* in_host, const size_t* n_in,
+                            const int* last, void* const* out_host, const size_t* cap_samples, size_t* n_samples);
+q3_status q3_pcm_stage_bound(uint32_t sample_rate, size_t n_in, size_t* n_out_max);          /* host only: cap for a push of n_in */
+/* host only: L, M and (taps_host != NULL) the table [L][128] the stage uploads for this rate */
+q3_status q3_pcm_stage_taps(uint32_t sample_rate, float* taps_host, size_t cap_floats, int* L, int* M);
+/* q3_codec_stream_push through a stage: the same decode pass, then the samples of row rows[i] go through stage row ps_rows[i]
+ * on the stream's stream and the converted bytes are what is copied to the host (out_host[i], n_samples[i] of at most
+ * cap_samples[i]; last may be NULL). n_frames[i] = 0 with last[i] != 0 only flushes. The checks of both calls apply, before
+ * anything changes. The stage is the caller's: q3_codec_stream_reset does not restart a stage row — it follows the samples that
+ * were delivered, so a row that is pushed again from its first frame after a failed push goes on where its listener stopped. */
+q3_status q3_codec_stream_push_out(q3_codec_stream* cs, int n_rows, const int* rows, const uint32_t* const* frames_host, const int* n_frames,
+                                   q3_pcm_stage* ps, const int* ps_rows, const int* last,
+                                   void* const* out_host, const size_t* cap_samples, size_t* n_samples);
+/* Sessions: the output of q3_session_next_chunks_out, for all rows; legal before the first streamed chunk (Q3_INVALID_ARG after).
+ * q3_session_replace restarts the replaced row's stage row. q3_session_next_chunks_out is q3_session_next_chunks through the
+ * session's stage: out_host[b] receives n_samples[b] samples at that rate and format; a row's tail is flushed in the call that
+ * reports it done. q3_session_next_chunk* / _decode / _run ignore the setting. */
+q3_status q3_session_set_output(q3_session* s, uint32_t sample_rate, int format);
+q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_host, const size_t* cap_samples, size_t* n_samples, int* done);
+/* Batcher: a streamed ticket's own output (q3_batcher_submit_streamed, or _submit_open with Q3_WANT_STREAM), legal between its
+ * submission and the next q3_batcher_step. Its samples then leave through q3_batcher_read_out (cap_samples / n_samples count
+ * samples of the ticket's format; otherwise q3_batcher_read's contract) — q3_batcher_read refuses such a ticket and names
+ * q3_batcher_read_out; q3_batcher_read_out serves every streamed ticket (24 kHz f32 by default). */
+q3_status q3_batcher_ticket_output(q3_batcher* b, int64_t ticket, uint32_t sample_rate, int format);
+q3_status q3_batcher_read_out(q3_batcher* b, int64_t ticket, void* out_host, size_t cap_samples, size_t* n_samples, int* done);
 /* codes_to_tensor (lib.rs:1417-1431): [n][16] u32 → [16][n] i64 (host helper) */
 void      q3_codes_to_tensor(const uint32_t* frames, int n_frames, int64_t* out);
 

@@ -114,6 +114,20 @@ SYMBOLS = {
     "q3_codec_stream_reset": (c_int, [c_void_p, c_int]),
     "q3_codec_stream_pos": (c_int, [c_void_p, c_int, P(c_int)]),
     "q3_codec_stream_push": (c_int, [c_void_p, c_int, P(c_int), P(c_void_p), P(c_int), P(c_void_p), P(ctypes.c_size_t)]),
+    "q3_pcm_stage_create": (c_int, [c_int, c_int, ctypes.c_size_t, P(c_void_p)]),
+    "q3_pcm_stage_free": (None, [c_void_p]),
+    "q3_pcm_stage_set": (c_int, [c_void_p, c_int, ctypes.c_uint32, c_int]),
+    "q3_pcm_stage_reset": (c_int, [c_void_p, c_int]),
+    "q3_pcm_stage_push": (c_int, [c_void_p, c_int, P(c_int), P(c_void_p), P(ctypes.c_size_t), P(c_int), P(c_void_p), P(ctypes.c_size_t),
+                                  P(ctypes.c_size_t)]),
+    "q3_pcm_stage_bound": (c_int, [ctypes.c_uint32, ctypes.c_size_t, P(ctypes.c_size_t)]),
+    "q3_pcm_stage_taps": (c_int, [ctypes.c_uint32, c_void_p, ctypes.c_size_t, P(c_int), P(c_int)]),
+    "q3_codec_stream_push_out": (c_int, [c_void_p, c_int, P(c_int), P(c_void_p), P(c_int), c_void_p, P(c_int), P(c_int), P(c_void_p),
+                                         P(ctypes.c_size_t), P(ctypes.c_size_t)]),
+    "q3_session_set_output": (c_int, [c_void_p, ctypes.c_uint32, c_int]),
+    "q3_session_next_chunks_out": (c_int, [c_void_p, P(c_void_p), P(ctypes.c_size_t), P(ctypes.c_size_t), P(c_int)]),
+    "q3_batcher_ticket_output": (c_int, [c_void_p, ctypes.c_int64, ctypes.c_uint32, c_int]),
+    "q3_batcher_read_out": (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_size_t, P(ctypes.c_size_t), P(c_int)]),
     "q3_session_replace": (c_int, [c_void_p, c_int, c_void_p]),
     "q3_batcher_create": (c_int, [c_void_p, c_int, c_int, c_int, P(c_void_p)]),
     "q3_batcher_free": (None, [c_void_p]),

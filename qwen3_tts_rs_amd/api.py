@@ -258,6 +258,26 @@ class Session:
         check(lib.q3_session_next_chunks(self._h, ptrs, caps, n, d))
         return [((AudioBuffer(bufs[b][:n[b]].copy()) if n[b] else None), bool(d[b])) for b in range(B)]
 
+    def set_output(self, rate: int, pcm16: bool = False):
+        """The output of `next_chunks_out`, for all rows (q3_session_set_output): a sample rate the output stage supports, float32
+        or int16. Legal before the first streamed chunk; `next_chunks` and the whole-utterance calls ignore it."""
+        check(lib.q3_session_set_output(self._h, int(rate), PCM_S16 if pcm16 else PCM_F32))
+        self._out = (int(rate), bool(pcm16))
+
+    def next_chunks_out(self) -> List[Tuple[Optional[AudioBuffer], bool]]:
+        """`next_chunks` through the session's output stage (q3_session_next_chunks_out): one (chunk or None, done) per row, the
+        chunks at the rate of `set_output`, int16 arrays when it asked for them. A row's last samples (the resampler holds 64
+        input samples back) come in the call that reports it done."""
+        B = self.B; spf = self.model.config.samples_per_frame
+        rate, s16 = getattr(self, "_out", (24000, False))
+        cap = pcm_stage_bound(rate, max(self.options.chunk_frames, 1) * spf)
+        bufs = [np.zeros(cap, dtype=np.int16 if s16 else np.float32) for _ in range(B)]
+        ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data_as(ctypes.c_void_p) for b in bufs])
+        caps = (ctypes.c_size_t * B)(*[b.size for b in bufs])
+        n = (ctypes.c_size_t * B)(); d = (ctypes.c_int * B)()
+        check(lib.q3_session_next_chunks_out(self._h, ptrs, caps, n, d))
+        return [((AudioBuffer(bufs[b][:n[b]].copy(), rate) if n[b] else None), bool(d[b])) for b in range(B)]
+
     def prefill(self):
         check(lib.q3_session_prefill(self._h))
 
@@ -422,6 +442,7 @@ class Batcher:
         check(lib.q3_batcher_create(model._h, int(slots), int(frame_budget), int(prompt_budget), ctypes.byref(h)))
         self._h = h
         self._streamed = set()                      # tickets of submit_streamed (their samples leave through read, not fetch)
+        self._output = {}                           # ticket -> (rate, pcm16) of the streamed tickets with an output of their own
 
     def close(self):
         if getattr(self, "_h", None):
@@ -437,26 +458,49 @@ class Batcher:
         check(lib.q3_batcher_submit(self._h, ctypes.byref(r), 1 if want_pcm else 0, ctypes.byref(t)))
         return int(t.value)
 
-    def submit_streamed(self, utt: Utterance) -> int:
-        """Queue one request whose audio is delivered while it runs (`read`); returns its ticket."""
+    def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False) -> int:
+        """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16: the
+        ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked."""
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
         t = ctypes.c_int64()
         check(lib.q3_batcher_submit_streamed(self._h, ctypes.byref(r), ctypes.byref(t)))
         self._streamed.add(int(t.value))
+        self._set_output(int(t.value), sample_rate, pcm16)
         return int(t.value)
 
-    def submit_open(self, utt: Utterance, want: str = "stream") -> int:
+    def _set_output(self, ticket: int, sample_rate: int, pcm16: bool):
+        if int(sample_rate) == 24000 and not pcm16:
+            return
+        try:
+            self.ticket_output(ticket, sample_rate, pcm16)
+        except _lib.Q3Error:
+            self.cancel(ticket); self.fetch(ticket)      # the ticket was never run: it leaves with the refusal
+            raise
+
+    def ticket_output(self, ticket: int, sample_rate: int, pcm16: bool = False):
+        """A streamed ticket's own output (q3_batcher_ticket_output): between its submission and the next `step`."""
+        check(lib.q3_batcher_ticket_output(self._h, int(ticket), int(sample_rate), PCM_S16 if pcm16 else PCM_F32))
+        if int(sample_rate) == 24000 and not pcm16:
+            self._output.pop(int(ticket), None)
+        else:
+            self._output[int(ticket)] = (int(sample_rate), bool(pcm16))
+
+    def submit_open(self, utt: Utterance, want: str = "stream", sample_rate: int = 24000, pcm16: bool = False) -> int:
         """Queue one request whose text arrives in pieces (`append_text`); the utterance carries the first ids. want: "stream"
-        (samples through `read`), "pcm" or "codes" (through `fetch`). Returns its ticket."""
+        (samples through `read`), "pcm" or "codes" (through `fetch`). sample_rate / pcm16 (want "stream" only): the ticket's own
+        output, as in `submit_streamed`. Returns its ticket."""
         if want not in self._WANT:
             raise ValueError(f"want must be one of {sorted(self._WANT)}, not {want!r}")
+        if want != "stream" and (int(sample_rate) != 24000 or pcm16):
+            raise ValueError("sample_rate / pcm16 apply to streamed tickets (want=\"stream\")")
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
         t = ctypes.c_int64()
         check(lib.q3_batcher_submit_open(self._h, ctypes.byref(r), self._WANT[want], ctypes.byref(t)))
         if want == "stream":
             self._streamed.add(int(t.value))
+            self._set_output(int(t.value), sample_rate, pcm16)
         return int(t.value)
 
     def append_text(self, ticket: int, ids: Sequence[int], last: bool = False):
@@ -479,9 +523,15 @@ class Batcher:
 
     def read(self, ticket: int, max_samples: Optional[int] = None) -> Tuple[np.ndarray, bool]:
         """(samples of a streamed ticket that have landed and were not read yet — at most max_samples —, done). Never blocks;
-        done is True once the ticket has finished and its last sample has been read. A failed ticket raises its error."""
+        done is True once the ticket has finished and its last sample has been read. A failed ticket raises its error. A ticket
+        with an output of its own (`submit_streamed(..., sample_rate=, pcm16=)`) is read in that format (q3_batcher_read_out)."""
         if max_samples is None:
             max_samples = max(self.poll(ticket)[2], 1)      # every landed sample (more may land before the read: they come next time)
+        if int(ticket) in self._output:
+            buf = np.zeros(int(max_samples), np.int16 if self._output[int(ticket)][1] else np.float32)
+            n = ctypes.c_size_t(); d = ctypes.c_int()
+            check(lib.q3_batcher_read_out(self._h, int(ticket), buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(n), ctypes.byref(d)))
+            return buf[:n.value].copy(), bool(d.value)
         buf = np.zeros(int(max_samples), np.float32)
         n = ctypes.c_size_t(); d = ctypes.c_int()
         check(lib.q3_batcher_read(self._h, int(ticket), buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(n), ctypes.byref(d)))
@@ -514,6 +564,7 @@ class Batcher:
         check(lib.q3_batcher_fetch(self._h, int(ticket), codes.ctypes.data_as(ctypes.c_void_p), n,
                                    pcm.ctypes.data_as(ctypes.c_void_p) if ns else None, ns))
         self._streamed.discard(int(ticket))          # released by the library (a call that raised above keeps it)
+        self._output.pop(int(ticket), None)
         return codes, (pcm if ns else None)
 
     def run_all(self, utts: Sequence[Utterance], want_pcm: bool = True, poll_frames: int = 32, use_graph: bool = True):
@@ -999,6 +1050,11 @@ class Qwen3TTS:
         32): the state is allocated in blocks of that many frames as a row grows, at most max_blocks of them (0 = no bound)."""
         return CodecStream(self, rows, max_frames, block_frames, max_blocks)
 
+    def pcm_stage(self, rows: int, max_push_samples: int) -> "PcmStage":
+        """The output stage (q3_pcm_stage_*): rows that each resample the engine's 24 kHz f32 to their own rate and format as it
+        streams; max_push_samples: the most 24 kHz samples a row takes in one push."""
+        return PcmStage(self, rows, max_push_samples)
+
     def frame_embed(self, sem_token: int, codes15, text_add: np.ndarray) -> np.ndarray:
         c = np.ascontiguousarray(codes15, dtype=np.uint32); t = np.ascontiguousarray(text_add, dtype=np.float32)
         out = np.zeros(self.config.hidden, dtype=np.float32)
@@ -1029,9 +1085,26 @@ class CodecStream:
         return {"block_frames": bf.value, "block_bytes": bb.value, "blocks_total": tot.value, "blocks_in_use": use.value,
                 "blocks_peak": peak.value}
 
-    def push(self, frames: dict) -> dict:
-        """{row: codes [n][16]} -> {row: samples [n * samples_per_frame]}: every row of the call in one decode pass."""
-        return self._push_lists(list(frames.keys()), list(frames.values()))
+    def push(self, frames: dict, stage: Optional["PcmStage"] = None, stage_rows: Optional[dict] = None, last=()) -> dict:
+        """{row: codes [n][16]} -> {row: samples [n * samples_per_frame]}: every row of the call in one decode pass.
+        stage: the rows' samples go through it (q3_codec_stream_push_out) — row r through stage row stage_rows[r] (default r) —
+        and come back at that row's rate and format; rows in `last` flush their stage row (no frames: only the flush)."""
+        if stage is None:
+            return self._push_lists(list(frames.keys()), list(frames.values()))
+        rows = list(frames.keys()); n = len(rows); spf = self.model.config.samples_per_frame
+        cs = [np.ascontiguousarray(frames[r], dtype=np.uint32).reshape(-1, 16) for r in rows]
+        srows = [int((stage_rows or {}).get(r, r)) for r in rows]
+        outs = [np.zeros(stage.bound(sr, c.shape[0] * spf), dtype=stage.dtype(sr)) for sr, c in zip(srows, cs)]
+        r_ = (ctypes.c_int * n)(*[int(x) for x in rows])
+        fp = (ctypes.c_void_p * n)(*[c.ctypes.data_as(ctypes.c_void_p) for c in cs])
+        nf = (ctypes.c_int * n)(*[c.shape[0] for c in cs])
+        sr_ = (ctypes.c_int * n)(*srows)
+        ls = (ctypes.c_int * n)(*[1 if r in last else 0 for r in rows])
+        op = (ctypes.c_void_p * n)(*[o.ctypes.data_as(ctypes.c_void_p) for o in outs])
+        cp = (ctypes.c_size_t * n)(*[o.size for o in outs])
+        ns = (ctypes.c_size_t * n)()
+        check(lib.q3_codec_stream_push_out(self._h, n, r_, fp, nf, stage._h, sr_, ls, op, cp, ns))
+        return {int(rows[i]): outs[i][:ns[i]].copy() for i in range(n)}
 
     def _push_lists(self, rows: Sequence[int], codes: Sequence[np.ndarray], cap: Optional[Sequence[int]] = None) -> dict:
         """push with the rows as given (a row may be listed twice: the call is then refused); cap overrides the buffer sizes."""
@@ -1059,6 +1132,96 @@ class CodecStream:
             lib.q3_codec_stream_free(self._h); self._h = None
 
     __del__ = close
+
+
+PCM_F32, PCM_S16 = 0, 1
+
+
+def pcm_stage_taps(rate: int) -> Tuple[np.ndarray, int, int]:
+    """(taps [L][128] f32, L, M) of the output stage's filter for `rate` (q3_pcm_stage_taps); an unsupported rate raises."""
+    L = ctypes.c_int(); M = ctypes.c_int()
+    check(lib.q3_pcm_stage_taps(int(rate), None, 0, ctypes.byref(L), ctypes.byref(M)))
+    t = np.zeros((L.value, 128), np.float32)
+    check(lib.q3_pcm_stage_taps(int(rate), t.ctypes.data_as(ctypes.c_void_p), t.size, ctypes.byref(L), ctypes.byref(M)))
+    return t, L.value, M.value
+
+
+def pcm_stage_bound(rate: int, n_in: int) -> int:
+    """The most samples one push of n_in 24 kHz samples returns at `rate` (q3_pcm_stage_bound)."""
+    n = ctypes.c_size_t()
+    check(lib.q3_pcm_stage_bound(int(rate), int(n_in), ctypes.byref(n)))
+    return int(n.value)
+
+
+class PcmStage:
+    """The output stage (q3_pcm_stage): `rows` independent rows, each with its own output rate and format (float32 or int16), fed
+    24 kHz float32 in pushes of any size; one pass serves every row of a push."""
+
+    def __init__(self, model, rows: int, max_push_samples: int):
+        """model: a Qwen3TTS (the stage is created on its device) or a device index."""
+        self.device_index = int(model) if isinstance(model, int) else int(model.device_index)
+        self.rows = int(rows); self.max_push_samples = int(max_push_samples)
+        self._fmt = [(24000, False)] * self.rows
+        self._h = ctypes.c_void_p()
+        check(lib.q3_pcm_stage_create(self.device_index, self.rows, self.max_push_samples, ctypes.byref(self._h)))
+
+    def set(self, row: int, rate: int, pcm16: bool = False):
+        """Row's output rate and format; also restarts the row."""
+        check(lib.q3_pcm_stage_set(self._h, int(row), int(rate), PCM_S16 if pcm16 else PCM_F32))
+        self._fmt[int(row)] = (int(rate), bool(pcm16))
+
+    def reset(self, row: int):
+        check(lib.q3_pcm_stage_reset(self._h, int(row)))
+
+    def rate(self, row: int) -> int:
+        return self._fmt[int(row)][0]
+
+    def dtype(self, row: int):
+        return np.int16 if self._fmt[int(row)][1] else np.float32
+
+    def bound(self, row: int, n_in: int) -> int:
+        return pcm_stage_bound(self._fmt[int(row)][0], n_in)
+
+    def push(self, samples: dict, last=()) -> dict:
+        """{row: 24 kHz f32 samples} -> {row: samples at the row's rate and format}, every row in one pass; rows in `last` are
+        flushed (their input ends here)."""
+        return self._push_lists(list(samples.keys()), list(samples.values()), [r in last for r in samples.keys()])
+
+    def _push_lists(self, rows: Sequence[int], samples: Sequence[np.ndarray], last: Sequence[bool], cap: Optional[Sequence[int]] = None) -> dict:
+        """push with the rows as given (a row may be listed twice: the call is then refused); cap overrides the buffer sizes."""
+        n = len(rows)
+        xs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in samples]
+        ok = [0 <= int(r) < self.rows for r in rows]
+        outs = [np.zeros(self.bound(r, x.size) if k else 1, dtype=self.dtype(r) if k else np.float32) for r, x, k in zip(rows, xs, ok)]
+        r_ = (ctypes.c_int * n)(*[int(x) for x in rows])
+        ip = (ctypes.c_void_p * n)(*[x.ctypes.data_as(ctypes.c_void_p) for x in xs])
+        ni = (ctypes.c_size_t * n)(*[x.size for x in xs])
+        ls = (ctypes.c_int * n)(*[1 if l else 0 for l in last])
+        op = (ctypes.c_void_p * n)(*[o.ctypes.data_as(ctypes.c_void_p) for o in outs])
+        cp = (ctypes.c_size_t * n)(*[int(c) for c in (cap if cap is not None else [o.size for o in outs])])
+        ns = (ctypes.c_size_t * n)()
+        check(lib.q3_pcm_stage_push(self._h, n, r_, ip, ni, ls, op, cp, ns))
+        return {int(rows[i]): outs[i][:ns[i]].copy() for i in range(n)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.q3_pcm_stage_free(self._h); self._h = None
+
+    __del__ = close
+
+
+def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0) -> AudioBuffer:
+    """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked — what a caller
+    of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their result."""
+    x = np.ascontiguousarray(audio.samples if isinstance(audio, AudioBuffer) else audio, dtype=np.float32).reshape(-1)
+    if isinstance(audio, AudioBuffer) and audio.sample_rate != 24000:
+        raise ValueError(f"resample_gpu takes the engine's 24 kHz audio, not {audio.sample_rate} Hz")
+    ps = PcmStage(int(device), 1, max(x.size, 1))
+    try:
+        ps.set(0, rate, pcm16)
+        return AudioBuffer(ps.push({0: x}, last=(0,))[0], int(rate))
+    finally:
+        ps.close()
 
 
 def pcm16(samples: np.ndarray) -> np.ndarray:

@@ -53,6 +53,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--xvector-npy", default=None, help="speaker embedding [hidden] f32 (.npy) for voice cloning")
     ap.add_argument("--ref-codes-bin", default=None, help="reference codec frames (codes_*.bin) for ICL voice cloning")
     ap.add_argument("--streaming", action="store_true", help="stream chunks (reports time to first audio)")
+    ap.add_argument("--output-rate", type=int, default=24000, metavar="HZ",
+                    help="with --streaming: the chunks leave through the output stage at this sample rate (8000, 16000, 44100, 48000, ...); "
+                         "the WAV header carries it")
     ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
                     help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
                          "first token to the first audio; writes the same WAV as without the flag)")
@@ -245,7 +248,29 @@ def main(argv=None) -> int:
             utt.ref_text_ids = tok.encode(a.ref_text or "")
     print(f"Generating up to {frames} frames...")
     t1 = time.time(); ttfa = None
-    if a.streaming:
+    out_rate = 24000
+    if a.output_rate != 24000 and not a.streaming:
+        print("error: --output-rate applies to --streaming (resample a whole utterance with api.resample_gpu)", file=sys.stderr)
+        return 2
+    if a.streaming and a.output_rate != 24000:
+        # the chunks of the streaming session, each through the session's output stage as it leaves
+        s = model.session([utt], opts)
+        try:
+            s.set_output(a.output_rate)
+        except api._lib.Q3Error as e:
+            print(f"error: {e}", file=sys.stderr)
+            return 2
+        chunks, done = [], False
+        while not done:
+            c, done = s.next_chunks_out()[0]
+            if c is not None:
+                if ttfa is None:
+                    ttfa = (time.time() - t1) * 1000.0
+                chunks.append(c.samples)
+        samples = np.concatenate(chunks) if chunks else np.zeros(0, np.float32)
+        codes = s.codes(0); s.close()
+        timing = None; out_rate = a.output_rate
+    elif a.streaming:
         ss = api.StreamingSession(model, utt, opts)
         chunks = []
         for c in ss:
@@ -265,7 +290,7 @@ def main(argv=None) -> int:
         samples, codes = audio[0].samples, s.codes(0); s.close()
     wall = time.time() - t1
     n = int(codes.shape[0])
-    audio = api.AudioBuffer(samples, 24000)
+    audio = api.AudioBuffer(samples, out_rate)
     print(f"Generated: {audio.duration():.2f}s, {len(audio)} samples, {n} frames in {wall * 1e3:.0f} ms (RTF {wall / max(audio.duration(), 1e-9):.3f})"
           + (f", TTFA {ttfa:.1f} ms" if ttfa is not None else ""))
     os.makedirs(a.output_dir, exist_ok=True)
@@ -274,7 +299,7 @@ def main(argv=None) -> int:
     api.save_codes_binary(os.path.join(a.output_dir, f"codes_seed{a.seed}_frames{n}.bin"), codes)
     api.save_audio_binary(os.path.join(a.output_dir, f"audio_seed{a.seed}_frames{n}.bin"), samples)
     meta = {"text": a.text, "seed": a.seed, "num_frames": n, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
-            "input_ids": ids, "codes_shape": [n, 16], "audio_samples": int(len(audio)), "sample_rate": 24000}
+            "input_ids": ids, "codes_shape": [n, 16], "audio_samples": int(len(audio)), "sample_rate": out_rate}
     with open(os.path.join(a.output_dir, f"metadata_seed{a.seed}_frames{n}.json"), "w") as f:
         json.dump(meta, f, indent=2)
     print(f"Saved WAV to: {wav}")

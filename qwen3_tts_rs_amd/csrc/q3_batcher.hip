@@ -84,6 +84,7 @@ q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limi
     }
     if (b == 0) s->stream_pos = 0;       // q3_session_next_chunk (the row-0 streaming call) starts over with the new utterance too
     if (s->cstream) codec_stream_reset(s->cstream, b);      // q3_session_next_chunks: the row's vocoder state belonged to the old utterance
+    if (s->ostage) pcm_stage_reset(s->ostage, b);           // q3_session_next_chunks_out: so did its output row's
     s->codes_host_valid = false;
     return Q3_OK;
 }
@@ -173,6 +174,12 @@ struct BatTicket {
     // for it — already holds; the rest goes in with the next flush of q3_batcher_step. Host thread only.
     bool open = false, closed = false, close_taken = false; std::vector<uint32_t> text_all; size_t n_taken = 0;
     bool cancelled = false;                             // q3_batcher_cancel took its row (or its place in the queue)
+    // A streamed ticket's own output (q3_batcher_ticket_output; host thread, fixed before the step that follows `born`). o_conv: other
+    // than 24 kHz f32 — its samples go through the worker's output stage and land, as bytes of that format, in sout (under the
+    // worker's mutex, like spcm, which stays empty) and leave through q3_batcher_read_out alone.
+    long born = 0; uint32_t o_rate = 24000; int o_fmt = Q3_PCM_F32; bool o_conv = false;
+    std::vector<char> sout; size_t o_read = 0;
+    size_t o_bytes() const { return o_fmt == Q3_PCM_S16 ? 2 : 4; }
 };
 // frames [f0, f0 + n) of a streamed ticket for the stream row of its slot: `first` resets the row (and primes it with the ticket's
 // reference frames), `last` gives the row's blocks back once the samples have landed
@@ -199,6 +206,7 @@ struct q3_batcher {
     // streamed tickets: the parts of the step in progress (one job at its end), the stream's shape (environment, read at create)
     std::vector<StreamPart> sparts; int n_streamed = 0;
     int s_block_frames = 128, s_max_blocks = 0;
+    long steps = 0;                                   // q3_batcher_step calls so far (q3_batcher_ticket_output: before the ticket's first)
     bool want_text = false;                           // an open ticket was submitted: the session runs the frame with the hold kernels
     // Q3_BAT_TEXT_STATS=1 (development aid): what the text flushes did, printed when the batcher is freed
     long tx_flushes = 0, tx_tokens = 0, tx_steps = 0; double tx_ms = 0;
@@ -217,6 +225,7 @@ struct BatDecoder {
     std::thread thr; std::mutex mu; std::condition_variable cv, cv_done; std::deque<DecJob> q; bool stop = false;
     hipStream_t stream = nullptr; CodecWS ws;
     q3_codec_stream* cs = nullptr;                    // the streamed tickets' vocoder state (created by the first stream job)
+    q3_pcm_stage* ps = nullptr;                       // their output stage, one row per slot (created by the first part of a ticket with an output of its own)
     int info_bf = 0, info_total = 0, info_use = 0, info_peak = 0; size_t info_bytes = 0;      // its figures after the last job (under mu)
     // Q3_BAT_STREAM_STATS=1 (development aid): what the worker did, printed when the batcher is freed
     long st_jobs = 0, st_pushes = 0, st_frames = 0, st_depth_sum = 0; int st_depth_max = 0; double st_busy_ms = 0;
@@ -272,6 +281,7 @@ static void decoder_stop(q3_batcher* b) {
                         "queue depth at enqueue: max %d\n", d.st_jobs, d.st_pushes, d.st_frames, d.st_busy_ms, d.st_busy_ms / d.st_jobs, d.st_depth_max);
     if (d.stream) (void)hipStreamSynchronize(d.stream);
     if (d.cs) { q3_codec_stream_free(d.cs); d.cs = nullptr; }
+    if (d.ps) { q3_pcm_stage_free(d.ps); d.ps = nullptr; }
     if (d.stream) { (void)hipStreamDestroy(d.stream); d.stream = nullptr; }
     d.ws.release();
 }
@@ -293,6 +303,9 @@ static q3_status decoder_run(q3_batcher* b, BatTicket& t) {
 // own frames; after a failed push put the row back to frame 0, everything from the ticket's first (reference) frame, with `skip`
 // set to what was already delivered — no sample is lost or repeated. A joint push that is refused or fails is repeated row by
 // row, and the tickets whose own push fails are FAILED with its message.
+// A ticket with an output of its own (o_conv): its first part sets — and so restarts — the slot's row of the worker's output stage,
+// its pushes carry that row, its last part flushes it. The stage follows the samples that were DELIVERED: the put-back above resets
+// the codec stream's row, never the stage's, so the ticket's listener hears neither a gap nor a repeat.
 static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
     BatDecoder& d = *b->dec;
     const auto t_job = std::chrono::steady_clock::now();
@@ -306,14 +319,16 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
         std::lock_guard<std::mutex> g(d.mu);
         if (!t.s_failed) { t.s_failed = true; t.s_st = st; t.s_err = msg; }
     };
-    struct Out { StreamPart* p; int n_new; std::vector<float> pcm; };
+    struct Out { StreamPart* p; int n_new; std::vector<float> pcm; std::vector<char> out; size_t n_out = 0; };
+    auto flush_only = [&](const Out& o) { return o.n_new <= 0 && o.p->t->o_conv && o.p->last; };
     auto is_failed = [&](BatTicket& t) { std::lock_guard<std::mutex> g(d.mu); return t.s_failed; };
     // the samples of a served part land; a failed ticket's row and a finished one's give their blocks back
     auto land = [&](Out& o) {
         BatTicket& t = *o.p->t;
         t.s_deliv += o.n_new;
         std::lock_guard<std::mutex> g(d.mu);
-        t.spcm.insert(t.spcm.end(), o.pcm.begin(), o.pcm.end());
+        if (t.o_conv) t.sout.insert(t.sout.end(), o.out.begin(), o.out.begin() + (long)(o.n_out * t.o_bytes()));
+        else t.spcm.insert(t.spcm.end(), o.pcm.begin(), o.pcm.end());
     };
     size_t i = 0;
     while (i < parts.size()) {
@@ -324,6 +339,12 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
             seen[(size_t)p.row] = 1;
             if (st0 != Q3_OK) { fail(t, st0, q3_last_error()); continue; }
             if (p.first) { codec_stream_reset(d.cs, p.row); t.s_all = t.req.ref_codes; t.s_deliv = 0; }
+            if (p.first && t.o_conv) {
+                q3_status so = Q3_OK;
+                if (!d.ps) so = q3_pcm_stage_create(m->device, b->slots, (size_t)std::min(b->frame_budget + b->prompt_budget, 100000) * spf, &d.ps);
+                if (so == Q3_OK) so = q3_pcm_stage_set(d.ps, p.row, t.o_rate, t.o_fmt);
+                if (so != Q3_OK) fail(t, so, q3_last_error());
+            }
             if (is_failed(t)) continue;
             t.s_all.insert(t.s_all.end(), p.frames.begin(), p.frames.end());
             grp.push_back({&p, (int)(p.frames.size() / 16), {}});
@@ -331,11 +352,18 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
         auto push_of = [&](Out& o) {
             BatTicket& t = *o.p->t;
             const int n_ref = (int)(t.req.ref_codes.size() / 16), sp = codec_stream_pos(d.cs, o.p->row);
-            o.pcm.resize((size_t)o.n_new * spf);
-            return CsPush{o.p->row, n_ref + t.s_deliv + o.n_new - sp, n_ref + t.s_deliv - sp, t.s_all.data() + (size_t)sp * 16, nullptr, o.pcm.data()};
+            if (!t.o_conv) {
+                o.pcm.resize((size_t)o.n_new * spf);
+                return CsPush{o.p->row, n_ref + t.s_deliv + o.n_new - sp, n_ref + t.s_deliv - sp, t.s_all.data() + (size_t)sp * 16, nullptr, o.pcm.data()};
+            }
+            o.out.resize(pcm_stage_count(d.ps, o.p->row, (size_t)o.n_new * spf, o.p->last) * t.o_bytes());
+            CsPush p{o.p->row, 0, 0, nullptr, nullptr, nullptr};      // (no new frames: only the stage row's tail)
+            if (o.n_new > 0) { p.n = n_ref + t.s_deliv + o.n_new - sp; p.skip = n_ref + t.s_deliv - sp; p.host = t.s_all.data() + (size_t)sp * 16; }
+            p.ps = d.ps; p.ps_row = o.p->row; p.last = o.p->last; p.out_host = o.out.data(); p.n_out = &o.n_out;
+            return p;
         };
         std::vector<CsPush> P;
-        for (Out& o : grp) if (o.n_new > 0) P.push_back(push_of(o));
+        for (Out& o : grp) if (o.n_new > 0 || flush_only(o)) P.push_back(push_of(o));
         bool joint_ok = true;
         if (!P.empty()) { joint_ok = codec_stream_push(d.cs, P) == Q3_OK; d.st_pushes++; for (const CsPush& p : P) d.st_frames += p.n; }
         // A refused joint push (Q3_OOM under max_blocks) is repeated row by row, the rows that need no new block first and then the
@@ -353,7 +381,7 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
             });
         for (Out& o : grp) {
             BatTicket& t = *o.p->t;
-            if (!joint_ok && o.n_new > 0) {            // alone: this row's own push decides about this ticket
+            if (!joint_ok && (o.n_new > 0 || flush_only(o))) {            // alone: this row's own push decides about this ticket
                 const q3_status st = codec_stream_push(d.cs, {push_of(o)});
                 if (st != Q3_OK) { fail(t, st, q3_last_error()); codec_stream_reset(d.cs, o.p->row); continue; }
             }
@@ -493,7 +521,7 @@ static q3_status batcher_submit(q3_batcher* b, const q3_request* req, int want_p
         return set_err(Q3_UNSUPPORTED, "q3_batcher_submit: max_length %d outside 1..%d (the batcher's frame budget)", req->opts.max_length, b->frame_budget);
     if (req->n_text < 0 || req->n_instruct < 0 || req->n_ref < 0 || req->n_ref_text < 0) return set_err(Q3_INVALID_ARG, "q3_batcher_submit: negative length");
     std::unique_ptr<BatTicket> t(new BatTicket());
-    t->req.own(*req, b->m->cfg.hidden); t->want_pcm = want_pcm != 0; t->streamed = streamed;
+    t->req.own(*req, b->m->cfg.hidden); t->want_pcm = want_pcm != 0; t->streamed = streamed; t->born = b->steps;
     if (streamed) b->n_streamed++;
     const int64_t id = b->next_id++;
     b->t[id] = std::move(t);
@@ -649,6 +677,7 @@ static q3_status bat_collect(q3_batcher* b, int row) {
 extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph, int* n_running, int* n_queued, int* n_finished) {
     if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_step: null batcher");
     if (n_frames < 1) return set_err(Q3_INVALID_ARG, "q3_batcher_step: n_frames must be >= 1");
+    b->steps++;
     int finished = 0;
     // Open the session on `slots` idle rows: copies of a one-token CustomVoice prompt with a one-frame limit (ten prefill
     // positions per row — opening on the first request itself would prefill, and size every row's KV extent for, `slots`
@@ -941,7 +970,7 @@ extern "C" q3_status q3_batcher_poll(q3_batcher* b, int64_t ticket, int* state, 
     }
     if (n_frames) *n_frames = nf;
     if (n_samples) *n_samples = t.pcm.size();         // (of a ticket still being vocoded: the samples it WILL hold — the size q3_batcher_fetch wants)
-    if (n_samples && t.streamed) { std::lock_guard<std::mutex> g(b->dec->mu); *n_samples = t.spcm.size(); }      // streamed: the samples that have landed
+    if (n_samples && t.streamed) { std::lock_guard<std::mutex> g(b->dec->mu); *n_samples = t.o_conv ? t.sout.size() / t.o_bytes() : t.spcm.size(); }      // streamed: the samples that have landed
     return Q3_OK;
 }
 
@@ -985,6 +1014,9 @@ extern "C" q3_status q3_batcher_read(q3_batcher* b, int64_t ticket, float* pcm_h
     if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_read: unknown ticket %lld", (long long)ticket);
     BatTicket& t = *it->second;
     if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_read: ticket %lld was not submitted as streamed (its samples come with q3_batcher_fetch)", (long long)ticket);
+    if (t.o_conv)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_read: ticket %lld has an output of its own (%u Hz, %s): its samples come with q3_batcher_read_out", (long long)ticket,
+                       t.o_rate, t.o_fmt == Q3_PCM_S16 ? "s16" : "f32");
     *n_samples = 0; *done = 0;
     stream_settle(b, t, false);
     if (t.state == Q3_TICKET_FAILED) return set_err(t.st, "%s", t.err.c_str());
@@ -995,6 +1027,42 @@ extern "C" q3_status q3_batcher_read(q3_batcher* b, int64_t ticket, float* pcm_h
     t.s_read += n;
     *n_samples = n;
     *done = ((t.state == Q3_TICKET_DONE || t.state == Q3_TICKET_CANCELLED) && t.s_read == t.spcm.size()) ? 1 : 0;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_ticket_output(q3_batcher* b, int64_t ticket, uint32_t sample_rate, int format) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: ticket %lld was not submitted as streamed", (long long)ticket);
+    if (format != Q3_PCM_F32 && format != Q3_PCM_S16) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: format must be Q3_PCM_F32 (0) or Q3_PCM_S16 (1)");
+    Q3C(q3_pcm_stage_taps(sample_rate, nullptr, 0, nullptr, nullptr));
+    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: ticket %lld has been through a step: its output is set between its submission and the next q3_batcher_step", (long long)ticket);
+    t.o_rate = sample_rate; t.o_fmt = format; t.o_conv = sample_rate != 24000 || format != Q3_PCM_F32;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_read_out(q3_batcher* b, int64_t ticket, void* out_host, size_t cap_samples, size_t* n_samples, int* done) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_read_out: null batcher");
+    if (!n_samples || !done || (cap_samples > 0 && !out_host)) return set_err(Q3_INVALID_ARG, "q3_batcher_read_out: null argument");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_read_out: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_read_out: ticket %lld was not submitted as streamed (its samples come with q3_batcher_fetch)", (long long)ticket);
+    if (!t.o_conv) return q3_batcher_read(b, ticket, (float*)out_host, cap_samples, n_samples, done);      // 24 kHz f32: the samples as they are
+    *n_samples = 0; *done = 0;
+    stream_settle(b, t, false);
+    if (t.state == Q3_TICKET_FAILED) return set_err(t.st, "%s", t.err.c_str());
+    std::lock_guard<std::mutex> g(b->dec->mu);
+    const size_t sb = t.o_bytes();
+    size_t n = (t.sout.size() - t.o_read) / sb;
+    if (n > cap_samples) n = cap_samples;
+    if (n > 0) memcpy(out_host, t.sout.data() + t.o_read, n * sb);
+    t.o_read += n * sb;
+    *n_samples = n;
+    *done = ((t.state == Q3_TICKET_DONE || t.state == Q3_TICKET_CANCELLED) && t.o_read == t.sout.size()) ? 1 : 0;
     return Q3_OK;
 }
 

@@ -145,12 +145,29 @@ struct DescBlock {
 // Every row at most once, 0 <= row < R, pos + n <= cap, codes on the host (all rows) or on the device (all rows): checked by the
 // callers' entry points, which refuse before anything changes. pcm_host[i] receives the (n - skip) * spf samples of the row's last
 // n - skip frames.
+// Rows that name an output stage (CsPush::ps, one stage per push): their samples go through it on the stream's stream, behind the
+// copy that gathers them and in front of the copy to the host, which then carries the converted bytes. The stage's descriptors
+// ride in this push's descriptor block. The stage's rows move on only when the push has succeeded; nothing here restarts them.
 q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all) {
     q3_model* m = cs->m;
     const q3_config& c = m->cfg;
     std::vector<CsPush> P;
     for (const CsPush& p : all) if (p.n > 0) P.push_back(p);
-    if (P.empty()) return Q3_OK;
+    q3_pcm_stage* ps = nullptr;
+    std::vector<const CsPush*> flush;                       // no frames, but the row's stage row ends: only its tail comes out
+    for (const CsPush& p : all) {
+        if (p.ps) ps = p.ps;
+        if (p.n_out) *p.n_out = 0;
+        if (p.n <= 0 && p.ps && p.last) flush.push_back(&p);
+    }
+    if (P.empty()) {
+        if (flush.empty()) return Q3_OK;
+        std::vector<PsSeg> segs; std::vector<void*> outs; std::vector<size_t> cnt(flush.size(), 0);
+        for (const CsPush* f : flush) { segs.push_back({f->ps_row, nullptr, 0, 1}); outs.push_back(f->out_host); }
+        Q3C(pcm_stage_push_dev(ps, segs, cs->st, outs.data(), cnt.data()));
+        for (size_t k = 0; k < flush.size(); ++k) if (flush[k]->n_out) *flush[k]->n_out = cnt[k];
+        return Q3_OK;
+    }
     HIPC(hipSetDevice(m->device));
     hipStream_t st = cs->st;
     const int Q = c.dec_q_dim, LAT = c.dec_latent, QD = c.dec_heads * c.dec_head_dim, cap = cs->cap, spf = samples_per_frame(c);
@@ -249,6 +266,14 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
         HIPC(hipHostMalloc((void**)&cs->stage_host, (size_t)W * spf * 4, hipHostMallocDefault));
         cs->stage_cap = (size_t)W * spf;
     }
+    // the output stage's part of the plan: the delivered samples of its rows, where launch_copy_segs puts them
+    std::vector<PsSeg> psegs; std::vector<const CsPush*> pseg_of; PsPlan plan;
+    if (ps) {
+        for (int i = 0; i < nP; ++i)
+            if (P[i].ps) { psegs.push_back({P[i].ps_row, cs->stage + (size_t)out0[i] * spf, (size_t)(P[i].n - P[i].skip) * spf, P[i].last}); pseg_of.push_back(&P[i]); }
+        for (const CsPush* f : flush) { psegs.push_back({f->ps_row, nullptr, 0, 1}); pseg_of.push_back(f); }
+        Q3C(pcm_stage_plan(ps, psegs, plan));
+    }
     float *A = ws.bufA, *B = ws.bufB, *C = ws.bufC, *F = ws.bufF;
     float* knew = A + (size_t)QD * N;                       // k | v of the new columns, [2*QD][N] (codec_front_transformer)
     // descriptors
@@ -304,7 +329,7 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
     DescBlock db;
     const size_t o_pos = db.add(pos), o_arows = db.add(arows), o_xin = db.add(xin), o_hist = db.add(hist), o_compact = db.add(compact),
                  o_kvsc = db.add(kvsc), o_latsc = db.add(latsc), o_latg = db.add(latg), o_segs = db.add(segs), o_fsrc = db.add(fsrc),
-                 o_brows = db.add(brows), o_tabs = db.add(tabs), o_solog = db.add(solog);
+                 o_brows = db.add(brows), o_tabs = db.add(tabs), o_solog = db.add(solog), o_ps = db.add(plan.desc);
     if (db.host.size() > cs->desc_cap) {
         HIPC(hipStreamSynchronize(st));
         dev_free(cs->desc); cs->desc = nullptr; cs->desc_cap = 0;
@@ -361,10 +386,20 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
         Q3C(codec_stack_dev(m, ws, F, e, st, nullptr, scope));
         HIPC(launch_copy_segs(ws.pcm, cs->stage, dsegs + conc.size() + k, 1, (size_t)(P[i].n - P[i].skip) * spf, st));
     }
-    if (W > 0) HIPC(hipMemcpyAsync(cs->stage_host, cs->stage, (size_t)W * spf * 4, hipMemcpyDeviceToHost, st));
+    bool raw = false;                                       // rows that take their 24 kHz f32 as it is (every row, without a stage)
+    for (int i = 0; i < nP; ++i) raw = raw || !P[i].ps;
+    if (ps) HIPC(pcm_stage_launch((const PsDesc*)D(o_ps), plan, st));
+    if (W > 0 && raw) HIPC(hipMemcpyAsync(cs->stage_host, cs->stage, (size_t)W * spf * 4, hipMemcpyDeviceToHost, st));
+    if (plan.bytes > 0) HIPC(hipMemcpyAsync(pcm_stage_out_host(ps), pcm_stage_out_dev(ps), plan.bytes, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
+    for (size_t k = 0; k < psegs.size(); ++k) {
+        const CsPush& p = *pseg_of[k];
+        if (p.out_host && plan.count[k] > 0) memcpy(p.out_host, pcm_stage_out_host(ps) + plan.off[k], plan.count[k] * pcm_stage_sample_bytes(ps, p.ps_row));
+        if (p.n_out) *p.n_out = plan.count[k];
+    }
+    if (ps) pcm_stage_commit(ps, psegs, plan);
     for (int i = 0; i < nP; ++i) {
-        if (P[i].pcm_host) memcpy(P[i].pcm_host, cs->stage_host + (size_t)out0[i] * spf, (size_t)(P[i].n - P[i].skip) * spf * 4);
+        if (P[i].pcm_host && !P[i].ps) memcpy(P[i].pcm_host, cs->stage_host + (size_t)out0[i] * spf, (size_t)(P[i].n - P[i].skip) * spf * 4);
         cs->rows[P[i].row].pos += P[i].n;
     }
     failed.armed = false; untake.armed = false;
@@ -396,6 +431,42 @@ extern "C" q3_status q3_codec_stream_push(q3_codec_stream* cs, int n_rows, const
                 if (frames_host[i][(size_t)f * 16 + g] >= (uint32_t)cs->m->cfg.dec_cb_size)
                     return set_err(Q3_INVALID_ARG, "code %u out of range for codebook %d (row %d, frame %d)", frames_host[i][(size_t)f * 16 + g], g, r, f);
         P.push_back({r, n, 0, frames_host[i], nullptr, pcm_host[i]});
+    }
+    return codec_stream_push(cs, P);
+}
+
+extern "C" q3_status q3_codec_stream_push_out(q3_codec_stream* cs, int n_rows, const int* rows, const uint32_t* const* frames_host, const int* n_frames,
+                                              q3_pcm_stage* ps, const int* ps_rows, const int* last,
+                                              void* const* out_host, const size_t* cap_samples, size_t* n_samples) {
+    if (!cs) return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: null stream");
+    if (!ps) return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: null stage");
+    if (n_rows < 0 || (n_rows > 0 && (!rows || !frames_host || !n_frames || !ps_rows || !out_host || !cap_samples || !n_samples)))
+        return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: null argument");
+    Q3C(pcm_stage_check_rows(ps, "q3_codec_stream_push_out", n_rows, ps_rows));
+    const int spf = samples_per_frame(cs->m->cfg);
+    std::vector<char> seen(cs->R, 0);
+    std::vector<CsPush> P;
+    for (int i = 0; i < n_rows; ++i) {
+        const int r = rows[i], n = n_frames[i], lst = last ? last[i] : 0;
+        if (r < 0 || r >= cs->R) return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: row %d out of range (%d rows)", r, cs->R);
+        if (seen[r]) return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: row %d listed twice", r);
+        seen[r] = 1;
+        n_samples[i] = 0;
+        if (n < 0) return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: negative frame count for row %d", r);
+        if (n == 0 && !lst) continue;
+        if (cs->rows[r].pos + n > cs->cap)
+            return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: row %d would reach %d frames, the stream holds %d", r, cs->rows[r].pos + n, cs->cap);
+        if (n > 0 && !frames_host[i]) return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: null frames pointer for row %d", r);
+        const size_t cnt = pcm_stage_count(ps, ps_rows[i], (size_t)n * spf, lst);
+        if (cap_samples[i] < cnt) return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: output buffer of row %d too small (%zu < %zu samples)", r, cap_samples[i], cnt);
+        if (cnt > 0 && !out_host[i]) return set_err(Q3_INVALID_ARG, "q3_codec_stream_push_out: null output pointer for row %d", r);
+        for (int f = 0; f < n; ++f)
+            for (int g = 1; g < 16; ++g)
+                if (frames_host[i][(size_t)f * 16 + g] >= (uint32_t)cs->m->cfg.dec_cb_size)
+                    return set_err(Q3_INVALID_ARG, "code %u out of range for codebook %d (row %d, frame %d)", frames_host[i][(size_t)f * 16 + g], g, r, f);
+        CsPush p{r, n, 0, frames_host[i], nullptr, nullptr};
+        p.ps = ps; p.ps_row = ps_rows[i]; p.last = lst; p.out_host = out_host[i]; p.n_out = &n_samples[i];
+        P.push_back(p);
     }
     return codec_stream_push(cs, P);
 }

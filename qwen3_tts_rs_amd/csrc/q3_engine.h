@@ -4,6 +4,7 @@
 //   q3_prefix_cache.hip the prefix cache: prefilled instruct pages shared across requests (q3_prefix_cache.h)
 //   q3_codec_run.hip device-memory cache, the vocoder pipeline (codec_decode_dev) and q3_decode_codes
 //   q3_codec_stream.hip the codec stream: the vocoder with per-row state, many rows per pass
+//   q3_pcm_stage.hip the output stage: per-row resampling to a requested rate and f32 / PCM16 conversion
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
 //                    streaming chunks, q3_session_run / decode / get
 //   q3_batcher.hip   continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
@@ -445,6 +446,9 @@ struct q3_session {
     bool precapture = false;       // q3_session_prefill captures the frame while the prompt's kernels run (set by the callers that will replay it)
     CodecWS cws;
     q3_codec_stream* cstream = nullptr;   // q3_session_next_chunks, stream mode 1: per-row vocoder state (created on the first call)
+    // q3_session_next_chunks_out: the session's output (q3_session_set_output) and its stage, one row per session row (created on
+    // the first such call: out_started, after which the setting is fixed)
+    q3_pcm_stage* ostage = nullptr; uint32_t out_rate = 24000; int out_fmt = Q3_PCM_F32; bool out_started = false;
     // overlapped segment decode (q3_session_run): vocoder segments run on their own stream while the frame loop continues
     hipStream_t dec_stream = nullptr; hipEvent_t dec_ev = nullptr;
     std::vector<CodecWS> par_ws; std::vector<hipStream_t> par_streams;     // q3_session_run: utterances vocoded side by side
@@ -498,7 +502,13 @@ Q3_HIDDEN q3_status codec_front_transformer(const q3_model* m, CodecWS& ws, int 
 Q3_HIDDEN q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, int L, hipStream_t st, float** taps, const CodecScope& scope);
 // q3_codec_stream.hip
 // n new frames of one row, codes on the host OR the device; the first `skip` of them only catch the row's state up (no samples)
-struct CsPush { int row; int n; int skip; const uint32_t* host; const uint32_t* dev; float* pcm_host; };
+// With an output stage (q3_pcm_stage.hip): the samples of the n - skip delivered frames go through row ps_row of `ps` on the
+// stream's stream before they are copied to the host — out_host receives *n_out samples in that row's rate and format, the tail
+// included when `last` is set — and pcm_host is not used. Every row of a push names the same stage. Without one: today's path.
+struct CsPush {
+    int row; int n; int skip; const uint32_t* host; const uint32_t* dev; float* pcm_host;
+    q3_pcm_stage* ps = nullptr; int ps_row = -1; int last = 0; void* out_host = nullptr; size_t* n_out = nullptr;
+};
 // block_frames > 0: block-allocated state (a multiple of 32), at most max_blocks blocks (0 = no limit)
 Q3_HIDDEN q3_status codec_stream_create(q3_model* m, int rows, int max_frames, hipStream_t st, q3_codec_stream** out, int block_frames = 0,
                                         int max_blocks = 0);
@@ -506,6 +516,28 @@ Q3_HIDDEN q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsP
 Q3_HIDDEN int codec_stream_pos(const q3_codec_stream* cs, int row);
 Q3_HIDDEN void codec_stream_blocks(const q3_codec_stream* cs, int row, int upto, int* held, int* need);
 Q3_HIDDEN void codec_stream_reset(q3_codec_stream* cs, int row);
+// q3_pcm_stage.hip
+// n samples of 24 kHz f32 on the device for stage row `row`; last: the row's input ends here (its tail is flushed)
+struct PsSeg { int row; const float* dev; size_t n; int last; };
+// one row of a pass of k_pcm_stage (device-visible, 8-byte aligned)
+struct PsDesc {
+    const float* src; const float* tail_in; float* tail_out; const float* taps; void* out;
+    long long base, i0;                     // input samples the row had consumed, first output index of this pass
+    int n_new, n_out, L, M, fmt, pad;
+};
+// a checked push: descriptors of the rows that run, per segment the byte offset into the stage's staging buffer and the samples
+struct PsPlan { std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t bytes = 0; int max_tiles = 1; };
+Q3_HIDDEN int pcm_stage_rows(const q3_pcm_stage* ps);
+Q3_HIDDEN size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row);
+Q3_HIDDEN void pcm_stage_reset(q3_pcm_stage* ps, int row);
+Q3_HIDDEN q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_rows, const int* rows);
+Q3_HIDDEN size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last);
+Q3_HIDDEN q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan);
+Q3_HIDDEN hipError_t pcm_stage_launch(const PsDesc* desc_dev, const PsPlan& plan, hipStream_t st);
+Q3_HIDDEN void pcm_stage_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const PsPlan& plan);
+Q3_HIDDEN const char* pcm_stage_out_dev(const q3_pcm_stage* ps);
+Q3_HIDDEN char* pcm_stage_out_host(const q3_pcm_stage* ps);
+Q3_HIDDEN q3_status pcm_stage_push_dev(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, hipStream_t st, void* const* out_host, size_t* n_samples);
 // q3_session.hip
 Q3_HIDDEN hipError_t sync_frames(q3_session* s);
 Q3_HIDDEN q3_status kv_reserve_row(q3_session* s, int b, int n_pos);

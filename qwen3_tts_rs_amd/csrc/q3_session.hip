@@ -687,6 +687,7 @@ q3_session::~q3_session() {
     if (graph) (void)hipGraphDestroy(graph);
     for (auto& ev : prof_pool) (void)hipEventDestroy(ev);
     for (auto st : par_streams) (void)hipStreamDestroy(st);
+    if (ostage) q3_pcm_stage_free(ostage);
     if (cstream) q3_codec_stream_free(cstream);          // (drops its own reference to the model: ours is still held)
     cws.release(); seg_ws.release();
     for (auto& w : par_ws) w.release();
@@ -1758,10 +1759,39 @@ static q3_status chunk_decode_row(q3_session* s, int b, int avail, float* pcm_ho
 // the rest then: the boundaries are the per-row calls'). Then one vocoder pass: in stream mode 1 every row that is not ICL
 // goes through the session's codec stream (q3_codec_stream.hip) in ONE push — a chunk costs its own frames, not the utterance
 // so far, and the launches do not multiply with the rows; ICL rows and stream mode 0 keep the per-row context-free decode.
+// `out`: q3_session_next_chunks_out — the same rounds, every row's samples through its row of the session's output stage
+// (out_host / cap in samples of the session's output); a row's stage row is flushed in the call that reports it done.
+static q3_status next_chunks(q3_session* s, float* const* pcm_host, const size_t* cap, size_t* n_samples, int* done, bool out, void* const* out_host);
 extern "C" q3_status q3_session_next_chunks(q3_session* s, float* const* pcm_host, const size_t* cap, size_t* n_samples, int* done) {
     if (!s) return set_err(Q3_INVALID_ARG, "null session");
     if (!n_samples || !done) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks: n_samples and done are required");
     if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks: the model has no device");
+    return next_chunks(s, pcm_host, cap, n_samples, done, false, nullptr);
+}
+extern "C" q3_status q3_session_set_output(q3_session* s, uint32_t sample_rate, int format) {
+    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_output: null session");
+    if (format != Q3_PCM_F32 && format != Q3_PCM_S16) return set_err(Q3_INVALID_ARG, "q3_session_set_output: format must be Q3_PCM_F32 (0) or Q3_PCM_S16 (1)");
+    Q3C(q3_pcm_stage_taps(sample_rate, nullptr, 0, nullptr, nullptr));      // the rate, before anything else
+    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_output: the model has no device");
+    bool started = s->out_started || s->stream_pos > 0;
+    for (const SeqInfo& q : s->seq) started = started || q.stream_pos > 0;
+    if (started) return set_err(Q3_INVALID_ARG, "q3_session_set_output: the session has streamed its first chunk: the output is set before it");
+    s->out_rate = sample_rate; s->out_fmt = format;
+    return Q3_OK;
+}
+extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_host, const size_t* cap_samples, size_t* n_samples, int* done) {
+    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null session");
+    if (!n_samples || !done || !out_host || !cap_samples) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null argument");
+    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: the model has no device");
+    if (!s->ostage) {
+        const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
+        Q3C(q3_pcm_stage_create(s->m->device, s->B, (size_t)chunk * samples_per_frame(s->m->cfg), &s->ostage));
+        for (int b = 0; b < s->B; ++b) Q3C(q3_pcm_stage_set(s->ostage, b, s->out_rate, s->out_fmt));
+    }
+    s->out_started = true;
+    return next_chunks(s, nullptr, cap_samples, n_samples, done, true, out_host);
+}
+static q3_status next_chunks(q3_session* s, float* const* pcm_host, const size_t* cap, size_t* n_samples, int* done, bool out, void* const* out_host) {
     HIPC(hipSetDevice(s->m->device));
     if (!s->prefilled) Q3C(q3_session_prefill(s));
     Q3C(refresh_codes(s));
@@ -1776,21 +1806,50 @@ extern "C" q3_status q3_session_next_chunks(q3_session* s, float* const* pcm_hos
     }
     // what every row gets; refused as a whole before any row moves
     std::vector<int> avail((size_t)s->B, 0);
-    std::vector<char> held((size_t)s->B, 0);
+    std::vector<char> held((size_t)s->B, 0), ends((size_t)s->B, 0);
     for (int b = 0; b < s->B; ++b) {
         const SeqInfo& q = s->seq[b];
         int a = std::min(q.n_frames - q.stream_pos, chunk);
         held[(size_t)b] = q.opened && !q.done && a < chunk;          // an opened row whose text does not reach a whole chunk yet: nothing now
         if (a < 0 || held[(size_t)b]) a = 0;
         avail[(size_t)b] = a;
-        if (a > 0 && pcm_host && pcm_host[b] && (!cap || cap[b] < (size_t)a * spf))
+        ends[(size_t)b] = held[(size_t)b] ? 0 : (a <= 0 || (q.done && q.stream_pos + a >= q.n_frames)) ? 1 : 0;      // what done[b] will say
+        if (out) {
+            const size_t cnt = pcm_stage_count(s->ostage, b, (size_t)a * spf, ends[(size_t)b]);
+            if (cnt > 0 && (!out_host[b] || cap[b] < cnt))
+                return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: output buffer of row %d too small (%zu samples needed)", b, cnt);
+        } else if (a > 0 && pcm_host && pcm_host[b] && (!cap || cap[b] < (size_t)a * spf))
             return set_err(Q3_INVALID_ARG, "q3_session_next_chunks: pcm buffer of row %d too small", b);
     }
     std::vector<CsPush> pushes;
+    std::vector<float> tmp;
     for (int b = 0; b < s->B; ++b) {
         SeqInfo& q = s->seq[b];
         const int a = avail[(size_t)b];
-        n_samples[b] = (size_t)a * spf;
+        n_samples[b] = out ? 0 : (size_t)a * spf;
+        if (out) {
+            const int last = ends[(size_t)b];
+            if (a <= 0 && !last) continue;
+            if (s->stream_mode == 1 && !q.icl) {
+                if (!s->cstream) Q3C(codec_stream_create(s->m, s->B, s->max_frames, s->stream, &s->cstream));
+                int n = 0, skip = 0, sp = 0;
+                if (a > 0) {
+                    if (codec_stream_pos(s->cstream, b) > q.stream_pos) codec_stream_reset(s->cstream, b);
+                    sp = codec_stream_pos(s->cstream, b);
+                    n = q.stream_pos + a - sp; skip = q.stream_pos - sp;
+                }
+                CsPush p{b, n, skip, nullptr, s->codes + ((size_t)b * s->max_frames + sp) * 16, nullptr};
+                p.ps = s->ostage; p.ps_row = b; p.last = last; p.out_host = out_host[b]; p.n_out = &n_samples[b];
+                pushes.push_back(p);
+            } else {
+                // ICL rows and stream mode 0 keep the per-row context-free decode; its samples take the stage's host entry
+                tmp.resize((size_t)a * spf);
+                if (a > 0) Q3C(chunk_decode_row(s, b, a, tmp.data(), tmp.size(), nullptr));
+                const float* in = tmp.data(); const size_t n_in = tmp.size();
+                Q3C(q3_pcm_stage_push(s->ostage, 1, &b, &in, &n_in, &last, &out_host[b], &cap[b], &n_samples[b]));
+            }
+            continue;
+        }
         if (a <= 0) continue;
         if (s->stream_mode == 1 && !q.icl) {
             if (!s->cstream) Q3C(codec_stream_create(s->m, s->B, s->max_frames, s->stream, &s->cstream));
