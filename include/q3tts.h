@@ -269,6 +269,32 @@ q3_status q3_session_next_chunks(q3_session* s, float* const* pcm_host, const si
  * lib.rs:1154-1160, is resolved into its own row). Each row of a session stops at its own opts.max_length;
  * q3_session_generate returns early once every row is done. Other rows are bit-for-bit unaffected. */
 q3_status q3_session_replace(q3_session* s, int b, const q3_request* req);
+/* Park and resume: a RUNNING row's state as an object (no reference counterpart: the reference runs one utterance per call to
+ * its end). q3_session_park_row takes row b out of a prefilled session between two frames: the row's K/V pages (relinked, never
+ * copied), its slice of every device array a frame reads before it writes (last hidden state, current token, penalty mask,
+ * counters, pre-drawn PCG stream, frame limit, text state and trailing text rows, sampler record), its latest logits, the codes it
+ * has committed and its host bookkeeping move into a record. The row is left idle — frozen, holding one zero-filled page of its
+ * own — and may take a q3_session_replace or a record. The row may be live, held by open text or already ended; an idle row is
+ * Q3_INVALID_ARG; a Q3_KV_CONTIGUOUS=1 session, a debug / profiling session and a row that has delivered chunks through
+ * q3_session_next_chunk* are Q3_UNSUPPORTED; Q3_KV_OVERFLOW when the pool cannot give the vacated row its page, Q3_OOM when the
+ * device refuses the record's block. Nothing changes when the call is REFUSED with one of these; a device error in the middle
+ * (Q3_HIP_ERROR) leaves the session as unusable as any other failed launch does. The record's device state lives in one block
+ * (a power of two from 64 KB on) from the session's own shelf of such blocks: a block is asked of the device only while the
+ * session has never had as many records of that size parked at once, and goes back to the shelf at the resume or free.
+ * q3_session_resume_row puts a record into row b of THE SAME session (another session's record: Q3_INVALID_ARG), any row that is
+ * idle or has ended (a live row: Q3_INVALID_ARG). The row's own pages go back to the pool, the record's are linked, its text
+ * moves to row b's slot. It consumes the record on success only; on failure the record is intact and the session unchanged.
+ * For any schedule of parks and resumes, into any rows, a row's codes and PCM are those of the same session run without them,
+ * and no other row's bits change. A row that sampled its EOS before it was parked resumes as ended: q3_session_frames reports
+ * the same frame count and done = 1 (q3_parked_info: done), and the record's codes are the utterance's.
+ * A record holds a reference on the model and may outlive its session; its pages stay charged to q3_model_kv_pool_limit until
+ * q3_parked_free (which gives them back) or the resume. q3_parked_info: frames committed, the row's frame limit, whether it
+ * had ended, pages held, bytes of device state (any pointer may be NULL). */
+typedef struct q3_parked q3_parked;
+q3_status q3_session_park_row(q3_session* s, int b, q3_parked** out);
+q3_status q3_session_resume_row(q3_session* s, int b, q3_parked* p);
+void      q3_parked_free(q3_parked* p);
+q3_status q3_parked_info(const q3_parked* p, int* frames_committed, int* limit, int* done, int* kv_pages, size_t* state_bytes);
 /* ---------------- continuous batcher: a queue of requests through the rows of one session ----------------
  * The serving loop around q3_session_replace, native: requests of any prompt kind, length and options are queued; a step
  * fills free rows from the queue, runs up to n_frames frames of the shared frame graph and collects the rows that ended.
@@ -344,6 +370,40 @@ q3_status q3_batcher_submit_open(q3_batcher* b, const q3_request* req, int want,
 q3_status q3_batcher_append_text(q3_batcher* b, int64_t ticket, const uint32_t* ids, int n, int last);
 q3_status q3_batcher_text_state(q3_batcher* b, int64_t ticket, int* n_text, int* frames_committed, int* frames_runnable, int* closed);
 q3_status q3_batcher_cancel(q3_batcher* b, int64_t ticket);
+/* Parked tickets (opt-in; no reference counterpart): more requests in flight than rows. A running ticket's row goes into a record
+ * (q3_session_park_row) and the row is free for another ticket; the parked ticket re-enters ANY free row later by
+ * q3_session_resume_row and goes on where it stopped. For any schedule a ticket's codes, PCM and streamed bytes are those of the
+ * same request run to completion in one row.
+ * q3_batcher_set_parking, before the first q3_batcher_step (Q3_INVALID_ARG after): max_parked = 0 (the default) is the batcher
+ * without parking — no entry point changes its behaviour, bits or timing. quantum_frames = 0: only explicit parks.
+ * quantum_frames > 0, the TIME SLICE: at the start of every piece of a step, while something waits, no row is free and fewer than
+ * max_parked tickets are parked, the running ticket that has committed the most frames since it entered its row is parked if
+ * that is at least quantum_frames (ties: the lowest row; a row HELD by open text counts as having used its quantum and goes
+ * first), and the head of the waiting list takes its row; a ticket parked by one such round is not resumed by the same round.
+ * Pieces are also cut where the next quantum ends while something waits. The policy reads no clock: it is a function of
+ * submissions, steps and frames. ONE waiting list holds fresh tickets and parked tickets that want a row: with fresh_first = 0
+ * in order of arrival / park time; with fresh_first != 0 a fresh ticket stands ahead of the parked ones, behind earlier fresh
+ * ones. A ticket the scheduler parked waits at once; a parked OPEN ticket waits only while its text allows another frame or is
+ * closed (text appended meanwhile is recorded and published by the first flush after it re-enters).
+ * q3_batcher_park (between steps, like q3_batcher_cancel): a ticket RUNNING in a row reads Q3_TICKET_PARKED and stays parked
+ * until q3_batcher_unpark, which puts it on the waiting list. A ticket that has ended or is with the decode worker: Q3_OK,
+ * nothing happens; a queued one: Q3_INVALID_ARG; with max_parked tickets parked already: Q3_UNSUPPORTED, nothing changes.
+ * q3_batcher_poll reports a parked ticket's committed frames; q3_batcher_cancel gives its codes (their decode with want_pcm, the
+ * last part of a streamed ticket) out of the record and frees it; q3_batcher_free frees what is still parked. A streamed
+ * ticket's row of the decode worker's codec stream and output stage follows the ticket (slots + max_parked rows; blocks are
+ * taken on demand). Under a page limit a parked ticket keeps its admission claim, exactly as if it still sat in its row, and the
+ * row it left holds one page like any idle row. A request that does not fit beside the claims WAITS while a row runs or a parked
+ * ticket wants a row (a parked ticket passes it: it needs no admission); beside tickets the host holds parked and nothing else
+ * it fails on its ticket with Q3_KV_OVERFLOW, as a request that cannot fit does today — unpark first, or raise the limit.
+ * n_running of q3_batcher_step keeps counting rows; parked tickets that want a row count in n_queued (a host loop that stops on
+ * running == 0 && queued == 0 does not stop while they wait); q3_batcher_park_info gives the parked count, the limit, parks,
+ * resumes, resumes into another row than the one left, and the K/V pages the records hold (any pointer may be NULL). */
+enum { Q3_TICKET_PARKED = 5 };
+q3_status q3_batcher_set_parking(q3_batcher* b, int max_parked, int quantum_frames, int fresh_first);
+q3_status q3_batcher_park(q3_batcher* b, int64_t ticket);
+q3_status q3_batcher_unpark(q3_batcher* b, int64_t ticket);
+q3_status q3_batcher_park_info(q3_batcher* b, int* n_parked, int* max_parked, long long* parks, long long* resumes, long long* moved,
+                               int* pages_parked);
 
 /* Chunk decode mode of q3_session_next_chunk. 0 (default) = each chunk decoded as an independent utterance, exactly
  * as the reference does (lib.rs:1755-1758: audible seams, every chunk restarts from zero padding). 1 = continuous:
@@ -453,6 +513,12 @@ typedef struct q3_attn_step_args {
     float* kcache; float* vcache; float* out;
 } q3_attn_step_args;
 q3_status q3_attn_step(int device, const q3_attn_step_args* args);
+/* Test API: one launch of the row-state kernel (k_row_move, q3_session_park_row / _resume_row) over host buffers. Both buffers go
+ * to the device, the n_segs segments — bytes seg_bytes[i] from src_off[i] of the source to dst_off[i] of the destination; mode 0
+ * copies, mode 1 exchanges the two runs — run in ONE launch, both buffers come back. Any length and alignment; a segment that
+ * leaves a buffer is Q3_INVALID_ARG before anything runs. Segments of one call must not overlap one another. */
+q3_status q3_row_move(int device, void* src_host, size_t src_bytes, void* dst_host, size_t dst_bytes, int n_segs, const size_t* src_off,
+                      const size_t* dst_off, const size_t* seg_bytes, const int* mode);
 /* Qwen3TTS::decode_codes (lib.rs:881-890) / Decoder12Hz::decode (decoder_12hz.rs:411-505):
  * frames [n][16] u32 → n*1920 f32 samples. taps (optional, [Q3_DEC_N] host pointers or NULL)
  * receive stage outputs for the stage-by-stage validation the reference does in

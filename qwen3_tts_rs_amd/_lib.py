@@ -129,6 +129,12 @@ SYMBOLS = {
     "q3_batcher_ticket_output": (c_int, [c_void_p, ctypes.c_int64, ctypes.c_uint32, c_int]),
     "q3_batcher_read_out": (c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_size_t, P(ctypes.c_size_t), P(c_int)]),
     "q3_session_replace": (c_int, [c_void_p, c_int, c_void_p]),
+    "q3_session_park_row": (c_int, [c_void_p, c_int, P(c_void_p)]),
+    "q3_session_resume_row": (c_int, [c_void_p, c_int, c_void_p]),
+    "q3_parked_free": (None, [c_void_p]),
+    "q3_parked_info": (c_int, [c_void_p, P(c_int), P(c_int), P(c_int), P(c_int), P(ctypes.c_size_t)]),
+    "q3_row_move": (c_int, [c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_int, P(ctypes.c_size_t), P(ctypes.c_size_t),
+                            P(ctypes.c_size_t), P(c_int)]),
     "q3_batcher_create": (c_int, [c_void_p, c_int, c_int, c_int, P(c_void_p)]),
     "q3_batcher_free": (None, [c_void_p]),
     "q3_batcher_submit": (c_int, [c_void_p, c_void_p, c_int, P(ctypes.c_int64)]),
@@ -139,6 +145,10 @@ SYMBOLS = {
     "q3_batcher_append_text": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_int]),
     "q3_batcher_text_state": (c_int, [c_void_p, ctypes.c_int64, P(c_int), P(c_int), P(c_int), P(c_int)]),
     "q3_batcher_cancel": (c_int, [c_void_p, ctypes.c_int64]),
+    "q3_batcher_set_parking": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "q3_batcher_park": (c_int, [c_void_p, ctypes.c_int64]),
+    "q3_batcher_unpark": (c_int, [c_void_p, ctypes.c_int64]),
+    "q3_batcher_park_info": (c_int, [c_void_p, P(c_int), P(c_int), P(ctypes.c_longlong), P(ctypes.c_longlong), P(ctypes.c_longlong), P(c_int)]),
     "q3_batcher_step": (c_int, [c_void_p, c_int, c_int, P(c_int), P(c_int), P(c_int)]),
     "q3_batcher_poll": (c_int, [c_void_p, ctypes.c_int64, P(c_int), P(c_int), P(ctypes.c_size_t)]),
     "q3_batcher_fetch": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, ctypes.c_size_t]),

@@ -239,6 +239,26 @@ class Session:
             self._row_limit[b] = self._limit_of(utt)
         self._ref_frames[b] = 0 if utt.ref_codes is None else int(np.asarray(utt.ref_codes).reshape(-1, 16).shape[0])
 
+    def park_row(self, b: int) -> "Parked":
+        """Take running row b out of the session between two frames (q3_session_park_row): its K/V pages, device state and codes
+        move into the returned record; the row is left idle. The other rows keep their bits."""
+        h = ctypes.c_void_p()
+        check(lib.q3_session_park_row(self._h, int(b), ctypes.byref(h)))
+        p = Parked(h, self, self._row_limit[b] if b < len(self._row_limit) else 0, self._ref_frames[b])
+        self._ref_frames[b] = 0
+        return p
+
+    def resume_row(self, b: int, parked: "Parked"):
+        """Put a record of this session into row b — idle or ended — (q3_session_resume_row): the row goes on exactly where it
+        stopped. The record is consumed on success."""
+        if parked._h is None:
+            raise ValueError("the record has been resumed or freed")
+        check(lib.q3_session_resume_row(self._h, int(b), parked._h))
+        parked._h = None
+        if b < len(self._row_limit):
+            self._row_limit[b] = max(self._row_limit[b], parked._row_limit)
+        self._ref_frames[b] = parked._ref_frames
+
     def next_chunk_row(self, b: int) -> Tuple[Optional[AudioBuffer], bool]:
         """StreamingSession::next_chunk for row b of a multi-sequence session: (chunk or None, done)."""
         spf = self.model.config.samples_per_frame
@@ -423,24 +443,55 @@ class Session:
         return w.value, k.value
 
 
+class Parked:
+    """A parked row (q3_parked): what Session.park_row returns and Session.resume_row consumes. It holds the row's K/V pages
+    until it is resumed or freed, and may outlive its session."""
+
+    def __init__(self, handle, session: "Session", row_limit: int, ref_frames: int):
+        self._h = handle
+        self._model = session.model          # the record holds its own reference on the native model; this keeps the wrapper too
+        self._row_limit = row_limit
+        self._ref_frames = ref_frames
+
+    def info(self) -> dict:
+        if self._h is None:
+            raise ValueError("the record has been resumed or freed")
+        v = [ctypes.c_int() for _ in range(4)]; nb = ctypes.c_size_t()
+        check(lib.q3_parked_info(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(nb)))
+        return {"frames_committed": v[0].value, "limit": v[1].value, "done": bool(v[2].value), "kv_pages": v[3].value,
+                "state_bytes": nb.value}
+
+    def free(self):
+        """Give the record's pages back without resuming it."""
+        if getattr(self, "_h", None):
+            lib.q3_parked_free(self._h); self._h = None
+
+    __del__ = free
+
+
 class Batcher:
     """Continuous batcher (q3_batcher): requests of any prompt kind, length and options queue up and run through the rows of
     one session; `step` fills free rows, runs a few frames of the shared frame graph and collects finished rows. The
     scheduling loop is native — this class only marshals requests and results."""
     QUEUED, RUNNING, DONE, FAILED = 0, 1, 2, 3
     CANCELLED = 4
+    PARKED = 5
     _WANT = {"codes": 0, "pcm": 1, "stream": 2}
 
     def __init__(self, model: "Qwen3TTS", slots: int = 8, frame_budget: int = 2048, prompt_budget: int = 0,
-                 options: Optional[SynthesisOptions] = None):
+                 options: Optional[SynthesisOptions] = None, max_parked: int = 0, quantum_frames: int = 0, fresh_first: bool = False):
         """slots: rows of the session; frame_budget: largest max_length a request may ask for; prompt_budget: prefill
         positions a row can hold (at least 16 = CustomVoice / x-vector prompts; VoiceDesign: instruct length + 16; ICL:
-        reference frames + 16); options: defaults for utterances without their own."""
+        reference frames + 16); options: defaults for utterances without their own. max_parked > 0 switches parking on
+        (q3_batcher_set_parking): up to that many tickets may wait parked beside the rows; quantum_frames > 0 adds the time
+        slice; fresh_first puts tickets that have never run ahead of parked ones."""
         self.model = model
         self.options = options or SynthesisOptions()
         h = ctypes.c_void_p()
         check(lib.q3_batcher_create(model._h, int(slots), int(frame_budget), int(prompt_budget), ctypes.byref(h)))
         self._h = h
+        if max_parked or quantum_frames or fresh_first:
+            check(lib.q3_batcher_set_parking(self._h, int(max_parked), int(quantum_frames), 1 if fresh_first else 0))
         self._streamed = set()                      # tickets of submit_streamed (their samples leave through read, not fetch)
         self._output = {}                           # ticket -> (rate, pcm16) of the streamed tickets with an output of their own
 
@@ -520,6 +571,22 @@ class Batcher:
         """Give a ticket's place back (between steps): a queued one leaves the queue, a running one keeps the frames it has
         committed (`fetch` / `read` deliver them) and frees its row. The ticket reads CANCELLED."""
         check(lib.q3_batcher_cancel(self._h, int(ticket)))
+
+    def park(self, ticket: int):
+        """Take a running ticket out of its row (between steps); it reads PARKED and keeps its frames until `unpark`."""
+        check(lib.q3_batcher_park(self._h, int(ticket)))
+
+    def unpark(self, ticket: int):
+        """A parked ticket waits for a row again: it re-enters — any free row — at a later fill and goes on where it stopped."""
+        check(lib.q3_batcher_unpark(self._h, int(ticket)))
+
+    def park_info(self) -> dict:
+        """n_parked, max_parked, parks, resumes, moved (resumes into another row than the one left), pages_parked."""
+        n = ctypes.c_int(); mx = ctypes.c_int(); pg = ctypes.c_int()
+        v = [ctypes.c_longlong() for _ in range(3)]
+        check(lib.q3_batcher_park_info(self._h, ctypes.byref(n), ctypes.byref(mx), *[ctypes.byref(x) for x in v], ctypes.byref(pg)))
+        return {"n_parked": n.value, "max_parked": mx.value, "parks": v[0].value, "resumes": v[1].value, "moved": v[2].value,
+                "pages_parked": pg.value}
 
     def read(self, ticket: int, max_samples: Optional[int] = None) -> Tuple[np.ndarray, bool]:
         """(samples of a streamed ticket that have landed and were not read yet — at most max_samples —, done). Never blocks;
@@ -1423,3 +1490,15 @@ def auto_device() -> int:
     if n <= 0:
         raise RuntimeError("no HIP device visible: the MI355X-native build has no CPU fallback")
     return 0
+
+
+def row_move(src: np.ndarray, dst: np.ndarray, segments, device: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """One launch of the row-state kernel over host byte buffers (q3_row_move, test API of Session.park_row / resume_row).
+    segments: (src_offset, dst_offset, n_bytes, mode) with mode 0 = copy src -> dst, 1 = exchange. Returns (src, dst) after it."""
+    a = np.ascontiguousarray(src, dtype=np.uint8).reshape(-1).copy()
+    b = np.ascontiguousarray(dst, dtype=np.uint8).reshape(-1).copy()
+    n = len(segments)
+    so = (ctypes.c_size_t * n)(*[int(g[0]) for g in segments]); do = (ctypes.c_size_t * n)(*[int(g[1]) for g in segments])
+    nb = (ctypes.c_size_t * n)(*[int(g[2]) for g in segments]); md = (ctypes.c_int * n)(*[int(g[3]) for g in segments])
+    check(lib.q3_row_move(int(device), a.ctypes.data_as(ctypes.c_void_p), a.size, b.ctypes.data_as(ctypes.c_void_p), b.size, n, so, do, nb, md))
+    return a, b

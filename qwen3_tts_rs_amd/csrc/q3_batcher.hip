@@ -180,17 +180,29 @@ struct BatTicket {
     long born = 0; uint32_t o_rate = 24000; int o_fmt = Q3_PCM_F32; bool o_conv = false;
     std::vector<char> sout; size_t o_read = 0;
     size_t o_bytes() const { return o_fmt == Q3_PCM_S16 ? 2 : 4; }
+    // Parking (q3_batcher_set_parking; host thread). rec: the ticket's row as a record while it reads PARKED; want_in: it
+    // wants a row again (parked by the scheduler, or q3_batcher_unpark) — it stands in the waiting list once a frame is runnable;
+    // units: its admission claim, which it keeps while parked; entered: frames it had committed when it entered its row (the time
+    // slice counts from there); last_row: the row it left; srow: its row of the worker's codec stream and output stage when
+    // parking is on (the stream row follows the ticket, not the slot), -1 = none
+    q3_parked* rec = nullptr; bool want_in = false, in_queue = false; long units = 0; int entered = 0, last_row = -1, srow = -1;
 };
 // frames [f0, f0 + n) of a streamed ticket for the stream row of its slot: `first` resets the row (and primes it with the ticket's
 // reference frames), `last` gives the row's blocks back once the samples have landed
-struct StreamPart { BatTicket* t; int row; std::vector<uint32_t> frames; bool first, last; };
+struct StreamPart { BatTicket* t; int row; std::vector<uint32_t> frames; bool first, last; };      // (row: of the worker's stream — the slot, or the ticket's own row with parking on)
 struct DecJob { BatTicket* whole = nullptr; std::vector<StreamPart> parts; };      // a whole-ticket decode OR one step's stream parts
 struct q3_batcher {
     q3_model* m = nullptr; int slots = 0, frame_budget = 0, prompt_budget = 0, chunk_frames = 0;
     q3_session* s = nullptr;
     std::vector<int64_t> owner;                       // ticket running in each row, -1 = free
     std::vector<long> commit;                         // KvBudget units row r may still come to hold (worst case of its request), 0 = free row
-    std::vector<int64_t> queue;                       // FIFO of waiting tickets
+    std::vector<int64_t> queue;                       // the ONE waiting list: fresh tickets (QUEUED) and parked ones that want a row again (PARKED)
+    // Parking (q3_batcher_set_parking): off with max_parked = 0 — nothing below is then touched and every entry point behaves as before
+    int max_parked = 0, quantum = 0; bool fresh_first = false;
+    std::vector<int64_t> parked;                      // tickets that hold a record, in park order
+    long long n_parks = 0, n_resumes = 0, n_moved = 0;
+    std::vector<int> srow_free;                       // free rows of the worker's stream / stage (slots + max_parked of them), highest first
+    int stream_rows() const { return slots + max_parked; }
     std::unordered_map<int64_t, std::unique_ptr<BatTicket>> t;
     int64_t next_id = 1;
     // Round 6: the head of the queue is prefilled AHEAD of the row it will enter. A worker thread opens its one-row side session
@@ -314,7 +326,7 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
     q3_status st0 = hipSetDevice(m->device) == hipSuccess ? Q3_OK : set_err(Q3_HIP_ERROR, "hipSetDevice");
     if (st0 == Q3_OK && !d.stream && hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking) != hipSuccess) st0 = set_err(Q3_HIP_ERROR, "hipStreamCreateWithFlags");
     if (st0 == Q3_OK && !d.cs)
-        st0 = codec_stream_create(b->m, b->slots, b->frame_budget + b->prompt_budget, d.stream, &d.cs, b->s_block_frames, b->s_max_blocks);
+        st0 = codec_stream_create(b->m, b->stream_rows(), b->frame_budget + b->prompt_budget, d.stream, &d.cs, b->s_block_frames, b->s_max_blocks);
     auto fail = [&](BatTicket& t, q3_status st, const char* msg) {
         std::lock_guard<std::mutex> g(d.mu);
         if (!t.s_failed) { t.s_failed = true; t.s_st = st; t.s_err = msg; }
@@ -333,7 +345,7 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
     size_t i = 0;
     while (i < parts.size()) {
         // the next group: parts up to the first repeated row
-        std::vector<Out> grp; std::vector<char> seen((size_t)b->slots, 0);
+        std::vector<Out> grp; std::vector<char> seen((size_t)b->stream_rows(), 0);
         for (; i < parts.size() && !seen[(size_t)parts[i].row]; ++i) {
             StreamPart& p = parts[i]; BatTicket& t = *p.t;
             seen[(size_t)p.row] = 1;
@@ -341,7 +353,7 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
             if (p.first) { codec_stream_reset(d.cs, p.row); t.s_all = t.req.ref_codes; t.s_deliv = 0; }
             if (p.first && t.o_conv) {
                 q3_status so = Q3_OK;
-                if (!d.ps) so = q3_pcm_stage_create(m->device, b->slots, (size_t)std::min(b->frame_budget + b->prompt_budget, 100000) * spf, &d.ps);
+                if (!d.ps) so = q3_pcm_stage_create(m->device, b->stream_rows(), (size_t)std::min(b->frame_budget + b->prompt_budget, 100000) * spf, &d.ps);
                 if (so == Q3_OK) so = q3_pcm_stage_set(d.ps, p.row, t.o_rate, t.o_fmt);
                 if (so != Q3_OK) fail(t, so, q3_last_error());
             }
@@ -499,10 +511,13 @@ extern "C" void q3_batcher_free(q3_batcher* b) {
     if (b->tx_steps > 0 && getenv("Q3_BAT_TEXT_STATS"))
         fprintf(stderr, "[q3 batcher text] %ld flushes in %ld steps, %ld tokens, %.3f ms in flushes (%.4f ms per step)\n", b->tx_flushes, b->tx_steps, b->tx_tokens,
                 b->tx_ms, b->tx_ms / b->tx_steps);
+    for (int64_t id : b->parked) { q3_parked_free(b->t[id]->rec); b->t[id]->rec = nullptr; }      // what is still parked gives its pages back
+    b->parked.clear();
     if (b->dec) decoder_stop(b);                       // finishes what is queued (tickets nobody will fetch included), then ends the worker
     if (b->s) q3_session_free(b->s);
     delete b;
 }
+static void queue_enter(q3_batcher* b, int64_t id, bool fresh);
 static q3_status batcher_submit(q3_batcher* b, const q3_request* req, int want_pcm, bool streamed, int64_t* ticket);
 extern "C" q3_status q3_batcher_submit(q3_batcher* b, const q3_request* req, int want_pcm, int64_t* ticket) {
     if (!b || !req || !ticket) return set_err(Q3_INVALID_ARG, "q3_batcher_submit: null argument");
@@ -525,7 +540,7 @@ static q3_status batcher_submit(q3_batcher* b, const q3_request* req, int want_p
     if (streamed) b->n_streamed++;
     const int64_t id = b->next_id++;
     b->t[id] = std::move(t);
-    b->queue.push_back(id);
+    queue_enter(b, id, true);
     *ticket = id;
     return Q3_OK;
 }
@@ -571,7 +586,7 @@ extern "C" q3_status q3_batcher_submit_open(q3_batcher* b, const q3_request* req
     BatTicket& t = *b->t[id];
     t.open = true; t.text_all = t.req.text;
     if (ticket_n_trail(t, t.text_all.size()) + 1 > batcher_text_cap(b)) {
-        b->queue.pop_back(); if (t.streamed) b->n_streamed--; b->t.erase(id);
+        b->queue.erase(std::remove(b->queue.begin(), b->queue.end(), id), b->queue.end()); if (t.streamed) b->n_streamed--; b->t.erase(id);
         return set_err(Q3_UNSUPPORTED, "q3_batcher_submit_open: the text exceeds the row's slot (%d rows)", batcher_text_cap(b));
     }
     b->want_text = true;
@@ -606,7 +621,10 @@ extern "C" q3_status q3_batcher_text_state(q3_batcher* b, int64_t ticket, int* n
     const int lim = t.open ? ticket_limit(t) : 0;
     const int allowed = !t.open ? 0 : t.closed ? lim : std::min(lim, ticket_n_trail(t, t.text_all.size()));
     if (t.state == Q3_TICKET_QUEUED) runnable = t.open ? allowed : t.req.r.opts.max_length;
-    else if (t.row >= 0 && b->s) {
+    else if (t.state == Q3_TICKET_PARKED) {
+        committed = parked_committed(t.rec);
+        runnable = parked_done(t.rec) ? 0 : std::max(0, (t.open ? allowed : parked_seq(t.rec).limit) - committed);
+    } else if (t.row >= 0 && b->s) {
         int done = 0;
         Q3C(q3_session_frames(b->s, t.row, nullptr, &done));
         committed = session_row_committed(b->s, t.row);
@@ -635,10 +653,31 @@ static void stream_part(q3_batcher* b, BatTicket& t, int row, const uint32_t* fr
         n_total = t.s_pushed;
     }
     if (!last && n_total == t.s_pushed) return;
+    if (b->max_parked > 0) {
+        // parking on: the stream row follows the ticket, not the slot — taken with its first part, returned with its last (jobs run
+        // in order and a job is cut where a row repeats, so the row's next owner's first part is served after this last one)
+        if (t.srow < 0) {
+            // (slots + max_parked rows for at most that many tickets in rows or parked; should a row have been lost on an error path,
+            // this ticket fails with a message instead)
+            if (b->srow_free.empty()) {
+                std::lock_guard<std::mutex> g(b->dec->mu);
+                if (!t.s_failed) { t.s_failed = true; t.s_st = Q3_OOM; t.s_err = "streamed ticket: no free row of the decode worker's stream"; }
+                return;
+            }
+            t.srow = b->srow_free.back(); b->srow_free.pop_back();
+        }
+        row = t.srow;
+        if (last) { b->srow_free.push_back(t.srow); std::sort(b->srow_free.begin(), b->srow_free.end(), std::greater<int>()); t.srow = -1; }
+    }
     StreamPart p{&t, row, {}, !t.s_started, last};
-    p.frames.assign(frames + (size_t)t.s_pushed * 16, frames + (size_t)n_total * 16);
+    if (n_total > t.s_pushed) p.frames.assign(frames + (size_t)t.s_pushed * 16, frames + (size_t)n_total * 16);
     t.s_started = true; t.s_pushed = n_total;
     b->sparts.push_back(std::move(p));
+}
+// a streamed ticket that leaves without a last part (the worker failed it) gives its stream row back
+static void stream_row_release(q3_batcher* b, BatTicket& t) {
+    if (t.srow < 0) return;
+    b->srow_free.push_back(t.srow); std::sort(b->srow_free.begin(), b->srow_free.end(), std::greater<int>()); t.srow = -1;
 }
 // the row's sequence has ended: keep its codes (and PCM), free the row
 static q3_status bat_collect(q3_batcher* b, int row) {
@@ -672,6 +711,60 @@ static q3_status bat_collect(q3_batcher* b, int row) {
     // the device freezes a row at its frame limit, not at EOS: idle it now so that it stops advancing — and taking pages — while
     // the queue is empty or waits for room; its pages but one go back to the pool
     return session_idle_row(b->s, row);
+}
+
+// ---- parked tickets (q3_batcher_set_parking) ----
+// frames the text an open ticket has received allows (unflushed tokens included), as q3_batcher_text_state counts them
+static int ticket_allowed(const BatTicket& t) {
+    const int lim = ticket_limit(t);
+    return t.closed ? lim : std::min(lim, ticket_n_trail(t, t.text_all.size()));
+}
+// an open ticket with `committed` frames can commit another one (or is closed: it runs to its end, or is collected)
+static bool ticket_runnable(const BatTicket& t, int committed) { return !t.open || t.closed || ticket_allowed(t) > committed; }
+// The one waiting order. fresh_first = 0: FIFO by arrival / park time. fresh_first != 0: a fresh ticket stands ahead of the parked
+// ones, behind every earlier fresh one.
+static void queue_enter(q3_batcher* b, int64_t id, bool fresh) {
+    auto pos = b->queue.end();
+    if (fresh && b->fresh_first)
+        pos = std::find_if(b->queue.begin(), b->queue.end(), [&](int64_t q) { return b->t[q]->state == Q3_TICKET_PARKED; });
+    b->queue.insert(pos, id);
+    b->t[id]->in_queue = true;
+}
+// parked tickets that want a row again enter the waiting list, in park order, once a frame of theirs is runnable
+static void parked_requeue(q3_batcher* b) {
+    for (int64_t id : b->parked) {
+        BatTicket& t = *b->t[id];
+        if (t.want_in && !t.in_queue && ticket_runnable(t, parked_committed(t.rec))) queue_enter(b, id, false);
+    }
+}
+static int parked_waiting(const q3_batcher* b) {      // want a row, not in the list yet (an open ticket without text)
+    int n = 0;
+    for (int64_t id : b->parked) { const BatTicket& t = *b->t.at(id); n += (t.want_in && !t.in_queue) ? 1 : 0; }
+    return n;
+}
+static void stream_part(q3_batcher* b, BatTicket& t, int row, const uint32_t* frames, int n_total, bool last);
+// row -> record: the ticket reads PARKED, its row is free. A streamed ticket's frames that no step has handed over yet go to the
+// worker as a part with last = false. from_host: q3_batcher_park — the ticket then waits for q3_batcher_unpark.
+static q3_status bat_park(q3_batcher* b, int row, bool from_host) {
+    const int64_t id = b->owner[row];
+    BatTicket& t = *b->t[id];
+    q3_parked* rec = nullptr;
+    Q3C(q3_session_park_row(b->s, row, &rec));
+    if (t.streamed) {
+        const uint32_t* codes = nullptr; const int n = parked_frames(rec, &codes);
+        if (n > t.s_pushed) stream_part(b, t, row, codes, n, false);
+        if (from_host) stream_flush(b);           // (inside a step: with the step's job)
+    }
+    t.rec = rec; t.state = Q3_TICKET_PARKED; t.last_row = row; t.row = -1; t.units = b->commit[row]; t.want_in = !from_host; t.in_queue = false;
+    b->owner[row] = -1; b->commit[row] = 0;
+    b->parked.push_back(id); b->n_parks++;
+    return Q3_OK;
+}
+static void parked_forget(q3_batcher* b, int64_t id) {      // the ticket no longer holds a record
+    b->parked.erase(std::remove(b->parked.begin(), b->parked.end(), id), b->parked.end());
+    b->queue.erase(std::remove(b->queue.begin(), b->queue.end(), id), b->queue.end());
+    BatTicket& t = *b->t[id];
+    t.rec = nullptr; t.want_in = false; t.in_queue = false;
 }
 
 extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph, int* n_running, int* n_queued, int* n_finished) {
@@ -715,7 +808,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
     // holds now — so a page shortage shows up here, as a request that waits in the queue (rows are running: room will come) or
     // fails on its ticket (it cannot fit even alone), never in the middle of a generation where it would stop every row.
     auto held_units = [&](int r) -> long { return (long)b->s->kv_rows[(size_t)r].size() * (b->s->kv_in_bf16 ? 1 : 2); };
-    auto admit = [&](const q3_request& rq, bool open, long* units_out, bool* wait) -> bool {
+    auto admit = [&](const q3_request& rq, bool open, long* units_out, bool* wait, long extra = 0) -> bool {
         *wait = false; *units_out = 0;
         if (!b->s->paged) return true;
         int S = 0, lim = 0; request_shape(rq, &S, &lim);
@@ -728,13 +821,22 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
             mine += h;
             if (b->owner[r] >= 0) { claimed += std::max(b->commit[r], h); running++; } else claimed += h;
         }
+        // a parked ticket counts exactly as if it still sat in a row: the pages its record holds, and its worst case
+        for (int64_t pid : b->parked) {
+            const BatTicket& pt = *b->t[pid];
+            const long h = (long)parked_pages(pt.rec) * (b->s->kv_in_bf16 ? 1 : 2);
+            mine += h; claimed += std::max(pt.units, h);
+            // (only a ticket that wants a row again makes a request WAIT for it: one the host holds parked may stay so for ever,
+            // and a request that cannot fit beside it fails on its ticket, as it does when nothing runs)
+            if (pt.want_in) running++;
+        }
         // pages only the prefix cache holds are reclaimable (kv_take evicts them before a row's request fails): they do not stand
         // in a request's way. A request is never discounted for the pages it hopes to find cached.
         const long reclaim = 2L * prefix_reclaimable(b->m);
         std::lock_guard<std::mutex> g(b->m->kv_budget.mu);
         if (b->m->kv_budget.limit <= 0) return true;
         const long others = std::max(0L, b->m->kv_budget.used - mine - reclaim);
-        if (others + claimed + units <= b->m->kv_budget.limit) return true;
+        if (others + claimed + units + extra <= b->m->kv_budget.limit) return true;      // (extra: the page a row vacated by a park will hold)
         *wait = running > 0;
         return false;
     };
@@ -745,8 +847,25 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
                 const int64_t id = b->queue.front();
                 BatTicket& t = *b->t[id];
                 long units = 0; bool wait = false;
+                if (t.state == Q3_TICKET_PARKED) {
+                    // a parked ticket enters by q3_session_resume_row, into whichever row is free; its admission claim never left
+                    q3_parked* rec = t.rec; const int committed = parked_committed(rec); const long claim = t.units;
+                    const q3_status st = q3_session_resume_row(b->s, r, rec);
+                    parked_forget(b, id);
+                    if (st != Q3_OK) { q3_parked_free(rec); stream_row_release(b, t); bat_fail(t, st); finished++; continue; }
+                    t.state = Q3_TICKET_RUNNING; t.row = r; t.entered = committed; b->owner[r] = id; b->commit[r] = claim;
+                    b->n_resumes++; if (r != t.last_row) b->n_moved++;
+                    break;
+                }
                 if (!admit(t.req.r, t.open, &units, &wait)) {
-                    if (wait) return Q3_OK;          // FIFO: the head of the queue waits for running rows to end
+                    if (wait) {
+                        // FIFO: the head of the queue waits for running rows to end — and for parked tickets, whose claims stand in
+                        // its way like a running row's: the first parked ticket of the list goes ahead (it needs no admission)
+                        auto pk = std::find_if(b->queue.begin(), b->queue.end(), [&](int64_t x) { return b->t[x]->state == Q3_TICKET_PARKED; });
+                        if (pk == b->queue.end()) return Q3_OK;
+                        std::rotate(b->queue.begin(), pk, pk + 1);
+                        continue;
+                    }
                     b->queue.erase(b->queue.begin());
                     if (b->stage.id == id) stage_drop(b);      // (a limit set after it was prefilled ahead) its side session goes with it
                     int S = 0, lim = 0; request_shape(t.req.r, &S, &lim);
@@ -777,7 +896,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
                 } else
                     st = q3_session_replace(b->s, r, &t.req.r);
                 if (st != Q3_OK) { bat_fail(t, st); finished++; continue; }     // does not fit: the ticket carries the reason; try the next one
-                t.state = Q3_TICKET_RUNNING; t.row = r; b->owner[r] = id; b->commit[r] = units;
+                t.state = Q3_TICKET_RUNNING; t.row = r; t.entered = 0; t.in_queue = false; b->owner[r] = id; b->commit[r] = units;
                 break;
             }
         }
@@ -796,6 +915,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
         if (any_free) return;                        // a free row takes the head at once (fill): nothing to run ahead of
         const int64_t id = b->queue.front();
         BatTicket& t = *b->t[id];
+        if (t.state == Q3_TICKET_PARKED) return;     // the worker serves fresh tickets only: a parked one enters by a state copy
         q3_request rq = t.req.r;                     // (arrays owned by the ticket, which lives until it is fetched)
         rq.opts.chunk_frames = b->chunk_frames;
         // an open ticket is staged with a copy of the text it has now (q3_batcher_append_text may grow the ticket's own while the
@@ -849,8 +969,43 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
         b->tx_flushes++; b->tx_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return Q3_OK;
     };
+    // The time slice (quantum_frames > 0), at the start of every piece: while something waits, no row is free and fewer than
+    // max_parked tickets are parked, ONE running ticket is parked — a HELD one first (it counts as having used its quantum), else
+    // the one that has committed the most frames since it entered its row if that is at least the quantum; ties go to the lowest
+    // row — and the list's head takes its row (fill). Reads no clock: a function of submissions, steps and frames.
+    auto used_of = [&](int r) { return session_row_committed(b->s, r) - b->t[b->owner[r]]->entered; };
+    auto slice = [&]() -> q3_status {
+        std::vector<int64_t> mine;                   // parked by this call: the list is served until one of them is its head
+        for (;;) {
+            parked_requeue(b);
+            if (!b->queue.empty() && std::find(mine.begin(), mine.end(), b->queue.front()) != mine.end()) return Q3_OK;
+            if (b->quantum <= 0 || b->queue.empty() || (int)b->parked.size() >= b->max_parked) return Q3_OK;
+            for (int r = 0; r < b->slots; ++r) if (b->owner[r] < 0) return Q3_OK;
+            {   // a fresh head that admission would keep waiting gains nothing from a free row (a parked ticket keeps its claim)
+                BatTicket& h = *b->t[b->queue.front()];
+                long units = 0; bool wait = false;
+                if (h.state != Q3_TICKET_PARKED && !admit(h.req.r, h.open, &units, &wait, b->s->kv_in_bf16 ? 1 : 2)) return Q3_OK;
+            }
+            int victim = -1, most = -1;
+            for (int r = 0; r < b->slots && victim < 0; ++r) {
+                const BatTicket& t = *b->t[b->owner[r]];
+                if (t.open && !ticket_runnable(t, session_row_committed(b->s, r))) victim = r;      // HELD
+            }
+            if (victim < 0) {
+                for (int r = 0; r < b->slots; ++r) { const int u = used_of(r); if (u > most) { most = u; victim = r; } }
+                if (most < b->quantum) return Q3_OK;
+            }
+            const int64_t vid = b->owner[victim];
+            const q3_status st = bat_park(b, victim, false);
+            if (st == Q3_KV_OVERFLOW) return Q3_OK;      // no page for the vacated row under the limit: nothing changed, no slice now
+            Q3C(st);
+            mine.push_back(vid);
+            Q3C(fill());
+        }
+    };
     for (int left = n_frames; left > 0;) {
         Q3C(fill());
+        if (b->max_parked > 0) Q3C(slice());
         Q3C(flush_text());
         int piece = left, busy = 0;
         for (int r = 0; r < b->slots; ++r) {
@@ -859,6 +1014,8 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
             // nothing runnable with the text it has — does not make the piece busy)
             const int rem = session_row_remaining(b->s, r);
             if (rem > 0) { busy++; if (rem < piece) piece = rem; }
+            // something waits: the piece also ends where this row's quantum does
+            if (b->quantum > 0 && rem > 0 && !b->queue.empty()) { const int u = used_of(r); if (u < b->quantum && b->quantum - u < piece) piece = b->quantum - u; }
         }
         if (busy > 0) {
             stage_begin();
@@ -868,6 +1025,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
                 // row that needs the page fails alone and is frozen; the others go on
                 const int row = b->s->kv_overflow_row;
                 bat_fail(*b->t[b->owner[row]], gst);
+                stream_row_release(b, *b->t[b->owner[row]]);
                 b->owner[row] = -1; b->commit[row] = 0;
                 Q3C(session_idle_row(b->s, row));
                 finished++;
@@ -901,6 +1059,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
             bool failed; { std::lock_guard<std::mutex> g(b->dec->mu); failed = t.s_failed; }
             if (failed) {
                 t.state = Q3_TICKET_FAILED; t.st = t.s_st; t.err = t.s_err; t.row = -1;
+                stream_row_release(b, t);
                 b->owner[r] = -1; b->commit[r] = 0;
                 Q3C(session_idle_row(b->s, r));
                 finished++;
@@ -917,14 +1076,34 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
     for (int r = 0; r < b->slots; ++r) running += b->owner[r] >= 0 ? 1 : 0;
     // Nothing runs and nothing waits: the rows that just ended may still be with the decode worker. Their samples are waited for
     // HERE, so that a host loop that stops on "running == 0 && queued == 0" finds every ticket DONE, as it always did.
-    if (running == 0 && b->queue.empty())
+    parked_requeue(b);
+    const int queued = (int)b->queue.size() + parked_waiting(b);      // (parked tickets that want a row count as queued: a host loop must not stop on them)
+    if (running == 0 && queued == 0)
         for (auto& kv : b->t) { ticket_wait_decode(b, *kv.second); stream_settle(b, *kv.second, true); }
     if (n_running) *n_running = running;
-    if (n_queued) *n_queued = (int)b->queue.size();
+    if (n_queued) *n_queued = queued;
     if (n_finished) *n_finished = finished;
     return Q3_OK;
 }
 
+// the samples of a ticket's host codes on the session's stream and workspace, as q3_session_decode gives them for a whole row:
+// an ICL ticket's reference frames are prepended and their share of the samples cut (lib.rs:1022-1041)
+static q3_status decode_host_codes(q3_batcher* b, BatTicket& t) {
+    q3_session* s = b->s; const q3_model* m = b->m;
+    HIPC(hipSetDevice(m->device));
+    HIPC(sync_frames(s));
+    const int spf = samples_per_frame(m->cfg), n = t.n_frames;
+    const int n_ref = t.req.r.mode == Q3_MODE_VOICE_CLONE ? (int)(t.req.ref_codes.size() / 16) : 0, total = n_ref + n;
+    const size_t all = (size_t)total * spf, cut = n_ref > 0 ? (size_t)n_ref * all / (size_t)total : 0;
+    Q3C(codec_reserve(m, s->cws, total));
+    if (n_ref > 0) HIPC(hipMemcpyAsync(s->cws.frames, t.req.ref_codes.data(), (size_t)n_ref * 64, hipMemcpyHostToDevice, s->stream));
+    HIPC(hipMemcpyAsync(s->cws.frames + (size_t)n_ref * 16, t.codes.data(), (size_t)n * 64, hipMemcpyHostToDevice, s->stream));
+    Q3C(codec_decode_dev(m, s->cws, total, s->stream, nullptr));
+    HIPC(sync_frames(s));
+    t.pcm.resize(all - cut);
+    HIPC(q3_hipMemcpy(t.pcm.data(), s->cws.pcm + cut, (all - cut) * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
 // A ticket whose client went away gives its place back. Synchronous: between two steps nothing of the session is in flight.
 // Queued: it leaves the queue (a side session staged for it is dropped with its pages). Running: its row is collected with the
 // frames it has committed — the codes, and their samples: every layer of the vocoder is causal, so they are the first n * 1920
@@ -941,12 +1120,30 @@ extern "C" q3_status q3_batcher_cancel(q3_batcher* b, int64_t ticket) {
         t.cancelled = true; t.state = Q3_TICKET_CANCELLED; t.n_frames = 0; t.s_ended = true;
         return Q3_OK;
     }
+    if (t.state == Q3_TICKET_PARKED) {
+        // out of the record: the codes it has committed, their decode for want_pcm (the session's own decode path over the host
+        // copy, reference frames of an ICL ticket included), the last part of a streamed ticket; the record's pages go back
+        q3_parked* rec = t.rec;
+        const uint32_t* codes = nullptr; const int n = parked_frames(rec, &codes);
+        t.cancelled = true; t.codes.assign(codes, codes + (size_t)n * 16); t.n_frames = n;
+        parked_forget(b, ticket);
+        q3_parked_free(rec);
+        q3_status st = Q3_OK;
+        if (t.streamed) { stream_part(b, t, -1, t.codes.data(), n, true); t.s_ended = true; t.state = Q3_TICKET_RUNNING; stream_settle(b, t, true); }
+        else {
+            if (t.want_pcm && n > 0) st = decode_host_codes(b, t);
+            if (st != Q3_OK) { bat_fail(t, st); return set_err(st, "%s", t.err.c_str()); }
+            t.state = Q3_TICKET_CANCELLED;
+        }
+        return Q3_OK;
+    }
     if (t.state != Q3_TICKET_RUNNING || t.row < 0) return Q3_OK;      // DONE / FAILED / CANCELLED, or ended and with the decode worker: nothing to take back
     const int row = t.row;
     t.cancelled = true;
     const q3_status st = bat_collect(b, row);
     if (st != Q3_OK) {           // the row could not be read: the ticket fails, the row is given up all the same
         bat_fail(t, st); t.decoding = false;
+        stream_row_release(b, t);
         b->owner[row] = -1; b->commit[row] = 0;
         (void)session_idle_row(b->s, row);
         return set_err(st, "%s", t.err.c_str());
@@ -968,6 +1165,7 @@ extern "C" q3_status q3_batcher_poll(q3_batcher* b, int64_t ticket, int* state, 
     if (t.state == Q3_TICKET_RUNNING && b->s && t.row >= 0) {       // frames run so far (an EOS inside them is only looked at when the row is collected)
         nf = session_row_committed(b->s, t.row);      // (an open row: the frames it committed — it may have been held)
     }
+    if (t.state == Q3_TICKET_PARKED) nf = parked_committed(t.rec);      // the frames it had committed when it left its row
     if (n_frames) *n_frames = nf;
     if (n_samples) *n_samples = t.pcm.size();         // (of a ticket still being vocoded: the samples it WILL hold — the size q3_batcher_fetch wants)
     if (n_samples && t.streamed) { std::lock_guard<std::mutex> g(b->dec->mu); *n_samples = t.o_conv ? t.sout.size() / t.o_bytes() : t.spcm.size(); }      // streamed: the samples that have landed
@@ -1077,5 +1275,49 @@ extern "C" q3_status q3_batcher_stream_info(q3_batcher* b, int* block_frames, si
     if (blocks_total) *blocks_total = d.info_total;
     if (blocks_in_use) *blocks_in_use = d.info_use;
     if (blocks_peak) *blocks_peak = d.info_peak;
+    return Q3_OK;
+}
+
+
+// ---- parking: the public calls (include/q3tts.h) ----
+extern "C" q3_status q3_batcher_set_parking(q3_batcher* b, int max_parked, int quantum_frames, int fresh_first) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_set_parking: null batcher");
+    if (b->steps > 0) return set_err(Q3_INVALID_ARG, "q3_batcher_set_parking: after the first q3_batcher_step (the decode worker's stream is sized for slots + max_parked rows)");
+    if (max_parked < 0 || max_parked > 4096 || quantum_frames < 0) return set_err(Q3_INVALID_ARG, "q3_batcher_set_parking: max_parked must be 0..4096, quantum_frames >= 0");
+    b->max_parked = max_parked; b->quantum = max_parked > 0 ? quantum_frames : 0; b->fresh_first = fresh_first != 0;
+    b->srow_free.clear();
+    for (int r = b->stream_rows() - 1; r >= 0; --r) b->srow_free.push_back(r);      // lowest row first (taken from the back)
+    return Q3_OK;
+}
+extern "C" q3_status q3_batcher_park(q3_batcher* b, int64_t ticket) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_park: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_park: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (t.state == Q3_TICKET_QUEUED) return set_err(Q3_INVALID_ARG, "q3_batcher_park: ticket %lld has not entered a row yet", (long long)ticket);
+    if (t.state == Q3_TICKET_PARKED) { t.want_in = false; if (t.in_queue) { b->queue.erase(std::remove(b->queue.begin(), b->queue.end(), ticket), b->queue.end()); t.in_queue = false; } return Q3_OK; }      // the scheduler's park becomes the host's
+    if (t.state != Q3_TICKET_RUNNING || t.row < 0) return Q3_OK;      // ended, or with the decode worker: nothing happens
+    if ((int)b->parked.size() >= b->max_parked)
+        return set_err(Q3_UNSUPPORTED, "q3_batcher_park: %d ticket(s) are parked already (max_parked, q3_batcher_set_parking)", (int)b->parked.size());
+    return bat_park(b, t.row, true);
+}
+extern "C" q3_status q3_batcher_unpark(q3_batcher* b, int64_t ticket) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_unpark: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_unpark: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (t.state != Q3_TICKET_PARKED) return Q3_OK;      // not parked (any more): nothing happens
+    t.want_in = true;
+    parked_requeue(b);
+    return Q3_OK;
+}
+extern "C" q3_status q3_batcher_park_info(q3_batcher* b, int* n_parked, int* max_parked, long long* parks, long long* resumes, long long* moved, int* pages_parked) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_park_info: null batcher");
+    if (n_parked) *n_parked = (int)b->parked.size();
+    if (max_parked) *max_parked = b->max_parked;
+    if (parks) *parks = b->n_parks;
+    if (resumes) *resumes = b->n_resumes;
+    if (moved) *moved = b->n_moved;
+    if (pages_parked) { int n = 0; for (int64_t id : b->parked) n += parked_pages(b->t[id]->rec); *pages_parked = n; }
     return Q3_OK;
 }

@@ -8,6 +8,7 @@
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
 //                    streaming chunks, q3_session_run / decode / get
 //   q3_batcher.hip   continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
+//   q3_row_state.hip a running row's state as an object: k_row_move, q3_session_park_row / _resume_row, q3_parked_* 
 //   q3_testapi.hip   low-level entry points of the parity tests and of bench.py's roofline replays
 // Together they are the host side of libq3tts.so: weight arena, sessions (KV pages, RNG streams, penalty masks), the per-frame
 // launch sequence (captured once, replayed from the library's own AQL queue), the codec-decoder pipeline and the C ABI declared in
@@ -395,6 +396,12 @@ struct SeqInfo {
 };
 
 struct ProfAcc { double ms = 0; double bytes = 0; long launches = 0; };
+// Park / resume (q3_row_state.hip): the device blocks of a session's records. A block a resumed or freed record no longer needs
+// stays on the session's shelf for the next park — the park path then allocates nothing —; once the session is gone (a record
+// may outlive it) blocks go back to the device-memory cache instead. Blocks are powers of two from 64 KB on.
+struct ParkShelf { std::mutex mu; bool alive = true; std::vector<std::pair<void*, size_t>> blocks; };
+enum { PARK_MAX_SEGS = 24, PARK_PAYLOAD_INTS = 8 };      // one k_row_move launch of a park / resume: descriptors + host-made values
+constexpr size_t PARK_DESC_BYTES = (size_t)PARK_MAX_SEGS * 32 + (size_t)PARK_PAYLOAD_INTS * 16;
 struct ProfShape { int M, N, K, epi, rms, produce, tiled, count; };
 
 struct q3_session {
@@ -439,6 +446,10 @@ struct q3_session {
     float* U = nullptr; uint32_t* codes = nullptr;
     float* logits_hist = nullptr; float* cp_logits_hist = nullptr; bool debug = false;
     bool prefilled = false; int frames_run = 0;
+    // park / resume (q3_row_state.hip): what a record names its session by (never reused, unlike the address), and the device table
+    // of one k_row_move launch — descriptors and a few host-made values, one upload (allocated with a paged session) —, and the
+    // shelf its records' device blocks come from and go back to
+    uint64_t uid = 0; char* park_desc = nullptr; std::shared_ptr<ParkShelf> shelf;
     hipGraphExec_t graph_exec = nullptr; hipGraph_t graph = nullptr;
     // the captured frame as a packet program on the library's own AQL queue (q3_aql.cpp); nullptr: frames replay through
     // hipGraphLaunch.  aql_mode: 0 = off, 1 = HIP's header policy (agent-scope fences on every packet), 2 = no fences
@@ -562,6 +573,17 @@ Q3_HIDDEN q3_status session_text_enable(q3_session* s);
 Q3_HIDDEN q3_status session_append_many(q3_session* s, const std::vector<TextPiece>& pieces);
 Q3_HIDDEN int session_row_remaining(const q3_session* s, int b);
 Q3_HIDDEN int session_row_committed(const q3_session* s, int b);
+Q3_HIDDEN q3_status session_refresh_codes(q3_session* s);      // the host copy of the codes, every row's n_frames / done
+// q3_row_state.hip
+// one run of bytes of a k_row_move launch (device-visible, 32 bytes): copied src -> dst, or exchanged
+enum { ROW_MOVE_COPY = 0, ROW_MOVE_EXCHANGE = 1 };
+struct RowSeg { void* src; void* dst; unsigned long long bytes; int mode; int pad; };
+Q3_HIDDEN hipError_t launch_row_move(const RowSeg* segs_dev, int n_segs, size_t max_bytes, hipStream_t st);
+Q3_HIDDEN int parked_frames(const q3_parked* p, const uint32_t** codes);      // frames (cut at an EOS) and the host copy of the codes
+Q3_HIDDEN int parked_committed(const q3_parked* p);
+Q3_HIDDEN int parked_pages(const q3_parked* p);
+Q3_HIDDEN bool parked_done(const q3_parked* p);
+Q3_HIDDEN const SeqInfo& parked_seq(const q3_parked* p);
 // q3_prefix_cache.hip: see q3_prefix_cache.h
 // q3_batcher.hip
 Q3_HIDDEN q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limit);

@@ -490,6 +490,7 @@ q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int fra
     const q3_config& c = m->cfg;
     std::unique_ptr<q3_session> s(new q3_session());
     s->m = m; s->B = batch; s->opts = reqs[0].opts;
+    { static std::atomic<uint64_t> next_uid{1}; s->uid = next_uid.fetch_add(1); }
     m->refs.fetch_add(1);
     if (s->opts.max_length < 1) return set_err(Q3_INVALID_ARG, "max_length must be >= 1");
     s->seq.resize(batch);
@@ -624,6 +625,8 @@ q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int fra
             if (s->max_seq > KV_MAX_PAGES * KV_PAGE_POS) return set_err(Q3_KV_OVERFLOW, "sequence length %d exceeds a row's page table (%d)", s->max_seq, KV_MAX_PAGES * KV_PAGE_POS);
             HIPC(s->pool.alloc(&s->kv_table, (size_t)B * KV_MAX_PAGES));
             HIPC(s->pool.alloc(&s->kv_conv, (size_t)2 * B * KV_MAX_PAGES));
+            HIPC(s->pool.alloc(&s->park_desc, PARK_DESC_BYTES));      // q3_session_park_row / _resume_row: nothing is allocated at a frame boundary
+            s->shelf = std::make_shared<ParkShelf>();
             s->kv_rows.resize((size_t)B);
             for (auto& r : s->kv_rows) r.reserve(KV_MAX_PAGES);
         } else {
@@ -683,6 +686,12 @@ q3_session::~q3_session() {
     for (auto st : par_streams) (void)hipStreamSynchronize(st);
     if (aql) q3::aql_program_destroy(aql);               // waits for its outstanding replays
     for (int b = 0; b < (int)kv_rows.size(); ++b) kv_release_row(this, b);      // every stream that touched them is idle
+    if (shelf) {         // records that outlive the session give their blocks to the device-memory cache themselves
+        std::lock_guard<std::mutex> g(shelf->mu);
+        shelf->alive = false;
+        for (auto& blk : shelf->blocks) dev_free(blk.first);
+        shelf->blocks.clear();
+    }
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     if (graph) (void)hipGraphDestroy(graph);
     for (auto& ev : prof_pool) (void)hipEventDestroy(ev);
@@ -1447,6 +1456,7 @@ static q3_status refresh_codes(q3_session* s) {
     return Q3_OK;
 }
 
+q3_status session_refresh_codes(q3_session* s) { return refresh_codes(s); }
 static bool all_done(q3_session* s) { for (auto& q : s->seq) if (!q.done) return false; return true; }
 // frames the session still has to run for its longest-remaining row (lockstep sessions: max_frames - frames_run)
 // An opened row can commit frames up to what its text allows; a held or finished one none.

@@ -449,4 +449,32 @@ extern "C" q3_status q3_bench_linear(int device, int M, int N, int K, int epi, i
     return Q3_OK;
 }
 
-
+// Op-level test entry: both host buffers (guard bytes included: the caller's business) go to the device, ONE launch runs the
+// segment list, both come back (an exchange changes the source too). Offsets are bytes into the two buffers; a segment that does
+// not lie inside both is refused before anything runs.
+extern "C" q3_status q3_row_move(int device, void* src_host, size_t src_bytes, void* dst_host, size_t dst_bytes, int n_segs, const size_t* src_off,
+                                 const size_t* dst_off, const size_t* seg_bytes, const int* mode) {
+    if (!src_host || !dst_host || !src_off || !dst_off || !seg_bytes || !mode) return set_err(Q3_INVALID_ARG, "q3_row_move: null argument");
+    if (n_segs < 1 || n_segs > 65535) return set_err(Q3_INVALID_ARG, "q3_row_move: %d segments outside 1..65535", n_segs);
+    if (src_bytes == 0 || dst_bytes == 0) return set_err(Q3_INVALID_ARG, "q3_row_move: empty buffer");
+    std::vector<RowSeg> segs((size_t)n_segs); size_t max_bytes = 0;
+    for (int i = 0; i < n_segs; ++i) {
+        if (mode[i] != ROW_MOVE_COPY && mode[i] != ROW_MOVE_EXCHANGE) return set_err(Q3_INVALID_ARG, "q3_row_move: segment %d: mode %d is neither copy (0) nor exchange (1)", i, mode[i]);
+        if (src_off[i] > src_bytes || seg_bytes[i] > src_bytes - src_off[i] || dst_off[i] > dst_bytes || seg_bytes[i] > dst_bytes - dst_off[i])
+            return set_err(Q3_INVALID_ARG, "q3_row_move: segment %d (%zu bytes at %zu -> %zu) leaves its buffers (%zu, %zu bytes)", i, seg_bytes[i], src_off[i], dst_off[i], src_bytes, dst_bytes);
+        max_bytes = std::max(max_bytes, seg_bytes[i]);
+    }
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    char *sd = nullptr, *dd = nullptr; RowSeg* segs_dev = nullptr;
+    HIPC(pool.alloc(&sd, src_bytes)); HIPC(pool.alloc(&dd, dst_bytes)); HIPC(pool.alloc(&segs_dev, (size_t)n_segs));
+    for (int i = 0; i < n_segs; ++i) segs[(size_t)i] = RowSeg{sd + src_off[i], dd + dst_off[i], (unsigned long long)seg_bytes[i], mode[i], 0};
+    HIPC(q3_hipMemcpy(sd, src_host, src_bytes, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(dd, dst_host, dst_bytes, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(segs_dev, segs.data(), segs.size() * sizeof(RowSeg), hipMemcpyHostToDevice));
+    HIPC(launch_row_move(segs_dev, n_segs, max_bytes, nullptr));
+    HIPC(q3_null_stream_sync());
+    HIPC(q3_hipMemcpy(src_host, sd, src_bytes, hipMemcpyDeviceToHost));
+    HIPC(q3_hipMemcpy(dst_host, dd, dst_bytes, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}

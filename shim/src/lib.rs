@@ -67,6 +67,11 @@ pub mod ffi {
                                     pcm: *const *mut f32, cap: *const usize) -> i32;
         pub fn q3_session_create_reserved(m: *mut c_void, reqs: *const Q3Request, batch: i32, frame_budget: i32, prompt_budget: i32, out: *mut *mut c_void) -> i32;
         pub fn q3_session_replace(s: *mut c_void, b: i32, req: *const Q3Request) -> i32;
+        pub fn q3_session_park_row(s: *mut c_void, b: i32, out: *mut *mut c_void) -> i32;
+        pub fn q3_session_resume_row(s: *mut c_void, b: i32, p: *mut c_void) -> i32;
+        pub fn q3_parked_free(p: *mut c_void);
+        pub fn q3_parked_info(p: *const c_void, frames_committed: *mut i32, limit: *mut i32, done: *mut i32, kv_pages: *mut i32, state_bytes: *mut usize) -> i32;
+        pub fn q3_row_move(device: i32, src_host: *mut c_void, src_bytes: usize, dst_host: *mut c_void, dst_bytes: usize, n_segs: i32, src_off: *const usize, dst_off: *const usize, seg_bytes: *const usize, mode: *const i32) -> i32;
         pub fn q3_session_open_text(s: *mut c_void, b: i32) -> i32;
         pub fn q3_session_append_text(s: *mut c_void, b: i32, ids: *const u32, n: i32, last: i32) -> i32;
         pub fn q3_session_text_state(s: *mut c_void, b: i32, n_text: *mut i32, frames_committed: *mut i32, frames_runnable: *mut i32, closed: *mut i32, frames_replayed: *mut i32) -> i32;
@@ -80,6 +85,10 @@ pub mod ffi {
         pub fn q3_batcher_append_text(b: *mut c_void, ticket: i64, ids: *const u32, n: i32, last: i32) -> i32;
         pub fn q3_batcher_text_state(b: *mut c_void, ticket: i64, n_text: *mut i32, frames_committed: *mut i32, frames_runnable: *mut i32, closed: *mut i32) -> i32;
         pub fn q3_batcher_cancel(b: *mut c_void, ticket: i64) -> i32;
+        pub fn q3_batcher_set_parking(b: *mut c_void, max_parked: i32, quantum_frames: i32, fresh_first: i32) -> i32;
+        pub fn q3_batcher_park(b: *mut c_void, ticket: i64) -> i32;
+        pub fn q3_batcher_unpark(b: *mut c_void, ticket: i64) -> i32;
+        pub fn q3_batcher_park_info(b: *mut c_void, n_parked: *mut i32, max_parked: *mut i32, parks: *mut i64, resumes: *mut i64, moved: *mut i64, pages_parked: *mut i32) -> i32;
         pub fn q3_batcher_step(b: *mut c_void, n_frames: i32, use_graph: i32, n_running: *mut i32, n_queued: *mut i32, n_finished: *mut i32) -> i32;
         pub fn q3_batcher_poll(b: *mut c_void, ticket: i64, state: *mut i32, n_frames: *mut i32, n_samples: *mut usize) -> i32;
         pub fn q3_batcher_fetch(b: *mut c_void, ticket: i64, codes: *mut u32, cap_frames: i32, pcm: *mut f32, cap_samples: usize) -> i32;
