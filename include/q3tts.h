@@ -513,6 +513,45 @@ typedef struct q3_attn_step_args {
     float* kcache; float* vcache; float* out;
 } q3_attn_step_args;
 q3_status q3_attn_step(int device, const q3_attn_step_args* args);
+/* Test API: which kernel instance the vocoder conv family runs for a shape — the launchers' own decision function, no GPU
+ * needed. Returns a ConvPath code: low 5 bits the kernel (0 refused, 1 k_conv_out1, 2 k_conv_out1_v4, 3 / 4 k_lin_small_bf16x3
+ * <4 | 8>, 5..11 the k_conv_bf16x3 geometries 96x128 T_M=4 / 4 waves x 32x128 / 4 waves x 32x256 / 64x128 / 64x64 / 128x128 /
+ * 96x128 six waves, 12 / 13 k_conv1d_mfma<CO_W = 2 | 1>, 14 k_conv1d, 15 / 16 k_resunit_bf16x3<3 | 6>), then flags 32 PRE, 64 SEG,
+ * 128 CIS = 128, 256 NP = 2. phases > 1: the polyphase transposed conv (k = taps, dil = 1). q3_conv_path_name: the code as text
+ * (thread-local buffer). q3_resunit_path: launch_resunit's acceptance rule (0 = refused: the caller runs the two convs). */
+int         q3_conv_path(int cout, int cin, int L, int k, int dil, int phases, int packed, int has_resid, int planes, int aligned16);
+int         q3_resunit_path(int C, int L, int dil, int packed, int ya_is_xa, int planes);
+const char* q3_conv_path_name(int code);
+/* Test API: ONE launch of the vocoder conv family over host arrays ([C][L] f32, time contiguous).
+ * kind 0 = launch_conv1d (causal, left zero padding): x [cin][L], w [cout][cin][k], optional b [cout], snake_a / snake_b [cin]
+ *   (SnakeBeta on load), resid [cout][L] (or resid_in_place != 0: the residual is y itself, as the residual units use it), scale
+ *   [cout], act 0..6, post_a / post_ib [cout] (SnakeBeta on the output), y2 (raw in y, activated in y2).
+ * kind 1 = launch_transconv1d_taps: w in the checkpoint layout [cin][cout][k], k = stride * taps; output [cout][L * stride].
+ * kind 2 = launch_resunit: y += conv1x1(snake_mid(conv7_dil(x) + b)) + b2 in place, y2 = snake_post(y); w [C][C][7], w2 [C][C],
+ *   mid_a / mid_ib [C]; cin = cout = C; y2_is_x != 0 passes the operand as the activated output (refused).
+ * packed != 0: the entry packs the weights (launch_pack_conv_w, per phase for kind 1) and passes them; else the f32 kernels run.
+ * snake_raw != 0: the snake pairs are (alpha, beta) and the entry builds each (a, 1/b) table with launch_snake_tables first.
+ * y and y2 are host buffers of y_elems floats whose result starts y_front floats in (y_front % 4 == 0): both are uploaded whole
+ * before the launch and copied back whole after it, guards included. *path (optional) receives the ConvPath code of the launch.
+ * A launch the dispatcher refuses returns Q3_UNSUPPORTED (never another kernel) and leaves y / y2 as they were. */
+typedef struct q3_conv_ex_args {
+    int kind, cin, cout, L, k, dil, stride;
+    int act, planes, packed, resid_in_place, snake_raw, y2_is_x;
+    int y_front, y_elems;
+    int* path;
+    const float* x; const float* w; const float* b;
+    const float* snake_a; const float* snake_b; const float* resid; const float* scale;
+    const float* post_a; const float* post_ib;
+    const float* w2; const float* b2; const float* mid_a; const float* mid_ib;
+    float* y; float* y2;
+} q3_conv_ex_args;
+q3_status q3_conv_ex(int device, const q3_conv_ex_args* args);
+/* Test API: channel norm of x [C][L] over C (launch_layernorm_c / launch_rmsnorm_c): layernorm != 0 takes w and b [C], else w only.
+ * y: host buffer of y_elems floats, result at y_front, uploaded and copied back whole. */
+q3_status q3_norm_c(int device, int layernorm, const float* x, const float* w, const float* b, int C, int L, float eps,
+                    float* y, int y_front, int y_elems);
+/* Test API: depthwise causal conv, 7 taps (launch_dwconv7): x [C][L], w [C][7], b [C]; y as in q3_norm_c. */
+q3_status q3_dwconv7(int device, const float* x, const float* w, const float* b, int C, int L, float* y, int y_front, int y_elems);
 /* Test API: one launch of the row-state kernel (k_row_move, q3_session_park_row / _resume_row) over host buffers. Both buffers go
  * to the device, the n_segs segments — bytes seg_bytes[i] from src_off[i] of the source to dst_off[i] of the destination; mode 0
  * copies, mode 1 exchanges the two runs — run in ONE launch, both buffers come back. Any length and alignment; a segment that

@@ -64,6 +64,13 @@ class CAttnStep(ctypes.Structure):       # q3_attn_step_args
                [(n, ctypes.c_void_p) for n in ("pos", "qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache", "out")]
 
 
+class CConvEx(ctypes.Structure):         # q3_conv_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "cin", "cout", "L", "k", "dil", "stride", "act", "planes", "packed", "resid_in_place",
+                                              "snake_raw", "y2_is_x", "y_front", "y_elems")] + [("path", ctypes.POINTER(ctypes.c_int32))] + \
+               [(n, ctypes.c_void_p) for n in ("x", "w", "b", "snake_a", "snake_b", "resid", "scale", "post_a", "post_ib", "w2", "b2", "mid_a",
+                                               "mid_ib", "y", "y2")]
+
+
 class CTiming(ctypes.Structure):
     _fields_ = [("prefill_ms", ctypes.c_double), ("generation_ms", ctypes.c_double), ("decode_ms", ctypes.c_double),
                 ("generation_frames", ctypes.c_int32)]
@@ -165,6 +172,12 @@ SYMBOLS = {
     "q3_linear": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "q3_linear_ex": (c_int, [c_int, P(CLinearEx)]),
     "q3_attn_step": (c_int, [c_int, P(CAttnStep)]),
+    "q3_conv_path": (c_int, [c_int] * 10),
+    "q3_resunit_path": (c_int, [c_int] * 6),
+    "q3_conv_path_name": (c_char_p, [c_int]),
+    "q3_conv_ex": (c_int, [c_int, P(CConvEx)]),
+    "q3_norm_c": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_int, c_int]),
+    "q3_dwconv7": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     "q3_decode_codes": (c_int, [c_void_p, c_void_p, c_int, c_void_p, P(c_void_p)]),
     "q3_codes_to_tensor": (None, [c_void_p, c_int, c_void_p]),
     "q3_session_set_profile": (c_int, [c_void_p, c_int]),

@@ -1458,6 +1458,100 @@ def attn_step(variant: int, qkv: np.ndarray, pos, q_norm_w: np.ndarray, k_norm_w
     return out, kc, vc
 
 
+def conv_path(cout: int, cin: int, L: int, k: int, dil: int = 1, phases: int = 1, packed: bool = True, has_resid: bool = False,
+              planes: int = 3, aligned16: bool = True) -> int:
+    """q3_conv_path: the ConvPath code launch_conv1d (phases == 1) / launch_transconv1d_taps (phases = stride, k = taps) picks for a
+    shape — kernel in the low 5 bits, flags 32 PRE, 64 SEG, 128 CIS = 128, 256 NP = 2; 0 = refused. No GPU needed."""
+    return lib.q3_conv_path(cout, cin, L, k, dil, phases, int(packed), int(has_resid), planes, int(aligned16))
+
+
+def resunit_path(C: int, L: int, dil: int, packed: bool = True, ya_is_xa: bool = False, planes: int = 3) -> int:
+    """q3_resunit_path: launch_resunit's acceptance rule as a ConvPath code (0 = refused). No GPU needed."""
+    return lib.q3_resunit_path(C, L, dil, int(packed), int(ya_is_xa), planes)
+
+
+def conv_path_name(code: int) -> str:
+    return lib.q3_conv_path_name(code).decode()
+
+
+def conv_ex(kind: int, x: np.ndarray, w: np.ndarray, *, dil: int = 1, stride: int = 1, b: Optional[np.ndarray] = None, snake=None,
+            post=None, mid=None, resid: Optional[np.ndarray] = None, resid_in_place: bool = False, scale: Optional[np.ndarray] = None,
+            act: int = 0, planes: int = 3, packed: bool = True, snake_raw: bool = False, w2: Optional[np.ndarray] = None,
+            b2: Optional[np.ndarray] = None, y: Optional[np.ndarray] = None, y2: Optional[np.ndarray] = None, y_front: int = 0,
+            y2_is_x: bool = False, device: int = 0):
+    """q3_conv_ex: one launch of the vocoder conv family (parity tests). kind 0 = causal conv (w [cout][cin][k]), 1 = transposed conv
+    (w [cin][cout][k], k = stride * taps), 2 = residual unit (w [C][C][7], w2 [C][C], y holds the raw tensor and is updated in place).
+    x [cin][L]. snake / post / mid: pairs of [C] arrays — (a, 1/b) tables, or (alpha, beta) with snake_raw. y / y2: flat f32 buffers
+    whose result starts at y_front; uploaded, written in place and returned whole (y defaults to zeros without guards). Returns
+    (y, y2, path). Raises Q3Error (status 7, with .path) when the launcher refuses the arguments."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    x = f(x); w = f(w)
+    assert x.ndim == 2 and w.ndim == 3
+    cin, L = x.shape
+    cout = w.shape[1] if kind == 1 else w.shape[0]
+    assert (w.shape[0] if kind == 1 else w.shape[1]) == cin
+    a = _lib.CConvEx()
+    a.kind, a.cin, a.cout, a.L, a.k, a.dil, a.stride = kind, cin, cout, L, w.shape[2], dil, stride
+    a.act, a.planes, a.packed, a.resid_in_place, a.snake_raw, a.y2_is_x = act, planes, int(packed), int(resid_in_place), int(snake_raw), int(y2_is_x)
+    n_out = cout * L * (stride if kind == 1 else 1)
+    if y is None:
+        y = np.zeros(n_out, dtype=np.float32); y_front = 0
+    for buf in (y, y2):
+        assert buf is None or (buf.dtype == np.float32 and buf.flags.c_contiguous and buf.ndim == 1 and buf.size == y.size)
+    a.y_front, a.y_elems = y_front, y.size
+    path = ctypes.c_int32(0)
+    a.path = ctypes.pointer(path)
+    keep = [x, w]
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    a.x, a.w, a.y = ptr(x), ptr(w), ptr(y)
+    if y2 is not None:
+        a.y2 = ptr(y2)
+
+    def opt(name, arr, n):
+        if arr is not None:
+            arr = f(arr); assert arr.size == n, (name, arr.size, n)
+            keep.append(arr); setattr(a, name, ptr(arr))
+    opt("b", b, cout); opt("b2", b2, cout); opt("scale", scale, cout); opt("resid", resid, n_out)
+    if w2 is not None:
+        opt("w2", w2, cout * cin)
+    for (na, nb, pr, n) in (("snake_a", "snake_b", snake, cin), ("post_a", "post_ib", post, cout), ("mid_a", "mid_ib", mid, cout)):
+        if pr is not None:
+            opt(na, pr[0], n); opt(nb, pr[1], n)
+    try:
+        check(lib.q3_conv_ex(device, ctypes.byref(a)))
+    except _lib.Q3Error as e:
+        e.path = path.value
+        raise
+    return y, y2, path.value
+
+
+def norm_c(x: np.ndarray, w: np.ndarray, b: Optional[np.ndarray] = None, eps: float = 1e-6, y: Optional[np.ndarray] = None,
+           y_front: int = 0, device: int = 0) -> np.ndarray:
+    """q3_norm_c: LayerNorm (b given) / RMSNorm over the channels of x [C][L]; y as in conv_ex."""
+    x = np.ascontiguousarray(x, dtype=np.float32); C, L = x.shape
+    w = np.ascontiguousarray(w, dtype=np.float32); assert w.shape == (C,)
+    bb = None if b is None else np.ascontiguousarray(b, dtype=np.float32)
+    if y is None:
+        y = np.zeros(C * L, dtype=np.float32); y_front = 0
+    assert y.dtype == np.float32 and y.flags.c_contiguous and y.ndim == 1
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    check(lib.q3_norm_c(device, 0 if bb is None else 1, ptr(x), ptr(w), None if bb is None else ptr(bb), C, L, eps, ptr(y), y_front, y.size))
+    return y
+
+
+def dwconv7(x: np.ndarray, w: np.ndarray, b: np.ndarray, y: Optional[np.ndarray] = None, y_front: int = 0, device: int = 0) -> np.ndarray:
+    """q3_dwconv7: depthwise causal conv with 7 taps, x [C][L], w [C][7], b [C]; y as in conv_ex."""
+    x = np.ascontiguousarray(x, dtype=np.float32); C, L = x.shape
+    w = np.ascontiguousarray(w, dtype=np.float32); b = np.ascontiguousarray(b, dtype=np.float32)
+    assert w.shape == (C, 7) and b.shape == (C,)
+    if y is None:
+        y = np.zeros(C * L, dtype=np.float32); y_front = 0
+    assert y.dtype == np.float32 and y.flags.c_contiguous and y.ndim == 1
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    check(lib.q3_dwconv7(device, ptr(x), ptr(w), ptr(b), C, L, ptr(y), y_front, y.size))
+    return y
+
+
 def sample(logits: np.ndarray, u: np.ndarray, options: SynthesisOptions, seen: Optional[np.ndarray] = None,
            token_count: int = -1, device: int = 0) -> np.ndarray:
     """apply_generation_penalties + sample on the GPU (token_count < 0: plain `sample`, sampling.rs:140)."""

@@ -321,7 +321,40 @@ struct ConvArgs {
 // one-time split of f32 conv weights [cout][cin][K] into bf16 hi/mid/lo MFMA A-operand tiles (cout % 32 == 0, cin % 16 == 0)
 hipError_t launch_pack_conv_w(const float* w, void* out, int cout, int cin, int K, hipStream_t st);
 size_t packed_conv_w_bytes(int cout, int cin, int K);
-hipError_t launch_conv1d(const ConvArgs& a, hipStream_t st);
+// ---- kernel selection of the conv family: pure host functions (no HIP call), so the shape table is testable without a GPU ----
+// The kernel (for k_conv_bf16x3: the workgroup geometry) a launch runs; with the flag bits below: the ConvPath code of q3_conv_path.
+enum ConvKernel {
+    CK_NONE = 0,                 // refused: ConvPath::refusal says how
+    CK_OUT1 = 1, CK_OUT1_V4 = 2, // k_conv_out1, k_conv_out1_v4 (cout = 1)
+    CK_LIN_SMALL_4W = 3, CK_LIN_SMALL_8W = 4,        // k_lin_small_bf16x3<4 | 8>
+    // k_conv_bf16x3<K, CO_M, T_M, WCO, WT>:
+    CK_BF16X3_96x128_TM4 = 5,    // <1, 4, 3, 1>  96 co x 128 t, 3 waves
+    CK_BF16X3_4Wx32x128 = 6,     // <1, 4, 4, 1>  4 waves x 32 co x 128 t
+    CK_BF16X3_4Wx32x256 = 7,     // <1, 8, 4, 1>  4 waves x 32 co x 256 t (Q3_CONV_TM4=3 only)
+    CK_BF16X3_64x128 = 8,        // <1, 2, 2, 2>
+    CK_BF16X3_64x64 = 9,         // <1, 1, 2, 2>
+    CK_BF16X3_128x128 = 10,      // <2, 2, 2, 2>
+    CK_BF16X3_96x128_6W = 11,    // <1, 2, 3, 2>  96 co x 128 t, 6 waves
+    CK_MFMA_F32_64 = 12, CK_MFMA_F32_32 = 13,        // k_conv1d_mfma<K, 2 | 1, 16>
+    CK_VALU = 14,                // k_conv1d
+    CK_RESUNIT_3W = 15, CK_RESUNIT_6W = 16,          // k_resunit_bf16x3<3 | 6>
+    CK_COUNT = 17
+};
+enum { CP_KERNEL_MASK = 31, CP_PRE = 32, CP_SEG = 64, CP_CIS128 = 128, CP_NP2 = 256 };
+struct ConvPath {
+    int kernel = CK_NONE;
+    int co_m = 0, t_m = 0, wco = 0, wt = 0;          // wave tile (32 co_m x 32 t_m) and waves per workgroup (matrix-core kernels; else 0)
+    bool pre = false, seg = false;                   // k_conv_bf16x3<.., PRE, SEG, ..>
+    int cis = 0, np = 0;                             // input channels per LDS stage (32 / 128); bf16 planes (3 / 2); 0: not a bf16x3 kernel
+    hipError_t refusal = hipSuccess;                 // CK_NONE: what the launcher returns
+};
+ConvPath conv_pick(int cout, int cin, int L, int k, int dil, int phases, bool packed, bool has_resid, int planes, bool aligned16,
+                   bool transposed = false);
+ConvPath resunit_pick(int C, int L, int dil, bool complete, bool ya_is_xa, int planes);
+int conv_path_code(const ConvPath& p);               // kernel | CP_* flags
+const char* conv_path_name(int code);                // for messages (thread-local buffer)
+// path (optional, here and below): receives the ConvPath code of the launch (CK_NONE when refused)
+hipError_t launch_conv1d(const ConvArgs& a, hipStream_t st, int* path = nullptr);
 // a whole residual unit (decoder_block.rs:81-92) in one launch: y += conv1x1(snake_mid(conv7_dil(xa) + b1)) + b2, ya = snake_post(y).
 // hipErrorNotSupported (nothing launched) outside 96 / 192 channels with packed weights: the caller runs the two convs.
 struct ResUnitArgs {
@@ -331,13 +364,15 @@ struct ResUnitArgs {
     int C, L, dil;
     int planes = 3;                  // as ConvArgs::planes
 };
-hipError_t launch_resunit(const ResUnitArgs& r, hipStream_t st);
+hipError_t launch_resunit(const ResUnitArgs& r, hipStream_t st, int* path = nullptr);
 // polyphase transposed conv: wp = per-phase causal-conv weights [stride][cout][cin][taps]
 hipError_t launch_transconv1d_taps(const float* x, const float* wp, const float* b, float* y, int cin, int cout, int L,
                                    int stride, int taps, const float* snake_a, const float* snake_ib, hipStream_t st,
                                    const float* post_a = nullptr, const float* post_ib = nullptr, float* y2 = nullptr,
                                    const void* wpk = nullptr,    // wpk: per-phase packed weights, phase-major
-                                   int planes = 3);
+                                   int planes = 3, int* path = nullptr);
+// ConvTranspose1d weights [cin][cout][k] -> the per-phase causal-conv weights above (host; k % stride == 0)
+void transconv_phase_weights(const float* w, int cin, int cout, int k, int stride, float* out);
 hipError_t launch_snake_tables(const float* alpha, const float* beta, float* a, float* ib, int C, hipStream_t st);
 hipError_t launch_dwconv7(const float* x, const float* w, const float* b, float* y, int C, int L, hipStream_t st);
 hipError_t launch_layernorm_c(const float* x, const float* w, const float* b, float* y, int C, int L, float eps,

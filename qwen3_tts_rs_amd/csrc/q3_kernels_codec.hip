@@ -10,6 +10,7 @@
 #include "q3_kernels.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 namespace q3 {
@@ -240,8 +241,8 @@ __global__ __launch_bounds__(256) void k_conv1d_mfma(ConvDev a) {
 }
 
 template <int K>
-static hipError_t launch_conv_mfma_k(const ConvDev& a, int phases, hipStream_t st) {
-    if (a.cout % 64 == 0) {
+static hipError_t launch_conv_mfma_k(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
+    if (p.kernel == CK_MFMA_F32_64) {
         dim3 grid((a.L + 127) / 128, a.cout / 64, phases);
         hipLaunchKernelGGL((k_conv1d_mfma<K, 2, 16>), grid, dim3(256), 0, st, a);
     } else {
@@ -250,16 +251,21 @@ static hipError_t launch_conv_mfma_k(const ConvDev& a, int phases, hipStream_t s
     }
     return hipGetLastError();
 }
-// returns hipErrorNotSupported when the shape should use the VALU kernel
-static hipError_t launch_conv_mfma(const ConvDev& a, int phases, hipStream_t st) {
+// the f32-MFMA generation's part of conv_pick: false when the shape should use the VALU kernel
+static bool conv_pick_mfma(ConvPath& p, int cout, int k) {
     static const bool off = getenv("Q3_CONV_VALU") != nullptr;       // A/B aid
-    if (off || a.cout < 32) return hipErrorNotSupported;
+    if (off || cout < 32) return false;
+    if (k != 1 && k != 2 && k != 3 && k != 7) return false;
+    p.kernel = cout % 64 == 0 ? CK_MFMA_F32_64 : CK_MFMA_F32_32;
+    return true;
+}
+static hipError_t launch_conv_mfma(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
     switch (a.k) {
-        case 1: return launch_conv_mfma_k<1>(a, phases, st);
-        case 2: return launch_conv_mfma_k<2>(a, phases, st);
-        case 3: return launch_conv_mfma_k<3>(a, phases, st);
-        case 7: return launch_conv_mfma_k<7>(a, phases, st);
-        default: return hipErrorNotSupported;
+        case 1: return launch_conv_mfma_k<1>(p, a, phases, st);
+        case 2: return launch_conv_mfma_k<2>(p, a, phases, st);
+        case 3: return launch_conv_mfma_k<3>(p, a, phases, st);
+        case 7: return launch_conv_mfma_k<7>(p, a, phases, st);
+        default: return hipErrorInvalidValue;       // conv_pick never names this kernel for another tap count
     }
 }
 
@@ -814,14 +820,26 @@ __global__ __launch_bounds__(64 * NW, 3) void k_resunit_bf16x3(ResUnitDev a) {
 
 static int conv_planes(int asked) { return asked == 2 ? 2 : 3; }      // ConvArgs::planes: anything but 2 means the exact products
 
-hipError_t launch_resunit(const ResUnitArgs& r, hipStream_t st) {
+// The acceptance rule of launch_resunit as a pure host function (CK_NONE: the caller runs the two convs). `complete`: both
+// packed weights, the middle SnakeBeta and the x / y tensors are there; `ya_is_xa`: the activated output would alias the operand.
+ConvPath resunit_pick(int C, int L, int dil, bool complete, bool ya_is_xa, int planes) {
     static const bool off = getenv("Q3_CONV_F32") != nullptr || getenv("Q3_CODEC_NO_UNIT_FUSE") != nullptr;    // A/B aids
     // 192 channels = six waves per workgroup: measured 1803 us per unit against 1050 + 414 for the two launches (the conv7
     // already prefers two 96-channel workgroups over one of 192: 1.32 vs 1.50 ms) — off unless Q3_CODEC_UNIT_FUSE_192=1
     static const bool fuse192 = getenv("Q3_CODEC_UNIT_FUSE_192") != nullptr;
-    if (off || !r.w1pk || !r.w2pk || (r.C != 96 && !(r.C == 192 && fuse192)) || r.L < 4096 || (r.dil != 1 && r.dil != 3 && r.dil != 9) ||
-        !r.mid_a || !r.xa || !r.y || r.ya == r.xa)
-        return hipErrorNotSupported;
+    ConvPath p;
+    p.refusal = hipErrorNotSupported;
+    if (off || !complete || (C != 96 && !(C == 192 && fuse192)) || L < 4096 || (dil != 1 && dil != 3 && dil != 9) || ya_is_xa) return p;
+    p.kernel = C == 96 ? CK_RESUNIT_3W : CK_RESUNIT_6W;
+    p.co_m = 1; p.t_m = 4; p.wco = C / 32; p.wt = 1; p.cis = 32; p.np = conv_planes(planes);
+    p.refusal = hipSuccess;
+    return p;
+}
+
+hipError_t launch_resunit(const ResUnitArgs& r, hipStream_t st, int* path) {
+    const ConvPath p = resunit_pick(r.C, r.L, r.dil, r.w1pk && r.w2pk && r.mid_a && r.xa && r.y, r.ya == r.xa, r.planes);
+    if (path) *path = conv_path_code(p);
+    if (p.kernel == CK_NONE) return p.refusal;
     ResUnitDev a{};
     a.xa = r.xa; a.y = r.y; a.ya = r.ya; a.w1pk = r.w1pk; a.w2pk = r.w2pk; a.b1 = r.b1; a.b2 = r.b2;
     a.mid_a = r.mid_a; a.mid_ib = r.mid_ib; a.post_a = r.post_a; a.post_ib = r.post_ib; a.C = r.C; a.L = r.L; a.dil = r.dil;
@@ -932,22 +950,20 @@ __global__ __launch_bounds__(64 * W) void k_lin_small_bf16x3(ConvDev a) {
 }
 
 template <int K, int CO_M, int T_M, int WCO, int WT, int NP>
-static hipError_t launch_bf16x3_vp(const ConvDev& a, int phases, hipStream_t st) {
+static hipError_t launch_bf16x3_vp(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
     constexpr int CO_WG = 32 * CO_M * WCO, T_WG = 32 * T_M * WT;
     constexpr bool K1 = K == 1;
-    // 1x1 convs on 64-column tiles (the pre-transformer / ConvNeXt linears): 128 channels per stage, 33 -> 29 and
-    // 75 -> 68 us per launch; on 128-column tiles 64 channels per stage LOST (326 -> 476 us: the residual convs are
-    // bound by their epilogue traffic, and the bigger stage only delays it). Q3_CONV_CIS32=1: 32 everywhere (A/B aid)
-    static const bool cis32 = getenv("Q3_CONV_CIS32") != nullptr;
-    constexpr int CIS1 = T_WG <= 64 ? 128 : 32;
-    const bool wide = K1 && CIS1 > 32 && !cis32 && a.cin >= 2 * CIS1;
-    const size_t lds = (size_t)NP * (T_WG + (K - 1) * a.dil) * ((wide ? CIS1 : 32) * 2 + 16);
+    constexpr int CIS1 = T_WG <= 64 ? 128 : 32;                   // the stage width conv_pick may ask of this geometry besides 32
+    // flags this instance family does not have: conv_pick and the instances below must change together
+    if ((p.cis != 32 && !(K1 && p.cis == CIS1)) || (!K1 && (p.pre || p.seg)) || (p.pre && CO_M != 1)) return hipErrorInvalidValue;
+    const bool wide = p.cis > 32;
+    const size_t lds = (size_t)NP * (T_WG + (K - 1) * a.dil) * (p.cis * 2 + 16);
     dim3 grid(((a.L + T_WG - 1) / T_WG) * (a.cout / CO_WG) * phases);         // tile order: see the kernel
     ConvDev ap = a; ap.phases = phases;
-    const bool segm = conv_segmented(a.k, a.cin);
+    const bool segm = p.seg;
     const dim3 blk(64 * WCO * WT);
     if constexpr (K1) {
-        const bool pre = CO_M == 1 && a.resid;
+        const bool pre = p.pre;
 #define Q3_CV(P, S, C) hipLaunchKernelGGL((k_conv_bf16x3<K, CO_M, T_M, WCO, WT, P, S, C, NP>), grid, blk, lds, st, ap)
         if (wide) {
             if (segm) { if (pre) Q3_CV(CO_M == 1, true, CIS1); else Q3_CV(false, true, CIS1); }
@@ -965,18 +981,33 @@ static hipError_t launch_bf16x3_vp(const ConvDev& a, int phases, hipStream_t st)
     }
     return hipGetLastError();
 }
+// two-plane instances only for the tap counts the vocoder's heavy layers use (1, 2, 7); its one k = 3 conv (pre_conv,
+// 0.06 ms) and the encoders' k = 3 / 5 convs always run three planes — in every decode mode alike, so chunked and
+// whole-utterance decodes still agree
+static bool conv_two_plane_taps(int k) { return k == 1 || k == 2 || k == 7; }
 template <int K, int CO_M, int T_M, int WCO, int WT>
-static hipError_t launch_bf16x3_v(const ConvDev& a, int phases, hipStream_t st) {
-    // two-plane instances only for the tap counts the vocoder's heavy layers use (1, 2, 7); its one k = 3 conv (pre_conv,
-    // 0.06 ms) and the encoders' k = 3 / 5 convs always run three planes — in every decode mode alike, so chunked and
-    // whole-utterance decodes still agree
+static hipError_t launch_bf16x3_v(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
     if constexpr (K == 1 || K == 2 || K == 7)
-        if (a.planes == 2) return launch_bf16x3_vp<K, CO_M, T_M, WCO, WT, 2>(a, phases, st);
-    return launch_bf16x3_vp<K, CO_M, T_M, WCO, WT, 3>(a, phases, st);
+        if (p.np == 2) return launch_bf16x3_vp<K, CO_M, T_M, WCO, WT, 2>(p, a, phases, st);
+    if (p.np != 3) return hipErrorInvalidValue;
+    return launch_bf16x3_vp<K, CO_M, T_M, WCO, WT, 3>(p, a, phases, st);
 }
 template <int K>
-static hipError_t launch_bf16x3_k(const ConvDev& a, int phases, hipStream_t st) {
-    const long big_tiles = (long)((a.L + 127) / 128) * (a.cout / 128) * phases;
+static hipError_t launch_bf16x3_k(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
+    switch (p.kernel) {
+        case CK_BF16X3_96x128_TM4: return launch_bf16x3_v<K, 1, 4, 3, 1>(p, a, phases, st);
+        case CK_BF16X3_4Wx32x128: return launch_bf16x3_v<K, 1, 4, 4, 1>(p, a, phases, st);
+        case CK_BF16X3_4Wx32x256: return launch_bf16x3_v<K, 1, 8, 4, 1>(p, a, phases, st);
+        case CK_BF16X3_64x128: return launch_bf16x3_v<K, 1, 2, 2, 2>(p, a, phases, st);
+        case CK_BF16X3_64x64: return launch_bf16x3_v<K, 1, 1, 2, 2>(p, a, phases, st);
+        case CK_BF16X3_128x128: return launch_bf16x3_v<K, 2, 2, 2, 2>(p, a, phases, st);
+        case CK_BF16X3_96x128_6W: return launch_bf16x3_v<K, 1, 2, 3, 2>(p, a, phases, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+// the workgroup geometry of k_conv_bf16x3 for a shape: one of CK_BF16X3_*, or CK_NONE (no geometry for this cout)
+static int conv_pick_geometry(int K, int cout, int L, int phases, bool has_resid) {
+    const long big_tiles = (long)((L + 127) / 128) * (cout / 128) * phases;
     // 96- and 192-channel layers with taps: wave tiles of 128 time columns (T_M = 4) — a weight fragment serves 4 column
     // tiles instead of 2, half the fragment traffic through the texture path per MFMA (k = 7: 1182 -> 1034 us; the
     // 128-co geometry needs 256 VGPRs for it and loses). Q3_CONV_TM4=0: the T_M = 2 geometry (A/B aid)
@@ -985,61 +1016,100 @@ static hipError_t launch_bf16x3_k(const ConvDev& a, int phases, hipStream_t st) 
     static const int geo = [] { const char* e = getenv("Q3_CONV_TM4"); return e ? atoi(e) : 2; }();
     // (192 co x 64 t in ONE 3-wave workgroup — x staged once instead of twice, but twice the weight-fragment traffic per MFMA —
     // measured 1125-1137 us against 1064-1074 for two workgroups of 96 co x 128 t: rejected)
-    if (geo && K >= 2 && a.L >= 4096 && (a.cout == 192 || a.cout == 96)) return launch_bf16x3_v<K, 1, 4, 3, 1>(a, phases, st);
-    if (geo >= 2 && K >= 2 && a.L >= 4096 && a.cout % 128 == 0 && big_tiles >= 192) {      // experiment: 4 waves x (32 co x 128 / 256 t)
-        if (geo == 2) return launch_bf16x3_v<K, 1, 4, 4, 1>(a, phases, st);
-        if (geo == 3) return launch_bf16x3_v<K, 1, 8, 4, 1>(a, phases, st);
+    if (geo && K >= 2 && L >= 4096 && (cout == 192 || cout == 96)) return CK_BF16X3_96x128_TM4;
+    if (geo >= 2 && K >= 2 && L >= 4096 && cout % 128 == 0 && big_tiles >= 192) {      // experiment: 4 waves x (32 co x 128 / 256 t)
+        if (geo == 2) return CK_BF16X3_4Wx32x128;
+        if (geo == 3) return CK_BF16X3_4Wx32x256;
     }
     // 1x1 convs with a residual (second conv of every residual unit) are bound by their epilogue traffic, not by x
     // staging: the single-co-tile 64 co x 128 t geometry with batched residual loads wins at every width
-    if (K == 1 && a.resid && a.cout % 64 == 0 && a.cout != 96 && big_tiles >= 192) return launch_bf16x3_v<K, 1, 2, 2, 2>(a, phases, st);
+    if (K == 1 && has_resid && cout % 64 == 0 && cout != 96 && big_tiles >= 192) return CK_BF16X3_64x128;
     // wide 1x1 convs without a residual on SMALL grids (the ConvNeXt pw1: 4096 output channels at 1280 / 2560 columns = 320 / 640
     // workgroups of 128 x 128 — barely more than one per CU, each walking all of K): 64 co x 64 t tiles fill the chip four times
     // over instead: 136 -> < 100 us and 243 -> 174 us (round 5; Q3_CONV_PW1_GEO=0 restores the 128 x 128 tiles: A/B aid)
     {
         static const int pw = [] { const char* e = getenv("Q3_CONV_PW1_GEO"); return e ? atoi(e) : 2; }();
-        if (pw && K == 1 && !a.resid && a.cout % 128 == 0 && big_tiles >= 192 && big_tiles < 1024) {
-            if (pw == 1) return launch_bf16x3_v<K, 1, 2, 2, 2>(a, phases, st);      // 64 co x 128 t
-            return launch_bf16x3_v<K, 1, 1, 2, 2>(a, phases, st);                   // 64 co x 64 t
+        if (pw && K == 1 && !has_resid && cout % 128 == 0 && big_tiles >= 192 && big_tiles < 1024) {
+            if (pw == 1) return CK_BF16X3_64x128;      // 64 co x 128 t
+            return CK_BF16X3_64x64;                    // 64 co x 64 t
         }
     }
-    if (a.cout % 128 == 0 && big_tiles >= 192) return launch_bf16x3_v<K, 2, 2, 2, 2>(a, phases, st);   // 128 co x 128 t (64 x 128: 5-13 % slower at k = 7)
-    if (a.cout == 192) return launch_bf16x3_v<K, 1, 2, 3, 2>(a, phases, st);   // 2 x (96 co x 128 t): 1.32 ms vs 1.50 for 192 x 128 (k = 7)
-    if (a.cout == 96) return launch_bf16x3_v<K, 1, 2, 3, 2>(a, phases, st);                             //  96 co x 128 t
-    if (a.cout % 64 == 0) return launch_bf16x3_v<K, 1, 1, 2, 2>(a, phases, st);                         //  64 co x  64 t (small grids)
-    return hipErrorNotSupported;
+    if (cout % 128 == 0 && big_tiles >= 192) return CK_BF16X3_128x128;   // 128 co x 128 t (64 x 128: 5-13 % slower at k = 7)
+    if (cout == 192) return CK_BF16X3_96x128_6W;   // 2 x (96 co x 128 t): 1.32 ms vs 1.50 for 192 x 128 (k = 7)
+    if (cout == 96) return CK_BF16X3_96x128_6W;                             //  96 co x 128 t
+    if (cout % 64 == 0) return CK_BF16X3_64x64;                             //  64 co x  64 t (small grids)
+    return CK_NONE;
 }
-// returns hipErrorNotSupported when the shape has no packed weights / unsupported geometry
-static hipError_t launch_conv_bf16x3(const ConvDev& a, int phases, hipStream_t st) {
+// the bf16x3 generation's part of conv_pick: false when the shape has no packed weights / unsupported geometry
+static bool conv_pick_bf16x3(ConvPath& p, int cout, int cin, int L, int k, int phases, bool packed, bool has_resid, int np) {
     static const bool off = getenv("Q3_CONV_F32") != nullptr;        // A/B aid: force the f32-MFMA generation
-    if (off || !a.wpk || a.cin % 16 || a.cout % 32) return hipErrorNotSupported;
+    if (off || !packed || cin % 16 || cout % 32) return false;
     static const bool no_small = getenv("Q3_CONV_NO_SMALL") != nullptr;   // A/B aid
     // ... and, since it is the same bits, for the narrow deep linears of a whole utterance too (the pre-transformer's o / down
     // projections, 1024 -> 512 at 640 frames: 80 workgroups of the tiled kernel walk 8 serial stages, 38.8 us; as 320
     // one-shot workgroups of 32 x 32 outputs the chip is full once). Only while the grid stays within two rounds —
     // wider outputs (q|k|v, gate|up, the ConvNeXt linears) are already full grids and gain nothing.
     static const bool no_small_tiles = getenv("Q3_CONV_NO_SMALL_TILES") != nullptr;   // A/B aid
-    const long small_wgs = (long)(a.cout / 32) * ((a.L + 31) / 32);
-    const bool small_tiles = a.L > 32 && a.cin >= 1024 && small_wgs <= 512 && !no_small_tiles;
-    if (conv_segmented(a.k, a.cin) && (a.L <= 32 || small_tiles) && phases == 1 && a.cout % 64 == 0 && !no_small) {
-        const dim3 grid(a.cout / 32, (a.L + 31) / 32);
-        if (a.planes == 2) {                                          // the mode's summation is the tiled kernel's in either form
-            if (a.cin >= 1024) hipLaunchKernelGGL((k_lin_small_bf16x3<8, 2>), grid, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((k_lin_small_bf16x3<4, 2>), grid, dim3(256), 0, st, a);
-        } else {
-            if (a.cin >= 1024) hipLaunchKernelGGL((k_lin_small_bf16x3<8, 3>), grid, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((k_lin_small_bf16x3<4, 3>), grid, dim3(256), 0, st, a);
-        }
-        return hipGetLastError();
+    const long small_wgs = (long)(cout / 32) * ((L + 31) / 32);
+    const bool small_tiles = L > 32 && cin >= 1024 && small_wgs <= 512 && !no_small_tiles;
+    if (conv_segmented(k, cin) && (L <= 32 || small_tiles) && phases == 1 && cout % 64 == 0 && !no_small) {
+        p.kernel = cin >= 1024 ? CK_LIN_SMALL_8W : CK_LIN_SMALL_4W;          // the mode's summation is the tiled kernel's in either form
+        p.co_m = 1; p.t_m = 1; p.wco = 1; p.wt = 1; p.seg = true; p.np = np;      // one 32 x 32 tile per workgroup, a wave per 128-channel segment
+        return true;
     }
-    switch (a.k) {
-        case 1: return launch_bf16x3_k<1>(a, phases, st);
-        case 2: return launch_bf16x3_k<2>(a, phases, st);
-        case 3: return launch_bf16x3_k<3>(a, phases, st);
-        case 5: return launch_bf16x3_k<5>(a, phases, st);     // speaker encoder front TDNN
-        case 7: return launch_bf16x3_k<7>(a, phases, st);
-        default: return hipErrorNotSupported;
+    if (k != 1 && k != 2 && k != 3 && k != 5 && k != 7) return false;       // (5: speaker encoder front TDNN)
+    const int g = conv_pick_geometry(k, cout, L, phases, has_resid);
+    if (g == CK_NONE) return false;
+    static const int GEO[7][4] = {{1, 4, 3, 1}, {1, 4, 4, 1}, {1, 8, 4, 1}, {1, 2, 2, 2}, {1, 1, 2, 2}, {2, 2, 2, 2}, {1, 2, 3, 2}};
+    const int* q = GEO[g - CK_BF16X3_96x128_TM4];
+    p.kernel = g; p.co_m = q[0]; p.t_m = q[1]; p.wco = q[2]; p.wt = q[3];
+    p.np = conv_two_plane_taps(k) ? np : 3;
+    p.cis = 32;
+    if (k == 1) {
+        // 1x1 convs on 64-column tiles (the pre-transformer / ConvNeXt linears): 128 channels per stage, 33 -> 29 and
+        // 75 -> 68 us per launch; on 128-column tiles 64 channels per stage LOST (326 -> 476 us: the residual convs are
+        // bound by their epilogue traffic, and the bigger stage only delays it). Q3_CONV_CIS32=1: 32 everywhere (A/B aid)
+        static const bool cis32 = getenv("Q3_CONV_CIS32") != nullptr;
+        const int cis1 = 32 * p.t_m * p.wt <= 64 ? 128 : 32;
+        if (cis1 > 32 && !cis32 && cin >= 2 * cis1) p.cis = cis1;
+        p.seg = conv_segmented(k, cin);
+        p.pre = p.co_m == 1 && has_resid;
     }
+    return true;
+}
+
+// Which kernel — and which instance of it — a conv runs on: the whole decision chain of launch_conv1d /
+// launch_transconv1d_taps as one pure host function (no HIP call; the A/B knobs above are read once per process).
+// `packed`: bf16x3-packed weights are there; `aligned16`: x and y are 16-byte aligned (the float4 form of the 1-channel conv);
+// `transposed`: the phases of a polyphase transposed conv (k = taps, dil = 1) — launch_transconv1d_taps has no 1-channel form.
+ConvPath conv_pick(int cout, int cin, int L, int k, int dil, int phases, bool packed, bool has_resid, int planes, bool aligned16, bool transposed) {
+    ConvPath p;
+    if (k < 1 || k > CV_MAXK || (k - 1) * dil > CV_MAXHALO || L <= 0 || cout < 1 || cin < 1 || phases < 1) { p.refusal = hipErrorInvalidValue; return p; }
+    if (cout == 1 && !transposed) {
+        p.kernel = (k == 7 && dil == 1 && L % 4 == 0 && aligned16) ? CK_OUT1_V4 : CK_OUT1;
+        return p;
+    }
+    if (conv_pick_bf16x3(p, cout, cin, L, k, phases, packed, has_resid, conv_planes(planes))) return p;
+    if (conv_pick_mfma(p, cout, k)) return p;
+    p.kernel = CK_VALU;
+    return p;
+}
+
+int conv_path_code(const ConvPath& p) {
+    return p.kernel | (p.pre ? CP_PRE : 0) | (p.seg ? CP_SEG : 0) | (p.cis == 128 ? CP_CIS128 : 0) | (p.np == 2 ? CP_NP2 : 0);
+}
+const char* conv_path_name(int code) {
+    static const char* const KN[CK_COUNT] = {
+        "none", "k_conv_out1", "k_conv_out1_v4", "k_lin_small_bf16x3<4>", "k_lin_small_bf16x3<8>",
+        "k_conv_bf16x3<96co x 128t, 3 waves, T_M=4>", "k_conv_bf16x3<4 waves x 32co x 128t>", "k_conv_bf16x3<4 waves x 32co x 256t>",
+        "k_conv_bf16x3<64co x 128t>", "k_conv_bf16x3<64co x 64t>", "k_conv_bf16x3<128co x 128t>", "k_conv_bf16x3<96co x 128t, 6 waves>",
+        "k_conv1d_mfma<CO_W=2>", "k_conv1d_mfma<CO_W=1>", "k_conv1d", "k_resunit_bf16x3<3>", "k_resunit_bf16x3<6>"};
+    static thread_local char buf[96];
+    const int k = code & CP_KERNEL_MASK;
+    if (code < 0 || k >= CK_COUNT || (code & ~(CP_KERNEL_MASK | CP_PRE | CP_SEG | CP_CIS128 | CP_NP2))) return "invalid";
+    snprintf(buf, sizeof buf, "%s%s%s%s%s", KN[k], (code & CP_PRE) ? " PRE" : "", (code & CP_SEG) ? " SEG" : "", (code & CP_CIS128) ? " CIS=128" : "",
+             (code & CP_NP2) ? " NP=2" : "");
+    return buf;
 }
 
 // single-output-channel conv (final 96→1, k=7): one thread per time step
@@ -1099,36 +1169,68 @@ __global__ __launch_bounds__(256) void k_conv_out1_v4(ConvDev a) {
     *reinterpret_cast<float4*>(a.y + t) = make_float4(o[0], o[1], o[2], o[3]);
 }
 
-hipError_t launch_conv1d(const ConvArgs& c, hipStream_t st) {
-    if (c.k > CV_MAXK || (c.k - 1) * c.dil > CV_MAXHALO || c.L <= 0) return hipErrorInvalidValue;
+// one launch of the kernel instance conv_pick named
+static hipError_t launch_conv_path(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
+    switch (p.kernel) {
+        case CK_NONE: return p.refusal != hipSuccess ? p.refusal : hipErrorInvalidValue;
+        case CK_OUT1_V4: hipLaunchKernelGGL(k_conv_out1_v4, dim3((a.L / 4 + 255) / 256), dim3(256), 0, st, a); break;
+        case CK_OUT1: hipLaunchKernelGGL(k_conv_out1, dim3((a.L + 255) / 256), dim3(256), 0, st, a); break;
+        case CK_LIN_SMALL_4W:
+        case CK_LIN_SMALL_8W: {
+            const dim3 grid(a.cout / 32, (a.L + 31) / 32);
+            if (p.np == 2) {
+                if (p.kernel == CK_LIN_SMALL_8W) hipLaunchKernelGGL((k_lin_small_bf16x3<8, 2>), grid, dim3(512), 0, st, a);
+                else hipLaunchKernelGGL((k_lin_small_bf16x3<4, 2>), grid, dim3(256), 0, st, a);
+            } else {
+                if (p.kernel == CK_LIN_SMALL_8W) hipLaunchKernelGGL((k_lin_small_bf16x3<8, 3>), grid, dim3(512), 0, st, a);
+                else hipLaunchKernelGGL((k_lin_small_bf16x3<4, 3>), grid, dim3(256), 0, st, a);
+            }
+            break;
+        }
+        case CK_MFMA_F32_64:
+        case CK_MFMA_F32_32: return launch_conv_mfma(p, a, phases, st);
+        case CK_VALU: {
+            dim3 grid((a.L + CV_T - 1) / CV_T, (a.cout + CV_CO - 1) / CV_CO, phases);
+            hipLaunchKernelGGL(k_conv1d, grid, dim3(256), 0, st, a);
+            break;
+        }
+        default:
+            switch (a.k) {
+                case 1: return launch_bf16x3_k<1>(p, a, phases, st);
+                case 2: return launch_bf16x3_k<2>(p, a, phases, st);
+                case 3: return launch_bf16x3_k<3>(p, a, phases, st);
+                case 5: return launch_bf16x3_k<5>(p, a, phases, st);     // speaker encoder front TDNN
+                case 7: return launch_bf16x3_k<7>(p, a, phases, st);
+                default: return hipErrorInvalidValue;
+            }
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_conv1d(const ConvArgs& c, hipStream_t st, int* path) {
+    const ConvPath p = conv_pick(c.cout, c.cin, c.L, c.k, c.dil, 1, c.wpk != nullptr, c.resid != nullptr, c.planes,
+                                 (((uintptr_t)c.x | (uintptr_t)c.y) & 15) == 0, false);
+    if (path) *path = conv_path_code(p);
+    if (p.kernel == CK_NONE) return p.refusal;
     ConvDev a{};
     a.x = c.x; a.w = c.w; a.b = c.b; a.y = c.y; a.cin = c.cin; a.cout = c.cout; a.L = c.L; a.k = c.k; a.dil = c.dil;
     a.snake_a = c.snake_a; a.snake_ib = c.snake_b; a.resid = c.resid; a.scale = c.scale; a.act = c.act;
     a.ostride = 1; a.ooff = 0; a.oL = c.L; a.w_phase_stride = 0; a.ooff_phase = 0;
     a.post_a = c.post_a; a.post_ib = c.post_ib; a.y2 = c.y2;
     a.wpk = c.wpk; a.wpk_phase_stride = 0; a.planes = conv_planes(c.planes);
-    if (c.cout == 1) {
-        if (c.k == 7 && c.dil == 1 && c.L % 4 == 0 && (((uintptr_t)c.x | (uintptr_t)c.y) & 15) == 0)
-            hipLaunchKernelGGL(k_conv_out1_v4, dim3((c.L / 4 + 255) / 256), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_conv_out1, dim3((c.L + 255) / 256), dim3(256), 0, st, a);
-    } else if (hipError_t e = launch_conv_bf16x3(a, 1, st); e != hipErrorNotSupported) {
-        return e;
-    } else if (hipError_t e = launch_conv_mfma(a, 1, st); e != hipErrorNotSupported) {
-        return e;
-    } else {
-        dim3 grid((c.L + CV_T - 1) / CV_T, (c.cout + CV_CO - 1) / CV_CO, 1);
-        hipLaunchKernelGGL(k_conv1d, grid, dim3(256), 0, st, a);
-    }
-    return hipGetLastError();
+    return launch_conv_path(p, a, 1, st);
 }
 
 // Transposed conv, polyphase form. Host code pre-arranges the weight [cin][cout][k] into per-phase
-// causal-conv weights wp[ph][cout][cin][taps] (taps = k/stride: tap 0 ↔ x[j-1] (w[.][.][ph+s]),
+// causal-conv weights wp[ph][cout][cin][taps] (transconv_phase_weights: taps = k/stride: tap 0 ↔ x[j-1] (w[.][.][ph+s]),
 // last tap ↔ x[j] (w[.][.][ph])), so phase ph is a k=taps causal conv whose outputs land at
 // t = j*stride + ph; the right-trim k - s of causal_trans_conv.rs:79 is implicit (length L*stride).
 hipError_t launch_transconv1d_taps(const float* x, const float* wp, const float* b, float* y, int cin, int cout, int L,
                                    int stride, int taps, const float* snake_a, const float* snake_ib, hipStream_t st,
-                                   const float* post_a, const float* post_ib, float* y2, const void* wpk, int planes) {
+                                   const float* post_a, const float* post_ib, float* y2, const void* wpk, int planes, int* path) {
+    const ConvPath p = conv_pick(cout, cin, L, taps, 1, stride, wpk != nullptr, false, planes, false, true);
+    if (path) *path = conv_path_code(p);
+    if (p.kernel == CK_NONE) return p.refusal;
     ConvDev a{};
     a.planes = conv_planes(planes);
     a.wpk = wpk; a.wpk_phase_stride = packed_conv_w_bytes(cout, cin, taps) / 16;
@@ -1137,11 +1239,20 @@ hipError_t launch_transconv1d_taps(const float* x, const float* wp, const float*
     a.snake_a = snake_a; a.snake_ib = snake_ib; a.resid = nullptr; a.scale = nullptr; a.act = 0;
     a.ostride = stride; a.ooff = 0; a.oL = L * stride;
     a.w_phase_stride = (size_t)cout * cin * taps; a.ooff_phase = 1;
-    if (hipError_t e = launch_conv_bf16x3(a, stride, st); e != hipErrorNotSupported) return e;
-    if (hipError_t e = launch_conv_mfma(a, stride, st); e != hipErrorNotSupported) return e;
-    dim3 grid((L + CV_T - 1) / CV_T, (cout + CV_CO - 1) / CV_CO, stride);
-    hipLaunchKernelGGL(k_conv1d, grid, dim3(256), 0, st, a);
-    return hipGetLastError();
+    return launch_conv_path(p, a, stride, st);
+}
+
+// [cin][cout][k] (the checkpoint's ConvTranspose1d layout) -> per-phase causal-conv weights [stride][cout][cin][taps], taps = k / stride:
+// tap tp multiplies x[j - (taps-1-tp)], i.e. kernel index ph + (taps-1-tp)*stride. Shared by the model loader and the op-level test entry.
+void transconv_phase_weights(const float* w, int cin, int cout, int k, int stride, float* out) {
+    const int taps = k / stride;
+    for (int ph = 0; ph < stride; ++ph)
+        for (int co = 0; co < cout; ++co)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int tp = 0; tp < taps; ++tp) {
+                    const int kk = ph + (taps - 1 - tp) * stride;
+                    out[(((size_t)ph * cout + co) * cin + ci) * taps + tp] = w[((size_t)ci * cout + co) * k + kk];
+                }
 }
 
 // depthwise causal conv k=7 (ConvNeXt, convnext_block.rs:116)

@@ -429,17 +429,8 @@ extern "C" q3_status q3_model_set_tensor(q3_model* m, const char* name, int dtyp
         std::vector<float> w((size_t)n);
         if (dtype == Q3_DTYPE_F32) memcpy(w.data(), data, (size_t)n * 4);
         else for (int64_t i = 0; i < n; ++i) w[(size_t)i] = bf16_to_f32_host(((const uint16_t*)data)[i]);
-        const int cin = s.tc_cin, cout = s.tc_cout, k = s.tc_k, st = s.tc_stride, taps = k / st;
         tmp.resize(bytes);
-        float* o = (float*)tmp.data();
-        for (int ph = 0; ph < st; ++ph)
-            for (int co = 0; co < cout; ++co)
-                for (int ci = 0; ci < cin; ++ci)
-                    for (int tp = 0; tp < taps; ++tp) {
-                        // tap tp multiplies x[j - (taps-1-tp)]  ⇒  kernel index ph + (taps-1-tp)*stride
-                        const int kk = ph + (taps - 1 - tp) * st;
-                        o[(((size_t)ph * cout + co) * cin + ci) * taps + tp] = w[((size_t)ci * cout + co) * k + kk];
-                    }
+        transconv_phase_weights(w.data(), s.tc_cin, s.tc_cout, s.tc_k, s.tc_stride, (float*)tmp.data());
         src = tmp.data();
     } else if (s.stored == Q3_DTYPE_BF16 && dtype == Q3_DTYPE_F32) {
         tmp.resize(bytes);

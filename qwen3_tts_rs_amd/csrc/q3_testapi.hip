@@ -296,6 +296,158 @@ extern "C" q3_status q3_attn_step(int device, const q3_attn_step_args* p) {
     return Q3_OK;
 }
 
+// ---- the vocoder conv family, one launch at a time (tests/test_gpu_conv_ops.py) ----
+extern "C" int q3_conv_path(int cout, int cin, int L, int k, int dil, int phases, int packed, int has_resid, int planes, int aligned16) {
+    return conv_path_code(conv_pick(cout, cin, L, k, dil, phases, packed != 0, has_resid != 0, planes, aligned16 != 0, phases > 1));
+}
+extern "C" int q3_resunit_path(int C, int L, int dil, int packed, int ya_is_xa, int planes) {
+    return conv_path_code(resunit_pick(C, L, dil, packed != 0, ya_is_xa != 0, planes));
+}
+extern "C" const char* q3_conv_path_name(int code) { return conv_path_name(code); }
+
+// One launch_conv1d / launch_transconv1d_taps / launch_resunit call over host arrays. The weight packing, the transposed conv's
+// per-phase rearrangement (the loader's own helper) and the snake tables are preparation; exactly one launch of the family runs.
+// A launch the dispatcher refuses comes back as a status — never another kernel in its place — and leaves the host y / y2 alone.
+extern "C" q3_status q3_conv_ex(int device, const q3_conv_ex_args* p) {
+    if (!p || !p->x || !p->w || !p->y) return set_err(Q3_INVALID_ARG, "q3_conv_ex: null argument");
+    if (p->path) *p->path = 0;
+    const int kind = p->kind, cin = p->cin, cout = p->cout, L = p->L, k = p->k, dil = p->dil;
+    if (kind < 0 || kind > 2) return set_err(Q3_INVALID_ARG, "q3_conv_ex: kind 0..2");
+    if (cin < 1 || cin > 8192 || cout < 1 || cout > 8192 || L < 1 || L > (1 << 22) || k < 1 || k > 64 || dil < 1 || dil > 64 || p->act < 0 || p->act > 6)
+        return set_err(Q3_INVALID_ARG, "q3_conv_ex: bad shape (channels 1..8192, L 1..2^22, k 1..64, dil 1..64, act 0..6)");
+    const int stride = kind == 1 ? p->stride : 1;
+    if (kind == 1 && (stride < 1 || stride > 16 || k % stride)) return set_err(Q3_INVALID_ARG, "q3_conv_ex: transposed conv needs 1 <= stride <= 16 and k %% stride == 0");
+    const int taps = k / stride;
+    if (kind == 2 && (cin != cout || k != 7 || !p->w2 || !p->mid_a || !p->mid_ib)) return set_err(Q3_INVALID_ARG, "q3_conv_ex: residual unit needs cin == cout, k == 7, w2 and the middle snake pair");
+    if (!p->snake_a != !p->snake_b || !p->post_a != !p->post_ib || !p->mid_a != !p->mid_ib) return set_err(Q3_INVALID_ARG, "q3_conv_ex: half a snake pair");
+    if (kind != 0 && (p->resid || p->resid_in_place || p->scale || p->act)) return set_err(Q3_INVALID_ARG, "q3_conv_ex: resid / scale / act belong to kind 0");
+    if (kind != 0 && kind != 2 && p->y2_is_x) return set_err(Q3_INVALID_ARG, "q3_conv_ex: y2_is_x belongs to kind 2");
+    if ((p->resid && p->resid_in_place) || (p->y2 && p->y2_is_x)) return set_err(Q3_INVALID_ARG, "q3_conv_ex: two residuals / two y2");
+    const size_t out_n = (size_t)cout * L * stride, xn = (size_t)cin * L, wn = (size_t)cout * cin * k;
+    if (p->y_front < 0 || p->y_front % 4 || p->y_elems < 0 || (size_t)p->y_elems < (size_t)p->y_front + out_n)
+        return set_err(Q3_INVALID_ARG, "q3_conv_ex: y must hold y_front (a multiple of 4) + cout * L * stride floats");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    float *x, *w, *w2 = nullptr, *b = nullptr, *b2 = nullptr, *res = nullptr, *scale = nullptr, *y, *y2 = nullptr;
+    void *wpk = nullptr, *w2pk = nullptr;
+    HIPC(pool.alloc(&x, xn)); HIPC(q3_hipMemcpy(x, p->x, xn * 4, hipMemcpyHostToDevice));
+    HIPC(pool.alloc(&w, wn));
+    if (kind == 1) {          // checkpoint layout in, the loader's rearrangement, per-phase weights up
+        std::vector<float> wp(wn);
+        transconv_phase_weights(p->w, cin, cout, k, stride, wp.data());
+        HIPC(q3_hipMemcpy(w, wp.data(), wn * 4, hipMemcpyHostToDevice));
+    } else HIPC(q3_hipMemcpy(w, p->w, wn * 4, hipMemcpyHostToDevice));
+    if (kind == 2) { HIPC(pool.alloc(&w2, (size_t)cout * cin)); HIPC(q3_hipMemcpy(w2, p->w2, (size_t)cout * cin * 4, hipMemcpyHostToDevice)); }
+    auto vec = [&](const float* h, int n, float** d) -> q3_status {
+        *d = nullptr;
+        if (!h) return Q3_OK;
+        HIPC(pool.alloc(d, (size_t)n)); HIPC(q3_hipMemcpy(*d, h, (size_t)n * 4, hipMemcpyHostToDevice));
+        return Q3_OK;
+    };
+    // a snake pair: the tables as given, or built from (alpha, beta) by the engine's own kernel
+    auto pair = [&](const float* ha, const float* hb, int n, float** da, float** db) -> q3_status {
+        Q3C(vec(ha, n, da)); Q3C(vec(hb, n, db));
+        if (ha && p->snake_raw) {
+            float *ta, *tb;
+            HIPC(pool.alloc(&ta, (size_t)n)); HIPC(pool.alloc(&tb, (size_t)n));
+            HIPC(launch_snake_tables(*da, *db, ta, tb, n, 0));
+            *da = ta; *db = tb;
+        }
+        return Q3_OK;
+    };
+    float *sa, *sb, *pa, *pb, *ma, *mb;
+    Q3C(vec(p->b, cout, &b)); Q3C(vec(p->b2, cout, &b2)); Q3C(vec(p->scale, cout, &scale)); Q3C(vec(p->resid, (int)out_n, &res));
+    Q3C(pair(p->snake_a, p->snake_b, cin, &sa, &sb)); Q3C(pair(p->post_a, p->post_ib, cout, &pa, &pb)); Q3C(pair(p->mid_a, p->mid_ib, cout, &ma, &mb));
+    const size_t yn = (size_t)p->y_elems;
+    HIPC(pool.alloc(&y, yn)); HIPC(q3_hipMemcpy(y, p->y, yn * 4, hipMemcpyHostToDevice));
+    if (p->y2) { HIPC(pool.alloc(&y2, yn)); HIPC(q3_hipMemcpy(y2, p->y2, yn * 4, hipMemcpyHostToDevice)); }
+    float* yr = y + p->y_front; float* y2r = y2 ? y2 + p->y_front : nullptr;
+    if (p->packed) {
+        const int pk = kind == 1 ? taps : k;
+        if (cout % 32 || cin % 16 || pk < 1) return set_err(Q3_UNSUPPORTED, "q3_conv_ex: cout %d / cin %d cannot be packed (cout %% 32, cin %% 16)", cout, cin);
+        const size_t per = packed_conv_w_bytes(cout, cin, pk);
+        char* d; HIPC(pool.alloc(&d, per * (size_t)stride)); wpk = d;
+        for (int ph = 0; ph < stride; ++ph) HIPC(launch_pack_conv_w(w + (size_t)ph * cout * cin * pk, d + (size_t)ph * per, cout, cin, pk, 0));
+        if (kind == 2) {
+            char* d2; HIPC(pool.alloc(&d2, packed_conv_w_bytes(cout, cin, 1))); w2pk = d2;
+            HIPC(launch_pack_conv_w(w2, d2, cout, cin, 1, 0));
+        }
+    }
+    HIPC(q3_hipDeviceSynchronize());
+    hipError_t e;
+    int path = 0;
+    if (kind == 0) {
+        ConvArgs a;
+        a.x = x; a.w = w; a.b = b; a.y = yr; a.cin = cin; a.cout = cout; a.L = L; a.k = k; a.dil = dil;
+        a.snake_a = sa; a.snake_b = sb; a.resid = p->resid_in_place ? yr : res; a.scale = scale; a.act = p->act;
+        a.post_a = pa; a.post_ib = pb; a.y2 = y2r; a.wpk = wpk; a.planes = p->planes;
+        e = launch_conv1d(a, 0, &path);
+    } else if (kind == 1) {
+        e = launch_transconv1d_taps(x, w, b, yr, cin, cout, L, stride, taps, sa, sb, 0, pa, pb, y2r, wpk, p->planes, &path);
+    } else {
+        ResUnitArgs r{};
+        r.xa = x; r.y = yr; r.ya = p->y2_is_x ? x : y2r; r.w1pk = wpk; r.w2pk = w2pk; r.b1 = b; r.b2 = b2;
+        r.mid_a = ma; r.mid_ib = mb; r.post_a = pa; r.post_ib = pb; r.C = cout; r.L = L; r.dil = dil; r.planes = p->planes;
+        e = launch_resunit(r, 0, &path);
+    }
+    if (p->path) *p->path = path;
+    if (e == hipErrorInvalidValue || e == hipErrorNotSupported) {
+        (void)hipGetLastError();
+        return set_err(Q3_UNSUPPORTED, "q3_conv_ex: the launcher refused kind=%d cin=%d cout=%d L=%d k=%d dil=%d stride=%d packed=%d planes=%d (%s)", kind, cin, cout,
+                       L, k, dil, stride, p->packed, p->planes, hipGetErrorString(e));
+    }
+    HIPC(e);
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->y, y, yn * 4, hipMemcpyDeviceToHost));
+    if (y2) HIPC(q3_hipMemcpy(p->y2, y2, yn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+static q3_status check_cl_out(const char* who, const void* x, const void* w, const void* y, int C, int L, int y_front, int y_elems) {
+    if (!x || !w || !y) return set_err(Q3_INVALID_ARG, "%s: null argument", who);
+    if (C < 1 || C > 8192 || L < 1 || L > (1 << 22)) return set_err(Q3_INVALID_ARG, "%s: bad shape (C 1..8192, L 1..2^22)", who);
+    if (y_front < 0 || y_elems < 0 || (size_t)y_elems < (size_t)y_front + (size_t)C * L) return set_err(Q3_INVALID_ARG, "%s: y must hold y_front + C * L floats", who);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_norm_c(int device, int layernorm, const float* x_host, const float* w_host, const float* b_host, int C, int L, float eps,
+                               float* y_host, int y_front, int y_elems) {
+    Q3C(check_cl_out("q3_norm_c", x_host, w_host, y_host, C, L, y_front, y_elems));
+    if (layernorm && !b_host) return set_err(Q3_INVALID_ARG, "q3_norm_c: LayerNorm needs a bias");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    float *x, *w, *b = nullptr, *y;
+    const size_t n = (size_t)C * L;
+    HIPC(pool.alloc(&x, n)); HIPC(pool.alloc(&w, (size_t)C)); HIPC(pool.alloc(&y, (size_t)y_elems));
+    HIPC(q3_hipMemcpy(x, x_host, n * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(w, w_host, (size_t)C * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(y, y_host, (size_t)y_elems * 4, hipMemcpyHostToDevice));
+    if (layernorm) { HIPC(pool.alloc(&b, (size_t)C)); HIPC(q3_hipMemcpy(b, b_host, (size_t)C * 4, hipMemcpyHostToDevice)); }
+    HIPC(q3_hipDeviceSynchronize());
+    if (layernorm) HIPC(launch_layernorm_c(x, w, b, y + y_front, C, L, eps, 0));
+    else HIPC(launch_rmsnorm_c(x, w, y + y_front, C, L, eps, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(y_host, y, (size_t)y_elems * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_dwconv7(int device, const float* x_host, const float* w_host, const float* b_host, int C, int L, float* y_host, int y_front,
+                                int y_elems) {
+    Q3C(check_cl_out("q3_dwconv7", x_host, w_host, y_host, C, L, y_front, y_elems));
+    if (!b_host) return set_err(Q3_INVALID_ARG, "q3_dwconv7: null argument");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    float *x, *w, *b, *y;
+    const size_t n = (size_t)C * L;
+    HIPC(pool.alloc(&x, n)); HIPC(pool.alloc(&w, (size_t)C * 7)); HIPC(pool.alloc(&b, (size_t)C)); HIPC(pool.alloc(&y, (size_t)y_elems));
+    HIPC(q3_hipMemcpy(x, x_host, n * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(w, w_host, (size_t)C * 7 * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(b, b_host, (size_t)C * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(y, y_host, (size_t)y_elems * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_dwconv7(x, w, b, y + y_front, C, L, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(y_host, y, (size_t)y_elems * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
 #ifdef Q3_TRACE
 // development builds only (not declared in include/q3tts.h): arm the per-node stamp buffer BEFORE the first
 // q3_session_generate (the captured graph keeps the slice pointers), then read the stamps of the last replayed frame.

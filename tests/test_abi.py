@@ -120,6 +120,25 @@ def test_no_cpu_fallback():
         assert e.status == 5
     else:
         raise AssertionError("q3_attn_step succeeded without a GPU")
+    for call, name in ((lambda: q.conv_ex(0, np.zeros((16, 8), np.float32), np.zeros((32, 16, 1), np.float32)), "q3_conv_ex"),
+                       (lambda: q.norm_c(np.zeros((16, 8), np.float32), np.ones(16, np.float32)), "q3_norm_c"),
+                       (lambda: q.dwconv7(np.zeros((16, 8), np.float32), np.zeros((16, 7), np.float32), np.zeros(16, np.float32)), "q3_dwconv7")):
+        try:
+            call()
+        except _lib.Q3Error as e:
+            assert e.status == 5, name
+        else:
+            raise AssertionError(f"{name} succeeded without a GPU")
+
+
+def test_conv_path_is_host_only():
+    """kernel selection of the conv family answers without a GPU: a code, its text, and 0 for what the launchers refuse"""
+    code = q.conv_path(96, 96, 4096, 7, 9)
+    assert code == 5 and q.conv_path_name(code).startswith("k_conv_bf16x3<96co x 128t, 3 waves")
+    assert q.conv_path(1, 96, 1920, 7) == 2 and q.conv_path(1, 96, 1920, 7, aligned16=False) == 1
+    assert q.conv_path(64, 16, 100, 9) == 0 and q.conv_path_name(0) == "none" and q.conv_path_name(-1) == "invalid"
+    assert q.resunit_path(96, 4096, 3) == 15 and q.resunit_path(96, 4096, 3, planes=2) == 15 + 256 and q.resunit_path(96, 4095, 3) == 0
+    assert ctypes.sizeof(_lib.CConvEx) == 16 * 4 + 16 * 8
 
 
 def test_speaker_language_tables():
@@ -189,6 +208,10 @@ def test_null_handles_return_status_not_crash():
         lambda: L.q3_linear_ex(0, ctypes.byref(_lib.CLinearEx())),
         lambda: L.q3_attn_step(0, None),
         lambda: L.q3_attn_step(0, ctypes.byref(_lib.CAttnStep())),
+        lambda: L.q3_conv_ex(0, None),
+        lambda: L.q3_conv_ex(0, ctypes.byref(_lib.CConvEx())),
+        lambda: L.q3_norm_c(0, 0, None, None, None, 16, 8, 1e-6, None, 0, 128),
+        lambda: L.q3_dwconv7(0, None, None, None, 16, 8, None, 0, 128),
     ]
     for k, f in enumerate(calls):
         st = f()
