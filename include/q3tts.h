@@ -648,6 +648,35 @@ q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_host, const
  * q3_batcher_read_out; q3_batcher_read_out serves every streamed ticket (24 kHz f32 by default). */
 q3_status q3_batcher_ticket_output(q3_batcher* b, int64_t ticket, uint32_t sample_rate, int format);
 q3_status q3_batcher_read_out(q3_batcher* b, int64_t ticket, void* out_host, size_t cap_samples, size_t* n_samples, int* done);
+/* ---------------- output stage: a speaking rate per row (time-scale modification in front of the resampler) ----------------
+ * tempo_permille in 500..2000 (1250: the speech runs 1.25 x as fast; else Q3_INVALID_ARG before the device is touched); 1000, the
+ * default, is off: such a row takes the path above and returns its bits. Otherwise the row's 24 kHz input x goes through WSOLA
+ * first: frames of W = 720 samples, one every Hs = 360 samples of the output y, frame k taken at p_k = a_k + lag_k with
+ * a_k = floor(k Hs tempo / 1000), p_0 = 0 and lag_k in [max(-240, -a_k), 240] the lag whose frame correlates best, normalised by its
+ * energy, with the continuation x[p_{k-1} + Hs ..] of the frame before (ties: the smallest |lag|, then the negative one; digital
+ * silence gives 0). y[k Hs + j] = w[Hs + j] x[p_{k-1} + Hs + j] + w[j] x[p_k + j] for j < Hs with the periodic Hann window w of W
+ * points, and y[j] = x[j] for j < Hs. f32 sums in an order that does not depend on how the input was cut into pushes.
+ * Streaming rule: after n input samples in total, the frames k with need_k <= n are computed (need_0 = W, need_k =
+ * max(a_k, a_{k-1} + Hs) + 240 + W) and frames x Hs samples of y are final; a push with `last` computes the frames up to
+ * ceil(N_out / Hs), N_out = floor((n 1000 + tempo / 2) / tempo), against zeros beyond the end and y is N_out samples long. The
+ * resampler takes y as its input stream: the counts and the edge rule above with N_out in the place of n_in. The stretcher's
+ * state obeys the same commit rule: a push that is refused or fails leaves the row where it was. Its buffers are allocated by a
+ * row's first tempo other than 1000. No reference counterpart (the reference returns whole clips at the model's own pace). */
+q3_status q3_pcm_stage_set_tempo(q3_pcm_stage* ps, int row, int tempo_permille);            /* also restarts the row; kept by _set / _reset */
+/* host only: the streaming rule — frames computed and samples of y final after n_in_total input samples (ended: after the flush) */
+q3_status q3_pcm_stage_tempo_count(int tempo_permille, size_t n_in_total, int ended, size_t* frames, size_t* samples_24k);
+/* host only: cap for a push of n_in new samples to a row at this rate and tempo, wherever the row stands and with `last` */
+q3_status q3_pcm_stage_bound_tempo(uint32_t sample_rate, int tempo_permille, size_t n_in, size_t* n_out_max);
+/* the lags of the frames k0 .. k0 + n - 1 the row's last successful push computed (n = 0: none; lags = NULL with
+ * cap = 0: the count alone; any other cap < n: Q3_INVALID_ARG, *n set) */
+q3_status q3_pcm_stage_tempo_lags(q3_pcm_stage* ps, int row, int64_t* k0, int* lags, size_t cap, size_t* n);
+/* Sessions: the tempo of row b's stage row (b = -1: every row) in q3_session_next_chunks_out; legal while the row has delivered no
+ * streamed sample since its start or its q3_session_replace (Q3_INVALID_ARG after, and then no row changes). The other chunk,
+ * decode and run calls ignore it, as they ignore q3_session_set_output. */
+q3_status q3_session_set_tempo(q3_session* s, int b, int tempo_permille);
+/* Batcher: a streamed ticket's tempo; the window and the read of q3_batcher_ticket_output (q3_batcher_read_out). A parked streamed
+ * ticket keeps its stage row. */
+q3_status q3_batcher_ticket_tempo(q3_batcher* b, int64_t ticket, int tempo_permille);
 /* codes_to_tensor (lib.rs:1417-1431): [n][16] u32 → [16][n] i64 (host helper) */
 void      q3_codes_to_tensor(const uint32_t* frames, int n_frames, int64_t* out);
 

@@ -129,6 +129,12 @@ SYMBOLS = {
                                   P(ctypes.c_size_t)]),
     "q3_pcm_stage_bound": (c_int, [ctypes.c_uint32, ctypes.c_size_t, P(ctypes.c_size_t)]),
     "q3_pcm_stage_taps": (c_int, [ctypes.c_uint32, c_void_p, ctypes.c_size_t, P(c_int), P(c_int)]),
+    "q3_pcm_stage_set_tempo": (c_int, [c_void_p, c_int, c_int]),
+    "q3_pcm_stage_tempo_count": (c_int, [c_int, ctypes.c_size_t, c_int, P(ctypes.c_size_t), P(ctypes.c_size_t)]),
+    "q3_pcm_stage_bound_tempo": (c_int, [ctypes.c_uint32, c_int, ctypes.c_size_t, P(ctypes.c_size_t)]),
+    "q3_pcm_stage_tempo_lags": (c_int, [c_void_p, c_int, P(ctypes.c_int64), c_void_p, ctypes.c_size_t, P(ctypes.c_size_t)]),
+    "q3_session_set_tempo": (c_int, [c_void_p, c_int, c_int]),
+    "q3_batcher_ticket_tempo": (c_int, [c_void_p, ctypes.c_int64, c_int]),
     "q3_codec_stream_push_out": (c_int, [c_void_p, c_int, P(c_int), P(c_void_p), P(c_int), c_void_p, P(c_int), P(c_int), P(c_void_p),
                                          P(ctypes.c_size_t), P(ctypes.c_size_t)]),
     "q3_session_set_output": (c_int, [c_void_p, ctypes.c_uint32, c_int]),

@@ -284,14 +284,26 @@ class Session:
         check(lib.q3_session_set_output(self._h, int(rate), PCM_S16 if pcm16 else PCM_F32))
         self._out = (int(rate), bool(pcm16))
 
+    def set_tempo(self, tempo_permille: int, b: int = -1):
+        """The speaking rate of row b (-1: every row) in `next_chunks_out` (q3_session_set_tempo): 500..2000 permille, 1250 = 1.25 x
+        as fast, 1000 = off. Legal while the row has streamed nothing since its start or its `replace`; the setting stays with the
+        row across a `replace` until it is set again."""
+        check(lib.q3_session_set_tempo(self._h, int(b), int(tempo_permille)))
+        t = getattr(self, "_tempo", None) or [1000] * self.B
+        for r in (range(self.B) if int(b) < 0 else [int(b)]):
+            t[r] = int(tempo_permille)
+        self._tempo = t
+
     def next_chunks_out(self) -> List[Tuple[Optional[AudioBuffer], bool]]:
         """`next_chunks` through the session's output stage (q3_session_next_chunks_out): one (chunk or None, done) per row, the
         chunks at the rate of `set_output`, int16 arrays when it asked for them. A row's last samples (the resampler holds 64
         input samples back) come in the call that reports it done."""
         B = self.B; spf = self.model.config.samples_per_frame
         rate, s16 = getattr(self, "_out", (24000, False))
-        cap = pcm_stage_bound(rate, max(self.options.chunk_frames, 1) * spf)
-        bufs = [np.zeros(cap, dtype=np.int16 if s16 else np.float32) for _ in range(B)]
+        tempo = getattr(self, "_tempo", None) or [1000] * B
+        n_in = max(self.options.chunk_frames, 1) * spf
+        cap = {t: pcm_stage_bound(rate, n_in, t) for t in set(tempo)}
+        bufs = [np.zeros(cap[tempo[b]], dtype=np.int16 if s16 else np.float32) for b in range(B)]
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data_as(ctypes.c_void_p) for b in bufs])
         caps = (ctypes.c_size_t * B)(*[b.size for b in bufs])
         n = (ctypes.c_size_t * B)(); d = (ctypes.c_int * B)()
@@ -509,22 +521,26 @@ class Batcher:
         check(lib.q3_batcher_submit(self._h, ctypes.byref(r), 1 if want_pcm else 0, ctypes.byref(t)))
         return int(t.value)
 
-    def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False) -> int:
+    def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False, tempo_permille: int = 1000) -> int:
         """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16: the
-        ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked."""
+        ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked.
+        tempo_permille: its speaking rate (q3_batcher_ticket_tempo; 1250 = 1.25 x as fast, 1000 = off)."""
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
         t = ctypes.c_int64()
         check(lib.q3_batcher_submit_streamed(self._h, ctypes.byref(r), ctypes.byref(t)))
         self._streamed.add(int(t.value))
-        self._set_output(int(t.value), sample_rate, pcm16)
+        self._set_output(int(t.value), sample_rate, pcm16, tempo_permille)
         return int(t.value)
 
-    def _set_output(self, ticket: int, sample_rate: int, pcm16: bool):
-        if int(sample_rate) == 24000 and not pcm16:
+    def _set_output(self, ticket: int, sample_rate: int, pcm16: bool, tempo_permille: int = 1000):
+        if int(sample_rate) == 24000 and not pcm16 and int(tempo_permille) == 1000:
             return
         try:
-            self.ticket_output(ticket, sample_rate, pcm16)
+            if int(sample_rate) != 24000 or pcm16:
+                self.ticket_output(ticket, sample_rate, pcm16)
+            if int(tempo_permille) != 1000:
+                self.ticket_tempo(ticket, tempo_permille)
         except _lib.Q3Error:
             self.cancel(ticket); self.fetch(ticket)      # the ticket was never run: it leaves with the refusal
             raise
@@ -536,6 +552,12 @@ class Batcher:
             self._output.pop(int(ticket), None)
         else:
             self._output[int(ticket)] = (int(sample_rate), bool(pcm16))
+
+    def ticket_tempo(self, ticket: int, tempo_permille: int):
+        """A streamed ticket's speaking rate (q3_batcher_ticket_tempo): between its submission and the next `step`."""
+        check(lib.q3_batcher_ticket_tempo(self._h, int(ticket), int(tempo_permille)))
+        if int(tempo_permille) != 1000:
+            self._output.setdefault(int(ticket), (24000, False))      # read through q3_batcher_read_out
 
     def submit_open(self, utt: Utterance, want: str = "stream", sample_rate: int = 24000, pcm16: bool = False) -> int:
         """Queue one request whose text arrives in pieces (`append_text`); the utterance carries the first ids. want: "stream"
@@ -1213,11 +1235,22 @@ def pcm_stage_taps(rate: int) -> Tuple[np.ndarray, int, int]:
     return t, L.value, M.value
 
 
-def pcm_stage_bound(rate: int, n_in: int) -> int:
-    """The most samples one push of n_in 24 kHz samples returns at `rate` (q3_pcm_stage_bound)."""
+def pcm_stage_bound(rate: int, n_in: int, tempo_permille: int = 1000) -> int:
+    """The most samples one push of n_in 24 kHz samples returns at `rate` (q3_pcm_stage_bound), for a row at tempo_permille
+    (q3_pcm_stage_bound_tempo)."""
     n = ctypes.c_size_t()
-    check(lib.q3_pcm_stage_bound(int(rate), int(n_in), ctypes.byref(n)))
+    if int(tempo_permille) == 1000:
+        check(lib.q3_pcm_stage_bound(int(rate), int(n_in), ctypes.byref(n)))
+    else:
+        check(lib.q3_pcm_stage_bound_tempo(int(rate), int(tempo_permille), int(n_in), ctypes.byref(n)))
     return int(n.value)
+
+
+def pcm_stage_tempo_count(tempo_permille: int, n_in_total: int, ended: bool = False) -> Tuple[int, int]:
+    """(frames computed, 24 kHz samples final) of the time stretcher after n_in_total input samples (q3_pcm_stage_tempo_count)."""
+    f = ctypes.c_size_t(); y = ctypes.c_size_t()
+    check(lib.q3_pcm_stage_tempo_count(int(tempo_permille), int(n_in_total), 1 if ended else 0, ctypes.byref(f), ctypes.byref(y)))
+    return int(f.value), int(y.value)
 
 
 class PcmStage:
@@ -1229,6 +1262,7 @@ class PcmStage:
         self.device_index = int(model) if isinstance(model, int) else int(model.device_index)
         self.rows = int(rows); self.max_push_samples = int(max_push_samples)
         self._fmt = [(24000, False)] * self.rows
+        self._tempo = [1000] * self.rows
         self._h = ctypes.c_void_p()
         check(lib.q3_pcm_stage_create(self.device_index, self.rows, self.max_push_samples, ctypes.byref(self._h)))
 
@@ -1236,6 +1270,20 @@ class PcmStage:
         """Row's output rate and format; also restarts the row."""
         check(lib.q3_pcm_stage_set(self._h, int(row), int(rate), PCM_S16 if pcm16 else PCM_F32))
         self._fmt[int(row)] = (int(rate), bool(pcm16))
+
+    def set_tempo(self, row: int, tempo_permille: int):
+        """Row's speaking rate (q3_pcm_stage_set_tempo): 500..2000 permille, 1250 = 1.25 x as fast, 1000 = off; also restarts the
+        row. `set` and `reset` keep it."""
+        check(lib.q3_pcm_stage_set_tempo(self._h, int(row), int(tempo_permille)))
+        self._tempo[int(row)] = int(tempo_permille)
+
+    def tempo_lags(self, row: int) -> Tuple[int, np.ndarray]:
+        """(k0, lags) of the frames k0 .. the row's last successful push computed (q3_pcm_stage_tempo_lags)."""
+        k0 = ctypes.c_int64(); n = ctypes.c_size_t()
+        check(lib.q3_pcm_stage_tempo_lags(self._h, int(row), ctypes.byref(k0), None, 0, ctypes.byref(n)))      # the count
+        lags = np.zeros(int(n.value), np.int32)
+        check(lib.q3_pcm_stage_tempo_lags(self._h, int(row), ctypes.byref(k0), lags.ctypes.data_as(ctypes.c_void_p), lags.size, ctypes.byref(n)))
+        return int(k0.value), lags
 
     def reset(self, row: int):
         check(lib.q3_pcm_stage_reset(self._h, int(row)))
@@ -1247,7 +1295,7 @@ class PcmStage:
         return np.int16 if self._fmt[int(row)][1] else np.float32
 
     def bound(self, row: int, n_in: int) -> int:
-        return pcm_stage_bound(self._fmt[int(row)][0], n_in)
+        return pcm_stage_bound(self._fmt[int(row)][0], n_in, self._tempo[int(row)])
 
     def push(self, samples: dict, last=()) -> dict:
         """{row: 24 kHz f32 samples} -> {row: samples at the row's rate and format}, every row in one pass; rows in `last` are
@@ -1277,15 +1325,18 @@ class PcmStage:
     __del__ = close
 
 
-def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0) -> AudioBuffer:
+def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_permille: int = 1000) -> AudioBuffer:
     """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked — what a caller
-    of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their result."""
+    of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their result. tempo_permille: the clip's speaking
+    rate (1250 = 1.25 x as fast, 1000 = as it is)."""
     x = np.ascontiguousarray(audio.samples if isinstance(audio, AudioBuffer) else audio, dtype=np.float32).reshape(-1)
     if isinstance(audio, AudioBuffer) and audio.sample_rate != 24000:
         raise ValueError(f"resample_gpu takes the engine's 24 kHz audio, not {audio.sample_rate} Hz")
     ps = PcmStage(int(device), 1, max(x.size, 1))
     try:
         ps.set(0, rate, pcm16)
+        if int(tempo_permille) != 1000:
+            ps.set_tempo(0, tempo_permille)
         return AudioBuffer(ps.push({0: x}, last=(0,))[0], int(rate))
     finally:
         ps.close()

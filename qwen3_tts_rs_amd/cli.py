@@ -56,6 +56,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--output-rate", type=int, default=24000, metavar="HZ",
                     help="with --streaming: the chunks leave through the output stage at this sample rate (8000, 16000, 44100, 48000, ...); "
                          "the WAV header carries it")
+    ap.add_argument("--tempo", type=float, default=1.0, metavar="X",
+                    help="with --streaming: the speaking rate, 0.5 .. 2.0 (1.25 = 1.25 x as fast), applied by the output stage's time "
+                         "stretcher as the chunks leave")
     ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
                     help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
                          "first token to the first audio; writes the same WAV as without the flag)")
@@ -252,11 +255,17 @@ def main(argv=None) -> int:
     if a.output_rate != 24000 and not a.streaming:
         print("error: --output-rate applies to --streaming (resample a whole utterance with api.resample_gpu)", file=sys.stderr)
         return 2
-    if a.streaming and a.output_rate != 24000:
+    tempo = int(round(a.tempo * 1000.0))
+    if tempo != 1000 and not a.streaming:
+        print("error: --tempo applies to --streaming (stretch a whole utterance with api.resample_gpu(..., tempo_permille=))", file=sys.stderr)
+        return 2
+    if a.streaming and (a.output_rate != 24000 or tempo != 1000):
         # the chunks of the streaming session, each through the session's output stage as it leaves
         s = model.session([utt], opts)
         try:
             s.set_output(a.output_rate)
+            if tempo != 1000:
+                s.set_tempo(tempo)
         except api._lib.Q3Error as e:
             print(f"error: {e}", file=sys.stderr)
             return 2

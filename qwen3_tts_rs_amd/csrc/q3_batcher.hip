@@ -177,7 +177,7 @@ struct BatTicket {
     // A streamed ticket's own output (q3_batcher_ticket_output; host thread, fixed before the step that follows `born`). o_conv: other
     // than 24 kHz f32 — its samples go through the worker's output stage and land, as bytes of that format, in sout (under the
     // worker's mutex, like spcm, which stays empty) and leave through q3_batcher_read_out alone.
-    long born = 0; uint32_t o_rate = 24000; int o_fmt = Q3_PCM_F32; bool o_conv = false;
+    long born = 0; uint32_t o_rate = 24000; int o_fmt = Q3_PCM_F32; bool o_conv = false; int o_tempo = 1000;      // (q3_batcher_ticket_tempo: the stage too)
     std::vector<char> sout; size_t o_read = 0;
     size_t o_bytes() const { return o_fmt == Q3_PCM_S16 ? 2 : 4; }
     // Parking (q3_batcher_set_parking; host thread). rec: the ticket's row as a record while it reads PARKED; want_in: it
@@ -355,6 +355,7 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
                 q3_status so = Q3_OK;
                 if (!d.ps) so = q3_pcm_stage_create(m->device, b->stream_rows(), (size_t)std::min(b->frame_budget + b->prompt_budget, 100000) * spf, &d.ps);
                 if (so == Q3_OK) so = q3_pcm_stage_set(d.ps, p.row, t.o_rate, t.o_fmt);
+                if (so == Q3_OK) so = q3_pcm_stage_set_tempo(d.ps, p.row, t.o_tempo);      // (1000 too: the row may have had another ticket's)
                 if (so != Q3_OK) fail(t, so, q3_last_error());
             }
             if (is_failed(t)) continue;
@@ -1238,7 +1239,21 @@ extern "C" q3_status q3_batcher_ticket_output(q3_batcher* b, int64_t ticket, uin
     Q3C(q3_pcm_stage_taps(sample_rate, nullptr, 0, nullptr, nullptr));
     if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
         return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: ticket %lld has been through a step: its output is set between its submission and the next q3_batcher_step", (long long)ticket);
-    t.o_rate = sample_rate; t.o_fmt = format; t.o_conv = sample_rate != 24000 || format != Q3_PCM_F32;
+    t.o_rate = sample_rate; t.o_fmt = format; t.o_conv = sample_rate != 24000 || format != Q3_PCM_F32 || t.o_tempo != 1000;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_ticket_tempo(q3_batcher* b, int64_t ticket, int tempo_permille) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: ticket %lld was not submitted as streamed", (long long)ticket);
+    if (tempo_permille < 500 || tempo_permille > 2000)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: tempo %d permille out of range (500..2000; 1000 = off)", tempo_permille);
+    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: ticket %lld has been through a step: its tempo is set between its submission and the next q3_batcher_step", (long long)ticket);
+    t.o_tempo = tempo_permille; t.o_conv = t.o_rate != 24000 || t.o_fmt != Q3_PCM_F32 || tempo_permille != 1000;
     return Q3_OK;
 }
 

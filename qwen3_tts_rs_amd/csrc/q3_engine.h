@@ -4,7 +4,8 @@
 //   q3_prefix_cache.hip the prefix cache: prefilled instruct pages shared across requests (q3_prefix_cache.h)
 //   q3_codec_run.hip device-memory cache, the vocoder pipeline (codec_decode_dev) and q3_decode_codes
 //   q3_codec_stream.hip the codec stream: the vocoder with per-row state, many rows per pass
-//   q3_pcm_stage.hip the output stage: per-row resampling to a requested rate and f32 / PCM16 conversion
+//   q3_pcm_stage.hip the output stage: per-row resampling to a requested rate and f32 / PCM16 conversion, and a
+//                    speaking rate per row by time-scale modification in front of it
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
 //                    streaming chunks, q3_session_run / decode / get
 //   q3_batcher.hip   continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
@@ -460,6 +461,7 @@ struct q3_session {
     // q3_session_next_chunks_out: the session's output (q3_session_set_output) and its stage, one row per session row (created on
     // the first such call: out_started, after which the setting is fixed)
     q3_pcm_stage* ostage = nullptr; uint32_t out_rate = 24000; int out_fmt = Q3_PCM_F32; bool out_started = false;
+    std::vector<int> out_tempo;           // q3_session_set_tempo: per row, permille (empty: every row at 1000)
     // overlapped segment decode (q3_session_run): vocoder segments run on their own stream while the frame loop continues
     hipStream_t dec_stream = nullptr; hipEvent_t dec_ev = nullptr;
     std::vector<CodecWS> par_ws; std::vector<hipStream_t> par_streams;     // q3_session_run: utterances vocoded side by side
@@ -537,7 +539,19 @@ struct PsDesc {
     int n_new, n_out, L, M, fmt, pad;
 };
 // a checked push: descriptors of the rows that run, per segment the byte offset into the stage's staging buffer and the samples
-struct PsPlan { std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t bytes = 0; int max_tiles = 1; };
+// one row of a pass of k_tempo (device-visible, 8-byte aligned): the row's stream is hist_in (from sample hist_lo on) below
+// `base`, the n_new samples of src from there, zeros from n_total on; frames k0 .. k1 - 1 run, n_y samples of y come out
+struct TpDesc {
+    const float* src; const float* hist_in; float* hist_out; const long long* p_in; long long* p_out; int* lags; float* y; const float* win;
+    long long base, n_total, hist_lo, lo_next, k0, k1;
+    int n_new, n_y, tempo, pad;
+};
+// (tdesc, t_y, t_k1: the time stretcher in front, DESIGN 4.12a — the rows at a tempo other than 1000, per segment the y samples of
+// this push and the frame the row reaches; pcm_stage_launch uploads tdesc itself, into the stage's own buffer)
+struct PsPlan {
+    std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t bytes = 0; int max_tiles = 1;
+    q3_pcm_stage* ps = nullptr; std::vector<TpDesc> tdesc; std::vector<long long> t_y, t_k1;
+};
 Q3_HIDDEN int pcm_stage_rows(const q3_pcm_stage* ps);
 Q3_HIDDEN size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row);
 Q3_HIDDEN void pcm_stage_reset(q3_pcm_stage* ps, int row);

@@ -13,6 +13,13 @@
 //
 // One launch serves every row of a push: grid (output tile, row), a descriptor per row. A block stages its tile's input window
 // (kept tail | new samples | zeros) in LDS and computes one output per thread; tile 0 of a row also writes the row's next tail.
+//
+// In front of the resampler, for the rows that ask for it: a speaking rate. k_tempo stretches the row's 24 kHz
+// stream by WSOLA — frames of 720 samples every 360 of the output, each taken from where the input continues the frame before it
+// best within +-240 samples of its nominal place — into the row's part of a y buffer, which k_pcm_stage then takes as the row's
+// input. Which frames a push reaches follows from the sample counts alone (tempo_frames), so the host never reads a count back;
+// the row keeps the input the next frame can still touch and the last frame's position, in two copies flipped like the tails.
+// A row at tempo 1000 is not touched by any of it.
 #include "q3_engine.h"
 
 namespace {
@@ -72,6 +79,147 @@ __global__ __launch_bounds__(PS_TILE) void k_pcm_stage(const PsDesc* __restrict_
     else ((float*)d.out)[o0 + tid] = y;
 }
 
+// ---- the time stretcher ----
+constexpr int TP_W = 720, TP_HS = 360, TP_D = 240;             // frame, synthesis hop, search reach
+constexpr int TP_MIN = 500, TP_MAX = 2000, TP_OFF = 1000;       // tempo in permille; 1000: no stretcher
+constexpr int TP_LAGS = 2 * TP_D + 1;                           // 481 candidates
+constexpr int TP_THREADS = 256;                                 // 64 groups of 8 consecutive lags (61 in use) x the 4 interleaved sums
+constexpr int TP_SP = 1216;                                     // pitch of one copy of the search region: 8 * 60 + 4 * 180 + 8 <= 1216
+constexpr int TP_S_FLOATS = 3 * TP_SP + 36 + TP_SP;
+constexpr int TP_HIST = 2048;                                   // input a row keeps: < |a_k - a_{k-1} - Hs| + 2 * 240 + 720 <= 1561
+constexpr int TP_NONE = 9999;                                   // no candidate yet
+
+__device__ inline bool tp_better(float s1, int d1, float s2, int d2) {
+    if (s1 > s2) return true;
+    if (!(s1 == s2)) return false;
+    const int a1 = d1 < 0 ? -d1 : d1, a2 = d2 < 0 ? -d2 : d2;
+    return a1 < a2 || (a1 == a2 && d1 < d2);                    // ties: the smallest |lag|, then the negative one
+}
+
+// One workgroup per row; the row's frames k0 .. k1 - 1 in order (frame k's template is the continuation of frame k - 1).
+// Thread (g, m) = (tid >> 2, tid & 3) owns lags 8g .. 8g + 7 and the partial sums over j = m (mod 4): per step of j one
+// float4 of the search region (a sliding window of 8) and a quarter float4 of the template feed 16 FMAs. The four partial
+// sums meet by two quad shuffles in the order (s0 + s1) + (s2 + s3): the order of the sums does not depend on how the
+// input was cut into pushes. Copy m of the search region is shifted by m samples, so that every window is 16-byte aligned;
+// the copies start at banks 0 / 4 / 32 / 36, so that the 16 lanes of one LDS pass read 64 different banks.
+__global__ __launch_bounds__(TP_THREADS) void k_tempo(const TpDesc* __restrict__ descs) {
+    __shared__ __attribute__((aligned(16))) float Tt[TP_W];           // template, transposed: Tt[m * 180 + i] = T[m + 4 i]
+    __shared__ __attribute__((aligned(16))) float Sc[TP_S_FLOATS];    // copy m at sbase(m): Sc[sbase(m) + i] = x[a_k - 240 + i + m]
+    __shared__ float red_s[TP_THREADS / 64]; __shared__ int red_d[TP_THREADS / 64];
+    const TpDesc d = descs[blockIdx.x];
+    const int tid = threadIdx.x, m = tid & 3, g = tid >> 2;
+    auto sbase = [](int mm) { return mm * TP_SP + ((mm & 1) ? 4 : 0) + ((mm & 2) ? 32 : 0); };
+    auto x_at = [&](long long q) -> float {
+        if (q < 0 || q >= d.n_total) return 0.0f;
+        if (q >= d.base) return d.src[q - d.base];
+        const long long h = q - d.hist_lo;
+        return (h >= 0 && h < TP_HIST && d.hist_in) ? d.hist_in[h] : 0.0f;
+    };
+    const long long y_base = d.k0 * TP_HS;
+    long long p_prev = (d.k0 > 0 && d.p_in) ? d.p_in[0] : 0;
+    for (long long k = d.k0; k < d.k1; ++k) {
+        if (k == 0) {                                                // frame 0: its first half as it is
+            for (int j = tid; j < TP_HS; j += TP_THREADS) if (j < d.n_y) d.y[j] = x_at(j);
+            if (tid == 0) d.lags[0] = 0;
+            p_prev = 0;
+            continue;
+        }
+        const long long a = (k * TP_HS * (long long)d.tempo) / 1000;
+        __syncthreads();                                             // (the frame before has read its LDS)
+        for (int j = tid; j < TP_W; j += TP_THREADS) Tt[(j & 3) * (TP_W / 4) + (j >> 2)] = x_at(p_prev + TP_HS + j);
+        for (int i = tid; i < TP_SP + 3; i += TP_THREADS) {
+            const float v = i < TP_W + 2 * TP_D ? x_at(a - TP_D + i) : 0.0f;
+#pragma unroll
+            for (int mm = 0; mm < 4; ++mm) if (i - mm >= 0 && i - mm < TP_SP) Sc[sbase(mm) + i - mm] = v;
+        }
+        __syncthreads();
+        float bs = -INFINITY; int bd = TP_NONE;
+        if (g * 8 < TP_LAGS) {
+            float c[8], e[8], w[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) c[u] = e[u] = 0.0f;
+            const float4* S4 = (const float4*)(Sc + sbase(m)) + 2 * g;
+            const float4* T4 = (const float4*)(Tt + m * (TP_W / 4));
+            { const float4 lo = S4[0], hi = S4[1]; w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w; w[4] = hi.x; w[5] = hi.y; w[6] = hi.z; w[7] = hi.w; }
+            for (int ib = 0; ib < TP_W / 16; ++ib) {
+                const float4 t4 = T4[ib];
+                const float tq[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 nx = S4[4 * ib + q + 2];            // (the last one is read and not used: inside the copy's pitch)
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { c[u] = fmaf(w[u], tq[q], c[u]); e[u] = fmaf(w[u], w[u], e[u]); }
+                    w[0] = w[4]; w[1] = w[5]; w[2] = w[6]; w[3] = w[7]; w[4] = nx.x; w[5] = nx.y; w[6] = nx.z; w[7] = nx.w;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                c[u] = q3::add_rn(c[u], __shfl_xor(c[u], 1)); c[u] = q3::add_rn(c[u], __shfl_xor(c[u], 2));
+                e[u] = q3::add_rn(e[u], __shfl_xor(e[u], 1)); e[u] = q3::add_rn(e[u], __shfl_xor(e[u], 2));
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if ((u >> 1) != m) continue;                         // each lane of the quad scores two of the eight
+                const int lag = g * 8 + u - TP_D;
+                if (lag > TP_D || (long long)lag < -a) continue;
+                const float sc = e[u] > 0.0f ? __fdiv_rn(c[u], __fsqrt_rn(e[u])) : 0.0f;
+                if (tp_better(sc, lag, bs, bd)) { bs = sc; bd = lag; }
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float os = __shfl_xor(bs, o); const int od = __shfl_xor(bd, o);
+            if (tp_better(os, od, bs, bd)) { bs = os; bd = od; }
+        }
+        if ((tid & 63) == 0) { red_s[tid >> 6] = bs; red_d[tid >> 6] = bd; }
+        __syncthreads();
+        bs = red_s[0]; bd = red_d[0];
+#pragma unroll
+        for (int v = 1; v < TP_THREADS / 64; ++v) if (tp_better(red_s[v], red_d[v], bs, bd)) { bs = red_s[v]; bd = red_d[v]; }
+        if (bd == TP_NONE) bd = 0;                                   // (every score a NaN)
+        // overlap-add: the second half of the frame before (the template's first half) under the window's second half, the
+        // first half of this frame under its first: two products and one sum, each rounded once
+        for (int j = tid; j < TP_HS; j += TP_THREADS) {
+            const long long idx = k * TP_HS + j - y_base;
+            if (idx < d.n_y)
+                d.y[idx] = q3::add_rn(q3::mul_rn(d.win[TP_HS + j], Tt[(j & 3) * (TP_W / 4) + (j >> 2)]), q3::mul_rn(d.win[j], Sc[bd + TP_D + j]));
+        }
+        if (tid == 0) d.lags[k - d.k0] = bd;
+        p_prev = a + bd;
+    }
+    if (tid == 0) d.p_out[0] = p_prev;
+    // what the next frame can still touch, for the next push
+    if (d.hist_out) {
+        const long long n = d.n_total - d.lo_next;
+        for (long long i = tid; i < n && i < TP_HIST; i += TP_THREADS) d.hist_out[i] = x_at(d.lo_next + i);
+    }
+}
+
+// a_k = floor(k * Hs * t / 1000)
+inline long long tp_a(long long k, int t) { return (long long)(((__int128)k * TP_HS * t) / 1000); }
+inline long long tp_need(long long k, int t) { return k == 0 ? TP_W : std::max(tp_a(k, t), tp_a(k - 1, t) + TP_HS) + TP_D + TP_W; }
+// the first input sample frame k can touch
+inline long long tp_lo(long long k, int t) { return k == 0 ? 0 : std::max<long long>(0, std::min(tp_a(k, t), tp_a(k - 1, t) + TP_HS) - TP_D); }
+// The streaming rule: after n input samples the frames with need_k <= n are computed and frames * Hs samples of y are final;
+// once the input has ended, the frames up to ceil(N_out / Hs) are, and y is N_out = floor((n * 1000 + t / 2) / t) samples long.
+void tempo_frames(int t, long long n, bool ended, long long* frames, long long* samples) {
+    if (ended) {
+        const long long n_out = (long long)(((__int128)n * 1000 + t / 2) / t);
+        *frames = (n_out + TP_HS - 1) / TP_HS; *samples = n_out;
+        return;
+    }
+    long long f = 0;
+    if (n >= TP_W) {
+        // need_k >= k * Hs * t / 1000 - 1 + 960 and <= k * Hs * t / 1000 + 1320: an estimate from below, then single steps
+        f = std::max<long long>(1, (long long)(((__int128)(n - TP_W - TP_D - TP_HS) * 1000) / ((long long)TP_HS * t)));
+        while (f > 1 && tp_need(f - 1, t) > n) --f;
+        while (tp_need(f, t) <= n) ++f;
+    }
+    *frames = f; *samples = f * TP_HS;
+}
+// the most y samples one push of n new input samples adds, at any place of the stream and with `last`
+size_t tempo_y_bound(int t, size_t n) { return (size_t)((((__int128)n + TP_W + TP_D + TP_HS) * 1000 + t - 1) / t) + 1; }
+
 struct Rate { int L = 1, M = 1; };
 bool rate_of(uint32_t sr, Rate* r) {
     if (sr < PS_RATE_MIN || sr > PS_RATE_MAX) return false;
@@ -118,7 +266,14 @@ struct PsRow {
     long long n_in = 0, n_out = 0;            // input samples consumed, output samples emitted
     int cur = 0; bool fresh = true;           // which of the two tail buffers holds the last 128 inputs; fresh: none yet (zeros)
     bool ended = false;                       // flushed by a push with `last`: restarted by set / reset only
+    // the time stretcher in front (tempo != 1000: n_in then counts its output y, the resampler's input)
+    int tempo = TP_OFF;
+    long long t_in = 0, t_frames = 0;         // 24 kHz samples consumed, frames computed
+    char* t_state = nullptr; int t_cur = 0;   // on the device, two copies: [last frame's position (16 bytes) | TP_HIST floats of input]
+    int* t_lags[2] = {nullptr, nullptr}; size_t t_lag_cap[2] = {0, 0};      // the lags of a push, two buffers: t_lag_cur holds the last successful push's
+    int t_lag_cur = 0; long long t_lag_k0 = 0, t_lag_n = 0;
 };
+constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
 struct q3_pcm_stage {
     int device = 0, R = 0; size_t max_push = 0;
     hipStream_t st = nullptr;
@@ -127,6 +282,10 @@ struct q3_pcm_stage {
     float* tails = nullptr;                                    // [R][2][128]
     char *out_dev = nullptr, *out_host = nullptr; size_t out_cap = 0;      // converted samples of a push: device, pinned host
     char *in_dev = nullptr, *in_host = nullptr; size_t in_cap = 0;         // q3_pcm_stage_push: descriptors | the rows' new samples
+    // the time stretcher (all of it allocated by the first row at a tempo other than 1000, or the first push of one)
+    float* t_win = nullptr;                                                // the Hann window, 720 floats
+    float* y_dev = nullptr; size_t y_cap = 0;                              // the stretched samples of a push, row after row: the resampler's input
+    char *td_dev = nullptr, *td_host = nullptr; size_t td_cap = 0;         // k_tempo's descriptors
 };
 
 extern "C" q3_status q3_pcm_stage_taps(uint32_t sample_rate, float* taps_host, size_t cap_floats, int* L, int* M) {
@@ -151,6 +310,28 @@ extern "C" q3_status q3_pcm_stage_bound(uint32_t sample_rate, size_t n_in, size_
     return Q3_OK;
 }
 
+static q3_status tempo_checked(const char* who, int tempo) {
+    if (tempo >= TP_MIN && tempo <= TP_MAX) return Q3_OK;
+    return set_err(Q3_INVALID_ARG, "%s: tempo %d permille out of range (%d..%d; %d = off)", who, tempo, TP_MIN, TP_MAX, TP_OFF);
+}
+
+extern "C" q3_status q3_pcm_stage_tempo_count(int tempo_permille, size_t n_in_total, int ended, size_t* frames, size_t* samples_24k) {
+    Q3C(tempo_checked("q3_pcm_stage_tempo_count", tempo_permille));
+    if (n_in_total > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_count: n_in_total above 2^48");
+    long long f = 0, y = 0;
+    tempo_frames(tempo_permille, (long long)n_in_total, ended != 0, &f, &y);
+    if (frames) *frames = (size_t)f;
+    if (samples_24k) *samples_24k = (size_t)y;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_bound_tempo(uint32_t sample_rate, int tempo_permille, size_t n_in, size_t* n_out_max) {
+    Q3C(tempo_checked("q3_pcm_stage_bound_tempo", tempo_permille));
+    if (n_in > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_tempo: n_in above 2^48");
+    // the resampler's cap for the most y samples the push can add (tempo_y_bound): its rule holds with N_out in the place of n_in
+    return q3_pcm_stage_bound(sample_rate, tempo_permille == TP_OFF ? n_in : tempo_y_bound(tempo_permille, n_in), n_out_max);
+}
+
 extern "C" q3_status q3_pcm_stage_create(int device, int rows, size_t max_push_samples, q3_pcm_stage** out) {
     if (!out || rows < 1 || max_push_samples < 1) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_create: rows and max_push_samples must be positive");
     if (device < 0) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_create: no device (a manifest-only model has none): the stage runs on the GPU");
@@ -170,6 +351,9 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
     if (ps->st) (void)hipStreamSynchronize(ps->st);
     for (auto& kv : ps->taps) dev_free(kv.second);
     dev_free(ps->tails); dev_free(ps->out_dev); dev_free(ps->in_dev);
+    for (PsRow& r : ps->rows) { dev_free(r.t_state); dev_free(r.t_lags[0]); dev_free(r.t_lags[1]); }
+    dev_free(ps->t_win); dev_free(ps->y_dev); dev_free(ps->td_dev);
+    if (ps->td_host) (void)hipHostFree(ps->td_host);
     if (ps->out_host) (void)hipHostFree(ps->out_host);
     if (ps->in_host) (void)hipHostFree(ps->in_host);
     if (ps->st) (void)hipStreamDestroy(ps->st);
@@ -181,6 +365,7 @@ size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row) { return fmt_byte
 void pcm_stage_reset(q3_pcm_stage* ps, int row) {
     PsRow& r = ps->rows[(size_t)row];
     r.n_in = r.n_out = 0; r.cur = 0; r.fresh = true; r.ended = false;
+    r.t_in = r.t_frames = 0; r.t_lag_k0 = r.t_lag_n = 0;
 }
 
 extern "C" q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row) {
@@ -215,18 +400,88 @@ extern "C" q3_status q3_pcm_stage_set(q3_pcm_stage* ps, int row, uint32_t sample
     return Q3_OK;
 }
 
+extern "C" q3_status q3_pcm_stage_set_tempo(q3_pcm_stage* ps, int row, int tempo_permille) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_tempo: bad row");
+    Q3C(tempo_checked("q3_pcm_stage_set_tempo", tempo_permille));      // (before the device is touched)
+    PsRow& r = ps->rows[(size_t)row];
+    if (tempo_permille != TP_OFF) {
+        HIPC(hipSetDevice(ps->device));
+        if (!ps->t_win) {
+            // periodic Hann, built in f64
+            std::vector<float> w((size_t)TP_W);
+            for (int j = 0; j < TP_W; ++j) w[(size_t)j] = (float)(0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * (double)j / (double)TP_W));
+            float* d = nullptr;
+            if (dev_malloc((void**)&d, w.size() * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "q3_pcm_stage_set_tempo: window"); }
+            const hipError_t e = q3_hipMemcpy(d, w.data(), w.size() * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "q3_pcm_stage_set_tempo: window upload: %s", hipGetErrorString(e)); }
+            ps->t_win = d;
+        }
+        if (!r.t_state && dev_malloc((void**)&r.t_state, 2 * TP_STATE_BYTES) != hipSuccess) {
+            (void)hipGetLastError(); r.t_state = nullptr;
+            return set_err(Q3_OOM, "q3_pcm_stage_set_tempo: state of row %d", row);
+        }
+    }
+    r.tempo = tempo_permille;
+    pcm_stage_reset(ps, row);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_tempo_lags(q3_pcm_stage* ps, int row, int64_t* k0, int* lags, size_t cap, size_t* n) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: bad row");
+    if (!n) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: null argument");
+    const PsRow& r = ps->rows[(size_t)row];
+    *n = (size_t)r.t_lag_n;
+    if (k0) *k0 = (int64_t)r.t_lag_k0;
+    if (r.t_lag_n == 0 || (!lags && cap == 0)) return Q3_OK;      // (no buffer: the count alone)
+    if (!lags || cap < (size_t)r.t_lag_n) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: %lld lags, the buffer takes %zu", r.t_lag_n, cap);
+    HIPC(hipSetDevice(ps->device));
+    HIPC(q3_hipMemcpy(lags, r.t_lags[r.t_lag_cur], (size_t)r.t_lag_n * sizeof(int), hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+// what a row has emitted once n more 24 kHz samples have arrived: through the stretcher first, where the row has one
+// (y: the stretched samples by then, k1: the frames)
+static long long row_emitted(const PsRow& r, size_t n, bool last, long long* y = nullptr, long long* k1 = nullptr) {
+    long long in_total = r.n_in + (long long)n;
+    if (r.tempo != TP_OFF) {
+        long long f = 0;
+        tempo_frames(r.tempo, r.t_in + (long long)n, last, &f, &in_total);
+        if (f < r.t_frames) f = r.t_frames;
+        if (k1) *k1 = f;
+    }
+    if (y) *y = in_total;
+    return emitted(r.sr, r.r, in_total, last);
+}
+static q3_status dev_grow(q3_pcm_stage* ps, void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return Q3_OK;
+    HIPC(hipSetDevice(ps->device));
+    dev_free(*p); *p = nullptr; *cap = 0;
+    HIPC(dev_malloc(p, bytes * 2));
+    *cap = bytes * 2;
+    return Q3_OK;
+}
+
 // Checks a push (every row at most once and in range — the entry points' business —, n within max_push_samples, no samples for a
 // row that was flushed), lays the rows' outputs out in the staging buffer (16-byte aligned each) and writes the descriptors.
-// Changes no row. The staging buffers may be reallocated: no push is in flight (each ends with a wait).
+// Changes no row. The staging buffers (and a row's lag buffer that is not the current one) may be reallocated: no push is in
+// flight (each ends with a wait). Rows with a tempo get their stretcher's descriptor and their part of the y buffer here too.
 q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan) {
     plan.desc.clear(); plan.off.assign(segs.size(), 0); plan.count.assign(segs.size(), 0); plan.bytes = 0; plan.max_tiles = 1;
+    plan.ps = ps; plan.tdesc.clear(); plan.t_y.assign(segs.size(), 0); plan.t_k1.assign(segs.size(), 0);
+    std::vector<size_t> y_off(segs.size(), 0); size_t y_floats = 0;
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
         if (sg.n > ps->max_push) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, ps->max_push);
         if (r.ended && sg.n > 0) return set_err(Q3_INVALID_ARG, "pcm stage: row %d was flushed (last): q3_pcm_stage_reset or _set restarts it", sg.row);
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
-        const long long total = emitted(r.sr, r.r, r.n_in + (long long)sg.n, sg.last != 0);
+        long long y_total = 0, k1 = 0;
+        const long long total = row_emitted(r, sg.n, sg.last != 0, &y_total, &k1);
         plan.count[i] = (size_t)std::max<long long>(0, total - r.n_out);
+        if (r.tempo != TP_OFF) {
+            if (!r.t_state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tempo and no state", sg.row);
+            plan.t_y[i] = y_total - r.n_in; plan.t_k1[i] = k1;
+            y_off[i] = y_floats; y_floats += ((size_t)plan.t_y[i] + 3) & ~(size_t)3;
+        }
         plan.off[i] = plan.bytes;
         plan.bytes = (plan.bytes + plan.count[i] * fmt_bytes(r.fmt) + 15) & ~(size_t)15;
     }
@@ -239,12 +494,30 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
         HIPC(hipHostMalloc((void**)&ps->out_host, plan.bytes * 2, hipHostMallocDefault));
         ps->out_cap = plan.bytes * 2;
     }
+    if (y_floats > 0) Q3C(dev_grow(ps, (void**)&ps->y_dev, &ps->y_cap, y_floats * 4));
     for (size_t i = 0; i < segs.size(); ++i) {
-        const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
+        const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row];
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
+        if (r.tempo != TP_OFF) {
+            // (the buffer that is written is the one the last successful push did not write: its lags stay readable)
+            const int lw = r.t_lag_cur ^ 1; const long long nk = plan.t_k1[i] - r.t_frames;
+            if (nk > 0) { size_t cap_b = r.t_lag_cap[lw]; Q3C(dev_grow(ps, (void**)&r.t_lags[lw], &cap_b, (size_t)nk * sizeof(int))); r.t_lag_cap[lw] = cap_b; }
+        }
         float* tails = ps->tails + (size_t)sg.row * 2 * PS_TAPS;
         PsDesc d{};
         d.src = sg.dev; d.n_new = (int)sg.n; d.n_out = (int)plan.count[i]; d.out = ps->out_dev + plan.off[i];
+        if (r.tempo != TP_OFF) {
+            char* in = r.t_state + (size_t)r.t_cur * TP_STATE_BYTES; char* out = r.t_state + (size_t)(r.t_cur ^ 1) * TP_STATE_BYTES;
+            TpDesc t{};
+            t.src = sg.dev; t.hist_in = r.t_in > 0 ? (const float*)(in + 16) : nullptr; t.hist_out = sg.last ? nullptr : (float*)(out + 16);
+            t.p_in = (const long long*)in; t.p_out = (long long*)out; t.lags = r.t_lags[r.t_lag_cur ^ 1];
+            t.y = ps->y_dev + y_off[i]; t.win = ps->t_win;
+            t.base = r.t_in; t.n_total = r.t_in + (long long)sg.n; t.hist_lo = tp_lo(r.t_frames, r.tempo); t.lo_next = tp_lo(plan.t_k1[i], r.tempo);
+            t.k0 = r.t_frames; t.k1 = plan.t_k1[i]; t.n_new = (int)sg.n; t.n_y = (int)plan.t_y[i]; t.tempo = r.tempo;
+            if (!sg.last && t.n_total - t.lo_next > TP_HIST) return set_err(Q3_INVALID_ARG, "pcm stage: row %d would keep %lld samples", sg.row, t.n_total - t.lo_next);
+            plan.tdesc.push_back(t);
+            d.src = t.y; d.n_new = t.n_y;                             // the resampler's input: the stretched samples
+        }
         d.base = r.n_in; d.i0 = r.n_out; d.L = r.r.L; d.M = r.r.M; d.fmt = r.fmt; d.taps = r.taps;
         if (r.taps) { d.tail_in = r.fresh ? nullptr : tails + (size_t)r.cur * PS_TAPS; d.tail_out = tails + (size_t)(r.cur ^ 1) * PS_TAPS; }
         plan.max_tiles = std::max(plan.max_tiles, (d.n_out + PS_TILE - 1) / PS_TILE);
@@ -255,6 +528,27 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
 // the one launch of a push: descriptors (plan.desc, uploaded by the caller) on the device
 hipError_t pcm_stage_launch(const PsDesc* desc_dev, const PsPlan& plan, hipStream_t st) {
     if (plan.desc.empty()) return hipSuccess;
+    if (!plan.tdesc.empty()) {
+        // the stretcher's rows first: its descriptors go up from the stage's own pinned buffer (no push is in flight: each ends
+        // with a wait), one workgroup per row
+        q3_pcm_stage* ps = plan.ps;
+        const size_t tb = plan.tdesc.size() * sizeof(TpDesc);
+        if (tb > ps->td_cap) {
+            dev_free(ps->td_dev); ps->td_dev = nullptr;
+            if (ps->td_host) { (void)hipHostFree(ps->td_host); ps->td_host = nullptr; }
+            ps->td_cap = 0;
+            hipError_t e = dev_malloc((void**)&ps->td_dev, tb * 2);
+            if (e == hipSuccess) e = hipHostMalloc((void**)&ps->td_host, tb * 2, hipHostMallocDefault);
+            if (e != hipSuccess) return e;
+            ps->td_cap = tb * 2;
+        }
+        memcpy(ps->td_host, plan.tdesc.data(), tb);
+        hipError_t e = hipMemcpyAsync(ps->td_dev, ps->td_host, tb, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_tempo, dim3((unsigned)plan.tdesc.size()), dim3(TP_THREADS), 0, st, (const TpDesc*)ps->td_dev);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(k_pcm_stage, dim3((unsigned)plan.max_tiles, (unsigned)plan.desc.size()), dim3(PS_TILE), 0, st, desc_dev);
     return hipGetLastError();
 }
@@ -263,7 +557,12 @@ void pcm_stage_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const Ps
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row];
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
-        r.n_in += (long long)sg.n; r.n_out += (long long)plan.count[i];
+        if (r.tempo != TP_OFF) {
+            r.t_lag_cur ^= 1; r.t_lag_k0 = r.t_frames; r.t_lag_n = plan.t_k1[i] - r.t_frames;
+            r.t_in += (long long)sg.n; r.t_frames = plan.t_k1[i]; r.t_cur ^= 1;
+            r.n_in += plan.t_y[i];
+        } else r.n_in += (long long)sg.n;
+        r.n_out += (long long)plan.count[i];
         if (r.taps) { r.cur ^= 1; r.fresh = false; }
         if (sg.last) r.ended = true;
     }
@@ -329,7 +628,7 @@ q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_ro
 size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last) {
     const PsRow& r = ps->rows[(size_t)row];
     if (r.ended || (n == 0 && !last)) return 0;
-    return (size_t)std::max<long long>(0, emitted(r.sr, r.r, r.n_in + (long long)n, last != 0) - r.n_out);
+    return (size_t)std::max<long long>(0, row_emitted(r, n, last != 0) - r.n_out);
 }
 
 extern "C" q3_status q3_pcm_stage_push(q3_pcm_stage* ps, int n_rows, const int* rows, const float* const* in_host, const size_t* n_in,

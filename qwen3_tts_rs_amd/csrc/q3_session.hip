@@ -1789,6 +1789,23 @@ extern "C" q3_status q3_session_set_output(q3_session* s, uint32_t sample_rate, 
     s->out_rate = sample_rate; s->out_fmt = format;
     return Q3_OK;
 }
+extern "C" q3_status q3_session_set_tempo(q3_session* s, int b, int tempo_permille) {
+    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: null session");
+    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: row %d out of range (%d rows; -1 = every row)", b, s->B);
+    if (tempo_permille < 500 || tempo_permille > 2000)
+        return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: tempo %d permille out of range (500..2000; 1000 = off)", tempo_permille);
+    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: the model has no device");
+    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
+    for (int r = b0; r < b1; ++r)
+        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
+            return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: row %d has streamed its first chunk: the tempo is set before it, or after q3_session_replace", r);
+    if (s->out_tempo.empty()) s->out_tempo.assign((size_t)s->B, 1000);
+    for (int r = b0; r < b1; ++r) {
+        if (s->ostage) Q3C(q3_pcm_stage_set_tempo(s->ostage, r, tempo_permille));
+        s->out_tempo[(size_t)r] = tempo_permille;
+    }
+    return Q3_OK;
+}
 extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_host, const size_t* cap_samples, size_t* n_samples, int* done) {
     if (!s) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null session");
     if (!n_samples || !done || !out_host || !cap_samples) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null argument");
@@ -1797,6 +1814,8 @@ extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_
         const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
         Q3C(q3_pcm_stage_create(s->m->device, s->B, (size_t)chunk * samples_per_frame(s->m->cfg), &s->ostage));
         for (int b = 0; b < s->B; ++b) Q3C(q3_pcm_stage_set(s->ostage, b, s->out_rate, s->out_fmt));
+        for (int b = 0; b < s->B && !s->out_tempo.empty(); ++b)
+            if (s->out_tempo[(size_t)b] != 1000) Q3C(q3_pcm_stage_set_tempo(s->ostage, b, s->out_tempo[(size_t)b]));
     }
     s->out_started = true;
     return next_chunks(s, nullptr, cap_samples, n_samples, done, true, out_host);

@@ -112,6 +112,13 @@ pub mod ffi {
         pub fn q3_mimi_encode(enc: *mut c_void, samples: *const f32, n: i64, sample_rate: u32, codes: *mut u32, cap_frames: i32,
                               n_frames: *mut i32, taps: *mut *mut f32) -> i32;
         pub fn q3_mimi_free(enc: *mut c_void);
+        // the output stage's time stretcher: a speaking rate per row, in permille
+        pub fn q3_pcm_stage_set_tempo(ps: *mut c_void, row: i32, tempo_permille: i32) -> i32;
+        pub fn q3_pcm_stage_tempo_count(tempo_permille: i32, n_in_total: usize, ended: i32, frames: *mut usize, samples_24k: *mut usize) -> i32;
+        pub fn q3_pcm_stage_bound_tempo(sample_rate: u32, tempo_permille: i32, n_in: usize, n_out_max: *mut usize) -> i32;
+        pub fn q3_pcm_stage_tempo_lags(ps: *mut c_void, row: i32, k0: *mut i64, lags: *mut i32, cap: usize, n: *mut usize) -> i32;
+        pub fn q3_session_set_tempo(s: *mut c_void, b: i32, tempo_permille: i32) -> i32;
+        pub fn q3_batcher_ticket_tempo(b: *mut c_void, ticket: i64, tempo_permille: i32) -> i32;
     }
 }
 use ffi::*;
@@ -120,6 +127,20 @@ fn check(st: i32) -> Result<()> {
     if st == 0 { Ok(()) } else { bail!("{}", unsafe { CStr::from_ptr(q3_last_error()) }.to_string_lossy()) }
 }
 fn cstr(s: &str) -> CString { CString::new(s).expect("path / name without interior NUL") }
+
+/// (frames computed, 24 kHz samples final) of the output stage's time stretcher after `n_in_total` input samples at
+/// `tempo_permille` (500..=2000; 1250 = 1.25 x as fast); `ended`: after the flush. Host only. No reference counterpart.
+pub fn pcm_stage_tempo_count(tempo_permille: i32, n_in_total: usize, ended: bool) -> Result<(usize, usize)> {
+    let (mut f, mut y) = (0usize, 0usize);
+    check(unsafe { q3_pcm_stage_tempo_count(tempo_permille, n_in_total, ended as i32, &mut f, &mut y) })?;
+    Ok((f, y))
+}
+/// The most samples one push of `n_in` 24 kHz samples returns at `sample_rate` from a row at `tempo_permille`. Host only.
+pub fn pcm_stage_bound_tempo(sample_rate: u32, tempo_permille: i32, n_in: usize) -> Result<usize> {
+    let mut n = 0usize;
+    check(unsafe { q3_pcm_stage_bound_tempo(sample_rate, tempo_permille, n_in, &mut n) })?;
+    Ok(n)
+}
 
 pub const CODEC_EOS_TOKEN_ID: u32 = 2150;     // lib.rs:1466
 pub const SAMPLES_PER_FRAME: usize = 1920;    // lib.rs:1469
