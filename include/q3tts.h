@@ -611,8 +611,10 @@ q3_status q3_codec_stream_prime(q3_codec_stream* cs, int row, const uint32_t* fr
  * llround(n_in * sample_rate / 24000) samples in total, against zeros beyond the end — q3_resample's n_out and edge handling.
  * The row then takes no more samples until q3_pcm_stage_set / _reset restarts it (a further flush returns 0 samples).
  * Q3_PCM_S16: q3_pcm16_from_f32's rule on the device (clamp to +-1, x 32767.0f, truncation toward zero, NaN -> 0); the copy to
- * the host carries 2 bytes per sample. No reference counterpart (nearest: audio::resample / save_wav, whole clips on the host). */
-enum { Q3_PCM_F32 = 0, Q3_PCM_S16 = 1 };
+ * the host carries 2 bytes per sample. Q3_PCM_ULAW / Q3_PCM_ALAW: the ITU-T G.711 mu-law / A-law companding of that int16 value
+ * (q3_g711_from_pcm16's bytes: what RTP PCMU / PCMA and telephony media streams carry), 1 byte per sample (uint8_t); a NaN gives
+ * the byte of 0 (0xFF / 0xD5). No reference counterpart (nearest: audio::resample / save_wav, whole clips on the host). */
+enum { Q3_PCM_F32 = 0, Q3_PCM_S16 = 1, Q3_PCM_ULAW = 2, Q3_PCM_ALAW = 3 };
 typedef struct q3_pcm_stage q3_pcm_stage;
 /* max_push_samples: the most 24 kHz samples one row takes in one push */
 q3_status q3_pcm_stage_create(int device, int rows, size_t max_push_samples, q3_pcm_stage** out);
@@ -620,7 +622,7 @@ void      q3_pcm_stage_free(q3_pcm_stage* ps);
 q3_status q3_pcm_stage_set(q3_pcm_stage* ps, int row, uint32_t sample_rate, int format);   /* also restarts the row */
 q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row);                                   /* row starts over at sample 0 */
 /* n_in[i] samples (host) for row rows[i], all rows in one pass; last (may be NULL = none) flushes a row. out_host[i] receives
- * n_samples[i] samples in the row's format (float or int16_t), at most cap_samples[i]. A null argument, a row out of range or
+ * n_samples[i] samples in the row's format (float, int16_t or uint8_t), at most cap_samples[i]. A null argument, a row out of range or
  * listed twice, n_in[i] above max_push_samples, samples for a flushed row or a cap below what the push returns
  * (q3_pcm_stage_bound) is Q3_INVALID_ARG and changes no row; so does a push that fails on the device. */
 q3_status q3_pcm_stage_push(q3_pcm_stage* ps, int n_rows, const int* rows, const float* const* in_host, const size_t* n_in,
@@ -677,6 +679,36 @@ q3_status q3_session_set_tempo(q3_session* s, int b, int tempo_permille);
 /* Batcher: a streamed ticket's tempo; the window and the read of q3_batcher_ticket_output (q3_batcher_read_out). A parked streamed
  * ticket keeps its stage row. */
 q3_status q3_batcher_ticket_tempo(q3_batcher* b, int64_t ticket, int tempo_permille);
+/* ---------------- output stage: a level per row (gain and look-ahead peak limiter, between the stretcher and the resampler) --------
+ * gain_mB in -6000..2400 and ceiling_mB in -2400..0, both in millibel (1/100 dB; else Q3_INVALID_ARG before the device is
+ * touched); (0, 0), the default, is off: such a row takes the paths above and returns their bits and their launches. Otherwise,
+ * with g = (float)pow(10, gain_mB / 2000) and c = (float)pow(10, ceiling_mB / 2000) (f64, rounded once), the row's 24 kHz
+ * stream x (the stretcher's y where it has one) becomes y, all in f32 with every operation rounded once:
+ *   u[i] = g x[i];  r[i] = c / |u[i]| where |u[i]| > c, else 1 (a NaN compares false), and 1 for i < 0 and beyond the end;
+ *   m[j] = min(r[j] .. r[j + 127]);  a[n] = ((s0 + s1) + (s2 + s3)) / 128, s_q the sum in ascending k of m[n - 127 + k] over
+ *   k = q (mod 4), k = 0..127;  y[n] = min(max(u[n] a[n], -c), c).
+ * A peak limiter, not a compressor: the gain falls over the 5.3 ms (127 samples) before a peak and recovers over the 5.3 ms
+ * after it; every window holds r[n], so |y| <= c at 24 kHz exactly (after a rate change up to the resampler's own overshoot; the
+ * S16 / G.711 clamp is still behind it). y is a function of the sample index alone: the stream does not depend on its cuts.
+ * Streaming rule: after n input samples the outputs [0, max(0, n - 127)) are final; a push with `last` returns the rest, up to
+ * n. The resampler takes y as its input stream: its counts with this count in the place of n_in. The row keeps its last 254
+ * inputs under the commit rule of the tails: a push that is refused or fails leaves the row where it was. The step's buffers are
+ * allocated by a row's first level other than (0, 0). No reference counterpart. */
+q3_status q3_pcm_stage_set_level(q3_pcm_stage* ps, int row, int gain_mB, int ceiling_mB);  /* also restarts the row; kept by _set / _reset / _set_tempo */
+/* host only: g and c as the stage computes them (either may be NULL) */
+q3_status q3_pcm_stage_level_coeffs(int gain_mB, int ceiling_mB, float* g, float* c);
+/* host only: the streaming rule — outputs of the level step final after n_in_total inputs (ended: after the flush) */
+q3_status q3_pcm_stage_level_count(size_t n_in_total, int ended, size_t* n_out);
+/* host only: cap for a push of n_in new samples to a row with a level at this rate and tempo (1000: no stretcher), wherever the
+ * row stands and with `last`: q3_pcm_stage_bound(sample_rate, Y + 127), Y = q3_pcm_stage_bound_tempo's 24 kHz bound or n_in */
+q3_status q3_pcm_stage_bound_level(uint32_t sample_rate, int tempo_permille, size_t n_in, size_t* n_out_max);
+/* Sessions: the level of row b's stage row (b = -1: every row) in q3_session_next_chunks_out; q3_session_set_tempo's window
+ * (legal while the row has delivered no streamed sample since its start or its q3_session_replace) and its persistence (the
+ * setting stays with the row across a replace until it is set again). The other chunk, decode and run calls ignore it. */
+q3_status q3_session_set_level(q3_session* s, int b, int gain_mB, int ceiling_mB);
+/* Batcher: a streamed ticket's level; the window and the read of q3_batcher_ticket_output (q3_batcher_read_out, also at 24 kHz
+ * f32). A slot's next owner gets its own setting, off included; a parked streamed ticket keeps its stage row. */
+q3_status q3_batcher_ticket_level(q3_batcher* b, int64_t ticket, int gain_mB, int ceiling_mB);
 /* codes_to_tensor (lib.rs:1417-1431): [n][16] u32 → [16][n] i64 (host helper) */
 void      q3_codes_to_tensor(const uint32_t* frames, int n_frames, int64_t* out);
 
@@ -739,6 +771,12 @@ q3_status q3_safetensors_info(const char* path, const char* name, int* dtype, in
 /* save_wav (audio/io.rs:143-165): mono PCM16, `(clamp(x,-1,1) * 32767) as i16` */
 q3_status q3_pcm16_from_f32(const float* samples_host, int64_t n, int16_t* out_host);
 q3_status q3_wav_write_pcm16(const char* path, const float* samples_host, int64_t n, uint32_t sample_rate);
+/* ITU-T G.711 of n int16 samples, one byte each: law = Q3_PCM_ULAW or Q3_PCM_ALAW (else Q3_INVALID_ARG) — the bytes of the output
+ * stage's formats of that name. No reference counterpart. */
+q3_status q3_g711_from_pcm16(const int16_t* in_host, int64_t n, int law, uint8_t* out_host);
+/* mono G.711 WAV: format tag 7 (mu-law) or 6 (A-law), 8 bits, an 18-byte fmt chunk (cbSize 0) and a fact chunk. q3_wav_read
+ * does not read it back (it takes PCM and float). */
+q3_status q3_wav_write_g711(const char* path, const uint8_t* bytes_host, int64_t n, uint32_t sample_rate, int law);
 /* load_wav (audio/io.rs:106-141): int PCM scaled by 2^(bits-1), float as is, channels averaged to mono.
  * out_host = NULL queries *n_samples / *sample_rate only */
 q3_status q3_wav_read(const char* path, float* out_host, int64_t cap, int64_t* n_samples, uint32_t* sample_rate);

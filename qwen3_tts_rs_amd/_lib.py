@@ -135,6 +135,12 @@ SYMBOLS = {
     "q3_pcm_stage_tempo_lags": (c_int, [c_void_p, c_int, P(ctypes.c_int64), c_void_p, ctypes.c_size_t, P(ctypes.c_size_t)]),
     "q3_session_set_tempo": (c_int, [c_void_p, c_int, c_int]),
     "q3_batcher_ticket_tempo": (c_int, [c_void_p, ctypes.c_int64, c_int]),
+    "q3_pcm_stage_set_level": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "q3_pcm_stage_level_coeffs": (c_int, [c_int, c_int, P(ctypes.c_float), P(ctypes.c_float)]),
+    "q3_pcm_stage_level_count": (c_int, [ctypes.c_size_t, c_int, P(ctypes.c_size_t)]),
+    "q3_pcm_stage_bound_level": (c_int, [ctypes.c_uint32, c_int, ctypes.c_size_t, P(ctypes.c_size_t)]),
+    "q3_session_set_level": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "q3_batcher_ticket_level": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int]),
     "q3_codec_stream_push_out": (c_int, [c_void_p, c_int, P(c_int), P(c_void_p), P(c_int), c_void_p, P(c_int), P(c_int), P(c_void_p),
                                          P(ctypes.c_size_t), P(ctypes.c_size_t)]),
     "q3_session_set_output": (c_int, [c_void_p, ctypes.c_uint32, c_int]),
@@ -206,6 +212,8 @@ SYMBOLS = {
     "q3_safetensors_info": (c_int, [c_char_p, c_char_p, P(c_int), P(ctypes.c_int64), c_int, P(c_int)]),
     "q3_pcm16_from_f32": (c_int, [c_void_p, ctypes.c_int64, c_void_p]),
     "q3_wav_write_pcm16": (c_int, [c_char_p, c_void_p, ctypes.c_int64, ctypes.c_uint32]),
+    "q3_g711_from_pcm16": (c_int, [c_void_p, ctypes.c_int64, c_int, c_void_p]),
+    "q3_wav_write_g711": (c_int, [c_char_p, c_void_p, ctypes.c_int64, ctypes.c_uint32, c_int]),
     "q3_wav_read": (c_int, [c_char_p, c_void_p, ctypes.c_int64, P(ctypes.c_int64), P(ctypes.c_uint32)]),
     "q3_codes_write_bin": (c_int, [c_char_p, c_void_p, c_int, c_int]),
     "q3_codes_read_bin": (c_int, [c_char_p, c_void_p, c_int, c_int, P(c_int)]),

@@ -278,11 +278,22 @@ class Session:
         check(lib.q3_session_next_chunks(self._h, ptrs, caps, n, d))
         return [((AudioBuffer(bufs[b][:n[b]].copy()) if n[b] else None), bool(d[b])) for b in range(B)]
 
-    def set_output(self, rate: int, pcm16: bool = False):
+    def set_output(self, rate: int, pcm16: bool = False, fmt: Optional[str] = None):
         """The output of `next_chunks_out`, for all rows (q3_session_set_output): a sample rate the output stage supports, float32
-        or int16. Legal before the first streamed chunk; `next_chunks` and the whole-utterance calls ignore it."""
-        check(lib.q3_session_set_output(self._h, int(rate), PCM_S16 if pcm16 else PCM_F32))
-        self._out = (int(rate), bool(pcm16))
+        or int16 — or fmt = "f32" / "s16" / "ulaw" / "alaw" (G.711, one uint8 per sample). Legal before the first streamed chunk;
+        `next_chunks` and the whole-utterance calls ignore it."""
+        code = pcm_format(pcm16, fmt)
+        check(lib.q3_session_set_output(self._h, int(rate), code))
+        self._out = (int(rate), code)
+
+    def set_level(self, gain_mb: int, ceiling_mb: int, b: int = -1):
+        """The level of row b (-1: every row) in `next_chunks_out` (q3_session_set_level): a gain and the ceiling of its look-ahead
+        peak limiter, in millibel (1/100 dB); (0, 0) = off. The window and the persistence of `set_tempo`."""
+        check(lib.q3_session_set_level(self._h, int(b), int(gain_mb), int(ceiling_mb)))
+        lv = getattr(self, "_level", None) or [False] * self.B
+        for r in (range(self.B) if int(b) < 0 else [int(b)]):
+            lv[r] = bool(int(gain_mb) or int(ceiling_mb))
+        self._level = lv
 
     def set_tempo(self, tempo_permille: int, b: int = -1):
         """The speaking rate of row b (-1: every row) in `next_chunks_out` (q3_session_set_tempo): 500..2000 permille, 1250 = 1.25 x
@@ -301,9 +312,10 @@ class Session:
         B = self.B; spf = self.model.config.samples_per_frame
         rate, s16 = getattr(self, "_out", (24000, False))
         tempo = getattr(self, "_tempo", None) or [1000] * B
+        level = getattr(self, "_level", None) or [False] * B
         n_in = max(self.options.chunk_frames, 1) * spf
-        cap = {t: pcm_stage_bound(rate, n_in, t) for t in set(tempo)}
-        bufs = [np.zeros(cap[tempo[b]], dtype=np.int16 if s16 else np.float32) for b in range(B)]
+        cap = {k: pcm_stage_bound(rate, n_in, k[0], k[1]) for k in set(zip(tempo, level))}
+        bufs = [np.zeros(cap[(tempo[b], level[b])], dtype=PCM_DTYPE[int(s16)]) for b in range(B)]
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data_as(ctypes.c_void_p) for b in bufs])
         caps = (ctypes.c_size_t * B)(*[b.size for b in bufs])
         n = (ctypes.c_size_t * B)(); d = (ctypes.c_int * B)()
@@ -521,51 +533,66 @@ class Batcher:
         check(lib.q3_batcher_submit(self._h, ctypes.byref(r), 1 if want_pcm else 0, ctypes.byref(t)))
         return int(t.value)
 
-    def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False, tempo_permille: int = 1000) -> int:
-        """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16: the
-        ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked.
-        tempo_permille: its speaking rate (q3_batcher_ticket_tempo; 1250 = 1.25 x as fast, 1000 = off)."""
+    def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False, tempo_permille: int = 1000,
+                        fmt: Optional[str] = None, gain_mb: int = 0, ceiling_mb: int = 0) -> int:
+        """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16 / fmt: the
+        ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked, uint8 for
+        fmt "ulaw" / "alaw". tempo_permille: its speaking rate (q3_batcher_ticket_tempo; 1250 = 1.25 x as fast, 1000 = off).
+        gain_mb / ceiling_mb: its level (q3_batcher_ticket_level; millibel, (0, 0) = off)."""
+        code = pcm_format(pcm16, fmt)
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
         t = ctypes.c_int64()
         check(lib.q3_batcher_submit_streamed(self._h, ctypes.byref(r), ctypes.byref(t)))
         self._streamed.add(int(t.value))
-        self._set_output(int(t.value), sample_rate, pcm16, tempo_permille)
+        self._set_output(int(t.value), sample_rate, code, tempo_permille, gain_mb, ceiling_mb)
         return int(t.value)
 
-    def _set_output(self, ticket: int, sample_rate: int, pcm16: bool, tempo_permille: int = 1000):
-        if int(sample_rate) == 24000 and not pcm16 and int(tempo_permille) == 1000:
+    def _set_output(self, ticket: int, sample_rate: int, code: int, tempo_permille: int = 1000, gain_mb: int = 0, ceiling_mb: int = 0):
+        code = int(code); level = bool(int(gain_mb) or int(ceiling_mb))
+        if int(sample_rate) == 24000 and not code and int(tempo_permille) == 1000 and not level:
             return
         try:
-            if int(sample_rate) != 24000 or pcm16:
-                self.ticket_output(ticket, sample_rate, pcm16)
+            if int(sample_rate) != 24000 or code:
+                self.ticket_output(ticket, sample_rate, fmt=PCM_NAMES[code])
             if int(tempo_permille) != 1000:
                 self.ticket_tempo(ticket, tempo_permille)
+            if level:
+                self.ticket_level(ticket, gain_mb, ceiling_mb)
         except _lib.Q3Error:
             self.cancel(ticket); self.fetch(ticket)      # the ticket was never run: it leaves with the refusal
             raise
 
-    def ticket_output(self, ticket: int, sample_rate: int, pcm16: bool = False):
+    def ticket_output(self, ticket: int, sample_rate: int, pcm16: bool = False, fmt: Optional[str] = None):
         """A streamed ticket's own output (q3_batcher_ticket_output): between its submission and the next `step`."""
-        check(lib.q3_batcher_ticket_output(self._h, int(ticket), int(sample_rate), PCM_S16 if pcm16 else PCM_F32))
-        if int(sample_rate) == 24000 and not pcm16:
+        code = pcm_format(pcm16, fmt)
+        check(lib.q3_batcher_ticket_output(self._h, int(ticket), int(sample_rate), code))
+        if int(sample_rate) == 24000 and not code:
             self._output.pop(int(ticket), None)
         else:
-            self._output[int(ticket)] = (int(sample_rate), bool(pcm16))
+            self._output[int(ticket)] = (int(sample_rate), code)
+
+    def ticket_level(self, ticket: int, gain_mb: int, ceiling_mb: int):
+        """A streamed ticket's level (q3_batcher_ticket_level): between its submission and the next `step`."""
+        check(lib.q3_batcher_ticket_level(self._h, int(ticket), int(gain_mb), int(ceiling_mb)))
+        if int(gain_mb) or int(ceiling_mb):
+            self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
 
     def ticket_tempo(self, ticket: int, tempo_permille: int):
         """A streamed ticket's speaking rate (q3_batcher_ticket_tempo): between its submission and the next `step`."""
         check(lib.q3_batcher_ticket_tempo(self._h, int(ticket), int(tempo_permille)))
         if int(tempo_permille) != 1000:
-            self._output.setdefault(int(ticket), (24000, False))      # read through q3_batcher_read_out
+            self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
 
-    def submit_open(self, utt: Utterance, want: str = "stream", sample_rate: int = 24000, pcm16: bool = False) -> int:
+    def submit_open(self, utt: Utterance, want: str = "stream", sample_rate: int = 24000, pcm16: bool = False,
+                    fmt: Optional[str] = None) -> int:
         """Queue one request whose text arrives in pieces (`append_text`); the utterance carries the first ids. want: "stream"
-        (samples through `read`), "pcm" or "codes" (through `fetch`). sample_rate / pcm16 (want "stream" only): the ticket's own
-        output, as in `submit_streamed`. Returns its ticket."""
+        (samples through `read`), "pcm" or "codes" (through `fetch`). sample_rate / pcm16 / fmt (want "stream" only): the ticket's
+        own output, as in `submit_streamed`. Returns its ticket."""
         if want not in self._WANT:
             raise ValueError(f"want must be one of {sorted(self._WANT)}, not {want!r}")
-        if want != "stream" and (int(sample_rate) != 24000 or pcm16):
+        code = pcm_format(pcm16, fmt)
+        if want != "stream" and (int(sample_rate) != 24000 or code):
             raise ValueError("sample_rate / pcm16 apply to streamed tickets (want=\"stream\")")
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
@@ -573,7 +600,7 @@ class Batcher:
         check(lib.q3_batcher_submit_open(self._h, ctypes.byref(r), self._WANT[want], ctypes.byref(t)))
         if want == "stream":
             self._streamed.add(int(t.value))
-            self._set_output(int(t.value), sample_rate, pcm16)
+            self._set_output(int(t.value), sample_rate, code)
         return int(t.value)
 
     def append_text(self, ticket: int, ids: Sequence[int], last: bool = False):
@@ -617,7 +644,7 @@ class Batcher:
         if max_samples is None:
             max_samples = max(self.poll(ticket)[2], 1)      # every landed sample (more may land before the read: they come next time)
         if int(ticket) in self._output:
-            buf = np.zeros(int(max_samples), np.int16 if self._output[int(ticket)][1] else np.float32)
+            buf = np.zeros(int(max_samples), PCM_DTYPE[int(self._output[int(ticket)][1])])
             n = ctypes.c_size_t(); d = ctypes.c_int()
             check(lib.q3_batcher_read_out(self._h, int(ticket), buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(n), ctypes.byref(d)))
             return buf[:n.value].copy(), bool(d.value)
@@ -1223,7 +1250,20 @@ class CodecStream:
     __del__ = close
 
 
-PCM_F32, PCM_S16 = 0, 1
+PCM_F32, PCM_S16, PCM_ULAW, PCM_ALAW = 0, 1, 2, 3
+PCM_NAMES = ("f32", "s16", "ulaw", "alaw")
+PCM_DTYPE = (np.float32, np.int16, np.uint8, np.uint8)
+
+
+def pcm_format(pcm16: bool = False, fmt: Optional[str] = None) -> int:
+    """The Q3_PCM_* code of a `pcm16=` / `fmt=` pair of keywords (one of them at most)."""
+    if fmt is None:
+        return PCM_S16 if pcm16 else PCM_F32
+    if pcm16:
+        raise ValueError("give pcm16= or fmt=, not both")
+    if fmt not in PCM_NAMES:
+        raise ValueError(f"fmt must be one of {list(PCM_NAMES)}, not {fmt!r}")
+    return PCM_NAMES.index(fmt)
 
 
 def pcm_stage_taps(rate: int) -> Tuple[np.ndarray, int, int]:
@@ -1235,11 +1275,13 @@ def pcm_stage_taps(rate: int) -> Tuple[np.ndarray, int, int]:
     return t, L.value, M.value
 
 
-def pcm_stage_bound(rate: int, n_in: int, tempo_permille: int = 1000) -> int:
+def pcm_stage_bound(rate: int, n_in: int, tempo_permille: int = 1000, level: bool = False) -> int:
     """The most samples one push of n_in 24 kHz samples returns at `rate` (q3_pcm_stage_bound), for a row at tempo_permille
-    (q3_pcm_stage_bound_tempo)."""
+    (q3_pcm_stage_bound_tempo) and, with `level`, one that has a level (q3_pcm_stage_bound_level)."""
     n = ctypes.c_size_t()
-    if int(tempo_permille) == 1000:
+    if level:
+        check(lib.q3_pcm_stage_bound_level(int(rate), int(tempo_permille), int(n_in), ctypes.byref(n)))
+    elif int(tempo_permille) == 1000:
         check(lib.q3_pcm_stage_bound(int(rate), int(n_in), ctypes.byref(n)))
     else:
         check(lib.q3_pcm_stage_bound_tempo(int(rate), int(tempo_permille), int(n_in), ctypes.byref(n)))
@@ -1253,23 +1295,45 @@ def pcm_stage_tempo_count(tempo_permille: int, n_in_total: int, ended: bool = Fa
     return int(f.value), int(y.value)
 
 
+def pcm_stage_level_coeffs(gain_mb: int, ceiling_mb: int) -> Tuple[np.float32, np.float32]:
+    """(g, c) as the stage computes them from millibel (q3_pcm_stage_level_coeffs)."""
+    g = ctypes.c_float(); c = ctypes.c_float()
+    check(lib.q3_pcm_stage_level_coeffs(int(gain_mb), int(ceiling_mb), ctypes.byref(g), ctypes.byref(c)))
+    return np.float32(g.value), np.float32(c.value)
+
+
+def pcm_stage_level_count(n_in_total: int, ended: bool = False) -> int:
+    """Outputs of the level step that are final after n_in_total inputs (q3_pcm_stage_level_count)."""
+    n = ctypes.c_size_t()
+    check(lib.q3_pcm_stage_level_count(int(n_in_total), 1 if ended else 0, ctypes.byref(n)))
+    return int(n.value)
+
+
 class PcmStage:
-    """The output stage (q3_pcm_stage): `rows` independent rows, each with its own output rate and format (float32 or int16), fed
-    24 kHz float32 in pushes of any size; one pass serves every row of a push."""
+    """The output stage (q3_pcm_stage): `rows` independent rows, each with its own output rate and format (float32, int16 or G.711
+    bytes), fed 24 kHz float32 in pushes of any size; one pass serves every row of a push."""
 
     def __init__(self, model, rows: int, max_push_samples: int):
         """model: a Qwen3TTS (the stage is created on its device) or a device index."""
         self.device_index = int(model) if isinstance(model, int) else int(model.device_index)
         self.rows = int(rows); self.max_push_samples = int(max_push_samples)
-        self._fmt = [(24000, False)] * self.rows
+        self._fmt = [(24000, PCM_F32)] * self.rows
         self._tempo = [1000] * self.rows
+        self._level = [False] * self.rows
         self._h = ctypes.c_void_p()
         check(lib.q3_pcm_stage_create(self.device_index, self.rows, self.max_push_samples, ctypes.byref(self._h)))
 
-    def set(self, row: int, rate: int, pcm16: bool = False):
-        """Row's output rate and format; also restarts the row."""
-        check(lib.q3_pcm_stage_set(self._h, int(row), int(rate), PCM_S16 if pcm16 else PCM_F32))
-        self._fmt[int(row)] = (int(rate), bool(pcm16))
+    def set(self, row: int, rate: int, pcm16: bool = False, fmt: Optional[str] = None):
+        """Row's output rate and format (pcm16, or fmt = "f32" / "s16" / "ulaw" / "alaw"); also restarts the row."""
+        code = pcm_format(pcm16, fmt)
+        check(lib.q3_pcm_stage_set(self._h, int(row), int(rate), code))
+        self._fmt[int(row)] = (int(rate), code)
+
+    def set_level(self, row: int, gain_mb: int, ceiling_mb: int):
+        """Row's level (q3_pcm_stage_set_level): a gain and the ceiling of its look-ahead peak limiter in millibel (1/100 dB),
+        -6000..2400 and -2400..0; (0, 0) = off; also restarts the row. `set`, `reset` and `set_tempo` keep it."""
+        check(lib.q3_pcm_stage_set_level(self._h, int(row), int(gain_mb), int(ceiling_mb)))
+        self._level[int(row)] = bool(int(gain_mb) or int(ceiling_mb))
 
     def set_tempo(self, row: int, tempo_permille: int):
         """Row's speaking rate (q3_pcm_stage_set_tempo): 500..2000 permille, 1250 = 1.25 x as fast, 1000 = off; also restarts the
@@ -1292,10 +1356,10 @@ class PcmStage:
         return self._fmt[int(row)][0]
 
     def dtype(self, row: int):
-        return np.int16 if self._fmt[int(row)][1] else np.float32
+        return PCM_DTYPE[self._fmt[int(row)][1]]
 
     def bound(self, row: int, n_in: int) -> int:
-        return pcm_stage_bound(self._fmt[int(row)][0], n_in, self._tempo[int(row)])
+        return pcm_stage_bound(self._fmt[int(row)][0], n_in, self._tempo[int(row)], self._level[int(row)])
 
     def push(self, samples: dict, last=()) -> dict:
         """{row: 24 kHz f32 samples} -> {row: samples at the row's rate and format}, every row in one pass; rows in `last` are
@@ -1325,18 +1389,22 @@ class PcmStage:
     __del__ = close
 
 
-def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_permille: int = 1000) -> AudioBuffer:
-    """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked — what a caller
-    of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their result. tempo_permille: the clip's speaking
-    rate (1250 = 1.25 x as fast, 1000 = as it is)."""
+def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_permille: int = 1000, fmt: Optional[str] = None,
+                 gain_mb: int = 0, ceiling_mb: int = 0) -> AudioBuffer:
+    """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked (fmt: "f32" /
+    "s16" / "ulaw" / "alaw") — what a caller of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their
+    result. tempo_permille: the clip's speaking rate (1250 = 1.25 x as fast, 1000 = as it is). gain_mb / ceiling_mb: its level."""
+    code = pcm_format(pcm16, fmt)
     x = np.ascontiguousarray(audio.samples if isinstance(audio, AudioBuffer) else audio, dtype=np.float32).reshape(-1)
     if isinstance(audio, AudioBuffer) and audio.sample_rate != 24000:
         raise ValueError(f"resample_gpu takes the engine's 24 kHz audio, not {audio.sample_rate} Hz")
     ps = PcmStage(int(device), 1, max(x.size, 1))
     try:
-        ps.set(0, rate, pcm16)
+        ps.set(0, rate, fmt=PCM_NAMES[code])
         if int(tempo_permille) != 1000:
             ps.set_tempo(0, tempo_permille)
+        if int(gain_mb) or int(ceiling_mb):
+            ps.set_level(0, gain_mb, ceiling_mb)
         return AudioBuffer(ps.push({0: x}, last=(0,))[0], int(rate))
     finally:
         ps.close()
@@ -1348,6 +1416,24 @@ def pcm16(samples: np.ndarray) -> np.ndarray:
     out = np.empty(a.size, dtype=np.int16)
     check(lib.q3_pcm16_from_f32(a.ctypes.data_as(ctypes.c_void_p), a.size, out.ctypes.data_as(ctypes.c_void_p)))
     return out
+
+
+def g711(samples_i16: np.ndarray, law: str) -> np.ndarray:
+    """ITU-T G.711 of int16 samples, one uint8 each (q3_g711_from_pcm16): law "ulaw" or "alaw"."""
+    if law not in ("ulaw", "alaw"):
+        raise ValueError(f"law must be \"ulaw\" or \"alaw\", not {law!r}")
+    a = np.ascontiguousarray(samples_i16, dtype=np.int16).reshape(-1)
+    out = np.empty(a.size, dtype=np.uint8)
+    check(lib.q3_g711_from_pcm16(a.ctypes.data_as(ctypes.c_void_p), a.size, PCM_NAMES.index(law), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def save_wav_g711(path: str, g711_bytes: np.ndarray, sample_rate: int = 8000, law: str = "ulaw"):
+    """Mono G.711 WAV (q3_wav_write_g711): format tag 7 for "ulaw", 6 for "alaw"."""
+    if law not in ("ulaw", "alaw"):
+        raise ValueError(f"law must be \"ulaw\" or \"alaw\", not {law!r}")
+    a = np.ascontiguousarray(g711_bytes, dtype=np.uint8).reshape(-1)
+    check(lib.q3_wav_write_g711(str(path).encode(), a.ctypes.data_as(ctypes.c_void_p), a.size, int(sample_rate), PCM_NAMES.index(law)))
 
 
 def save_wav(path: str, samples: np.ndarray, sample_rate: int = 24000):

@@ -59,6 +59,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--tempo", type=float, default=1.0, metavar="X",
                     help="with --streaming: the speaking rate, 0.5 .. 2.0 (1.25 = 1.25 x as fast), applied by the output stage's time "
                          "stretcher as the chunks leave")
+    ap.add_argument("--output-format", choices=["f32", "s16", "ulaw", "alaw"], default="f32",
+                    help="with --streaming: the format the chunks leave the output stage in; ulaw / alaw (ITU-T G.711, one byte per "
+                         "sample) write a G.711 WAV (format tag 7 / 6)")
+    ap.add_argument("--gain-db", type=float, default=0.0, metavar="X",
+                    help="with --streaming: a gain, -60 .. +24 dB, applied by the output stage in front of its look-ahead peak limiter")
+    ap.add_argument("--ceiling-db", type=float, default=0.0, metavar="Y", help="with --streaming: the limiter's ceiling, -24 .. 0 dBFS")
     ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
                     help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
                          "first token to the first audio; writes the same WAV as without the flag)")
@@ -251,7 +257,7 @@ def main(argv=None) -> int:
             utt.ref_text_ids = tok.encode(a.ref_text or "")
     print(f"Generating up to {frames} frames...")
     t1 = time.time(); ttfa = None
-    out_rate = 24000
+    out_rate = 24000; g711 = None
     if a.output_rate != 24000 and not a.streaming:
         print("error: --output-rate applies to --streaming (resample a whole utterance with api.resample_gpu)", file=sys.stderr)
         return 2
@@ -259,13 +265,20 @@ def main(argv=None) -> int:
     if tempo != 1000 and not a.streaming:
         print("error: --tempo applies to --streaming (stretch a whole utterance with api.resample_gpu(..., tempo_permille=))", file=sys.stderr)
         return 2
-    if a.streaming and (a.output_rate != 24000 or tempo != 1000):
+    gain_mb, ceiling_mb = int(round(a.gain_db * 100.0)), int(round(a.ceiling_db * 100.0))
+    if (a.output_format != "f32" or gain_mb or ceiling_mb) and not a.streaming:
+        print("error: --output-format / --gain-db / --ceiling-db apply to --streaming (convert a whole utterance with "
+              "api.resample_gpu(..., fmt=, gain_mb=, ceiling_mb=))", file=sys.stderr)
+        return 2
+    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or a.output_format != "f32" or gain_mb or ceiling_mb):
         # the chunks of the streaming session, each through the session's output stage as it leaves
         s = model.session([utt], opts)
         try:
-            s.set_output(a.output_rate)
+            s.set_output(a.output_rate, fmt=a.output_format)
             if tempo != 1000:
                 s.set_tempo(tempo)
+            if gain_mb or ceiling_mb:
+                s.set_level(gain_mb, ceiling_mb)
         except api._lib.Q3Error as e:
             print(f"error: {e}", file=sys.stderr)
             return 2
@@ -276,9 +289,13 @@ def main(argv=None) -> int:
                 if ttfa is None:
                     ttfa = (time.time() - t1) * 1000.0
                 chunks.append(c.samples)
-        samples = np.concatenate(chunks) if chunks else np.zeros(0, np.float32)
+        samples = np.concatenate(chunks) if chunks else np.zeros(0, api.PCM_DTYPE[api.PCM_NAMES.index(a.output_format)])
         codes = s.codes(0); s.close()
         timing = None; out_rate = a.output_rate
+        if a.output_format in ("ulaw", "alaw"):
+            g711 = samples; samples = np.zeros(0, np.float32)
+        elif a.output_format == "s16":
+            samples = samples.astype(np.float32) / np.float32(32767.0)
     elif a.streaming:
         ss = api.StreamingSession(model, utt, opts)
         chunks = []
@@ -299,14 +316,18 @@ def main(argv=None) -> int:
         samples, codes = audio[0].samples, s.codes(0); s.close()
     wall = time.time() - t1
     n = int(codes.shape[0])
-    audio = api.AudioBuffer(samples, out_rate)
+    audio = api.AudioBuffer(samples if g711 is None else np.zeros(g711.size, np.float32), out_rate)      # (G.711: the length alone)
     print(f"Generated: {audio.duration():.2f}s, {len(audio)} samples, {n} frames in {wall * 1e3:.0f} ms (RTF {wall / max(audio.duration(), 1e-9):.3f})"
           + (f", TTFA {ttfa:.1f} ms" if ttfa is not None else ""))
     os.makedirs(a.output_dir, exist_ok=True)
     wav = a.output or os.path.join(a.output_dir, f"audio_seed{a.seed}_frames{n}.wav")
-    audio.save(wav)
+    if g711 is not None:
+        api.save_wav_g711(wav, g711, out_rate, a.output_format)
+    else:
+        audio.save(wav)
     api.save_codes_binary(os.path.join(a.output_dir, f"codes_seed{a.seed}_frames{n}.bin"), codes)
-    api.save_audio_binary(os.path.join(a.output_dir, f"audio_seed{a.seed}_frames{n}.bin"), samples)
+    if g711 is None:                                  # (the dump is f32: a G.711 run leaves its WAV)
+        api.save_audio_binary(os.path.join(a.output_dir, f"audio_seed{a.seed}_frames{n}.bin"), samples)
     meta = {"text": a.text, "seed": a.seed, "num_frames": n, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
             "input_ids": ids, "codes_shape": [n, 16], "audio_samples": int(len(audio)), "sample_rate": out_rate}
     with open(os.path.join(a.output_dir, f"metadata_seed{a.seed}_frames{n}.json"), "w") as f:

@@ -178,8 +178,10 @@ struct BatTicket {
     // than 24 kHz f32 — its samples go through the worker's output stage and land, as bytes of that format, in sout (under the
     // worker's mutex, like spcm, which stays empty) and leave through q3_batcher_read_out alone.
     long born = 0; uint32_t o_rate = 24000; int o_fmt = Q3_PCM_F32; bool o_conv = false; int o_tempo = 1000;      // (q3_batcher_ticket_tempo: the stage too)
+    int o_gain = 0, o_ceil = 0;                       // (q3_batcher_ticket_level: the stage too)
+    bool o_stage() const { return o_rate != 24000 || o_fmt != Q3_PCM_F32 || o_tempo != 1000 || o_gain != 0 || o_ceil != 0; }
     std::vector<char> sout; size_t o_read = 0;
-    size_t o_bytes() const { return o_fmt == Q3_PCM_S16 ? 2 : 4; }
+    size_t o_bytes() const { return o_fmt == Q3_PCM_F32 ? 4 : o_fmt == Q3_PCM_S16 ? 2 : 1; }
     // Parking (q3_batcher_set_parking; host thread). rec: the ticket's row as a record while it reads PARKED; want_in: it
     // wants a row again (parked by the scheduler, or q3_batcher_unpark) — it stands in the waiting list once a frame is runnable;
     // units: its admission claim, which it keeps while parked; entered: frames it had committed when it entered its row (the time
@@ -356,6 +358,7 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
                 if (!d.ps) so = q3_pcm_stage_create(m->device, b->stream_rows(), (size_t)std::min(b->frame_budget + b->prompt_budget, 100000) * spf, &d.ps);
                 if (so == Q3_OK) so = q3_pcm_stage_set(d.ps, p.row, t.o_rate, t.o_fmt);
                 if (so == Q3_OK) so = q3_pcm_stage_set_tempo(d.ps, p.row, t.o_tempo);      // (1000 too: the row may have had another ticket's)
+                if (so == Q3_OK) so = q3_pcm_stage_set_level(d.ps, p.row, t.o_gain, t.o_ceil);      // (off too, for the same reason)
                 if (so != Q3_OK) fail(t, so, q3_last_error());
             }
             if (is_failed(t)) continue;
@@ -1215,7 +1218,7 @@ extern "C" q3_status q3_batcher_read(q3_batcher* b, int64_t ticket, float* pcm_h
     if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_read: ticket %lld was not submitted as streamed (its samples come with q3_batcher_fetch)", (long long)ticket);
     if (t.o_conv)
         return set_err(Q3_INVALID_ARG, "q3_batcher_read: ticket %lld has an output of its own (%u Hz, %s): its samples come with q3_batcher_read_out", (long long)ticket,
-                       t.o_rate, t.o_fmt == Q3_PCM_S16 ? "s16" : "f32");
+                       t.o_rate, t.o_fmt == Q3_PCM_S16 ? "s16" : t.o_fmt == Q3_PCM_ULAW ? "ulaw" : t.o_fmt == Q3_PCM_ALAW ? "alaw" : "f32");
     *n_samples = 0; *done = 0;
     stream_settle(b, t, false);
     if (t.state == Q3_TICKET_FAILED) return set_err(t.st, "%s", t.err.c_str());
@@ -1235,11 +1238,12 @@ extern "C" q3_status q3_batcher_ticket_output(q3_batcher* b, int64_t ticket, uin
     if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: unknown ticket %lld", (long long)ticket);
     BatTicket& t = *it->second;
     if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: ticket %lld was not submitted as streamed", (long long)ticket);
-    if (format != Q3_PCM_F32 && format != Q3_PCM_S16) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: format must be Q3_PCM_F32 (0) or Q3_PCM_S16 (1)");
+    if (format < Q3_PCM_F32 || format > Q3_PCM_ALAW)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: format must be Q3_PCM_F32 (0), Q3_PCM_S16 (1), Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)");
     Q3C(q3_pcm_stage_taps(sample_rate, nullptr, 0, nullptr, nullptr));
     if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
         return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: ticket %lld has been through a step: its output is set between its submission and the next q3_batcher_step", (long long)ticket);
-    t.o_rate = sample_rate; t.o_fmt = format; t.o_conv = sample_rate != 24000 || format != Q3_PCM_F32 || t.o_tempo != 1000;
+    t.o_rate = sample_rate; t.o_fmt = format; t.o_conv = t.o_stage();
     return Q3_OK;
 }
 
@@ -1253,7 +1257,21 @@ extern "C" q3_status q3_batcher_ticket_tempo(q3_batcher* b, int64_t ticket, int 
         return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: tempo %d permille out of range (500..2000; 1000 = off)", tempo_permille);
     if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
         return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: ticket %lld has been through a step: its tempo is set between its submission and the next q3_batcher_step", (long long)ticket);
-    t.o_tempo = tempo_permille; t.o_conv = t.o_rate != 24000 || t.o_fmt != Q3_PCM_F32 || tempo_permille != 1000;
+    t.o_tempo = tempo_permille; t.o_conv = t.o_stage();
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_ticket_level(q3_batcher* b, int64_t ticket, int gain_mB, int ceiling_mB) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: ticket %lld was not submitted as streamed", (long long)ticket);
+    if (gain_mB < -6000 || gain_mB > 2400 || ceiling_mB < -2400 || ceiling_mB > 0)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: gain %d mB / ceiling %d mB out of range (-6000..2400 / -2400..0; 0 / 0 = off)", gain_mB, ceiling_mB);
+    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: ticket %lld has been through a step: its level is set between its submission and the next q3_batcher_step", (long long)ticket);
+    t.o_gain = gain_mB; t.o_ceil = ceiling_mB; t.o_conv = t.o_stage();
     return Q3_OK;
 }
 

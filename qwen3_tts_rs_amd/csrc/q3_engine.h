@@ -5,7 +5,8 @@
 //   q3_codec_run.hip device-memory cache, the vocoder pipeline (codec_decode_dev) and q3_decode_codes
 //   q3_codec_stream.hip the codec stream: the vocoder with per-row state, many rows per pass
 //   q3_pcm_stage.hip the output stage: per-row resampling to a requested rate and f32 / PCM16 conversion, and a
-//                    speaking rate per row by time-scale modification in front of it
+//                    speaking rate per row by time-scale modification in front of it; G.711 bytes and a level per
+//                    row — a gain and a look-ahead peak limiter — between the two
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
 //                    streaming chunks, q3_session_run / decode / get
 //   q3_batcher.hip   continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
@@ -462,6 +463,7 @@ struct q3_session {
     // the first such call: out_started, after which the setting is fixed)
     q3_pcm_stage* ostage = nullptr; uint32_t out_rate = 24000; int out_fmt = Q3_PCM_F32; bool out_started = false;
     std::vector<int> out_tempo;           // q3_session_set_tempo: per row, permille (empty: every row at 1000)
+    std::vector<int> out_level;           // q3_session_set_level: per row, gain and ceiling in mB (empty: every row off)
     // overlapped segment decode (q3_session_run): vocoder segments run on their own stream while the frame loop continues
     hipStream_t dec_stream = nullptr; hipEvent_t dec_ev = nullptr;
     std::vector<CodecWS> par_ws; std::vector<hipStream_t> par_streams;     // q3_session_run: utterances vocoded side by side
@@ -546,11 +548,21 @@ struct TpDesc {
     long long base, n_total, hist_lo, lo_next, k0, k1;
     int n_new, n_y, tempo, pad;
 };
+// one row of a pass of k_level (device-visible, 8-byte aligned): the row's stream into the level step is tail_in (its last 254
+// samples) below `base`, the n_new samples of src from there, nothing from n_total on; outputs o_base .. o_base + n_z - 1 go to z
+struct LvDesc {
+    const float* src; const float* tail_in; float* tail_out; float* z;
+    long long base, n_total, o_base;
+    int n_new, n_z; float g, c;
+};
 // (tdesc, t_y, t_k1: the time stretcher in front, DESIGN 4.12a — the rows at a tempo other than 1000, per segment the y samples of
-// this push and the frame the row reaches; pcm_stage_launch uploads tdesc itself, into the stage's own buffer)
+// this push and the frame the row reaches; pcm_stage_launch uploads tdesc itself, into the stage's own buffer.
+// ldesc, l_in, l_z, l_tiles: the level step between the two, DESIGN 4.12b — the rows with a level, per segment the samples that
+// enter the step and leave it in this push; its descriptors go up the same way)
 struct PsPlan {
     std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t bytes = 0; int max_tiles = 1;
     q3_pcm_stage* ps = nullptr; std::vector<TpDesc> tdesc; std::vector<long long> t_y, t_k1;
+    std::vector<LvDesc> ldesc; std::vector<long long> l_in, l_z; int l_tiles = 1;
 };
 Q3_HIDDEN int pcm_stage_rows(const q3_pcm_stage* ps);
 Q3_HIDDEN size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row);

@@ -623,6 +623,53 @@ extern "C" q3_status q3_wav_write_pcm16(const char* path, const float* samples, 
     return Q3_OK;
 }
 
+// ITU-T G.711: the segment is the first of eight bounds that holds the magnitude
+static uint8_t g711_ulaw(int64_t v) {
+    static const int64_t bound[8] = {0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF};
+    int64_t p = v >> 2, mask = 0xFF;
+    if (p < 0) { p = -p; mask = 0x7F; }
+    p = std::min<int64_t>(p, 8159) + 33;
+    int seg = 0;
+    while (seg < 8 && bound[seg] < p) ++seg;
+    return (uint8_t)((seg == 8 ? 0x7F : ((seg << 4) | ((p >> (seg + 1)) & 0xF))) ^ mask);
+}
+static uint8_t g711_alaw(int64_t v) {
+    static const int64_t bound[8] = {0x1F, 0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF};
+    int64_t p = v >> 3, mask = 0xD5;
+    if (p < 0) { mask = 0x55; p = -p - 1; }
+    int seg = 0;
+    while (seg < 8 && bound[seg] < p) ++seg;
+    return (uint8_t)((seg == 8 ? 0x7F : ((seg << 4) | ((seg < 2 ? p >> 1 : p >> seg) & 0xF))) ^ mask);
+}
+
+extern "C" q3_status q3_g711_from_pcm16(const int16_t* in, int64_t n, int law, uint8_t* out) {
+    if (law != Q3_PCM_ULAW && law != Q3_PCM_ALAW) return q3i_set_err(Q3_INVALID_ARG, "q3_g711_from_pcm16: law must be Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)");
+    if (n < 0 || ((!in || !out) && n > 0)) return q3i_set_err(Q3_INVALID_ARG, "q3_g711_from_pcm16: bad argument");
+    if (law == Q3_PCM_ULAW) for (int64_t i = 0; i < n; ++i) out[i] = g711_ulaw(in[i]);
+    else for (int64_t i = 0; i < n; ++i) out[i] = g711_alaw(in[i]);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_wav_write_g711(const char* path, const uint8_t* bytes, int64_t n, uint32_t sample_rate, int law) {
+    if (law != Q3_PCM_ULAW && law != Q3_PCM_ALAW) return q3i_set_err(Q3_INVALID_ARG, "q3_wav_write_g711: law must be Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)");
+    if (!path || (!bytes && n > 0) || n < 0) return q3i_set_err(Q3_INVALID_ARG, "q3_wav_write_g711: bad argument");
+    if ((uint64_t)n > 0xFFFFFFFFull - 64) return q3i_set_err(Q3_INVALID_ARG, "q3_wav_write_g711: %lld samples do not fit a RIFF file", (long long)n);
+    FILE* f = fopen(path, "wb");
+    if (!f) return q3i_set_err(Q3_IO, "Failed to create WAV file: %s", path);
+    // WAVE_FORMAT_MULAW 7 / WAVE_FORMAT_ALAW 6: an 18-byte fmt chunk (cbSize 0) and a fact chunk with the sample count
+    const uint32_t data_bytes = (uint32_t)n, pad = data_bytes & 1;
+    fwrite("RIFF", 1, 4, f); put_u32(f, 4 + (8 + 18) + (8 + 4) + (8 + data_bytes + pad)); fwrite("WAVE", 1, 4, f);
+    fwrite("fmt ", 1, 4, f); put_u32(f, 18); put_u16(f, law == Q3_PCM_ULAW ? 7 : 6); put_u16(f, 1); put_u32(f, sample_rate);
+    put_u32(f, sample_rate); put_u16(f, 1); put_u16(f, 8); put_u16(f, 0);
+    fwrite("fact", 1, 4, f); put_u32(f, 4); put_u32(f, data_bytes);
+    fwrite("data", 1, 4, f); put_u32(f, data_bytes);
+    if (n > 0) fwrite(bytes, 1, (size_t)n, f);
+    if (pad) fputc(0, f);
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) return q3i_set_err(Q3_IO, "Failed to write WAV file: %s", path);
+    return Q3_OK;
+}
+
 extern "C" q3_status q3_wav_read(const char* path, float* out, int64_t cap, int64_t* n_samples, uint32_t* sample_rate) {
     if (!path || !n_samples) return q3i_set_err(Q3_INVALID_ARG, "q3_wav_read: null argument");
     Mapped mp;

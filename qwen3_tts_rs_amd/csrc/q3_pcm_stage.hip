@@ -20,6 +20,14 @@
 // input. Which frames a push reaches follows from the sample counts alone (tempo_frames), so the host never reads a count back;
 // the row keeps the input the next frame can still touch and the last frame's position, in two copies flipped like the tails.
 // A row at tempo 1000 is not touched by any of it.
+//
+// Between the two, for the rows that ask for it: a level. k_level multiplies the row's 24 kHz stream by a gain and
+// by the mean, over 128 samples, of the minima, over 128 samples, of the reduction each sample needs to stay under a ceiling: a
+// look-ahead peak limiter whose output is a function of the sample index alone. It holds 127 samples back, keeps the row's last
+// 254 inputs in two copies flipped like the tails, and writes into the row's part of a z buffer that k_pcm_stage then takes as
+// the row's input. A row without a level is not touched by any of it.
+//
+// Formats: f32, PCM16, and G.711 mu-law / A-law — the companding of the PCM16 value, one byte per sample.
 #include "q3_engine.h"
 
 namespace {
@@ -35,6 +43,21 @@ __device__ inline int16_t pcm16_of(float x) {
     const float c = x < -1.0f ? -1.0f : (x > 1.0f ? 1.0f : x);
     const float s = c * 32767.0f;
     return s != s ? (int16_t)0 : (int16_t)(int)s;
+}
+
+// G.711 of the int16 v that pcm16_of gives (ITU-T G.711; the segment is the place of the leading bit)
+__device__ inline uint8_t ulaw_of(int v) {
+    int p = v >> 2, mask = 0xFF;
+    if (p < 0) { p = -p; mask = 0x7F; }
+    p = min(p, 8159) + 33;                                       // 33 .. 8192
+    const int seg = 26 - __clz(p);                               // leading bit 5 + seg (p >= 33: seg >= 0)
+    return (uint8_t)((seg >= 8 ? 0x7F : ((seg << 4) | ((p >> (seg + 1)) & 0xF))) ^ mask);
+}
+__device__ inline uint8_t alaw_of(int v) {
+    int p = v >> 3, mask = 0xD5;
+    if (p < 0) { mask = 0x55; p = -p - 1; }
+    const int seg = max(0, 27 - __clz(p));                       // leading bit 4 + seg (p = 0: segment 0)
+    return (uint8_t)((seg >= 8 ? 0x7F : ((seg << 4) | ((seg < 2 ? p >> 1 : p >> seg) & 0xF))) ^ mask);
 }
 
 __global__ __launch_bounds__(PS_TILE) void k_pcm_stage(const PsDesc* __restrict__ descs) {
@@ -75,9 +98,65 @@ __global__ __launch_bounds__(PS_TILE) void k_pcm_stage(const PsDesc* __restrict_
         }
         y = (a0 + a1) + (a2 + a3);
     }
-    if (d.fmt == Q3_PCM_S16) ((int16_t*)d.out)[o0 + tid] = pcm16_of(y);
-    else ((float*)d.out)[o0 + tid] = y;
+    if (d.fmt == Q3_PCM_F32) ((float*)d.out)[o0 + tid] = y;
+    else if (d.fmt == Q3_PCM_S16) ((int16_t*)d.out)[o0 + tid] = pcm16_of(y);
+    else if (d.fmt == Q3_PCM_ULAW) ((uint8_t*)d.out)[o0 + tid] = ulaw_of(pcm16_of(y));
+    else ((uint8_t*)d.out)[o0 + tid] = alaw_of(pcm16_of(y));
 }
+
+// ---- the level step ----
+constexpr int LV_W = 128, LV_D = LV_W - 1;                      // window, look-ahead
+constexpr int LV_TAIL = 2 * LV_D, LV_TAIL_PITCH = 256;          // inputs a row keeps (in 256 floats a copy)
+constexpr int LV_R = PS_TILE + 2 * LV_D;                        // 510 reductions a tile reads, 383 minima
+constexpr int LV_GAIN_MIN = -6000, LV_GAIN_MAX = 2400, LV_CEIL_MIN = -2400;
+
+// Grid (tile of 256 outputs, row). The tile's outputs are n = o0 .. o0 + 255 of the row's stream; it stages the reductions
+// r[o0 - 127 .. o0 + 255 + 127], halves them seven times into the minima over 128 (a minimum is exact: its order is free), and
+// each thread sums the 128 minima that end at its sample in four interleaved sums, in ascending order. Both arrays are read and
+// written at consecutive words by consecutive lanes: the 32 lanes of a half-wave meet 32 different banks.
+__global__ __launch_bounds__(PS_TILE) void k_level(const LvDesc* __restrict__ descs) {
+    __shared__ float ra[LV_R + 2], rb[LV_R + 2];
+    const LvDesc d = descs[blockIdx.y];
+    const int tid = threadIdx.x;
+    // sample q of the row's stream into the step: the kept tail below `base`, the new samples from there; 0 outside [0, n_total)
+    auto x_at = [&](long long q) -> float {
+        if (q < 0 || q >= d.n_total) return 0.0f;
+        if (q >= d.base) return d.src[q - d.base];
+        const long long k = q - (d.base - LV_TAIL);
+        return (k >= 0 && d.tail_in) ? d.tail_in[k] : 0.0f;
+    };
+    if (blockIdx.x == 0 && d.tail_out && tid < LV_TAIL) d.tail_out[tid] = x_at(d.n_total - LV_TAIL + tid);
+    const long long o0 = d.o_base + (long long)blockIdx.x * PS_TILE;
+    if ((long long)blockIdx.x * PS_TILE >= d.n_z) return;        // (uniform over the block)
+    for (int j = tid; j < LV_R; j += PS_TILE) {
+        // outside the stream x_at gives 0 and the reduction is 1; a NaN compares false: 1 too
+        const float au = fabsf(q3::mul_rn(d.g, x_at(o0 - LV_D + j)));
+        ra[j] = au > d.c ? __fdiv_rn(d.c, au) : 1.0f;
+    }
+    __syncthreads();
+    float *a = ra, *b = rb;
+    int len = LV_R;
+#pragma unroll
+    for (int s = 1; s < LV_W; s <<= 1) {                         // a[j] = min r[j .. j + 2 s - 1] after the step
+        len -= s;
+        for (int j = tid; j < len; j += PS_TILE) b[j] = fminf(a[j], a[j + s]);
+        __syncthreads();
+        float* t = a; a = b; b = t;
+    }
+    if ((long long)blockIdx.x * PS_TILE + tid >= d.n_z) return;
+    // a[tid + k] = m[n - 127 + k]
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll 8
+    for (int k = 0; k < LV_W; k += 4) {
+        s0 = q3::add_rn(s0, a[tid + k]); s1 = q3::add_rn(s1, a[tid + k + 1]);
+        s2 = q3::add_rn(s2, a[tid + k + 2]); s3 = q3::add_rn(s3, a[tid + k + 3]);
+    }
+    const float av = q3::mul_rn(q3::add_rn(q3::add_rn(s0, s1), q3::add_rn(s2, s3)), 1.0f / (float)LV_W);
+    const float y = q3::mul_rn(q3::mul_rn(d.g, x_at(o0 + tid)), av);
+    d.z[(long long)blockIdx.x * PS_TILE + tid] = y < -d.c ? -d.c : (y > d.c ? d.c : y);      // (a NaN stays one)
+}
+// the streaming rule: the outputs final after n inputs
+inline long long level_emitted(long long n, bool ended) { return ended ? n : std::max<long long>(0, n - LV_D); }
 
 // ---- the time stretcher ----
 constexpr int TP_W = 720, TP_HS = 360, TP_D = 240;             // frame, synthesis hop, search reach
@@ -258,7 +337,8 @@ long long emitted(uint32_t sr, const Rate& r, long long n_in, bool ended) {
     if (ended) return (long long)llround((double)n_in * ((double)sr / (double)PS_RATE_IN));
     return n_in > PS_HALF ? ((n_in - PS_HALF) * r.L + r.M - 1) / r.M : 0;
 }
-size_t fmt_bytes(int fmt) { return fmt == Q3_PCM_S16 ? 2 : 4; }
+size_t fmt_bytes(int fmt) { return fmt == Q3_PCM_F32 ? 4 : fmt == Q3_PCM_S16 ? 2 : 1; }
+bool fmt_ok(int fmt) { return fmt >= Q3_PCM_F32 && fmt <= Q3_PCM_ALAW; }
 }  // namespace
 
 struct PsRow {
@@ -272,6 +352,10 @@ struct PsRow {
     char* t_state = nullptr; int t_cur = 0;   // on the device, two copies: [last frame's position (16 bytes) | TP_HIST floats of input]
     int* t_lags[2] = {nullptr, nullptr}; size_t t_lag_cap[2] = {0, 0};      // the lags of a push, two buffers: t_lag_cur holds the last successful push's
     int t_lag_cur = 0; long long t_lag_k0 = 0, t_lag_n = 0;
+    // the level step between the two (level: n_in then counts its output z, the resampler's input; l_in what has entered it)
+    bool level = false; int gain_mB = 0, ceil_mB = 0; float l_g = 1.0f, l_c = 1.0f;
+    long long l_in = 0;
+    float* l_tail = nullptr; int l_cur = 0;   // on the device, two copies of LV_TAIL_PITCH floats: the last 254 inputs
 };
 constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
 struct q3_pcm_stage {
@@ -286,6 +370,9 @@ struct q3_pcm_stage {
     float* t_win = nullptr;                                                // the Hann window, 720 floats
     float* y_dev = nullptr; size_t y_cap = 0;                              // the stretched samples of a push, row after row: the resampler's input
     char *td_dev = nullptr, *td_host = nullptr; size_t td_cap = 0;         // k_tempo's descriptors
+    // the level step (all of it allocated by the first row with a level, or the first push of one)
+    float* z_dev = nullptr; size_t z_cap = 0;                              // the levelled samples of a push, row after row
+    char *ld_dev = nullptr, *ld_host = nullptr; size_t ld_cap = 0;         // k_level's descriptors
 };
 
 extern "C" q3_status q3_pcm_stage_taps(uint32_t sample_rate, float* taps_host, size_t cap_floats, int* L, int* M) {
@@ -332,6 +419,36 @@ extern "C" q3_status q3_pcm_stage_bound_tempo(uint32_t sample_rate, int tempo_pe
     return q3_pcm_stage_bound(sample_rate, tempo_permille == TP_OFF ? n_in : tempo_y_bound(tempo_permille, n_in), n_out_max);
 }
 
+static q3_status level_checked(const char* who, int gain_mB, int ceiling_mB) {
+    if (gain_mB < LV_GAIN_MIN || gain_mB > LV_GAIN_MAX)
+        return set_err(Q3_INVALID_ARG, "%s: gain %d mB out of range (%d..%d)", who, gain_mB, LV_GAIN_MIN, LV_GAIN_MAX);
+    if (ceiling_mB < LV_CEIL_MIN || ceiling_mB > 0)
+        return set_err(Q3_INVALID_ARG, "%s: ceiling %d mB out of range (%d..0)", who, ceiling_mB, LV_CEIL_MIN);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_level_coeffs(int gain_mB, int ceiling_mB, float* g, float* c) {
+    Q3C(level_checked("q3_pcm_stage_level_coeffs", gain_mB, ceiling_mB));
+    // in f64, rounded once
+    if (g) *g = (float)pow(10.0, (double)gain_mB / 2000.0);
+    if (c) *c = (float)pow(10.0, (double)ceiling_mB / 2000.0);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_level_count(size_t n_in_total, int ended, size_t* n_out) {
+    if (!n_out) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_level_count: null argument");
+    if (n_in_total > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_level_count: n_in_total above 2^48");
+    *n_out = (size_t)level_emitted((long long)n_in_total, ended != 0);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_bound_level(uint32_t sample_rate, int tempo_permille, size_t n_in, size_t* n_out_max) {
+    Q3C(tempo_checked("q3_pcm_stage_bound_level", tempo_permille));
+    if (n_in > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_level: n_in above 2^48");
+    // the most the step can hand on in one push: what entered it and, with `last`, the 127 held back
+    return q3_pcm_stage_bound(sample_rate, (tempo_permille == TP_OFF ? n_in : tempo_y_bound(tempo_permille, n_in)) + LV_D, n_out_max);
+}
+
 extern "C" q3_status q3_pcm_stage_create(int device, int rows, size_t max_push_samples, q3_pcm_stage** out) {
     if (!out || rows < 1 || max_push_samples < 1) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_create: rows and max_push_samples must be positive");
     if (device < 0) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_create: no device (a manifest-only model has none): the stage runs on the GPU");
@@ -351,9 +468,10 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
     if (ps->st) (void)hipStreamSynchronize(ps->st);
     for (auto& kv : ps->taps) dev_free(kv.second);
     dev_free(ps->tails); dev_free(ps->out_dev); dev_free(ps->in_dev);
-    for (PsRow& r : ps->rows) { dev_free(r.t_state); dev_free(r.t_lags[0]); dev_free(r.t_lags[1]); }
-    dev_free(ps->t_win); dev_free(ps->y_dev); dev_free(ps->td_dev);
+    for (PsRow& r : ps->rows) { dev_free(r.t_state); dev_free(r.t_lags[0]); dev_free(r.t_lags[1]); dev_free(r.l_tail); }
+    dev_free(ps->t_win); dev_free(ps->y_dev); dev_free(ps->td_dev); dev_free(ps->z_dev); dev_free(ps->ld_dev);
     if (ps->td_host) (void)hipHostFree(ps->td_host);
+    if (ps->ld_host) (void)hipHostFree(ps->ld_host);
     if (ps->out_host) (void)hipHostFree(ps->out_host);
     if (ps->in_host) (void)hipHostFree(ps->in_host);
     if (ps->st) (void)hipStreamDestroy(ps->st);
@@ -366,6 +484,7 @@ void pcm_stage_reset(q3_pcm_stage* ps, int row) {
     PsRow& r = ps->rows[(size_t)row];
     r.n_in = r.n_out = 0; r.cur = 0; r.fresh = true; r.ended = false;
     r.t_in = r.t_frames = 0; r.t_lag_k0 = r.t_lag_n = 0;
+    r.l_in = 0;
 }
 
 extern "C" q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row) {
@@ -376,7 +495,7 @@ extern "C" q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row) {
 
 extern "C" q3_status q3_pcm_stage_set(q3_pcm_stage* ps, int row, uint32_t sample_rate, int format) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set: bad row");
-    if (format != Q3_PCM_F32 && format != Q3_PCM_S16) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set: format must be Q3_PCM_F32 (0) or Q3_PCM_S16 (1)");
+    if (!fmt_ok(format)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set: format must be Q3_PCM_F32 (0), Q3_PCM_S16 (1), Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)");
     Rate r;
     Q3C(rate_checked("q3_pcm_stage_set", sample_rate, &r));      // (before the device is touched)
     const float* taps = nullptr;
@@ -426,6 +545,24 @@ extern "C" q3_status q3_pcm_stage_set_tempo(q3_pcm_stage* ps, int row, int tempo
     return Q3_OK;
 }
 
+extern "C" q3_status q3_pcm_stage_set_level(q3_pcm_stage* ps, int row, int gain_mB, int ceiling_mB) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_level: bad row");
+    Q3C(level_checked("q3_pcm_stage_set_level", gain_mB, ceiling_mB));      // (before the device is touched)
+    PsRow& r = ps->rows[(size_t)row];
+    const bool on = gain_mB != 0 || ceiling_mB != 0;
+    if (on && !r.l_tail) {
+        HIPC(hipSetDevice(ps->device));
+        if (dev_malloc((void**)&r.l_tail, 2 * (size_t)LV_TAIL_PITCH * 4) != hipSuccess) {
+            (void)hipGetLastError(); r.l_tail = nullptr;
+            return set_err(Q3_OOM, "q3_pcm_stage_set_level: state of row %d", row);
+        }
+    }
+    r.level = on; r.gain_mB = gain_mB; r.ceil_mB = ceiling_mB;
+    (void)q3_pcm_stage_level_coeffs(gain_mB, ceiling_mB, &r.l_g, &r.l_c);
+    pcm_stage_reset(ps, row);
+    return Q3_OK;
+}
+
 extern "C" q3_status q3_pcm_stage_tempo_lags(q3_pcm_stage* ps, int row, int64_t* k0, int* lags, size_t cap, size_t* n) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: bad row");
     if (!n) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: null argument");
@@ -441,8 +578,9 @@ extern "C" q3_status q3_pcm_stage_tempo_lags(q3_pcm_stage* ps, int row, int64_t*
 
 // what a row has emitted once n more 24 kHz samples have arrived: through the stretcher first, where the row has one
 // (y: the stretched samples by then, k1: the frames)
-static long long row_emitted(const PsRow& r, size_t n, bool last, long long* y = nullptr, long long* k1 = nullptr) {
-    long long in_total = r.n_in + (long long)n;
+// (y: the stretched samples by then, k1: the frames; lv: the samples that have entered the level step by then)
+static long long row_emitted(const PsRow& r, size_t n, bool last, long long* y = nullptr, long long* k1 = nullptr, long long* lv = nullptr) {
+    long long in_total = (r.level ? r.l_in : r.n_in) + (long long)n;
     if (r.tempo != TP_OFF) {
         long long f = 0;
         tempo_frames(r.tempo, r.t_in + (long long)n, last, &f, &in_total);
@@ -450,6 +588,10 @@ static long long row_emitted(const PsRow& r, size_t n, bool last, long long* y =
         if (k1) *k1 = f;
     }
     if (y) *y = in_total;
+    if (r.level) {
+        if (lv) *lv = in_total;
+        in_total = level_emitted(in_total, last);
+    }
     return emitted(r.sr, r.r, in_total, last);
 }
 static q3_status dev_grow(q3_pcm_stage* ps, void** p, size_t* cap, size_t bytes) {
@@ -468,19 +610,25 @@ static q3_status dev_grow(q3_pcm_stage* ps, void** p, size_t* cap, size_t bytes)
 q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan) {
     plan.desc.clear(); plan.off.assign(segs.size(), 0); plan.count.assign(segs.size(), 0); plan.bytes = 0; plan.max_tiles = 1;
     plan.ps = ps; plan.tdesc.clear(); plan.t_y.assign(segs.size(), 0); plan.t_k1.assign(segs.size(), 0);
-    std::vector<size_t> y_off(segs.size(), 0); size_t y_floats = 0;
+    plan.ldesc.clear(); plan.l_in.assign(segs.size(), 0); plan.l_z.assign(segs.size(), 0); plan.l_tiles = 1;
+    std::vector<size_t> y_off(segs.size(), 0), z_off(segs.size(), 0); size_t y_floats = 0, z_floats = 0;
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
         if (sg.n > ps->max_push) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, ps->max_push);
         if (r.ended && sg.n > 0) return set_err(Q3_INVALID_ARG, "pcm stage: row %d was flushed (last): q3_pcm_stage_reset or _set restarts it", sg.row);
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
-        long long y_total = 0, k1 = 0;
-        const long long total = row_emitted(r, sg.n, sg.last != 0, &y_total, &k1);
+        long long y_total = 0, k1 = 0, lv_total = 0;
+        const long long total = row_emitted(r, sg.n, sg.last != 0, &y_total, &k1, &lv_total);
         plan.count[i] = (size_t)std::max<long long>(0, total - r.n_out);
         if (r.tempo != TP_OFF) {
             if (!r.t_state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tempo and no state", sg.row);
-            plan.t_y[i] = y_total - r.n_in; plan.t_k1[i] = k1;
+            plan.t_y[i] = y_total - (r.level ? r.l_in : r.n_in); plan.t_k1[i] = k1;
             y_off[i] = y_floats; y_floats += ((size_t)plan.t_y[i] + 3) & ~(size_t)3;
+        }
+        if (r.level) {
+            if (!r.l_tail) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a level and no state", sg.row);
+            plan.l_in[i] = lv_total - r.l_in; plan.l_z[i] = level_emitted(lv_total, sg.last != 0) - r.n_in;
+            z_off[i] = z_floats; z_floats += ((size_t)plan.l_z[i] + 3) & ~(size_t)3;
         }
         plan.off[i] = plan.bytes;
         plan.bytes = (plan.bytes + plan.count[i] * fmt_bytes(r.fmt) + 15) & ~(size_t)15;
@@ -495,6 +643,7 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
         ps->out_cap = plan.bytes * 2;
     }
     if (y_floats > 0) Q3C(dev_grow(ps, (void**)&ps->y_dev, &ps->y_cap, y_floats * 4));
+    if (z_floats > 0) Q3C(dev_grow(ps, (void**)&ps->z_dev, &ps->z_cap, z_floats * 4));
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row];
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
@@ -517,6 +666,17 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
             if (!sg.last && t.n_total - t.lo_next > TP_HIST) return set_err(Q3_INVALID_ARG, "pcm stage: row %d would keep %lld samples", sg.row, t.n_total - t.lo_next);
             plan.tdesc.push_back(t);
             d.src = t.y; d.n_new = t.n_y;                             // the resampler's input: the stretched samples
+        }
+        if (r.level) {
+            // (the step's input: the stretched samples where the row has a stretcher, else the segment's own)
+            LvDesc l{};
+            l.src = d.src; l.n_new = (int)plan.l_in[i]; l.base = r.l_in; l.n_total = r.l_in + plan.l_in[i];
+            l.tail_in = r.l_in > 0 ? r.l_tail + (size_t)r.l_cur * LV_TAIL_PITCH : nullptr;
+            l.tail_out = sg.last ? nullptr : r.l_tail + (size_t)(r.l_cur ^ 1) * LV_TAIL_PITCH;
+            l.z = ps->z_dev + z_off[i]; l.o_base = r.n_in; l.n_z = (int)plan.l_z[i]; l.g = r.l_g; l.c = r.l_c;
+            plan.l_tiles = std::max(plan.l_tiles, (l.n_z + PS_TILE - 1) / PS_TILE);
+            plan.ldesc.push_back(l);
+            d.src = l.z; d.n_new = l.n_z;                             // the resampler's input: the levelled samples
         }
         d.base = r.n_in; d.i0 = r.n_out; d.L = r.r.L; d.M = r.r.M; d.fmt = r.fmt; d.taps = r.taps;
         if (r.taps) { d.tail_in = r.fresh ? nullptr : tails + (size_t)r.cur * PS_TAPS; d.tail_out = tails + (size_t)(r.cur ^ 1) * PS_TAPS; }
@@ -549,6 +709,26 @@ hipError_t pcm_stage_launch(const PsDesc* desc_dev, const PsPlan& plan, hipStrea
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
+    if (!plan.ldesc.empty()) {
+        // the rows with a level next, directly in front of the resampler: descriptors as above, a workgroup per tile of 256 outputs
+        q3_pcm_stage* ps = plan.ps;
+        const size_t lb = plan.ldesc.size() * sizeof(LvDesc);
+        if (lb > ps->ld_cap) {
+            dev_free(ps->ld_dev); ps->ld_dev = nullptr;
+            if (ps->ld_host) { (void)hipHostFree(ps->ld_host); ps->ld_host = nullptr; }
+            ps->ld_cap = 0;
+            hipError_t e = dev_malloc((void**)&ps->ld_dev, lb * 2);
+            if (e == hipSuccess) e = hipHostMalloc((void**)&ps->ld_host, lb * 2, hipHostMallocDefault);
+            if (e != hipSuccess) return e;
+            ps->ld_cap = lb * 2;
+        }
+        memcpy(ps->ld_host, plan.ldesc.data(), lb);
+        hipError_t e = hipMemcpyAsync(ps->ld_dev, ps->ld_host, lb, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_level, dim3((unsigned)plan.l_tiles, (unsigned)plan.ldesc.size()), dim3(PS_TILE), 0, st, (const LvDesc*)ps->ld_dev);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(k_pcm_stage, dim3((unsigned)plan.max_tiles, (unsigned)plan.desc.size()), dim3(PS_TILE), 0, st, desc_dev);
     return hipGetLastError();
 }
@@ -560,8 +740,9 @@ void pcm_stage_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const Ps
         if (r.tempo != TP_OFF) {
             r.t_lag_cur ^= 1; r.t_lag_k0 = r.t_frames; r.t_lag_n = plan.t_k1[i] - r.t_frames;
             r.t_in += (long long)sg.n; r.t_frames = plan.t_k1[i]; r.t_cur ^= 1;
-            r.n_in += plan.t_y[i];
-        } else r.n_in += (long long)sg.n;
+        }
+        if (r.level) { r.l_in += plan.l_in[i]; r.n_in += plan.l_z[i]; if (!sg.last) r.l_cur ^= 1; }
+        else r.n_in += r.tempo != TP_OFF ? plan.t_y[i] : (long long)sg.n;
         r.n_out += (long long)plan.count[i];
         if (r.taps) { r.cur ^= 1; r.fresh = false; }
         if (sg.last) r.ended = true;

@@ -1780,7 +1780,8 @@ extern "C" q3_status q3_session_next_chunks(q3_session* s, float* const* pcm_hos
 }
 extern "C" q3_status q3_session_set_output(q3_session* s, uint32_t sample_rate, int format) {
     if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_output: null session");
-    if (format != Q3_PCM_F32 && format != Q3_PCM_S16) return set_err(Q3_INVALID_ARG, "q3_session_set_output: format must be Q3_PCM_F32 (0) or Q3_PCM_S16 (1)");
+    if (format < Q3_PCM_F32 || format > Q3_PCM_ALAW)
+        return set_err(Q3_INVALID_ARG, "q3_session_set_output: format must be Q3_PCM_F32 (0), Q3_PCM_S16 (1), Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)");
     Q3C(q3_pcm_stage_taps(sample_rate, nullptr, 0, nullptr, nullptr));      // the rate, before anything else
     if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_output: the model has no device");
     bool started = s->out_started || s->stream_pos > 0;
@@ -1806,6 +1807,23 @@ extern "C" q3_status q3_session_set_tempo(q3_session* s, int b, int tempo_permil
     }
     return Q3_OK;
 }
+extern "C" q3_status q3_session_set_level(q3_session* s, int b, int gain_mB, int ceiling_mB) {
+    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_level: null session");
+    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_level: row %d out of range (%d rows; -1 = every row)", b, s->B);
+    if (gain_mB < -6000 || gain_mB > 2400 || ceiling_mB < -2400 || ceiling_mB > 0)
+        return set_err(Q3_INVALID_ARG, "q3_session_set_level: gain %d mB / ceiling %d mB out of range (-6000..2400 / -2400..0; 0 / 0 = off)", gain_mB, ceiling_mB);
+    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_level: the model has no device");
+    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
+    for (int r = b0; r < b1; ++r)
+        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
+            return set_err(Q3_INVALID_ARG, "q3_session_set_level: row %d has streamed its first chunk: the level is set before it, or after q3_session_replace", r);
+    if (s->out_level.empty()) s->out_level.assign((size_t)s->B * 2, 0);
+    for (int r = b0; r < b1; ++r) {
+        if (s->ostage) Q3C(q3_pcm_stage_set_level(s->ostage, r, gain_mB, ceiling_mB));
+        s->out_level[(size_t)r * 2] = gain_mB; s->out_level[(size_t)r * 2 + 1] = ceiling_mB;
+    }
+    return Q3_OK;
+}
 extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_host, const size_t* cap_samples, size_t* n_samples, int* done) {
     if (!s) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null session");
     if (!n_samples || !done || !out_host || !cap_samples) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null argument");
@@ -1816,6 +1834,9 @@ extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_
         for (int b = 0; b < s->B; ++b) Q3C(q3_pcm_stage_set(s->ostage, b, s->out_rate, s->out_fmt));
         for (int b = 0; b < s->B && !s->out_tempo.empty(); ++b)
             if (s->out_tempo[(size_t)b] != 1000) Q3C(q3_pcm_stage_set_tempo(s->ostage, b, s->out_tempo[(size_t)b]));
+        for (int b = 0; b < s->B && !s->out_level.empty(); ++b)
+            if (s->out_level[(size_t)b * 2] != 0 || s->out_level[(size_t)b * 2 + 1] != 0)
+                Q3C(q3_pcm_stage_set_level(s->ostage, b, s->out_level[(size_t)b * 2], s->out_level[(size_t)b * 2 + 1]));
     }
     s->out_started = true;
     return next_chunks(s, nullptr, cap_samples, n_samples, done, true, out_host);

@@ -119,6 +119,15 @@ pub mod ffi {
         pub fn q3_pcm_stage_tempo_lags(ps: *mut c_void, row: i32, k0: *mut i64, lags: *mut i32, cap: usize, n: *mut usize) -> i32;
         pub fn q3_session_set_tempo(s: *mut c_void, b: i32, tempo_permille: i32) -> i32;
         pub fn q3_batcher_ticket_tempo(b: *mut c_void, ticket: i64, tempo_permille: i32) -> i32;
+        // G.711 and the output stage's level step: a gain and a limiter's ceiling per row, in millibel
+        pub fn q3_g711_from_pcm16(input: *const i16, n: i64, law: i32, out: *mut u8) -> i32;
+        pub fn q3_wav_write_g711(path: *const c_char, bytes: *const u8, n: i64, rate: u32, law: i32) -> i32;
+        pub fn q3_pcm_stage_set_level(ps: *mut c_void, row: i32, gain_mb: i32, ceiling_mb: i32) -> i32;
+        pub fn q3_pcm_stage_level_coeffs(gain_mb: i32, ceiling_mb: i32, g: *mut f32, c: *mut f32) -> i32;
+        pub fn q3_pcm_stage_level_count(n_in_total: usize, ended: i32, n_out: *mut usize) -> i32;
+        pub fn q3_pcm_stage_bound_level(sample_rate: u32, tempo_permille: i32, n_in: usize, n_out_max: *mut usize) -> i32;
+        pub fn q3_session_set_level(s: *mut c_void, b: i32, gain_mb: i32, ceiling_mb: i32) -> i32;
+        pub fn q3_batcher_ticket_level(b: *mut c_void, ticket: i64, gain_mb: i32, ceiling_mb: i32) -> i32;
     }
 }
 use ffi::*;
