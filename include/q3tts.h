@@ -709,6 +709,47 @@ q3_status q3_session_set_level(q3_session* s, int b, int gain_mB, int ceiling_mB
 /* Batcher: a streamed ticket's level; the window and the read of q3_batcher_ticket_output (q3_batcher_read_out, also at 24 kHz
  * f32). A slot's next owner gets its own setting, off included; a parked streamed ticket keeps its stage row. */
 q3_status q3_batcher_ticket_level(q3_batcher* b, int64_t ticket, int gain_mB, int ceiling_mB);
+/* ---------------- output stage: a loudness meter and normaliser per row (ITU-R BS.1770-4, in front of the level) ----------------
+ * Q3_LOUD_OFF, the default: the row takes the paths above and returns their bits and their launches. Q3_LOUD_METER measures and
+ * passes the samples bit for bit; Q3_LOUD_NORMALIZE steers the row to target_mB (millibel of LUFS: -1900 = -19 LUFS, -4000..-500)
+ * from the gain prior_mB (-6000..2400, 0 by default); anything else is Q3_INVALID_ARG before the device is touched.
+ * The row's 24 kHz stream x (the stretcher's y where it has one) is K-weighted by two biquads (high shelf, high-pass:
+ * q3_loudness_kweight(24000), rounded to f32) in transposed direct form II, a non-finite sample entering as 0; all f32, every
+ * operation rounded once:  o = b0 v + s1;  s1 = (b1 v - a1 o) + s2;  s2 = b2 v - a2 o.
+ * Hops of 2400 samples: e_h = the sum of the squares k^2 in 64 interleaved partial sums (sample j of the hop to partial j mod 64,
+ * ascending; folded s_q += s_(q+d), d = 32 .. 1). Blocks of four hops: z_h = ((e_(h-3) + e_(h-2)) + (e_(h-1) + e_h)) (float)(1/9600)
+ * for h >= 3. After every hop the gate runs over z_3 .. z_h in f64 (64 interleaved partials as above): Sa, ca over z > Ga =
+ * (float)10^(-6.9309); none: no estimate; Gr = 0.1 Sa / ca; Sg, cg over z > Ga and z > Gr; M_h = (float)(Sg / cg). Integrated loudness
+ * = -0.691 + 10 log10(M) LUFS, computed by the host. A_h = P = (float)10^(prior_mB / 2000) for h < 3, else
+ * min(max(sqrt(T / M_h), A_lo), A_hi) with T = (float)10^((target_mB / 100 + 0.691) / 10), A_lo / A_hi = -+24 dB, else A_(h-1).
+ * Sample j of hop h leaves as x (A_(h-2) + (A_(h-1) - A_(h-2)) (j / 2400)): a gain that depends on the hops that ended before hop h
+ * began alone, so the step holds nothing back: n samples leave for n that enter, and no count or bound above changes. At most 4096
+ * blocks (410 s) are kept; past them M and A are frozen. Not a compressor and not a true-peak limiter: with a gain above 1 set a
+ * ceiling (q3_pcm_stage_set_level) behind it. The row's state (filter states, partials, three e, two A, M; the block values
+ * append-only) follows the commit rule of the tails. The step's buffers are allocated by a row's first mode other than off.
+ * No reference counterpart. */
+enum { Q3_LOUD_OFF = 0, Q3_LOUD_METER = 1, Q3_LOUD_NORMALIZE = 2 };
+/* host only: the K-weighting's two biquads at a rate of 8000..192000 Hz, each as b0 b1 b2 a0 a1 a2 in f64 (BS.1770's analogue
+ * prototypes through the tangent pre-warped bilinear form; at 48000 the tables printed in BS.1770-4) */
+q3_status q3_loudness_kweight(uint32_t sample_rate, double* shelf_ba, double* highpass_ba);
+/* host only: T, P, the absolute gate and the gain's bounds as the stage computes them (any may be NULL) */
+q3_status q3_pcm_stage_loudness_consts(int target_mB, int prior_mB, float* T, float* P, float* gate_abs, float* a_lo, float* a_hi);
+q3_status q3_pcm_stage_set_loudness(q3_pcm_stage* ps, int row, int mode, int target_mB, int prior_mB);  /* also restarts the row; kept by _set / _reset / _set_tempo / _set_level */
+/* after the row's last successful push: M (0 without an estimate), the last A, the blocks stored and cg (any may be NULL);
+ * Q3_INVALID_ARG for a row whose step is off */
+q3_status q3_pcm_stage_loudness(q3_pcm_stage* ps, int row, float* mean_square, float* gain, int* blocks, int* gated);
+/* the stored block values z_3 ..; cap / n as in q3_pcm_stage_tempo_lags (no buffer and cap 0: the count alone) */
+q3_status q3_pcm_stage_loudness_blocks(q3_pcm_stage* ps, int row, float* z, size_t cap, size_t* n);
+/* Sessions: the loudness step of row b's stage row (b = -1: every row) in q3_session_next_chunks_out; q3_session_set_tempo's
+ * window and persistence. q3_session_loudness: the row's reading (b = -1 is not a row). */
+q3_status q3_session_set_loudness(q3_session* s, int b, int mode, int target_mB, int prior_mB);
+q3_status q3_session_loudness(q3_session* s, int b, float* mean_square, float* gain, int* blocks, int* gated);
+/* Batcher: a streamed ticket's loudness step; the window and the read of q3_batcher_ticket_output (q3_batcher_read_out, also at
+ * 24 kHz f32). A slot's next owner gets its own setting, off included; a parked streamed ticket keeps its stage row, history
+ * included. _read: the ticket's reading after the parts that have landed — final once q3_batcher_read_out has reported the
+ * ticket done, valid until q3_batcher_fetch releases it. */
+q3_status q3_batcher_ticket_loudness(q3_batcher* b, int64_t ticket, int mode, int target_mB, int prior_mB);
+q3_status q3_batcher_ticket_loudness_read(q3_batcher* b, int64_t ticket, float* mean_square, float* gain, int* blocks, int* gated);
 /* codes_to_tensor (lib.rs:1417-1431): [n][16] u32 → [16][n] i64 (host helper) */
 void      q3_codes_to_tensor(const uint32_t* frames, int n_frames, int64_t* out);
 

@@ -141,6 +141,15 @@ SYMBOLS = {
     "q3_pcm_stage_bound_level": (c_int, [ctypes.c_uint32, c_int, ctypes.c_size_t, P(ctypes.c_size_t)]),
     "q3_session_set_level": (c_int, [c_void_p, c_int, c_int, c_int]),
     "q3_batcher_ticket_level": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int]),
+    "q3_loudness_kweight": (c_int, [ctypes.c_uint32, P(ctypes.c_double), P(ctypes.c_double)]),
+    "q3_pcm_stage_loudness_consts": (c_int, [c_int, c_int, P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_float)]),
+    "q3_pcm_stage_set_loudness": (c_int, [c_void_p, c_int, c_int, c_int, c_int]),
+    "q3_pcm_stage_loudness": (c_int, [c_void_p, c_int, P(ctypes.c_float), P(ctypes.c_float), P(c_int), P(c_int)]),
+    "q3_pcm_stage_loudness_blocks": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_size_t, P(ctypes.c_size_t)]),
+    "q3_session_set_loudness": (c_int, [c_void_p, c_int, c_int, c_int, c_int]),
+    "q3_session_loudness": (c_int, [c_void_p, c_int, P(ctypes.c_float), P(ctypes.c_float), P(c_int), P(c_int)]),
+    "q3_batcher_ticket_loudness": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_int]),
+    "q3_batcher_ticket_loudness_read": (c_int, [c_void_p, ctypes.c_int64, P(ctypes.c_float), P(ctypes.c_float), P(c_int), P(c_int)]),
     "q3_codec_stream_push_out": (c_int, [c_void_p, c_int, P(c_int), P(c_void_p), P(c_int), c_void_p, P(c_int), P(c_int), P(c_void_p),
                                          P(ctypes.c_size_t), P(ctypes.c_size_t)]),
     "q3_session_set_output": (c_int, [c_void_p, ctypes.c_uint32, c_int]),

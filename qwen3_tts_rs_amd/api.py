@@ -10,7 +10,7 @@ batch 1; each sequence behaves exactly like its own batch-1 run).
 import ctypes
 import enum
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -295,6 +295,18 @@ class Session:
             lv[r] = bool(int(gain_mb) or int(ceiling_mb))
         self._level = lv
 
+    def set_loudness(self, mode: int, target_mb: int = -1900, prior_mb: int = 0, b: int = -1):
+        """The loudness step of row b (-1: every row) in `next_chunks_out` (q3_session_set_loudness): LOUD_OFF, LOUD_METER or
+        LOUD_NORMALIZE to target_mb (millibel of LUFS, -1900 = -19 LUFS) from the gain prior_mb. The window and the persistence of
+        `set_tempo`."""
+        check(lib.q3_session_set_loudness(self._h, int(b), int(mode), int(target_mb), int(prior_mb)))
+
+    def loudness(self, b: int = 0) -> "Loudness":
+        """Row b's reading after its last streamed chunk (q3_session_loudness)."""
+        m = ctypes.c_float(); g = ctypes.c_float(); nb = ctypes.c_int(); cg = ctypes.c_int()
+        check(lib.q3_session_loudness(self._h, int(b), ctypes.byref(m), ctypes.byref(g), ctypes.byref(nb), ctypes.byref(cg)))
+        return Loudness.of(m.value, g.value, nb.value, cg.value)
+
     def set_tempo(self, tempo_permille: int, b: int = -1):
         """The speaking rate of row b (-1: every row) in `next_chunks_out` (q3_session_set_tempo): 500..2000 permille, 1250 = 1.25 x
         as fast, 1000 = off. Legal while the row has streamed nothing since its start or its `replace`; the setting stays with the
@@ -534,11 +546,13 @@ class Batcher:
         return int(t.value)
 
     def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False, tempo_permille: int = 1000,
-                        fmt: Optional[str] = None, gain_mb: int = 0, ceiling_mb: int = 0) -> int:
+                        fmt: Optional[str] = None, gain_mb: int = 0, ceiling_mb: int = 0, target_lufs: Optional[float] = None,
+                        prior_gain_db: float = 0.0) -> int:
         """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16 / fmt: the
         ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked, uint8 for
         fmt "ulaw" / "alaw". tempo_permille: its speaking rate (q3_batcher_ticket_tempo; 1250 = 1.25 x as fast, 1000 = off).
-        gain_mb / ceiling_mb: its level (q3_batcher_ticket_level; millibel, (0, 0) = off)."""
+        gain_mb / ceiling_mb: its level (q3_batcher_ticket_level; millibel, (0, 0) = off). target_lufs: the loudness it is steered
+        to, from the gain prior_gain_db (q3_batcher_ticket_loudness; `loudness(ticket)` reads the result)."""
         code = pcm_format(pcm16, fmt)
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
@@ -546,6 +560,12 @@ class Batcher:
         check(lib.q3_batcher_submit_streamed(self._h, ctypes.byref(r), ctypes.byref(t)))
         self._streamed.add(int(t.value))
         self._set_output(int(t.value), sample_rate, code, tempo_permille, gain_mb, ceiling_mb)
+        if target_lufs is not None:
+            try:
+                self.ticket_loudness(int(t.value), LOUD_NORMALIZE, int(round(float(target_lufs) * 100.0)), int(round(float(prior_gain_db) * 100.0)))
+            except _lib.Q3Error:
+                self.cancel(int(t.value)); self.fetch(int(t.value))      # the ticket was never run: it leaves with the refusal
+                raise
         return int(t.value)
 
     def _set_output(self, ticket: int, sample_rate: int, code: int, tempo_permille: int = 1000, gain_mb: int = 0, ceiling_mb: int = 0):
@@ -577,6 +597,19 @@ class Batcher:
         check(lib.q3_batcher_ticket_level(self._h, int(ticket), int(gain_mb), int(ceiling_mb)))
         if int(gain_mb) or int(ceiling_mb):
             self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
+
+    def ticket_loudness(self, ticket: int, mode: int, target_mb: int = -1900, prior_mb: int = 0):
+        """A streamed ticket's loudness step (q3_batcher_ticket_loudness): between its submission and the next `step`."""
+        check(lib.q3_batcher_ticket_loudness(self._h, int(ticket), int(mode), int(target_mb), int(prior_mb)))
+        if int(mode) != LOUD_OFF:
+            self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
+
+    def loudness(self, ticket: int) -> "Loudness":
+        """The ticket's reading after the parts that have landed (q3_batcher_ticket_loudness_read): final once `read` has reported
+        it done, valid until `fetch`."""
+        m = ctypes.c_float(); g = ctypes.c_float(); nb = ctypes.c_int(); cg = ctypes.c_int()
+        check(lib.q3_batcher_ticket_loudness_read(self._h, int(ticket), ctypes.byref(m), ctypes.byref(g), ctypes.byref(nb), ctypes.byref(cg)))
+        return Loudness.of(m.value, g.value, nb.value, cg.value)
 
     def ticket_tempo(self, ticket: int, tempo_permille: int):
         """A streamed ticket's speaking rate (q3_batcher_ticket_tempo): between its submission and the next `step`."""
@@ -1309,6 +1342,40 @@ def pcm_stage_level_count(n_in_total: int, ended: bool = False) -> int:
     return int(n.value)
 
 
+LOUD_OFF, LOUD_METER, LOUD_NORMALIZE = 0, 1, 2
+
+
+class Loudness(NamedTuple):
+    """A row's reading: integrated loudness in LUFS (-inf without an estimate), the gated mean square it comes from, the last gain
+    (a factor, and in dB: what a host passes as the next request's prior), the blocks stored and those that passed both gates."""
+    lufs: float
+    mean_square: float
+    gain: float
+    gain_db: float
+    blocks: int
+    gated: int
+
+    @classmethod
+    def of(cls, m, g, blocks, gated):
+        m = float(np.float32(m)); g = float(np.float32(g))
+        return cls(-0.691 + 10.0 * float(np.log10(m)) if m > 0.0 else float("-inf"), m, g, 20.0 * float(np.log10(g)) if g > 0.0 else float("-inf"),
+                   int(blocks), int(gated))
+
+
+def loudness_kweight(rate: int) -> Tuple[np.ndarray, np.ndarray]:
+    """BS.1770's K-weighting at `rate`: (shelf, high-pass), each b0 b1 b2 a0 a1 a2 in float64 (q3_loudness_kweight)."""
+    sh = np.zeros(6, np.float64); hp = np.zeros(6, np.float64)
+    check(lib.q3_loudness_kweight(int(rate), sh.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), hp.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return sh, hp
+
+
+def pcm_stage_loudness_consts(target_mb: int = -1900, prior_mb: int = 0) -> Tuple[np.float32, ...]:
+    """(T, P, gate_abs, a_lo, a_hi) as the stage computes them from millibel (q3_pcm_stage_loudness_consts)."""
+    v = [ctypes.c_float() for _ in range(5)]
+    check(lib.q3_pcm_stage_loudness_consts(int(target_mb), int(prior_mb), *[ctypes.byref(x) for x in v]))
+    return tuple(np.float32(x.value) for x in v)
+
+
 class PcmStage:
     """The output stage (q3_pcm_stage): `rows` independent rows, each with its own output rate and format (float32, int16 or G.711
     bytes), fed 24 kHz float32 in pushes of any size; one pass serves every row of a push."""
@@ -1340,6 +1407,26 @@ class PcmStage:
         row. `set` and `reset` keep it."""
         check(lib.q3_pcm_stage_set_tempo(self._h, int(row), int(tempo_permille)))
         self._tempo[int(row)] = int(tempo_permille)
+
+    def set_loudness(self, row: int, mode: int, target_mb: int = -1900, prior_mb: int = 0):
+        """Row's loudness step (q3_pcm_stage_set_loudness): LOUD_OFF, LOUD_METER (measure, the samples pass) or LOUD_NORMALIZE
+        (steer the row to target_mb, millibel of LUFS, from the gain prior_mb); also restarts the row. `set`, `reset`, `set_tempo`
+        and `set_level` keep it."""
+        check(lib.q3_pcm_stage_set_loudness(self._h, int(row), int(mode), int(target_mb), int(prior_mb)))
+
+    def loudness(self, row: int) -> Loudness:
+        """The row's reading after its last successful push (q3_pcm_stage_loudness)."""
+        m = ctypes.c_float(); g = ctypes.c_float(); nb = ctypes.c_int(); cg = ctypes.c_int()
+        check(lib.q3_pcm_stage_loudness(self._h, int(row), ctypes.byref(m), ctypes.byref(g), ctypes.byref(nb), ctypes.byref(cg)))
+        return Loudness.of(m.value, g.value, nb.value, cg.value)
+
+    def loudness_blocks(self, row: int) -> np.ndarray:
+        """The row's stored block values z_3 .. (q3_pcm_stage_loudness_blocks), float32."""
+        n = ctypes.c_size_t()
+        check(lib.q3_pcm_stage_loudness_blocks(self._h, int(row), None, 0, ctypes.byref(n)))      # the count
+        z = np.zeros(int(n.value), np.float32)
+        check(lib.q3_pcm_stage_loudness_blocks(self._h, int(row), z.ctypes.data_as(ctypes.c_void_p), z.size, ctypes.byref(n)))
+        return z
 
     def tempo_lags(self, row: int) -> Tuple[int, np.ndarray]:
         """(k0, lags) of the frames k0 .. the row's last successful push computed (q3_pcm_stage_tempo_lags)."""
@@ -1390,10 +1477,11 @@ class PcmStage:
 
 
 def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_permille: int = 1000, fmt: Optional[str] = None,
-                 gain_mb: int = 0, ceiling_mb: int = 0) -> AudioBuffer:
+                 gain_mb: int = 0, ceiling_mb: int = 0, target_mb: Optional[int] = None, prior_mb: int = 0) -> AudioBuffer:
     """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked (fmt: "f32" /
     "s16" / "ulaw" / "alaw") — what a caller of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their
-    result. tempo_permille: the clip's speaking rate (1250 = 1.25 x as fast, 1000 = as it is). gain_mb / ceiling_mb: its level."""
+    result. tempo_permille: the clip's speaking rate (1250 = 1.25 x as fast, 1000 = as it is). gain_mb / ceiling_mb: its level. target_mb / prior_mb: the loudness it is
+    steered to (millibel of LUFS) and the gain it starts from — a causal normaliser: the first 400 ms leave at the prior."""
     code = pcm_format(pcm16, fmt)
     x = np.ascontiguousarray(audio.samples if isinstance(audio, AudioBuffer) else audio, dtype=np.float32).reshape(-1)
     if isinstance(audio, AudioBuffer) and audio.sample_rate != 24000:
@@ -1405,7 +1493,24 @@ def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_p
             ps.set_tempo(0, tempo_permille)
         if int(gain_mb) or int(ceiling_mb):
             ps.set_level(0, gain_mb, ceiling_mb)
+        if target_mb is not None:
+            ps.set_loudness(0, LOUD_NORMALIZE, target_mb, prior_mb)
         return AudioBuffer(ps.push({0: x}, last=(0,))[0], int(rate))
+    finally:
+        ps.close()
+
+
+def loudness(pcm_24k, device: int = 0) -> float:
+    """Integrated loudness (ITU-R BS.1770-4, LUFS) of a whole 24 kHz clip (AudioBuffer or array), measured by a one-row output stage
+    in meter mode — for a reference clip at enrolment. -inf for a clip shorter than 400 ms or below the absolute gate."""
+    x = np.ascontiguousarray(pcm_24k.samples if isinstance(pcm_24k, AudioBuffer) else pcm_24k, dtype=np.float32).reshape(-1)
+    if isinstance(pcm_24k, AudioBuffer) and pcm_24k.sample_rate != 24000:
+        raise ValueError(f"loudness takes 24 kHz audio, not {pcm_24k.sample_rate} Hz (resample it first)")
+    ps = PcmStage(int(device), 1, max(x.size, 1))
+    try:
+        ps.set_loudness(0, LOUD_METER)
+        ps.push({0: x}, last=(0,))
+        return ps.loudness(0).lufs
     finally:
         ps.close()
 

@@ -64,7 +64,14 @@ def build_parser() -> argparse.ArgumentParser:
                          "sample) write a G.711 WAV (format tag 7 / 6)")
     ap.add_argument("--gain-db", type=float, default=0.0, metavar="X",
                     help="with --streaming: a gain, -60 .. +24 dB, applied by the output stage in front of its look-ahead peak limiter")
-    ap.add_argument("--ceiling-db", type=float, default=0.0, metavar="Y", help="with --streaming: the limiter's ceiling, -24 .. 0 dBFS")
+    ap.add_argument("--ceiling-db", type=float, default=0.0, metavar="Y", action=_Given, help="with --streaming: the limiter's ceiling, -24 .. 0 dBFS")
+    ap.add_argument("--target-lufs", type=float, default=None, metavar="L",
+                    help="with --streaming: steer the audio to this integrated loudness (ITU-R BS.1770-4), -40 .. -5 LUFS, by the output "
+                         "stage's causal normaliser; sets a -1 dB ceiling unless --ceiling-db is given, and prints the measured loudness "
+                         "and the final gain (the next request's --prior-gain-db)")
+    ap.add_argument("--prior-gain-db", type=float, default=0.0, metavar="X",
+                    help="with --target-lufs: the gain the first 400 ms leave at, -60 .. +24 dB (the final gain of an earlier request "
+                         "with the same voice)")
     ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
                     help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
                          "first token to the first audio; writes the same WAV as without the flag)")
@@ -147,6 +154,31 @@ def compare_with_reference(reference_dir: str, seed: int, num_frames: int, codes
     return rep
 
 
+class _Given(argparse.Action):
+    """stores the value and, as <dest>_given, that the flag was on the command line"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values); setattr(namespace, self.dest + "_given", True)
+
+
+def loudness_from_args(a):
+    """(target_mB, prior_mB, ceiling_mB) of --target-lufs / --prior-gain-db / --ceiling-db, or None without --target-lufs;
+    ValueError for a combination the CLI refuses (before anything is loaded)."""
+    if a.target_lufs is None:
+        if a.prior_gain_db != 0.0:
+            raise ValueError("--prior-gain-db applies to --target-lufs")
+        return None
+    if not a.streaming:
+        raise ValueError("--target-lufs applies to --streaming (normalise a whole utterance with api.resample_gpu(..., target_mb=))")
+    target, prior = int(round(a.target_lufs * 100.0)), int(round(a.prior_gain_db * 100.0))
+    if not -4000 <= target <= -500:
+        raise ValueError(f"--target-lufs {a.target_lufs} out of range (-40 .. -5)")
+    if not -6000 <= prior <= 2400:
+        raise ValueError(f"--prior-gain-db {a.prior_gain_db} out of range (-60 .. +24)")
+    ceiling = int(round(a.ceiling_db * 100.0)) if getattr(a, "ceiling_db_given", False) else -100
+    return target, prior, ceiling
+
+
 def max_frames_from_args(a) -> int:
     return int(a.duration * 12.5) if a.duration is not None else a.frames
 
@@ -197,6 +229,11 @@ def main(argv=None) -> int:
         return 2
     if a.x_vector_only and a.ref_text:
         print("error: --x-vector-only and --ref-text are contradictory.\n  x_vector_only uses only the speaker embedding (no ICL).", file=sys.stderr)
+        return 2
+    try:
+        loud = loudness_from_args(a)
+    except ValueError as e:
+        print(f"error: {e}", file=sys.stderr)
         return 2
     dev = parse_device(a.device)
     speaker, language = q.Speaker.from_str(a.speaker), q.Language.from_str(a.language)
@@ -266,11 +303,14 @@ def main(argv=None) -> int:
         print("error: --tempo applies to --streaming (stretch a whole utterance with api.resample_gpu(..., tempo_permille=))", file=sys.stderr)
         return 2
     gain_mb, ceiling_mb = int(round(a.gain_db * 100.0)), int(round(a.ceiling_db * 100.0))
+    if loud is not None:
+        ceiling_mb = loud[2]
+    reading = None
     if (a.output_format != "f32" or gain_mb or ceiling_mb) and not a.streaming:
         print("error: --output-format / --gain-db / --ceiling-db apply to --streaming (convert a whole utterance with "
               "api.resample_gpu(..., fmt=, gain_mb=, ceiling_mb=))", file=sys.stderr)
         return 2
-    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or a.output_format != "f32" or gain_mb or ceiling_mb):
+    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None):
         # the chunks of the streaming session, each through the session's output stage as it leaves
         s = model.session([utt], opts)
         try:
@@ -279,6 +319,8 @@ def main(argv=None) -> int:
                 s.set_tempo(tempo)
             if gain_mb or ceiling_mb:
                 s.set_level(gain_mb, ceiling_mb)
+            if loud is not None:
+                s.set_loudness(api.LOUD_NORMALIZE, loud[0], loud[1])
         except api._lib.Q3Error as e:
             print(f"error: {e}", file=sys.stderr)
             return 2
@@ -290,6 +332,8 @@ def main(argv=None) -> int:
                     ttfa = (time.time() - t1) * 1000.0
                 chunks.append(c.samples)
         samples = np.concatenate(chunks) if chunks else np.zeros(0, api.PCM_DTYPE[api.PCM_NAMES.index(a.output_format)])
+        if loud is not None:
+            reading = s.loudness(0)
         codes = s.codes(0); s.close()
         timing = None; out_rate = a.output_rate
         if a.output_format in ("ulaw", "alaw"):
@@ -319,6 +363,9 @@ def main(argv=None) -> int:
     audio = api.AudioBuffer(samples if g711 is None else np.zeros(g711.size, np.float32), out_rate)      # (G.711: the length alone)
     print(f"Generated: {audio.duration():.2f}s, {len(audio)} samples, {n} frames in {wall * 1e3:.0f} ms (RTF {wall / max(audio.duration(), 1e-9):.3f})"
           + (f", TTFA {ttfa:.1f} ms" if ttfa is not None else ""))
+    if reading is not None:
+        print(f"Loudness: {reading.lufs:.2f} LUFS measured over {reading.gated} of {reading.blocks} blocks (target {a.target_lufs:.2f}), "
+              f"final gain {reading.gain_db:+.2f} dB (--prior-gain-db {reading.gain_db:.2f} for the next request of this voice)")
     os.makedirs(a.output_dir, exist_ok=True)
     wav = a.output or os.path.join(a.output_dir, f"audio_seed{a.seed}_frames{n}.wav")
     if g711 is not None:

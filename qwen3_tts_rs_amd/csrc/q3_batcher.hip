@@ -179,7 +179,9 @@ struct BatTicket {
     // worker's mutex, like spcm, which stays empty) and leave through q3_batcher_read_out alone.
     long born = 0; uint32_t o_rate = 24000; int o_fmt = Q3_PCM_F32; bool o_conv = false; int o_tempo = 1000;      // (q3_batcher_ticket_tempo: the stage too)
     int o_gain = 0, o_ceil = 0;                       // (q3_batcher_ticket_level: the stage too)
-    bool o_stage() const { return o_rate != 24000 || o_fmt != Q3_PCM_F32 || o_tempo != 1000 || o_gain != 0 || o_ceil != 0; }
+    // (q3_batcher_ticket_loudness: the stage too; lo_*: the reading after the parts that have landed, under the worker's mutex)
+    int o_loud = Q3_LOUD_OFF, o_target = -1900, o_prior = 0; float lo_M = 0.0f, lo_gain = 1.0f; int lo_blocks = 0, lo_gated = 0;
+    bool o_stage() const { return o_rate != 24000 || o_fmt != Q3_PCM_F32 || o_tempo != 1000 || o_gain != 0 || o_ceil != 0 || o_loud != Q3_LOUD_OFF; }
     std::vector<char> sout; size_t o_read = 0;
     size_t o_bytes() const { return o_fmt == Q3_PCM_F32 ? 4 : o_fmt == Q3_PCM_S16 ? 2 : 1; }
     // Parking (q3_batcher_set_parking; host thread). rec: the ticket's row as a record while it reads PARKED; want_in: it
@@ -340,7 +342,10 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
     auto land = [&](Out& o) {
         BatTicket& t = *o.p->t;
         t.s_deliv += o.n_new;
+        float lm = 0.0f, lg = 1.0f; int lb = 0, lc = 0;
+        const bool loud = t.o_conv && t.o_loud != Q3_LOUD_OFF && q3_pcm_stage_loudness(d.ps, o.p->row, &lm, &lg, &lb, &lc) == Q3_OK;
         std::lock_guard<std::mutex> g(d.mu);
+        if (loud) { t.lo_M = lm; t.lo_gain = lg; t.lo_blocks = lb; t.lo_gated = lc; }
         if (t.o_conv) t.sout.insert(t.sout.end(), o.out.begin(), o.out.begin() + (long)(o.n_out * t.o_bytes()));
         else t.spcm.insert(t.spcm.end(), o.pcm.begin(), o.pcm.end());
     };
@@ -359,6 +364,7 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
                 if (so == Q3_OK) so = q3_pcm_stage_set(d.ps, p.row, t.o_rate, t.o_fmt);
                 if (so == Q3_OK) so = q3_pcm_stage_set_tempo(d.ps, p.row, t.o_tempo);      // (1000 too: the row may have had another ticket's)
                 if (so == Q3_OK) so = q3_pcm_stage_set_level(d.ps, p.row, t.o_gain, t.o_ceil);      // (off too, for the same reason)
+                if (so == Q3_OK) so = q3_pcm_stage_set_loudness(d.ps, p.row, t.o_loud, t.o_target, t.o_prior);      // (off too)
                 if (so != Q3_OK) fail(t, so, q3_last_error());
             }
             if (is_failed(t)) continue;
@@ -1258,6 +1264,34 @@ extern "C" q3_status q3_batcher_ticket_tempo(q3_batcher* b, int64_t ticket, int 
     if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
         return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: ticket %lld has been through a step: its tempo is set between its submission and the next q3_batcher_step", (long long)ticket);
     t.o_tempo = tempo_permille; t.o_conv = t.o_stage();
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_ticket_loudness(q3_batcher* b, int64_t ticket, int mode, int target_mB, int prior_mB) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness: ticket %lld was not submitted as streamed", (long long)ticket);
+    Q3C(pcm_stage_loud_checked("q3_batcher_ticket_loudness", mode, target_mB, prior_mB));
+    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness: ticket %lld has been through a step: its loudness step is set between its submission and the next q3_batcher_step", (long long)ticket);
+    t.o_loud = mode; t.o_target = target_mB; t.o_prior = prior_mB; t.o_conv = t.o_stage();
+    (void)q3_pcm_stage_loudness_consts(target_mB, prior_mB, nullptr, &t.lo_gain, nullptr, nullptr, nullptr);      // (until a part lands: the prior)
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_ticket_loudness_read(q3_batcher* b, int64_t ticket, float* mean_square, float* gain, int* blocks, int* gated) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness_read: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness_read: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (t.o_loud == Q3_LOUD_OFF) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness_read: ticket %lld has no loudness step (q3_batcher_ticket_loudness)", (long long)ticket);
+    std::lock_guard<std::mutex> g(b->dec->mu);
+    if (mean_square) *mean_square = t.lo_M;
+    if (gain) *gain = t.lo_gain;
+    if (blocks) *blocks = t.lo_blocks;
+    if (gated) *gated = t.lo_gated;
     return Q3_OK;
 }
 

@@ -6,7 +6,8 @@
 //   q3_codec_stream.hip the codec stream: the vocoder with per-row state, many rows per pass
 //   q3_pcm_stage.hip the output stage: per-row resampling to a requested rate and f32 / PCM16 conversion, and a
 //                    speaking rate per row by time-scale modification in front of it; G.711 bytes and a level per
-//                    row — a gain and a look-ahead peak limiter — between the two
+//                    row — a gain and a look-ahead peak limiter — between the two; a BS.1770 loudness meter and
+//                    normaliser per row in front of the level
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
 //                    streaming chunks, q3_session_run / decode / get
 //   q3_batcher.hip   continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
@@ -464,6 +465,7 @@ struct q3_session {
     q3_pcm_stage* ostage = nullptr; uint32_t out_rate = 24000; int out_fmt = Q3_PCM_F32; bool out_started = false;
     std::vector<int> out_tempo;           // q3_session_set_tempo: per row, permille (empty: every row at 1000)
     std::vector<int> out_level;           // q3_session_set_level: per row, gain and ceiling in mB (empty: every row off)
+    std::vector<int> out_loud;            // q3_session_set_loudness: per row, mode, target and prior in mB (empty: every row off)
     // overlapped segment decode (q3_session_run): vocoder segments run on their own stream while the frame loop continues
     hipStream_t dec_stream = nullptr; hipEvent_t dec_ev = nullptr;
     std::vector<CodecWS> par_ws; std::vector<hipStream_t> par_streams;     // q3_session_run: utterances vocoded side by side
@@ -555,18 +557,31 @@ struct LvDesc {
     long long base, n_total, o_base;
     int n_new, n_z; float g, c;
 };
+// one row of a pass of k_loud (device-visible, 8-byte aligned): samples base .. base + n_new - 1 of the row's stream into the loudness
+// step come from src; st_in (null at the row's start) / st_out are the two copies of its small state, hist its block values; w
+// (null in meter mode) receives the n_new normalised samples. coef: b0 b1 b2 a1 a2 of the shelf, then of the high-pass
+struct LoDesc {
+    const float* src; float* w; const float* st_in; float* st_out; float* hist;
+    long long base;
+    int n_new, mode; float T, P, gate, a_lo, a_hi; int pad;
+    float coef[10];
+};
 // (tdesc, t_y, t_k1: the time stretcher in front, DESIGN 4.12a — the rows at a tempo other than 1000, per segment the y samples of
 // this push and the frame the row reaches; pcm_stage_launch uploads tdesc itself, into the stage's own buffer.
 // ldesc, l_in, l_z, l_tiles: the level step between the two, DESIGN 4.12b — the rows with a level, per segment the samples that
-// enter the step and leave it in this push; its descriptors go up the same way)
+// enter the step and leave it in this push; its descriptors go up the same way.
+// odesc, o_n: the loudness step between the stretcher and the level, DESIGN 4.12c — the rows that meter or normalise, per segment
+// the samples that pass the step in this push)
 struct PsPlan {
     std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t bytes = 0; int max_tiles = 1;
     q3_pcm_stage* ps = nullptr; std::vector<TpDesc> tdesc; std::vector<long long> t_y, t_k1;
     std::vector<LvDesc> ldesc; std::vector<long long> l_in, l_z; int l_tiles = 1;
+    std::vector<LoDesc> odesc; std::vector<long long> o_n;
 };
 Q3_HIDDEN int pcm_stage_rows(const q3_pcm_stage* ps);
 Q3_HIDDEN size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row);
 Q3_HIDDEN void pcm_stage_reset(q3_pcm_stage* ps, int row);
+Q3_HIDDEN q3_status pcm_stage_loud_checked(const char* who, int mode, int target_mB, int prior_mB);      // the ranges of q3_pcm_stage_set_loudness
 Q3_HIDDEN q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_rows, const int* rows);
 Q3_HIDDEN size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last);
 Q3_HIDDEN q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan);

@@ -27,6 +27,14 @@
 // 254 inputs in two copies flipped like the tails, and writes into the row's part of a z buffer that k_pcm_stage then takes as
 // the row's input. A row without a level is not touched by any of it.
 //
+// In front of the level, for the rows that ask for it: a loudness step. k_loud K-weights the row's 24 kHz stream
+// (ITU-R BS.1770-4: two biquads), keeps the energy of every 100 ms hop and the mean square of every 400 ms block, gates the
+// blocks the row has seen so far (absolute and relative gate) into its integrated loudness, and — where the row normalises —
+// multiplies the stream by a gain that ramps, hop by hop, toward the one that would bring that loudness to a target. A hop's gain
+// depends on the hops that ended before it alone, so the step holds nothing back: n samples leave, into the row's part of a w
+// buffer, for n that enter. The row keeps its filter states, partial sums, last energies and gains in two copies flipped like the
+// tails, its block values append-only. A row whose step is off is not touched by any of it.
+//
 // Formats: f32, PCM16, and G.711 mu-law / A-law — the companding of the PCM16 value, one byte per sample.
 #include "q3_engine.h"
 
@@ -157,6 +165,167 @@ __global__ __launch_bounds__(PS_TILE) void k_level(const LvDesc* __restrict__ de
 }
 // the streaming rule: the outputs final after n inputs
 inline long long level_emitted(long long n, bool ended) { return ended ? n : std::max<long long>(0, n - LV_D); }
+
+// ---- the loudness step ----
+constexpr int LD_HOP = 2400, LD_HIST = 4096;                    // 100 ms; the block values a row keeps
+constexpr int LD_THREADS = 256;
+constexpr int LD_STATE = 80;                                    // floats a copy of the small state: [filter states 4 | partials 64 | e 3 | A1 A2 M cg est]
+constexpr int LD_S_E = 68, LD_S_A1 = 71, LD_S_A2 = 72, LD_S_M = 73, LD_S_CG = 74, LD_S_EST = 75;
+constexpr int LD_TARGET_MIN = -4000, LD_TARGET_MAX = -500, LD_PRIOR_MIN = -6000, LD_PRIOR_MAX = 2400;
+
+// The root of the gain, rounded once: sqrtf is the correctly rounded root in this build (no fast-math flag), where __fsqrt_rn
+// compiles to the hardware's approximation, one ulp wide.
+__device__ inline float ld_sqrt_rn(float x) { return sqrtf(x); }
+
+// two f32 operations in one instruction (v_pk_mul_f32 / v_pk_add_f32), each half rounded once; no contraction, as in q3_kernels.h
+typedef float ld_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ ld_f2 ld_mul2(ld_f2 a, ld_f2 b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ ld_f2 ld_add2(ld_f2 a, ld_f2 b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ ld_f2 ld_sub2(ld_f2 a, ld_f2 b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+// One workgroup per row; the hops the push touches in order. Per hop: the block stages the new samples (a non-finite one as 0)
+// and, where the row normalises, writes them times the ramp between the two gains that were known before the hop began; lane 0
+// runs the two biquads over the staged samples in place; lanes 0..63 add the squares to the hop's 64 partial sums. A hop that
+// completes is folded by wave 0, its block value joins the history (kept in LDS for the launch, appended in memory), and wave 0
+// runs the gate over the history in f64, 64 interleaved partials folded by shuffles in the defined order.
+// LDS: staging and squares are read and written at consecutive words by consecutive lanes (the squares rotated by the hop's
+// offset: a permutation of 64 consecutive words), the history at word lane + 64 k: no pass meets a bank twice.
+__global__ __launch_bounds__(LD_THREADS) void k_loud(const LoDesc* __restrict__ descs) {
+    __shared__ float buf[LD_HOP];
+    __shared__ float zh[LD_HIST];
+    __shared__ float pub[4];                                     // wave 0 -> the block: A_h, M, cg, est
+    const LoDesc d = descs[blockIdx.x];
+    const int tid = threadIdx.x;
+    long long h = d.base / LD_HOP;                               // the hop in progress
+    int j0 = (int)(d.base - h * LD_HOP);
+    // the row's small state: the gains and the reading in every thread, the hop energies in wave 0, the filter states in thread 0,
+    // partial q in thread q
+    float e3 = 0.0f, e2 = 0.0f, e1 = 0.0f, A1 = d.P, A2 = d.P, M = 0.0f, part = 0.0f;
+    float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f, f3 = 0.0f;
+    int cg = 0, est = 0;
+    if (d.st_in) {
+        e3 = d.st_in[LD_S_E]; e2 = d.st_in[LD_S_E + 1]; e1 = d.st_in[LD_S_E + 2];
+        A1 = d.st_in[LD_S_A1]; A2 = d.st_in[LD_S_A2]; M = d.st_in[LD_S_M];
+        cg = __float_as_int(d.st_in[LD_S_CG]); est = __float_as_int(d.st_in[LD_S_EST]);
+        f0 = d.st_in[0]; f1 = d.st_in[1]; f2 = d.st_in[2]; f3 = d.st_in[3];
+        if (tid < 64) part = d.st_in[4 + tid];
+    }
+    {
+        const long long nb = h < 3 ? 0 : (h - 3 < LD_HIST ? h - 3 : LD_HIST);      // blocks of the hops that ended before this push
+        for (int i = tid; i < (int)nb; i += LD_THREADS) zh[i] = d.hist[i];
+    }
+    const float b0 = d.coef[0], b1 = d.coef[1], b2 = d.coef[2], a1 = d.coef[3], a2 = d.coef[4];
+    const float c0 = d.coef[5], c1 = d.coef[6], c2 = d.coef[7], a3 = d.coef[8], a4 = d.coef[9];
+    long long done = 0;
+    while (done < d.n_new) {
+        const int cnt = (int)(d.n_new - done < (long long)(LD_HOP - j0) ? d.n_new - done : (long long)(LD_HOP - j0));
+        const float* x = d.src + done;
+        const float dg = q3::sub_rn(A1, A2);
+        for (int i = tid; i < cnt; i += LD_THREADS) {
+            const float v = x[i];
+            buf[i] = __builtin_isfinite(v) ? v : 0.0f;
+            if (d.w) d.w[done + i] = q3::mul_rn(v, q3::add_rn(A2, q3::mul_rn(dg, __fdiv_rn((float)(j0 + i), (float)LD_HOP))));
+        }
+        __syncthreads();
+        if (tid == 0) {
+            // The high-pass runs one sample behind the shelf, so that the two chains are the two halves of packed f32
+            // operations (.x: the shelf at sample i, .y: the high-pass at sample i - 1): the same operations on the same
+            // operands, each rounded once, at half the instructions a lone lane has to issue.
+            const ld_f2 B0 = {b0, c0}, B1 = {b1, c1}, B2 = {b2, c2}, A1v = {a1, a3}, A2v = {a2, a4};
+            ld_f2 S1 = {f0, f2}, S2 = {f1, f3};
+            float o;
+            {                                                    // the shelf alone at sample 0
+                const float v = buf[0];
+                o = q3::add_rn(q3::mul_rn(b0, v), S1.x);
+                S1.x = q3::add_rn(q3::sub_rn(q3::mul_rn(b1, v), q3::mul_rn(a1, o)), S2.x);
+                S2.x = q3::sub_rn(q3::mul_rn(b2, v), q3::mul_rn(a2, o));
+            }
+            int i = 1;
+            for (; i + 8 <= cnt; i += 8) {                       // (the loads first: the stores below go to words already read)
+                float v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = buf[i + u];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const ld_f2 V = {v[u], o};
+                    const ld_f2 O = ld_add2(ld_mul2(B0, V), S1);
+                    S1 = ld_add2(ld_sub2(ld_mul2(B1, V), ld_mul2(A1v, O)), S2);
+                    S2 = ld_sub2(ld_mul2(B2, V), ld_mul2(A2v, O));
+                    o = O.x; buf[i + u - 1] = O.y;
+                }
+            }
+            for (; i < cnt; ++i) {
+                const ld_f2 V = {buf[i], o};
+                const ld_f2 O = ld_add2(ld_mul2(B0, V), S1);
+                S1 = ld_add2(ld_sub2(ld_mul2(B1, V), ld_mul2(A1v, O)), S2);
+                S2 = ld_sub2(ld_mul2(B2, V), ld_mul2(A2v, O));
+                o = O.x; buf[i - 1] = O.y;
+            }
+            {                                                    // the high-pass alone at the last sample
+                const float k = q3::add_rn(q3::mul_rn(c0, o), S1.y);
+                S1.y = q3::add_rn(q3::sub_rn(q3::mul_rn(c1, o), q3::mul_rn(a3, k)), S2.y);
+                S2.y = q3::sub_rn(q3::mul_rn(c2, o), q3::mul_rn(a4, k));
+                buf[cnt - 1] = k;
+            }
+            f0 = S1.x; f2 = S1.y; f1 = S2.x; f3 = S2.y;
+        }
+        __syncthreads();
+        if (tid < 64)                                            // sample i of the staging is sample j0 + i of the hop
+            for (int i = (tid - j0) & 63; i < cnt; i += 64) part = q3::add_rn(part, q3::mul_rn(buf[i], buf[i]));
+        j0 += cnt; done += cnt;
+        if (j0 < LD_HOP) break;                                  // (the push ends inside the hop)
+        if (tid < 64) {                                          // wave 0: hop h is complete
+            float s = part;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) s = q3::add_rn(s, __shfl_down(s, o));
+            const float e0 = __shfl(s, 0);
+            float An = h < 3 ? d.P : A1, Mn = M; int cgn = cg, en = est;
+            const long long bi = h - 3;
+            if (bi >= 0 && bi < LD_HIST) {
+                const float z = q3::mul_rn(q3::add_rn(q3::add_rn(e3, e2), q3::add_rn(e1, e0)), (float)(1.0 / 9600.0));
+                if (tid == 0) { zh[bi] = z; d.hist[bi] = z; }
+                const int nb = (int)bi + 1;                      // (the newest block from the register: every lane has it)
+                double Sa = 0.0; int ca = 0;
+                for (int i = tid; i < nb; i += 64) { const float zi = i == (int)bi ? z : zh[i]; if (zi > d.gate) { Sa += (double)zi; ++ca; } }
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) { Sa += __shfl_down(Sa, o); ca += __shfl_down(ca, o); }
+                Sa = __shfl(Sa, 0); ca = __shfl(ca, 0);
+                if (ca > 0) {
+                    const double Gr = (0.1 * Sa) / (double)ca;
+                    double Sg = 0.0; int c2n = 0;
+                    for (int i = tid; i < nb; i += 64) { const float zi = i == (int)bi ? z : zh[i]; if (zi > d.gate && (double)zi > Gr) { Sg += (double)zi; ++c2n; } }
+#pragma unroll
+                    for (int o = 32; o >= 1; o >>= 1) { Sg += __shfl_down(Sg, o); c2n += __shfl_down(c2n, o); }
+                    Sg = __shfl(Sg, 0); c2n = __shfl(c2n, 0);
+                    Mn = (float)(Sg / (double)c2n); cgn = c2n; en = 1;
+                }
+                An = en ? fminf(fmaxf(ld_sqrt_rn(__fdiv_rn(d.T, Mn)), d.a_lo), d.a_hi) : A1;
+            }
+            if (tid == 0) { pub[0] = An; pub[1] = Mn; pub[2] = __int_as_float(cgn); pub[3] = __int_as_float(en); }
+            e3 = e2; e2 = e1; e1 = e0; part = 0.0f;
+        }
+        __syncthreads();
+        A2 = A1; A1 = pub[0]; M = pub[1]; cg = __float_as_int(pub[2]); est = __float_as_int(pub[3]);
+        j0 = 0; ++h;
+        __syncthreads();                                         // (pub and buf are written again)
+    }
+    if (tid == 0) {
+        d.st_out[0] = f0; d.st_out[1] = f1; d.st_out[2] = f2; d.st_out[3] = f3;
+        d.st_out[LD_S_E] = e3; d.st_out[LD_S_E + 1] = e2; d.st_out[LD_S_E + 2] = e1;
+        d.st_out[LD_S_A1] = A1; d.st_out[LD_S_A2] = A2; d.st_out[LD_S_M] = M;
+        d.st_out[LD_S_CG] = __int_as_float(cg); d.st_out[LD_S_EST] = __int_as_float(est);
+    }
+    if (tid < 64) d.st_out[4 + tid] = part;
+}
 
 // ---- the time stretcher ----
 constexpr int TP_W = 720, TP_HS = 360, TP_D = 240;             // frame, synthesis hop, search reach
@@ -356,6 +525,10 @@ struct PsRow {
     bool level = false; int gain_mB = 0, ceil_mB = 0; float l_g = 1.0f, l_c = 1.0f;
     long long l_in = 0;
     float* l_tail = nullptr; int l_cur = 0;   // on the device, two copies of LV_TAIL_PITCH floats: the last 254 inputs
+    // the loudness step in front of the level: o_in counts the 24 kHz samples that have passed it
+    int loud = Q3_LOUD_OFF, o_target = -1900, o_prior = 0; float o_T = 0.0f, o_P = 1.0f, o_gate = 0.0f, o_lo = 0.0f, o_hi = 0.0f;
+    long long o_in = 0;
+    float* o_state = nullptr; int o_cur = 0;  // on the device: two copies of LD_STATE floats, then the LD_HIST block values (one copy)
 };
 constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
 struct q3_pcm_stage {
@@ -373,6 +546,10 @@ struct q3_pcm_stage {
     // the level step (all of it allocated by the first row with a level, or the first push of one)
     float* z_dev = nullptr; size_t z_cap = 0;                              // the levelled samples of a push, row after row
     char *ld_dev = nullptr, *ld_host = nullptr; size_t ld_cap = 0;         // k_level's descriptors
+    // the loudness step (all of it allocated by the first row that meters or normalises, or the first push of one)
+    float o_coef[10] = {0}; bool o_coef_set = false;                       // the K-weighting at 24 kHz, f32
+    float* w_dev = nullptr; size_t w_cap = 0;                              // the normalised samples of a push, row after row
+    char *od_dev = nullptr, *od_host = nullptr; size_t od_cap = 0;         // k_loud's descriptors
 };
 
 extern "C" q3_status q3_pcm_stage_taps(uint32_t sample_rate, float* taps_host, size_t cap_floats, int* L, int* M) {
@@ -449,6 +626,48 @@ extern "C" q3_status q3_pcm_stage_bound_level(uint32_t sample_rate, int tempo_pe
     return q3_pcm_stage_bound(sample_rate, (tempo_permille == TP_OFF ? n_in : tempo_y_bound(tempo_permille, n_in)) + LV_D, n_out_max);
 }
 
+extern "C" q3_status q3_loudness_kweight(uint32_t sample_rate, double* shelf_ba, double* highpass_ba) {
+    if (sample_rate < 8000 || sample_rate > 192000) return set_err(Q3_INVALID_ARG, "q3_loudness_kweight: sample rate %u out of range (8000..192000)", sample_rate);
+    if (!shelf_ba || !highpass_ba) return set_err(Q3_INVALID_ARG, "q3_loudness_kweight: null argument");
+    // ITU-R BS.1770's analogue prototypes through the tangent pre-warped bilinear form
+    const double PI = 3.14159265358979323846, fs = (double)sample_rate;
+    {
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = tan(PI * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416), a0 = 1.0 + K / Q + K * K;
+        shelf_ba[0] = (Vh + Vb * K / Q + K * K) / a0; shelf_ba[1] = 2.0 * (K * K - Vh) / a0; shelf_ba[2] = (Vh - Vb * K / Q + K * K) / a0;
+        shelf_ba[3] = 1.0; shelf_ba[4] = 2.0 * (K * K - 1.0) / a0; shelf_ba[5] = (1.0 - K / Q + K * K) / a0;
+    }
+    {
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = tan(PI * f0 / fs), a0 = 1.0 + K / Q + K * K;
+        highpass_ba[0] = 1.0; highpass_ba[1] = -2.0; highpass_ba[2] = 1.0;
+        highpass_ba[3] = 1.0; highpass_ba[4] = 2.0 * (K * K - 1.0) / a0; highpass_ba[5] = (1.0 - K / Q + K * K) / a0;
+    }
+    return Q3_OK;
+}
+
+static q3_status loud_checked(const char* who, int mode, int target_mB, int prior_mB) {
+    if (mode < Q3_LOUD_OFF || mode > Q3_LOUD_NORMALIZE)
+        return set_err(Q3_INVALID_ARG, "%s: mode must be Q3_LOUD_OFF (0), Q3_LOUD_METER (1) or Q3_LOUD_NORMALIZE (2)", who);
+    if (target_mB < LD_TARGET_MIN || target_mB > LD_TARGET_MAX)
+        return set_err(Q3_INVALID_ARG, "%s: target %d mB out of range (%d..%d; -1900 = -19 LUFS)", who, target_mB, LD_TARGET_MIN, LD_TARGET_MAX);
+    if (prior_mB < LD_PRIOR_MIN || prior_mB > LD_PRIOR_MAX)
+        return set_err(Q3_INVALID_ARG, "%s: prior gain %d mB out of range (%d..%d)", who, prior_mB, LD_PRIOR_MIN, LD_PRIOR_MAX);
+    return Q3_OK;
+}
+q3_status pcm_stage_loud_checked(const char* who, int mode, int target_mB, int prior_mB) { return loud_checked(who, mode, target_mB, prior_mB); }
+
+extern "C" q3_status q3_pcm_stage_loudness_consts(int target_mB, int prior_mB, float* T, float* P, float* gate_abs, float* a_lo, float* a_hi) {
+    Q3C(loud_checked("q3_pcm_stage_loudness_consts", Q3_LOUD_OFF, target_mB, prior_mB));
+    // in f64, rounded once
+    if (T) *T = (float)pow(10.0, ((double)target_mB / 100.0 + 0.691) / 10.0);
+    if (P) *P = (float)pow(10.0, (double)prior_mB / 2000.0);
+    if (gate_abs) *gate_abs = (float)pow(10.0, (-70.0 + 0.691) / 10.0);
+    if (a_lo) *a_lo = (float)pow(10.0, -2400.0 / 2000.0);
+    if (a_hi) *a_hi = (float)pow(10.0, 2400.0 / 2000.0);
+    return Q3_OK;
+}
+
 extern "C" q3_status q3_pcm_stage_create(int device, int rows, size_t max_push_samples, q3_pcm_stage** out) {
     if (!out || rows < 1 || max_push_samples < 1) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_create: rows and max_push_samples must be positive");
     if (device < 0) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_create: no device (a manifest-only model has none): the stage runs on the GPU");
@@ -468,8 +687,10 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
     if (ps->st) (void)hipStreamSynchronize(ps->st);
     for (auto& kv : ps->taps) dev_free(kv.second);
     dev_free(ps->tails); dev_free(ps->out_dev); dev_free(ps->in_dev);
-    for (PsRow& r : ps->rows) { dev_free(r.t_state); dev_free(r.t_lags[0]); dev_free(r.t_lags[1]); dev_free(r.l_tail); }
+    for (PsRow& r : ps->rows) { dev_free(r.t_state); dev_free(r.t_lags[0]); dev_free(r.t_lags[1]); dev_free(r.l_tail); dev_free(r.o_state); }
     dev_free(ps->t_win); dev_free(ps->y_dev); dev_free(ps->td_dev); dev_free(ps->z_dev); dev_free(ps->ld_dev);
+    dev_free(ps->w_dev); dev_free(ps->od_dev);
+    if (ps->od_host) (void)hipHostFree(ps->od_host);
     if (ps->td_host) (void)hipHostFree(ps->td_host);
     if (ps->ld_host) (void)hipHostFree(ps->ld_host);
     if (ps->out_host) (void)hipHostFree(ps->out_host);
@@ -485,6 +706,7 @@ void pcm_stage_reset(q3_pcm_stage* ps, int row) {
     r.n_in = r.n_out = 0; r.cur = 0; r.fresh = true; r.ended = false;
     r.t_in = r.t_frames = 0; r.t_lag_k0 = r.t_lag_n = 0;
     r.l_in = 0;
+    r.o_in = 0;
 }
 
 extern "C" q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row) {
@@ -563,6 +785,66 @@ extern "C" q3_status q3_pcm_stage_set_level(q3_pcm_stage* ps, int row, int gain_
     return Q3_OK;
 }
 
+extern "C" q3_status q3_pcm_stage_set_loudness(q3_pcm_stage* ps, int row, int mode, int target_mB, int prior_mB) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_loudness: bad row");
+    Q3C(loud_checked("q3_pcm_stage_set_loudness", mode, target_mB, prior_mB));      // (before the device is touched)
+    PsRow& r = ps->rows[(size_t)row];
+    if (mode != Q3_LOUD_OFF) {
+        if (!ps->o_coef_set) {
+            // the K-weighting at 24 kHz: in f64, rounded once
+            double sh[6], hp[6];
+            Q3C(q3_loudness_kweight(PS_RATE_IN, sh, hp));
+            const double c[10] = {sh[0], sh[1], sh[2], sh[4], sh[5], hp[0], hp[1], hp[2], hp[4], hp[5]};
+            for (int i = 0; i < 10; ++i) ps->o_coef[i] = (float)c[i];
+            ps->o_coef_set = true;
+        }
+        if (!r.o_state) {
+            HIPC(hipSetDevice(ps->device));
+            if (dev_malloc((void**)&r.o_state, (2 * (size_t)LD_STATE + LD_HIST) * 4) != hipSuccess) {
+                (void)hipGetLastError(); r.o_state = nullptr;
+                return set_err(Q3_OOM, "q3_pcm_stage_set_loudness: state of row %d", row);
+            }
+        }
+    }
+    r.loud = mode; r.o_target = target_mB; r.o_prior = prior_mB;
+    (void)q3_pcm_stage_loudness_consts(target_mB, prior_mB, &r.o_T, &r.o_P, &r.o_gate, &r.o_lo, &r.o_hi);
+    pcm_stage_reset(ps, row);
+    return Q3_OK;
+}
+
+// the blocks a row has stored once n samples have passed its loudness step
+static long long loud_blocks(long long n) { return std::min<long long>(LD_HIST, std::max<long long>(0, n / LD_HOP - 3)); }
+
+extern "C" q3_status q3_pcm_stage_loudness(q3_pcm_stage* ps, int row, float* mean_square, float* gain, int* blocks, int* gated) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness: bad row");
+    const PsRow& r = ps->rows[(size_t)row];
+    if (r.loud == Q3_LOUD_OFF) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness: row %d has no loudness step (q3_pcm_stage_set_loudness)", row);
+    float v[4] = {r.o_P, r.o_P, 0.0f, 0.0f};                      // A1 A2 M cg: a row that has taken no sample stands at its prior
+    if (r.o_in > 0) {
+        HIPC(hipSetDevice(ps->device));
+        HIPC(q3_hipMemcpy(v, r.o_state + (size_t)r.o_cur * LD_STATE + LD_S_A1, sizeof(v), hipMemcpyDeviceToHost));
+    }
+    int cg = 0; memcpy(&cg, &v[3], 4);
+    if (mean_square) *mean_square = v[2];
+    if (gain) *gain = v[0];
+    if (blocks) *blocks = (int)loud_blocks(r.o_in);
+    if (gated) *gated = cg;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_loudness_blocks(q3_pcm_stage* ps, int row, float* z, size_t cap, size_t* n) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness_blocks: bad row");
+    if (!n) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness_blocks: null argument");
+    const PsRow& r = ps->rows[(size_t)row];
+    const long long nb = r.loud == Q3_LOUD_OFF ? 0 : loud_blocks(r.o_in);
+    *n = (size_t)nb;
+    if (nb == 0 || (!z && cap == 0)) return Q3_OK;                 // (no buffer: the count alone)
+    if (!z || cap < (size_t)nb) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness_blocks: %lld blocks, the buffer takes %zu", nb, cap);
+    HIPC(hipSetDevice(ps->device));
+    HIPC(q3_hipMemcpy(z, r.o_state + 2 * (size_t)LD_STATE, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
 extern "C" q3_status q3_pcm_stage_tempo_lags(q3_pcm_stage* ps, int row, int64_t* k0, int* lags, size_t cap, size_t* n) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: bad row");
     if (!n) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: null argument");
@@ -611,7 +893,8 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
     plan.desc.clear(); plan.off.assign(segs.size(), 0); plan.count.assign(segs.size(), 0); plan.bytes = 0; plan.max_tiles = 1;
     plan.ps = ps; plan.tdesc.clear(); plan.t_y.assign(segs.size(), 0); plan.t_k1.assign(segs.size(), 0);
     plan.ldesc.clear(); plan.l_in.assign(segs.size(), 0); plan.l_z.assign(segs.size(), 0); plan.l_tiles = 1;
-    std::vector<size_t> y_off(segs.size(), 0), z_off(segs.size(), 0); size_t y_floats = 0, z_floats = 0;
+    plan.odesc.clear(); plan.o_n.clear();
+    std::vector<size_t> y_off(segs.size(), 0), z_off(segs.size(), 0), w_off; size_t y_floats = 0, z_floats = 0, w_floats = 0;
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
         if (sg.n > ps->max_push) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, ps->max_push);
@@ -624,6 +907,13 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
             if (!r.t_state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tempo and no state", sg.row);
             plan.t_y[i] = y_total - (r.level ? r.l_in : r.n_in); plan.t_k1[i] = k1;
             y_off[i] = y_floats; y_floats += ((size_t)plan.t_y[i] + 3) & ~(size_t)3;
+        }
+        if (r.loud != Q3_LOUD_OFF) {
+            // (what passes the step in this push: the stretched samples where the row has a stretcher, else the segment's own)
+            if (!r.o_state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a loudness step and no state", sg.row);
+            if (plan.o_n.empty()) { plan.o_n.assign(segs.size(), 0); w_off.assign(segs.size(), 0); }
+            plan.o_n[i] = y_total - r.o_in;
+            if (r.loud == Q3_LOUD_NORMALIZE) { w_off[i] = w_floats; w_floats += ((size_t)plan.o_n[i] + 3) & ~(size_t)3; }
         }
         if (r.level) {
             if (!r.l_tail) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a level and no state", sg.row);
@@ -644,6 +934,7 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
     }
     if (y_floats > 0) Q3C(dev_grow(ps, (void**)&ps->y_dev, &ps->y_cap, y_floats * 4));
     if (z_floats > 0) Q3C(dev_grow(ps, (void**)&ps->z_dev, &ps->z_cap, z_floats * 4));
+    if (w_floats > 0) Q3C(dev_grow(ps, (void**)&ps->w_dev, &ps->w_cap, w_floats * 4));
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row];
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
@@ -667,8 +958,19 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
             plan.tdesc.push_back(t);
             d.src = t.y; d.n_new = t.n_y;                             // the resampler's input: the stretched samples
         }
+        if (r.loud != Q3_LOUD_OFF && plan.o_n[i] > 0) {
+            LoDesc o{};
+            o.src = d.src; o.w = r.loud == Q3_LOUD_NORMALIZE ? ps->w_dev + w_off[i] : nullptr;
+            o.st_in = r.o_in > 0 ? r.o_state + (size_t)r.o_cur * LD_STATE : nullptr; o.st_out = r.o_state + (size_t)(r.o_cur ^ 1) * LD_STATE;
+            o.hist = r.o_state + 2 * (size_t)LD_STATE;
+            o.base = r.o_in; o.n_new = (int)plan.o_n[i]; o.mode = r.loud;
+            o.T = r.o_T; o.P = r.o_P; o.gate = r.o_gate; o.a_lo = r.o_lo; o.a_hi = r.o_hi;
+            memcpy(o.coef, ps->o_coef, sizeof(o.coef));
+            plan.odesc.push_back(o);
+            if (o.w) d.src = o.w;                                     // the next step's input: the normalised samples (the count stays)
+        }
         if (r.level) {
-            // (the step's input: the stretched samples where the row has a stretcher, else the segment's own)
+            // (the step's input: the samples as they left the steps in front, else the segment's own)
             LvDesc l{};
             l.src = d.src; l.n_new = (int)plan.l_in[i]; l.base = r.l_in; l.n_total = r.l_in + plan.l_in[i];
             l.tail_in = r.l_in > 0 ? r.l_tail + (size_t)r.l_cur * LV_TAIL_PITCH : nullptr;
@@ -709,6 +1011,26 @@ hipError_t pcm_stage_launch(const PsDesc* desc_dev, const PsPlan& plan, hipStrea
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
+    if (!plan.odesc.empty()) {
+        // the rows that meter or normalise, between the stretcher and the level: descriptors as above, one workgroup per row
+        q3_pcm_stage* ps = plan.ps;
+        const size_t ob = plan.odesc.size() * sizeof(LoDesc);
+        if (ob > ps->od_cap) {
+            dev_free(ps->od_dev); ps->od_dev = nullptr;
+            if (ps->od_host) { (void)hipHostFree(ps->od_host); ps->od_host = nullptr; }
+            ps->od_cap = 0;
+            hipError_t e = dev_malloc((void**)&ps->od_dev, ob * 2);
+            if (e == hipSuccess) e = hipHostMalloc((void**)&ps->od_host, ob * 2, hipHostMallocDefault);
+            if (e != hipSuccess) return e;
+            ps->od_cap = ob * 2;
+        }
+        memcpy(ps->od_host, plan.odesc.data(), ob);
+        hipError_t e = hipMemcpyAsync(ps->od_dev, ps->od_host, ob, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_loud, dim3((unsigned)plan.odesc.size()), dim3(LD_THREADS), 0, st, (const LoDesc*)ps->od_dev);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     if (!plan.ldesc.empty()) {
         // the rows with a level next, directly in front of the resampler: descriptors as above, a workgroup per tile of 256 outputs
         q3_pcm_stage* ps = plan.ps;
@@ -741,6 +1063,7 @@ void pcm_stage_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const Ps
             r.t_lag_cur ^= 1; r.t_lag_k0 = r.t_frames; r.t_lag_n = plan.t_k1[i] - r.t_frames;
             r.t_in += (long long)sg.n; r.t_frames = plan.t_k1[i]; r.t_cur ^= 1;
         }
+        if (r.loud != Q3_LOUD_OFF && plan.o_n[i] > 0) { r.o_in += plan.o_n[i]; r.o_cur ^= 1; }
         if (r.level) { r.l_in += plan.l_in[i]; r.n_in += plan.l_z[i]; if (!sg.last) r.l_cur ^= 1; }
         else r.n_in += r.tempo != TP_OFF ? plan.t_y[i] : (long long)sg.n;
         r.n_out += (long long)plan.count[i];

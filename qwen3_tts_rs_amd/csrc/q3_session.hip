@@ -1824,6 +1824,38 @@ extern "C" q3_status q3_session_set_level(q3_session* s, int b, int gain_mB, int
     }
     return Q3_OK;
 }
+extern "C" q3_status q3_session_set_loudness(q3_session* s, int b, int mode, int target_mB, int prior_mB) {
+    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_loudness: null session");
+    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_loudness: row %d out of range (%d rows; -1 = every row)", b, s->B);
+    Q3C(pcm_stage_loud_checked("q3_session_set_loudness", mode, target_mB, prior_mB));
+    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_loudness: the model has no device");
+    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
+    for (int r = b0; r < b1; ++r)
+        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
+            return set_err(Q3_INVALID_ARG, "q3_session_set_loudness: row %d has streamed its first chunk: the loudness step is set before it, or after q3_session_replace", r);
+    if (s->out_loud.empty()) { s->out_loud.assign((size_t)s->B * 3, 0); for (int r = 0; r < s->B; ++r) s->out_loud[(size_t)r * 3 + 1] = -1900; }
+    for (int r = b0; r < b1; ++r) {
+        if (s->ostage) Q3C(q3_pcm_stage_set_loudness(s->ostage, r, mode, target_mB, prior_mB));
+        s->out_loud[(size_t)r * 3] = mode; s->out_loud[(size_t)r * 3 + 1] = target_mB; s->out_loud[(size_t)r * 3 + 2] = prior_mB;
+    }
+    return Q3_OK;
+}
+extern "C" q3_status q3_session_loudness(q3_session* s, int b, float* mean_square, float* gain, int* blocks, int* gated) {
+    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_loudness: null session");
+    if (b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_loudness: row %d out of range (%d rows)", b, s->B);
+    if (s->out_loud.empty() || s->out_loud[(size_t)b * 3] == Q3_LOUD_OFF)
+        return set_err(Q3_INVALID_ARG, "q3_session_loudness: row %d has no loudness step (q3_session_set_loudness)", b);
+    if (!s->ostage) {                                              // nothing streamed yet: the row stands at its prior
+        float P = 1.0f;
+        (void)q3_pcm_stage_loudness_consts(s->out_loud[(size_t)b * 3 + 1], s->out_loud[(size_t)b * 3 + 2], nullptr, &P, nullptr, nullptr, nullptr);
+        if (mean_square) *mean_square = 0.0f;
+        if (gain) *gain = P;
+        if (blocks) *blocks = 0;
+        if (gated) *gated = 0;
+        return Q3_OK;
+    }
+    return q3_pcm_stage_loudness(s->ostage, b, mean_square, gain, blocks, gated);
+}
 extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_host, const size_t* cap_samples, size_t* n_samples, int* done) {
     if (!s) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null session");
     if (!n_samples || !done || !out_host || !cap_samples) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null argument");
@@ -1837,6 +1869,9 @@ extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_
         for (int b = 0; b < s->B && !s->out_level.empty(); ++b)
             if (s->out_level[(size_t)b * 2] != 0 || s->out_level[(size_t)b * 2 + 1] != 0)
                 Q3C(q3_pcm_stage_set_level(s->ostage, b, s->out_level[(size_t)b * 2], s->out_level[(size_t)b * 2 + 1]));
+        for (int b = 0; b < s->B && !s->out_loud.empty(); ++b)
+            if (s->out_loud[(size_t)b * 3] != Q3_LOUD_OFF)
+                Q3C(q3_pcm_stage_set_loudness(s->ostage, b, s->out_loud[(size_t)b * 3], s->out_loud[(size_t)b * 3 + 1], s->out_loud[(size_t)b * 3 + 2]));
     }
     s->out_started = true;
     return next_chunks(s, nullptr, cap_samples, n_samples, done, true, out_host);

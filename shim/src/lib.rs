@@ -128,6 +128,16 @@ pub mod ffi {
         pub fn q3_pcm_stage_bound_level(sample_rate: u32, tempo_permille: i32, n_in: usize, n_out_max: *mut usize) -> i32;
         pub fn q3_session_set_level(s: *mut c_void, b: i32, gain_mb: i32, ceiling_mb: i32) -> i32;
         pub fn q3_batcher_ticket_level(b: *mut c_void, ticket: i64, gain_mb: i32, ceiling_mb: i32) -> i32;
+        // the output stage's loudness step: a BS.1770 meter and normaliser per row; mode 0 off, 1 meter, 2 normalise
+        pub fn q3_loudness_kweight(sample_rate: u32, shelf_ba: *mut f64, highpass_ba: *mut f64) -> i32;
+        pub fn q3_pcm_stage_loudness_consts(target_mb: i32, prior_mb: i32, t: *mut f32, p: *mut f32, gate_abs: *mut f32, a_lo: *mut f32, a_hi: *mut f32) -> i32;
+        pub fn q3_pcm_stage_set_loudness(ps: *mut c_void, row: i32, mode: i32, target_mb: i32, prior_mb: i32) -> i32;
+        pub fn q3_pcm_stage_loudness(ps: *mut c_void, row: i32, mean_square: *mut f32, gain: *mut f32, blocks: *mut i32, gated: *mut i32) -> i32;
+        pub fn q3_pcm_stage_loudness_blocks(ps: *mut c_void, row: i32, z: *mut f32, cap: usize, n: *mut usize) -> i32;
+        pub fn q3_session_set_loudness(s: *mut c_void, b: i32, mode: i32, target_mb: i32, prior_mb: i32) -> i32;
+        pub fn q3_session_loudness(s: *mut c_void, b: i32, mean_square: *mut f32, gain: *mut f32, blocks: *mut i32, gated: *mut i32) -> i32;
+        pub fn q3_batcher_ticket_loudness(b: *mut c_void, ticket: i64, mode: i32, target_mb: i32, prior_mb: i32) -> i32;
+        pub fn q3_batcher_ticket_loudness_read(b: *mut c_void, ticket: i64, mean_square: *mut f32, gain: *mut f32, blocks: *mut i32, gated: *mut i32) -> i32;
     }
 }
 use ffi::*;
