@@ -750,6 +750,45 @@ q3_status q3_session_loudness(q3_session* s, int b, float* mean_square, float* g
  * ticket done, valid until q3_batcher_fetch releases it. */
 q3_status q3_batcher_ticket_loudness(q3_batcher* b, int64_t ticket, int mode, int target_mB, int prior_mB);
 q3_status q3_batcher_ticket_loudness_read(q3_batcher* b, int64_t ticket, float* mean_square, float* gain, int* blocks, int* gated);
+/* ---------------- output stage: a pitch per row in cents (a varispeed step behind the time stretcher) ----------------
+ * cents in -1200..1200; 0, the default, is off: such a row takes the paths above and returns their bits and their launches. With the
+ * row's tempo t (q3_pcm_stage_set_tempo; 1000 by default) and p = 2^(cents / 1200) in f64, te = llround(t / p) must lie in 500..2000,
+ * else Q3_INVALID_ARG before the device is touched: whichever of _set_tempo / _set_pitch comes second refuses and changes nothing.
+ * The stretcher then runs at te in the place of t (not at all when te = 1000; q3_pcm_stage_tempo_lags reports the lags of te), and
+ * where te != t its output y is resampled by te / t, which brings the duration back to t's and moves the pitch by t / te — within
+ * 1.8 cents of the request. Varispeed compensated by time stretching: formants move with the pitch; +-300 cents is the useful
+ * range for natural speech, +-1200 is accepted; a formant-preserving shifter is out of scope.
+ * The step is q3_resample's filter at sr_in = t, sr_out = te: output j sits at input time j t / te, cj = floor(j t / te),
+ * r = (j t) mod te, taps over the inputs cj + k, k = -63 .. 64, at tau = r / te - k: h = fc sinc(fc tau) w^2(tau / 64),
+ * fc = 0.95 min(1, te / t), w the Blackman-Harris window (0 from |tau| = 64 on). The taps come from two tables, f64 rounded to
+ * f32: Sc[m] = sinc(m / S1), m = 0 .. 61 S1 + 1, and W2[m] = w^2(m / (64 S2)), m = 0 .. 64 S2 + 1, S1 = 512, S2 = 64. With
+ * q = |r - k te| the sinc is read at 19 q S1 / (20 max(t, te)) and the window at q S2 / te, each split in integers into an index m
+ * and a remainder, f = (float)rem / (float)den correctly rounded; then, every operation rounded once,
+ *   s = fma(f1, Sc[m1 + 1] - Sc[m1], Sc[m1]);  w = fma(f2, W2[m2 + 1] - W2[m2], W2[m2]);  a[k mod 4] = fma(s w, x[cj + k], a[k mod 4])
+ * in ascending k, and v[j] = (float)fc ((a0 + a1) + (a2 + a3)). Inputs outside [0, N_y) are zeros.
+ * Streaming rule, the resampler's with y in the place of its input: after F final samples of y every j with
+ * floor(j t / te) + 64 <= F - 1 is out; a push with `last` returns the rest, up to floor((2 N_y te + t) / (2 t)) in total (within 2
+ * samples of the row's count without a pitch). The steps behind (loudness, level, resampler) take v as their input stream. The row
+ * keeps its last 128 samples of y under the commit rule of the tails. The tables (138 KB, one pair per stage) and a row's tail are
+ * allocated by the first pitch that moves a tempo. No reference counterpart (Qwen3-TTS has no pitch input). */
+q3_status q3_pcm_stage_set_pitch(q3_pcm_stage* ps, int row, int cents);                    /* also restarts the row; kept by _set / _reset / every _set_* */
+/* host only: te and the pitch the row then has, 1200 log2(t / te) cents (either may be NULL) */
+q3_status q3_pcm_stage_pitch_plan(int tempo_permille, int cents, int* tempo_eff, double* cents_realized);
+/* host only (test hook): S1, S2 and the two tables as the stage uploads them: 61 S1 + 2 and 64 S2 + 2 floats (either buffer may
+ * be NULL; both NULL: S1 / S2 alone) */
+q3_status q3_pcm_stage_pitch_tables(float* sinc, size_t cap1, float* win, size_t cap2, int* S1, int* S2);
+/* host only: the streaming rule — 24 kHz samples behind the stretcher and the pitch step after n_in_total input samples */
+q3_status q3_pcm_stage_pitch_count(int tempo_permille, int cents, size_t n_in_total, int ended, size_t* samples_24k);
+/* host only: cap for a push of n_in new samples to a row at this rate, tempo and pitch (with_level: and a level), wherever the
+ * row stands and with `last`; at 0 cents q3_pcm_stage_bound_tempo's / _bound_level's value */
+q3_status q3_pcm_stage_bound_pitch(uint32_t sample_rate, int tempo_permille, int cents, int with_level, size_t n_in, size_t* n_out_max);
+/* Sessions: the pitch of row b's stage row (b = -1: every row) in q3_session_next_chunks_out; q3_session_set_tempo's window and
+ * persistence; a pitch the row's tempo does not admit (or, in q3_session_set_tempo, a tempo its pitch does not admit) is
+ * Q3_INVALID_ARG and then no row changes. */
+q3_status q3_session_set_pitch(q3_session* s, int b, int cents);
+/* Batcher: a streamed ticket's pitch; the window and the read of q3_batcher_ticket_tempo. A slot's next owner gets its own setting,
+ * off included; a parked streamed ticket keeps its stage row. */
+q3_status q3_batcher_ticket_pitch(q3_batcher* b, int64_t ticket, int cents);
 /* codes_to_tensor (lib.rs:1417-1431): [n][16] u32 → [16][n] i64 (host helper) */
 void      q3_codes_to_tensor(const uint32_t* frames, int n_frames, int64_t* out);
 

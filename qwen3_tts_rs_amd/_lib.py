@@ -135,6 +135,13 @@ SYMBOLS = {
     "q3_pcm_stage_tempo_lags": (c_int, [c_void_p, c_int, P(ctypes.c_int64), c_void_p, ctypes.c_size_t, P(ctypes.c_size_t)]),
     "q3_session_set_tempo": (c_int, [c_void_p, c_int, c_int]),
     "q3_batcher_ticket_tempo": (c_int, [c_void_p, ctypes.c_int64, c_int]),
+    "q3_pcm_stage_set_pitch": (c_int, [c_void_p, c_int, c_int]),
+    "q3_pcm_stage_pitch_plan": (c_int, [c_int, c_int, P(c_int), P(ctypes.c_double)]),
+    "q3_pcm_stage_pitch_tables": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, P(c_int), P(c_int)]),
+    "q3_pcm_stage_pitch_count": (c_int, [c_int, c_int, ctypes.c_size_t, c_int, P(ctypes.c_size_t)]),
+    "q3_pcm_stage_bound_pitch": (c_int, [ctypes.c_uint32, c_int, c_int, c_int, ctypes.c_size_t, P(ctypes.c_size_t)]),
+    "q3_session_set_pitch": (c_int, [c_void_p, c_int, c_int]),
+    "q3_batcher_ticket_pitch": (c_int, [c_void_p, ctypes.c_int64, c_int]),
     "q3_pcm_stage_set_level": (c_int, [c_void_p, c_int, c_int, c_int]),
     "q3_pcm_stage_level_coeffs": (c_int, [c_int, c_int, P(ctypes.c_float), P(ctypes.c_float)]),
     "q3_pcm_stage_level_count": (c_int, [ctypes.c_size_t, c_int, P(ctypes.c_size_t)]),

@@ -317,6 +317,17 @@ class Session:
             t[r] = int(tempo_permille)
         self._tempo = t
 
+    def set_pitch(self, cents: int, b: int = -1):
+        """The pitch of row b (-1: every row) in `next_chunks_out` (q3_session_set_pitch): -1200..1200 cents, 0 = off; the row's
+        duration stays that of its tempo. Varispeed behind the time stretcher: formants move with the pitch, +-300 cents is the
+        useful range for speech. The window and the persistence of `set_tempo`; a pitch that the row's tempo does not admit (the
+        stretcher would leave 500..2000) is refused."""
+        check(lib.q3_session_set_pitch(self._h, int(b), int(cents)))
+        c = getattr(self, "_pitch", None) or [0] * self.B
+        for r in (range(self.B) if int(b) < 0 else [int(b)]):
+            c[r] = int(cents)
+        self._pitch = c
+
     def next_chunks_out(self) -> List[Tuple[Optional[AudioBuffer], bool]]:
         """`next_chunks` through the session's output stage (q3_session_next_chunks_out): one (chunk or None, done) per row, the
         chunks at the rate of `set_output`, int16 arrays when it asked for them. A row's last samples (the resampler holds 64
@@ -325,9 +336,10 @@ class Session:
         rate, s16 = getattr(self, "_out", (24000, False))
         tempo = getattr(self, "_tempo", None) or [1000] * B
         level = getattr(self, "_level", None) or [False] * B
+        pitch = getattr(self, "_pitch", None) or [0] * B
         n_in = max(self.options.chunk_frames, 1) * spf
-        cap = {k: pcm_stage_bound(rate, n_in, k[0], k[1]) for k in set(zip(tempo, level))}
-        bufs = [np.zeros(cap[(tempo[b], level[b])], dtype=PCM_DTYPE[int(s16)]) for b in range(B)]
+        cap = {k: pcm_stage_bound(rate, n_in, k[0], k[1], k[2]) for k in set(zip(tempo, level, pitch))}
+        bufs = [np.zeros(cap[(tempo[b], level[b], pitch[b])], dtype=PCM_DTYPE[int(s16)]) for b in range(B)]
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data_as(ctypes.c_void_p) for b in bufs])
         caps = (ctypes.c_size_t * B)(*[b.size for b in bufs])
         n = (ctypes.c_size_t * B)(); d = (ctypes.c_int * B)()
@@ -547,19 +559,20 @@ class Batcher:
 
     def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False, tempo_permille: int = 1000,
                         fmt: Optional[str] = None, gain_mb: int = 0, ceiling_mb: int = 0, target_lufs: Optional[float] = None,
-                        prior_gain_db: float = 0.0) -> int:
+                        prior_gain_db: float = 0.0, pitch_cents: int = 0) -> int:
         """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16 / fmt: the
         ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked, uint8 for
         fmt "ulaw" / "alaw". tempo_permille: its speaking rate (q3_batcher_ticket_tempo; 1250 = 1.25 x as fast, 1000 = off).
         gain_mb / ceiling_mb: its level (q3_batcher_ticket_level; millibel, (0, 0) = off). target_lufs: the loudness it is steered
-        to, from the gain prior_gain_db (q3_batcher_ticket_loudness; `loudness(ticket)` reads the result)."""
+        to, from the gain prior_gain_db (q3_batcher_ticket_loudness; `loudness(ticket)` reads the result). pitch_cents: its pitch
+        (q3_batcher_ticket_pitch; -1200..1200, 0 = off)."""
         code = pcm_format(pcm16, fmt)
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
         t = ctypes.c_int64()
         check(lib.q3_batcher_submit_streamed(self._h, ctypes.byref(r), ctypes.byref(t)))
         self._streamed.add(int(t.value))
-        self._set_output(int(t.value), sample_rate, code, tempo_permille, gain_mb, ceiling_mb)
+        self._set_output(int(t.value), sample_rate, code, tempo_permille, gain_mb, ceiling_mb, pitch_cents)
         if target_lufs is not None:
             try:
                 self.ticket_loudness(int(t.value), LOUD_NORMALIZE, int(round(float(target_lufs) * 100.0)), int(round(float(prior_gain_db) * 100.0)))
@@ -568,15 +581,18 @@ class Batcher:
                 raise
         return int(t.value)
 
-    def _set_output(self, ticket: int, sample_rate: int, code: int, tempo_permille: int = 1000, gain_mb: int = 0, ceiling_mb: int = 0):
+    def _set_output(self, ticket: int, sample_rate: int, code: int, tempo_permille: int = 1000, gain_mb: int = 0, ceiling_mb: int = 0,
+                    pitch_cents: int = 0):
         code = int(code); level = bool(int(gain_mb) or int(ceiling_mb))
-        if int(sample_rate) == 24000 and not code and int(tempo_permille) == 1000 and not level:
+        if int(sample_rate) == 24000 and not code and int(tempo_permille) == 1000 and not level and not int(pitch_cents):
             return
         try:
             if int(sample_rate) != 24000 or code:
                 self.ticket_output(ticket, sample_rate, fmt=PCM_NAMES[code])
             if int(tempo_permille) != 1000:
                 self.ticket_tempo(ticket, tempo_permille)
+            if int(pitch_cents):
+                self.ticket_pitch(ticket, pitch_cents)
             if level:
                 self.ticket_level(ticket, gain_mb, ceiling_mb)
         except _lib.Q3Error:
@@ -615,6 +631,12 @@ class Batcher:
         """A streamed ticket's speaking rate (q3_batcher_ticket_tempo): between its submission and the next `step`."""
         check(lib.q3_batcher_ticket_tempo(self._h, int(ticket), int(tempo_permille)))
         if int(tempo_permille) != 1000:
+            self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
+
+    def ticket_pitch(self, ticket: int, cents: int):
+        """A streamed ticket's pitch in cents (q3_batcher_ticket_pitch): between its submission and the next `step`."""
+        check(lib.q3_batcher_ticket_pitch(self._h, int(ticket), int(cents)))
+        if int(cents):
             self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
 
     def submit_open(self, utt: Utterance, want: str = "stream", sample_rate: int = 24000, pcm16: bool = False,
@@ -1308,11 +1330,14 @@ def pcm_stage_taps(rate: int) -> Tuple[np.ndarray, int, int]:
     return t, L.value, M.value
 
 
-def pcm_stage_bound(rate: int, n_in: int, tempo_permille: int = 1000, level: bool = False) -> int:
+def pcm_stage_bound(rate: int, n_in: int, tempo_permille: int = 1000, level: bool = False, pitch_cents: int = 0) -> int:
     """The most samples one push of n_in 24 kHz samples returns at `rate` (q3_pcm_stage_bound), for a row at tempo_permille
-    (q3_pcm_stage_bound_tempo) and, with `level`, one that has a level (q3_pcm_stage_bound_level)."""
+    (q3_pcm_stage_bound_tempo), with `level` one that has a level (q3_pcm_stage_bound_level), with pitch_cents one that has a pitch
+    (q3_pcm_stage_bound_pitch)."""
     n = ctypes.c_size_t()
-    if level:
+    if int(pitch_cents):
+        check(lib.q3_pcm_stage_bound_pitch(int(rate), int(tempo_permille), int(pitch_cents), 1 if level else 0, int(n_in), ctypes.byref(n)))
+    elif level:
         check(lib.q3_pcm_stage_bound_level(int(rate), int(tempo_permille), int(n_in), ctypes.byref(n)))
     elif int(tempo_permille) == 1000:
         check(lib.q3_pcm_stage_bound(int(rate), int(n_in), ctypes.byref(n)))
@@ -1326,6 +1351,31 @@ def pcm_stage_tempo_count(tempo_permille: int, n_in_total: int, ended: bool = Fa
     f = ctypes.c_size_t(); y = ctypes.c_size_t()
     check(lib.q3_pcm_stage_tempo_count(int(tempo_permille), int(n_in_total), 1 if ended else 0, ctypes.byref(f), ctypes.byref(y)))
     return int(f.value), int(y.value)
+
+
+def pcm_stage_pitch_plan(tempo_permille: int, cents: int) -> Tuple[int, float]:
+    """(the tempo the stretcher runs at, the pitch in cents the row then has) for a row at tempo_permille asked for `cents`
+    (q3_pcm_stage_pitch_plan); a combination the stretcher cannot serve raises."""
+    te = ctypes.c_int(); c = ctypes.c_double()
+    check(lib.q3_pcm_stage_pitch_plan(int(tempo_permille), int(cents), ctypes.byref(te), ctypes.byref(c)))
+    return int(te.value), float(c.value)
+
+
+def pcm_stage_pitch_tables() -> Tuple[np.ndarray, np.ndarray, int, int]:
+    """(Sc, W2, S1, S2): the pitch step's sinc and squared-window tables as the stage uploads them (q3_pcm_stage_pitch_tables)."""
+    s1 = ctypes.c_int(); s2 = ctypes.c_int()
+    check(lib.q3_pcm_stage_pitch_tables(None, 0, None, 0, ctypes.byref(s1), ctypes.byref(s2)))
+    sc = np.zeros(61 * s1.value + 2, np.float32); w2 = np.zeros(64 * s2.value + 2, np.float32)
+    check(lib.q3_pcm_stage_pitch_tables(sc.ctypes.data_as(ctypes.c_void_p), sc.size, w2.ctypes.data_as(ctypes.c_void_p), w2.size,
+                                        ctypes.byref(s1), ctypes.byref(s2)))
+    return sc, w2, s1.value, s2.value
+
+
+def pcm_stage_pitch_count(tempo_permille: int, cents: int, n_in_total: int, ended: bool = False) -> int:
+    """24 kHz samples that have left the stretcher and the pitch step after n_in_total input samples (q3_pcm_stage_pitch_count)."""
+    n = ctypes.c_size_t()
+    check(lib.q3_pcm_stage_pitch_count(int(tempo_permille), int(cents), int(n_in_total), 1 if ended else 0, ctypes.byref(n)))
+    return int(n.value)
 
 
 def pcm_stage_level_coeffs(gain_mb: int, ceiling_mb: int) -> Tuple[np.float32, np.float32]:
@@ -1387,6 +1437,7 @@ class PcmStage:
         self._fmt = [(24000, PCM_F32)] * self.rows
         self._tempo = [1000] * self.rows
         self._level = [False] * self.rows
+        self._pitch = [0] * self.rows
         self._h = ctypes.c_void_p()
         check(lib.q3_pcm_stage_create(self.device_index, self.rows, self.max_push_samples, ctypes.byref(self._h)))
 
@@ -1407,6 +1458,13 @@ class PcmStage:
         row. `set` and `reset` keep it."""
         check(lib.q3_pcm_stage_set_tempo(self._h, int(row), int(tempo_permille)))
         self._tempo[int(row)] = int(tempo_permille)
+
+    def set_pitch(self, row: int, cents: int):
+        """Row's pitch (q3_pcm_stage_set_pitch): -1200..1200 cents, 0 = off; also restarts the row. The stretcher then runs at
+        `pcm_stage_pitch_plan(tempo, cents)[0]` and a varispeed step behind it brings the duration back: formants move with the
+        pitch. Refused where that tempo leaves 500..2000. `set`, `reset` and the other `set_*` keep it."""
+        check(lib.q3_pcm_stage_set_pitch(self._h, int(row), int(cents)))
+        self._pitch[int(row)] = int(cents)
 
     def set_loudness(self, row: int, mode: int, target_mb: int = -1900, prior_mb: int = 0):
         """Row's loudness step (q3_pcm_stage_set_loudness): LOUD_OFF, LOUD_METER (measure, the samples pass) or LOUD_NORMALIZE
@@ -1446,7 +1504,7 @@ class PcmStage:
         return PCM_DTYPE[self._fmt[int(row)][1]]
 
     def bound(self, row: int, n_in: int) -> int:
-        return pcm_stage_bound(self._fmt[int(row)][0], n_in, self._tempo[int(row)], self._level[int(row)])
+        return pcm_stage_bound(self._fmt[int(row)][0], n_in, self._tempo[int(row)], self._level[int(row)], self._pitch[int(row)])
 
     def push(self, samples: dict, last=()) -> dict:
         """{row: 24 kHz f32 samples} -> {row: samples at the row's rate and format}, every row in one pass; rows in `last` are
@@ -1477,11 +1535,12 @@ class PcmStage:
 
 
 def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_permille: int = 1000, fmt: Optional[str] = None,
-                 gain_mb: int = 0, ceiling_mb: int = 0, target_mb: Optional[int] = None, prior_mb: int = 0) -> AudioBuffer:
+                 gain_mb: int = 0, ceiling_mb: int = 0, target_mb: Optional[int] = None, prior_mb: int = 0, pitch_cents: int = 0) -> AudioBuffer:
     """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked (fmt: "f32" /
     "s16" / "ulaw" / "alaw") — what a caller of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their
     result. tempo_permille: the clip's speaking rate (1250 = 1.25 x as fast, 1000 = as it is). gain_mb / ceiling_mb: its level. target_mb / prior_mb: the loudness it is
-    steered to (millibel of LUFS) and the gain it starts from — a causal normaliser: the first 400 ms leave at the prior."""
+    steered to (millibel of LUFS) and the gain it starts from — a causal normaliser: the first 400 ms leave at the prior.
+    pitch_cents: its pitch (-1200..1200 cents, 0 = as it is; the duration stays that of the tempo)."""
     code = pcm_format(pcm16, fmt)
     x = np.ascontiguousarray(audio.samples if isinstance(audio, AudioBuffer) else audio, dtype=np.float32).reshape(-1)
     if isinstance(audio, AudioBuffer) and audio.sample_rate != 24000:
@@ -1491,6 +1550,8 @@ def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_p
         ps.set(0, rate, fmt=PCM_NAMES[code])
         if int(tempo_permille) != 1000:
             ps.set_tempo(0, tempo_permille)
+        if int(pitch_cents):
+            ps.set_pitch(0, pitch_cents)
         if int(gain_mb) or int(ceiling_mb):
             ps.set_level(0, gain_mb, ceiling_mb)
         if target_mb is not None:

@@ -59,6 +59,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--tempo", type=float, default=1.0, metavar="X",
                     help="with --streaming: the speaking rate, 0.5 .. 2.0 (1.25 = 1.25 x as fast), applied by the output stage's time "
                          "stretcher as the chunks leave")
+    ap.add_argument("--pitch", type=float, default=0.0, metavar="SEMITONES",
+                    help="with --streaming: the pitch, -12 .. +12 semitones, applied by the output stage (varispeed behind the time "
+                         "stretcher: the duration stays, formants move with the pitch; +-3 is the useful range for speech)")
     ap.add_argument("--output-format", choices=["f32", "s16", "ulaw", "alaw"], default="f32",
                     help="with --streaming: the format the chunks leave the output stage in; ulaw / alaw (ITU-T G.711, one byte per "
                          "sample) write a G.711 WAV (format tag 7 / 6)")
@@ -302,6 +305,10 @@ def main(argv=None) -> int:
     if tempo != 1000 and not a.streaming:
         print("error: --tempo applies to --streaming (stretch a whole utterance with api.resample_gpu(..., tempo_permille=))", file=sys.stderr)
         return 2
+    cents = int(round(a.pitch * 100.0))
+    if cents != 0 and not a.streaming:
+        print("error: --pitch applies to --streaming (shift a whole utterance with api.resample_gpu(..., pitch_cents=))", file=sys.stderr)
+        return 2
     gain_mb, ceiling_mb = int(round(a.gain_db * 100.0)), int(round(a.ceiling_db * 100.0))
     if loud is not None:
         ceiling_mb = loud[2]
@@ -310,13 +317,15 @@ def main(argv=None) -> int:
         print("error: --output-format / --gain-db / --ceiling-db apply to --streaming (convert a whole utterance with "
               "api.resample_gpu(..., fmt=, gain_mb=, ceiling_mb=))", file=sys.stderr)
         return 2
-    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None):
+    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None):
         # the chunks of the streaming session, each through the session's output stage as it leaves
         s = model.session([utt], opts)
         try:
             s.set_output(a.output_rate, fmt=a.output_format)
             if tempo != 1000:
                 s.set_tempo(tempo)
+            if cents != 0:
+                s.set_pitch(cents)
             if gain_mb or ceiling_mb:
                 s.set_level(gain_mb, ceiling_mb)
             if loud is not None:

@@ -179,9 +179,10 @@ struct BatTicket {
     // worker's mutex, like spcm, which stays empty) and leave through q3_batcher_read_out alone.
     long born = 0; uint32_t o_rate = 24000; int o_fmt = Q3_PCM_F32; bool o_conv = false; int o_tempo = 1000;      // (q3_batcher_ticket_tempo: the stage too)
     int o_gain = 0, o_ceil = 0;                       // (q3_batcher_ticket_level: the stage too)
+    int o_pitch = 0;                                  // (q3_batcher_ticket_pitch, cents: the stage too)
     // (q3_batcher_ticket_loudness: the stage too; lo_*: the reading after the parts that have landed, under the worker's mutex)
     int o_loud = Q3_LOUD_OFF, o_target = -1900, o_prior = 0; float lo_M = 0.0f, lo_gain = 1.0f; int lo_blocks = 0, lo_gated = 0;
-    bool o_stage() const { return o_rate != 24000 || o_fmt != Q3_PCM_F32 || o_tempo != 1000 || o_gain != 0 || o_ceil != 0 || o_loud != Q3_LOUD_OFF; }
+    bool o_stage() const { return o_rate != 24000 || o_fmt != Q3_PCM_F32 || o_tempo != 1000 || o_pitch != 0 || o_gain != 0 || o_ceil != 0 || o_loud != Q3_LOUD_OFF; }
     std::vector<char> sout; size_t o_read = 0;
     size_t o_bytes() const { return o_fmt == Q3_PCM_F32 ? 4 : o_fmt == Q3_PCM_S16 ? 2 : 1; }
     // Parking (q3_batcher_set_parking; host thread). rec: the ticket's row as a record while it reads PARKED; want_in: it
@@ -362,7 +363,9 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
                 q3_status so = Q3_OK;
                 if (!d.ps) so = q3_pcm_stage_create(m->device, b->stream_rows(), (size_t)std::min(b->frame_budget + b->prompt_budget, 100000) * spf, &d.ps);
                 if (so == Q3_OK) so = q3_pcm_stage_set(d.ps, p.row, t.o_rate, t.o_fmt);
+                if (so == Q3_OK) so = q3_pcm_stage_set_pitch(d.ps, p.row, 0);      // (the row may have had another ticket's, which need not admit this tempo)
                 if (so == Q3_OK) so = q3_pcm_stage_set_tempo(d.ps, p.row, t.o_tempo);      // (1000 too: the row may have had another ticket's)
+                if (so == Q3_OK && t.o_pitch != 0) so = q3_pcm_stage_set_pitch(d.ps, p.row, t.o_pitch);
                 if (so == Q3_OK) so = q3_pcm_stage_set_level(d.ps, p.row, t.o_gain, t.o_ceil);      // (off too, for the same reason)
                 if (so == Q3_OK) so = q3_pcm_stage_set_loudness(d.ps, p.row, t.o_loud, t.o_target, t.o_prior);      // (off too)
                 if (so != Q3_OK) fail(t, so, q3_last_error());
@@ -1261,9 +1264,23 @@ extern "C" q3_status q3_batcher_ticket_tempo(q3_batcher* b, int64_t ticket, int 
     if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: ticket %lld was not submitted as streamed", (long long)ticket);
     if (tempo_permille < 500 || tempo_permille > 2000)
         return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: tempo %d permille out of range (500..2000; 1000 = off)", tempo_permille);
+    if (t.o_pitch != 0) Q3C(pcm_stage_pitch_checked("q3_batcher_ticket_tempo", tempo_permille, t.o_pitch));      // (its pitch has to admit the tempo)
     if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
         return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: ticket %lld has been through a step: its tempo is set between its submission and the next q3_batcher_step", (long long)ticket);
     t.o_tempo = tempo_permille; t.o_conv = t.o_stage();
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_ticket_pitch(q3_batcher* b, int64_t ticket, int cents) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_pitch: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_pitch: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_pitch: ticket %lld was not submitted as streamed", (long long)ticket);
+    Q3C(pcm_stage_pitch_checked("q3_batcher_ticket_pitch", t.o_tempo, cents));
+    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_pitch: ticket %lld has been through a step: its pitch is set between its submission and the next q3_batcher_step", (long long)ticket);
+    t.o_pitch = cents; t.o_conv = t.o_stage();
     return Q3_OK;
 }
 

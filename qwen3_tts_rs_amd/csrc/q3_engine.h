@@ -7,7 +7,8 @@
 //   q3_pcm_stage.hip the output stage: per-row resampling to a requested rate and f32 / PCM16 conversion, and a
 //                    speaking rate per row by time-scale modification in front of it; G.711 bytes and a level per
 //                    row — a gain and a look-ahead peak limiter — between the two; a BS.1770 loudness meter and
-//                    normaliser per row in front of the level
+//                    normaliser per row in front of the level; a pitch per row in cents, a varispeed step behind the
+//                    stretcher
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
 //                    streaming chunks, q3_session_run / decode / get
 //   q3_batcher.hip   continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
@@ -465,6 +466,7 @@ struct q3_session {
     q3_pcm_stage* ostage = nullptr; uint32_t out_rate = 24000; int out_fmt = Q3_PCM_F32; bool out_started = false;
     std::vector<int> out_tempo;           // q3_session_set_tempo: per row, permille (empty: every row at 1000)
     std::vector<int> out_level;           // q3_session_set_level: per row, gain and ceiling in mB (empty: every row off)
+    std::vector<int> out_pitch;           // q3_session_set_pitch: per row, cents (empty: every row at 0)
     std::vector<int> out_loud;            // q3_session_set_loudness: per row, mode, target and prior in mB (empty: every row off)
     // overlapped segment decode (q3_session_run): vocoder segments run on their own stream while the frame loop continues
     hipStream_t dec_stream = nullptr; hipEvent_t dec_ev = nullptr;
@@ -566,13 +568,25 @@ struct LoDesc {
     int n_new, mode; float T, P, gate, a_lo, a_hi; int pad;
     float coef[10];
 };
+// one row of a pass of k_pitch (device-visible, 8-byte aligned): the row's stream into the pitch step is tail_in (its last 128
+// samples) below `base`, the n_new samples of src from there, zeros beyond; outputs j0 .. j0 + n_v - 1 go to v, output j at input
+// time j t / te. sc / w2: the stage's sinc and window tables. den1 = 20 max(t, te); dq1, dr1: quotient and remainder of
+// 19 S1 te by den1, what the sinc position advances by per tap; fc: (float)(0.95 min(1, te / t))
+struct PtDesc {
+    const float* src; const float* tail_in; float* tail_out; float* v; const float* sc; const float* w2;
+    long long base, j0;
+    int n_new, n_v, t, te, den1, dq1, dr1; float fc;
+};
 // (tdesc, t_y, t_k1: the time stretcher in front, DESIGN 4.12a — the rows at a tempo other than 1000, per segment the y samples of
 // this push and the frame the row reaches; pcm_stage_launch uploads tdesc itself, into the stage's own buffer.
 // ldesc, l_in, l_z, l_tiles: the level step between the two, DESIGN 4.12b — the rows with a level, per segment the samples that
 // enter the step and leave it in this push; its descriptors go up the same way.
 // odesc, o_n: the loudness step between the stretcher and the level, DESIGN 4.12c — the rows that meter or normalise, per segment
-// the samples that pass the step in this push)
+// the samples that pass the step in this push.
+// pdesc, p_n, p_v, p_tiles: the pitch step behind the stretcher, DESIGN 4.12d — the rows whose effective tempo differs from
+// their tempo, per segment the samples that enter the step and leave it in this push)
 struct PsPlan {
+    std::vector<PtDesc> pdesc; std::vector<long long> p_n, p_v; int p_tiles = 1;
     std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t bytes = 0; int max_tiles = 1;
     q3_pcm_stage* ps = nullptr; std::vector<TpDesc> tdesc; std::vector<long long> t_y, t_k1;
     std::vector<LvDesc> ldesc; std::vector<long long> l_in, l_z; int l_tiles = 1;
@@ -581,6 +595,7 @@ struct PsPlan {
 Q3_HIDDEN int pcm_stage_rows(const q3_pcm_stage* ps);
 Q3_HIDDEN size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row);
 Q3_HIDDEN void pcm_stage_reset(q3_pcm_stage* ps, int row);
+Q3_HIDDEN q3_status pcm_stage_pitch_checked(const char* who, int tempo_permille, int cents);      // the ranges of q3_pcm_stage_set_pitch
 Q3_HIDDEN q3_status pcm_stage_loud_checked(const char* who, int mode, int target_mB, int prior_mB);      // the ranges of q3_pcm_stage_set_loudness
 Q3_HIDDEN q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_rows, const int* rows);
 Q3_HIDDEN size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last);

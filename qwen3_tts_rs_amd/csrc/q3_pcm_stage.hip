@@ -35,6 +35,14 @@
 // buffer, for n that enter. The row keeps its filter states, partial sums, last energies and gains in two copies flipped like the
 // tails, its block values append-only. A row whose step is off is not touched by any of it.
 //
+// Behind the stretcher, for the rows that ask for it: a pitch in cents. The stretcher runs at the effective tempo
+// te = llround(t / 2^(c / 1200)) in the place of the row's tempo t, and k_pitch resamples its output by te / t: q3_resample's filter
+// again, at a ratio whose table taps[te][128] would be too large to build per request, so the taps are evaluated per output from
+// two tables that serve every ratio: the sinc at 512 points per zero crossing and the squared window at 64 points per tap, both
+// interpolated linearly at positions that integer arithmetic splits exactly into an index and a remainder. It holds 64 samples
+// back like the resampler, keeps the row's last 128 inputs in two copies flipped like the tails, and writes into the row's part of
+// a v buffer that the steps behind take as the row's stream. A row at 0 cents is not touched by any of it.
+//
 // Formats: f32, PCM16, and G.711 mu-law / A-law — the companding of the PCM16 value, one byte per sample.
 #include "q3_engine.h"
 
@@ -468,6 +476,109 @@ void tempo_frames(int t, long long n, bool ended, long long* frames, long long* 
 // the most y samples one push of n new input samples adds, at any place of the stream and with `last`
 size_t tempo_y_bound(int t, size_t n) { return (size_t)((((__int128)n + TP_W + TP_D + TP_HS) * 1000 + t - 1) / t) + 1; }
 
+// ---- the pitch step ----
+constexpr int PT_S1 = 512, PT_S2 = 64;                          // table points per zero crossing of the sinc, per tap of the window
+constexpr int PT_SC_N = 61 * PT_S1 + 2, PT_W2_N = PS_HALF * PT_S2 + 2;
+constexpr int PT_CENTS_MAX = 1200;
+// the window of a tile: floor((r0 + 255 t) / te) + 128 inputs, r0 < te and t / te <= 2: at most 638
+constexpr int PT_WIN = 641;
+
+// One tap: the sinc and the window, each interpolated between two table points, their product, and the sum it joins; every
+// operation rounded once. rem1 < den1 <= 40000: both exact in f32, the quotient correctly rounded.
+__device__ __forceinline__ float pt_tap(const float* __restrict__ sc, const float* __restrict__ w2, int m1, int rem1, float fden1, int m2,
+                                        float f2, float x, float acc) {
+    const float s0 = sc[m1], w0 = w2[m2];
+    const float s = fmaf(__fdiv_rn((float)rem1, fden1), q3::sub_rn(sc[m1 + 1], s0), s0);
+    const float w = fmaf(f2, q3::sub_rn(w2[m2 + 1], w0), w0);
+    return fmaf(q3::mul_rn(s, w), x, acc);
+}
+
+// Grid (tile of 256 outputs, row). Output j of the row sits at input time j t / te: cj = floor(j t / te), r = (j t) mod te, taps
+// over inputs cj + k, k = -63 .. 64, at tau = r / te - k. With q = |r - k te| the sinc is read at 19 q S1 / (20 max(t, te)) and the
+// window at q S2 / te, both as (index, remainder / denominator): k <= 0 walks q down from r + 63 te by te a tap, k >= 1 up from
+// te - r, so the index and the remainder move by constants (the window's by S2 and 0) and one division per half places them.
+// Bounds: the window holds wlen <= 638 < PT_WIN floats and thread tid reads win[dc .. dc + 127], dc <= wlen - 128;
+// q <= 64 te, so the sinc index + 1 <= 19 * 64 * S1 / 20 + 1 = 31130 < PT_SC_N and the window index + 1 <= 64 S2 + 1 < PT_W2_N;
+// in_at reads src[0 .. n_new) and tail_in[0 .. 128); v takes n_v floats.
+__global__ __launch_bounds__(PS_TILE) void k_pitch(const PtDesc* __restrict__ descs) {
+    __shared__ float win[PT_WIN];
+    const PtDesc d = descs[blockIdx.y];
+    const int tid = threadIdx.x, o0 = blockIdx.x * PS_TILE;
+    // sample g of the row's stream into the step: the kept tail below `base`, the new samples from there, zeros outside
+    auto in_at = [&](long long g) -> float {
+        if (g >= d.base) { const long long k = g - d.base; return k < d.n_new ? d.src[k] : 0.0f; }
+        const long long k = g - (d.base - PS_TAPS);
+        return (k >= 0 && d.tail_in) ? d.tail_in[k] : 0.0f;
+    };
+    if (blockIdx.x == 0 && d.tail_out && tid < PS_TAPS) d.tail_out[tid] = in_at(d.base + d.n_new - PS_TAPS + tid);
+    if (o0 >= d.n_v) return;                                     // (uniform over the block)
+    const int cnt = min(PS_TILE, d.n_v - o0);
+    const long long q0 = (d.j0 + o0) * (long long)d.t, c0 = q0 / d.te;
+    const int r0 = (int)(q0 - c0 * d.te);
+    const long long w0 = c0 - (PS_HALF - 1);                     // first input of the window
+    const int wlen = (r0 + (cnt - 1) * d.t) / d.te + PS_TAPS;
+    for (int k = tid; k < wlen; k += PS_TILE) win[k] = in_at(w0 + k);
+    __syncthreads();
+    if (tid >= cnt) return;
+    const int qq = r0 + tid * d.t, dc = qq / d.te, r = qq - dc * d.te;
+    const float* x = win + dc;                                   // x[i]: input cj + k, k = i - 63
+    const float fden1 = (float)d.den1, fte = (float)d.te;
+    const int n2 = r * PT_S2, m2r = n2 / d.te, rem2r = n2 - m2r * d.te;       // the window's position of q = r
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;            // a[k mod 4], each in ascending k
+    {                                                            // k = -63 .. 0: q = r - k te
+        const unsigned n1 = 19u * PT_S1 * (unsigned)(r + (PS_HALF - 1) * d.te);      // (< 2^31)
+        int m1 = (int)(n1 / (unsigned)d.den1), rem1 = (int)(n1 - (unsigned)m1 * (unsigned)d.den1);
+        int m2 = m2r + (PS_HALF - 1) * PT_S2;
+        const float f2 = __fdiv_rn((float)rem2r, fte);
+        auto step = [&]() { m1 -= d.dq1; rem1 -= d.dr1; if (rem1 < 0) { rem1 += d.den1; --m1; } m2 -= PT_S2; };
+#pragma unroll 2
+        for (int i = 0; i < PS_HALF; i += 4) {                   // (k = -63 is 1 mod 4)
+            a1 = pt_tap(d.sc, d.w2, m1, rem1, fden1, m2, f2, x[i], a1); step();
+            a2 = pt_tap(d.sc, d.w2, m1, rem1, fden1, m2, f2, x[i + 1], a2); step();
+            a3 = pt_tap(d.sc, d.w2, m1, rem1, fden1, m2, f2, x[i + 2], a3); step();
+            a0 = pt_tap(d.sc, d.w2, m1, rem1, fden1, m2, f2, x[i + 3], a0); step();      // (the step past k = 0 is not read)
+        }
+    }
+    {                                                            // k = 1 .. 64: q = k te - r
+        const unsigned n1 = 19u * PT_S1 * (unsigned)(d.te - r);
+        int m1 = (int)(n1 / (unsigned)d.den1), rem1 = (int)(n1 - (unsigned)m1 * (unsigned)d.den1);
+        int m2 = rem2r ? PT_S2 - m2r - 1 : PT_S2 - m2r;
+        const float f2 = rem2r ? __fdiv_rn((float)(d.te - rem2r), fte) : 0.0f;
+        auto step = [&]() { m1 += d.dq1; rem1 += d.dr1; if (rem1 >= d.den1) { rem1 -= d.den1; ++m1; } m2 += PT_S2; };
+#pragma unroll 2
+        for (int i = PS_HALF; i < PS_TAPS; i += 4) {
+            a1 = pt_tap(d.sc, d.w2, m1, rem1, fden1, m2, f2, x[i], a1); step();
+            a2 = pt_tap(d.sc, d.w2, m1, rem1, fden1, m2, f2, x[i + 1], a2); step();
+            a3 = pt_tap(d.sc, d.w2, m1, rem1, fden1, m2, f2, x[i + 2], a3); step();
+            a0 = pt_tap(d.sc, d.w2, m1, rem1, fden1, m2, f2, x[i + 3], a0); step();      // (the step past k = 64 is not read)
+        }
+    }
+    d.v[o0 + tid] = q3::mul_rn(d.fc, q3::add_rn(q3::add_rn(a0, a1), q3::add_rn(a2, a3)));
+}
+
+// te = llround(t / 2^(c / 1200)): the tempo the stretcher runs at so that the step's t / te brings the duration back to t's
+inline int pitch_te(int t, int c) { return c == 0 ? t : (int)llround((double)t / pow(2.0, (double)c / 1200.0)); }
+// The streaming rule, the resampler's with L / M = te / t: after F final inputs every j with floor(j t / te) + 64 <= F - 1 is out,
+// and after the flush floor((2 F te + t) / (2 t)) in total
+inline long long pitch_emitted(int t, int te, long long F, bool ended) {
+    if (ended) return (2 * F * te + t) / (2 * (long long)t);
+    return F > PS_HALF ? ((F - PS_HALF) * te + t - 1) / t : 0;
+}
+// the most outputs one push of n new inputs adds, at any place of the stream and with `last`
+inline size_t pitch_v_bound(int t, int te, size_t n) { return (size_t)((((long long)n + PS_HALF) * te + t - 1) / t + 1); }
+// Sc[m] = sinc(m / S1), W2[m] = w^2(m / (64 S2)) with q3_resample's window (0 from |v| = 1 on, as there): f64, rounded once
+void pitch_tables(std::vector<float>& sc, std::vector<float>& w2) {
+    const double a0 = 0.35875, a1 = 0.48829, a2 = 0.14128, a3 = 0.01168, PI = 3.14159265358979323846;
+    sc.assign((size_t)PT_SC_N, 0.0f); w2.assign((size_t)PT_W2_N, 0.0f);
+    sc[0] = 1.0f;
+    for (int m = 1; m < PT_SC_N; ++m) { const double xs = PI * (double)m / (double)PT_S1; sc[(size_t)m] = (float)(sin(xs) / xs); }
+    for (int m = 0; m < PS_HALF * PT_S2; ++m) {
+        const double v = (double)m / (double)(PS_HALF * PT_S2);
+        const double w = a0 + a1 * cos(PI * v) + a2 * cos(2.0 * PI * v) + a3 * cos(3.0 * PI * v);
+        w2[(size_t)m] = (float)(w * w);
+    }
+}
+
 struct Rate { int L = 1, M = 1; };
 bool rate_of(uint32_t sr, Rate* r) {
     if (sr < PS_RATE_MIN || sr > PS_RATE_MAX) return false;
@@ -529,6 +640,10 @@ struct PsRow {
     int loud = Q3_LOUD_OFF, o_target = -1900, o_prior = 0; float o_T = 0.0f, o_P = 1.0f, o_gate = 0.0f, o_lo = 0.0f, o_hi = 0.0f;
     long long o_in = 0;
     float* o_state = nullptr; int o_cur = 0;  // on the device: two copies of LD_STATE floats, then the LD_HIST block values (one copy)
+    // the pitch step behind the stretcher: te is the tempo the stretcher runs at (te == tempo: the step is off)
+    int pitch = 0, te = TP_OFF;
+    long long p_in = 0, p_out = 0;            // samples that have entered the step, and left it
+    float* p_tail = nullptr; int p_cur = 0;   // on the device, two copies of 128 floats: the last 128 inputs
 };
 constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
 struct q3_pcm_stage {
@@ -550,6 +665,10 @@ struct q3_pcm_stage {
     float o_coef[10] = {0}; bool o_coef_set = false;                       // the K-weighting at 24 kHz, f32
     float* w_dev = nullptr; size_t w_cap = 0;                              // the normalised samples of a push, row after row
     char *od_dev = nullptr, *od_host = nullptr; size_t od_cap = 0;         // k_loud's descriptors
+    // the pitch step (all of it allocated by the first row whose pitch moves its tempo, or the first push of one)
+    float* p_tab = nullptr;                                                // the sinc table, PT_SC_N floats, then the window's, PT_W2_N
+    float* v_dev = nullptr; size_t v_cap = 0;                              // the repitched samples of a push, row after row
+    char *pd_dev = nullptr, *pd_host = nullptr; size_t pd_cap = 0;         // k_pitch's descriptors
 };
 
 extern "C" q3_status q3_pcm_stage_taps(uint32_t sample_rate, float* taps_host, size_t cap_floats, int* L, int* M) {
@@ -687,9 +806,11 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
     if (ps->st) (void)hipStreamSynchronize(ps->st);
     for (auto& kv : ps->taps) dev_free(kv.second);
     dev_free(ps->tails); dev_free(ps->out_dev); dev_free(ps->in_dev);
-    for (PsRow& r : ps->rows) { dev_free(r.t_state); dev_free(r.t_lags[0]); dev_free(r.t_lags[1]); dev_free(r.l_tail); dev_free(r.o_state); }
+    for (PsRow& r : ps->rows) { dev_free(r.t_state); dev_free(r.t_lags[0]); dev_free(r.t_lags[1]); dev_free(r.l_tail); dev_free(r.o_state); dev_free(r.p_tail); }
     dev_free(ps->t_win); dev_free(ps->y_dev); dev_free(ps->td_dev); dev_free(ps->z_dev); dev_free(ps->ld_dev);
     dev_free(ps->w_dev); dev_free(ps->od_dev);
+    dev_free(ps->p_tab); dev_free(ps->v_dev); dev_free(ps->pd_dev);
+    if (ps->pd_host) (void)hipHostFree(ps->pd_host);
     if (ps->od_host) (void)hipHostFree(ps->od_host);
     if (ps->td_host) (void)hipHostFree(ps->td_host);
     if (ps->ld_host) (void)hipHostFree(ps->ld_host);
@@ -707,6 +828,7 @@ void pcm_stage_reset(q3_pcm_stage* ps, int row) {
     r.t_in = r.t_frames = 0; r.t_lag_k0 = r.t_lag_n = 0;
     r.l_in = 0;
     r.o_in = 0;
+    r.p_in = r.p_out = 0;
 }
 
 extern "C" q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row) {
@@ -741,30 +863,113 @@ extern "C" q3_status q3_pcm_stage_set(q3_pcm_stage* ps, int row, uint32_t sample
     return Q3_OK;
 }
 
-extern "C" q3_status q3_pcm_stage_set_tempo(q3_pcm_stage* ps, int row, int tempo_permille) {
-    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_tempo: bad row");
-    Q3C(tempo_checked("q3_pcm_stage_set_tempo", tempo_permille));      // (before the device is touched)
+static q3_status pitch_checked(const char* who, int tempo, int cents) {
+    Q3C(tempo_checked(who, tempo));
+    if (cents < -PT_CENTS_MAX || cents > PT_CENTS_MAX)
+        return set_err(Q3_INVALID_ARG, "%s: pitch %d cents out of range (%d..%d; 0 = off)", who, cents, -PT_CENTS_MAX, PT_CENTS_MAX);
+    const int te = pitch_te(tempo, cents);
+    if (te < TP_MIN || te > TP_MAX)
+        return set_err(Q3_INVALID_ARG, "%s: tempo %d permille with a pitch of %d cents needs the stretcher at %d permille (%d..%d)", who, tempo, cents, te,
+                       TP_MIN, TP_MAX);
+    return Q3_OK;
+}
+q3_status pcm_stage_pitch_checked(const char* who, int tempo_permille, int cents) { return pitch_checked(who, tempo_permille, cents); }
+
+// the row's tempo and pitch together (checked by the caller): what the stretcher at te and the pitch step need, then the restart
+static q3_status tempo_pitch_set(q3_pcm_stage* ps, int row, const char* who, int tempo, int cents) {
     PsRow& r = ps->rows[(size_t)row];
-    if (tempo_permille != TP_OFF) {
+    const int te = pitch_te(tempo, cents);
+    if (te != TP_OFF) {
         HIPC(hipSetDevice(ps->device));
         if (!ps->t_win) {
             // periodic Hann, built in f64
             std::vector<float> w((size_t)TP_W);
             for (int j = 0; j < TP_W; ++j) w[(size_t)j] = (float)(0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * (double)j / (double)TP_W));
             float* d = nullptr;
-            if (dev_malloc((void**)&d, w.size() * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "q3_pcm_stage_set_tempo: window"); }
+            if (dev_malloc((void**)&d, w.size() * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "%s: window", who); }
             const hipError_t e = q3_hipMemcpy(d, w.data(), w.size() * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "q3_pcm_stage_set_tempo: window upload: %s", hipGetErrorString(e)); }
+            if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "%s: window upload: %s", who, hipGetErrorString(e)); }
             ps->t_win = d;
         }
         if (!r.t_state && dev_malloc((void**)&r.t_state, 2 * TP_STATE_BYTES) != hipSuccess) {
             (void)hipGetLastError(); r.t_state = nullptr;
-            return set_err(Q3_OOM, "q3_pcm_stage_set_tempo: state of row %d", row);
+            return set_err(Q3_OOM, "%s: state of row %d", who, row);
         }
     }
-    r.tempo = tempo_permille;
+    if (te != tempo) {
+        HIPC(hipSetDevice(ps->device));
+        if (!ps->p_tab) {
+            std::vector<float> sc, w2;
+            pitch_tables(sc, w2);
+            sc.insert(sc.end(), w2.begin(), w2.end());
+            float* d = nullptr;
+            if (dev_malloc((void**)&d, sc.size() * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "%s: tables", who); }
+            const hipError_t e = q3_hipMemcpy(d, sc.data(), sc.size() * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "%s: table upload: %s", who, hipGetErrorString(e)); }
+            ps->p_tab = d;
+        }
+        if (!r.p_tail && dev_malloc((void**)&r.p_tail, 2 * (size_t)PS_TAPS * 4) != hipSuccess) {
+            (void)hipGetLastError(); r.p_tail = nullptr;
+            return set_err(Q3_OOM, "%s: tail of row %d", who, row);
+        }
+    }
+    r.tempo = tempo; r.pitch = cents; r.te = te;
     pcm_stage_reset(ps, row);
     return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_set_tempo(q3_pcm_stage* ps, int row, int tempo_permille) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_tempo: bad row");
+    Q3C(pitch_checked("q3_pcm_stage_set_tempo", tempo_permille, ps->rows[(size_t)row].pitch));      // (before the device is touched)
+    return tempo_pitch_set(ps, row, "q3_pcm_stage_set_tempo", tempo_permille, ps->rows[(size_t)row].pitch);
+}
+
+extern "C" q3_status q3_pcm_stage_set_pitch(q3_pcm_stage* ps, int row, int cents) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_pitch: bad row");
+    Q3C(pitch_checked("q3_pcm_stage_set_pitch", ps->rows[(size_t)row].tempo, cents));      // (before the device is touched)
+    return tempo_pitch_set(ps, row, "q3_pcm_stage_set_pitch", ps->rows[(size_t)row].tempo, cents);
+}
+
+extern "C" q3_status q3_pcm_stage_pitch_plan(int tempo_permille, int cents, int* tempo_eff, double* cents_realized) {
+    Q3C(pitch_checked("q3_pcm_stage_pitch_plan", tempo_permille, cents));
+    const int te = pitch_te(tempo_permille, cents);
+    if (tempo_eff) *tempo_eff = te;
+    if (cents_realized) *cents_realized = te == tempo_permille ? 0.0 : 1200.0 * log2((double)tempo_permille / (double)te);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_pitch_tables(float* sinc, size_t cap1, float* win, size_t cap2, int* S1, int* S2) {
+    if (S1) *S1 = PT_S1;
+    if (S2) *S2 = PT_S2;
+    if (!sinc && !win) return Q3_OK;                               // S1 / S2 query
+    if ((sinc && cap1 < (size_t)PT_SC_N) || (win && cap2 < (size_t)PT_W2_N))
+        return set_err(Q3_INVALID_ARG, "q3_pcm_stage_pitch_tables: buffer too small (%d and %d floats needed)", PT_SC_N, PT_W2_N);
+    std::vector<float> sc, w2;
+    pitch_tables(sc, w2);
+    if (sinc) memcpy(sinc, sc.data(), sc.size() * 4);
+    if (win) memcpy(win, w2.data(), w2.size() * 4);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_pitch_count(int tempo_permille, int cents, size_t n_in_total, int ended, size_t* samples_24k) {
+    Q3C(pitch_checked("q3_pcm_stage_pitch_count", tempo_permille, cents));
+    if (!samples_24k) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_pitch_count: null argument");
+    if (n_in_total > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_pitch_count: n_in_total above 2^48");
+    const int te = pitch_te(tempo_permille, cents);
+    long long f = 0, y = (long long)n_in_total;
+    if (te != TP_OFF) tempo_frames(te, (long long)n_in_total, ended != 0, &f, &y);
+    *samples_24k = (size_t)(te == tempo_permille ? y : pitch_emitted(tempo_permille, te, y, ended != 0));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_bound_pitch(uint32_t sample_rate, int tempo_permille, int cents, int with_level, size_t n_in, size_t* n_out_max) {
+    Q3C(pitch_checked("q3_pcm_stage_bound_pitch", tempo_permille, cents));
+    if (n_in > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_pitch: n_in above 2^48");
+    // the caps of the steps in a row: the most y samples the push can add, the most the pitch step then hands on, the level's 127
+    const int te = pitch_te(tempo_permille, cents);
+    size_t n = te == TP_OFF ? n_in : tempo_y_bound(te, n_in);
+    if (te != tempo_permille) n = pitch_v_bound(tempo_permille, te, n);
+    return q3_pcm_stage_bound(sample_rate, n + (with_level ? LV_D : 0), n_out_max);
 }
 
 extern "C" q3_status q3_pcm_stage_set_level(q3_pcm_stage* ps, int row, int gain_mB, int ceiling_mB) {
@@ -861,15 +1066,20 @@ extern "C" q3_status q3_pcm_stage_tempo_lags(q3_pcm_stage* ps, int row, int64_t*
 // what a row has emitted once n more 24 kHz samples have arrived: through the stretcher first, where the row has one
 // (y: the stretched samples by then, k1: the frames)
 // (y: the stretched samples by then, k1: the frames; lv: the samples that have entered the level step by then)
-static long long row_emitted(const PsRow& r, size_t n, bool last, long long* y = nullptr, long long* k1 = nullptr, long long* lv = nullptr) {
-    long long in_total = (r.level ? r.l_in : r.n_in) + (long long)n;
-    if (r.tempo != TP_OFF) {
+// (pv: the samples that have left the pitch step by then, where the row has one: the stream the steps behind it take)
+static long long row_emitted(const PsRow& r, size_t n, bool last, long long* y = nullptr, long long* k1 = nullptr, long long* lv = nullptr,
+                             long long* pv = nullptr) {
+    const bool pitch = r.te != r.tempo;
+    long long in_total = (pitch ? r.p_in : r.level ? r.l_in : r.n_in) + (long long)n;
+    if (r.te != TP_OFF) {
         long long f = 0;
-        tempo_frames(r.tempo, r.t_in + (long long)n, last, &f, &in_total);
+        tempo_frames(r.te, r.t_in + (long long)n, last, &f, &in_total);
         if (f < r.t_frames) f = r.t_frames;
         if (k1) *k1 = f;
     }
     if (y) *y = in_total;
+    if (pitch) in_total = pitch_emitted(r.tempo, r.te, in_total, last);
+    if (pv) *pv = in_total;
     if (r.level) {
         if (lv) *lv = in_total;
         in_total = level_emitted(in_total, last);
@@ -894,25 +1104,33 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
     plan.ps = ps; plan.tdesc.clear(); plan.t_y.assign(segs.size(), 0); plan.t_k1.assign(segs.size(), 0);
     plan.ldesc.clear(); plan.l_in.assign(segs.size(), 0); plan.l_z.assign(segs.size(), 0); plan.l_tiles = 1;
     plan.odesc.clear(); plan.o_n.clear();
-    std::vector<size_t> y_off(segs.size(), 0), z_off(segs.size(), 0), w_off; size_t y_floats = 0, z_floats = 0, w_floats = 0;
+    plan.pdesc.clear(); plan.p_n.clear(); plan.p_v.clear(); plan.p_tiles = 1;
+    std::vector<size_t> y_off(segs.size(), 0), z_off(segs.size(), 0), w_off, v_off; size_t y_floats = 0, z_floats = 0, w_floats = 0, v_floats = 0;
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
         if (sg.n > ps->max_push) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, ps->max_push);
         if (r.ended && sg.n > 0) return set_err(Q3_INVALID_ARG, "pcm stage: row %d was flushed (last): q3_pcm_stage_reset or _set restarts it", sg.row);
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
-        long long y_total = 0, k1 = 0, lv_total = 0;
-        const long long total = row_emitted(r, sg.n, sg.last != 0, &y_total, &k1, &lv_total);
+        long long y_total = 0, k1 = 0, lv_total = 0, v_total = 0;
+        const long long total = row_emitted(r, sg.n, sg.last != 0, &y_total, &k1, &lv_total, &v_total);
+        const bool pitch = r.te != r.tempo;
         plan.count[i] = (size_t)std::max<long long>(0, total - r.n_out);
-        if (r.tempo != TP_OFF) {
+        if (r.te != TP_OFF) {
             if (!r.t_state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tempo and no state", sg.row);
-            plan.t_y[i] = y_total - (r.level ? r.l_in : r.n_in); plan.t_k1[i] = k1;
+            plan.t_y[i] = y_total - (pitch ? r.p_in : r.level ? r.l_in : r.n_in); plan.t_k1[i] = k1;
             y_off[i] = y_floats; y_floats += ((size_t)plan.t_y[i] + 3) & ~(size_t)3;
+        }
+        if (pitch) {
+            if (!r.p_tail || !ps->p_tab) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a pitch and no state", sg.row);
+            if (plan.p_n.empty()) { plan.p_n.assign(segs.size(), 0); plan.p_v.assign(segs.size(), 0); v_off.assign(segs.size(), 0); }
+            plan.p_n[i] = y_total - r.p_in; plan.p_v[i] = v_total - r.p_out;
+            v_off[i] = v_floats; v_floats += ((size_t)plan.p_v[i] + 3) & ~(size_t)3;
         }
         if (r.loud != Q3_LOUD_OFF) {
             // (what passes the step in this push: the stretched samples where the row has a stretcher, else the segment's own)
             if (!r.o_state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a loudness step and no state", sg.row);
             if (plan.o_n.empty()) { plan.o_n.assign(segs.size(), 0); w_off.assign(segs.size(), 0); }
-            plan.o_n[i] = y_total - r.o_in;
+            plan.o_n[i] = v_total - r.o_in;
             if (r.loud == Q3_LOUD_NORMALIZE) { w_off[i] = w_floats; w_floats += ((size_t)plan.o_n[i] + 3) & ~(size_t)3; }
         }
         if (r.level) {
@@ -935,10 +1153,11 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
     if (y_floats > 0) Q3C(dev_grow(ps, (void**)&ps->y_dev, &ps->y_cap, y_floats * 4));
     if (z_floats > 0) Q3C(dev_grow(ps, (void**)&ps->z_dev, &ps->z_cap, z_floats * 4));
     if (w_floats > 0) Q3C(dev_grow(ps, (void**)&ps->w_dev, &ps->w_cap, w_floats * 4));
+    if (v_floats > 0) Q3C(dev_grow(ps, (void**)&ps->v_dev, &ps->v_cap, v_floats * 4));
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row];
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
-        if (r.tempo != TP_OFF) {
+        if (r.te != TP_OFF) {
             // (the buffer that is written is the one the last successful push did not write: its lags stay readable)
             const int lw = r.t_lag_cur ^ 1; const long long nk = plan.t_k1[i] - r.t_frames;
             if (nk > 0) { size_t cap_b = r.t_lag_cap[lw]; Q3C(dev_grow(ps, (void**)&r.t_lags[lw], &cap_b, (size_t)nk * sizeof(int))); r.t_lag_cap[lw] = cap_b; }
@@ -946,17 +1165,31 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
         float* tails = ps->tails + (size_t)sg.row * 2 * PS_TAPS;
         PsDesc d{};
         d.src = sg.dev; d.n_new = (int)sg.n; d.n_out = (int)plan.count[i]; d.out = ps->out_dev + plan.off[i];
-        if (r.tempo != TP_OFF) {
+        if (r.te != TP_OFF) {
             char* in = r.t_state + (size_t)r.t_cur * TP_STATE_BYTES; char* out = r.t_state + (size_t)(r.t_cur ^ 1) * TP_STATE_BYTES;
             TpDesc t{};
             t.src = sg.dev; t.hist_in = r.t_in > 0 ? (const float*)(in + 16) : nullptr; t.hist_out = sg.last ? nullptr : (float*)(out + 16);
             t.p_in = (const long long*)in; t.p_out = (long long*)out; t.lags = r.t_lags[r.t_lag_cur ^ 1];
             t.y = ps->y_dev + y_off[i]; t.win = ps->t_win;
-            t.base = r.t_in; t.n_total = r.t_in + (long long)sg.n; t.hist_lo = tp_lo(r.t_frames, r.tempo); t.lo_next = tp_lo(plan.t_k1[i], r.tempo);
-            t.k0 = r.t_frames; t.k1 = plan.t_k1[i]; t.n_new = (int)sg.n; t.n_y = (int)plan.t_y[i]; t.tempo = r.tempo;
+            t.base = r.t_in; t.n_total = r.t_in + (long long)sg.n; t.hist_lo = tp_lo(r.t_frames, r.te); t.lo_next = tp_lo(plan.t_k1[i], r.te);
+            t.k0 = r.t_frames; t.k1 = plan.t_k1[i]; t.n_new = (int)sg.n; t.n_y = (int)plan.t_y[i]; t.tempo = r.te;
             if (!sg.last && t.n_total - t.lo_next > TP_HIST) return set_err(Q3_INVALID_ARG, "pcm stage: row %d would keep %lld samples", sg.row, t.n_total - t.lo_next);
             plan.tdesc.push_back(t);
             d.src = t.y; d.n_new = t.n_y;                             // the resampler's input: the stretched samples
+        }
+        if (r.te != r.tempo) {
+            // (the step's input: the stretched samples where the stretcher runs, te != 1000, else the segment's own)
+            PtDesc q{};
+            q.src = d.src; q.n_new = (int)plan.p_n[i]; q.base = r.p_in; q.j0 = r.p_out;
+            q.tail_in = r.p_in > 0 ? r.p_tail + (size_t)r.p_cur * PS_TAPS : nullptr;
+            q.tail_out = sg.last ? nullptr : r.p_tail + (size_t)(r.p_cur ^ 1) * PS_TAPS;
+            q.v = ps->v_dev + v_off[i]; q.n_v = (int)plan.p_v[i]; q.sc = ps->p_tab; q.w2 = ps->p_tab + PT_SC_N;
+            q.t = r.tempo; q.te = r.te; q.den1 = 20 * std::max(r.tempo, r.te);
+            q.dq1 = (19 * PT_S1 * r.te) / q.den1; q.dr1 = (19 * PT_S1 * r.te) % q.den1;
+            q.fc = (float)(0.95 * (r.te < r.tempo ? (double)r.te / (double)r.tempo : 1.0));
+            plan.p_tiles = std::max(plan.p_tiles, (q.n_v + PS_TILE - 1) / PS_TILE);
+            plan.pdesc.push_back(q);
+            d.src = q.v; d.n_new = q.n_v;                             // the next step's input: the repitched samples
         }
         if (r.loud != Q3_LOUD_OFF && plan.o_n[i] > 0) {
             LoDesc o{};
@@ -1011,6 +1244,26 @@ hipError_t pcm_stage_launch(const PsDesc* desc_dev, const PsPlan& plan, hipStrea
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
+    if (!plan.pdesc.empty()) {
+        // the rows with a pitch, behind the stretcher: descriptors as above, a workgroup per tile of 256 outputs
+        q3_pcm_stage* ps = plan.ps;
+        const size_t pb = plan.pdesc.size() * sizeof(PtDesc);
+        if (pb > ps->pd_cap) {
+            dev_free(ps->pd_dev); ps->pd_dev = nullptr;
+            if (ps->pd_host) { (void)hipHostFree(ps->pd_host); ps->pd_host = nullptr; }
+            ps->pd_cap = 0;
+            hipError_t e = dev_malloc((void**)&ps->pd_dev, pb * 2);
+            if (e == hipSuccess) e = hipHostMalloc((void**)&ps->pd_host, pb * 2, hipHostMallocDefault);
+            if (e != hipSuccess) return e;
+            ps->pd_cap = pb * 2;
+        }
+        memcpy(ps->pd_host, plan.pdesc.data(), pb);
+        hipError_t e = hipMemcpyAsync(ps->pd_dev, ps->pd_host, pb, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_pitch, dim3((unsigned)plan.p_tiles, (unsigned)plan.pdesc.size()), dim3(PS_TILE), 0, st, (const PtDesc*)ps->pd_dev);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     if (!plan.odesc.empty()) {
         // the rows that meter or normalise, between the stretcher and the level: descriptors as above, one workgroup per row
         q3_pcm_stage* ps = plan.ps;
@@ -1059,13 +1312,15 @@ void pcm_stage_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const Ps
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row];
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
-        if (r.tempo != TP_OFF) {
+        const bool pitch = r.te != r.tempo;
+        if (r.te != TP_OFF) {
             r.t_lag_cur ^= 1; r.t_lag_k0 = r.t_frames; r.t_lag_n = plan.t_k1[i] - r.t_frames;
             r.t_in += (long long)sg.n; r.t_frames = plan.t_k1[i]; r.t_cur ^= 1;
         }
+        if (pitch) { r.p_in += plan.p_n[i]; r.p_out += plan.p_v[i]; if (!sg.last) r.p_cur ^= 1; }
         if (r.loud != Q3_LOUD_OFF && plan.o_n[i] > 0) { r.o_in += plan.o_n[i]; r.o_cur ^= 1; }
         if (r.level) { r.l_in += plan.l_in[i]; r.n_in += plan.l_z[i]; if (!sg.last) r.l_cur ^= 1; }
-        else r.n_in += r.tempo != TP_OFF ? plan.t_y[i] : (long long)sg.n;
+        else r.n_in += pitch ? plan.p_v[i] : r.te != TP_OFF ? plan.t_y[i] : (long long)sg.n;
         r.n_out += (long long)plan.count[i];
         if (r.taps) { r.cur ^= 1; r.fresh = false; }
         if (sg.last) r.ended = true;

@@ -1800,10 +1800,29 @@ extern "C" q3_status q3_session_set_tempo(q3_session* s, int b, int tempo_permil
     for (int r = b0; r < b1; ++r)
         if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
             return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: row %d has streamed its first chunk: the tempo is set before it, or after q3_session_replace", r);
+    for (int r = b0; r < b1 && !s->out_pitch.empty(); ++r)      // (a row's pitch has to admit the tempo)
+        if (s->out_pitch[(size_t)r] != 0) Q3C(pcm_stage_pitch_checked("q3_session_set_tempo", tempo_permille, s->out_pitch[(size_t)r]));
     if (s->out_tempo.empty()) s->out_tempo.assign((size_t)s->B, 1000);
     for (int r = b0; r < b1; ++r) {
         if (s->ostage) Q3C(q3_pcm_stage_set_tempo(s->ostage, r, tempo_permille));
         s->out_tempo[(size_t)r] = tempo_permille;
+    }
+    return Q3_OK;
+}
+extern "C" q3_status q3_session_set_pitch(q3_session* s, int b, int cents) {
+    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_pitch: null session");
+    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_pitch: row %d out of range (%d rows; -1 = every row)", b, s->B);
+    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
+    for (int r = b0; r < b1; ++r)
+        Q3C(pcm_stage_pitch_checked("q3_session_set_pitch", s->out_tempo.empty() ? 1000 : s->out_tempo[(size_t)r], cents));
+    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_pitch: the model has no device");
+    for (int r = b0; r < b1; ++r)
+        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
+            return set_err(Q3_INVALID_ARG, "q3_session_set_pitch: row %d has streamed its first chunk: the pitch is set before it, or after q3_session_replace", r);
+    if (s->out_pitch.empty()) s->out_pitch.assign((size_t)s->B, 0);
+    for (int r = b0; r < b1; ++r) {
+        if (s->ostage) Q3C(q3_pcm_stage_set_pitch(s->ostage, r, cents));
+        s->out_pitch[(size_t)r] = cents;
     }
     return Q3_OK;
 }
@@ -1866,6 +1885,8 @@ extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_
         for (int b = 0; b < s->B; ++b) Q3C(q3_pcm_stage_set(s->ostage, b, s->out_rate, s->out_fmt));
         for (int b = 0; b < s->B && !s->out_tempo.empty(); ++b)
             if (s->out_tempo[(size_t)b] != 1000) Q3C(q3_pcm_stage_set_tempo(s->ostage, b, s->out_tempo[(size_t)b]));
+        for (int b = 0; b < s->B && !s->out_pitch.empty(); ++b)
+            if (s->out_pitch[(size_t)b] != 0) Q3C(q3_pcm_stage_set_pitch(s->ostage, b, s->out_pitch[(size_t)b]));
         for (int b = 0; b < s->B && !s->out_level.empty(); ++b)
             if (s->out_level[(size_t)b * 2] != 0 || s->out_level[(size_t)b * 2 + 1] != 0)
                 Q3C(q3_pcm_stage_set_level(s->ostage, b, s->out_level[(size_t)b * 2], s->out_level[(size_t)b * 2 + 1]));

@@ -138,6 +138,14 @@ pub mod ffi {
         pub fn q3_session_loudness(s: *mut c_void, b: i32, mean_square: *mut f32, gain: *mut f32, blocks: *mut i32, gated: *mut i32) -> i32;
         pub fn q3_batcher_ticket_loudness(b: *mut c_void, ticket: i64, mode: i32, target_mb: i32, prior_mb: i32) -> i32;
         pub fn q3_batcher_ticket_loudness_read(b: *mut c_void, ticket: i64, mean_square: *mut f32, gain: *mut f32, blocks: *mut i32, gated: *mut i32) -> i32;
+        // the output stage's pitch step: a pitch per row in cents, varispeed behind the time stretcher
+        pub fn q3_pcm_stage_set_pitch(ps: *mut c_void, row: i32, cents: i32) -> i32;
+        pub fn q3_pcm_stage_pitch_plan(tempo_permille: i32, cents: i32, tempo_eff: *mut i32, cents_realized: *mut f64) -> i32;
+        pub fn q3_pcm_stage_pitch_tables(sinc: *mut f32, cap1: usize, win: *mut f32, cap2: usize, s1: *mut i32, s2: *mut i32) -> i32;
+        pub fn q3_pcm_stage_pitch_count(tempo_permille: i32, cents: i32, n_in_total: usize, ended: i32, samples_24k: *mut usize) -> i32;
+        pub fn q3_pcm_stage_bound_pitch(sample_rate: u32, tempo_permille: i32, cents: i32, with_level: i32, n_in: usize, n_out_max: *mut usize) -> i32;
+        pub fn q3_session_set_pitch(s: *mut c_void, b: i32, cents: i32) -> i32;
+        pub fn q3_batcher_ticket_pitch(b: *mut c_void, ticket: i64, cents: i32) -> i32;
     }
 }
 use ffi::*;
@@ -153,6 +161,13 @@ pub fn pcm_stage_tempo_count(tempo_permille: i32, n_in_total: usize, ended: bool
     let (mut f, mut y) = (0usize, 0usize);
     check(unsafe { q3_pcm_stage_tempo_count(tempo_permille, n_in_total, ended as i32, &mut f, &mut y) })?;
     Ok((f, y))
+}
+/// (the tempo the stretcher runs at, the pitch in cents the row then has) for a row at `tempo_permille` asked for `cents`
+/// (-1200..=1200); an error where the stretcher would leave 500..=2000. Host only. No reference counterpart.
+pub fn pcm_stage_pitch_plan(tempo_permille: i32, cents: i32) -> Result<(i32, f64)> {
+    let (mut te, mut c) = (0i32, 0f64);
+    check(unsafe { q3_pcm_stage_pitch_plan(tempo_permille, cents, &mut te, &mut c) })?;
+    Ok((te, c))
 }
 /// The most samples one push of `n_in` 24 kHz samples returns at `sample_rate` from a row at `tempo_permille`. Host only.
 pub fn pcm_stage_bound_tempo(sample_rate: u32, tempo_permille: i32, n_in: usize) -> Result<usize> {
