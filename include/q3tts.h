@@ -546,6 +546,49 @@ typedef struct q3_conv_ex_args {
     float* y; float* y2;
 } q3_conv_ex_args;
 q3_status q3_conv_ex(int device, const q3_conv_ex_args* args);
+/* Test API: which geometry launch_lm_gemm (the long-prompt prefill GEMM) picks for a shape — the launcher's own decision function,
+ * no GPU needed. norm / w2 / planes != 0: a fused input RMSNorm, a second (SwiGLU "up") matrix, pre-split activation planes with
+ * the split-K workspace q3_gemm_ex passes. Returns the geometry (0 = geometry 1 with the split in the kernel, 1 = geometry 1 over
+ * planes, 2 = k_lm_gemm2, 3 = k_lm_gemm3) or -1 for arguments the launcher refuses; path (optional) [4] = geometry, k_ranges,
+ * k_split, n_split. */
+int q3_gemm_path(int M, int N, int K, int epi, int norm, int w2, int planes, int* path);
+/* Test API: ONE launch_lm_gemm call over host arrays. x [M][ldx]; w / w2 row-major bf16 [N][K] (retiled as the loader does);
+ * bias [N], norm_w [K] (the entry runs launch_row_den first) and resid [M][ldr] may be NULL; epi as in q3_linear_ex. geometry -1 =
+ * the engine's pick over planes, 0 = geometry 1 with the split in the kernel (no planes), 1 / 2 / 3 = that geometry over planes
+ * (launch_split_rows into a NaN-filled buffer of whole 128-row tiles). k_split 0 = the engine's, else forced (geometry 3; the
+ * split-K workspace is NaN-filled); sup_m, sup_n 0 = the engine's, else the forced super-tile. y [M_alloc][ldy] is uploaded whole
+ * before the launch and copied back whole after it. path (optional) [4] = what ran: geometry, k_ranges, k_split, n_split.
+ * A launch the dispatcher refuses returns Q3_UNSUPPORTED (never another geometry) and leaves y as it was. */
+typedef struct q3_gemm_ex_args {
+    int M, N, K, ldx, ldy, ldr, M_alloc;
+    int epi, geometry, k_split, sup_m, sup_n;
+    float eps;
+    int* path;
+    const float* x; const uint16_t* w; const uint16_t* w2;
+    const float* bias; const float* norm_w; const float* resid;
+    float* y;
+} q3_gemm_ex_args;
+q3_status q3_gemm_ex(int device, const q3_gemm_ex_args* args);
+/* Test API: which prefill attention kernel launch_attn_prefill picks (0 = VALU, 8 query rows per workgroup; 1 = S = Q.K^T on the
+ * f32 matrix cores; 2 = the transposed product; 3 = bf16x3 planes) for heads / kv heads, with or without K/V planes, over 1 or 2
+ * key halves. No GPU needed. Returns the kernel or -1 (refused); path (optional) [2] = kernel, halves. */
+int q3_attn_prefill_path(int nh, int nkv, int use_planes, int halves, int* path);
+/* Test API: one prefill attention step over a contiguous cache: n_seq sequences of rps rows at positions base_pos .. base_pos +
+ * rps - 1. launch_qknorm_rope_kv, launch_kv_planes (bf16x3 kernel only; NaN-filled buffer, more tiles allocated than used), ONE
+ * launch_attn_prefill, launch_attn_merge for two halves. qkv [n_seq * rps][ld_qkv]; q_norm_w / k_norm_w [128]; rope_cos / rope_sin
+ * [max_seq][64]; kcache / vcache [n_seq][nkv][max_seq][128] in and out; out [n_seq * rps][ld_out] is uploaded whole and copied
+ * back whole. kernel -1 = the engine's pick (use_planes != 0: with K/V planes), 0..3 as q3_attn_prefill_path; halves 1 or 2.
+ * path (optional) [2] = kernel, halves that ran. A refused launch returns Q3_UNSUPPORTED and leaves the caches and out alone. */
+typedef struct q3_attn_prefill_ex_args {
+    int n_seq, rps, base_pos, nh, nkv, max_seq, ld_qkv, ld_out;
+    int kernel, halves, use_planes;
+    float eps;
+    int* path;
+    const float* qkv; const float* q_norm_w; const float* k_norm_w;
+    const float* rope_cos; const float* rope_sin;
+    float* kcache; float* vcache; float* out;
+} q3_attn_prefill_ex_args;
+q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_args* args);
 /* Test API: channel norm of x [C][L] over C (launch_layernorm_c / launch_rmsnorm_c): layernorm != 0 takes w and b [C], else w only.
  * y: host buffer of y_elems floats, result at y_front, uploaded and copied back whole. */
 q3_status q3_norm_c(int device, int layernorm, const float* x, const float* w, const float* b, int C, int L, float eps,

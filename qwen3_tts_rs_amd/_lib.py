@@ -71,6 +71,18 @@ class CConvEx(ctypes.Structure):         # q3_conv_ex_args
                                                "mid_ib", "y", "y2")]
 
 
+class CGemmEx(ctypes.Structure):         # q3_gemm_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("M", "N", "K", "ldx", "ldy", "ldr", "M_alloc", "epi", "geometry", "k_split", "sup_m",
+                                              "sup_n")] + [("eps", ctypes.c_float), ("path", ctypes.POINTER(ctypes.c_int32))] + \
+               [(n, ctypes.c_void_p) for n in ("x", "w", "w2", "bias", "norm_w", "resid", "y")]
+
+
+class CAttnPrefillEx(ctypes.Structure):  # q3_attn_prefill_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_seq", "rps", "base_pos", "nh", "nkv", "max_seq", "ld_qkv", "ld_out", "kernel", "halves",
+                                              "use_planes")] + [("eps", ctypes.c_float), ("path", ctypes.POINTER(ctypes.c_int32))] + \
+               [(n, ctypes.c_void_p) for n in ("qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache", "out")]
+
+
 class CTiming(ctypes.Structure):
     _fields_ = [("prefill_ms", ctypes.c_double), ("generation_ms", ctypes.c_double), ("decode_ms", ctypes.c_double),
                 ("generation_frames", ctypes.c_int32)]
@@ -204,6 +216,10 @@ SYMBOLS = {
     "q3_resunit_path": (c_int, [c_int] * 6),
     "q3_conv_path_name": (c_char_p, [c_int]),
     "q3_conv_ex": (c_int, [c_int, P(CConvEx)]),
+    "q3_gemm_path": (c_int, [c_int] * 7 + [P(ctypes.c_int32)]),
+    "q3_gemm_ex": (c_int, [c_int, P(CGemmEx)]),
+    "q3_attn_prefill_path": (c_int, [c_int] * 4 + [P(ctypes.c_int32)]),
+    "q3_attn_prefill_ex": (c_int, [c_int, P(CAttnPrefillEx)]),
     "q3_norm_c": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_int, c_int]),
     "q3_dwconv7": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     "q3_decode_codes": (c_int, [c_void_p, c_void_p, c_int, c_void_p, P(c_void_p)]),

@@ -1768,6 +1768,90 @@ def conv_path(cout: int, cin: int, L: int, k: int, dil: int = 1, phases: int = 1
     return lib.q3_conv_path(cout, cin, L, k, dil, phases, int(packed), int(has_resid), planes, int(aligned16))
 
 
+def gemm_path(M: int, N: int, K: int, epi: int = 0, norm: bool = False, w2: bool = False, planes: bool = True):
+    """q3_gemm_path: (geometry, k_ranges, k_split, n_split) launch_lm_gemm picks for a shape, or None when it refuses the
+    arguments. geometry 0 = geometry 1 with the split in the kernel, 1 = geometry 1 over planes, 2, 3. No GPU needed."""
+    path = (ctypes.c_int32 * 4)()
+    g = lib.q3_gemm_path(M, N, K, epi, int(norm), int(w2), int(planes), path)
+    return None if g < 0 else tuple(path)
+
+
+def gemm_ex(x: np.ndarray, w_bf16: np.ndarray, *, w2_bf16: Optional[np.ndarray] = None, bias: Optional[np.ndarray] = None,
+            norm_w: Optional[np.ndarray] = None, eps: float = 1e-6, resid: Optional[np.ndarray] = None, epi: int = 0, geometry: int = -1,
+            k_split: int = 0, sup: Tuple[int, int] = (0, 0), y: Optional[np.ndarray] = None, M: Optional[int] = None, device: int = 0):
+    """q3_gemm_ex: one launch of the long-prompt prefill GEMM (parity tests); arguments as linear_ex. geometry -1 = the engine's
+    pick, 0 = geometry 1 with the split in the kernel, 1 / 2 / 3 forced over planes; k_split / sup = (sup_m, sup_n): 0 = the
+    engine's. Returns (y, path) with path = (geometry, k_ranges, k_split, n_split) that ran. Raises Q3Error (status 7) when the
+    launcher refuses."""
+    w = np.ascontiguousarray(w_bf16, dtype=np.uint16); N, K = w.shape
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    M = x.shape[0] if M is None else M
+    assert x.ndim == 2 and x.shape[0] >= M
+    if y is None:
+        y = np.zeros((M, N), dtype=np.float32)
+    assert y.dtype == np.float32 and y.flags.c_contiguous and y.ndim == 2
+    path = (ctypes.c_int32 * 4)()
+    a = _lib.CGemmEx()
+    a.M, a.N, a.K, a.ldx, a.ldy, a.M_alloc = M, N, K, x.shape[1], y.shape[1], y.shape[0]
+    a.epi, a.geometry, a.k_split, a.sup_m, a.sup_n, a.eps = epi, geometry, k_split, sup[0], sup[1], eps
+    a.path = ctypes.cast(path, ctypes.POINTER(ctypes.c_int32))
+    keep = [x, w, y]
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    a.x, a.w, a.y = ptr(x), ptr(w), ptr(y)
+    if w2_bf16 is not None:
+        w2 = np.ascontiguousarray(w2_bf16, dtype=np.uint16); assert w2.shape == w.shape
+        keep.append(w2); a.w2 = ptr(w2)
+    if bias is not None:
+        b = np.ascontiguousarray(bias, dtype=np.float32); assert b.shape == (N,)
+        keep.append(b); a.bias = ptr(b)
+    if norm_w is not None:
+        nw = np.ascontiguousarray(norm_w, dtype=np.float32); assert nw.shape == (K,)
+        keep.append(nw); a.norm_w = ptr(nw)
+    if resid is not None:
+        r = np.ascontiguousarray(resid, dtype=np.float32); assert r.ndim == 2 and r.shape[0] >= M
+        keep.append(r); a.resid = ptr(r); a.ldr = r.shape[1]
+    check(lib.q3_gemm_ex(device, ctypes.byref(a)))
+    return y, tuple(path)
+
+
+def attn_prefill_path(nh: int, nkv: int, use_planes: bool, halves: int = 1):
+    """q3_attn_prefill_path: (kernel, halves) launch_attn_prefill picks, or None when it refuses. No GPU needed."""
+    path = (ctypes.c_int32 * 2)()
+    k = lib.q3_attn_prefill_path(nh, nkv, int(use_planes), halves, path)
+    return None if k < 0 else tuple(path)
+
+
+def attn_prefill_ex(qkv: np.ndarray, n_seq: int, base_pos: int, q_norm_w: np.ndarray, k_norm_w: np.ndarray, eps: float, rope_cos: np.ndarray,
+                    rope_sin: np.ndarray, kcache: np.ndarray, vcache: np.ndarray, nh: int, nkv: int, *, kernel: int = -1, halves: int = 1,
+                    use_planes: bool = False, out: Optional[np.ndarray] = None, device: int = 0):
+    """q3_attn_prefill_ex: one prefill attention step over a contiguous cache [n_seq][nkv][max_seq][128] (parity tests): qkv
+    [n_seq * rps][ld_qkv] are the rows of n_seq sequences at positions base_pos .. base_pos + rps - 1. kernel -1 = the engine's pick
+    (with K/V planes when use_planes), 0 VALU / 1 gen2 MFMA / 2 transposed f32 MFMA / 3 bf16x3. out ([rows][ld_out] f32) is uploaded,
+    written in place and returned whole. Returns (out, kcache, vcache, (kernel, halves)) — the caches are copies."""
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32); rows = qkv.shape[0]
+    assert qkv.ndim == 2 and rows % n_seq == 0
+    rps = rows // n_seq
+    kc = np.array(kcache, dtype=np.float32, order="C"); vc = np.array(vcache, dtype=np.float32, order="C")
+    max_seq = kc.shape[2]
+    assert kc.shape == (n_seq, nkv, max_seq, 128) and vc.shape == kc.shape
+    qw = np.ascontiguousarray(q_norm_w, dtype=np.float32); kw = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    rc = np.ascontiguousarray(rope_cos, dtype=np.float32); rs = np.ascontiguousarray(rope_sin, dtype=np.float32)
+    assert qw.shape == (128,) and kw.shape == (128,) and rc.shape == (max_seq, 64) and rs.shape == (max_seq, 64)
+    if out is None:
+        out = np.zeros((rows, nh * 128), dtype=np.float32)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.ndim == 2 and out.shape[0] == rows
+    path = (ctypes.c_int32 * 2)()
+    a = _lib.CAttnPrefillEx()
+    a.n_seq, a.rps, a.base_pos, a.nh, a.nkv, a.max_seq, a.ld_qkv, a.ld_out = n_seq, rps, base_pos, nh, nkv, max_seq, qkv.shape[1], out.shape[1]
+    a.kernel, a.halves, a.use_planes, a.eps = kernel, halves, int(use_planes), eps
+    a.path = ctypes.cast(path, ctypes.POINTER(ctypes.c_int32))
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    a.qkv, a.q_norm_w, a.k_norm_w, a.rope_cos, a.rope_sin = ptr(qkv), ptr(qw), ptr(kw), ptr(rc), ptr(rs)
+    a.kcache, a.vcache, a.out = ptr(kc), ptr(vc), ptr(out)
+    check(lib.q3_attn_prefill_ex(device, ctypes.byref(a)))
+    return out, kc, vc, tuple(path)
+
+
 def resunit_path(C: int, L: int, dil: int, packed: bool = True, ya_is_xa: bool = False, planes: int = 3) -> int:
     """q3_resunit_path: launch_resunit's acceptance rule as a ConvPath code (0 = refused). No GPU needed."""
     return lib.q3_resunit_path(C, L, dil, int(packed), int(ya_is_xa), planes)

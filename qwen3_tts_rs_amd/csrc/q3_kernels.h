@@ -106,7 +106,22 @@ struct GemmArgs {
     int k_ranges = 1, k_split = 1, wg_per_split = 0;             // set by launch_lm_gemm
     int sup_m = 4, sup_n = 8;                                    // set by launch_lm_gemm (third geometry): M x N tiles of the super-tile one XCD runs at a time
 };
-hipError_t launch_lm_gemm(const GemmArgs& a, hipStream_t st);
+// Which geometry launch_lm_gemm runs for a shape, and with what work split: the launcher's own decision function (the prefill
+// knobs Q3_GEMM_* are read here and nowhere else), so that tests can table it and force any other legal pick.
+enum { GEMM_G1_SPLIT = 0,       // k_lm_gemm<.., PL = false>: 64 x 128 tiles, the bf16x3 split done while staging (no planes)
+       GEMM_G1_PLANES = 1,      // k_lm_gemm<.., PL = true>: the same geometry over pre-split planes
+       GEMM_G2 = 2,             // k_lm_gemm2
+       GEMM_G3 = 3 };           // k_lm_gemm3 (+ k_gemm_splitk_reduce when k_split > 1)
+struct GemmPick {
+    int geometry = GEMM_G1_SPLIT;
+    int n_split = 1;                                             // geometry 2: XCD work units per M tile
+    int k_ranges = 1, k_split = 1, sup_m = 4, sup_n = 8;         // geometry 3
+};
+// geometry < 0: the engine's choice; else the engine's work split for that geometry (legal for the shape or not: the launch decides)
+GemmPick lm_gemm_pick(const GemmArgs& a, int geometry = -1);
+hipError_t launch_lm_gemm(const GemmArgs& a, hipStream_t st);    // = launch_lm_gemm(a, lm_gemm_pick(a), st)
+// the named pick and nothing else: hipErrorInvalidValue for a pick the shape (or the epilogue / norm combination) does not allow
+hipError_t launch_lm_gemm(const GemmArgs& a, const GemmPick& p, hipStream_t st);
 // planes[pl][row][k] (pitch Kpad, zero beyond K) = pl-th bf16 term of x[row][k] * (norm_w ? norm_w[k] : 1); K % 8 == 0
 hipError_t launch_split_rows(const float* x, int ldx, const float* norm_w, uint16_t* planes, size_t plane_elems, int rows, int K,
                              int Kpad, hipStream_t st);
@@ -213,7 +228,18 @@ hipError_t launch_attn_merge(const AttnArgs& a, hipStream_t st);
 // the code predictor's 2-token first pass (rows 2b / 2b+1 at positions 0 / 1 of an empty cache), one launch
 hipError_t launch_attn_first2(const AttnArgs& a, hipStream_t st);
 // prefill: causal attention of rows_per_seq consecutive positions per sequence (B = total rows), after launch_qknorm_rope_kv
-hipError_t launch_attn_prefill(const AttnArgs& a, hipStream_t st);
+// Which kernel launch_attn_prefill runs and over how many key halves: the launcher's own decision function (Q3_PREFILL_ATTN_VALU /
+// Q3_PREFILL_ATTN_GEN2 are read here and nowhere else). halves == 2: partial records in a.part, launch_attn_merge follows.
+enum { AP_VALU = 0,             // k_attn_prefill<NREP, 8>: heads / kv heads 1 or 2
+       AP_GEN2 = 1,             // k_attn_prefill_mfma (S = Q.K^T on the f32 matrix cores)
+       AP_T = 2,                // k_attn_prefill_t (transposed product, f32 matrix cores)
+       AP_X3 = 3 };             // k_attn_prefill_x3 (bf16x3 planes of K/V: a.kvp)
+struct AttnPrefillPick { int kernel = AP_T; int halves = 1; };
+AttnPrefillPick attn_prefill_pick(const AttnArgs& a);
+int attn_prefill_rows_wg(int kernel, int nrep);                       // query rows per workgroup of a kernel
+hipError_t launch_attn_prefill(const AttnArgs& a, hipStream_t st);    // = launch_attn_prefill(a, attn_prefill_pick(a), st)
+// the named pick and nothing else: hipErrorInvalidValue for a pick the arguments do not allow
+hipError_t launch_attn_prefill(const AttnArgs& a, const AttnPrefillPick& p, hipStream_t st);
 // fused q/k-norm + RoPE + KV append + attention (+ final normalisation when n_splits == 1)
 hipError_t launch_attn_fused(const AttnArgs& a, hipStream_t st);
 // the same for caches that never exceed 16 positions with the position known at launch (the code predictor's single-row

@@ -645,98 +645,141 @@ __global__ __launch_bounds__(256) void k_gemm_splitk_reduce(GemmArgs a) {
     *reinterpret_cast<float4*>(a.y + (size_t)m * a.ldy + n) = make_float4(o[0], o[1], o[2], o[3]);
 }
 
+// ---- kernel selection (lm_gemm_pick) apart from launching (launch_lm_gemm): the prefill GEMM knobs are read here only ----
 static bool lm_gemm_geo3(const GemmArgs& a) {
     if (!a.xp || getenv("Q3_GEMM_GEO1")) return false;
     const char* ge = getenv("Q3_GEMM_GEO");
     const int force = ge ? atoi(ge) : 0;
     const int nt3 = a.epi == EPI_SWIGLU ? 128 : 256;
     const bool ok3 = a.Kpad % 128 == 0 && a.N % nt3 == 0;
-    const int nMt = (a.M + 127) / 128;
-    (void)nMt;                                                   // any grid size: with split-K small grids fill the chip too (round 2:
-    return ok3 && force != 2;                                    //   forced geometry 3 beat geometry 2 at 200 / 500 / 1000 positions already)
+    // any grid size: with split-K small grids fill the chip too (round 2: forced geometry 3 beat geometry 2 at 200 / 500 / 1000
+    // positions already); Q3_GEMM_GEO=2 keeps the second geometry (A/B aid, read per call)
+    return ok3 && force != 2;
+}
+// what the shape itself allows (the pick may still be refused for its work split: launch_lm_gemm)
+static bool lm_gemm_shape_ok(const GemmArgs& a, int geometry) {
+    if (a.M < 1 || a.N < 1 || a.Kpad < 32) return false;
+    switch (geometry) {
+        case GEMM_G1_SPLIT: return a.x != nullptr;
+        case GEMM_G1_PLANES: return a.xp != nullptr;
+        case GEMM_G2: return a.xp && a.N % (a.epi == EPI_SWIGLU ? 64 : 128) == 0;
+        case GEMM_G3: return a.xp && a.Kpad % 128 == 0 && a.N % (a.epi == EPI_SWIGLU ? 128 : 256) == 0;
+        default: return false;
+    }
+}
+// the engine's work split of the second geometry
+static void lm_gemm_split2(const GemmArgs& a, GemmPick& p) {
+    static const int q_env = [] { const char* e = getenv("Q3_GEMM_NSPLIT"); return e ? atoi(e) : 0; }();   // tuning aid
+    const int nNt = a.N / (a.epi == EPI_SWIGLU ? 64 : 128);
+    int Q = q_env > 0 ? q_env : 2;
+    while (Q > 1 && nNt % Q) --Q;
+    p.n_split = Q;
+}
+// ... and of the third
+static void lm_gemm_split3(const GemmArgs& a, GemmPick& p) {
+    // super-tile shape: 4 x 8 when the grid fills the chip; fewer M tiles per super-tile for small problems so
+    // that every XCD still gets work (Q3_GEMM3_SUP="m,n" overrides, A/B aid)
+    const int nt3 = a.epi == EPI_SWIGLU ? 128 : 256;
+    const int nMt = (a.M + 127) / 128, nNt = a.N / nt3, T = nMt * nNt;
+    p.sup_n = nNt < 8 ? nNt : 8;
+    p.sup_m = (T / 8 + p.sup_n - 1) / p.sup_n; p.sup_m = p.sup_m < 1 ? 1 : (p.sup_m > 4 ? 4 : p.sup_m);
+    if (const char* se = getenv("Q3_GEMM3_SUP")) { int m_ = 0, n_ = 0; if (sscanf(se, "%d,%d", &m_, &n_) == 2 && m_ > 0 && n_ > 0) { p.sup_m = m_; p.sup_n = n_; } }
+    // K ranges and split-K (see the kernel): 8 ranges when the stage count is a multiple of 16; the ranges are
+    // spread over 2 / 4 / 8 workgroups while that still leaves the grid within one round of the chip and the
+    // partial sums fit the workspace (Q3_GEMM3_KSPLIT = forced split, A/B aid)
+    const int nst = a.Kpad >> 6;
+    p.k_ranges = (nst % 16 == 0) ? 8 : 1;
+    p.k_split = 1;
+    const int nw = a.epi == EPI_SWIGLU ? 2 : 1;
+    if (p.k_ranges == 8 && a.splitk_ws) {
+        const char* ke = getenv("Q3_GEMM3_KSPLIT");
+        int ks = 1;
+        if (ke) ks = atoi(ke);
+        else while (ks < 8 && T * ks * 2 <= 256) ks *= 2;
+        if (ks != 1 && ks != 2 && ks != 4 && ks != 8) ks = 1;
+        if ((size_t)8 * nw * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) ks = 1;
+        p.k_split = ks;
+    }
+}
+GemmPick lm_gemm_pick(const GemmArgs& a, int geometry) {
+    GemmPick p;
+    if (geometry < 0) {
+        static const bool geo1 = getenv("Q3_GEMM_GEO1") != nullptr;          // A/B aid: the 64 x 128 geometry
+        // geometry 3 (256-row workgroup tiles, LDS-DMA, one barrier per stage) whenever the shape allows it, else geometry 2,
+        // else (or without planes) geometry 1
+        if (a.xp && !geo1 && lm_gemm_geo3(a)) geometry = GEMM_G3;
+        else if (a.xp && !geo1 && a.N % (a.epi == EPI_SWIGLU ? 64 : 128) == 0) geometry = GEMM_G2;
+        else geometry = a.xp ? GEMM_G1_PLANES : GEMM_G1_SPLIT;
+    }
+    p.geometry = geometry;
+    if (lm_gemm_shape_ok(a, geometry)) {
+        if (geometry == GEMM_G2) lm_gemm_split2(a, p);
+        if (geometry == GEMM_G3) lm_gemm_split3(a, p);
+    }
+    return p;
 }
 
 hipError_t launch_lm_gemm(const GemmArgs& a, hipStream_t st) {
+    // the argument check comes first, as it always has: lm_gemm_pick is not asked about arguments no geometry takes
+    if (a.Kpad % 32 || a.K % 4 || a.K > a.Kpad || a.ldx % 4 || a.ldy % 4 || a.N % 64 || a.M < 1 || !a.W) return hipErrorInvalidValue;
+    return launch_lm_gemm(a, lm_gemm_pick(a), st);
+}
+
+hipError_t launch_lm_gemm(const GemmArgs& a, const GemmPick& p, hipStream_t st) {
     if (a.Kpad % 32 || a.K % 4 || a.K > a.Kpad || a.ldx % 4 || a.ldy % 4 || a.N % 64 || a.M < 1 || !a.W) return hipErrorInvalidValue;
     const bool rms = a.norm_w != nullptr;
     if (rms && !a.den) return hipErrorInvalidValue;
-    static const bool geo1 = getenv("Q3_GEMM_GEO1") != nullptr;          // A/B aid: the 64 x 128 geometry
-    // geometry 3 (256-row workgroup tiles, LDS-DMA, one barrier per stage) when it fills the chip: one workgroup per CU,
-    // so its grid wants >= 256 workgroups; Q3_GEMM_GEO=2 / 3 forces a geometry (A/B aid, read per call)
-    if (a.xp && !geo1) {
-        const int nt3 = a.epi == EPI_SWIGLU ? 128 : 256;
-        const int nMt = (a.M + 127) / 128;
-        if (lm_gemm_geo3(a)) {
-            // super-tile shape: 4 x 8 when the grid fills the chip; fewer M tiles per super-tile for small problems so
-            // that every XCD still gets work (Q3_GEMM3_SUP="m,n" overrides, A/B aid)
-            const int nNt = a.N / nt3, T = nMt * nNt;
-            GemmArgs b = a;
-            b.sup_n = nNt < 8 ? nNt : 8;
-            b.sup_m = (T / 8 + b.sup_n - 1) / b.sup_n; b.sup_m = b.sup_m < 1 ? 1 : (b.sup_m > 4 ? 4 : b.sup_m);
-            if (const char* se = getenv("Q3_GEMM3_SUP")) { int m_ = 0, n_ = 0; if (sscanf(se, "%d,%d", &m_, &n_) == 2 && m_ > 0 && n_ > 0) { b.sup_m = m_; b.sup_n = n_; } }
-            const int nsup = ((nMt + b.sup_m - 1) / b.sup_m) * ((nNt + b.sup_n - 1) / b.sup_n);
-            dim3 g3((unsigned)(8 * ((nsup + 7) / 8) * b.sup_m * b.sup_n));
-            // K ranges and split-K (see the kernel): 8 ranges when the stage count is a multiple of 16; the ranges are
-            // spread over 2 / 4 / 8 workgroups while that still leaves the grid within one round of the chip and the
-            // partial sums fit the workspace (Q3_GEMM3_KSPLIT = forced split, A/B aid)
-            const int nst = a.Kpad >> 6;
-            b.k_ranges = (nst % 16 == 0) ? 8 : 1;
-            b.k_split = 1;
-            const int nw = a.epi == EPI_SWIGLU ? 2 : 1;
-            if (b.k_ranges == 8 && a.splitk_ws) {
-                const char* ke = getenv("Q3_GEMM3_KSPLIT");
-                int ks = 1;
-                if (ke) ks = atoi(ke);
-                else while (ks < 8 && T * ks * 2 <= 256) ks *= 2;
-                if (ks != 1 && ks != 2 && ks != 4 && ks != 8) ks = 1;
-                if ((size_t)8 * nw * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) ks = 1;
-                b.k_split = ks;
-            }
-            b.wg_per_split = (int)g3.x;
-            g3.x *= b.k_split;
-#define Q3_GEMM3(E, R) do { hipLaunchKernelGGL((k_lm_gemm3<E, R>), g3, dim3(512), 0, st, b); \
-                            if (b.k_split > 1) hipLaunchKernelGGL((k_gemm_splitk_reduce<E, R>), dim3((unsigned)(((size_t)a.M * (a.N / 4) + 255) / 256)), dim3(256), 0, st, b); } while (0)
-            switch (a.epi) {
-                case EPI_NONE: if (rms) Q3_GEMM3(EPI_NONE, true); else Q3_GEMM3(EPI_NONE, false); return hipGetLastError();
-                case EPI_RESID: if (rms) return hipErrorInvalidValue; Q3_GEMM3(EPI_RESID, false); return hipGetLastError();
-                case EPI_SILU: if (rms) return hipErrorInvalidValue; Q3_GEMM3(EPI_SILU, false); return hipGetLastError();
-                case EPI_SWIGLU: if (!rms || !a.W2) return hipErrorInvalidValue; Q3_GEMM3(EPI_SWIGLU, true); return hipGetLastError();
-                default: return hipErrorInvalidValue;
-            }
-#undef Q3_GEMM3
-        }
-    }
-    if (a.xp && !geo1) {
-        const int nt = a.epi == EPI_SWIGLU ? 64 : 128;
-        if (a.N % nt == 0) {
-            static const int q_env = [] { const char* e = getenv("Q3_GEMM_NSPLIT"); return e ? atoi(e) : 0; }();   // tuning aid
-            const int nMt = (a.M + 127) / 128, nNt = a.N / nt;
-            int Q = q_env > 0 ? q_env : 2;
-            while (Q > 1 && nNt % Q) --Q;
-            GemmArgs b = a; b.n_split = Q;
-            const int units = nMt * Q, rounds = (units + 7) / 8;
-            dim3 g2(8 * rounds * (nNt / Q));
-#define Q3_GEMM2(E, R) hipLaunchKernelGGL((k_lm_gemm2<E, R>), g2, dim3(256), 0, st, b)
-            switch (a.epi) {
-                case EPI_NONE: if (rms) Q3_GEMM2(EPI_NONE, true); else Q3_GEMM2(EPI_NONE, false); return hipGetLastError();
-                case EPI_RESID: if (rms) return hipErrorInvalidValue; Q3_GEMM2(EPI_RESID, false); return hipGetLastError();
-                case EPI_SILU: if (rms) return hipErrorInvalidValue; Q3_GEMM2(EPI_SILU, false); return hipGetLastError();
-                case EPI_SWIGLU: if (!rms || !a.W2) return hipErrorInvalidValue; Q3_GEMM2(EPI_SWIGLU, true); return hipGetLastError();
-                default: return hipErrorInvalidValue;
-            }
-#undef Q3_GEMM2
-        }
-    }
-    dim3 grid((a.M + 127) / 128, a.N / 64);
-#define Q3_GEMM(E, R) do { if (a.xp) hipLaunchKernelGGL((k_lm_gemm<E, R, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((k_lm_gemm<E, R, false>), grid, dim3(256), 0, st, a); } while (0)
-    switch (a.epi) {
-        case EPI_NONE: if (rms) Q3_GEMM(EPI_NONE, true); else Q3_GEMM(EPI_NONE, false); break;
-        case EPI_RESID: if (rms) return hipErrorInvalidValue; Q3_GEMM(EPI_RESID, false); break;
-        case EPI_SILU: if (rms) return hipErrorInvalidValue; Q3_GEMM(EPI_SILU, false); break;
-        case EPI_SWIGLU: if (!rms || !a.W2) return hipErrorInvalidValue; Q3_GEMM(EPI_SWIGLU, true); break;
+    switch (a.epi) {                                             // the epilogue / norm combinations the kernels are built for
+        case EPI_NONE: break;
+        case EPI_RESID: case EPI_SILU: if (rms) return hipErrorInvalidValue; break;
+        case EPI_SWIGLU: if (!rms || !a.W2) return hipErrorInvalidValue; break;
         default: return hipErrorInvalidValue;
     }
+    if (!lm_gemm_shape_ok(a, p.geometry)) return hipErrorInvalidValue;
+#define Q3_GEMM_BY_EPI(L) switch (a.epi) { \
+        case EPI_NONE: if (rms) L(EPI_NONE, true); else L(EPI_NONE, false); break; \
+        case EPI_RESID: L(EPI_RESID, false); break; \
+        case EPI_SILU: L(EPI_SILU, false); break; \
+        default: L(EPI_SWIGLU, true); break; }
+    if (p.geometry == GEMM_G3) {
+        const int nt3 = a.epi == EPI_SWIGLU ? 128 : 256, nw = a.epi == EPI_SWIGLU ? 2 : 1;
+        const int nMt = (a.M + 127) / 128, nNt = a.N / nt3, nst = a.Kpad >> 6;
+        if (p.sup_m < 1 || p.sup_n < 1) return hipErrorInvalidValue;
+        // a range is a whole number of stage pairs; split-K spreads the 8 ranges and needs the workspace for all of them
+        if ((p.k_ranges != 1 && p.k_ranges != 8) || nst % (2 * p.k_ranges)) return hipErrorInvalidValue;
+        if (p.k_split != 1) {
+            if (p.k_ranges != 8 || (p.k_split != 2 && p.k_split != 4 && p.k_split != 8)) return hipErrorInvalidValue;
+            if (!a.splitk_ws || (size_t)8 * nw * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) return hipErrorInvalidValue;
+        }
+        GemmArgs b = a;
+        b.sup_m = p.sup_m; b.sup_n = p.sup_n; b.k_ranges = p.k_ranges; b.k_split = p.k_split;
+        const int nsup = ((nMt + b.sup_m - 1) / b.sup_m) * ((nNt + b.sup_n - 1) / b.sup_n);
+        dim3 g3((unsigned)(8 * ((nsup + 7) / 8) * b.sup_m * b.sup_n));
+        b.wg_per_split = (int)g3.x;
+        g3.x *= b.k_split;
+#define Q3_GEMM3(E, R) do { hipLaunchKernelGGL((k_lm_gemm3<E, R>), g3, dim3(512), 0, st, b); \
+                            if (b.k_split > 1) hipLaunchKernelGGL((k_gemm_splitk_reduce<E, R>), dim3((unsigned)(((size_t)a.M * (a.N / 4) + 255) / 256)), dim3(256), 0, st, b); } while (0)
+        Q3_GEMM_BY_EPI(Q3_GEMM3)
+#undef Q3_GEMM3
+        return hipGetLastError();
+    }
+    if (p.geometry == GEMM_G2) {
+        const int nt = a.epi == EPI_SWIGLU ? 64 : 128;
+        const int nMt = (a.M + 127) / 128, nNt = a.N / nt, Q = p.n_split;
+        if (Q < 1 || nNt % Q) return hipErrorInvalidValue;
+        GemmArgs b = a; b.n_split = Q;
+        const int units = nMt * Q, rounds = (units + 7) / 8;
+        dim3 g2(8 * rounds * (nNt / Q));
+#define Q3_GEMM2(E, R) hipLaunchKernelGGL((k_lm_gemm2<E, R>), g2, dim3(256), 0, st, b)
+        Q3_GEMM_BY_EPI(Q3_GEMM2)
+#undef Q3_GEMM2
+        return hipGetLastError();
+    }
+    dim3 grid((a.M + 127) / 128, a.N / 64);
+#define Q3_GEMM(E, R) do { if (p.geometry == GEMM_G1_PLANES) hipLaunchKernelGGL((k_lm_gemm<E, R, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((k_lm_gemm<E, R, false>), grid, dim3(256), 0, st, a); } while (0)
+    Q3_GEMM_BY_EPI(Q3_GEMM)
 #undef Q3_GEMM
+#undef Q3_GEMM_BY_EPI
     return hipGetLastError();
 }
 
@@ -1083,11 +1126,16 @@ __global__ __launch_bounds__(256, 2) void k_attn_prefill_t(AttnArgs a) {      //
             S[r] = sv; cm = fmaxf(cm, sv);
         }
         cm = fmaxf(cm, __shfl_xor(cm, 32));
-        const float mn = fmaxf(m, cm);                         // finite from tile 0 on: key 0 is visible to every query
-        const float corr = expf(m - mn);
+        // mn is finite from tile 0 on (key 0 is visible to every query) — but the second key half starts at tile h0, and when
+        // the chunk's base is not a multiple of 32 a wave's positions straddle a tile start: its early queries see that tile
+        // fully masked and keep m = mn = -inf. They take 0 as the reference, so corr and every pe are exp(-inf) = 0 and not
+        // exp(-inf + inf); the record (0, -inf, 0) merges as nothing. A finite mn is its own reference: the same bits as ever.
+        const float mn = fmaxf(m, cm);
+        const float mref = mn == -INFINITY ? 0.0f : mn;
+        const float corr = expf(m - mref);
         float ps = 0.0f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { const float pe = expf(S[r] - mn); S[r] = pe; ps += pe; }
+        for (int r = 0; r < 16; ++r) { const float pe = expf(S[r] - mref); S[r] = pe; ps += pe; }
         lsum = lsum * corr + ps;
         m = mn;
 #pragma unroll
@@ -1318,11 +1366,12 @@ __global__ __launch_bounds__(512) void k_attn_prefill_x3(AttnArgs a) {
             S[r] = sv; cm = fmaxf(cm, sv);
         }
         cm = fmaxf(cm, __shfl_xor(cm, 32));
-        const float mn = fmaxf(m, cm);                         // finite from tile 0 on: key 0 is visible to every query
-        const float corr = expf(m - mn);
+        const float mn = fmaxf(m, cm);                         // -inf in a second key half at an unaligned base: see k_attn_prefill_t
+        const float mref = mn == -INFINITY ? 0.0f : mn;
+        const float corr = expf(m - mref);
         float ps = 0.0f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { const float pe = expf(S[r] - mn); S[r] = pe; ps += pe; }
+        for (int r = 0; r < 16; ++r) { const float pe = expf(S[r] - mref); S[r] = pe; ps += pe; }
         lsum = lsum * corr + ps;
         m = mn;
 #pragma unroll
@@ -1392,39 +1441,63 @@ __global__ __launch_bounds__(512) void k_attn_prefill_x3(AttnArgs a) {
                 make_float4(O[b][4 * q4] / den, O[b][4 * q4 + 1] / den, O[b][4 * q4 + 2] / den, O[b][4 * q4 + 3] / den);
 }
 
-hipError_t launch_attn_prefill(const AttnArgs& a, hipStream_t st) {
-    const int nrep = a.nh / a.nkv;
-    const int rps = a.rows_per_seq;
-    if (rps < 1 || a.B % rps) return hipErrorInvalidValue;
+// ---- kernel selection (attn_prefill_pick) apart from launching: the prefill attention knobs are read here only ----
+AttnPrefillPick attn_prefill_pick(const AttnArgs& a) {
+    AttnPrefillPick p;
+    const int nrep = a.nkv > 0 ? a.nh / a.nkv : 0;
     static const bool valu = getenv("Q3_PREFILL_ATTN_VALU") != nullptr;      // A/B aid: the VALU kernel
     if (!valu && (nrep == 1 || nrep == 2 || nrep == 4)) {
-        if (a.kvp) {                                              // bf16x3 generation: 256/nrep query rows per workgroup
-            const int rows_x3 = 256 / nrep;
-            const int nb = ((rps + rows_x3 - 1) / rows_x3) * ((a.n_splits == 2 && a.part) ? 2 : 1);
-            const int npairs = (a.B / rps) * a.nkv, rounds = (npairs + 7) / 8;
-            dim3 gx((unsigned)(8 * rounds) * nb);
-            if (nrep == 1) hipLaunchKernelGGL((k_attn_prefill_x3<1>), gx, dim3(512), 0, st, a);
-            else if (nrep == 2) hipLaunchKernelGGL((k_attn_prefill_x3<2>), gx, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((k_attn_prefill_x3<4>), gx, dim3(512), 0, st, a);
-            return hipGetLastError();
-        }
-        const int rows_wg = 128 / nrep;
-        dim3 grid((rps + rows_wg - 1) / rows_wg, a.nkv, a.B / rps);
-        static const bool gen2 = getenv("Q3_PREFILL_ATTN_GEN2") != nullptr;  // A/B aid: the S = Q·Kᵀ generation
-        if (!gen2 && a.n_splits == 2 && a.part) grid.x *= 2;
-        if (gen2) {
-            if (nrep == 1) hipLaunchKernelGGL((k_attn_prefill_mfma<1>), grid, dim3(256), 0, st, a);
-            else if (nrep == 2) hipLaunchKernelGGL((k_attn_prefill_mfma<2>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((k_attn_prefill_mfma<4>), grid, dim3(256), 0, st, a);
+        const int halves = (a.n_splits == 2 && a.part) ? 2 : 1;
+        if (a.kvp) { p.kernel = AP_X3; p.halves = halves; return p; }        // bf16x3 generation: 256/nrep query rows per workgroup
+        static const bool gen2 = getenv("Q3_PREFILL_ATTN_GEN2") != nullptr;  // A/B aid: the S = Q·Kᵀ generation (no key halves)
+        if (gen2) { p.kernel = AP_GEN2; p.halves = 1; } else { p.kernel = AP_T; p.halves = halves; }
+        return p;
+    }
+    p.kernel = AP_VALU; p.halves = 1;                                         // ratios 1 and 2 only: the launch refuses the rest
+    return p;
+}
+int attn_prefill_rows_wg(int kernel, int nrep) { return kernel == AP_VALU ? 8 : (kernel == AP_X3 ? 256 : 128) / (nrep > 0 ? nrep : 1); }
+
+hipError_t launch_attn_prefill(const AttnArgs& a, hipStream_t st) {
+    if (a.rows_per_seq < 1 || a.B % a.rows_per_seq) return hipErrorInvalidValue;
+    return launch_attn_prefill(a, attn_prefill_pick(a), st);
+}
+
+hipError_t launch_attn_prefill(const AttnArgs& a, const AttnPrefillPick& p, hipStream_t st) {
+    const int rps = a.rows_per_seq;
+    if (rps < 1 || a.B % rps || a.nkv < 1 || a.nh % a.nkv) return hipErrorInvalidValue;
+    const int nrep = a.nh / a.nkv;
+    const int npairs = (a.B / rps) * a.nkv, rounds = (npairs + 7) / 8;
+    if (p.kernel == AP_T || p.kernel == AP_X3) {
+        if (nrep != 1 && nrep != 2 && nrep != 4) return hipErrorInvalidValue;
+        // the kernels take their halves count from n_splits: the pick, the grid and the records must agree
+        if (p.halves != ((a.n_splits == 2) ? 2 : 1) || (p.halves == 2 && !a.part)) return hipErrorInvalidValue;
+        if (p.kernel == AP_X3 && !a.kvp) return hipErrorInvalidValue;
+        const int rows_wg = attn_prefill_rows_wg(p.kernel, nrep);
+        const int nb = ((rps + rows_wg - 1) / rows_wg) * p.halves;            // (query blocks x key halves)
+        dim3 g1((unsigned)(8 * rounds) * nb);
+        if (p.kernel == AP_X3) {
+            if (nrep == 1) hipLaunchKernelGGL((k_attn_prefill_x3<1>), g1, dim3(512), 0, st, a);
+            else if (nrep == 2) hipLaunchKernelGGL((k_attn_prefill_x3<2>), g1, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((k_attn_prefill_x3<4>), g1, dim3(512), 0, st, a);
         } else {
-            const int npairs = (a.B / rps) * a.nkv, rounds = (npairs + 7) / 8;
-            dim3 g1((unsigned)(8 * rounds) * grid.x);            // grid.x already counts (query blocks x key halves)
             if (nrep == 1) hipLaunchKernelGGL((k_attn_prefill_t<1>), g1, dim3(256), 0, st, a);
             else if (nrep == 2) hipLaunchKernelGGL((k_attn_prefill_t<2>), g1, dim3(256), 0, st, a);
             else hipLaunchKernelGGL((k_attn_prefill_t<4>), g1, dim3(256), 0, st, a);
         }
         return hipGetLastError();
     }
+    if (p.halves != 1) return hipErrorInvalidValue;                           // the first two generations have no key halves
+    if (p.kernel == AP_GEN2) {
+        if (nrep != 1 && nrep != 2 && nrep != 4) return hipErrorInvalidValue;
+        const int rows_wg = 128 / nrep;
+        dim3 grid((rps + rows_wg - 1) / rows_wg, a.nkv, a.B / rps);
+        if (nrep == 1) hipLaunchKernelGGL((k_attn_prefill_mfma<1>), grid, dim3(256), 0, st, a);
+        else if (nrep == 2) hipLaunchKernelGGL((k_attn_prefill_mfma<2>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_attn_prefill_mfma<4>), grid, dim3(256), 0, st, a);
+        return hipGetLastError();
+    }
+    if (p.kernel != AP_VALU) return hipErrorInvalidValue;
     constexpr int RQ = 8;
     dim3 grid((rps + RQ - 1) / RQ, a.nkv, a.B / rps);
     if (nrep == 1) hipLaunchKernelGGL((k_attn_prefill<1, RQ>), grid, dim3(256), 0, st, a);

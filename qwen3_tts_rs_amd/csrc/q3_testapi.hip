@@ -448,6 +448,178 @@ extern "C" q3_status q3_dwconv7(int device, const float* x_host, const float* w_
     return Q3_OK;
 }
 
+// ---- the long-prompt prefill kernels, one launch at a time (tests/test_gpu_prefill_ops.py) ----
+static hipError_t fill_ff(void* dev, size_t bytes) {                 // 0xFF bytes: bf16 / f32 NaN wherever a kernel reads what nobody wrote
+    std::vector<unsigned char> h(bytes, 0xFF);
+    return q3_hipMemcpy(dev, h.data(), bytes, hipMemcpyHostToDevice);
+}
+static void gemm_path_out(const GemmPick& p, int* path) {
+    if (!path) return;
+    path[0] = p.geometry; path[1] = p.geometry == GEMM_G3 ? p.k_ranges : 1; path[2] = p.geometry == GEMM_G3 ? p.k_split : 1;
+    path[3] = p.geometry == GEMM_G2 ? p.n_split : 1;
+}
+// the split-K workspace the entry passes — every range sum of the shape — when the stage count lets k_split != 1 be picked at all
+static size_t gemm_ex_ws_bytes(int M, int N, int Kpad, int epi) {
+    if (Kpad % 128 || (Kpad >> 6) % 16) return 0;
+    return (size_t)8 * (epi == EPI_SWIGLU ? 2 : 1) * M * N * sizeof(float);
+}
+
+extern "C" int q3_gemm_path(int M, int N, int K, int epi, int norm, int w2, int planes, int* path) {
+    if (path) path[0] = path[1] = path[2] = path[3] = 0;
+    if (M < 1 || N < 1 || K < 4) return -1;
+    // nothing is dereferenced by the pick: the pointers only say what the caller has
+    static float dummy[4];
+    GemmArgs g;
+    g.W = reinterpret_cast<const uint16_t*>(dummy); g.W2 = w2 ? g.W : nullptr; g.x = dummy; g.ldx = up32(K); g.y = dummy; g.ldy = N;
+    g.norm_w = norm ? dummy : nullptr; g.den = norm ? dummy : nullptr;
+    g.M = M; g.N = N; g.K = K; g.Kpad = up32(K); g.epi = epi;
+    if (planes) { g.xp = g.W; g.xp_plane = (size_t)up128(M) * g.Kpad; g.splitk_ws_bytes = gemm_ex_ws_bytes(M, N, g.Kpad, epi); g.splitk_ws = g.splitk_ws_bytes ? dummy : nullptr; }
+    if (g.K % 4 || g.N % 64 || (planes && K % 8)) return -1;
+    const bool rms = norm != 0;
+    if (epi < EPI_NONE || epi > EPI_SWIGLU || ((epi == EPI_RESID || epi == EPI_SILU) && rms) || (epi == EPI_SWIGLU && (!rms || !w2))) return -1;
+    const GemmPick p = lm_gemm_pick(g);
+    gemm_path_out(p, path);
+    return p.geometry;
+}
+
+// One launch_lm_gemm call over host arrays: the weights go through the loader's retile_bf16, a norm through launch_row_den, the
+// planes through launch_split_rows into a NaN-filled buffer of whole 128-row tiles; exactly one GEMM launch (+ its split-K reduce)
+// runs. A launch the dispatcher refuses comes back as a status — never another geometry in its place — and leaves the host y alone.
+extern "C" q3_status q3_gemm_ex(int device, const q3_gemm_ex_args* p) {
+    if (!p || !p->x || !p->w || !p->y) return set_err(Q3_INVALID_ARG, "q3_gemm_ex: null argument");
+    if (p->path) p->path[0] = p->path[1] = p->path[2] = p->path[3] = 0;
+    const int M = p->M, N = p->N, K = p->K;
+    if (M < 1 || M > 8192 || N < 1 || N > 16384 || K < 4 || K > 16384) return set_err(Q3_INVALID_ARG, "q3_gemm_ex: bad shape (M 1..8192, N 1..16384, K 4..16384)");
+    if (p->ldx < K || p->ldy < N || p->M_alloc < M) return set_err(Q3_INVALID_ARG, "q3_gemm_ex: bad pitch (ldx >= K, ldy >= N, M_alloc >= M)");
+    if (p->epi < EPI_NONE || p->epi > EPI_SWIGLU || p->geometry < -1 || p->geometry > GEMM_G3 || p->k_split < 0 || p->sup_m < 0 || p->sup_n < 0 || !p->sup_m != !p->sup_n)
+        return set_err(Q3_INVALID_ARG, "q3_gemm_ex: epi 0..3, geometry -1..3, k_split / sup_m / sup_n >= 0 (the super-tile as a pair)");
+    if (p->epi == EPI_RESID && (!p->resid || p->ldr < N)) return set_err(Q3_INVALID_ARG, "q3_gemm_ex: residual epilogue needs resid with ldr >= N");
+    const bool planes = p->geometry != GEMM_G1_SPLIT;
+    // what no kernel of the family can address (vector loads and stores of 4 floats, 8 k per plane store) is refused here: the
+    // launchers say the same, but the preparation launches would run first
+    if (K % 4 || p->ldx % 4 || p->ldy % 4 || N % 64 || (p->resid && p->ldr % 4)) return set_err(Q3_UNSUPPORTED, "q3_gemm_ex: K, ldx, ldy, ldr multiples of 4 and N of 64");
+    if (planes && K % 8) return set_err(Q3_UNSUPPORTED, "q3_gemm_ex: pre-split planes need K %% 8 == 0 (K = %d)", K);
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const int nmat = p->w2 ? 2 : 1, Kpad = up32(K);
+    const size_t welems = tiled_elems(1, N, K);
+    uint16_t* w; float *x, *y, *b = nullptr, *nw = nullptr, *den = nullptr, *res = nullptr, *ws = nullptr; uint16_t* xp = nullptr;
+    HIPC(pool.alloc(&w, welems * nmat));
+    for (int i = 0; i < nmat; ++i) {
+        std::vector<uint16_t> wt(welems);
+        retile_bf16(i ? p->w2 : p->w, N, K, wt.data(), 1);
+        HIPC(q3_hipMemcpy(w + (size_t)i * welems, wt.data(), welems * 2, hipMemcpyHostToDevice));
+    }
+    const size_t xn = (size_t)M * p->ldx, yn = (size_t)p->M_alloc * p->ldy;
+    HIPC(pool.alloc(&x, xn)); HIPC(q3_hipMemcpy(x, p->x, xn * 4, hipMemcpyHostToDevice));
+    HIPC(pool.alloc(&y, yn)); HIPC(q3_hipMemcpy(y, p->y, yn * 4, hipMemcpyHostToDevice));
+    if (p->bias) { HIPC(pool.alloc(&b, (size_t)N)); HIPC(q3_hipMemcpy(b, p->bias, (size_t)N * 4, hipMemcpyHostToDevice)); }
+    if (p->norm_w) { HIPC(pool.alloc(&nw, (size_t)K)); HIPC(q3_hipMemcpy(nw, p->norm_w, (size_t)K * 4, hipMemcpyHostToDevice)); HIPC(pool.alloc(&den, (size_t)M)); }
+    if (p->epi == EPI_RESID) { HIPC(pool.alloc(&res, (size_t)M * p->ldr)); HIPC(q3_hipMemcpy(res, p->resid, (size_t)M * p->ldr * 4, hipMemcpyHostToDevice)); }
+    const size_t plane_elems = (size_t)up128(M) * Kpad;              // whole 128-row tiles (GemmArgs::xp)
+    size_t ws_bytes = 0;
+    if (planes) {
+        HIPC(pool.alloc(&xp, plane_elems * 3)); HIPC(fill_ff(xp, plane_elems * 3 * 2));
+        ws_bytes = gemm_ex_ws_bytes(M, N, Kpad, p->epi);
+        if (ws_bytes) { HIPC(pool.alloc(&ws, ws_bytes / 4)); HIPC(fill_ff(ws, ws_bytes)); }
+    }
+    GemmArgs g;
+    g.W = w; g.W2 = nmat == 2 ? w + welems : nullptr; g.x = x; g.ldx = p->ldx; g.norm_w = nw; g.den = den; g.bias = b;
+    g.resid = res; g.ldr = res ? p->ldr : 0; g.y = y; g.ldy = p->ldy; g.M = M; g.N = N; g.K = K; g.Kpad = Kpad; g.epi = p->epi;
+    g.xp = xp; g.xp_plane = xp ? plane_elems : 0; g.splitk_ws = ws; g.splitk_ws_bytes = ws_bytes;
+    GemmPick pick = lm_gemm_pick(g, p->geometry);
+    if (p->k_split) pick.k_split = p->k_split;
+    if (p->sup_m) { pick.sup_m = p->sup_m; pick.sup_n = p->sup_n; }
+    HIPC(q3_hipDeviceSynchronize());
+    if (nw) HIPC(launch_row_den(x, p->ldx, den, M, K, p->eps, 0));
+    if (xp) HIPC(launch_split_rows(x, p->ldx, nw, xp, plane_elems, M, K, Kpad, 0));
+    const hipError_t e = launch_lm_gemm(g, pick, 0);
+    if (e == hipErrorInvalidValue || e == hipErrorNotSupported) {
+        (void)hipGetLastError();
+        (void)q3_hipDeviceSynchronize();
+        return set_err(Q3_UNSUPPORTED, "q3_gemm_ex: launch_lm_gemm refused M=%d N=%d K=%d epi=%d norm=%d geometry=%d k_ranges=%d k_split=%d sup=%dx%d (%s)", M, N, K,
+                       p->epi, nw ? 1 : 0, pick.geometry, pick.k_ranges, pick.k_split, pick.sup_m, pick.sup_n, hipGetErrorString(e));
+    }
+    HIPC(e);
+    HIPC(q3_hipDeviceSynchronize());
+    gemm_path_out(pick, p->path);
+    HIPC(q3_hipMemcpy(p->y, y, yn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" int q3_attn_prefill_path(int nh, int nkv, int use_planes, int halves, int* path) {
+    if (path) path[0] = path[1] = 0;
+    if (nkv < 1 || nh < nkv || nh % nkv || halves < 1 || halves > 2) return -1;
+    static float dummy[4];
+    AttnArgs t{};
+    t.nh = nh; t.nkv = nkv; t.n_splits = halves; t.part = halves == 2 ? dummy : nullptr; t.kvp = use_planes ? reinterpret_cast<const unsigned char*>(dummy) : nullptr;
+    const AttnPrefillPick p = attn_prefill_pick(t);
+    if (p.kernel == AP_VALU && nh / nkv > 2) return -1;              // what the launch refuses
+    if (path) { path[0] = p.kernel; path[1] = p.halves; }
+    return p.kernel;
+}
+
+// One prefill attention step over a contiguous cache: launch_qknorm_rope_kv (rows_per_seq = rps), launch_kv_planes for the bf16x3
+// kernel (into a NaN-filled buffer with more tiles allocated than used), ONE launch_attn_prefill, launch_attn_merge for two halves
+// (over NaN-filled records). A refused launch comes back as a status and leaves the host caches and out alone.
+extern "C" q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_args* p) {
+    if (!p || !p->qkv || !p->q_norm_w || !p->k_norm_w || !p->rope_cos || !p->rope_sin || !p->kcache || !p->vcache || !p->out)
+        return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: null argument");
+    if (p->path) p->path[0] = p->path[1] = 0;
+    const int n_seq = p->n_seq, rps = p->rps, nh = p->nh, nkv = p->nkv, base = p->base_pos;
+    if (p->kernel < -1 || p->kernel > AP_X3 || p->halves < 1 || p->halves > 2) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: kernel -1..3, halves 1..2");
+    if (n_seq < 1 || n_seq > 64 || rps < 1 || rps > 8192 || nkv < 1 || nh < nkv || nh > 64 || nh % nkv || p->max_seq < 1 || base < 0 || base + rps > p->max_seq)
+        return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: bad shape (the chunk [base_pos, base_pos + rps) must lie inside max_seq)");
+    const int ld_qkv = p->ld_qkv, QD = nh * HEAD_DIM, rows = n_seq * rps;
+    if (ld_qkv < (nh + 2 * nkv) * HEAD_DIM || ld_qkv % 4 || p->ld_out < QD || p->ld_out % 4) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: bad pitch");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const size_t cn = (size_t)n_seq * nkv * p->max_seq * HEAD_DIM, rn = (size_t)p->max_seq * 64, on = (size_t)rows * p->ld_out;
+    float *qkv, *qw, *kw, *rc, *rs, *kv, *qbuf, *part = nullptr, *out; unsigned char* kvp = nullptr;
+    HIPC(pool.alloc(&qkv, (size_t)rows * ld_qkv)); HIPC(pool.alloc(&qw, (size_t)HEAD_DIM)); HIPC(pool.alloc(&kw, (size_t)HEAD_DIM));
+    HIPC(pool.alloc(&rc, rn)); HIPC(pool.alloc(&rs, rn)); HIPC(pool.alloc(&kv, 2 * cn));
+    HIPC(pool.alloc(&qbuf, (size_t)rows * QD)); HIPC(pool.alloc(&out, on));
+    HIPC(q3_hipMemcpy(qkv, p->qkv, (size_t)rows * ld_qkv * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(qw, p->q_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kw, p->k_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(rc, p->rope_cos, rn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(rs, p->rope_sin, rn * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(kv, p->kcache, cn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kv + cn, p->vcache, cn * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(out, p->out, on * 4, hipMemcpyHostToDevice));
+    AttnArgs t{};
+    t.qkv = qkv; t.ld_qkv = ld_qkv; t.q_norm_w = qw; t.k_norm_w = kw; t.eps = p->eps; t.rope_cos = rc; t.rope_sin = rs;
+    t.pos_dev = nullptr; t.pos_static = base; t.kcache = kv; t.vcache = kv + cn; t.max_seq = p->max_seq; t.qbuf = qbuf; t.out = out; t.ld_out = p->ld_out;
+    t.B = rows; t.nh = nh; t.nkv = nkv; t.n_splits = 1; t.rows_per_seq = rps;
+    const int tiles = (base + rps + 31) / 32, kvp_tiles = tiles + 2;
+    const bool want_planes = p->kernel == AP_X3 || (p->kernel < 0 && p->use_planes);
+    if (want_planes) {
+        const size_t kb = (size_t)n_seq * nkv * kvp_tiles * KVP_TILE_BYTES;
+        HIPC(pool.alloc(&kvp, kb)); HIPC(fill_ff(kvp, kb));
+    }
+    if (p->halves == 2) {
+        const size_t pn = (size_t)rows * nh * 2 * PART_STRIDE;
+        HIPC(pool.alloc(&part, pn)); HIPC(fill_ff(part, pn * 4));
+    }
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_qknorm_rope_kv(t, 0));
+    if (kvp) { HIPC(launch_kv_planes(t, n_seq * nkv, base + rps, kvp_tiles, kvp, 0)); t.kvp = kvp; t.kvp_tiles = kvp_tiles; }
+    if (p->halves == 2) { t.part = part; t.n_splits = 2; }
+    AttnPrefillPick pick = attn_prefill_pick(t);
+    if (p->kernel >= 0) { pick.kernel = p->kernel; pick.halves = p->halves; }
+    hipError_t e = pick.halves == p->halves ? launch_attn_prefill(t, pick, 0) : hipErrorInvalidValue;      // the engine's pick has no key halves here
+    if (e == hipErrorInvalidValue || e == hipErrorNotSupported) {
+        (void)hipGetLastError();
+        (void)q3_hipDeviceSynchronize();
+        return set_err(Q3_UNSUPPORTED, "q3_attn_prefill_ex: launch_attn_prefill refused kernel=%d halves=%d nh=%d nkv=%d rps=%d base_pos=%d (%s)", pick.kernel,
+                       p->halves, nh, nkv, rps, base, hipGetErrorString(e));
+    }
+    HIPC(e);
+    if (pick.halves == 2) HIPC(launch_attn_merge(t, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    if (p->path) { p->path[0] = pick.kernel; p->path[1] = pick.halves; }
+    HIPC(q3_hipMemcpy(p->out, out, on * 4, hipMemcpyDeviceToHost));
+    HIPC(q3_hipMemcpy(p->kcache, kv, cn * 4, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(p->vcache, kv + cn, cn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
 #ifdef Q3_TRACE
 // development builds only (not declared in include/q3tts.h): arm the per-node stamp buffer BEFORE the first
 // q3_session_generate (the captured graph keeps the slice pointers), then read the stamps of the last replayed frame.

@@ -121,6 +121,10 @@ def test_no_cpu_fallback():
     else:
         raise AssertionError("q3_attn_step succeeded without a GPU")
     for call, name in ((lambda: q.conv_ex(0, np.zeros((16, 8), np.float32), np.zeros((32, 16, 1), np.float32)), "q3_conv_ex"),
+                       (lambda: q.gemm_ex(np.zeros((1, 64), np.float32), np.zeros((64, 64), np.uint16)), "q3_gemm_ex"),
+                       (lambda: q.attn_prefill_ex(np.zeros((2, 4 * 128), np.float32), 1, 0, np.ones(128, np.float32), np.ones(128, np.float32), 1e-6,
+                                                  np.ones((4, 64), np.float32), np.zeros((4, 64), np.float32), np.zeros((1, 1, 4, 128), np.float32),
+                                                  np.zeros((1, 1, 4, 128), np.float32), 2, 1), "q3_attn_prefill_ex"),
                        (lambda: q.norm_c(np.zeros((16, 8), np.float32), np.ones(16, np.float32)), "q3_norm_c"),
                        (lambda: q.dwconv7(np.zeros((16, 8), np.float32), np.zeros((16, 7), np.float32), np.zeros(16, np.float32)), "q3_dwconv7")):
         try:
@@ -139,6 +143,15 @@ def test_conv_path_is_host_only():
     assert q.conv_path(64, 16, 100, 9) == 0 and q.conv_path_name(0) == "none" and q.conv_path_name(-1) == "invalid"
     assert q.resunit_path(96, 4096, 3) == 15 and q.resunit_path(96, 4096, 3, planes=2) == 15 + 256 and q.resunit_path(96, 4095, 3) == 0
     assert ctypes.sizeof(_lib.CConvEx) == 16 * 4 + 16 * 8
+
+
+def test_prefill_paths_are_host_only():
+    """kernel selection of the prefill GEMM and attention answers without a GPU; None for what the launchers refuse"""
+    assert q.gemm_path(4105, 2048, 2048) == (3, 8, 1, 1) and q.gemm_path(509, 2048, 6144) == (3, 8, 8, 1)
+    assert q.gemm_path(130, 384, 128) == (2, 1, 1, 1) and q.gemm_path(130, 64, 40) == (1, 1, 1, 1) and q.gemm_path(130, 64, 36, planes=False) == (0, 1, 1, 1)
+    assert q.gemm_path(130, 96, 128) is None and q.gemm_path(0, 64, 128) is None
+    assert q.attn_prefill_path(16, 8, True, 2) == (3, 2) and q.attn_prefill_path(16, 8, False) == (2, 1) and q.attn_prefill_path(16, 2, False) is None
+    assert ctypes.sizeof(_lib.CGemmEx) == 14 * 4 + 8 * 8 and ctypes.sizeof(_lib.CAttnPrefillEx) == 12 * 4 + 9 * 8
 
 
 def test_speaker_language_tables():
@@ -210,6 +223,10 @@ def test_null_handles_return_status_not_crash():
         lambda: L.q3_attn_step(0, ctypes.byref(_lib.CAttnStep())),
         lambda: L.q3_conv_ex(0, None),
         lambda: L.q3_conv_ex(0, ctypes.byref(_lib.CConvEx())),
+        lambda: L.q3_gemm_ex(0, None),
+        lambda: L.q3_gemm_ex(0, ctypes.byref(_lib.CGemmEx())),
+        lambda: L.q3_attn_prefill_ex(0, None),
+        lambda: L.q3_attn_prefill_ex(0, ctypes.byref(_lib.CAttnPrefillEx())),
         lambda: L.q3_norm_c(0, 0, None, None, None, 16, 8, 1e-6, None, 0, 128),
         lambda: L.q3_dwconv7(0, None, None, None, 16, 8, None, 0, 128),
     ]
