@@ -589,6 +589,53 @@ typedef struct q3_attn_prefill_ex_args {
     float* kcache; float* vcache; float* out;
 } q3_attn_prefill_ex_args;
 q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_args* args);
+/* Test API: which kernel launch_attn_c (the codec transformer's whole-utterance attention) runs: kernel -1 = the engine's pick
+ * (k_attn_c_mfma unless the Q3_ATTN_C_VALU aid is set), 0 = k_attn_c (VALU), 1 = k_attn_c_mfma. Returns the kernel, or -1 for what
+ * the launcher refuses (hd != 64, any other kernel value). No GPU needed. */
+int q3_attn_c_path(int hd, int kernel);
+/* Test API: ONE launch of the codec transformer / speech encoder attention family over host arrays ([nh*hd][columns] f32, hd = 64,
+ * softmax(q.K^T * scale).V per head over keys j <= i).
+ * mode 0 = launch_attn_c (whole utterance): q, k, v, o [nh*hd][L]; kernel as in q3_attn_c_path.
+ * mode 1 = launch_attn_cs (codec stream): q, o [nh*hd][N]; row r = rows[3r ..] = (a0, e, qcol): its new frames [a0, e) are columns
+ *   qcol .. of q / o, its keys and values frames [0, e) of its cache caches[r] = [layers][K | V][nh*hd][cap]; the launch is on
+ *   `layer`. max_tiles as the codec stream computes it: the largest tile count ((e - 1) >> 5) - (a0 >> 5) + 1 of a row.
+ * mode 2 = launch_attn_cb (block-allocated stream): as mode 1, caches being a pool of n_blocks blocks [layers][K | V][nh*hd][bf]
+ *   (bf = cap, a multiple of 32); row r's frames [b * bf, (b + 1) * bf) live in block tabs[tab0[r] + b], b < tab_n[r].
+ * mode 3 = launch_mimi_attn (sliding window): as mode 0 over keys i - window < j <= i.
+ * o is uploaded whole before the launch and copied back whole after it; the caches are uploaded as given. A bad shape (hd != 64,
+ * bf % 32 != 0, e <= a0, e > cap, a row's columns outside [0, N), a block list shorter than ceil(e / bf) or naming a block outside
+ * the pool, kernel outside -1..1, window < 1) is Q3_INVALID_ARG and nothing is launched. */
+typedef struct q3_attn_c_ex_args {
+    int mode, nh, hd, L, kernel, window;
+    int N, n_rows, layers, layer, cap, n_blocks, n_tabs;
+    float scale;
+    const float* q; const float* k; const float* v;
+    const int* rows; const float* caches;
+    const int* tabs; const int* tab0; const int* tab_n;
+    float* o;
+} q3_attn_c_ex_args;
+q3_status q3_attn_c_ex(int device, const q3_attn_c_ex_args* args);
+/* Test API: launch_rope_c (pos NULL: column t at position t) or launch_rope_c_pos (column t at position pos[t]) on q and k
+ * [nh*hd][L] in place; cs / sn [n_pos][hd / 2]. hd even; every position must lie inside [0, n_pos). */
+q3_status q3_rope_c_ex(int device, float* q, float* k, const float* cs, const float* sn, const int* pos, int nh, int hd, int L, int n_pos);
+/* Test API: the codec stream's descriptor-driven movers, one launch each over host buffers that are uploaded whole and copied back
+ * whole (guards included). Offsets are in elements; a descriptor that leaves its buffer is Q3_INVALID_ARG before anything runs.
+ * q3_copy_cols_ex (launch_copy_cols): column j < n: dst[dst_off + d_off[j] + c * dp[j]] = src[src_off + s_off[j] + c * sp[j]] for
+ *   c < C, or 0 when s_off[j] < 0 (a null source).
+ * q3_copy_segs_ex (launch_copy_segs): segment s = segs[3s ..] = (src, dst, n): dst[dst + i] = src[src + i], i < n; max_n is the
+ *   largest n of the list.
+ * q3_gather_frames_ex (launch_gather_frames): dst[j][16] = src[s_off[j] .. + 16] for j < n (u32 codes). */
+q3_status q3_copy_cols_ex(int device, const float* src, size_t src_elems, float* dst, size_t dst_elems, int n, int C, const long long* s_off,
+                          const long long* d_off, const int* sp, const int* dp, size_t src_off, size_t dst_off);
+q3_status q3_copy_segs_ex(int device, const float* src, size_t src_elems, float* dst, size_t dst_elems, int n_segs, const unsigned long long* segs);
+q3_status q3_gather_frames_ex(int device, const uint32_t* src, size_t src_elems, const long long* s_off, int n, uint32_t* dst, size_t dst_elems);
+/* Test API: launch_rvq_embed: frames [n_frames][16] u32, first_cb [cb_size][cb_dim], rest_cbs [15][cb_size][cb_dim];
+ * first_out / rest_out: host buffers of out_elems floats with the [cb_dim][n_frames] result at out_front, uploaded and copied back
+ * whole. cb_dim 1..256. Code 0 is taken modulo cb_size; a rest code at or above cb_size reads the last entry. */
+q3_status q3_rvq_embed_ex(int device, const uint32_t* frames, int n_frames, const float* first_cb, const float* rest_cbs, int cb_dim, int cb_size,
+                          float* first_out, float* rest_out, int out_front, int out_elems);
+/* Test API: launch_silu_mul: y[i] = silu(g[i]) * u[i], i < n; y: host buffer of y_elems >= n floats, uploaded and copied back whole. */
+q3_status q3_silu_mul_ex(int device, const float* g, const float* u, float* y, long long n, long long y_elems);
 /* Test API: channel norm of x [C][L] over C (launch_layernorm_c / launch_rmsnorm_c): layernorm != 0 takes w and b [C], else w only.
  * y: host buffer of y_elems floats, result at y_front, uploaded and copied back whole. */
 q3_status q3_norm_c(int device, int layernorm, const float* x, const float* w, const float* b, int C, int L, float eps,

@@ -83,6 +83,12 @@ class CAttnPrefillEx(ctypes.Structure):  # q3_attn_prefill_ex_args
                [(n, ctypes.c_void_p) for n in ("qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache", "out")]
 
 
+class CAttnCEx(ctypes.Structure):        # q3_attn_c_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("mode", "nh", "hd", "L", "kernel", "window", "N", "n_rows", "layers", "layer", "cap", "n_blocks",
+                                              "n_tabs")] + [("scale", ctypes.c_float)] + \
+               [(n, ctypes.c_void_p) for n in ("q", "k", "v", "rows", "caches", "tabs", "tab0", "tab_n", "o")]
+
+
 class CTiming(ctypes.Structure):
     _fields_ = [("prefill_ms", ctypes.c_double), ("generation_ms", ctypes.c_double), ("decode_ms", ctypes.c_double),
                 ("generation_frames", ctypes.c_int32)]
@@ -220,6 +226,15 @@ SYMBOLS = {
     "q3_gemm_ex": (c_int, [c_int, P(CGemmEx)]),
     "q3_attn_prefill_path": (c_int, [c_int] * 4 + [P(ctypes.c_int32)]),
     "q3_attn_prefill_ex": (c_int, [c_int, P(CAttnPrefillEx)]),
+    "q3_attn_c_path": (c_int, [c_int, c_int]),
+    "q3_attn_c_ex": (c_int, [c_int, P(CAttnCEx)]),
+    "q3_rope_c_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
+    "q3_copy_cols_ex": (c_int, [c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                ctypes.c_size_t, ctypes.c_size_t]),
+    "q3_copy_segs_ex": (c_int, [c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_int, c_void_p]),
+    "q3_gather_frames_ex": (c_int, [c_int, c_void_p, ctypes.c_size_t, c_void_p, c_int, c_void_p, ctypes.c_size_t]),
+    "q3_rvq_embed_ex": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int]),
+    "q3_silu_mul_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong]),
     "q3_norm_c": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_int, c_int]),
     "q3_dwconv7": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     "q3_decode_codes": (c_int, [c_void_p, c_void_p, c_int, c_void_p, P(c_void_p)]),

@@ -1852,6 +1852,118 @@ def attn_prefill_ex(qkv: np.ndarray, n_seq: int, base_pos: int, q_norm_w: np.nda
     return out, kc, vc, tuple(path)
 
 
+def _vp(arr):
+    return None if arr is None else arr.ctypes.data_as(ctypes.c_void_p)
+
+
+def attn_c_path(kernel: int = -1, hd: int = 64):
+    """q3_attn_c_path: the kernel launch_attn_c runs (0 = k_attn_c, VALU; 1 = k_attn_c_mfma) for kernel -1 (the engine's pick) / 0 /
+    1, or None for what the launcher refuses. No GPU needed."""
+    k = lib.q3_attn_c_path(hd, kernel)
+    return None if k < 0 else k
+
+
+def attn_c_ex(mode: int, q_: np.ndarray, o: np.ndarray, *, nh: int, hd: int = 64, scale: Optional[float] = None, k: Optional[np.ndarray] = None,
+              v: Optional[np.ndarray] = None, kernel: int = -1, window: int = 0, rows=None, caches: Optional[np.ndarray] = None, layer: int = 0,
+              tabs=None, tab0=None, tab_n=None, device: int = 0) -> np.ndarray:
+    """q3_attn_c_ex: one launch of the codec transformer's attention family (parity tests). mode 0 = launch_attn_c over q / k / v
+    [nh*hd][L] (kernel -1 = the engine's pick, 0 VALU, 1 MFMA), 3 = launch_mimi_attn with `window`; 1 = launch_attn_cs: q / o
+    [nh*hd][N], rows [(a0, e, qcol)], caches [n_rows][layers][2][nh*hd][cap]; 2 = launch_attn_cb: caches is the pool
+    [n_blocks][layers][2][nh*hd][bf], row r's blocks are tabs[tab0[r] : tab0[r] + tab_n[r]]. o (f32, C order) is uploaded, written in
+    place and returned whole. Raises Q3Error (status 1) for a shape the entry refuses."""
+    qq = np.ascontiguousarray(q_, dtype=np.float32)
+    assert qq.ndim == 2 and o.dtype == np.float32 and o.flags.c_contiguous and o.shape == qq.shape and qq.shape[0] == nh * hd
+    a = _lib.CAttnCEx()
+    a.mode, a.nh, a.hd, a.kernel, a.window, a.layer = mode, nh, hd, kernel, window, layer
+    a.scale = float(hd) ** -0.5 if scale is None else scale
+    keep = [qq]
+    a.q, a.o = _vp(qq), _vp(o)
+    if mode in (0, 3):
+        a.L = qq.shape[1]
+        kk = np.ascontiguousarray(k, dtype=np.float32); vv = np.ascontiguousarray(v, dtype=np.float32)
+        assert kk.shape == qq.shape and vv.shape == qq.shape
+        keep += [kk, vv]; a.k, a.v = _vp(kk), _vp(vv)
+    elif mode in (1, 2):
+        rr = np.ascontiguousarray(rows, dtype=np.int32); assert rr.ndim == 2 and rr.shape[1] == 3
+        cc = np.ascontiguousarray(caches, dtype=np.float32); assert cc.ndim == 5 and cc.shape[2] == 2 and cc.shape[3] == nh * hd
+        a.N, a.n_rows, a.layers, a.cap = qq.shape[1], rr.shape[0], cc.shape[1], cc.shape[4]
+        keep += [rr, cc]; a.rows, a.caches = _vp(rr), _vp(cc)
+        if mode == 2:
+            tt = np.ascontiguousarray(tabs, dtype=np.int32); t0 = np.ascontiguousarray(tab0, dtype=np.int32); tn = np.ascontiguousarray(tab_n, dtype=np.int32)
+            assert tt.ndim == 1 and t0.shape == (rr.shape[0],) and tn.shape == t0.shape
+            a.n_blocks, a.n_tabs = cc.shape[0], tt.size
+            keep += [tt, t0, tn]; a.tabs, a.tab0, a.tab_n = _vp(tt), _vp(t0), _vp(tn)
+        else:
+            assert cc.shape[0] == rr.shape[0]
+    check(lib.q3_attn_c_ex(device, ctypes.byref(a)))
+    return o
+
+
+def rope_c_ex(q_: np.ndarray, k: np.ndarray, cs: np.ndarray, sn: np.ndarray, nh: int, pos=None, device: int = 0):
+    """q3_rope_c_ex: launch_rope_c (pos None) / launch_rope_c_pos on copies of q and k [nh*hd][L]; cs / sn [n_pos][hd/2]. Returns
+    the rotated (q, k)."""
+    qq = np.array(q_, dtype=np.float32, order="C"); kk = np.array(k, dtype=np.float32, order="C")
+    cs = np.ascontiguousarray(cs, dtype=np.float32); sn = np.ascontiguousarray(sn, dtype=np.float32)
+    assert qq.ndim == 2 and kk.shape == qq.shape and qq.shape[0] % nh == 0 and cs.ndim == 2 and sn.shape == cs.shape
+    hd = qq.shape[0] // nh; assert cs.shape[1] * 2 == hd
+    pp = None if pos is None else np.ascontiguousarray(pos, dtype=np.int32)
+    assert pp is None or pp.shape == (qq.shape[1],)
+    check(lib.q3_rope_c_ex(device, _vp(qq), _vp(kk), _vp(cs), _vp(sn), _vp(pp), nh, hd, qq.shape[1], cs.shape[0]))
+    return qq, kk
+
+
+def copy_cols_ex(src: np.ndarray, dst: np.ndarray, C: int, s_off, d_off, sp, dp, src_off: int = 0, dst_off: int = 0, device: int = 0) -> np.ndarray:
+    """q3_copy_cols_ex: one launch_copy_cols over flat f32 buffers; column j: dst[dst_off + d_off[j] + c * dp[j]] = src[src_off +
+    s_off[j] + c * sp[j]], c < C, or 0 for s_off[j] < 0. dst is written in place and returned."""
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    assert dst.dtype == np.float32 and dst.flags.c_contiguous and dst.ndim == 1 and src.ndim == 1
+    so = np.ascontiguousarray(s_off, dtype=np.int64); do = np.ascontiguousarray(d_off, dtype=np.int64)
+    spp = np.ascontiguousarray(sp, dtype=np.int32); dpp = np.ascontiguousarray(dp, dtype=np.int32)
+    n = so.size; assert do.shape == (n,) and spp.shape == (n,) and dpp.shape == (n,)
+    check(lib.q3_copy_cols_ex(device, _vp(src), src.size, _vp(dst), dst.size, n, C, _vp(so), _vp(do), _vp(spp), _vp(dpp), src_off, dst_off))
+    return dst
+
+
+def copy_segs_ex(src: np.ndarray, dst: np.ndarray, segs, device: int = 0) -> np.ndarray:
+    """q3_copy_segs_ex: one launch_copy_segs; segs [(src offset, dst offset, n)] in floats. dst is written in place and returned."""
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    assert dst.dtype == np.float32 and dst.flags.c_contiguous and dst.ndim == 1 and src.ndim == 1
+    sg = np.ascontiguousarray(segs, dtype=np.uint64); assert sg.ndim == 2 and sg.shape[1] == 3
+    check(lib.q3_copy_segs_ex(device, _vp(src), src.size, _vp(dst), dst.size, sg.shape[0], _vp(sg)))
+    return dst
+
+
+def gather_frames_ex(src: np.ndarray, s_off, dst: np.ndarray, device: int = 0) -> np.ndarray:
+    """q3_gather_frames_ex: one launch_gather_frames; frame j = src[s_off[j] : s_off[j] + 16] (u32) to dst[16 j ..]."""
+    src = np.ascontiguousarray(src, dtype=np.uint32)
+    assert dst.dtype == np.uint32 and dst.flags.c_contiguous and dst.ndim == 1 and src.ndim == 1
+    so = np.ascontiguousarray(s_off, dtype=np.int64); assert so.ndim == 1
+    check(lib.q3_gather_frames_ex(device, _vp(src), src.size, _vp(so), so.size, _vp(dst), dst.size))
+    return dst
+
+
+def rvq_embed_ex(frames: np.ndarray, first_cb: np.ndarray, rest_cbs: np.ndarray, first_out: np.ndarray, rest_out: np.ndarray, out_front: int = 0,
+                 device: int = 0):
+    """q3_rvq_embed_ex: one launch_rvq_embed; frames [n][16] u32, first_cb [cb_size][cb_dim], rest_cbs [15][cb_size][cb_dim]; the two
+    flat f32 outputs hold [cb_dim][n] at out_front, are written in place and returned."""
+    fr = np.ascontiguousarray(frames, dtype=np.uint32); assert fr.ndim == 2 and fr.shape[1] == 16
+    fc = np.ascontiguousarray(first_cb, dtype=np.float32); rc = np.ascontiguousarray(rest_cbs, dtype=np.float32)
+    assert fc.ndim == 2 and rc.shape == (15,) + fc.shape
+    for buf in (first_out, rest_out):
+        assert buf.dtype == np.float32 and buf.flags.c_contiguous and buf.ndim == 1 and buf.size == first_out.size
+    check(lib.q3_rvq_embed_ex(device, _vp(fr), fr.shape[0], _vp(fc), _vp(rc), fc.shape[1], fc.shape[0], _vp(first_out), _vp(rest_out), out_front,
+                              first_out.size))
+    return first_out, rest_out
+
+
+def silu_mul_ex(g: np.ndarray, u: np.ndarray, y: np.ndarray, device: int = 0) -> np.ndarray:
+    """q3_silu_mul_ex: one launch_silu_mul over g, u [n]; y (flat f32, >= n) is written in place and returned whole."""
+    g = np.ascontiguousarray(g, dtype=np.float32); u = np.ascontiguousarray(u, dtype=np.float32)
+    assert g.ndim == 1 and u.shape == g.shape and y.dtype == np.float32 and y.flags.c_contiguous and y.ndim == 1
+    check(lib.q3_silu_mul_ex(device, _vp(g), _vp(u), _vp(y), g.size, y.size))
+    return y
+
+
 def resunit_path(C: int, L: int, dil: int, packed: bool = True, ya_is_xa: bool = False, planes: int = 3) -> int:
     """q3_resunit_path: launch_resunit's acceptance rule as a ConvPath code (0 = refused). No GPU needed."""
     return lib.q3_resunit_path(C, L, dil, int(packed), int(ya_is_xa), planes)

@@ -405,8 +405,17 @@ hipError_t launch_layernorm_c(const float* x, const float* w, const float* b, fl
                               hipStream_t st);
 hipError_t launch_rmsnorm_c(const float* x, const float* w, float* y, int C, int L, float eps, hipStream_t st);
 hipError_t launch_rope_c(float* q, float* k, const float* cs, const float* sn, int nh, int hd, int L, hipStream_t st);
+// causal MHA over [nh*64][L]: attn_c_pick() is the engine's kernel (the only reader of Q3_ATTN_C_VALU), the first form launches it,
+// the second the kernel it is given (hipErrorInvalidValue for any other value: never another kernel in its place)
+enum { ATTN_C_VALU = 0, ATTN_C_MFMA = 1 };
+int attn_c_pick();
 hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* o, int nh, int hd, int L, float scale,
                          hipStream_t st);
+hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* o, int nh, int hd, int L, float scale, int kernel,
+                         hipStream_t st);
+// the speech encoder's causal sliding-window MHA over [nh*64][T]: keys j in (t - window, t] (q3_mimi.hip)
+hipError_t launch_mimi_attn(const float* q, const float* k, const float* v, float* o, int nh, int hd, int T, int window, float scale,
+                            hipStream_t st);
 // codec stream (q3_codec_stream.hip): the front over the new columns of several rows, K / V from per-row caches
 struct AttnCsRow { const float* kv; int a0, e, qcol; };      // row cache [layer][K | V][QD][cap]; new frames [a0, e) at columns qcol ..
 struct AttnCbRow { int tab0, a0, e, qcol; };                  // as AttnCsRow, the cache being the block list tabs[tab0 ..] (block-allocated stream)

@@ -1637,13 +1637,21 @@ hipError_t launch_attn_cb(const float* q, float* o, const AttnCbRow* rows, const
     hipLaunchKernelGGL(k_attn_cb, dim3(max_tiles, nh, n_rows), dim3(64 * ATC_NW), 0, st, q, o, rows, tabs, layer_off, N, bf, nh * hd, scale);
     return hipGetLastError();
 }
-hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* o, int nh, int hd, int L, float scale,
-                         hipStream_t st) {
-    if (hd != 64) return hipErrorInvalidValue;
+// which kernel launch_attn_c runs: the only reader of the Q3_ATTN_C_VALU switch
+int attn_c_pick() {
     static const bool valu = getenv("Q3_ATTN_C_VALU") != nullptr;       // A/B aid: the first-generation VALU kernel
-    if (valu) hipLaunchKernelGGL(k_attn_c, dim3(L, nh), dim3(64), 0, st, q, k, v, o, L, scale);
+    return valu ? ATTN_C_VALU : ATTN_C_MFMA;
+}
+hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* o, int nh, int hd, int L, float scale, int kernel,
+                         hipStream_t st) {
+    if (hd != 64 || nh <= 0 || L <= 0 || (kernel != ATTN_C_VALU && kernel != ATTN_C_MFMA)) return hipErrorInvalidValue;
+    if (kernel == ATTN_C_VALU) hipLaunchKernelGGL(k_attn_c, dim3(L, nh), dim3(64), 0, st, q, k, v, o, L, scale);
     else hipLaunchKernelGGL(k_attn_c_mfma, dim3((L + 31) / 32, nh), dim3(64 * ATC_NW), 0, st, q, k, v, o, L, scale);
     return hipGetLastError();
+}
+hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* o, int nh, int hd, int L, float scale,
+                         hipStream_t st) {
+    return launch_attn_c(q, k, v, o, nh, hd, L, scale, attn_c_pick(), st);
 }
 
 __global__ __launch_bounds__(256) void k_silu_mul(const float* g, const float* u, float* y, int64_t n) {

@@ -81,6 +81,12 @@ __global__ __launch_bounds__(64) void k_mimi_attn(const float* __restrict__ q, c
     }
     o[hb + (size_t)lane * T + t] = acc / l;
 }
+hipError_t launch_mimi_attn(const float* q, const float* k, const float* v, float* o, int nh, int hd, int T, int window, float scale,
+                            hipStream_t st) {
+    if (hd != 64 || nh <= 0 || T <= 0 || window <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mimi_attn, dim3(T, nh), dim3(64), 0, st, q, k, v, o, T, window, scale);
+    return hipGetLastError();
+}
 // codebook = embed_sum / max(cluster_usage, 1e-5)  (MimiEuclideanCodebook.embed)
 __global__ __launch_bounds__(256) void k_mimi_codebook(const float* __restrict__ esum, const float* __restrict__ usage, float* __restrict__ out, int dim) {
     const int e = blockIdx.x;
@@ -450,7 +456,7 @@ extern "C" q3_status q3_mimi_encode(q3_speech_encoder* e, const float* samples, 
         M_HIP(launch_layernorm_c(hs, Lr.ln1w, Lr.ln1b, nrm, H, T25, c.norm_eps, st));
         M_HIP(m_run_conv(e, Lr.q, nrm, q, T25)); M_HIP(m_run_conv(e, Lr.k, nrm, k, T25)); M_HIP(m_run_conv(e, Lr.v, nrm, v, T25));
         M_HIP(launch_rope_c(q, k, e->cs, e->sn, c.n_heads, 64, T25, st));
-        hipLaunchKernelGGL(k_mimi_attn, dim3(T25, c.n_heads), dim3(64), 0, st, q, k, v, att, T25, c.window, scale);
+        M_HIP(launch_mimi_attn(q, k, v, att, c.n_heads, 64, T25, c.window, scale, st));
         M_HIP(m_run_conv(e, Lr.o, att, hs, T25, 0, hs, Lr.sa));                          // hs += scale_attn * o_proj(att)
         M_HIP(launch_layernorm_c(hs, Lr.ln2w, Lr.ln2b, nrm, H, T25, c.norm_eps, st));
         M_HIP(m_run_conv(e, Lr.f1, nrm, ff, T25, /*GELU*/ 1));

@@ -620,6 +620,248 @@ extern "C" q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_arg
     return Q3_OK;
 }
 
+// ---- the codec transformer's attention family and its small neighbours, one launch at a time (tests/test_gpu_codec_attn_ops.py) ----
+extern "C" int q3_attn_c_path(int hd, int kernel) {
+    if (hd != 64 || kernel < -1 || kernel > ATTN_C_MFMA) return -1;
+    return kernel < 0 ? attn_c_pick() : kernel;
+}
+
+// One launch_attn_c / launch_attn_cs / launch_attn_cb / launch_mimi_attn call over host arrays. Everything a kernel would address
+// is checked against the buffers first: a bad shape is a status, never a launch. o is uploaded whole and copied back whole; the
+// caches go up as given (NaNs beyond a row's end included).
+extern "C" q3_status q3_attn_c_ex(int device, const q3_attn_c_ex_args* p) {
+    if (!p || !p->q || !p->o) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: null argument");
+    const int mode = p->mode, nh = p->nh, hd = p->hd;
+    if (mode < 0 || mode > 3) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: mode 0..3");
+    if (hd != 64 || nh < 1 || nh > 64) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: bad shape (hd == 64, 1 <= nh <= 64)");
+    const int QD = nh * hd;
+    const bool whole = mode == 0 || mode == 3, blk = mode == 2;
+    if (whole) {
+        if (!p->k || !p->v) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: null argument");
+        if (p->L < 1 || p->L > (1 << 16)) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: bad shape (L 1..65536)");
+        if (mode == 0 && (p->kernel < -1 || p->kernel > ATTN_C_MFMA)) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: kernel -1..1");
+        if (mode == 3 && p->window < 1) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: window >= 1");
+    } else {
+        if (!p->rows || !p->caches || (blk && (!p->tabs || !p->tab0 || !p->tab_n))) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: null argument");
+        if (p->N < 1 || p->N > (1 << 16) || p->n_rows < 1 || p->n_rows > 1024 || p->layers < 1 || p->layers > 64 || p->layer < 0 || p->layer >= p->layers ||
+            p->cap < 1 || p->cap > (1 << 16))
+            return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: bad shape (N, cap 1..65536, n_rows 1..1024, layer inside layers 1..64)");
+        if (blk && (p->cap % 32 != 0 || p->n_blocks < 1 || p->n_blocks > (1 << 16) || p->n_tabs < 1 || p->n_tabs > (1 << 20)))
+            return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: bad shape (bf a multiple of 32, n_blocks 1..65536, n_tabs 1..2^20)");
+        for (int r = 0; r < p->n_rows; ++r) {
+            const int a0 = p->rows[3 * r], e = p->rows[3 * r + 1], qcol = p->rows[3 * r + 2];
+            if (a0 < 0 || e <= a0) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: row %d: no new frames (a0 = %d, e = %d)", r, a0, e);
+            if (qcol < 0 || qcol > p->N || e - a0 > p->N - qcol) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: row %d: columns %d .. %d outside [0, %d)", r, qcol, qcol + e - a0, p->N);
+            if (!blk) {
+                if (e > p->cap) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: row %d ends at %d, beyond its cache (%d)", r, e, p->cap);
+                continue;
+            }
+            const int t0 = p->tab0[r], tn = p->tab_n[r], need = (e + p->cap - 1) / p->cap;
+            if (t0 < 0 || tn < 0 || t0 > p->n_tabs || tn > p->n_tabs - t0) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: row %d: block list %d + %d outside the table (%d)", r, t0, tn, p->n_tabs);
+            if (tn < need) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: row %d: %d blocks for %d frames of %d per block", r, tn, e, p->cap);
+            for (int b = 0; b < tn; ++b)
+                if (p->tabs[t0 + b] < 0 || p->tabs[t0 + b] >= p->n_blocks) return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: row %d: block %d outside the pool (%d)", r, p->tabs[t0 + b], p->n_blocks);
+        }
+    }
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const size_t cols = whole ? (size_t)p->L : (size_t)p->N, qn = (size_t)QD * cols;
+    float *q, *o, *k = nullptr, *v = nullptr;
+    HIPC(pool.alloc(&q, qn)); HIPC(pool.alloc(&o, qn));
+    HIPC(q3_hipMemcpy(q, p->q, qn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(o, p->o, qn * 4, hipMemcpyHostToDevice));
+    hipError_t e;
+    if (whole) {
+        HIPC(pool.alloc(&k, qn)); HIPC(pool.alloc(&v, qn));
+        HIPC(q3_hipMemcpy(k, p->k, qn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(v, p->v, qn * 4, hipMemcpyHostToDevice));
+        HIPC(q3_hipDeviceSynchronize());
+        if (mode == 0) e = launch_attn_c(q, k, v, o, nh, hd, p->L, p->scale, p->kernel < 0 ? attn_c_pick() : p->kernel, 0);
+        else e = launch_mimi_attn(q, k, v, o, nh, hd, p->L, p->window, p->scale, 0);
+    } else {
+        const size_t unit = (size_t)p->layers * 2 * QD * p->cap;              // one row's cache / one block
+        const size_t cn = unit * (blk ? (size_t)p->n_blocks : (size_t)p->n_rows), layer_off = (size_t)p->layer * 2 * QD * p->cap;
+        float* kv; HIPC(pool.alloc(&kv, cn)); HIPC(q3_hipMemcpy(kv, p->caches, cn * 4, hipMemcpyHostToDevice));
+        int max_tiles = 0;
+        for (int r = 0; r < p->n_rows; ++r) max_tiles = std::max(max_tiles, ((p->rows[3 * r + 1] - 1) >> 5) - (p->rows[3 * r] >> 5) + 1);
+        if (blk) {
+            std::vector<AttnCbRow> rows((size_t)p->n_rows); std::vector<const float*> tabs((size_t)p->n_tabs);
+            for (int r = 0; r < p->n_rows; ++r) rows[(size_t)r] = AttnCbRow{p->tab0[r], p->rows[3 * r], p->rows[3 * r + 1], p->rows[3 * r + 2]};
+            for (int i = 0; i < p->n_tabs; ++i) {          // entries no row owns may hold anything: they point at block 0
+                const int b = p->tabs[i];
+                tabs[(size_t)i] = kv + unit * (size_t)((b < 0 || b >= p->n_blocks) ? 0 : b);
+            }
+            AttnCbRow* rd; const float** td;
+            HIPC(pool.alloc(&rd, rows.size())); HIPC(pool.alloc(&td, tabs.size()));
+            HIPC(q3_hipMemcpy(rd, rows.data(), rows.size() * sizeof(AttnCbRow), hipMemcpyHostToDevice));
+            HIPC(q3_hipMemcpy(td, tabs.data(), tabs.size() * sizeof(const float*), hipMemcpyHostToDevice));
+            HIPC(q3_hipDeviceSynchronize());
+            e = launch_attn_cb(q, o, rd, td, p->n_rows, max_tiles, layer_off, nh, hd, p->N, p->cap, p->scale, 0);
+        } else {
+            std::vector<AttnCsRow> rows((size_t)p->n_rows);
+            for (int r = 0; r < p->n_rows; ++r) rows[(size_t)r] = AttnCsRow{kv + unit * (size_t)r, p->rows[3 * r], p->rows[3 * r + 1], p->rows[3 * r + 2]};
+            AttnCsRow* rd;
+            HIPC(pool.alloc(&rd, rows.size()));
+            HIPC(q3_hipMemcpy(rd, rows.data(), rows.size() * sizeof(AttnCsRow), hipMemcpyHostToDevice));
+            HIPC(q3_hipDeviceSynchronize());
+            e = launch_attn_cs(q, o, rd, p->n_rows, max_tiles, layer_off, nh, hd, p->N, p->cap, p->scale, 0);
+        }
+    }
+    if (e == hipErrorInvalidValue) {
+        (void)hipGetLastError();
+        return set_err(Q3_INVALID_ARG, "q3_attn_c_ex: the launcher refused mode=%d nh=%d hd=%d (%s)", mode, nh, hd, hipGetErrorString(e));
+    }
+    HIPC(e);
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->o, o, qn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_rope_c_ex(int device, float* q_host, float* k_host, const float* cs_host, const float* sn_host, const int* pos_host, int nh,
+                                  int hd, int L, int n_pos) {
+    if (!q_host || !k_host || !cs_host || !sn_host) return set_err(Q3_INVALID_ARG, "q3_rope_c_ex: null argument");
+    if (nh < 1 || nh > 64 || hd < 2 || hd > 256 || hd % 2 || L < 1 || L > (1 << 20) || n_pos < 1 || n_pos > (1 << 20))
+        return set_err(Q3_INVALID_ARG, "q3_rope_c_ex: bad shape (nh 1..64, hd even 2..256, L, n_pos 1..2^20)");
+    if (!pos_host && n_pos < L) return set_err(Q3_INVALID_ARG, "q3_rope_c_ex: %d positions for %d columns", n_pos, L);
+    if (pos_host) for (int t = 0; t < L; ++t) if (pos_host[t] < 0 || pos_host[t] >= n_pos) return set_err(Q3_INVALID_ARG, "q3_rope_c_ex: pos[%d] = %d outside [0, %d)", t, pos_host[t], n_pos);
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const size_t n = (size_t)nh * hd * L, rn = (size_t)n_pos * (hd / 2);
+    float *q, *k, *cs, *sn; int* pos = nullptr;
+    HIPC(pool.alloc(&q, n)); HIPC(pool.alloc(&k, n)); HIPC(pool.alloc(&cs, rn)); HIPC(pool.alloc(&sn, rn));
+    HIPC(q3_hipMemcpy(q, q_host, n * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(k, k_host, n * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(cs, cs_host, rn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(sn, sn_host, rn * 4, hipMemcpyHostToDevice));
+    if (pos_host) { HIPC(pool.alloc(&pos, (size_t)L)); HIPC(q3_hipMemcpy(pos, pos_host, (size_t)L * 4, hipMemcpyHostToDevice)); }
+    HIPC(q3_hipDeviceSynchronize());
+    if (pos) HIPC(launch_rope_c_pos(q, k, cs, sn, pos, nh, hd, L, 0));
+    else HIPC(launch_rope_c(q, k, cs, sn, nh, hd, L, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(q_host, q, n * 4, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(k_host, k, n * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+// does [off, off + (C - 1) * pitch] lie inside a buffer of `elems`?
+static bool col_inside(size_t base, long long off, int pitch, int C, size_t elems) {
+    if (off < 0 || pitch < 0) return false;
+    const size_t last = base + (size_t)off + (size_t)(C - 1) * (size_t)pitch;
+    return base <= elems && (size_t)off <= elems && last < elems;
+}
+
+extern "C" q3_status q3_copy_cols_ex(int device, const float* src_host, size_t src_elems, float* dst_host, size_t dst_elems, int n, int C,
+                                     const long long* s_off, const long long* d_off, const int* sp, const int* dp, size_t src_off, size_t dst_off) {
+    if (!src_host || !dst_host || !s_off || !d_off || !sp || !dp) return set_err(Q3_INVALID_ARG, "q3_copy_cols_ex: null argument");
+    const size_t lim = (size_t)1 << 28;
+    if (n < 1 || n > (1 << 20) || C < 1 || C > (1 << 16) || src_elems < 1 || src_elems > lim || dst_elems < 1 || dst_elems > lim)
+        return set_err(Q3_INVALID_ARG, "q3_copy_cols_ex: bad shape (n 1..2^20, C 1..65536, buffers 1..2^28 floats)");
+    for (int j = 0; j < n; ++j) {
+        if (s_off[j] >= 0 && !col_inside(src_off, s_off[j], sp[j], C, src_elems)) return set_err(Q3_INVALID_ARG, "q3_copy_cols_ex: column %d leaves the source", j);
+        if (!col_inside(dst_off, d_off[j], dp[j], C, dst_elems)) return set_err(Q3_INVALID_ARG, "q3_copy_cols_ex: column %d leaves the destination", j);
+    }
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    float *src, *dst; ColCopy* dd;
+    HIPC(pool.alloc(&src, src_elems)); HIPC(pool.alloc(&dst, dst_elems)); HIPC(pool.alloc(&dd, (size_t)n));
+    std::vector<ColCopy> d((size_t)n);
+    for (int j = 0; j < n; ++j) d[(size_t)j] = ColCopy{s_off[j] < 0 ? nullptr : src + s_off[j], dst + d_off[j], sp[j], dp[j]};
+    HIPC(q3_hipMemcpy(src, src_host, src_elems * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(dst, dst_host, dst_elems * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(dd, d.data(), d.size() * sizeof(ColCopy), hipMemcpyHostToDevice));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_copy_cols(dd, n, C, src_off, dst_off, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(dst_host, dst, dst_elems * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_copy_segs_ex(int device, const float* src_host, size_t src_elems, float* dst_host, size_t dst_elems, int n_segs,
+                                     const unsigned long long* segs_host) {
+    if (!src_host || !dst_host || !segs_host) return set_err(Q3_INVALID_ARG, "q3_copy_segs_ex: null argument");
+    const size_t lim = (size_t)1 << 28;
+    if (n_segs < 1 || n_segs > 65535 || src_elems < 1 || src_elems > lim || dst_elems < 1 || dst_elems > lim)
+        return set_err(Q3_INVALID_ARG, "q3_copy_segs_ex: bad shape (1..65535 segments, buffers 1..2^28 floats)");
+    std::vector<SegCopy> segs((size_t)n_segs); size_t max_n = 0;
+    for (int i = 0; i < n_segs; ++i) {
+        const unsigned long long s = segs_host[3 * i], d = segs_host[3 * i + 1], n = segs_host[3 * i + 2];
+        if (s > src_elems || n > src_elems - s || d > dst_elems || n > dst_elems - d)
+            return set_err(Q3_INVALID_ARG, "q3_copy_segs_ex: segment %d (%llu floats at %llu -> %llu) leaves its buffers", i, n, s, d);
+        segs[(size_t)i] = SegCopy{s, d, n}; max_n = std::max(max_n, (size_t)n);
+    }
+    if (max_n == 0) return set_err(Q3_INVALID_ARG, "q3_copy_segs_ex: every segment is empty");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    float *src, *dst; SegCopy* sd;
+    HIPC(pool.alloc(&src, src_elems)); HIPC(pool.alloc(&dst, dst_elems)); HIPC(pool.alloc(&sd, segs.size()));
+    HIPC(q3_hipMemcpy(src, src_host, src_elems * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(dst, dst_host, dst_elems * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(sd, segs.data(), segs.size() * sizeof(SegCopy), hipMemcpyHostToDevice));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_copy_segs(src, dst, sd, n_segs, max_n, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(dst_host, dst, dst_elems * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_gather_frames_ex(int device, const uint32_t* src_host, size_t src_elems, const long long* s_off, int n, uint32_t* dst_host,
+                                         size_t dst_elems) {
+    if (!src_host || !s_off || !dst_host) return set_err(Q3_INVALID_ARG, "q3_gather_frames_ex: null argument");
+    const size_t lim = (size_t)1 << 28;
+    if (n < 1 || n > (1 << 20) || src_elems < 16 || src_elems > lim || dst_elems < (size_t)n * 16 || dst_elems > lim)
+        return set_err(Q3_INVALID_ARG, "q3_gather_frames_ex: bad shape (n 1..2^20, source >= 16, destination >= 16 n, both <= 2^28)");
+    for (int j = 0; j < n; ++j)
+        if (s_off[j] < 0 || (size_t)s_off[j] > src_elems - 16) return set_err(Q3_INVALID_ARG, "q3_gather_frames_ex: frame %d leaves the source", j);
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    uint32_t *src, *dst; const uint32_t** pd;
+    HIPC(pool.alloc(&src, src_elems)); HIPC(pool.alloc(&dst, dst_elems)); HIPC(pool.alloc(&pd, (size_t)n));
+    std::vector<const uint32_t*> ptrs((size_t)n);
+    for (int j = 0; j < n; ++j) ptrs[(size_t)j] = src + s_off[j];
+    HIPC(q3_hipMemcpy(src, src_host, src_elems * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(dst, dst_host, dst_elems * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(pd, ptrs.data(), ptrs.size() * sizeof(const uint32_t*), hipMemcpyHostToDevice));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_gather_frames(pd, dst, n, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(dst_host, dst, dst_elems * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_rvq_embed_ex(int device, const uint32_t* frames_host, int n_frames, const float* first_cb_host, const float* rest_cbs_host,
+                                     int cb_dim, int cb_size, float* first_out_host, float* rest_out_host, int out_front, int out_elems) {
+    if (!frames_host || !first_cb_host || !rest_cbs_host || !first_out_host || !rest_out_host) return set_err(Q3_INVALID_ARG, "q3_rvq_embed_ex: null argument");
+    if (n_frames < 1 || n_frames > (1 << 16) || cb_dim < 1 || cb_dim > 256 || cb_size < 1 || cb_size > (1 << 16))
+        return set_err(Q3_INVALID_ARG, "q3_rvq_embed_ex: bad shape (n_frames 1..65536, cb_dim 1..256, cb_size 1..65536)");
+    if (out_front < 0 || out_elems < 0 || (size_t)out_elems < (size_t)out_front + (size_t)cb_dim * n_frames)
+        return set_err(Q3_INVALID_ARG, "q3_rvq_embed_ex: the outputs must hold out_front + cb_dim * n_frames floats");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const size_t cbn = (size_t)cb_size * cb_dim;
+    uint32_t* frames; float *fcb, *rcb, *fo, *ro; const float** tabs;
+    HIPC(pool.alloc(&frames, (size_t)n_frames * 16)); HIPC(pool.alloc(&fcb, cbn)); HIPC(pool.alloc(&rcb, cbn * 15));
+    HIPC(pool.alloc(&fo, (size_t)out_elems)); HIPC(pool.alloc(&ro, (size_t)out_elems)); HIPC(pool.alloc(&tabs, 15));
+    const float* th[15];
+    for (int i = 0; i < 15; ++i) th[i] = rcb + (size_t)i * cbn;
+    HIPC(q3_hipMemcpy(frames, frames_host, (size_t)n_frames * 64, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(fcb, first_cb_host, cbn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(rcb, rest_cbs_host, cbn * 15 * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(fo, first_out_host, (size_t)out_elems * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(ro, rest_out_host, (size_t)out_elems * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(tabs, th, sizeof th, hipMemcpyHostToDevice));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_rvq_embed(frames, n_frames, fcb, tabs, fo + out_front, ro + out_front, cb_dim, cb_size, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(first_out_host, fo, (size_t)out_elems * 4, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(rest_out_host, ro, (size_t)out_elems * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_silu_mul_ex(int device, const float* g_host, const float* u_host, float* y_host, long long n, long long y_elems) {
+    if (!g_host || !u_host || !y_host) return set_err(Q3_INVALID_ARG, "q3_silu_mul_ex: null argument");
+    if (n < 1 || n > (1LL << 28) || y_elems < n || y_elems > (1LL << 28)) return set_err(Q3_INVALID_ARG, "q3_silu_mul_ex: bad shape (1 <= n <= y_elems <= 2^28)");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    float *g, *u, *y;
+    HIPC(pool.alloc(&g, (size_t)n)); HIPC(pool.alloc(&u, (size_t)n)); HIPC(pool.alloc(&y, (size_t)y_elems));
+    HIPC(q3_hipMemcpy(g, g_host, (size_t)n * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(u, u_host, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(y, y_host, (size_t)y_elems * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_silu_mul(g, u, y, (int64_t)n, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(y_host, y, (size_t)y_elems * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
 #ifdef Q3_TRACE
 // development builds only (not declared in include/q3tts.h): arm the per-node stamp buffer BEFORE the first
 // q3_session_generate (the captured graph keeps the slice pointers), then read the stamps of the last replayed frame.

@@ -125,6 +125,20 @@ def test_no_cpu_fallback():
                        (lambda: q.attn_prefill_ex(np.zeros((2, 4 * 128), np.float32), 1, 0, np.ones(128, np.float32), np.ones(128, np.float32), 1e-6,
                                                   np.ones((4, 64), np.float32), np.zeros((4, 64), np.float32), np.zeros((1, 1, 4, 128), np.float32),
                                                   np.zeros((1, 1, 4, 128), np.float32), 2, 1), "q3_attn_prefill_ex"),
+                       (lambda: q.attn_c_ex(0, np.zeros((128, 8), np.float32), np.zeros((128, 8), np.float32), nh=2, k=np.zeros((128, 8), np.float32),
+                                            v=np.zeros((128, 8), np.float32)), "q3_attn_c_ex"),
+                       (lambda: q.attn_c_ex(1, np.zeros((128, 8), np.float32), np.zeros((128, 8), np.float32), nh=2, rows=[(0, 4, 0)],
+                                            caches=np.zeros((1, 1, 2, 128, 32), np.float32)), "q3_attn_c_ex (stream)"),
+                       (lambda: q.attn_c_ex(2, np.zeros((128, 8), np.float32), np.zeros((128, 8), np.float32), nh=2, rows=[(0, 4, 0)],
+                                            caches=np.zeros((1, 1, 2, 128, 32), np.float32), tabs=[0], tab0=[0], tab_n=[1]), "q3_attn_c_ex (blocked)"),
+                       (lambda: q.rope_c_ex(np.zeros((128, 4), np.float32), np.zeros((128, 4), np.float32), np.ones((4, 32), np.float32),
+                                            np.zeros((4, 32), np.float32), 2), "q3_rope_c_ex"),
+                       (lambda: q.copy_cols_ex(np.zeros(16, np.float32), np.zeros(16, np.float32), 4, [0], [0], [4], [4]), "q3_copy_cols_ex"),
+                       (lambda: q.copy_segs_ex(np.zeros(16, np.float32), np.zeros(16, np.float32), [(0, 0, 8)]), "q3_copy_segs_ex"),
+                       (lambda: q.gather_frames_ex(np.zeros(32, np.uint32), [3], np.zeros(16, np.uint32)), "q3_gather_frames_ex"),
+                       (lambda: q.rvq_embed_ex(np.zeros((2, 16), np.uint32), np.zeros((4, 8), np.float32), np.zeros((15, 4, 8), np.float32),
+                                               np.zeros(16, np.float32), np.zeros(16, np.float32)), "q3_rvq_embed_ex"),
+                       (lambda: q.silu_mul_ex(np.zeros(8, np.float32), np.zeros(8, np.float32), np.zeros(8, np.float32)), "q3_silu_mul_ex"),
                        (lambda: q.norm_c(np.zeros((16, 8), np.float32), np.ones(16, np.float32)), "q3_norm_c"),
                        (lambda: q.dwconv7(np.zeros((16, 8), np.float32), np.zeros((16, 7), np.float32), np.zeros(16, np.float32)), "q3_dwconv7")):
         try:
@@ -152,6 +166,26 @@ def test_prefill_paths_are_host_only():
     assert q.gemm_path(130, 96, 128) is None and q.gemm_path(0, 64, 128) is None
     assert q.attn_prefill_path(16, 8, True, 2) == (3, 2) and q.attn_prefill_path(16, 8, False) == (2, 1) and q.attn_prefill_path(16, 2, False) is None
     assert ctypes.sizeof(_lib.CGemmEx) == 14 * 4 + 8 * 8 and ctypes.sizeof(_lib.CAttnPrefillEx) == 12 * 4 + 9 * 8
+
+
+def test_codec_attn_entries_are_host_checked():
+    """kernel selection of launch_attn_c answers without a GPU, and q3_attn_c_ex refuses a bad shape with Q3_INVALID_ARG before it
+    touches a device (the full list: tests/test_codec_attn_reference.py)"""
+    assert q.attn_c_path() == 1 and q.attn_c_path(0) == 0 and q.attn_c_path(2) is None and q.attn_c_path(1, hd=128) is None
+    assert ctypes.sizeof(_lib.CAttnCEx) == 14 * 4 + 9 * 8
+    z = lambda *s: np.zeros(s, np.float32)
+    bad = [lambda: q.attn_c_ex(0, z(64, 8), z(64, 8), nh=2, hd=32, k=z(64, 8), v=z(64, 8)),                                    # hd != 64
+           lambda: q.attn_c_ex(1, z(128, 8), z(128, 8), nh=2, rows=[(5, 5, 0)], caches=z(1, 1, 2, 128, 64)),                   # e <= a0
+           lambda: q.attn_c_ex(1, z(128, 8), z(128, 8), nh=2, rows=[(60, 65, 0)], caches=z(1, 1, 2, 128, 64)),                 # e > cap
+           lambda: q.attn_c_ex(2, z(128, 8), z(128, 8), nh=2, rows=[(0, 4, 0)], caches=z(2, 1, 2, 128, 48), tabs=[0], tab0=[0], tab_n=[1]),      # bf % 32
+           lambda: q.attn_c_ex(2, z(128, 8), z(128, 8), nh=2, rows=[(30, 34, 0)], caches=z(2, 1, 2, 128, 32), tabs=[0], tab0=[0], tab_n=[1])]    # short block list
+    for k, call in enumerate(bad):
+        try:
+            call()
+        except _lib.Q3Error as e:
+            assert e.status == 1, k
+        else:
+            raise AssertionError(f"bad shape {k} accepted")
 
 
 def test_speaker_language_tables():
@@ -227,6 +261,14 @@ def test_null_handles_return_status_not_crash():
         lambda: L.q3_gemm_ex(0, ctypes.byref(_lib.CGemmEx())),
         lambda: L.q3_attn_prefill_ex(0, None),
         lambda: L.q3_attn_prefill_ex(0, ctypes.byref(_lib.CAttnPrefillEx())),
+        lambda: L.q3_attn_c_ex(0, None),
+        lambda: L.q3_attn_c_ex(0, ctypes.byref(_lib.CAttnCEx())),
+        lambda: L.q3_rope_c_ex(0, None, None, None, None, None, 2, 64, 8, 8),
+        lambda: L.q3_copy_cols_ex(0, None, 16, None, 16, 1, 1, None, None, None, None, 0, 0),
+        lambda: L.q3_copy_segs_ex(0, None, 16, None, 16, 1, None),
+        lambda: L.q3_gather_frames_ex(0, None, 16, None, 1, None, 16),
+        lambda: L.q3_rvq_embed_ex(0, None, 1, None, None, 8, 16, None, None, 0, 8),
+        lambda: L.q3_silu_mul_ex(0, None, None, None, 8, 8),
         lambda: L.q3_norm_c(0, 0, None, None, None, 16, 8, 1e-6, None, 0, 128),
         lambda: L.q3_dwconv7(0, None, None, None, 16, 8, None, 0, 128),
     ]
