@@ -879,6 +879,63 @@ q3_status q3_session_set_pitch(q3_session* s, int b, int cents);
 /* Batcher: a streamed ticket's pitch; the window and the read of q3_batcher_ticket_tempo. A slot's next owner gets its own setting,
  * off included; a parked streamed ticket keeps its stage row. */
 q3_status q3_batcher_ticket_pitch(q3_batcher* b, int64_t ticket, int cents);
+/* ---------------- output stage: a silence trim and pause cap per row (at the very front of the row, before the stretcher) ----------------
+ * threshold_mB: 0, the default, is off: such a row takes the paths above and returns their bits and their launches, and a push
+ * without such a row has no launch, copy or wait it did not have. Otherwise -9000..-2000, millibel re full scale of a hop's mean
+ * square; edge_ms 0..1000 and pause_ms 20..2000, both multiples of 10; anything else is Q3_INVALID_ARG before the device is touched.
+ * E = edge_ms / 10 and P = pause_ms / 10 are hops, P1 = P - P / 2, P2 = P / 2 (integer division).
+ * A hop is H = 240 samples (10 ms) of the row's 24 kHz input x; hop h covers x[h H .. h H + H); with N samples in all there are
+ * NH = ceil(N / H) hops, samples past N being zeros for the energy and never emitted. e_h is the sum of squares of the hop in 64
+ * interleaved f32 partial sums as in the loudness step: sample j goes to partial j mod 64 in ascending j, product and sum each
+ * rounded once (no fma), the partials folded s_q += s_(q + d), d = 32 .. 1. A non-finite sample enters the energy as 0 and, where it
+ * is kept, leaves unchanged. loud_h = e_h > theta, theta = (float)(240 10^(threshold_mB / 1000)) (f64, rounded once; a NaN compares
+ * false). active_h = some loud_g with |g - h| <= G, 0 <= g < NH, G = 2: a guard of 20 ms around onsets and decays. A run is a maximal
+ * stretch [s, s + S) of non-active hops. Per run:
+ *   leading (s = 0, also when it is the whole stream): hops [0, S - min(S, E)) are dropped;
+ *   trailing (s > 0, s + S = NH): hops [s + min(S, E), NH) are dropped;
+ *   inner, S <= P: kept whole;
+ *   inner, S > P: hops [s + P1, s + S - P2) are dropped, and the seam hop a = s + P1 - 1 leaves crossfaded with hop b = s + S - P2 - 1:
+ *     y = add_rn(mul_rn(x[a H + j], w1[j]), mul_rn(x[b H + j], w0[j])), w0[j] = (float)((j + 0.5) / 240), w1[j] = (float)(1 - (j + 0.5) / 240)
+ *     (f64, rounded once).
+ * Every other kept sample leaves bit for bit; y is the kept hops in order, a function of x alone: it does not depend on how the
+ * stream was cut into pushes.
+ * Streaming rule: a hop is classified once hops <= h + G are complete, or at the flush. A kept hop leaves in the first push after
+ * which its fate no longer depends on samples that have not arrived: an active hop when it is classified; hop i of a later run
+ * (s > 0) at once for i < min(E, P1 - 1); a leading run's last min(S, E) hops and everything else a run keeps when the run ends (at
+ * the flush for a trailing one). What a row retains is bounded whatever a run's length: of a later run the hops
+ * [min(E, P1 - 1), max(E, P1)) and the last P2 + 1, of a leading run the last E, and G complete hops and the partial one:
+ * hold(edge_ms, pause_ms) = (max(E, P1) + P2 + G + 2) 240 samples, at most 48 960. The steps behind take y as the row's 24 kHz input
+ * stream; their definitions, counts and bounds hold with the kept samples in the place of n_in.
+ * The count a push returns depends on the data. A push in which some row has the step on runs in two passes: the samples go up,
+ * k_trim runs for those rows, their kept counts come back (one small copy and one wait), then the plan and the launches of the
+ * steps behind. max_push_samples applies to what enters the step. For such a row cap_samples must cover
+ * q3_pcm_stage_bound_silence(...), checked before the device is touched; n_samples reports what came. The state (two copies under
+ * the commit rule of the tails: a push that is refused or fails leaves the row where it was) is allocated by a row's first setting
+ * other than off. No reference counterpart. */
+q3_status q3_pcm_stage_set_silence(q3_pcm_stage* ps, int row, int threshold_mB, int edge_ms, int pause_ms);  /* also restarts the row; kept by _set / _reset / every other _set_* */
+/* the 24 kHz sample counts after the row's last successful push: what entered the step, what left it, and what was cut at the front,
+ * in pauses and at the end (a run's cut counts when the run ends; lead_cut is the input index of the first sample that was kept);
+ * after the flush n_in - lead_cut - pause_cut - trail_cut == n_out. Any pointer may be NULL; Q3_INVALID_ARG for a row whose step
+ * is off */
+q3_status q3_pcm_stage_silence(q3_pcm_stage* ps, int row, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut);
+/* host only: hold(edge_ms, pause_ms) in samples */
+q3_status q3_pcm_stage_silence_hold(int edge_ms, int pause_ms, size_t* samples);
+/* host only: cap for a push of n_in new samples to a row with the step on: q3_pcm_stage_bound_pitch(..., n_in + hold) */
+q3_status q3_pcm_stage_bound_silence(uint32_t sample_rate, int tempo_permille, int cents, int with_level, int edge_ms, int pause_ms, size_t n_in,
+                                     size_t* n_out_max);
+/* host only: the whole definition for one clip on the CPU, the same f32 operations in the same order — for the whole-utterance
+ * paths, whose callers convert on the host. y receives *n_y <= n samples (y NULL and cap 0: the counts alone); counts (may be NULL)
+ * receives n_in, n_out, lead_cut, pause_cut, trail_cut. threshold_mB 0 (off) is Q3_INVALID_ARG here. */
+q3_status q3_silence_trim(const float* x, size_t n, int threshold_mB, int edge_ms, int pause_ms, float* y, size_t cap, size_t* n_y, int64_t* counts);
+/* Sessions: the silence step of row b's stage row (b = -1: every row) in q3_session_next_chunks_out; q3_session_set_tempo's window
+ * and persistence. q3_session_silence: the row's counts (b = -1 is not a row; zeros before the first streamed chunk). */
+q3_status q3_session_set_silence(q3_session* s, int b, int threshold_mB, int edge_ms, int pause_ms);
+q3_status q3_session_silence(q3_session* s, int b, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut);
+/* Batcher: a streamed ticket's silence step; the window and the read of q3_batcher_ticket_output (q3_batcher_read_out, whose counts
+ * are then what the step handed on). A slot's next owner gets its own setting, off included; a parked streamed ticket keeps its
+ * stage row and the step's state. _read: the counts after the parts that have landed, final once the ticket is done. */
+q3_status q3_batcher_ticket_silence(q3_batcher* b, int64_t ticket, int threshold_mB, int edge_ms, int pause_ms);
+q3_status q3_batcher_ticket_silence_read(q3_batcher* b, int64_t ticket, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut);
 /* codes_to_tensor (lib.rs:1417-1431): [n][16] u32 → [16][n] i64 (host helper) */
 void      q3_codes_to_tensor(const uint32_t* frames, int n_frames, int64_t* out);
 

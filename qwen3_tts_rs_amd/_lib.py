@@ -160,6 +160,15 @@ SYMBOLS = {
     "q3_pcm_stage_bound_pitch": (c_int, [ctypes.c_uint32, c_int, c_int, c_int, ctypes.c_size_t, P(ctypes.c_size_t)]),
     "q3_session_set_pitch": (c_int, [c_void_p, c_int, c_int]),
     "q3_batcher_ticket_pitch": (c_int, [c_void_p, ctypes.c_int64, c_int]),
+    "q3_pcm_stage_set_silence": (c_int, [c_void_p, c_int, c_int, c_int, c_int]),
+    "q3_pcm_stage_silence": (c_int, [c_void_p, c_int] + [P(ctypes.c_int64)] * 5),
+    "q3_pcm_stage_silence_hold": (c_int, [c_int, c_int, P(ctypes.c_size_t)]),
+    "q3_pcm_stage_bound_silence": (c_int, [ctypes.c_uint32, c_int, c_int, c_int, c_int, c_int, ctypes.c_size_t, P(ctypes.c_size_t)]),
+    "q3_silence_trim": (c_int, [c_void_p, ctypes.c_size_t, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, P(ctypes.c_size_t), P(ctypes.c_int64)]),
+    "q3_session_set_silence": (c_int, [c_void_p, c_int, c_int, c_int, c_int]),
+    "q3_session_silence": (c_int, [c_void_p, c_int] + [P(ctypes.c_int64)] * 5),
+    "q3_batcher_ticket_silence": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_int]),
+    "q3_batcher_ticket_silence_read": (c_int, [c_void_p, ctypes.c_int64] + [P(ctypes.c_int64)] * 5),
     "q3_pcm_stage_set_level": (c_int, [c_void_p, c_int, c_int, c_int]),
     "q3_pcm_stage_level_coeffs": (c_int, [c_int, c_int, P(ctypes.c_float), P(ctypes.c_float)]),
     "q3_pcm_stage_level_count": (c_int, [ctypes.c_size_t, c_int, P(ctypes.c_size_t)]),

@@ -307,6 +307,23 @@ class Session:
         check(lib.q3_session_loudness(self._h, int(b), ctypes.byref(m), ctypes.byref(g), ctypes.byref(nb), ctypes.byref(cg)))
         return Loudness.of(m.value, g.value, nb.value, cg.value)
 
+    def set_silence(self, threshold_db, edge_ms: int = 50, pause_ms: int = 400, b: int = -1):
+        """The silence step of row b (-1: every row) in `next_chunks_out` (q3_session_set_silence): hops under threshold_db (dB re
+        full scale, -90..-20; None or 0 = off) are cut at the row's two ends down to edge_ms and inside it down to pause_ms. The
+        window and the persistence of `set_tempo`."""
+        thr = silence_mb(threshold_db)
+        check(lib.q3_session_set_silence(self._h, int(b), thr, int(edge_ms), int(pause_ms)))
+        v = getattr(self, "_silence", None) or [None] * self.B
+        for r in (range(self.B) if int(b) < 0 else [int(b)]):
+            v[r] = (int(edge_ms), int(pause_ms)) if thr else None
+        self._silence = v
+
+    def silence(self, b: int = 0) -> "Silence":
+        """Row b's counts after its last streamed chunk (q3_session_silence)."""
+        v = [ctypes.c_int64() for _ in range(5)]
+        check(lib.q3_session_silence(self._h, int(b), *[ctypes.byref(x) for x in v]))
+        return Silence(*[int(x.value) for x in v])
+
     def set_tempo(self, tempo_permille: int, b: int = -1):
         """The speaking rate of row b (-1: every row) in `next_chunks_out` (q3_session_set_tempo): 500..2000 permille, 1250 = 1.25 x
         as fast, 1000 = off. Legal while the row has streamed nothing since its start or its `replace`; the setting stays with the
@@ -338,8 +355,9 @@ class Session:
         level = getattr(self, "_level", None) or [False] * B
         pitch = getattr(self, "_pitch", None) or [0] * B
         n_in = max(self.options.chunk_frames, 1) * spf
-        cap = {k: pcm_stage_bound(rate, n_in, k[0], k[1], k[2]) for k in set(zip(tempo, level, pitch))}
-        bufs = [np.zeros(cap[(tempo[b], level[b], pitch[b])], dtype=PCM_DTYPE[int(s16)]) for b in range(B)]
+        sil = getattr(self, "_silence", None) or [None] * B
+        cap = {k: pcm_stage_bound(rate, n_in, k[0], k[1], k[2], k[3]) for k in set(zip(tempo, level, pitch, sil))}
+        bufs = [np.zeros(cap[(tempo[b], level[b], pitch[b], sil[b])], dtype=PCM_DTYPE[int(s16)]) for b in range(B)]
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data_as(ctypes.c_void_p) for b in bufs])
         caps = (ctypes.c_size_t * B)(*[b.size for b in bufs])
         n = (ctypes.c_size_t * B)(); d = (ctypes.c_int * B)()
@@ -559,13 +577,14 @@ class Batcher:
 
     def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False, tempo_permille: int = 1000,
                         fmt: Optional[str] = None, gain_mb: int = 0, ceiling_mb: int = 0, target_lufs: Optional[float] = None,
-                        prior_gain_db: float = 0.0, pitch_cents: int = 0) -> int:
+                        prior_gain_db: float = 0.0, pitch_cents: int = 0, silence=None) -> int:
         """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16 / fmt: the
         ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked, uint8 for
         fmt "ulaw" / "alaw". tempo_permille: its speaking rate (q3_batcher_ticket_tempo; 1250 = 1.25 x as fast, 1000 = off).
         gain_mb / ceiling_mb: its level (q3_batcher_ticket_level; millibel, (0, 0) = off). target_lufs: the loudness it is steered
         to, from the gain prior_gain_db (q3_batcher_ticket_loudness; `loudness(ticket)` reads the result). pitch_cents: its pitch
-        (q3_batcher_ticket_pitch; -1200..1200, 0 = off)."""
+        (q3_batcher_ticket_pitch; -1200..1200, 0 = off). silence = (threshold_db, edge_ms, pause_ms): its silence step
+        (q3_batcher_ticket_silence; `silence(ticket)` reads the counts)."""
         code = pcm_format(pcm16, fmt)
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
@@ -578,6 +597,12 @@ class Batcher:
                 self.ticket_loudness(int(t.value), LOUD_NORMALIZE, int(round(float(target_lufs) * 100.0)), int(round(float(prior_gain_db) * 100.0)))
             except _lib.Q3Error:
                 self.cancel(int(t.value)); self.fetch(int(t.value))      # the ticket was never run: it leaves with the refusal
+                raise
+        if silence is not None:
+            try:
+                self.ticket_silence(int(t.value), *silence)
+            except _lib.Q3Error:
+                self.cancel(int(t.value)); self.fetch(int(t.value))
                 raise
         return int(t.value)
 
@@ -626,6 +651,20 @@ class Batcher:
         m = ctypes.c_float(); g = ctypes.c_float(); nb = ctypes.c_int(); cg = ctypes.c_int()
         check(lib.q3_batcher_ticket_loudness_read(self._h, int(ticket), ctypes.byref(m), ctypes.byref(g), ctypes.byref(nb), ctypes.byref(cg)))
         return Loudness.of(m.value, g.value, nb.value, cg.value)
+
+    def ticket_silence(self, ticket: int, threshold_db, edge_ms: int = 50, pause_ms: int = 400):
+        """A streamed ticket's silence step (q3_batcher_ticket_silence): between its submission and the next `step`."""
+        thr = silence_mb(threshold_db)
+        check(lib.q3_batcher_ticket_silence(self._h, int(ticket), thr, int(edge_ms), int(pause_ms)))
+        if thr:
+            self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
+
+    def silence(self, ticket: int) -> "Silence":
+        """The ticket's counts after the parts that have landed (q3_batcher_ticket_silence_read): final once `read` has reported it
+        done, valid until `fetch`."""
+        v = [ctypes.c_int64() for _ in range(5)]
+        check(lib.q3_batcher_ticket_silence_read(self._h, int(ticket), *[ctypes.byref(x) for x in v]))
+        return Silence(*[int(x.value) for x in v])
 
     def ticket_tempo(self, ticket: int, tempo_permille: int):
         """A streamed ticket's speaking rate (q3_batcher_ticket_tempo): between its submission and the next `step`."""
@@ -1330,12 +1369,15 @@ def pcm_stage_taps(rate: int) -> Tuple[np.ndarray, int, int]:
     return t, L.value, M.value
 
 
-def pcm_stage_bound(rate: int, n_in: int, tempo_permille: int = 1000, level: bool = False, pitch_cents: int = 0) -> int:
+def pcm_stage_bound(rate: int, n_in: int, tempo_permille: int = 1000, level: bool = False, pitch_cents: int = 0, silence=None) -> int:
     """The most samples one push of n_in 24 kHz samples returns at `rate` (q3_pcm_stage_bound), for a row at tempo_permille
     (q3_pcm_stage_bound_tempo), with `level` one that has a level (q3_pcm_stage_bound_level), with pitch_cents one that has a pitch
-    (q3_pcm_stage_bound_pitch)."""
+    (q3_pcm_stage_bound_pitch), with silence = (edge_ms, pause_ms) one that has a silence step (q3_pcm_stage_bound_silence)."""
     n = ctypes.c_size_t()
-    if int(pitch_cents):
+    if silence is not None:
+        check(lib.q3_pcm_stage_bound_silence(int(rate), int(tempo_permille), int(pitch_cents), 1 if level else 0, int(silence[0]), int(silence[1]),
+                                             int(n_in), ctypes.byref(n)))
+    elif int(pitch_cents):
         check(lib.q3_pcm_stage_bound_pitch(int(rate), int(tempo_permille), int(pitch_cents), 1 if level else 0, int(n_in), ctypes.byref(n)))
     elif level:
         check(lib.q3_pcm_stage_bound_level(int(rate), int(tempo_permille), int(n_in), ctypes.byref(n)))
@@ -1426,6 +1468,44 @@ def pcm_stage_loudness_consts(target_mb: int = -1900, prior_mb: int = 0) -> Tupl
     return tuple(np.float32(x.value) for x in v)
 
 
+class Silence(NamedTuple):
+    """A row's silence step in 24 kHz samples: what entered it, what left it, and what was cut at the front (the input index of the
+    first sample kept), in pauses and at the end. After the flush n_in - lead_cut - pause_cut - trail_cut == n_out."""
+    n_in: int
+    n_out: int
+    lead_cut: int
+    pause_cut: int
+    trail_cut: int
+
+
+def silence_mb(threshold_db) -> int:
+    """A threshold in dB re full scale as the stage's millibel (None or 0: off)."""
+    return 0 if threshold_db is None else int(round(float(threshold_db) * 100.0))
+
+
+def pcm_stage_silence_hold(edge_ms: int, pause_ms: int) -> int:
+    """The most samples a row's silence step retains (q3_pcm_stage_silence_hold)."""
+    n = ctypes.c_size_t()
+    check(lib.q3_pcm_stage_silence_hold(int(edge_ms), int(pause_ms), ctypes.byref(n)))
+    return int(n.value)
+
+
+def trim_silence(samples, threshold_db: float, edge_ms: int = 50, pause_ms: int = 400, counts: bool = False):
+    """The silence step's definition on the CPU for one whole 24 kHz clip (q3_silence_trim): the edges cut down to edge_ms, pauses
+    down to pause_ms, with the bits a stage row with `set_silence` returns. AudioBuffer in, AudioBuffer out; an array gives an
+    array. counts: also the Silence counts."""
+    x = np.ascontiguousarray(samples.samples if isinstance(samples, AudioBuffer) else samples, dtype=np.float32).reshape(-1)
+    if isinstance(samples, AudioBuffer) and samples.sample_rate != 24000:
+        raise ValueError(f"trim_silence takes 24 kHz audio, not {samples.sample_rate} Hz")
+    y = np.zeros(max(x.size, 1), np.float32)
+    n = ctypes.c_size_t(); c = (ctypes.c_int64 * 5)()
+    check(lib.q3_silence_trim(x.ctypes.data_as(ctypes.c_void_p), x.size, silence_mb(threshold_db), int(edge_ms), int(pause_ms),
+                              y.ctypes.data_as(ctypes.c_void_p), y.size, ctypes.byref(n), c))
+    y = y[:int(n.value)].copy()
+    out = AudioBuffer(y, 24000) if isinstance(samples, AudioBuffer) else y
+    return (out, Silence(*[int(v) for v in c])) if counts else out
+
+
 class PcmStage:
     """The output stage (q3_pcm_stage): `rows` independent rows, each with its own output rate and format (float32, int16 or G.711
     bytes), fed 24 kHz float32 in pushes of any size; one pass serves every row of a push."""
@@ -1438,6 +1518,7 @@ class PcmStage:
         self._tempo = [1000] * self.rows
         self._level = [False] * self.rows
         self._pitch = [0] * self.rows
+        self._silence = [None] * self.rows
         self._h = ctypes.c_void_p()
         check(lib.q3_pcm_stage_create(self.device_index, self.rows, self.max_push_samples, ctypes.byref(self._h)))
 
@@ -1472,6 +1553,20 @@ class PcmStage:
         and `set_level` keep it."""
         check(lib.q3_pcm_stage_set_loudness(self._h, int(row), int(mode), int(target_mb), int(prior_mb)))
 
+    def set_silence(self, row: int, threshold_db: float, edge_ms: int = 50, pause_ms: int = 400):
+        """Row's silence step (q3_pcm_stage_set_silence): hops of 10 ms whose mean square is under threshold_db (dB re full scale,
+        -90..-20; 0 or None = off) for more than 20 ms around them are cut at the stream's two ends down to edge_ms and inside it
+        down to pause_ms; also restarts the row. `set`, `reset` and the other `set_*` keep it."""
+        thr = silence_mb(threshold_db)
+        check(lib.q3_pcm_stage_set_silence(self._h, int(row), thr, int(edge_ms), int(pause_ms)))
+        self._silence[int(row)] = (int(edge_ms), int(pause_ms)) if thr else None
+
+    def silence(self, row: int) -> "Silence":
+        """The row's counts after its last successful push (q3_pcm_stage_silence)."""
+        v = [ctypes.c_int64() for _ in range(5)]
+        check(lib.q3_pcm_stage_silence(self._h, int(row), *[ctypes.byref(x) for x in v]))
+        return Silence(*[int(x.value) for x in v])
+
     def loudness(self, row: int) -> Loudness:
         """The row's reading after its last successful push (q3_pcm_stage_loudness)."""
         m = ctypes.c_float(); g = ctypes.c_float(); nb = ctypes.c_int(); cg = ctypes.c_int()
@@ -1504,7 +1599,8 @@ class PcmStage:
         return PCM_DTYPE[self._fmt[int(row)][1]]
 
     def bound(self, row: int, n_in: int) -> int:
-        return pcm_stage_bound(self._fmt[int(row)][0], n_in, self._tempo[int(row)], self._level[int(row)], self._pitch[int(row)])
+        return pcm_stage_bound(self._fmt[int(row)][0], n_in, self._tempo[int(row)], self._level[int(row)], self._pitch[int(row)],
+                               self._silence[int(row)])
 
     def push(self, samples: dict, last=()) -> dict:
         """{row: 24 kHz f32 samples} -> {row: samples at the row's rate and format}, every row in one pass; rows in `last` are
@@ -1535,12 +1631,13 @@ class PcmStage:
 
 
 def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_permille: int = 1000, fmt: Optional[str] = None,
-                 gain_mb: int = 0, ceiling_mb: int = 0, target_mb: Optional[int] = None, prior_mb: int = 0, pitch_cents: int = 0) -> AudioBuffer:
+                 gain_mb: int = 0, ceiling_mb: int = 0, target_mb: Optional[int] = None, prior_mb: int = 0, pitch_cents: int = 0, silence=None) -> AudioBuffer:
     """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked (fmt: "f32" /
     "s16" / "ulaw" / "alaw") — what a caller of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their
     result. tempo_permille: the clip's speaking rate (1250 = 1.25 x as fast, 1000 = as it is). gain_mb / ceiling_mb: its level. target_mb / prior_mb: the loudness it is
     steered to (millibel of LUFS) and the gain it starts from — a causal normaliser: the first 400 ms leave at the prior.
-    pitch_cents: its pitch (-1200..1200 cents, 0 = as it is; the duration stays that of the tempo)."""
+    pitch_cents: its pitch (-1200..1200 cents, 0 = as it is; the duration stays that of the tempo). silence = (threshold_db, edge_ms,
+    pause_ms): its edges and pauses cut first, as `trim_silence` does."""
     code = pcm_format(pcm16, fmt)
     x = np.ascontiguousarray(audio.samples if isinstance(audio, AudioBuffer) else audio, dtype=np.float32).reshape(-1)
     if isinstance(audio, AudioBuffer) and audio.sample_rate != 24000:
@@ -1556,6 +1653,8 @@ def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_p
             ps.set_level(0, gain_mb, ceiling_mb)
         if target_mb is not None:
             ps.set_loudness(0, LOUD_NORMALIZE, target_mb, prior_mb)
+        if silence is not None:
+            ps.set_silence(0, *silence)
         return AudioBuffer(ps.push({0: x}, last=(0,))[0], int(rate))
     finally:
         ps.close()

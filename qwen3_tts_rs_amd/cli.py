@@ -75,6 +75,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prior-gain-db", type=float, default=0.0, metavar="X",
                     help="with --target-lufs: the gain the first 400 ms leave at, -60 .. +24 dB (the final gain of an earlier request "
                          "with the same voice)")
+    ap.add_argument("--trim-silence-db", type=float, default=None, metavar="T",
+                    help="with --streaming: cut near-silence by the output stage before anything else touches the audio: 10 ms hops "
+                         "whose level is under T dBFS (-90 .. -20, e.g. -50) are dropped at the two ends beyond --edge-ms and inside "
+                         "the utterance beyond --max-pause-ms; prints the samples cut at the front, in pauses and at the end")
+    ap.add_argument("--edge-ms", type=int, default=50, metavar="MS", action=_Given,
+                    help="with --trim-silence-db: the silence kept at the start and at the end, 0 .. 1000 ms in steps of 10")
+    ap.add_argument("--max-pause-ms", type=int, default=400, metavar="MS", action=_Given,
+                    help="with --trim-silence-db: the longest pause left inside the utterance, 20 .. 2000 ms in steps of 10")
     ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
                     help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
                          "first token to the first audio; writes the same WAV as without the flag)")
@@ -182,6 +190,24 @@ def loudness_from_args(a):
     return target, prior, ceiling
 
 
+def silence_from_args(a):
+    """(threshold_db, edge_ms, pause_ms) of --trim-silence-db / --edge-ms / --max-pause-ms, or None without --trim-silence-db;
+    ValueError for a combination the CLI refuses (before anything is loaded)."""
+    if a.trim_silence_db is None:
+        if getattr(a, "edge_ms_given", False) or getattr(a, "max_pause_ms_given", False):
+            raise ValueError("--edge-ms / --max-pause-ms apply to --trim-silence-db")
+        return None
+    if not a.streaming:
+        raise ValueError("--trim-silence-db applies to --streaming (trim a whole utterance with api.trim_silence)")
+    if not -90.0 <= a.trim_silence_db <= -20.0:
+        raise ValueError(f"--trim-silence-db {a.trim_silence_db} out of range (-90 .. -20)")
+    if not 0 <= a.edge_ms <= 1000 or a.edge_ms % 10:
+        raise ValueError(f"--edge-ms {a.edge_ms} out of range (0 .. 1000 in steps of 10)")
+    if not 20 <= a.max_pause_ms <= 2000 or a.max_pause_ms % 10:
+        raise ValueError(f"--max-pause-ms {a.max_pause_ms} out of range (20 .. 2000 in steps of 10)")
+    return a.trim_silence_db, a.edge_ms, a.max_pause_ms
+
+
 def max_frames_from_args(a) -> int:
     return int(a.duration * 12.5) if a.duration is not None else a.frames
 
@@ -235,6 +261,7 @@ def main(argv=None) -> int:
         return 2
     try:
         loud = loudness_from_args(a)
+        sil = silence_from_args(a)
     except ValueError as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
@@ -312,12 +339,12 @@ def main(argv=None) -> int:
     gain_mb, ceiling_mb = int(round(a.gain_db * 100.0)), int(round(a.ceiling_db * 100.0))
     if loud is not None:
         ceiling_mb = loud[2]
-    reading = None
+    reading = None; cuts = None
     if (a.output_format != "f32" or gain_mb or ceiling_mb) and not a.streaming:
         print("error: --output-format / --gain-db / --ceiling-db apply to --streaming (convert a whole utterance with "
               "api.resample_gpu(..., fmt=, gain_mb=, ceiling_mb=))", file=sys.stderr)
         return 2
-    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None):
+    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None or sil is not None):
         # the chunks of the streaming session, each through the session's output stage as it leaves
         s = model.session([utt], opts)
         try:
@@ -330,6 +357,8 @@ def main(argv=None) -> int:
                 s.set_level(gain_mb, ceiling_mb)
             if loud is not None:
                 s.set_loudness(api.LOUD_NORMALIZE, loud[0], loud[1])
+            if sil is not None:
+                s.set_silence(*sil)
         except api._lib.Q3Error as e:
             print(f"error: {e}", file=sys.stderr)
             return 2
@@ -343,6 +372,8 @@ def main(argv=None) -> int:
         samples = np.concatenate(chunks) if chunks else np.zeros(0, api.PCM_DTYPE[api.PCM_NAMES.index(a.output_format)])
         if loud is not None:
             reading = s.loudness(0)
+        if sil is not None:
+            cuts = s.silence(0)
         codes = s.codes(0); s.close()
         timing = None; out_rate = a.output_rate
         if a.output_format in ("ulaw", "alaw"):
@@ -375,6 +406,9 @@ def main(argv=None) -> int:
     if reading is not None:
         print(f"Loudness: {reading.lufs:.2f} LUFS measured over {reading.gated} of {reading.blocks} blocks (target {a.target_lufs:.2f}), "
               f"final gain {reading.gain_db:+.2f} dB (--prior-gain-db {reading.gain_db:.2f} for the next request of this voice)")
+    if cuts is not None:
+        print(f"Silence: {cuts.lead_cut} samples cut at the front, {cuts.pause_cut} in pauses, {cuts.trail_cut} at the end "
+              f"({cuts.n_out} of {cuts.n_in} samples at 24 kHz kept; under {a.trim_silence_db:.1f} dBFS, edges {a.edge_ms} ms, pauses {a.max_pause_ms} ms)")
     os.makedirs(a.output_dir, exist_ok=True)
     wav = a.output or os.path.join(a.output_dir, f"audio_seed{a.seed}_frames{n}.wav")
     if g711 is not None:

@@ -182,7 +182,8 @@ struct BatTicket {
     int o_pitch = 0;                                  // (q3_batcher_ticket_pitch, cents: the stage too)
     // (q3_batcher_ticket_loudness: the stage too; lo_*: the reading after the parts that have landed, under the worker's mutex)
     int o_loud = Q3_LOUD_OFF, o_target = -1900, o_prior = 0; float lo_M = 0.0f, lo_gain = 1.0f; int lo_blocks = 0, lo_gated = 0;
-    bool o_stage() const { return o_rate != 24000 || o_fmt != Q3_PCM_F32 || o_tempo != 1000 || o_pitch != 0 || o_gain != 0 || o_ceil != 0 || o_loud != Q3_LOUD_OFF; }
+    int o_sil = 0, o_edge = 0, o_pause = 20; int64_t si[5] = {0, 0, 0, 0, 0};      // the silence step (0: off) and its counts after the parts that have landed
+    bool o_stage() const { return o_rate != 24000 || o_fmt != Q3_PCM_F32 || o_tempo != 1000 || o_pitch != 0 || o_gain != 0 || o_ceil != 0 || o_loud != Q3_LOUD_OFF || o_sil != 0; }
     std::vector<char> sout; size_t o_read = 0;
     size_t o_bytes() const { return o_fmt == Q3_PCM_F32 ? 4 : o_fmt == Q3_PCM_S16 ? 2 : 1; }
     // Parking (q3_batcher_set_parking; host thread). rec: the ticket's row as a record while it reads PARKED; want_in: it
@@ -345,8 +346,11 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
         t.s_deliv += o.n_new;
         float lm = 0.0f, lg = 1.0f; int lb = 0, lc = 0;
         const bool loud = t.o_conv && t.o_loud != Q3_LOUD_OFF && q3_pcm_stage_loudness(d.ps, o.p->row, &lm, &lg, &lb, &lc) == Q3_OK;
+        int64_t si[5] = {0, 0, 0, 0, 0};
+        const bool sil = t.o_conv && t.o_sil != 0 && q3_pcm_stage_silence(d.ps, o.p->row, &si[0], &si[1], &si[2], &si[3], &si[4]) == Q3_OK;
         std::lock_guard<std::mutex> g(d.mu);
         if (loud) { t.lo_M = lm; t.lo_gain = lg; t.lo_blocks = lb; t.lo_gated = lc; }
+        if (sil) memcpy(t.si, si, sizeof(si));
         if (t.o_conv) t.sout.insert(t.sout.end(), o.out.begin(), o.out.begin() + (long)(o.n_out * t.o_bytes()));
         else t.spcm.insert(t.spcm.end(), o.pcm.begin(), o.pcm.end());
     };
@@ -368,6 +372,7 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
                 if (so == Q3_OK && t.o_pitch != 0) so = q3_pcm_stage_set_pitch(d.ps, p.row, t.o_pitch);
                 if (so == Q3_OK) so = q3_pcm_stage_set_level(d.ps, p.row, t.o_gain, t.o_ceil);      // (off too, for the same reason)
                 if (so == Q3_OK) so = q3_pcm_stage_set_loudness(d.ps, p.row, t.o_loud, t.o_target, t.o_prior);      // (off too)
+                if (so == Q3_OK) so = q3_pcm_stage_set_silence(d.ps, p.row, t.o_sil, t.o_edge, t.o_pause);      // (off too)
                 if (so != Q3_OK) fail(t, so, q3_last_error());
             }
             if (is_failed(t)) continue;
@@ -1309,6 +1314,34 @@ extern "C" q3_status q3_batcher_ticket_loudness_read(q3_batcher* b, int64_t tick
     if (gain) *gain = t.lo_gain;
     if (blocks) *blocks = t.lo_blocks;
     if (gated) *gated = t.lo_gated;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_ticket_silence(q3_batcher* b, int64_t ticket, int threshold_mB, int edge_ms, int pause_ms) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence: ticket %lld was not submitted as streamed", (long long)ticket);
+    Q3C(pcm_stage_silence_checked("q3_batcher_ticket_silence", threshold_mB, edge_ms, pause_ms));
+    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
+        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence: ticket %lld has been through a step: its silence step is set between its submission and the next q3_batcher_step", (long long)ticket);
+    t.o_sil = threshold_mB; t.o_edge = edge_ms; t.o_pause = pause_ms; t.o_conv = t.o_stage();
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_batcher_ticket_silence_read(q3_batcher* b, int64_t ticket, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut) {
+    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence_read: null batcher");
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence_read: unknown ticket %lld", (long long)ticket);
+    BatTicket& t = *it->second;
+    if (t.o_sil == 0) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence_read: ticket %lld has no silence step (q3_batcher_ticket_silence)", (long long)ticket);
+    std::lock_guard<std::mutex> g(b->dec->mu);
+    if (n_in) *n_in = t.si[0];
+    if (n_out) *n_out = t.si[1];
+    if (lead_cut) *lead_cut = t.si[2];
+    if (pause_cut) *pause_cut = t.si[3];
+    if (trail_cut) *trail_cut = t.si[4];
     return Q3_OK;
 }
 

@@ -468,6 +468,7 @@ struct q3_session {
     std::vector<int> out_level;           // q3_session_set_level: per row, gain and ceiling in mB (empty: every row off)
     std::vector<int> out_pitch;           // q3_session_set_pitch: per row, cents (empty: every row at 0)
     std::vector<int> out_loud;            // q3_session_set_loudness: per row, mode, target and prior in mB (empty: every row off)
+    std::vector<int> out_sil;             // q3_session_set_silence: per row, threshold in mB, edge and pause in ms (empty: every row off)
     // overlapped segment decode (q3_session_run): vocoder segments run on their own stream while the frame loop continues
     hipStream_t dec_stream = nullptr; hipEvent_t dec_ev = nullptr;
     std::vector<CodecWS> par_ws; std::vector<hipStream_t> par_streams;     // q3_session_run: utterances vocoded side by side
@@ -537,7 +538,8 @@ Q3_HIDDEN void codec_stream_blocks(const q3_codec_stream* cs, int row, int upto,
 Q3_HIDDEN void codec_stream_reset(q3_codec_stream* cs, int row);
 // q3_pcm_stage.hip
 // n samples of 24 kHz f32 on the device for stage row `row`; last: the row's input ends here (its tail is flushed)
-struct PsSeg { int row; const float* dev; size_t n; int last; };
+// (trimmed: set by pcm_stage_trim for a row with a silence step — dev and n are then what the step kept, in the stage's own buffer)
+struct PsSeg { int row; const float* dev; size_t n; int last; int trimmed = 0; };
 // one row of a pass of k_pcm_stage (device-visible, 8-byte aligned)
 struct PsDesc {
     const float* src; const float* tail_in; float* tail_out; const float* taps; void* out;
@@ -577,6 +579,21 @@ struct PtDesc {
     long long base, j0;
     int n_new, n_v, t, te, den1, dq1, dr1; float fc;
 };
+// one row of a pass of k_trim (device-visible, 8-byte aligned), DESIGN 4.12e: the row's stream into the silence step is head_in (the
+// undecided front of the run in progress, head hops from hop run + m on), tail_in (its last `tail` samples) below `base`, the n_new
+// samples of src from there, zeros from n_total on. Hops c_old .. c_end - 1 get their energy in this pass, hops k_old .. k_new - 1
+// are classified; st_in (null at the row's start) / st_out: the two copies of the row's TR_ST counters, res: st_out again, where the
+// host reads it; y: the kept samples, ops: the kept hops (source hop, seam partner or -1), fl: loud and active flags of the pass
+struct TrDesc {
+    const float* src; const float* tail_in; float* tail_out; const float* head_in; float* head_out;
+    const long long* st_in; long long* st_out; long long* res;
+    float* y; int* ops; unsigned char* fl; const float* win;
+    long long base, n_total, c_old, c_end, c_new, k_old, k_new;
+    int n_new, last, E, P1, P2, tail, head, cap_ops; float theta; int fl_n;
+    int tail_lead, tail_run;                // what tail_out takes: behind a leading run in progress, and otherwise (tail: what tail_in holds)
+};
+// the pre-pass of a push with silence steps: per such segment its index, what entered the step and the counters it left
+struct PsTrim { std::vector<int> seg; std::vector<long long> n_new; std::vector<long long> res; };
 // (tdesc, t_y, t_k1: the time stretcher in front, DESIGN 4.12a — the rows at a tempo other than 1000, per segment the y samples of
 // this push and the frame the row reaches; pcm_stage_launch uploads tdesc itself, into the stage's own buffer.
 // ldesc, l_in, l_z, l_tiles: the level step between the two, DESIGN 4.12b — the rows with a level, per segment the samples that
@@ -591,6 +608,7 @@ struct PsPlan {
     q3_pcm_stage* ps = nullptr; std::vector<TpDesc> tdesc; std::vector<long long> t_y, t_k1;
     std::vector<LvDesc> ldesc; std::vector<long long> l_in, l_z; int l_tiles = 1;
     std::vector<LoDesc> odesc; std::vector<long long> o_n;
+    PsTrim trim;                             // filled by pcm_stage_trim in front of pcm_stage_plan, which leaves it alone
 };
 Q3_HIDDEN int pcm_stage_rows(const q3_pcm_stage* ps);
 Q3_HIDDEN size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row);
@@ -599,7 +617,13 @@ Q3_HIDDEN q3_status pcm_stage_pitch_checked(const char* who, int tempo_permille,
 Q3_HIDDEN q3_status pcm_stage_loud_checked(const char* who, int mode, int target_mB, int prior_mB);      // the ranges of q3_pcm_stage_set_loudness
 Q3_HIDDEN q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_rows, const int* rows);
 Q3_HIDDEN size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last);
+Q3_HIDDEN q3_status pcm_stage_silence_checked(const char* who, int threshold_mB, int edge_ms, int pause_ms);      // the ranges of q3_pcm_stage_set_silence
+// Rows with a silence step: whether a push has one; the pre-pass — k_trim for those segments on `st` (which has the
+// samples), their counters back, a wait — that replaces their dev / n by what the step kept and fills plan.trim for the commit
+Q3_HIDDEN bool pcm_stage_has_trim(const q3_pcm_stage* ps, const std::vector<PsSeg>& segs);
+Q3_HIDDEN q3_status pcm_stage_trim(q3_pcm_stage* ps, std::vector<PsSeg>& segs, hipStream_t st, PsPlan& plan);
 Q3_HIDDEN q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan);
+Q3_HIDDEN q3_status pcm_stage_desc_upload(q3_pcm_stage* ps, const PsPlan& plan, hipStream_t st, const PsDesc** desc_dev);
 Q3_HIDDEN hipError_t pcm_stage_launch(const PsDesc* desc_dev, const PsPlan& plan, hipStream_t st);
 Q3_HIDDEN void pcm_stage_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const PsPlan& plan);
 Q3_HIDDEN const char* pcm_stage_out_dev(const q3_pcm_stage* ps);

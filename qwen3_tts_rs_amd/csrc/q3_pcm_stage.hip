@@ -43,6 +43,14 @@
 // back like the resampler, keeps the row's last 128 inputs in two copies flipped like the tails, and writes into the row's part of
 // a v buffer that the steps behind take as the row's stream. A row at 0 cents is not touched by any of it.
 //
+// At the very front, for the rows that ask for it: a silence step. k_trim takes the energy of every 10 ms hop of the
+// row's 24 kHz stream, calls a hop active when a hop within 20 ms of it is above a threshold, and drops what a run of non-active
+// hops has beyond an edge (at the stream's two ends) or beyond a cap (inside it, with one crossfaded hop at the seam). How many
+// samples leave depends on the data, so a push with such a row runs in two passes: k_trim into the row's part of an s buffer, the
+// kept counts back to the host, then the plan and the launches of the steps behind, which take s as the row's input. The row keeps
+// the input whose fate is open (the last hops, and the front of the run in progress) and its counters, in two copies flipped like
+// the tails. A row whose step is off is not touched by any of it, and a push without such a row is the single pass it was.
+//
 // Formats: f32, PCM16, and G.711 mu-law / A-law — the companding of the PCM16 value, one byte per sample.
 #include "q3_engine.h"
 
@@ -579,6 +587,170 @@ void pitch_tables(std::vector<float>& sc, std::vector<float>& w2) {
     }
 }
 
+// ---- the silence step ----
+constexpr int TR_H = 240, TR_G = 2;                             // hop (10 ms), guard in hops
+constexpr int TR_THREADS = 256;
+constexpr int TR_ST = 8;                                        // long longs a copy of the counters: [out | run | lead | pause | trail | bits | - | overflow]
+constexpr int TR_S_OUT = 0, TR_S_RUN = 1, TR_S_LEAD = 2, TR_S_PAUSE = 3, TR_S_TRAIL = 4, TR_S_BITS = 5, TR_S_OVER = 7;
+constexpr int TR_THR_MIN = -9000, TR_THR_MAX = -2000, TR_EDGE_MAX = 1000, TR_PAUSE_MIN = 20, TR_PAUSE_MAX = 2000;
+
+// the run in progress (its first hop, -1: none) and the samples cut so far at the front, in pauses and at the end
+struct TrRun { long long s, lead, pause, trail; };
+// The rules per run over the classified hops k0 .. k1 - 1 (last: k1 = NH, the stream of N samples ends): emit(a, b) names the kept
+// hops in order, b = -1 for a hop that leaves as it is and the seam's partner otherwise. m = min(E, P1 - 1): hop i of a later run
+// leaves at once for i < m, whatever the run turns out to be.
+template <typename Act, typename Emit>
+__host__ __device__ __forceinline__ void tr_walk(TrRun& r, long long k0, long long k1, bool last, long long N, int E, int P1, int P2, Act act, Emit emit) {
+    const int P = P1 + P2, m = E < P1 - 1 ? E : P1 - 1;
+    for (long long h = k0; h < k1; ++h) {
+        if (act(h)) {
+            if (r.s >= 0) {
+                const long long S = h - r.s;
+                if (r.s == 0) {                                  // leading: its last min(S, E) hops
+                    const long long k = S < E ? S : E;
+                    for (long long i = h - k; i < h; ++i) emit(i, -1);
+                    r.lead = (h - k) * TR_H;
+                } else if (S <= P) {                             // a short pause: whole
+                    for (long long i = r.s + (S < m ? S : m); i < h; ++i) emit(i, -1);
+                } else {                                         // a long one: P1 hops, the last of them the seam, and the last P2
+                    for (long long i = r.s + m; i < r.s + P1 - 1; ++i) emit(i, -1);
+                    emit(r.s + P1 - 1, h - P2 - 1);
+                    for (long long i = h - P2; i < h; ++i) emit(i, -1);
+                    r.pause += (S - P) * TR_H;
+                }
+                r.s = -1;
+            }
+            emit(h, -1);
+        } else {
+            if (r.s < 0) r.s = h;
+            if (r.s > 0 && h - r.s < m) emit(h, -1);
+        }
+    }
+    if (last && r.s >= 0) {
+        const long long S = k1 - r.s, k = S < E ? S : E;
+        if (r.s == 0) {                                          // silent throughout
+            for (long long i = k1 - k; i < k1; ++i) emit(i, -1);
+            r.lead = (k1 - k) * TR_H < N ? (k1 - k) * TR_H : N;
+        } else {                                                 // trailing: its first min(S, E) hops
+            for (long long i = r.s + (S < m ? S : m); i < r.s + k; ++i) emit(i, -1);
+            r.trail = N - ((r.s + k) * TR_H < N ? (r.s + k) * TR_H : N);
+        }
+        r.s = -1;
+    }
+}
+
+// One workgroup per row, four phases with a barrier between them. (1) Energies: wave w takes hops c_old + w, + 4, ...; lane q adds
+// the squares of samples q, q + 64, ... of the hop in ascending order (partial q), the fold is the wave reduction d = 32 .. 1, and
+// lane 0 stores whether the hop is loud, behind the flags of the four hops before c_old, which the row's counters carry. Then every
+// thread ORs five neighbours into the active flag of a hop k_old .. k_new - 1. (2) Thread 0 walks those hops from the row's run
+// (tr_walk) and lists the kept hops. (3) Every thread gathers: output i is sample i % 240 of kept hop i / 240, the seam hop two
+// products and a sum, each rounded once. (4) The row's next tail, the front of the run still open, the counters.
+// Bounds: fl holds fl_n = c_end - c_old + 4 loud flags and, from fl_n on, k_new - k_old active ones; g - (c_old - 4) >= 0 since
+// g >= k_old - 2 >= c_old - 4, and < fl_n since g < c_end. ops holds cap_ops pairs and the walk stops listing at cap_ops (reported
+// in the counters: the host refuses the push). x_at reads src[0 .. n_new), tail_in[0 .. tail) and head_in[0 .. head * 240), each
+// behind its own range check; y takes at most 240 * cap_ops floats; tail_out tail_lead or tail_run floats; head_out head * 240
+// from float tail_run on: a copy holds max(tail_lead, tail_run + head * 240) floats, and a head exists only behind the shorter tail.
+__global__ __launch_bounds__(TR_THREADS) void k_trim(const TrDesc* __restrict__ descs) {
+    __shared__ long long sh[2];                                  // thread 0 -> the block: samples kept, the run at the end
+    const TrDesc d = descs[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    TrRun run = {-1, 0, 0, 0};
+    long long out0 = 0, bits = 0;
+    if (d.st_in) {
+        out0 = d.st_in[TR_S_OUT]; run.s = d.st_in[TR_S_RUN]; run.lead = d.st_in[TR_S_LEAD]; run.pause = d.st_in[TR_S_PAUSE];
+        run.trail = d.st_in[TR_S_TRAIL]; bits = d.st_in[TR_S_BITS];
+    }
+    const int m = min(d.E, d.P1 - 1), M = max(d.E, d.P1);
+    const long long head_lo = run.s > 0 ? (run.s + m) * TR_H : -1;
+    // sample q of the row's stream into the step: zeros outside [0, n_total), the new samples from `base`, the tail below, the head
+    auto x_at = [&](long long q) -> float {
+        if (q < 0 || q >= d.n_total) return 0.0f;
+        if (q >= d.base) return d.src[q - d.base];
+        const long long k = q - (d.base - d.tail);
+        if (k >= 0) return d.tail_in ? d.tail_in[k] : 0.0f;
+        const long long hq = q - head_lo;
+        return (head_lo >= 0 && hq >= 0 && hq < (long long)d.head * TR_H && d.head_in) ? d.head_in[hq] : 0.0f;
+    };
+    const long long f0 = d.c_old - 4;                            // the hop of fl[0]
+    if (tid < 4) d.fl[tid] = (unsigned char)((bits >> (3 - tid)) & 1);
+    for (long long h = d.c_old + wave; h < d.c_end; h += TR_THREADS / 64) {
+        float part = 0.0f;
+        for (int j = lane; j < TR_H; j += 64) {
+            float v = x_at(h * TR_H + j);
+            v = __builtin_isfinite(v) ? v : 0.0f;
+            part = q3::add_rn(part, q3::mul_rn(v, v));
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) part = q3::add_rn(part, __shfl_down(part, o));
+        if (lane == 0) d.fl[h - f0] = part > d.theta ? 1 : 0;    // (a NaN compares false)
+    }
+    __syncthreads();
+    unsigned char* ac = d.fl + d.fl_n;
+    for (long long i = tid; i < d.k_new - d.k_old; i += TR_THREADS) {
+        const long long h = d.k_old + i;
+        int a = 0;
+        for (long long g = h - TR_G; g <= h + TR_G; ++g) if (g >= 0 && g >= f0 && g < d.c_end) a |= d.fl[g - f0];
+        ac[i] = (unsigned char)a;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        long long nops = 0, over = 0, last_hop = -1;
+        tr_walk(run, d.k_old, d.k_new, d.last != 0, d.n_total, d.E, d.P1, d.P2,
+                [&](long long h) { return ac[h - d.k_old] != 0; },
+                [&](long long a, long long b) {
+                    if (nops >= d.cap_ops) { over = 1; return; }
+                    d.ops[2 * nops] = (int)a; d.ops[2 * nops + 1] = (int)b; ++nops; last_hop = a;
+                });
+        long long kept = nops * TR_H;
+        if (last_hop >= 0 && (last_hop + 1) * TR_H > d.n_total) kept -= (last_hop + 1) * TR_H - d.n_total;      // the stream's last, partial hop
+        long long nb = 0;                                        // loud flags of the last four complete hops, the newest in bit 0
+        for (int i = 0; i < 4; ++i) { const long long g = d.c_new - 1 - i; if (g >= 0 && g >= f0) nb |= (long long)d.fl[g - f0] << i; }
+        auto put = [&](int i, long long v) { d.st_out[i] = v; d.res[i] = v; };
+        put(TR_S_OUT, out0 + kept); put(TR_S_RUN, run.s); put(TR_S_LEAD, run.lead); put(TR_S_PAUSE, run.pause); put(TR_S_TRAIL, run.trail);
+        put(TR_S_BITS, nb); put(6, 0); put(TR_S_OVER, over);
+        sh[0] = kept; sh[1] = run.s;
+    }
+    __syncthreads();
+    const long long kept = sh[0], s_end = sh[1];
+    for (long long i = tid; i < kept; i += TR_THREADS) {
+        const long long k = i / TR_H; const int j = (int)(i - k * TR_H);
+        const long long a = d.ops[2 * k], b = d.ops[2 * k + 1];
+        const float xa = x_at(a * TR_H + j);
+        d.y[i] = b < 0 ? xa : q3::add_rn(q3::mul_rn(xa, d.win[TR_H + j]), q3::mul_rn(x_at(b * TR_H + j), d.win[j]));
+    }
+    // (a leading run still open needs its last E hops; anything else the last P2 + 1: the head lies behind the shorter tail)
+    const int tl = s_end == 0 ? d.tail_lead : d.tail_run;
+    for (int i = tid; i < tl; i += TR_THREADS) d.tail_out[i] = x_at(d.n_total - tl + i);
+    if (s_end > 0) {                                             // hops m .. M - 1 of the run in progress, as far as they are classified
+        const long long lo = (s_end + m) * TR_H, hi = (s_end + M < d.k_new ? s_end + M : d.k_new) * TR_H;
+        for (long long q = lo + tid; q < hi; q += TR_THREADS) d.head_out[q - lo] = x_at(q);
+    }
+}
+
+// hops: E, P1, P2 of a setting; what a row retains at most (the issue's hold) and what its state keeps beside the counters
+struct TrSet { int E, P1, P2; };
+inline TrSet tr_set(int edge_ms, int pause_ms) { const int P = pause_ms / 10; return {edge_ms / 10, P - P / 2, P / 2}; }
+inline size_t tr_hold(const TrSet& t) { return (size_t)(std::max(t.E, t.P1) + t.P2 + TR_G + 2) * TR_H; }
+inline int tr_head(const TrSet& t) { return std::max(t.E, t.P1) - std::min(t.E, t.P1 - 1); }   // hops
+// samples of the tail: the last hops that can still leave (E of a leading run in progress, else P2 + 1), the guard, the partial hop
+inline int tr_tail_lead(const TrSet& t) { return (t.E + TR_G + 1) * TR_H; }
+inline int tr_tail_run(const TrSet& t) { return (t.P2 + 1 + TR_G + 1) * TR_H; }
+// floats of a copy behind the counters: a leading run's tail, or the shorter tail and the head — never more than tr_hold
+inline size_t tr_state_floats(const TrSet& t) { return std::max((size_t)tr_tail_lead(t), (size_t)tr_tail_run(t) + (size_t)tr_head(t) * TR_H); }
+inline float tr_theta(int threshold_mB) { return (float)(240.0 * pow(10.0, (double)threshold_mB / 1000.0)); }
+// w0[j] = (float)((j + 0.5) / 240), then w1[j] = (float)(1 - (j + 0.5) / 240): f64, rounded once
+void tr_window(float* w) {
+    for (int j = 0; j < TR_H; ++j) { const double t = ((double)j + 0.5) / (double)TR_H; w[j] = (float)t; w[TR_H + j] = (float)(1.0 - t); }
+}
+inline float h_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+inline float h_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 struct Rate { int L = 1, M = 1; };
 bool rate_of(uint32_t sr, Rate* r) {
     if (sr < PS_RATE_MIN || sr > PS_RATE_MAX) return false;
@@ -644,6 +816,11 @@ struct PsRow {
     int pitch = 0, te = TP_OFF;
     long long p_in = 0, p_out = 0;            // samples that have entered the step, and left it
     float* p_tail = nullptr; int p_cur = 0;   // on the device, two copies of 128 floats: the last 128 inputs
+    // the silence step at the very front: s_thr == 0: off; s_in counts the 24 kHz samples that have entered it
+    int s_thr = 0, s_edge = 0, s_pause = 0; TrSet s_set = {0, 0, 0}; float s_theta = 0.0f;
+    long long s_in = 0;
+    long long s_read[TR_ST] = {0, -1, 0, 0, 0, 0, 0, 0};      // the counters after the last successful push (the host's copy)
+    char* s_state = nullptr; size_t s_copy = 0, s_cap = 0; int s_cur = 0;      // on the device, two copies of s_copy bytes: [TR_ST counters | tail | head]
 };
 constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
 struct q3_pcm_stage {
@@ -669,6 +846,10 @@ struct q3_pcm_stage {
     float* p_tab = nullptr;                                                // the sinc table, PT_SC_N floats, then the window's, PT_W2_N
     float* v_dev = nullptr; size_t v_cap = 0;                              // the repitched samples of a push, row after row
     char *pd_dev = nullptr, *pd_host = nullptr; size_t pd_cap = 0;         // k_pitch's descriptors
+    // the silence step (all of it allocated by the first row with a setting other than off, or the first push of one)
+    float* s_win = nullptr;                                                // the seam's weights: w0, then w1, 240 floats each
+    char* s_dev = nullptr; size_t s_cap = 0;                               // of a push, row after row: kept samples | kept hops | flags
+    char *sd_dev = nullptr, *sd_host = nullptr; size_t sd_cap = 0;         // k_trim's descriptors, then the rows' counters coming back
 };
 
 extern "C" q3_status q3_pcm_stage_taps(uint32_t sample_rate, float* taps_host, size_t cap_floats, int* L, int* M) {
@@ -810,6 +991,9 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
     dev_free(ps->t_win); dev_free(ps->y_dev); dev_free(ps->td_dev); dev_free(ps->z_dev); dev_free(ps->ld_dev);
     dev_free(ps->w_dev); dev_free(ps->od_dev);
     dev_free(ps->p_tab); dev_free(ps->v_dev); dev_free(ps->pd_dev);
+    for (PsRow& r : ps->rows) dev_free(r.s_state);
+    dev_free(ps->s_win); dev_free(ps->s_dev); dev_free(ps->sd_dev);
+    if (ps->sd_host) (void)hipHostFree(ps->sd_host);
     if (ps->pd_host) (void)hipHostFree(ps->pd_host);
     if (ps->od_host) (void)hipHostFree(ps->od_host);
     if (ps->td_host) (void)hipHostFree(ps->td_host);
@@ -829,6 +1013,8 @@ void pcm_stage_reset(q3_pcm_stage* ps, int row) {
     r.l_in = 0;
     r.o_in = 0;
     r.p_in = r.p_out = 0;
+    r.s_in = 0;
+    for (int i = 0; i < TR_ST; ++i) r.s_read[i] = i == TR_S_RUN ? -1 : 0;
 }
 
 extern "C" q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row) {
@@ -1063,6 +1249,119 @@ extern "C" q3_status q3_pcm_stage_tempo_lags(q3_pcm_stage* ps, int row, int64_t*
     return Q3_OK;
 }
 
+static q3_status silence_checked(const char* who, int threshold_mB, int edge_ms, int pause_ms) {
+    if (threshold_mB != 0 && (threshold_mB < TR_THR_MIN || threshold_mB > TR_THR_MAX))
+        return set_err(Q3_INVALID_ARG, "%s: threshold %d mB out of range (%d..%d; 0 = off)", who, threshold_mB, TR_THR_MIN, TR_THR_MAX);
+    if (edge_ms < 0 || edge_ms > TR_EDGE_MAX || edge_ms % 10 != 0)
+        return set_err(Q3_INVALID_ARG, "%s: edge of %d ms (0..%d, a multiple of 10)", who, edge_ms, TR_EDGE_MAX);
+    if (pause_ms < TR_PAUSE_MIN || pause_ms > TR_PAUSE_MAX || pause_ms % 10 != 0)
+        return set_err(Q3_INVALID_ARG, "%s: pause cap of %d ms (%d..%d, a multiple of 10)", who, pause_ms, TR_PAUSE_MIN, TR_PAUSE_MAX);
+    return Q3_OK;
+}
+q3_status pcm_stage_silence_checked(const char* who, int threshold_mB, int edge_ms, int pause_ms) { return silence_checked(who, threshold_mB, edge_ms, pause_ms); }
+
+extern "C" q3_status q3_pcm_stage_silence_hold(int edge_ms, int pause_ms, size_t* samples) {
+    Q3C(silence_checked("q3_pcm_stage_silence_hold", 0, edge_ms, pause_ms));
+    if (!samples) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_silence_hold: null argument");
+    *samples = tr_hold(tr_set(edge_ms, pause_ms));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_bound_silence(uint32_t sample_rate, int tempo_permille, int cents, int with_level, int edge_ms, int pause_ms, size_t n_in,
+                                                size_t* n_out_max) {
+    Q3C(silence_checked("q3_pcm_stage_bound_silence", 0, edge_ms, pause_ms));
+    if (n_in > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_silence: n_in above 2^48");
+    // a push hands on at most its own samples and what the row had retained
+    return q3_pcm_stage_bound_pitch(sample_rate, tempo_permille, cents, with_level, n_in + tr_hold(tr_set(edge_ms, pause_ms)), n_out_max);
+}
+
+// the whole definition for one clip on the CPU: the same f32 operations in the same order as k_trim
+extern "C" q3_status q3_silence_trim(const float* x, size_t n, int threshold_mB, int edge_ms, int pause_ms, float* y, size_t cap, size_t* n_y, int64_t* counts) {
+    Q3C(silence_checked("q3_silence_trim", threshold_mB, edge_ms, pause_ms));
+    if (threshold_mB == 0) return set_err(Q3_INVALID_ARG, "q3_silence_trim: threshold 0 is off: nothing to do");
+    if ((n > 0 && !x) || !n_y) return set_err(Q3_INVALID_ARG, "q3_silence_trim: null argument");
+    if (n > ((size_t)1 << 40)) return set_err(Q3_INVALID_ARG, "q3_silence_trim: n above 2^40");
+    const TrSet t = tr_set(edge_ms, pause_ms);
+    const float theta = tr_theta(threshold_mB);
+    const long long N = (long long)n, NH = (N + TR_H - 1) / TR_H;
+    std::vector<char> loud((size_t)NH, 0), act((size_t)NH, 0);
+    for (long long h = 0; h < NH; ++h) {
+        float p[64];
+        for (int q = 0; q < 64; ++q) p[q] = 0.0f;
+        for (int j = 0; j < TR_H; ++j) {
+            const long long i = h * TR_H + j;
+            float v = i < N ? x[i] : 0.0f;
+            if (!std::isfinite(v)) v = 0.0f;
+            p[j & 63] = h_add_rn(p[j & 63], h_mul_rn(v, v));
+        }
+        for (int d = 32; d >= 1; d >>= 1) for (int q = 0; q < d; ++q) p[q] = h_add_rn(p[q], p[q + d]);
+        loud[(size_t)h] = p[0] > theta ? 1 : 0;
+    }
+    for (long long h = 0; h < NH; ++h)
+        for (long long g = std::max<long long>(0, h - TR_G); g <= std::min(NH - 1, h + TR_G); ++g) act[(size_t)h] |= loud[(size_t)g];
+    std::vector<std::pair<long long, long long>> ops;
+    TrRun run = {-1, 0, 0, 0};
+    tr_walk(run, 0, NH, true, N, t.E, t.P1, t.P2, [&](long long h) { return act[(size_t)h] != 0; },
+            [&](long long a, long long b) { ops.push_back({a, b}); });
+    long long kept = (long long)ops.size() * TR_H;
+    if (!ops.empty() && (ops.back().first + 1) * TR_H > N) kept -= (ops.back().first + 1) * TR_H - N;
+    *n_y = (size_t)kept;
+    if (counts) { counts[0] = N; counts[1] = kept; counts[2] = run.lead; counts[3] = run.pause; counts[4] = run.trail; }
+    if (!y && cap == 0) return Q3_OK;                              // (no buffer: the counts alone)
+    if (!y || cap < (size_t)kept) return set_err(Q3_INVALID_ARG, "q3_silence_trim: %lld samples, the buffer takes %zu", kept, cap);
+    float w[2 * TR_H];
+    tr_window(w);
+    for (long long i = 0; i < kept; ++i) {
+        const long long k = i / TR_H, j = i - k * TR_H, a = ops[(size_t)k].first, b = ops[(size_t)k].second;
+        y[i] = b < 0 ? x[a * TR_H + j] : h_add_rn(h_mul_rn(x[a * TR_H + j], w[TR_H + j]), h_mul_rn(x[b * TR_H + j], w[j]));
+    }
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_set_silence(q3_pcm_stage* ps, int row, int threshold_mB, int edge_ms, int pause_ms) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_silence: bad row");
+    Q3C(silence_checked("q3_pcm_stage_set_silence", threshold_mB, edge_ms, pause_ms));      // (before the device is touched)
+    PsRow& r = ps->rows[(size_t)row];
+    const TrSet t = tr_set(edge_ms, pause_ms);
+    if (threshold_mB != 0) {
+        HIPC(hipSetDevice(ps->device));
+        if (!ps->s_win) {
+            float w[2 * TR_H];
+            tr_window(w);
+            float* d = nullptr;
+            if (dev_malloc((void**)&d, sizeof(w)) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "q3_pcm_stage_set_silence: seam weights"); }
+            const hipError_t e = q3_hipMemcpy(d, w, sizeof(w), hipMemcpyHostToDevice);
+            if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "q3_pcm_stage_set_silence: weight upload: %s", hipGetErrorString(e)); }
+            ps->s_win = d;
+        }
+        const size_t copy = ((size_t)TR_ST * 8 + tr_state_floats(t) * 4 + 15) & ~(size_t)15;
+        if (2 * copy > r.s_cap) {                                  // (the row restarts below: what the old state held is not needed)
+            dev_free(r.s_state); r.s_state = nullptr; r.s_cap = 0;
+            if (dev_malloc((void**)&r.s_state, 2 * copy) != hipSuccess) {
+                (void)hipGetLastError(); r.s_state = nullptr; r.s_thr = 0;
+                return set_err(Q3_OOM, "q3_pcm_stage_set_silence: state of row %d", row);
+            }
+            r.s_cap = 2 * copy;
+        }
+        r.s_copy = copy;
+    }
+    r.s_thr = threshold_mB; r.s_edge = edge_ms; r.s_pause = pause_ms; r.s_set = t; r.s_theta = tr_theta(threshold_mB);
+    pcm_stage_reset(ps, row);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_silence(q3_pcm_stage* ps, int row, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_silence: bad row");
+    const PsRow& r = ps->rows[(size_t)row];
+    if (r.s_thr == 0) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_silence: row %d has no silence step (q3_pcm_stage_set_silence)", row);
+    if (n_in) *n_in = r.s_in;
+    if (n_out) *n_out = r.s_read[TR_S_OUT];
+    if (lead_cut) *lead_cut = r.s_read[TR_S_LEAD];
+    if (pause_cut) *pause_cut = r.s_read[TR_S_PAUSE];
+    if (trail_cut) *trail_cut = r.s_read[TR_S_TRAIL];
+    return Q3_OK;
+}
+
 // what a row has emitted once n more 24 kHz samples have arrived: through the stretcher first, where the row has one
 // (y: the stretched samples by then, k1: the frames)
 // (y: the stretched samples by then, k1: the frames; lv: the samples that have entered the level step by then)
@@ -1095,7 +1394,84 @@ static q3_status dev_grow(q3_pcm_stage* ps, void** p, size_t* cap, size_t bytes)
     return Q3_OK;
 }
 
-// Checks a push (every row at most once and in range — the entry points' business —, n within max_push_samples, no samples for a
+bool pcm_stage_has_trim(const q3_pcm_stage* ps, const std::vector<PsSeg>& segs) {
+    for (const PsSeg& sg : segs) if (ps->rows[(size_t)sg.row].s_thr != 0) return true;
+    return false;
+}
+// The pre-pass of a push in which some row has a silence step. The samples are on the device, readable by work on
+// `st`. One descriptor upload, one k_trim launch (a workgroup per such row), the rows' counters back in one copy, a wait. Then
+// those segments name what the step kept, in the stage's s buffer, and plan.trim holds what pcm_stage_commit needs. Changes no row:
+// k_trim writes the copy of the row's state that is not the current one.
+q3_status pcm_stage_trim(q3_pcm_stage* ps, std::vector<PsSeg>& segs, hipStream_t st, PsPlan& plan) {
+    PsTrim& tr = plan.trim;
+    tr.seg.clear(); tr.n_new.clear(); tr.res.clear();
+    std::vector<TrDesc> descs;
+    std::vector<size_t> y_off, o_off, f_off;
+    size_t bytes = 0;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
+        if (r.s_thr == 0 || r.ended) continue;
+        if (sg.n > ps->max_push) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, ps->max_push);
+        sg.trimmed = 1;
+        if (sg.n == 0 && !sg.last) continue;
+        if (!r.s_state || !ps->s_win) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a silence step and no state", sg.row);
+        TrDesc d{};
+        const TrSet& t = r.s_set;
+        d.base = r.s_in; d.n_new = (int)sg.n; d.n_total = r.s_in + (long long)sg.n; d.last = sg.last ? 1 : 0;
+        d.c_old = d.base / TR_H; d.c_new = d.n_total / TR_H; d.c_end = sg.last ? (d.n_total + TR_H - 1) / TR_H : d.c_new;
+        d.k_old = std::max<long long>(0, d.c_old - TR_G); d.k_new = sg.last ? d.c_end : std::max<long long>(0, d.c_new - TR_G);
+        d.E = t.E; d.P1 = t.P1; d.P2 = t.P2; d.head = tr_head(t); d.theta = r.s_theta;
+        d.tail_lead = tr_tail_lead(t); d.tail_run = tr_tail_run(t);
+        d.tail = r.s_read[TR_S_RUN] == 0 ? d.tail_lead : d.tail_run;      // (what the last successful push left: the host's copy of the counters says which)
+        // the hops a push can hand on: the ones it classifies and the ones the row had retained
+        d.cap_ops = (int)(d.k_new - d.k_old) + (int)(tr_hold(t) / TR_H) + 2;
+        d.fl_n = (int)(d.c_end - d.c_old) + 4;
+        y_off.push_back(bytes); bytes += ((size_t)d.cap_ops * TR_H * 4 + 15) & ~(size_t)15;
+        o_off.push_back(bytes); bytes += ((size_t)d.cap_ops * 2 * sizeof(int) + 15) & ~(size_t)15;
+        f_off.push_back(bytes); bytes += ((size_t)d.fl_n + (size_t)(d.k_new - d.k_old) + 15) & ~(size_t)15;
+        d.src = sg.dev; d.win = ps->s_win;
+        char* in = r.s_state + (size_t)r.s_cur * r.s_copy; char* out = r.s_state + (size_t)(r.s_cur ^ 1) * r.s_copy;
+        d.st_in = r.s_in > 0 ? (const long long*)in : nullptr; d.st_out = (long long*)out;
+        d.tail_in = r.s_in > 0 ? (const float*)(in + TR_ST * 8) : nullptr; d.tail_out = (float*)(out + TR_ST * 8);
+        d.head_in = r.s_in > 0 ? (const float*)(in + TR_ST * 8) + d.tail_run : nullptr; d.head_out = (float*)(out + TR_ST * 8) + d.tail_run;
+        descs.push_back(d); tr.seg.push_back((int)i); tr.n_new.push_back((long long)sg.n);
+    }
+    if (descs.empty()) return Q3_OK;
+    HIPC(hipSetDevice(ps->device));
+    Q3C(dev_grow(ps, (void**)&ps->s_dev, &ps->s_cap, bytes));
+    const size_t nd = descs.size(), db = (nd * sizeof(TrDesc) + 15) & ~(size_t)15, rb = nd * TR_ST * 8;
+    if (db + rb > ps->sd_cap) {
+        dev_free(ps->sd_dev); ps->sd_dev = nullptr;
+        if (ps->sd_host) { (void)hipHostFree(ps->sd_host); ps->sd_host = nullptr; }
+        ps->sd_cap = 0;
+        HIPC(dev_malloc((void**)&ps->sd_dev, (db + rb) * 2));
+        HIPC(hipHostMalloc((void**)&ps->sd_host, (db + rb) * 2, hipHostMallocDefault));
+        ps->sd_cap = (db + rb) * 2;
+    }
+    for (size_t k = 0; k < nd; ++k) {
+        descs[k].y = (float*)(ps->s_dev + y_off[k]); descs[k].ops = (int*)(ps->s_dev + o_off[k]); descs[k].fl = (unsigned char*)(ps->s_dev + f_off[k]);
+        descs[k].res = (long long*)(ps->sd_dev + db) + k * TR_ST;
+    }
+    memcpy(ps->sd_host, descs.data(), nd * sizeof(TrDesc));
+    HIPC(hipMemcpyAsync(ps->sd_dev, ps->sd_host, nd * sizeof(TrDesc), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_trim, dim3((unsigned)nd), dim3(TR_THREADS), 0, st, (const TrDesc*)ps->sd_dev);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(ps->sd_host + db, ps->sd_dev + db, rb, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    tr.res.assign((const long long*)(ps->sd_host + db), (const long long*)(ps->sd_host + db) + nd * TR_ST);
+    for (size_t k = 0; k < nd; ++k) {
+        PsSeg& sg = segs[(size_t)tr.seg[k]]; const PsRow& r = ps->rows[(size_t)sg.row];
+        const long long* res = &tr.res[k * TR_ST];
+        const long long kept = res[TR_S_OUT] - r.s_read[TR_S_OUT];
+        if (res[TR_S_OVER] || kept < 0 || kept > (long long)descs[k].cap_ops * TR_H)
+            return set_err(Q3_HIP_ERROR, "pcm stage: the silence step of row %d kept %lld samples, its buffer takes %d hops", sg.row, kept, descs[k].cap_ops);
+        sg.dev = descs[k].y; sg.n = (size_t)kept;
+    }
+    return Q3_OK;
+}
+
+// Checks a push (every row at most once and in range — the entry points' business —, n within max_push_samples, or that and the
+// row's hold for a segment that has passed a silence step, no samples for a
 // row that was flushed), lays the rows' outputs out in the staging buffer (16-byte aligned each) and writes the descriptors.
 // Changes no row. The staging buffers (and a row's lag buffer that is not the current one) may be reallocated: no push is in
 // flight (each ends with a wait). Rows with a tempo get their stretcher's descriptor and their part of the y buffer here too.
@@ -1108,8 +1484,12 @@ q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPla
     std::vector<size_t> y_off(segs.size(), 0), z_off(segs.size(), 0), w_off, v_off; size_t y_floats = 0, z_floats = 0, w_floats = 0, v_floats = 0;
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
-        if (sg.n > ps->max_push) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, ps->max_push);
+        // (behind a silence step a segment carries what the step kept: up to what entered it and what the row had retained)
+        const size_t n_max = ps->max_push + (sg.trimmed ? tr_hold(r.s_set) : 0);
+        if (sg.n > n_max) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, n_max);
         if (r.ended && sg.n > 0) return set_err(Q3_INVALID_ARG, "pcm stage: row %d was flushed (last): q3_pcm_stage_reset or _set restarts it", sg.row);
+        if (r.s_thr != 0 && !sg.trimmed && !r.ended)
+            return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a silence step and its segment has not passed it (pcm_stage_trim)", sg.row);
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
         long long y_total = 0, k1 = 0, lv_total = 0, v_total = 0;
         const long long total = row_emitted(r, sg.n, sg.last != 0, &y_total, &k1, &lv_total, &v_total);
@@ -1309,6 +1689,11 @@ hipError_t pcm_stage_launch(const PsDesc* desc_dev, const PsPlan& plan, hipStrea
 }
 // the push has succeeded (the caller waited for its stream): the rows move on
 void pcm_stage_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const PsPlan& plan) {
+    for (size_t k = 0; k < plan.trim.seg.size(); ++k) {            // the silence steps of the pre-pass
+        PsRow& r = ps->rows[(size_t)segs[(size_t)plan.trim.seg[k]].row];
+        r.s_in += plan.trim.n_new[k]; r.s_cur ^= 1;
+        memcpy(r.s_read, &plan.trim.res[k * TR_ST], sizeof(r.s_read));
+    }
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row];
         if (r.ended || (sg.n == 0 && !sg.last)) continue;
@@ -1348,22 +1733,39 @@ static q3_status in_reserve(q3_pcm_stage* ps, size_t bytes) {
     return Q3_OK;
 }
 
-// Segments already on the device (readable by work on `st` — the caller's own stream, or nullptr for the stage's): one descriptor
-// upload, the launch, the copy of the converted bytes to the host, a wait. out_host[i] (may be null) receives plan.count[i]
-// samples of segment i. The rows move on only when all of it has succeeded.
-q3_status pcm_stage_push_dev(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, hipStream_t st, void* const* out_host, size_t* n_samples) {
-    PsPlan plan;
-    Q3C(pcm_stage_plan(ps, segs, plan));
-    for (size_t i = 0; i < segs.size(); ++i) if (n_samples) n_samples[i] = plan.count[i];
-    if (plan.desc.empty()) return Q3_OK;
-    HIPC(hipSetDevice(ps->device));
-    if (!st) { Q3C(own_stream(ps)); st = ps->st; }
+// plan.desc into the stage's own staging, for a caller that has no descriptor block of its own to carry it (or planned too late for
+// it: behind a silence step)
+// (the input staging's front holds the descriptors; q3_pcm_stage_push has put the samples behind them already)
+q3_status pcm_stage_desc_upload(q3_pcm_stage* ps, const PsPlan& plan, hipStream_t st, const PsDesc** desc_dev) {
     const size_t db = plan.desc.size() * sizeof(PsDesc);
-    // (the input staging's front holds the descriptors; q3_pcm_stage_push has put the samples behind them already)
     if (ps->in_cap < db) Q3C(in_reserve(ps, db));
     memcpy(ps->in_host, plan.desc.data(), db);
     HIPC(hipMemcpyAsync(ps->in_dev, ps->in_host, db, hipMemcpyHostToDevice, st));
-    HIPC(pcm_stage_launch((const PsDesc*)ps->in_dev, plan, st));
+    *desc_dev = (const PsDesc*)ps->in_dev;
+    return Q3_OK;
+}
+
+// Segments already on the device (readable by work on `st` — the caller's own stream, or nullptr for the stage's): one descriptor
+// upload, the launch, the copy of the converted bytes to the host, a wait. out_host[i] (may be null) receives plan.count[i]
+// samples of segment i. The rows move on only when all of it has succeeded.
+q3_status pcm_stage_push_dev(q3_pcm_stage* ps, const std::vector<PsSeg>& segs_in, hipStream_t st, void* const* out_host, size_t* n_samples) {
+    PsPlan plan;
+    std::vector<PsSeg> trimmed;                                    // (a copy only where a row has a silence step)
+    if (pcm_stage_has_trim(ps, segs_in)) {
+        HIPC(hipSetDevice(ps->device));
+        if (!st) { Q3C(own_stream(ps)); st = ps->st; }
+        trimmed = segs_in;
+        Q3C(pcm_stage_trim(ps, trimmed, st, plan));
+    }
+    const std::vector<PsSeg>& segs = trimmed.empty() ? segs_in : trimmed;
+    Q3C(pcm_stage_plan(ps, segs, plan));
+    for (size_t i = 0; i < segs.size(); ++i) if (n_samples) n_samples[i] = plan.count[i];
+    if (plan.desc.empty()) { pcm_stage_commit(ps, segs, plan); return Q3_OK; }      // (a silence step may have taken samples and kept none yet)
+    HIPC(hipSetDevice(ps->device));
+    if (!st) { Q3C(own_stream(ps)); st = ps->st; }
+    const PsDesc* desc_dev = nullptr;
+    Q3C(pcm_stage_desc_upload(ps, plan, st, &desc_dev));
+    HIPC(pcm_stage_launch(desc_dev, plan, st));
     if (plan.bytes > 0) HIPC(hipMemcpyAsync(ps->out_host, ps->out_dev, plan.bytes, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     for (size_t i = 0; i < segs.size(); ++i)
@@ -1387,6 +1789,12 @@ q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_ro
 size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last) {
     const PsRow& r = ps->rows[(size_t)row];
     if (r.ended || (n == 0 && !last)) return 0;
+    if (r.s_thr != 0) {
+        // a silence step in front: what comes is known after the pre-pass alone; the cap covers the a-priori bound
+        size_t b = 0;
+        (void)q3_pcm_stage_bound_silence(r.sr, r.tempo, r.pitch, r.level ? 1 : 0, r.s_edge, r.s_pause, n, &b);
+        return b;
+    }
     return (size_t)std::max<long long>(0, row_emitted(r, n, last != 0) - r.n_out);
 }
 

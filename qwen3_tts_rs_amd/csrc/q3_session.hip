@@ -1875,6 +1875,33 @@ extern "C" q3_status q3_session_loudness(q3_session* s, int b, float* mean_squar
     }
     return q3_pcm_stage_loudness(s->ostage, b, mean_square, gain, blocks, gated);
 }
+extern "C" q3_status q3_session_set_silence(q3_session* s, int b, int threshold_mB, int edge_ms, int pause_ms) {
+    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_silence: null session");
+    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_silence: row %d out of range (%d rows; -1 = every row)", b, s->B);
+    Q3C(pcm_stage_silence_checked("q3_session_set_silence", threshold_mB, edge_ms, pause_ms));
+    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_silence: the model has no device");
+    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
+    for (int r = b0; r < b1; ++r)
+        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
+            return set_err(Q3_INVALID_ARG, "q3_session_set_silence: row %d has streamed its first chunk: the silence step is set before it, or after q3_session_replace", r);
+    if (s->out_sil.empty()) { s->out_sil.assign((size_t)s->B * 3, 0); for (int r = 0; r < s->B; ++r) s->out_sil[(size_t)r * 3 + 2] = 20; }
+    for (int r = b0; r < b1; ++r) {
+        if (s->ostage) Q3C(q3_pcm_stage_set_silence(s->ostage, r, threshold_mB, edge_ms, pause_ms));
+        s->out_sil[(size_t)r * 3] = threshold_mB; s->out_sil[(size_t)r * 3 + 1] = edge_ms; s->out_sil[(size_t)r * 3 + 2] = pause_ms;
+    }
+    return Q3_OK;
+}
+extern "C" q3_status q3_session_silence(q3_session* s, int b, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut) {
+    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_silence: null session");
+    if (b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_silence: row %d out of range (%d rows)", b, s->B);
+    if (s->out_sil.empty() || s->out_sil[(size_t)b * 3] == 0)
+        return set_err(Q3_INVALID_ARG, "q3_session_silence: row %d has no silence step (q3_session_set_silence)", b);
+    if (!s->ostage) {                                              // nothing streamed yet
+        for (int64_t* p : {n_in, n_out, lead_cut, pause_cut, trail_cut}) if (p) *p = 0;
+        return Q3_OK;
+    }
+    return q3_pcm_stage_silence(s->ostage, b, n_in, n_out, lead_cut, pause_cut, trail_cut);
+}
 extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_host, const size_t* cap_samples, size_t* n_samples, int* done) {
     if (!s) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null session");
     if (!n_samples || !done || !out_host || !cap_samples) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null argument");
@@ -1893,6 +1920,9 @@ extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_
         for (int b = 0; b < s->B && !s->out_loud.empty(); ++b)
             if (s->out_loud[(size_t)b * 3] != Q3_LOUD_OFF)
                 Q3C(q3_pcm_stage_set_loudness(s->ostage, b, s->out_loud[(size_t)b * 3], s->out_loud[(size_t)b * 3 + 1], s->out_loud[(size_t)b * 3 + 2]));
+        for (int b = 0; b < s->B && !s->out_sil.empty(); ++b)
+            if (s->out_sil[(size_t)b * 3] != 0)
+                Q3C(q3_pcm_stage_set_silence(s->ostage, b, s->out_sil[(size_t)b * 3], s->out_sil[(size_t)b * 3 + 1], s->out_sil[(size_t)b * 3 + 2]));
     }
     s->out_started = true;
     return next_chunks(s, nullptr, cap_samples, n_samples, done, true, out_host);

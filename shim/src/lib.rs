@@ -146,6 +146,16 @@ pub mod ffi {
         pub fn q3_pcm_stage_bound_pitch(sample_rate: u32, tempo_permille: i32, cents: i32, with_level: i32, n_in: usize, n_out_max: *mut usize) -> i32;
         pub fn q3_session_set_pitch(s: *mut c_void, b: i32, cents: i32) -> i32;
         pub fn q3_batcher_ticket_pitch(b: *mut c_void, ticket: i64, cents: i32) -> i32;
+        // the output stage's silence step: edges trimmed and pauses capped per row, at the very front; threshold 0 = off
+        pub fn q3_pcm_stage_set_silence(ps: *mut c_void, row: i32, threshold_mb: i32, edge_ms: i32, pause_ms: i32) -> i32;
+        pub fn q3_pcm_stage_silence(ps: *mut c_void, row: i32, n_in: *mut i64, n_out: *mut i64, lead_cut: *mut i64, pause_cut: *mut i64, trail_cut: *mut i64) -> i32;
+        pub fn q3_pcm_stage_silence_hold(edge_ms: i32, pause_ms: i32, samples: *mut usize) -> i32;
+        pub fn q3_pcm_stage_bound_silence(sample_rate: u32, tempo_permille: i32, cents: i32, with_level: i32, edge_ms: i32, pause_ms: i32, n_in: usize, n_out_max: *mut usize) -> i32;
+        pub fn q3_silence_trim(x: *const f32, n: usize, threshold_mb: i32, edge_ms: i32, pause_ms: i32, y: *mut f32, cap: usize, n_y: *mut usize, counts: *mut i64) -> i32;
+        pub fn q3_session_set_silence(s: *mut c_void, b: i32, threshold_mb: i32, edge_ms: i32, pause_ms: i32) -> i32;
+        pub fn q3_session_silence(s: *mut c_void, b: i32, n_in: *mut i64, n_out: *mut i64, lead_cut: *mut i64, pause_cut: *mut i64, trail_cut: *mut i64) -> i32;
+        pub fn q3_batcher_ticket_silence(b: *mut c_void, ticket: i64, threshold_mb: i32, edge_ms: i32, pause_ms: i32) -> i32;
+        pub fn q3_batcher_ticket_silence_read(b: *mut c_void, ticket: i64, n_in: *mut i64, n_out: *mut i64, lead_cut: *mut i64, pause_cut: *mut i64, trail_cut: *mut i64) -> i32;
     }
 }
 use ffi::*;
