@@ -513,6 +513,46 @@ typedef struct q3_attn_step_args {
     float* kcache; float* vcache; float* out;
 } q3_attn_step_args;
 q3_status q3_attn_step(int device, const q3_attn_step_args* args);
+/* Test API: one decode-attention step in the forms a session runs (tests/test_gpu_attention_forms.py). variant 0 =
+ * launch_attn_fused (+ launch_attn_merge when n_splits > 1), 1 = launch_qknorm_rope_kv + launch_attn_decode + launch_attn_merge,
+ * 2 = launch_attn_cp, 3 = launch_attn_first2. layout 0 = one contiguous f32 cache, 1 = f32 pages, 2 = bf16 pages (variant 0 only;
+ * every cache value must be exact in bf16). The caller always passes and receives the LOGICAL cache of the selected layer,
+ * kcache / vcache [n_seq][nkv][max_seq][128] f32. For a paged layout the entry builds n_slabs (1, 2) slabs of KvPool's geometry
+ * for n_layers (1..4) layers, fills all of them with a pattern, scatters the cache into the pages page_slots [n_seq][ceil(max_seq
+ * / 128)] names (slots 0 .. 32 n_slabs - 1, each at most once) under each page's row rotation, runs the step on layer `layer`
+ * with kv_row_pages as given (1..8 and >= the pages of max_seq: the scalar table form; 0 or 9..64: one entry per lane), gathers
+ * the cache back and reports in stray[0] how many elements outside the gathered rows no longer hold the pattern, in stray[1] the
+ * offset of the first (-1: none); rot_used [n_seq][pages][nkv] receives the rotations. B counts rows, n_seq = B / rows_per_seq
+ * sequences; pos [n_seq] is a sequence's base position. rows_per_seq 1..8 with variant 1, exactly 2 (pos 0) with variant 3, else 1.
+ * Sources of q|k|v: qkv [B][(nh + 2 nkv) * 128]; or (variants 0, 2) the K-slice sums qkv_part [qkv_S][B][ld_qkv] with qkv_ssq
+ * [qkv_S][B], qkv_S 1..8, qkv_K, qkv_eps; or the folded gather: g_logits [B][g_vocab] (variants 0, 2: the row is the first
+ * maximum) or g_tok [n_seq] (variant 3: row 1 of a sequence) naming a row of g_qkv_tab [g_vocab][ld_qkv] and g_proj_tab
+ * [g_vocab][g_proj_dim], which is copied to g_x [B or n_seq][g_ldx] (in and out); variants 0 and 2 record the row in g_codes
+ * [B][g_max_frames][16] (in and out) at [g_frame_idx[b]][g_code_slot] while g_frame_idx[b] < g_max_frames. qkv may be NULL where
+ * no row is read from it. zero_buf [zero_n + zero_guard] (in and out, zero_n % 4 == 0; variants 0, 2, 3): the zero side job.
+ * Everything the kernels cannot address is refused before a device is touched (Q3_INVALID_ARG / Q3_UNSUPPORTED). */
+typedef struct q3_attn_step_ex_args {
+    int variant, layout, B, nh, nkv, n_splits, max_seq, rows_per_seq;
+    int n_layers, layer, n_slabs, kv_row_pages;
+    int qkv_S, qkv_K, g_vocab, g_proj_dim, g_ldx, g_max_frames, g_code_slot, zero_n, zero_guard;
+    float eps, qkv_eps; int reserved;
+    const int* pos; const float* qkv; const float* q_norm_w; const float* k_norm_w;
+    const float* rope_cos; const float* rope_sin;
+    float* kcache; float* vcache; float* out;
+    const int* page_slots; int* rot_used; long long* stray;
+    const float* qkv_part; const float* qkv_ssq;
+    const float* g_logits; const uint32_t* g_tok; const float* g_qkv_tab; const float* g_proj_tab;
+    float* g_x; uint32_t* g_codes; const int* g_frame_idx;
+    float* zero_buf;
+} q3_attn_step_ex_args;
+q3_status q3_attn_step_ex(int device, const q3_attn_step_ex_args* args);
+/* Test API: launch_kv_pages_to_bf16 over n_pages (1..32) pages of n_layers (1..4) layers and nkv kv heads: src [n_pages]
+ * [n_layers][2 (K, V)][nkv][128][128] f32 is scattered into slots src_slots [n_pages] of a pattern-filled f32 slab, converted
+ * into slots dst_slots [n_pages] of a pattern-filled bf16 slab (both of KvPool's geometry; slots 0..31, each at most once per
+ * list) and gathered into dst (uint16, the same shape). stray as in q3_attn_step_ex, over the destination slab; rot_used
+ * [2 (src, dst)][n_pages][nkv]. */
+q3_status q3_kv_pages_to_bf16_ex(int device, int n_layers, int nkv, int n_pages, const int* src_slots, const int* dst_slots,
+                                 const float* src, uint16_t* dst, int* rot_used, long long* stray);
 /* Test API: which kernel instance the vocoder conv family runs for a shape — the launchers' own decision function, no GPU
  * needed. Returns a ConvPath code: low 5 bits the kernel (0 refused, 1 k_conv_out1, 2 k_conv_out1_v4, 3 / 4 k_lin_small_bf16x3
  * <4 | 8>, 5..11 the k_conv_bf16x3 geometries 96x128 T_M=4 / 4 waves x 32x128 / 4 waves x 32x256 / 64x128 / 64x64 / 128x128 /

@@ -64,6 +64,16 @@ class CAttnStep(ctypes.Structure):       # q3_attn_step_args
                [(n, ctypes.c_void_p) for n in ("pos", "qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache", "out")]
 
 
+class CAttnStepEx(ctypes.Structure):     # q3_attn_step_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("variant", "layout", "B", "nh", "nkv", "n_splits", "max_seq", "rows_per_seq", "n_layers", "layer",
+                                              "n_slabs", "kv_row_pages", "qkv_S", "qkv_K", "g_vocab", "g_proj_dim", "g_ldx", "g_max_frames",
+                                              "g_code_slot", "zero_n", "zero_guard")] + \
+               [("eps", ctypes.c_float), ("qkv_eps", ctypes.c_float), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("pos", "qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache", "out", "page_slots",
+                                               "rot_used", "stray", "qkv_part", "qkv_ssq", "g_logits", "g_tok", "g_qkv_tab", "g_proj_tab", "g_x",
+                                               "g_codes", "g_frame_idx", "zero_buf")]
+
+
 class CConvEx(ctypes.Structure):         # q3_conv_ex_args
     _fields_ = [(n, ctypes.c_int32) for n in ("kind", "cin", "cout", "L", "k", "dil", "stride", "act", "planes", "packed", "resid_in_place",
                                               "snake_raw", "y2_is_x", "y_front", "y_elems")] + [("path", ctypes.POINTER(ctypes.c_int32))] + \
@@ -227,6 +237,8 @@ SYMBOLS = {
     "q3_linear": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "q3_linear_ex": (c_int, [c_int, P(CLinearEx)]),
     "q3_attn_step": (c_int, [c_int, P(CAttnStep)]),
+    "q3_attn_step_ex": (c_int, [c_int, P(CAttnStepEx)]),
+    "q3_kv_pages_to_bf16_ex": (c_int, [c_int] * 4 + [c_void_p] * 6),
     "q3_conv_path": (c_int, [c_int] * 10),
     "q3_resunit_path": (c_int, [c_int] * 6),
     "q3_conv_path_name": (c_char_p, [c_int]),

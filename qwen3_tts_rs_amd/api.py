@@ -1860,6 +1860,98 @@ def attn_step(variant: int, qkv: np.ndarray, pos, q_norm_w: np.ndarray, k_norm_w
     return out, kc, vc
 
 
+def attn_step_ex(variant: int, pos, q_norm_w: np.ndarray, k_norm_w: np.ndarray, eps: float, rope_cos: np.ndarray, rope_sin: np.ndarray,
+                 kcache: np.ndarray, vcache: np.ndarray, nh: int, nkv: int, n_splits: int = 1, *, qkv: Optional[np.ndarray] = None,
+                 B: Optional[int] = None, layout: int = 0, rows_per_seq: int = 1, n_layers: int = 1, layer: int = 0, n_slabs: int = 1,
+                 kv_row_pages: int = 0, page_slots=None, qkv_part: Optional[np.ndarray] = None, qkv_ssq: Optional[np.ndarray] = None,
+                 qkv_K: int = 0, qkv_eps: float = 0.0, g_logits: Optional[np.ndarray] = None, g_tok=None,
+                 g_qkv_tab: Optional[np.ndarray] = None, g_proj_tab: Optional[np.ndarray] = None, g_x: Optional[np.ndarray] = None,
+                 g_codes: Optional[np.ndarray] = None, g_frame_idx=None, g_code_slot: int = 0, zero_buf: Optional[np.ndarray] = None,
+                 zero_n: int = 0, device: int = 0) -> dict:
+    """q3_attn_step_ex: one decode-attention step in the forms a session runs (parity tests; include/q3tts.h describes the
+    arguments). kcache / vcache are the LOGICAL caches [n_seq][nkv][max_seq][128] f32 whatever the layout (0 contiguous, 1 f32 pages,
+    2 bf16 pages). Returns a dict: out [B][nh*128], kcache, vcache (copies with the step's rows appended), stray / stray_at (paged
+    layouts: elements outside the cache rows that changed, and the first one's offset), rot_used [n_seq][pages][nkv], and copies
+    of g_x / g_codes / zero_buf as the step left them. Raises Q3Error (1 / 7) for what the entry refuses."""
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    f32 = lambda arr: np.ascontiguousarray(arr, dtype=np.float32)
+    kc = np.array(kcache, dtype=np.float32, order="C"); vc = np.array(vcache, dtype=np.float32, order="C")
+    assert kc.ndim == 4 and kc.shape[3] == 128 and kc.shape[1] == nkv and vc.shape == kc.shape
+    n_seq, max_seq = kc.shape[0], kc.shape[2]
+    ld = (nh + 2 * nkv) * 128
+    a = _lib.CAttnStepEx()
+    keep = []
+    if qkv is not None:
+        qkv = f32(qkv); assert qkv.ndim == 2 and qkv.shape[1] == ld
+        B = qkv.shape[0] if B is None else B; assert qkv.shape[0] == B
+        a.qkv = ptr(qkv)
+    if qkv_part is not None:
+        qkv_part = f32(qkv_part); qkv_ssq = f32(qkv_ssq); assert qkv_part.ndim == 3 and qkv_part.shape[2] == ld
+        B = qkv_part.shape[1] if B is None else B
+        assert qkv_part.shape[1] == B and qkv_ssq.shape == qkv_part.shape[:2]
+        a.qkv_part, a.qkv_ssq, a.qkv_S, a.qkv_K, a.qkv_eps = ptr(qkv_part), ptr(qkv_ssq), qkv_part.shape[0], qkv_K, qkv_eps
+    if g_logits is not None:
+        g_logits = f32(g_logits); assert g_logits.ndim == 2
+        B = g_logits.shape[0] if B is None else B; assert g_logits.shape[0] == B
+        a.g_logits = ptr(g_logits)
+    assert B is not None, "no source of q|k|v"
+    pos = np.ascontiguousarray(pos, dtype=np.int32); assert pos.shape == (n_seq,)
+    qw = f32(q_norm_w); kw = f32(k_norm_w); rc = f32(rope_cos); rs = f32(rope_sin)
+    assert qw.shape == (128,) and kw.shape == (128,) and rc.shape == (max_seq, 64) and rs.shape == (max_seq, 64)
+    out = np.zeros((B, nh * 128), dtype=np.float32)
+    n_pg = (max_seq + 127) // 128
+    stray = np.array([0, -1], dtype=np.int64)
+    rot = np.full((n_seq, n_pg, nkv), -1, dtype=np.int32)
+    a.variant, a.layout, a.B, a.nh, a.nkv, a.n_splits, a.max_seq, a.rows_per_seq = variant, layout, B, nh, nkv, n_splits, max_seq, rows_per_seq
+    a.n_layers, a.layer, a.n_slabs, a.kv_row_pages, a.eps = n_layers, layer, n_slabs, kv_row_pages, eps
+    a.pos, a.q_norm_w, a.k_norm_w, a.rope_cos, a.rope_sin = ptr(pos), ptr(qw), ptr(kw), ptr(rc), ptr(rs)
+    a.kcache, a.vcache, a.out, a.stray, a.rot_used = ptr(kc), ptr(vc), ptr(out), ptr(stray), ptr(rot)
+    if page_slots is not None:
+        page_slots = np.ascontiguousarray(page_slots, dtype=np.int32); assert page_slots.shape == (n_seq, n_pg)
+        a.page_slots = ptr(page_slots)
+    res = dict(out=out, kcache=kc, vcache=vc, rot_used=rot)
+    if g_logits is not None or g_tok is not None:
+        tq = f32(g_qkv_tab); tp = f32(g_proj_tab); gx = np.array(g_x, dtype=np.float32, order="C")
+        assert tq.ndim == 2 and tq.shape[1] == ld and tp.ndim == 2 and tp.shape[0] == tq.shape[0] and gx.ndim == 2
+        if g_logits is not None:
+            assert g_logits.shape[1] == tq.shape[0]
+        keep += [tq, tp]
+        a.g_qkv_tab, a.g_proj_tab, a.g_x, a.g_vocab, a.g_proj_dim, a.g_ldx = ptr(tq), ptr(tp), ptr(gx), tq.shape[0], tp.shape[1], gx.shape[1]
+        res["g_x"] = gx
+    if g_logits is not None:
+        gc = np.array(g_codes, dtype=np.uint32, order="C"); gf = np.ascontiguousarray(g_frame_idx, dtype=np.int32)
+        assert gc.ndim == 3 and gc.shape[0] == B and gc.shape[2] == 16 and gf.shape == (B,)
+        keep.append(gf)
+        a.g_codes, a.g_frame_idx, a.g_max_frames, a.g_code_slot = ptr(gc), ptr(gf), gc.shape[1], g_code_slot
+        res["g_codes"] = gc
+    if g_tok is not None:
+        gt = np.ascontiguousarray(g_tok, dtype=np.uint32); assert gt.shape == (n_seq,)
+        keep.append(gt); a.g_tok = ptr(gt)
+    if zero_buf is not None:
+        zb = np.array(zero_buf, dtype=np.float32, order="C"); assert zb.ndim == 1 and zb.size >= zero_n
+        a.zero_buf, a.zero_n, a.zero_guard = ptr(zb), zero_n, zb.size - zero_n
+        res["zero_buf"] = zb
+    check(lib.q3_attn_step_ex(device, ctypes.byref(a)))
+    res["stray"], res["stray_at"] = int(stray[0]), int(stray[1])
+    return res
+
+
+def kv_pages_to_bf16_ex(src: np.ndarray, src_slots, dst_slots, device: int = 0):
+    """q3_kv_pages_to_bf16_ex: launch_kv_pages_to_bf16 over src [n_pages][n_layers][2][nkv][128][128] f32, scattered into the
+    f32 slots src_slots and converted into the bf16 slots dst_slots (parity tests). Returns (dst uint16 of the same shape, stray,
+    stray_at, rot_used [2 (src, dst)][n_pages][nkv])."""
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    assert src.ndim == 6 and src.shape[2] == 2 and src.shape[4:] == (128, 128)
+    n_pages, n_layers, nkv = src.shape[0], src.shape[1], src.shape[3]
+    ss = np.ascontiguousarray(src_slots, dtype=np.int32); ds = np.ascontiguousarray(dst_slots, dtype=np.int32)
+    assert ss.shape == (n_pages,) and ds.shape == (n_pages,)
+    dst = np.zeros(src.shape, dtype=np.uint16)
+    rot = np.full((2, n_pages, nkv), -1, dtype=np.int32); stray = np.array([0, -1], dtype=np.int64)
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    check(lib.q3_kv_pages_to_bf16_ex(device, n_layers, nkv, n_pages, ptr(ss), ptr(ds), ptr(src), ptr(dst), ptr(rot), ptr(stray)))
+    return dst, int(stray[0]), int(stray[1]), rot
+
+
 def conv_path(cout: int, cin: int, L: int, k: int, dil: int = 1, phases: int = 1, packed: bool = True, has_resid: bool = False,
               planes: int = 3, aligned16: bool = True) -> int:
     """q3_conv_path: the ConvPath code launch_conv1d (phases == 1) / launch_transconv1d_taps (phases = stride, k = taps) picks for a

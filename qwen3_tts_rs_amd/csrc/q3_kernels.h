@@ -191,7 +191,7 @@ struct AttnArgs {
 // the workgroups of a decode-attention launch all read the same position range of their sequences at the same time — without
 // the rotation the 64 (sequence, head) streams of a B = 8 launch walk addresses that are equal modulo 64 KB (the contiguous
 // layout staggers them by max_seq * 512 B) and crowd the same memory channels.
-__device__ __forceinline__ int kv_rot(unsigned long long page, int kvh) {
+__host__ __device__ __forceinline__ int kv_rot(unsigned long long page, int kvh) {      // (host: the test entries' scatter / gather)
     const unsigned h = (unsigned)(page >> 19);            // slot number of the page within its slab region (512 KB apart at 8 KV heads)
     return (int)((kvh * 16 + (h & 15) * 8 + ((h >> 4) & 7)) & (KV_PAGE_POS - 1));
 }

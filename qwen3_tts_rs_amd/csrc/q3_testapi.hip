@@ -296,6 +296,316 @@ extern "C" q3_status q3_attn_step(int device, const q3_attn_step_args* p) {
     return Q3_OK;
 }
 
+// ---- decode attention in the forms a session runs (tests/test_gpu_attention_forms.py) ----
+// Slabs of KvPool's geometry for a test entry: nothing is taken from the pool object, it only answers run_floats / v_delta() /
+// layer_stride() / slab_bytes(), so that the layout under test is the engine's. Every 32-bit word of a slab starts as a hash of its
+// index; cache rows are scattered over that, and whatever differs from the image afterwards outside those rows is a stray write.
+namespace {
+struct TestSlabs {
+    KvPool geo;
+    std::vector<char*> dev;                          // one device block per slab (owned by the caller's DevPool)
+    std::vector<std::vector<uint32_t>> img;          // what the slab holds (host)
+    static uint32_t pattern(size_t slab, size_t word) {
+        uint32_t x = (uint32_t)(word + slab * 0x632be5abu) * 2654435761u + 0x9e3779b9u;
+        x ^= x >> 15; x *= 0x85ebca6bu; x ^= x >> 13;
+        return x;
+    }
+    void shape(int n_layers, int nkv, size_t elem_bytes) { geo.n_layers = n_layers; geo.run_floats = (size_t)nkv * KV_PAGE_POS * HEAD_DIM; geo.elem_bytes = elem_bytes; }
+    hipError_t add_slab(DevPool& pool) {             // (allocation only: a page's rotation depends on its address, so the images follow once all slabs exist)
+        char* d = nullptr;
+        const hipError_t e = pool.alloc(&d, geo.slab_bytes());
+        if (e == hipSuccess) dev.push_back(d);
+        return e;
+    }
+    void fill_pattern() {
+        const size_t words = geo.slab_bytes() / 4;
+        for (size_t s = 0; s < dev.size(); ++s) {
+            img.emplace_back(words);
+            for (size_t w = 0; w < words; ++w) img[s][w] = pattern(s, w);
+        }
+    }
+    size_t slab_elems() const { return geo.slab_bytes() / geo.elem_bytes; }
+    unsigned long long page(int slot) const {        // a page is named by the address of its layer-0 K run
+        return (unsigned long long)(uintptr_t)dev[(size_t)(slot / KvPool::SLAB_SLOTS)] + (size_t)(slot % KvPool::SLAB_SLOTS) * geo.run_floats * geo.elem_bytes;
+    }
+    // element offset, within its slab, of the row that holds position p of (slot, layer, K | V, kv head)
+    size_t row_elem(int slot, int layer, int is_v, int kvh, int p) const {
+        return (size_t)layer * geo.layer_stride() + (is_v ? geo.v_delta() : 0) + (size_t)(slot % KvPool::SLAB_SLOTS) * geo.run_floats +
+               ((size_t)kvh * KV_PAGE_POS + (size_t)((p + kv_rot(page(slot), kvh)) & (KV_PAGE_POS - 1))) * HEAD_DIM;
+    }
+    // one row of 128 values between a host f32 row and an image (f32 elements, or bf16 = the high halves)
+    void put_row(std::vector<std::vector<uint32_t>>& im, int slot, size_t elem, const float* row) const {
+        char* base = reinterpret_cast<char*>(im[(size_t)(slot / KvPool::SLAB_SLOTS)].data());
+        if (geo.elem_bytes == 4) memcpy(base + elem * 4, row, HEAD_DIM * 4);
+        else for (int d = 0; d < HEAD_DIM; ++d) { uint32_t u; memcpy(&u, row + d, 4); const uint16_t h = (uint16_t)(u >> 16); memcpy(base + (elem + d) * 2, &h, 2); }
+    }
+    void get_row(const std::vector<std::vector<uint32_t>>& im, int slot, size_t elem, float* row) const {
+        const char* base = reinterpret_cast<const char*>(im[(size_t)(slot / KvPool::SLAB_SLOTS)].data());
+        if (geo.elem_bytes == 4) memcpy(row, base + elem * 4, HEAD_DIM * 4);
+        else for (int d = 0; d < HEAD_DIM; ++d) { uint16_t h; memcpy(&h, base + (elem + d) * 2, 2); const uint32_t u = (uint32_t)h << 16; memcpy(row + d, &u, 4); }
+    }
+    void copy_row(std::vector<std::vector<uint32_t>>& to, const std::vector<std::vector<uint32_t>>& from, int slot, size_t elem) const {
+        const size_t s = (size_t)(slot / KvPool::SLAB_SLOTS);
+        memcpy(reinterpret_cast<char*>(to[s].data()) + elem * geo.elem_bytes, reinterpret_cast<const char*>(from[s].data()) + elem * geo.elem_bytes, HEAD_DIM * geo.elem_bytes);
+    }
+    hipError_t upload() const {
+        for (size_t s = 0; s < dev.size(); ++s) { const hipError_t e = q3_hipMemcpy(dev[s], img[s].data(), geo.slab_bytes(), hipMemcpyHostToDevice); if (e != hipSuccess) return e; }
+        return hipSuccess;
+    }
+    hipError_t download(std::vector<std::vector<uint32_t>>& got) const {
+        got.resize(dev.size());
+        for (size_t s = 0; s < dev.size(); ++s) {
+            got[s].resize(img[s].size());
+            const hipError_t e = q3_hipMemcpy(got[s].data(), dev[s], geo.slab_bytes(), hipMemcpyDeviceToHost); if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    // elements of `got` that differ from the image: count and the first offset (slab * slab_elems + element)
+    void strays(const std::vector<std::vector<uint32_t>>& got, long long* out) const {
+        long long n = 0, first = -1;
+        for (size_t s = 0; s < img.size(); ++s) {
+            if (memcmp(img[s].data(), got[s].data(), geo.slab_bytes()) == 0) continue;
+            const char* a = reinterpret_cast<const char*>(img[s].data()); const char* b = reinterpret_cast<const char*>(got[s].data());
+            for (size_t e = 0; e < slab_elems(); ++e)
+                if (memcmp(a + e * geo.elem_bytes, b + e * geo.elem_bytes, geo.elem_bytes) != 0) { if (first < 0) first = (long long)(s * slab_elems() + e); ++n; }
+        }
+        out[0] = n; out[1] = first;
+    }
+};
+bool slots_ok(const int* slots, int n, int limit) {
+    std::vector<char> seen((size_t)limit, 0);
+    for (int i = 0; i < n; ++i) { if (slots[i] < 0 || slots[i] >= limit || seen[(size_t)slots[i]]) return false; seen[(size_t)slots[i]] = 1; }
+    return true;
+}
+}  // namespace
+
+// One decode-attention step through a complete AttnArgs in any form lm_layer builds: contiguous / paged f32 / paged bf16 cache,
+// q|k|v from a row, from K-slice sums or from a table row (folded gather), several rows per sequence, the zero side job. The
+// launches are the session's own for the variant — a launcher's refusal is a status, never another kernel in its place.
+extern "C" q3_status q3_attn_step_ex(int device, const q3_attn_step_ex_args* p) {
+    if (!p || !p->pos || !p->q_norm_w || !p->k_norm_w || !p->rope_cos || !p->rope_sin || !p->kcache || !p->vcache || !p->out)
+        return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: null argument");
+    const int B = p->B, nh = p->nh, nkv = p->nkv, variant = p->variant, layout = p->layout, max_seq = p->max_seq;
+    if (variant < 0 || variant > 3 || layout < 0 || layout > 2) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: variant 0..3, layout 0..2");
+    if (B < 1 || B > Q3_MAX_BATCH || nkv < 1 || nh < nkv || nh > 64 || nh % nkv || max_seq < 1 || max_seq > (1 << 20) || p->n_splits < 1 || p->n_splits > MAX_SPLITS)
+        return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: bad shape");
+    const int nrep = nh / nkv;
+    if (nrep != 1 && nrep != 2 && nrep != 4) return set_err(Q3_UNSUPPORTED, "q3_attn_step_ex: heads / kv heads must be 1, 2 or 4");
+    const int rps = p->rows_per_seq <= 0 ? 1 : p->rows_per_seq;
+    if (rps > 8 || B % rps) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: rows_per_seq 1..8, a divisor of B");
+    if (rps > 1 && (variant == 0 || variant == 2)) return set_err(Q3_UNSUPPORTED, "q3_attn_step_ex: variants 0 and 2 take one row per sequence");
+    if (variant == 3 && rps != 2) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: variant 3 takes exactly two rows per sequence");
+    if (layout != 0 && variant >= 2) return set_err(Q3_UNSUPPORTED, "q3_attn_step_ex: variants 2 and 3 run on a contiguous cache only");
+    if (layout == 2 && variant != 0) return set_err(Q3_UNSUPPORTED, "q3_attn_step_ex: only the one-launch kernel reads bf16 pages");
+    const int n_seq = B / rps;
+    for (int s = 0; s < n_seq; ++s)
+        if (p->pos[s] < 0 || p->pos[s] > max_seq - rps) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: pos[%d] = %d (+ %d rows) outside the cache (%d)", s, p->pos[s], rps, max_seq);
+    if (variant == 2) {
+        for (int b = 1; b < B; ++b) if (p->pos[b] != p->pos[0]) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: variant 2 takes one position for every row");
+        if (p->n_splits != 1 || p->pos[0] >= 16 || max_seq >= 256) return set_err(Q3_UNSUPPORTED, "q3_attn_step_ex: arguments outside launch_attn_cp (one split, position < 16, max_seq < 256)");
+    }
+    if (variant == 3) {
+        for (int s = 0; s < n_seq; ++s) if (p->pos[s] != 0) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: variant 3 starts from an empty cache (pos 0)");
+        if (p->n_splits != 1) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: variant 3 has no splits");
+    }
+    const int n_pg = (max_seq + KV_PAGE_POS - 1) / KV_PAGE_POS;
+    const size_t cn = (size_t)n_seq * nkv * max_seq * HEAD_DIM;
+    if (layout != 0) {
+        if (max_seq > KV_MAX_PAGES * KV_PAGE_POS) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: a paged row holds at most %d positions", KV_MAX_PAGES * KV_PAGE_POS);
+        if (p->n_layers < 1 || p->n_layers > 4 || p->layer < 0 || p->layer >= p->n_layers || p->n_slabs < 1 || p->n_slabs > 2)
+            return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: n_layers 1..4, layer inside them, n_slabs 1..2");
+        if (!p->page_slots || !p->stray) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: a paged layout needs page_slots and stray");
+        if (p->kv_row_pages < 0 || p->kv_row_pages > KV_MAX_PAGES || (p->kv_row_pages >= 1 && p->kv_row_pages <= 8 && p->kv_row_pages < n_pg))
+            return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: kv_row_pages 0..%d, and from 1 to 8 no fewer than the pages of max_seq (%d)", KV_MAX_PAGES, n_pg);
+        if (!slots_ok(p->page_slots, n_seq * n_pg, KvPool::SLAB_SLOTS * p->n_slabs))
+            return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: page_slots must be distinct slots of 0 .. %d", KvPool::SLAB_SLOTS * p->n_slabs - 1);
+        if (layout == 2)
+            for (size_t i = 0; i < cn; ++i) {
+                uint32_t a, b; memcpy(&a, p->kcache + i, 4); memcpy(&b, p->vcache + i, 4);
+                if ((a | b) & 0xffffu) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: cache element %zu is not exact in bf16", i);
+            }
+    }
+    const bool slices = p->qkv_part != nullptr, g_l = p->g_logits != nullptr, g_t = p->g_tok != nullptr;
+    if (slices && (variant == 1 || variant == 3)) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: slice sums belong to variants 0 and 2");
+    if (g_l && (variant == 1 || variant == 3)) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: g_logits belongs to variants 0 and 2");
+    if (g_t && variant != 3) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: g_tok belongs to variant 3");
+    if (slices && g_l) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: slice sums and the folded gather exclude each other");
+    if (slices && (!p->qkv_ssq || p->qkv_S < 1 || p->qkv_S > 8 || p->qkv_K < 1)) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: slice sums need qkv_ssq, qkv_S 1..8, qkv_K >= 1");
+    if (g_l || g_t) {
+        if (!p->g_qkv_tab || !p->g_proj_tab || !p->g_x) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: the gather needs g_qkv_tab, g_proj_tab and g_x");
+        if (p->g_vocab < 1 || p->g_vocab > 65536 || p->g_proj_dim < 4 || p->g_proj_dim % 4 || p->g_ldx < p->g_proj_dim || p->g_ldx % 4 || p->g_ldx > 65536)
+            return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: g_vocab 1..65536, g_proj_dim and g_ldx multiples of 4, g_proj_dim <= g_ldx <= 65536");
+    }
+    if (g_l) {
+        if (!p->g_codes || !p->g_frame_idx || p->g_max_frames < 1 || p->g_max_frames > 4096 || p->g_code_slot < 0 || p->g_code_slot > 15)
+            return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: g_logits needs g_codes, g_frame_idx, g_max_frames 1..4096, g_code_slot 0..15");
+        for (int b = 0; b < B; ++b) if (p->g_frame_idx[b] < 0) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: g_frame_idx[%d] < 0", b);
+    }
+    if (g_t) for (int s = 0; s < n_seq; ++s) if (p->g_tok[s] >= (uint32_t)p->g_vocab) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: g_tok[%d] outside the table", s);
+    if (!p->qkv && !slices && !g_l) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: null argument (qkv)");
+    if (p->zero_n < 0 || p->zero_n % 4 || p->zero_guard < 0 || (p->zero_n > 0 && !p->zero_buf)) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: zero_n must be a multiple of 4 with a buffer");
+    if (p->zero_n > 0 && variant == 1) return set_err(Q3_INVALID_ARG, "q3_attn_step_ex: the three-launch path has no zero side job");
+
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const int ld_qkv = (nh + 2 * nkv) * HEAD_DIM, QD = nh * HEAD_DIM;
+    const size_t rn = (size_t)max_seq * 64;
+    int* pos; float *qkv = nullptr, *qw, *kw, *rc, *rs, *kv = nullptr, *qbuf, *part, *out;
+    unsigned long long* table = nullptr;
+    TestSlabs slabs;
+    // (slab, table, slab: with two slabs the pages of a row lie on both sides of the table the kernel forms their addresses from)
+    if (layout != 0) {
+        slabs.shape(p->n_layers, nkv, layout == 2 ? 2 : 4);
+        for (int s = 0; s < p->n_slabs; ++s) {
+            if (s == 1) HIPC(pool.alloc(&table, (size_t)n_seq * KV_MAX_PAGES));
+            HIPC(slabs.add_slab(pool));
+        }
+        if (!table) HIPC(pool.alloc(&table, (size_t)n_seq * KV_MAX_PAGES));
+        if (slabs.geo.v_delta() > 0x7fffffffu) return set_err(Q3_UNSUPPORTED, "q3_attn_step_ex: K -> V distance beyond the kernels' 32-bit form");
+    } else HIPC(pool.alloc(&kv, 2 * cn));       // K and V in one block: their distance fits every kernel's 32-bit form
+    HIPC(pool.alloc(&pos, (size_t)n_seq)); HIPC(pool.alloc(&qw, (size_t)HEAD_DIM)); HIPC(pool.alloc(&kw, (size_t)HEAD_DIM));
+    HIPC(pool.alloc(&rc, rn)); HIPC(pool.alloc(&rs, rn));
+    HIPC(pool.alloc(&qbuf, (size_t)B * QD)); HIPC(pool.alloc(&part, (size_t)B * nh * p->n_splits * PART_STRIDE)); HIPC(pool.alloc(&out, (size_t)B * QD));
+    HIPC(q3_hipMemcpy(pos, p->pos, (size_t)n_seq * 4, hipMemcpyHostToDevice));
+    if (p->qkv) { HIPC(pool.alloc(&qkv, (size_t)B * ld_qkv)); HIPC(q3_hipMemcpy(qkv, p->qkv, (size_t)B * ld_qkv * 4, hipMemcpyHostToDevice)); }
+    HIPC(q3_hipMemcpy(qw, p->q_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kw, p->k_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(rc, p->rope_cos, rn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(rs, p->rope_sin, rn * 4, hipMemcpyHostToDevice));
+    auto cache_row = [&](float* c, int s, int g, int pp) { return c + (((size_t)s * nkv + g) * max_seq + pp) * HEAD_DIM; };
+    auto each_row = [&](auto&& f) {             // every (sequence, kv head, position, K | V) of the logical cache with its slot and element offset
+        for (int s = 0; s < n_seq; ++s) for (int g = 0; g < nkv; ++g) for (int pp = 0; pp < max_seq; ++pp) for (int v = 0; v < 2; ++v) {
+            const int slot = p->page_slots[(size_t)s * n_pg + pp / KV_PAGE_POS];
+            f(slot, slabs.row_elem(slot, p->layer, v, g, pp), cache_row(v ? p->vcache : p->kcache, s, g, pp));
+        }
+    };
+    if (layout != 0) {
+        slabs.fill_pattern();
+        each_row([&](int slot, size_t elem, float* row) { slabs.put_row(slabs.img, slot, elem, row); });
+        HIPC(slabs.upload());
+        std::vector<unsigned long long> tab((size_t)n_seq * KV_MAX_PAGES);
+        for (int s = 0; s < n_seq; ++s)
+            for (int i = 0; i < KV_MAX_PAGES; ++i) tab[(size_t)s * KV_MAX_PAGES + i] = slabs.page(p->page_slots[(size_t)s * n_pg + (i < n_pg ? i : 0)]);      // beyond the row's pages: its first, as a session leaves them
+        HIPC(q3_hipMemcpy(table, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+        if (p->rot_used)
+            for (int s = 0; s < n_seq; ++s) for (int i = 0; i < n_pg; ++i) for (int g = 0; g < nkv; ++g)
+                p->rot_used[((size_t)s * n_pg + i) * nkv + g] = kv_rot(slabs.page(p->page_slots[(size_t)s * n_pg + i]), g);
+    } else {
+        HIPC(q3_hipMemcpy(kv, p->kcache, cn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kv + cn, p->vcache, cn * 4, hipMemcpyHostToDevice));
+    }
+    auto up = [&](const void* h, size_t bytes, void** d) -> q3_status {
+        char* q; HIPC(pool.alloc(&q, bytes)); HIPC(q3_hipMemcpy(q, h, bytes, hipMemcpyHostToDevice)); *d = q;
+        return Q3_OK;
+    };
+    AttnArgs t{};
+    t.qkv = qkv; t.ld_qkv = ld_qkv; t.q_norm_w = qw; t.k_norm_w = kw; t.eps = p->eps; t.rope_cos = rc; t.rope_sin = rs;
+    t.pos_dev = variant >= 2 ? nullptr : pos; t.pos_static = variant == 2 ? p->pos[0] : 0;
+    t.max_seq = max_seq; t.qbuf = qbuf; t.part = part; t.out = out; t.ld_out = QD;
+    t.B = B; t.nh = nh; t.nkv = nkv; t.n_splits = p->n_splits; t.rows_per_seq = rps;
+    if (layout != 0) {
+        t.kv_pages = table; t.kv_layer_off = (size_t)p->layer * slabs.geo.layer_stride(); t.kv_vdelta = slabs.geo.v_delta();
+        t.kv_row_pages = p->kv_row_pages; t.kv_bf16 = layout == 2 ? 1 : 0;
+    } else { t.kcache = kv; t.vcache = kv + cn; }
+    void* d = nullptr;
+    const size_t gx_rows = variant == 3 ? (size_t)n_seq : (size_t)B, zn = (size_t)p->zero_n + p->zero_guard;
+    if (slices) {
+        Q3C(up(p->qkv_part, (size_t)p->qkv_S * B * ld_qkv * 4, &d)); t.qkv_part = (const float*)d;
+        Q3C(up(p->qkv_ssq, (size_t)p->qkv_S * B * 4, &d)); t.qkv_ssq = (const float*)d;
+        t.qkv_S = p->qkv_S; t.qkv_K = p->qkv_K; t.qkv_eps = p->qkv_eps;
+    }
+    if (g_l || g_t) {
+        Q3C(up(p->g_qkv_tab, (size_t)p->g_vocab * ld_qkv * 4, &d)); t.g_qkv_tab = (const float*)d;
+        Q3C(up(p->g_proj_tab, (size_t)p->g_vocab * p->g_proj_dim * 4, &d)); t.g_proj_tab = (const float*)d;
+        Q3C(up(p->g_x, gx_rows * p->g_ldx * 4, &d)); t.g_x = (float*)d;
+        t.g_vocab = p->g_vocab; t.g_proj_dim = p->g_proj_dim; t.g_ldx = p->g_ldx;
+    }
+    if (g_l) {
+        Q3C(up(p->g_logits, (size_t)B * p->g_vocab * 4, &d)); t.g_logits = (const float*)d;
+        Q3C(up(p->g_codes, (size_t)B * p->g_max_frames * 16 * 4, &d)); t.g_codes = (uint32_t*)d;
+        Q3C(up(p->g_frame_idx, (size_t)B * 4, &d)); t.g_frame_idx = (const int*)d;
+        t.g_max_frames = p->g_max_frames; t.g_code_slot = p->g_code_slot;
+    }
+    if (g_t) { Q3C(up(p->g_tok, (size_t)n_seq * 4, &d)); t.g_tok = (const uint32_t*)d; }
+    if (p->zero_n > 0) { Q3C(up(p->zero_buf, zn * 4, &d)); t.zero = (float*)d; t.zero_n = p->zero_n; }
+    if (variant == 2 && !attn_cp_ok(t)) return set_err(Q3_UNSUPPORTED, "q3_attn_step_ex: arguments outside launch_attn_cp");
+    HIPC(q3_hipDeviceSynchronize());
+    hipError_t e = hipSuccess;
+    if (variant == 0) {
+        e = launch_attn_fused(t, 0);
+        if (e == hipSuccess && p->n_splits > 1) e = launch_attn_merge(t, 0);
+    } else if (variant == 1) {
+        e = launch_qknorm_rope_kv(t, 0);
+        if (e == hipSuccess) e = launch_attn_decode(t, 0);
+        if (e == hipSuccess) e = launch_attn_merge(t, 0);
+    } else if (variant == 2) e = launch_attn_cp(t, 0);
+    else e = launch_attn_first2(t, 0);
+    if (e == hipErrorInvalidValue || e == hipErrorNotSupported) {
+        (void)hipGetLastError();
+        (void)q3_hipDeviceSynchronize();
+        return set_err(Q3_UNSUPPORTED, "q3_attn_step_ex: the launcher refused variant=%d layout=%d nh=%d nkv=%d splits=%d rows_per_seq=%d (%s)", variant, layout, nh, nkv,
+                       p->n_splits, rps, hipGetErrorString(e));
+    }
+    HIPC(e);
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->out, out, (size_t)B * QD * 4, hipMemcpyDeviceToHost));
+    if (layout != 0) {
+        std::vector<std::vector<uint32_t>> got;
+        HIPC(slabs.download(got));
+        each_row([&](int slot, size_t elem, float* row) { slabs.get_row(got, slot, elem, row); slabs.copy_row(slabs.img, got, slot, elem); });
+        slabs.strays(got, p->stray);
+    } else {
+        HIPC(q3_hipMemcpy(p->kcache, kv, cn * 4, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(p->vcache, kv + cn, cn * 4, hipMemcpyDeviceToHost));
+        if (p->stray) { p->stray[0] = 0; p->stray[1] = -1; }
+    }
+    if (t.g_x) HIPC(q3_hipMemcpy(p->g_x, t.g_x, gx_rows * p->g_ldx * 4, hipMemcpyDeviceToHost));
+    if (t.g_codes) HIPC(q3_hipMemcpy(p->g_codes, t.g_codes, (size_t)B * p->g_max_frames * 16 * 4, hipMemcpyDeviceToHost));
+    if (t.zero) HIPC(q3_hipMemcpy(p->zero_buf, t.zero, zn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+// launch_kv_pages_to_bf16 between a slab of the f32 pool's geometry and one of the bf16 pool's
+extern "C" q3_status q3_kv_pages_to_bf16_ex(int device, int n_layers, int nkv, int n_pages, const int* src_slots, const int* dst_slots,
+                                            const float* src, uint16_t* dst, int* rot_used, long long* stray) {
+    if (!src_slots || !dst_slots || !src || !dst || !stray) return set_err(Q3_INVALID_ARG, "q3_kv_pages_to_bf16_ex: null argument");
+    if (n_layers < 1 || n_layers > 4 || nkv < 1 || nkv > 8 || n_pages < 1 || n_pages > KvPool::SLAB_SLOTS)
+        return set_err(Q3_INVALID_ARG, "q3_kv_pages_to_bf16_ex: bad shape (n_layers 1..4, nkv 1..8, n_pages 1..%d)", KvPool::SLAB_SLOTS);
+    if (!slots_ok(src_slots, n_pages, KvPool::SLAB_SLOTS) || !slots_ok(dst_slots, n_pages, KvPool::SLAB_SLOTS))
+        return set_err(Q3_INVALID_ARG, "q3_kv_pages_to_bf16_ex: the slots of a list must be distinct slots of 0 .. %d", KvPool::SLAB_SLOTS - 1);
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    TestSlabs a, b;
+    a.shape(n_layers, nkv, 4); b.shape(n_layers, nkv, 2);
+    HIPC(a.add_slab(pool)); HIPC(b.add_slab(pool));
+    a.fill_pattern(); b.fill_pattern();
+    auto each_row = [&](auto&& f) {
+        for (int pg = 0; pg < n_pages; ++pg) for (int l = 0; l < n_layers; ++l) for (int v = 0; v < 2; ++v) for (int g = 0; g < nkv; ++g) for (int pp = 0; pp < KV_PAGE_POS; ++pp)
+            f(pg, l, v, g, pp, (((((size_t)pg * n_layers + l) * 2 + v) * nkv + g) * KV_PAGE_POS + pp) * HEAD_DIM);
+    };
+    each_row([&](int pg, int l, int v, int g, int pp, size_t at) { a.put_row(a.img, src_slots[pg], a.row_elem(src_slots[pg], l, v, g, pp), src + at); });
+    HIPC(a.upload()); HIPC(b.upload());
+    std::vector<unsigned long long> lists((size_t)2 * n_pages);
+    for (int pg = 0; pg < n_pages; ++pg) { lists[(size_t)pg] = a.page(src_slots[pg]); lists[(size_t)n_pages + pg] = b.page(dst_slots[pg]); }
+    if (rot_used)
+        for (int pg = 0; pg < n_pages; ++pg) for (int g = 0; g < nkv; ++g) {
+            rot_used[(size_t)pg * nkv + g] = kv_rot(lists[(size_t)pg], g);
+            rot_used[((size_t)n_pages + pg) * nkv + g] = kv_rot(lists[(size_t)n_pages + pg], g);
+        }
+    unsigned long long* dl; HIPC(pool.alloc(&dl, lists.size()));
+    HIPC(q3_hipMemcpy(dl, lists.data(), lists.size() * 8, hipMemcpyHostToDevice));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_kv_pages_to_bf16(dl, dl + n_pages, n_pages, n_layers, nkv, a.geo.layer_stride(), a.geo.v_delta(), 0));
+    HIPC(q3_hipDeviceSynchronize());
+    std::vector<std::vector<uint32_t>> got;
+    HIPC(b.download(got));
+    std::vector<float> row((size_t)HEAD_DIM);
+    each_row([&](int pg, int l, int v, int g, int pp, size_t at) {
+        const size_t elem = b.row_elem(dst_slots[pg], l, v, g, pp);
+        b.get_row(got, dst_slots[pg], elem, row.data());
+        for (int dd = 0; dd < HEAD_DIM; ++dd) { uint32_t u; memcpy(&u, &row[(size_t)dd], 4); dst[at + dd] = (uint16_t)(u >> 16); }
+        b.copy_row(b.img, got, dst_slots[pg], elem);
+    });
+    b.strays(got, stray);
+    return Q3_OK;
+}
+
 // ---- the vocoder conv family, one launch at a time (tests/test_gpu_conv_ops.py) ----
 extern "C" int q3_conv_path(int cout, int cin, int L, int k, int dil, int phases, int packed, int has_resid, int planes, int aligned16) {
     return conv_path_code(conv_pick(cout, cin, L, k, dil, phases, packed != 0, has_resid != 0, planes, aligned16 != 0, phases > 1));

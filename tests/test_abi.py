@@ -120,7 +120,11 @@ def test_no_cpu_fallback():
         assert e.status == 5
     else:
         raise AssertionError("q3_attn_step succeeded without a GPU")
-    for call, name in ((lambda: q.conv_ex(0, np.zeros((16, 8), np.float32), np.zeros((32, 16, 1), np.float32)), "q3_conv_ex"),
+    for call, name in ((lambda: q.attn_step_ex(0, [0], np.ones(128, np.float32), np.ones(128, np.float32), 1e-6, np.ones((4, 64), np.float32),
+                                               np.zeros((4, 64), np.float32), np.zeros((1, 1, 4, 128), np.float32), np.zeros((1, 1, 4, 128), np.float32), 2, 1,
+                                               qkv=np.zeros((1, 4 * 128), np.float32)), "q3_attn_step_ex"),
+                       (lambda: q.kv_pages_to_bf16_ex(np.zeros((1, 1, 2, 1, 128, 128), np.float32), [0], [1]), "q3_kv_pages_to_bf16_ex"),
+                       (lambda: q.conv_ex(0, np.zeros((16, 8), np.float32), np.zeros((32, 16, 1), np.float32)), "q3_conv_ex"),
                        (lambda: q.gemm_ex(np.zeros((1, 64), np.float32), np.zeros((64, 64), np.uint16)), "q3_gemm_ex"),
                        (lambda: q.attn_prefill_ex(np.zeros((2, 4 * 128), np.float32), 1, 0, np.ones(128, np.float32), np.ones(128, np.float32), 1e-6,
                                                   np.ones((4, 64), np.float32), np.zeros((4, 64), np.float32), np.zeros((1, 1, 4, 128), np.float32),
@@ -255,6 +259,9 @@ def test_null_handles_return_status_not_crash():
         lambda: L.q3_linear_ex(0, ctypes.byref(_lib.CLinearEx())),
         lambda: L.q3_attn_step(0, None),
         lambda: L.q3_attn_step(0, ctypes.byref(_lib.CAttnStep())),
+        lambda: L.q3_attn_step_ex(0, None),
+        lambda: L.q3_attn_step_ex(0, ctypes.byref(_lib.CAttnStepEx())),
+        lambda: L.q3_kv_pages_to_bf16_ex(0, 1, 1, 1, None, None, None, None, None, None),
         lambda: L.q3_conv_ex(0, None),
         lambda: L.q3_conv_ex(0, ctypes.byref(_lib.CConvEx())),
         lambda: L.q3_gemm_ex(0, None),

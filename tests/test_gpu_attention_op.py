@@ -106,7 +106,7 @@ def _all_case_keys():
         keys.append((nh, nkv, 256, (37,)))
         keys.append((nh, nkv, 256, (37, 37, 37)))
         keys.append((nh, nkv, 256, (200, 200, 200), True))
-        for p in (0, 1, 7, 15):
+        for p in (0, 1, 3, 4, 7, 8, 15):
             for B in (1, 8, 64):
                 keys.append((nh, nkv, 17, (p,) * B))
     return keys
@@ -195,7 +195,7 @@ def test_softmax_stress(variant, nh, nkv):
 @pytest.mark.parametrize("nh,nkv", RATIOS)
 @pytest.mark.parametrize("B", [1, 8, 64])
 def test_code_predictor_kernel(nh, nkv, B):
-    for p in (0, 1, 7, 15):           # k_attn_cp<4> / <4> / <8> / <16>
+    for p in (0, 1, 3, 4, 7, 8, 15):  # k_attn_cp<4> (0 .. 3) / <8> (4 .. 7) / <16> (8 .. 15): the first and last position of each
         _run(2, (nh, nkv, 17, (p,) * B), 1)
 
 
