@@ -1155,6 +1155,53 @@ int q3_mimi_frames(const q3_mimi_config* cfg, int64_t n_samples);
 q3_status q3_mimi_encode(q3_speech_encoder* e, const float* samples_host, int64_t n, uint32_t sample_rate, uint32_t* codes_host,
                          int cap_frames, int* n_frames, float** taps_host);
 
+/* ---------------- reference audio intake (q3_intake.hip, q3_io.cpp): a clip as it lies on disk -> 24 kHz mono f32 on the device ----
+ * The mirror of the output stage (q3_pcm_stage_*) on the input side, DESIGN 4.14: load_wav + resample_to_24k (audio/io.rs:106-141,
+ * audio/resample.rs:173-176, lib.rs:1156-1166) as one launch, k_intake. A clip's interleaved samples in their on-disk format are
+ * decoded by q3_wav_read's rule (an integer iv becomes (float)iv / 2^(bits-1), 8-bit is unsigned, f32 as it is, G.711 expanded to
+ * int16 first), the channels summed in ascending order in f32 and divided by (float)channels, and the mono stream resampled with
+ * q3_resample's filter as a table: L / M = 24000 / sample_rate in lowest terms, output i = row (i M) mod L of taps[L][128] against
+ * inputs c - 63 .. c + 64, c = floor(i M / L), zeros outside the clip, f32 fmas in k_pcm_stage's fixed order, n_out =
+ * llround(frames * 24000 / sample_rate). At 24000 Hz there is no filter: the decoded, downmixed samples bit for bit.
+ * Rates: 4000 .. 96000 Hz with 24000 / gcd(sample_rate, 24000) <= 320 (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100,
+ * 48000, 96000, ...), else Q3_UNSUPPORTED before the device is touched (q3_resample takes every rate, on the host). Channels 1 .. 8,
+ * n_out 1 .. 24000 * 120 (q3_mimi_encode's limit). The samples stay on the device for both encoders (q3_spk_encode_ref,
+ * q3_mimi_encode_ref). No reference counterpart beyond the lines above. */
+enum { Q3_SRC_U8 = 0, Q3_SRC_S16 = 1, Q3_SRC_S24 = 2, Q3_SRC_S32 = 3, Q3_SRC_F32 = 4, Q3_SRC_ULAW = 5, Q3_SRC_ALAW = 6 };
+/* data: frames * channels interleaved little-endian samples of `format` (Q3_SRC_*), at any address */
+typedef struct q3_clip { const void* data; int64_t frames; int32_t channels; uint32_t sample_rate; int32_t format; } q3_clip;
+/* format: Q3_SRC_*; bits per sample as the file states them; data_offset / data_bytes: the data chunk's samples within the file
+ * (whole frames only: frames * channels * bits / 8 bytes) */
+typedef struct q3_wav_desc { int32_t format, channels, bits; uint32_t sample_rate; int64_t frames, data_offset, data_bytes; } q3_wav_desc;
+typedef struct q3_ref_audio q3_ref_audio;
+/* what a WAV file holds, without decoding it (host only): everything q3_wav_read accepts, and WAVE tags 7 / 6 (mu-law / A-law, 8
+ * bits: the files q3_wav_write_g711 writes). Q3_IO / Q3_UNSUPPORTED as q3_wav_read. */
+q3_status q3_wav_info(const char* path, q3_wav_desc* out);
+/* ITU-T G.711 expansion of n bytes to int16, law = Q3_PCM_ULAW or Q3_PCM_ALAW (else Q3_INVALID_ARG): the counterpart of
+ * q3_g711_from_pcm16 (host only) */
+q3_status q3_g711_to_pcm16(const uint8_t* in_host, int64_t n, int law, int16_t* out_host);
+/* the intake's table for sample_rate: *L, *M and taps_host[L][128]; taps_host == NULL queries L / M only (q3_pcm_stage_taps'
+ * contract; host only) */
+q3_status q3_intake_taps(uint32_t sample_rate, float* taps_host, size_t cap_floats, int* L, int* M);
+/* *n_out = the 24 kHz samples n_in frames at sample_rate become (q3_resample's count; host only) */
+q3_status q3_intake_count(uint32_t sample_rate, int64_t n_in, int64_t* n_out);
+/* n clips (1 .. 64) in one upload and one launch; out[i] receives clip i's object. All or nothing: on any refusal or device error no
+ * object is created and out is untouched. Synchronises before it returns: work on any stream may read the objects afterwards. */
+q3_status q3_ref_audio_create_many(int device, int n, const q3_clip* clips, q3_ref_audio** out /* [n] */);
+q3_status q3_ref_audio_create(int device, const q3_clip* clip, q3_ref_audio** out);
+/* q3_wav_info, a read-only mapping of the file, q3_ref_audio_create */
+q3_status q3_ref_audio_from_wav(const char* path, int device, q3_ref_audio** out);
+/* any of the out pointers may be NULL; sr_in / format / channels: what the clip was */
+q3_status q3_ref_audio_info(const q3_ref_audio* r, int64_t* n_samples, int* device, uint32_t* sr_in, int* format, int* channels);
+/* the 24 kHz samples; host == NULL: only *n */
+q3_status q3_ref_audio_read(q3_ref_audio* r, float* host, int64_t cap, int64_t* n);
+void q3_ref_audio_free(q3_ref_audio* r);
+/* q3_spk_encode / q3_mimi_encode of the object's samples, read on the device by the encoder's own stream: the same kernels, workspace
+ * and length checks. An object on another device than the encoder's: Q3_INVALID_ARG. */
+q3_status q3_spk_encode_ref(q3_speaker_encoder* e, const q3_ref_audio* r, float* out_host);
+q3_status q3_mimi_encode_ref(q3_speech_encoder* e, const q3_ref_audio* r, uint32_t* codes_host, int cap_frames, int* n_frames,
+                             float** taps_host);
+
 /* ---------------- data parallelism without torch.distributed (q3_dp.cpp) ----------------
  * one process per GPU, utterance i -> rank i mod N, exactly one collective on the data path — the
  * broadcast of rank 0's weight arena over RCCL (xGMI) — plus an all-gather of a few doubles for end-of-job timing. The

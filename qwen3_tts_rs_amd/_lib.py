@@ -99,6 +99,16 @@ class CAttnCEx(ctypes.Structure):        # q3_attn_c_ex_args
                [(n, ctypes.c_void_p) for n in ("q", "k", "v", "rows", "caches", "tabs", "tab0", "tab_n", "o")]
 
 
+class CClip(ctypes.Structure):           # q3_clip
+    _fields_ = [("data", ctypes.c_void_p), ("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("sample_rate", ctypes.c_uint32),
+                ("format", ctypes.c_int32)]
+
+
+class CWavDesc(ctypes.Structure):        # q3_wav_desc
+    _fields_ = [("format", ctypes.c_int32), ("channels", ctypes.c_int32), ("bits", ctypes.c_int32), ("sample_rate", ctypes.c_uint32),
+                ("frames", ctypes.c_int64), ("data_offset", ctypes.c_int64), ("data_bytes", ctypes.c_int64)]
+
+
 class CTiming(ctypes.Structure):
     _fields_ = [("prefill_ms", ctypes.c_double), ("generation_ms", ctypes.c_double), ("decode_ms", ctypes.c_double),
                 ("generation_frames", ctypes.c_int32)]
@@ -319,6 +329,18 @@ SYMBOLS = {
     "q3_mimi_load_safetensors": (c_int, [c_void_p, c_char_p]),
     "q3_mimi_frames": (c_int, [P(CMimiConfig), ctypes.c_int64]),
     "q3_mimi_encode": (c_int, [c_void_p, c_void_p, ctypes.c_int64, ctypes.c_uint32, c_void_p, c_int, P(c_int), P(c_void_p)]),
+    "q3_wav_info": (c_int, [c_char_p, P(CWavDesc)]),
+    "q3_g711_to_pcm16": (c_int, [c_void_p, ctypes.c_int64, c_int, c_void_p]),
+    "q3_intake_taps": (c_int, [ctypes.c_uint32, c_void_p, ctypes.c_size_t, P(c_int), P(c_int)]),
+    "q3_intake_count": (c_int, [ctypes.c_uint32, ctypes.c_int64, P(ctypes.c_int64)]),
+    "q3_ref_audio_create_many": (c_int, [c_int, c_int, P(CClip), P(c_void_p)]),
+    "q3_ref_audio_create": (c_int, [c_int, P(CClip), P(c_void_p)]),
+    "q3_ref_audio_from_wav": (c_int, [c_char_p, c_int, P(c_void_p)]),
+    "q3_ref_audio_info": (c_int, [c_void_p, P(ctypes.c_int64), P(c_int), P(ctypes.c_uint32), P(c_int), P(c_int)]),
+    "q3_ref_audio_read": (c_int, [c_void_p, c_void_p, ctypes.c_int64, P(ctypes.c_int64)]),
+    "q3_ref_audio_free": (None, [c_void_p]),
+    "q3_spk_encode_ref": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "q3_mimi_encode_ref": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(c_int), P(c_void_p)]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

@@ -970,7 +970,17 @@ class Qwen3TTS:
                                            "Use a Base model for voice cloning."}.get(
                 self.model_type, " Ensure model weights contain `speaker_encoder.*` keys (only Base models include a speaker encoder).")
             raise _lib.Q3Error(3, "Speaker encoder not available." + hint)
-        if ref_audio.sample_rate != 24000:        # both encoders assume 24 kHz input (lib.rs:1156-1166)
+        if isinstance(ref_audio, RefAudio):       # converted on the device already: both encoders read it there
+            emb = self.speaker_encoder.encode_ref(ref_audio)
+            if ref_text_ids is None:
+                return VoiceClonePrompt(emb)
+            if ref_codes is None:
+                if self.speech_encoder is None:
+                    raise _lib.Q3Error(7, "ICL voice cloning requires a speech encoder, but it was not loaded. Ensure the speech tokenizer "
+                                          "weights contain encoder keys, or use x_vector_only mode by passing ref_text=None.")
+                ref_codes = self.speech_encoder.encode_ref(ref_audio)
+            return VoiceClonePrompt(emb, np.ascontiguousarray(ref_codes, dtype=np.uint32), np.asarray(ref_text_ids, dtype=np.uint32))
+        if ref_audio.sample_rate != 24000:       # both encoders assume 24 kHz input (lib.rs:1156-1166)
             ref_audio = resample_to_24k(ref_audio)
         emb = self.speaker_encoder.encode(ref_audio.samples, ref_audio.sample_rate)
         if ref_text_ids is None:
@@ -1729,6 +1739,124 @@ def resample(audio: AudioBuffer, target_rate: int) -> AudioBuffer:
 
 def resample_to_24k(audio: AudioBuffer) -> AudioBuffer:      # audio/resample.rs:174-176
     return resample(audio, 24000)
+
+
+# ---- reference audio intake (q3_intake.hip) ----
+SRC_NAMES = ("u8", "s16", "s24", "s32", "f32", "ulaw", "alaw")      # Q3_SRC_*
+SRC_BYTES = (1, 2, 3, 4, 4, 1, 1)
+
+
+class WavInfo(NamedTuple):
+    fmt: str                 # one of SRC_NAMES
+    channels: int
+    bits: int
+    sample_rate: int
+    frames: int
+    data_offset: int
+    data_bytes: int
+
+
+def wav_info(path: str) -> WavInfo:
+    """What a WAV file holds, without decoding it (q3_wav_info): PCM 8 / 16 / 24 / 32, float32, G.711."""
+    d = _lib.CWavDesc()
+    check(lib.q3_wav_info(str(path).encode(), ctypes.byref(d)))
+    return WavInfo(SRC_NAMES[d.format], d.channels, d.bits, int(d.sample_rate), d.frames, d.data_offset, d.data_bytes)
+
+
+def g711_expand(g711_bytes: np.ndarray, law: str) -> np.ndarray:
+    """ITU-T G.711 expansion of uint8 bytes to int16 (q3_g711_to_pcm16): law "ulaw" or "alaw"."""
+    if law not in ("ulaw", "alaw"):
+        raise ValueError(f"law must be \"ulaw\" or \"alaw\", not {law!r}")
+    a = np.ascontiguousarray(g711_bytes, dtype=np.uint8).reshape(-1)
+    out = np.empty(a.size, dtype=np.int16)
+    check(lib.q3_g711_to_pcm16(a.ctypes.data_as(ctypes.c_void_p), a.size, PCM_NAMES.index(law), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def intake_taps(rate: int) -> Tuple[np.ndarray, int, int]:
+    """(taps [L, 128] f32, L, M) of the intake's resampler for an input rate: L / M = 24000 / rate (q3_intake_taps)."""
+    L = ctypes.c_int(); M = ctypes.c_int()
+    check(lib.q3_intake_taps(int(rate), None, 0, ctypes.byref(L), ctypes.byref(M)))
+    taps = np.empty((L.value, 128), np.float32)
+    check(lib.q3_intake_taps(int(rate), taps.ctypes.data_as(ctypes.c_void_p), taps.size, ctypes.byref(L), ctypes.byref(M)))
+    return taps, L.value, M.value
+
+
+def intake_count(rate: int, n_in: int) -> int:
+    """24 kHz samples that n_in frames at `rate` become (q3_intake_count)."""
+    n = ctypes.c_int64()
+    check(lib.q3_intake_count(int(rate), int(n_in), ctypes.byref(n)))
+    return n.value
+
+
+def _clip_of(data, sample_rate: int, fmt: str, channels: int, keep: list) -> "_lib.CClip":
+    if fmt not in SRC_NAMES:
+        raise ValueError(f"fmt must be one of {SRC_NAMES}, not {fmt!r}")
+    raw = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    keep.append(raw)
+    c = _lib.CClip()
+    c.data = raw.ctypes.data if raw.size else None
+    c.frames = raw.size // (SRC_BYTES[SRC_NAMES.index(fmt)] * max(1, int(channels)))
+    c.channels = int(channels); c.sample_rate = int(sample_rate); c.format = SRC_NAMES.index(fmt)
+    return c
+
+
+class RefAudio:
+    """A reference clip converted to 24 kHz mono f32 on the device by one launch (k_intake), where it stays for
+    SpeakerEncoder.encode_ref / SpeechEncoder.encode_ref / Qwen3TTS.create_voice_clone_prompt. Decode and downmix are load_wav's,
+    the filter is resample's."""
+
+    def __init__(self, handle):
+        self._h = handle
+        n = ctypes.c_int64(); dev = ctypes.c_int(); sr = ctypes.c_uint32(); f = ctypes.c_int(); ch = ctypes.c_int()
+        check(lib.q3_ref_audio_info(handle, ctypes.byref(n), ctypes.byref(dev), ctypes.byref(sr), ctypes.byref(f), ctypes.byref(ch)))
+        self.n_samples, self.device_index, self.source_rate, self.source_format, self.source_channels = \
+            n.value, dev.value, int(sr.value), SRC_NAMES[f.value], ch.value
+        self.sample_rate = 24000
+
+    @classmethod
+    def from_wav(cls, path: str, device: int = 0) -> "RefAudio":
+        h = ctypes.c_void_p()
+        check(lib.q3_ref_audio_from_wav(str(path).encode(), device, ctypes.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_samples(cls, data, sample_rate: int, fmt: str, channels: int = 1, device: int = 0) -> "RefAudio":
+        """`data`: the clip's interleaved samples as they lie on disk — bytes, or an array whose memory is exactly that."""
+        keep = []
+        c = _clip_of(data, sample_rate, fmt, channels, keep)
+        h = ctypes.c_void_p()
+        check(lib.q3_ref_audio_create(device, ctypes.byref(c), ctypes.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def many(cls, clips, device: int = 0) -> List["RefAudio"]:
+        """One upload and one launch for all of `clips`: each (data, sample_rate, fmt) or (data, sample_rate, fmt, channels).
+        All or nothing."""
+        keep = []
+        cs = [_clip_of(c[0], c[1], c[2], c[3] if len(c) > 3 else 1, keep) for c in clips]
+        arr = (_lib.CClip * max(1, len(cs)))(*cs)
+        hs = (ctypes.c_void_p * max(1, len(cs)))()
+        check(lib.q3_ref_audio_create_many(device, len(cs), arr, hs))
+        return [cls(ctypes.c_void_p(h)) for h in hs[:len(cs)]]
+
+    def samples(self) -> np.ndarray:
+        out = np.empty(self.n_samples, np.float32); n = ctypes.c_int64()
+        check(lib.q3_ref_audio_read(self._h, out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n)))
+        return out
+
+    def __len__(self) -> int:
+        return self.n_samples
+
+    def duration(self) -> float:
+        return self.n_samples / 24000.0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.q3_ref_audio_free(self._h); self._h = None
+
+    __del__ = close
 
 
 def save_codes_binary(path: str, codes: np.ndarray):

@@ -42,6 +42,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--custom-voice", action="store_true", help="accepted for compatibility: the model size always comes from config.json here")
     ap.add_argument("--instruct", default=None, help="voice description (VoiceDesign models)")
     ap.add_argument("--ref-audio", default=None)
+    ap.add_argument("--ref-intake", choices=["host", "device"], default="host",
+                    help="where --ref-audio is decoded, downmixed and resampled to 24 kHz: on the host (q3_wav_read + q3_resample), or on the "
+                         "GPU in one launch (RefAudio.from_wav: PCM 8/16/24/32, float32, G.711; up to 8 channels)")
     ap.add_argument("--ref-text", default=None)
     ap.add_argument("--x-vector-only", action="store_true")
     ap.add_argument("--output", default=None, help="output WAV path (overrides default naming)")
@@ -303,8 +306,17 @@ def main(argv=None) -> int:
     if a.instruct or a.instruct_ids:
         utt.instruct_ids = [int(x) for x in a.instruct_ids.split(",")] if a.instruct_ids else tok.encode(a.instruct)
     if a.ref_audio:          # run_voice_clone (generate_audio.rs:213-300): speaker embedding from the reference WAV
-        ref = api.AudioBuffer.load(a.ref_audio)
-        print(f"Reference audio: {a.ref_audio} ({ref.duration():.2f}s, {ref.sample_rate} Hz)")
+        if a.ref_intake == "device":      # decode, downmix and resampling on the GPU, the samples stay there
+            try:
+                ref = api.RefAudio.from_wav(a.ref_audio, device=dev)
+            except api._lib.Q3Error as e:
+                print(f"error: {e}", file=sys.stderr)
+                return 2
+            print(f"Reference audio: {a.ref_audio} ({ref.duration():.2f}s, {ref.source_rate} Hz, {ref.source_format}, "
+                  f"{ref.source_channels} ch)")
+        else:
+            ref = api.AudioBuffer.load(a.ref_audio)
+            print(f"Reference audio: {a.ref_audio} ({ref.duration():.2f}s, {ref.sample_rate} Hz)")
         print("Mode: ICL (reference codes + text)" if a.ref_text else "Mode: x_vector_only (no reference text)")
         try:
             if a.ref_text and not a.ref_codes_bin and not a.x_vector_only:

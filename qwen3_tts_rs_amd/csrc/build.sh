@@ -33,8 +33,8 @@ API="$HERE/../../include/q3tts.h"
 for f in q3_kernels_lm q3_kernels_gemv q3_kernels_wide q3_kernels_codec q3_kernels_prefill q3_speaker q3_mimi; do
   compile "$HERE/$f.hip" "$BUILD/$f.o" "$DEV_FLAGS" "$HERE/q3_kernels.h" "$HERE/q3_internal.h" "$HERE/q3_capture_lock.h" "$API"
 done
-# the engine (host side of the hot path): nine units behind q3_engine.h
-for f in q3_model q3_prefix_cache q3_codec_run q3_codec_stream q3_pcm_stage q3_session q3_batcher q3_row_state q3_testapi; do
+# the engine (host side of the hot path): ten units behind q3_engine.h
+for f in q3_model q3_prefix_cache q3_codec_run q3_codec_stream q3_pcm_stage q3_intake q3_session q3_batcher q3_row_state q3_testapi; do
   compile "$HERE/$f.hip" "$BUILD/$f.o" "$DEV_FLAGS" "$HERE/q3_engine.h" "$HERE/q3_prefix_cache.h" "$HERE/q3_capture_lock.h" "$HERE/q3_kernels.h" "$HERE/q3_internal.h" "$HERE/q3_aql.h" "$API"
 done
 compile "$HERE/q3_io.cpp" "$BUILD/q3_io.o" "$HOST_FLAGS" "$HERE/q3_internal.h" "$API"

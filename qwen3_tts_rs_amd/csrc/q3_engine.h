@@ -9,6 +9,8 @@
 //                    row — a gain and a look-ahead peak limiter — between the two; a BS.1770 loudness meter and
 //                    normaliser per row in front of the level; a pitch per row in cents, a varispeed step behind the
 //                    stretcher
+//   q3_intake.hip    the reference-audio intake: a clip in its on-disk sample format -> 24 kHz mono f32 on the device in one launch,
+//                    where both encoders read it
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
 //                    streaming chunks, q3_session_run / decode / get
 //   q3_batcher.hip   continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
@@ -610,6 +612,9 @@ struct PsPlan {
     std::vector<LoDesc> odesc; std::vector<long long> o_n;
     PsTrim trim;                             // filled by pcm_stage_trim in front of pcm_stage_plan, which leaves it alone
 };
+// q3_resample's filter as a table for output / input = L / M in lowest terms, out[L][128] (taps_of): the output stage's at
+// L / M = sr_out / 24000, the intake's (q3_intake.hip) at L / M = 24000 / sr_in
+Q3_HIDDEN void resampler_taps(int L, int M, std::vector<float>& out);
 Q3_HIDDEN int pcm_stage_rows(const q3_pcm_stage* ps);
 Q3_HIDDEN size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row);
 Q3_HIDDEN void pcm_stage_reset(q3_pcm_stage* ps, int row);

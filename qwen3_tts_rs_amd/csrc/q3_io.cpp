@@ -723,6 +723,63 @@ extern "C" q3_status q3_wav_read(const char* path, float* out, int64_t cap, int6
     return Q3_OK;
 }
 
+// What a WAV file holds, for the intake (q3_intake.hip), which decodes on the device: q3_wav_read's chunk walk and its checks, and
+// G.711 (tags 7 / 6, 8 bits) beside PCM and float.
+extern "C" q3_status q3_wav_info(const char* path, q3_wav_desc* out) {
+    if (!path || !out) return q3i_set_err(Q3_INVALID_ARG, "q3_wav_info: null argument");
+    Mapped mp;
+    if (!mp.open(path)) return q3i_set_err(Q3_IO, "Failed to open WAV file: %s", path);
+    const uint8_t* p = mp.p; const size_t n = mp.n;
+    if (n < 12 || memcmp(p, "RIFF", 4) != 0 || memcmp(p + 8, "WAVE", 4) != 0) return q3i_set_err(Q3_IO, "%s: not a RIFF/WAVE file", path);
+    size_t off = 12; int fmt = 0, ch = 0, bits = 0; uint32_t rate = 0; const uint8_t* data = nullptr; size_t dlen = 0;
+    while (off + 8 <= n) {
+        const uint32_t len = rd_u32(p + off + 4);
+        const uint8_t* body = p + off + 8;
+        const size_t avail = n - off - 8;
+        if (memcmp(p + off, "fmt ", 4) == 0) {
+            if (len < 16 || avail < 16) return q3i_set_err(Q3_IO, "%s: short fmt chunk", path);
+            fmt = rd_u16(body); ch = rd_u16(body + 2); rate = rd_u32(body + 4); bits = rd_u16(body + 14);
+            if (fmt == 0xFFFE && len >= 26 && avail >= 26) fmt = rd_u16(body + 24);   // WAVE_FORMAT_EXTENSIBLE sub-format
+        } else if (memcmp(p + off, "data", 4) == 0) {
+            data = body; dlen = std::min<size_t>(len, avail); break;
+        }
+        off += 8 + (size_t)len + (len & 1);
+    }
+    if (!data || !ch) return q3i_set_err(Q3_IO, "%s: missing fmt or data chunk", path);
+    int src = -1;
+    if (fmt == 1) src = bits == 8 ? Q3_SRC_U8 : bits == 16 ? Q3_SRC_S16 : bits == 24 ? Q3_SRC_S24 : bits == 32 ? Q3_SRC_S32 : -1;
+    else if (fmt == 3 && bits == 32) src = Q3_SRC_F32;
+    else if ((fmt == 7 || fmt == 6) && bits == 8) src = fmt == 7 ? Q3_SRC_ULAW : Q3_SRC_ALAW;
+    if (src < 0) return q3i_set_err(Q3_UNSUPPORTED, "%s: unsupported WAV sample format (tag %d, %d bits)", path, fmt, bits);
+    const size_t frame_bytes = (size_t)(bits / 8) * (size_t)ch;
+    out->format = src; out->channels = ch; out->bits = bits; out->sample_rate = rate;
+    out->frames = (int64_t)(dlen / frame_bytes);
+    out->data_offset = (int64_t)(data - p);
+    out->data_bytes = out->frames * (int64_t)frame_bytes;
+    return Q3_OK;
+}
+
+// ITU-T G.711 expansion, the counterpart of g711_ulaw / g711_alaw above
+extern "C" q3_status q3_g711_to_pcm16(const uint8_t* in, int64_t n, int law, int16_t* out) {
+    if (law != Q3_PCM_ULAW && law != Q3_PCM_ALAW) return q3i_set_err(Q3_INVALID_ARG, "q3_g711_to_pcm16: law must be Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)");
+    if (n < 0 || ((!in || !out) && n > 0)) return q3i_set_err(Q3_INVALID_ARG, "q3_g711_to_pcm16: bad argument");
+    if (law == Q3_PCM_ULAW) {
+        for (int64_t i = 0; i < n; ++i) {
+            const int u = ~in[i] & 0xFF;
+            const int t = (((u & 0x0F) << 3) + 0x84) << ((u & 0x70) >> 4);
+            out[i] = (int16_t)((u & 0x80) ? 0x84 - t : t - 0x84);
+        }
+    } else {
+        for (int64_t i = 0; i < n; ++i) {
+            const int a = in[i] ^ 0x55, seg = (a & 0x70) >> 4;
+            int t = (a & 0x0F) << 4;
+            t = seg == 0 ? t + 8 : seg == 1 ? t + 0x108 : (t + 0x108) << (seg - 1);
+            out[i] = (int16_t)((a & 0x80) ? t : -t);
+        }
+    }
+    return Q3_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // codes_*.bin (i64 LE, frame-major) and audio_*.bin (f32 LE)
 // ------------------------------------------------------------------------------------------------

@@ -374,11 +374,32 @@ static hipError_t m_run_conv(q3_speech_encoder* e, const MConv& cv, const float*
 
 // codes_host [T][n_q]; taps_host: NULL or 3 host pointers (NULL entries skipped): SEANet out [hidden][T25], transformer out [hidden][T25],
 // downsampled [hidden][T]
+static q3_status mimi_encode_from(q3_speech_encoder* e, const float* samples, hipMemcpyKind kind, int64_t n, uint32_t* codes_host,
+                                  int cap_frames, int* n_frames, float** taps_host);
+
 extern "C" q3_status q3_mimi_encode(q3_speech_encoder* e, const float* samples, int64_t n, uint32_t sample_rate, uint32_t* codes_host,
                                     int cap_frames, int* n_frames, float** taps_host) {
     if (!e || !samples || !n_frames) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_encode: null argument");
     if (!e->finalized) return q3i_set_err(Q3_INVALID_ARG, "speech encoder not finalized");
     if (sample_rate != 24000) return q3i_set_err(Q3_INVALID_ARG, "speech encoder expects 24000 Hz audio, got %u (resample first: q3_resample)", sample_rate);
+    return mimi_encode_from(e, samples, hipMemcpyHostToDevice, n, codes_host, cap_frames, n_frames, taps_host);
+}
+
+// the same for samples that are on the encoder's device already (q3_intake.hip): the first conv's input buffer is reused further
+// down, so they are copied into it, device to device, by the encoder's own stream
+extern "C" q3_status q3_mimi_encode_ref(q3_speech_encoder* e, const q3_ref_audio* r, uint32_t* codes_host, int cap_frames, int* n_frames,
+                                        float** taps_host) {
+    if (!e || !r || !n_frames) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_encode_ref: null argument");
+    int64_t n = 0; int dev = 0;
+    const float* x_d = q3i_ref_audio_dev(r, &n, &dev);
+    if (dev != e->device) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_encode_ref: reference audio is on device %d, the encoder on device %d", dev, e->device);
+    if (!e->finalized) return q3i_set_err(Q3_INVALID_ARG, "speech encoder not finalized");
+    return mimi_encode_from(e, x_d, hipMemcpyDeviceToDevice, n, codes_host, cap_frames, n_frames, taps_host);
+}
+
+// q3_mimi_encode behind its checks of handle and rate: `samples` on the host or on the encoder's device, as `kind` says
+static q3_status mimi_encode_from(q3_speech_encoder* e, const float* samples, hipMemcpyKind kind, int64_t n, uint32_t* codes_host,
+                                  int cap_frames, int* n_frames, float** taps_host) {
     if (n < 1 || n > (int64_t)24000 * 120) return q3i_set_err(Q3_INVALID_ARG, "reference audio of %lld samples unsupported (1 .. 120 s)", (long long)n);
     const q3_mimi_config& c = e->cfg;
     const int T = q3_mimi_frames(&c, n);
@@ -427,7 +448,7 @@ extern "C" q3_status q3_mimi_encode(q3_speech_encoder* e, const float* samples, 
         return Q3_OK;
     };
     // ---- SEANet ----
-    M_HIP(hipMemcpyAsync(C, samples, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    M_HIP(hipMemcpyAsync(C, samples, (size_t)n * 4, kind, st));
     M_HIP(m_run_conv(e, e->c0, C, A, (int)n));                                          // x = A [F][n]
     float* x = A; float* o1 = B; float* o2 = C;
     int dim = F, L = (int)n;

@@ -793,6 +793,8 @@ size_t fmt_bytes(int fmt) { return fmt == Q3_PCM_F32 ? 4 : fmt == Q3_PCM_S16 ? 2
 bool fmt_ok(int fmt) { return fmt >= Q3_PCM_F32 && fmt <= Q3_PCM_ALAW; }
 }  // namespace
 
+void resampler_taps(int L, int M, std::vector<float>& out) { Rate r; r.L = L; r.M = M; taps_of(r, out); }
+
 struct PsRow {
     uint32_t sr = PS_RATE_IN; int fmt = Q3_PCM_F32; Rate r; const float* taps = nullptr;
     long long n_in = 0, n_out = 0;            // input samples consumed, output samples emitted

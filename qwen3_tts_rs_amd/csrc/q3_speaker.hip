@@ -529,6 +529,18 @@ extern "C" q3_status q3_spk_forward(q3_speaker_encoder* e, const float* mel_host
     return Q3_OK;
 }
 
+// q3_spk_encode behind its upload: n samples at x_d on the encoder's device, the workspace reserved ([samples | mel | out | rest])
+static q3_status spk_encode_dev(q3_speaker_encoder* e, const float* x_d, int64_t n, int T, float* out_host) {
+    const size_t xs = ((size_t)n + 63) & ~(size_t)63;
+    float* mel_d = e->ws + xs; float* out_d = mel_d + (((size_t)e->cfg.mel_dim * T + 63) & ~(size_t)63);
+    float* base = out_d + ((e->cfg.enc_dim + 63) & ~63);
+    hipLaunchKernelGGL(k_spk_stft_mel, dim3(T), dim3(256), 0, e->st, x_d, (long)n, T, e->win, e->dft_cs, e->dft_sn, e->fb, mel_d, e->cfg.mel_dim);
+    Q3I_CHECK(spk_forward_dev(e, mel_d, T, out_d, base, nullptr));
+    SPK_HIP(hipMemcpyAsync(out_host, out_d, (size_t)e->cfg.enc_dim * 4, hipMemcpyDeviceToHost, e->st));
+    SPK_HIP(hipStreamSynchronize(e->st));
+    return Q3_OK;
+}
+
 extern "C" q3_status q3_spk_encode(q3_speaker_encoder* e, const float* samples, int64_t n, uint32_t sample_rate, float* out_host) {
     if (!e || !samples || !out_host || n < 1) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode: bad argument");
     if (!e->finalized) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode: encoder not finalized");
@@ -539,12 +551,23 @@ extern "C" q3_status q3_spk_encode(q3_speaker_encoder* e, const float* samples, 
     SPK_HIP(hipSetDevice(e->device));
     const size_t xs = ((size_t)n + 63) & ~(size_t)63;
     Q3I_CHECK(spk_reserve(e, xs + spk_ws_floats(e, T)));
-    float* x_d = e->ws; float* mel_d = x_d + xs; float* out_d = mel_d + (((size_t)e->cfg.mel_dim * T + 63) & ~(size_t)63);
-    float* base = out_d + ((e->cfg.enc_dim + 63) & ~63);
-    SPK_HIP(hipMemcpyAsync(x_d, samples, (size_t)n * 4, hipMemcpyHostToDevice, e->st));
-    hipLaunchKernelGGL(k_spk_stft_mel, dim3(T), dim3(256), 0, e->st, x_d, (long)n, T, e->win, e->dft_cs, e->dft_sn, e->fb, mel_d, e->cfg.mel_dim);
-    Q3I_CHECK(spk_forward_dev(e, mel_d, T, out_d, base, nullptr));
-    SPK_HIP(hipMemcpyAsync(out_host, out_d, (size_t)e->cfg.enc_dim * 4, hipMemcpyDeviceToHost, e->st));
-    SPK_HIP(hipStreamSynchronize(e->st));
-    return Q3_OK;
+    SPK_HIP(hipMemcpyAsync(e->ws, samples, (size_t)n * 4, hipMemcpyHostToDevice, e->st));
+    return spk_encode_dev(e, e->ws, n, T, out_host);
+}
+
+// the same for samples that are on the encoder's device already (q3_intake.hip): read where they lie, by the encoder's own stream
+extern "C" q3_status q3_spk_encode_ref(q3_speaker_encoder* e, const q3_ref_audio* r, float* out_host) {
+    if (!e || !r || !out_host) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_ref: null argument");
+    int64_t n = 0; int dev = 0;
+    const float* x_d = q3i_ref_audio_dev(r, &n, &dev);
+    if (dev != e->device) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_ref: reference audio is on device %d, the encoder on device %d", dev, e->device);
+    if (!e->finalized) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_ref: encoder not finalized");
+    if ((uint32_t)e->cfg.sample_rate != 24000u)
+        return q3i_set_err(Q3_UNSUPPORTED, "speaker encoder expects %d Hz audio, got 24000 Hz: resample first (the reference does, lib.rs:1156-1166)", e->cfg.sample_rate);
+    const int T = q3_spk_mel_frames(n);
+    Q3I_CHECK(spk_check_T(e, T));
+    SPK_HIP(hipSetDevice(e->device));
+    const size_t xs = ((size_t)n + 63) & ~(size_t)63;
+    Q3I_CHECK(spk_reserve(e, xs + spk_ws_floats(e, T)));            // q3_spk_encode's workspace, its sample region unused
+    return spk_encode_dev(e, x_d, n, T, out_host);
 }

@@ -126,6 +126,12 @@ class SpeakerEncoder:
         check(lib.q3_spk_encode(self._h, x.ctypes.data_as(ctypes.c_void_p), x.size, sample_rate, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def encode_ref(self, ref) -> np.ndarray:
+        """encode() of a RefAudio's 24 kHz samples, read where they lie on the device (q3_spk_encode_ref)."""
+        out = np.empty(self.config.enc_dim, np.float32)
+        check(lib.q3_spk_encode_ref(self._h, ref._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
     def tap_shapes(self, T: int) -> List[Tuple[int, ...]]:
         c = self.config
         return [(c.enc_channels[0], T), (c.enc_channels[1], T), (c.enc_channels[2], T), (c.enc_channels[3], T), (c.enc_channels[4], T), (2 * c.enc_channels[4],)]

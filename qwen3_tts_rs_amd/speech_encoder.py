@@ -116,6 +116,17 @@ class SpeechEncoder:
                                  codes.shape[0], ctypes.byref(nf), tp))
         return codes
 
+    def encode_ref(self, ref, taps: Optional[List[Optional[np.ndarray]]] = None) -> np.ndarray:
+        """encode() of a RefAudio's 24 kHz samples, copied on the device (q3_mimi_encode_ref)."""
+        nf = ctypes.c_int()
+        check(lib.q3_mimi_encode_ref(self._h, ref._h, None, 0, ctypes.byref(nf), None))
+        codes = np.zeros((nf.value, self.config.n_q), np.uint32)
+        tp = None
+        if taps is not None:
+            tp = (ctypes.c_void_p * 3)(*[t.ctypes.data_as(ctypes.c_void_p) if t is not None else None for t in taps])
+        check(lib.q3_mimi_encode_ref(self._h, ref._h, codes.ctypes.data_as(ctypes.c_void_p), codes.shape[0], ctypes.byref(nf), tp))
+        return codes
+
 
 def synthetic_speech_checkpoint(enc: SpeechEncoder, seed: int) -> Iterator[Tuple[str, np.ndarray]]:
     """Conv / linear weights ~ 1.4 / sqrt(fan_in) (activations stay O(1) through ELU / LayerNorm), LayerNorm weights near 1,
