@@ -676,6 +676,59 @@ q3_status q3_rvq_embed_ex(int device, const uint32_t* frames, int n_frames, cons
                           float* first_out, float* rest_out, int out_front, int out_elems);
 /* Test API: launch_silu_mul: y[i] = silu(g[i]) * u[i], i < n; y: host buffer of y_elems >= n floats, uploaded and copied back whole. */
 q3_status q3_silu_mul_ex(int device, const float* g, const float* u, float* y, long long n, long long y_elems);
+/* Test API: the sampler and the frame-seam kernels in the forms a session launches them, ONE launch each over host arrays (op-level
+ * tests). Arguments are checked before any device call: a null pointer, a token / code / row index that would make the kernel read
+ * outside a table, a draw outside `u`, a sampler vocab outside 2..4096 are Q3_INVALID_ARG. Every buffer a kernel may write holds
+ * `guard` extra elements in front of and behind its payload; it is uploaded whole before the launch and copied back whole after it.
+ *
+ * q3_sample_row: the per-row sampler record a session derives from a request's options (host only; `pad` is 0). */
+typedef struct q3_sample_rec {
+    float inv_temp; int apply_temp, greedy;
+    int top_k; float top_p; int use_top_p;
+    float rep_pen, rep_inv; int use_rep;
+    int eos_id, min_new_tokens, pad;
+} q3_sample_rec;
+q3_status q3_sample_row(const q3_options* opts, q3_sample_rec* out);
+/* q3_sample_ex (launch_sample): row b samples logits[b * ld .. + vocab) with the draw u[b * u_stride + (draw_idx ? draw_idx[b] : 0)]
+ * under rows[b] (or `scalar` when rows is NULL) and writes tok[b]. seen [B][vocab] u8: penalty mask, marked at the sampled id.
+ * token_count: per-row counters (NULL: token_count_static for every row). advance != 0: frame_idx / pos are advanced, unless the row
+ * is FROZEN (limit given, frame_idx >= limit: counters stay, tok / seen are still written) or HELD (text_ready given, frame_idx >=
+ * text_ready: nothing is written). logits_hist [B][hist_stride_b]: the raw row is copied to index token_count while that is below
+ * hist_cap. Guarded (in/out): tok, seen, token_count, frame_idx, pos, logits_hist. */
+typedef struct q3_sample_ex_args {
+    int B, vocab, ld, u_stride, u_elems, advance, token_count_static, hist_stride_b, hist_cap, codec_eos, use_suppress, guard;
+    q3_sample_rec scalar;
+    const float* logits; const float* u; const int* draw_idx; const q3_sample_rec* rows;
+    const int* limit; const int* text_ready;
+    uint32_t* tok; uint8_t* seen; int* token_count; int* frame_idx; int* pos; float* logits_hist;
+} q3_sample_ex_args;
+q3_status q3_sample_ex(int device, const q3_sample_ex_args* args);
+/* q3_frame_embed_ex (launch_frame_embed): codec_emb [n_sem][H] bf16, cp_embs [15][cp_vocab][H] bf16, tok [B], cp_logits_last
+ * [B][cp_vocab], frame_idx / trail_base / trail_len / pad_row / text_ready (nullable) [B], text_rows [n_text_rows][H] f32.
+ * Guarded (in/out): codes [B][max_frames][16] u32, out [B][H] f32. frame_idx may equal max_frames (a frozen row). */
+typedef struct q3_frame_embed_ex_args {
+    int B, H, n_sem, cp_vocab, max_frames, n_text_rows, guard, reserved;
+    const uint16_t* codec_emb; const uint16_t* cp_embs; const uint32_t* tok; const float* cp_logits_last;
+    const int* frame_idx; const float* text_rows; const int* trail_base; const int* trail_len; const int* pad_row; const int* text_ready;
+    uint32_t* codes; float* out;
+} q3_frame_embed_ex_args;
+q3_status q3_frame_embed_ex(int device, const q3_frame_embed_ex_args* args);
+/* q3_cp_gather_ex (launch_cp_gather), one pass: 0 = last_hidden [B][H]; 1 = row tok[b] of codec_emb [n_sem][H] bf16; >= 2 = row
+ * argmax(cp_logits[b]) of cp_emb [cp_vocab][H] bf16, recorded as codes[b][frame_idx[b]][pass - 1] while frame_idx[b] < max_frames.
+ * proj_tab (nullable, [table rows][proj_dim] f32) replaces the bf16 table for pass >= 1; qkv_tab (nullable, [table rows][qkv_dim]
+ * f32, qkv_dim % 4 == 0) is copied to qkv_out as well. Guarded (in/out): out [B][ld_out], qkv_out [B][ld_qkv_out], codes. */
+typedef struct q3_cp_gather_ex_args {
+    int pass, B, H, n_sem, cp_vocab, max_frames, proj_dim, qkv_dim, ld_out, ld_qkv_out, guard, reserved;
+    const float* last_hidden; const uint16_t* codec_emb; const uint32_t* tok; const uint16_t* cp_emb; const float* cp_logits;
+    const float* proj_tab; const float* qkv_tab; const int* frame_idx;
+    uint32_t* codes; float* out; float* qkv_out;
+} q3_cp_gather_ex_args;
+q3_status q3_cp_gather_ex(int device, const q3_cp_gather_ex_args* args);
+/* q3_rmsnorm_ex: launch_rmsnorm, or launch_rmsnorm_hold when frame_idx / text_ready [rows] are given (a row with frame_idx >=
+ * text_ready keeps its old output): y[y_front + r * ldy + c] = x[x_off + r * ldx + c] / sqrt(mean(x_r^2) + eps) * w[c]. x / y are
+ * host buffers of x_elems / y_elems floats; y is uploaded and copied back whole. */
+q3_status q3_rmsnorm_ex(int device, const float* x, long long x_elems, long long x_off, int ldx, const float* w, float* y, long long y_elems,
+                        long long y_front, int ldy, int rows, int cols, float eps, const int* frame_idx, const int* text_ready);
 /* Test API: channel norm of x [C][L] over C (launch_layernorm_c / launch_rmsnorm_c): layernorm != 0 takes w and b [C], else w only.
  * y: host buffer of y_elems floats, result at y_front, uploaded and copied back whole. */
 q3_status q3_norm_c(int device, int layernorm, const float* x, const float* w, const float* b, int C, int L, float eps,

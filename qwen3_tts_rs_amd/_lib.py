@@ -99,6 +99,32 @@ class CAttnCEx(ctypes.Structure):        # q3_attn_c_ex_args
                [(n, ctypes.c_void_p) for n in ("q", "k", "v", "rows", "caches", "tabs", "tab0", "tab_n", "o")]
 
 
+class CSampleRow(ctypes.Structure):      # q3_sample_rec (the sampler's per-row record)
+    _fields_ = [("inv_temp", ctypes.c_float), ("apply_temp", ctypes.c_int32), ("greedy", ctypes.c_int32), ("top_k", ctypes.c_int32),
+                ("top_p", ctypes.c_float), ("use_top_p", ctypes.c_int32), ("rep_pen", ctypes.c_float), ("rep_inv", ctypes.c_float),
+                ("use_rep", ctypes.c_int32), ("eos_id", ctypes.c_int32), ("min_new_tokens", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class CSampleEx(ctypes.Structure):       # q3_sample_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "vocab", "ld", "u_stride", "u_elems", "advance", "token_count_static", "hist_stride_b",
+                                              "hist_cap", "codec_eos", "use_suppress", "guard")] + [("scalar", CSampleRow)] + \
+               [(n, ctypes.c_void_p) for n in ("logits", "u", "draw_idx", "rows", "limit", "text_ready", "tok", "seen", "token_count",
+                                               "frame_idx", "pos", "logits_hist")]
+
+
+class CFrameEmbedEx(ctypes.Structure):   # q3_frame_embed_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "H", "n_sem", "cp_vocab", "max_frames", "n_text_rows", "guard", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("codec_emb", "cp_embs", "tok", "cp_logits_last", "frame_idx", "text_rows", "trail_base",
+                                               "trail_len", "pad_row", "text_ready", "codes", "out")]
+
+
+class CCpGatherEx(ctypes.Structure):     # q3_cp_gather_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("pass_", "B", "H", "n_sem", "cp_vocab", "max_frames", "proj_dim", "qkv_dim", "ld_out",
+                                              "ld_qkv_out", "guard", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("last_hidden", "codec_emb", "tok", "cp_emb", "cp_logits", "proj_tab", "qkv_tab", "frame_idx",
+                                               "codes", "out", "qkv_out")]
+
+
 class CClip(ctypes.Structure):           # q3_clip
     _fields_ = [("data", ctypes.c_void_p), ("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("sample_rate", ctypes.c_uint32),
                 ("format", ctypes.c_int32)]
@@ -266,6 +292,12 @@ SYMBOLS = {
     "q3_gather_frames_ex": (c_int, [c_int, c_void_p, ctypes.c_size_t, c_void_p, c_int, c_void_p, ctypes.c_size_t]),
     "q3_rvq_embed_ex": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int]),
     "q3_silu_mul_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong]),
+    "q3_sample_row": (c_int, [P(COptions), P(CSampleRow)]),
+    "q3_sample_ex": (c_int, [c_int, P(CSampleEx)]),
+    "q3_frame_embed_ex": (c_int, [c_int, P(CFrameEmbedEx)]),
+    "q3_cp_gather_ex": (c_int, [c_int, P(CCpGatherEx)]),
+    "q3_rmsnorm_ex": (c_int, [c_int, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_int, c_void_p, c_void_p, ctypes.c_longlong,
+                              ctypes.c_longlong, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]),
     "q3_norm_c": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_int, c_int]),
     "q3_dwconv7": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     "q3_decode_codes": (c_int, [c_void_p, c_void_p, c_int, c_void_p, P(c_void_p)]),

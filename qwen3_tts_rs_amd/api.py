@@ -2370,6 +2370,131 @@ def dwconv7(x: np.ndarray, w: np.ndarray, b: np.ndarray, y: Optional[np.ndarray]
     return y
 
 
+def _io(arr, dtype, n, name):
+    """a caller's in/out buffer: flat, C order, exactly n elements of dtype (written in place)"""
+    assert isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.flags.c_contiguous and arr.ndim == 1 and arr.size == n, (name, n)
+    return _vp(arr)
+
+
+def sample_row(options: SynthesisOptions) -> "_lib.CSampleRow":
+    """q3_sample_row: the sampler's per-row record as a session derives it from a request's options (host only)."""
+    r = _lib.CSampleRow(); o = options.to_c()
+    check(lib.q3_sample_row(ctypes.byref(o), ctypes.byref(r)))
+    return r
+
+
+def sample_ex(logits: np.ndarray, u: np.ndarray, vocab: int, tok: np.ndarray, scalar, *, rows=None, seen: Optional[np.ndarray] = None,
+              u_stride: int = 1, draw_idx=None, token_count: Optional[np.ndarray] = None, token_count_static: int = 0, advance: bool = False,
+              frame_idx: Optional[np.ndarray] = None, pos: Optional[np.ndarray] = None, limit=None, text_ready=None,
+              logits_hist: Optional[np.ndarray] = None, hist_stride_b: int = 0, hist_cap: int = 0, codec_eos: int = 2150,
+              use_suppress: bool = True, guard: int = 0, device: int = 0) -> np.ndarray:
+    """q3_sample_ex: ONE launch_sample through a complete SampleArgs. logits [B][ld] (ld >= vocab), u flat, scalar / rows[b]:
+    CSampleRow records (sample_row()). The in/out buffers are flat arrays with `guard` elements on both sides of the payload and are
+    written in place: tok u32 [B], seen u8 [B * vocab], token_count / frame_idx / pos i32 [B], logits_hist f32 [B * hist_stride_b].
+    Returns tok. Raises Q3Error (status 1) for arguments the entry refuses."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32); assert lg.ndim == 2
+    B, ld = lg.shape
+    uu = np.ascontiguousarray(u, dtype=np.float32).reshape(-1)
+    a = _lib.CSampleEx()
+    a.B, a.vocab, a.ld, a.u_stride, a.u_elems, a.advance, a.token_count_static = B, vocab, ld, u_stride, uu.size, int(advance), token_count_static
+    a.hist_stride_b, a.hist_cap, a.codec_eos, a.use_suppress, a.guard = hist_stride_b, hist_cap, codec_eos, int(use_suppress), guard
+    a.scalar = scalar
+    keep = [lg, uu]
+    a.logits, a.u = _vp(lg), _vp(uu)
+    a.tok = _io(tok, np.uint32, B + 2 * guard, "tok")
+    if seen is not None:
+        a.seen = _io(seen, np.uint8, B * vocab + 2 * guard, "seen")
+    for name, arr in (("token_count", token_count), ("frame_idx", frame_idx), ("pos", pos)):
+        if arr is not None:
+            setattr(a, name, _io(arr, np.int32, B + 2 * guard, name))
+    if logits_hist is not None:
+        a.logits_hist = _io(logits_hist, np.float32, B * hist_stride_b + 2 * guard, "logits_hist")
+    for name, arr in (("draw_idx", draw_idx), ("limit", limit), ("text_ready", text_ready)):
+        if arr is not None:
+            v = np.ascontiguousarray(arr, dtype=np.int32); assert v.shape == (B,), name
+            keep.append(v); setattr(a, name, _vp(v))
+    if rows is not None:
+        assert len(rows) == B
+        rr = (_lib.CSampleRow * B)(*rows); keep.append(rr)
+        a.rows = ctypes.cast(rr, ctypes.c_void_p)
+    check(lib.q3_sample_ex(device, ctypes.byref(a)))
+    return tok
+
+
+def frame_embed_ex(codec_emb: np.ndarray, cp_embs: np.ndarray, tok, cp_logits_last: np.ndarray, codes: np.ndarray, frame_idx, max_frames: int,
+                   text_rows: np.ndarray, trail_base, trail_len, pad_row, out: np.ndarray, text_ready=None, guard: int = 0, device: int = 0):
+    """q3_frame_embed_ex: ONE launch_frame_embed. codec_emb [n_sem][H] / cp_embs [15][cp_vocab][H] bf16 bits (u16), tok [B], cp_logits_last
+    [B][cp_vocab], text_rows [n][H] f32, per-row i32 lists. codes (u32, flat, guard + B * max_frames * 16 + guard) and out (f32, flat,
+    guard + B * H + guard) are written in place. Returns (out, codes)."""
+    ce = np.ascontiguousarray(codec_emb, dtype=np.uint16); pe = np.ascontiguousarray(cp_embs, dtype=np.uint16)
+    lg = np.ascontiguousarray(cp_logits_last, dtype=np.float32); tx = np.ascontiguousarray(text_rows, dtype=np.float32)
+    assert ce.ndim == 2 and pe.ndim == 3 and pe.shape[0] == 15 and pe.shape[2] == ce.shape[1] and lg.ndim == 2 and lg.shape[1] == pe.shape[1]
+    assert tx.ndim == 2 and tx.shape[1] == ce.shape[1]
+    B, H = lg.shape[0], ce.shape[1]
+    a = _lib.CFrameEmbedEx()
+    a.B, a.H, a.n_sem, a.cp_vocab, a.max_frames, a.n_text_rows, a.guard = B, H, ce.shape[0], pe.shape[1], max_frames, tx.shape[0], guard
+    tk = np.ascontiguousarray(tok, dtype=np.uint32); assert tk.shape == (B,)
+    keep = [ce, pe, lg, tx, tk]
+    a.codec_emb, a.cp_embs, a.cp_logits_last, a.text_rows, a.tok = _vp(ce), _vp(pe), _vp(lg), _vp(tx), _vp(tk)
+    for name, arr in (("frame_idx", frame_idx), ("trail_base", trail_base), ("trail_len", trail_len), ("pad_row", pad_row), ("text_ready", text_ready)):
+        if arr is not None:
+            v = np.ascontiguousarray(arr, dtype=np.int32); assert v.shape == (B,), name
+            keep.append(v); setattr(a, name, _vp(v))
+    a.codes = _io(codes, np.uint32, B * max_frames * 16 + 2 * guard, "codes")
+    a.out = _io(out, np.float32, B * H + 2 * guard, "out")
+    check(lib.q3_frame_embed_ex(device, ctypes.byref(a)))
+    return out, codes
+
+
+def cp_gather_ex(pass_: int, out: np.ndarray, ld_out: int, B: int, H: int, *, last_hidden=None, codec_emb=None, tok=None, cp_emb=None,
+                 cp_logits=None, proj_tab=None, qkv_tab=None, qkv_out: Optional[np.ndarray] = None, ld_qkv_out: int = 0,
+                 codes: Optional[np.ndarray] = None, frame_idx=None, max_frames: int = 0, guard: int = 0, device: int = 0):
+    """q3_cp_gather_ex: ONE launch_cp_gather for pass `pass_`. Tables: codec_emb [n_sem][H] / cp_emb [cp_vocab][H] bf16 bits, proj_tab
+    [rows][proj_dim] / qkv_tab [rows][qkv_dim] f32. out (f32, flat, guard + B * ld_out + guard), qkv_out (guard + B * ld_qkv_out + guard)
+    and codes (u32, guard + B * max_frames * 16 + guard) are written in place. Returns (out, qkv_out, codes)."""
+    a = _lib.CCpGatherEx()
+    a.pass_, a.B, a.H, a.max_frames, a.ld_out, a.ld_qkv_out, a.guard = pass_, B, H, max_frames, ld_out, ld_qkv_out, guard
+    keep = []
+
+    def put(name, arr, dtype, ndim):
+        if arr is None:
+            return None
+        v = np.ascontiguousarray(arr, dtype=dtype); assert v.ndim == ndim, name
+        keep.append(v); setattr(a, name, _vp(v))
+        return v
+    put("last_hidden", last_hidden, np.float32, 2)
+    ce = put("codec_emb", codec_emb, np.uint16, 2); pe = put("cp_emb", cp_emb, np.uint16, 2)
+    put("tok", tok, np.uint32, 1); lg = put("cp_logits", cp_logits, np.float32, 2); put("frame_idx", frame_idx, np.int32, 1)
+    pt = put("proj_tab", proj_tab, np.float32, 2); qt = put("qkv_tab", qkv_tab, np.float32, 2)
+    tabs = [t for t in (pt, qt, ce if pass_ == 1 else pe) if t is not None]
+    n_rows = tabs[0].shape[0] if tabs else 0
+    assert all(t.shape[0] == n_rows for t in tabs)
+    a.n_sem = n_rows if pass_ == 1 else 0
+    a.cp_vocab = lg.shape[1] if lg is not None else 0
+    assert pass_ < 2 or not tabs or n_rows == a.cp_vocab
+    a.proj_dim = 0 if pt is None else pt.shape[1]; a.qkv_dim = 0 if qt is None else qt.shape[1]
+    a.out = _io(out, np.float32, B * ld_out + 2 * guard, "out")
+    if qkv_out is not None:
+        a.qkv_out = _io(qkv_out, np.float32, B * ld_qkv_out + 2 * guard, "qkv_out")
+    if codes is not None:
+        a.codes = _io(codes, np.uint32, B * max_frames * 16 + 2 * guard, "codes")
+    check(lib.q3_cp_gather_ex(device, ctypes.byref(a)))
+    return out, qkv_out, codes
+
+
+def rmsnorm_ex(x: np.ndarray, w: np.ndarray, y: np.ndarray, rows: int, cols: int, *, x_off: int = 0, ldx: Optional[int] = None, y_front: int = 0,
+               ldy: Optional[int] = None, eps: float = 1e-6, frame_idx=None, text_ready=None, device: int = 0) -> np.ndarray:
+    """q3_rmsnorm_ex: ONE launch_rmsnorm (or launch_rmsnorm_hold with frame_idx / text_ready [rows]): row r reads x[x_off + r * ldx ..
+    + cols) and writes y[y_front + r * ldy ..). x, y: flat f32; y is written in place and returned whole."""
+    xx = np.ascontiguousarray(x, dtype=np.float32).reshape(-1); ww = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+    assert y.dtype == np.float32 and y.flags.c_contiguous and y.ndim == 1
+    fi = None if frame_idx is None else np.ascontiguousarray(frame_idx, dtype=np.int32)
+    tr = None if text_ready is None else np.ascontiguousarray(text_ready, dtype=np.int32)
+    check(lib.q3_rmsnorm_ex(device, _vp(xx), xx.size, x_off, cols if ldx is None else ldx, _vp(ww), _vp(y), y.size, y_front,
+                            cols if ldy is None else ldy, rows, cols, eps, _vp(fi), _vp(tr)))
+    return y
+
+
 def sample(logits: np.ndarray, u: np.ndarray, options: SynthesisOptions, seen: Optional[np.ndarray] = None,
            token_count: int = -1, device: int = 0) -> np.ndarray:
     """apply_generation_penalties + sample on the GPU (token_count < 0: plain `sample`, sampling.rs:140)."""

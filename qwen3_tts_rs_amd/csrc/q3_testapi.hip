@@ -1354,3 +1354,184 @@ extern "C" q3_status q3_row_move(int device, void* src_host, size_t src_bytes, v
     HIPC(q3_hipMemcpy(dst_host, dd, dst_bytes, hipMemcpyDeviceToHost));
     return Q3_OK;
 }
+
+// ---- the frame's sampler and seam kernels in their session forms (tests/test_gpu_sampler_op.py, tests/test_gpu_frame_seam.py) ----
+// Every entry checks its arguments before the first device call, uploads every buffer a kernel may write WITH the caller's guard
+// elements (`guard` in front of and behind it), runs ONE launch and copies those buffers back whole.
+namespace {
+template <typename T> hipError_t upload(DevPool& pool, T** dev, const T* host, size_t n) {
+    hipError_t e = pool.alloc(dev, n);
+    if (e != hipSuccess) return e;
+    return q3_hipMemcpy(*dev, host, n * sizeof(T), hipMemcpyHostToDevice);
+}
+static_assert(sizeof(q3_sample_rec) == sizeof(SampleRow), "q3_sample_rec is SampleRow");
+}  // namespace
+
+extern "C" q3_status q3_sample_row(const q3_options* o, q3_sample_rec* out) {
+    if (!o || !out) return set_err(Q3_INVALID_ARG, "q3_sample_row: null argument");
+    const SampleRow r = sample_row(*o);
+    memcpy(out, &r, sizeof r);
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_sample_ex(int device, const q3_sample_ex_args* p) {
+    if (!p || !p->logits || !p->u || !p->tok) return set_err(Q3_INVALID_ARG, "q3_sample_ex: null argument");
+    const int B = p->B, V = p->vocab, G = p->guard;
+    if (V < 2 || V > 4096) return set_err(Q3_INVALID_ARG, "q3_sample_ex: vocab %d outside 2..4096", V);
+    if (B < 1 || B > 1024 || G < 0 || G > 4096 || p->ld < V || p->ld > (1 << 16) || p->u_stride < 1 || p->u_elems < 1)
+        return set_err(Q3_INVALID_ARG, "q3_sample_ex: bad shape (B 1..1024, guard 0..4096, vocab <= ld <= 65536, u_stride >= 1, u_elems >= 1)");
+    if (p->advance && (!p->frame_idx || !p->pos)) return set_err(Q3_INVALID_ARG, "q3_sample_ex: advance needs frame_idx and pos");
+    if (p->logits_hist && (p->hist_cap < 0 || p->hist_cap > 4096 || (long long)p->hist_stride_b < (long long)p->hist_cap * V))
+        return set_err(Q3_INVALID_ARG, "q3_sample_ex: logits_hist needs 0 <= hist_cap <= 4096 and hist_stride_b >= hist_cap * vocab");
+    for (int b = 0; b < B; ++b) {
+        const long long d = p->draw_idx ? p->draw_idx[b] : 0, at = (long long)b * p->u_stride + d;
+        if (d < 0 || at >= p->u_elems) return set_err(Q3_INVALID_ARG, "q3_sample_ex: row %d draws u[%lld] of %d", b, at, p->u_elems);
+        const int tc = p->token_count ? p->token_count[G + b] : p->token_count_static;
+        if (p->logits_hist && tc < 0) return set_err(Q3_INVALID_ARG, "q3_sample_ex: row %d: token_count %d indexes logits_hist", b, tc);
+    }
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const size_t nB = (size_t)B + 2 * (size_t)G, n_seen = (size_t)B * V + 2 * (size_t)G, n_hist = (size_t)B * (size_t)p->hist_stride_b + 2 * (size_t)G;
+    float *lg, *u, *hist = nullptr; uint8_t* seen = nullptr; uint32_t* tok; int *tc = nullptr, *fi = nullptr, *pos = nullptr, *didx = nullptr, *lim = nullptr, *rdy = nullptr;
+    SampleRow* rows = nullptr;
+    HIPC(upload(pool, &lg, p->logits, (size_t)B * p->ld)); HIPC(upload(pool, &u, p->u, (size_t)p->u_elems)); HIPC(upload(pool, &tok, p->tok, nB));
+    if (p->seen) HIPC(upload(pool, &seen, p->seen, n_seen));
+    if (p->draw_idx) HIPC(upload(pool, &didx, const_cast<int*>(p->draw_idx), (size_t)B));
+    if (p->rows) HIPC(upload(pool, &rows, reinterpret_cast<SampleRow*>(const_cast<q3_sample_rec*>(p->rows)), (size_t)B));
+    if (p->token_count) HIPC(upload(pool, &tc, p->token_count, nB));
+    if (p->frame_idx) HIPC(upload(pool, &fi, p->frame_idx, nB));
+    if (p->pos) HIPC(upload(pool, &pos, p->pos, nB));
+    if (p->limit) HIPC(upload(pool, &lim, const_cast<int*>(p->limit), (size_t)B));
+    if (p->text_ready) HIPC(upload(pool, &rdy, const_cast<int*>(p->text_ready), (size_t)B));
+    if (p->logits_hist) HIPC(upload(pool, &hist, p->logits_hist, n_hist));
+    SampleArgs a; memset(&a, 0, sizeof a);
+    a.logits = lg; a.ld = p->ld; a.seen = seen ? seen + G : nullptr; a.u = u; a.u_stride = p->u_stride; a.draw_idx = didx; a.tok = tok + G;
+    a.token_count = tc ? tc + G : nullptr; a.token_count_static = p->token_count_static;
+    a.frame_idx = fi ? fi + G : nullptr; a.pos = pos ? pos + G : nullptr; a.advance = p->advance; a.rows = rows; a.limit = lim; a.text_ready = rdy;
+    a.logits_hist = hist ? hist + G : nullptr; a.hist_stride_b = p->hist_stride_b; a.hist_cap = p->hist_cap; a.vocab = V; a.B = B;
+    const q3_sample_rec& s = p->scalar;
+    a.inv_temp = s.inv_temp; a.apply_temp = s.apply_temp; a.greedy = s.greedy; a.top_k = s.top_k; a.top_p = s.top_p; a.use_top_p = s.use_top_p;
+    a.rep_pen = s.rep_pen; a.rep_inv = s.rep_inv; a.use_rep = s.use_rep; a.eos_id = s.eos_id; a.min_new_tokens = s.min_new_tokens;
+    a.codec_eos = p->codec_eos; a.use_suppress = p->use_suppress;
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_sample(a, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->tok, tok, nB * 4, hipMemcpyDeviceToHost));
+    if (seen) HIPC(q3_hipMemcpy(p->seen, seen, n_seen, hipMemcpyDeviceToHost));
+    if (tc) HIPC(q3_hipMemcpy(p->token_count, tc, nB * 4, hipMemcpyDeviceToHost));
+    if (fi) HIPC(q3_hipMemcpy(p->frame_idx, fi, nB * 4, hipMemcpyDeviceToHost));
+    if (pos) HIPC(q3_hipMemcpy(p->pos, pos, nB * 4, hipMemcpyDeviceToHost));
+    if (hist) HIPC(q3_hipMemcpy(p->logits_hist, hist, n_hist * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_frame_embed_ex(int device, const q3_frame_embed_ex_args* p) {
+    if (!p || !p->codec_emb || !p->cp_embs || !p->tok || !p->cp_logits_last || !p->codes || !p->frame_idx || !p->text_rows || !p->trail_base ||
+        !p->trail_len || !p->pad_row || !p->out)
+        return set_err(Q3_INVALID_ARG, "q3_frame_embed_ex: null argument");
+    const int B = p->B, H = p->H, V = p->cp_vocab, MF = p->max_frames, G = p->guard;
+    if (B < 1 || B > 1024 || H < 1 || H > 8192 || V < 1 || V > 65536 || MF < 1 || MF > 4096 || p->n_sem < 1 || p->n_sem > 65536 || p->n_text_rows < 1 ||
+        p->n_text_rows > (1 << 20) || G < 0 || G > 4096)
+        return set_err(Q3_INVALID_ARG, "q3_frame_embed_ex: bad shape (B 1..1024, H 1..8192, cp_vocab, n_sem 1..65536, max_frames 1..4096, guard 0..4096)");
+    for (int b = 0; b < B; ++b) {
+        const int f = p->frame_idx[b];
+        if (f < 0 || f > MF) return set_err(Q3_INVALID_ARG, "q3_frame_embed_ex: row %d: frame_idx %d outside [0, %d]", b, f, MF);
+        if (p->tok[b] >= (uint32_t)p->n_sem) return set_err(Q3_INVALID_ARG, "q3_frame_embed_ex: row %d: token %u outside the table", b, p->tok[b]);
+        const uint32_t* slot = p->codes + G + ((size_t)b * MF + (f < MF ? f : MF - 1)) * 16;
+        for (int g = 1; g < 15; ++g)
+            if (slot[g] >= (uint32_t)V) return set_err(Q3_INVALID_ARG, "q3_frame_embed_ex: row %d: code %d = %u outside the table", b, g, slot[g]);
+        const long long row = f < p->trail_len[b] ? (long long)p->trail_base[b] + f : (long long)p->pad_row[b];
+        if (row < 0 || row >= p->n_text_rows) return set_err(Q3_INVALID_ARG, "q3_frame_embed_ex: row %d: text row %lld of %d", b, row, p->n_text_rows);
+    }
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const size_t n_codes = (size_t)B * MF * 16 + 2 * (size_t)G, n_out = (size_t)B * H + 2 * (size_t)G, tab = (size_t)V * H;
+    uint16_t *sem, *embs; uint32_t *tok, *codes; float *lg, *text, *out; int *fi, *tb, *tl, *pr, *rdy = nullptr;
+    HIPC(upload(pool, &sem, const_cast<uint16_t*>(p->codec_emb), (size_t)p->n_sem * H)); HIPC(upload(pool, &embs, const_cast<uint16_t*>(p->cp_embs), 15 * tab));
+    HIPC(upload(pool, &tok, const_cast<uint32_t*>(p->tok), (size_t)B)); HIPC(upload(pool, &lg, const_cast<float*>(p->cp_logits_last), (size_t)B * V));
+    HIPC(upload(pool, &codes, p->codes, n_codes)); HIPC(upload(pool, &fi, const_cast<int*>(p->frame_idx), (size_t)B));
+    HIPC(upload(pool, &text, const_cast<float*>(p->text_rows), (size_t)p->n_text_rows * H));
+    HIPC(upload(pool, &tb, const_cast<int*>(p->trail_base), (size_t)B)); HIPC(upload(pool, &tl, const_cast<int*>(p->trail_len), (size_t)B));
+    HIPC(upload(pool, &pr, const_cast<int*>(p->pad_row), (size_t)B)); HIPC(upload(pool, &out, p->out, n_out));
+    if (p->text_ready) HIPC(upload(pool, &rdy, const_cast<int*>(p->text_ready), (size_t)B));
+    FrameEmbedArgs f{};
+    f.codec_emb = sem; for (int g = 0; g < 15; ++g) f.cp_embs[g] = embs + (size_t)g * tab;
+    f.tok = tok; f.cp_logits_last = lg; f.cp_vocab = V; f.codes = codes + G; f.frame_idx = fi; f.max_frames = MF;
+    f.text_rows = text; f.trail_base = tb; f.trail_len = tl; f.pad_row = pr; f.out = out + G; f.H = H; f.B = B; f.n_acoustic = 15; f.text_ready = rdy;
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_frame_embed(f, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->codes, codes, n_codes * 4, hipMemcpyDeviceToHost));
+    HIPC(q3_hipMemcpy(p->out, out, n_out * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_cp_gather_ex(int device, const q3_cp_gather_ex_args* p) {
+    if (!p || !p->out) return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: null argument");
+    const int B = p->B, H = p->H, V = p->cp_vocab, MF = p->max_frames, G = p->guard, pass = p->pass;
+    if (pass < 0 || pass > 15 || B < 1 || B > 1024 || H < 1 || H > 8192 || G < 0 || G > 4096)
+        return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: bad shape (pass 0..15, B 1..1024, H 1..8192, guard 0..4096)");
+    const bool proj = pass >= 1 && p->proj_tab, qkv = pass >= 1 && p->qkv_tab;
+    const int n_rows = pass == 1 ? p->n_sem : V, width = proj ? p->proj_dim : H;
+    if (pass == 0 && !p->last_hidden) return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: pass 0 needs last_hidden");
+    if (pass >= 1 && (n_rows < 1 || n_rows > 65536)) return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: table of %d rows", n_rows);
+    if (pass == 1 && (!p->tok || (!proj && !p->codec_emb))) return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: pass 1 needs tok and a table");
+    if (pass >= 2 && (!p->cp_logits || !p->codes || !p->frame_idx || (!proj && !p->cp_emb) || MF < 1 || MF > 4096))
+        return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: pass >= 2 needs cp_logits, codes, frame_idx, a table and max_frames 1..4096");
+    if (width < 1 || width > 8192 || p->ld_out < width) return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: ld_out %d below the row (%d)", p->ld_out, width);
+    if (qkv && (!p->qkv_out || p->qkv_dim < 4 || p->qkv_dim > 16384 || p->qkv_dim % 4 || p->ld_qkv_out < p->qkv_dim || p->ld_qkv_out % 4 || G % 4))
+        return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: qkv_tab needs qkv_out, qkv_dim a multiple of 4 (4..16384), ld_qkv_out >= qkv_dim, ld_qkv_out and guard multiples of 4");
+    for (int b = 0; b < B; ++b) {
+        if (pass == 1 && p->tok[b] >= (uint32_t)n_rows) return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: row %d: token %u outside the table", b, p->tok[b]);
+        if (pass >= 2 && p->frame_idx[b] < 0) return set_err(Q3_INVALID_ARG, "q3_cp_gather_ex: row %d: frame_idx %d", b, p->frame_idx[b]);
+    }
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const size_t n_out = (size_t)B * p->ld_out + 2 * (size_t)G, n_qkv = (size_t)B * p->ld_qkv_out + 2 * (size_t)G, n_codes = (size_t)B * MF * 16 + 2 * (size_t)G;
+    float *out, *qo = nullptr, *lh = nullptr, *lg = nullptr, *pt = nullptr, *qt = nullptr; uint16_t* emb = nullptr; uint32_t *tok = nullptr, *codes = nullptr; int* fi = nullptr;
+    HIPC(upload(pool, &out, p->out, n_out));
+    if (pass == 0) HIPC(upload(pool, &lh, const_cast<float*>(p->last_hidden), (size_t)B * H));
+    if (pass == 1) HIPC(upload(pool, &tok, const_cast<uint32_t*>(p->tok), (size_t)B));
+    if (pass >= 1 && !proj) HIPC(upload(pool, &emb, const_cast<uint16_t*>(pass == 1 ? p->codec_emb : p->cp_emb), (size_t)n_rows * H));
+    if (proj) HIPC(upload(pool, &pt, const_cast<float*>(p->proj_tab), (size_t)n_rows * p->proj_dim));
+    if (qkv) { HIPC(upload(pool, &qt, const_cast<float*>(p->qkv_tab), (size_t)n_rows * p->qkv_dim)); HIPC(upload(pool, &qo, p->qkv_out, n_qkv)); }
+    if (pass >= 2) {
+        HIPC(upload(pool, &lg, const_cast<float*>(p->cp_logits), (size_t)B * V)); HIPC(upload(pool, &codes, p->codes, n_codes));
+        HIPC(upload(pool, &fi, const_cast<int*>(p->frame_idx), (size_t)B));
+    }
+    CpGatherArgs a{};
+    a.pass = pass; a.last_hidden = lh; a.H = H; a.codec_emb = pass == 1 ? emb : nullptr; a.tok = tok; a.cp_emb = pass >= 2 ? emb : nullptr; a.cp_logits = lg;
+    a.cp_vocab = V; a.codes = codes ? codes + G : nullptr; a.frame_idx = fi; a.max_frames = MF; a.out = out + G; a.ld_out = p->ld_out;
+    a.proj_tab = pt; a.proj_dim = proj ? p->proj_dim : 0; a.qkv_tab = qt; a.qkv_dim = qkv ? p->qkv_dim : 0; a.qkv_out = qo ? qo + G : nullptr;
+    a.ld_qkv_out = p->ld_qkv_out; a.B = B;
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_cp_gather(a, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->out, out, n_out * 4, hipMemcpyDeviceToHost));
+    if (qo) HIPC(q3_hipMemcpy(p->qkv_out, qo, n_qkv * 4, hipMemcpyDeviceToHost));
+    if (codes) HIPC(q3_hipMemcpy(p->codes, codes, n_codes * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_rmsnorm_ex(int device, const float* x_host, long long x_elems, long long x_off, int ldx, const float* w_host, float* y_host,
+                                   long long y_elems, long long y_front, int ldy, int rows, int cols, float eps, const int* frame_idx,
+                                   const int* text_ready) {
+    if (!x_host || !w_host || !y_host) return set_err(Q3_INVALID_ARG, "q3_rmsnorm_ex: null argument");
+    if ((frame_idx == nullptr) != (text_ready == nullptr)) return set_err(Q3_INVALID_ARG, "q3_rmsnorm_ex: frame_idx and text_ready come together");
+    const long long lim = 1LL << 28;
+    if (rows < 1 || rows > 4096 || cols < 1 || cols > (1 << 16) || ldx < 1 || ldy < cols || x_off < 0 || y_front < 0 || x_elems < 1 || x_elems > lim ||
+        y_elems < 1 || y_elems > lim || x_off + (long long)(rows - 1) * ldx + cols > x_elems || y_front + (long long)(rows - 1) * ldy + cols > y_elems)
+        return set_err(Q3_INVALID_ARG, "q3_rmsnorm_ex: bad shape (rows 1..4096, cols 1..65536, ldx >= 1, ldy >= cols, every row inside its buffer)");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    float *x, *w, *y; int *fi = nullptr, *rdy = nullptr;
+    HIPC(upload(pool, &x, const_cast<float*>(x_host), (size_t)x_elems)); HIPC(upload(pool, &w, const_cast<float*>(w_host), (size_t)cols));
+    HIPC(upload(pool, &y, y_host, (size_t)y_elems));
+    if (frame_idx) { HIPC(upload(pool, &fi, const_cast<int*>(frame_idx), (size_t)rows)); HIPC(upload(pool, &rdy, const_cast<int*>(text_ready), (size_t)rows)); }
+    HIPC(q3_hipDeviceSynchronize());
+    if (fi) HIPC(launch_rmsnorm_hold(x + x_off, ldx, w, y + y_front, ldy, rows, cols, eps, fi, rdy, 0));
+    else HIPC(launch_rmsnorm(x + x_off, ldx, w, y + y_front, ldy, rows, cols, eps, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(y_host, y, (size_t)y_elems * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}

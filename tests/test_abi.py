@@ -143,6 +143,13 @@ def test_no_cpu_fallback():
                        (lambda: q.rvq_embed_ex(np.zeros((2, 16), np.uint32), np.zeros((4, 8), np.float32), np.zeros((15, 4, 8), np.float32),
                                                np.zeros(16, np.float32), np.zeros(16, np.float32)), "q3_rvq_embed_ex"),
                        (lambda: q.silu_mul_ex(np.zeros(8, np.float32), np.zeros(8, np.float32), np.zeros(8, np.float32)), "q3_silu_mul_ex"),
+                       (lambda: q.sample_ex(np.zeros((2, 8), np.float32), np.zeros(2, np.float32), 8, np.zeros(2, np.uint32), q.sample_row(q.SynthesisOptions())),
+                        "q3_sample_ex"),
+                       (lambda: q.frame_embed_ex(np.zeros((4, 8), np.uint16), np.zeros((15, 5, 8), np.uint16), [0], np.zeros((1, 5), np.float32),
+                                                 np.zeros(16, np.uint32), [0], 1, np.zeros((2, 8), np.float32), [0], [1], [1], np.zeros(8, np.float32)),
+                        "q3_frame_embed_ex"),
+                       (lambda: q.cp_gather_ex(0, np.zeros(8, np.float32), 8, 1, 8, last_hidden=np.zeros((1, 8), np.float32)), "q3_cp_gather_ex"),
+                       (lambda: q.rmsnorm_ex(np.zeros(8, np.float32), np.ones(8, np.float32), np.zeros(8, np.float32), 1, 8), "q3_rmsnorm_ex"),
                        (lambda: q.norm_c(np.zeros((16, 8), np.float32), np.ones(16, np.float32)), "q3_norm_c"),
                        (lambda: q.dwconv7(np.zeros((16, 8), np.float32), np.zeros((16, 7), np.float32), np.zeros(16, np.float32)), "q3_dwconv7")):
         try:
@@ -190,6 +197,18 @@ def test_codec_attn_entries_are_host_checked():
             assert e.status == 1, k
         else:
             raise AssertionError(f"bad shape {k} accepted")
+
+
+def test_sampler_and_seam_entries_are_host_checked():
+    """struct sizes of the sampler / frame-seam test entries, and q3_sample_row answering without a GPU (the refusals of each entry:
+    tests/test_sampler_reference.py, tests/test_frame_seam_reference.py)"""
+    assert ctypes.sizeof(_lib.CSampleRow) == 12 * 4
+    assert ctypes.sizeof(_lib.CSampleEx) == 12 * 4 + 12 * 4 + 12 * 8
+    assert ctypes.sizeof(_lib.CFrameEmbedEx) == 8 * 4 + 12 * 8
+    assert ctypes.sizeof(_lib.CCpGatherEx) == 12 * 4 + 11 * 8
+    r = q.sample_row(q.SynthesisOptions())
+    assert (r.apply_temp, r.greedy, r.top_k, r.use_top_p, r.use_rep, r.eos_id, r.min_new_tokens, r.pad) == (1, 0, 50, 1, 1, 2150, 2, 0)
+    assert r.inv_temp == np.float32(1.0 / 0.9) and r.top_p == np.float32(0.9) and r.rep_inv == np.float32(1.0) / np.float32(1.05)
 
 
 def test_speaker_language_tables():
@@ -276,6 +295,14 @@ def test_null_handles_return_status_not_crash():
         lambda: L.q3_gather_frames_ex(0, None, 16, None, 1, None, 16),
         lambda: L.q3_rvq_embed_ex(0, None, 1, None, None, 8, 16, None, None, 0, 8),
         lambda: L.q3_silu_mul_ex(0, None, None, None, 8, 8),
+        lambda: L.q3_sample_row(None, None),
+        lambda: L.q3_sample_ex(0, None),
+        lambda: L.q3_sample_ex(0, ctypes.byref(_lib.CSampleEx())),
+        lambda: L.q3_frame_embed_ex(0, None),
+        lambda: L.q3_frame_embed_ex(0, ctypes.byref(_lib.CFrameEmbedEx())),
+        lambda: L.q3_cp_gather_ex(0, None),
+        lambda: L.q3_cp_gather_ex(0, ctypes.byref(_lib.CCpGatherEx())),
+        lambda: L.q3_rmsnorm_ex(0, None, 8, 0, 8, None, None, 8, 0, 8, 1, 8, 1e-6, None, None),
         lambda: L.q3_norm_c(0, 0, None, None, None, 16, 8, 1e-6, None, 0, 128),
         lambda: L.q3_dwconv7(0, None, None, None, 16, 8, None, 0, 128),
     ]
