@@ -267,15 +267,15 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
         cs->stage_cap = (size_t)W * spf;
     }
     // the output stage's part of the plan: the delivered samples of its rows, where launch_copy_segs puts them
-    std::vector<PsSeg> psegs; std::vector<const CsPush*> pseg_of; PsPlan plan; bool trim = false;
+    std::vector<PsSeg> psegs; std::vector<const CsPush*> pseg_of; std::vector<void*> pouts; PsPlan plan;
     if (ps) {
         for (int i = 0; i < nP; ++i)
             if (P[i].ps) { psegs.push_back({P[i].ps_row, cs->stage + (size_t)out0[i] * spf, (size_t)(P[i].n - P[i].skip) * spf, P[i].last}); pseg_of.push_back(&P[i]); }
         for (const CsPush* f : flush) { psegs.push_back({f->ps_row, nullptr, 0, 1}); pseg_of.push_back(f); }
-        // (rows with a silence step, DESIGN 4.12e: what they hand on is known once their samples exist, so the stage is planned
-        // behind the vocoder, after the step's pre-pass)
-        trim = pcm_stage_has_trim(ps, psegs);
-        if (!trim) Q3C(pcm_stage_plan(ps, psegs, plan));
+        for (const CsPush* p : pseg_of) pouts.push_back(p->out_host);
+        // (with a silence step on some row, DESIGN 4.12e, what the rows hand on is known once their samples exist: plan.desc is
+        // then empty here, and the stage plans behind the vocoder, in pcm_stage_run)
+        Q3C(pcm_stage_begin(ps, psegs, plan));
     }
     float *A = ws.bufA, *B = ws.bufB, *C = ws.bufC, *F = ws.bufF;
     float* knew = A + (size_t)QD * N;                       // k | v of the new columns, [2*QD][N] (codec_front_transformer)
@@ -391,22 +391,11 @@ q3_status codec_stream_push(q3_codec_stream* cs, const std::vector<CsPush>& all)
     }
     bool raw = false;                                       // rows that take their 24 kHz f32 as it is (every row, without a stage)
     for (int i = 0; i < nP; ++i) raw = raw || !P[i].ps;
-    const PsDesc* ps_desc = (const PsDesc*)D(o_ps);
-    if (trim) {
-        Q3C(pcm_stage_trim(ps, psegs, st, plan));             // (waits for the stream: the kept counts come back)
-        Q3C(pcm_stage_plan(ps, psegs, plan));
-        if (!plan.desc.empty()) Q3C(pcm_stage_desc_upload(ps, plan, st, &ps_desc));
-    }
-    if (ps) HIPC(pcm_stage_launch(ps_desc, plan, st));
     if (W > 0 && raw) HIPC(hipMemcpyAsync(cs->stage_host, cs->stage, (size_t)W * spf * 4, hipMemcpyDeviceToHost, st));
-    if (plan.bytes > 0) HIPC(hipMemcpyAsync(pcm_stage_out_host(ps), pcm_stage_out_dev(ps), plan.bytes, hipMemcpyDeviceToHost, st));
+    if (ps) Q3C(pcm_stage_run(ps, psegs, plan, (const PsDesc*)D(o_ps), st));      // (with a silence step: waits for the stream once, its kept counts come back)
     HIPC(hipStreamSynchronize(st));
-    for (size_t k = 0; k < psegs.size(); ++k) {
-        const CsPush& p = *pseg_of[k];
-        if (p.out_host && plan.count[k] > 0) memcpy(p.out_host, pcm_stage_out_host(ps) + plan.off[k], plan.count[k] * pcm_stage_sample_bytes(ps, p.ps_row));
-        if (p.n_out) *p.n_out = plan.count[k];
-    }
-    if (ps) pcm_stage_commit(ps, psegs, plan);
+    if (ps) pcm_stage_finish(ps, psegs, plan, pouts.data(), nullptr);
+    for (size_t k = 0; k < psegs.size(); ++k) if (pseg_of[k]->n_out) *pseg_of[k]->n_out = plan.count[k];
     for (int i = 0; i < nP; ++i) {
         if (P[i].pcm_host && !P[i].ps) memcpy(P[i].pcm_host, cs->stage_host + (size_t)out0[i] * spf, (size_t)(P[i].n - P[i].skip) * spf * 4);
         cs->rows[P[i].row].pos += P[i].n;

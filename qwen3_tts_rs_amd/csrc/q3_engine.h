@@ -4,11 +4,9 @@
 //   q3_prefix_cache.hip the prefix cache: prefilled instruct pages shared across requests (q3_prefix_cache.h)
 //   q3_codec_run.hip device-memory cache, the vocoder pipeline (codec_decode_dev) and q3_decode_codes
 //   q3_codec_stream.hip the codec stream: the vocoder with per-row state, many rows per pass
-//   q3_pcm_stage.hip the output stage: per-row resampling to a requested rate and f32 / PCM16 conversion, and a
-//                    speaking rate per row by time-scale modification in front of it; G.711 bytes and a level per
-//                    row — a gain and a look-ahead peak limiter — between the two; a BS.1770 loudness meter and
-//                    normaliser per row in front of the level; a pitch per row in cents, a varispeed step behind the
-//                    stretcher
+//   q3_pcm_stage.hip the output stage, per row a chain of steps: silence trim and pause cap -> speaking rate
+//                    (WSOLA) -> pitch in cents (varispeed) -> BS.1770 loudness meter / normaliser -> level (gain and look-ahead peak
+//                    limiter) -> resampling to a requested rate as f32, PCM16 or G.711 bytes
 //   q3_intake.hip    the reference-audio intake: a clip in its on-disk sample format -> 24 kHz mono f32 on the device in one launch,
 //                    where both encoders read it
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
@@ -540,78 +538,17 @@ Q3_HIDDEN void codec_stream_blocks(const q3_codec_stream* cs, int row, int upto,
 Q3_HIDDEN void codec_stream_reset(q3_codec_stream* cs, int row);
 // q3_pcm_stage.hip
 // n samples of 24 kHz f32 on the device for stage row `row`; last: the row's input ends here (its tail is flushed)
-// (trimmed: set by pcm_stage_trim for a row with a silence step — dev and n are then what the step kept, in the stage's own buffer)
-struct PsSeg { int row; const float* dev; size_t n; int last; int trimmed = 0; };
+struct PsSeg { int row; const float* dev; size_t n; int last; };
 // one row of a pass of k_pcm_stage (device-visible, 8-byte aligned)
 struct PsDesc {
     const float* src; const float* tail_in; float* tail_out; const float* taps; void* out;
     long long base, i0;                     // input samples the row had consumed, first output index of this pass
     int n_new, n_out, L, M, fmt, pad;
 };
-// a checked push: descriptors of the rows that run, per segment the byte offset into the stage's staging buffer and the samples
-// one row of a pass of k_tempo (device-visible, 8-byte aligned): the row's stream is hist_in (from sample hist_lo on) below
-// `base`, the n_new samples of src from there, zeros from n_total on; frames k0 .. k1 - 1 run, n_y samples of y come out
-struct TpDesc {
-    const float* src; const float* hist_in; float* hist_out; const long long* p_in; long long* p_out; int* lags; float* y; const float* win;
-    long long base, n_total, hist_lo, lo_next, k0, k1;
-    int n_new, n_y, tempo, pad;
-};
-// one row of a pass of k_level (device-visible, 8-byte aligned): the row's stream into the level step is tail_in (its last 254
-// samples) below `base`, the n_new samples of src from there, nothing from n_total on; outputs o_base .. o_base + n_z - 1 go to z
-struct LvDesc {
-    const float* src; const float* tail_in; float* tail_out; float* z;
-    long long base, n_total, o_base;
-    int n_new, n_z; float g, c;
-};
-// one row of a pass of k_loud (device-visible, 8-byte aligned): samples base .. base + n_new - 1 of the row's stream into the loudness
-// step come from src; st_in (null at the row's start) / st_out are the two copies of its small state, hist its block values; w
-// (null in meter mode) receives the n_new normalised samples. coef: b0 b1 b2 a1 a2 of the shelf, then of the high-pass
-struct LoDesc {
-    const float* src; float* w; const float* st_in; float* st_out; float* hist;
-    long long base;
-    int n_new, mode; float T, P, gate, a_lo, a_hi; int pad;
-    float coef[10];
-};
-// one row of a pass of k_pitch (device-visible, 8-byte aligned): the row's stream into the pitch step is tail_in (its last 128
-// samples) below `base`, the n_new samples of src from there, zeros beyond; outputs j0 .. j0 + n_v - 1 go to v, output j at input
-// time j t / te. sc / w2: the stage's sinc and window tables. den1 = 20 max(t, te); dq1, dr1: quotient and remainder of
-// 19 S1 te by den1, what the sinc position advances by per tap; fc: (float)(0.95 min(1, te / t))
-struct PtDesc {
-    const float* src; const float* tail_in; float* tail_out; float* v; const float* sc; const float* w2;
-    long long base, j0;
-    int n_new, n_v, t, te, den1, dq1, dr1; float fc;
-};
-// one row of a pass of k_trim (device-visible, 8-byte aligned), DESIGN 4.12e: the row's stream into the silence step is head_in (the
-// undecided front of the run in progress, head hops from hop run + m on), tail_in (its last `tail` samples) below `base`, the n_new
-// samples of src from there, zeros from n_total on. Hops c_old .. c_end - 1 get their energy in this pass, hops k_old .. k_new - 1
-// are classified; st_in (null at the row's start) / st_out: the two copies of the row's TR_ST counters, res: st_out again, where the
-// host reads it; y: the kept samples, ops: the kept hops (source hop, seam partner or -1), fl: loud and active flags of the pass
-struct TrDesc {
-    const float* src; const float* tail_in; float* tail_out; const float* head_in; float* head_out;
-    const long long* st_in; long long* st_out; long long* res;
-    float* y; int* ops; unsigned char* fl; const float* win;
-    long long base, n_total, c_old, c_end, c_new, k_old, k_new;
-    int n_new, last, E, P1, P2, tail, head, cap_ops; float theta; int fl_n;
-    int tail_lead, tail_run;                // what tail_out takes: behind a leading run in progress, and otherwise (tail: what tail_in holds)
-};
-// the pre-pass of a push with silence steps: per such segment its index, what entered the step and the counters it left
-struct PsTrim { std::vector<int> seg; std::vector<long long> n_new; std::vector<long long> res; };
-// (tdesc, t_y, t_k1: the time stretcher in front, DESIGN 4.12a — the rows at a tempo other than 1000, per segment the y samples of
-// this push and the frame the row reaches; pcm_stage_launch uploads tdesc itself, into the stage's own buffer.
-// ldesc, l_in, l_z, l_tiles: the level step between the two, DESIGN 4.12b — the rows with a level, per segment the samples that
-// enter the step and leave it in this push; its descriptors go up the same way.
-// odesc, o_n: the loudness step between the stretcher and the level, DESIGN 4.12c — the rows that meter or normalise, per segment
-// the samples that pass the step in this push.
-// pdesc, p_n, p_v, p_tiles: the pitch step behind the stretcher, DESIGN 4.12d — the rows whose effective tempo differs from
-// their tempo, per segment the samples that enter the step and leave it in this push)
-struct PsPlan {
-    std::vector<PtDesc> pdesc; std::vector<long long> p_n, p_v; int p_tiles = 1;
-    std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t bytes = 0; int max_tiles = 1;
-    q3_pcm_stage* ps = nullptr; std::vector<TpDesc> tdesc; std::vector<long long> t_y, t_k1;
-    std::vector<LvDesc> ldesc; std::vector<long long> l_in, l_z; int l_tiles = 1;
-    std::vector<LoDesc> odesc; std::vector<long long> o_n;
-    PsTrim trim;                             // filled by pcm_stage_trim in front of pcm_stage_plan, which leaves it alone
-};
+// The public part of a push's plan: the resampler's descriptors of the rows that run, and per segment the byte offset into the
+// stage's staging buffer and the samples it returns. late: a row has a silence step, so the plan is made by pcm_stage_run, behind
+// that step's pre-pass. What the other steps of the chain need for the push is the stage's own business.
+struct PsPlan { std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t bytes = 0; bool late = false; };
 // q3_resample's filter as a table for output / input = L / M in lowest terms, out[L][128] (taps_of): the output stage's at
 // L / M = sr_out / 24000, the intake's (q3_intake.hip) at L / M = 24000 / sr_in
 Q3_HIDDEN void resampler_taps(int L, int M, std::vector<float>& out);
@@ -623,16 +560,18 @@ Q3_HIDDEN q3_status pcm_stage_loud_checked(const char* who, int mode, int target
 Q3_HIDDEN q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_rows, const int* rows);
 Q3_HIDDEN size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last);
 Q3_HIDDEN q3_status pcm_stage_silence_checked(const char* who, int threshold_mB, int edge_ms, int pause_ms);      // the ranges of q3_pcm_stage_set_silence
-// Rows with a silence step: whether a push has one; the pre-pass — k_trim for those segments on `st` (which has the
-// samples), their counters back, a wait — that replaces their dev / n by what the step kept and fills plan.trim for the commit
-Q3_HIDDEN bool pcm_stage_has_trim(const q3_pcm_stage* ps, const std::vector<PsSeg>& segs);
-Q3_HIDDEN q3_status pcm_stage_trim(q3_pcm_stage* ps, std::vector<PsSeg>& segs, hipStream_t st, PsPlan& plan);
-Q3_HIDDEN q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan);
-Q3_HIDDEN q3_status pcm_stage_desc_upload(q3_pcm_stage* ps, const PsPlan& plan, hipStream_t st, const PsDesc** desc_dev);
-Q3_HIDDEN hipError_t pcm_stage_launch(const PsDesc* desc_dev, const PsPlan& plan, hipStream_t st);
-Q3_HIDDEN void pcm_stage_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const PsPlan& plan);
-Q3_HIDDEN const char* pcm_stage_out_dev(const q3_pcm_stage* ps);
-Q3_HIDDEN char* pcm_stage_out_host(const q3_pcm_stage* ps);
+// A push of segments that are on the device, in three calls (one push per stage at a time; the rows move on in the last one alone):
+// begin   checks the segments and, unless a row has a silence step (plan.late), makes the plan: a caller with a descriptor block of
+//         its own can then carry plan.desc in it
+// run     on `st`, which has the samples: where the plan is late, the silence step's pre-pass (a wait for `st`: its kept counts come
+//         back), the plan, and plan.desc into the stage's own staging; then every step's launch, and the copy of the converted bytes
+//         to the stage's pinned buffer. desc_dev: where the caller has put plan.desc on the device (null: the stage uploads it)
+// finish  after the caller's wait for `st`: segment i's plan.count[i] samples to out_host[i] (may be null), the counts to n_samples
+//         (may be null), and the commit
+Q3_HIDDEN q3_status pcm_stage_begin(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan);
+Q3_HIDDEN q3_status pcm_stage_run(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan, const PsDesc* desc_dev, hipStream_t st);
+Q3_HIDDEN void pcm_stage_finish(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const PsPlan& plan, void* const* out_host, size_t* n_samples);
+// the three in a row, with the wait (st null: the stage's own stream)
 Q3_HIDDEN q3_status pcm_stage_push_dev(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, hipStream_t st, void* const* out_host, size_t* n_samples);
 // q3_session.hip
 Q3_HIDDEN hipError_t sync_frames(q3_session* s);

@@ -1,58 +1,104 @@
-// q3_pcm_stage.hip — the output stage: 24 kHz f32 from the vocoder -> a requested sample rate, f32 or PCM16, per row
-// (a unit of the engine: q3_engine.h says which holds what)
+// q3_pcm_stage.hip — the output stage: 24 kHz f32 from the vocoder -> per row a requested sample rate and format, through the
+// steps the row has asked for. (A unit of the engine: q3_engine.h says which holds what.)
 //
-// The resampler is q3_resample's (q3_io.cpp): a 128-tap Blackman-Harris²-windowed sinc at 0.95 x the lower Nyquist, output i at
-// input time i * M / L with L / M = sr_out / 24000 in lowest terms. What the host loop evaluates per output sample in f64 is a
-// function of the phase p = (i * M) mod L alone, so it is tabulated once per rate: taps[L][128] (f64, rounded to f32), and output i
-// is the dot product of row p with inputs c - 63 .. c + 64, c = floor(i * M / L): f32 products, accumulated in a fixed order.
+// A row's stream passes a chain of six steps, front to back: silence -> stretcher -> pitch -> loudness -> level -> resampler /
+// format. The last one every row has; each of the others is on for the rows that ask for it, and a row whose step is off is not
+// touched by any of it: no launch, no buffer, no descriptor, no allocation. Every step counts the samples that have entered and
+// left it, keeps what the next push still needs on the device in two copies — a push reads one and writes the other, and they are
+// flipped when the push has succeeded: a push that fails or is refused leaves the row exactly where it was — and writes a push's
+// samples into the row's part of a buffer of its own (s, y, v, w, z), which the next step that is on takes as the row's input.
+// One launch per step serves every row of a push that has the step, a descriptor per row. The host side further down writes the
+// chain once (step_on, step_emitted, step_cap, chain_walk); the count, the plan and the commit of a push are three uses of it.
 //
-// Streaming: a row emits output i once input c + 64 has arrived (and, with `last`, everything up to llround(n_in * sr_out / 24000)
-// against zeros). The next output to emit then starts no earlier than 127 samples before the end of what has arrived, so a row
-// keeps its last 128 input samples — two buffers, read one / write the other in the same launch, flipped when the push has
-// succeeded: a push that fails or is refused leaves the row exactly where it was.
+// 1. The silence step. k_trim takes the energy of every 10 ms hop of the row's 24 kHz stream, calls a hop active
+// when a hop within 20 ms of it is above a threshold, and drops what a run of non-active hops has beyond an edge (at the stream's
+// two ends) or beyond a cap (inside it, with one crossfaded hop at the seam). How many samples leave depends on the data, so a push
+// with such a row runs in two passes: k_trim into s, the kept counts back to the host, then the plan and the launches of the
+// steps behind. The row keeps the input whose fate is open (the last hops, and the front of the run in progress) and its counters.
+// A push without such a row is a single pass.
 //
-// One launch serves every row of a push: grid (output tile, row), a descriptor per row. A block stages its tile's input window
-// (kept tail | new samples | zeros) in LDS and computes one output per thread; tile 0 of a row also writes the row's next tail.
+// 2. The stretcher: a speaking rate. k_tempo stretches the stream by WSOLA — frames of 720 samples every 360 of the
+// output, each taken from where the input continues the frame before it best within +-240 samples of its nominal place — into y.
+// Which frames a push reaches follows from the sample counts alone (tempo_frames), so the host never reads a count back; the row
+// keeps the input the next frame can still touch and the last frame's position. It runs at the effective tempo te, which is the
+// row's tempo t moved by its pitch; a row at te = 1000 has no stretcher.
 //
-// In front of the resampler, for the rows that ask for it: a speaking rate. k_tempo stretches the row's 24 kHz
-// stream by WSOLA — frames of 720 samples every 360 of the output, each taken from where the input continues the frame before it
-// best within +-240 samples of its nominal place — into the row's part of a y buffer, which k_pcm_stage then takes as the row's
-// input. Which frames a push reaches follows from the sample counts alone (tempo_frames), so the host never reads a count back;
-// the row keeps the input the next frame can still touch and the last frame's position, in two copies flipped like the tails.
-// A row at tempo 1000 is not touched by any of it.
+// 3. The pitch step: a pitch in cents. With te = llround(t / 2^(c / 1200)) in the place of t in the stretcher,
+// k_pitch resamples the stretcher's output by te / t into v: q3_resample's filter, at a ratio whose table taps[te][128] would be
+// too large to build per request, so the taps are evaluated per output from two tables that serve every ratio: the sinc at 512
+// points per zero crossing and the squared window at 64 points per tap, both interpolated linearly at positions that integer
+// arithmetic splits exactly into an index and a remainder. It holds 64 samples back like the resampler and keeps the row's last 128
+// inputs. A row whose te equals its t (0 cents) has no pitch step.
 //
-// Between the two, for the rows that ask for it: a level. k_level multiplies the row's 24 kHz stream by a gain and
-// by the mean, over 128 samples, of the minima, over 128 samples, of the reduction each sample needs to stay under a ceiling: a
-// look-ahead peak limiter whose output is a function of the sample index alone. It holds 127 samples back, keeps the row's last
-// 254 inputs in two copies flipped like the tails, and writes into the row's part of a z buffer that k_pcm_stage then takes as
-// the row's input. A row without a level is not touched by any of it.
+// 4. The loudness step. k_loud K-weights the stream (ITU-R BS.1770-4: two biquads), keeps the energy of every 100 ms
+// hop and the mean square of every 400 ms block, gates the blocks the row has seen so far (absolute and relative gate) into its
+// integrated loudness, and — where the row normalises — multiplies the stream by a gain that ramps, hop by hop, toward the one that
+// would bring that loudness to a target, into w. A hop's gain depends on the hops that ended before it alone, so the step holds
+// nothing back: n samples leave for n that enter (a row that only meters hands its input on as it is). The row keeps its filter
+// states, partial sums, last energies and gains in two copies, its block values append-only.
 //
-// In front of the level, for the rows that ask for it: a loudness step. k_loud K-weights the row's 24 kHz stream
-// (ITU-R BS.1770-4: two biquads), keeps the energy of every 100 ms hop and the mean square of every 400 ms block, gates the
-// blocks the row has seen so far (absolute and relative gate) into its integrated loudness, and — where the row normalises —
-// multiplies the stream by a gain that ramps, hop by hop, toward the one that would bring that loudness to a target. A hop's gain
-// depends on the hops that ended before it alone, so the step holds nothing back: n samples leave, into the row's part of a w
-// buffer, for n that enter. The row keeps its filter states, partial sums, last energies and gains in two copies flipped like the
-// tails, its block values append-only. A row whose step is off is not touched by any of it.
+// 5. The level step. k_level multiplies the stream by a gain and by the mean, over 128 samples, of the minima, over
+// 128 samples, of the reduction each sample needs to stay under a ceiling: a look-ahead peak limiter whose output is a function of
+// the sample index alone, into z. It holds 127 samples back and keeps the row's last 254 inputs.
 //
-// Behind the stretcher, for the rows that ask for it: a pitch in cents. The stretcher runs at the effective tempo
-// te = llround(t / 2^(c / 1200)) in the place of the row's tempo t, and k_pitch resamples its output by te / t: q3_resample's filter
-// again, at a ratio whose table taps[te][128] would be too large to build per request, so the taps are evaluated per output from
-// two tables that serve every ratio: the sinc at 512 points per zero crossing and the squared window at 64 points per tap, both
-// interpolated linearly at positions that integer arithmetic splits exactly into an index and a remainder. It holds 64 samples
-// back like the resampler, keeps the row's last 128 inputs in two copies flipped like the tails, and writes into the row's part of
-// a v buffer that the steps behind take as the row's stream. A row at 0 cents is not touched by any of it.
-//
-// At the very front, for the rows that ask for it: a silence step. k_trim takes the energy of every 10 ms hop of the
-// row's 24 kHz stream, calls a hop active when a hop within 20 ms of it is above a threshold, and drops what a run of non-active
-// hops has beyond an edge (at the stream's two ends) or beyond a cap (inside it, with one crossfaded hop at the seam). How many
-// samples leave depends on the data, so a push with such a row runs in two passes: k_trim into the row's part of an s buffer, the
-// kept counts back to the host, then the plan and the launches of the steps behind, which take s as the row's input. The row keeps
-// the input whose fate is open (the last hops, and the front of the run in progress) and its counters, in two copies flipped like
-// the tails. A row whose step is off is not touched by any of it, and a push without such a row is the single pass it was.
-//
-// Formats: f32, PCM16, and G.711 mu-law / A-law — the companding of the PCM16 value, one byte per sample.
+// 6. The resampler and the format. The filter is q3_resample's (q3_io.cpp): a 128-tap Blackman-Harris²-windowed sinc
+// at 0.95 x the lower Nyquist, output i at input time i * M / L with L / M = sr_out / 24000 in lowest terms. What the host loop
+// evaluates per output sample in f64 is a function of the phase p = (i * M) mod L alone, so it is tabulated once per rate:
+// taps[L][128] (f64, rounded to f32), and output i is the dot product of row p with inputs c - 63 .. c + 64, c = floor(i * M / L):
+// f32 products, accumulated in a fixed order. A row emits output i once input c + 64 has arrived (and, with `last`, everything up
+// to llround(n_in * sr_out / 24000) against zeros). The next output to emit then starts no earlier than 127 samples before the
+// end of what has arrived, so a row keeps its last 128 input samples. k_pcm_stage's grid is (output tile, row): a block stages its
+// tile's input window (kept tail | new samples | zeros) in LDS and computes one output per thread; tile 0 of a row also writes
+// the row's next tail. Formats: f32, PCM16, and G.711 mu-law / A-law — the companding of the PCM16 value, one byte per sample.
 #include "q3_engine.h"
+
+// The steps' descriptors: one row of a pass of a step's kernel each (device-visible, 8-byte aligned). PsDesc, the resampler's, is
+// in q3_engine.h: a codec stream carries it in its own descriptor block.
+// k_trim, DESIGN 4.12e: the row's stream into the silence step is head_in (the
+// undecided front of the run in progress, head hops from hop run + m on), tail_in (its last `tail` samples) below `base`, the n_new
+// samples of src from there, zeros from n_total on. Hops c_old .. c_end - 1 get their energy in this pass, hops k_old .. k_new - 1
+// are classified; st_in (null at the row's start) / st_out: the two copies of the row's TR_ST counters, res: st_out again, where the
+// host reads it; y: the kept samples, ops: the kept hops (source hop, seam partner or -1), fl: loud and active flags of the pass
+struct TrDesc {
+    const float* src; const float* tail_in; float* tail_out; const float* head_in; float* head_out;
+    const long long* st_in; long long* st_out; long long* res;
+    float* y; int* ops; unsigned char* fl; const float* win;
+    long long base, n_total, c_old, c_end, c_new, k_old, k_new;
+    int n_new, last, E, P1, P2, tail, head, cap_ops; float theta; int fl_n;
+    int tail_lead, tail_run;                // what tail_out takes: behind a leading run in progress, and otherwise (tail: what tail_in holds)
+};
+// k_tempo: the row's stream is hist_in (from sample hist_lo on) below
+// `base`, the n_new samples of src from there, zeros from n_total on; frames k0 .. k1 - 1 run, n_y samples of y come out
+struct TpDesc {
+    const float* src; const float* hist_in; float* hist_out; const long long* p_in; long long* p_out; int* lags; float* y; const float* win;
+    long long base, n_total, hist_lo, lo_next, k0, k1;
+    int n_new, n_y, tempo, pad;
+};
+// k_pitch: the row's stream into the pitch step is tail_in (its last 128
+// samples) below `base`, the n_new samples of src from there, zeros beyond; outputs j0 .. j0 + n_v - 1 go to v, output j at input
+// time j t / te. sc / w2: the stage's sinc and window tables. den1 = 20 max(t, te); dq1, dr1: quotient and remainder of
+// 19 S1 te by den1, what the sinc position advances by per tap; fc: (float)(0.95 min(1, te / t))
+struct PtDesc {
+    const float* src; const float* tail_in; float* tail_out; float* v; const float* sc; const float* w2;
+    long long base, j0;
+    int n_new, n_v, t, te, den1, dq1, dr1; float fc;
+};
+// k_loud: samples base .. base + n_new - 1 of the row's stream into the loudness
+// step come from src; st_in (null at the row's start) / st_out are the two copies of its small state, hist its block values; w
+// (null in meter mode) receives the n_new normalised samples. coef: b0 b1 b2 a1 a2 of the shelf, then of the high-pass
+struct LoDesc {
+    const float* src; float* w; const float* st_in; float* st_out; float* hist;
+    long long base;
+    int n_new, mode; float T, P, gate, a_lo, a_hi; int pad;
+    float coef[10];
+};
+// k_level: the row's stream into the level step is tail_in (its last 254
+// samples) below `base`, the n_new samples of src from there, nothing from n_total on; outputs o_base .. o_base + n_z - 1 go to z
+struct LvDesc {
+    const float* src; const float* tail_in; float* tail_out; float* z;
+    long long base, n_total, o_base;
+    int n_new, n_z; float g, c;
+};
 
 namespace {
 constexpr int PS_TILE = 256;                     // outputs per block, one per thread
@@ -795,64 +841,210 @@ bool fmt_ok(int fmt) { return fmt >= Q3_PCM_F32 && fmt <= Q3_PCM_ALAW; }
 
 void resampler_taps(int L, int M, std::vector<float>& out) { Rate r; r.L = L; r.M = M; taps_of(r, out); }
 
-struct PsRow {
+// ---- buffers ----
+// A device buffer of a push. It grows by free, then 2 x the request: no push is in flight (each ends with a wait).
+struct DevBuf {
+    char* dev = nullptr; size_t cap = 0;
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = dev_malloc((void**)&dev, bytes * 2);
+        if (e == hipSuccess) cap = bytes * 2;
+        return e;
+    }
+    void release() { dev_free(dev); dev = nullptr; cap = 0; }
+};
+// ... with a pinned host twin: what a push sends up (descriptors, samples) or takes back (converted samples, counters)
+struct PairBuf {
+    char *dev = nullptr, *host = nullptr; size_t cap = 0;
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        hipError_t e = dev_malloc((void**)&dev, bytes * 2);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&host, bytes * 2, hipHostMallocDefault);
+        if (e == hipSuccess) cap = bytes * 2;
+        return e;
+    }
+    hipError_t upload(const void* src, size_t bytes, hipStream_t st) {
+        const hipError_t e = reserve(bytes);
+        if (e != hipSuccess) return e;
+        memcpy(host, src, bytes);
+        return hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st);
+    }
+    void release() {
+        dev_free(dev); dev = nullptr;
+        if (host) { (void)hipHostFree(host); host = nullptr; }
+        cap = 0;
+    }
+};
+
+// ---- a row: its steps in chain order ----
+// Every step holds its setting, the running totals of the samples that have entered and left it since the row's (re)start, and its
+// state on the device in two copies: a push reads copy `cur` and writes the other, the commit flips. Between two steps that are on,
+// what has left the one in front is what has entered the one behind.
+struct Totals { long long in = 0, out = 0; };
+struct SilStep : Totals {                     // DESIGN 4.12e; thr == 0: off
+    int thr = 0, edge = 0, pause = 0; TrSet set = {0, 0, 0}; float theta = 0.0f;
+    long long read[TR_ST] = {0, -1, 0, 0, 0, 0, 0, 0};        // the counters after the last successful push (the host's copy)
+    char* state = nullptr; size_t copy = 0, cap = 0; int cur = 0;      // two copies of `copy` bytes: [TR_ST counters | tail | head]
+    void reset() { in = out = 0; for (int i = 0; i < TR_ST; ++i) read[i] = i == TR_S_RUN ? -1 : 0; }
+};
+struct TempoStep : Totals {                   // DESIGN 4.12a; te: the tempo the stretcher runs at (PitchStep), 1000: off
+    int te = TP_OFF;
+    long long frames = 0;                     // frames computed
+    char* state = nullptr; int cur = 0;       // two copies: [last frame's position (16 bytes) | TP_HIST floats of input]
+    DevBuf lags[2]; int lag_cur = 0; long long lag_k0 = 0, lag_n = 0;      // the lags of a push: lag_cur holds the last successful push's
+    void reset() { in = out = 0; frames = 0; lag_k0 = lag_n = 0; }
+};
+struct PitchStep : Totals {                   // DESIGN 4.12d; the row's tempo t and pitch are one setting (tempo_pitch_set): the
+    int cents = 0, t = TP_OFF, te = TP_OFF;   // stretcher runs at te, this step brings the duration back to t; te == t: off
+    float* tail = nullptr; int cur = 0;       // two copies of 128 floats: the last 128 inputs
+    void reset() { in = out = 0; }
+};
+struct LoudStep : Totals {                    // DESIGN 4.12c; out == in: the step holds nothing back
+    int mode = Q3_LOUD_OFF, target = -1900, prior = 0; float T = 0.0f, P = 1.0f, gate = 0.0f, lo = 0.0f, hi = 0.0f;
+    float* state = nullptr; int cur = 0;      // two copies of LD_STATE floats, then the LD_HIST block values (one copy)
+    void reset() { in = out = 0; }
+};
+struct LevelStep : Totals {
+    bool on = false; int gain_mB = 0, ceil_mB = 0; float g = 1.0f, c = 1.0f;
+    float* tail = nullptr; int cur = 0;       // two copies of LV_TAIL_PITCH floats: the last 254 inputs
+    void reset() { in = out = 0; }
+};
+struct ResStep : Totals {                     // the resampler and the format; every row has it
     uint32_t sr = PS_RATE_IN; int fmt = Q3_PCM_F32; Rate r; const float* taps = nullptr;
-    long long n_in = 0, n_out = 0;            // input samples consumed, output samples emitted
-    int cur = 0; bool fresh = true;           // which of the two tail buffers holds the last 128 inputs; fresh: none yet (zeros)
+    int cur = 0; bool fresh = true;           // which of the row's two tails (q3_pcm_stage::tails) holds the last 128 inputs; fresh: none yet (zeros)
+    void reset() { in = out = 0; cur = 0; fresh = true; }
+};
+struct PsRow {
+    SilStep sil; TempoStep tp; PitchStep pt; LoudStep ld; LevelStep lv; ResStep rs;
     bool ended = false;                       // flushed by a push with `last`: restarted by set / reset only
-    // the time stretcher in front (tempo != 1000: n_in then counts its output y, the resampler's input)
-    int tempo = TP_OFF;
-    long long t_in = 0, t_frames = 0;         // 24 kHz samples consumed, frames computed
-    char* t_state = nullptr; int t_cur = 0;   // on the device, two copies: [last frame's position (16 bytes) | TP_HIST floats of input]
-    int* t_lags[2] = {nullptr, nullptr}; size_t t_lag_cap[2] = {0, 0};      // the lags of a push, two buffers: t_lag_cur holds the last successful push's
-    int t_lag_cur = 0; long long t_lag_k0 = 0, t_lag_n = 0;
-    // the level step between the two (level: n_in then counts its output z, the resampler's input; l_in what has entered it)
-    bool level = false; int gain_mB = 0, ceil_mB = 0; float l_g = 1.0f, l_c = 1.0f;
-    long long l_in = 0;
-    float* l_tail = nullptr; int l_cur = 0;   // on the device, two copies of LV_TAIL_PITCH floats: the last 254 inputs
-    // the loudness step in front of the level: o_in counts the 24 kHz samples that have passed it
-    int loud = Q3_LOUD_OFF, o_target = -1900, o_prior = 0; float o_T = 0.0f, o_P = 1.0f, o_gate = 0.0f, o_lo = 0.0f, o_hi = 0.0f;
-    long long o_in = 0;
-    float* o_state = nullptr; int o_cur = 0;  // on the device: two copies of LD_STATE floats, then the LD_HIST block values (one copy)
-    // the pitch step behind the stretcher: te is the tempo the stretcher runs at (te == tempo: the step is off)
-    int pitch = 0, te = TP_OFF;
-    long long p_in = 0, p_out = 0;            // samples that have entered the step, and left it
-    float* p_tail = nullptr; int p_cur = 0;   // on the device, two copies of 128 floats: the last 128 inputs
-    // the silence step at the very front: s_thr == 0: off; s_in counts the 24 kHz samples that have entered it
-    int s_thr = 0, s_edge = 0, s_pause = 0; TrSet s_set = {0, 0, 0}; float s_theta = 0.0f;
-    long long s_in = 0;
-    long long s_read[TR_ST] = {0, -1, 0, 0, 0, 0, 0, 0};      // the counters after the last successful push (the host's copy)
-    char* s_state = nullptr; size_t s_copy = 0, s_cap = 0; int s_cur = 0;      // on the device, two copies of s_copy bytes: [TR_ST counters | tail | head]
+    void reset() { sil.reset(); tp.reset(); pt.reset(); ld.reset(); lv.reset(); rs.reset(); ended = false; }
 };
 constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
+
+// ---- the chain, written once ----
+enum { ST_SIL, ST_TEMPO, ST_PITCH, ST_LOUD, ST_LEVEL, ST_RES, ST_N };
+static bool step_on(const PsRow& r, int s) {
+    switch (s) {
+    case ST_SIL: return r.sil.thr != 0;
+    case ST_TEMPO: return r.tp.te != TP_OFF;
+    case ST_PITCH: return r.pt.te != r.pt.t;
+    case ST_LOUD: return r.ld.mode != Q3_LOUD_OFF;
+    case ST_LEVEL: return r.lv.on;
+    default: return true;
+    }
+}
+static const Totals& step_totals(const PsRow& r, int s) {
+    switch (s) {
+    case ST_SIL: return r.sil;
+    case ST_TEMPO: return r.tp;
+    case ST_PITCH: return r.pt;
+    case ST_LOUD: return r.ld;
+    case ST_LEVEL: return r.lv;
+    default: return r.rs;
+    }
+}
+// The count rule of a step behind the silence step: the total that has left it once `in` samples have entered (with `last`: and the
+// input has ended). The stretcher also says which frame it reaches. (What leaves the silence step depends on the data: its pre-pass
+// says.)
+static long long step_emitted(const PsRow& r, int s, long long in, bool last, long long* frames) {
+    switch (s) {
+    case ST_TEMPO: {
+        long long f = 0, y = 0;
+        tempo_frames(r.tp.te, in, last, &f, &y);
+        *frames = std::max(f, r.tp.frames);
+        return y;
+    }
+    case ST_PITCH: return pitch_emitted(r.pt.t, r.pt.te, in, last);
+    case ST_LEVEL: return level_emitted(in, last);
+    case ST_RES: return emitted(r.rs.sr, r.rs.r, in, last);
+    default: return in;
+    }
+}
+// The cap rule of a step in front of the resampler (whose own is q3_pcm_stage_bound): the most one push can hand on for n that enter
+static size_t step_cap(const PsRow& r, int s, size_t n) {
+    switch (s) {
+    case ST_SIL: return n + tr_hold(r.sil.set);                    // its own samples and what the row had retained
+    case ST_TEMPO: return tempo_y_bound(r.tp.te, n);
+    case ST_PITCH: return pitch_v_bound(r.pt.t, r.pt.te, n);
+    case ST_LEVEL: return n + LV_D;                                // with `last`, the 127 held back
+    default: return n;
+    }
+}
+static size_t chain_cap(const PsRow& r, size_t n) {
+    for (int s = ST_SIL; s < ST_RES; ++s) if (step_on(r, s)) n = step_cap(r, s, n);
+    return n;
+}
+// One segment's way through the chain in a push: per step that is on, the new samples that enter and leave it (zero where it is
+// off); the frame its stretcher reaches; where its slice of each step's push buffer starts; and what stands at the front of the
+// steps behind the silence step — the segment's own samples, or what the pre-pass kept.
+struct SegWalk {
+    long long n_in[ST_N], n_out[ST_N], frames;
+    size_t off[ST_N];
+    const float* front; long long n_front;
+    bool sil, runs;                           // the pre-pass ran for it; it passes the steps behind
+};
+// new in = what the step in front hands on, new out = rule - step.out, from step `first` on, into which n new samples go
+static void chain_walk(const PsRow& r, int first, long long n, bool last, SegWalk& w) {
+    for (int s = first; s < ST_N; ++s) {
+        if (!step_on(r, s)) continue;
+        const Totals& t = step_totals(r, s);
+        w.n_in[s] = n;
+        n = w.n_out[s] = std::max<long long>(0, step_emitted(r, s, t.in + n, last, &w.frames) - t.out);
+    }
+}
+
+// what the chain needs for the push in progress beside PsPlan: per segment its walk, per step the descriptors and the tiles of a row
+struct StepPlan {
+    std::vector<SegWalk> seg;
+    std::vector<TrDesc> sdesc; std::vector<int> sseg; std::vector<long long> sres;      // the pre-pass: descriptors, their segments, the counters that came back
+    std::vector<TpDesc> tdesc; std::vector<PtDesc> pdesc; std::vector<LoDesc> odesc; std::vector<LvDesc> ldesc;
+    int tiles[ST_N];
+};
 struct q3_pcm_stage {
     int device = 0, R = 0; size_t max_push = 0;
     hipStream_t st = nullptr;
     std::vector<PsRow> rows;
-    std::unordered_map<uint32_t, float*> taps;                 // per rate, on the device
-    float* tails = nullptr;                                    // [R][2][128]
-    char *out_dev = nullptr, *out_host = nullptr; size_t out_cap = 0;      // converted samples of a push: device, pinned host
-    char *in_dev = nullptr, *in_host = nullptr; size_t in_cap = 0;         // q3_pcm_stage_push: descriptors | the rows' new samples
-    // the time stretcher (all of it allocated by the first row at a tempo other than 1000, or the first push of one)
-    float* t_win = nullptr;                                                // the Hann window, 720 floats
-    float* y_dev = nullptr; size_t y_cap = 0;                              // the stretched samples of a push, row after row: the resampler's input
-    char *td_dev = nullptr, *td_host = nullptr; size_t td_cap = 0;         // k_tempo's descriptors
-    // the level step (all of it allocated by the first row with a level, or the first push of one)
-    float* z_dev = nullptr; size_t z_cap = 0;                              // the levelled samples of a push, row after row
-    char *ld_dev = nullptr, *ld_host = nullptr; size_t ld_cap = 0;         // k_level's descriptors
-    // the loudness step (all of it allocated by the first row that meters or normalises, or the first push of one)
-    float o_coef[10] = {0}; bool o_coef_set = false;                       // the K-weighting at 24 kHz, f32
-    float* w_dev = nullptr; size_t w_cap = 0;                              // the normalised samples of a push, row after row
-    char *od_dev = nullptr, *od_host = nullptr; size_t od_cap = 0;         // k_loud's descriptors
-    // the pitch step (all of it allocated by the first row whose pitch moves its tempo, or the first push of one)
-    float* p_tab = nullptr;                                                // the sinc table, PT_SC_N floats, then the window's, PT_W2_N
-    float* v_dev = nullptr; size_t v_cap = 0;                              // the repitched samples of a push, row after row
-    char *pd_dev = nullptr, *pd_host = nullptr; size_t pd_cap = 0;         // k_pitch's descriptors
-    // the silence step (all of it allocated by the first row with a setting other than off, or the first push of one)
-    float* s_win = nullptr;                                                // the seam's weights: w0, then w1, 240 floats each
-    char* s_dev = nullptr; size_t s_cap = 0;                               // of a push, row after row: kept samples | kept hops | flags
-    char *sd_dev = nullptr, *sd_host = nullptr; size_t sd_cap = 0;         // k_trim's descriptors, then the rows' counters coming back
+    std::unordered_map<uint32_t, float*> taps;                 // the resampler's, per rate, on the device
+    float* tails = nullptr;                                    // the resampler's, [R][2][128]
+    // the steps' tables, each built by the first row that turns the step on
+    float* s_win = nullptr;                                    // the seam's weights: w0, then w1, 240 floats each
+    float* t_win = nullptr;                                    // the Hann window, 720 floats
+    float* p_tab = nullptr;                                    // the sinc table, PT_SC_N floats, then the window's, PT_W2_N
+    float o_coef[10] = {0}; bool o_coef_set = false;           // the K-weighting at 24 kHz, f32
+    // per step, allocated by the first push of a row that has it: what it writes in a push, row after row (s: kept samples | kept
+    // hops | flags; y, v, w, z: samples; the resampler's is `out`), and its descriptors (the silence step's: then the rows' counters
+    // coming back; the resampler's: then the rows' new samples of q3_pcm_stage_push)
+    DevBuf buf[ST_N]; PairBuf desc[ST_N];
+    PairBuf out;                                               // the converted samples of a push
+    StepPlan plan;
 };
+template <class B>
+static q3_status buf_reserve(q3_pcm_stage* ps, B& b, size_t bytes) {
+    if (bytes <= b.cap) return Q3_OK;
+    HIPC(hipSetDevice(ps->device));
+    HIPC(b.reserve(bytes));
+    return Q3_OK;
+}
+// a small table built on the host -> the device (undone on error)
+static q3_status table_upload(q3_pcm_stage* ps, float** dst, const float* host, size_t n, const char* who, const char* what, const char* up) {
+    HIPC(hipSetDevice(ps->device));
+    float* d = nullptr;
+    if (dev_malloc((void**)&d, n * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "%s: %s", who, what); }
+    const hipError_t e = q3_hipMemcpy(d, host, n * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "%s: %s upload: %s", who, up, hipGetErrorString(e)); }
+    *dst = d;
+    return Q3_OK;
+}
+// a row's state of a step, if it has none
+template <class T>
+static q3_status row_state(q3_pcm_stage* ps, T** p, size_t bytes, const char* who, const char* what, int row) {
+    if (*p) return Q3_OK;
+    HIPC(hipSetDevice(ps->device));
+    if (dev_malloc((void**)p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return set_err(Q3_OOM, "%s: %s of row %d", who, what, row); }
+    return Q3_OK;
+}
 
 extern "C" q3_status q3_pcm_stage_taps(uint32_t sample_rate, float* taps_host, size_t cap_floats, int* L, int* M) {
     Rate r;
@@ -876,6 +1068,14 @@ extern "C" q3_status q3_pcm_stage_bound(uint32_t sample_rate, size_t n_in, size_
     return Q3_OK;
 }
 
+// The _bound family: the caps of the steps a row with these settings has, in chain order (chain_cap), then the resampler's. hold: what
+// the row's silence step can retain (0: none). Each caller checks its own ranges first; tempo and cents are in range.
+static q3_status bound_through(uint32_t sample_rate, int tempo, int cents, int with_level, size_t hold, size_t n_in, size_t* n_out_max) {
+    PsRow r;                                                       // (the settings alone; its silence step's cap is n_in + hold)
+    r.pt.t = tempo; r.pt.te = r.tp.te = pitch_te(tempo, cents); r.lv.on = with_level != 0;
+    return q3_pcm_stage_bound(sample_rate, chain_cap(r, n_in + hold), n_out_max);
+}
+
 static q3_status tempo_checked(const char* who, int tempo) {
     if (tempo >= TP_MIN && tempo <= TP_MAX) return Q3_OK;
     return set_err(Q3_INVALID_ARG, "%s: tempo %d permille out of range (%d..%d; %d = off)", who, tempo, TP_MIN, TP_MAX, TP_OFF);
@@ -894,8 +1094,7 @@ extern "C" q3_status q3_pcm_stage_tempo_count(int tempo_permille, size_t n_in_to
 extern "C" q3_status q3_pcm_stage_bound_tempo(uint32_t sample_rate, int tempo_permille, size_t n_in, size_t* n_out_max) {
     Q3C(tempo_checked("q3_pcm_stage_bound_tempo", tempo_permille));
     if (n_in > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_tempo: n_in above 2^48");
-    // the resampler's cap for the most y samples the push can add (tempo_y_bound): its rule holds with N_out in the place of n_in
-    return q3_pcm_stage_bound(sample_rate, tempo_permille == TP_OFF ? n_in : tempo_y_bound(tempo_permille, n_in), n_out_max);
+    return bound_through(sample_rate, tempo_permille, 0, 0, 0, n_in, n_out_max);
 }
 
 static q3_status level_checked(const char* who, int gain_mB, int ceiling_mB) {
@@ -924,8 +1123,7 @@ extern "C" q3_status q3_pcm_stage_level_count(size_t n_in_total, int ended, size
 extern "C" q3_status q3_pcm_stage_bound_level(uint32_t sample_rate, int tempo_permille, size_t n_in, size_t* n_out_max) {
     Q3C(tempo_checked("q3_pcm_stage_bound_level", tempo_permille));
     if (n_in > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_level: n_in above 2^48");
-    // the most the step can hand on in one push: what entered it and, with `last`, the 127 held back
-    return q3_pcm_stage_bound(sample_rate, (tempo_permille == TP_OFF ? n_in : tempo_y_bound(tempo_permille, n_in)) + LV_D, n_out_max);
+    return bound_through(sample_rate, tempo_permille, 0, 1, 0, n_in, n_out_max);
 }
 
 extern "C" q3_status q3_loudness_kweight(uint32_t sample_rate, double* shelf_ba, double* highpass_ba) {
@@ -988,36 +1186,20 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
     (void)hipSetDevice(ps->device);
     if (ps->st) (void)hipStreamSynchronize(ps->st);
     for (auto& kv : ps->taps) dev_free(kv.second);
-    dev_free(ps->tails); dev_free(ps->out_dev); dev_free(ps->in_dev);
-    for (PsRow& r : ps->rows) { dev_free(r.t_state); dev_free(r.t_lags[0]); dev_free(r.t_lags[1]); dev_free(r.l_tail); dev_free(r.o_state); dev_free(r.p_tail); }
-    dev_free(ps->t_win); dev_free(ps->y_dev); dev_free(ps->td_dev); dev_free(ps->z_dev); dev_free(ps->ld_dev);
-    dev_free(ps->w_dev); dev_free(ps->od_dev);
-    dev_free(ps->p_tab); dev_free(ps->v_dev); dev_free(ps->pd_dev);
-    for (PsRow& r : ps->rows) dev_free(r.s_state);
-    dev_free(ps->s_win); dev_free(ps->s_dev); dev_free(ps->sd_dev);
-    if (ps->sd_host) (void)hipHostFree(ps->sd_host);
-    if (ps->pd_host) (void)hipHostFree(ps->pd_host);
-    if (ps->od_host) (void)hipHostFree(ps->od_host);
-    if (ps->td_host) (void)hipHostFree(ps->td_host);
-    if (ps->ld_host) (void)hipHostFree(ps->ld_host);
-    if (ps->out_host) (void)hipHostFree(ps->out_host);
-    if (ps->in_host) (void)hipHostFree(ps->in_host);
+    dev_free(ps->tails); dev_free(ps->s_win); dev_free(ps->t_win); dev_free(ps->p_tab);
+    for (PsRow& r : ps->rows) {
+        dev_free(r.sil.state); dev_free(r.tp.state); dev_free(r.pt.tail); dev_free(r.ld.state); dev_free(r.lv.tail);
+        r.tp.lags[0].release(); r.tp.lags[1].release();
+    }
+    for (int s = 0; s < ST_N; ++s) { ps->buf[s].release(); ps->desc[s].release(); }
+    ps->out.release();
     if (ps->st) (void)hipStreamDestroy(ps->st);
     delete ps;
 }
 
 int pcm_stage_rows(const q3_pcm_stage* ps) { return ps->R; }
-size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row) { return fmt_bytes(ps->rows[(size_t)row].fmt); }
-void pcm_stage_reset(q3_pcm_stage* ps, int row) {
-    PsRow& r = ps->rows[(size_t)row];
-    r.n_in = r.n_out = 0; r.cur = 0; r.fresh = true; r.ended = false;
-    r.t_in = r.t_frames = 0; r.t_lag_k0 = r.t_lag_n = 0;
-    r.l_in = 0;
-    r.o_in = 0;
-    r.p_in = r.p_out = 0;
-    r.s_in = 0;
-    for (int i = 0; i < TR_ST; ++i) r.s_read[i] = i == TR_S_RUN ? -1 : 0;
-}
+size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row) { return fmt_bytes(ps->rows[(size_t)row].rs.fmt); }
+void pcm_stage_reset(q3_pcm_stage* ps, int row) { ps->rows[(size_t)row].reset(); }
 
 extern "C" q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_reset: bad row");
@@ -1034,19 +1216,18 @@ extern "C" q3_status q3_pcm_stage_set(q3_pcm_stage* ps, int row, uint32_t sample
     if (sample_rate != PS_RATE_IN) {
         auto it = ps->taps.find(sample_rate);
         if (it == ps->taps.end()) {
-            HIPC(hipSetDevice(ps->device));
             std::vector<float> t;
             taps_of(r, t);
+            char what[48];
+            snprintf(what, sizeof(what), "tap table of %u Hz", sample_rate);
             float* d = nullptr;
-            if (dev_malloc((void**)&d, t.size() * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "q3_pcm_stage_set: tap table of %u Hz", sample_rate); }
-            const hipError_t e = q3_hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "q3_pcm_stage_set: tap upload: %s", hipGetErrorString(e)); }
+            Q3C(table_upload(ps, &d, t.data(), t.size(), "q3_pcm_stage_set", what, "tap"));
             it = ps->taps.emplace(sample_rate, d).first;
         }
         taps = it->second;
     }
-    PsRow& pr = ps->rows[(size_t)row];
-    pr.sr = sample_rate; pr.fmt = format; pr.r = r; pr.taps = taps;
+    ResStep& rs = ps->rows[(size_t)row].rs;
+    rs.sr = sample_rate; rs.fmt = format; rs.r = r; rs.taps = taps;
     pcm_stage_reset(ps, row);
     return Q3_OK;
 }
@@ -1068,54 +1249,38 @@ static q3_status tempo_pitch_set(q3_pcm_stage* ps, int row, const char* who, int
     PsRow& r = ps->rows[(size_t)row];
     const int te = pitch_te(tempo, cents);
     if (te != TP_OFF) {
-        HIPC(hipSetDevice(ps->device));
         if (!ps->t_win) {
             // periodic Hann, built in f64
             std::vector<float> w((size_t)TP_W);
             for (int j = 0; j < TP_W; ++j) w[(size_t)j] = (float)(0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * (double)j / (double)TP_W));
-            float* d = nullptr;
-            if (dev_malloc((void**)&d, w.size() * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "%s: window", who); }
-            const hipError_t e = q3_hipMemcpy(d, w.data(), w.size() * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "%s: window upload: %s", who, hipGetErrorString(e)); }
-            ps->t_win = d;
+            Q3C(table_upload(ps, &ps->t_win, w.data(), w.size(), who, "window", "window"));
         }
-        if (!r.t_state && dev_malloc((void**)&r.t_state, 2 * TP_STATE_BYTES) != hipSuccess) {
-            (void)hipGetLastError(); r.t_state = nullptr;
-            return set_err(Q3_OOM, "%s: state of row %d", who, row);
-        }
+        Q3C(row_state(ps, &r.tp.state, 2 * TP_STATE_BYTES, who, "state", row));
     }
     if (te != tempo) {
-        HIPC(hipSetDevice(ps->device));
         if (!ps->p_tab) {
             std::vector<float> sc, w2;
             pitch_tables(sc, w2);
             sc.insert(sc.end(), w2.begin(), w2.end());
-            float* d = nullptr;
-            if (dev_malloc((void**)&d, sc.size() * 4) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "%s: tables", who); }
-            const hipError_t e = q3_hipMemcpy(d, sc.data(), sc.size() * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "%s: table upload: %s", who, hipGetErrorString(e)); }
-            ps->p_tab = d;
+            Q3C(table_upload(ps, &ps->p_tab, sc.data(), sc.size(), who, "tables", "table"));
         }
-        if (!r.p_tail && dev_malloc((void**)&r.p_tail, 2 * (size_t)PS_TAPS * 4) != hipSuccess) {
-            (void)hipGetLastError(); r.p_tail = nullptr;
-            return set_err(Q3_OOM, "%s: tail of row %d", who, row);
-        }
+        Q3C(row_state(ps, &r.pt.tail, 2 * (size_t)PS_TAPS * 4, who, "tail", row));
     }
-    r.tempo = tempo; r.pitch = cents; r.te = te;
+    r.pt.t = tempo; r.pt.cents = cents; r.pt.te = r.tp.te = te;
     pcm_stage_reset(ps, row);
     return Q3_OK;
 }
 
 extern "C" q3_status q3_pcm_stage_set_tempo(q3_pcm_stage* ps, int row, int tempo_permille) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_tempo: bad row");
-    Q3C(pitch_checked("q3_pcm_stage_set_tempo", tempo_permille, ps->rows[(size_t)row].pitch));      // (before the device is touched)
-    return tempo_pitch_set(ps, row, "q3_pcm_stage_set_tempo", tempo_permille, ps->rows[(size_t)row].pitch);
+    Q3C(pitch_checked("q3_pcm_stage_set_tempo", tempo_permille, ps->rows[(size_t)row].pt.cents));      // (before the device is touched)
+    return tempo_pitch_set(ps, row, "q3_pcm_stage_set_tempo", tempo_permille, ps->rows[(size_t)row].pt.cents);
 }
 
 extern "C" q3_status q3_pcm_stage_set_pitch(q3_pcm_stage* ps, int row, int cents) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_pitch: bad row");
-    Q3C(pitch_checked("q3_pcm_stage_set_pitch", ps->rows[(size_t)row].tempo, cents));      // (before the device is touched)
-    return tempo_pitch_set(ps, row, "q3_pcm_stage_set_pitch", ps->rows[(size_t)row].tempo, cents);
+    Q3C(pitch_checked("q3_pcm_stage_set_pitch", ps->rows[(size_t)row].pt.t, cents));      // (before the device is touched)
+    return tempo_pitch_set(ps, row, "q3_pcm_stage_set_pitch", ps->rows[(size_t)row].pt.t, cents);
 }
 
 extern "C" q3_status q3_pcm_stage_pitch_plan(int tempo_permille, int cents, int* tempo_eff, double* cents_realized) {
@@ -1153,27 +1318,17 @@ extern "C" q3_status q3_pcm_stage_pitch_count(int tempo_permille, int cents, siz
 extern "C" q3_status q3_pcm_stage_bound_pitch(uint32_t sample_rate, int tempo_permille, int cents, int with_level, size_t n_in, size_t* n_out_max) {
     Q3C(pitch_checked("q3_pcm_stage_bound_pitch", tempo_permille, cents));
     if (n_in > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_pitch: n_in above 2^48");
-    // the caps of the steps in a row: the most y samples the push can add, the most the pitch step then hands on, the level's 127
-    const int te = pitch_te(tempo_permille, cents);
-    size_t n = te == TP_OFF ? n_in : tempo_y_bound(te, n_in);
-    if (te != tempo_permille) n = pitch_v_bound(tempo_permille, te, n);
-    return q3_pcm_stage_bound(sample_rate, n + (with_level ? LV_D : 0), n_out_max);
+    return bound_through(sample_rate, tempo_permille, cents, with_level, 0, n_in, n_out_max);
 }
 
 extern "C" q3_status q3_pcm_stage_set_level(q3_pcm_stage* ps, int row, int gain_mB, int ceiling_mB) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_level: bad row");
     Q3C(level_checked("q3_pcm_stage_set_level", gain_mB, ceiling_mB));      // (before the device is touched)
-    PsRow& r = ps->rows[(size_t)row];
+    LevelStep& lv = ps->rows[(size_t)row].lv;
     const bool on = gain_mB != 0 || ceiling_mB != 0;
-    if (on && !r.l_tail) {
-        HIPC(hipSetDevice(ps->device));
-        if (dev_malloc((void**)&r.l_tail, 2 * (size_t)LV_TAIL_PITCH * 4) != hipSuccess) {
-            (void)hipGetLastError(); r.l_tail = nullptr;
-            return set_err(Q3_OOM, "q3_pcm_stage_set_level: state of row %d", row);
-        }
-    }
-    r.level = on; r.gain_mB = gain_mB; r.ceil_mB = ceiling_mB;
-    (void)q3_pcm_stage_level_coeffs(gain_mB, ceiling_mB, &r.l_g, &r.l_c);
+    if (on) Q3C(row_state(ps, &lv.tail, 2 * (size_t)LV_TAIL_PITCH * 4, "q3_pcm_stage_set_level", "state", row));
+    lv.on = on; lv.gain_mB = gain_mB; lv.ceil_mB = ceiling_mB;
+    (void)q3_pcm_stage_level_coeffs(gain_mB, ceiling_mB, &lv.g, &lv.c);
     pcm_stage_reset(ps, row);
     return Q3_OK;
 }
@@ -1181,7 +1336,7 @@ extern "C" q3_status q3_pcm_stage_set_level(q3_pcm_stage* ps, int row, int gain_
 extern "C" q3_status q3_pcm_stage_set_loudness(q3_pcm_stage* ps, int row, int mode, int target_mB, int prior_mB) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_loudness: bad row");
     Q3C(loud_checked("q3_pcm_stage_set_loudness", mode, target_mB, prior_mB));      // (before the device is touched)
-    PsRow& r = ps->rows[(size_t)row];
+    LoudStep& ld = ps->rows[(size_t)row].ld;
     if (mode != Q3_LOUD_OFF) {
         if (!ps->o_coef_set) {
             // the K-weighting at 24 kHz: in f64, rounded once
@@ -1191,16 +1346,10 @@ extern "C" q3_status q3_pcm_stage_set_loudness(q3_pcm_stage* ps, int row, int mo
             for (int i = 0; i < 10; ++i) ps->o_coef[i] = (float)c[i];
             ps->o_coef_set = true;
         }
-        if (!r.o_state) {
-            HIPC(hipSetDevice(ps->device));
-            if (dev_malloc((void**)&r.o_state, (2 * (size_t)LD_STATE + LD_HIST) * 4) != hipSuccess) {
-                (void)hipGetLastError(); r.o_state = nullptr;
-                return set_err(Q3_OOM, "q3_pcm_stage_set_loudness: state of row %d", row);
-            }
-        }
+        Q3C(row_state(ps, &ld.state, (2 * (size_t)LD_STATE + LD_HIST) * 4, "q3_pcm_stage_set_loudness", "state", row));
     }
-    r.loud = mode; r.o_target = target_mB; r.o_prior = prior_mB;
-    (void)q3_pcm_stage_loudness_consts(target_mB, prior_mB, &r.o_T, &r.o_P, &r.o_gate, &r.o_lo, &r.o_hi);
+    ld.mode = mode; ld.target = target_mB; ld.prior = prior_mB;
+    (void)q3_pcm_stage_loudness_consts(target_mB, prior_mB, &ld.T, &ld.P, &ld.gate, &ld.lo, &ld.hi);
     pcm_stage_reset(ps, row);
     return Q3_OK;
 }
@@ -1210,17 +1359,17 @@ static long long loud_blocks(long long n) { return std::min<long long>(LD_HIST, 
 
 extern "C" q3_status q3_pcm_stage_loudness(q3_pcm_stage* ps, int row, float* mean_square, float* gain, int* blocks, int* gated) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness: bad row");
-    const PsRow& r = ps->rows[(size_t)row];
-    if (r.loud == Q3_LOUD_OFF) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness: row %d has no loudness step (q3_pcm_stage_set_loudness)", row);
-    float v[4] = {r.o_P, r.o_P, 0.0f, 0.0f};                      // A1 A2 M cg: a row that has taken no sample stands at its prior
-    if (r.o_in > 0) {
+    const LoudStep& ld = ps->rows[(size_t)row].ld;
+    if (ld.mode == Q3_LOUD_OFF) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness: row %d has no loudness step (q3_pcm_stage_set_loudness)", row);
+    float v[4] = {ld.P, ld.P, 0.0f, 0.0f};                        // A1 A2 M cg: a row that has taken no sample stands at its prior
+    if (ld.in > 0) {
         HIPC(hipSetDevice(ps->device));
-        HIPC(q3_hipMemcpy(v, r.o_state + (size_t)r.o_cur * LD_STATE + LD_S_A1, sizeof(v), hipMemcpyDeviceToHost));
+        HIPC(q3_hipMemcpy(v, ld.state + (size_t)ld.cur * LD_STATE + LD_S_A1, sizeof(v), hipMemcpyDeviceToHost));
     }
     int cg = 0; memcpy(&cg, &v[3], 4);
     if (mean_square) *mean_square = v[2];
     if (gain) *gain = v[0];
-    if (blocks) *blocks = (int)loud_blocks(r.o_in);
+    if (blocks) *blocks = (int)loud_blocks(ld.in);
     if (gated) *gated = cg;
     return Q3_OK;
 }
@@ -1228,26 +1377,26 @@ extern "C" q3_status q3_pcm_stage_loudness(q3_pcm_stage* ps, int row, float* mea
 extern "C" q3_status q3_pcm_stage_loudness_blocks(q3_pcm_stage* ps, int row, float* z, size_t cap, size_t* n) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness_blocks: bad row");
     if (!n) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness_blocks: null argument");
-    const PsRow& r = ps->rows[(size_t)row];
-    const long long nb = r.loud == Q3_LOUD_OFF ? 0 : loud_blocks(r.o_in);
+    const LoudStep& ld = ps->rows[(size_t)row].ld;
+    const long long nb = ld.mode == Q3_LOUD_OFF ? 0 : loud_blocks(ld.in);
     *n = (size_t)nb;
     if (nb == 0 || (!z && cap == 0)) return Q3_OK;                 // (no buffer: the count alone)
     if (!z || cap < (size_t)nb) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness_blocks: %lld blocks, the buffer takes %zu", nb, cap);
     HIPC(hipSetDevice(ps->device));
-    HIPC(q3_hipMemcpy(z, r.o_state + 2 * (size_t)LD_STATE, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    HIPC(q3_hipMemcpy(z, ld.state + 2 * (size_t)LD_STATE, (size_t)nb * 4, hipMemcpyDeviceToHost));
     return Q3_OK;
 }
 
 extern "C" q3_status q3_pcm_stage_tempo_lags(q3_pcm_stage* ps, int row, int64_t* k0, int* lags, size_t cap, size_t* n) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: bad row");
     if (!n) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: null argument");
-    const PsRow& r = ps->rows[(size_t)row];
-    *n = (size_t)r.t_lag_n;
-    if (k0) *k0 = (int64_t)r.t_lag_k0;
-    if (r.t_lag_n == 0 || (!lags && cap == 0)) return Q3_OK;      // (no buffer: the count alone)
-    if (!lags || cap < (size_t)r.t_lag_n) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: %lld lags, the buffer takes %zu", r.t_lag_n, cap);
+    const TempoStep& tp = ps->rows[(size_t)row].tp;
+    *n = (size_t)tp.lag_n;
+    if (k0) *k0 = (int64_t)tp.lag_k0;
+    if (tp.lag_n == 0 || (!lags && cap == 0)) return Q3_OK;       // (no buffer: the count alone)
+    if (!lags || cap < (size_t)tp.lag_n) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_tempo_lags: %lld lags, the buffer takes %zu", tp.lag_n, cap);
     HIPC(hipSetDevice(ps->device));
-    HIPC(q3_hipMemcpy(lags, r.t_lags[r.t_lag_cur], (size_t)r.t_lag_n * sizeof(int), hipMemcpyDeviceToHost));
+    HIPC(q3_hipMemcpy(lags, tp.lags[tp.lag_cur].dev, (size_t)tp.lag_n * sizeof(int), hipMemcpyDeviceToHost));
     return Q3_OK;
 }
 
@@ -1273,8 +1422,11 @@ extern "C" q3_status q3_pcm_stage_bound_silence(uint32_t sample_rate, int tempo_
                                                 size_t* n_out_max) {
     Q3C(silence_checked("q3_pcm_stage_bound_silence", 0, edge_ms, pause_ms));
     if (n_in > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_silence: n_in above 2^48");
-    // a push hands on at most its own samples and what the row had retained
-    return q3_pcm_stage_bound_pitch(sample_rate, tempo_permille, cents, with_level, n_in + tr_hold(tr_set(edge_ms, pause_ms)), n_out_max);
+    // a push hands on at most its own samples and what the row had retained: q3_pcm_stage_bound_pitch's refusals, for n_in + hold
+    const size_t hold = tr_hold(tr_set(edge_ms, pause_ms));
+    Q3C(pitch_checked("q3_pcm_stage_bound_pitch", tempo_permille, cents));
+    if (n_in + hold > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_pitch: n_in above 2^48");
+    return bound_through(sample_rate, tempo_permille, cents, with_level, hold, n_in, n_out_max);
 }
 
 // the whole definition for one clip on the CPU: the same f32 operations in the same order as k_trim
@@ -1323,398 +1475,276 @@ extern "C" q3_status q3_silence_trim(const float* x, size_t n, int threshold_mB,
 extern "C" q3_status q3_pcm_stage_set_silence(q3_pcm_stage* ps, int row, int threshold_mB, int edge_ms, int pause_ms) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_silence: bad row");
     Q3C(silence_checked("q3_pcm_stage_set_silence", threshold_mB, edge_ms, pause_ms));      // (before the device is touched)
-    PsRow& r = ps->rows[(size_t)row];
+    SilStep& sil = ps->rows[(size_t)row].sil;
     const TrSet t = tr_set(edge_ms, pause_ms);
     if (threshold_mB != 0) {
-        HIPC(hipSetDevice(ps->device));
         if (!ps->s_win) {
             float w[2 * TR_H];
             tr_window(w);
-            float* d = nullptr;
-            if (dev_malloc((void**)&d, sizeof(w)) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "q3_pcm_stage_set_silence: seam weights"); }
-            const hipError_t e = q3_hipMemcpy(d, w, sizeof(w), hipMemcpyHostToDevice);
-            if (e != hipSuccess) { dev_free(d); return set_err(Q3_HIP_ERROR, "q3_pcm_stage_set_silence: weight upload: %s", hipGetErrorString(e)); }
-            ps->s_win = d;
+            Q3C(table_upload(ps, &ps->s_win, w, 2 * TR_H, "q3_pcm_stage_set_silence", "seam weights", "weight"));
         }
         const size_t copy = ((size_t)TR_ST * 8 + tr_state_floats(t) * 4 + 15) & ~(size_t)15;
-        if (2 * copy > r.s_cap) {                                  // (the row restarts below: what the old state held is not needed)
-            dev_free(r.s_state); r.s_state = nullptr; r.s_cap = 0;
-            if (dev_malloc((void**)&r.s_state, 2 * copy) != hipSuccess) {
-                (void)hipGetLastError(); r.s_state = nullptr; r.s_thr = 0;
-                return set_err(Q3_OOM, "q3_pcm_stage_set_silence: state of row %d", row);
-            }
-            r.s_cap = 2 * copy;
+        if (2 * copy > sil.cap) {                                  // (the row restarts below: what the old state held is not needed)
+            dev_free(sil.state); sil.state = nullptr; sil.cap = 0;
+            const q3_status st = row_state(ps, &sil.state, 2 * copy, "q3_pcm_stage_set_silence", "state", row);
+            if (st != Q3_OK) { sil.thr = 0; return st; }
+            sil.cap = 2 * copy;
         }
-        r.s_copy = copy;
+        sil.copy = copy;
     }
-    r.s_thr = threshold_mB; r.s_edge = edge_ms; r.s_pause = pause_ms; r.s_set = t; r.s_theta = tr_theta(threshold_mB);
+    sil.thr = threshold_mB; sil.edge = edge_ms; sil.pause = pause_ms; sil.set = t; sil.theta = tr_theta(threshold_mB);
     pcm_stage_reset(ps, row);
     return Q3_OK;
 }
 
 extern "C" q3_status q3_pcm_stage_silence(q3_pcm_stage* ps, int row, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_silence: bad row");
-    const PsRow& r = ps->rows[(size_t)row];
-    if (r.s_thr == 0) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_silence: row %d has no silence step (q3_pcm_stage_set_silence)", row);
-    if (n_in) *n_in = r.s_in;
-    if (n_out) *n_out = r.s_read[TR_S_OUT];
-    if (lead_cut) *lead_cut = r.s_read[TR_S_LEAD];
-    if (pause_cut) *pause_cut = r.s_read[TR_S_PAUSE];
-    if (trail_cut) *trail_cut = r.s_read[TR_S_TRAIL];
+    const SilStep& sil = ps->rows[(size_t)row].sil;
+    if (sil.thr == 0) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_silence: row %d has no silence step (q3_pcm_stage_set_silence)", row);
+    if (n_in) *n_in = sil.in;
+    if (n_out) *n_out = sil.out;
+    if (lead_cut) *lead_cut = sil.read[TR_S_LEAD];
+    if (pause_cut) *pause_cut = sil.read[TR_S_PAUSE];
+    if (trail_cut) *trail_cut = sil.read[TR_S_TRAIL];
     return Q3_OK;
 }
 
-// what a row has emitted once n more 24 kHz samples have arrived: through the stretcher first, where the row has one
-// (y: the stretched samples by then, k1: the frames)
-// (y: the stretched samples by then, k1: the frames; lv: the samples that have entered the level step by then)
-// (pv: the samples that have left the pitch step by then, where the row has one: the stream the steps behind it take)
-static long long row_emitted(const PsRow& r, size_t n, bool last, long long* y = nullptr, long long* k1 = nullptr, long long* lv = nullptr,
-                             long long* pv = nullptr) {
-    const bool pitch = r.te != r.tempo;
-    long long in_total = (pitch ? r.p_in : r.level ? r.l_in : r.n_in) + (long long)n;
-    if (r.te != TP_OFF) {
-        long long f = 0;
-        tempo_frames(r.te, r.t_in + (long long)n, last, &f, &in_total);
-        if (f < r.t_frames) f = r.t_frames;
-        if (k1) *k1 = f;
-    }
-    if (y) *y = in_total;
-    if (pitch) in_total = pitch_emitted(r.tempo, r.te, in_total, last);
-    if (pv) *pv = in_total;
-    if (r.level) {
-        if (lv) *lv = in_total;
-        in_total = level_emitted(in_total, last);
-    }
-    return emitted(r.sr, r.r, in_total, last);
-}
-static q3_status dev_grow(q3_pcm_stage* ps, void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return Q3_OK;
-    HIPC(hipSetDevice(ps->device));
-    dev_free(*p); *p = nullptr; *cap = 0;
-    HIPC(dev_malloc(p, bytes * 2));
-    *cap = bytes * 2;
-    return Q3_OK;
+// one step's descriptors of a push up from its pinned buffer, and its launch
+template <class D, void (*K)(const D*)>
+static hipError_t step_launch(PairBuf& b, const std::vector<D>& descs, dim3 grid, dim3 block, hipStream_t st) {
+    if (descs.empty()) return hipSuccess;
+    const hipError_t e = b.upload(descs.data(), descs.size() * sizeof(D), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(K, grid, block, 0, st, (const D*)b.dev);
+    return hipGetLastError();
 }
 
-bool pcm_stage_has_trim(const q3_pcm_stage* ps, const std::vector<PsSeg>& segs) {
-    for (const PsSeg& sg : segs) if (ps->rows[(size_t)sg.row].s_thr != 0) return true;
-    return false;
-}
-// The pre-pass of a push in which some row has a silence step. The samples are on the device, readable by work on
-// `st`. One descriptor upload, one k_trim launch (a workgroup per such row), the rows' counters back in one copy, a wait. Then
-// those segments name what the step kept, in the stage's s buffer, and plan.trim holds what pcm_stage_commit needs. Changes no row:
+// The chain's first step, in a pass of its own: what leaves it depends on the data. The samples are on the device,
+// readable by work on `st`. One descriptor upload, one k_trim launch (a workgroup per such row), the rows' counters back in one
+// copy, a wait. Then those segments' walks say what the step kept and where it stands, in the stage's s buffer. Changes no row:
 // k_trim writes the copy of the row's state that is not the current one.
-q3_status pcm_stage_trim(q3_pcm_stage* ps, std::vector<PsSeg>& segs, hipStream_t st, PsPlan& plan) {
-    PsTrim& tr = plan.trim;
-    tr.seg.clear(); tr.n_new.clear(); tr.res.clear();
-    std::vector<TrDesc> descs;
-    std::vector<size_t> y_off, o_off, f_off;
+static q3_status chain_prepass(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, hipStream_t st) {
+    StepPlan& p = ps->plan;
+    std::vector<TrDesc>& descs = p.sdesc;
+    descs.clear(); p.sseg.clear();
     size_t bytes = 0;
     for (size_t i = 0; i < segs.size(); ++i) {
-        PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
-        if (r.s_thr == 0 || r.ended) continue;
-        if (sg.n > ps->max_push) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, ps->max_push);
-        sg.trimmed = 1;
+        const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row]; const SilStep& sil = r.sil;
+        if (!step_on(r, ST_SIL) || r.ended) continue;
+        p.seg[i].n_front = 0;                                      // (until the step hands something on)
         if (sg.n == 0 && !sg.last) continue;
-        if (!r.s_state || !ps->s_win) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a silence step and no state", sg.row);
+        if (!sil.state || !ps->s_win) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a silence step and no state", sg.row);
         TrDesc d{};
-        const TrSet& t = r.s_set;
-        d.base = r.s_in; d.n_new = (int)sg.n; d.n_total = r.s_in + (long long)sg.n; d.last = sg.last ? 1 : 0;
+        const TrSet& t = sil.set;
+        d.base = sil.in; d.n_new = (int)sg.n; d.n_total = sil.in + (long long)sg.n; d.last = sg.last ? 1 : 0;
         d.c_old = d.base / TR_H; d.c_new = d.n_total / TR_H; d.c_end = sg.last ? (d.n_total + TR_H - 1) / TR_H : d.c_new;
         d.k_old = std::max<long long>(0, d.c_old - TR_G); d.k_new = sg.last ? d.c_end : std::max<long long>(0, d.c_new - TR_G);
-        d.E = t.E; d.P1 = t.P1; d.P2 = t.P2; d.head = tr_head(t); d.theta = r.s_theta;
+        d.E = t.E; d.P1 = t.P1; d.P2 = t.P2; d.head = tr_head(t); d.theta = sil.theta;
         d.tail_lead = tr_tail_lead(t); d.tail_run = tr_tail_run(t);
-        d.tail = r.s_read[TR_S_RUN] == 0 ? d.tail_lead : d.tail_run;      // (what the last successful push left: the host's copy of the counters says which)
+        d.tail = sil.read[TR_S_RUN] == 0 ? d.tail_lead : d.tail_run;      // (what the last successful push left: the host's copy of the counters says which)
         // the hops a push can hand on: the ones it classifies and the ones the row had retained
         d.cap_ops = (int)(d.k_new - d.k_old) + (int)(tr_hold(t) / TR_H) + 2;
         d.fl_n = (int)(d.c_end - d.c_old) + 4;
-        y_off.push_back(bytes); bytes += ((size_t)d.cap_ops * TR_H * 4 + 15) & ~(size_t)15;
-        o_off.push_back(bytes); bytes += ((size_t)d.cap_ops * 2 * sizeof(int) + 15) & ~(size_t)15;
-        f_off.push_back(bytes); bytes += ((size_t)d.fl_n + (size_t)(d.k_new - d.k_old) + 15) & ~(size_t)15;
+        // its slice of s: kept samples | kept hops | flags
+        p.seg[i].off[ST_SIL] = bytes;
+        bytes += (((size_t)d.cap_ops * TR_H * 4 + 15) & ~(size_t)15) + (((size_t)d.cap_ops * 2 * sizeof(int) + 15) & ~(size_t)15) +
+                 (((size_t)d.fl_n + (size_t)(d.k_new - d.k_old) + 15) & ~(size_t)15);
         d.src = sg.dev; d.win = ps->s_win;
-        char* in = r.s_state + (size_t)r.s_cur * r.s_copy; char* out = r.s_state + (size_t)(r.s_cur ^ 1) * r.s_copy;
-        d.st_in = r.s_in > 0 ? (const long long*)in : nullptr; d.st_out = (long long*)out;
-        d.tail_in = r.s_in > 0 ? (const float*)(in + TR_ST * 8) : nullptr; d.tail_out = (float*)(out + TR_ST * 8);
-        d.head_in = r.s_in > 0 ? (const float*)(in + TR_ST * 8) + d.tail_run : nullptr; d.head_out = (float*)(out + TR_ST * 8) + d.tail_run;
-        descs.push_back(d); tr.seg.push_back((int)i); tr.n_new.push_back((long long)sg.n);
+        char* in = sil.state + (size_t)sil.cur * sil.copy; char* out = sil.state + (size_t)(sil.cur ^ 1) * sil.copy;
+        d.st_in = sil.in > 0 ? (const long long*)in : nullptr; d.st_out = (long long*)out;
+        d.tail_in = sil.in > 0 ? (const float*)(in + TR_ST * 8) : nullptr; d.tail_out = (float*)(out + TR_ST * 8);
+        d.head_in = sil.in > 0 ? (const float*)(in + TR_ST * 8) + d.tail_run : nullptr; d.head_out = (float*)(out + TR_ST * 8) + d.tail_run;
+        descs.push_back(d); p.sseg.push_back((int)i);
     }
     if (descs.empty()) return Q3_OK;
     HIPC(hipSetDevice(ps->device));
-    Q3C(dev_grow(ps, (void**)&ps->s_dev, &ps->s_cap, bytes));
+    DevBuf& s = ps->buf[ST_SIL]; PairBuf& sd = ps->desc[ST_SIL];
+    Q3C(buf_reserve(ps, s, bytes));
     const size_t nd = descs.size(), db = (nd * sizeof(TrDesc) + 15) & ~(size_t)15, rb = nd * TR_ST * 8;
-    if (db + rb > ps->sd_cap) {
-        dev_free(ps->sd_dev); ps->sd_dev = nullptr;
-        if (ps->sd_host) { (void)hipHostFree(ps->sd_host); ps->sd_host = nullptr; }
-        ps->sd_cap = 0;
-        HIPC(dev_malloc((void**)&ps->sd_dev, (db + rb) * 2));
-        HIPC(hipHostMalloc((void**)&ps->sd_host, (db + rb) * 2, hipHostMallocDefault));
-        ps->sd_cap = (db + rb) * 2;
-    }
+    Q3C(buf_reserve(ps, sd, db + rb));
     for (size_t k = 0; k < nd; ++k) {
-        descs[k].y = (float*)(ps->s_dev + y_off[k]); descs[k].ops = (int*)(ps->s_dev + o_off[k]); descs[k].fl = (unsigned char*)(ps->s_dev + f_off[k]);
-        descs[k].res = (long long*)(ps->sd_dev + db) + k * TR_ST;
+        TrDesc& d = descs[k];
+        char* at = s.dev + p.seg[(size_t)p.sseg[k]].off[ST_SIL];
+        d.y = (float*)at; at += ((size_t)d.cap_ops * TR_H * 4 + 15) & ~(size_t)15;
+        d.ops = (int*)at; at += ((size_t)d.cap_ops * 2 * sizeof(int) + 15) & ~(size_t)15;
+        d.fl = (unsigned char*)at;
+        d.res = (long long*)(sd.dev + db) + k * TR_ST;
     }
-    memcpy(ps->sd_host, descs.data(), nd * sizeof(TrDesc));
-    HIPC(hipMemcpyAsync(ps->sd_dev, ps->sd_host, nd * sizeof(TrDesc), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_trim, dim3((unsigned)nd), dim3(TR_THREADS), 0, st, (const TrDesc*)ps->sd_dev);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(ps->sd_host + db, ps->sd_dev + db, rb, hipMemcpyDeviceToHost, st));
+    HIPC((step_launch<TrDesc, k_trim>(sd, descs, dim3((unsigned)nd), dim3(TR_THREADS), st)));
+    HIPC(hipMemcpyAsync(sd.host + db, sd.dev + db, rb, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
-    tr.res.assign((const long long*)(ps->sd_host + db), (const long long*)(ps->sd_host + db) + nd * TR_ST);
+    p.sres.assign((const long long*)(sd.host + db), (const long long*)(sd.host + db) + nd * TR_ST);
     for (size_t k = 0; k < nd; ++k) {
-        PsSeg& sg = segs[(size_t)tr.seg[k]]; const PsRow& r = ps->rows[(size_t)sg.row];
-        const long long* res = &tr.res[k * TR_ST];
-        const long long kept = res[TR_S_OUT] - r.s_read[TR_S_OUT];
+        const size_t i = (size_t)p.sseg[k];
+        const PsSeg& sg = segs[i]; const SilStep& sil = ps->rows[(size_t)sg.row].sil; SegWalk& w = p.seg[i];
+        const long long* res = &p.sres[k * TR_ST];
+        const long long kept = res[TR_S_OUT] - sil.out;
         if (res[TR_S_OVER] || kept < 0 || kept > (long long)descs[k].cap_ops * TR_H)
             return set_err(Q3_HIP_ERROR, "pcm stage: the silence step of row %d kept %lld samples, its buffer takes %d hops", sg.row, kept, descs[k].cap_ops);
-        sg.dev = descs[k].y; sg.n = (size_t)kept;
+        w.sil = true; w.n_in[ST_SIL] = (long long)sg.n; w.n_out[ST_SIL] = kept;
+        w.front = descs[k].y; w.n_front = kept;
     }
     return Q3_OK;
 }
 
-// Checks a push (every row at most once and in range — the entry points' business —, n within max_push_samples, or that and the
-// row's hold for a segment that has passed a silence step, no samples for a
-// row that was flushed), lays the rows' outputs out in the staging buffer (16-byte aligned each) and writes the descriptors.
-// Changes no row. The staging buffers (and a row's lag buffer that is not the current one) may be reallocated: no push is in
-// flight (each ends with a wait). Rows with a tempo get their stretcher's descriptor and their part of the y buffer here too.
-q3_status pcm_stage_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan) {
-    plan.desc.clear(); plan.off.assign(segs.size(), 0); plan.count.assign(segs.size(), 0); plan.bytes = 0; plan.max_tiles = 1;
-    plan.ps = ps; plan.tdesc.clear(); plan.t_y.assign(segs.size(), 0); plan.t_k1.assign(segs.size(), 0);
-    plan.ldesc.clear(); plan.l_in.assign(segs.size(), 0); plan.l_z.assign(segs.size(), 0); plan.l_tiles = 1;
-    plan.odesc.clear(); plan.o_n.clear();
-    plan.pdesc.clear(); plan.p_n.clear(); plan.p_v.clear(); plan.p_tiles = 1;
-    std::vector<size_t> y_off(segs.size(), 0), z_off(segs.size(), 0), w_off, v_off; size_t y_floats = 0, z_floats = 0, w_floats = 0, v_floats = 0;
-    for (size_t i = 0; i < segs.size(); ++i) {
-        const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
-        // (behind a silence step a segment carries what the step kept: up to what entered it and what the row had retained)
-        const size_t n_max = ps->max_push + (sg.trimmed ? tr_hold(r.s_set) : 0);
-        if (sg.n > n_max) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, n_max);
-        if (r.ended && sg.n > 0) return set_err(Q3_INVALID_ARG, "pcm stage: row %d was flushed (last): q3_pcm_stage_reset or _set restarts it", sg.row);
-        if (r.s_thr != 0 && !sg.trimmed && !r.ended)
-            return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a silence step and its segment has not passed it (pcm_stage_trim)", sg.row);
-        if (r.ended || (sg.n == 0 && !sg.last)) continue;
-        long long y_total = 0, k1 = 0, lv_total = 0, v_total = 0;
-        const long long total = row_emitted(r, sg.n, sg.last != 0, &y_total, &k1, &lv_total, &v_total);
-        const bool pitch = r.te != r.tempo;
-        plan.count[i] = (size_t)std::max<long long>(0, total - r.n_out);
-        if (r.te != TP_OFF) {
-            if (!r.t_state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tempo and no state", sg.row);
-            plan.t_y[i] = y_total - (pitch ? r.p_in : r.level ? r.l_in : r.n_in); plan.t_k1[i] = k1;
-            y_off[i] = y_floats; y_floats += ((size_t)plan.t_y[i] + 3) & ~(size_t)3;
-        }
-        if (pitch) {
-            if (!r.p_tail || !ps->p_tab) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a pitch and no state", sg.row);
-            if (plan.p_n.empty()) { plan.p_n.assign(segs.size(), 0); plan.p_v.assign(segs.size(), 0); v_off.assign(segs.size(), 0); }
-            plan.p_n[i] = y_total - r.p_in; plan.p_v[i] = v_total - r.p_out;
-            v_off[i] = v_floats; v_floats += ((size_t)plan.p_v[i] + 3) & ~(size_t)3;
-        }
-        if (r.loud != Q3_LOUD_OFF) {
-            // (what passes the step in this push: the stretched samples where the row has a stretcher, else the segment's own)
-            if (!r.o_state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a loudness step and no state", sg.row);
-            if (plan.o_n.empty()) { plan.o_n.assign(segs.size(), 0); w_off.assign(segs.size(), 0); }
-            plan.o_n[i] = v_total - r.o_in;
-            if (r.loud == Q3_LOUD_NORMALIZE) { w_off[i] = w_floats; w_floats += ((size_t)plan.o_n[i] + 3) & ~(size_t)3; }
-        }
-        if (r.level) {
-            if (!r.l_tail) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a level and no state", sg.row);
-            plan.l_in[i] = lv_total - r.l_in; plan.l_z[i] = level_emitted(lv_total, sg.last != 0) - r.n_in;
-            z_off[i] = z_floats; z_floats += ((size_t)plan.l_z[i] + 3) & ~(size_t)3;
-        }
-        plan.off[i] = plan.bytes;
-        plan.bytes = (plan.bytes + plan.count[i] * fmt_bytes(r.fmt) + 15) & ~(size_t)15;
-    }
-    if (plan.bytes > ps->out_cap) {
-        HIPC(hipSetDevice(ps->device));
-        dev_free(ps->out_dev); ps->out_dev = nullptr;
-        if (ps->out_host) { (void)hipHostFree(ps->out_host); ps->out_host = nullptr; }
-        ps->out_cap = 0;
-        HIPC(dev_malloc((void**)&ps->out_dev, plan.bytes * 2));
-        HIPC(hipHostMalloc((void**)&ps->out_host, plan.bytes * 2, hipHostMallocDefault));
-        ps->out_cap = plan.bytes * 2;
-    }
-    if (y_floats > 0) Q3C(dev_grow(ps, (void**)&ps->y_dev, &ps->y_cap, y_floats * 4));
-    if (z_floats > 0) Q3C(dev_grow(ps, (void**)&ps->z_dev, &ps->z_cap, z_floats * 4));
-    if (w_floats > 0) Q3C(dev_grow(ps, (void**)&ps->w_dev, &ps->w_cap, w_floats * 4));
-    if (v_floats > 0) Q3C(dev_grow(ps, (void**)&ps->v_dev, &ps->v_cap, v_floats * 4));
-    for (size_t i = 0; i < segs.size(); ++i) {
-        const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row];
-        if (r.ended || (sg.n == 0 && !sg.last)) continue;
-        if (r.te != TP_OFF) {
-            // (the buffer that is written is the one the last successful push did not write: its lags stay readable)
-            const int lw = r.t_lag_cur ^ 1; const long long nk = plan.t_k1[i] - r.t_frames;
-            if (nk > 0) { size_t cap_b = r.t_lag_cap[lw]; Q3C(dev_grow(ps, (void**)&r.t_lags[lw], &cap_b, (size_t)nk * sizeof(int))); r.t_lag_cap[lw] = cap_b; }
-        }
-        float* tails = ps->tails + (size_t)sg.row * 2 * PS_TAPS;
-        PsDesc d{};
-        d.src = sg.dev; d.n_new = (int)sg.n; d.n_out = (int)plan.count[i]; d.out = ps->out_dev + plan.off[i];
-        if (r.te != TP_OFF) {
-            char* in = r.t_state + (size_t)r.t_cur * TP_STATE_BYTES; char* out = r.t_state + (size_t)(r.t_cur ^ 1) * TP_STATE_BYTES;
-            TpDesc t{};
-            t.src = sg.dev; t.hist_in = r.t_in > 0 ? (const float*)(in + 16) : nullptr; t.hist_out = sg.last ? nullptr : (float*)(out + 16);
-            t.p_in = (const long long*)in; t.p_out = (long long*)out; t.lags = r.t_lags[r.t_lag_cur ^ 1];
-            t.y = ps->y_dev + y_off[i]; t.win = ps->t_win;
-            t.base = r.t_in; t.n_total = r.t_in + (long long)sg.n; t.hist_lo = tp_lo(r.t_frames, r.te); t.lo_next = tp_lo(plan.t_k1[i], r.te);
-            t.k0 = r.t_frames; t.k1 = plan.t_k1[i]; t.n_new = (int)sg.n; t.n_y = (int)plan.t_y[i]; t.tempo = r.te;
-            if (!sg.last && t.n_total - t.lo_next > TP_HIST) return set_err(Q3_INVALID_ARG, "pcm stage: row %d would keep %lld samples", sg.row, t.n_total - t.lo_next);
-            plan.tdesc.push_back(t);
-            d.src = t.y; d.n_new = t.n_y;                             // the resampler's input: the stretched samples
-        }
-        if (r.te != r.tempo) {
-            // (the step's input: the stretched samples where the stretcher runs, te != 1000, else the segment's own)
-            PtDesc q{};
-            q.src = d.src; q.n_new = (int)plan.p_n[i]; q.base = r.p_in; q.j0 = r.p_out;
-            q.tail_in = r.p_in > 0 ? r.p_tail + (size_t)r.p_cur * PS_TAPS : nullptr;
-            q.tail_out = sg.last ? nullptr : r.p_tail + (size_t)(r.p_cur ^ 1) * PS_TAPS;
-            q.v = ps->v_dev + v_off[i]; q.n_v = (int)plan.p_v[i]; q.sc = ps->p_tab; q.w2 = ps->p_tab + PT_SC_N;
-            q.t = r.tempo; q.te = r.te; q.den1 = 20 * std::max(r.tempo, r.te);
-            q.dq1 = (19 * PT_S1 * r.te) / q.den1; q.dr1 = (19 * PT_S1 * r.te) % q.den1;
-            q.fc = (float)(0.95 * (r.te < r.tempo ? (double)r.te / (double)r.tempo : 1.0));
-            plan.p_tiles = std::max(plan.p_tiles, (q.n_v + PS_TILE - 1) / PS_TILE);
-            plan.pdesc.push_back(q);
-            d.src = q.v; d.n_new = q.n_v;                             // the next step's input: the repitched samples
-        }
-        if (r.loud != Q3_LOUD_OFF && plan.o_n[i] > 0) {
-            LoDesc o{};
-            o.src = d.src; o.w = r.loud == Q3_LOUD_NORMALIZE ? ps->w_dev + w_off[i] : nullptr;
-            o.st_in = r.o_in > 0 ? r.o_state + (size_t)r.o_cur * LD_STATE : nullptr; o.st_out = r.o_state + (size_t)(r.o_cur ^ 1) * LD_STATE;
-            o.hist = r.o_state + 2 * (size_t)LD_STATE;
-            o.base = r.o_in; o.n_new = (int)plan.o_n[i]; o.mode = r.loud;
-            o.T = r.o_T; o.P = r.o_P; o.gate = r.o_gate; o.a_lo = r.o_lo; o.a_hi = r.o_hi;
-            memcpy(o.coef, ps->o_coef, sizeof(o.coef));
-            plan.odesc.push_back(o);
-            if (o.w) d.src = o.w;                                     // the next step's input: the normalised samples (the count stays)
-        }
-        if (r.level) {
-            // (the step's input: the samples as they left the steps in front, else the segment's own)
-            LvDesc l{};
-            l.src = d.src; l.n_new = (int)plan.l_in[i]; l.base = r.l_in; l.n_total = r.l_in + plan.l_in[i];
-            l.tail_in = r.l_in > 0 ? r.l_tail + (size_t)r.l_cur * LV_TAIL_PITCH : nullptr;
-            l.tail_out = sg.last ? nullptr : r.l_tail + (size_t)(r.l_cur ^ 1) * LV_TAIL_PITCH;
-            l.z = ps->z_dev + z_off[i]; l.o_base = r.n_in; l.n_z = (int)plan.l_z[i]; l.g = r.l_g; l.c = r.l_c;
-            plan.l_tiles = std::max(plan.l_tiles, (l.n_z + PS_TILE - 1) / PS_TILE);
-            plan.ldesc.push_back(l);
-            d.src = l.z; d.n_new = l.n_z;                             // the resampler's input: the levelled samples
-        }
-        d.base = r.n_in; d.i0 = r.n_out; d.L = r.r.L; d.M = r.r.M; d.fmt = r.fmt; d.taps = r.taps;
-        if (r.taps) { d.tail_in = r.fresh ? nullptr : tails + (size_t)r.cur * PS_TAPS; d.tail_out = tails + (size_t)(r.cur ^ 1) * PS_TAPS; }
-        plan.max_tiles = std::max(plan.max_tiles, (d.n_out + PS_TILE - 1) / PS_TILE);
-        plan.desc.push_back(d);
+// whether a step that is on has what its _set_* allocates
+static q3_status step_ready(const q3_pcm_stage* ps, const PsRow& r, int row, int s) {
+    switch (s) {
+    case ST_TEMPO: if (!r.tp.state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tempo and no state", row); break;
+    case ST_PITCH: if (!r.pt.tail || !ps->p_tab) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a pitch and no state", row); break;
+    case ST_LOUD: if (!r.ld.state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a loudness step and no state", row); break;
+    case ST_LEVEL: if (!r.lv.tail) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a level and no state", row); break;
+    default: break;
     }
     return Q3_OK;
 }
-// the one launch of a push: descriptors (plan.desc, uploaded by the caller) on the device
-hipError_t pcm_stage_launch(const PsDesc* desc_dev, const PsPlan& plan, hipStream_t st) {
-    if (plan.desc.empty()) return hipSuccess;
-    if (!plan.tdesc.empty()) {
-        // the stretcher's rows first: its descriptors go up from the stage's own pinned buffer (no push is in flight: each ends
-        // with a wait), one workgroup per row
-        q3_pcm_stage* ps = plan.ps;
-        const size_t tb = plan.tdesc.size() * sizeof(TpDesc);
-        if (tb > ps->td_cap) {
-            dev_free(ps->td_dev); ps->td_dev = nullptr;
-            if (ps->td_host) { (void)hipHostFree(ps->td_host); ps->td_host = nullptr; }
-            ps->td_cap = 0;
-            hipError_t e = dev_malloc((void**)&ps->td_dev, tb * 2);
-            if (e == hipSuccess) e = hipHostMalloc((void**)&ps->td_host, tb * 2, hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-            ps->td_cap = tb * 2;
-        }
-        memcpy(ps->td_host, plan.tdesc.data(), tb);
-        hipError_t e = hipMemcpyAsync(ps->td_dev, ps->td_host, tb, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_tempo, dim3((unsigned)plan.tdesc.size()), dim3(TP_THREADS), 0, st, (const TpDesc*)ps->td_dev);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+// One step's descriptor for one segment: w.n_in[s] new samples at src enter, w.n_out[s] leave into dst, the segment's slice of the
+// step's push buffer (the resampler's: of the staging buffer). Moves src on to what the next step reads.
+static q3_status step_fill(q3_pcm_stage* ps, PsPlan& plan, const PsSeg& sg, const SegWalk& w, int s, char* dst, const float*& src) {
+    StepPlan& p = ps->plan; const PsRow& r = ps->rows[(size_t)sg.row];
+    const int n_in = (int)w.n_in[s], n_out = (int)w.n_out[s];
+    switch (s) {
+    case ST_TEMPO: {
+        const TempoStep& tp = r.tp;
+        char* in = tp.state + (size_t)tp.cur * TP_STATE_BYTES; char* out = tp.state + (size_t)(tp.cur ^ 1) * TP_STATE_BYTES;
+        TpDesc t{};
+        t.src = src; t.hist_in = tp.in > 0 ? (const float*)(in + 16) : nullptr; t.hist_out = sg.last ? nullptr : (float*)(out + 16);
+        // (the lag buffer that is written is the one the last successful push did not write: its lags stay readable)
+        t.p_in = (const long long*)in; t.p_out = (long long*)out; t.lags = (int*)tp.lags[tp.lag_cur ^ 1].dev;
+        t.y = (float*)dst; t.win = ps->t_win;
+        t.base = tp.in; t.n_total = tp.in + n_in; t.hist_lo = tp_lo(tp.frames, tp.te); t.lo_next = tp_lo(w.frames, tp.te);
+        t.k0 = tp.frames; t.k1 = w.frames; t.n_new = n_in; t.n_y = n_out; t.tempo = tp.te;
+        if (!sg.last && t.n_total - t.lo_next > TP_HIST) return set_err(Q3_INVALID_ARG, "pcm stage: row %d would keep %lld samples", sg.row, t.n_total - t.lo_next);
+        p.tdesc.push_back(t);
+        break;
     }
-    if (!plan.pdesc.empty()) {
-        // the rows with a pitch, behind the stretcher: descriptors as above, a workgroup per tile of 256 outputs
-        q3_pcm_stage* ps = plan.ps;
-        const size_t pb = plan.pdesc.size() * sizeof(PtDesc);
-        if (pb > ps->pd_cap) {
-            dev_free(ps->pd_dev); ps->pd_dev = nullptr;
-            if (ps->pd_host) { (void)hipHostFree(ps->pd_host); ps->pd_host = nullptr; }
-            ps->pd_cap = 0;
-            hipError_t e = dev_malloc((void**)&ps->pd_dev, pb * 2);
-            if (e == hipSuccess) e = hipHostMalloc((void**)&ps->pd_host, pb * 2, hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-            ps->pd_cap = pb * 2;
-        }
-        memcpy(ps->pd_host, plan.pdesc.data(), pb);
-        hipError_t e = hipMemcpyAsync(ps->pd_dev, ps->pd_host, pb, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_pitch, dim3((unsigned)plan.p_tiles, (unsigned)plan.pdesc.size()), dim3(PS_TILE), 0, st, (const PtDesc*)ps->pd_dev);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+    case ST_PITCH: {
+        const PitchStep& pt = r.pt;
+        PtDesc q{};
+        q.src = src; q.n_new = n_in; q.base = pt.in; q.j0 = pt.out;
+        q.tail_in = pt.in > 0 ? pt.tail + (size_t)pt.cur * PS_TAPS : nullptr;
+        q.tail_out = sg.last ? nullptr : pt.tail + (size_t)(pt.cur ^ 1) * PS_TAPS;
+        q.v = (float*)dst; q.n_v = n_out; q.sc = ps->p_tab; q.w2 = ps->p_tab + PT_SC_N;
+        q.t = pt.t; q.te = pt.te; q.den1 = 20 * std::max(pt.t, pt.te);
+        q.dq1 = (19 * PT_S1 * pt.te) / q.den1; q.dr1 = (19 * PT_S1 * pt.te) % q.den1;
+        q.fc = (float)(0.95 * (pt.te < pt.t ? (double)pt.te / (double)pt.t : 1.0));
+        p.pdesc.push_back(q);
+        break;
     }
-    if (!plan.odesc.empty()) {
-        // the rows that meter or normalise, between the stretcher and the level: descriptors as above, one workgroup per row
-        q3_pcm_stage* ps = plan.ps;
-        const size_t ob = plan.odesc.size() * sizeof(LoDesc);
-        if (ob > ps->od_cap) {
-            dev_free(ps->od_dev); ps->od_dev = nullptr;
-            if (ps->od_host) { (void)hipHostFree(ps->od_host); ps->od_host = nullptr; }
-            ps->od_cap = 0;
-            hipError_t e = dev_malloc((void**)&ps->od_dev, ob * 2);
-            if (e == hipSuccess) e = hipHostMalloc((void**)&ps->od_host, ob * 2, hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-            ps->od_cap = ob * 2;
-        }
-        memcpy(ps->od_host, plan.odesc.data(), ob);
-        hipError_t e = hipMemcpyAsync(ps->od_dev, ps->od_host, ob, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_loud, dim3((unsigned)plan.odesc.size()), dim3(LD_THREADS), 0, st, (const LoDesc*)ps->od_dev);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+    case ST_LOUD: {
+        if (n_in == 0) return Q3_OK;                               // (nothing passes: no descriptor, no flip)
+        const LoudStep& ld = r.ld;
+        LoDesc o{};
+        o.src = src; o.w = (float*)dst;                            // (null where the row only meters: the samples pass as they are)
+        o.st_in = ld.in > 0 ? ld.state + (size_t)ld.cur * LD_STATE : nullptr; o.st_out = ld.state + (size_t)(ld.cur ^ 1) * LD_STATE;
+        o.hist = ld.state + 2 * (size_t)LD_STATE;
+        o.base = ld.in; o.n_new = n_in; o.mode = ld.mode;
+        o.T = ld.T; o.P = ld.P; o.gate = ld.gate; o.a_lo = ld.lo; o.a_hi = ld.hi;
+        memcpy(o.coef, ps->o_coef, sizeof(o.coef));
+        p.odesc.push_back(o);
+        if (!dst) return Q3_OK;
+        break;
     }
-    if (!plan.ldesc.empty()) {
-        // the rows with a level next, directly in front of the resampler: descriptors as above, a workgroup per tile of 256 outputs
-        q3_pcm_stage* ps = plan.ps;
-        const size_t lb = plan.ldesc.size() * sizeof(LvDesc);
-        if (lb > ps->ld_cap) {
-            dev_free(ps->ld_dev); ps->ld_dev = nullptr;
-            if (ps->ld_host) { (void)hipHostFree(ps->ld_host); ps->ld_host = nullptr; }
-            ps->ld_cap = 0;
-            hipError_t e = dev_malloc((void**)&ps->ld_dev, lb * 2);
-            if (e == hipSuccess) e = hipHostMalloc((void**)&ps->ld_host, lb * 2, hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-            ps->ld_cap = lb * 2;
-        }
-        memcpy(ps->ld_host, plan.ldesc.data(), lb);
-        hipError_t e = hipMemcpyAsync(ps->ld_dev, ps->ld_host, lb, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_level, dim3((unsigned)plan.l_tiles, (unsigned)plan.ldesc.size()), dim3(PS_TILE), 0, st, (const LvDesc*)ps->ld_dev);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+    case ST_LEVEL: {
+        const LevelStep& lv = r.lv;
+        LvDesc l{};
+        l.src = src; l.n_new = n_in; l.base = lv.in; l.n_total = lv.in + n_in;
+        l.tail_in = lv.in > 0 ? lv.tail + (size_t)lv.cur * LV_TAIL_PITCH : nullptr;
+        l.tail_out = sg.last ? nullptr : lv.tail + (size_t)(lv.cur ^ 1) * LV_TAIL_PITCH;
+        l.z = (float*)dst; l.o_base = lv.out; l.n_z = n_out; l.g = lv.g; l.c = lv.c;
+        p.ldesc.push_back(l);
+        break;
     }
-    hipLaunchKernelGGL(k_pcm_stage, dim3((unsigned)plan.max_tiles, (unsigned)plan.desc.size()), dim3(PS_TILE), 0, st, desc_dev);
+    default: {
+        const ResStep& rs = r.rs;
+        float* tails = ps->tails + (size_t)sg.row * 2 * PS_TAPS;
+        PsDesc d{};
+        d.src = src; d.n_new = n_in; d.n_out = n_out; d.out = dst;
+        d.base = rs.in; d.i0 = rs.out; d.L = rs.r.L; d.M = rs.r.M; d.fmt = rs.fmt; d.taps = rs.taps;
+        if (rs.taps) { d.tail_in = rs.fresh ? nullptr : tails + (size_t)rs.cur * PS_TAPS; d.tail_out = tails + (size_t)(rs.cur ^ 1) * PS_TAPS; }
+        plan.desc.push_back(d);
+        break;
+    }
+    }
+    p.tiles[s] = std::max(p.tiles[s], (n_out + PS_TILE - 1) / PS_TILE);
+    src = (const float*)dst;
+    return Q3_OK;
+}
+// The plan of a push, behind the silence step's pre-pass where a row has that step: walks every segment through the chain, lays its
+// slices out in the steps' push buffers (4 floats aligned) and its output in the staging buffer (16 bytes aligned), and writes
+// the descriptors. Changes no row. The buffers (and a row's lag buffer that is not the current one) may be reallocated: no push is
+// in flight (each ends with a wait).
+static q3_status chain_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan) {
+    StepPlan& p = ps->plan;
+    plan.desc.clear(); plan.off.assign(segs.size(), 0); plan.count.assign(segs.size(), 0); plan.bytes = 0;
+    p.tdesc.clear(); p.pdesc.clear(); p.odesc.clear(); p.ldesc.clear();
+    size_t floats[ST_N] = {0};
+    for (int s = 0; s < ST_N; ++s) p.tiles[s] = 1;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row]; SegWalk& w = p.seg[i];
+        w.runs = !r.ended && (w.n_front > 0 || sg.last);
+        if (!w.runs) continue;
+        chain_walk(r, ST_TEMPO, w.n_front, sg.last != 0, w);
+        for (int s = ST_TEMPO; s < ST_RES; ++s) {
+            if (!step_on(r, s)) continue;
+            Q3C(step_ready(ps, r, sg.row, s));
+            if (s == ST_LOUD && r.ld.mode != Q3_LOUD_NORMALIZE) continue;      // (a row that only meters writes no samples)
+            w.off[s] = floats[s]; floats[s] += ((size_t)w.n_out[s] + 3) & ~(size_t)3;
+        }
+        plan.count[i] = (size_t)w.n_out[ST_RES];
+        plan.off[i] = w.off[ST_RES] = plan.bytes;
+        plan.bytes = (plan.bytes + plan.count[i] * fmt_bytes(r.rs.fmt) + 15) & ~(size_t)15;
+    }
+    Q3C(buf_reserve(ps, ps->out, plan.bytes));
+    for (int s = ST_TEMPO; s < ST_RES; ++s) if (floats[s] > 0) Q3C(buf_reserve(ps, ps->buf[s], floats[s] * 4));
+    for (size_t i = 0; i < segs.size(); ++i) {
+        const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row]; const SegWalk& w = p.seg[i];
+        if (!w.runs) continue;
+        if (step_on(r, ST_TEMPO) && w.frames > r.tp.frames) Q3C(buf_reserve(ps, r.tp.lags[r.tp.lag_cur ^ 1], (size_t)(w.frames - r.tp.frames) * sizeof(int)));
+        const float* src = w.front;
+        for (int s = ST_TEMPO; s < ST_N; ++s) {
+            if (!step_on(r, s)) continue;
+            char* dst = s == ST_RES ? ps->out.dev + w.off[s] : s == ST_LOUD && r.ld.mode != Q3_LOUD_NORMALIZE ? nullptr : ps->buf[s].dev + w.off[s] * 4;
+            Q3C(step_fill(ps, plan, sg, w, s, dst, src));
+        }
+    }
+    return Q3_OK;
+}
+// The launches of a push behind the pre-pass, in chain order: each step's descriptors go up from the stage's own pinned buffer (no
+// push is in flight: each ends with a wait). The stretcher and the loudness step run a workgroup per row, the others one per tile
+// of 256 outputs and row. The resampler's descriptors (plan.desc) are on the device already, at desc_dev.
+static hipError_t chain_launch(q3_pcm_stage* ps, const PsPlan& plan, const PsDesc* desc_dev, hipStream_t st) {
+    const StepPlan& p = ps->plan;
+    hipError_t e = step_launch<TpDesc, k_tempo>(ps->desc[ST_TEMPO], p.tdesc, dim3((unsigned)p.tdesc.size()), dim3(TP_THREADS), st);
+    if (e == hipSuccess) e = step_launch<PtDesc, k_pitch>(ps->desc[ST_PITCH], p.pdesc, dim3((unsigned)p.tiles[ST_PITCH], (unsigned)p.pdesc.size()), dim3(PS_TILE), st);
+    if (e == hipSuccess) e = step_launch<LoDesc, k_loud>(ps->desc[ST_LOUD], p.odesc, dim3((unsigned)p.odesc.size()), dim3(LD_THREADS), st);
+    if (e == hipSuccess) e = step_launch<LvDesc, k_level>(ps->desc[ST_LEVEL], p.ldesc, dim3((unsigned)p.tiles[ST_LEVEL], (unsigned)p.ldesc.size()), dim3(PS_TILE), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_pcm_stage, dim3((unsigned)p.tiles[ST_RES], (unsigned)plan.desc.size()), dim3(PS_TILE), 0, st, desc_dev);
     return hipGetLastError();
 }
-// the push has succeeded (the caller waited for its stream): the rows move on
-void pcm_stage_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const PsPlan& plan) {
-    for (size_t k = 0; k < plan.trim.seg.size(); ++k) {            // the silence steps of the pre-pass
-        PsRow& r = ps->rows[(size_t)segs[(size_t)plan.trim.seg[k]].row];
-        r.s_in += plan.trim.n_new[k]; r.s_cur ^= 1;
-        memcpy(r.s_read, &plan.trim.res[k * TR_ST], sizeof(r.s_read));
-    }
+// the push has succeeded (the caller waited for its stream): every step that ran adds what the plan recorded, and flips
+static void chain_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs) {
+    const StepPlan& p = ps->plan;
+    for (size_t k = 0; k < p.sseg.size(); ++k) memcpy(ps->rows[(size_t)segs[(size_t)p.sseg[k]].row].sil.read, &p.sres[k * TR_ST], sizeof(SilStep::read));
     for (size_t i = 0; i < segs.size(); ++i) {
-        const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row];
-        if (r.ended || (sg.n == 0 && !sg.last)) continue;
-        const bool pitch = r.te != r.tempo;
-        if (r.te != TP_OFF) {
-            r.t_lag_cur ^= 1; r.t_lag_k0 = r.t_frames; r.t_lag_n = plan.t_k1[i] - r.t_frames;
-            r.t_in += (long long)sg.n; r.t_frames = plan.t_k1[i]; r.t_cur ^= 1;
+        const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row]; const SegWalk& w = p.seg[i];
+        auto add = [&](Totals& t, int s) { t.in += w.n_in[s]; t.out += w.n_out[s]; };
+        if (w.sil) { add(r.sil, ST_SIL); r.sil.cur ^= 1; }
+        if (!w.runs) continue;
+        if (step_on(r, ST_TEMPO)) {
+            TempoStep& tp = r.tp;
+            tp.lag_cur ^= 1; tp.lag_k0 = tp.frames; tp.lag_n = w.frames - tp.frames;
+            add(tp, ST_TEMPO); tp.frames = w.frames; tp.cur ^= 1;
         }
-        if (pitch) { r.p_in += plan.p_n[i]; r.p_out += plan.p_v[i]; if (!sg.last) r.p_cur ^= 1; }
-        if (r.loud != Q3_LOUD_OFF && plan.o_n[i] > 0) { r.o_in += plan.o_n[i]; r.o_cur ^= 1; }
-        if (r.level) { r.l_in += plan.l_in[i]; r.n_in += plan.l_z[i]; if (!sg.last) r.l_cur ^= 1; }
-        else r.n_in += pitch ? plan.p_v[i] : r.te != TP_OFF ? plan.t_y[i] : (long long)sg.n;
-        r.n_out += (long long)plan.count[i];
-        if (r.taps) { r.cur ^= 1; r.fresh = false; }
+        if (step_on(r, ST_PITCH)) { add(r.pt, ST_PITCH); if (!sg.last) r.pt.cur ^= 1; }
+        if (step_on(r, ST_LOUD) && w.n_in[ST_LOUD] > 0) { add(r.ld, ST_LOUD); r.ld.cur ^= 1; }
+        if (step_on(r, ST_LEVEL)) { add(r.lv, ST_LEVEL); if (!sg.last) r.lv.cur ^= 1; }
+        add(r.rs, ST_RES);
+        if (r.rs.taps) { r.rs.cur ^= 1; r.rs.fresh = false; }
         if (sg.last) r.ended = true;
     }
 }
-const char* pcm_stage_out_dev(const q3_pcm_stage* ps) { return ps->out_dev; }
-char* pcm_stage_out_host(const q3_pcm_stage* ps) { return ps->out_host; }
 
 // the stage's own stream, for pushes that do not come with one (created on the first: a stage behind a codec stream never needs it)
 static q3_status own_stream(q3_pcm_stage* ps) {
@@ -1724,55 +1754,57 @@ static q3_status own_stream(q3_pcm_stage* ps) {
     if (e != hipSuccess) { ps->st = nullptr; return set_err(Q3_HIP_ERROR, "hipStreamCreateWithFlags: %s", hipGetErrorString(e)); }
     return Q3_OK;
 }
-static q3_status in_reserve(q3_pcm_stage* ps, size_t bytes) {
-    if (bytes <= ps->in_cap) return Q3_OK;
-    dev_free(ps->in_dev); ps->in_dev = nullptr;
-    if (ps->in_host) { (void)hipHostFree(ps->in_host); ps->in_host = nullptr; }
-    ps->in_cap = 0;
-    HIPC(dev_malloc((void**)&ps->in_dev, bytes * 2));
-    HIPC(hipHostMalloc((void**)&ps->in_host, bytes * 2, hipHostMallocDefault));
-    ps->in_cap = bytes * 2;
+
+// The push sequence (q3_engine.h says what each call is for). Every row at most once and in range is the entry points' business
+// (pcm_stage_check_rows); here: n within max_push_samples — which applies to what enters the chain — and no samples for a row that
+// was flushed.
+q3_status pcm_stage_begin(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan) {
+    StepPlan& p = ps->plan;
+    p.seg.assign(segs.size(), SegWalk{}); p.sdesc.clear(); p.sseg.clear();
+    plan.desc.clear(); plan.off.assign(segs.size(), 0); plan.count.assign(segs.size(), 0); plan.bytes = 0; plan.late = false;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row];
+        if (sg.n > ps->max_push) return set_err(Q3_INVALID_ARG, "pcm stage: %zu samples for row %d, the stage takes %zu per push", sg.n, sg.row, ps->max_push);
+        if (r.ended && sg.n > 0) return set_err(Q3_INVALID_ARG, "pcm stage: row %d was flushed (last): q3_pcm_stage_reset or _set restarts it", sg.row);
+        p.seg[i].front = sg.dev; p.seg[i].n_front = (long long)sg.n;
+        if (step_on(r, ST_SIL)) plan.late = true;
+    }
+    return plan.late ? Q3_OK : chain_plan(ps, segs, plan);
+}
+q3_status pcm_stage_run(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan, const PsDesc* desc_dev, hipStream_t st) {
+    if (plan.late) {
+        Q3C(chain_prepass(ps, segs, st));
+        Q3C(chain_plan(ps, segs, plan));
+        desc_dev = nullptr;                                        // (planned too late for the caller's descriptor block)
+    }
+    if (plan.desc.empty()) return Q3_OK;                           // (a silence step may have taken samples and kept none yet)
+    if (!desc_dev) {
+        // (the front of the resampler's staging holds the descriptors; q3_pcm_stage_push has put the samples behind them already)
+        PairBuf& in = ps->desc[ST_RES];
+        HIPC(in.upload(plan.desc.data(), plan.desc.size() * sizeof(PsDesc), st));
+        desc_dev = (const PsDesc*)in.dev;
+    }
+    HIPC(chain_launch(ps, plan, desc_dev, st));
+    if (plan.bytes > 0) HIPC(hipMemcpyAsync(ps->out.host, ps->out.dev, plan.bytes, hipMemcpyDeviceToHost, st));
     return Q3_OK;
 }
-
-// plan.desc into the stage's own staging, for a caller that has no descriptor block of its own to carry it (or planned too late for
-// it: behind a silence step)
-// (the input staging's front holds the descriptors; q3_pcm_stage_push has put the samples behind them already)
-q3_status pcm_stage_desc_upload(q3_pcm_stage* ps, const PsPlan& plan, hipStream_t st, const PsDesc** desc_dev) {
-    const size_t db = plan.desc.size() * sizeof(PsDesc);
-    if (ps->in_cap < db) Q3C(in_reserve(ps, db));
-    memcpy(ps->in_host, plan.desc.data(), db);
-    HIPC(hipMemcpyAsync(ps->in_dev, ps->in_host, db, hipMemcpyHostToDevice, st));
-    *desc_dev = (const PsDesc*)ps->in_dev;
-    return Q3_OK;
+void pcm_stage_finish(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const PsPlan& plan, void* const* out_host, size_t* n_samples) {
+    for (size_t i = 0; i < segs.size(); ++i) {
+        if (n_samples) n_samples[i] = plan.count[i];
+        if (out_host && out_host[i] && plan.count[i] > 0) memcpy(out_host[i], ps->out.host + plan.off[i], plan.count[i] * fmt_bytes(ps->rows[(size_t)segs[i].row].rs.fmt));
+    }
+    chain_commit(ps, segs);
 }
-
-// Segments already on the device (readable by work on `st` — the caller's own stream, or nullptr for the stage's): one descriptor
-// upload, the launch, the copy of the converted bytes to the host, a wait. out_host[i] (may be null) receives plan.count[i]
-// samples of segment i. The rows move on only when all of it has succeeded.
-q3_status pcm_stage_push_dev(q3_pcm_stage* ps, const std::vector<PsSeg>& segs_in, hipStream_t st, void* const* out_host, size_t* n_samples) {
+q3_status pcm_stage_push_dev(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, hipStream_t st, void* const* out_host, size_t* n_samples) {
     PsPlan plan;
-    std::vector<PsSeg> trimmed;                                    // (a copy only where a row has a silence step)
-    if (pcm_stage_has_trim(ps, segs_in)) {
+    Q3C(pcm_stage_begin(ps, segs, plan));
+    if (plan.late || !plan.desc.empty()) {
         HIPC(hipSetDevice(ps->device));
         if (!st) { Q3C(own_stream(ps)); st = ps->st; }
-        trimmed = segs_in;
-        Q3C(pcm_stage_trim(ps, trimmed, st, plan));
+        Q3C(pcm_stage_run(ps, segs, plan, nullptr, st));
+        if (!plan.desc.empty()) HIPC(hipStreamSynchronize(st));
     }
-    const std::vector<PsSeg>& segs = trimmed.empty() ? segs_in : trimmed;
-    Q3C(pcm_stage_plan(ps, segs, plan));
-    for (size_t i = 0; i < segs.size(); ++i) if (n_samples) n_samples[i] = plan.count[i];
-    if (plan.desc.empty()) { pcm_stage_commit(ps, segs, plan); return Q3_OK; }      // (a silence step may have taken samples and kept none yet)
-    HIPC(hipSetDevice(ps->device));
-    if (!st) { Q3C(own_stream(ps)); st = ps->st; }
-    const PsDesc* desc_dev = nullptr;
-    Q3C(pcm_stage_desc_upload(ps, plan, st, &desc_dev));
-    HIPC(pcm_stage_launch(desc_dev, plan, st));
-    if (plan.bytes > 0) HIPC(hipMemcpyAsync(ps->out_host, ps->out_dev, plan.bytes, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    for (size_t i = 0; i < segs.size(); ++i)
-        if (out_host && out_host[i] && plan.count[i] > 0) memcpy(out_host[i], ps->out_host + plan.off[i], plan.count[i] * fmt_bytes(ps->rows[(size_t)segs[i].row].fmt));
-    pcm_stage_commit(ps, segs, plan);
+    pcm_stage_finish(ps, segs, plan, out_host, n_samples);
     return Q3_OK;
 }
 
@@ -1791,13 +1823,15 @@ q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_ro
 size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last) {
     const PsRow& r = ps->rows[(size_t)row];
     if (r.ended || (n == 0 && !last)) return 0;
-    if (r.s_thr != 0) {
-        // a silence step in front: what comes is known after the pre-pass alone; the cap covers the a-priori bound
+    if (step_on(r, ST_SIL)) {
+        // what comes is known after the pre-pass alone; the cap covers the a-priori bound: the caps of the row's steps, in a row
         size_t b = 0;
-        (void)q3_pcm_stage_bound_silence(r.sr, r.tempo, r.pitch, r.level ? 1 : 0, r.s_edge, r.s_pause, n, &b);
+        (void)q3_pcm_stage_bound(r.rs.sr, chain_cap(r, n), &b);
         return b;
     }
-    return (size_t)std::max<long long>(0, row_emitted(r, n, last != 0) - r.n_out);
+    SegWalk w{};
+    chain_walk(r, ST_TEMPO, (long long)n, last != 0, w);
+    return (size_t)w.n_out[ST_RES];
 }
 
 extern "C" q3_status q3_pcm_stage_push(q3_pcm_stage* ps, int n_rows, const int* rows, const float* const* in_host, const size_t* n_in,
@@ -1821,14 +1855,15 @@ extern "C" q3_status q3_pcm_stage_push(q3_pcm_stage* ps, int n_rows, const int* 
     if (n_rows == 0) return Q3_OK;
     HIPC(hipSetDevice(ps->device));
     Q3C(own_stream(ps));
-    Q3C(in_reserve(ps, db + total * 4));
+    PairBuf& in = ps->desc[ST_RES];                                // the resampler's descriptors | the rows' new samples
+    HIPC(in.reserve(db + total * 4));
     std::vector<PsSeg> segs((size_t)n_rows);
     size_t off = db;
     for (int i = 0; i < n_rows; ++i) {
-        if (n_in[i] > 0) memcpy(ps->in_host + off, in_host[i], n_in[i] * 4);
-        segs[(size_t)i] = {rows[i], (const float*)(ps->in_dev + off), n_in[i], last ? last[i] : 0};
+        if (n_in[i] > 0) memcpy(in.host + off, in_host[i], n_in[i] * 4);
+        segs[(size_t)i] = {rows[i], (const float*)(in.dev + off), n_in[i], last ? last[i] : 0};
         off += ((n_in[i] + 3) & ~(size_t)3) * 4;
     }
-    if (total > 0) HIPC(hipMemcpyAsync(ps->in_dev + db, ps->in_host + db, total * 4, hipMemcpyHostToDevice, ps->st));
+    if (total > 0) HIPC(hipMemcpyAsync(in.dev + db, in.host + db, total * 4, hipMemcpyHostToDevice, ps->st));
     return pcm_stage_push_dev(ps, segs, ps->st, out_host, n_samples);
 }
