@@ -200,6 +200,8 @@ class Session:
         self._ref_frames = [0 if u.ref_codes is None else int(np.asarray(u.ref_codes).reshape(-1, 16).shape[0]) for u in utts]
         self._frame_budget = int(frame_budget)
         self._row_limit = [self._limit_of(u) for u in utts]       # frames a row can reach: sizes the PCM buffers of run()
+        # per row what sizes the buffers of next_chunks_out: [tempo, level on, pitch, silence (edge_ms, pause_ms) or None]
+        self._out_rows = [[1000, False, 0, None] for _ in utts]
         reqs = (CRequest * self.B)()
         for i, u in enumerate(utts):
             self._fill(reqs[i], u)
@@ -216,6 +218,10 @@ class Session:
 
     def _fill(self, r, u: Utterance):
         fill_request(r, u, self.options, self._keep)
+
+    def _note_out(self, b: int, field: int, value):
+        for r in (range(self.B) if int(b) < 0 else [int(b)]):
+            self._out_rows[r][field] = value
 
     def _limit_of(self, u: Utterance) -> int:
         lim = u.max_length if u.max_length is not None else (u.options or self.options).max_length
@@ -290,10 +296,7 @@ class Session:
         """The level of row b (-1: every row) in `next_chunks_out` (q3_session_set_level): a gain and the ceiling of its look-ahead
         peak limiter, in millibel (1/100 dB); (0, 0) = off. The window and the persistence of `set_tempo`."""
         check(lib.q3_session_set_level(self._h, int(b), int(gain_mb), int(ceiling_mb)))
-        lv = getattr(self, "_level", None) or [False] * self.B
-        for r in (range(self.B) if int(b) < 0 else [int(b)]):
-            lv[r] = bool(int(gain_mb) or int(ceiling_mb))
-        self._level = lv
+        self._note_out(b, 1, bool(int(gain_mb) or int(ceiling_mb)))
 
     def set_loudness(self, mode: int, target_mb: int = -1900, prior_mb: int = 0, b: int = -1):
         """The loudness step of row b (-1: every row) in `next_chunks_out` (q3_session_set_loudness): LOUD_OFF, LOUD_METER or
@@ -313,10 +316,7 @@ class Session:
         window and the persistence of `set_tempo`."""
         thr = silence_mb(threshold_db)
         check(lib.q3_session_set_silence(self._h, int(b), thr, int(edge_ms), int(pause_ms)))
-        v = getattr(self, "_silence", None) or [None] * self.B
-        for r in (range(self.B) if int(b) < 0 else [int(b)]):
-            v[r] = (int(edge_ms), int(pause_ms)) if thr else None
-        self._silence = v
+        self._note_out(b, 3, (int(edge_ms), int(pause_ms)) if thr else None)
 
     def silence(self, b: int = 0) -> "Silence":
         """Row b's counts after its last streamed chunk (q3_session_silence)."""
@@ -329,10 +329,7 @@ class Session:
         as fast, 1000 = off. Legal while the row has streamed nothing since its start or its `replace`; the setting stays with the
         row across a `replace` until it is set again."""
         check(lib.q3_session_set_tempo(self._h, int(b), int(tempo_permille)))
-        t = getattr(self, "_tempo", None) or [1000] * self.B
-        for r in (range(self.B) if int(b) < 0 else [int(b)]):
-            t[r] = int(tempo_permille)
-        self._tempo = t
+        self._note_out(b, 0, int(tempo_permille))
 
     def set_pitch(self, cents: int, b: int = -1):
         """The pitch of row b (-1: every row) in `next_chunks_out` (q3_session_set_pitch): -1200..1200 cents, 0 = off; the row's
@@ -340,10 +337,7 @@ class Session:
         useful range for speech. The window and the persistence of `set_tempo`; a pitch that the row's tempo does not admit (the
         stretcher would leave 500..2000) is refused."""
         check(lib.q3_session_set_pitch(self._h, int(b), int(cents)))
-        c = getattr(self, "_pitch", None) or [0] * self.B
-        for r in (range(self.B) if int(b) < 0 else [int(b)]):
-            c[r] = int(cents)
-        self._pitch = c
+        self._note_out(b, 2, int(cents))
 
     def next_chunks_out(self) -> List[Tuple[Optional[AudioBuffer], bool]]:
         """`next_chunks` through the session's output stage (q3_session_next_chunks_out): one (chunk or None, done) per row, the
@@ -351,13 +345,10 @@ class Session:
         input samples back) come in the call that reports it done."""
         B = self.B; spf = self.model.config.samples_per_frame
         rate, s16 = getattr(self, "_out", (24000, False))
-        tempo = getattr(self, "_tempo", None) or [1000] * B
-        level = getattr(self, "_level", None) or [False] * B
-        pitch = getattr(self, "_pitch", None) or [0] * B
         n_in = max(self.options.chunk_frames, 1) * spf
-        sil = getattr(self, "_silence", None) or [None] * B
-        cap = {k: pcm_stage_bound(rate, n_in, k[0], k[1], k[2], k[3]) for k in set(zip(tempo, level, pitch, sil))}
-        bufs = [np.zeros(cap[(tempo[b], level[b], pitch[b], sil[b])], dtype=PCM_DTYPE[int(s16)]) for b in range(B)]
+        rows = [tuple(r) for r in self._out_rows]
+        cap = {k: pcm_stage_bound(rate, n_in, *k) for k in set(rows)}
+        bufs = [np.zeros(cap[rows[b]], dtype=PCM_DTYPE[int(s16)]) for b in range(B)]
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data_as(ctypes.c_void_p) for b in bufs])
         caps = (ctypes.c_size_t * B)(*[b.size for b in bufs])
         n = (ctypes.c_size_t * B)(); d = (ctypes.c_int * B)()

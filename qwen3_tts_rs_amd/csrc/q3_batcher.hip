@@ -174,18 +174,13 @@ struct BatTicket {
     // for it — already holds; the rest goes in with the next flush of q3_batcher_step. Host thread only.
     bool open = false, closed = false, close_taken = false; std::vector<uint32_t> text_all; size_t n_taken = 0;
     bool cancelled = false;                             // q3_batcher_cancel took its row (or its place in the queue)
-    // A streamed ticket's own output (q3_batcher_ticket_output; host thread, fixed before the step that follows `born`). o_conv: other
-    // than 24 kHz f32 — its samples go through the worker's output stage and land, as bytes of that format, in sout (under the
-    // worker's mutex, like spcm, which stays empty) and leave through q3_batcher_read_out alone.
-    long born = 0; uint32_t o_rate = 24000; int o_fmt = Q3_PCM_F32; bool o_conv = false; int o_tempo = 1000;      // (q3_batcher_ticket_tempo: the stage too)
-    int o_gain = 0, o_ceil = 0;                       // (q3_batcher_ticket_level: the stage too)
-    int o_pitch = 0;                                  // (q3_batcher_ticket_pitch, cents: the stage too)
-    // (q3_batcher_ticket_loudness: the stage too; lo_*: the reading after the parts that have landed, under the worker's mutex)
-    int o_loud = Q3_LOUD_OFF, o_target = -1900, o_prior = 0; float lo_M = 0.0f, lo_gain = 1.0f; int lo_blocks = 0, lo_gated = 0;
-    int o_sil = 0, o_edge = 0, o_pause = 20; int64_t si[5] = {0, 0, 0, 0, 0};      // the silence step (0: off) and its counts after the parts that have landed
-    bool o_stage() const { return o_rate != 24000 || o_fmt != Q3_PCM_F32 || o_tempo != 1000 || o_pitch != 0 || o_gain != 0 || o_ceil != 0 || o_loud != Q3_LOUD_OFF || o_sil != 0; }
+    // A streamed ticket's own output (q3_batcher_ticket_*; host thread, fixed before the step that follows `born`). Other than
+    // out.plain(), its samples go through the worker's output stage and land, as bytes of that format, in sout (under the worker's
+    // mutex, like spcm, which stays empty) and leave through q3_batcher_read_out alone. lo_* / si: the readings of its loudness
+    // and silence steps after the parts that have landed (under the worker's mutex; until then: out_*_at_rest)
+    long born = 0; OutSettings out;
+    float lo_M = 0.0f, lo_gain = 1.0f; int lo_blocks = 0, lo_gated = 0; int64_t si[5] = {0, 0, 0, 0, 0};
     std::vector<char> sout; size_t o_read = 0;
-    size_t o_bytes() const { return o_fmt == Q3_PCM_F32 ? 4 : o_fmt == Q3_PCM_S16 ? 2 : 1; }
     // Parking (q3_batcher_set_parking; host thread). rec: the ticket's row as a record while it reads PARKED; want_in: it
     // wants a row again (parked by the scheduler, or q3_batcher_unpark) — it stands in the waiting list once a frame is runnable;
     // units: its admission claim, which it keeps while parked; entered: frames it had committed when it entered its row (the time
@@ -321,7 +316,7 @@ static q3_status decoder_run(q3_batcher* b, BatTicket& t) {
 // own frames; after a failed push put the row back to frame 0, everything from the ticket's first (reference) frame, with `skip`
 // set to what was already delivered — no sample is lost or repeated. A joint push that is refused or fails is repeated row by
 // row, and the tickets whose own push fails are FAILED with its message.
-// A ticket with an output of its own (o_conv): its first part sets — and so restarts — the slot's row of the worker's output stage,
+// A ticket with an output of its own (not out.plain()): its first part sets — and so restarts — the slot's row of the worker's output stage,
 // its pushes carry that row, its last part flushes it. The stage follows the samples that were DELIVERED: the put-back above resets
 // the codec stream's row, never the stage's, so the ticket's listener hears neither a gap nor a repeat.
 static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
@@ -338,20 +333,20 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
         if (!t.s_failed) { t.s_failed = true; t.s_st = st; t.s_err = msg; }
     };
     struct Out { StreamPart* p; int n_new; std::vector<float> pcm; std::vector<char> out; size_t n_out = 0; };
-    auto flush_only = [&](const Out& o) { return o.n_new <= 0 && o.p->t->o_conv && o.p->last; };
+    auto flush_only = [&](const Out& o) { return o.n_new <= 0 && !o.p->t->out.plain() && o.p->last; };
     auto is_failed = [&](BatTicket& t) { std::lock_guard<std::mutex> g(d.mu); return t.s_failed; };
     // the samples of a served part land; a failed ticket's row and a finished one's give their blocks back
     auto land = [&](Out& o) {
         BatTicket& t = *o.p->t;
         t.s_deliv += o.n_new;
         float lm = 0.0f, lg = 1.0f; int lb = 0, lc = 0;
-        const bool loud = t.o_conv && t.o_loud != Q3_LOUD_OFF && q3_pcm_stage_loudness(d.ps, o.p->row, &lm, &lg, &lb, &lc) == Q3_OK;
+        const bool loud = t.out.loud != Q3_LOUD_OFF && q3_pcm_stage_loudness(d.ps, o.p->row, &lm, &lg, &lb, &lc) == Q3_OK;
         int64_t si[5] = {0, 0, 0, 0, 0};
-        const bool sil = t.o_conv && t.o_sil != 0 && q3_pcm_stage_silence(d.ps, o.p->row, &si[0], &si[1], &si[2], &si[3], &si[4]) == Q3_OK;
+        const bool sil = t.out.sil_mB != 0 && q3_pcm_stage_silence(d.ps, o.p->row, &si[0], &si[1], &si[2], &si[3], &si[4]) == Q3_OK;
         std::lock_guard<std::mutex> g(d.mu);
         if (loud) { t.lo_M = lm; t.lo_gain = lg; t.lo_blocks = lb; t.lo_gated = lc; }
         if (sil) memcpy(t.si, si, sizeof(si));
-        if (t.o_conv) t.sout.insert(t.sout.end(), o.out.begin(), o.out.begin() + (long)(o.n_out * t.o_bytes()));
+        if (!t.out.plain()) t.sout.insert(t.sout.end(), o.out.begin(), o.out.begin() + (long)(o.n_out * t.out.sample_bytes()));
         else t.spcm.insert(t.spcm.end(), o.pcm.begin(), o.pcm.end());
     };
     size_t i = 0;
@@ -363,16 +358,10 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
             seen[(size_t)p.row] = 1;
             if (st0 != Q3_OK) { fail(t, st0, q3_last_error()); continue; }
             if (p.first) { codec_stream_reset(d.cs, p.row); t.s_all = t.req.ref_codes; t.s_deliv = 0; }
-            if (p.first && t.o_conv) {
+            if (p.first && !t.out.plain()) {
                 q3_status so = Q3_OK;
                 if (!d.ps) so = q3_pcm_stage_create(m->device, b->stream_rows(), (size_t)std::min(b->frame_budget + b->prompt_budget, 100000) * spf, &d.ps);
-                if (so == Q3_OK) so = q3_pcm_stage_set(d.ps, p.row, t.o_rate, t.o_fmt);
-                if (so == Q3_OK) so = q3_pcm_stage_set_pitch(d.ps, p.row, 0);      // (the row may have had another ticket's, which need not admit this tempo)
-                if (so == Q3_OK) so = q3_pcm_stage_set_tempo(d.ps, p.row, t.o_tempo);      // (1000 too: the row may have had another ticket's)
-                if (so == Q3_OK && t.o_pitch != 0) so = q3_pcm_stage_set_pitch(d.ps, p.row, t.o_pitch);
-                if (so == Q3_OK) so = q3_pcm_stage_set_level(d.ps, p.row, t.o_gain, t.o_ceil);      // (off too, for the same reason)
-                if (so == Q3_OK) so = q3_pcm_stage_set_loudness(d.ps, p.row, t.o_loud, t.o_target, t.o_prior);      // (off too)
-                if (so == Q3_OK) so = q3_pcm_stage_set_silence(d.ps, p.row, t.o_sil, t.o_edge, t.o_pause);      // (off too)
+                if (so == Q3_OK) so = pcm_stage_apply(d.ps, p.row, "q3_batcher_step", t.out);      // (whatever the row's last ticket had)
                 if (so != Q3_OK) fail(t, so, q3_last_error());
             }
             if (is_failed(t)) continue;
@@ -382,11 +371,11 @@ static void decoder_stream_job(q3_batcher* b, std::vector<StreamPart>& parts) {
         auto push_of = [&](Out& o) {
             BatTicket& t = *o.p->t;
             const int n_ref = (int)(t.req.ref_codes.size() / 16), sp = codec_stream_pos(d.cs, o.p->row);
-            if (!t.o_conv) {
+            if (t.out.plain()) {
                 o.pcm.resize((size_t)o.n_new * spf);
                 return CsPush{o.p->row, n_ref + t.s_deliv + o.n_new - sp, n_ref + t.s_deliv - sp, t.s_all.data() + (size_t)sp * 16, nullptr, o.pcm.data()};
             }
-            o.out.resize(pcm_stage_count(d.ps, o.p->row, (size_t)o.n_new * spf, o.p->last) * t.o_bytes());
+            o.out.resize(pcm_stage_count(d.ps, o.p->row, (size_t)o.n_new * spf, o.p->last) * t.out.sample_bytes());
             CsPush p{o.p->row, 0, 0, nullptr, nullptr, nullptr};      // (no new frames: only the stage row's tail)
             if (o.n_new > 0) { p.n = n_ref + t.s_deliv + o.n_new - sp; p.skip = n_ref + t.s_deliv - sp; p.host = t.s_all.data() + (size_t)sp * 16; }
             p.ps = d.ps; p.ps_row = o.p->row; p.last = o.p->last; p.out_host = o.out.data(); p.n_out = &o.n_out;
@@ -1186,7 +1175,7 @@ extern "C" q3_status q3_batcher_poll(q3_batcher* b, int64_t ticket, int* state, 
     if (t.state == Q3_TICKET_PARKED) nf = parked_committed(t.rec);      // the frames it had committed when it left its row
     if (n_frames) *n_frames = nf;
     if (n_samples) *n_samples = t.pcm.size();         // (of a ticket still being vocoded: the samples it WILL hold — the size q3_batcher_fetch wants)
-    if (n_samples && t.streamed) { std::lock_guard<std::mutex> g(b->dec->mu); *n_samples = t.o_conv ? t.sout.size() / t.o_bytes() : t.spcm.size(); }      // streamed: the samples that have landed
+    if (n_samples && t.streamed) { std::lock_guard<std::mutex> g(b->dec->mu); *n_samples = t.out.plain() ? t.spcm.size() : t.sout.size() / t.out.sample_bytes(); }      // streamed: the samples that have landed
     return Q3_OK;
 }
 
@@ -1230,9 +1219,9 @@ extern "C" q3_status q3_batcher_read(q3_batcher* b, int64_t ticket, float* pcm_h
     if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_read: unknown ticket %lld", (long long)ticket);
     BatTicket& t = *it->second;
     if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_read: ticket %lld was not submitted as streamed (its samples come with q3_batcher_fetch)", (long long)ticket);
-    if (t.o_conv)
+    if (!t.out.plain())
         return set_err(Q3_INVALID_ARG, "q3_batcher_read: ticket %lld has an output of its own (%u Hz, %s): its samples come with q3_batcher_read_out", (long long)ticket,
-                       t.o_rate, t.o_fmt == Q3_PCM_S16 ? "s16" : t.o_fmt == Q3_PCM_ULAW ? "ulaw" : t.o_fmt == Q3_PCM_ALAW ? "alaw" : "f32");
+                       t.out.rate, t.out.fmt == Q3_PCM_S16 ? "s16" : t.out.fmt == Q3_PCM_ULAW ? "ulaw" : t.out.fmt == Q3_PCM_ALAW ? "alaw" : "f32");
     *n_samples = 0; *done = 0;
     stream_settle(b, t, false);
     if (t.state == Q3_TICKET_FAILED) return set_err(t.st, "%s", t.err.c_str());
@@ -1246,60 +1235,47 @@ extern "C" q3_status q3_batcher_read(q3_batcher* b, int64_t ticket, float* pcm_h
     return Q3_OK;
 }
 
+// The ticket setters: `edit` on the ticket's setting, legal for a streamed ticket between its submission and the next step. what: the
+// setting's name in the window's refusal.
+template <class Edit>
+static q3_status ticket_set(q3_batcher* b, int64_t ticket, const char* who, const char* what, Edit edit) {
+    if (!b) return set_err(Q3_INVALID_ARG, "%s: null batcher", who);
+    auto it = b->t.find(ticket);
+    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "%s: unknown ticket %lld", who, (long long)ticket);
+    BatTicket& t = *it->second;
+    if (!t.streamed) return set_err(Q3_INVALID_ARG, "%s: ticket %lld was not submitted as streamed", who, (long long)ticket);
+    OutSettings o = t.out;
+    Q3C(edit(who, o));
+    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
+        return set_err(Q3_INVALID_ARG, "%s: ticket %lld has been through a step: its %s is set between its submission and the next q3_batcher_step", who,
+                       (long long)ticket, what);
+    t.out = o;
+    return Q3_OK;
+}
 extern "C" q3_status q3_batcher_ticket_output(q3_batcher* b, int64_t ticket, uint32_t sample_rate, int format) {
-    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: null batcher");
-    auto it = b->t.find(ticket);
-    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: unknown ticket %lld", (long long)ticket);
-    BatTicket& t = *it->second;
-    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: ticket %lld was not submitted as streamed", (long long)ticket);
-    if (format < Q3_PCM_F32 || format > Q3_PCM_ALAW)
-        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: format must be Q3_PCM_F32 (0), Q3_PCM_S16 (1), Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)");
-    Q3C(q3_pcm_stage_taps(sample_rate, nullptr, 0, nullptr, nullptr));
-    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
-        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_output: ticket %lld has been through a step: its output is set between its submission and the next q3_batcher_step", (long long)ticket);
-    t.o_rate = sample_rate; t.o_fmt = format; t.o_conv = t.o_stage();
-    return Q3_OK;
+    return ticket_set(b, ticket, "q3_batcher_ticket_output", "output", [&](const char* who, OutSettings& o) { return out_set_output(who, o, sample_rate, format); });
 }
-
 extern "C" q3_status q3_batcher_ticket_tempo(q3_batcher* b, int64_t ticket, int tempo_permille) {
-    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: null batcher");
-    auto it = b->t.find(ticket);
-    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: unknown ticket %lld", (long long)ticket);
-    BatTicket& t = *it->second;
-    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: ticket %lld was not submitted as streamed", (long long)ticket);
-    if (tempo_permille < 500 || tempo_permille > 2000)
-        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: tempo %d permille out of range (500..2000; 1000 = off)", tempo_permille);
-    if (t.o_pitch != 0) Q3C(pcm_stage_pitch_checked("q3_batcher_ticket_tempo", tempo_permille, t.o_pitch));      // (its pitch has to admit the tempo)
-    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
-        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_tempo: ticket %lld has been through a step: its tempo is set between its submission and the next q3_batcher_step", (long long)ticket);
-    t.o_tempo = tempo_permille; t.o_conv = t.o_stage();
-    return Q3_OK;
+    return ticket_set(b, ticket, "q3_batcher_ticket_tempo", "tempo", [&](const char* who, OutSettings& o) { return out_set_tempo(who, o, tempo_permille); });
 }
-
 extern "C" q3_status q3_batcher_ticket_pitch(q3_batcher* b, int64_t ticket, int cents) {
-    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_pitch: null batcher");
-    auto it = b->t.find(ticket);
-    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_pitch: unknown ticket %lld", (long long)ticket);
-    BatTicket& t = *it->second;
-    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_pitch: ticket %lld was not submitted as streamed", (long long)ticket);
-    Q3C(pcm_stage_pitch_checked("q3_batcher_ticket_pitch", t.o_tempo, cents));
-    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
-        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_pitch: ticket %lld has been through a step: its pitch is set between its submission and the next q3_batcher_step", (long long)ticket);
-    t.o_pitch = cents; t.o_conv = t.o_stage();
+    return ticket_set(b, ticket, "q3_batcher_ticket_pitch", "pitch", [&](const char* who, OutSettings& o) { return out_set_pitch(who, o, cents); });
+}
+extern "C" q3_status q3_batcher_ticket_level(q3_batcher* b, int64_t ticket, int gain_mB, int ceiling_mB) {
+    return ticket_set(b, ticket, "q3_batcher_ticket_level", "level", [&](const char* who, OutSettings& o) { return out_set_level(who, o, gain_mB, ceiling_mB); });
+}
+extern "C" q3_status q3_batcher_ticket_loudness(q3_batcher* b, int64_t ticket, int mode, int target_mB, int prior_mB) {
+    Q3C(ticket_set(b, ticket, "q3_batcher_ticket_loudness", "loudness step",
+                   [&](const char* who, OutSettings& o) { return out_set_loudness(who, o, mode, target_mB, prior_mB); }));
+    BatTicket& t = *b->t.find(ticket)->second;
+    out_loudness_at_rest(t.out, &t.lo_M, &t.lo_gain, &t.lo_blocks, &t.lo_gated);      // (until a part lands)
     return Q3_OK;
 }
-
-extern "C" q3_status q3_batcher_ticket_loudness(q3_batcher* b, int64_t ticket, int mode, int target_mB, int prior_mB) {
-    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness: null batcher");
-    auto it = b->t.find(ticket);
-    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness: unknown ticket %lld", (long long)ticket);
-    BatTicket& t = *it->second;
-    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness: ticket %lld was not submitted as streamed", (long long)ticket);
-    Q3C(pcm_stage_loud_checked("q3_batcher_ticket_loudness", mode, target_mB, prior_mB));
-    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
-        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness: ticket %lld has been through a step: its loudness step is set between its submission and the next q3_batcher_step", (long long)ticket);
-    t.o_loud = mode; t.o_target = target_mB; t.o_prior = prior_mB; t.o_conv = t.o_stage();
-    (void)q3_pcm_stage_loudness_consts(target_mB, prior_mB, nullptr, &t.lo_gain, nullptr, nullptr, nullptr);      // (until a part lands: the prior)
+extern "C" q3_status q3_batcher_ticket_silence(q3_batcher* b, int64_t ticket, int threshold_mB, int edge_ms, int pause_ms) {
+    Q3C(ticket_set(b, ticket, "q3_batcher_ticket_silence", "silence step",
+                   [&](const char* who, OutSettings& o) { return out_set_silence(who, o, threshold_mB, edge_ms, pause_ms); }));
+    BatTicket& t = *b->t.find(ticket)->second;
+    out_silence_at_rest(&t.si[0], &t.si[1], &t.si[2], &t.si[3], &t.si[4]);      // (until a part lands)
     return Q3_OK;
 }
 
@@ -1308,7 +1284,7 @@ extern "C" q3_status q3_batcher_ticket_loudness_read(q3_batcher* b, int64_t tick
     auto it = b->t.find(ticket);
     if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness_read: unknown ticket %lld", (long long)ticket);
     BatTicket& t = *it->second;
-    if (t.o_loud == Q3_LOUD_OFF) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness_read: ticket %lld has no loudness step (q3_batcher_ticket_loudness)", (long long)ticket);
+    if (t.out.loud == Q3_LOUD_OFF) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_loudness_read: ticket %lld has no loudness step (q3_batcher_ticket_loudness)", (long long)ticket);
     std::lock_guard<std::mutex> g(b->dec->mu);
     if (mean_square) *mean_square = t.lo_M;
     if (gain) *gain = t.lo_gain;
@@ -1317,45 +1293,18 @@ extern "C" q3_status q3_batcher_ticket_loudness_read(q3_batcher* b, int64_t tick
     return Q3_OK;
 }
 
-extern "C" q3_status q3_batcher_ticket_silence(q3_batcher* b, int64_t ticket, int threshold_mB, int edge_ms, int pause_ms) {
-    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence: null batcher");
-    auto it = b->t.find(ticket);
-    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence: unknown ticket %lld", (long long)ticket);
-    BatTicket& t = *it->second;
-    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence: ticket %lld was not submitted as streamed", (long long)ticket);
-    Q3C(pcm_stage_silence_checked("q3_batcher_ticket_silence", threshold_mB, edge_ms, pause_ms));
-    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
-        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence: ticket %lld has been through a step: its silence step is set between its submission and the next q3_batcher_step", (long long)ticket);
-    t.o_sil = threshold_mB; t.o_edge = edge_ms; t.o_pause = pause_ms; t.o_conv = t.o_stage();
-    return Q3_OK;
-}
-
 extern "C" q3_status q3_batcher_ticket_silence_read(q3_batcher* b, int64_t ticket, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut) {
     if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence_read: null batcher");
     auto it = b->t.find(ticket);
     if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence_read: unknown ticket %lld", (long long)ticket);
     BatTicket& t = *it->second;
-    if (t.o_sil == 0) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence_read: ticket %lld has no silence step (q3_batcher_ticket_silence)", (long long)ticket);
+    if (t.out.sil_mB == 0) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_silence_read: ticket %lld has no silence step (q3_batcher_ticket_silence)", (long long)ticket);
     std::lock_guard<std::mutex> g(b->dec->mu);
     if (n_in) *n_in = t.si[0];
     if (n_out) *n_out = t.si[1];
     if (lead_cut) *lead_cut = t.si[2];
     if (pause_cut) *pause_cut = t.si[3];
     if (trail_cut) *trail_cut = t.si[4];
-    return Q3_OK;
-}
-
-extern "C" q3_status q3_batcher_ticket_level(q3_batcher* b, int64_t ticket, int gain_mB, int ceiling_mB) {
-    if (!b) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: null batcher");
-    auto it = b->t.find(ticket);
-    if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: unknown ticket %lld", (long long)ticket);
-    BatTicket& t = *it->second;
-    if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: ticket %lld was not submitted as streamed", (long long)ticket);
-    if (gain_mB < -6000 || gain_mB > 2400 || ceiling_mB < -2400 || ceiling_mB > 0)
-        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: gain %d mB / ceiling %d mB out of range (-6000..2400 / -2400..0; 0 / 0 = off)", gain_mB, ceiling_mB);
-    if (t.born != b->steps || t.state != Q3_TICKET_QUEUED)
-        return set_err(Q3_INVALID_ARG, "q3_batcher_ticket_level: ticket %lld has been through a step: its level is set between its submission and the next q3_batcher_step", (long long)ticket);
-    t.o_gain = gain_mB; t.o_ceil = ceiling_mB; t.o_conv = t.o_stage();
     return Q3_OK;
 }
 
@@ -1366,12 +1315,12 @@ extern "C" q3_status q3_batcher_read_out(q3_batcher* b, int64_t ticket, void* ou
     if (it == b->t.end()) return set_err(Q3_INVALID_ARG, "q3_batcher_read_out: unknown ticket %lld", (long long)ticket);
     BatTicket& t = *it->second;
     if (!t.streamed) return set_err(Q3_INVALID_ARG, "q3_batcher_read_out: ticket %lld was not submitted as streamed (its samples come with q3_batcher_fetch)", (long long)ticket);
-    if (!t.o_conv) return q3_batcher_read(b, ticket, (float*)out_host, cap_samples, n_samples, done);      // 24 kHz f32: the samples as they are
+    if (t.out.plain()) return q3_batcher_read(b, ticket, (float*)out_host, cap_samples, n_samples, done);      // 24 kHz f32: the samples as they are
     *n_samples = 0; *done = 0;
     stream_settle(b, t, false);
     if (t.state == Q3_TICKET_FAILED) return set_err(t.st, "%s", t.err.c_str());
     std::lock_guard<std::mutex> g(b->dec->mu);
-    const size_t sb = t.o_bytes();
+    const size_t sb = t.out.sample_bytes();
     size_t n = (t.sout.size() - t.o_read) / sb;
     if (n > cap_samples) n = cap_samples;
     if (n > 0) memcpy(out_host, t.sout.data() + t.o_read, n * sb);

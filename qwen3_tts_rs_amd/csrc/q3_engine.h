@@ -408,6 +408,22 @@ enum { PARK_MAX_SEGS = 24, PARK_PAYLOAD_INTS = 8 };      // one k_row_move launc
 constexpr size_t PARK_DESC_BYTES = (size_t)PARK_MAX_SEGS * 32 + (size_t)PARK_PAYLOAD_INTS * 16;
 struct ProfShape { int M, N, K, epi, rms, produce, tiled, count; };
 
+// What one row of an output stage has been asked for (Settings): the one value a stage row, a session row and a
+// batcher ticket hold. The defaults are a row with every step off. It changes through the checked edits (out_set_*, further down)
+// alone and reaches a stage row through pcm_stage_apply. (pause_ms: the silence step's range starts at 20, on or off.)
+struct OutSettings {
+    uint32_t rate = 24000; int fmt = Q3_PCM_F32;              // the resampler and the format
+    int tempo = 1000, cents = 0;                              // permille, 1000: off; cents, 0: off
+    int gain_mB = 0, ceil_mB = 0;                             // the level; 0 / 0: off
+    int loud = Q3_LOUD_OFF, target_mB = -1900, prior_mB = 0;
+    int sil_mB = 0, edge_ms = 0, pause_ms = 20;               // the silence step's threshold, 0: off
+    // 24 kHz f32 with every step off: the samples leave as they are, and no stage is needed
+    bool plain() const {
+        return rate == 24000 && fmt == Q3_PCM_F32 && tempo == 1000 && cents == 0 && gain_mB == 0 && ceil_mB == 0 && loud == Q3_LOUD_OFF && sil_mB == 0;
+    }
+    size_t sample_bytes() const { return fmt == Q3_PCM_F32 ? 4 : fmt == Q3_PCM_S16 ? 2 : 1; }
+};
+
 struct q3_session {
     q3_model* m = nullptr; int B = 0;
     hipStream_t stream = nullptr; bool owns_stream = true;     // the side session of a swap borrows its host's stream
@@ -461,14 +477,11 @@ struct q3_session {
     bool precapture = false;       // q3_session_prefill captures the frame while the prompt's kernels run (set by the callers that will replay it)
     CodecWS cws;
     q3_codec_stream* cstream = nullptr;   // q3_session_next_chunks, stream mode 1: per-row vocoder state (created on the first call)
-    // q3_session_next_chunks_out: the session's output (q3_session_set_output) and its stage, one row per session row (created on
-    // the first such call: out_started, after which the setting is fixed)
-    q3_pcm_stage* ostage = nullptr; uint32_t out_rate = 24000; int out_fmt = Q3_PCM_F32; bool out_started = false;
-    std::vector<int> out_tempo;           // q3_session_set_tempo: per row, permille (empty: every row at 1000)
-    std::vector<int> out_level;           // q3_session_set_level: per row, gain and ceiling in mB (empty: every row off)
-    std::vector<int> out_pitch;           // q3_session_set_pitch: per row, cents (empty: every row at 0)
-    std::vector<int> out_loud;            // q3_session_set_loudness: per row, mode, target and prior in mB (empty: every row off)
-    std::vector<int> out_sil;             // q3_session_set_silence: per row, threshold in mB, edge and pause in ms (empty: every row off)
+    // q3_session_next_chunks_out: its stage, one row per session row (created on the first such call: out_started, after which
+    // q3_session_set_output is refused), and what each row has been asked for (q3_session_set_*): a row's entry stays with it across
+    // q3_session_replace, and reaches the stage's row when the stage is created or, once it exists, with the setter
+    q3_pcm_stage* ostage = nullptr; bool out_started = false;
+    std::vector<OutSettings> out;
     // overlapped segment decode (q3_session_run): vocoder segments run on their own stream while the frame loop continues
     hipStream_t dec_stream = nullptr; hipEvent_t dec_ev = nullptr;
     std::vector<CodecWS> par_ws; std::vector<hipStream_t> par_streams;     // q3_session_run: utterances vocoded side by side
@@ -553,13 +566,25 @@ struct PsPlan { std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t
 // L / M = sr_out / 24000, the intake's (q3_intake.hip) at L / M = 24000 / sr_in
 Q3_HIDDEN void resampler_taps(int L, int M, std::vector<float>& out);
 Q3_HIDDEN int pcm_stage_rows(const q3_pcm_stage* ps);
-Q3_HIDDEN size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row);
 Q3_HIDDEN void pcm_stage_reset(q3_pcm_stage* ps, int row);
-Q3_HIDDEN q3_status pcm_stage_pitch_checked(const char* who, int tempo_permille, int cents);      // the ranges of q3_pcm_stage_set_pitch
-Q3_HIDDEN q3_status pcm_stage_loud_checked(const char* who, int mode, int target_mB, int prior_mB);      // the ranges of q3_pcm_stage_set_loudness
 Q3_HIDDEN q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_rows, const int* rows);
 Q3_HIDDEN size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last);
-Q3_HIDDEN q3_status pcm_stage_silence_checked(const char* who, int threshold_mB, int edge_ms, int pause_ms);      // the ranges of q3_pcm_stage_set_silence
+// The checked edits, one per public setter of every layer: the only way an OutSettings changes. Each validates the new values
+// against the rest of the setting (a tempo and a pitch have to admit each other) and writes them on success alone; a refusal
+// starts with `who`.
+Q3_HIDDEN q3_status out_set_output(const char* who, OutSettings& o, uint32_t sample_rate, int format);
+Q3_HIDDEN q3_status out_set_tempo(const char* who, OutSettings& o, int tempo_permille);
+Q3_HIDDEN q3_status out_set_pitch(const char* who, OutSettings& o, int cents);
+Q3_HIDDEN q3_status out_set_level(const char* who, OutSettings& o, int gain_mB, int ceiling_mB);
+Q3_HIDDEN q3_status out_set_loudness(const char* who, OutSettings& o, int mode, int target_mB, int prior_mB);
+Q3_HIDDEN q3_status out_set_silence(const char* who, OutSettings& o, int threshold_mB, int edge_ms, int pause_ms);
+// The only writer of a row's step settings: what the steps that `o` turns on need on the device, the values derived from `o`,
+// and the row's restart. All or nothing (but see the silence step's state there). pcm_stage_settings: what the row was given last.
+Q3_HIDDEN q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutSettings& o);
+Q3_HIDDEN const OutSettings& pcm_stage_settings(const q3_pcm_stage* ps, int row);
+// What a row that has taken no sample reads: its loudness step stands at the prior gain with no block, its silence step at five zeros
+Q3_HIDDEN void out_loudness_at_rest(const OutSettings& o, float* mean_square, float* gain, int* blocks, int* gated);
+Q3_HIDDEN void out_silence_at_rest(int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut);
 // A push of segments that are on the device, in three calls (one push per stage at a time; the rows move on in the last one alone):
 // begin   checks the segments and, unless a row has a silence step (plan.late), makes the plan: a caller with a descriptor block of
 //         its own can then carry plan.desc in it

@@ -879,12 +879,13 @@ struct PairBuf {
 };
 
 // ---- a row: its steps in chain order ----
-// Every step holds its setting, the running totals of the samples that have entered and left it since the row's (re)start, and its
+// The row holds what it was asked for (OutSettings) as pcm_stage_apply got it; every step holds what that function derived from it
+// for the chain and the kernels (a step's own test of being on among it: step_on), the running totals of the samples that have entered and left it since the row's (re)start, and its
 // state on the device in two copies: a push reads copy `cur` and writes the other, the commit flips. Between two steps that are on,
 // what has left the one in front is what has entered the one behind.
 struct Totals { long long in = 0, out = 0; };
 struct SilStep : Totals {                     // DESIGN 4.12e; thr == 0: off
-    int thr = 0, edge = 0, pause = 0; TrSet set = {0, 0, 0}; float theta = 0.0f;
+    int thr = 0; TrSet set = {0, 0, 0}; float theta = 0.0f;
     long long read[TR_ST] = {0, -1, 0, 0, 0, 0, 0, 0};        // the counters after the last successful push (the host's copy)
     char* state = nullptr; size_t copy = 0, cap = 0; int cur = 0;      // two copies of `copy` bytes: [TR_ST counters | tail | head]
     void reset() { in = out = 0; for (int i = 0; i < TR_ST; ++i) read[i] = i == TR_S_RUN ? -1 : 0; }
@@ -896,18 +897,18 @@ struct TempoStep : Totals {                   // DESIGN 4.12a; te: the tempo the
     DevBuf lags[2]; int lag_cur = 0; long long lag_k0 = 0, lag_n = 0;      // the lags of a push: lag_cur holds the last successful push's
     void reset() { in = out = 0; frames = 0; lag_k0 = lag_n = 0; }
 };
-struct PitchStep : Totals {                   // DESIGN 4.12d; the row's tempo t and pitch are one setting (tempo_pitch_set): the
-    int cents = 0, t = TP_OFF, te = TP_OFF;   // stretcher runs at te, this step brings the duration back to t; te == t: off
+struct PitchStep : Totals {                   // DESIGN 4.12d; the row's tempo t and pitch are one setting: the stretcher runs at
+    int t = TP_OFF, te = TP_OFF;              // te = pitch_te(t, cents), this step brings the duration back to t; te == t: off
     float* tail = nullptr; int cur = 0;       // two copies of 128 floats: the last 128 inputs
     void reset() { in = out = 0; }
 };
 struct LoudStep : Totals {                    // DESIGN 4.12c; out == in: the step holds nothing back
-    int mode = Q3_LOUD_OFF, target = -1900, prior = 0; float T = 0.0f, P = 1.0f, gate = 0.0f, lo = 0.0f, hi = 0.0f;
+    int mode = Q3_LOUD_OFF; float T = 0.0f, P = 1.0f, gate = 0.0f, lo = 0.0f, hi = 0.0f;
     float* state = nullptr; int cur = 0;      // two copies of LD_STATE floats, then the LD_HIST block values (one copy)
     void reset() { in = out = 0; }
 };
 struct LevelStep : Totals {
-    bool on = false; int gain_mB = 0, ceil_mB = 0; float g = 1.0f, c = 1.0f;
+    bool on = false; float g = 1.0f, c = 1.0f;
     float* tail = nullptr; int cur = 0;       // two copies of LV_TAIL_PITCH floats: the last 254 inputs
     void reset() { in = out = 0; }
 };
@@ -917,8 +918,9 @@ struct ResStep : Totals {                     // the resampler and 
     void reset() { in = out = 0; cur = 0; fresh = true; }
 };
 struct PsRow {
+    OutSettings asked;
     SilStep sil; TempoStep tp; PitchStep pt; LoudStep ld; LevelStep lv; ResStep rs;
-    bool ended = false;                       // flushed by a push with `last`: restarted by set / reset only
+    bool ended = false;                       // flushed by a push with `last`: restarted by pcm_stage_apply / reset only
     void reset() { sil.reset(); tp.reset(); pt.reset(); ld.reset(); lv.reset(); rs.reset(); ended = false; }
 };
 constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
@@ -1155,7 +1157,6 @@ static q3_status loud_checked(const char* who, int mode, int target_mB, int prio
         return set_err(Q3_INVALID_ARG, "%s: prior gain %d mB out of range (%d..%d)", who, prior_mB, LD_PRIOR_MIN, LD_PRIOR_MAX);
     return Q3_OK;
 }
-q3_status pcm_stage_loud_checked(const char* who, int mode, int target_mB, int prior_mB) { return loud_checked(who, mode, target_mB, prior_mB); }
 
 extern "C" q3_status q3_pcm_stage_loudness_consts(int target_mB, int prior_mB, float* T, float* P, float* gate_abs, float* a_lo, float* a_hi) {
     Q3C(loud_checked("q3_pcm_stage_loudness_consts", Q3_LOUD_OFF, target_mB, prior_mB));
@@ -1166,6 +1167,12 @@ extern "C" q3_status q3_pcm_stage_loudness_consts(int target_mB, int prior_mB, f
     if (a_lo) *a_lo = (float)pow(10.0, -2400.0 / 2000.0);
     if (a_hi) *a_hi = (float)pow(10.0, 2400.0 / 2000.0);
     return Q3_OK;
+}
+void out_loudness_at_rest(const OutSettings& o, float* mean_square, float* gain, int* blocks, int* gated) {
+    if (gain) (void)q3_pcm_stage_loudness_consts(o.target_mB, o.prior_mB, nullptr, gain, nullptr, nullptr, nullptr);
+    if (mean_square) *mean_square = 0.0f;
+    if (blocks) *blocks = 0;
+    if (gated) *gated = 0;
 }
 
 extern "C" q3_status q3_pcm_stage_create(int device, int rows, size_t max_push_samples, q3_pcm_stage** out) {
@@ -1198,36 +1205,11 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
 }
 
 int pcm_stage_rows(const q3_pcm_stage* ps) { return ps->R; }
-size_t pcm_stage_sample_bytes(const q3_pcm_stage* ps, int row) { return fmt_bytes(ps->rows[(size_t)row].rs.fmt); }
+const OutSettings& pcm_stage_settings(const q3_pcm_stage* ps, int row) { return ps->rows[(size_t)row].asked; }
 void pcm_stage_reset(q3_pcm_stage* ps, int row) { ps->rows[(size_t)row].reset(); }
 
 extern "C" q3_status q3_pcm_stage_reset(q3_pcm_stage* ps, int row) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_reset: bad row");
-    pcm_stage_reset(ps, row);
-    return Q3_OK;
-}
-
-extern "C" q3_status q3_pcm_stage_set(q3_pcm_stage* ps, int row, uint32_t sample_rate, int format) {
-    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set: bad row");
-    if (!fmt_ok(format)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set: format must be Q3_PCM_F32 (0), Q3_PCM_S16 (1), Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)");
-    Rate r;
-    Q3C(rate_checked("q3_pcm_stage_set", sample_rate, &r));      // (before the device is touched)
-    const float* taps = nullptr;
-    if (sample_rate != PS_RATE_IN) {
-        auto it = ps->taps.find(sample_rate);
-        if (it == ps->taps.end()) {
-            std::vector<float> t;
-            taps_of(r, t);
-            char what[48];
-            snprintf(what, sizeof(what), "tap table of %u Hz", sample_rate);
-            float* d = nullptr;
-            Q3C(table_upload(ps, &d, t.data(), t.size(), "q3_pcm_stage_set", what, "tap"));
-            it = ps->taps.emplace(sample_rate, d).first;
-        }
-        taps = it->second;
-    }
-    ResStep& rs = ps->rows[(size_t)row].rs;
-    rs.sr = sample_rate; rs.fmt = format; rs.r = r; rs.taps = taps;
     pcm_stage_reset(ps, row);
     return Q3_OK;
 }
@@ -1241,46 +1223,6 @@ static q3_status pitch_checked(const char* who, int tempo, int cents) {
         return set_err(Q3_INVALID_ARG, "%s: tempo %d permille with a pitch of %d cents needs the stretcher at %d permille (%d..%d)", who, tempo, cents, te,
                        TP_MIN, TP_MAX);
     return Q3_OK;
-}
-q3_status pcm_stage_pitch_checked(const char* who, int tempo_permille, int cents) { return pitch_checked(who, tempo_permille, cents); }
-
-// the row's tempo and pitch together (checked by the caller): what the stretcher at te and the pitch step need, then the restart
-static q3_status tempo_pitch_set(q3_pcm_stage* ps, int row, const char* who, int tempo, int cents) {
-    PsRow& r = ps->rows[(size_t)row];
-    const int te = pitch_te(tempo, cents);
-    if (te != TP_OFF) {
-        if (!ps->t_win) {
-            // periodic Hann, built in f64
-            std::vector<float> w((size_t)TP_W);
-            for (int j = 0; j < TP_W; ++j) w[(size_t)j] = (float)(0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * (double)j / (double)TP_W));
-            Q3C(table_upload(ps, &ps->t_win, w.data(), w.size(), who, "window", "window"));
-        }
-        Q3C(row_state(ps, &r.tp.state, 2 * TP_STATE_BYTES, who, "state", row));
-    }
-    if (te != tempo) {
-        if (!ps->p_tab) {
-            std::vector<float> sc, w2;
-            pitch_tables(sc, w2);
-            sc.insert(sc.end(), w2.begin(), w2.end());
-            Q3C(table_upload(ps, &ps->p_tab, sc.data(), sc.size(), who, "tables", "table"));
-        }
-        Q3C(row_state(ps, &r.pt.tail, 2 * (size_t)PS_TAPS * 4, who, "tail", row));
-    }
-    r.pt.t = tempo; r.pt.cents = cents; r.pt.te = r.tp.te = te;
-    pcm_stage_reset(ps, row);
-    return Q3_OK;
-}
-
-extern "C" q3_status q3_pcm_stage_set_tempo(q3_pcm_stage* ps, int row, int tempo_permille) {
-    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_tempo: bad row");
-    Q3C(pitch_checked("q3_pcm_stage_set_tempo", tempo_permille, ps->rows[(size_t)row].pt.cents));      // (before the device is touched)
-    return tempo_pitch_set(ps, row, "q3_pcm_stage_set_tempo", tempo_permille, ps->rows[(size_t)row].pt.cents);
-}
-
-extern "C" q3_status q3_pcm_stage_set_pitch(q3_pcm_stage* ps, int row, int cents) {
-    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_pitch: bad row");
-    Q3C(pitch_checked("q3_pcm_stage_set_pitch", ps->rows[(size_t)row].pt.t, cents));      // (before the device is touched)
-    return tempo_pitch_set(ps, row, "q3_pcm_stage_set_pitch", ps->rows[(size_t)row].pt.t, cents);
 }
 
 extern "C" q3_status q3_pcm_stage_pitch_plan(int tempo_permille, int cents, int* tempo_eff, double* cents_realized) {
@@ -1321,39 +1263,6 @@ extern "C" q3_status q3_pcm_stage_bound_pitch(uint32_t sample_rate, int tempo_pe
     return bound_through(sample_rate, tempo_permille, cents, with_level, 0, n_in, n_out_max);
 }
 
-extern "C" q3_status q3_pcm_stage_set_level(q3_pcm_stage* ps, int row, int gain_mB, int ceiling_mB) {
-    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_level: bad row");
-    Q3C(level_checked("q3_pcm_stage_set_level", gain_mB, ceiling_mB));      // (before the device is touched)
-    LevelStep& lv = ps->rows[(size_t)row].lv;
-    const bool on = gain_mB != 0 || ceiling_mB != 0;
-    if (on) Q3C(row_state(ps, &lv.tail, 2 * (size_t)LV_TAIL_PITCH * 4, "q3_pcm_stage_set_level", "state", row));
-    lv.on = on; lv.gain_mB = gain_mB; lv.ceil_mB = ceiling_mB;
-    (void)q3_pcm_stage_level_coeffs(gain_mB, ceiling_mB, &lv.g, &lv.c);
-    pcm_stage_reset(ps, row);
-    return Q3_OK;
-}
-
-extern "C" q3_status q3_pcm_stage_set_loudness(q3_pcm_stage* ps, int row, int mode, int target_mB, int prior_mB) {
-    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_loudness: bad row");
-    Q3C(loud_checked("q3_pcm_stage_set_loudness", mode, target_mB, prior_mB));      // (before the device is touched)
-    LoudStep& ld = ps->rows[(size_t)row].ld;
-    if (mode != Q3_LOUD_OFF) {
-        if (!ps->o_coef_set) {
-            // the K-weighting at 24 kHz: in f64, rounded once
-            double sh[6], hp[6];
-            Q3C(q3_loudness_kweight(PS_RATE_IN, sh, hp));
-            const double c[10] = {sh[0], sh[1], sh[2], sh[4], sh[5], hp[0], hp[1], hp[2], hp[4], hp[5]};
-            for (int i = 0; i < 10; ++i) ps->o_coef[i] = (float)c[i];
-            ps->o_coef_set = true;
-        }
-        Q3C(row_state(ps, &ld.state, (2 * (size_t)LD_STATE + LD_HIST) * 4, "q3_pcm_stage_set_loudness", "state", row));
-    }
-    ld.mode = mode; ld.target = target_mB; ld.prior = prior_mB;
-    (void)q3_pcm_stage_loudness_consts(target_mB, prior_mB, &ld.T, &ld.P, &ld.gate, &ld.lo, &ld.hi);
-    pcm_stage_reset(ps, row);
-    return Q3_OK;
-}
-
 // the blocks a row has stored once n samples have passed its loudness step
 static long long loud_blocks(long long n) { return std::min<long long>(LD_HIST, std::max<long long>(0, n / LD_HOP - 3)); }
 
@@ -1361,11 +1270,10 @@ extern "C" q3_status q3_pcm_stage_loudness(q3_pcm_stage* ps, int row, float* mea
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness: bad row");
     const LoudStep& ld = ps->rows[(size_t)row].ld;
     if (ld.mode == Q3_LOUD_OFF) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_loudness: row %d has no loudness step (q3_pcm_stage_set_loudness)", row);
-    float v[4] = {ld.P, ld.P, 0.0f, 0.0f};                        // A1 A2 M cg: a row that has taken no sample stands at its prior
-    if (ld.in > 0) {
-        HIPC(hipSetDevice(ps->device));
-        HIPC(q3_hipMemcpy(v, ld.state + (size_t)ld.cur * LD_STATE + LD_S_A1, sizeof(v), hipMemcpyDeviceToHost));
-    }
+    if (ld.in == 0) { out_loudness_at_rest(ps->rows[(size_t)row].asked, mean_square, gain, blocks, gated); return Q3_OK; }
+    float v[4];                                                    // A1 A2 M cg
+    HIPC(hipSetDevice(ps->device));
+    HIPC(q3_hipMemcpy(v, ld.state + (size_t)ld.cur * LD_STATE + LD_S_A1, sizeof(v), hipMemcpyDeviceToHost));
     int cg = 0; memcpy(&cg, &v[3], 4);
     if (mean_square) *mean_square = v[2];
     if (gain) *gain = v[0];
@@ -1409,7 +1317,6 @@ static q3_status silence_checked(const char* who, int threshold_mB, int edge_ms,
         return set_err(Q3_INVALID_ARG, "%s: pause cap of %d ms (%d..%d, a multiple of 10)", who, pause_ms, TR_PAUSE_MIN, TR_PAUSE_MAX);
     return Q3_OK;
 }
-q3_status pcm_stage_silence_checked(const char* who, int threshold_mB, int edge_ms, int pause_ms) { return silence_checked(who, threshold_mB, edge_ms, pause_ms); }
 
 extern "C" q3_status q3_pcm_stage_silence_hold(int edge_ms, int pause_ms, size_t* samples) {
     Q3C(silence_checked("q3_pcm_stage_silence_hold", 0, edge_ms, pause_ms));
@@ -1472,35 +1379,161 @@ extern "C" q3_status q3_silence_trim(const float* x, size_t n, int threshold_mB,
     return Q3_OK;
 }
 
-extern "C" q3_status q3_pcm_stage_set_silence(q3_pcm_stage* ps, int row, int threshold_mB, int edge_ms, int pause_ms) {
-    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_set_silence: bad row");
-    Q3C(silence_checked("q3_pcm_stage_set_silence", threshold_mB, edge_ms, pause_ms));      // (before the device is touched)
-    SilStep& sil = ps->rows[(size_t)row].sil;
-    const TrSet t = tr_set(edge_ms, pause_ms);
-    if (threshold_mB != 0) {
+// ---- settings (Settings) ----
+// The checked edits: every range of an output setting, and the rule that ties a tempo to a pitch, is in the *_checked functions
+// above and reaches every layer through these.
+q3_status out_set_output(const char* who, OutSettings& o, uint32_t sample_rate, int format) {
+    if (!fmt_ok(format)) return set_err(Q3_INVALID_ARG, "%s: format must be Q3_PCM_F32 (0), Q3_PCM_S16 (1), Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)", who);
+    Rate r;
+    Q3C(rate_checked(who, sample_rate, &r));
+    o.rate = sample_rate; o.fmt = format;
+    return Q3_OK;
+}
+q3_status out_set_tempo(const char* who, OutSettings& o, int tempo_permille) {
+    Q3C(pitch_checked(who, tempo_permille, o.cents));
+    o.tempo = tempo_permille;
+    return Q3_OK;
+}
+q3_status out_set_pitch(const char* who, OutSettings& o, int cents) {
+    Q3C(pitch_checked(who, o.tempo, cents));
+    o.cents = cents;
+    return Q3_OK;
+}
+q3_status out_set_level(const char* who, OutSettings& o, int gain_mB, int ceiling_mB) {
+    Q3C(level_checked(who, gain_mB, ceiling_mB));
+    o.gain_mB = gain_mB; o.ceil_mB = ceiling_mB;
+    return Q3_OK;
+}
+q3_status out_set_loudness(const char* who, OutSettings& o, int mode, int target_mB, int prior_mB) {
+    Q3C(loud_checked(who, mode, target_mB, prior_mB));
+    o.loud = mode; o.target_mB = target_mB; o.prior_mB = prior_mB;
+    return Q3_OK;
+}
+q3_status out_set_silence(const char* who, OutSettings& o, int threshold_mB, int edge_ms, int pause_ms) {
+    Q3C(silence_checked(who, threshold_mB, edge_ms, pause_ms));
+    o.sil_mB = threshold_mB; o.edge_ms = edge_ms; o.pause_ms = pause_ms;
+    return Q3_OK;
+}
+
+// `o` (which came through the checked edits) onto a row. First everything that can fail — the tables and the row's states of the
+// steps that `o` turns on, each made by the first call that needs it and kept from then on —, then the step fields, then the
+// restart: a call that fails leaves the row as it was and where it was. The one exception is a silence step whose state has to
+// grow: the old state is freed first (grow-only, and the row restarts anyway), so when the new one cannot be had the row is left
+// with its silence step off (asked.sil_mB == 0) and otherwise untouched. That allocation comes last, so nothing fails behind it.
+q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutSettings& o) {
+    PsRow& r = ps->rows[(size_t)row];
+    Rate rate;
+    Q3C(rate_checked(who, o.rate, &rate));                      // (before the device is touched)
+    const float* taps = nullptr;
+    if (o.rate != PS_RATE_IN) {
+        auto it = ps->taps.find(o.rate);
+        if (it == ps->taps.end()) {
+            std::vector<float> t;
+            taps_of(rate, t);
+            char what[48];
+            snprintf(what, sizeof(what), "tap table of %u Hz", o.rate);
+            float* d = nullptr;
+            Q3C(table_upload(ps, &d, t.data(), t.size(), who, what, "tap"));
+            it = ps->taps.emplace(o.rate, d).first;
+        }
+        taps = it->second;
+    }
+    const int te = pitch_te(o.tempo, o.cents);
+    if (te != TP_OFF) {
+        if (!ps->t_win) {
+            // periodic Hann, built in f64
+            std::vector<float> w((size_t)TP_W);
+            for (int j = 0; j < TP_W; ++j) w[(size_t)j] = (float)(0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * (double)j / (double)TP_W));
+            Q3C(table_upload(ps, &ps->t_win, w.data(), w.size(), who, "window", "window"));
+        }
+        Q3C(row_state(ps, &r.tp.state, 2 * TP_STATE_BYTES, who, "state", row));
+    }
+    if (te != o.tempo) {
+        if (!ps->p_tab) {
+            std::vector<float> sc, w2;
+            pitch_tables(sc, w2);
+            sc.insert(sc.end(), w2.begin(), w2.end());
+            Q3C(table_upload(ps, &ps->p_tab, sc.data(), sc.size(), who, "tables", "table"));
+        }
+        Q3C(row_state(ps, &r.pt.tail, 2 * (size_t)PS_TAPS * 4, who, "tail", row));
+    }
+    if (o.loud != Q3_LOUD_OFF) {
+        if (!ps->o_coef_set) {
+            // the K-weighting at 24 kHz: in f64, rounded once
+            double sh[6], hp[6];
+            Q3C(q3_loudness_kweight(PS_RATE_IN, sh, hp));
+            const double c[10] = {sh[0], sh[1], sh[2], sh[4], sh[5], hp[0], hp[1], hp[2], hp[4], hp[5]};
+            for (int i = 0; i < 10; ++i) ps->o_coef[i] = (float)c[i];
+            ps->o_coef_set = true;
+        }
+        Q3C(row_state(ps, &r.ld.state, (2 * (size_t)LD_STATE + LD_HIST) * 4, who, "state", row));
+    }
+    const bool level = o.gain_mB != 0 || o.ceil_mB != 0;
+    if (level) Q3C(row_state(ps, &r.lv.tail, 2 * (size_t)LV_TAIL_PITCH * 4, who, "state", row));
+    const TrSet ts = tr_set(o.edge_ms, o.pause_ms);
+    const size_t sil_copy = ((size_t)TR_ST * 8 + tr_state_floats(ts) * 4 + 15) & ~(size_t)15;
+    if (o.sil_mB != 0) {
         if (!ps->s_win) {
             float w[2 * TR_H];
             tr_window(w);
-            Q3C(table_upload(ps, &ps->s_win, w, 2 * TR_H, "q3_pcm_stage_set_silence", "seam weights", "weight"));
+            Q3C(table_upload(ps, &ps->s_win, w, 2 * TR_H, who, "seam weights", "weight"));
         }
-        const size_t copy = ((size_t)TR_ST * 8 + tr_state_floats(t) * 4 + 15) & ~(size_t)15;
-        if (2 * copy > sil.cap) {                                  // (the row restarts below: what the old state held is not needed)
-            dev_free(sil.state); sil.state = nullptr; sil.cap = 0;
-            const q3_status st = row_state(ps, &sil.state, 2 * copy, "q3_pcm_stage_set_silence", "state", row);
-            if (st != Q3_OK) { sil.thr = 0; return st; }
-            sil.cap = 2 * copy;
+        if (2 * sil_copy > r.sil.cap) {
+            dev_free(r.sil.state); r.sil.state = nullptr; r.sil.cap = 0;
+            const q3_status st = row_state(ps, &r.sil.state, 2 * sil_copy, who, "state", row);
+            if (st != Q3_OK) { r.sil.thr = 0; r.asked.sil_mB = 0; return st; }
+            r.sil.cap = 2 * sil_copy;
         }
-        sil.copy = copy;
     }
-    sil.thr = threshold_mB; sil.edge = edge_ms; sil.pause = pause_ms; sil.set = t; sil.theta = tr_theta(threshold_mB);
+    r.asked = o;
+    r.rs.sr = o.rate; r.rs.fmt = o.fmt; r.rs.r = rate; r.rs.taps = taps;
+    r.pt.t = o.tempo; r.pt.te = r.tp.te = te;
+    r.lv.on = level;
+    (void)q3_pcm_stage_level_coeffs(o.gain_mB, o.ceil_mB, &r.lv.g, &r.lv.c);
+    r.ld.mode = o.loud;
+    (void)q3_pcm_stage_loudness_consts(o.target_mB, o.prior_mB, &r.ld.T, &r.ld.P, &r.ld.gate, &r.ld.lo, &r.ld.hi);
+    r.sil.thr = o.sil_mB; r.sil.set = ts; r.sil.theta = tr_theta(o.sil_mB);
+    if (o.sil_mB != 0) r.sil.copy = sil_copy;
     pcm_stage_reset(ps, row);
     return Q3_OK;
+}
+
+// a public setter: the row's settings with one checked edit, applied
+template <class Edit>
+static q3_status stage_set(q3_pcm_stage* ps, int row, const char* who, Edit edit) {
+    if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "%s: bad row", who);
+    OutSettings o = ps->rows[(size_t)row].asked;
+    Q3C(edit(who, o));
+    return pcm_stage_apply(ps, row, who, o);
+}
+extern "C" q3_status q3_pcm_stage_set(q3_pcm_stage* ps, int row, uint32_t sample_rate, int format) {
+    return stage_set(ps, row, "q3_pcm_stage_set", [&](const char* who, OutSettings& o) { return out_set_output(who, o, sample_rate, format); });
+}
+extern "C" q3_status q3_pcm_stage_set_tempo(q3_pcm_stage* ps, int row, int tempo_permille) {
+    return stage_set(ps, row, "q3_pcm_stage_set_tempo", [&](const char* who, OutSettings& o) { return out_set_tempo(who, o, tempo_permille); });
+}
+extern "C" q3_status q3_pcm_stage_set_pitch(q3_pcm_stage* ps, int row, int cents) {
+    return stage_set(ps, row, "q3_pcm_stage_set_pitch", [&](const char* who, OutSettings& o) { return out_set_pitch(who, o, cents); });
+}
+extern "C" q3_status q3_pcm_stage_set_level(q3_pcm_stage* ps, int row, int gain_mB, int ceiling_mB) {
+    return stage_set(ps, row, "q3_pcm_stage_set_level", [&](const char* who, OutSettings& o) { return out_set_level(who, o, gain_mB, ceiling_mB); });
+}
+extern "C" q3_status q3_pcm_stage_set_loudness(q3_pcm_stage* ps, int row, int mode, int target_mB, int prior_mB) {
+    return stage_set(ps, row, "q3_pcm_stage_set_loudness", [&](const char* who, OutSettings& o) { return out_set_loudness(who, o, mode, target_mB, prior_mB); });
+}
+extern "C" q3_status q3_pcm_stage_set_silence(q3_pcm_stage* ps, int row, int threshold_mB, int edge_ms, int pause_ms) {
+    return stage_set(ps, row, "q3_pcm_stage_set_silence", [&](const char* who, OutSettings& o) { return out_set_silence(who, o, threshold_mB, edge_ms, pause_ms); });
+}
+
+void out_silence_at_rest(int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut) {
+    for (int64_t* p : {n_in, n_out, lead_cut, pause_cut, trail_cut}) if (p) *p = 0;
 }
 
 extern "C" q3_status q3_pcm_stage_silence(q3_pcm_stage* ps, int row, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut) {
     if (!ps || row < 0 || row >= ps->R) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_silence: bad row");
     const SilStep& sil = ps->rows[(size_t)row].sil;
     if (sil.thr == 0) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_silence: row %d has no silence step (q3_pcm_stage_set_silence)", row);
+    if (sil.in == 0) { out_silence_at_rest(n_in, n_out, lead_cut, pause_cut, trail_cut); return Q3_OK; }
     if (n_in) *n_in = sil.in;
     if (n_out) *n_out = sil.out;
     if (lead_cut) *lead_cut = sil.read[TR_S_LEAD];

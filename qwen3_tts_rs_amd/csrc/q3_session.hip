@@ -493,7 +493,7 @@ q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int fra
     { static std::atomic<uint64_t> next_uid{1}; s->uid = next_uid.fetch_add(1); }
     m->refs.fetch_add(1);
     if (s->opts.max_length < 1) return set_err(Q3_INVALID_ARG, "max_length must be >= 1");
-    s->seq.resize(batch);
+    s->seq.resize(batch); s->out.resize((size_t)batch);
     int rows = 0;
     for (int b = 0; b < batch; ++b) {
         const q3_request& r = reqs[b];
@@ -1780,126 +1780,65 @@ extern "C" q3_status q3_session_next_chunks(q3_session* s, float* const* pcm_hos
 }
 extern "C" q3_status q3_session_set_output(q3_session* s, uint32_t sample_rate, int format) {
     if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_output: null session");
-    if (format < Q3_PCM_F32 || format > Q3_PCM_ALAW)
-        return set_err(Q3_INVALID_ARG, "q3_session_set_output: format must be Q3_PCM_F32 (0), Q3_PCM_S16 (1), Q3_PCM_ULAW (2) or Q3_PCM_ALAW (3)");
-    Q3C(q3_pcm_stage_taps(sample_rate, nullptr, 0, nullptr, nullptr));      // the rate, before anything else
+    std::vector<OutSettings> next = s->out;
+    for (OutSettings& o : next) Q3C(out_set_output("q3_session_set_output", o, sample_rate, format));
     if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_output: the model has no device");
     bool started = s->out_started || s->stream_pos > 0;
     for (const SeqInfo& q : s->seq) started = started || q.stream_pos > 0;
     if (started) return set_err(Q3_INVALID_ARG, "q3_session_set_output: the session has streamed its first chunk: the output is set before it");
-    s->out_rate = sample_rate; s->out_fmt = format;
+    s->out = next;
+    return Q3_OK;
+}
+// The per-row setters (b = -1: every row): `edit` on a copy of each row's setting — no row changes unless every row accepts —, then
+// the window, then the rows' settings and, where the stage exists, its rows. what: the setting's name in the window's refusal.
+template <class Edit>
+static q3_status session_set_rows(q3_session* s, int b, const char* who, const char* what, Edit edit) {
+    if (!s) return set_err(Q3_INVALID_ARG, "%s: null session", who);
+    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "%s: row %d out of range (%d rows; -1 = every row)", who, b, s->B);
+    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
+    std::vector<OutSettings> next(s->out.begin() + b0, s->out.begin() + b1);
+    for (OutSettings& o : next) Q3C(edit(who, o));
+    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "%s: the model has no device", who);
+    for (int r = b0; r < b1; ++r)
+        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
+            return set_err(Q3_INVALID_ARG, "%s: row %d has streamed its first chunk: the %s is set before it, or after q3_session_replace", who, r, what);
+    for (int r = b0; r < b1; ++r) {
+        if (s->ostage) Q3C(pcm_stage_apply(s->ostage, r, who, next[(size_t)(r - b0)]));
+        s->out[(size_t)r] = next[(size_t)(r - b0)];
+    }
     return Q3_OK;
 }
 extern "C" q3_status q3_session_set_tempo(q3_session* s, int b, int tempo_permille) {
-    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: null session");
-    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: row %d out of range (%d rows; -1 = every row)", b, s->B);
-    if (tempo_permille < 500 || tempo_permille > 2000)
-        return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: tempo %d permille out of range (500..2000; 1000 = off)", tempo_permille);
-    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: the model has no device");
-    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
-    for (int r = b0; r < b1; ++r)
-        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
-            return set_err(Q3_INVALID_ARG, "q3_session_set_tempo: row %d has streamed its first chunk: the tempo is set before it, or after q3_session_replace", r);
-    for (int r = b0; r < b1 && !s->out_pitch.empty(); ++r)      // (a row's pitch has to admit the tempo)
-        if (s->out_pitch[(size_t)r] != 0) Q3C(pcm_stage_pitch_checked("q3_session_set_tempo", tempo_permille, s->out_pitch[(size_t)r]));
-    if (s->out_tempo.empty()) s->out_tempo.assign((size_t)s->B, 1000);
-    for (int r = b0; r < b1; ++r) {
-        if (s->ostage) Q3C(q3_pcm_stage_set_tempo(s->ostage, r, tempo_permille));
-        s->out_tempo[(size_t)r] = tempo_permille;
-    }
-    return Q3_OK;
+    return session_set_rows(s, b, "q3_session_set_tempo", "tempo", [&](const char* who, OutSettings& o) { return out_set_tempo(who, o, tempo_permille); });
 }
 extern "C" q3_status q3_session_set_pitch(q3_session* s, int b, int cents) {
-    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_pitch: null session");
-    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_pitch: row %d out of range (%d rows; -1 = every row)", b, s->B);
-    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
-    for (int r = b0; r < b1; ++r)
-        Q3C(pcm_stage_pitch_checked("q3_session_set_pitch", s->out_tempo.empty() ? 1000 : s->out_tempo[(size_t)r], cents));
-    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_pitch: the model has no device");
-    for (int r = b0; r < b1; ++r)
-        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
-            return set_err(Q3_INVALID_ARG, "q3_session_set_pitch: row %d has streamed its first chunk: the pitch is set before it, or after q3_session_replace", r);
-    if (s->out_pitch.empty()) s->out_pitch.assign((size_t)s->B, 0);
-    for (int r = b0; r < b1; ++r) {
-        if (s->ostage) Q3C(q3_pcm_stage_set_pitch(s->ostage, r, cents));
-        s->out_pitch[(size_t)r] = cents;
-    }
-    return Q3_OK;
+    return session_set_rows(s, b, "q3_session_set_pitch", "pitch", [&](const char* who, OutSettings& o) { return out_set_pitch(who, o, cents); });
 }
 extern "C" q3_status q3_session_set_level(q3_session* s, int b, int gain_mB, int ceiling_mB) {
-    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_level: null session");
-    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_level: row %d out of range (%d rows; -1 = every row)", b, s->B);
-    if (gain_mB < -6000 || gain_mB > 2400 || ceiling_mB < -2400 || ceiling_mB > 0)
-        return set_err(Q3_INVALID_ARG, "q3_session_set_level: gain %d mB / ceiling %d mB out of range (-6000..2400 / -2400..0; 0 / 0 = off)", gain_mB, ceiling_mB);
-    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_level: the model has no device");
-    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
-    for (int r = b0; r < b1; ++r)
-        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
-            return set_err(Q3_INVALID_ARG, "q3_session_set_level: row %d has streamed its first chunk: the level is set before it, or after q3_session_replace", r);
-    if (s->out_level.empty()) s->out_level.assign((size_t)s->B * 2, 0);
-    for (int r = b0; r < b1; ++r) {
-        if (s->ostage) Q3C(q3_pcm_stage_set_level(s->ostage, r, gain_mB, ceiling_mB));
-        s->out_level[(size_t)r * 2] = gain_mB; s->out_level[(size_t)r * 2 + 1] = ceiling_mB;
-    }
-    return Q3_OK;
+    return session_set_rows(s, b, "q3_session_set_level", "level", [&](const char* who, OutSettings& o) { return out_set_level(who, o, gain_mB, ceiling_mB); });
 }
 extern "C" q3_status q3_session_set_loudness(q3_session* s, int b, int mode, int target_mB, int prior_mB) {
-    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_loudness: null session");
-    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_loudness: row %d out of range (%d rows; -1 = every row)", b, s->B);
-    Q3C(pcm_stage_loud_checked("q3_session_set_loudness", mode, target_mB, prior_mB));
-    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_loudness: the model has no device");
-    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
-    for (int r = b0; r < b1; ++r)
-        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
-            return set_err(Q3_INVALID_ARG, "q3_session_set_loudness: row %d has streamed its first chunk: the loudness step is set before it, or after q3_session_replace", r);
-    if (s->out_loud.empty()) { s->out_loud.assign((size_t)s->B * 3, 0); for (int r = 0; r < s->B; ++r) s->out_loud[(size_t)r * 3 + 1] = -1900; }
-    for (int r = b0; r < b1; ++r) {
-        if (s->ostage) Q3C(q3_pcm_stage_set_loudness(s->ostage, r, mode, target_mB, prior_mB));
-        s->out_loud[(size_t)r * 3] = mode; s->out_loud[(size_t)r * 3 + 1] = target_mB; s->out_loud[(size_t)r * 3 + 2] = prior_mB;
-    }
-    return Q3_OK;
+    return session_set_rows(s, b, "q3_session_set_loudness", "loudness step",
+                            [&](const char* who, OutSettings& o) { return out_set_loudness(who, o, mode, target_mB, prior_mB); });
 }
 extern "C" q3_status q3_session_loudness(q3_session* s, int b, float* mean_square, float* gain, int* blocks, int* gated) {
     if (!s) return set_err(Q3_INVALID_ARG, "q3_session_loudness: null session");
     if (b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_loudness: row %d out of range (%d rows)", b, s->B);
-    if (s->out_loud.empty() || s->out_loud[(size_t)b * 3] == Q3_LOUD_OFF)
+    if (s->out[(size_t)b].loud == Q3_LOUD_OFF)
         return set_err(Q3_INVALID_ARG, "q3_session_loudness: row %d has no loudness step (q3_session_set_loudness)", b);
-    if (!s->ostage) {                                              // nothing streamed yet: the row stands at its prior
-        float P = 1.0f;
-        (void)q3_pcm_stage_loudness_consts(s->out_loud[(size_t)b * 3 + 1], s->out_loud[(size_t)b * 3 + 2], nullptr, &P, nullptr, nullptr, nullptr);
-        if (mean_square) *mean_square = 0.0f;
-        if (gain) *gain = P;
-        if (blocks) *blocks = 0;
-        if (gated) *gated = 0;
-        return Q3_OK;
-    }
+    if (!s->ostage) { out_loudness_at_rest(s->out[(size_t)b], mean_square, gain, blocks, gated); return Q3_OK; }      // nothing streamed yet
     return q3_pcm_stage_loudness(s->ostage, b, mean_square, gain, blocks, gated);
 }
 extern "C" q3_status q3_session_set_silence(q3_session* s, int b, int threshold_mB, int edge_ms, int pause_ms) {
-    if (!s) return set_err(Q3_INVALID_ARG, "q3_session_set_silence: null session");
-    if (b < -1 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_set_silence: row %d out of range (%d rows; -1 = every row)", b, s->B);
-    Q3C(pcm_stage_silence_checked("q3_session_set_silence", threshold_mB, edge_ms, pause_ms));
-    if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_silence: the model has no device");
-    const int b0 = b < 0 ? 0 : b, b1 = b < 0 ? s->B : b + 1;
-    for (int r = b0; r < b1; ++r)
-        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
-            return set_err(Q3_INVALID_ARG, "q3_session_set_silence: row %d has streamed its first chunk: the silence step is set before it, or after q3_session_replace", r);
-    if (s->out_sil.empty()) { s->out_sil.assign((size_t)s->B * 3, 0); for (int r = 0; r < s->B; ++r) s->out_sil[(size_t)r * 3 + 2] = 20; }
-    for (int r = b0; r < b1; ++r) {
-        if (s->ostage) Q3C(q3_pcm_stage_set_silence(s->ostage, r, threshold_mB, edge_ms, pause_ms));
-        s->out_sil[(size_t)r * 3] = threshold_mB; s->out_sil[(size_t)r * 3 + 1] = edge_ms; s->out_sil[(size_t)r * 3 + 2] = pause_ms;
-    }
-    return Q3_OK;
+    return session_set_rows(s, b, "q3_session_set_silence", "silence step",
+                            [&](const char* who, OutSettings& o) { return out_set_silence(who, o, threshold_mB, edge_ms, pause_ms); });
 }
 extern "C" q3_status q3_session_silence(q3_session* s, int b, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut) {
     if (!s) return set_err(Q3_INVALID_ARG, "q3_session_silence: null session");
     if (b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_silence: row %d out of range (%d rows)", b, s->B);
-    if (s->out_sil.empty() || s->out_sil[(size_t)b * 3] == 0)
+    if (s->out[(size_t)b].sil_mB == 0)
         return set_err(Q3_INVALID_ARG, "q3_session_silence: row %d has no silence step (q3_session_set_silence)", b);
-    if (!s->ostage) {                                              // nothing streamed yet
-        for (int64_t* p : {n_in, n_out, lead_cut, pause_cut, trail_cut}) if (p) *p = 0;
-        return Q3_OK;
-    }
+    if (!s->ostage) { out_silence_at_rest(n_in, n_out, lead_cut, pause_cut, trail_cut); return Q3_OK; }      // nothing streamed yet
     return q3_pcm_stage_silence(s->ostage, b, n_in, n_out, lead_cut, pause_cut, trail_cut);
 }
 extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_host, const size_t* cap_samples, size_t* n_samples, int* done) {
@@ -1909,20 +1848,7 @@ extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_
     if (!s->ostage) {
         const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
         Q3C(q3_pcm_stage_create(s->m->device, s->B, (size_t)chunk * samples_per_frame(s->m->cfg), &s->ostage));
-        for (int b = 0; b < s->B; ++b) Q3C(q3_pcm_stage_set(s->ostage, b, s->out_rate, s->out_fmt));
-        for (int b = 0; b < s->B && !s->out_tempo.empty(); ++b)
-            if (s->out_tempo[(size_t)b] != 1000) Q3C(q3_pcm_stage_set_tempo(s->ostage, b, s->out_tempo[(size_t)b]));
-        for (int b = 0; b < s->B && !s->out_pitch.empty(); ++b)
-            if (s->out_pitch[(size_t)b] != 0) Q3C(q3_pcm_stage_set_pitch(s->ostage, b, s->out_pitch[(size_t)b]));
-        for (int b = 0; b < s->B && !s->out_level.empty(); ++b)
-            if (s->out_level[(size_t)b * 2] != 0 || s->out_level[(size_t)b * 2 + 1] != 0)
-                Q3C(q3_pcm_stage_set_level(s->ostage, b, s->out_level[(size_t)b * 2], s->out_level[(size_t)b * 2 + 1]));
-        for (int b = 0; b < s->B && !s->out_loud.empty(); ++b)
-            if (s->out_loud[(size_t)b * 3] != Q3_LOUD_OFF)
-                Q3C(q3_pcm_stage_set_loudness(s->ostage, b, s->out_loud[(size_t)b * 3], s->out_loud[(size_t)b * 3 + 1], s->out_loud[(size_t)b * 3 + 2]));
-        for (int b = 0; b < s->B && !s->out_sil.empty(); ++b)
-            if (s->out_sil[(size_t)b * 3] != 0)
-                Q3C(q3_pcm_stage_set_silence(s->ostage, b, s->out_sil[(size_t)b * 3], s->out_sil[(size_t)b * 3 + 1], s->out_sil[(size_t)b * 3 + 2]));
+        for (int b = 0; b < s->B; ++b) Q3C(pcm_stage_apply(s->ostage, b, "q3_session_next_chunks_out", s->out[(size_t)b]));
     }
     s->out_started = true;
     return next_chunks(s, nullptr, cap_samples, n_samples, done, true, out_host);
