@@ -689,6 +689,19 @@ typedef struct q3_sample_rec {
     int eos_id, min_new_tokens, pad;
 } q3_sample_rec;
 q3_status q3_sample_row(const q3_options* opts, q3_sample_rec* out);
+/* q3_prompt_shape: the prompt layout a session derives from a request (host only: no device, no model; DESIGN "Prompt layout").
+ * n_text: the text tokens counted — the request's own n_text, or the text an open row has received so far. Row indices are relative
+ * to the row's first projected text row. The tables are optional (both or neither; cap_positions >= prefill_len): per prefill
+ * position the projected text row (-1: none) and the codec embedding (a codec id; -1: none, -2: the x-vector, -3 - i: the summed
+ * embeddings of reference frame i). A null request or record, a negative length and too small a table are Q3_INVALID_ARG. */
+typedef struct q3_prompt_shape_rec {
+    int32_t icl, n_ins, n_ref_text, n_icl, overlay;      /* ICL prompt; instruct / reference-text rows; ICL block and codec overlay positions */
+    int32_t prefill_len, n_rows;                         /* prefill positions; projected text rows (tts_eos included) */
+    int32_t trailing_len, n_trail;                       /* trailing text rows of the closed text (>= 1) / of an open text so far (no tts_eos) */
+    int32_t limit, open_need, prefix_pages;              /* max_length under the ICL cap; fewest text tokens an open row needs; cacheable pages */
+    int32_t r_role, r_pad, r_bos, r_text, r_eos, trail_base;
+} q3_prompt_shape_rec;
+q3_status q3_prompt_shape(const q3_request* req, int n_text, q3_prompt_shape_rec* out, int* text_row, int* codec_id, int cap_positions);
 /* q3_sample_ex (launch_sample): row b samples logits[b * ld .. + vocab) with the draw u[b * u_stride + (draw_idx ? draw_idx[b] : 0)]
  * under rows[b] (or `scalar` when rows is NULL) and writes tok[b]. seen [B][vocab] u8: penalty mask, marked at the sampled id.
  * token_count: per-row counters (NULL: token_count_static for every row). advance != 0: frame_idx / pos are advanced, unless the row

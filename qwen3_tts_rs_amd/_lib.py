@@ -105,6 +105,11 @@ class CSampleRow(ctypes.Structure):      # q3_sample_rec (the sampler's per-row 
                 ("use_rep", ctypes.c_int32), ("eos_id", ctypes.c_int32), ("min_new_tokens", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class CPromptShape(ctypes.Structure):    # q3_prompt_shape_rec (the prompt layout of a request)
+    _fields_ = [(n, ctypes.c_int32) for n in ("icl", "n_ins", "n_ref_text", "n_icl", "overlay", "prefill_len", "n_rows", "trailing_len", "n_trail",
+                                              "limit", "open_need", "prefix_pages", "r_role", "r_pad", "r_bos", "r_text", "r_eos", "trail_base")]
+
+
 class CSampleEx(ctypes.Structure):       # q3_sample_ex_args
     _fields_ = [(n, ctypes.c_int32) for n in ("B", "vocab", "ld", "u_stride", "u_elems", "advance", "token_count_static", "hist_stride_b",
                                               "hist_cap", "codec_eos", "use_suppress", "guard")] + [("scalar", CSampleRow)] + \
@@ -293,6 +298,7 @@ SYMBOLS = {
     "q3_rvq_embed_ex": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int]),
     "q3_silu_mul_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong]),
     "q3_sample_row": (c_int, [P(COptions), P(CSampleRow)]),
+    "q3_prompt_shape": (c_int, [P(CRequest), c_int, P(CPromptShape), c_void_p, c_void_p, c_int]),
     "q3_sample_ex": (c_int, [c_int, P(CSampleEx)]),
     "q3_frame_embed_ex": (c_int, [c_int, P(CFrameEmbedEx)]),
     "q3_cp_gather_ex": (c_int, [c_int, P(CCpGatherEx)]),

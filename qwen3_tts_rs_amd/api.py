@@ -1110,15 +1110,6 @@ class Qwen3TTS:
         finally:
             s.close()
 
-    @staticmethod
-    def prefill_shape(u: "Utterance") -> Tuple[int, int, int, int]:
-        """What fixes an utterance's prefill length: rows of one shape are prefilled together (q3_session_create groups a
-        ragged batch by it)."""
-        icl = u.ref_codes is not None and u.ref_text_ids is not None
-        n_ins = len(u.instruct_ids) if u.instruct_ids is not None else 0
-        n_icl = (len(np.asarray(u.ref_codes).reshape(-1, 16)) + 1) if icl else 0
-        return (u.mode(), n_ins, 1 if (len(u.text_ids) > 0 and not icl) else 0, n_icl)
-
     def synthesize_batch(self, utts: Sequence[Utterance], options=None):
         """Batch of arbitrary requests (any mix of prompt kinds and lengths): up to Q3_MAX_BATCH (64) of them per session — a
         session prefills rows of equal prefill length together and decodes all rows in one captured frame graph
@@ -2365,6 +2356,21 @@ def _io(arr, dtype, n, name):
     """a caller's in/out buffer: flat, C order, exactly n elements of dtype (written in place)"""
     assert isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.flags.c_contiguous and arr.ndim == 1 and arr.size == n, (name, n)
     return _vp(arr)
+
+
+def prompt_shape(u: Utterance, options: SynthesisOptions, n_text: Optional[int] = None, tables: bool = False):
+    """q3_prompt_shape: the prompt layout a session derives from a request (host only) — the record and, with `tables`, per prefill
+    position the projected text row and the codec embedding (-1: none, -2: the x-vector, -3 - i: reference frame i), row base 0.
+    n_text: the text tokens counted (default: the utterance's own; an open row's text so far)."""
+    r = CRequest(); keep = []; rec = _lib.CPromptShape()
+    fill_request(r, u, options, keep)
+    n = r.n_text if n_text is None else int(n_text)
+    check(lib.q3_prompt_shape(ctypes.byref(r), n, ctypes.byref(rec), None, None, 0))
+    if not tables:
+        return rec
+    tr = np.zeros(rec.prefill_len, np.int32); ci = np.zeros(rec.prefill_len, np.int32)
+    check(lib.q3_prompt_shape(ctypes.byref(r), n, ctypes.byref(rec), tr.ctypes.data_as(ctypes.c_void_p), ci.ctypes.data_as(ctypes.c_void_p), rec.prefill_len))
+    return rec, tr, ci
 
 
 def sample_row(options: SynthesisOptions) -> "_lib.CSampleRow":

@@ -77,11 +77,7 @@ q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limi
     // request's own max_length when its text closes (open_counts): the side session was created with the session's frame budget
     if (sq.opened) { nq.committed = 0; nq.max_length_req = limit; }
     s->seq[(size_t)b] = nq;
-    {   // the request's arrays live in the row's own vectors (the caller's pointers need not outlive the call)
-        SeqInfo& q = s->seq[(size_t)b];
-        q.req.text_ids = q.text.data(); q.req.instruct_ids = q.instruct.data(); q.req.ref_codes = q.ref_codes.data();
-        q.req.ref_text_ids = q.ref_text.data(); q.req.xvector = q.xvec.empty() ? nullptr : q.xvec.data();
-    }
+    s->seq[(size_t)b].req = s->seq[(size_t)b].request();      // the request's arrays live in the row's own vectors (the caller's pointers need not outlive the call)
     if (b == 0) s->stream_pos = 0;       // q3_session_next_chunk (the row-0 streaming call) starts over with the new utterance too
     if (s->cstream) codec_stream_reset(s->cstream, b);      // q3_session_next_chunks: the row's vocoder state belonged to the old utterance
     if (s->ostage) pcm_stage_reset(s->ostage, b);           // q3_session_next_chunks_out: so did its output row's
@@ -89,7 +85,7 @@ q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limi
     return Q3_OK;
 }
 // what a side session must satisfy before its rows may enter the host session
-q3_status transplant_check(q3_session* s, q3_session* side, int j, int limit_req, int* limit_out) {
+static q3_status transplant_check(q3_session* s, q3_session* side, int j, int limit_req, int* limit_out) {
     const SeqInfo& sq = side->seq[(size_t)j];
     if (side->opts.chunk_frames != s->opts.chunk_frames) return set_err(Q3_UNSUPPORTED, "q3_session_replace: chunk_frames is a property of the session");
     const int limit = limit_req < sq.limit ? limit_req : sq.limit;
@@ -104,10 +100,26 @@ q3_status transplant_check(q3_session* s, q3_session* side, int j, int limit_req
     return Q3_OK;
 }
 
-// a one-row side session takes the request with its text open (and already closed again, if the close came before the prefill)
-static q3_status side_open_text(q3_session* side, bool closed) {
-    Q3C(q3_session_open_text(side, 0));
-    if (closed) Q3C(q3_session_append_text(side, 0, nullptr, 0, 1));
+// The one side prefill (q3_engine.h): q3_session_replace, the batcher's stage worker and the groups of a ragged first batch.
+q3_status side_prefill(q3_session* host, const q3_request* reqs, const int* limit_req, int n, bool open_text, bool closed,
+                       bool prefix_common, hipStream_t borrow, std::unique_ptr<q3_session>* side_out, int* limit_out,
+                       const std::function<void()>& created) {
+    std::vector<q3_request> rq(reqs, reqs + n);
+    for (q3_request& r : rq) r.opts.max_length = host->max_frames;      // the side session draws the rows' PCG streams with the host session's stride
+    q3_session* side_raw = nullptr;
+    // (an open request: with the host's frame budget — an ICL row's length cap, which would size the side session, is not known yet)
+    Q3C(session_create(host->m, rq.data(), n, open_text ? host->max_frames : 0, 0, &side_raw, borrow));
+    std::unique_ptr<q3_session> side(side_raw);
+    side->kv_bf16 = host->kv_bf16;                      // the side session prefills in f32 and converts, as the host session did
+    side->prefix_common = prefix_common;
+    if (open_text) Q3C(q3_session_open_text(side.get(), 0));       // the one request is taken with its text open
+    if (open_text && closed) Q3C(q3_session_append_text(side.get(), 0, nullptr, 0, 1));      // ... and closed again: the close came before the prefill
+    if (created) created();
+    // (sampling options are per row — SampleRow —, resolved by the side session: an ICL request's repetition-penalty floor and
+    // length cap, lib.rs:913-929, come along)
+    for (int j = 0; j < n; ++j) Q3C(transplant_check(host, side.get(), j, limit_req[j], &limit_out[j]));
+    Q3C(q3_session_prefill(side.get()));                // ends with a synchronisation of the side stream
+    *side_out = std::move(side);
     return Q3_OK;
 }
 static q3_status session_replace(q3_session* s, int b, const q3_request* req, bool open_text, bool closed);
@@ -119,27 +131,16 @@ static q3_status session_replace(q3_session* s, int b, const q3_request* req, bo
     if (s->debug || s->profile) return set_err(Q3_UNSUPPORTED, "q3_session_replace: not on debug / profiling sessions");
     const q3_model* m = s->m;
     HIPC(hipSetDevice(m->device));
-    q3_request r = *req;
-    const int limit_req = r.opts.max_length;
+    const int limit_req = req->opts.max_length;
     if (limit_req < 1 || limit_req > s->max_frames) return set_err(Q3_UNSUPPORTED, "q3_session_replace: max_length %d outside 1..%d (the session's frame budget)", limit_req, s->max_frames);
-    r.opts.max_length = s->max_frames;                 // the side session draws the row's PCG stream with the host session's stride
     static const bool timing = getenv("Q3_REPLACE_TIMING") != nullptr;      // development aid: where a swap's milliseconds go
     const auto tp0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (timing) fprintf(stderr, "[q3 replace] %-8s %.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count());
     };
-    q3_session* side_raw = nullptr;
-    // (an open request: with the host's frame budget — an ICL row's length cap, which would size the side session, is not known yet)
-    Q3C(session_create(s->m, &r, 1, open_text ? s->max_frames : 0, 0, &side_raw, s->stream));      // on the host's stream: its frames and this prefill are serial anyway
-    std::unique_ptr<q3_session> side(side_raw);
-    side->kv_bf16 = s->kv_bf16;                        // the side session prefills in f32 and converts, as the host session did
-    if (open_text) Q3C(side_open_text(side.get(), closed));
-    lap("create");
-    // (sampling options are per row — SampleRow —, resolved by the side session: an ICL request's repetition-penalty floor and
-    // length cap, lib.rs:913-929, come along)
-    int limit = 0;
-    Q3C(transplant_check(s, side.get(), 0, limit_req, &limit));
-    Q3C(q3_session_prefill(side.get()));               // ends with a synchronisation of the side stream
+    std::unique_ptr<q3_session> side; int limit = 0;
+    // on the host's stream: its frames and this prefill are serial anyway
+    Q3C(side_prefill(s, req, &limit_req, 1, open_text, closed, false, s->stream, &side, &limit, [&] { lap("create"); }));
     lap("prefill");
     HIPC(sync_frames(s));             // no frame of the host session in flight while its row changes
     Q3C(transplant_row(s, b, side.get(), 0, limit));
@@ -553,22 +554,10 @@ static q3_status batcher_submit(q3_batcher* b, const q3_request* req, int want_p
 }
 
 // ---- open tickets: the text arrives in pieces ----
-// trailing text rows of a text of n_text tokens: what the prefill does not consume (open_trailing_ids of q3_session.hip)
-static int ticket_n_trail(const BatTicket& t, size_t n_text) {
-    const q3_request& r = t.req.r;
-    const bool icl = r.mode == Q3_MODE_VOICE_CLONE && r.n_ref > 0 && r.ref_codes && r.ref_text_ids;
-    if (!icl) return n_text > 1 ? (int)n_text - 1 : 0;
-    const long all = (long)r.n_ref_text + (long)n_text, n_icl = (long)r.n_ref + 1;
-    return all > n_icl ? (int)(all - n_icl) : 0;
-}
-// the frame limit of an open ticket with the text it has: its max_length, for an ICL ticket whose text is closed the length cap too
-static int ticket_limit(const BatTicket& t) {
-    const q3_request& r = t.req.r;
-    const bool icl = r.mode == Q3_MODE_VOICE_CLONE && r.n_ref > 0 && r.ref_codes && r.ref_text_ids;
-    int lim = r.opts.max_length;
-    if (icl && t.closed) { int cap = 6 * (int)t.text_all.size(); if (cap < 75) cap = 75; if (lim > cap) lim = cap; }
-    return lim;
-}
+// trailing text rows of a text of n_text tokens: what the prefill does not consume
+static int ticket_n_trail(const BatTicket& t, size_t n_text) { return prompt_shape(t.req.r, (int)n_text).n_trail; }
+// the frame limit of an open ticket with the text it has: its max_length, once its text is closed under the ICL cap over that text
+static int ticket_limit(const BatTicket& t) { return t.closed ? prompt_shape(t.req.r, (int)t.text_all.size()).limit : t.req.r.opts.max_length; }
 // text rows a slot of the batcher's session takes from an open ticket (its last row holds tts_pad: transplant_row)
 static int batcher_text_cap(const q3_batcher* b) { return (b->prompt_budget > 16 ? b->prompt_budget : 16) + 1024 - 1; }
 
@@ -580,8 +569,9 @@ extern "C" q3_status q3_batcher_submit_open(q3_batcher* b, const q3_request* req
     if (req->n_text < 1 || !req->text_ids)
         return set_err(Q3_INVALID_ARG, "q3_session_open_text: the request has no text token (an open row needs one at creation: the prefill consumes it)");
     for (int i = 0; i < req->n_text; ++i) if (req->text_ids[i] >= (uint32_t)b->m->cfg.text_vocab) return set_err(Q3_INVALID_ARG, "text id %u out of range", req->text_ids[i]);
-    if (req->mode == Q3_MODE_VOICE_CLONE && req->n_ref > 0 && req->ref_codes && req->ref_text_ids) {
-        const int need = req->n_ref + 1 - req->n_ref_text;
+    const PromptShape sh = prompt_shape(*req);
+    if (sh.icl) {
+        const int need = sh.open_need;
         if (req->n_text < need)
             return set_err(Q3_INVALID_ARG, "q3_session_open_text: the ICL request needs at least %d target text tokens at creation (%d given), so that tts_eos falls after the ICL block", need, req->n_text);
         if (req->opts.max_length > b->frame_budget)
@@ -818,9 +808,9 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
     auto admit = [&](const q3_request& rq, bool open, long* units_out, bool* wait, long extra = 0) -> bool {
         *wait = false; *units_out = 0;
         if (!b->s->paged) return true;
-        int S = 0, lim = 0; request_shape(rq, &S, &lim);
-        if (open) lim = rq.opts.max_length;          // an open ICL ticket's length cap is not known before its text closes
-        const long units = row_worst_units(S, lim, b->s->kv_bf16);
+        const PromptShape sh = prompt_shape(rq);
+        const int lim = open ? rq.opts.max_length : sh.limit;          // an open ICL ticket's length cap is not known before its text closes
+        const long units = row_worst_units(sh.prefill_len, lim, b->s->kv_bf16);
         *units_out = units;
         long mine = 0, claimed = 0; int running = 0;
         for (int r = 0; r < b->slots; ++r) {
@@ -875,9 +865,9 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
                     }
                     b->queue.erase(b->queue.begin());
                     if (b->stage.id == id) stage_drop(b);      // (a limit set after it was prefilled ahead) its side session goes with it
-                    int S = 0, lim = 0; request_shape(t.req.r, &S, &lim);
+                    const PromptShape sh = prompt_shape(t.req.r);
                     bat_fail(t, set_err(Q3_KV_OVERFLOW, "KV page pool exhausted: the request's %d prompt positions + %d frames need %ld page(s) (f32 equivalents), more than the pool's limit leaves",
-                                        S, lim, (units + 1) / 2));
+                                        sh.prefill_len, sh.limit, (units + 1) / 2));
                     finished++; continue;
                 }
                 b->queue.erase(b->queue.begin());
@@ -932,21 +922,17 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
         if (open) { text_now = t.text_all; t.n_taken = text_now.size(); t.close_taken = closed; }
         const int limit_req = rq.opts.max_length;
         if (limit_req < 1 || limit_req > b->s->max_frames) return;      // the synchronous path reports it on the ticket
-        rq.opts.max_length = b->s->max_frames;       // the side session draws the row's PCG stream with the host session's stride
         b->stage.id = id; b->stage.st = Q3_OK; b->stage.err.clear(); b->stage.side = nullptr; b->stage.limit = 0;
         q3_batcher* bp = b;
         try {
         b->stage.thr = std::thread([bp, rq, limit_req, open, closed, text_now]() {
             q3_batcher::Stage& g = bp->stage;
-            q3_session* side = nullptr;
+            std::unique_ptr<q3_session> side;
             q3_request rw = rq;
             if (open) { rw.text_ids = text_now.data(); rw.n_text = (int32_t)text_now.size(); }
             q3_status st = hipSetDevice(bp->m->device) == hipSuccess ? Q3_OK : set_err(Q3_HIP_ERROR, "hipSetDevice");
-            if (st == Q3_OK) st = session_create(bp->m, &rw, 1, open ? bp->s->max_frames : 0, 0, &side);          // a stream of its own: runs beside the frames
-            if (st == Q3_OK && open) st = side_open_text(side, closed);
-            if (st == Q3_OK) { side->kv_bf16 = bp->s->kv_bf16; st = transplant_check(bp->s, side, 0, limit_req, &g.limit); }
-            if (st == Q3_OK) st = q3_session_prefill(side);                            // ends with a synchronisation of that stream
-            g.side = side; g.st = st;
+            if (st == Q3_OK) st = side_prefill(bp->s, &rw, &limit_req, 1, open, closed, false, nullptr, &side, &g.limit);      // a stream of its own: runs beside the frames
+            g.side = side.release(); g.st = st;
             if (st != Q3_OK) g.err = q3_last_error();
         });
         } catch (...) { b->stage.id = -1; }          // no thread to be had: the swap prefills synchronously, as before

@@ -397,6 +397,18 @@ struct SeqInfo {
     bool opened = false, text_closed = true;
     std::vector<uint32_t> text_all;       // every text token received so far (the request's own first)
     int n_trail = 0, ready = 0x7fffffff, committed = 0;
+    // the row's request pointing at the row's own vectors (as BatReq::fix; an ICL row stays one with an empty transcript: the
+    // predicate reads the pointer)
+    q3_request request() const {
+        static const uint32_t none[1] = {0};
+        q3_request r = req;
+        r.text_ids = text.data(); r.n_text = (int32_t)text.size();
+        r.instruct_ids = instruct.empty() ? nullptr : instruct.data(); r.n_instruct = (int32_t)instruct.size();
+        r.ref_codes = ref_codes.empty() ? nullptr : ref_codes.data(); r.n_ref = (int32_t)(ref_codes.size() / 16);
+        r.ref_text_ids = !ref_text.empty() ? ref_text.data() : icl ? none : nullptr; r.n_ref_text = (int32_t)ref_text.size();
+        r.xvector = xvec.empty() ? nullptr : xvec.data();
+        return r;
+    }
 };
 
 struct ProfAcc { double ms = 0; double bytes = 0; long launches = 0; };
@@ -608,7 +620,15 @@ Q3_HIDDEN LmDims cp_dims(const q3_config& c);
 Q3_HIDDEN q3_status talker_step(q3_session* s, const int* pos_dev, int pos_static, bool with_head, int rows_per_seq = 1,
                                 const int* text_ready = nullptr);
 Q3_HIDDEN SampleRow sample_row(const q3_options& o);
-Q3_HIDDEN void request_shape(const q3_request& r, int* prefill_len, int* limit);
+// Prompt layout (DESIGN "Prompt layout"): everything a request's prompt kind and lengths decide, in one record (q3_prompt_shape_rec,
+// include/q3tts.h) made by one pure function. n_text: the text counted — the request's own, or what an open row has received so far
+// (prefill_len, n_rows and the row indices of a session row are those of its text at creation). The lengths must not be negative.
+using PromptShape = q3_prompt_shape_rec;
+Q3_HIDDEN int icl_frame_cap(int n_text);
+Q3_HIDDEN PromptShape prompt_shape(const q3_request& r, int n_text);
+static inline PromptShape prompt_shape(const q3_request& r) { return prompt_shape(r, r.n_text); }
+// per prefill position of a row whose text rows start at row_base: the text row and the codec embedding (-1: none, -2: the x-vector, -3 - i: reference frame i)
+Q3_HIDDEN void prompt_positions(const PromptShape& sh, const q3_request& r, int row_base, int* text_row, int* codec_id);
 Q3_HIDDEN long row_worst_units(int prefill_len, int limit, bool bf16);
 Q3_HIDDEN q3_request idle_request(int chunk_frames);
 Q3_HIDDEN q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int frame_budget, int prompt_budget, q3_session** out,
@@ -636,4 +656,11 @@ Q3_HIDDEN const SeqInfo& parked_seq(const q3_parked* p);
 // q3_prefix_cache.hip: see q3_prefix_cache.h
 // q3_batcher.hip
 Q3_HIDDEN q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limit);
-Q3_HIDDEN q3_status transplant_check(q3_session* s, q3_session* side, int j, int limit_req, int* limit_out);
+// n requests prefilled in a side session so that their rows can enter `host` (transplant_row): the side session and, per row, the
+// limit resolved from limit_req[j] (which the caller has checked against the host's frame budget). open_text: one request, taken
+// with its text open (closed: and closed again before the prefill); prefix_common: the rows link what their shortest cached chain
+// allows; borrow: the stream to prefill on (null: one of its own); created: called once the side session stands, before the
+// checks and the prefill. Of `host` it reads what never changes under a running frame (the stage worker calls it on its thread).
+Q3_HIDDEN q3_status side_prefill(q3_session* host, const q3_request* reqs, const int* limit_req, int n, bool open_text, bool closed,
+                                 bool prefix_common, hipStream_t borrow, std::unique_ptr<q3_session>* side_out, int* limit_out,
+                                 const std::function<void()>& created = nullptr);

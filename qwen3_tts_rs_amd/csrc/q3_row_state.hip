@@ -74,10 +74,6 @@ struct q3_parked {
 // the stash's scalars, 16 bytes apart: tok, token_count, pos, frame_idx, limit, trail_len, text_ready, then the SampleRow
 enum { PS_TOK = 0, PS_COUNT, PS_POS, PS_FIDX, PS_LIMIT, PS_TLEN, PS_READY, PS_SROW, PS_N };
 static size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
-static void fix_req(SeqInfo& q) {      // the request's arrays live in the SeqInfo's own vectors
-    q.req.text_ids = q.text.data(); q.req.instruct_ids = q.instruct.data(); q.req.ref_codes = q.ref_codes.data();
-    q.req.ref_text_ids = q.ref_text.data(); q.req.xvector = q.xvec.empty() ? nullptr : q.xvec.data();
-}
 // the segments between row b and a stash, in one direction; trail rows / pad row live at `trail_row` / `pad_row` of s->rows
 static void park_segments(q3_session* s, int b, const q3_parked& p, int trail_row, int pad_row, bool to_stash, std::vector<RowSeg>& out, size_t* max_bytes) {
     const int H = p.H, V = p.V;
@@ -195,7 +191,7 @@ extern "C" q3_status q3_session_park_row(q3_session* s, int b, q3_parked** out) 
     p->codes_host.assign(s->codes_host.begin() + (ptrdiff_t)((size_t)b * s->max_frames * 16), s->codes_host.begin() + (ptrdiff_t)(((size_t)b * s->max_frames + (size_t)p->committed) * 16));
     p->pages.assign(s->kv_rows[(size_t)b].begin(), s->kv_rows[(size_t)b].end());
     s->kv_rows[(size_t)b].assign(1, own[0]);
-    p->seq = q; fix_req(p->seq);
+    p->seq = q; p->seq.req = p->seq.request();      // the request's arrays live in the record's own vectors
     q.opened = false; q.text_closed = true; q.ready = 0x7fffffff;      // the vacated row: a closed row frozen at its count
     q.limit = p->committed; q.start_run = s->frames_run - p->committed; q.committed = p->committed;
     q.idle = true; q.stream_pos = 0;
@@ -244,7 +240,7 @@ extern "C" q3_status q3_session_resume_row(q3_session* s, int b, q3_parked* p) {
     // every `frames_run - start_run` of the engine keeps meaning "frames this row has committed" (an opened row counts in `committed`)
     nq.start_run = s->frames_run - p->committed; nq.committed = p->committed;
     nq.idle = false; nq.stream_pos = 0;
-    s->seq[(size_t)b] = nq; fix_req(s->seq[(size_t)b]);
+    s->seq[(size_t)b] = nq; s->seq[(size_t)b].req = s->seq[(size_t)b].request();
     if (b == 0) s->stream_pos = 0;
     if (s->cstream) codec_stream_reset(s->cstream, b);
     if (s->ostage) pcm_stage_reset(s->ostage, b);

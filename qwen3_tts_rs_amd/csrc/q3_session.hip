@@ -411,16 +411,52 @@ static q3_status frame_launch(q3_session* s) {
 }
 
 
-// prefill positions and frame limit of a request as session_create will resolve them (talker.rs:451-491 / 511-564 / 585-627; the
-// ICL length cap of lib.rs:913-929) — for callers that must know a row's worst-case KV extent before a session exists
-void request_shape(const q3_request& r, int* prefill_len, int* limit) {
-    const bool icl = r.mode == Q3_MODE_VOICE_CLONE && r.n_ref > 0 && r.ref_codes && r.ref_text_ids;
-    const int n_ins = r.mode == Q3_MODE_VOICE_DESIGN ? r.n_instruct : 0;
-    const int overlay = r.mode == Q3_MODE_VOICE_DESIGN ? 5 : 6;
-    *prefill_len = n_ins + 3 + overlay + ((r.n_text > 0 && !icl) ? 1 : 0) + (icl ? r.n_ref + 1 : 0);
-    int lim = r.opts.max_length;
-    if (icl) { int cap = 6 * r.n_text; if (cap < 75) cap = 75; if (lim > cap) lim = cap; }
-    *limit = lim;
+// ---- prompt layout (DESIGN "Prompt layout"): the one description of how a request becomes a prompt ----
+// the ICL length cap in frames over a text of n_text tokens (lib.rs:913-929)
+int icl_frame_cap(int n_text) { return std::max(75, 6 * n_text); }
+// Projected text rows of a request: [instruct…, im_start, assistant, newline, tts_pad, tts_bos, (ICL: ref_text…,) text…, tts_eos].
+// Prefill positions (talker.rs:451-491 CustomVoice / 511-564 voice clone / 585-627 VoiceDesign): instruct, role x 3, the codec
+// overlay over tts_pad… tts_bos, then the first text token — or, ICL, the block of n_ref + 1 positions that pairs
+// [ref_text, text, tts_eos] (tts_pad once that runs out) with codec_bos and the reference frames (the streaming overlay,
+// talker.rs:646-710). What the prefill does not consume is the trailing text (lib.rs:508-519; ICL: talker.rs:692-708).
+PromptShape prompt_shape(const q3_request& r, int n_text) {
+    PromptShape p{};
+    const bool vd = r.mode == Q3_MODE_VOICE_DESIGN;
+    p.icl = r.mode == Q3_MODE_VOICE_CLONE && r.n_ref > 0 && r.ref_codes && r.ref_text_ids;
+    p.n_ins = vd ? r.n_instruct : 0;
+    p.n_ref_text = p.icl ? r.n_ref_text : 0;
+    p.n_icl = p.icl ? r.n_ref + 1 : 0;                  // streaming overlay: icl_len = n_codec
+    p.overlay = vd ? 5 : 6;                             // think, think_bos, language, think_eos, (speaker | x-vector,) pad; codec_bos follows
+    p.prefill_len = p.n_ins + 3 + p.overlay + ((n_text > 0 && !p.icl) ? 1 : 0) + p.n_icl;
+    p.n_rows = p.n_ins + 5 + p.n_ref_text + n_text + 1;
+    const int n_all = p.n_ref_text + n_text;            // ICL: [ref_text, text], + tts_eos once closed
+    p.n_trail = p.icl ? std::max(n_all - p.n_icl, 0) : std::max(n_text - 1, 0);
+    p.trailing_len = p.icl ? std::max(n_all + 1 - p.n_icl, 1) : p.n_trail + 1;
+    p.limit = p.icl ? std::min(r.opts.max_length, icl_frame_cap(n_text)) : r.opts.max_length;
+    p.open_need = p.icl ? std::max(p.n_icl - p.n_ref_text, 1) : 1;      // tts_eos must fall after the ICL block
+    p.prefix_pages = vd ? r.n_instruct / KV_PAGE_POS : 0;      // the instruct positions, in whole pages (q3_prefix_cache.h)
+    p.r_role = p.n_ins; p.r_pad = p.r_role + 3; p.r_bos = p.r_pad + 1; p.r_text = p.r_bos + 1; p.r_eos = p.r_text + n_all;
+    if (p.icl) p.trail_base = n_all + 1 > p.n_icl ? p.r_text + p.n_icl : p.r_pad;
+    else p.trail_base = n_text > 1 ? p.r_text + 1 : p.r_eos;
+    return p;
+}
+void prompt_positions(const PromptShape& sh, const q3_request& r, int row_base, int* tr, int* ci) {
+    const int codec[7] = {CODEC_THINK, CODEC_THINK_BOS, (int)r.language_id, CODEC_THINK_EOS,
+                          r.mode == Q3_MODE_VOICE_CLONE ? -2 : (int)r.speaker_id, CODEC_PAD, CODEC_BOS};
+    int p = 0;
+    for (int i = 0; i < sh.n_ins + 3; ++i) { tr[p] = row_base + i; ci[p] = -1; ++p; }      // instruct, role: text alone
+    for (int i = 0; i < sh.overlay; ++i) {
+        tr[p] = row_base + (i == sh.overlay - 1 ? sh.r_bos : sh.r_pad);
+        ci[p] = codec[i < 4 || sh.overlay == 6 ? i : i + 1];      // VoiceDesign has no speaker position
+        ++p;
+    }
+    if (p + sh.n_icl < sh.prefill_len) { tr[p] = row_base + sh.r_text; ci[p] = CODEC_BOS; ++p; }      // the first text token (not ICL)
+    const int n_text_all = sh.r_eos + 1 - sh.r_text;      // [ref_text, text, tts_eos]
+    for (int i = 0; i < sh.n_icl; ++i) {      // ICL block: text (or tts_pad) row + codec_bos / Σ16 reference-frame embeddings
+        tr[p] = row_base + (i < n_text_all ? sh.r_text + i : sh.r_pad);
+        ci[p] = i == 0 ? CODEC_BOS : -3 - (i - 1);
+        ++p;
+    }
 }
 // worst-case cost of a row against the model's KV budget (KvBudget units): every page prompt + limit + 1 positions can reach; a
 // bf16 row holds f32 pages for its prompt and, while they are converted, bf16 pages beside them
@@ -449,18 +485,17 @@ q3_request idle_request(int chunk_frames) {
 static q3_status session_create_any(q3_model* m, const q3_request* reqs, int batch, int frame_budget, int prompt_budget, q3_session** out) {
     if (!m || !reqs || !out) return set_err(Q3_INVALID_ARG, "q3_session_create: null argument");
     if (batch < 1 || batch > Q3_MAX_BATCH) return set_err(Q3_UNSUPPORTED, "batch %d unsupported (1..%d sequences per session)", batch, Q3_MAX_BATCH);
-    bool ragged = false; int S0 = 0, L0 = 0, Smax = 0, Lmax = 0, rows_max = 0;
+    bool ragged = false; int S0 = 0, Smax = 0, Lmax = 0, rows_max = 0;
     for (int b = 0; b < batch; ++b) {
         const q3_request& r = reqs[b];
         if (r.n_text < 0 || r.n_instruct < 0 || r.n_ref < 0 || r.n_ref_text < 0) return set_err(Q3_INVALID_ARG, "bad token id arrays");
-        int S = 0, L = 0; request_shape(r, &S, &L);
-        if (b == 0) { S0 = S; L0 = L; }
-        ragged = ragged || S != S0;
-        Smax = std::max(Smax, S); Lmax = std::max(Lmax, L);
-        rows_max = std::max(rows_max, (r.mode == Q3_MODE_VOICE_DESIGN ? r.n_instruct : 0) + 5 + r.n_ref_text + r.n_text + 1);
+        const PromptShape sh = prompt_shape(r);
+        if (b == 0) S0 = sh.prefill_len;
+        ragged = ragged || sh.prefill_len != S0;
+        Smax = std::max(Smax, sh.prefill_len); Lmax = std::max(Lmax, sh.limit);
+        rows_max = std::max(rows_max, sh.n_rows);
         if (r.opts.chunk_frames != reqs[0].opts.chunk_frames) return set_err(Q3_UNSUPPORTED, "all requests of a batch must share chunk_frames (the streaming chunk is a property of the session)");
     }
-    (void)L0;
     if (!ragged) return session_create(m, reqs, batch, frame_budget, prompt_budget, out);
     if (Lmax < 1) return set_err(Q3_INVALID_ARG, "max_length must be >= 1");
     const int fb = std::max(frame_budget, Lmax);
@@ -497,7 +532,6 @@ q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int fra
     int rows = 0;
     for (int b = 0; b < batch; ++b) {
         const q3_request& r = reqs[b];
-        const bool icl_req = r.mode == Q3_MODE_VOICE_CLONE && r.n_ref > 0 && r.ref_codes && r.ref_text_ids;
         if (r.opts.chunk_frames != s->opts.chunk_frames) return set_err(Q3_UNSUPPORTED, "all requests of a batch must share chunk_frames (the streaming chunk is a property of the session)");
         if (!(r.opts.temperature >= 0.0) || r.opts.repetition_penalty <= 0.0) return set_err(Q3_INVALID_ARG, "bad sampling options");
         if (r.mode < 0 || r.mode > 2) return set_err(Q3_INVALID_ARG, "bad mode %d", r.mode);
@@ -513,7 +547,8 @@ q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int fra
         if (r.language_id >= (uint32_t)c.codec_vocab || (r.mode == Q3_MODE_CUSTOM_VOICE && r.speaker_id >= (uint32_t)c.codec_vocab))
             return set_err(Q3_INVALID_ARG, "speaker/language id out of range");
         if (r.xvector) q.xvec.assign(r.xvector, r.xvector + c.hidden);
-        q.icl = r.mode == Q3_MODE_VOICE_CLONE && r.n_ref > 0 && r.ref_codes && r.ref_text_ids;
+        const PromptShape sh = prompt_shape(r);      // (arithmetic alone; a negative n_ref_text is refused below, before the shape sizes anything)
+        q.icl = sh.icl;
         if (r.mode == Q3_MODE_VOICE_CLONE && r.n_ref > 0 && r.ref_codes) {
             // reference frames are prepended at decode whenever the prompt carries them — also without a reference
             // transcript, when the prefill stays x-vector-only (lib.rs:1022: `if let Some(ref_codes) = &prompt.ref_codes`)
@@ -529,18 +564,11 @@ q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int fra
             for (uint32_t id : q.ref_text) if (id >= (uint32_t)c.text_vocab) return set_err(Q3_INVALID_ARG, "reference text id %u out of range", id);
             // lib.rs:913-929 (must be identical for every sequence of the batch, checked below through s->opts)
             q.req.opts.repetition_penalty = r.opts.repetition_penalty < 1.5 ? 1.5 : r.opts.repetition_penalty;
-            int cap = 6 * r.n_text; if (cap < 75) cap = 75;
-            if (q.req.opts.max_length > cap) q.req.opts.max_length = cap;
+            q.req.opts.max_length = sh.limit;
             if (b == 0) s->opts = q.req.opts;
         }
-        const int n_ins = (int)q.instruct.size();
-        const int overlay = r.mode == Q3_MODE_VOICE_DESIGN ? 5 : 6;
-        const int n_icl = q.icl ? r.n_ref + 1 : 0;                              // streaming overlay: icl_len = n_codec
-        const int n_text_all = q.icl ? r.n_ref_text + r.n_text + 1 : 0;         // [ref_text, text, tts_eos]
-        q.prefill_len = n_ins + 3 + overlay + ((r.n_text > 0 && !q.icl) ? 1 : 0) + n_icl;
-        q.trailing_len = q.icl ? (n_text_all > n_icl ? n_text_all - n_icl : 1) : (r.n_text > 1 ? r.n_text - 1 : 0) + 1;
-        q.row_base = rows;
-        q.n_rows = n_ins + 5 + (q.icl ? r.n_ref_text : 0) + r.n_text + 1;     // instruct, role×3, pad, bos, [ref_text…], text…, eos
+        q.prefill_len = sh.prefill_len; q.trailing_len = sh.trailing_len;
+        q.row_base = rows; q.n_rows = sh.n_rows;
         rows += q.n_rows;
         if (q.prefill_len != s->seq[0].prefill_len)
             return set_err(Q3_UNSUPPORTED, "all sequences of a batch must have the same prefill length (%d vs %d)", q.prefill_len, s->seq[0].prefill_len);
@@ -752,8 +780,7 @@ extern "C" q3_status q3_session_stream(q3_session* s, void** stream) {
 extern "C" q3_status q3_session_prefill_len(q3_session* s, int b, int* prefill_len, int* trailing_len) {
     if (!s || b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "bad sequence index");
     if (!s->ragged.empty()) {                    // a ragged batch before its prefill: the rows are still idle placeholders
-        int S = 0, L = 0; request_shape(s->ragged[(size_t)b].r, &S, &L);
-        if (prefill_len) *prefill_len = S;
+        if (prefill_len) *prefill_len = prompt_shape(s->ragged[(size_t)b].r).prefill_len;
         if (trailing_len) *trailing_len = -1;
         return Q3_OK;
     }
@@ -799,29 +826,21 @@ static q3_status text_project(q3_session* s, const uint32_t* ids_dev, int n, flo
 // An opened row's trailing text rows live in its replacement slot (rows repl_base + b * row_cap ..), contiguous as k_frame_embed
 // indexes them; frame f of the row may commit only once trailing row f is there (text_ready[b] > f), else the row is HELD.
 static int slot_row0(const q3_session* s, int b) { return s->repl_base + b * s->row_cap; }
-// trailing text ids of an opened row so far: its text minus what the prefill consumes (text[0]; ICL: the first n_ref + 1 of
-// [ref_text, text], talker.rs:656-708), without tts_eos
+// trailing text rows of an opened row so far, without tts_eos: its text minus what the prefill consumes
+static int open_n_trail(const SeqInfo& q) { return prompt_shape(q.request(), (int)q.text_all.size()).n_trail; }
+// ... and their ids: the tail of [ref_text (ICL rows alone hold one), text]
 static void open_trailing_ids(const SeqInfo& q, std::vector<uint32_t>& out) {
-    out.clear();
-    if (q.icl) {
-        const size_t n_icl = q.ref_codes.size() / 16 + 1;
-        std::vector<uint32_t> all(q.ref_text);
-        all.insert(all.end(), q.text_all.begin(), q.text_all.end());
-        if (all.size() > n_icl) out.assign(all.begin() + (ptrdiff_t)n_icl, all.end());
-    } else if (q.text_all.size() > 1) {
-        out.assign(q.text_all.begin() + 1, q.text_all.end());
-    }
+    std::vector<uint32_t> all(q.ref_text);
+    all.insert(all.end(), q.text_all.begin(), q.text_all.end());
+    out.assign(all.end() - open_n_trail(q), all.end());
 }
 // host view of an opened row's text: trailing rows present, what the frame reads (+ tts_eos once closed), frames allowed
 static void open_counts(SeqInfo& q) {
-    std::vector<uint32_t> t; open_trailing_ids(q, t);
-    q.n_trail = (int)t.size();
+    q.n_trail = open_n_trail(q);
     q.trailing_len = q.n_trail + (q.text_closed ? 1 : 0);
     q.ready = q.text_closed ? 0x7fffffff : q.n_trail;
-    if (q.icl && q.text_closed) {       // the ICL length cap (lib.rs:913-929) over the whole text, resolved at close
-        int cap = 6 * (int)q.text_all.size(); if (cap < 75) cap = 75;
-        q.limit = q.max_length_req < cap ? q.max_length_req : cap;
-    }
+    // the ICL length cap over the whole text, resolved at close against the request's own max_length
+    if (q.icl && q.text_closed) q.limit = std::min(q.max_length_req, icl_frame_cap((int)q.text_all.size()));
 }
 // Appended text rows take ONE projection path whatever a call carries: 8-row GEMV groups, the unused rows of the last group
 // padded in scratch. (text_project picks two GEMMs from 48 rows on, and at 1.7B the two sum in different orders: a token's bits
@@ -893,7 +912,7 @@ extern "C" q3_status q3_session_open_text(q3_session* s, int b) {
     if (q.opened) return Q3_OK;
     if (q.text.empty()) return set_err(Q3_INVALID_ARG, "q3_session_open_text: row %d has no text token (an open row needs one at creation: the prefill consumes it)", b);
     if (q.icl) {
-        const int n_ref = (int)(q.ref_codes.size() / 16), need = n_ref + 1 - (int)q.ref_text.size();
+        const int need = prompt_shape(q.request()).open_need;
         if ((int)q.text.size() < need)
             return set_err(Q3_INVALID_ARG, "q3_session_open_text: ICL row %d needs at least %d target text tokens at creation (%d given), so that tts_eos falls after the ICL block", b, need, (int)q.text.size());
         if (q.max_length_req > s->max_frames)
@@ -1106,10 +1125,10 @@ static bool prefill_cut(const q3_session* s, int S, int* Sg) {
 static int prefill_step_chunk(const q3_session* s) { return s->no_chunk ? 1 : (16 / s->B > 0 ? 16 / s->B : 1); }
 
 // ---- prefix cache (q3_prefix_cache.h): what a session asks of it ----
-// Eligible: the instruct positions of a VoiceDesign row, in whole pages — the only prompt positions whose input is a pure
-// function of the cache key. Never for debug / profile / no_chunk sessions or contiguous K/V.
+// Eligible (PromptShape::prefix_pages): the instruct positions of a VoiceDesign row, in whole pages — the only prompt positions
+// whose input is a pure function of the cache key. Never for debug / profile / no_chunk sessions or contiguous K/V.
 static bool prefix_session_ok(const q3_session* s) { return prefix_on(s->m) && s->paged && !s->debug && !s->profile && !s->no_chunk; }
-static int prefix_eligible_pages(const SeqInfo& q) { return q.req.mode == Q3_MODE_VOICE_DESIGN ? (int)q.instruct.size() / KV_PAGE_POS : 0; }
+static int prefix_eligible_pages(const SeqInfo& q) { return prompt_shape(q.request()).prefix_pages; }
 // The regime of this session's prefill: everything besides the token ids that decides the BITS of a cached position.
 //   GEMM path: which attention kernel the prompt length selects (below 256 positions / bf16x3 / bf16x3 with key halves). With
 //   key halves a query block's half boundary comes from the block's last position. At GQA ratio 2 a block is 128 rows = one
@@ -1195,16 +1214,7 @@ static int prefix_link(q3_session* s, q3_status* st) {
 static void prefix_regroup(q3_session* s) {
     s->regrouped = true;      // transplant_row also brings each row's prompt embeddings (Q3_GET_PREFILL_EMBEDS stays valid)
     s->ragged.resize((size_t)s->B);
-    for (int b = 0; b < s->B; ++b) {
-        const SeqInfo& q = s->seq[(size_t)b];
-        q3_request r = q.req;
-        r.text_ids = q.text.data(); r.n_text = (int32_t)q.text.size();
-        r.instruct_ids = q.instruct.empty() ? nullptr : q.instruct.data(); r.n_instruct = (int32_t)q.instruct.size();
-        r.ref_codes = q.ref_codes.empty() ? nullptr : q.ref_codes.data(); r.n_ref = (int32_t)(q.ref_codes.size() / 16);
-        r.ref_text_ids = q.ref_text.empty() ? nullptr : q.ref_text.data(); r.n_ref_text = (int32_t)q.ref_text.size();
-        r.xvector = q.xvec.empty() ? nullptr : q.xvec.data();
-        s->ragged[(size_t)b].own(r, s->m->cfg.hidden);
-    }
+    for (int b = 0; b < s->B; ++b) s->ragged[(size_t)b].own(s->seq[(size_t)b].request(), s->m->cfg.hidden);
 }
 
 // q3_session_prefill of a ragged first batch (session_create_any): the idle rows never run — every row's state comes from a side
@@ -1221,35 +1231,29 @@ static q3_status prefill_ragged(q3_session* s) {
     // The plan takes the regime and the rounding of a one-row group (the width of a group is not known before the groups are);
     // where those depend on the width — the decode-step path, several chunks at ratio 1 — a group may link less than planned:
     // its side session links what its shortest chain allows (prefix_common), which keeps the bits right and only costs hits.
+    std::vector<PromptShape> shape((size_t)B);
+    for (int b = 0; b < B; ++b) shape[(size_t)b] = prompt_shape(s->ragged[(size_t)b].r);
     if (prefix_session_ok(s))
         for (int b = 0; b < B; ++b) {
             const q3_request& r = s->ragged[(size_t)b].r;
-            const int el = r.mode == Q3_MODE_VOICE_DESIGN ? r.n_instruct / KV_PAGE_POS : 0;
-            int S = 0, Lb = 0; request_shape(r, &S, &Lb);
+            const int el = shape[(size_t)b].prefix_pages, S = shape[(size_t)b].prefill_len;
             if (el > 0) hit[(size_t)b] = prefix_usable_pages_of(s->m, 1, S, prefix_peek(s->m, prefix_regime_of(s->m, 1, S, s->n_splits), r.instruct_ids, el));
         }
     for (int b0 = 0; b0 < B; ++b0) {
         if (placed[(size_t)b0]) continue;
-        int S0 = 0, L = 0; request_shape(s->ragged[(size_t)b0].r, &S0, &L);
         std::vector<int> rows; std::vector<q3_request> reqs; std::vector<int> limits;
         for (int b = b0; b < B; ++b) {
-            int S = 0, Lb = 0; request_shape(s->ragged[(size_t)b].r, &S, &Lb);
-            if (placed[(size_t)b] || S != S0 || hit[(size_t)b] != hit[(size_t)b0]) continue;
-            q3_request r = s->ragged[(size_t)b].r;
-            // the row's RESOLVED limit (an ICL row's max_length is capped at max(75, 6 * n_text), talker.rs:646-710 / lib.rs:897-1046) is
-            // what session_create_any sized max_frames for — the raw max_length of an ICL row may well exceed it
+            if (placed[(size_t)b] || shape[(size_t)b].prefill_len != shape[(size_t)b0].prefill_len || hit[(size_t)b] != hit[(size_t)b0]) continue;
+            const q3_request& r = s->ragged[(size_t)b].r;
+            // the row's RESOLVED limit (PromptShape::limit: under the ICL cap) is what session_create_any sized max_frames for — the
+            // raw max_length of an ICL row may well exceed it
+            const int Lb = shape[(size_t)b].limit;
             if (r.opts.max_length < 1 || Lb < 1 || Lb > s->max_frames) { s->prefilled = false; return set_err(Q3_INVALID_ARG, "row %d: max_length %d (resolved %d) outside 1..%d", b, r.opts.max_length, Lb, s->max_frames); }
             limits.push_back(Lb);
-            r.opts.max_length = s->max_frames;           // the side session draws the row's PCG stream with the host session's stride
             rows.push_back(b); reqs.push_back(r); placed[(size_t)b] = 1;
         }
-        q3_session* side_raw = nullptr;
-        q3_status st = session_create(s->m, reqs.data(), (int)reqs.size(), 0, 0, &side_raw, s->stream);
-        std::unique_ptr<q3_session> side(side_raw);
-        if (st == Q3_OK) { side->kv_bf16 = s->kv_bf16; side->prefix_common = true; }
-        std::vector<int> lim(rows.size(), 0);
-        for (size_t j = 0; j < rows.size() && st == Q3_OK; ++j) st = transplant_check(s, side.get(), (int)j, limits[j], &lim[j]);
-        if (st == Q3_OK) st = q3_session_prefill(side.get());
+        std::unique_ptr<q3_session> side; std::vector<int> lim(rows.size(), 0);
+        q3_status st = side_prefill(s, reqs.data(), limits.data(), (int)reqs.size(), false, false, true, s->stream, &side, lim.data());
         if (st == Q3_OK && sync_frames(s) != hipSuccess) st = set_err(Q3_HIP_ERROR, "ragged prefill: stream");
         for (size_t j = 0; j < rows.size() && st == Q3_OK; ++j) st = transplant_row(s, rows[j], side.get(), (int)j, lim[j]);
         if (st != Q3_OK) { s->prefilled = false; return st; }
@@ -1291,41 +1295,18 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
     std::vector<float> xv((size_t)B * H, 0.0f);
     for (int b = 0; b < B; ++b) {
         SeqInfo& q = s->seq[b];
-        const int n_ins = (int)q.instruct.size(), n_text = (int)q.text.size(), base = q.row_base;
         for (uint32_t id : q.instruct) ids.push_back(id);
         ids.push_back(IM_START); ids.push_back(ASSISTANT); ids.push_back(NEWLINE); ids.push_back(TTS_PAD); ids.push_back(TTS_BOS);
-        if (q.icl) for (uint32_t id : q.ref_text) ids.push_back(id);       // ICL: [ref_text, target_text, tts_eos] (talker.rs:656-663)
+        for (uint32_t id : q.ref_text) ids.push_back(id);      // (ICL rows alone hold one)
         for (uint32_t id : q.text) ids.push_back(id);
         ids.push_back(TTS_EOS);
-        const int n_ref_text = q.icl ? (int)q.ref_text.size() : 0;
-        const int r_role = base + n_ins, r_pad = r_role + 3, r_bos = r_pad + 1, r_text = r_bos + 1, r_eos = r_text + n_ref_text + n_text;
-        const int n_icl = q.icl ? (int)(q.ref_codes.size() / 16) + 1 : 0, n_text_all = n_ref_text + n_text + 1;
-        q.pad_row = r_pad;
-        if (q.icl) q.trail_base = n_text_all > n_icl ? r_text + n_icl : r_pad;       // talker.rs:692-708
-        else q.trail_base = n_text > 1 ? r_text + 1 : r_eos;          // build_trailing_text (lib.rs:508-519)
+        const q3_request r = q.request();
+        const PromptShape sh = prompt_shape(r);
+        if (sh.prefill_len != S) return set_err(Q3_INVALID_ARG, "prefill: row %d has %d positions, the session %d", b, sh.prefill_len, S);
+        q.pad_row = q.row_base + sh.r_pad; q.trail_base = q.row_base + sh.trail_base;
         if (q.opened) { q.trail_base = slot_row0(s, b); open_counts(q); }      // open text: trailing rows in the row's slot (below)
         trail_base[b] = q.trail_base; trail_len[b] = q.trailing_len; pad_row[b] = q.pad_row;
-        // prefill positions (talker.rs:451-491 / 511-564 / 585-627)
-        int* tr = &text_row[(size_t)b * S]; int* ci = &codec_id[(size_t)b * S];
-        int p = 0;
-        for (int i = 0; i < n_ins; ++i) tr[p++] = base + i;
-        for (int i = 0; i < 3; ++i) tr[p++] = r_role + i;
-        const bool vd = q.req.mode == Q3_MODE_VOICE_DESIGN;
-        int codec[7]; int nc;
-        if (vd) { int t[6] = {CODEC_THINK, CODEC_THINK_BOS, (int)q.req.language_id, CODEC_THINK_EOS, CODEC_PAD, CODEC_BOS}; memcpy(codec, t, sizeof t); nc = 6; }
-        else { int t[7] = {CODEC_THINK, CODEC_THINK_BOS, (int)q.req.language_id, CODEC_THINK_EOS, (int)q.req.speaker_id, CODEC_PAD, CODEC_BOS}; memcpy(codec, t, sizeof t); nc = 7; }
-        const int overlay = nc - 1;
-        for (int i = 0; i < overlay; ++i) {
-            tr[p] = (i == overlay - 1) ? r_bos : r_pad;
-            ci[p] = (q.req.mode == Q3_MODE_VOICE_CLONE && i == 4) ? -2 : codec[i];
-            ++p;
-        }
-        if (n_text > 0 && !q.icl) { tr[p] = r_text; ci[p] = codec[nc - 1]; ++p; }
-        for (int i = 0; i < n_icl; ++i) {      // ICL block: text (or tts_pad) row + codec_bos / Σ16 reference-frame embeddings
-            tr[p] = i < n_text_all ? r_text + i : r_pad;
-            ci[p] = i == 0 ? CODEC_BOS : -3 - (i - 1);
-            ++p;
-        }
+        prompt_positions(sh, r, q.row_base, &text_row[(size_t)b * S], &codec_id[(size_t)b * S]);
         if (!q.xvec.empty()) memcpy(&xv[(size_t)b * H], q.xvec.data(), (size_t)H * 4);
     }
     uint32_t* ids_dev = s->ids_dev; int *tr_dev = s->tr_dev, *ci_dev = s->ci_dev;

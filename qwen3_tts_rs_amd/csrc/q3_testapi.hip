@@ -1374,6 +1374,18 @@ extern "C" q3_status q3_sample_row(const q3_options* o, q3_sample_rec* out) {
     return Q3_OK;
 }
 
+extern "C" q3_status q3_prompt_shape(const q3_request* r, int n_text, q3_prompt_shape_rec* out, int* text_row, int* codec_id, int cap_positions) {
+    if (!r || !out) return set_err(Q3_INVALID_ARG, "q3_prompt_shape: null argument");
+    if (n_text < 0 || r->n_instruct < 0 || r->n_ref < 0 || r->n_ref_text < 0) return set_err(Q3_INVALID_ARG, "q3_prompt_shape: negative length");
+    if ((long long)n_text + r->n_instruct + r->n_ref + r->n_ref_text > (1 << 28)) return set_err(Q3_INVALID_ARG, "q3_prompt_shape: lengths beyond 2^28");
+    *out = prompt_shape(*r, n_text);
+    if (!text_row && !codec_id) return Q3_OK;
+    if (!text_row || !codec_id) return set_err(Q3_INVALID_ARG, "q3_prompt_shape: one table without the other");
+    if (cap_positions < out->prefill_len) return set_err(Q3_INVALID_ARG, "q3_prompt_shape: tables of %d positions, the prompt has %d", cap_positions, out->prefill_len);
+    prompt_positions(*out, *r, 0, text_row, codec_id);
+    return Q3_OK;
+}
+
 extern "C" q3_status q3_sample_ex(int device, const q3_sample_ex_args* p) {
     if (!p || !p->logits || !p->u || !p->tok) return set_err(Q3_INVALID_ARG, "q3_sample_ex: null argument");
     const int B = p->B, V = p->vocab, G = p->guard;

@@ -216,9 +216,10 @@ class OracleSession:
             r.xvector = self._x.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
         if getattr(utt, "ref_codes", None) is not None:
             self._rc = np.ascontiguousarray(utt.ref_codes, dtype=np.uint32).reshape(-1, 16)
-            self._rt = np.ascontiguousarray(utt.ref_text_ids, dtype=np.uint32)
             r.ref_codes = self._rc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)); r.n_ref = self._rc.shape[0]
-            r.ref_text_ids = self._rt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)); r.n_ref_text = len(self._rt)
+            if utt.ref_text_ids is not None:                    # (without a transcript the prompt is not ICL)
+                self._rt = np.ascontiguousarray(utt.ref_text_ids, dtype=np.uint32)
+                r.ref_text_ids = self._rt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)); r.n_ref_text = len(self._rt)
         o = to_ooptions(options)
         if utt.seed is not None:
             o.seed = int(utt.seed); o.has_seed = 1

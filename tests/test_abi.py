@@ -296,6 +296,7 @@ def test_null_handles_return_status_not_crash():
         lambda: L.q3_rvq_embed_ex(0, None, 1, None, None, 8, 16, None, None, 0, 8),
         lambda: L.q3_silu_mul_ex(0, None, None, None, 8, 8),
         lambda: L.q3_sample_row(None, None),
+        lambda: L.q3_prompt_shape(None, 0, None, None, None, 0),
         lambda: L.q3_sample_ex(0, None),
         lambda: L.q3_sample_ex(0, ctypes.byref(_lib.CSampleEx())),
         lambda: L.q3_frame_embed_ex(0, None),

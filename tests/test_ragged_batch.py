@@ -137,3 +137,18 @@ def test_ragged_icl_rows_above_their_cap(pair):
         s1 = gm.session([u], o); s1.prefill(); s1.generate(12, use_graph=False)
         assert got[b].shape == (12, 16) and caps[b] >= 12
         np.testing.assert_array_equal(got[b], s1.codes(0), err_msg=f"row {b} vs its batch-1 run"); s1.close()
+
+
+def test_prefill_len_is_the_prompt_shape(pair):
+    """what a session reports for its rows — as idle placeholders of a ragged batch, and as the rows it really built — is what the
+    host-only q3_prompt_shape says of their requests"""
+    cfg, gm, om = pair
+    utts = _mixed(cfg)
+    host = q.SynthesisOptions(max_length=20, eos_token_id=None, seed=1)
+    shapes = [api.prompt_shape(u, host) for u in utts]
+    s = gm.session(utts, host)
+    assert [s.prefill_len(b) for b in range(len(utts))] == [(r.prefill_len, -1) for r in shapes]
+    s.prefill()
+    assert [s.prefill_len(b) for b in range(len(utts))] == [(r.prefill_len, r.trailing_len) for r in shapes]
+    s.close()
+    assert gm.kv_pool_info()["pages_in_use"] == 0
