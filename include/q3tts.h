@@ -676,6 +676,41 @@ q3_status q3_rvq_embed_ex(int device, const uint32_t* frames, int n_frames, cons
                           float* first_out, float* rest_out, int out_front, int out_elems);
 /* Test API: launch_silu_mul: y[i] = silu(g[i]) * u[i], i < n; y: host buffer of y_elems >= n floats, uploaded and copied back whole. */
 q3_status q3_silu_mul_ex(int device, const float* g, const float* u, float* y, long long n, long long y_elems);
+/* Test API: the voice-clone encoders' own kernels, ONE launch each over host arrays (tests/test_gpu_clone_ops.py). Everything a kernel
+ * would address is checked against the host buffers before the device is touched: a bad shape is Q3_INVALID_ARG, never a launch.
+ * `out` is a host buffer of out_elems floats with the result at out_front; it is uploaded whole and copied back whole.
+ * q3_spk_op_ex, by op (a / b / result):
+ *   0 PAD (launch_spk_pad): a [C][T], b NULL or [C][T] -> [C][Tp] = reflect-padded a (+ b), pl columns on the left, Tp - T - pl on
+ *     the right; 0 <= pl <= T - 1, 0 <= Tp - T - pl <= T - 1.
+ *   1 COLS (launch_spk_cols): a [C][ld] -> [C][T] = a[c][off + t]; 0 <= off, off + T <= ld.
+ *   2 MEAN (launch_spk_mean): a [C][T] -> [C].
+ *   3 SE_APPLY (launch_spk_se_apply): a = o [C][T], b = g [C], the result region holds h [C][T] going in: h = o * g[c] + h.
+ *   4 ASP_IN (launch_spk_asp_in): a [C][T] -> [3C][T] = [a ; mean ; sqrt(var + 1e-5)].
+ *   5 ASP_POOL (launch_spk_asp_pool): a = logits [C][T], b = m [C][T] -> [2C] = softmax-weighted [mean ; sqrt(var + 1e-5)] of m.
+ * a_elems / b_elems: floats behind a / b (b_elems 0 with b NULL). C 1..65535, T, Tp, ld 1..2^20. */
+typedef struct q3_spk_op_ex_args {
+    int op, C, T, pl, Tp, ld, off, reserved;
+    long long a_elems, b_elems, out_front, out_elems;
+    const float* a; const float* b; float* out;
+} q3_spk_op_ex_args;
+q3_status q3_spk_op_ex(int device, const q3_spk_op_ex_args* args);
+/* q3_mimi_op_ex, by op:
+ *   0 ELU (launch_mimi_elu): a [L] -> [L] (C, r, Lf unused).
+ *   1 FOLD (launch_mimi_fold): a [C][L] -> [C*r][Lf + lead]; replicate == 0: lead 0, zeros beyond L, (Lf - 1) * r < L; replicate != 0:
+ *     lead 1, column 0 = a[c][0], a[c][L - 1] beyond L. elu != 0: ELU on the way. r 1..64, C * r <= 65535.
+ *   2 CODEBOOK (launch_mimi_codebook): a = embed_sum [C][L], b = cluster_usage [C] -> [C][L] = a / max(b, 1e-5) (C entries of L floats).
+ * L, Lf 1..2^24. */
+typedef struct q3_mimi_op_ex_args {
+    int op, C, L, r, Lf, elu, replicate, reserved;
+    long long a_elems, b_elems, out_front, out_elems;
+    const float* a; const float* b; float* out;
+} q3_mimi_op_ex_args;
+q3_status q3_mimi_op_ex(int device, const q3_mimi_op_ex_args* args);
+/* q3_mimi_rvq_ex (launch_mimi_rvq): proj [CD][T], books [n_layers][CB][CD]; codes [T][n_q] u32 is uploaded whole and copied back
+ * whole: columns q0 .. q0 + n_layers - 1 of every frame are written, the rest keep what they held. 1 <= CD <= 256, CB 1..65536,
+ * T 1..65536, n_layers >= 1, q0 >= 0, q0 + n_layers <= n_q <= 64. */
+q3_status q3_mimi_rvq_ex(int device, const float* proj, int T, const float* books, int n_layers, int CB, int CD, uint32_t* codes, int n_q,
+                         int q0);
 /* Test API: the sampler and the frame-seam kernels in the forms a session launches them, ONE launch each over host arrays (op-level
  * tests). Arguments are checked before any device call: a null pointer, a token / code / row index that would make the kernel read
  * outside a table, a draw outside `u`, a sampler vocab outside 2..4096 are Q3_INVALID_ARG. Every buffer a kernel may write holds
@@ -1165,6 +1200,9 @@ q3_status q3_spk_load_safetensors(q3_speaker_encoder* e, const char* path);
 int q3_spk_mel_frames(int64_t n_samples);
 /* MelSpectrogram::compute_for_speaker_encoder (mel.rs:135-166): mel_host [mel_dim][T], T = q3_spk_mel_frames(n) */
 q3_status q3_spk_mel(q3_speaker_encoder* e, const float* samples_host, int64_t n, float* mel_host, int64_t cap_floats, int* n_frames);
+/* Test API: the front-end tables of a finalized encoder as its mel kernel reads them, copied back from the device: the periodic Hann
+ * window win_host [1024] and the Slaney filterbank fb_host [mel_dim][513] */
+q3_status q3_spk_tables(q3_speaker_encoder* e, float* win_host, float* fb_host);
 /* SpeakerEncoder::forward (speaker.rs:443-469) for one mel [mel_dim][T]; taps (test hook): NULL or 6 host pointers
  * (NULL entries skipped): blocks.0 out, the three SE-Res2Net outs [C][T], MFA out [C4][T], pooled [2*C4] */
 q3_status q3_spk_forward(q3_speaker_encoder* e, const float* mel_host, int T, float* out_host, float** taps_host);

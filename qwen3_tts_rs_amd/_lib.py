@@ -99,6 +99,18 @@ class CAttnCEx(ctypes.Structure):        # q3_attn_c_ex_args
                [(n, ctypes.c_void_p) for n in ("q", "k", "v", "rows", "caches", "tabs", "tab0", "tab_n", "o")]
 
 
+class CSpkOpEx(ctypes.Structure):        # q3_spk_op_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("op", "C", "T", "pl", "Tp", "ld", "off", "reserved")] + \
+               [(n, ctypes.c_longlong) for n in ("a_elems", "b_elems", "out_front", "out_elems")] + \
+               [(n, ctypes.c_void_p) for n in ("a", "b", "out")]
+
+
+class CMimiOpEx(ctypes.Structure):       # q3_mimi_op_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("op", "C", "L", "r", "Lf", "elu", "replicate", "reserved")] + \
+               [(n, ctypes.c_longlong) for n in ("a_elems", "b_elems", "out_front", "out_elems")] + \
+               [(n, ctypes.c_void_p) for n in ("a", "b", "out")]
+
+
 class CSampleRow(ctypes.Structure):      # q3_sample_rec (the sampler's per-row record)
     _fields_ = [("inv_temp", ctypes.c_float), ("apply_temp", ctypes.c_int32), ("greedy", ctypes.c_int32), ("top_k", ctypes.c_int32),
                 ("top_p", ctypes.c_float), ("use_top_p", ctypes.c_int32), ("rep_pen", ctypes.c_float), ("rep_inv", ctypes.c_float),
@@ -297,6 +309,10 @@ SYMBOLS = {
     "q3_gather_frames_ex": (c_int, [c_int, c_void_p, ctypes.c_size_t, c_void_p, c_int, c_void_p, ctypes.c_size_t]),
     "q3_rvq_embed_ex": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int]),
     "q3_silu_mul_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong]),
+    "q3_spk_op_ex": (c_int, [c_int, P(CSpkOpEx)]),
+    "q3_mimi_op_ex": (c_int, [c_int, P(CMimiOpEx)]),
+    "q3_mimi_rvq_ex": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int]),
+    "q3_spk_tables": (c_int, [c_void_p, c_void_p, c_void_p]),
     "q3_sample_row": (c_int, [P(COptions), P(CSampleRow)]),
     "q3_prompt_shape": (c_int, [P(CRequest), c_int, P(CPromptShape), c_void_p, c_void_p, c_int]),
     "q3_sample_ex": (c_int, [c_int, P(CSampleEx)]),

@@ -2265,6 +2265,50 @@ def silu_mul_ex(g: np.ndarray, u: np.ndarray, y: np.ndarray, device: int = 0) ->
     return y
 
 
+SPK_PAD, SPK_COLS, SPK_MEAN, SPK_SE_APPLY, SPK_ASP_IN, SPK_ASP_POOL = range(6)      # ops of q3_spk_op_ex
+MIMI_ELU, MIMI_FOLD, MIMI_CODEBOOK = range(3)                                       # ops of q3_mimi_op_ex
+
+
+def _clone_op(args, call, a, b, out, out_front, device):
+    aa = np.ascontiguousarray(a, dtype=np.float32)
+    bb = None if b is None else np.ascontiguousarray(b, dtype=np.float32)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.ndim == 1
+    args.a_elems, args.b_elems, args.out_front, args.out_elems = aa.size, 0 if bb is None else bb.size, out_front, out.size
+    args.a, args.b, args.out = _vp(aa), _vp(bb), _vp(out)
+    check(call(device, ctypes.byref(args)))
+    return out
+
+
+def spk_op_ex(op: int, a: np.ndarray, out: np.ndarray, *, C: int, T: int, b: Optional[np.ndarray] = None, pl: int = 0, Tp: int = 0, ld: int = 0,
+              off: int = 0, out_front: int = 0, device: int = 0) -> np.ndarray:
+    """q3_spk_op_ex: one launch of a speaker-encoder kernel (op = SPK_PAD: a [C][T] (+ b) -> [C][Tp] with pl columns on the left; SPK_COLS:
+    a [C][ld] -> [C][T] from column off; SPK_MEAN: a [C][T] -> [C]; SPK_SE_APPLY: a = o, b = g [C], out holds h; SPK_ASP_IN: a -> [3C][T];
+    SPK_ASP_POOL: a = logits, b = m -> [2C]). out: flat f32 with the result at out_front, uploaded, written in place and returned whole.
+    Raises Q3Error (status 1) for a shape the entry refuses."""
+    args = _lib.CSpkOpEx()
+    args.op, args.C, args.T, args.pl, args.Tp, args.ld, args.off = op, C, T, pl, Tp, ld, off
+    return _clone_op(args, lib.q3_spk_op_ex, a, b, out, out_front, device)
+
+
+def mimi_op_ex(op: int, a: np.ndarray, out: np.ndarray, *, L: int, C: int = 1, r: int = 1, Lf: int = 0, elu: bool = False, replicate: bool = False,
+               b: Optional[np.ndarray] = None, out_front: int = 0, device: int = 0) -> np.ndarray:
+    """q3_mimi_op_ex: one launch of a speech-encoder kernel (op = MIMI_ELU: a [L] -> [L]; MIMI_FOLD: a [C][L] -> [C*r][Lf (+ 1 in
+    replicate mode)]; MIMI_CODEBOOK: a = embed_sum [C][L], b = cluster_usage [C] -> [C][L]). out as in spk_op_ex."""
+    args = _lib.CMimiOpEx()
+    args.op, args.C, args.L, args.r, args.Lf, args.elu, args.replicate = op, C, L, r, Lf, int(elu), int(replicate)
+    return _clone_op(args, lib.q3_mimi_op_ex, a, b, out, out_front, device)
+
+
+def mimi_rvq_ex(proj: np.ndarray, books: np.ndarray, codes: np.ndarray, q0: int = 0, device: int = 0) -> np.ndarray:
+    """q3_mimi_rvq_ex: one launch_mimi_rvq; proj [CD][T], books [n_layers][CB][CD], codes [T][n_q] u32: columns q0 .. q0 + n_layers - 1
+    are written in place, the array is returned whole."""
+    pp = np.ascontiguousarray(proj, dtype=np.float32); bk = np.ascontiguousarray(books, dtype=np.float32)
+    assert pp.ndim == 2 and bk.ndim == 3 and bk.shape[2] == pp.shape[0]
+    assert codes.dtype == np.uint32 and codes.flags.c_contiguous and codes.ndim == 2 and codes.shape[0] == pp.shape[1]
+    check(lib.q3_mimi_rvq_ex(device, _vp(pp), pp.shape[1], _vp(bk), bk.shape[0], bk.shape[1], bk.shape[2], _vp(codes), codes.shape[1], q0))
+    return codes
+
+
 def resunit_path(C: int, L: int, dil: int, packed: bool = True, ya_is_xa: bool = False, planes: int = 3) -> int:
     """q3_resunit_path: launch_resunit's acceptance rule as a ConvPath code (0 = refused). No GPU needed."""
     return lib.q3_resunit_path(C, L, dil, int(packed), int(ya_is_xa), planes)

@@ -416,6 +416,25 @@ hipError_t launch_attn_c(const float* q, const float* k, const float* v, float* 
 // the speech encoder's causal sliding-window MHA over [nh*64][T]: keys j in (t - window, t] (q3_mimi.hip)
 hipError_t launch_mimi_attn(const float* q, const float* k, const float* v, float* o, int nh, int hd, int T, int window, float scale,
                             hipStream_t st);
+// the speech encoder's own small kernels (q3_mimi.hip); each refuses what its kernel could not address with hipErrorInvalidValue
+hipError_t launch_mimi_elu(const float* x, float* y, size_t n, hipStream_t st);                       // y = ELU(x), n >= 1
+// y [C*r][Lf + lead] from x [C][L]: plain mode (lead 0, zeros beyond L; (Lf - 1) * r < L) or replicate mode (lead 1 = x[c][0], x[c][L-1]
+// beyond L); elu != 0: ELU on the way
+hipError_t launch_mimi_fold(const float* x, float* y, int C, int L, int r, int Lf, int elu, int replicate, hipStream_t st);
+hipError_t launch_mimi_codebook(const float* esum, const float* usage, float* out, int CB, int dim, hipStream_t st);   // esum / max(usage, 1e-5)
+// proj [CD][T], books [n_layers][CB][CD] -> codes[t * n_q + q0 + l] (first minimum per layer); 1 <= CD <= 256, q0 + n_layers <= n_q
+hipError_t launch_mimi_rvq(const float* proj, int T, const float* books, int n_layers, int CB, int CD, uint32_t* codes, int n_q, int q0,
+                           hipStream_t st);
+// the speaker encoder's own kernels (q3_speaker.hip), refusing likewise. x: n >= 1 samples -> mel [n_mels][T] log-mel over the tables
+hipError_t launch_spk_stft_mel(const float* x, long n, int T, const float* win, const double* cs, const double* sn, const float* fb, float* mel,
+                               int n_mels, hipStream_t st);
+// out [C][Tp] = reflect-padded a [C][T] (+ b): pl on the left, Tp - T - pl on the right, neither more than T - 1
+hipError_t launch_spk_pad(const float* a, const float* b, float* out, int C, int T, int pl, int Tp, hipStream_t st);
+hipError_t launch_spk_cols(const float* src, int ld, int off, float* dst, int C, int T, hipStream_t st);   // dst [C][T] = src[c][off + t], off + T <= ld
+hipError_t launch_spk_mean(const float* x, float* mean, int C, int T, hipStream_t st);
+hipError_t launch_spk_se_apply(const float* o, const float* g, float* h, int C, int T, hipStream_t st);   // h = o * g[c] + h
+hipError_t launch_spk_asp_in(const float* m, float* ain, int C, int T, hipStream_t st);                   // ain [3C][T] = [m ; mean ; std]
+hipError_t launch_spk_asp_pool(const float* aw, const float* m, float* pooled, int C, int T, hipStream_t st);   // pooled [2C] = [mean ; std]
 // codec stream (q3_codec_stream.hip): the front over the new columns of several rows, K / V from per-row caches
 struct AttnCsRow { const float* kv; int a0, e, qcol; };      // row cache [layer][K | V][QD][cap]; new frames [a0, e) at columns qcol ..
 struct AttnCbRow { int tab0, a0, e, qcol; };                  // as AttnCsRow, the cache being the block list tabs[tab0 ..] (block-allocated stream)

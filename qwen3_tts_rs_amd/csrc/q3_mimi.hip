@@ -32,6 +32,11 @@ __global__ __launch_bounds__(256) void k_mimi_elu(const float* __restrict__ x, f
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) { const float v = x[i]; y[i] = v > 0.0f ? v : expf(v) - 1.0f; }
 }
+hipError_t launch_mimi_elu(const float* x, float* y, size_t n, hipStream_t st) {
+    if (n < 1 || (n + 255) / 256 > 0x7fffffffu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mimi_elu, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, n);
+    return hipGetLastError();
+}
 // fold r consecutive samples into channels: y[(c*r + p)][lead + tau] = f(x[c][tau*r + p]) (0 beyond L), f = ELU or identity.
 // lead = 1 (replicate mode): column 0 holds x[c][0] for every phase — the replicate left padding of the downsample conv —
 // and samples beyond L repeat x[c][L-1].
@@ -49,6 +54,15 @@ __global__ __launch_bounds__(256) void k_mimi_fold(const float* __restrict__ x, 
     }
     if (elu) v = v > 0.0f ? v : expf(v) - 1.0f;
     y[(size_t)cp * W + col] = v;
+}
+hipError_t launch_mimi_fold(const float* x, float* y, int C, int L, int r, int Lf, int elu, int replicate, hipStream_t st) {
+    if (C < 1 || r < 1 || L < 1 || Lf < 1 || (long long)C * r > 65535) return hipErrorInvalidValue;
+    // plain mode: the last column starts inside the signal (i = (Lf - 1) * r + p as an int); replicate mode clamps
+    if (!replicate && (long long)(Lf - 1) * r >= L) return hipErrorInvalidValue;
+    if ((long long)Lf * r > 0x7fffffffLL) return hipErrorInvalidValue;
+    const int W = Lf + (replicate ? 1 : 0);
+    hipLaunchKernelGGL(k_mimi_fold, dim3((W + 255) / 256, C * r), dim3(256), 0, st, x, y, L, r, Lf, elu, replicate);
+    return hipGetLastError();
 }
 // causal sliding-window MHA on [nh*64][T] tensors: one 64-lane wave per (query t, head h), keys j in (t - window, t]
 __global__ __launch_bounds__(64) void k_mimi_attn(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
@@ -93,6 +107,11 @@ __global__ __launch_bounds__(256) void k_mimi_codebook(const float* __restrict__
     const float u = fmaxf(usage[e], 1e-5f);
     for (int d = threadIdx.x; d < dim; d += 256) out[(size_t)e * dim + d] = esum[(size_t)e * dim + d] / u;
 }
+hipError_t launch_mimi_codebook(const float* esum, const float* usage, float* out, int CB, int dim, hipStream_t st) {
+    if (CB < 1 || dim < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mimi_codebook, dim3(CB), dim3(256), 0, st, esum, usage, out, dim);
+    return hipGetLastError();
+}
 // MimiResidualVectorQuantizer.encode for one group: proj [CD][T] (input_proj output), books = n_layers tables [CB][CD];
 // codes[t*n_q + q0 + l] = argmin_e |r - e|^2 (first minimum), r -= e. One workgroup per frame.
 __global__ __launch_bounds__(256) void k_mimi_rvq(const float* __restrict__ proj, int T, const float* __restrict__ books, int n_layers, int CB, int CD,
@@ -125,6 +144,13 @@ __global__ __launch_bounds__(256) void k_mimi_rvq(const float* __restrict__ proj
         if (tid < CD) r[tid] = sub_rn(r[tid], book[(size_t)win * CD + tid]);
         __syncthreads();
     }
+}
+hipError_t launch_mimi_rvq(const float* proj, int T, const float* books, int n_layers, int CB, int CD, uint32_t* codes, int n_q, int q0,
+                           hipStream_t st) {
+    // the residual lives in r[256]; a layer's column q0 + l must lie inside a frame's n_q codes
+    if (CD < 1 || CD > 256 || CB < 1 || n_layers < 1 || q0 < 0 || (long long)q0 + n_layers > n_q || T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mimi_rvq, dim3(T), dim3(256), 0, st, proj, T, books, n_layers, CB, CD, codes, n_q, q0);
+    return hipGetLastError();
 }
 
 }  // namespace q3
@@ -331,8 +357,8 @@ extern "C" q3_status q3_mimi_finalize(q3_speech_encoder* e) {
         const int nl = g ? c.n_q - c.n_sem : c.n_sem;
         if (!e->books[g] && nl > 0) M_HIP(hipMalloc((void**)&e->books[g], (size_t)nl * c.cb_size * c.cb_dim * 4));
         for (int l = 0; l < nl; ++l)
-            hipLaunchKernelGGL(k_mimi_codebook, dim3(c.cb_size), dim3(256), 0, e->st, m_vec(e, p + fm(".layers.%d.codebook.embed_sum", l)),
-                               m_vec(e, p + fm(".layers.%d.codebook.cluster_usage", l)), e->books[g] + (size_t)l * c.cb_size * c.cb_dim, c.cb_dim);
+            M_HIP(launch_mimi_codebook(m_vec(e, p + fm(".layers.%d.codebook.embed_sum", l)), m_vec(e, p + fm(".layers.%d.codebook.cluster_usage", l)),
+                                       e->books[g] + (size_t)l * c.cb_size * c.cb_dim, c.cb_size, c.cb_dim, e->st));
     }
     // bf16x3 matrix-core images of every conv whose channel counts allow it (cout % 32 == 0, cin % 16 == 0)
     std::vector<MConv*> all = {&e->c0, &e->last, &e->dsamp, &e->qproj[0], &e->qproj[1]};
@@ -455,17 +481,17 @@ static q3_status mimi_encode_from(q3_speech_encoder* e, const float* samples, hi
     for (int s = 0; s < 4; ++s) {
         const int r = c.ratios[s], hid = dim / c.compress;
         // MimiResnetBlock: x + conv1(ELU(conv3(ELU(x))))
-        hipLaunchKernelGGL(k_mimi_elu, dim3((unsigned)(((size_t)dim * L + 255) / 256)), dim3(256), 0, st, x, o1, (size_t)dim * L);
+        M_HIP(launch_mimi_elu(x, o1, (size_t)dim * L, st));
         M_HIP(m_run_conv(e, e->res1[s], o1, o2, L, /*ELU*/ 6));                         // o2 [hid][L]
         M_HIP(m_run_conv(e, e->res2[s], o2, o1, L, 0, x));                              // o1 = x + conv1(.)  [dim][L]
         (void)hid;
         // ELU + strided conv as fold + 2-tap conv
         const int Lf = m_ceil_div(L, r);
-        hipLaunchKernelGGL(k_mimi_fold, dim3((Lf + 255) / 256, dim * r), dim3(256), 0, st, o1, o2, L, r, Lf, 1, 0);       // o2 [dim*r][Lf]
+        M_HIP(launch_mimi_fold(o1, o2, dim, L, r, Lf, 1, 0, st));                       // o2 [dim*r][Lf]
         M_HIP(m_run_conv(e, e->down[s], o2, x, Lf));                                    // x [2dim][Lf]
         dim *= 2; L = Lf;
     }
-    hipLaunchKernelGGL(k_mimi_elu, dim3((unsigned)(((size_t)dim * L + 255) / 256)), dim3(256), 0, st, x, o1, (size_t)dim * L);
+    M_HIP(launch_mimi_elu(x, o1, (size_t)dim * L, st));
     float* hs = o2;                                                                     // [H][T25]
     M_HIP(m_run_conv(e, e->last, o1, hs, L));
     Q3I_CHECK(TAP(0, hs, (size_t)H * T25));
@@ -487,7 +513,7 @@ static q3_status mimi_encode_from(q3_speech_encoder* e, const float* samples, hi
     // ---- downsample: k = 4, stride 2, replicate padding -> fold with a leading replicate column, drop output column 0 ----
     float* fd = ff + (size_t)c.inter * tf;                                              // [2H][T + 1]
     float* dy = x;                                                                      // [H][T + 1] (x is free now)
-    hipLaunchKernelGGL(k_mimi_fold, dim3((T + 1 + 255) / 256, H * 2), dim3(256), 0, st, hs, fd, T25, 2, T, 0, 1);
+    M_HIP(launch_mimi_fold(hs, fd, H, T25, 2, T, 0, 1, st));
     M_HIP(m_run_conv(e, e->dsamp, fd, dy, T + 1));
     float* xd = o1;                                                                     // [H][T]
     M_HIP(launch_copy_rows(dy + 1, T + 1, xd, T, H, T, st));
@@ -498,7 +524,7 @@ static q3_status mimi_encode_from(q3_speech_encoder* e, const float* samples, hi
         const int nl = g ? c.n_q - c.n_sem : c.n_sem, q0 = g ? c.n_sem : 0;
         if (nl <= 0) continue;
         M_HIP(m_run_conv(e, e->qproj[g], xd, proj, T));
-        hipLaunchKernelGGL(k_mimi_rvq, dim3(T), dim3(256), 0, st, proj, T, e->books[g], nl, c.cb_size, c.cb_dim, e->codes_dev, c.n_q, q0);
+        M_HIP(launch_mimi_rvq(proj, T, e->books[g], nl, c.cb_size, c.cb_dim, e->codes_dev, c.n_q, q0, st));
     }
     M_HIP(hipGetLastError());
     M_HIP(hipStreamSynchronize(st));

@@ -75,6 +75,12 @@ __global__ __launch_bounds__(256) void k_spk_stft_mel(const float* __restrict__ 
         mel[(size_t)m * T + f] = logf(fmaxf(acc, 1e-5f));
     }
 }
+hipError_t launch_spk_stft_mel(const float* x, long n, int T, const float* win, const double* cs, const double* sn, const float* fb, float* mel,
+                               int n_mels, hipStream_t st) {
+    if (n < 1 || T < 1 || n_mels < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_spk_stft_mel, dim3(T), dim3(256), 0, st, x, n, T, win, cs, sn, fb, mel, n_mels);
+    return hipGetLastError();
+}
 
 // out[c][tp] = a[c][r] (+ b[c][r]), r = reflect(tp - pl) (speaker.rs:24-51; the Res2Net "chunk + previous output",
 // speaker.rs:186-192, rides along)
@@ -88,10 +94,21 @@ __global__ __launch_bounds__(256) void k_spk_pad(const float* __restrict__ a, co
     if (b) v = v + b[(size_t)c * T + r];
     out[(size_t)c * Tp + tp] = v;
 }
+hipError_t launch_spk_pad(const float* a, const float* b, float* out, int C, int T, int pl, int Tp, hipStream_t st) {
+    // the reflection r = -r / 2T - 2 - r stays inside [0, T) for at most T - 1 columns on either side
+    if (C < 1 || T < 1 || pl < 0 || pl > T - 1 || Tp < T + pl || Tp - T - pl > T - 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_spk_pad, dim3((Tp + 255) / 256, C), dim3(256), 0, st, a, b, out, T, pl, Tp);
+    return hipGetLastError();
+}
 // dst[c][t] = src[c][off + t]
 __global__ __launch_bounds__(256) void k_spk_cols(const float* __restrict__ src, int ld, int off, float* __restrict__ dst, int T) {
     const int c = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
     if (t < T) dst[(size_t)c * T + t] = src[(size_t)c * ld + off + t];
+}
+hipError_t launch_spk_cols(const float* src, int ld, int off, float* dst, int C, int T, hipStream_t st) {
+    if (C < 1 || T < 1 || off < 0 || ld < 1 || T > ld - off) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_spk_cols, dim3((T + 255) / 256, C), dim3(256), 0, st, src, ld, off, dst, T);
+    return hipGetLastError();
 }
 // per-channel mean over time (SE squeeze, speaker.rs:220)
 __global__ __launch_bounds__(256) void k_spk_mean(const float* __restrict__ x, float* __restrict__ mean, int T) {
@@ -102,10 +119,20 @@ __global__ __launch_bounds__(256) void k_spk_mean(const float* __restrict__ x, f
     a = block_sum(a, sh);
     if (threadIdx.x == 0) mean[blockIdx.x] = a / (float)T;
 }
+hipError_t launch_spk_mean(const float* x, float* mean, int C, int T, hipStream_t st) {
+    if (C < 1 || T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_spk_mean, dim3(C), dim3(256), 0, st, x, mean, T);
+    return hipGetLastError();
+}
 // h = o * g[c] + h (SE excite + the block's residual, speaker.rs:224-226, 270-271)
 __global__ __launch_bounds__(256) void k_spk_se_apply(const float* __restrict__ o, const float* __restrict__ g, float* __restrict__ h, int T) {
     const int c = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
     if (t < T) { const size_t e = (size_t)c * T + t; h[e] = add_rn(mul_rn(o[e], g[c]), h[e]); }
+}
+hipError_t launch_spk_se_apply(const float* o, const float* g, float* h, int C, int T, hipStream_t st) {
+    if (C < 1 || T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_spk_se_apply, dim3((T + 255) / 256, C), dim3(256), 0, st, o, g, h, T);
+    return hipGetLastError();
 }
 // attention input of the pooling (speaker.rs:303-316): rows [x ; mean ; std] with std = sqrt(mean((x-mean)²) + 1e-5)
 __global__ __launch_bounds__(256) void k_spk_asp_in(const float* __restrict__ m, float* __restrict__ ain, int C, int T) {
@@ -123,6 +150,11 @@ __global__ __launch_bounds__(256) void k_spk_asp_in(const float* __restrict__ m,
         ain[(size_t)(C + c) * T + t] = mean;
         ain[(size_t)(2 * C + c) * T + t] = sd;
     }
+}
+hipError_t launch_spk_asp_in(const float* m, float* ain, int C, int T, hipStream_t st) {
+    if (C < 1 || T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_spk_asp_in, dim3(C), dim3(256), 0, st, m, ain, C, T);
+    return hipGetLastError();
 }
 // softmax over time of the attention logits, weighted mean and std (speaker.rs:322-342): pooled = [mean ; std]
 __global__ __launch_bounds__(256) void k_spk_asp_pool(const float* __restrict__ aw, const float* __restrict__ m, float* __restrict__ pooled, int C, int T) {
@@ -142,6 +174,11 @@ __global__ __launch_bounds__(256) void k_spk_asp_pool(const float* __restrict__ 
     for (int t = threadIdx.x; t < T; t += 256) { const float d = r[t] - wm; wv += d * d * (expf(a[t] - mx) / s); }
     wv = block_sum(wv, sh);
     if (threadIdx.x == 0) { pooled[c] = wm; pooled[C + c] = sqrtf(wv + 1e-5f); }
+}
+hipError_t launch_spk_asp_pool(const float* aw, const float* m, float* pooled, int C, int T, hipStream_t st) {
+    if (C < 1 || T < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_spk_asp_pool, dim3(C), dim3(256), 0, st, aw, m, pooled, C, T);
+    return hipGetLastError();
 }
 
 }  // namespace q3
@@ -383,6 +420,17 @@ extern "C" q3_status q3_spk_finalize(q3_speaker_encoder* e) {
     return Q3_OK;
 }
 
+// test API: the front-end tables as the kernel reads them, copied back from the device
+extern "C" q3_status q3_spk_tables(q3_speaker_encoder* e, float* win_host, float* fb_host) {
+    if (!e || !win_host || !fb_host) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_tables: null argument");
+    if (e->device < 0 || !e->finalized) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_tables: encoder not finalized");
+    SPK_HIP(hipSetDevice(e->device));
+    SPK_HIP(hipStreamSynchronize(e->st));
+    SPK_HIP(q3_hipMemcpy(win_host, e->win, 1024 * 4, hipMemcpyDeviceToHost));
+    SPK_HIP(q3_hipMemcpy(fb_host, e->fb, (size_t)e->cfg.mel_dim * 513 * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
 extern "C" int q3_spk_mel_frames(int64_t n) {
     const int64_t padded = n + 2 * 384;
     return (n < 1 || padded < 1024) ? 0 : (int)((padded - 1024) / 256 + 1);
@@ -408,7 +456,7 @@ static q3_status spk_same_conv(q3_speaker_encoder* e, const SpkConv& cv, const f
         return Q3_OK;
     }
     const int pl = tot / 2, Tp = T + tot;
-    hipLaunchKernelGGL(k_spk_pad, dim3((Tp + 255) / 256, cv.cin), dim3(256), 0, e->st, x, x2, pad_buf, T, pl, Tp);
+    SPK_HIP(launch_spk_pad(x, x2, pad_buf, cv.cin, T, pl, Tp, e->st));
     a.x = pad_buf; a.L = Tp;
     if (tot == 0) {
         a.y = y;
@@ -418,8 +466,7 @@ static q3_status spk_same_conv(q3_speaker_encoder* e, const SpkConv& cv, const f
     // causal conv over the padded signal: column t + tot of its output is the "valid" conv at t
     a.y = tmp_buf;
     SPK_HIP(launch_conv1d(a, e->st));
-    hipLaunchKernelGGL(k_spk_cols, dim3((T + 255) / 256, cv.cout), dim3(256), 0, e->st, tmp_buf, Tp, tot, y, T);
-    SPK_HIP(hipGetLastError());
+    SPK_HIP(launch_spk_cols(tmp_buf, Tp, tot, y, cv.cout, T, e->st));
     return Q3_OK;
 }
 
@@ -457,20 +504,20 @@ static q3_status spk_forward_dev(q3_speaker_encoder* e, const float* mel_d, int 
             Q3I_CHECK(spk_same_conv(e, b.res[i], chunk, prev, o2 + (size_t)(i + 1) * chn * T, T, 3, pad_buf, tmp_buf));
         }
         Q3I_CHECK(spk_same_conv(e, b.tdnn2, o2, nullptr, o1, T, 3, pad_buf, tmp_buf));
-        hipLaunchKernelGGL(k_spk_mean, dim3(C), dim3(256), 0, e->st, o1, sm, T);                         // SE (speaker.rs:218-226)
+        SPK_HIP(launch_spk_mean(o1, sm, C, T, e->st));                                                   // SE (speaker.rs:218-226)
         Q3I_CHECK(spk_same_conv(e, b.se1, sm, nullptr, s1, 1, 3, pad_buf, tmp_buf));
         Q3I_CHECK(spk_same_conv(e, b.se2, s1, nullptr, g, 1, 5, pad_buf, tmp_buf));
-        hipLaunchKernelGGL(k_spk_se_apply, dim3((T + 255) / 256, C), dim3(256), 0, e->st, o1, g, h, T);
+        SPK_HIP(launch_spk_se_apply(o1, g, h, C, T, e->st));
         SPK_HIP(hipMemcpyAsync(cat + (size_t)cat_off * T, h, (size_t)C * T * 4, hipMemcpyDeviceToDevice, e->st));
         cat_off += C;
         Q3I_CHECK(tap(1 + bi, h, (size_t)C * T));
     }
     Q3I_CHECK(spk_same_conv(e, e->mfa, cat, nullptr, m, T, 3, pad_buf, tmp_buf));                       // MFA (speaker.rs:455-459)
     Q3I_CHECK(tap(4, m, (size_t)C4 * T));
-    hipLaunchKernelGGL(k_spk_asp_in, dim3(C4), dim3(256), 0, e->st, m, ain, C4, T);                       // ASP (speaker.rs:301-343)
+    SPK_HIP(launch_spk_asp_in(m, ain, C4, T, e->st));                                                     // ASP (speaker.rs:301-343)
     Q3I_CHECK(spk_same_conv(e, e->asp_tdnn, ain, nullptr, at, T, 4, pad_buf, tmp_buf));                  // ReLU then tanh
     Q3I_CHECK(spk_same_conv(e, e->asp_conv, at, nullptr, aw, T, 0, pad_buf, tmp_buf));
-    hipLaunchKernelGGL(k_spk_asp_pool, dim3(C4), dim3(256), 0, e->st, aw, m, pooled, C4, T);
+    SPK_HIP(launch_spk_asp_pool(aw, m, pooled, C4, T, e->st));
     Q3I_CHECK(tap(5, pooled, (size_t)2 * C4));
     Q3I_CHECK(spk_same_conv(e, e->fc, pooled, nullptr, out_d, 1, 0, pad_buf, tmp_buf));                 // FC (speaker.rs:464-465)
     SPK_HIP(hipGetLastError());
@@ -507,8 +554,7 @@ extern "C" q3_status q3_spk_mel(q3_speaker_encoder* e, const float* samples, int
     Q3I_CHECK(spk_reserve(e, (size_t)n + 64 + (size_t)e->cfg.mel_dim * T));
     float* x_d = e->ws; float* mel_d = e->ws + (((size_t)n + 63) & ~(size_t)63);
     SPK_HIP(hipMemcpyAsync(x_d, samples, (size_t)n * 4, hipMemcpyHostToDevice, e->st));
-    hipLaunchKernelGGL(k_spk_stft_mel, dim3(T), dim3(256), 0, e->st, x_d, (long)n, T, e->win, e->dft_cs, e->dft_sn, e->fb, mel_d, e->cfg.mel_dim);
-    SPK_HIP(hipGetLastError());
+    SPK_HIP(launch_spk_stft_mel(x_d, (long)n, T, e->win, e->dft_cs, e->dft_sn, e->fb, mel_d, e->cfg.mel_dim, e->st));
     SPK_HIP(hipMemcpyAsync(mel_host, mel_d, (size_t)e->cfg.mel_dim * T * 4, hipMemcpyDeviceToHost, e->st));
     SPK_HIP(hipStreamSynchronize(e->st));
     return Q3_OK;
@@ -534,7 +580,7 @@ static q3_status spk_encode_dev(q3_speaker_encoder* e, const float* x_d, int64_t
     const size_t xs = ((size_t)n + 63) & ~(size_t)63;
     float* mel_d = e->ws + xs; float* out_d = mel_d + (((size_t)e->cfg.mel_dim * T + 63) & ~(size_t)63);
     float* base = out_d + ((e->cfg.enc_dim + 63) & ~63);
-    hipLaunchKernelGGL(k_spk_stft_mel, dim3(T), dim3(256), 0, e->st, x_d, (long)n, T, e->win, e->dft_cs, e->dft_sn, e->fb, mel_d, e->cfg.mel_dim);
+    SPK_HIP(launch_spk_stft_mel(x_d, (long)n, T, e->win, e->dft_cs, e->dft_sn, e->fb, mel_d, e->cfg.mel_dim, e->st));
     Q3I_CHECK(spk_forward_dev(e, mel_d, T, out_d, base, nullptr));
     SPK_HIP(hipMemcpyAsync(out_host, out_d, (size_t)e->cfg.enc_dim * 4, hipMemcpyDeviceToHost, e->st));
     SPK_HIP(hipStreamSynchronize(e->st));

@@ -1172,6 +1172,135 @@ extern "C" q3_status q3_silu_mul_ex(int device, const float* g_host, const float
     return Q3_OK;
 }
 
+// ---- the voice-clone encoders' own kernels, one launch at a time (tests/test_gpu_clone_ops.py) ----
+// the shared frame of q3_spk_op_ex / q3_mimi_op_ex: a (and b) up, `out` up whole, one launch on out + out_front, `out` back whole
+template <typename Launch>
+static q3_status clone_op_run(const char* who, int device, const float* a_host, size_t a_n, const float* b_host, size_t b_n, float* out_host,
+                              size_t out_front, size_t out_n, Launch launch) {
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    float *a, *b = nullptr, *out;
+    HIPC(pool.alloc(&a, a_n)); HIPC(pool.alloc(&out, out_n));
+    HIPC(q3_hipMemcpy(a, a_host, a_n * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(out, out_host, out_n * 4, hipMemcpyHostToDevice));
+    if (b_host) { HIPC(pool.alloc(&b, b_n)); HIPC(q3_hipMemcpy(b, b_host, b_n * 4, hipMemcpyHostToDevice)); }
+    HIPC(q3_hipDeviceSynchronize());
+    const hipError_t e = launch(a, b, out + out_front);
+    if (e == hipErrorInvalidValue) {
+        (void)hipGetLastError();
+        return set_err(Q3_INVALID_ARG, "%s: the launcher refused its arguments (%s)", who, hipGetErrorString(e));
+    }
+    HIPC(e);
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(out_host, out, out_n * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_spk_op_ex(int device, const q3_spk_op_ex_args* p) {
+    if (!p || !p->a || !p->out) return set_err(Q3_INVALID_ARG, "q3_spk_op_ex: null argument");
+    const int op = p->op, C = p->C, T = p->T;
+    const long long lim = 1LL << 28;
+    if (op < 0 || op > 5) return set_err(Q3_INVALID_ARG, "q3_spk_op_ex: op 0..5");
+    if (C < 1 || C > 65535 || T < 1 || T > (1 << 20)) return set_err(Q3_INVALID_ARG, "q3_spk_op_ex: bad shape (C 1..65535, T 1..2^20)");
+    if (p->a_elems < 1 || p->a_elems > lim || p->b_elems < 0 || p->b_elems > lim || p->out_elems < 1 || p->out_elems > lim || p->out_front < 0 ||
+        p->out_front > p->out_elems || (p->b == nullptr) != (p->b_elems == 0))
+        return set_err(Q3_INVALID_ARG, "q3_spk_op_ex: bad buffers (1..2^28 floats each, out_front inside out, b_elems 0 exactly when b is null)");
+    const long long CT = (long long)C * T;
+    long long need_a = CT, need_b = 0, need_out = 0;
+    switch (op) {
+    case 0: {
+        const long long pr = (long long)p->Tp - T - p->pl;
+        if (p->pl < 0 || p->pl > T - 1 || p->Tp > (1 << 20) || pr < 0 || pr > T - 1)
+            return set_err(Q3_INVALID_ARG, "q3_spk_op_ex: pad of %d + %lld columns around T = %d (each side 0..T - 1, Tp <= 2^20)", p->pl, pr, T);
+        need_b = p->b ? CT : 0; need_out = (long long)C * p->Tp;
+        break;
+    }
+    case 1:
+        if (p->ld < 1 || p->ld > (1 << 20) || p->off < 0 || T > p->ld - p->off)
+            return set_err(Q3_INVALID_ARG, "q3_spk_op_ex: columns %d .. %d outside a row of %d", p->off, p->off + T, p->ld);
+        need_a = (long long)C * p->ld; need_out = CT;
+        break;
+    case 2: need_out = C; break;
+    case 3: need_b = C; need_out = CT; break;
+    case 4: need_out = 3 * CT; break;
+    default: need_b = CT; need_out = 2LL * C; break;
+    }
+    if ((op == 3 || op == 5) && !p->b) return set_err(Q3_INVALID_ARG, "q3_spk_op_ex: op %d needs b", op);
+    if ((op == 1 || op == 2 || op == 4) && p->b) return set_err(Q3_INVALID_ARG, "q3_spk_op_ex: op %d takes no b", op);
+    if (p->a_elems < need_a || p->b_elems < need_b || need_out > p->out_elems - p->out_front)
+        return set_err(Q3_INVALID_ARG, "q3_spk_op_ex: op %d needs %lld / %lld / %lld floats in a / b / out behind out_front", op, need_a, need_b, need_out);
+    return clone_op_run("q3_spk_op_ex", device, p->a, (size_t)p->a_elems, p->b, (size_t)p->b_elems, p->out, (size_t)p->out_front, (size_t)p->out_elems,
+                        [&](const float* a, const float* b, float* out) -> hipError_t {
+                            switch (op) {
+                            case 0: return launch_spk_pad(a, b, out, C, T, p->pl, p->Tp, 0);
+                            case 1: return launch_spk_cols(a, p->ld, p->off, out, C, T, 0);
+                            case 2: return launch_spk_mean(a, out, C, T, 0);
+                            case 3: return launch_spk_se_apply(a, b, out, C, T, 0);
+                            case 4: return launch_spk_asp_in(a, out, C, T, 0);
+                            default: return launch_spk_asp_pool(a, b, out, C, T, 0);
+                            }
+                        });
+}
+
+extern "C" q3_status q3_mimi_op_ex(int device, const q3_mimi_op_ex_args* p) {
+    if (!p || !p->a || !p->out) return set_err(Q3_INVALID_ARG, "q3_mimi_op_ex: null argument");
+    const int op = p->op, C = p->C, L = p->L, r = p->r, Lf = p->Lf;
+    const long long lim = 1LL << 28;
+    if (op < 0 || op > 2) return set_err(Q3_INVALID_ARG, "q3_mimi_op_ex: op 0..2");
+    if (L < 1 || L > (1 << 24)) return set_err(Q3_INVALID_ARG, "q3_mimi_op_ex: bad shape (L 1..2^24)");
+    if (op != 0 && (C < 1 || C > 65535)) return set_err(Q3_INVALID_ARG, "q3_mimi_op_ex: bad shape (C 1..65535)");
+    if (p->a_elems < 1 || p->a_elems > lim || p->b_elems < 0 || p->b_elems > lim || p->out_elems < 1 || p->out_elems > lim || p->out_front < 0 ||
+        p->out_front > p->out_elems || (p->b == nullptr) != (p->b_elems == 0))
+        return set_err(Q3_INVALID_ARG, "q3_mimi_op_ex: bad buffers (1..2^28 floats each, out_front inside out, b_elems 0 exactly when b is null)");
+    long long need_a = L, need_b = 0, need_out = L;
+    if (op == 1) {
+        if (r < 1 || r > 64 || (long long)C * r > 65535 || Lf < 1 || Lf > (1 << 24))
+            return set_err(Q3_INVALID_ARG, "q3_mimi_op_ex: bad fold (r 1..64, C * r <= 65535, Lf 1..2^24)");
+        if (!p->replicate && (long long)(Lf - 1) * r >= L)
+            return set_err(Q3_INVALID_ARG, "q3_mimi_op_ex: plain fold of L = %d by r = %d has no column %d ((Lf - 1) * r < L)", L, r, Lf - 1);
+        need_a = (long long)C * L; need_out = (long long)C * r * (Lf + (p->replicate ? 1 : 0));
+    } else if (op == 2) {
+        need_a = need_out = (long long)C * L; need_b = C;
+    }
+    if ((op == 2) != (p->b != nullptr)) return set_err(Q3_INVALID_ARG, "q3_mimi_op_ex: b (cluster_usage) goes with op 2 alone");
+    if (p->a_elems < need_a || p->b_elems < need_b || need_out > p->out_elems - p->out_front)
+        return set_err(Q3_INVALID_ARG, "q3_mimi_op_ex: op %d needs %lld / %lld / %lld floats in a / b / out behind out_front", op, need_a, need_b, need_out);
+    return clone_op_run("q3_mimi_op_ex", device, p->a, (size_t)p->a_elems, p->b, (size_t)p->b_elems, p->out, (size_t)p->out_front, (size_t)p->out_elems,
+                        [&](const float* a, const float* b, float* out) -> hipError_t {
+                            if (op == 0) return launch_mimi_elu(a, out, (size_t)L, 0);
+                            if (op == 1) return launch_mimi_fold(a, out, C, L, r, Lf, p->elu, p->replicate, 0);
+                            return launch_mimi_codebook(a, b, out, C, L, 0);
+                        });
+}
+
+extern "C" q3_status q3_mimi_rvq_ex(int device, const float* proj_host, int T, const float* books_host, int n_layers, int CB, int CD,
+                                    uint32_t* codes_host, int n_q, int q0) {
+    if (!proj_host || !books_host || !codes_host) return set_err(Q3_INVALID_ARG, "q3_mimi_rvq_ex: null argument");
+    if (CD < 1 || CD > 256 || CB < 1 || CB > (1 << 16) || T < 1 || T > (1 << 16))
+        return set_err(Q3_INVALID_ARG, "q3_mimi_rvq_ex: bad shape (CD 1..256, CB 1..65536, T 1..65536)");
+    if (n_layers < 1 || q0 < 0 || n_q < 1 || n_q > 64 || n_layers > n_q - q0)
+        return set_err(Q3_INVALID_ARG, "q3_mimi_rvq_ex: layers %d .. %d outside a frame of %d codes (n_layers >= 1, q0 >= 0, n_q 1..64)", q0, q0 + n_layers, n_q);
+    const size_t pn = (size_t)CD * T, bn = (size_t)n_layers * CB * CD, cn = (size_t)T * n_q;
+    // the winner indexes the table: a frame whose every distance is inf or NaN has none, so the values must keep the distances finite
+    for (size_t i = 0; i < pn; ++i) if (!(fabsf(proj_host[i]) < 1e12f)) return set_err(Q3_INVALID_ARG, "q3_mimi_rvq_ex: proj[%zu] is not finite or beyond 1e12", i);
+    for (size_t i = 0; i < bn; ++i) if (!(fabsf(books_host[i]) < 1e12f)) return set_err(Q3_INVALID_ARG, "q3_mimi_rvq_ex: books[%zu] is not finite or beyond 1e12", i);
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    float *proj, *books; uint32_t* codes;
+    HIPC(pool.alloc(&proj, pn)); HIPC(pool.alloc(&books, bn)); HIPC(pool.alloc(&codes, cn));
+    HIPC(q3_hipMemcpy(proj, proj_host, pn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(books, books_host, bn * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(codes, codes_host, cn * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipDeviceSynchronize());
+    const hipError_t e = launch_mimi_rvq(proj, T, books, n_layers, CB, CD, codes, n_q, q0, 0);
+    if (e == hipErrorInvalidValue) {
+        (void)hipGetLastError();
+        return set_err(Q3_INVALID_ARG, "q3_mimi_rvq_ex: the launcher refused its arguments (%s)", hipGetErrorString(e));
+    }
+    HIPC(e);
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(codes_host, codes, cn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
 #ifdef Q3_TRACE
 // development builds only (not declared in include/q3tts.h): arm the per-node stamp buffer BEFORE the first
 // q3_session_generate (the captured graph keeps the slice pointers), then read the stamps of the last replayed frame.

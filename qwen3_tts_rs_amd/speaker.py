@@ -108,6 +108,12 @@ class SpeakerEncoder:
         check(lib.q3_spk_mel(self._h, x.ctypes.data_as(ctypes.c_void_p), x.size, out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(nf)))
         return out
 
+    def tables(self) -> Tuple[np.ndarray, np.ndarray]:
+        """q3_spk_tables: (Hann window [1024], mel filterbank [mel_dim][513]) as the finalized encoder holds them on the device."""
+        win = np.empty(1024, np.float32); fb = np.empty((self.config.mel_dim, 513), np.float32)
+        check(lib.q3_spk_tables(self._h, win.ctypes.data_as(ctypes.c_void_p), fb.ctypes.data_as(ctypes.c_void_p)))
+        return win, fb
+
     def forward(self, mel: np.ndarray, taps: Optional[List[Optional[np.ndarray]]] = None) -> np.ndarray:
         """SpeakerEncoder::forward (speaker.rs:443-469) on one mel [mel_dim, T] → [enc_dim]."""
         m = np.ascontiguousarray(mel, dtype=np.float32)

@@ -143,6 +143,19 @@ def test_no_cpu_fallback():
                        (lambda: q.rvq_embed_ex(np.zeros((2, 16), np.uint32), np.zeros((4, 8), np.float32), np.zeros((15, 4, 8), np.float32),
                                                np.zeros(16, np.float32), np.zeros(16, np.float32)), "q3_rvq_embed_ex"),
                        (lambda: q.silu_mul_ex(np.zeros(8, np.float32), np.zeros(8, np.float32), np.zeros(8, np.float32)), "q3_silu_mul_ex"),
+                       (lambda: q.spk_op_ex(q.api.SPK_PAD, np.zeros((2, 5), np.float32), np.zeros(18, np.float32), C=2, T=5, pl=2, Tp=9), "q3_spk_op_ex (pad)"),
+                       (lambda: q.spk_op_ex(q.api.SPK_COLS, np.zeros((2, 9), np.float32), np.zeros(10, np.float32), C=2, T=5, ld=9, off=4), "q3_spk_op_ex (cols)"),
+                       (lambda: q.spk_op_ex(q.api.SPK_MEAN, np.zeros((2, 5), np.float32), np.zeros(2, np.float32), C=2, T=5), "q3_spk_op_ex (mean)"),
+                       (lambda: q.spk_op_ex(q.api.SPK_SE_APPLY, np.zeros((2, 5), np.float32), np.zeros(10, np.float32), C=2, T=5, b=np.zeros(2, np.float32)),
+                        "q3_spk_op_ex (se_apply)"),
+                       (lambda: q.spk_op_ex(q.api.SPK_ASP_IN, np.zeros((2, 5), np.float32), np.zeros(30, np.float32), C=2, T=5), "q3_spk_op_ex (asp_in)"),
+                       (lambda: q.spk_op_ex(q.api.SPK_ASP_POOL, np.zeros((2, 5), np.float32), np.zeros(4, np.float32), C=2, T=5, b=np.zeros((2, 5), np.float32)),
+                        "q3_spk_op_ex (asp_pool)"),
+                       (lambda: q.mimi_op_ex(q.api.MIMI_ELU, np.zeros(8, np.float32), np.zeros(8, np.float32), L=8), "q3_mimi_op_ex (elu)"),
+                       (lambda: q.mimi_op_ex(q.api.MIMI_FOLD, np.zeros((2, 7), np.float32), np.zeros(16, np.float32), L=7, C=2, r=2, Lf=4), "q3_mimi_op_ex (fold)"),
+                       (lambda: q.mimi_op_ex(q.api.MIMI_CODEBOOK, np.zeros((3, 8), np.float32), np.zeros(24, np.float32), L=8, C=3, b=np.ones(3, np.float32)),
+                        "q3_mimi_op_ex (codebook)"),
+                       (lambda: q.mimi_rvq_ex(np.zeros((8, 3), np.float32), np.zeros((2, 4, 8), np.float32), np.zeros((3, 4), np.uint32)), "q3_mimi_rvq_ex"),
                        (lambda: q.sample_ex(np.zeros((2, 8), np.float32), np.zeros(2, np.float32), 8, np.zeros(2, np.uint32), q.sample_row(q.SynthesisOptions())),
                         "q3_sample_ex"),
                        (lambda: q.frame_embed_ex(np.zeros((4, 8), np.uint16), np.zeros((15, 5, 8), np.uint16), [0], np.zeros((1, 5), np.float32),
@@ -295,6 +308,12 @@ def test_null_handles_return_status_not_crash():
         lambda: L.q3_gather_frames_ex(0, None, 16, None, 1, None, 16),
         lambda: L.q3_rvq_embed_ex(0, None, 1, None, None, 8, 16, None, None, 0, 8),
         lambda: L.q3_silu_mul_ex(0, None, None, None, 8, 8),
+        lambda: L.q3_spk_op_ex(0, None),
+        lambda: L.q3_spk_op_ex(0, ctypes.byref(_lib.CSpkOpEx())),
+        lambda: L.q3_mimi_op_ex(0, None),
+        lambda: L.q3_mimi_op_ex(0, ctypes.byref(_lib.CMimiOpEx())),
+        lambda: L.q3_mimi_rvq_ex(0, None, 1, None, 1, 4, 8, None, 1, 0),
+        lambda: L.q3_spk_tables(None, None, None),
         lambda: L.q3_sample_row(None, None),
         lambda: L.q3_prompt_shape(None, 0, None, None, None, 0),
         lambda: L.q3_sample_ex(0, None),
