@@ -1306,6 +1306,30 @@ q3_status q3_spk_encode_ref(q3_speaker_encoder* e, const q3_ref_audio* r, float*
 q3_status q3_mimi_encode_ref(q3_speech_encoder* e, const q3_ref_audio* r, uint32_t* codes_host, int cap_frames, int* n_frames,
                              float** taps_host);
 
+/* ---------------- many reference clips in one packed pass of each encoder ----------------
+ * n = 1 .. 64 objects of different lengths, laid side by side along the time axis of the encoders' [C][L] tensors, so every conv
+ * launch covers all of them. Each clip's result is bit-equal to q3_spk_encode_ref / q3_mimi_encode_ref of that clip alone, whatever
+ * the other clips are and wherever it lies. All or nothing: every clip is checked before the device is touched (null entry, another
+ * device, more than 120 s, too few mel frames for the reflect padding, output too small); a refusal names the clip's index
+ * ("clip 2: ...") in q3_last_error and writes nothing. Both calls run on the encoder's own stream and synchronise before they return.
+ * No reference counterpart: the reference encodes one clip per call. */
+/* Encoder12Hz::encode's lengths (encoder_12hz.rs:119-144) for a list of clips: where each clip's slot lies. Pure host arithmetic, no
+ * device. A slot is the clip's q3_mimi_frames frames plus one guard frame of *frame_samples = 2 * prod(ratios) samples; `start` is
+ * the slot's first sample inside its pass. A pass holds consecutive clips whose slots sum to at most max_pass_samples (a clip whose
+ * own slot is larger gets a pass to itself). *packable = 0: one guard frame does not cover the left context of every conv of this
+ * configuration, and q3_mimi_encode_refs runs clip by clip. frame_samples / packable / n_passes may be NULL. */
+typedef struct q3_mimi_pack_clip { int32_t frames; int32_t pass; int64_t start; } q3_mimi_pack_clip;
+q3_status q3_mimi_pack_plan(const q3_mimi_config* cfg, const int64_t* n_samples, int n, int64_t max_pass_samples, q3_mimi_pack_clip* clips,
+                            int64_t* frame_samples, int* packable, int* n_passes);
+/* Encoder12Hz::encode (encoder_12hz.rs:119-144, as called by lib.rs:1172-1178) of n objects: n_frames [n]; codes_host
+ * [sum of n_frames][n_q], clip after clip (NULL: only n_frames); cap_frames: frames codes_host holds. taps_host (test hook): NULL or
+ * 3 * n host pointers indexed [clip][tap], each as q3_mimi_encode's (NULL entries skipped). Passes of at most 120 s of slots. */
+q3_status q3_mimi_encode_refs(q3_speech_encoder* e, const q3_ref_audio* const* refs, int n, uint32_t* codes_host, int cap_frames,
+                              int* n_frames, float** taps_host);
+/* SpeakerEncoder::encode (speaker.rs:431-438, as called by lib.rs:1168) of n objects: out_host [n][enc_dim]. taps_host (test hook):
+ * NULL or 6 * n host pointers indexed [clip][tap], each as q3_spk_forward's (NULL entries skipped). Passes of at most 120 s of audio. */
+q3_status q3_spk_encode_refs(q3_speaker_encoder* e, const q3_ref_audio* const* refs, int n, float* out_host, float** taps_host);
+
 /* ---------------- data parallelism without torch.distributed (q3_dp.cpp) ----------------
  * one process per GPU, utterance i -> rank i mod N, exactly one collective on the data path — the
  * broadcast of rank 0's weight arena over RCCL (xGMI) — plus an all-gather of a few doubles for end-of-job timing. The

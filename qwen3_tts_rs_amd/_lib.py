@@ -147,6 +147,10 @@ class CClip(ctypes.Structure):           # q3_clip
                 ("format", ctypes.c_int32)]
 
 
+class CMimiPackClip(ctypes.Structure):   # q3_mimi_pack_clip
+    _fields_ = [("frames", ctypes.c_int32), ("pass_", ctypes.c_int32), ("start", ctypes.c_int64)]
+
+
 class CWavDesc(ctypes.Structure):        # q3_wav_desc
     _fields_ = [("format", ctypes.c_int32), ("channels", ctypes.c_int32), ("bits", ctypes.c_int32), ("sample_rate", ctypes.c_uint32),
                 ("frames", ctypes.c_int64), ("data_offset", ctypes.c_int64), ("data_bytes", ctypes.c_int64)]
@@ -395,6 +399,9 @@ SYMBOLS = {
     "q3_ref_audio_free": (None, [c_void_p]),
     "q3_spk_encode_ref": (c_int, [c_void_p, c_void_p, c_void_p]),
     "q3_mimi_encode_ref": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(c_int), P(c_void_p)]),
+    "q3_mimi_pack_plan": (c_int, [P(CMimiConfig), P(ctypes.c_int64), c_int, ctypes.c_int64, P(CMimiPackClip), P(ctypes.c_int64), P(c_int), P(c_int)]),
+    "q3_mimi_encode_refs": (c_int, [c_void_p, P(c_void_p), c_int, c_void_p, c_int, P(c_int), P(c_void_p)]),
+    "q3_spk_encode_refs": (c_int, [c_void_p, P(c_void_p), c_int, c_void_p, P(c_void_p)]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():

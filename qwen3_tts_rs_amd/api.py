@@ -983,6 +983,32 @@ class Qwen3TTS:
             ref_codes = self.speech_encoder.encode(ref_audio.samples, ref_audio.sample_rate)      # [T_frames, 16]
         return VoiceClonePrompt(emb, np.ascontiguousarray(ref_codes, dtype=np.uint32), np.asarray(ref_text_ids, dtype=np.uint32))
 
+    def create_voice_clone_prompts(self, refs: List["RefAudio"], ref_text_ids=None):
+        """create_voice_clone_prompt for many RefAudio objects with one call per encoder (encode_refs). `ref_text_ids`:
+        None, or one entry per clip, None for an x-vector-only clip. Prompt i equals create_voice_clone_prompt(refs[i],
+        ref_text_ids[i]) field for field."""
+        from .speaker import VoiceClonePrompt
+        refs = list(refs)
+        texts = [None] * len(refs) if ref_text_ids is None else list(ref_text_ids)
+        if len(texts) != len(refs):
+            raise ValueError(f"{len(refs)} clips, {len(texts)} ref_text_ids entries")
+        if any(not isinstance(r, RefAudio) for r in refs):
+            raise TypeError("create_voice_clone_prompts takes RefAudio objects (RefAudio.many)")
+        if not refs:
+            return []
+        if self.speaker_encoder is None:
+            raise _lib.Q3Error(3, "Speaker encoder not available. Ensure model weights contain `speaker_encoder.*` keys "
+                                  "(only Base models include a speaker encoder).")
+        icl = [i for i, t in enumerate(texts) if t is not None]
+        if icl and self.speech_encoder is None:
+            raise _lib.Q3Error(7, "ICL voice cloning requires a speech encoder, but it was not loaded. Ensure the speech tokenizer "
+                                  "weights contain encoder keys, or use x_vector_only mode by passing ref_text=None.")
+        embs = self.speaker_encoder.encode_refs(refs)
+        codes = dict(zip(icl, self.speech_encoder.encode_refs([refs[i] for i in icl]))) if icl else {}
+        return [VoiceClonePrompt(embs[i].copy()) if texts[i] is None else
+                VoiceClonePrompt(embs[i].copy(), np.ascontiguousarray(codes[i], dtype=np.uint32), np.asarray(texts[i], dtype=np.uint32))
+                for i in range(len(refs))]
+
     def synthesize_voice_clone_prompt(self, text_ids, prompt, language: "Language", options=None):
         """synthesize_voice_clone (lib.rs:1202-1262) with a VoiceClonePrompt."""
         return self.synthesize_voice_clone(text_ids, prompt.speaker_embedding, language, options,

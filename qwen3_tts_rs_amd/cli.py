@@ -92,7 +92,50 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prefix-cache", type=int, default=0, metavar="PAGES",
                     help="keep up to PAGES KV pages (128 positions each) of prefilled --instruct prompts for later requests of this model (0 = off)")
     ap.add_argument("--no-eos", action="store_true", help="disable EOS (fixed-length runs on synthetic weights)")
+    ap.add_argument("--tokenize", nargs="+", default=None, metavar="WAV",
+                    help="instead of synthesizing: encode these clips with the 12.5 Hz speech tokenizer of --model-dir (or a seeded one with "
+                         "--synthetic) — one intake launch (RefAudio.many), one packed encoder pass (SpeechEncoder.encode_refs) — and write "
+                         "<output-dir>/<stem>.codes.bin per clip (the codes_*.bin format of --ref-codes-bin)")
     return ap
+
+
+def tokenize_clips(a, dev: int) -> int:
+    """--tokenize: WAV files -> <stem>.codes.bin through RefAudio.many and SpeechEncoder.encode_refs."""
+    import qwen3_tts_rs_amd as q
+    from qwen3_tts_rs_amd import api
+    stems = [os.path.splitext(os.path.basename(p))[0] for p in a.tokenize]
+    if len(set(stems)) != len(stems):
+        print("error: --tokenize: two clips share a file name; their outputs would overwrite each other", file=sys.stderr)
+        return 2
+    refs = []
+    try:
+        if a.synthetic:
+            enc = q.SpeechEncoder.from_synthetic(q.tiny_speech_config() if a.synthetic == "tiny" else None, device=dev)
+        else:
+            tok = os.path.join(a.model_dir, "speech_tokenizer", "model.safetensors")
+            if not os.path.exists(tok):
+                tok = os.path.join(os.path.dirname(os.path.abspath(a.model_dir)), "speech_tokenizer", "model.safetensors")
+            enc = q.SpeechEncoder.from_safetensors(tok, None, dev)
+        clips = []
+        for p in a.tokenize:
+            desc = api.wav_info(p)
+            with open(p, "rb") as f:
+                raw = f.read()
+            clips.append((raw[desc.data_offset:desc.data_offset + desc.data_bytes], desc.sample_rate, desc.fmt, desc.channels))
+        refs = api.RefAudio.many(clips, device=dev)
+        codes = enc.encode_refs(refs)
+    except (api._lib.Q3Error, OSError) as e:
+        print(f"error: {e}", file=sys.stderr)
+        return 2
+    os.makedirs(a.output_dir, exist_ok=True)
+    for p, stem, ref, c in zip(a.tokenize, stems, refs, codes):
+        out = os.path.join(a.output_dir, stem + ".codes.bin")
+        api.save_codes_binary(out, c)
+        print(f"Tokenized: {p} ({ref.duration():.2f}s, {ref.source_rate} Hz) -> {out} ({c.shape[0]} frames)")
+    for r in refs:
+        r.close()
+    enc.close()
+    return 0
 
 
 def parse_device(s: str) -> int:
@@ -269,6 +312,8 @@ def main(argv=None) -> int:
         print(f"error: {e}", file=sys.stderr)
         return 2
     dev = parse_device(a.device)
+    if a.tokenize:
+        return tokenize_clips(a, dev)
     speaker, language = q.Speaker.from_str(a.speaker), q.Language.from_str(a.language)
     frames = max_frames_from_args(a)
     t0 = time.time()

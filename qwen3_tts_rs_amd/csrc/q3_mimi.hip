@@ -13,6 +13,8 @@
 //   * transformer layers on the [C][T] layout as 1x1 convs + channel LayerNorm + rotate-half RoPE, attention with the
 //     250-frame causal window in k_mimi_attn;
 //   * k_mimi_rvq: one workgroup per frame walks the quantiser layers (distance to 2048 entries, first minimum, subtract).
+// Many clips per call (q3_mimi_encode_refs): the same launches once over all clips laid side by side, each in a slot with a guard
+// frame, the elementwise kernels as clip-aware instances (k_mimi_*_p) — bit-equal per clip to the clip alone.
 #include "../../include/q3tts.h"
 #include "q3_kernels.h"
 #include "q3_capture_lock.h"
@@ -65,12 +67,12 @@ hipError_t launch_mimi_fold(const float* x, float* y, int C, int L, int r, int L
     return hipGetLastError();
 }
 // causal sliding-window MHA on [nh*64][T] tensors: one 64-lane wave per (query t, head h), keys j in (t - window, t]
-__global__ __launch_bounds__(64) void k_mimi_attn(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                  float* __restrict__ o, int T, int window, float scale) {
-    const int t = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+// (query column t of head h against the keys j0 .. t, 64 per step from j0 on: the body of k_mimi_attn and of its packed instance)
+__device__ __forceinline__ void mimi_attn_col(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                              float* __restrict__ o, int T, int t, int j0, int h, float scale) {
+    const int lane = threadIdx.x;
     const size_t hb = (size_t)h * 64 * T;
     const float qd = q[hb + (size_t)lane * T + t];
-    int j0 = t - window + 1; if (j0 < 0) j0 = 0;
     float m = -INFINITY, l = 0.0f, acc = 0.0f;
     for (int jb = j0; jb <= t; jb += 64) {
         const int j = jb + lane; const bool ok = j <= t;
@@ -94,6 +96,12 @@ __global__ __launch_bounds__(64) void k_mimi_attn(const float* __restrict__ q, c
         m = mn;
     }
     o[hb + (size_t)lane * T + t] = acc / l;
+}
+__global__ __launch_bounds__(64) void k_mimi_attn(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                  float* __restrict__ o, int T, int window, float scale) {
+    const int t = blockIdx.x;
+    int j0 = t - window + 1; if (j0 < 0) j0 = 0;
+    mimi_attn_col(q, k, v, o, T, t, j0, blockIdx.y, scale);
 }
 hipError_t launch_mimi_attn(const float* q, const float* k, const float* v, float* o, int nh, int hd, int T, int window, float scale,
                             hipStream_t st) {
@@ -151,6 +159,63 @@ hipError_t launch_mimi_rvq(const float* proj, int T, const float* books, int n_l
     if (CD < 1 || CD > 256 || CB < 1 || n_layers < 1 || q0 < 0 || (long long)q0 + n_layers > n_q || T < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_mimi_rvq, dim3(T), dim3(256), 0, st, proj, T, books, n_layers, CB, CD, codes, n_q, q0);
     return hipGetLastError();
+}
+
+// ---- packed instances (q3_mimi_encode_refs): n clips side by side along the time axis of the [C][W] tensors. Clip i
+// owns a slot of `slot` columns from column `start`; its signal fills the first `len` of them, the rest — at least one 12.5 Hz
+// frame — is its guard. These kernels write exact zeros into every slot column outside [start, start + len): the zeros the
+// causal convs pad with when the clip is alone. One table entry per (stage, clip); the grid's z is the clip.
+struct MimiClip { int start, len, slot, out; };        // out: the clip's first frame in the dense [C][sum of T] tensors behind the guards
+__global__ __launch_bounds__(256) void k_mimi_elu_p(const MimiClip* __restrict__ tab, const float* __restrict__ x, float* __restrict__ y, int W) {
+    const MimiClip cl = tab[blockIdx.z];
+    const int col = blockIdx.x * 256 + threadIdx.x;
+    if (col >= cl.slot) return;
+    const size_t i = (size_t)blockIdx.y * W + cl.start + col;
+    float r = 0.0f;
+    if (col < cl.len) { const float v = x[i]; r = v > 0.0f ? v : expf(v) - 1.0f; }
+    y[i] = r;
+}
+// x [C][W] -> y [C*r][W / r] (slot starts and widths are multiples of r): y[(c*r + p)][start/r + tau] = f(x[c][start + tau*r + p]), 0 beyond len
+__global__ __launch_bounds__(256) void k_mimi_fold_p(const MimiClip* __restrict__ tab, const float* __restrict__ x, float* __restrict__ y, int W, int r, int elu) {
+    const MimiClip cl = tab[blockIdx.z];
+    const int col = blockIdx.x * 256 + threadIdx.x, cp = blockIdx.y;
+    if (col >= cl.slot / r) return;
+    const int c = cp / r, p = cp % r;
+    const int i = col * r + p;
+    float v = i < cl.len ? x[(size_t)c * W + cl.start + i] : 0.0f;
+    if (elu) v = v > 0.0f ? v : expf(v) - 1.0f;
+    y[(size_t)cp * (W / r) + cl.start / r + col] = v;
+}
+// the replicate-padded fold by 2 in front of the 12.5 Hz down-sampling conv: x [C][W] -> y [2C][W / 2], the clip's slot being
+// len/2-rounded-up + 1 columns wide: column 0 of the slot holds x[c][start] for both phases, samples beyond len repeat the last one
+__global__ __launch_bounds__(256) void k_mimi_fold_rep_p(const MimiClip* __restrict__ tab, const float* __restrict__ x, float* __restrict__ y, int W) {
+    const MimiClip cl = tab[blockIdx.z];
+    const int col = blockIdx.x * 256 + threadIdx.x, cp = blockIdx.y;
+    if (col >= cl.slot / 2) return;
+    const int c = cp / 2, p = cp % 2;
+    const float* xr = x + (size_t)c * W + cl.start;
+    float v;
+    if (col == 0) v = xr[0];
+    else {
+        const int i = (col - 1) * 2 + p;
+        v = i < cl.len ? xr[i] : xr[cl.len - 1];
+    }
+    y[(size_t)cp * (W / 2) + cl.start / 2 + col] = v;
+}
+// dst[c][out + t] = src[c][start + 1 + t], t < len: drops each slot's lead column and closes the guards (src [C][W], dst [C][Wd])
+__global__ __launch_bounds__(256) void k_mimi_cols_p(const MimiClip* __restrict__ tab, const float* __restrict__ src, int W, float* __restrict__ dst, int Wd) {
+    const MimiClip cl = tab[blockIdx.z];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < cl.len) dst[(size_t)blockIdx.y * Wd + cl.out + t] = src[(size_t)blockIdx.y * W + cl.start + 1 + t];
+}
+// k_mimi_attn over the packed 25 Hz columns: first[t] = the first column of the clip that owns column t (-1: a guard column, whose
+// output is zero), so the window starts at max(t - window + 1, first[t]) and the keys fall on the lanes as they do for the clip alone
+__global__ __launch_bounds__(64) void k_mimi_attn_p(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                    float* __restrict__ o, int W, const int* __restrict__ first, int window, float scale) {
+    const int t = blockIdx.x, s0 = first[t];
+    if (s0 < 0) { o[((size_t)blockIdx.y * 64 + threadIdx.x) * W + t] = 0.0f; return; }
+    int j0 = t - window + 1; if (j0 < s0) j0 = s0;
+    mimi_attn_col(q, k, v, o, W, t, j0, blockIdx.y, scale);
 }
 
 }  // namespace q3
@@ -423,25 +488,9 @@ extern "C" q3_status q3_mimi_encode_ref(q3_speech_encoder* e, const q3_ref_audio
     return mimi_encode_from(e, x_d, hipMemcpyDeviceToDevice, n, codes_host, cap_frames, n_frames, taps_host);
 }
 
-// q3_mimi_encode behind its checks of handle and rate: `samples` on the host or on the encoder's device, as `kind` says
-static q3_status mimi_encode_from(q3_speech_encoder* e, const float* samples, hipMemcpyKind kind, int64_t n, uint32_t* codes_host,
-                                  int cap_frames, int* n_frames, float** taps_host) {
-    if (n < 1 || n > (int64_t)24000 * 120) return q3i_set_err(Q3_INVALID_ARG, "reference audio of %lld samples unsupported (1 .. 120 s)", (long long)n);
+// the workspace, the RoPE tables for T25 positions and the device-side codes of T frames, each grown when a call needs more
+static q3_status mimi_reserve(q3_speech_encoder* e, size_t need, int T25, int T) {
     const q3_mimi_config& c = e->cfg;
-    const int T = q3_mimi_frames(&c, n);
-    *n_frames = T;
-    if (!codes_host) return Q3_OK;
-    if (cap_frames < T) return q3i_set_err(Q3_INVALID_ARG, "codes buffer too small (%d < %d frames)", cap_frames, T);
-    M_HIP(hipSetDevice(e->device));
-    const int F = c.n_filters, H = c.hidden;
-    // workspace: three ping-pong buffers of the largest [C][L] activation (+ folding slack), the transformer's q|k|v|att, the MLP hidden
-    int Ls[6]; Ls[0] = (int)n;
-    for (int s = 0; s < 4; ++s) Ls[s + 1] = m_ceil_div(Ls[s], c.ratios[s]);
-    const int T25 = Ls[4];
-    size_t big = 0; { int dim = F; for (int s = 0; s < 4; ++s) { const size_t v = (size_t)dim * ((size_t)Ls[s] + 16 * c.ratios[s]); if (v > big) big = v; dim *= 2; }
-                      const size_t v = (size_t)dim * (Ls[4] + 2); if (v > big) big = v; }
-    const size_t tf = (size_t)T25 + 4;
-    const size_t need = 3 * big + (size_t)(5 * H + c.inter) * tf + (size_t)2 * H * tf + (size_t)c.cb_dim * (T + 2) + 64;
     if (need > e->ws_floats) {
         M_HIP(hipStreamSynchronize(e->st));
         if (e->ws) M_HIP(hipFree(e->ws));
@@ -467,6 +516,29 @@ static q3_status mimi_encode_from(q3_speech_encoder* e, const float* samples, hi
         M_HIP(hipMalloc((void**)&e->codes_dev, (size_t)(T + 64) * c.n_q * 4));
         e->codes_cap = T + 64;
     }
+    return Q3_OK;
+}
+
+// q3_mimi_encode behind its checks of handle and rate: `samples` on the host or on the encoder's device, as `kind` says
+static q3_status mimi_encode_from(q3_speech_encoder* e, const float* samples, hipMemcpyKind kind, int64_t n, uint32_t* codes_host,
+                                  int cap_frames, int* n_frames, float** taps_host) {
+    if (n < 1 || n > (int64_t)24000 * 120) return q3i_set_err(Q3_INVALID_ARG, "reference audio of %lld samples unsupported (1 .. 120 s)", (long long)n);
+    const q3_mimi_config& c = e->cfg;
+    const int T = q3_mimi_frames(&c, n);
+    *n_frames = T;
+    if (!codes_host) return Q3_OK;
+    if (cap_frames < T) return q3i_set_err(Q3_INVALID_ARG, "codes buffer too small (%d < %d frames)", cap_frames, T);
+    M_HIP(hipSetDevice(e->device));
+    const int F = c.n_filters, H = c.hidden;
+    // workspace: three ping-pong buffers of the largest [C][L] activation (+ folding slack), the transformer's q|k|v|att, the MLP hidden
+    int Ls[6]; Ls[0] = (int)n;
+    for (int s = 0; s < 4; ++s) Ls[s + 1] = m_ceil_div(Ls[s], c.ratios[s]);
+    const int T25 = Ls[4];
+    size_t big = 0; { int dim = F; for (int s = 0; s < 4; ++s) { const size_t v = (size_t)dim * ((size_t)Ls[s] + 16 * c.ratios[s]); if (v > big) big = v; dim *= 2; }
+                      const size_t v = (size_t)dim * (Ls[4] + 2); if (v > big) big = v; }
+    const size_t tf = (size_t)T25 + 4;
+    const size_t need = 3 * big + (size_t)(5 * H + c.inter) * tf + (size_t)2 * H * tf + (size_t)c.cb_dim * (T + 2) + 64;
+    Q3I_CHECK(mimi_reserve(e, need, T25, T));
     float* A = e->ws; float* B = A + big; float* C = B + big; float* tr = C + big;
     hipStream_t st = e->st;
     auto TAP = [&](int id, const float* dev, size_t cnt) -> q3_status {
@@ -529,5 +601,208 @@ static q3_status mimi_encode_from(q3_speech_encoder* e, const float* samples, hi
     M_HIP(hipGetLastError());
     M_HIP(hipStreamSynchronize(st));
     M_HIP(q3_hipMemcpy(codes_host, e->codes_dev, (size_t)T * c.n_q * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+// ---- many clips in one packed pass of the encoder ----
+// Pure host arithmetic, no HIP call: where each clip's slot lies. A slot is the clip's frames plus one guard frame, S = 2 * prod(ratios)
+// samples per frame, so a slot starts on a whole column at every SEANet stage and on an even column at 25 Hz. Packable: one guard
+// frame covers the left context of every conv (kernel - 1 samples at stage 0, res_kernel - 1 columns at each stage, last_kernel - 1
+// at 25 Hz; a folded strided conv reaches one column back, and every stage has at least two columns per frame).
+extern "C" q3_status q3_mimi_pack_plan(const q3_mimi_config* cfg, const int64_t* n_samples, int n, int64_t max_pass_samples, q3_mimi_pack_clip* clips,
+                                       int64_t* frame_samples, int* packable, int* n_passes) {
+    if (!cfg || !n_samples || !clips) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_pack_plan: null argument");
+    if (n < 1 || n > 64) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_pack_plan: %d clips (1 .. 64)", n);
+    if (max_pass_samples < 1) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_pack_plan: max_pass_samples %lld", (long long)max_pass_samples);
+    int64_t S = 2;
+    for (int s = 0; s < 4; ++s) {
+        if (cfg->ratios[s] < 1 || cfg->ratios[s] > 16) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_pack_plan: bad ratio");
+        S *= cfg->ratios[s];
+    }
+    bool ok = cfg->kernel >= 1 && cfg->res_kernel >= 1 && cfg->last_kernel >= 1 && cfg->kernel - 1 <= S && cfg->last_kernel - 1 <= 2;
+    int64_t cpf = S;                                                   // columns per frame at stage s
+    for (int s = 0; s < 4; ++s) { if (cfg->res_kernel - 1 > cpf) ok = false; cpf /= cfg->ratios[s]; }
+    int pass = 0; int64_t at = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_samples[i] < 1) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_pack_plan: clip %d: %lld samples", i, (long long)n_samples[i]);
+        const int T = q3_mimi_frames(cfg, n_samples[i]);
+        const int64_t slot = ((int64_t)T + 1) * S;
+        if (at > 0 && at + slot > max_pass_samples) { ++pass; at = 0; }      // (a clip whose own slot is larger gets a pass to itself)
+        clips[i].frames = T; clips[i].pass = pass; clips[i].start = at;
+        at += slot;
+    }
+    if (frame_samples) *frame_samples = S;
+    if (packable) *packable = ok ? 1 : 0;
+    if (n_passes) *n_passes = pass + 1;
+    return Q3_OK;
+}
+
+// one pass: clips xs[i] (ns[i] samples, on the encoder's device) in the slots pc[i]; codes_host [sum of T][n_q], clip after clip;
+// taps_host: NULL or 3 pointers per clip. mimi_encode_from with the packed width in place of the clip's length: the same convs in
+// the same order over all slots at once, the elementwise steps as their packed instances.
+static q3_status mimi_encode_packed(q3_speech_encoder* e, const float* const* xs, const int64_t* ns, const q3_mimi_pack_clip* pc, int n, int64_t S,
+                                    uint32_t* codes_host, float** taps_host) {
+    const q3_mimi_config& c = e->cfg;
+    const int F = c.n_filters, H = c.hidden;
+    hipStream_t st = e->st;
+    int64_t W0 = 0; int Tsum = 0, maxT = 0, maxT25 = 0;
+    for (int i = 0; i < n; ++i) { W0 += ((int64_t)pc[i].frames + 1) * S; Tsum += pc[i].frames; maxT = std::max(maxT, pc[i].frames); }
+    if (W0 > 0x7fffffffLL - 4096) return q3i_set_err(Q3_INVALID_ARG, "packed pass of %lld samples unsupported", (long long)W0);
+    int Ws[5]; Ws[0] = (int)W0;
+    for (int s = 0; s < 4; ++s) Ws[s + 1] = Ws[s] / c.ratios[s];
+    const int W25 = Ws[4], W12 = W25 / 2;
+    // the tables: stage s = 0 .. 4 (the SEANet rates, 4 = 25 Hz), 5 = 12.5 Hz; first / pos per 25 Hz column
+    std::vector<MimiClip> tab((size_t)6 * n);
+    std::vector<int> colinfo((size_t)2 * W25, 0);
+    int* first_h = colinfo.data(); int* pos_h = first_h + W25;
+    for (int t = 0; t < W25; ++t) first_h[t] = -1;
+    int out = 0;
+    for (int i = 0; i < n; ++i) {
+        int64_t div = 1, L = ns[i];
+        for (int s = 0; s < 5; ++s) {
+            tab[(size_t)s * n + i] = MimiClip{(int)(pc[i].start / div), (int)L, (int)(((int64_t)pc[i].frames + 1) * S / div), 0};
+            if (s < 4) { div *= c.ratios[s]; L = (L + c.ratios[s] - 1) / c.ratios[s]; }
+        }
+        const MimiClip& c25 = tab[(size_t)4 * n + i];
+        maxT25 = std::max(maxT25, c25.len);
+        for (int t = 0; t < c25.len; ++t) { first_h[c25.start + t] = c25.start; pos_h[c25.start + t] = t; }
+        tab[(size_t)5 * n + i] = MimiClip{c25.start / 2, pc[i].frames, pc[i].frames + 1, out};
+        out += pc[i].frames;
+    }
+    size_t big = 0; { int dim = F; for (int s = 0; s < 4; ++s) { const size_t v = (size_t)dim * ((size_t)Ws[s] + 16 * c.ratios[s]); if (v > big) big = v; dim *= 2; }
+                      const size_t v = (size_t)dim * (Ws[4] + 2); if (v > big) big = v; }
+    const size_t tf = (size_t)W25 + 4;
+    const size_t floats = 3 * big + (size_t)(5 * H + c.inter) * tf + (size_t)2 * H * tf + (size_t)c.cb_dim * (W12 + 2) + 64;
+    const size_t ints = tab.size() * 4 + colinfo.size();
+    Q3I_CHECK(mimi_reserve(e, floats + ints + 64, maxT25, Tsum));
+    float* A = e->ws; float* B = A + big; float* C = B + big; float* tr = C + big;
+    MimiClip* tab_d = (MimiClip*)(e->ws + ((floats + 3) & ~(size_t)3));
+    int* first_d = (int*)(tab_d + tab.size()); int* pos_d = first_d + W25;
+    M_HIP(hipMemcpyAsync(tab_d, tab.data(), tab.size() * sizeof(MimiClip), hipMemcpyHostToDevice, st));
+    M_HIP(hipMemcpyAsync(first_d, colinfo.data(), colinfo.size() * 4, hipMemcpyHostToDevice, st));
+    // tap `id` of every clip: its columns [start, start + len) of src [H][ld]
+    auto TAP = [&](int id, const float* dev, int ld, int stage, bool dense) -> q3_status {
+        if (!taps_host) return Q3_OK;
+        bool any = false;
+        for (int i = 0; i < n; ++i) {
+            float* dst = taps_host[(size_t)3 * i + id];
+            if (!dst) continue;
+            const MimiClip& cl = tab[(size_t)stage * n + i];
+            M_HIP(hipMemcpy2DAsync(dst, (size_t)cl.len * 4, dev + (dense ? cl.out : cl.start), (size_t)ld * 4, (size_t)cl.len * 4, H, hipMemcpyDeviceToHost, st));
+            any = true;
+        }
+        if (any) M_HIP(hipStreamSynchronize(st));
+        return Q3_OK;
+    };
+    // ---- SEANet ----
+    M_HIP(hipMemsetAsync(C, 0, (size_t)W0 * 4, st));
+    for (int i = 0; i < n; ++i) M_HIP(hipMemcpyAsync(C + pc[i].start, xs[i], (size_t)ns[i] * 4, hipMemcpyDeviceToDevice, st));
+    M_HIP(m_run_conv(e, e->c0, C, A, Ws[0]));
+    float* x = A; float* o1 = B; float* o2 = C;
+    int dim = F; int64_t maxslot = ((int64_t)maxT + 1) * S;                             // the widest slot, in columns of the current stage
+    for (int s = 0; s < 4; ++s) {
+        const int r = c.ratios[s], W = Ws[s];
+        if ((long long)dim * r > 65535) return q3i_set_err(Q3_INVALID_ARG, "speech encoder: %d folded channels unsupported", dim * r);
+        const MimiClip* ts = tab_d + (size_t)s * n;
+        hipLaunchKernelGGL(k_mimi_elu_p, dim3((unsigned)((maxslot + 255) / 256), dim, n), dim3(256), 0, st, ts, x, o1, W);
+        M_HIP(hipGetLastError());
+        M_HIP(m_run_conv(e, e->res1[s], o1, o2, W, /*ELU*/ 6));
+        M_HIP(m_run_conv(e, e->res2[s], o2, o1, W, 0, x));
+        hipLaunchKernelGGL(k_mimi_fold_p, dim3((unsigned)((maxslot / r + 255) / 256), dim * r, n), dim3(256), 0, st, ts, o1, o2, W, r, 1);
+        M_HIP(hipGetLastError());
+        M_HIP(m_run_conv(e, e->down[s], o2, x, W / r));
+        dim *= 2; maxslot /= r;
+    }
+    hipLaunchKernelGGL(k_mimi_elu_p, dim3((unsigned)((maxslot + 255) / 256), dim, n), dim3(256), 0, st, tab_d + (size_t)4 * n, x, o1, W25);
+    M_HIP(hipGetLastError());
+    float* hs = o2;                                                                     // [H][W25]
+    M_HIP(m_run_conv(e, e->last, o1, hs, W25));
+    Q3I_CHECK(TAP(0, hs, W25, 4, false));
+    // ---- transformer: per-column work over the packed width; RoPE by the position inside the clip, attention inside the clip ----
+    float* nrm = tr; float* q = nrm + (size_t)H * tf; float* k = q + (size_t)H * tf; float* v = k + (size_t)H * tf; float* att = v + (size_t)H * tf;
+    float* ff = att + (size_t)H * tf;
+    const float scale = 1.0f / sqrtf(64.0f);
+    for (auto& Lr : e->layers) {
+        M_HIP(launch_layernorm_c(hs, Lr.ln1w, Lr.ln1b, nrm, H, W25, c.norm_eps, st));
+        M_HIP(m_run_conv(e, Lr.q, nrm, q, W25)); M_HIP(m_run_conv(e, Lr.k, nrm, k, W25)); M_HIP(m_run_conv(e, Lr.v, nrm, v, W25));
+        M_HIP(launch_rope_c_pos(q, k, e->cs, e->sn, pos_d, c.n_heads, 64, W25, st));
+        hipLaunchKernelGGL(k_mimi_attn_p, dim3(W25, c.n_heads), dim3(64), 0, st, q, k, v, att, W25, first_d, c.window, scale);
+        M_HIP(hipGetLastError());
+        M_HIP(m_run_conv(e, Lr.o, att, hs, W25, 0, hs, Lr.sa));
+        M_HIP(launch_layernorm_c(hs, Lr.ln2w, Lr.ln2b, nrm, H, W25, c.norm_eps, st));
+        M_HIP(m_run_conv(e, Lr.f1, nrm, ff, W25, /*GELU*/ 1));
+        M_HIP(m_run_conv(e, Lr.f2, ff, hs, W25, 0, hs, Lr.sm));
+    }
+    Q3I_CHECK(TAP(1, hs, W25, 4, false));
+    // ---- downsample: every slot with its own replicate lead column; the lead outputs are dropped and the guards closed ----
+    float* fd = ff + (size_t)c.inter * tf;                                              // [2H][W12]
+    float* dy = x;                                                                      // [H][W12]
+    hipLaunchKernelGGL(k_mimi_fold_rep_p, dim3((unsigned)((maxT + 1 + 255) / 256), 2 * H, n), dim3(256), 0, st, tab_d + (size_t)4 * n, hs, fd, W25);
+    M_HIP(hipGetLastError());
+    M_HIP(m_run_conv(e, e->dsamp, fd, dy, W12));
+    float* xd = o1;                                                                     // [H][Tsum]
+    hipLaunchKernelGGL(k_mimi_cols_p, dim3((unsigned)((maxT + 255) / 256), H, n), dim3(256), 0, st, tab_d + (size_t)5 * n, dy, W12, xd, Tsum);
+    M_HIP(hipGetLastError());
+    Q3I_CHECK(TAP(2, xd, Tsum, 5, true));
+    // ---- split residual vector quantiser over every clip's frames at once ----
+    float* proj = fd + (size_t)2 * H * tf;
+    for (int g = 0; g < 2; ++g) {
+        const int nl = g ? c.n_q - c.n_sem : c.n_sem, q0 = g ? c.n_sem : 0;
+        if (nl <= 0) continue;
+        M_HIP(m_run_conv(e, e->qproj[g], xd, proj, Tsum));
+        M_HIP(launch_mimi_rvq(proj, Tsum, e->books[g], nl, c.cb_size, c.cb_dim, e->codes_dev, c.n_q, q0, st));
+    }
+    M_HIP(hipGetLastError());
+    M_HIP(hipStreamSynchronize(st));
+    M_HIP(q3_hipMemcpy(codes_host, e->codes_dev, (size_t)Tsum * c.n_q * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+// Encoder12Hz::encode (encoder_12hz.rs:119-144) of n reference-audio objects: codes_host [sum of n_frames][n_q], clip after clip
+extern "C" q3_status q3_mimi_encode_refs(q3_speech_encoder* e, const q3_ref_audio* const* refs, int n, uint32_t* codes_host, int cap_frames,
+                                         int* n_frames, float** taps_host) {
+    if (!e || !refs || !n_frames) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_encode_refs: null argument");
+    if (n < 1 || n > 64) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_encode_refs: %d clips (1 .. 64)", n);
+    for (int i = 0; i < n; ++i)
+        if (!refs[i]) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_encode_refs: clip %d: null entry", i);
+    const int64_t LIMIT = (int64_t)24000 * 120;
+    std::vector<const float*> xs((size_t)n); std::vector<int64_t> ns((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        int dev = 0;
+        xs[i] = q3i_ref_audio_dev(refs[i], &ns[i], &dev);
+        if (dev != e->device)
+            return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_encode_refs: clip %d: reference audio is on device %d, the encoder on device %d", i, dev, e->device);
+    }
+    if (!e->finalized) return q3i_set_err(Q3_INVALID_ARG, "speech encoder not finalized");
+    for (int i = 0; i < n; ++i)
+        if (ns[i] < 1 || ns[i] > LIMIT)
+            return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_encode_refs: clip %d: reference audio of %lld samples unsupported (1 .. 120 s)", i, (long long)ns[i]);
+    std::vector<q3_mimi_pack_clip> pc((size_t)n);
+    int64_t S = 0; int packable = 0, passes = 0;
+    Q3I_CHECK(q3_mimi_pack_plan(&e->cfg, ns.data(), n, LIMIT, pc.data(), &S, &packable, &passes));
+    long long total = 0;
+    for (int i = 0; i < n; ++i) { n_frames[i] = pc[i].frames; total += pc[i].frames; }
+    if (!codes_host) return Q3_OK;
+    if (cap_frames < total) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_encode_refs: codes buffer too small (%d < %lld frames)", cap_frames, total);
+    M_HIP(hipSetDevice(e->device));
+    size_t frame0 = 0;
+    for (int first = 0; first < n;) {
+        int np = 1;
+        while (first + np < n && pc[first + np].pass == pc[first].pass) ++np;
+        uint32_t* codes = codes_host + frame0 * e->cfg.n_q;
+        float** taps = taps_host ? taps_host + (size_t)3 * first : nullptr;
+        // clip by clip where one guard frame does not cover the convs' context, and for a clip whose slot alone exceeds a pass
+        if (!packable || (np == 1 && ((int64_t)pc[first].frames + 1) * S > LIMIT)) {
+            for (int i = first; i < first + np; ++i) {
+                int nf = 0;
+                Q3I_CHECK(mimi_encode_from(e, xs[i], hipMemcpyDeviceToDevice, ns[i], codes, pc[i].frames, &nf, taps ? taps + (size_t)3 * (i - first) : nullptr));
+                codes += (size_t)nf * e->cfg.n_q;
+            }
+        } else {
+            Q3I_CHECK(mimi_encode_packed(e, xs.data() + first, ns.data() + first, pc.data() + first, np, S, codes, taps));
+        }
+        for (int i = first; i < first + np; ++i) frame0 += pc[i].frames;
+        first += np;
+    }
     return Q3_OK;
 }

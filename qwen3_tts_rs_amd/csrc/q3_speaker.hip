@@ -6,7 +6,8 @@
 // f32-equivalent accuracy) — 1x1 convs directly, k > 1 "same" convs as a causal conv over a reflect-padded copy
 // whose first (k-1)·dil output columns are dropped — plus five small kernels: STFT+mel (DFT in f64: MI355X has
 // the FP64 rate to make an FFT pointless at 1024 points), reflect-pad/add, column copy, SE scale+residual, and the
-// attentive-statistics reductions.
+// attentive-statistics reductions. Many clips per call (q3_spk_encode_refs): the same launches once over all clips side by side
+// along the time axis, the five kernels as clip-aware instances (k_spk_*_p) — bit-equal per clip to the clip alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +23,9 @@
 #include "q3_kernels.h"
 
 namespace q3 {
+
+// one clip of a packed pass (the table the packed kernels read): its samples on the device, its mel frames, its first column
+struct SpkClip { const float* x; long long n; int T, col0; };
 
 __device__ __forceinline__ float block_sum(float v, float* sh) {      // 256 threads
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -40,14 +44,15 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
 
 // One workgroup per STFT frame (mel.rs:168-227 stft, 135-166 compute_for_speaker_encoder): reflect-padded,
 // Hann-windowed 1024-point DFT in f64, magnitude sqrt(re² + im² + 1e-9) in f32, mel filterbank, ln(max(., 1e-5)).
-__global__ __launch_bounds__(256) void k_spk_stft_mel(const float* __restrict__ x, long n, int T, const float* __restrict__ win,
-                                                      const double* __restrict__ cs, const double* __restrict__ sn,
-                                                      const float* __restrict__ fb, float* __restrict__ mel, int n_mels) {
+// (frame f of the clip x[0..n) into column f of mel, rows ld apart: the body of k_spk_stft_mel and of its packed instance)
+__device__ __forceinline__ void spk_stft_mel_frame(const float* __restrict__ x, long n, int f, int ld, const float* __restrict__ win,
+                                                   const double* __restrict__ cs, const double* __restrict__ sn,
+                                                   const float* __restrict__ fb, float* __restrict__ mel, int n_mels) {
     constexpr int NF = 1024, HOP = 256, PAD = (NF - HOP) / 2, NB = NF / 2 + 1;
     __shared__ float buf[NF];
     __shared__ float mag[NB + 7];
     __shared__ double tc[NF], ts[NF];
-    const int f = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     for (int j = tid; j < NF; j += 256) {
         const long p = (long)f * HOP + j - PAD;
         long idx = p;
@@ -72,8 +77,13 @@ __global__ __launch_bounds__(256) void k_spk_stft_mel(const float* __restrict__ 
         const float* row = fb + (size_t)m * NB;
         float acc = 0.0f;
         for (int k = 0; k < NB; ++k) acc = add_rn(acc, mul_rn(row[k], mag[k]));
-        mel[(size_t)m * T + f] = logf(fmaxf(acc, 1e-5f));
+        mel[(size_t)m * ld + f] = logf(fmaxf(acc, 1e-5f));
     }
+}
+__global__ __launch_bounds__(256) void k_spk_stft_mel(const float* __restrict__ x, long n, int T, const float* __restrict__ win,
+                                                      const double* __restrict__ cs, const double* __restrict__ sn,
+                                                      const float* __restrict__ fb, float* __restrict__ mel, int n_mels) {
+    spk_stft_mel_frame(x, n, blockIdx.x, T, win, cs, sn, fb, mel, n_mels);
 }
 hipError_t launch_spk_stft_mel(const float* x, long n, int T, const float* win, const double* cs, const double* sn, const float* fb, float* mel,
                                int n_mels, hipStream_t st) {
@@ -135,10 +145,9 @@ hipError_t launch_spk_se_apply(const float* o, const float* g, float* h, int C, 
     return hipGetLastError();
 }
 // attention input of the pooling (speaker.rs:303-316): rows [x ; mean ; std] with std = sqrt(mean((x-mean)²) + 1e-5)
-__global__ __launch_bounds__(256) void k_spk_asp_in(const float* __restrict__ m, float* __restrict__ ain, int C, int T) {
-    __shared__ float sh[4];
-    const int c = blockIdx.x;
-    const float* r = m + (size_t)c * T;
+// (one channel: r = its T columns, the three output rows o_x / o_mean / o_sd: the body of k_spk_asp_in and of its packed instance)
+__device__ __forceinline__ void spk_asp_in_row(const float* __restrict__ r, int T, float* __restrict__ o_x, float* __restrict__ o_mean,
+                                               float* __restrict__ o_sd, float* sh) {
     float a = 0.0f;
     for (int t = threadIdx.x; t < T; t += 256) a += r[t];
     const float mean = block_sum(a, sh) / (float)T;
@@ -146,10 +155,15 @@ __global__ __launch_bounds__(256) void k_spk_asp_in(const float* __restrict__ m,
     for (int t = threadIdx.x; t < T; t += 256) { const float d = r[t] - mean; q += d * d; }
     const float sd = sqrtf(block_sum(q, sh) / (float)T + 1e-5f);
     for (int t = threadIdx.x; t < T; t += 256) {
-        ain[(size_t)c * T + t] = r[t];
-        ain[(size_t)(C + c) * T + t] = mean;
-        ain[(size_t)(2 * C + c) * T + t] = sd;
+        o_x[t] = r[t];
+        o_mean[t] = mean;
+        o_sd[t] = sd;
     }
+}
+__global__ __launch_bounds__(256) void k_spk_asp_in(const float* __restrict__ m, float* __restrict__ ain, int C, int T) {
+    __shared__ float sh[4];
+    const int c = blockIdx.x;
+    spk_asp_in_row(m + (size_t)c * T, T, ain + (size_t)c * T, ain + (size_t)(C + c) * T, ain + (size_t)(2 * C + c) * T, sh);
 }
 hipError_t launch_spk_asp_in(const float* m, float* ain, int C, int T, hipStream_t st) {
     if (C < 1 || T < 1) return hipErrorInvalidValue;
@@ -157,10 +171,9 @@ hipError_t launch_spk_asp_in(const float* m, float* ain, int C, int T, hipStream
     return hipGetLastError();
 }
 // softmax over time of the attention logits, weighted mean and std (speaker.rs:322-342): pooled = [mean ; std]
-__global__ __launch_bounds__(256) void k_spk_asp_pool(const float* __restrict__ aw, const float* __restrict__ m, float* __restrict__ pooled, int C, int T) {
-    __shared__ float sh[4];
-    const int c = blockIdx.x;
-    const float* a = aw + (size_t)c * T; const float* r = m + (size_t)c * T;
+// (one channel: a = its T attention logits, r = its T columns: the body of k_spk_asp_pool and of its packed instance)
+__device__ __forceinline__ void spk_asp_pool_row(const float* __restrict__ a, const float* __restrict__ r, int T, float* __restrict__ o_mean,
+                                                 float* __restrict__ o_sd, float* sh) {
     float mx = -INFINITY;
     for (int t = threadIdx.x; t < T; t += 256) mx = fmaxf(mx, a[t]);
     mx = block_max(mx, sh);
@@ -173,12 +186,79 @@ __global__ __launch_bounds__(256) void k_spk_asp_pool(const float* __restrict__ 
     float wv = 0.0f;
     for (int t = threadIdx.x; t < T; t += 256) { const float d = r[t] - wm; wv += d * d * (expf(a[t] - mx) / s); }
     wv = block_sum(wv, sh);
-    if (threadIdx.x == 0) { pooled[c] = wm; pooled[C + c] = sqrtf(wv + 1e-5f); }
+    if (threadIdx.x == 0) { *o_mean = wm; *o_sd = sqrtf(wv + 1e-5f); }
+}
+__global__ __launch_bounds__(256) void k_spk_asp_pool(const float* __restrict__ aw, const float* __restrict__ m, float* __restrict__ pooled, int C, int T) {
+    __shared__ float sh[4];
+    const int c = blockIdx.x;
+    spk_asp_pool_row(aw + (size_t)c * T, m + (size_t)c * T, T, pooled + c, pooled + C + c, sh);
 }
 hipError_t launch_spk_asp_pool(const float* aw, const float* m, float* pooled, int C, int T, hipStream_t st) {
     if (C < 1 || T < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_spk_asp_pool, dim3(C), dim3(256), 0, st, aw, m, pooled, C, T);
     return hipGetLastError();
+}
+
+// ---- packed instances (q3_spk_encode_refs): n clips side by side along the time axis of the [C][W] tensors, clip i at
+// columns [col0, col0 + T), W = sum of T. Each kernel is its single-clip instance with a clip index in the grid: the clip's own
+// columns, reflections and reductions, in the same order, so a clip's bits do not depend on its neighbours. Per-clip scalars
+// (means, gates, pooled statistics) are [C][n] tensors, the clip's in column i.
+__global__ __launch_bounds__(256) void k_spk_stft_mel_p(const SpkClip* __restrict__ tab, int W, const float* __restrict__ win,
+                                                        const double* __restrict__ cs, const double* __restrict__ sn,
+                                                        const float* __restrict__ fb, float* __restrict__ mel, int n_mels) {
+    const SpkClip c = tab[blockIdx.y];
+    if ((int)blockIdx.x >= c.T) return;                               // (the whole workgroup: no barrier is left waiting)
+    spk_stft_mel_frame(c.x, (long)c.n, blockIdx.x, W, win, cs, sn, fb, mel + c.col0, n_mels);
+}
+// the padded copies lie side by side as well: clip i at columns [col0 + i·tot, col0 + i·tot + T + tot) of out [C][W + n·tot]
+__global__ __launch_bounds__(256) void k_spk_pad_p(const SpkClip* __restrict__ tab, const float* __restrict__ a, const float* __restrict__ b,
+                                                   float* __restrict__ out, int W, int Wp, int pl, int tot) {
+    const SpkClip cl = tab[blockIdx.z];
+    const int c = blockIdx.y, tp = blockIdx.x * 256 + threadIdx.x, T = cl.T;
+    if (tp >= T + tot) return;
+    int r = tp - pl;
+    if (r < 0) r = -r; else if (r >= T) r = 2 * T - 2 - r;
+    float v = a[(size_t)c * W + cl.col0 + r];
+    if (b) v = v + b[(size_t)c * W + cl.col0 + r];
+    out[(size_t)c * Wp + cl.col0 + (size_t)blockIdx.z * tot + tp] = v;
+}
+// dst[c][col0 + t] = src[c][col0 + i·tot + tot + t]: the clip's first tot output columns — the only ones that can see the previous
+// clip's tail — are dropped
+__global__ __launch_bounds__(256) void k_spk_cols_p(const SpkClip* __restrict__ tab, const float* __restrict__ src, int Wp, int tot,
+                                                    float* __restrict__ dst, int W) {
+    const SpkClip cl = tab[blockIdx.z];
+    const int c = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+    if (t < cl.T) dst[(size_t)c * W + cl.col0 + t] = src[(size_t)c * Wp + cl.col0 + (size_t)(blockIdx.z + 1) * tot + t];
+}
+__global__ __launch_bounds__(256) void k_spk_mean_p(const SpkClip* __restrict__ tab, const float* __restrict__ x, int W, float* __restrict__ mean) {
+    __shared__ float sh[4];
+    const SpkClip cl = tab[blockIdx.y];
+    const int T = cl.T;
+    const float* r = x + (size_t)blockIdx.x * W + cl.col0;
+    float a = 0.0f;
+    for (int t = threadIdx.x; t < T; t += 256) a += r[t];
+    a = block_sum(a, sh);
+    if (threadIdx.x == 0) mean[(size_t)blockIdx.x * gridDim.y + blockIdx.y] = a / (float)T;
+}
+__global__ __launch_bounds__(256) void k_spk_se_apply_p(const SpkClip* __restrict__ tab, const float* __restrict__ o, const float* __restrict__ g,
+                                                        float* __restrict__ h, int W) {
+    const SpkClip cl = tab[blockIdx.z];
+    const int c = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+    if (t < cl.T) { const size_t e = (size_t)c * W + cl.col0 + t; h[e] = add_rn(mul_rn(o[e], g[(size_t)c * gridDim.z + blockIdx.z]), h[e]); }
+}
+__global__ __launch_bounds__(256) void k_spk_asp_in_p(const SpkClip* __restrict__ tab, const float* __restrict__ m, float* __restrict__ ain, int C, int W) {
+    __shared__ float sh[4];
+    const SpkClip cl = tab[blockIdx.y];
+    const int c = blockIdx.x;
+    spk_asp_in_row(m + (size_t)c * W + cl.col0, cl.T, ain + (size_t)c * W + cl.col0, ain + (size_t)(C + c) * W + cl.col0,
+                   ain + (size_t)(2 * C + c) * W + cl.col0, sh);
+}
+__global__ __launch_bounds__(256) void k_spk_asp_pool_p(const SpkClip* __restrict__ tab, const float* __restrict__ aw, const float* __restrict__ m,
+                                                        float* __restrict__ pooled, int C, int W) {
+    __shared__ float sh[4];
+    const SpkClip cl = tab[blockIdx.y];
+    const int c = blockIdx.x, n = gridDim.y, i = blockIdx.y;
+    spk_asp_pool_row(aw + (size_t)c * W + cl.col0, m + (size_t)c * W + cl.col0, cl.T, pooled + (size_t)c * n + i, pooled + (size_t)(C + c) * n + i, sh);
 }
 
 }  // namespace q3
@@ -616,4 +696,183 @@ extern "C" q3_status q3_spk_encode_ref(q3_speaker_encoder* e, const q3_ref_audio
     const size_t xs = ((size_t)n + 63) & ~(size_t)63;
     Q3I_CHECK(spk_reserve(e, xs + spk_ws_floats(e, T)));            // q3_spk_encode's workspace, its sample region unused
     return spk_encode_dev(e, x_d, n, T, out_host);
+}
+
+// ---- many clips in one packed pass of the encoder ----
+namespace {
+struct SpkPass { const SpkClip* tab_d; const SpkClip* tab; int n, W, maxT; };      // table on the device / on the host, clips, packed width
+}
+
+// spk_same_conv over the packed width: every clip reflect-padded by itself, one causal conv over all padded copies
+static q3_status spk_same_conv_p(q3_speaker_encoder* e, const SpkPass& ps, const SpkConv& cv, const float* x, const float* x2, float* y, int act,
+                                 float* pad_buf, float* tmp_buf) {
+    ConvArgs a{};
+    a.w = cv.w; a.b = cv.b; a.cin = cv.cin; a.cout = cv.cout; a.k = cv.k; a.dil = cv.dil; a.act = act; a.wpk = cv.wpk;
+    const int tot = cv.dil * (cv.k - 1);
+    if (tot == 0 && !x2) {
+        a.x = x; a.y = y; a.L = ps.W;
+        SPK_HIP(launch_conv1d(a, e->st));
+        return Q3_OK;
+    }
+    const int pl = tot / 2, Wp = ps.W + ps.n * tot;
+    hipLaunchKernelGGL(k_spk_pad_p, dim3((ps.maxT + tot + 255) / 256, cv.cin, ps.n), dim3(256), 0, e->st, ps.tab_d, x, x2, pad_buf, ps.W, Wp, pl, tot);
+    SPK_HIP(hipGetLastError());
+    a.x = pad_buf; a.L = Wp;
+    if (tot == 0) {
+        a.y = y;
+        SPK_HIP(launch_conv1d(a, e->st));
+        return Q3_OK;
+    }
+    a.y = tmp_buf;
+    SPK_HIP(launch_conv1d(a, e->st));
+    hipLaunchKernelGGL(k_spk_cols_p, dim3((ps.maxT + 255) / 256, cv.cout, ps.n), dim3(256), 0, e->st, ps.tab_d, tmp_buf, Wp, tot, y, ps.W);
+    SPK_HIP(hipGetLastError());
+    return Q3_OK;
+}
+
+// spk_forward_dev for a pass: mel_d [mel_dim][W] -> out_d [enc_dim][n]; taps_host: NULL or 6 pointers per clip of the pass
+static q3_status spk_forward_packed(q3_speaker_encoder* e, const SpkPass& ps, const float* mel_d, float* out_d, float* base, float** taps_host) {
+    const q3_spk_config& c = e->cfg;
+    const int C = c.channels[0], C4 = c.channels[4], mfa_in = c.channels[1] + c.channels[2] + c.channels[3];
+    const int chn = C / c.res2net_scale, A = c.attention_channels, n = ps.n, W = ps.W;
+    int maxtot = 0;
+    for (int i = 0; i < 5; ++i) maxtot = std::max(maxtot, c.dilations[i] * (c.kernel_sizes[i] - 1));
+    const int max_cin_pad = std::max(std::max(c.mel_dim, chn), c.kernel_sizes[4] > 1 ? mfa_in : 0);
+    const int max_cout_pad = std::max(C, c.kernel_sizes[4] > 1 ? C4 : 0);
+    const size_t Wp = (size_t)W + (size_t)n * maxtot;
+    float* p = base;
+    auto take = [&](size_t k) { float* r = p; p += (k + 63) & ~(size_t)63; return r; };
+    float* pad_buf = take((size_t)max_cin_pad * Wp);
+    float* tmp_buf = take((size_t)max_cout_pad * Wp);
+    float* h = take((size_t)C * W); float* o1 = take((size_t)C * W); float* o2 = take((size_t)C * W);
+    float* cat = take((size_t)mfa_in * W); float* m = take((size_t)C4 * W); float* ain = take((size_t)3 * C4 * W);
+    float* at = take((size_t)A * W); float* aw = take((size_t)C4 * W);
+    float* sm = take((size_t)C * n); float* s1 = take((size_t)c.se_channels * n); float* g = take((size_t)C * n); float* pooled = take((size_t)2 * C4 * n);
+    // tap `id` of every clip: `rows` rows of src (row stride ld floats), the clip's T columns from its first one — or, of a
+    // [C][n] tensor, the clip's one column
+    auto tap = [&](int id, const float* src, int rows, int ld, bool per_clip_column) -> q3_status {
+        if (!taps_host) return Q3_OK;
+        bool any = false;
+        for (int i = 0; i < n; ++i) {
+            float* dst = taps_host[(size_t)6 * i + id];
+            if (!dst) continue;
+            const int width = per_clip_column ? 1 : ps.tab[i].T, col = per_clip_column ? i : ps.tab[i].col0;
+            SPK_HIP(hipMemcpy2DAsync(dst, (size_t)width * 4, src + col, (size_t)ld * 4, (size_t)width * 4, rows, hipMemcpyDeviceToHost, e->st));
+            any = true;
+        }
+        if (any) SPK_HIP(hipStreamSynchronize(e->st));
+        return Q3_OK;
+    };
+    const unsigned col_blocks = (unsigned)(ps.maxT + 255) / 256;
+    Q3I_CHECK(spk_same_conv_p(e, ps, e->c0, mel_d, nullptr, h, 3, pad_buf, tmp_buf));
+    Q3I_CHECK(tap(0, h, C, W, false));
+    int cat_off = 0;
+    for (int bi = 0; bi < 3; ++bi) {
+        const SpkBlock& b = e->blk[bi];
+        Q3I_CHECK(spk_same_conv_p(e, ps, b.tdnn1, h, nullptr, o1, 3, pad_buf, tmp_buf));
+        SPK_HIP(hipMemcpyAsync(o2, o1, (size_t)chn * W * 4, hipMemcpyDeviceToDevice, e->st));
+        for (int i = 0; i < (int)b.res.size(); ++i) {
+            const float* chunk = o1 + (size_t)(i + 1) * chn * W;                                         // the packed width is the row stride
+            const float* prev = i == 0 ? nullptr : o2 + (size_t)i * chn * W;
+            Q3I_CHECK(spk_same_conv_p(e, ps, b.res[i], chunk, prev, o2 + (size_t)(i + 1) * chn * W, 3, pad_buf, tmp_buf));
+        }
+        Q3I_CHECK(spk_same_conv_p(e, ps, b.tdnn2, o2, nullptr, o1, 3, pad_buf, tmp_buf));
+        hipLaunchKernelGGL(k_spk_mean_p, dim3(C, n), dim3(256), 0, e->st, ps.tab_d, o1, W, sm);
+        SPK_HIP(hipGetLastError());
+        // the two SE convs over [C][n]: one column per clip instead of one L = 1 launch per clip
+        ConvArgs a{};
+        a.w = b.se1.w; a.b = b.se1.b; a.cin = b.se1.cin; a.cout = b.se1.cout; a.k = 1; a.dil = 1; a.act = 3; a.wpk = b.se1.wpk; a.x = sm; a.y = s1; a.L = n;
+        SPK_HIP(launch_conv1d(a, e->st));
+        a.w = b.se2.w; a.b = b.se2.b; a.cin = b.se2.cin; a.cout = b.se2.cout; a.act = 5; a.wpk = b.se2.wpk; a.x = s1; a.y = g;
+        SPK_HIP(launch_conv1d(a, e->st));
+        hipLaunchKernelGGL(k_spk_se_apply_p, dim3(col_blocks, C, n), dim3(256), 0, e->st, ps.tab_d, o1, g, h, W);
+        SPK_HIP(hipGetLastError());
+        SPK_HIP(hipMemcpyAsync(cat + (size_t)cat_off * W, h, (size_t)C * W * 4, hipMemcpyDeviceToDevice, e->st));
+        cat_off += C;
+        Q3I_CHECK(tap(1 + bi, h, C, W, false));
+    }
+    Q3I_CHECK(spk_same_conv_p(e, ps, e->mfa, cat, nullptr, m, 3, pad_buf, tmp_buf));
+    Q3I_CHECK(tap(4, m, C4, W, false));
+    hipLaunchKernelGGL(k_spk_asp_in_p, dim3(C4, n), dim3(256), 0, e->st, ps.tab_d, m, ain, C4, W);
+    SPK_HIP(hipGetLastError());
+    Q3I_CHECK(spk_same_conv_p(e, ps, e->asp_tdnn, ain, nullptr, at, 4, pad_buf, tmp_buf));
+    Q3I_CHECK(spk_same_conv_p(e, ps, e->asp_conv, at, nullptr, aw, 0, pad_buf, tmp_buf));
+    hipLaunchKernelGGL(k_spk_asp_pool_p, dim3(C4, n), dim3(256), 0, e->st, ps.tab_d, aw, m, pooled, C4, W);
+    SPK_HIP(hipGetLastError());
+    Q3I_CHECK(tap(5, pooled, 2 * C4, n, true));
+    ConvArgs a{};
+    a.w = e->fc.w; a.b = e->fc.b; a.cin = e->fc.cin; a.cout = e->fc.cout; a.k = 1; a.dil = 1; a.act = 0; a.wpk = e->fc.wpk; a.x = pooled; a.y = out_d; a.L = n;
+    SPK_HIP(launch_conv1d(a, e->st));
+    SPK_HIP(hipGetLastError());
+    return Q3_OK;
+}
+
+static size_t spk_ws_floats_p(const q3_speaker_encoder* e, size_t W, int n) {
+    const q3_spk_config& c = e->cfg;
+    const int C = c.channels[0], C4 = c.channels[4], mfa_in = c.channels[1] + c.channels[2] + c.channels[3];
+    int maxtot = 0;
+    for (int i = 0; i < 5; ++i) maxtot = std::max(maxtot, c.dilations[i] * (c.kernel_sizes[i] - 1));
+    const size_t Wp = W + (size_t)n * maxtot;
+    size_t k = (size_t)std::max(std::max(c.mel_dim, C), mfa_in) * Wp + (size_t)std::max(C, C4) * Wp;
+    k += (size_t)3 * C * W + (size_t)mfa_in * W + (size_t)C4 * W * 2 + (size_t)3 * C4 * W + (size_t)c.attention_channels * W;
+    k += ((size_t)2 * C + c.se_channels + 2 * C4 + c.enc_dim) * n + (size_t)c.mel_dim * W + (sizeof(SpkClip) * (size_t)n + 3) / 4;
+    return k + 64 * 26;
+}
+
+// SpeakerEncoder::encode (speaker.rs:431-438) of n reference-audio objects in one pass of the encoder (several, when the clips
+// together are longer than one call's 120 s): out_host [n][enc_dim]
+extern "C" q3_status q3_spk_encode_refs(q3_speaker_encoder* e, const q3_ref_audio* const* refs, int n, float* out_host, float** taps_host) {
+    if (!e || !refs || !out_host) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_refs: null argument");
+    if (n < 1 || n > 64) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_refs: %d clips (1 .. 64)", n);
+    for (int i = 0; i < n; ++i)
+        if (!refs[i]) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_refs: clip %d: null entry", i);
+    std::vector<SpkClip> tab((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        int64_t ns = 0; int dev = 0;
+        tab[i].x = q3i_ref_audio_dev(refs[i], &ns, &dev); tab[i].n = ns;
+        if (dev != e->device)
+            return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_refs: clip %d: reference audio is on device %d, the encoder on device %d", i, dev, e->device);
+    }
+    if (!e->finalized) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_refs: encoder not finalized");
+    if ((uint32_t)e->cfg.sample_rate != 24000u)
+        return q3i_set_err(Q3_UNSUPPORTED, "speaker encoder expects %d Hz audio, got 24000 Hz: resample first (the reference does, lib.rs:1156-1166)", e->cfg.sample_rate);
+    const long long LIMIT = 24000LL * 120;
+    int maxside = 0;
+    for (int i = 0; i < 5; ++i) maxside = std::max(maxside, (e->cfg.dilations[i] * (e->cfg.kernel_sizes[i] - 1) + 1) / 2);
+    for (int i = 0; i < n; ++i) {
+        if (tab[i].n < 1 || tab[i].n > LIMIT)
+            return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_refs: clip %d: reference audio of %lld samples unsupported (1 .. 120 s)", i, tab[i].n);
+        tab[i].T = q3_spk_mel_frames(tab[i].n);
+        if (tab[i].T <= maxside)
+            return q3i_set_err(Q3_INVALID_ARG, "q3_spk_encode_refs: clip %d: reference audio too short: %d mel frames, reflect padding needs more than %d",
+                               i, tab[i].T, maxside);
+    }
+    SPK_HIP(hipSetDevice(e->device));
+    const int enc = e->cfg.enc_dim, mel = e->cfg.mel_dim;
+    std::vector<float> col;
+    for (int first = 0; first < n;) {
+        // a pass: consecutive clips of at most 120 s together, so it needs no more workspace than one call can need today
+        int np = 0, W = 0, maxT = 0; long long sum = 0;
+        while (first + np < n && (np == 0 || sum + tab[first + np].n <= LIMIT)) {
+            SpkClip& c = tab[first + np];
+            c.col0 = W; W += c.T; maxT = std::max(maxT, c.T); sum += c.n; ++np;
+        }
+        Q3I_CHECK(spk_reserve(e, spk_ws_floats_p(e, (size_t)W, np)));
+        SpkClip* tab_d = (SpkClip*)e->ws;
+        float* mel_d = e->ws + (((sizeof(SpkClip) * (size_t)np + 3) / 4 + 63) & ~(size_t)63);
+        float* out_d = mel_d + (((size_t)mel * W + 63) & ~(size_t)63);
+        float* base = out_d + (((size_t)enc * np + 63) & ~(size_t)63);
+        SPK_HIP(hipMemcpyAsync(tab_d, tab.data() + first, sizeof(SpkClip) * (size_t)np, hipMemcpyHostToDevice, e->st));
+        const SpkPass ps{tab_d, tab.data() + first, np, W, maxT};
+        hipLaunchKernelGGL(k_spk_stft_mel_p, dim3(maxT, np), dim3(256), 0, e->st, tab_d, W, e->win, e->dft_cs, e->dft_sn, e->fb, mel_d, mel);
+        SPK_HIP(hipGetLastError());
+        Q3I_CHECK(spk_forward_packed(e, ps, mel_d, out_d, base, taps_host ? taps_host + (size_t)6 * first : nullptr));
+        col.resize((size_t)enc * np);
+        SPK_HIP(hipMemcpyAsync(col.data(), out_d, col.size() * 4, hipMemcpyDeviceToHost, e->st));
+        SPK_HIP(hipStreamSynchronize(e->st));
+        for (int i = 0; i < np; ++i)
+            for (int d = 0; d < enc; ++d) out_host[(size_t)(first + i) * enc + d] = col[(size_t)d * np + i];
+        first += np;
+    }
+    return Q3_OK;
 }

@@ -138,6 +138,20 @@ class SpeakerEncoder:
         check(lib.q3_spk_encode_ref(self._h, ref._h, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def encode_refs(self, refs, taps: Optional[List[Optional[List[Optional[np.ndarray]]]]] = None) -> np.ndarray:
+        """encode_ref() of every RefAudio of `refs` in one packed pass of the encoder (q3_spk_encode_refs):
+        [n, enc_dim], row i bit-equal to that clip's own encode_ref. `taps`: per clip None or six arrays / Nones (forward()'s)."""
+        n = len(refs)
+        hs = (ctypes.c_void_p * max(1, n))(*[r._h.value if r is not None else None for r in refs])
+        out = np.empty((n, self.config.enc_dim), np.float32)
+        tp = None
+        if taps is not None:
+            flat = [t for clip in taps for t in (clip if clip is not None else [None] * 6)]
+            assert len(flat) == 6 * n
+            tp = (ctypes.c_void_p * (6 * n))(*[t.ctypes.data_as(ctypes.c_void_p) if t is not None else None for t in flat])
+        check(lib.q3_spk_encode_refs(self._h, hs, n, out.ctypes.data_as(ctypes.c_void_p), tp))
+        return out
+
     def tap_shapes(self, T: int) -> List[Tuple[int, ...]]:
         c = self.config
         return [(c.enc_channels[0], T), (c.enc_channels[1], T), (c.enc_channels[2], T), (c.enc_channels[3], T), (c.enc_channels[4], T), (2 * c.enc_channels[4],)]

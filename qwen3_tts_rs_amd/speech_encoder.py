@@ -127,6 +127,50 @@ class SpeechEncoder:
         check(lib.q3_mimi_encode_ref(self._h, ref._h, codes.ctypes.data_as(ctypes.c_void_p), codes.shape[0], ctypes.byref(nf), tp))
         return codes
 
+    def pack_plan(self, n_samples: List[int], max_pass_samples: int = 24000 * 120) -> "PackPlan":
+        return pack_plan(self.config, n_samples, max_pass_samples)
+
+    def encode_refs(self, refs, taps: Optional[List[Optional[List[Optional[np.ndarray]]]]] = None) -> List[np.ndarray]:
+        """encode_ref() of every RefAudio of `refs` in one packed pass of the encoder (q3_mimi_encode_refs): one
+        [T_i, n_q] array per clip, each bit-equal to that clip's own encode_ref. `taps`: per clip None or three arrays / Nones."""
+        n = len(refs)
+        hs = (ctypes.c_void_p * max(1, n))(*[r._h.value if r is not None else None for r in refs])
+        nf = (ctypes.c_int * max(1, n))()
+        check(lib.q3_mimi_encode_refs(self._h, hs, n, None, 0, nf, None))
+        total = sum(nf[:n])
+        codes = np.zeros((total, self.config.n_q), np.uint32)
+        tp = None
+        if taps is not None:
+            flat = [t for clip in taps for t in (clip if clip is not None else [None] * 3)]
+            assert len(flat) == 3 * n
+            tp = (ctypes.c_void_p * (3 * n))(*[t.ctypes.data_as(ctypes.c_void_p) if t is not None else None for t in flat])
+        check(lib.q3_mimi_encode_refs(self._h, hs, n, codes.ctypes.data_as(ctypes.c_void_p), total, nf, tp))
+        ends = np.cumsum(nf[:n])
+        return [codes[e - t:e].copy() for e, t in zip(ends, nf[:n])]
+
+
+@dataclass
+class PackPlan:                    # q3_mimi_pack_plan
+    frames: List[int]              # q3_mimi_frames per clip
+    starts: List[int]              # first sample of the clip's slot inside its pass
+    passes: List[int]              # pass index per clip
+    frame_samples: int             # S = 2 * prod(ratios)
+    packable: bool
+    n_passes: int
+
+
+def pack_plan(config: SpeechEncoderConfig, n_samples: List[int], max_pass_samples: int = 24000 * 120) -> PackPlan:
+    """Where each clip's slot lies in the packed passes of SpeechEncoder.encode_refs (host arithmetic only)."""
+    from ._lib import CMimiPackClip
+    n = len(n_samples)
+    c = config.to_c()
+    ns = (ctypes.c_int64 * max(1, n))(*n_samples)
+    clips = (CMimiPackClip * max(1, n))()
+    S = ctypes.c_int64(); ok = ctypes.c_int(); np_ = ctypes.c_int()
+    check(lib.q3_mimi_pack_plan(ctypes.byref(c), ns, n, max_pass_samples, clips, ctypes.byref(S), ctypes.byref(ok), ctypes.byref(np_)))
+    return PackPlan([clips[i].frames for i in range(n)], [clips[i].start for i in range(n)], [clips[i].pass_ for i in range(n)],
+                    S.value, bool(ok.value), np_.value)
+
 
 def synthetic_speech_checkpoint(enc: SpeechEncoder, seed: int) -> Iterator[Tuple[str, np.ndarray]]:
     """Conv / linear weights ~ 1.4 / sqrt(fan_in) (activations stay O(1) through ELU / LayerNorm), LayerNorm weights near 1,
