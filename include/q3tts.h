@@ -618,7 +618,16 @@ int q3_attn_prefill_path(int nh, int nkv, int use_planes, int halves, int* path)
  * launch_attn_prefill, launch_attn_merge for two halves. qkv [n_seq * rps][ld_qkv]; q_norm_w / k_norm_w [128]; rope_cos / rope_sin
  * [max_seq][64]; kcache / vcache [n_seq][nkv][max_seq][128] in and out; out [n_seq * rps][ld_out] is uploaded whole and copied
  * back whole. kernel -1 = the engine's pick (use_planes != 0: with K/V planes), 0..3 as q3_attn_prefill_path; halves 1 or 2.
- * path (optional) [2] = kernel, halves that ran. A refused launch returns Q3_UNSUPPORTED and leaves the caches and out alone. */
+ * path (optional) [2] = kernel, halves that ran. A refused launch returns Q3_UNSUPPORTED and leaves the caches and out alone.
+ * The trailing fields select the cache layout; all zero = the contiguous form above. layout 1 = f32 pages (what prefill_gemm runs
+ * on by default): kcache / vcache stay the LOGICAL cache of the selected layer, and the entry builds n_slabs (1, 2) slabs of
+ * KvPool's geometry for n_layers (1..4) layers as q3_attn_step_ex does — pattern-filled, the cache scattered into the pages
+ * page_slots [n_seq][ceil(max_seq / 128)] names under each page's row rotation, the page table between two slabs, table entries
+ * beyond a row's pages naming its first — runs the same launches on layer `layer`, gathers the cache back and reports stray /
+ * rot_used [n_seq][pages][nkv] as there. max_seq <= 64 * 128. Slots are 0 .. 32 n_slabs - 1 and distinct, except that page i of
+ * several sequences may name ONE slot (a shared prefix page) when (i + 1) * 128 <= base_pos and those sequences' cache rows of
+ * the page are bit-equal. layout 2 (bf16 pages) is Q3_UNSUPPORTED: prefill never runs on them. Every argument, the slots and the
+ * sharing rule included, is checked before a device is touched (Q3_INVALID_ARG). */
 typedef struct q3_attn_prefill_ex_args {
     int n_seq, rps, base_pos, nh, nkv, max_seq, ld_qkv, ld_out;
     int kernel, halves, use_planes;
@@ -627,8 +636,33 @@ typedef struct q3_attn_prefill_ex_args {
     const float* qkv; const float* q_norm_w; const float* k_norm_w;
     const float* rope_cos; const float* rope_sin;
     float* kcache; float* vcache; float* out;
+    int layout, n_layers, layer, n_slabs;
+    const int* page_slots; int* rot_used; long long* stray;
 } q3_attn_prefill_ex_args;
 q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_args* args);
+/* Test API: the kernels that build the prompt rows, exactly ONE launch over host arrays (tests/test_gpu_prompt_rows.py). Every
+ * destination (out; trail_len / text_ready / limit) is a host buffer with 64 guard elements in front of and behind its payload; it
+ * is uploaded whole and copied back whole, and the kernel is given the payload. What a kernel could not address is Q3_INVALID_ARG
+ * before a device is touched. cols 1..65536, n 1..65535.
+ * mode 0 = launch_gather_rows_bf16: out [n][cols] = f32(table [n_table][cols] bf16 row ids[r]); ids < n_table.
+ * mode 1 = launch_assemble_rows: out [n][cols] from src = rows [n_rows][cols], text_row / codec_id [n], table = codec_emb
+ *   [n_table][cols], xvec [cols] (needed by a codec_id of -2), ref_codes [n_ref][16] and cp_embs [15][cp_vocab][cols] bf16 (needed by
+ *   a codec_id <= -3: frame -3 - codec_id < n_ref, its code 0 < n_table, codes 1..15 < cp_vocab). text_row < n_rows (negative: none);
+ *   codec_id < n_table.
+ * mode 2 = launch_copy_rows: out [n][ldd] <- src [n][lds], cols <= lds, ldd (the payload is n * ldd floats).
+ * mode 3 = launch_scatter_rows: out = rows [n_rows][cols], row dst_row[r] <- src [n][cols] row r; dst_row < n_rows, the non-negative
+ *   ones distinct (negative: skipped).
+ * mode 4 = launch_publish_text: ent [n][4] = (b, trail_len, text_ready, limit) into trail_len / text_ready / limit [n_rows]; b inside
+ *   [0, n_rows) and distinct. */
+typedef struct q3_prompt_rows_ex_args {
+    int mode, n, cols, n_table, n_rows, n_ref, cp_vocab, lds, ldd, reserved;
+    const uint16_t* table; const uint32_t* ids; const float* src;
+    const int* text_row; const int* codec_id; const float* xvec;
+    const uint32_t* ref_codes; const uint16_t* cp_embs;
+    const int* dst_row; const int* ent;
+    float* out; int* trail_len; int* text_ready; int* limit;
+} q3_prompt_rows_ex_args;
+q3_status q3_prompt_rows_ex(int device, const q3_prompt_rows_ex_args* args);
 /* Test API: which kernel launch_attn_c (the codec transformer's whole-utterance attention) runs: kernel -1 = the engine's pick
  * (k_attn_c_mfma unless the Q3_ATTN_C_VALU aid is set), 0 = k_attn_c (VALU), 1 = k_attn_c_mfma. Returns the kernel, or -1 for what
  * the launcher refuses (hd != 64, any other kernel value). No GPU needed. */

@@ -90,7 +90,15 @@ class CGemmEx(ctypes.Structure):         # q3_gemm_ex_args
 class CAttnPrefillEx(ctypes.Structure):  # q3_attn_prefill_ex_args
     _fields_ = [(n, ctypes.c_int32) for n in ("n_seq", "rps", "base_pos", "nh", "nkv", "max_seq", "ld_qkv", "ld_out", "kernel", "halves",
                                               "use_planes")] + [("eps", ctypes.c_float), ("path", ctypes.POINTER(ctypes.c_int32))] + \
-               [(n, ctypes.c_void_p) for n in ("qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache", "out")]
+               [(n, ctypes.c_void_p) for n in ("qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache", "out")] + \
+               [(n, ctypes.c_int32) for n in ("layout", "n_layers", "layer", "n_slabs")] + \
+               [(n, ctypes.c_void_p) for n in ("page_slots", "rot_used", "stray")]
+
+
+class CPromptRowsEx(ctypes.Structure):   # q3_prompt_rows_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("mode", "n", "cols", "n_table", "n_rows", "n_ref", "cp_vocab", "lds", "ldd", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("table", "ids", "src", "text_row", "codec_id", "xvec", "ref_codes", "cp_embs", "dst_row", "ent", "out",
+                                               "trail_len", "text_ready", "limit")]
 
 
 class CAttnCEx(ctypes.Structure):        # q3_attn_c_ex_args
@@ -304,6 +312,7 @@ SYMBOLS = {
     "q3_gemm_ex": (c_int, [c_int, P(CGemmEx)]),
     "q3_attn_prefill_path": (c_int, [c_int] * 4 + [P(ctypes.c_int32)]),
     "q3_attn_prefill_ex": (c_int, [c_int, P(CAttnPrefillEx)]),
+    "q3_prompt_rows_ex": (c_int, [c_int, P(CPromptRowsEx)]),
     "q3_attn_c_path": (c_int, [c_int, c_int]),
     "q3_attn_c_ex": (c_int, [c_int, P(CAttnCEx)]),
     "q3_rope_c_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),

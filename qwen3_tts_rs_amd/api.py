@@ -2150,11 +2150,14 @@ def attn_prefill_path(nh: int, nkv: int, use_planes: bool, halves: int = 1):
 
 def attn_prefill_ex(qkv: np.ndarray, n_seq: int, base_pos: int, q_norm_w: np.ndarray, k_norm_w: np.ndarray, eps: float, rope_cos: np.ndarray,
                     rope_sin: np.ndarray, kcache: np.ndarray, vcache: np.ndarray, nh: int, nkv: int, *, kernel: int = -1, halves: int = 1,
-                    use_planes: bool = False, out: Optional[np.ndarray] = None, device: int = 0):
-    """q3_attn_prefill_ex: one prefill attention step over a contiguous cache [n_seq][nkv][max_seq][128] (parity tests): qkv
+                    use_planes: bool = False, out: Optional[np.ndarray] = None, layout: int = 0, n_layers: int = 1, layer: int = 0,
+                    n_slabs: int = 1, page_slots=None, device: int = 0):
+    """q3_attn_prefill_ex: one prefill attention step over the LOGICAL cache [n_seq][nkv][max_seq][128] (parity tests): qkv
     [n_seq * rps][ld_qkv] are the rows of n_seq sequences at positions base_pos .. base_pos + rps - 1. kernel -1 = the engine's pick
     (with K/V planes when use_planes), 0 VALU / 1 gen2 MFMA / 2 transposed f32 MFMA / 3 bf16x3. out ([rows][ld_out] f32) is uploaded,
-    written in place and returned whole. Returns (out, kcache, vcache, (kernel, halves)) — the caches are copies."""
+    written in place and returned whole. layout 0 (contiguous): returns (out, kcache, vcache, (kernel, halves)) — the caches are
+    copies. layout 1 (f32 pages; page_slots [n_seq][ceil(max_seq / 128)], n_layers, layer, n_slabs as include/q3tts.h describes):
+    returns (out, kcache, vcache, (kernel, halves), info) with info = dict(stray, stray_at, rot_used [n_seq][pages][nkv])."""
     qkv = np.ascontiguousarray(qkv, dtype=np.float32); rows = qkv.shape[0]
     assert qkv.ndim == 2 and rows % n_seq == 0
     rps = rows // n_seq
@@ -2175,8 +2178,79 @@ def attn_prefill_ex(qkv: np.ndarray, n_seq: int, base_pos: int, q_norm_w: np.nda
     ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
     a.qkv, a.q_norm_w, a.k_norm_w, a.rope_cos, a.rope_sin = ptr(qkv), ptr(qw), ptr(kw), ptr(rc), ptr(rs)
     a.kcache, a.vcache, a.out = ptr(kc), ptr(vc), ptr(out)
+    if layout == 0:
+        check(lib.q3_attn_prefill_ex(device, ctypes.byref(a)))
+        return out, kc, vc, tuple(path)
+    n_pg = (max_seq + 127) // 128
+    stray = np.array([0, -1], dtype=np.int64)
+    rot = np.full((n_seq, n_pg, nkv), -1, dtype=np.int32)
+    a.layout, a.n_layers, a.layer, a.n_slabs, a.stray, a.rot_used = layout, n_layers, layer, n_slabs, ptr(stray), ptr(rot)
+    if page_slots is not None:
+        page_slots = np.ascontiguousarray(page_slots, dtype=np.int32); assert page_slots.shape == (n_seq, n_pg)
+        a.page_slots = ptr(page_slots)
     check(lib.q3_attn_prefill_ex(device, ctypes.byref(a)))
-    return out, kc, vc, tuple(path)
+    return out, kc, vc, tuple(path), dict(stray=int(stray[0]), stray_at=int(stray[1]), rot_used=rot)
+
+
+ROWS_GATHER, ROWS_ASSEMBLE, ROWS_COPY, ROWS_SCATTER, ROWS_PUBLISH = 0, 1, 2, 3, 4
+ROWS_GUARD = 64
+
+
+def prompt_rows_ex(mode: int, *, out: Optional[np.ndarray] = None, cols: int = 0, table: Optional[np.ndarray] = None, ids=None,
+                   src: Optional[np.ndarray] = None, text_row=None, codec_id=None, xvec: Optional[np.ndarray] = None, ref_codes=None,
+                   cp_embs: Optional[np.ndarray] = None, dst_row=None, ent=None, n_rows: int = 0, ldd: int = 0, trail_len=None, text_ready=None,
+                   limit=None, device: int = 0):
+    """q3_prompt_rows_ex: ONE launch of a prompt-row kernel over host arrays (parity tests; include/q3tts.h describes the modes:
+    ROWS_GATHER / ROWS_ASSEMBLE / ROWS_COPY / ROWS_SCATTER / ROWS_PUBLISH). `out` (flat f32) and the publish arrays (flat int32) carry
+    ROWS_GUARD elements in front of and behind their payload and are written in place. Returns out, or (trail_len, text_ready, limit)."""
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    a = _lib.CPromptRowsEx()
+    keep = []
+
+    def put(name, arr, dtype, shape=None):
+        if arr is None:
+            return None
+        arr = np.ascontiguousarray(arr, dtype=dtype)
+        assert shape is None or arr.shape == shape, (name, arr.shape, shape)
+        keep.append(arr); setattr(a, name, ptr(arr))
+        return arr
+    a.mode, a.cols, a.n_rows, a.ldd = mode, cols, n_rows, ldd
+    payload = None
+    if mode == ROWS_GATHER:
+        t = put("table", table, np.uint16); i_ = put("ids", ids, np.uint32)
+        assert t.ndim == 2 and t.shape[1] == cols and i_.ndim == 1
+        a.n, a.n_table = i_.size, t.shape[0]; payload = i_.size * cols
+    elif mode == ROWS_ASSEMBLE:
+        r = put("src", src, np.float32); t = put("table", table, np.uint16)
+        tr = put("text_row", text_row, np.int32); ci = put("codec_id", codec_id, np.int32)
+        assert r.ndim == 2 and r.shape[1] == cols and t.ndim == 2 and t.shape[1] == cols and tr.ndim == 1 and ci.shape == tr.shape
+        a.n, a.n_rows, a.n_table = tr.size, r.shape[0], t.shape[0]; payload = tr.size * cols
+        put("xvec", xvec, np.float32, (cols,))
+        rcod = put("ref_codes", ref_codes, np.uint32); ce = put("cp_embs", cp_embs, np.uint16)
+        if rcod is not None:
+            assert rcod.ndim == 2 and rcod.shape[1] == 16; a.n_ref = rcod.shape[0]
+        if ce is not None:
+            assert ce.ndim == 3 and ce.shape[0] == 15 and ce.shape[2] == cols; a.cp_vocab = ce.shape[1]
+    elif mode == ROWS_COPY:
+        s_ = put("src", src, np.float32); assert s_.ndim == 2
+        a.n, a.lds = s_.shape[0], s_.shape[1]
+        a.ldd = ldd if ldd else cols; payload = s_.shape[0] * a.ldd
+    elif mode == ROWS_SCATTER:
+        s_ = put("src", src, np.float32); d = put("dst_row", dst_row, np.int32)
+        assert s_.ndim == 2 and s_.shape[1] == cols and d.shape == (s_.shape[0],)
+        a.n = s_.shape[0]; payload = n_rows * cols
+    else:
+        e = put("ent", ent, np.int32); assert e.ndim == 2 and e.shape[1] == 4
+        a.n = e.shape[0]
+        for name, arr in (("trail_len", trail_len), ("text_ready", text_ready), ("limit", limit)):
+            assert arr.dtype == np.int32 and arr.flags.c_contiguous and arr.shape == (n_rows + 2 * ROWS_GUARD,)
+            setattr(a, name, ptr(arr))
+        check(lib.q3_prompt_rows_ex(device, ctypes.byref(a)))
+        return trail_len, text_ready, limit
+    assert out is not None and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (payload + 2 * ROWS_GUARD,), (out.shape, payload)
+    a.out = ptr(out)
+    check(lib.q3_prompt_rows_ex(device, ctypes.byref(a)))
+    return out
 
 
 def _vp(arr):

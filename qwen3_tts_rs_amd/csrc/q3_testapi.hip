@@ -869,34 +869,98 @@ extern "C" int q3_attn_prefill_path(int nh, int nkv, int use_planes, int halves,
     return p.kernel;
 }
 
-// One prefill attention step over a contiguous cache: launch_qknorm_rope_kv (rows_per_seq = rps), launch_kv_planes for the bf16x3
-// kernel (into a NaN-filled buffer with more tiles allocated than used), ONE launch_attn_prefill, launch_attn_merge for two halves
-// (over NaN-filled records). A refused launch comes back as a status and leaves the host caches and out alone.
+// One prefill attention step: launch_qknorm_rope_kv (rows_per_seq = rps), launch_kv_planes for the bf16x3 kernel (into a NaN-filled
+// buffer with more tiles allocated than used), ONE launch_attn_prefill, launch_attn_merge for two halves (over NaN-filled records).
+// layout 0: one contiguous cache. layout 1: the logical cache rows of `layer` scattered over pattern-filled slabs of KvPool's
+// geometry (TestSlabs, as q3_attn_step_ex), gathered back afterwards; pages of a cached prefix may be shared between sequences.
+// Everything is validated before a device is touched. A refused launch comes back as a status and leaves the host caches and out alone.
 extern "C" q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_args* p) {
     if (!p || !p->qkv || !p->q_norm_w || !p->k_norm_w || !p->rope_cos || !p->rope_sin || !p->kcache || !p->vcache || !p->out)
         return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: null argument");
     if (p->path) p->path[0] = p->path[1] = 0;
-    const int n_seq = p->n_seq, rps = p->rps, nh = p->nh, nkv = p->nkv, base = p->base_pos;
+    const int n_seq = p->n_seq, rps = p->rps, nh = p->nh, nkv = p->nkv, base = p->base_pos, layout = p->layout, max_seq = p->max_seq;
     if (p->kernel < -1 || p->kernel > AP_X3 || p->halves < 1 || p->halves > 2) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: kernel -1..3, halves 1..2");
-    if (n_seq < 1 || n_seq > 64 || rps < 1 || rps > 8192 || nkv < 1 || nh < nkv || nh > 64 || nh % nkv || p->max_seq < 1 || base < 0 || base + rps > p->max_seq)
+    if (n_seq < 1 || n_seq > 64 || rps < 1 || rps > 8192 || nkv < 1 || nh < nkv || nh > 64 || nh % nkv || max_seq < 1 || base < 0 || base + rps > max_seq)
         return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: bad shape (the chunk [base_pos, base_pos + rps) must lie inside max_seq)");
     const int ld_qkv = p->ld_qkv, QD = nh * HEAD_DIM, rows = n_seq * rps;
     if (ld_qkv < (nh + 2 * nkv) * HEAD_DIM || ld_qkv % 4 || p->ld_out < QD || p->ld_out % 4) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: bad pitch");
+    if (layout < 0 || layout > 2) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: layout 0..2");
+    if (layout == 2) return set_err(Q3_UNSUPPORTED, "q3_attn_prefill_ex: prefill never runs on bf16 pages");
+    const int n_pg = (max_seq + KV_PAGE_POS - 1) / KV_PAGE_POS;
+    auto cache_row = [&](float* c, int s, int g, int pp) { return c + (((size_t)s * nkv + g) * max_seq + pp) * HEAD_DIM; };
+    TestSlabs slabs;
+    if (layout == 1) {
+        if (max_seq > KV_MAX_PAGES * KV_PAGE_POS) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: a paged row holds at most %d positions", KV_MAX_PAGES * KV_PAGE_POS);
+        if (p->n_layers < 1 || p->n_layers > 4 || p->layer < 0 || p->layer >= p->n_layers || p->n_slabs < 1 || p->n_slabs > 2)
+            return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: n_layers 1..4, layer inside them, n_slabs 1..2");
+        if (!p->page_slots || !p->stray) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: a paged layout needs page_slots and stray");
+        slabs.shape(p->n_layers, nkv, 4);
+        if (slabs.geo.v_delta() > 0x7fffffffu) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: K -> V distance beyond the kernels' 32-bit form");
+        // a slot serves one page — or page i of several sequences where that page is a wholly cached prefix page holding the same bits
+        const int limit = KvPool::SLAB_SLOTS * p->n_slabs;
+        std::vector<int> owner((size_t)limit, -1);          // the first (sequence * n_pg + page) that named the slot
+        for (int s = 0; s < n_seq; ++s)
+            for (int i = 0; i < n_pg; ++i) {
+                const int slot = p->page_slots[(size_t)s * n_pg + i];
+                if (slot < 0 || slot >= limit) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: page_slots[%d][%d] = %d outside 0 .. %d", s, i, slot, limit - 1);
+                int& own = owner[(size_t)slot];
+                if (own < 0) { own = s * n_pg + i; continue; }
+                const int s0 = own / n_pg, i0 = own % n_pg;
+                if (s0 == s || i0 != i || (i + 1) * KV_PAGE_POS > base)
+                    return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: slot %d is named for page %d of sequence %d and page %d of sequence %d: only a whole page "
+                                   "below base_pos (%d) may be shared, as the same page of different sequences", slot, i0, s0, i, s, base);
+                const int p0 = i * KV_PAGE_POS;             // (a shared page lies below base_pos <= max_seq: all 128 rows exist)
+                for (int g = 0; g < nkv; ++g)
+                    if (memcmp(cache_row(p->kcache, s, g, p0), cache_row(p->kcache, s0, g, p0), (size_t)KV_PAGE_POS * HEAD_DIM * 4) != 0 ||
+                        memcmp(cache_row(p->vcache, s, g, p0), cache_row(p->vcache, s0, g, p0), (size_t)KV_PAGE_POS * HEAD_DIM * 4) != 0)
+                        return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: sequences %d and %d share slot %d but their cache rows of page %d differ", s0, s, slot, i);
+            }
+    }
     HIPC(hipSetDevice(device));
     DevPool pool;
-    const size_t cn = (size_t)n_seq * nkv * p->max_seq * HEAD_DIM, rn = (size_t)p->max_seq * 64, on = (size_t)rows * p->ld_out;
-    float *qkv, *qw, *kw, *rc, *rs, *kv, *qbuf, *part = nullptr, *out; unsigned char* kvp = nullptr;
+    const size_t cn = (size_t)n_seq * nkv * max_seq * HEAD_DIM, rn = (size_t)max_seq * 64, on = (size_t)rows * p->ld_out;
+    float *qkv, *qw, *kw, *rc, *rs, *kv = nullptr, *qbuf, *part = nullptr, *out; unsigned char* kvp = nullptr;
+    unsigned long long* table = nullptr;
+    // (slab, table, slab: with two slabs the pages of a row lie on both sides of the table the kernels form their addresses from)
+    if (layout == 1) {
+        for (int s = 0; s < p->n_slabs; ++s) {
+            if (s == 1) HIPC(pool.alloc(&table, (size_t)n_seq * KV_MAX_PAGES));
+            HIPC(slabs.add_slab(pool));
+        }
+        if (!table) HIPC(pool.alloc(&table, (size_t)n_seq * KV_MAX_PAGES));
+    } else HIPC(pool.alloc(&kv, 2 * cn));
     HIPC(pool.alloc(&qkv, (size_t)rows * ld_qkv)); HIPC(pool.alloc(&qw, (size_t)HEAD_DIM)); HIPC(pool.alloc(&kw, (size_t)HEAD_DIM));
-    HIPC(pool.alloc(&rc, rn)); HIPC(pool.alloc(&rs, rn)); HIPC(pool.alloc(&kv, 2 * cn));
+    HIPC(pool.alloc(&rc, rn)); HIPC(pool.alloc(&rs, rn));
     HIPC(pool.alloc(&qbuf, (size_t)rows * QD)); HIPC(pool.alloc(&out, on));
     HIPC(q3_hipMemcpy(qkv, p->qkv, (size_t)rows * ld_qkv * 4, hipMemcpyHostToDevice));
     HIPC(q3_hipMemcpy(qw, p->q_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kw, p->k_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice));
     HIPC(q3_hipMemcpy(rc, p->rope_cos, rn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(rs, p->rope_sin, rn * 4, hipMemcpyHostToDevice));
-    HIPC(q3_hipMemcpy(kv, p->kcache, cn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kv + cn, p->vcache, cn * 4, hipMemcpyHostToDevice));
+    auto each_row = [&](auto&& f) {             // every (sequence, kv head, position, K | V) of the logical cache with its slot and element offset
+        for (int s = 0; s < n_seq; ++s) for (int g = 0; g < nkv; ++g) for (int pp = 0; pp < max_seq; ++pp) for (int v = 0; v < 2; ++v) {
+            const int slot = p->page_slots[(size_t)s * n_pg + pp / KV_PAGE_POS];
+            f(slot, slabs.row_elem(slot, p->layer, v, g, pp), cache_row(v ? p->vcache : p->kcache, s, g, pp));
+        }
+    };
+    if (layout == 1) {
+        slabs.fill_pattern();
+        each_row([&](int slot, size_t elem, float* row) { slabs.put_row(slabs.img, slot, elem, row); });
+        HIPC(slabs.upload());
+        std::vector<unsigned long long> tab((size_t)n_seq * KV_MAX_PAGES);
+        for (int s = 0; s < n_seq; ++s)
+            for (int i = 0; i < KV_MAX_PAGES; ++i) tab[(size_t)s * KV_MAX_PAGES + i] = slabs.page(p->page_slots[(size_t)s * n_pg + (i < n_pg ? i : 0)]);      // beyond the row's pages: its first, as a session leaves them
+        HIPC(q3_hipMemcpy(table, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+        if (p->rot_used)
+            for (int s = 0; s < n_seq; ++s) for (int i = 0; i < n_pg; ++i) for (int g = 0; g < nkv; ++g)
+                p->rot_used[((size_t)s * n_pg + i) * nkv + g] = kv_rot(slabs.page(p->page_slots[(size_t)s * n_pg + i]), g);
+    } else {
+        HIPC(q3_hipMemcpy(kv, p->kcache, cn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kv + cn, p->vcache, cn * 4, hipMemcpyHostToDevice));
+    }
     HIPC(q3_hipMemcpy(out, p->out, on * 4, hipMemcpyHostToDevice));
     AttnArgs t{};
     t.qkv = qkv; t.ld_qkv = ld_qkv; t.q_norm_w = qw; t.k_norm_w = kw; t.eps = p->eps; t.rope_cos = rc; t.rope_sin = rs;
-    t.pos_dev = nullptr; t.pos_static = base; t.kcache = kv; t.vcache = kv + cn; t.max_seq = p->max_seq; t.qbuf = qbuf; t.out = out; t.ld_out = p->ld_out;
+    t.pos_dev = nullptr; t.pos_static = base; t.max_seq = max_seq; t.qbuf = qbuf; t.out = out; t.ld_out = p->ld_out;
+    if (layout == 1) { t.kv_pages = table; t.kv_layer_off = (size_t)p->layer * slabs.geo.layer_stride(); t.kv_vdelta = slabs.geo.v_delta(); }
+    else { t.kcache = kv; t.vcache = kv + cn; }
     t.B = rows; t.nh = nh; t.nkv = nkv; t.n_splits = 1; t.rows_per_seq = rps;
     const int tiles = (base + rps + 31) / 32, kvp_tiles = tiles + 2;
     const bool want_planes = p->kernel == AP_X3 || (p->kernel < 0 && p->use_planes);
@@ -926,7 +990,138 @@ extern "C" q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_arg
     HIPC(q3_hipDeviceSynchronize());
     if (p->path) { p->path[0] = pick.kernel; p->path[1] = pick.halves; }
     HIPC(q3_hipMemcpy(p->out, out, on * 4, hipMemcpyDeviceToHost));
-    HIPC(q3_hipMemcpy(p->kcache, kv, cn * 4, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(p->vcache, kv + cn, cn * 4, hipMemcpyDeviceToHost));
+    if (layout == 1) {
+        std::vector<std::vector<uint32_t>> got;
+        HIPC(slabs.download(got));
+        each_row([&](int slot, size_t elem, float* row) { slabs.get_row(got, slot, elem, row); slabs.copy_row(slabs.img, got, slot, elem); });
+        slabs.strays(got, p->stray);
+    } else {
+        HIPC(q3_hipMemcpy(p->kcache, kv, cn * 4, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(p->vcache, kv + cn, cn * 4, hipMemcpyDeviceToHost));
+        if (p->stray) { p->stray[0] = 0; p->stray[1] = -1; }
+    }
+    return Q3_OK;
+}
+
+// ---- the kernels that build the prompt rows, one launch at a time (tests/test_gpu_prompt_rows.py) ----
+// Exactly one launch_* per call. A destination goes up whole, 64 guard elements on both sides, and comes back whole; whatever the
+// kernel would read or write outside its arrays is refused here, before a device is touched.
+extern "C" q3_status q3_prompt_rows_ex(int device, const q3_prompt_rows_ex_args* p) {
+    constexpr int G = 64;
+    if (!p) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: null argument");
+    const int mode = p->mode, n = p->n, cols = p->cols;
+    if (mode < 0 || mode > 4) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: mode 0..4");
+    if (n < 1 || n > 65535) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: n 1..65535");
+    if (mode != 4 && (cols < 1 || cols > 65536 || !p->out)) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: cols 1..65536 and a destination");
+    auto table_ok = [](int rows) { return rows >= 1 && rows <= (1 << 20); };
+    size_t payload = 0;
+    if (mode == 0) {
+        if (!p->table || !p->ids || !table_ok(p->n_table)) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: the gather needs table [n_table][cols] and ids");
+        for (int r = 0; r < n; ++r) if (p->ids[r] >= (uint32_t)p->n_table) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: ids[%d] = %u outside the table (%d)", r, p->ids[r], p->n_table);
+        payload = (size_t)n * cols;
+    } else if (mode == 1) {
+        if (!p->src || !p->text_row || !p->codec_id || !p->table || !table_ok(p->n_table) || !table_ok(p->n_rows))
+            return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: the assembly needs rows [n_rows][cols], text_row, codec_id and codec_emb [n_table][cols]");
+        for (int i = 0; i < n; ++i) {
+            const int tr = p->text_row[i], cid = p->codec_id[i];
+            if (tr >= p->n_rows) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: text_row[%d] = %d outside rows (%d)", i, tr, p->n_rows);
+            if (cid >= p->n_table) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: codec_id[%d] = %d outside codec_emb (%d)", i, cid, p->n_table);
+            if (cid == -2 && !p->xvec) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: codec_id[%d] = -2 without xvec", i);
+            if (cid <= -3) {
+                const long long fr = -3LL - cid;
+                if (!p->ref_codes || !p->cp_embs || !table_ok(p->cp_vocab) || p->n_ref < 1 || fr >= p->n_ref)
+                    return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: codec_id[%d] = %d names frame %lld beyond ref_codes (%d frames)", i, cid, fr, p->ref_codes ? p->n_ref : 0);
+                const uint32_t* f = p->ref_codes + (size_t)fr * 16;
+                if (f[0] >= (uint32_t)p->n_table) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: ref_codes[%lld][0] = %u outside codec_emb (%d)", fr, f[0], p->n_table);
+                for (int g = 1; g < 16; ++g)
+                    if (f[g] >= (uint32_t)p->cp_vocab) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: ref_codes[%lld][%d] = %u outside its table (%d)", fr, g, f[g], p->cp_vocab);
+            }
+        }
+        payload = (size_t)n * cols;
+    } else if (mode == 2) {
+        if (!p->src || p->lds < cols || p->ldd < cols || p->lds > (1 << 20) || p->ldd > (1 << 20)) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: the copy needs src and cols <= lds, ldd");
+        payload = (size_t)n * p->ldd;
+    } else if (mode == 3) {
+        if (!p->src || !p->dst_row || !table_ok(p->n_rows)) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: the scatter needs src, dst_row and rows [n_rows][cols]");
+        std::vector<char> seen((size_t)p->n_rows, 0);
+        for (int r = 0; r < n; ++r) {
+            const int d = p->dst_row[r];
+            if (d < 0) continue;
+            if (d >= p->n_rows) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: dst_row[%d] = %d outside rows (%d)", r, d, p->n_rows);
+            if (seen[(size_t)d]) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: dst_row names row %d twice", d);
+            seen[(size_t)d] = 1;
+        }
+        payload = (size_t)p->n_rows * cols;
+    } else {
+        if (!p->ent || !p->trail_len || !p->text_ready || !p->limit || !table_ok(p->n_rows))
+            return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: the publish needs ent and trail_len / text_ready / limit [n_rows]");
+        std::vector<char> seen((size_t)p->n_rows, 0);
+        for (int i = 0; i < n; ++i) {
+            const int b = p->ent[4 * i];
+            if (b < 0 || b >= p->n_rows) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: ent[%d] names row %d outside [0, %d)", i, b, p->n_rows);
+            if (seen[(size_t)b]) return set_err(Q3_INVALID_ARG, "q3_prompt_rows_ex: ent names row %d twice", b);
+            seen[(size_t)b] = 1;
+        }
+    }
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    auto up = [&](const void* h, size_t bytes, void** d) -> q3_status {
+        char* q; HIPC(pool.alloc(&q, bytes)); HIPC(q3_hipMemcpy(q, h, bytes, hipMemcpyHostToDevice)); *d = q;
+        return Q3_OK;
+    };
+    void* d = nullptr;
+    if (mode == 4) {
+        const size_t bytes = ((size_t)p->n_rows + 2 * G) * 4;
+        int *ent, *tl, *trd, *lim;
+        Q3C(up(p->ent, (size_t)n * 16, &d)); ent = (int*)d;
+        Q3C(up(p->trail_len, bytes, &d)); tl = (int*)d; Q3C(up(p->text_ready, bytes, &d)); trd = (int*)d; Q3C(up(p->limit, bytes, &d)); lim = (int*)d;
+        HIPC(q3_hipDeviceSynchronize());
+        HIPC(launch_publish_text(ent, n, tl + G, trd + G, lim + G, 0));
+        HIPC(q3_hipDeviceSynchronize());
+        HIPC(q3_hipMemcpy(p->trail_len, tl, bytes, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(p->text_ready, trd, bytes, hipMemcpyDeviceToHost));
+        HIPC(q3_hipMemcpy(p->limit, lim, bytes, hipMemcpyDeviceToHost));
+        return Q3_OK;
+    }
+    const size_t out_bytes = (payload + 2 * G) * 4;
+    float* out;
+    Q3C(up(p->out, out_bytes, &d)); out = (float*)d + G;
+    hipError_t e = hipSuccess;
+    if (mode == 0) {
+        const uint16_t* table; const uint32_t* ids;
+        Q3C(up(p->table, (size_t)p->n_table * cols * 2, &d)); table = (const uint16_t*)d;
+        Q3C(up(p->ids, (size_t)n * 4, &d)); ids = (const uint32_t*)d;
+        HIPC(q3_hipDeviceSynchronize());
+        e = launch_gather_rows_bf16(table, ids, out, n, cols, 0);
+    } else if (mode == 1) {
+        const float *rows, *xvec = nullptr; const int *tr, *ci; const uint16_t *emb, *cp = nullptr; const uint32_t* ref = nullptr;
+        const uint16_t* const* cp_tab = nullptr;
+        Q3C(up(p->src, (size_t)p->n_rows * cols * 4, &d)); rows = (const float*)d;
+        Q3C(up(p->text_row, (size_t)n * 4, &d)); tr = (const int*)d; Q3C(up(p->codec_id, (size_t)n * 4, &d)); ci = (const int*)d;
+        Q3C(up(p->table, (size_t)p->n_table * cols * 2, &d)); emb = (const uint16_t*)d;
+        if (p->xvec) { Q3C(up(p->xvec, (size_t)cols * 4, &d)); xvec = (const float*)d; }
+        if (p->ref_codes && p->cp_embs && p->n_ref >= 1 && table_ok(p->cp_vocab)) {
+            Q3C(up(p->ref_codes, (size_t)p->n_ref * 64, &d)); ref = (const uint32_t*)d;
+            Q3C(up(p->cp_embs, (size_t)15 * p->cp_vocab * cols * 2, &d)); cp = (const uint16_t*)d;
+            const uint16_t* tabs[15];
+            for (int g = 0; g < 15; ++g) tabs[g] = cp + (size_t)g * p->cp_vocab * cols;
+            Q3C(up(tabs, sizeof(tabs), &d)); cp_tab = (const uint16_t* const*)d;
+        }
+        HIPC(q3_hipDeviceSynchronize());
+        e = launch_assemble_rows(rows, tr, emb, ci, xvec, out, n, cols, 0, ref, cp_tab);
+    } else if (mode == 2) {
+        const float* src;
+        Q3C(up(p->src, (size_t)n * p->lds * 4, &d)); src = (const float*)d;
+        HIPC(q3_hipDeviceSynchronize());
+        e = launch_copy_rows(src, p->lds, out, p->ldd, n, cols, 0);
+    } else {
+        const float* src; const int* dr;
+        Q3C(up(p->src, (size_t)n * cols * 4, &d)); src = (const float*)d;
+        Q3C(up(p->dst_row, (size_t)n * 4, &d)); dr = (const int*)d;
+        HIPC(q3_hipDeviceSynchronize());
+        e = launch_scatter_rows(src, dr, out, n, cols, 0);
+    }
+    HIPC(e);
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->out, out - G, out_bytes, hipMemcpyDeviceToHost));
     return Q3_OK;
 }
 

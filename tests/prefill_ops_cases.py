@@ -1,5 +1,5 @@
-"""Inputs, shape tables and float64 references shared by tests/test_gpu_prefill_ops.py (the kernels, -m gpu) and
-tests/test_prefill_ops_reference.py (what can be checked without a GPU). TEST INFRASTRUCTURE — no test lives here.
+"""Inputs, shape tables and float64 references shared by tests/test_gpu_prefill_ops.py and tests/test_gpu_prefill_paged.py (the
+kernels, -m gpu) and tests/test_prefill_ops_reference.py (what can be checked without a GPU). TEST INFRASTRUCTURE — no test lives here.
 
 GEMM: y = epilogue(rms_norm(x, w) @ W^T) on bf16-rounded weights, as in tests/test_gpu_linear_paths.py.
 Attention: one prefill chunk — n_seq sequences of rps rows at positions base_pos .. base_pos + rps - 1 over a contiguous cache:
@@ -16,6 +16,8 @@ NONE, RESID, SILU, SWIGLU = 0, 1, 2, 3
 EPS = 1e-6
 HD = 128
 MAX_SEQ = 512
+PAGE = 128                               # positions of a K/V page
+SLAB_SLOTS = 32                          # pages of a slab
 SENT = np.float32(-7.0625e33)            # sentinel around y / in `out`: no kernel computes this value
 # geometry codes of q3_gemm_ex / q3_gemm_path
 G1_SPLIT, G1_PLANES, G2, G3 = 0, 1, 2, 3
@@ -184,8 +186,9 @@ STRESS = dict(rps=20, base=128, n_seq=3)       # last row at position 147: tiles
 
 
 @functools.lru_cache(maxsize=None)
-def attn_case(nh, nkv, rps, base, n_seq, stress=False, max_seq=MAX_SEQ):
-    """inputs of one prefill chunk (read-only, shared by the kernels and halves counts that run it)"""
+def attn_case(nh, nkv, rps, base, n_seq, stress=False, max_seq=MAX_SEQ, shared=0):
+    """inputs of one prefill chunk (read-only, shared by the kernels and halves counts that run it). shared: sequences 0 and 1 hold
+    the same K/V in their first `shared` pages of 128 positions (a cached prefix they have in common)"""
     nrep = nh // nkv; rows = n_seq * rps
     rng = np.random.default_rng(nh * 1000 + nkv * 100 + rps * 13 + base * 7 + n_seq + (5 if stress else 0))
     qkv = rng.standard_normal((rows, (nh + 2 * nkv) * HD)).astype(np.float32)
@@ -208,6 +211,9 @@ def attn_case(nh, nkv, rps, base, n_seq, stress=False, max_seq=MAX_SEQ):
             kc[0, g, 0] = (HOT * qr[last[0], g * nrep]).astype(np.float32)
             kc[1, g, tile0 - 1] = (HOT * qr[last[1], g * nrep]).astype(np.float32)
             qkv[last[2], nh * HD + g * HD:nh * HD + (g + 1) * HD] = qkv[last[2], g * nrep * HD:(g * nrep + 1) * HD]
+    if shared:
+        assert n_seq >= 2 and shared * PAGE <= base and not stress
+        kc[1, :, :shared * PAGE] = kc[0, :, :shared * PAGE]; vc[1, :, :shared * PAGE] = vc[0, :, :shared * PAGE]
     for a in (qkv, qw, kw, kc, vc, pos):
         a.setflags(write=False)
     return dict(nh=nh, nkv=nkv, rps=rps, base=base, n_seq=n_seq, max_seq=max_seq, pos=pos, qkv=qkv, qw=qw, kw=kw, kc=kc, vc=vc)
@@ -346,3 +352,157 @@ def d_ref(keys):
 D_REF = 1.61e-6
 D_REF_K = 2.15e-7
 D_REF_STRESS = 1.75e-6
+
+
+# ---------------------------------------------------------------- prefill attention over pages
+# (tests/test_gpu_prefill_paged.py; the CPU side is in test_prefill_ops_reference.py.) The same chunk as above through
+# q3_attn_prefill_ex with layout = 1: the logical cache scattered over two pattern-filled slabs, the page table between them.
+LONG = dict(rps=40, base=8152, n_seq=1, max_seq=8192)      # page 63 of the table, 256 key tiles, both slabs full
+LONG_RATIOS = [(2, 1), (2, 2)]
+LONG_KERNELS = [(GEN_T, 2), (X3, 1), (X3, 2)]               # what a prompt of >= 1024 positions runs (bf16x3, two halves) and its neighbours
+SHARED = dict(rps=70, base=256, n_seq=3, pages=2)           # sequences 0 and 1 share pages 0 and 1: the prefix-cache form
+
+
+def paged_max_seq(rps, base):
+    """MAX_SEQ: four pages per row — every row has page edges, several rotations and pages beyond the chunk that must keep their
+    bits — and the inputs of a (rps, base, n_seq) the contiguous tests also run are the very same arrays"""
+    assert base + rps <= MAX_SEQ
+    return MAX_SEQ
+
+
+def paged_key(nh, nkv, rps, base, n_seq, stress=False, shared=0, max_seq=None):
+    return (nh, nkv, rps, base, n_seq, stress, paged_max_seq(rps, base) if max_seq is None else max_seq, shared)
+
+
+def paged_rows(kernel, halves, nrep):
+    """(rps, base_pos, n_seq, stress, shared pages) a (kernel, halves) pair runs over pages, each against one rule of the paged path"""
+    qb = query_block(kernel, nrep)
+    rows = [
+        (1, 127, 1, False, 0),        # the appended row is the last row of page 0
+        (1, 128, 1, False, 0),        # the append opens page 1 over a wholly visible page 0
+        (130, 0, 2, False, 0),        # no cache: one k_qknorm_rope_kv launch writes two pages of each row
+        (33, 112, 3, False, 0),       # a chunk across the 127 / 128 edge, 3 sequences
+        (qb + 1, 128, 1, False, 0),   # a second query block (one live row) behind a whole cached page
+        (200, 128, 2, False, 0),      # three pages, the 255 / 256 edge inside the chunk
+        (STRESS["rps"], STRESS["base"], STRESS["n_seq"], True, 0),      # sequence 1's hot key at position 127 is the last row of page 0
+        (SHARED["rps"], SHARED["base"], SHARED["n_seq"], False, SHARED["pages"]),
+    ]
+    if kernel in (GEN_T, X3):         # the unaligned-base fix, now with a page edge inside the cache (100) and inside the first wave (130)
+        rows += [(100, base, 1, False, 0) for base in UNALIGNED_BASES]
+    return rows
+
+
+def paged_cases():
+    """every launch of the GPU file: (key, kernel, halves, n_layers, layer). The layer alternates between the cases of a ratio; the
+    last case of each ratio runs on layer 3 of 4."""
+    out = []
+    for (nh, nkv) in RATIOS:
+        nrep = nh // nkv
+        mine = []
+        for (kernel, halves) in attn_kernels(nrep):
+            for (rps, base, n_seq, stress, shared) in paged_rows(kernel, halves, nrep):
+                mine.append((paged_key(nh, nkv, rps, base, n_seq, stress, shared), kernel, halves))
+        if (nh, nkv) in LONG_RATIOS:
+            for (kernel, halves) in LONG_KERNELS:
+                mine.append((paged_key(nh, nkv, LONG["rps"], LONG["base"], LONG["n_seq"], max_seq=LONG["max_seq"]), kernel, halves))
+        for i, (key, kernel, halves) in enumerate(mine):
+            n_layers, layer = (4, 3) if i == len(mine) - 1 else (2, i % 2)
+            out.append((key, kernel, halves, n_layers, layer))
+    return out
+
+
+def paged_case_keys():
+    """the distinct inputs of paged_cases(): what the D_REF recomputation and the mutation check run over"""
+    keys = []
+    for (key, _, _, _, _) in paged_cases():
+        if key not in keys:
+            keys.append(key)
+    return keys
+
+
+def is_long(key):
+    return key[6] == LONG["max_seq"]
+
+
+def case_d_ref(key):
+    return D_REF_STRESS if key[5] else D_REF
+
+
+def prefill_page_slots(n_seq, n_pg, n_slabs, seed, shared=None, private=False):
+    """[n_seq][n_pg] slots of 0 .. 32 * n_slabs - 1, drawn from a seeded permutation: distinct, a row's pages in no order (not
+    ascending when it has more than two) and — with two slabs and more than one page — on both slabs. shared = (sequences, pages):
+    those sequences name the first of them's slots for their first `pages` pages (a prefix they have in common); the slots they
+    would have had stay unused — private = True returns the table with those slots instead, equal everywhere else."""
+    total = SLAB_SLOTS * n_slabs
+    assert n_seq * n_pg <= total, "not enough slots"
+    rng = np.random.default_rng(seed)
+
+    def fine(slots):
+        both = n_slabs < 2 or n_pg < 2 or all(len(set((slots[s] // SLAB_SLOTS).tolist())) == 2 for s in range(n_seq))
+        return both and (n_pg <= 2 or all(not (np.diff(slots[s]) > 0).all() for s in range(n_seq)))
+    for _ in range(1000):
+        own = rng.permutation(total)[:n_seq * n_pg].reshape(n_seq, n_pg).astype(np.int32)
+        slots = own.copy()
+        if shared is not None:
+            seqs, pages = shared
+            assert pages <= n_pg and len(seqs) >= 2
+            for s in seqs[1:]:
+                slots[s, :pages] = slots[seqs[0], :pages]
+        if fine(own) and fine(slots):
+            return own if private else slots
+    raise AssertionError("no slot table with the wanted properties")
+
+
+def case_page_slots(key, private=False):
+    """the slot table of a paged case (seeded by the case): two slabs; the shared-prefix case shares unless `private`"""
+    nh, nkv, rps, base, n_seq, stress, max_seq, shared = key
+    seed = nh * 1009 + nkv * 101 + rps * 17 + base * 3 + n_seq
+    return prefill_page_slots(n_seq, max_seq // PAGE, 2, seed, ((0, 1), shared) if shared else None, private)
+
+
+# --- what the bound can see: mutations of the key set, in float64
+def attn_reference_mutated(c, mutation):
+    """attn_reference in float64 with ONE thing wrong in the LAST sequence's keys (every head): 'drop' = the key at the last page
+    edge below the chunk's end (position 0 when there is none) is left out, 'dup' = it is counted twice, 'page' = the rows of its
+    page 0 come from the neighbour sequence (the next one; a sequence alone gets other random rows — what a stranger's page holds)."""
+    nh, nkv, rps, base, n_seq = c["nh"], c["nkv"], c["rps"], c["base"], c["n_seq"]
+    rows = n_seq * rps; nrep = nh // nkv
+    dtype = np.float64
+    qkv = c["qkv"]
+    qr = norm_rope(qkv[:, :nh * HD].reshape(rows, nh, HD), c["qw"], c["pos"], dtype, c["max_seq"])
+    kr = norm_rope(qkv[:, nh * HD:(nh + nkv) * HD].reshape(rows, nkv, HD), c["kw"], c["pos"], dtype, c["max_seq"])
+    v = qkv[:, (nh + nkv) * HD:].reshape(rows, nkv, HD).astype(dtype)
+    n_keys = base + rps
+    edge = max(0, (n_keys - 1) // PAGE * PAGE - 1)
+    keys_of = lambda s, g: (np.concatenate([c["kc"][s, g, :base].astype(dtype), kr[s * rps:(s + 1) * rps, g]], 0),
+                            np.concatenate([c["vc"][s, g, :base].astype(dtype), v[s * rps:(s + 1) * rps, g]], 0))
+    out = np.zeros((rows, nh, HD), dtype=dtype)
+    scale = dtype(HD ** -0.5)
+    kpos = np.arange(n_keys)
+    stranger = np.random.default_rng(99).standard_normal((2, nkv, PAGE, HD))
+    for s in range(n_seq):
+        sl = slice(s * rps, (s + 1) * rps)
+        for h in range(nh):
+            g = h // nrep
+            K, V = keys_of(s, g)
+            pos_k = kpos
+            if s == n_seq - 1:
+                if mutation == "drop":
+                    K = np.delete(K, edge, 0); V = np.delete(V, edge, 0); pos_k = np.delete(kpos, edge)
+                elif mutation == "dup":
+                    K = np.concatenate([K, K[edge:edge + 1]], 0); V = np.concatenate([V, V[edge:edge + 1]], 0); pos_k = np.append(kpos, edge)
+                elif mutation == "page":
+                    n0 = min(PAGE, n_keys)
+                    K = K.copy(); V = V.copy()
+                    if n_seq > 1:
+                        K2, V2 = keys_of((s + 1) % n_seq, g)
+                        K[:n0] = K2[:n0]; V[:n0] = V2[:n0]
+                    else:
+                        K[:n0] = stranger[0, g, :n0]; V[:n0] = stranger[1, g, :n0]
+                else:
+                    raise ValueError(mutation)
+            visible = pos_k[None, :] <= (base + np.arange(rps))[:, None]
+            sc = np.where(visible, (qr[sl, h] @ K.T) * scale, -np.inf)
+            pr = np.exp(sc - sc.max(axis=1, keepdims=True)); pr = pr / pr.sum(axis=1, keepdims=True)
+            out[sl, h] = pr @ V
+    return out.reshape(rows, nh * HD)

@@ -129,6 +129,11 @@ def test_no_cpu_fallback():
                        (lambda: q.attn_prefill_ex(np.zeros((2, 4 * 128), np.float32), 1, 0, np.ones(128, np.float32), np.ones(128, np.float32), 1e-6,
                                                   np.ones((4, 64), np.float32), np.zeros((4, 64), np.float32), np.zeros((1, 1, 4, 128), np.float32),
                                                   np.zeros((1, 1, 4, 128), np.float32), 2, 1), "q3_attn_prefill_ex"),
+                       (lambda: q.attn_prefill_ex(np.zeros((2, 4 * 128), np.float32), 1, 0, np.ones(128, np.float32), np.ones(128, np.float32), 1e-6,
+                                                  np.ones((4, 64), np.float32), np.zeros((4, 64), np.float32), np.zeros((1, 1, 4, 128), np.float32),
+                                                  np.zeros((1, 1, 4, 128), np.float32), 2, 1, layout=1, page_slots=[[5]]), "q3_attn_prefill_ex (paged)"),
+                       (lambda: q.prompt_rows_ex(q.api.ROWS_COPY, src=np.zeros((2, 8), np.float32), out=np.zeros(64 + 16 + 64, np.float32), cols=8),
+                        "q3_prompt_rows_ex"),
                        (lambda: q.attn_c_ex(0, np.zeros((128, 8), np.float32), np.zeros((128, 8), np.float32), nh=2, k=np.zeros((128, 8), np.float32),
                                             v=np.zeros((128, 8), np.float32)), "q3_attn_c_ex"),
                        (lambda: q.attn_c_ex(1, np.zeros((128, 8), np.float32), np.zeros((128, 8), np.float32), nh=2, rows=[(0, 4, 0)],
@@ -189,7 +194,8 @@ def test_prefill_paths_are_host_only():
     assert q.gemm_path(130, 384, 128) == (2, 1, 1, 1) and q.gemm_path(130, 64, 40) == (1, 1, 1, 1) and q.gemm_path(130, 64, 36, planes=False) == (0, 1, 1, 1)
     assert q.gemm_path(130, 96, 128) is None and q.gemm_path(0, 64, 128) is None
     assert q.attn_prefill_path(16, 8, True, 2) == (3, 2) and q.attn_prefill_path(16, 8, False) == (2, 1) and q.attn_prefill_path(16, 2, False) is None
-    assert ctypes.sizeof(_lib.CGemmEx) == 14 * 4 + 8 * 8 and ctypes.sizeof(_lib.CAttnPrefillEx) == 12 * 4 + 9 * 8
+    assert ctypes.sizeof(_lib.CGemmEx) == 14 * 4 + 8 * 8 and ctypes.sizeof(_lib.CAttnPrefillEx) == 16 * 4 + 12 * 8 and \
+        ctypes.sizeof(_lib.CPromptRowsEx) == 10 * 4 + 14 * 8
 
 
 def test_codec_attn_entries_are_host_checked():
@@ -300,6 +306,8 @@ def test_null_handles_return_status_not_crash():
         lambda: L.q3_gemm_ex(0, ctypes.byref(_lib.CGemmEx())),
         lambda: L.q3_attn_prefill_ex(0, None),
         lambda: L.q3_attn_prefill_ex(0, ctypes.byref(_lib.CAttnPrefillEx())),
+        lambda: L.q3_prompt_rows_ex(0, None),
+        lambda: L.q3_prompt_rows_ex(0, ctypes.byref(_lib.CPromptRowsEx())),
         lambda: L.q3_attn_c_ex(0, None),
         lambda: L.q3_attn_c_ex(0, ctypes.byref(_lib.CAttnCEx())),
         lambda: L.q3_rope_c_ex(0, None, None, None, None, None, 2, 64, 8, 8),

@@ -1,6 +1,7 @@
 """What tests/test_gpu_prefill_ops.py rests on and a CPU can check: the frozen D_REF figures, the bound that makes the exact GEMM
 check exact, the launchers' own pick for every shape of the tables (host-only: q3_gemm_path / q3_attn_prefill_path), and the
-vectorised attention reference against plain loops."""
+vectorised attention reference against plain loops. For tests/test_gpu_prefill_paged.py: the same D_REF recomputation over the
+paged cases, the power of the bound against a wrong key set, the slot helper's properties and every refusal of the paged entry."""
 import numpy as np
 
 import qwen3_tts_rs_amd as q
@@ -106,3 +107,142 @@ def test_tables_name_every_kernel_choice():
                 assert base + rps <= C.MAX_SEQ
     # the rows the table claims: an odd tile count, a single tile, a second XCD round
     assert (31 + 256 - 1) // 32 + 1 == 9 and (200 + 128 - 1) // 32 + 1 == 11 and 5 * 2 > 8
+
+
+# ---------------------------------------------------------------- prefill attention over pages (tests/test_gpu_prefill_paged.py)
+def test_paged_cases_stay_under_the_frozen_d_ref():
+    """the paged cases take no constant of their own: numpy float32 against float64 over paged_case_keys() does not exceed D_REF /
+    D_REF_K (stress cases: D_REF_STRESS), and the long case — 8192 keys — lies well below (measured here: 9.7e-7 and 1.2e-7)"""
+    keys = C.paged_case_keys()
+    plain = [k for k in keys if not k[5] and not C.is_long(k)]
+    stress = [k for k in keys if k[5]]
+    long_ = [k for k in keys if C.is_long(k)]
+    assert len(plain) + len(stress) + len(long_) == len(keys) and len(stress) == len(C.RATIOS) and len(long_) == len(C.LONG_RATIOS)
+    d, dk = C.d_ref(plain); ds, dks = C.d_ref(stress); dl, dkl = C.d_ref(long_)
+    print(f"paged: out {d:.3e} (D_REF {C.D_REF:.3e}), stress {ds:.3e} (D_REF_STRESS {C.D_REF_STRESS:.3e}), long {dl:.3e}; K rows {max(dk, dks, dkl):.3e}")
+    assert d <= C.D_REF and ds <= C.D_REF_STRESS and dl <= C.D_REF
+    assert max(dk, dks, dkl) <= C.D_REF_K
+
+
+def test_paged_table_names_every_rule():
+    cases = C.paged_cases()
+    keys = C.paged_case_keys()
+    rows = {k[2:5] for k in keys}
+    assert {(1, 127, 1), (1, 128, 1), (130, 0, 2), (33, 112, 3), (200, 128, 2), (100, 100, 1), (100, 130, 1), (20, 128, 3), (70, 256, 3), (40, 8152, 1)} <= rows
+    assert {k[2] for k in keys if k[3:5] == (128, 1)} >= {9, 65, 129, 257, 33, 1}          # query block + 1 of every kernel at every ratio
+    for (key, kernel, halves, n_layers, layer) in cases:
+        nh, nkv, rps, base, n_seq, stress, max_seq, shared = key
+        assert base + rps <= max_seq <= 64 * C.PAGE and max_seq % C.PAGE == 0 and layer < n_layers
+        assert (kernel, halves) in C.attn_kernels(nh // nkv)
+        if C.is_long(key):
+            assert (nh, nkv) in C.LONG_RATIOS and (kernel, halves) in C.LONG_KERNELS and max_seq // C.PAGE == 64 and (base + rps + 31) // 32 == 256
+        if rps == 100:
+            assert kernel in (GEN_T, X3)
+    for ratio in C.RATIOS:          # both layers of two, and layer 3 of four once per ratio
+        mine = [(c[3], c[4]) for c in cases if c[0][:2] == ratio]
+        assert set(mine) == {(2, 0), (2, 1), (4, 3)} and mine.count((4, 3)) == 1
+    for ratio in C.LONG_RATIOS:
+        assert {(c[1], c[2]) for c in cases if c[0][:2] == ratio and C.is_long(c[0])} == set(C.LONG_KERNELS)
+    # the stress case's hot key of sequence 1 sits in the last row of page 0; the shared case's pages lie wholly below its base
+    assert (C.STRESS["base"] + C.STRESS["rps"] - 1) // 32 * 32 - 1 == C.PAGE - 1
+    for (nh, nkv) in C.RATIOS:          # ... and carries nearly all the weight of that sequence's last row
+        key = C.paged_key(nh, nkv, C.STRESS["rps"], C.STRESS["base"], C.STRESS["n_seq"], True)
+        assert key in keys
+        cs = C.attn_case(*key)
+        o64, _ = C.attn_ref64(key)
+        for g in range(nkv):
+            h = g * (nh // nkv)
+            assert np.abs(o64[2 * cs["rps"] - 1, h * C.HD:(h + 1) * C.HD] - cs["vc"][1, g, C.PAGE - 1]).max() < 1e-6
+    assert C.SHARED["pages"] * C.PAGE <= C.SHARED["base"]
+    c = C.attn_case(*C.paged_key(2, 1, C.SHARED["rps"], C.SHARED["base"], C.SHARED["n_seq"], shared=C.SHARED["pages"]))
+    n = C.SHARED["pages"] * C.PAGE
+    assert (c["kc"][0, :, :n] == c["kc"][1, :, :n]).all() and (c["vc"][0, :, :n] == c["vc"][1, :, :n]).all()
+    assert not (c["kc"][0, :, n:] == c["kc"][1, :, n:]).any(axis=-1).any() and not (c["kc"][0, :, :n] == c["kc"][2, :, :n]).any(axis=-1).any()
+
+
+def test_the_bound_sees_a_wrong_key_set():
+    """for every paged case: a key left out, a key counted twice, one page taken from the neighbour sequence — each moves the float64
+    `out` by more than ten times the bound the GPU file holds the kernels to"""
+    worst = {}
+    for key in C.paged_case_keys():
+        c = C.attn_case(*key)
+        o64, _ = C.attn_ref64(key)
+        bound = 4 * C.case_d_ref(key)
+        for mutation in ("drop", "dup", "page"):
+            dev = float(np.abs(C.attn_reference_mutated(c, mutation) - o64).max() / np.abs(o64).max())
+            worst[mutation] = min(worst.get(mutation, np.inf), dev / bound)
+            assert dev > 10 * bound, f"{key}: '{mutation}' moves out by {dev:.3e}, bound {bound:.3e}"
+    print("smallest effect of a mutation, in units of the bound:", {m: f"{v:.0f}" for m, v in worst.items()})
+
+
+def test_prefill_page_slots_properties():
+    """distinct slots; a row's pages on both slabs and in no order; shared exactly where asked; seeded"""
+    for key in C.paged_case_keys():
+        n_seq, n_pg, shared = key[4], key[6] // C.PAGE, key[7]
+        s = C.case_page_slots(key)
+        assert s.shape == (n_seq, n_pg) and s.dtype == np.int32 and s.min() >= 0 and s.max() < 2 * C.SLAB_SLOTS
+        assert (s == C.case_page_slots(key)).all()
+        for r in range(n_seq):
+            assert len(set(s[r].tolist())) == n_pg and len(set((s[r] // C.SLAB_SLOTS).tolist())) == 2
+            assert n_pg <= 2 or not (np.diff(s[r]) > 0).all()
+        flat = s.ravel().tolist()
+        if not shared:
+            assert len(set(flat)) == len(flat)
+        else:
+            assert (s[0, :shared] == s[1, :shared]).all()
+            priv = np.concatenate([s[0], s[1, shared:], s[2]]).tolist()
+            assert len(set(priv)) == len(priv) == len(set(flat))
+            p = C.case_page_slots(key, private=True)
+            assert len(set(p.ravel().tolist())) == p.size and (p[0] == s[0]).all() and (p[2] == s[2]).all() and (p[1, shared:] == s[1, shared:]).all()
+        if C.is_long(key):
+            assert sorted(flat) == list(range(64))          # both slabs full
+    one = C.prefill_page_slots(3, 4, 1, 5)
+    assert one.max() < C.SLAB_SLOTS and len(set(one.ravel().tolist())) == 12
+    assert not (C.prefill_page_slots(3, 4, 2, 5) == C.prefill_page_slots(3, 4, 2, 6)).all()
+
+
+def test_paged_entry_refuses_before_a_device_is_touched():
+    """Q3_INVALID_ARG (1) / Q3_UNSUPPORTED (7) for everything the paged form cannot run — slot range, the sharing rule, max_seq, the
+    layer — on a machine without a GPU, where a call that passes validation ends as Q3_NO_DEVICE (5)"""
+    from qwen3_tts_rs_amd import _lib
+    I, U = 1, 7
+    key = C.paged_key(2, 1, C.SHARED["rps"], C.SHARED["base"], C.SHARED["n_seq"], shared=C.SHARED["pages"])
+    c = C.attn_case(*key)
+    good = C.case_page_slots(key)
+
+    def run(slots=good, kc=None, max_seq=None, **kw):
+        ms = c["max_seq"] if max_seq is None else max_seq
+        rc, rs = C.rope(ms)
+        kcache = c["kc"] if kc is None else kc
+        vcache = c["vc"] if max_seq is None else np.zeros((3, 1, ms, 128), np.float32)
+        if max_seq is not None:
+            kcache = vcache
+        a = dict(layout=1, n_layers=2, layer=1, n_slabs=2, page_slots=slots, kernel=GEN_T); a.update(kw)
+        try:
+            q.attn_prefill_ex(c["qkv"], 3, c["base"], c["qw"], c["kw"], C.EPS, rc, rs, kcache, vcache, 2, 1, **a)
+        except _lib.Q3Error as e:
+            return e.status
+        return 0
+
+    def with_(r, i, v):
+        s = good.copy(); s[r, i] = v
+        return s
+    have_gpu = _lib.lib.q3_device_count() > 0
+    if not have_gpu:
+        assert run() == 5 and run(slots=C.case_page_slots(key, private=True)) == 5
+    assert run(slots=with_(2, 3, 64)) == I and run(slots=with_(2, 3, -1)) == I          # slot range
+    assert run(slots=with_(2, 3, 32), n_slabs=1) == I
+    assert run(slots=with_(2, 1, good[2, 0])) == I                                       # one row, one slot twice
+    assert run(slots=with_(2, 0, good[0, 0])) == I                                       # shared below base, but the rows differ
+    assert run(slots=with_(1, 2, good[0, 2])) == I                                       # page 2 reaches beyond base_pos = 256
+    assert run(slots=with_(1, 1, good[0, 0])) == I                                       # page 1 of one sequence, page 0 of another
+    kc = c["kc"].copy(); kc[1, 0, 255, 127] = np.nextafter(kc[1, 0, 255, 127], np.float32(9))
+    assert run(kc=kc) == I                                                               # one bit of a shared page differs
+    assert run(layer=2) == I and run(layer=-1) == I and run(n_layers=5, layer=4) == I and run(n_layers=0, layer=0) == I
+    assert run(n_slabs=3) == I and run(n_slabs=0) == I and run(page_slots=None) == I
+    assert run(layout=3) == I and run(layout=-1) == I
+    assert run(layout=2) == U                                                            # bf16 pages: prefill never runs on them
+    assert run(slots=np.zeros((3, 65), np.int32), max_seq=65 * 128) == I                 # beyond 64 pages of 128
+    # the contiguous form is untouched by all of this
+    a = _lib.CAttnPrefillEx()
+    assert _lib.lib.q3_attn_prefill_ex(0, a) == I
