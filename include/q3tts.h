@@ -586,6 +586,11 @@ typedef struct q3_conv_ex_args {
     float* y; float* y2;
 } q3_conv_ex_args;
 q3_status q3_conv_ex(int device, const q3_conv_ex_args* args);
+/* Test API: q3_conv_ex under a residency cap — at most `resident` workgroups of the launch per CU (0 = none: q3_conv_ex itself),
+ * the cap the session's overlapped decode puts on the vocoder launches that run beside the frame loop (Q3_DECODE_RESIDENT). The cap
+ * is padding of the launch's dynamic LDS; the kernels and their results are the same. *lds_bytes (optional) receives the dynamic
+ * LDS the launch asked for. Q3_UNSUPPORTED for a shape whose kernel has only static LDS (nothing to cap). */
+q3_status q3_test_conv_resident(int device, const q3_conv_ex_args* args, int resident, int* lds_bytes);
 /* Test API: which geometry launch_lm_gemm (the long-prompt prefill GEMM) picks for a shape — the launcher's own decision function,
  * no GPU needed. norm / w2 / planes != 0: a fused input RMSNorm, a second (SwiGLU "up") matrix, pre-split activation planes with
  * the split-K workspace q3_gemm_ex passes. Returns the geometry (0 = geometry 1 with the split in the kernel, 1 = geometry 1 over

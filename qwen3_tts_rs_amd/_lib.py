@@ -308,6 +308,7 @@ SYMBOLS = {
     "q3_resunit_path": (c_int, [c_int] * 6),
     "q3_conv_path_name": (c_char_p, [c_int]),
     "q3_conv_ex": (c_int, [c_int, P(CConvEx)]),
+    "q3_test_conv_resident": (c_int, [c_int, P(CConvEx), c_int, P(ctypes.c_int32)]),
     "q3_gemm_path": (c_int, [c_int] * 7 + [P(ctypes.c_int32)]),
     "q3_gemm_ex": (c_int, [c_int, P(CGemmEx)]),
     "q3_attn_prefill_path": (c_int, [c_int] * 4 + [P(ctypes.c_int32)]),

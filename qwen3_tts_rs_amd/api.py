@@ -2422,12 +2422,14 @@ def conv_ex(kind: int, x: np.ndarray, w: np.ndarray, *, dil: int = 1, stride: in
             post=None, mid=None, resid: Optional[np.ndarray] = None, resid_in_place: bool = False, scale: Optional[np.ndarray] = None,
             act: int = 0, planes: int = 3, packed: bool = True, snake_raw: bool = False, w2: Optional[np.ndarray] = None,
             b2: Optional[np.ndarray] = None, y: Optional[np.ndarray] = None, y2: Optional[np.ndarray] = None, y_front: int = 0,
-            y2_is_x: bool = False, device: int = 0):
+            y2_is_x: bool = False, device: int = 0, resident: Optional[int] = None):
     """q3_conv_ex: one launch of the vocoder conv family (parity tests). kind 0 = causal conv (w [cout][cin][k]), 1 = transposed conv
     (w [cin][cout][k], k = stride * taps), 2 = residual unit (w [C][C][7], w2 [C][C], y holds the raw tensor and is updated in place).
     x [cin][L]. snake / post / mid: pairs of [C] arrays — (a, 1/b) tables, or (alpha, beta) with snake_raw. y / y2: flat f32 buffers
     whose result starts at y_front; uploaded, written in place and returned whole (y defaults to zeros without guards). Returns
-    (y, y2, path). Raises Q3Error (status 7, with .path) when the launcher refuses the arguments."""
+    (y, y2, path). Raises Q3Error (status 7, with .path) when the launcher refuses the arguments.
+    resident = n (q3_test_conv_resident): the same launch under a residency cap of n workgroups per CU (0 = none); returns
+    (y, y2, path, lds_bytes) with the dynamic LDS the launch asked for."""
     f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
     x = f(x); w = f(w)
     assert x.ndim == 2 and w.ndim == 3
@@ -2461,12 +2463,16 @@ def conv_ex(kind: int, x: np.ndarray, w: np.ndarray, *, dil: int = 1, stride: in
     for (na, nb, pr, n) in (("snake_a", "snake_b", snake, cin), ("post_a", "post_ib", post, cout), ("mid_a", "mid_ib", mid, cout)):
         if pr is not None:
             opt(na, pr[0], n); opt(nb, pr[1], n)
+    lds = ctypes.c_int32(0)
     try:
-        check(lib.q3_conv_ex(device, ctypes.byref(a)))
+        if resident is None:
+            check(lib.q3_conv_ex(device, ctypes.byref(a)))
+        else:
+            check(lib.q3_test_conv_resident(device, ctypes.byref(a), int(resident), ctypes.byref(lds)))
     except _lib.Q3Error as e:
         e.path = path.value
         raise
-    return y, y2, path.value
+    return (y, y2, path.value) if resident is None else (y, y2, path.value, lds.value)
 
 
 def norm_c(x: np.ndarray, w: np.ndarray, b: Optional[np.ndarray] = None, eps: float = 1e-6, y: Optional[np.ndarray] = None,

@@ -131,25 +131,27 @@ static const void* packed_of(const float* w) { return tl_codec_model ? tl_codec_
 // bf16 planes per operand in the vocoder's matrix-core convs (q3_model_set_codec_planes): only codec_decode_dev sets 2,
 // for its own launches — the encoders that share the kernels (speaker / speech tokenizer) always run the exact products
 static thread_local int tl_codec_planes = 3;
+static thread_local int tl_codec_resident = 0;                    // ConvArgs::resident of the decode running on this thread
 // what one decode sets for the launch helpers below: the model (packed weights) and the planes of ITS launches
-CodecScope::CodecScope(const q3_model* m) {
+CodecScope::CodecScope(const q3_model* m, int resident_) {
     // Q3_CODEC_PLANES=2|3: A/B aid, overrides q3_model_set_codec_planes for the vocoder only (never the encoders)
     static const int env_planes = [] { const char* e = getenv("Q3_CODEC_PLANES"); const int v = e ? atoi(e) : 0; return (v == 2 || v == 3) ? v : 0; }();
     planes = env_planes ? env_planes : m->codec_planes;
-    tl_codec_model = m; tl_codec_planes = planes;
+    resident = resident_ < 0 ? 0 : resident_;
+    tl_codec_model = m; tl_codec_planes = planes; tl_codec_resident = resident;
 }
-CodecScope::~CodecScope() { tl_codec_planes = 3; }
+CodecScope::~CodecScope() { tl_codec_planes = 3; tl_codec_resident = 0; }
 static hipError_t conv1(const float* x, const float* w, const float* b, float* y, int cin, int cout, int L, hipStream_t st,
                         const float* resid = nullptr, const float* scale = nullptr, int act = 0,
                         const float* sa = nullptr, const float* sib = nullptr) {
     ConvArgs a; a.x = x; a.w = w; a.b = b; a.y = y; a.cin = cin; a.cout = cout; a.L = L; a.k = 1; a.dil = 1;
-    a.resid = resid; a.scale = scale; a.act = act; a.snake_a = sa; a.snake_b = sib; a.wpk = packed_of(w); a.planes = tl_codec_planes;
+    a.resid = resid; a.scale = scale; a.act = act; a.snake_a = sa; a.snake_b = sib; a.wpk = packed_of(w); a.planes = tl_codec_planes; a.resident = tl_codec_resident;
     return launch_conv1d(a, st);
 }
 static hipError_t convk(const float* x, const float* w, const float* b, float* y, int cin, int cout, int L, int k, int dil,
                         hipStream_t st, const float* sa = nullptr, const float* sib = nullptr, int act = 0) {
     ConvArgs a; a.x = x; a.w = w; a.b = b; a.y = y; a.cin = cin; a.cout = cout; a.L = L; a.k = k; a.dil = dil;
-    a.snake_a = sa; a.snake_b = sib; a.act = act; a.wpk = packed_of(w); a.planes = tl_codec_planes;
+    a.snake_a = sa; a.snake_b = sib; a.act = act; a.wpk = packed_of(w); a.planes = tl_codec_planes; a.resident = tl_codec_resident;
     return launch_conv1d(a, st);
 }
 
@@ -227,7 +229,7 @@ q3_status codec_front_transformer(const q3_model* m, CodecWS& ws, int T, hipStre
 }
 // D4-D9, the convolutional stack: latent cur [LAT][L] (ws.bufC or ws.bufF) → ws.pcm [L*spf]
 q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, int L, hipStream_t st, float** taps, const CodecScope& scope) {
-    const int NPL = scope.planes;
+    const int NPL = scope.planes, RES = scope.resident;
     const q3_config& c = m->cfg;
     const int LAT = c.dec_latent;
     auto TAP = [&](int id, const float* dev, size_t n) -> q3_status { return tap_out(taps, id, dev, n, st); };
@@ -236,7 +238,7 @@ q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, int L, hip
     for (int i = 0; i < 2; ++i) {
         const UpW& U = m->up[i];
         float* upo = (cur == C) ? A : C;            // transconv output [LAT][L*r]
-        HIPC(launch_transconv1d_taps(cur, U.tw, U.tb, upo, LAT, LAT, L, U.ratio, 1, nullptr, nullptr, st, nullptr, nullptr, nullptr, m->pk(U.tw), NPL));
+        HIPC(launch_transconv1d_taps(cur, U.tw, U.tb, upo, LAT, LAT, L, U.ratio, 1, nullptr, nullptr, st, nullptr, nullptr, nullptr, m->pk(U.tw), NPL, nullptr, RES));
         L *= U.ratio;
         // dwconv → LN → pw1+GELU → pw2·gamma + residual (in place into upo)
         float* dw = (upo == A) ? C : A;             // [LAT][L]
@@ -260,7 +262,7 @@ q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, int L, hip
     // decoder.0 (k=7): raw only if tapped; activated with block 0's snake
     float* xact = other({cur});
     {
-        ConvArgs a; a.x = cur; a.w = m->init_w; a.wpk = m->pk(m->init_w); a.b = m->init_b; a.cin = LAT; a.cout = Cc; a.L = L; a.k = 7; a.dil = 1; a.planes = NPL;
+        ConvArgs a; a.x = cur; a.w = m->init_w; a.wpk = m->pk(m->init_w); a.b = m->init_b; a.cin = LAT; a.cout = Cc; a.L = L; a.k = 7; a.dil = 1; a.planes = NPL; a.resident = RES;
         a.post_a = m->blk[0].a; a.post_ib = m->blk[0].ib;
         if (taps && taps[Q3_DEC_INIT]) { float* raw = other({cur, xact}); a.y = raw; a.y2 = xact; HIPC(launch_conv1d(a, st)); Q3C(TAP(Q3_DEC_INIT, raw, (size_t)Cc * L)); }
         else { a.y = xact; HIPC(launch_conv1d(a, st)); }
@@ -271,7 +273,7 @@ q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, int L, hip
         // transposed conv: raw Y (residual of unit 0) + YA = snake(act1 of unit 0)
         float* Y = other({xact});
         float* YA = other({xact, Y});
-        HIPC(launch_transconv1d_taps(xact, Bk.tw, Bk.tb, Y, Bk.cin, Bk.cout, L, Bk.rate, 2, nullptr, nullptr, st, Bk.res[0].a1, Bk.res[0].ib1, YA, m->pk(Bk.tw), NPL));
+        HIPC(launch_transconv1d_taps(xact, Bk.tw, Bk.tb, Y, Bk.cin, Bk.cout, L, Bk.rate, 2, nullptr, nullptr, st, Bk.res[0].a1, Bk.res[0].ib1, YA, m->pk(Bk.tw), NPL, nullptr, RES));
         L *= Bk.rate; Cc = Bk.cout;
         float* T2 = other({Y, YA});
         for (int uu = 0; uu < 3; ++uu) {
@@ -281,18 +283,18 @@ q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, int L, hip
             {   // 96 / 192 channels: the whole unit in one launch (raw tensor updated in place, activated copy into T2)
                 ResUnitArgs r{};
                 r.xa = YA; r.y = Y; r.ya = T2; r.w1pk = m->pk(R.c1w); r.w2pk = m->pk(R.c2w); r.b1 = R.c1b; r.b2 = R.c2b;
-                r.mid_a = R.a2; r.mid_ib = R.ib2; r.post_a = nxt_a; r.post_ib = nxt_ib; r.C = Cc; r.L = L; r.dil = dils[uu]; r.planes = NPL;
+                r.mid_a = R.a2; r.mid_ib = R.ib2; r.post_a = nxt_a; r.post_ib = nxt_ib; r.C = Cc; r.L = L; r.dil = dils[uu]; r.planes = NPL; r.resident = RES;
                 const hipError_t e = launch_resunit(r, st);
                 if (e == hipSuccess) { float* t = YA; YA = T2; T2 = t; continue; }
                 if (e != hipErrorNotSupported) HIPC(e);
             }
             {   // conv7 (dilated) on the activated input; output activated with act2
-                ConvArgs a; a.x = YA; a.w = R.c1w; a.wpk = m->pk(R.c1w); a.b = R.c1b; a.y = T2; a.cin = Cc; a.cout = Cc; a.L = L; a.k = 7; a.dil = dils[uu]; a.planes = NPL;
+                ConvArgs a; a.x = YA; a.w = R.c1w; a.wpk = m->pk(R.c1w); a.b = R.c1b; a.y = T2; a.cin = Cc; a.cout = Cc; a.L = L; a.k = 7; a.dil = dils[uu]; a.planes = NPL; a.resident = RES;
                 a.post_a = R.a2; a.post_ib = R.ib2;
                 HIPC(launch_conv1d(a, st));
             }
             {   // conv1 + residual: raw → Y (in place), activated → YA for the next consumer
-                ConvArgs a; a.x = T2; a.w = R.c2w; a.wpk = m->pk(R.c2w); a.b = R.c2b; a.y = Y; a.y2 = YA; a.cin = Cc; a.cout = Cc; a.L = L; a.k = 1; a.dil = 1; a.resid = Y; a.planes = NPL;
+                ConvArgs a; a.x = T2; a.w = R.c2w; a.wpk = m->pk(R.c2w); a.b = R.c2b; a.y = Y; a.y2 = YA; a.cin = Cc; a.cout = Cc; a.L = L; a.k = 1; a.dil = 1; a.resid = Y; a.planes = NPL; a.resident = RES;
                 if (uu < 2) { a.post_a = Bk.res[uu + 1].a1; a.post_ib = Bk.res[uu + 1].ib1; }
                 else if (b < 3) { a.post_a = m->blk[b + 1].a; a.post_ib = m->blk[b + 1].ib; }
                 else { a.post_a = m->fin_a; a.post_ib = m->fin_ib; }
@@ -312,9 +314,9 @@ q3_status codec_stack_dev(const q3_model* m, CodecWS& ws, float* cur, int L, hip
 // pre-transformer: everything with unbounded left context, and cheap) runs over all T frames, the convolutional
 // stack only over frames [c0, T), and ws.pcm = [(T-c0)*spf]; samples of frames >= c0 + CODEC_CTX_FRAMES are
 // identical to the whole-utterance decode (every kernel sums each output in a position-independent order).
-q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st, float** taps, int c0) {
+q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st, float** taps, int c0, int resident) {
     const q3_config& c = m->cfg;
-    const CodecScope scope(m);
+    const CodecScope scope(m, resident);
     const int Q = c.dec_q_dim, LAT = c.dec_latent;
     float *B = ws.bufB, *C = ws.bufC;
     Q3C(codec_front_quant(m, ws, T, st));

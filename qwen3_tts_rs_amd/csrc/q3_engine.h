@@ -535,10 +535,12 @@ Q3_HIDDEN void retile_bf16(const uint16_t* src, int N, int K, uint16_t* dst, int
 // q3_codec_run.hip
 Q3_HIDDEN q3_status codec_reserve(const q3_model* m, CodecWS& ws, int T, int Tf = 0);
 Q3_HIDDEN int samples_per_frame(const q3_config& c);
-Q3_HIDDEN q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st, float** taps, int c0 = 0);
+// resident: residency cap of this decode's matrix-core launches (ConvArgs::resident): 0 = none; n >= 1 = at most n workgroups of a
+// launch per CU — for a decode that runs beside the frame loop (q3_session_run) and must leave every CU room for a frame workgroup
+Q3_HIDDEN q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st, float** taps, int c0 = 0, int resident = 0);
 // the stages of codec_decode_dev, for the codec stream (q3_codec_stream.hip). A CodecScope must be alive on the calling thread
-// while they run: it names the model (packed weights) and the bf16 planes (q3_model_set_codec_planes) of their launches.
-struct Q3_HIDDEN CodecScope { int planes; explicit CodecScope(const q3_model* m); ~CodecScope(); CodecScope(const CodecScope&) = delete; };
+// while they run: it names the model (packed weights), the bf16 planes (q3_model_set_codec_planes) and the residency cap of their launches.
+struct Q3_HIDDEN CodecScope { int planes, resident; explicit CodecScope(const q3_model* m, int resident = 0); ~CodecScope(); CodecScope(const CodecScope&) = delete; };
 using CodecAttnFn = std::function<q3_status(int layer, float* q, float* k, float* v, float* ao)>;
 Q3_HIDDEN q3_status codec_rope_table(const q3_config& c, int n, float* cs_dev, float* sn_dev);
 Q3_HIDDEN q3_status codec_front_quant(const q3_model* m, CodecWS& ws, int T, hipStream_t st);

@@ -343,7 +343,13 @@ struct ConvArgs {
     float* y2 = nullptr;             // if set: y = raw output, y2 = activated output; else y = activated output
     const void* wpk = nullptr;       // bf16x3-packed copy of w (launch_pack_conv_w) → bf16 matrix-core kernel; else f32 MFMA
     int planes = 3;                  // bf16 planes per operand used by the matrix-core kernel: 3 = f32-exact products, 2 = ~2^-17
+    int resident = 0;                // residency cap: at most this many workgroups of the launch per CU (conv_resident_lds); 0 = none
 };
+// The residency cap of the matrix-core conv launches: the dynamic-LDS size a launch that needs `lds` bytes asks for so that at most
+// `resident` of its workgroups fit a CU's 160 KB (resident < 1: lds itself). Pure host function. conv_last_dyn_lds: what this
+// thread's latest such launch asked for (the op-level tests read it).
+size_t conv_resident_lds(size_t lds, int resident);
+size_t conv_last_dyn_lds();
 // one-time split of f32 conv weights [cout][cin][K] into bf16 hi/mid/lo MFMA A-operand tiles (cout % 32 == 0, cin % 16 == 0)
 hipError_t launch_pack_conv_w(const float* w, void* out, int cout, int cin, int K, hipStream_t st);
 size_t packed_conv_w_bytes(int cout, int cin, int K);
@@ -389,6 +395,7 @@ struct ResUnitArgs {
     const float* mid_a; const float* mid_ib; const float* post_a; const float* post_ib;
     int C, L, dil;
     int planes = 3;                  // as ConvArgs::planes
+    int resident = 0;                // as ConvArgs::resident
 };
 hipError_t launch_resunit(const ResUnitArgs& r, hipStream_t st, int* path = nullptr);
 // polyphase transposed conv: wp = per-phase causal-conv weights [stride][cout][cin][taps]
@@ -396,7 +403,7 @@ hipError_t launch_transconv1d_taps(const float* x, const float* wp, const float*
                                    int stride, int taps, const float* snake_a, const float* snake_ib, hipStream_t st,
                                    const float* post_a = nullptr, const float* post_ib = nullptr, float* y2 = nullptr,
                                    const void* wpk = nullptr,    // wpk: per-phase packed weights, phase-major
-                                   int planes = 3, int* path = nullptr);
+                                   int planes = 3, int* path = nullptr, int resident = 0);    // resident: as ConvArgs::resident
 // ConvTranspose1d weights [cin][cout][k] -> the per-phase causal-conv weights above (host; k % stride == 0)
 void transconv_phase_weights(const float* w, int cin, int cout, int k, int stride, float* out);
 hipError_t launch_snake_tables(const float* alpha, const float* beta, float* a, float* ib, int C, hipStream_t st);

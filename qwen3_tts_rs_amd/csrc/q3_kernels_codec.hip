@@ -9,6 +9,7 @@
 // snake_beta.rs:58-77.
 #include "q3_kernels.h"
 
+#include <atomic>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -820,6 +821,51 @@ __global__ __launch_bounds__(64 * NW, 3) void k_resunit_bf16x3(ResUnitDev a) {
 
 static int conv_planes(int asked) { return asked == 2 ? 2 : 3; }      // ConvArgs::planes: anything but 2 means the exact products
 
+// ------------------------------------------------------------------------------------------------
+// Residency cap (ConvArgs::resident): at most n workgroups of a launch per CU, so that a decode running BESIDE the frame loop
+// leaves room on every CU for a frame kernel's workgroup. The matrix-core kernels take their x tile as dynamic LDS (at most
+// 44 KB); a CU has 160 KB, so a launch that asks for more than 160 KB / (n + 1) holds n workgroups per CU. The kernels do not
+// change and never look at the size: per output the same arithmetic, the same bits. 0 = no cap: the launch as it always was.
+// ------------------------------------------------------------------------------------------------
+// (sizes are rounded up to 1280 bytes, the gfx950 allocation granule of 320 dwords; with 512-byte granules the n = 1 and n = 2
+//  sizes, 83 200 and 55 040 bytes, still fit a CU n times and not n + 1 times)
+constexpr size_t CU_LDS_BYTES = 160 * 1024, LDS_GRANULE = 1280;
+size_t conv_resident_lds(size_t lds, int resident) {
+    if (resident < 1) return lds;
+    const size_t cap = (CU_LDS_BYTES / ((size_t)resident + 1) + 1 + LDS_GRANULE - 1) / LDS_GRANULE * LDS_GRANULE;
+    return lds > cap ? lds : cap;
+}
+static thread_local size_t tl_last_dyn_lds = 0;                       // dynamic LDS of this thread's latest matrix-core conv launch
+size_t conv_last_dyn_lds() { return tl_last_dyn_lds; }
+// The dynamic-LDS size to launch kernel instance `fn` with. Above 64 KB a kernel needs its limit raised (once per instance and
+// device: `raised` is the launch site's own flag set, 0 = not tried, 1 = raised, -1 = refused); where the runtime refuses, this
+// instance runs without the cap rather than not at all.
+static size_t capped_lds(const void* fn, std::atomic<int>* raised, size_t lds, int resident) {
+    size_t want = conv_resident_lds(lds, resident);
+    if (want > 64 * 1024) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) want = lds;
+        else {
+            int r = raised[dev].load(std::memory_order_acquire);
+            if (r == 0) {
+                r = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv_resident_lds(0, 1)) == hipSuccess ? 1 : -1;
+                if (r < 0) (void)hipGetLastError();
+                raised[dev].store(r, std::memory_order_release);
+            }
+            if (r < 0) want = lds;
+        }
+    }
+    tl_last_dyn_lds = want;
+    return want;
+}
+// one capped launch of kernel instance KERNEL (a parenthesised template-id): the function-local flags belong to that instance
+#define Q3_LAUNCH_CAPPED(KERNEL, grid, blk, lds, resident, st, ...)                                                              \
+    do {                                                                                                                       \
+        static std::atomic<int> raised_[16];                                                                                   \
+        const size_t lds_ = capped_lds(reinterpret_cast<const void*>(&KERNEL), raised_, (lds), (resident));                    \
+        hipLaunchKernelGGL(KERNEL, grid, blk, lds_, st, __VA_ARGS__);                                                          \
+    } while (0)
+
 // The acceptance rule of launch_resunit as a pure host function (CK_NONE: the caller runs the two convs). `complete`: both
 // packed weights, the middle SnakeBeta and the x / y tensors are there; `ya_is_xa`: the activated output would alias the operand.
 ConvPath resunit_pick(int C, int L, int dil, bool complete, bool ya_is_xa, int planes) {
@@ -849,11 +895,11 @@ hipError_t launch_resunit(const ResUnitArgs& r, hipStream_t st, int* path) {
     const size_t lds = lds_x > lds_mid ? lds_x : lds_mid;
     const dim3 grid((r.L + 127) / 128);
     if (np == 2) {
-        if (r.C == 96) hipLaunchKernelGGL((k_resunit_bf16x3<3, 2>), grid, dim3(192), lds, st, a);
-        else hipLaunchKernelGGL((k_resunit_bf16x3<6, 2>), grid, dim3(384), lds, st, a);
+        if (r.C == 96) Q3_LAUNCH_CAPPED((k_resunit_bf16x3<3, 2>), grid, dim3(192), lds, r.resident, st, a);
+        else Q3_LAUNCH_CAPPED((k_resunit_bf16x3<6, 2>), grid, dim3(384), lds, r.resident, st, a);
     } else {
-        if (r.C == 96) hipLaunchKernelGGL((k_resunit_bf16x3<3, 3>), grid, dim3(192), lds, st, a);
-        else hipLaunchKernelGGL((k_resunit_bf16x3<6, 3>), grid, dim3(384), lds, st, a);
+        if (r.C == 96) Q3_LAUNCH_CAPPED((k_resunit_bf16x3<3, 3>), grid, dim3(192), lds, r.resident, st, a);
+        else Q3_LAUNCH_CAPPED((k_resunit_bf16x3<6, 3>), grid, dim3(384), lds, r.resident, st, a);
     }
     return hipGetLastError();
 }
@@ -950,7 +996,7 @@ __global__ __launch_bounds__(64 * W) void k_lin_small_bf16x3(ConvDev a) {
 }
 
 template <int K, int CO_M, int T_M, int WCO, int WT, int NP>
-static hipError_t launch_bf16x3_vp(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
+static hipError_t launch_bf16x3_vp(const ConvPath& p, const ConvDev& a, int phases, int resident, hipStream_t st) {
     constexpr int CO_WG = 32 * CO_M * WCO, T_WG = 32 * T_M * WT;
     constexpr bool K1 = K == 1;
     constexpr int CIS1 = T_WG <= 64 ? 128 : 32;                   // the stage width conv_pick may ask of this geometry besides 32
@@ -964,7 +1010,7 @@ static hipError_t launch_bf16x3_vp(const ConvPath& p, const ConvDev& a, int phas
     const dim3 blk(64 * WCO * WT);
     if constexpr (K1) {
         const bool pre = p.pre;
-#define Q3_CV(P, S, C) hipLaunchKernelGGL((k_conv_bf16x3<K, CO_M, T_M, WCO, WT, P, S, C, NP>), grid, blk, lds, st, ap)
+#define Q3_CV(P, S, C) Q3_LAUNCH_CAPPED((k_conv_bf16x3<K, CO_M, T_M, WCO, WT, P, S, C, NP>), grid, blk, lds, resident, st, ap)
         if (wide) {
             if (segm) { if (pre) Q3_CV(CO_M == 1, true, CIS1); else Q3_CV(false, true, CIS1); }
             else { if (pre) Q3_CV(CO_M == 1, false, CIS1); else Q3_CV(false, false, CIS1); }
@@ -977,7 +1023,7 @@ static hipError_t launch_bf16x3_vp(const ConvPath& p, const ConvDev& a, int phas
     // between two barriers — was measured and lost at every width: 614 -> 645, 791 -> 903, 880 -> 1209, 841 -> 1260 us;
     // the larger x tile costs the 96-channel geometry its third workgroup per CU)
     } else {
-        hipLaunchKernelGGL((k_conv_bf16x3<K, CO_M, T_M, WCO, WT, false, false, 32, NP>), grid, blk, lds, st, ap);
+        Q3_LAUNCH_CAPPED((k_conv_bf16x3<K, CO_M, T_M, WCO, WT, false, false, 32, NP>), grid, blk, lds, resident, st, ap);
     }
     return hipGetLastError();
 }
@@ -986,22 +1032,22 @@ static hipError_t launch_bf16x3_vp(const ConvPath& p, const ConvDev& a, int phas
 // whole-utterance decodes still agree
 static bool conv_two_plane_taps(int k) { return k == 1 || k == 2 || k == 7; }
 template <int K, int CO_M, int T_M, int WCO, int WT>
-static hipError_t launch_bf16x3_v(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
+static hipError_t launch_bf16x3_v(const ConvPath& p, const ConvDev& a, int phases, int resident, hipStream_t st) {
     if constexpr (K == 1 || K == 2 || K == 7)
-        if (p.np == 2) return launch_bf16x3_vp<K, CO_M, T_M, WCO, WT, 2>(p, a, phases, st);
+        if (p.np == 2) return launch_bf16x3_vp<K, CO_M, T_M, WCO, WT, 2>(p, a, phases, resident, st);
     if (p.np != 3) return hipErrorInvalidValue;
-    return launch_bf16x3_vp<K, CO_M, T_M, WCO, WT, 3>(p, a, phases, st);
+    return launch_bf16x3_vp<K, CO_M, T_M, WCO, WT, 3>(p, a, phases, resident, st);
 }
 template <int K>
-static hipError_t launch_bf16x3_k(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
+static hipError_t launch_bf16x3_k(const ConvPath& p, const ConvDev& a, int phases, int resident, hipStream_t st) {
     switch (p.kernel) {
-        case CK_BF16X3_96x128_TM4: return launch_bf16x3_v<K, 1, 4, 3, 1>(p, a, phases, st);
-        case CK_BF16X3_4Wx32x128: return launch_bf16x3_v<K, 1, 4, 4, 1>(p, a, phases, st);
-        case CK_BF16X3_4Wx32x256: return launch_bf16x3_v<K, 1, 8, 4, 1>(p, a, phases, st);
-        case CK_BF16X3_64x128: return launch_bf16x3_v<K, 1, 2, 2, 2>(p, a, phases, st);
-        case CK_BF16X3_64x64: return launch_bf16x3_v<K, 1, 1, 2, 2>(p, a, phases, st);
-        case CK_BF16X3_128x128: return launch_bf16x3_v<K, 2, 2, 2, 2>(p, a, phases, st);
-        case CK_BF16X3_96x128_6W: return launch_bf16x3_v<K, 1, 2, 3, 2>(p, a, phases, st);
+        case CK_BF16X3_96x128_TM4: return launch_bf16x3_v<K, 1, 4, 3, 1>(p, a, phases, resident, st);
+        case CK_BF16X3_4Wx32x128: return launch_bf16x3_v<K, 1, 4, 4, 1>(p, a, phases, resident, st);
+        case CK_BF16X3_4Wx32x256: return launch_bf16x3_v<K, 1, 8, 4, 1>(p, a, phases, resident, st);
+        case CK_BF16X3_64x128: return launch_bf16x3_v<K, 1, 2, 2, 2>(p, a, phases, resident, st);
+        case CK_BF16X3_64x64: return launch_bf16x3_v<K, 1, 1, 2, 2>(p, a, phases, resident, st);
+        case CK_BF16X3_128x128: return launch_bf16x3_v<K, 2, 2, 2, 2>(p, a, phases, resident, st);
+        case CK_BF16X3_96x128_6W: return launch_bf16x3_v<K, 1, 2, 3, 2>(p, a, phases, resident, st);
         default: return hipErrorInvalidValue;
     }
 }
@@ -1170,7 +1216,8 @@ __global__ __launch_bounds__(256) void k_conv_out1_v4(ConvDev a) {
 }
 
 // one launch of the kernel instance conv_pick named
-static hipError_t launch_conv_path(const ConvPath& p, const ConvDev& a, int phases, hipStream_t st) {
+// (resident: ConvArgs::resident — only the kernels with dynamic LDS can be capped; the others are short and small)
+static hipError_t launch_conv_path(const ConvPath& p, const ConvDev& a, int phases, int resident, hipStream_t st) {
     switch (p.kernel) {
         case CK_NONE: return p.refusal != hipSuccess ? p.refusal : hipErrorInvalidValue;
         case CK_OUT1_V4: hipLaunchKernelGGL(k_conv_out1_v4, dim3((a.L / 4 + 255) / 256), dim3(256), 0, st, a); break;
@@ -1196,11 +1243,11 @@ static hipError_t launch_conv_path(const ConvPath& p, const ConvDev& a, int phas
         }
         default:
             switch (a.k) {
-                case 1: return launch_bf16x3_k<1>(p, a, phases, st);
-                case 2: return launch_bf16x3_k<2>(p, a, phases, st);
-                case 3: return launch_bf16x3_k<3>(p, a, phases, st);
-                case 5: return launch_bf16x3_k<5>(p, a, phases, st);     // speaker encoder front TDNN
-                case 7: return launch_bf16x3_k<7>(p, a, phases, st);
+                case 1: return launch_bf16x3_k<1>(p, a, phases, resident, st);
+                case 2: return launch_bf16x3_k<2>(p, a, phases, resident, st);
+                case 3: return launch_bf16x3_k<3>(p, a, phases, resident, st);
+                case 5: return launch_bf16x3_k<5>(p, a, phases, resident, st);     // speaker encoder front TDNN
+                case 7: return launch_bf16x3_k<7>(p, a, phases, resident, st);
                 default: return hipErrorInvalidValue;
             }
     }
@@ -1218,7 +1265,7 @@ hipError_t launch_conv1d(const ConvArgs& c, hipStream_t st, int* path) {
     a.ostride = 1; a.ooff = 0; a.oL = c.L; a.w_phase_stride = 0; a.ooff_phase = 0;
     a.post_a = c.post_a; a.post_ib = c.post_ib; a.y2 = c.y2;
     a.wpk = c.wpk; a.wpk_phase_stride = 0; a.planes = conv_planes(c.planes);
-    return launch_conv_path(p, a, 1, st);
+    return launch_conv_path(p, a, 1, c.resident, st);
 }
 
 // Transposed conv, polyphase form. Host code pre-arranges the weight [cin][cout][k] into per-phase
@@ -1227,7 +1274,7 @@ hipError_t launch_conv1d(const ConvArgs& c, hipStream_t st, int* path) {
 // t = j*stride + ph; the right-trim k - s of causal_trans_conv.rs:79 is implicit (length L*stride).
 hipError_t launch_transconv1d_taps(const float* x, const float* wp, const float* b, float* y, int cin, int cout, int L,
                                    int stride, int taps, const float* snake_a, const float* snake_ib, hipStream_t st,
-                                   const float* post_a, const float* post_ib, float* y2, const void* wpk, int planes, int* path) {
+                                   const float* post_a, const float* post_ib, float* y2, const void* wpk, int planes, int* path, int resident) {
     const ConvPath p = conv_pick(cout, cin, L, taps, 1, stride, wpk != nullptr, false, planes, false, true);
     if (path) *path = conv_path_code(p);
     if (p.kernel == CK_NONE) return p.refusal;
@@ -1239,7 +1286,7 @@ hipError_t launch_transconv1d_taps(const float* x, const float* wp, const float*
     a.snake_a = snake_a; a.snake_ib = snake_ib; a.resid = nullptr; a.scale = nullptr; a.act = 0;
     a.ostride = stride; a.ooff = 0; a.oL = L * stride;
     a.w_phase_stride = (size_t)cout * cin * taps; a.ooff_phase = 1;
-    return launch_conv_path(p, a, stride, st);
+    return launch_conv_path(p, a, stride, resident, st);
 }
 
 // [cin][cout][k] (the checkpoint's ConvTranspose1d layout) -> per-phase causal-conv weights [stride][cout][cin][taps], taps = k / stride:

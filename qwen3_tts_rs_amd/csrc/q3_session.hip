@@ -1981,14 +1981,28 @@ extern "C" q3_status q3_session_decode(q3_session* s, int b, int f0, int f1, flo
     return decode_range_on(s, b, f0, f1, s->stream, pcm_host, cap, n_samples);
 }
 
-// synthesize_with_timing for the whole batch. With Q3_DECODE_OVERLAP=1 (and no ICL sequence) the vocoder does not
-// wait for the last frame: every Q3_DECODE_SEG (default 128) generated frames a helper thread enqueues the segment's
+// synthesize_with_timing for the whole batch. In the overlapped path (Q3_DECODE_OVERLAP=1, or unset: DECODE_OVERLAP_DEFAULT
+// below; never with an ICL sequence) the vocoder does not
+// wait for the last frame: every Q3_DECODE_SEG (default 256) generated frames a helper thread enqueues the segment's
 // decode (exact: CODEC_CTX_FRAMES of left context re-run, see codec_decode_dev) on a second stream beside the frame
 // loop, the samples going straight to the caller's buffers; the last Q3_DECODE_TAIL (32) frames of a row are the only
-// segment nothing overlaps. OFF by default — measured again in round 6 (1.7B, 8 x 640 frames, frames on the own queue):
-// the frame loop slows from 1636 to 1767 ms while the decode tail shrinks from 155 to 54 ms (2843 -> 2797 frames/s); the
-// frame loop's workgroups need a whole CU's registers, so vocoder waves already resident on a CU hold them up, and
-// splitting the chip between the two (Q3_DECODE_CUS below) costs the frames more than the vocoder takes.
+// segment nothing overlaps.
+// Why the UNSPLIT overlap lost in round 6 (1.7B, 8 x 640 frames: frame loop 1636 -> 1767 ms, decode tail 155 -> 54 ms,
+// 2843 -> 2797 frames/s): registers. The conv kernels run three workgroups per CU at 150-168 VGPRs per lane, 3 x 160 = 480 of a
+// SIMD's 512. A frame kernel's workgroup is 8 waves, two per SIMD, at 88-168 VGPRs (k_gemv_mfma 101, k_gemv_sk2 118, k_gemv_gu24
+// 152, k_attn_fused 92, k_gemv_lds 166): it needs HALF a CU's registers, 2 x 104..168 per SIMD. A retiring conv workgroup frees
+// 160 per SIMD: only the next conv workgroup of the same launch fits that hole, so the frame node waits until the conv launch
+// drains — for each of 549 dependent nodes. Splitting the chip (Q3_DECODE_CUS below) costs the frames more than the vocoder takes.
+// Hence the residency cap (Q3_DECODE_RESIDENT, default 1; ConvArgs::resident): the segments decoded beside the frames hold one
+// conv workgroup per CU, 160 + 2 x 168 = 496 <= 512 registers per SIMD, so a frame workgroup always finds room on every CU; the
+// tail after the loop runs uncapped on the whole chip. Measured (profiles/decode_resident_overlap_ab.txt): with 128-frame segments
+// the cap turns the loss into a tie (no cap / 1 / 2 per CU: 2789 / 2836 / 2777 frames/s against 2835 serial); each segment re-runs
+// the front over [0, e) and 12 context frames, and with 256-frame segments the capped overlap wins: 2898-2899 against 2836-2847
+// (frame loop +101 ms, exposed decode 160 -> 21 ms). The enqueue thread never holds up the frame loop (Q3_DECODE_LOG: < 0.02 ms).
+// DECODE_OVERLAP_DEFAULT: what Q3_DECODE_OVERLAP unset means for sessions of 2 to 16 rows (16 rows: 3983-4051 -> 4139-4141 frames/s).
+// A single row has 21 ms of vocoder to hide and ends in a tie (413.8-415.3 serial, 414.0-414.6 overlapped): serial. Wider sessions run
+// the k_wide* frame kernels with other register counts and lose 6.5-12.8 % with every overlap variant: serial. DESIGN 4.3 / 7a / 8.3.
+static constexpr bool DECODE_OVERLAP_DEFAULT = true;
 extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_host, const size_t* cap, size_t* n_samples, q3_timing* timing) {
     if (!s) return set_err(Q3_INVALID_ARG, "null session");
     if (any_open_text(s)) return set_err(Q3_UNSUPPORTED, "q3_session_run: a row's text is still open (q3_session_append_text with last != 0 closes it; or drive the session with q3_session_generate)");
@@ -1998,9 +2012,14 @@ extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_ho
     s->precapture = use_graph != 0;
     Q3C(q3_session_prefill(s));
     const auto t1 = clk::now();
-    const int overlap_env = [] { const char* e = getenv("Q3_DECODE_OVERLAP"); return e ? atoi(e) : 0; }();     // read per call: opt-in, tests set it per test
-    static const int seg_env = [] { const char* e = getenv("Q3_DECODE_SEG"); const int v = e ? atoi(e) : 128; return v < 16 ? 16 : v; }();
-    bool overlap = overlap_env != 0 && !s->debug && !s->profile && s->max_frames > seg_env;
+    // read per call (tests set them per test): Q3_DECODE_OVERLAP=0 the serial path, =1 overlap on, unset the default below;
+    // Q3_DECODE_RESIDENT=0|1|2 the residency cap of the segments decoded beside the frames (0 = none: the unsplit overlap of round 6);
+    // Q3_DECODE_SEG / Q3_DECODE_TAIL (below) the segment schedule
+    const int overlap_env = [] { const char* e = getenv("Q3_DECODE_OVERLAP"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+    const int resident_env = [] { const char* e = getenv("Q3_DECODE_RESIDENT"); const int v = e ? atoi(e) : 1; return v < 0 ? 0 : (v > 2 ? 2 : v); }();
+    const int seg_env = [] { const char* e = getenv("Q3_DECODE_SEG"); const int v = e ? atoi(e) : 256; return v < 16 ? 16 : v; }();
+    const bool overlap_wanted = overlap_env >= 0 ? overlap_env != 0 : (DECODE_OVERLAP_DEFAULT && s->B >= 2 && s->B <= 16);
+    bool overlap = overlap_wanted && !s->debug && !s->profile && s->max_frames > seg_env;
     for (auto& q : s->seq) if (!q.ref_codes.empty()) overlap = false;
     const int spf = samples_per_frame(s->m->cfg);
     if (!overlap) {
@@ -2083,6 +2102,7 @@ extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_ho
     if (cus && s->aql && !s->aql_failed) { std::string why; if (q3::aql_restrict_cus(s->aql, 256 - cus, &why)) split.p = s->aql; }
     std::vector<int> dec_pos((size_t)s->B, 0);
     std::thread worker; q3_status wst = Q3_OK; std::string werr;
+    double join_wait_ms = 0.0; int n_dispatch = 0;         // what the frame loop's thread spent waiting for the enqueue thread (Q3_DECODE_LOG)
     auto join = [&]() -> q3_status {
         if (worker.joinable()) worker.join();
         if (wst != Q3_OK) return set_err(wst, "%s", werr.c_str());
@@ -2090,11 +2110,12 @@ extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_ho
     };
     struct Job { int b, a, e; };
     // one segment: codes -> workspace, vocoder over [a - context, e), the samples of [a, e) straight to the caller's buffer
-    auto seg_enqueue = [s, spf, pcm_host, cap](const Job& j, CodecWS& ws, hipStream_t st) -> q3_status {
+    // (resident: the residency cap of this decode's launches — resident_env beside the frames, 0 for the tail on the whole chip)
+    auto seg_enqueue = [s, spf, pcm_host, cap](const Job& j, CodecWS& ws, hipStream_t st, int resident) -> q3_status {
         const int c0 = j.a > CODEC_CTX_FRAMES ? j.a - CODEC_CTX_FRAMES : 0;
         if (pcm_host && pcm_host[j.b] && (!cap || cap[j.b] < (size_t)j.e * spf)) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
         HIPC(hipMemcpyAsync(ws.frames, s->codes + (size_t)j.b * s->max_frames * 16, (size_t)j.e * 16 * 4, hipMemcpyDeviceToDevice, st));
-        Q3C(codec_decode_dev(s->m, ws, j.e, st, nullptr, c0));
+        Q3C(codec_decode_dev(s->m, ws, j.e, st, nullptr, c0, resident));
         if (pcm_host && pcm_host[j.b])
             HIPC(hipMemcpyAsync(pcm_host[j.b] + (size_t)j.a * spf, ws.pcm + (size_t)(j.a - c0) * spf, (size_t)(j.e - j.a) * spf * 4, hipMemcpyDeviceToHost, st));
         return Q3_OK;
@@ -2115,18 +2136,22 @@ extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_ho
     auto dispatch = [&]() -> q3_status {
         std::vector<Job> jobs = collect(false);
         if (jobs.empty()) return Q3_OK;
-        Q3C(join());
-        worker = std::thread([s, jobs, seg_enqueue, &wst, &werr]() {
+        {   // the previous segment's enqueue must be over: normally long since (its thread only enqueues; a segment of frames is ~0.3 s)
+            const auto j0 = clk::now();
+            Q3C(join());
+            join_wait_ms += ms(j0, clk::now()); ++n_dispatch;
+        }
+        worker = std::thread([s, jobs, seg_enqueue, resident_env, &wst, &werr]() {
             if (hipSetDevice(s->m->device) != hipSuccess) { wst = Q3_HIP_ERROR; werr = "hipSetDevice failed in the decode thread"; return; }
             for (const Job& j : jobs) {
-                const q3_status st = seg_enqueue(j, s->seg_ws, s->dec_stream);
+                const q3_status st = seg_enqueue(j, s->seg_ws, s->dec_stream, resident_env);
                 if (st != Q3_OK) { wst = st; werr = q3_last_error(); return; }
             }
         });
         return Q3_OK;
     };
     // the last segment of a row is the only one nothing overlaps: it is kept short (Q3_DECODE_TAIL frames, default 32)
-    static const int tail_env = [] { const char* e = getenv("Q3_DECODE_TAIL"); const int v = e ? atoi(e) : 32; return v < 16 ? 16 : v; }();
+    const int tail_env = [] { const char* e = getenv("Q3_DECODE_TAIL"); const int v = e ? atoi(e) : 32; return v < 16 ? 16 : v; }();
     q3_status st = Q3_OK;
     while (st == Q3_OK && session_remaining(s) > 0 && !all_done(s)) {
         int n = seg_env;
@@ -2154,7 +2179,7 @@ extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_ho
                 s->par_ws.emplace_back(); s->par_streams.push_back(pst);
             }
             for (int k = 0; k < conc; ++k) Q3C(codec_reserve(s->m, ws_of(k), seg_env + CODEC_CTX_FRAMES, s->max_frames));
-            for (size_t i = 0; i < jobs.size(); ++i) Q3C(seg_enqueue(jobs[i], ws_of((int)(i % conc)), st_of((int)(i % conc))));
+            for (size_t i = 0; i < jobs.size(); ++i) Q3C(seg_enqueue(jobs[i], ws_of((int)(i % conc)), st_of((int)(i % conc)), 0));
             return Q3_OK;
         };
         st = tail();
@@ -2170,6 +2195,11 @@ extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_ho
     }
     const auto t3 = clk::now();
     if (timing) { timing->prefill_ms = ms(t0, t1); timing->generation_ms = ms(t1, t2); timing->decode_ms = ms(t2, t3); timing->generation_frames = total; }
+    // Q3_DECODE_LOG=1 (A/B aid): one line per run on stderr — did the enqueue thread ever hold up the frame loop, how long was the exposed tail
+    const bool log_env = getenv("Q3_DECODE_LOG") != nullptr;
+    if (log_env)
+        fprintf(stderr, "q3_session_run overlap: resident %d seg %d tail %d, %d dispatches, frame loop waited %.3f ms for the enqueue thread, frames %.1f ms, exposed decode %.1f ms\n",
+                resident_env, seg_env, tail_env, n_dispatch, join_wait_ms, ms(t1, t2), ms(t2, t3));
     return Q3_OK;
 }
 

@@ -618,7 +618,8 @@ extern "C" const char* q3_conv_path_name(int code) { return conv_path_name(code)
 // One launch_conv1d / launch_transconv1d_taps / launch_resunit call over host arrays. The weight packing, the transposed conv's
 // per-phase rearrangement (the loader's own helper) and the snake tables are preparation; exactly one launch of the family runs.
 // A launch the dispatcher refuses comes back as a status — never another kernel in its place — and leaves the host y / y2 alone.
-extern "C" q3_status q3_conv_ex(int device, const q3_conv_ex_args* p) {
+// (resident / lds_bytes: q3_test_conv_resident below — the launch's residency cap, and the dynamic LDS it asked for)
+static q3_status conv_ex_run(int device, const q3_conv_ex_args* p, int resident, int* lds_bytes) {
     if (!p || !p->x || !p->w || !p->y) return set_err(Q3_INVALID_ARG, "q3_conv_ex: null argument");
     if (p->path) *p->path = 0;
     const int kind = p->kind, cin = p->cin, cout = p->cout, L = p->L, k = p->k, dil = p->dil;
@@ -690,14 +691,14 @@ extern "C" q3_status q3_conv_ex(int device, const q3_conv_ex_args* p) {
         ConvArgs a;
         a.x = x; a.w = w; a.b = b; a.y = yr; a.cin = cin; a.cout = cout; a.L = L; a.k = k; a.dil = dil;
         a.snake_a = sa; a.snake_b = sb; a.resid = p->resid_in_place ? yr : res; a.scale = scale; a.act = p->act;
-        a.post_a = pa; a.post_ib = pb; a.y2 = y2r; a.wpk = wpk; a.planes = p->planes;
+        a.post_a = pa; a.post_ib = pb; a.y2 = y2r; a.wpk = wpk; a.planes = p->planes; a.resident = resident;
         e = launch_conv1d(a, 0, &path);
     } else if (kind == 1) {
-        e = launch_transconv1d_taps(x, w, b, yr, cin, cout, L, stride, taps, sa, sb, 0, pa, pb, y2r, wpk, p->planes, &path);
+        e = launch_transconv1d_taps(x, w, b, yr, cin, cout, L, stride, taps, sa, sb, 0, pa, pb, y2r, wpk, p->planes, &path, resident);
     } else {
         ResUnitArgs r{};
         r.xa = x; r.y = yr; r.ya = p->y2_is_x ? x : y2r; r.w1pk = wpk; r.w2pk = w2pk; r.b1 = b; r.b2 = b2;
-        r.mid_a = ma; r.mid_ib = mb; r.post_a = pa; r.post_ib = pb; r.C = cout; r.L = L; r.dil = dil; r.planes = p->planes;
+        r.mid_a = ma; r.mid_ib = mb; r.post_a = pa; r.post_ib = pb; r.C = cout; r.L = L; r.dil = dil; r.planes = p->planes; r.resident = resident;
         e = launch_resunit(r, 0, &path);
     }
     if (p->path) *p->path = path;
@@ -710,7 +711,26 @@ extern "C" q3_status q3_conv_ex(int device, const q3_conv_ex_args* p) {
     HIPC(q3_hipDeviceSynchronize());
     HIPC(q3_hipMemcpy(p->y, y, yn * 4, hipMemcpyDeviceToHost));
     if (y2) HIPC(q3_hipMemcpy(p->y2, y2, yn * 4, hipMemcpyDeviceToHost));
+    if (lds_bytes) *lds_bytes = (int)conv_last_dyn_lds();
     return Q3_OK;
+}
+extern "C" q3_status q3_conv_ex(int device, const q3_conv_ex_args* p) { return conv_ex_run(device, p, 0, nullptr); }
+// q3_conv_ex under a residency cap (ConvArgs::resident; tests/test_decode_resident.py): only launches of the kernels with dynamic
+// LDS (k_conv_bf16x3, k_resunit_bf16x3) take it — any other path is refused here, so a test never compares two uncapped launches.
+extern "C" q3_status q3_test_conv_resident(int device, const q3_conv_ex_args* p, int resident, int* lds_bytes) {
+    if (lds_bytes) *lds_bytes = 0;
+    if (resident < 0 || resident > 8) return set_err(Q3_INVALID_ARG, "q3_test_conv_resident: resident 0..8");
+    if (p && p->kind >= 0 && p->kind <= 2 && p->cin >= 1 && p->cout >= 1 && p->L >= 1 && p->k >= 1 && p->dil >= 1 && (p->kind != 1 || (p->stride >= 1 && p->k % p->stride == 0))) {
+        const int code = p->kind == 2 ? conv_path_code(resunit_pick(p->cout, p->L, p->dil, p->packed != 0 && p->w2 && p->mid_a, p->y2_is_x != 0, p->planes))
+                       : p->kind == 1 ? conv_path_code(conv_pick(p->cout, p->cin, p->L, p->k / p->stride, 1, p->stride, p->packed != 0, false, p->planes, false, true))
+                                      : conv_path_code(conv_pick(p->cout, p->cin, p->L, p->k, p->dil, 1, p->packed != 0, p->resid || p->resid_in_place, p->planes, false, false));
+        const int kern = code & CP_KERNEL_MASK;
+        if (!((kern >= CK_BF16X3_96x128_TM4 && kern <= CK_BF16X3_96x128_6W) || kern == CK_RESUNIT_3W || kern == CK_RESUNIT_6W)) {
+            if (p->path) *p->path = code;
+            return set_err(Q3_UNSUPPORTED, "q3_test_conv_resident: %s has no dynamic LDS to cap", conv_path_name(code));
+        }
+    }
+    return conv_ex_run(device, p, resident, lds_bytes);
 }
 
 static q3_status check_cl_out(const char* who, const void* x, const void* w, const void* y, int C, int L, int y_front, int y_elems) {

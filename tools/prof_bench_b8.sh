@@ -15,6 +15,8 @@ f=$(find /tmp/fpb -name "*kernel_trace.csv" | head -1)
   echo "# rocprofv3 --kernel-trace of: python bench.py --headline-only --steps 1 --warmup 0 $* (tools/prof_bench_b8.sh); steady segment of the frame loop only"
   echo "# bench line of the same (profiled) run: $(grep '^{' "$ROOT/gpurun_out/prof_bench_run.log" | python -c 'import sys,json; d=json.loads(sys.stdin.readline()); print({k: d[k] for k in ("value","ms_per_step","stage_ms")})' 2>/dev/null)"
   python "$ROOT/tools/prof_analyze.py" "$f" 640
+  # Q3_PROF_OVERLAP=1 (a run with Q3_DECODE_OVERLAP=1): the vocoder launches beside the frame loop and what they cost it
+  if [ -n "$Q3_PROF_OVERLAP" ]; then echo; python "$ROOT/tools/prof_overlap.py" "$f"; fi
 } > "$ROOT/gpurun_out/$NAME" 2>&1
 cat "$ROOT/gpurun_out/$NAME" | head -40
 rm -rf /tmp/fpb
