@@ -645,6 +645,42 @@ typedef struct q3_attn_prefill_ex_args {
     const int* page_slots; int* rot_used; long long* stray;
 } q3_attn_prefill_ex_args;
 q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_args* args);
+/* Test API: the PACKED sibling of q3_attn_prefill_ex (a ragged first batch's packed prefill pass): n_seq sequences of seq_len[i]
+ * rows (1 .. 8192 each, at most 16384 together), every one from position 0, laid end to end: qkv [sum(seq_len)][ld_qkv] and out
+ * [sum(seq_len)][ld_out] in pack order. It runs the packed q/k-norm + RoPE + K/V-append launch, the packed K/V plane split where a
+ * sequence takes the bf16x3 kernel (NaN-filled buffer, two spare tiles behind the last), and ONE packed attention launch per
+ * kernel present — nothing else. kernel -1 = per sequence the kernel its length selects when prefilled alone (below 256 rows the
+ * transposed f32-MFMA kernel, else bf16x3: possibly two launches), 2 = the transposed f32-MFMA kernel for all, 3 = bf16x3 for all.
+ * No key halves. kcache / vcache [n_seq][nkv][max_seq][128] (max_seq >= every seq_len), rope tables [max_seq][64], layouts 0 and 1,
+ * page_slots / rot_used / stray as q3_attn_prefill_ex (no slot may be shared: every sequence starts at 0). path (optional) [2] =
+ * launches of the f32-MFMA kernel, of the bf16x3 kernel (0 / 1 each). plane_tail (optional) [2] = bytes of the plane buffer behind
+ * the last sequence's tiles that are still NaN fill, bytes there in all. Every argument is checked before a device is touched. */
+typedef struct q3_attn_prefill_packed_ex_args {
+    int n_seq, nh, nkv, max_seq, ld_qkv, ld_out;
+    int kernel;
+    float eps;
+    const int* seq_len;
+    int* path; long long* plane_tail;
+    const float* qkv; const float* q_norm_w; const float* k_norm_w;
+    const float* rope_cos; const float* rope_sin;
+    float* kcache; float* vcache; float* out;
+    int layout, n_layers, layer, n_slabs;
+    const int* page_slots; int* rot_used; long long* stray;
+} q3_attn_prefill_packed_ex_args;
+q3_status q3_attn_prefill_packed_ex(int device, const q3_attn_prefill_packed_ex_args* args);
+/* Which rows of a ragged first batch share a packed prefill pass (host arithmetic, no GPU). lengths [n] = prefill
+ * positions per row (>= 1), hit_pages [n] = prefix-cache pages each row plans to link (>= 0; NULL = none), row_budget = most
+ * activation rows of a pass (>= 128), gemm_ok = the GEMM prefill path may run (model geometry, no debug / profile / no_chunk
+ * session, no attention A/B aid). A row packs when gemm_ok, 48 <= length < 1024 and it plans no hit; packs
+ * form in row order and close when the next row would pass the budget; a pack of one row is no pack. pass [n] = the row's pass or
+ * -1 (it stays in the equal-length groups), row0 [n] = its first activation row inside the pass (0 for -1), *n_passes (optional). */
+q3_status q3_prefill_pack_plan(const int32_t* lengths, const int32_t* hit_pages, int32_t n, int32_t row_budget, int32_t gemm_ok,
+                               int32_t* pass, int32_t* row0, int32_t* n_passes);
+/* What the last q3_session_prefill of a ragged first batch ran: info[0] = layer passes, [1] = of those packed passes, [2] = rows
+ * that went through packed passes, [3] = activation rows of the largest pack, [4] = rows that went through equal-length groups,
+ * [5..7] = 0. All zeros for a session whose rows have one prefill length (one batched prefill), before the prefill and after a
+ * failed one. Q3_PREFILL_PACK=0 (read per call) keeps every row in the groups. */
+q3_status q3_session_prefill_info(const q3_session* s, int32_t info[8]);
 /* Test API: the kernels that build the prompt rows, exactly ONE launch over host arrays (tests/test_gpu_prompt_rows.py). Every
  * destination (out; trail_len / text_ready / limit) is a host buffer with 64 guard elements in front of and behind its payload; it
  * is uploaded whole and copied back whole, and the kernel is given the payload. What a kernel could not address is Q3_INVALID_ARG

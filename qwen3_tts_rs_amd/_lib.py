@@ -95,6 +95,14 @@ class CAttnPrefillEx(ctypes.Structure):  # q3_attn_prefill_ex_args
                [(n, ctypes.c_void_p) for n in ("page_slots", "rot_used", "stray")]
 
 
+class CAttnPrefillPackedEx(ctypes.Structure):  # q3_attn_prefill_packed_ex_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_seq", "nh", "nkv", "max_seq", "ld_qkv", "ld_out", "kernel")] + [("eps", ctypes.c_float)] + \
+               [(n, ctypes.c_void_p) for n in ("seq_len", "path", "plane_tail", "qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache",
+                                               "out")] + \
+               [(n, ctypes.c_int32) for n in ("layout", "n_layers", "layer", "n_slabs")] + \
+               [(n, ctypes.c_void_p) for n in ("page_slots", "rot_used", "stray")]
+
+
 class CPromptRowsEx(ctypes.Structure):   # q3_prompt_rows_ex_args
     _fields_ = [(n, ctypes.c_int32) for n in ("mode", "n", "cols", "n_table", "n_rows", "n_ref", "cp_vocab", "lds", "ldd", "reserved")] + \
                [(n, ctypes.c_void_p) for n in ("table", "ids", "src", "text_row", "codec_id", "xvec", "ref_codes", "cp_embs", "dst_row", "ent", "out",
@@ -313,6 +321,10 @@ SYMBOLS = {
     "q3_gemm_ex": (c_int, [c_int, P(CGemmEx)]),
     "q3_attn_prefill_path": (c_int, [c_int] * 4 + [P(ctypes.c_int32)]),
     "q3_attn_prefill_ex": (c_int, [c_int, P(CAttnPrefillEx)]),
+    "q3_attn_prefill_packed_ex": (c_int, [c_int, P(CAttnPrefillPackedEx)]),
+    "q3_prefill_pack_plan": (c_int, [P(ctypes.c_int32), P(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P(ctypes.c_int32),
+                                     P(ctypes.c_int32), P(ctypes.c_int32)]),
+    "q3_session_prefill_info": (c_int, [c_void_p, P(ctypes.c_int32)]),
     "q3_prompt_rows_ex": (c_int, [c_int, P(CPromptRowsEx)]),
     "q3_attn_c_path": (c_int, [c_int, c_int]),
     "q3_attn_c_ex": (c_int, [c_int, P(CAttnCEx)]),

@@ -358,6 +358,13 @@ class Session:
     def prefill(self):
         check(lib.q3_session_prefill(self._h))
 
+    def prefill_info(self) -> dict:
+        """q3_session_prefill_info: what the prefill of a ragged first batch ran — layer passes, how many of them packed passes, rows
+        packed, activation rows of the largest pack, rows that went through equal-length groups. All zeros for a one-length session."""
+        info = (ctypes.c_int32 * 8)()
+        check(lib.q3_session_prefill_info(self._h, info))
+        return dict(passes=int(info[0]), packs=int(info[1]), rows_packed=int(info[2]), max_pack_rows=int(info[3]), rows_grouped=int(info[4]))
+
     # ---- streaming text input (DESIGN 4.10) ----
     def open_text(self, b: int):
         """Row b takes the rest of its text in pieces (append_text); before prefill. Its utterance carries the first ids."""
@@ -2190,6 +2197,62 @@ def attn_prefill_ex(qkv: np.ndarray, n_seq: int, base_pos: int, q_norm_w: np.nda
         a.page_slots = ptr(page_slots)
     check(lib.q3_attn_prefill_ex(device, ctypes.byref(a)))
     return out, kc, vc, tuple(path), dict(stray=int(stray[0]), stray_at=int(stray[1]), rot_used=rot)
+
+
+def attn_prefill_packed_ex(qkv: np.ndarray, seq_len, q_norm_w: np.ndarray, k_norm_w: np.ndarray, eps: float, rope_cos: np.ndarray,
+                           rope_sin: np.ndarray, kcache: np.ndarray, vcache: np.ndarray, nh: int, nkv: int, *, kernel: int = -1,
+                           out: Optional[np.ndarray] = None, layout: int = 0, n_layers: int = 1, layer: int = 0, n_slabs: int = 1,
+                           page_slots=None, device: int = 0):
+    """q3_attn_prefill_packed_ex: the packed prefill attention step (parity tests). qkv [sum(seq_len)][ld_qkv] holds the sequences end
+    to end, every one from position 0; kcache / vcache are the LOGICAL cache [n_seq][nkv][max_seq][128]. kernel -1 = per sequence by
+    its length, 2 = transposed f32 MFMA, 3 = bf16x3. Returns (out, kcache, vcache, (launches of kernel 2, of kernel 3), info) with
+    info = dict(stray, stray_at, rot_used, plane_tail = (bytes still NaN fill, bytes) behind the last plane tile)."""
+    lens = np.ascontiguousarray(list(seq_len), dtype=np.int32); n_seq = int(lens.size)
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32); rows = qkv.shape[0]
+    assert qkv.ndim == 2 and rows == int(lens.sum())
+    kc = np.array(kcache, dtype=np.float32, order="C"); vc = np.array(vcache, dtype=np.float32, order="C")
+    max_seq = kc.shape[2]
+    assert kc.shape == (n_seq, nkv, max_seq, 128) and vc.shape == kc.shape
+    qw = np.ascontiguousarray(q_norm_w, dtype=np.float32); kw = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    rc = np.ascontiguousarray(rope_cos, dtype=np.float32); rs = np.ascontiguousarray(rope_sin, dtype=np.float32)
+    assert qw.shape == (128,) and kw.shape == (128,) and rc.shape == (max_seq, 64) and rs.shape == (max_seq, 64)
+    if out is None:
+        out = np.zeros((rows, nh * 128), dtype=np.float32)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.ndim == 2 and out.shape[0] == rows
+    path = (ctypes.c_int32 * 2)()
+    tail = np.zeros(2, dtype=np.int64)
+    a = _lib.CAttnPrefillPackedEx()
+    a.n_seq, a.nh, a.nkv, a.max_seq, a.ld_qkv, a.ld_out, a.kernel, a.eps = n_seq, nh, nkv, max_seq, qkv.shape[1], out.shape[1], kernel, eps
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    a.path = ctypes.cast(path, ctypes.c_void_p)
+    a.seq_len, a.plane_tail = ptr(lens), ptr(tail)
+    a.qkv, a.q_norm_w, a.k_norm_w, a.rope_cos, a.rope_sin = ptr(qkv), ptr(qw), ptr(kw), ptr(rc), ptr(rs)
+    a.kcache, a.vcache, a.out = ptr(kc), ptr(vc), ptr(out)
+    n_pg = (max_seq + 127) // 128
+    stray = np.array([0, -1], dtype=np.int64)
+    rot = np.full((n_seq, n_pg, nkv), -1, dtype=np.int32)
+    a.layout, a.n_layers, a.layer, a.n_slabs, a.stray, a.rot_used = layout, n_layers, layer, n_slabs, ptr(stray), ptr(rot)
+    if page_slots is not None:
+        page_slots = np.ascontiguousarray(page_slots, dtype=np.int32); assert page_slots.shape == (n_seq, n_pg)
+        a.page_slots = ptr(page_slots)
+    check(lib.q3_attn_prefill_packed_ex(device, ctypes.byref(a)))
+    return out, kc, vc, tuple(path), dict(stray=int(stray[0]), stray_at=int(stray[1]), rot_used=rot, plane_tail=(int(tail[0]), int(tail[1])))
+
+
+PREFILL_PACK_ROWS = 4224      # the default row budget of a packed prefill pass (Q3_PREFILL_ROWS)
+
+
+def prefill_pack_plan(lengths, hit_pages=None, *, row_budget: int = PREFILL_PACK_ROWS, gemm_ok: bool = True):
+    """q3_prefill_pack_plan: which rows of a ragged first batch share a packed prefill pass (host arithmetic, no GPU). Returns
+    (passes [n] — the row's pass or -1 for the equal-length groups —, row0 [n] — its first activation row in the pass —, n_passes)."""
+    ln = np.ascontiguousarray(list(lengths), dtype=np.int32); n = int(ln.size)
+    hp = None if hit_pages is None else np.ascontiguousarray(list(hit_pages), dtype=np.int32)
+    assert hp is None or hp.size == n
+    ps = np.full(max(n, 1), -1, dtype=np.int32); r0 = np.zeros(max(n, 1), dtype=np.int32); npass = ctypes.c_int32(0)
+    i32 = lambda arr: arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    check(lib.q3_prefill_pack_plan(i32(ln) if n else None, None if hp is None else i32(hp), n, int(row_budget), int(bool(gemm_ok)), i32(ps), i32(r0),
+                                   ctypes.byref(npass)))
+    return ps[:n].tolist(), r0[:n].tolist(), int(npass.value)
 
 
 ROWS_GATHER, ROWS_ASSEMBLE, ROWS_COPY, ROWS_SCATTER, ROWS_PUBLISH = 0, 1, 2, 3, 4

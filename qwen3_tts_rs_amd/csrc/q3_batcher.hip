@@ -103,7 +103,7 @@ static q3_status transplant_check(q3_session* s, q3_session* side, int j, int li
 // The one side prefill (q3_engine.h): q3_session_replace, the batcher's stage worker and the groups of a ragged first batch.
 q3_status side_prefill(q3_session* host, const q3_request* reqs, const int* limit_req, int n, bool open_text, bool closed,
                        bool prefix_common, hipStream_t borrow, std::unique_ptr<q3_session>* side_out, int* limit_out,
-                       const std::function<void()>& created) {
+                       const std::function<void()>& created, bool staged_only) {
     std::vector<q3_request> rq(reqs, reqs + n);
     for (q3_request& r : rq) r.opts.max_length = host->max_frames;      // the side session draws the rows' PCG streams with the host session's stride
     q3_session* side_raw = nullptr;
@@ -118,7 +118,7 @@ q3_status side_prefill(q3_session* host, const q3_request* reqs, const int* limi
     // (sampling options are per row — SampleRow —, resolved by the side session: an ICL request's repetition-penalty floor and
     // length cap, lib.rs:913-929, come along)
     for (int j = 0; j < n; ++j) Q3C(transplant_check(host, side.get(), j, limit_req[j], &limit_out[j]));
-    Q3C(q3_session_prefill(side.get()));                // ends with a synchronisation of the side stream
+    if (!staged_only) Q3C(q3_session_prefill(side.get()));                // ends with a synchronisation of the side stream
     *side_out = std::move(side);
     return Q3_OK;
 }

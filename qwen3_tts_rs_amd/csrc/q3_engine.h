@@ -458,7 +458,8 @@ struct q3_session {
     // idle rows, these are the real requests; q3_session_prefill prefills them in groups of equal prefill length and moves each
     // row in (transplant_row), exactly as a continuous-batching swap would
     std::vector<BatReq> ragged;
-    bool regrouped = false;               // prefix cache: a one-length session whose rows were prefilled in groups (prefix_regroup); transplant_row then also fills embeds
+    int prefill_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // q3_session_prefill_info: what the ragged prefill ran (packed passes)
+    bool regrouped = false;              // prefix cache: a one-length session whose rows were prefilled in groups (prefix_regroup); transplant_row then also fills embeds
     bool prefix_common = false;           // prefix cache: rows that hit differently stay in this session (a group prefill_ragged formed)
     int kv_overflow_row = -1;             // the row whose page request the pool refused (kv_reserve_row): the batcher fails that row alone
     // bf16 K/V (opt-in, q3_session_set_kv_dtype; the reference GPU path's cache dtype): the prompt is prefilled into f32 pages
@@ -663,6 +664,7 @@ Q3_HIDDEN q3_status transplant_row(q3_session* s, int b, q3_session* side, int j
 // with its text open (closed: and closed again before the prefill); prefix_common: the rows link what their shortest cached chain
 // allows; borrow: the stream to prefill on (null: one of its own); created: called once the side session stands, before the
 // checks and the prefill. Of `host` it reads what never changes under a running frame (the stage worker calls it on its thread).
+// staged_only: the side session is left checked but NOT prefilled — a packed pass runs its layers with other rows' (prefill_ragged).
 Q3_HIDDEN q3_status side_prefill(q3_session* host, const q3_request* reqs, const int* limit_req, int n, bool open_text, bool closed,
                                  bool prefix_common, hipStream_t borrow, std::unique_ptr<q3_session>* side_out, int* limit_out,
-                                 const std::function<void()>& created = nullptr);
+                                 const std::function<void()>& created = nullptr, bool staged_only = false);

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 namespace q3 {
 
@@ -240,6 +241,40 @@ int attn_prefill_rows_wg(int kernel, int nrep);                       // query r
 hipError_t launch_attn_prefill(const AttnArgs& a, hipStream_t st);    // = launch_attn_prefill(a, attn_prefill_pick(a), st)
 // the named pick and nothing else: hipErrorInvalidValue for a pick the arguments do not allow
 hipError_t launch_attn_prefill(const AttnArgs& a, const AttnPrefillPick& p, hipStream_t st);
+// ---- packed prefill: sequences of UNEQUAL length laid end to end in one activation matrix, every sequence from
+// position 0. The attention-side launches find their rows through small device tables, built on the host once per pack
+// (pack_host_build) and reused by every layer. Inside a workgroup everything is relative to its sequence — rps = the sequence's
+// length, base_pos = 0, query blocks counted from its first row — so a position runs the instructions of its sequence's solo launch.
+struct PackSeq { int row0, len, trow, tile0; };     // first activation row; length; page-table row (contiguous cache: its sequence
+                                                    // index); first K/V-plane tile of kv head 0 (head g: tile0 + g * ceil(len / 32))
+struct PackTab {
+    const PackSeq* seq; int n_seq;
+    const int* row_seq; int rows;                   // activation row -> sequence
+    // per attention kernel (0: k_attn_prefill_t, 1: k_attn_prefill_x3): work[k][xcd * per_xcd[k] + j] = {(sequence * nkv + kv head)
+    // or -1 (padding), query block}: pair p on XCD p % 8, long query blocks first within an XCD (the rule of the uniform kernels)
+    const int2* work[2]; int per_xcd[2];
+    const int2* plane_items; int n_plane_items;     // {sequence, tile} of every K/V-plane tile of the bf16x3 sequences
+};
+// the tables as one block of ints (one upload) and where each lies in it
+struct PackHost {
+    std::vector<int> blob;
+    size_t off_seq = 0, off_row_seq = 0, off_work[2] = {0, 0}, off_planes = 0;
+    int n_seq = 0, rows = 0, per_xcd[2] = {0, 0}, n_plane_items = 0, plane_tiles = 0;      // plane_tiles: tiles of the plane buffer (all kv heads)
+    PackTab tab(const int* dev) const {
+        PackTab t;
+        t.seq = reinterpret_cast<const PackSeq*>(dev + off_seq); t.n_seq = n_seq; t.row_seq = dev + off_row_seq; t.rows = rows;
+        for (int k = 0; k < 2; ++k) { t.work[k] = reinterpret_cast<const int2*>(dev + off_work[k]); t.per_xcd[k] = per_xcd[k]; }
+        t.plane_items = reinterpret_cast<const int2*>(dev + off_planes); t.n_plane_items = n_plane_items;
+        return t;
+    }
+};
+// len[i] >= 1 positions, trow[i] = page-table row, kernel[i] = AP_T or AP_X3 for sequence i, in pack order. false: a bad argument.
+bool pack_host_build(const int* len, const int* trow, const int* kernel, int n, int nh, int nkv, PackHost* out);
+hipError_t launch_qknorm_rope_kv_pack(const AttnArgs& a, const PackTab& t, hipStream_t st);
+// planes of [0, len) of every bf16x3 sequence of the pack, each sequence in tiles of its own (kvp: PackHost::plane_tiles tiles)
+hipError_t launch_kv_planes_pack(const AttnArgs& kv, const PackTab& t, unsigned char* kvp, hipStream_t st);
+// kernel = AP_T or AP_X3: ONE launch over the sequences of the pack that take that kernel (none: no launch); no key halves
+hipError_t launch_attn_prefill_pack(const AttnArgs& a, const PackTab& t, int kernel, hipStream_t st);
 // fused q/k-norm + RoPE + KV append + attention (+ final normalisation when n_splits == 1)
 hipError_t launch_attn_fused(const AttnArgs& a, hipStream_t st);
 // the same for caches that never exceed 16 positions with the position known at launch (the code predictor's single-row

@@ -360,12 +360,21 @@ hipError_t launch_fused_residual_rmsnorm_bf16(const uint16_t* x, const uint16_t*
 // q/k per-head RMSNorm + rotate-half RoPE + in-place KV append (transformer.rs:263-284,
 // kv_cache.rs:290-347). grid (nh + nkv, B), one wave per head; lane i owns the pair (i, i+64).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_qknorm_rope_kv(AttnArgs a) {
+// PACK: activation row b -> (sequence, position) through the pack's tables; K/V go to that sequence's table row.
+template <bool PACK>
+__device__ __forceinline__ void qknorm_rope_kv_body(const AttnArgs& a, const PackTab& pk) {
     const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
     const int QD = a.nh * HEAD_DIM, KD = a.nkv * HEAD_DIM;
-    const int rps = a.rows_per_seq > 1 ? a.rows_per_seq : 1;
-    const int seq = b / rps;
-    const int pos = (a.pos_dev ? a.pos_dev[seq] : a.pos_static) + (b - seq * rps);
+    int seq, pos;
+    if constexpr (PACK) {
+        const int sq = pk.row_seq[b];
+        const PackSeq ps = pk.seq[sq];
+        seq = ps.trow; pos = b - ps.row0;
+    } else {
+        const int rps = a.rows_per_seq > 1 ? a.rows_per_seq : 1;
+        seq = b / rps;
+        pos = (a.pos_dev ? a.pos_dev[seq] : a.pos_static) + (b - seq * rps);
+    }
     const bool is_q = h < a.nh;
     const float* src = a.qkv + (size_t)b * a.ld_qkv + (is_q ? h * HEAD_DIM : QD + (h - a.nh) * HEAD_DIM);
     float x1 = src[lane], x2 = src[lane + 64];
@@ -388,9 +397,16 @@ __global__ __launch_bounds__(64) void k_qknorm_rope_kv(AttnArgs a) {
         vr[lane] = vs[lane]; vr[lane + 64] = vs[lane + 64];
     }
 }
+__global__ __launch_bounds__(64) void k_qknorm_rope_kv(AttnArgs a) { qknorm_rope_kv_body<false>(a, PackTab{}); }
+__global__ __launch_bounds__(64) void k_qknorm_rope_kv_pack(AttnArgs a, PackTab pk) { qknorm_rope_kv_body<true>(a, pk); }
 
 hipError_t launch_qknorm_rope_kv(const AttnArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_qknorm_rope_kv, dim3(a.nh + a.nkv, a.B), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_qknorm_rope_kv_pack(const AttnArgs& a, const PackTab& t, hipStream_t st) {
+    if (a.B != t.rows || a.B < 1 || a.B > 65535 || !t.seq || !t.row_seq) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_qknorm_rope_kv_pack, dim3(a.nh + a.nkv, a.B), dim3(64), 0, st, a, t);
     return hipGetLastError();
 }
 

@@ -19,6 +19,8 @@
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <algorithm>
+#include <utility>
 
 namespace q3 {
 
@@ -1023,30 +1025,40 @@ __global__ __launch_bounds__(256) void k_attn_prefill_mfma(AttnArgs a) {
 // are dispatched first. 4105-position prefill of the 1.7B talker: 3.03 -> see DESIGN §4.5 ms of attention per layer.
 // ------------------------------------------------------------------------------------------------
 __host__ __device__ __forceinline__ int rps_blocks(int rps, int rows_wg) { return (rps + rows_wg - 1) / rows_wg; }
-template <int NREP>
-__global__ __launch_bounds__(256, 2) void k_attn_prefill_t(AttnArgs a) {      // 2 waves per SIMD: <= 256 VGPRs + AGPRs
+// PACK (k_attn_prefill_t_pack below): the workgroup takes (sequence, kv head, query block) from the pack's work list
+// instead of the pair / nb arithmetic, and everything after that is relative to ITS sequence — rps = the sequence's length,
+// base_pos = 0, rows from the sequence's first activation row, K/V through its table row — so the key-tile walk and the masks of
+// a position are those of the sequence's solo launch. No key halves in a pack.
+template <int NREP, bool PACK>
+__device__ __forceinline__ void attn_prefill_t_body(const AttnArgs& a, const PackTab& pk) {
     constexpr int ROWS_WG = 128 / NREP;
     __shared__ __attribute__((aligned(16))) float sK[32 * KVP];
     __shared__ __attribute__((aligned(16))) float sV[32 * KVP];
     // n_splits == 2: the key range of every query block is halved over two workgroups (partials in a.part, merged by
     // k_attn_merge). All workgroups of a launch are resident at once, so the launch lasts as long as its longest
     // workgroup — the last query block's walk over every key tile; halving that chain is worth more than the merge costs.
-    const int halves = a.n_splits == 2 ? 2 : 1;
+    const int halves = PACK ? 1 : (a.n_splits == 2 ? 2 : 1);
     // 1-D grid, XCD-aware: workgroup b runs on XCD b % 8; (sequence, kv head) pair p is served by XCD p % 8 only, so the
     // 4.2 MB of K/V a pair's query blocks all walk (4105 positions) stay in that XCD's L2 instead of cycling eight
     // pairs' worth through every L2. Within an XCD: long (late) query blocks first.
-    int blk, half, kvh, seq;
-    {
+    int blk, half, kvh, seq, rps, row_base, base_pos;          // seq: the row of the page table (the cache's sequence)
+    if constexpr (PACK) {
+        const int lin = (int)blockIdx.x, xcd = lin & 7, j = lin >> 3;
+        const int2 w = pk.work[0][xcd * pk.per_xcd[0] + j];
+        if (w.x < 0) return;                                    // padding items of the shorter XCD lists
+        const PackSeq ps = pk.seq[w.x / a.nkv];
+        blk = w.y; half = 0; kvh = w.x % a.nkv; seq = ps.trow; rps = ps.len; row_base = ps.row0; base_pos = 0;
+    } else {
         const int nb = (rps_blocks(a.rows_per_seq, ROWS_WG)) * halves, npairs = (a.B / a.rows_per_seq) * a.nkv;
         const int lin = (int)blockIdx.x, xcd = lin & 7, j = lin >> 3;
         const int pair = xcd + 8 * (j / nb);                    // this XCD's (j / nb)-th pair
         if (pair >= npairs) return;                             // padding workgroups of the last round
         const int bid = nb - 1 - j % nb;
         blk = bid / halves; half = bid - blk * halves; kvh = pair % a.nkv; seq = pair / a.nkv;
+        rps = a.rows_per_seq; row_base = seq * rps;
+        base_pos = a.pos_dev ? a.pos_dev[seq] : a.pos_static;
     }
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, lk = lane >> 5;
-    const int rps = a.rows_per_seq;
-    const int base_pos = a.pos_dev ? a.pos_dev[seq] : a.pos_static;
     const int head = kvh * NREP + (wave % NREP);
     const int r0 = blk * ROWS_WG + (wave / NREP) * 32;         // first chunk row of this wave
     const int wg_rows = (rps - blk * ROWS_WG) < ROWS_WG ? (rps - blk * ROWS_WG) : ROWS_WG;
@@ -1060,7 +1072,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_prefill_t(AttnArgs a) {      //
     {
         const int i = r0 + li;
         const bool ok = i < rps;
-        const float* src = a.qbuf + ((size_t)(seq * rps + (ok ? i : 0)) * a.nh + head) * HEAD_DIM + lk * 64;
+        const float* src = a.qbuf + ((size_t)(row_base + (ok ? i : 0)) * a.nh + head) * HEAD_DIM + lk * 64;
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const float4 f = ok ? *reinterpret_cast<const float4*>(src + 4 * t) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1158,7 +1170,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_prefill_t(AttnArgs a) {      //
     const int row = r0 + li;
     if (halves == 2) {
         if (row < rps) {                                       // partial record: O (relative to m), m, l — k_attn_merge's format
-            float* rec = a.part + (((size_t)(seq * rps + row) * a.nh + head) * 2 + half) * PART_STRIDE;
+            float* rec = a.part + (((size_t)(row_base + row) * a.nh + head) * 2 + half) * PART_STRIDE;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int i = (r & 3) + 8 * (r >> 2) + 4 * lk;
@@ -1170,7 +1182,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_prefill_t(AttnArgs a) {      //
         return;
     }
     if (row < rps) {
-        float* dst = a.out + (size_t)(seq * rps + row) * a.ld_out + head * HEAD_DIM;
+        float* dst = a.out + (size_t)(row_base + row) * a.ld_out + head * HEAD_DIM;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {                         // register r of the four tiles = d 4i .. 4i+3, i = row(r, lk)
             const int i = (r & 3) + 8 * (r >> 2) + 4 * lk;
@@ -1178,6 +1190,12 @@ __global__ __launch_bounds__(256, 2) void k_attn_prefill_t(AttnArgs a) {      //
         }
     }
 }
+template <int NREP>
+__global__ __launch_bounds__(256, 2) void k_attn_prefill_t(AttnArgs a) {      // 2 waves per SIMD: <= 256 VGPRs + AGPRs
+    attn_prefill_t_body<NREP, false>(a, PackTab{});
+}
+template <int NREP>
+__global__ __launch_bounds__(256, 2) void k_attn_prefill_t_pack(AttnArgs a, PackTab pk) { attn_prefill_t_body<NREP, true>(a, pk); }
 
 // ------------------------------------------------------------------------------------------------
 // Fourth generation: the same transposed flash attention on the bf16 matrix cores. The f32-input MFMA above runs at
@@ -1201,14 +1219,28 @@ constexpr int X3_PLANE = 32 * HEAD_DIM * 2;          // bytes of one plane of on
 constexpr int X3_TILE = 6 * X3_PLANE;                // K h, m, l, Vᵀ h, m, l
 typedef __attribute__((ext_vector_type(16))) float pf32x16b_t;
 
-__global__ __launch_bounds__(256) void k_kv_planes(AttnArgs a, int n_pos, int tiles_alloc, unsigned char* __restrict__ kvp) {
+// PACK: workgroup (item, kv head) takes {sequence, tile} from the pack's plane list; the sequence's planes cover its
+// own [0, len) in tiles of its own (PackSeq::tile0), so no tile holds keys of two sequences.
+template <bool PACK>
+__device__ __forceinline__ void kv_planes_body(const AttnArgs& a, int n_pos, int tiles_alloc, unsigned char* __restrict__ kvp, const PackTab& pk) {
     __shared__ float sV[32 * 129];
-    const int tile = blockIdx.x, pair = blockIdx.y, tid = threadIdx.x;
-    unsigned char* dst = kvp + ((size_t)pair * tiles_alloc + tile) * X3_TILE;
+    const int tid = threadIdx.x;
+    int tile, seq, kvh;
+    unsigned char* dst;
+    if constexpr (PACK) {
+        const int2 it = pk.plane_items[blockIdx.x];
+        const PackSeq ps = pk.seq[it.x];
+        tile = it.y; seq = ps.trow; kvh = blockIdx.y; n_pos = ps.len;
+        dst = kvp + ((size_t)ps.tile0 + (size_t)kvh * ((ps.len + 31) / 32) + tile) * X3_TILE;
+    } else {
+        const int pair = blockIdx.y;                              // pair = sequence * nkv + kv head
+        tile = blockIdx.x; seq = pair / a.nkv; kvh = pair % a.nkv;
+        dst = kvp + ((size_t)pair * tiles_alloc + tile) * X3_TILE;
+    }
     const int key = tid >> 3, dc = (tid & 7) * 16;
     const int p = tile * 32 + key;
     const bool ok = p < n_pos;                                   // positions past the prompt: zeros (masked by causality anyway)
-    const float* krow = kv_krow(a, pair / a.nkv, pair % a.nkv, ok ? p : 0) + dc;      // pair = sequence * nkv + kv head
+    const float* krow = kv_krow(a, seq, kvh, ok ? p : 0) + dc;
     const float* vrow = krow + kv_vd(a);
     float kv[16], vv[16];
 #pragma unroll
@@ -1250,6 +1282,10 @@ __global__ __launch_bounds__(256) void k_kv_planes(AttnArgs a, int n_pos, int ti
         *reinterpret_cast<pu32x4_t*>(o + 2 * X3_PLANE) = l;
     }
 }
+__global__ __launch_bounds__(256) void k_kv_planes(AttnArgs a, int n_pos, int tiles_alloc, unsigned char* __restrict__ kvp) {
+    kv_planes_body<false>(a, n_pos, tiles_alloc, kvp, PackTab{});
+}
+__global__ __launch_bounds__(256) void k_kv_planes_pack(AttnArgs a, unsigned char* __restrict__ kvp, PackTab pk) { kv_planes_body<true>(a, 0, 0, kvp, pk); }
 hipError_t launch_kv_planes(const AttnArgs& kv, int n_pairs, int n_pos, int tiles_alloc,
                             unsigned char* kvp, hipStream_t st) {
     const int tiles = (n_pos + 31) / 32;
@@ -1259,24 +1295,33 @@ hipError_t launch_kv_planes(const AttnArgs& kv, int n_pairs, int n_pos, int tile
     return hipGetLastError();
 }
 
-template <int NREP>
-__global__ __launch_bounds__(512) void k_attn_prefill_x3(AttnArgs a) {
+template <int NREP, bool PACK>      // PACK: as attn_prefill_t_body; the sequence's planes lie in tiles of its own (PackSeq::tile0)
+__device__ __forceinline__ void attn_prefill_x3_body(const AttnArgs& a, const PackTab& pk) {
     constexpr int ROWS_WG = 256 / NREP;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * X3_TILE];
-    const int halves = a.n_splits == 2 ? 2 : 1;
-    int blk, half, kvh, seq, pair;
-    {   // XCD-aware 1-D grid of the third generation: a (sequence, kv head) pair is served by one XCD; long blocks first
+    const int halves = PACK ? 1 : (a.n_splits == 2 ? 2 : 1);
+    int blk, half, kvh, seq, rps, row_base, base_pos;
+    size_t tile_base;                                           // first plane tile of this (sequence, kv head)
+    if constexpr (PACK) {
+        const int lin = (int)blockIdx.x, xcd = lin & 7, j = lin >> 3;
+        const int2 w = pk.work[1][xcd * pk.per_xcd[1] + j];
+        if (w.x < 0) return;
+        const PackSeq ps = pk.seq[w.x / a.nkv];
+        blk = w.y; half = 0; kvh = w.x % a.nkv; seq = ps.trow; rps = ps.len; row_base = ps.row0; base_pos = 0;
+        tile_base = (size_t)(ps.tile0 + kvh * ((ps.len + 31) / 32));
+    } else {   // XCD-aware 1-D grid of the third generation: a (sequence, kv head) pair is served by one XCD; long blocks first
         const int nb = (rps_blocks(a.rows_per_seq, ROWS_WG)) * halves, npairs = (a.B / a.rows_per_seq) * a.nkv;
         const int lin = (int)blockIdx.x, xcd = lin & 7, j = lin >> 3;
-        pair = xcd + 8 * (j / nb);
+        const int pair = xcd + 8 * (j / nb);
         if (pair >= npairs) return;
         const int bid = nb - 1 - j % nb;
         blk = bid / halves; half = bid - blk * halves; kvh = pair % a.nkv; seq = pair / a.nkv;
+        rps = a.rows_per_seq; row_base = seq * rps;
+        base_pos = a.pos_dev ? a.pos_dev[seq] : a.pos_static;
+        tile_base = (size_t)pair * a.kvp_tiles;
     }
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lk = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int rps = a.rows_per_seq;
-    const int base_pos = a.pos_dev ? a.pos_dev[seq] : a.pos_static;
     const int head = kvh * NREP + (wave % NREP);
     const int r0 = blk * ROWS_WG + (wave / NREP) * 32;         // first chunk row of this wave
     const int wg_rows = (rps - blk * ROWS_WG) < ROWS_WG ? (rps - blk * ROWS_WG) : ROWS_WG;
@@ -1289,7 +1334,7 @@ __global__ __launch_bounds__(512) void k_attn_prefill_x3(AttnArgs a) {
     {
         const int i = r0 + li;
         const bool ok = i < rps;
-        const float* src = a.qbuf + ((size_t)(seq * rps + (ok ? i : 0)) * a.nh + head) * HEAD_DIM + lk * 8;
+        const float* src = a.qbuf + ((size_t)(row_base + (ok ? i : 0)) * a.nh + head) * HEAD_DIM + lk * 8;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             const float4 f0 = ok ? *reinterpret_cast<const float4*>(src + 16 * t) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1311,7 +1356,7 @@ __global__ __launch_bounds__(512) void k_attn_prefill_x3(AttnArgs a) {
     const int my_first_pos = base_pos + r0, my_last_pos = base_pos + r0 + 31;
 
     // LDS-DMA role: wave w moves 1-KB block w of each of the six planes (K: keys 4w .. 4w+3, Vᵀ: d 16w .. 16w+15)
-    const unsigned char* const tiles = a.kvp + (size_t)pair * a.kvp_tiles * X3_TILE;
+    const unsigned char* const tiles = a.kvp + tile_base * X3_TILE;
     const int skey = wave * 4 + (lane >> 4), sd = wave * 16 + (lane >> 2);
     const unsigned koff = (unsigned)(skey * 256 + (((lane & 15) ^ (skey & 15)) << 4));
     const unsigned voff = (unsigned)(sd * 64 + (((lane & 3) ^ ((sd >> 2) & 3)) << 4));
@@ -1420,7 +1465,7 @@ __global__ __launch_bounds__(512) void k_attn_prefill_x3(AttnArgs a) {
     const int row = r0 + li;
     if (row >= rps) return;
     if (halves == 2) {                                         // partial record: O (relative to m), m, l — k_attn_merge's format
-        float* rec = a.part + (((size_t)(seq * rps + row) * a.nh + head) * 2 + half) * PART_STRIDE;
+        float* rec = a.part + (((size_t)(row_base + row) * a.nh + head) * 2 + half) * PART_STRIDE;
 #pragma unroll
         for (int b = 0; b < 4; ++b)
 #pragma unroll
@@ -1432,13 +1477,103 @@ __global__ __launch_bounds__(512) void k_attn_prefill_x3(AttnArgs a) {
         if (lk == 0) { rec[HEAD_DIM] = m; rec[HEAD_DIM + 1] = den; }
         return;
     }
-    float* dst = a.out + (size_t)(seq * rps + row) * a.ld_out + head * HEAD_DIM;
+    float* dst = a.out + (size_t)(row_base + row) * a.ld_out + head * HEAD_DIM;
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4)
             *reinterpret_cast<float4*>(dst + 32 * b + 8 * q4 + 4 * lk) =
                 make_float4(O[b][4 * q4] / den, O[b][4 * q4 + 1] / den, O[b][4 * q4 + 2] / den, O[b][4 * q4 + 3] / den);
+}
+template <int NREP>
+__global__ __launch_bounds__(512) void k_attn_prefill_x3(AttnArgs a) { attn_prefill_x3_body<NREP, false>(a, PackTab{}); }
+template <int NREP>
+__global__ __launch_bounds__(512) void k_attn_prefill_x3_pack(AttnArgs a, PackTab pk) { attn_prefill_x3_body<NREP, true>(a, pk); }
+
+// ---- packed prefill: the tables (host) and the launches over them ----
+bool pack_host_build(const int* len, const int* trow, const int* kernel, int n, int nh, int nkv, PackHost* out) {
+    if (!len || !trow || !kernel || !out || n < 1 || nkv < 1 || nh < nkv || nh % nkv) return false;
+    const int nrep = nh / nkv;
+    if (nrep != 1 && nrep != 2 && nrep != 4) return false;
+    *out = PackHost{};
+    std::vector<int> seq((size_t)n * 4), row_seq;
+    std::vector<int> planes;
+    std::vector<std::vector<int>> work[2];
+    work[0].resize(8); work[1].resize(8);
+    int rows = 0, tiles = 0, pairs[2] = {0, 0};
+    for (int i = 0; i < n; ++i) {
+        if (len[i] < 1 || trow[i] < 0 || (kernel[i] != AP_T && kernel[i] != AP_X3)) return false;
+        const int k = kernel[i] == AP_X3 ? 1 : 0, nt = (len[i] + 31) / 32;
+        seq[(size_t)4 * i] = rows; seq[(size_t)4 * i + 1] = len[i]; seq[(size_t)4 * i + 2] = trow[i]; seq[(size_t)4 * i + 3] = k ? tiles : 0;
+        row_seq.insert(row_seq.end(), (size_t)len[i], i);
+        rows += len[i];
+        if (k) {
+            for (int t = 0; t < nt; ++t) { planes.push_back(i); planes.push_back(t); }
+            tiles += nt * nkv;
+        }
+        // the pairs of one kernel are numbered in pack order: pair p of that launch on XCD p % 8
+        const int nb = rps_blocks(len[i], attn_prefill_rows_wg(kernel[i], nrep));
+        for (int g = 0; g < nkv; ++g) {
+            std::vector<int>& w = work[k][(size_t)(pairs[k]++ & 7)];
+            for (int b = nb - 1; b >= 0; --b) { w.push_back(i * nkv + g); w.push_back(b); }
+        }
+    }
+    // long query blocks first within an XCD: by the last position of the block (the length of its key walk), stable
+    for (int k = 0; k < 2; ++k) {
+        const int rows_wg = attn_prefill_rows_wg(k ? AP_X3 : AP_T, nrep);
+        size_t most = 0;
+        for (std::vector<int>& w : work[k]) {
+            std::vector<std::pair<int, int>> it;
+            for (size_t j = 0; j < w.size(); j += 2) it.emplace_back(w[j], w[j + 1]);
+            auto last_pos = [&](const std::pair<int, int>& e) { const int L = len[e.first / nkv], e1 = (e.second + 1) * rows_wg; return e1 < L ? e1 : L; };
+            std::stable_sort(it.begin(), it.end(), [&](const std::pair<int, int>& x, const std::pair<int, int>& y) { return last_pos(x) > last_pos(y); });
+            for (size_t j = 0; j < it.size(); ++j) { w[2 * j] = it[j].first; w[2 * j + 1] = it[j].second; }
+            most = std::max(most, it.size());
+        }
+        out->per_xcd[k] = (int)most;
+    }
+    auto even = [&] { if (out->blob.size() & 3) out->blob.resize((out->blob.size() + 3) & ~(size_t)3, 0); };      // 16-byte starts
+    out->off_seq = 0; out->blob = seq; even();
+    out->off_row_seq = out->blob.size(); out->blob.insert(out->blob.end(), row_seq.begin(), row_seq.end()); even();
+    for (int k = 0; k < 2; ++k) {
+        out->off_work[k] = out->blob.size();
+        for (const std::vector<int>& w : work[k]) {
+            out->blob.insert(out->blob.end(), w.begin(), w.end());
+            for (size_t j = w.size() / 2; j < (size_t)out->per_xcd[k]; ++j) { out->blob.push_back(-1); out->blob.push_back(0); }
+        }
+        even();
+    }
+    out->off_planes = out->blob.size(); out->blob.insert(out->blob.end(), planes.begin(), planes.end()); even();
+    out->n_seq = n; out->rows = rows; out->n_plane_items = (int)(planes.size() / 2); out->plane_tiles = tiles;
+    return true;
+}
+
+hipError_t launch_kv_planes_pack(const AttnArgs& kv, const PackTab& t, unsigned char* kvp, hipStream_t st) {
+    if (t.n_plane_items < 1) return hipSuccess;
+    if (!kvp || !t.plane_items || !t.seq || kv.nkv < 1 || kv.nkv > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_kv_planes_pack, dim3(t.n_plane_items, kv.nkv), dim3(256), 0, st, kv, kvp, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_attn_prefill_pack(const AttnArgs& a, const PackTab& t, int kernel, hipStream_t st) {
+    if (kernel != AP_T && kernel != AP_X3) return hipErrorInvalidValue;
+    const int k = kernel == AP_X3 ? 1 : 0;
+    if (t.per_xcd[k] < 1) return hipSuccess;                                   // no sequence of the pack takes this kernel
+    if (a.nkv < 1 || a.nh % a.nkv || !t.seq || !t.work[k] || (k && !a.kvp)) return hipErrorInvalidValue;
+    const int nrep = a.nh / a.nkv;
+    dim3 g1((unsigned)(8 * t.per_xcd[k]));
+    if (k) {
+        if (nrep == 1) hipLaunchKernelGGL((k_attn_prefill_x3_pack<1>), g1, dim3(512), 0, st, a, t);
+        else if (nrep == 2) hipLaunchKernelGGL((k_attn_prefill_x3_pack<2>), g1, dim3(512), 0, st, a, t);
+        else if (nrep == 4) hipLaunchKernelGGL((k_attn_prefill_x3_pack<4>), g1, dim3(512), 0, st, a, t);
+        else return hipErrorInvalidValue;
+    } else {
+        if (nrep == 1) hipLaunchKernelGGL((k_attn_prefill_t_pack<1>), g1, dim3(256), 0, st, a, t);
+        else if (nrep == 2) hipLaunchKernelGGL((k_attn_prefill_t_pack<2>), g1, dim3(256), 0, st, a, t);
+        else if (nrep == 4) hipLaunchKernelGGL((k_attn_prefill_t_pack<4>), g1, dim3(256), 0, st, a, t);
+        else return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 // ---- kernel selection (attn_prefill_pick) apart from launching: the prefill attention knobs are read here only ----

@@ -997,14 +997,21 @@ static int prefill_gemm_chunk(int B) {
 // P0 > 0: positions [0, P0) are already in the rows' pages (linked from the prefix cache) and are not computed again. The passes
 // keep the cuts of the run from 0 — the same chunks, and inside the chunk P0 lies in the same query blocks (prefix_usable_pages rounds P0
 // to a block boundary of that chunk) — so every position from P0 on sees the arithmetic of the uncached run.
-static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, int P0 = 0) {      // positions [P0, S) of the S_all-position prompts
+// A packed pass (pk): the prompts of pk->side — one-row side sessions of `s`, staged, each from position 0 and
+// of its own length — lie end to end in ONE activation matrix and go through the layers together: the GEMMs see one M (their
+// bits are batch-invariant), the attention-side launches find sequences through the pack's tables, and each row's head writes
+// its side session's LASTH / LOGITS with the launches of its one-row prefill. S_all, S and P0 are unused then.
+struct PrefillPack { std::vector<q3_session*> side; PackHost host; };
+static bool prefill_x3_on() { const char* x3e = getenv("Q3_PREFILL_ATTN_X3"); return !(x3e && atoi(x3e) == 0); }
+static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, int P0 = 0, const PrefillPack* pk = nullptr) {      // positions [P0, S) of the S_all-position prompts
     const q3_model* m = s->m; const q3_config& c = m->cfg;
     const LmDims d = talker_dims(c);
-    const int B = s->B, H = d.H, QD = d.nh * HEAD_DIM, KD = d.nkv * HEAD_DIM, I = d.I;
+    const int B = pk ? 1 : s->B, H = d.H, QD = d.nh * HEAD_DIM, KD = d.nkv * HEAD_DIM, I = d.I;
+    if (pk) { S_all = S = pk->host.rows; P0 = 0; }      // one chunk of all the pack's rows
     // positions per sequence per pass: up to 4224 activation rows per launch (a whole 4k-position prompt in one pass:
     // 33 M-tiles x N/128 workgroups per GEMM, 520 attention workgroups; 2048-row passes: 113 ms instead of 99 for the
     // 4105-position prefill of the 1.7B model), at least one 128-row tile per sequence
-    const int C = prefill_gemm_chunk(B);
+    const int C = pk ? S : prefill_gemm_chunk(B);
     const int max_rows = B * (S < C ? S : C);
     struct SyncedPool : DevPool { hipStream_t st; explicit SyncedPool(hipStream_t s_) : st(s_) {} ~SyncedPool() { (void)hipStreamSynchronize(st); } };
     SyncedPool tmp(s->stream);       // on EVERY return path the stream is drained before the blocks go back to the cache
@@ -1018,16 +1025,25 @@ static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, i
     // long prompts: every query block's key range is halved over two workgroups and merged (k_attn_prefill_t)
     static const bool no_split = getenv("Q3_PREFILL_ATTN_NOSPLIT") != nullptr;
     static const bool gen2_attn = getenv("Q3_PREFILL_ATTN_GEN2") != nullptr || getenv("Q3_PREFILL_ATTN_VALU") != nullptr;
-    const bool kv_split = !no_split && !gen2_attn && S >= 1024;
+    const bool kv_split = !pk && !no_split && !gen2_attn && S >= 1024;
     float* PART = nullptr;
     if (kv_split) HIPC(tmp.alloc(&PART, (size_t)max_rows * d.nh * 2 * PART_STRIDE));
     // bf16-matrix-core attention (k_attn_prefill_x3) over per-layer bf16x3 planes of the cached K/V; Q3_PREFILL_ATTN_X3=0
     // keeps the f32-MFMA generation (A/B aid, read per call)
-    const char* x3e = getenv("Q3_PREFILL_ATTN_X3");
-    const bool attn_x3 = !gen2_attn && !(x3e && atoi(x3e) == 0) && S >= 256;
+    const bool attn_x3 = pk ? pk->host.n_plane_items > 0 : !gen2_attn && prefill_x3_on() && S >= 256;
     unsigned char* KVP = nullptr;
-    const int kvp_tiles = (S + 31) / 32;
-    if (attn_x3) HIPC(tmp.alloc(&KVP, (size_t)B * d.nkv * kvp_tiles * KVP_TILE_BYTES));
+    const int kvp_tiles = pk ? pk->host.plane_tiles : (S + 31) / 32;      // (a pack: all its sequences' tiles, kv heads included)
+    if (attn_x3) HIPC(tmp.alloc(&KVP, (size_t)(pk ? 1 : B * d.nkv) * kvp_tiles * KVP_TILE_BYTES));
+    // a pack's tables and the page-table rows of its side sessions, one block each
+    int* PKT = nullptr; unsigned long long* PKP = nullptr; PackTab ptab{};
+    if (pk) {
+        if (!s->paged || gen2_attn) return set_err(Q3_INVALID_ARG, "packed prefill: needs paged K/V and the default attention kernels");
+        HIPC(tmp.alloc(&PKT, pk->host.blob.size())); HIPC(tmp.alloc(&PKP, pk->side.size() * KV_MAX_PAGES));
+        HIPC(hipMemcpyAsync(PKT, pk->host.blob.data(), pk->host.blob.size() * 4, hipMemcpyHostToDevice, s->stream));
+        for (size_t j = 0; j < pk->side.size(); ++j)      // (the side sessions run on this stream: their table uploads are in order before this copy)
+            HIPC(hipMemcpyAsync(PKP + j * KV_MAX_PAGES, pk->side[j]->kv_table, (size_t)KV_MAX_PAGES * 8, hipMemcpyDeviceToDevice, s->stream));
+        ptab = pk->host.tab(PKT);
+    }
     static const bool no_planes = getenv("Q3_GEMM_NO_PLANES") != nullptr;
     const bool planes = !no_planes && H % 8 == 0 && QD % 8 == 0 && I % 8 == 0;
     const int kmax = std::max(kp(H), std::max(kp(QD), kp(I)));
@@ -1049,6 +1065,11 @@ static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, i
         const int t0 = c0 > P0 ? c0 : P0;
         ch = c1 - t0;
         const int rows = B * ch;
+        if (pk) {
+            const PackSeq* ps = reinterpret_cast<const PackSeq*>(pk->host.blob.data() + pk->host.off_seq);
+            for (size_t j = 0; j < pk->side.size(); ++j)
+                HIPC(launch_copy_rows(pk->side[j]->embeds, H, X + (size_t)ps[j].row0 * H, H, ps[j].len, H, s->stream));
+        } else
         for (int b = 0; b < B; ++b)
             HIPC(launch_copy_rows(s->embeds + ((size_t)b * S_all + t0) * H, H, X + (size_t)b * ch * H, H, ch, H, s->stream));
         for (int i = 0; i < d.layers; ++i) {
@@ -1062,10 +1083,16 @@ static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, i
             t.qkv = QKV; t.ld_qkv = QD + 2 * KD; t.q_norm_w = w.q_norm; t.k_norm_w = w.k_norm; t.eps = d.eps;
             t.rope_cos = m->rope_cos; t.rope_sin = m->rope_sin; t.pos_dev = nullptr; t.pos_static = t0;
             if (s->paged) {
-                t.kv_pages = s->kv_table; t.kv_layer_off = (size_t)i * m->kv_pool.layer_stride(); t.kv_vdelta = m->kv_pool.v_delta();
+                t.kv_pages = pk ? PKP : s->kv_table; t.kv_layer_off = (size_t)i * m->kv_pool.layer_stride(); t.kv_vdelta = m->kv_pool.v_delta();
             } else { t.kcache = s->kcache + (size_t)i * s->kv_layer_stride; t.vcache = s->vcache + (size_t)i * s->kv_layer_stride; }
             t.max_seq = s->max_seq; t.qbuf = Qb; t.part = nullptr; t.out = ATT; t.ld_out = QD;
             t.B = rows; t.nh = d.nh; t.nkv = d.nkv; t.n_splits = 1; t.rows_per_seq = ch;
+            if (pk) {      // one launch each of norm + RoPE + append and of the plane split, at most one per attention kernel
+                HIPC(launch_qknorm_rope_kv_pack(t, ptab, s->stream));
+                if (attn_x3) { HIPC(launch_kv_planes_pack(t, ptab, KVP, s->stream)); t.kvp = KVP; t.kvp_tiles = kvp_tiles; }
+                HIPC(launch_attn_prefill_pack(t, ptab, AP_T, s->stream));
+                HIPC(launch_attn_prefill_pack(t, ptab, AP_X3, s->stream));
+            } else {
             HIPC(launch_qknorm_rope_kv(t, s->stream));
             if (attn_x3) {
                 HIPC(launch_kv_planes(t, B * d.nkv, t0 + ch, kvp_tiles, KVP, s->stream));
@@ -1074,6 +1101,7 @@ static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, i
             if (kv_split) { t.part = PART; t.n_splits = 2; }
             HIPC(launch_attn_prefill(t, s->stream));
             if (kv_split) HIPC(launch_attn_merge(t, s->stream));
+            }
             GemmArgs o; o.W = w.o.t1; o.x = ATT; o.ldx = QD; o.resid = X; o.ldr = H; o.y = SUM; o.ldy = H;
             o.M = rows; o.N = H; o.K = QD; o.Kpad = kp(QD); o.epi = EPI_RESID;
             o.splitk_ws = SKW; o.splitk_ws_bytes = skw_bytes;
@@ -1090,6 +1118,19 @@ static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, i
         }
     }
     if (!with_head) { HIPC(sync_frames(s)); return Q3_OK; }      // the caller runs the remaining positions
+    if (pk) {      // each row's head as its one-row prefill launches it, into its side session
+        const PackSeq* ps = reinterpret_cast<const PackSeq*>(pk->host.blob.data() + pk->host.off_seq);
+        for (size_t j = 0; j < pk->side.size(); ++j) {
+            q3_session* sd = pk->side[j];
+            HIPC(launch_rmsnorm(X + (size_t)(ps[j].row0 + ps[j].len - 1) * H, ps[j].len * H, m->norm, sd->LASTH, H, 1, H, c.rms_eps, s->stream));
+            LinArgs h;
+            h.N = c.codec_vocab; h.K = H; set_w(h, m->codec_head, 1, h.N, h.K); h.x = sd->LASTH; h.ldx = H; h.y = sd->LOGITS; h.ldy = c.codec_vocab;
+            h.M = 1; h.epi = EPI_NONE;
+            HIPC(run_linear(sd, h));
+        }
+        HIPC(sync_frames(s));
+        return Q3_OK;
+    }
     // head on each sequence's last position (row b*ch + ch-1 of the last chunk): final norm -> LASTH, codec_head -> LOGITS
     HIPC(launch_rmsnorm(X + (size_t)(ch - 1) * H, ch * H, m->norm, s->LASTH, H, B, H, c.rms_eps, s->stream));
     LinArgs h;
@@ -1217,11 +1258,79 @@ static void prefix_regroup(q3_session* s) {
     for (int b = 0; b < s->B; ++b) s->ragged[(size_t)b].own(s->seq[(size_t)b].request(), s->m->cfg.hidden);
 }
 
+// q3_session_prefill in its three parts — stage the inputs, run the layers, finish — so that a packed pass (prefill_ragged) can run
+// the middle part once for several one-row side sessions. What the staged uploads read lives in PrefillStaged until the finish.
+struct PrefillStaged {
+    std::vector<uint32_t> ids; std::vector<int> text_row, codec_id, trail_base, trail_len, pad_row, ready_v, limit_v; std::vector<float> xv;
+    int P0 = 0; bool cached = false, regroup = false;      // regroup: the rows hit the prefix cache differently (prefix_link said -1)
+};
+static q3_status prefill_stage(q3_session* s, PrefillStaged& g);
+static q3_status prefill_layers(q3_session* s, int P0);
+static q3_status prefill_finish(q3_session* s, const PrefillStaged& g);
+
+// Which rows of a ragged first batch share a packed pass: pure host arithmetic. A row packs when the GEMM path may
+// run (gemm_ok), 48 <= length < 1024 (prefill_cut_of then gives Sg == S, and there are no key halves), it plans no prefix hit
+// and is not barred by ok_row; packs form in row order and close when the next row would pass the budget; a pack of
+// one row (a row longer than the budget always ends as one) is no pack. pass[b] = the row's pass or -1 (today's equal-length groups), row0[b] = its first activation row in the pass.
+static int pack_plan(const int32_t* len, const int32_t* hit, const char* ok_row, int n, int budget, bool gemm_ok, int32_t* pass, int32_t* row0) {
+    int n_pass = 0, first = -1, count = 0, total = 0;
+    auto close = [&] {
+        if (count >= 2) ++n_pass;
+        else if (count == 1) { pass[first] = -1; row0[first] = 0; }
+        count = 0; total = 0;
+    };
+    for (int b = 0; b < n; ++b) {
+        pass[b] = -1; row0[b] = 0;
+        if (!gemm_ok || len[b] < 48 || len[b] >= 1024 || (hit && hit[b] != 0) || (ok_row && !ok_row[b])) continue;
+        if (count > 0 && total + len[b] > budget) close();
+        if (count == 0) first = b;
+        pass[b] = n_pass; row0[b] = total; total += len[b]; ++count;
+    }
+    close();
+    return n_pass;
+}
+extern "C" q3_status q3_prefill_pack_plan(const int32_t* lengths, const int32_t* hit_pages, int32_t n, int32_t row_budget, int32_t gemm_ok,
+                                          int32_t* pass, int32_t* row0, int32_t* n_passes) {
+    if (!lengths || !pass || !row0) return set_err(Q3_INVALID_ARG, "q3_prefill_pack_plan: null argument");
+    if (n < 1) return set_err(Q3_INVALID_ARG, "q3_prefill_pack_plan: %d rows", n);
+    if (row_budget < 128) return set_err(Q3_INVALID_ARG, "q3_prefill_pack_plan: row budget %d below one 128-row tile", row_budget);
+    for (int b = 0; b < n; ++b) {
+        if (lengths[b] < 1) return set_err(Q3_INVALID_ARG, "q3_prefill_pack_plan: row %d: %d positions", b, lengths[b]);
+        if (hit_pages && hit_pages[b] < 0) return set_err(Q3_INVALID_ARG, "q3_prefill_pack_plan: row %d: %d hit pages", b, hit_pages[b]);
+    }
+    const int np = pack_plan(lengths, hit_pages, nullptr, n, row_budget, gemm_ok != 0, pass, row0);
+    if (n_passes) *n_passes = np;
+    return Q3_OK;
+}
+extern "C" q3_status q3_session_prefill_info(const q3_session* s, int32_t info[8]) {
+    if (!s || !info) return set_err(Q3_INVALID_ARG, "q3_session_prefill_info: null argument");
+    for (int i = 0; i < 8; ++i) info[i] = s->prefill_info[i];
+    return Q3_OK;
+}
+// the row budget of a pack: prefill_gemm_chunk's, read per call (a pack is one chunk)
+static int pack_row_budget() {
+    const char* e = getenv("Q3_PREFILL_ROWS");
+    const int r = e ? atoi(e) : 4224;
+    return r < 128 ? 128 : r;
+}
+// may this session's ragged rows pack at all (the per-row conditions are pack_plan's)
+static bool pack_session_ok(const q3_session* s) {
+    const char* e = getenv("Q3_PREFILL_PACK");           // read per call; 0 = the grouped path
+    if (e && atoi(e) == 0) return false;
+    if (!s->paged || s->debug || s->profile || s->no_chunk || !d_nh_ok(s->m->cfg)) return false;
+    // the attention A/B aids select kernels the packed launches do not have
+    for (const char* k : {"Q3_PREFILL_ATTN_VALU", "Q3_PREFILL_ATTN_GEN2", "Q3_PREFILL_ATTN_NOSPLIT", "Q3_GEMM_NO_PLANES"}) if (getenv(k)) return false;
+    return true;
+}
+
 // q3_session_prefill of a ragged first batch (session_create_any): the idle rows never run — every row's state comes from a side
-// session. Rows are grouped by prefill length in row order; a group of G rows is one batched side prefill.
+// session. Rows whose prompts take the GEMM path from position 0 share packed passes (pack_plan): each is the one-row
+// side session of a batch-1 run, staged and finished by that run's own code, and only the layers run once for all of them. The
+// other rows are grouped by prefill length in row order; a group of G rows is one batched side prefill.
 static q3_status prefill_ragged(q3_session* s) {
     if (s->debug || s->profile) return set_err(Q3_UNSUPPORTED, "debug / profiling sessions need rows of one prefill length");
     const int B = s->B;
+    for (int& v : s->prefill_info) v = 0;
     s->kv_in_bf16 = s->kv_bf16;                          // the idle rows hold no pages: nothing to convert
     s->prefilled = true; s->frames_run = 0; s->codes_host_valid = false;      // transplant_row stamps rows with start_run = frames_run
     std::vector<char> placed((size_t)B, 0);
@@ -1239,16 +1348,84 @@ static q3_status prefill_ragged(q3_session* s) {
             const int el = shape[(size_t)b].prefix_pages, S = shape[(size_t)b].prefill_len;
             if (el > 0) hit[(size_t)b] = prefix_usable_pages_of(s->m, 1, S, prefix_peek(s->m, prefix_regime_of(s->m, 1, S, s->n_splits), r.instruct_ids, el));
         }
+    // a failure leaves the session un-prefilled and holding no page (rows of earlier passes were moved in already)
+    auto fail = [&](q3_status st) {
+        (void)sync_frames(s);
+        for (int b = 0; b < B; ++b) kv_release_row(s, b);
+        s->prefilled = false;
+        for (int& v : s->prefill_info) v = 0;
+        return st;
+    };
+    auto row_limit = [&](int b, int* Lb) -> q3_status {
+        // the row's RESOLVED limit (PromptShape::limit: under the ICL cap) is what session_create_any sized max_frames for — the
+        // raw max_length of an ICL row may well exceed it
+        const q3_request& r = s->ragged[(size_t)b].r;
+        *Lb = shape[(size_t)b].limit;
+        if (r.opts.max_length < 1 || *Lb < 1 || *Lb > s->max_frames) return set_err(Q3_INVALID_ARG, "row %d: max_length %d (resolved %d) outside 1..%d", b, r.opts.max_length, *Lb, s->max_frames);
+        return Q3_OK;
+    };
+    // ---- packed passes ----
+    std::vector<int32_t> pass((size_t)B, -1), row0((size_t)B, 0);
+    int n_pass = 0;
+    if (pack_session_ok(s)) {
+        std::vector<int32_t> len((size_t)B); std::vector<char> ok((size_t)B, 1);
+        for (int b = 0; b < B; ++b) {
+            int Sg = 0; const int S = len[(size_t)b] = shape[(size_t)b].prefill_len;
+            // the row's own prefill must be ONE GEMM pass over [0, S): what the pack reproduces
+            ok[(size_t)b] = prefill_cut_of(s->m, S, &Sg) && Sg == S && S <= prefill_gemm_chunk(1);
+        }
+        n_pass = pack_plan(len.data(), hit.data(), ok.data(), B, pack_row_budget(), true, pass.data(), row0.data());
+    }
+    for (int p = 0; p < n_pass; ++p) {
+        std::vector<int> rows;
+        for (int b = 0; b < B; ++b) if (pass[(size_t)b] == p) rows.push_back(b);
+        const size_t n = rows.size();
+        std::vector<std::unique_ptr<q3_session>> side(n); std::vector<PrefillStaged> staged(n); std::vector<int> lim(n, 0);
+        q3_status st = Q3_OK;
+        for (size_t j = 0; j < n && st == Q3_OK; ++j) {
+            int Lb = 0;
+            st = row_limit(rows[j], &Lb);
+            if (st == Q3_OK) st = side_prefill(s, &s->ragged[(size_t)rows[j]].r, &Lb, 1, false, false, true, s->stream, &side[j], &lim[j], nullptr, true);
+            if (st == Q3_OK) st = prefill_stage(side[j].get(), staged[j]);
+            placed[(size_t)rows[j]] = 1;
+        }
+        // a row that links cached pages after all (the plan was only a look) starts at P0 > 0: it runs its own layers
+        PrefillPack pk; std::vector<int> plen, ptrow, pkern;
+        for (size_t j = 0; j < n && st == Q3_OK; ++j) {
+            if (staged[j].P0 > 0 || staged[j].regroup) continue;
+            const int S = side[j]->prefill_len;
+            pk.side.push_back(side[j].get()); plen.push_back(S); ptrow.push_back((int)pk.side.size() - 1);
+            pkern.push_back(prefill_x3_on() && S >= 256 ? AP_X3 : AP_T);      // the kernel its length selects when prefilled alone
+        }
+        if (st == Q3_OK && pk.side.size() >= 2) {
+            const LmDims d = talker_dims(s->m->cfg);
+            if (!pack_host_build(plen.data(), ptrow.data(), pkern.data(), (int)plen.size(), d.nh, d.nkv, &pk.host)) st = set_err(Q3_INVALID_ARG, "packed prefill: tables");
+            if (st == Q3_OK) st = prefill_gemm(s, 0, 0, true, 0, &pk);
+            if (st == Q3_OK) {
+                s->prefill_info[0] += 1; s->prefill_info[1] += 1; s->prefill_info[2] += (int)pk.side.size();
+                s->prefill_info[3] = std::max(s->prefill_info[3], pk.host.rows);
+            }
+        }
+        for (size_t j = 0; j < n && st == Q3_OK; ++j) {
+            const bool packed = pk.side.size() >= 2 && std::find(pk.side.begin(), pk.side.end(), side[j].get()) != pk.side.end();
+            if (staged[j].regroup) { st = set_err(Q3_INVALID_ARG, "packed prefill: a one-row side session cannot regroup"); break; }
+            if (!packed) { st = prefill_layers(side[j].get(), staged[j].P0); s->prefill_info[0] += 1; s->prefill_info[4] += 1; }
+            if (st == Q3_OK) st = prefill_finish(side[j].get(), staged[j]);
+        }
+        if (st == Q3_OK && sync_frames(s) != hipSuccess) st = set_err(Q3_HIP_ERROR, "ragged prefill: stream");
+        for (size_t j = 0; j < n && st == Q3_OK; ++j) st = transplant_row(s, rows[j], side[j].get(), 0, lim[j]);
+        if (st != Q3_OK) { (void)sync_frames(s); return fail(st); }      // (the stream is drained before the staged vectors and the side sessions go)
+    }
+    // ---- equal-length groups ----
     for (int b0 = 0; b0 < B; ++b0) {
         if (placed[(size_t)b0]) continue;
         std::vector<int> rows; std::vector<q3_request> reqs; std::vector<int> limits;
         for (int b = b0; b < B; ++b) {
             if (placed[(size_t)b] || shape[(size_t)b].prefill_len != shape[(size_t)b0].prefill_len || hit[(size_t)b] != hit[(size_t)b0]) continue;
             const q3_request& r = s->ragged[(size_t)b].r;
-            // the row's RESOLVED limit (PromptShape::limit: under the ICL cap) is what session_create_any sized max_frames for — the
-            // raw max_length of an ICL row may well exceed it
-            const int Lb = shape[(size_t)b].limit;
-            if (r.opts.max_length < 1 || Lb < 1 || Lb > s->max_frames) { s->prefilled = false; return set_err(Q3_INVALID_ARG, "row %d: max_length %d (resolved %d) outside 1..%d", b, r.opts.max_length, Lb, s->max_frames); }
+            int Lb = 0;
+            const q3_status ls = row_limit(b, &Lb);
+            if (ls != Q3_OK) return fail(ls);
             limits.push_back(Lb);
             rows.push_back(b); reqs.push_back(r); placed[(size_t)b] = 1;
         }
@@ -1256,23 +1433,20 @@ static q3_status prefill_ragged(q3_session* s) {
         q3_status st = side_prefill(s, reqs.data(), limits.data(), (int)reqs.size(), false, false, true, s->stream, &side, lim.data());
         if (st == Q3_OK && sync_frames(s) != hipSuccess) st = set_err(Q3_HIP_ERROR, "ragged prefill: stream");
         for (size_t j = 0; j < rows.size() && st == Q3_OK; ++j) st = transplant_row(s, rows[j], side.get(), (int)j, lim[j]);
-        if (st != Q3_OK) { s->prefilled = false; return st; }
+        if (st != Q3_OK) return fail(st);
+        s->prefill_info[0] += 1; s->prefill_info[4] += (int)rows.size();
     }
     s->ragged.clear();
     return Q3_OK;
 }
 
 static q3_status frame_capture(q3_session* s, bool stream_busy);
-extern "C" q3_status q3_session_prefill(q3_session* s) {
-    if (!s) return set_err(Q3_INVALID_ARG, "null session");
-    if (s->prefilled) return set_err(Q3_INVALID_ARG, "session already prefilled");
+static q3_status prefill_stage(q3_session* s, PrefillStaged& g) {
     const q3_model* m = s->m; const q3_config& c = m->cfg;
-    HIPC(hipSetDevice(m->device));
-    if (!s->ragged.empty()) return prefill_ragged(s);
     const int B = s->B, H = c.hidden, S = s->prefill_len;
     // prefix cache: the rows link the cached pages of their instructions and the prompt is computed from position P0 on
-    const bool cached = prefix_session_ok(s);
-    int P0 = 0;
+    const bool cached = g.cached = prefix_session_ok(s);
+    int& P0 = g.P0;
     if (cached) {
         // a prefill that failed after linking (a later row's Q3_KV_OVERFLOW) left pages in the rows: they go back first, so that
         // this attempt links again instead of computing [0, P) into pages the cache and other rows hold
@@ -1285,14 +1459,16 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
         q3_status lst = Q3_OK;
         P0 = prefix_link(s, &lst);
         Q3C(lst);
-        if (P0 < 0) { prefix_regroup(s); return prefill_ragged(s); }      // rows that hit differently: each group keeps the bits of its own run
+        if (P0 < 0) { g.regroup = true; return Q3_OK; }      // rows that hit differently: each group keeps the bits of its own run
     }
     for (int b = 0; b < B; ++b) Q3C(kv_reserve_row(s, b, S + 1));      // paged KV: the prompt's positions and the first frame's
     // 1. ids to project, per sequence: [instruct…, IM_START, ASSISTANT, NEWLINE, TTS_PAD, TTS_BOS, text…, TTS_EOS]
-    std::vector<uint32_t> ids; ids.reserve(s->n_rows_total);
-    std::vector<int> text_row((size_t)B * S, -1), codec_id((size_t)B * S, -1);
-    std::vector<int> trail_base(B), trail_len(B), pad_row(B);
-    std::vector<float> xv((size_t)B * H, 0.0f);
+    std::vector<uint32_t>& ids = g.ids; ids.clear(); ids.reserve(s->n_rows_total);
+    std::vector<int>& text_row = g.text_row; std::vector<int>& codec_id = g.codec_id;
+    text_row.assign((size_t)B * S, -1); codec_id.assign((size_t)B * S, -1);
+    std::vector<int>& trail_base = g.trail_base; std::vector<int>& trail_len = g.trail_len; std::vector<int>& pad_row = g.pad_row;
+    trail_base.assign((size_t)B, 0); trail_len.assign((size_t)B, 0); pad_row.assign((size_t)B, 0);
+    std::vector<float>& xv = g.xv; xv.assign((size_t)B * H, 0.0f);
     for (int b = 0; b < B; ++b) {
         SeqInfo& q = s->seq[b];
         for (uint32_t id : q.instruct) ids.push_back(id);
@@ -1320,7 +1496,7 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
             if (!s->seq[b].ref_codes.empty())
                 HIPC(q3_hipMemcpy(s->ref_codes_dev + ref_off[b], s->seq[b].ref_codes.data(), s->seq[b].ref_codes.size() * 4, hipMemcpyHostToDevice));
     }
-    // uploads ride the session stream (the host vectors live until the synchronisation that ends this function)
+    // uploads ride the session stream (the host vectors live in PrefillStaged until the synchronisation that ends the prefill)
     HIPC(hipMemcpyAsync(ids_dev, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s->stream));
     HIPC(hipMemcpyAsync(tr_dev, text_row.data(), text_row.size() * 4, hipMemcpyHostToDevice, s->stream));
     HIPC(hipMemcpyAsync(ci_dev, codec_id.data(), codec_id.size() * 4, hipMemcpyHostToDevice, s->stream));
@@ -1337,7 +1513,8 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
                                      s->ref_codes_dev ? s->ref_codes_dev + ref_off[b] : nullptr, m->cp_embs_dev);
         if (e != hipSuccess) st = set_err(Q3_HIP_ERROR, "prefill assembly: %s", hipGetErrorString(e));
     }
-    std::vector<int> ready_v, limit_v;
+    std::vector<int>& ready_v = g.ready_v; std::vector<int>& limit_v = g.limit_v;
+    ready_v.clear(); limit_v.clear();
     if (st == Q3_OK && s->text_ready) {
         // open rows: the trailing rows received so far (+ tts_eos if the text closed before the prefill) go through the appended
         // rows' projection path, whatever arrived when; text_ready / limit of every row published with the rest
@@ -1356,6 +1533,10 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
         }
     }
     if (st != Q3_OK) { (void)sync_frames(s); return st; }
+    return Q3_OK;
+}
+static q3_status prefill_layers(q3_session* s, int P0) {
+    const int B = s->B, H = s->m->cfg.hidden, S = s->prefill_len;
     // 2. run_prefill_layers (talker.rs:823-841): causal attention ⇒ token-by-token decode steps
     //    and the GEMV kernels take up to 16 rows for the price of one, so each weight pass carries a CHUNK of
     //    16/B consecutive positions per sequence (q3_kernels.h AttnArgs::rows_per_seq). Bit-identical to the
@@ -1374,6 +1555,10 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
             HIPC(launch_copy_rows(s->embeds + ((size_t)b * S + t0) * H, H, s->tb.X + (size_t)b * ch * H, H, ch, H, s->stream));
         Q3C(talker_step(s, nullptr, t0, t0 + ch >= S, ch));
     }
+    return Q3_OK;
+}
+static q3_status prefill_finish(q3_session* s, const PrefillStaged& g) {
+    const int B = s->B, S = s->prefill_len; const bool cached = g.cached;
     // 3. first sampling decision (lib.rs:558-571)
     std::vector<int> posv(B, S), zero(B, 0);
     HIPC(hipMemcpyAsync(s->pos, posv.data(), B * 4, hipMemcpyHostToDevice, s->stream));
@@ -1397,6 +1582,17 @@ extern "C" q3_status q3_session_prefill(q3_session* s) {
     if (s->kv_bf16 && !s->kv_in_bf16) Q3C(kv_convert_to_bf16(s));       // the prompt's K/V moves into pages of the bf16 pool, once
     s->prefilled = true; s->frames_run = 0; s->codes_host_valid = false;
     return Q3_OK;
+}
+extern "C" q3_status q3_session_prefill(q3_session* s) {
+    if (!s) return set_err(Q3_INVALID_ARG, "null session");
+    if (s->prefilled) return set_err(Q3_INVALID_ARG, "session already prefilled");
+    HIPC(hipSetDevice(s->m->device));
+    if (!s->ragged.empty()) return prefill_ragged(s);
+    PrefillStaged g;
+    Q3C(prefill_stage(s, g));
+    if (g.regroup) { prefix_regroup(s); return prefill_ragged(s); }
+    Q3C(prefill_layers(s, g.P0));
+    return prefill_finish(s, g);
 }
 
 static q3_status refresh_codes(q3_session* s) {

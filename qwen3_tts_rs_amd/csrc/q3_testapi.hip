@@ -1022,6 +1022,128 @@ extern "C" q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_arg
     return Q3_OK;
 }
 
+// The packed sibling: sequences of seq_len[i] rows, all from position 0, end to end in qkv / out. The packed q/k-norm
+// launch, the packed plane split where a sequence takes the bf16x3 kernel, one packed attention launch per kernel present.
+extern "C" q3_status q3_attn_prefill_packed_ex(int device, const q3_attn_prefill_packed_ex_args* p) {
+    if (!p || !p->seq_len || !p->qkv || !p->q_norm_w || !p->k_norm_w || !p->rope_cos || !p->rope_sin || !p->kcache || !p->vcache || !p->out)
+        return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: null argument");
+    if (p->path) p->path[0] = p->path[1] = 0;
+    if (p->plane_tail) p->plane_tail[0] = p->plane_tail[1] = 0;
+    const int n_seq = p->n_seq, nh = p->nh, nkv = p->nkv, layout = p->layout, max_seq = p->max_seq;
+    if (p->kernel != -1 && p->kernel != AP_T && p->kernel != AP_X3) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: kernel -1, 2 or 3");
+    if (n_seq < 1 || n_seq > 64 || nkv < 1 || nh < nkv || nh > 64 || nh % nkv || max_seq < 1 || max_seq > 8192)
+        return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: bad shape");
+    const int nrep = nh / nkv;
+    if (nrep != 1 && nrep != 2 && nrep != 4) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: heads / kv heads 1, 2 or 4");
+    int rows = 0;
+    std::vector<int> trow((size_t)n_seq), kern((size_t)n_seq);
+    for (int s = 0; s < n_seq; ++s) {
+        const int L = p->seq_len[s];
+        if (L < 1 || L > max_seq) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: seq_len[%d] = %d outside 1 .. max_seq (%d)", s, L, max_seq);
+        rows += L; trow[(size_t)s] = s; kern[(size_t)s] = p->kernel >= 0 ? p->kernel : (L >= 256 ? AP_X3 : AP_T);
+    }
+    if (rows > 16384) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: %d rows (at most 16384)", rows);
+    const int ld_qkv = p->ld_qkv, QD = nh * HEAD_DIM;
+    if (ld_qkv < (nh + 2 * nkv) * HEAD_DIM || ld_qkv % 4 || p->ld_out < QD || p->ld_out % 4) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: bad pitch");
+    if (layout < 0 || layout > 1) return set_err(layout == 2 ? Q3_UNSUPPORTED : Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: layout 0 or 1 (prefill never runs on bf16 pages)");
+    const int n_pg = (max_seq + KV_PAGE_POS - 1) / KV_PAGE_POS;
+    auto cache_row = [&](float* c, int s, int g, int pp) { return c + (((size_t)s * nkv + g) * max_seq + pp) * HEAD_DIM; };
+    TestSlabs slabs;
+    if (layout == 1) {
+        if (p->n_layers < 1 || p->n_layers > 4 || p->layer < 0 || p->layer >= p->n_layers || p->n_slabs < 1 || p->n_slabs > 2)
+            return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: n_layers 1..4, layer inside them, n_slabs 1..2");
+        if (!p->page_slots || !p->stray) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: a paged layout needs page_slots and stray");
+        slabs.shape(p->n_layers, nkv, 4);
+        if (slabs.geo.v_delta() > 0x7fffffffu) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: K -> V distance beyond the kernels' 32-bit form");
+        const int limit = KvPool::SLAB_SLOTS * p->n_slabs;
+        std::vector<char> taken((size_t)limit, 0);
+        for (int s = 0; s < n_seq; ++s)
+            for (int i = 0; i < n_pg; ++i) {
+                const int slot = p->page_slots[(size_t)s * n_pg + i];
+                if (slot < 0 || slot >= limit) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: page_slots[%d][%d] = %d outside 0 .. %d", s, i, slot, limit - 1);
+                if (taken[(size_t)slot]) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: slot %d is named twice (every sequence starts at 0: no shared page)", slot);
+                taken[(size_t)slot] = 1;
+            }
+    }
+    PackHost ph;
+    if (!pack_host_build(p->seq_len, trow.data(), kern.data(), n_seq, nh, nkv, &ph) || ph.rows != rows)
+        return set_err(Q3_INVALID_ARG, "q3_attn_prefill_packed_ex: the pack's tables refused the shape");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const size_t cn = (size_t)n_seq * nkv * max_seq * HEAD_DIM, rn = (size_t)max_seq * 64, on = (size_t)rows * p->ld_out;
+    float *qkv, *qw, *kw, *rc, *rs, *kv = nullptr, *qbuf, *out; unsigned char* kvp = nullptr; int* tabs = nullptr;
+    unsigned long long* table = nullptr;
+    if (layout == 1) {
+        for (int s = 0; s < p->n_slabs; ++s) {
+            if (s == 1) HIPC(pool.alloc(&table, (size_t)n_seq * KV_MAX_PAGES));
+            HIPC(slabs.add_slab(pool));
+        }
+        if (!table) HIPC(pool.alloc(&table, (size_t)n_seq * KV_MAX_PAGES));
+    } else HIPC(pool.alloc(&kv, 2 * cn));
+    HIPC(pool.alloc(&qkv, (size_t)rows * ld_qkv)); HIPC(pool.alloc(&qw, (size_t)HEAD_DIM)); HIPC(pool.alloc(&kw, (size_t)HEAD_DIM));
+    HIPC(pool.alloc(&rc, rn)); HIPC(pool.alloc(&rs, rn));
+    HIPC(pool.alloc(&qbuf, (size_t)rows * QD)); HIPC(pool.alloc(&out, on)); HIPC(pool.alloc(&tabs, ph.blob.size()));
+    HIPC(q3_hipMemcpy(qkv, p->qkv, (size_t)rows * ld_qkv * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(qw, p->q_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kw, p->k_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(rc, p->rope_cos, rn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(rs, p->rope_sin, rn * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(tabs, ph.blob.data(), ph.blob.size() * 4, hipMemcpyHostToDevice));
+    auto each_row = [&](auto&& f) {
+        for (int s = 0; s < n_seq; ++s) for (int g = 0; g < nkv; ++g) for (int pp = 0; pp < max_seq; ++pp) for (int v = 0; v < 2; ++v) {
+            const int slot = p->page_slots[(size_t)s * n_pg + pp / KV_PAGE_POS];
+            f(slot, slabs.row_elem(slot, p->layer, v, g, pp), cache_row(v ? p->vcache : p->kcache, s, g, pp));
+        }
+    };
+    if (layout == 1) {
+        slabs.fill_pattern();
+        each_row([&](int slot, size_t elem, float* row) { slabs.put_row(slabs.img, slot, elem, row); });
+        HIPC(slabs.upload());
+        std::vector<unsigned long long> tab((size_t)n_seq * KV_MAX_PAGES);
+        for (int s = 0; s < n_seq; ++s)
+            for (int i = 0; i < KV_MAX_PAGES; ++i) tab[(size_t)s * KV_MAX_PAGES + i] = slabs.page(p->page_slots[(size_t)s * n_pg + (i < n_pg ? i : 0)]);
+        HIPC(q3_hipMemcpy(table, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+        if (p->rot_used)
+            for (int s = 0; s < n_seq; ++s) for (int i = 0; i < n_pg; ++i) for (int g = 0; g < nkv; ++g)
+                p->rot_used[((size_t)s * n_pg + i) * nkv + g] = kv_rot(slabs.page(p->page_slots[(size_t)s * n_pg + i]), g);
+    } else {
+        HIPC(q3_hipMemcpy(kv, p->kcache, cn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kv + cn, p->vcache, cn * 4, hipMemcpyHostToDevice));
+    }
+    HIPC(q3_hipMemcpy(out, p->out, on * 4, hipMemcpyHostToDevice));
+    AttnArgs t{};
+    t.qkv = qkv; t.ld_qkv = ld_qkv; t.q_norm_w = qw; t.k_norm_w = kw; t.eps = p->eps; t.rope_cos = rc; t.rope_sin = rs;
+    t.pos_dev = nullptr; t.pos_static = 0; t.max_seq = max_seq; t.qbuf = qbuf; t.out = out; t.ld_out = p->ld_out;
+    if (layout == 1) { t.kv_pages = table; t.kv_layer_off = (size_t)p->layer * slabs.geo.layer_stride(); t.kv_vdelta = slabs.geo.v_delta(); }
+    else { t.kcache = kv; t.vcache = kv + cn; }
+    t.B = rows; t.nh = nh; t.nkv = nkv; t.n_splits = 1; t.rows_per_seq = rows;
+    const PackTab pt = ph.tab(tabs);
+    const size_t kb_used = (size_t)ph.plane_tiles * KVP_TILE_BYTES, kb = kb_used + 2 * KVP_TILE_BYTES;
+    if (ph.n_plane_items > 0) { HIPC(pool.alloc(&kvp, kb)); HIPC(fill_ff(kvp, kb)); }
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_qknorm_rope_kv_pack(t, pt, 0));
+    if (kvp) { HIPC(launch_kv_planes_pack(t, pt, kvp, 0)); t.kvp = kvp; t.kvp_tiles = ph.plane_tiles; }
+    HIPC(launch_attn_prefill_pack(t, pt, AP_T, 0));
+    HIPC(launch_attn_prefill_pack(t, pt, AP_X3, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    if (p->path) { p->path[0] = ph.per_xcd[0] > 0 ? 1 : 0; p->path[1] = ph.per_xcd[1] > 0 ? 1 : 0; }
+    if (kvp && p->plane_tail) {
+        std::vector<unsigned char> tail(2 * KVP_TILE_BYTES);
+        HIPC(q3_hipMemcpy(tail.data(), kvp + kb_used, tail.size(), hipMemcpyDeviceToHost));
+        long long still = 0;
+        for (unsigned char c : tail) still += c == 0xff;
+        p->plane_tail[0] = still; p->plane_tail[1] = (long long)tail.size();
+    }
+    HIPC(q3_hipMemcpy(p->out, out, on * 4, hipMemcpyDeviceToHost));
+    if (layout == 1) {
+        std::vector<std::vector<uint32_t>> got;
+        HIPC(slabs.download(got));
+        each_row([&](int slot, size_t elem, float* row) { slabs.get_row(got, slot, elem, row); slabs.copy_row(slabs.img, got, slot, elem); });
+        slabs.strays(got, p->stray);
+    } else {
+        HIPC(q3_hipMemcpy(p->kcache, kv, cn * 4, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(p->vcache, kv + cn, cn * 4, hipMemcpyDeviceToHost));
+        if (p->stray) { p->stray[0] = 0; p->stray[1] = -1; }
+    }
+    return Q3_OK;
+}
+
 // ---- the kernels that build the prompt rows, one launch at a time (tests/test_gpu_prompt_rows.py) ----
 // Exactly one launch_* per call. A destination goes up whole, 64 guard elements on both sides, and comes back whole; whatever the
 // kernel would read or write outside its arrays is refused here, before a device is touched.
