@@ -558,7 +558,8 @@ q3_status q3_kv_pages_to_bf16_ex(int device, int n_layers, int nkv, int n_pages,
  * <4 | 8>, 5..11 the k_conv_bf16x3 geometries 96x128 T_M=4 / 4 waves x 32x128 / 4 waves x 32x256 / 64x128 / 64x64 / 128x128 /
  * 96x128 six waves, 12 / 13 k_conv1d_mfma<CO_W = 2 | 1>, 14 k_conv1d, 15 / 16 k_resunit_bf16x3<3 | 6>), then flags 32 PRE, 64 SEG,
  * 128 CIS = 128, 256 NP = 2. phases > 1: the polyphase transposed conv (k = taps, dil = 1). q3_conv_path_name: the code as text
- * (thread-local buffer). q3_resunit_path: launch_resunit's acceptance rule (0 = refused: the caller runs the two convs). */
+ * (thread-local buffer). q3_resunit_path: launch_resunit's acceptance rule (0 = refused: the caller runs the two convs). Both
+ * answer 0 for L above 2^30, q3_conv_path also for a dilation beyond +-2^16. */
 int         q3_conv_path(int cout, int cin, int L, int k, int dil, int phases, int packed, int has_resid, int planes, int aligned16);
 int         q3_resunit_path(int C, int L, int dil, int packed, int ya_is_xa, int planes);
 const char* q3_conv_path_name(int code);
@@ -594,8 +595,8 @@ q3_status q3_test_conv_resident(int device, const q3_conv_ex_args* args, int res
 /* Test API: which geometry launch_lm_gemm (the long-prompt prefill GEMM) picks for a shape — the launcher's own decision function,
  * no GPU needed. norm / w2 / planes != 0: a fused input RMSNorm, a second (SwiGLU "up") matrix, pre-split activation planes with
  * the split-K workspace q3_gemm_ex passes. Returns the geometry (0 = geometry 1 with the split in the kernel, 1 = geometry 1 over
- * planes, 2 = k_lm_gemm2, 3 = k_lm_gemm3) or -1 for arguments the launcher refuses; path (optional) [4] = geometry, k_ranges,
- * k_split, n_split. */
+ * planes, 2 = k_lm_gemm2, 3 = k_lm_gemm3) or -1 for arguments the launcher refuses (and for M, N or K above 2^24); path (optional) [4] =
+ * geometry, k_ranges, k_split, n_split. */
 int q3_gemm_path(int M, int N, int K, int epi, int norm, int w2, int planes, int* path);
 /* Test API: ONE launch_lm_gemm call over host arrays. x [M][ldx]; w / w2 row-major bf16 [N][K] (retiled as the loader does);
  * bias [N], norm_w [K] (the entry runs launch_row_den first) and resid [M][ldr] may be NULL; epi as in q3_linear_ex. geometry -1 =
@@ -624,6 +625,7 @@ int q3_attn_prefill_path(int nh, int nkv, int use_planes, int halves, int* path)
  * [max_seq][64]; kcache / vcache [n_seq][nkv][max_seq][128] in and out; out [n_seq * rps][ld_out] is uploaded whole and copied
  * back whole. kernel -1 = the engine's pick (use_planes != 0: with K/V planes), 0..3 as q3_attn_prefill_path; halves 1 or 2.
  * path (optional) [2] = kernel, halves that ran. A refused launch returns Q3_UNSUPPORTED and leaves the caches and out alone.
+ * max_seq <= 2^20 and base_pos + rps <= max_seq, else Q3_INVALID_ARG.
  * The trailing fields select the cache layout; all zero = the contiguous form above. layout 1 = f32 pages (what prefill_gemm runs
  * on by default): kcache / vcache stay the LOGICAL cache of the selected layer, and the entry builds n_slabs (1, 2) slabs of
  * KvPool's geometry for n_layers (1..4) layers as q3_attn_step_ex does — pattern-filled, the cache scattered into the pages
@@ -1271,7 +1273,10 @@ q3_status q3_spk_finalize(q3_speaker_encoder* e);
 /* uploads every `speaker_encoder.*` tensor of a safetensors file and finalizes; Q3_MISSING_WEIGHT with the
  * reference's hint (lib.rs:1137-1153) when the file has none */
 q3_status q3_spk_load_safetensors(q3_speaker_encoder* e, const char* path);
-/* frames the mel front end yields for n samples: (n + 2*384 - 1024) / 256 + 1 (mel.rs:168-199) */
+/* frames the mel front end yields for n samples: (n + 2*384 - 1024) / 256 + 1 (mel.rs:168-199). 0 for a clip too short for one
+ * frame (n_samples < 256, zero and negative counts included). -1 = no count for n_samples above 2^38 (the count would leave the
+ * result's range long before n + 768 leaves int64_t's): q3_spk_mel, q3_spk_encode and q3_spk_encode_ref answer such a length with
+ * Q3_INVALID_ARG. Host only. */
 int q3_spk_mel_frames(int64_t n_samples);
 /* MelSpectrogram::compute_for_speaker_encoder (mel.rs:135-166): mel_host [mel_dim][T], T = q3_spk_mel_frames(n) */
 q3_status q3_spk_mel(q3_speaker_encoder* e, const float* samples_host, int64_t n, float* mel_host, int64_t cap_floats, int* n_frames);
@@ -1326,7 +1331,8 @@ q3_status q3_mimi_finalize(q3_speech_encoder* e);
 /* Encoder12Hz::from_safetensors (encoder_12hz.rs:45-48): every `encoder.*` tensor of speech_tokenizer/model.safetensors, then
  * finalize; Q3_MISSING_WEIGHT "No encoder keys found …" (encoder_12hz.rs:68-70) when the file has none */
 q3_status q3_mimi_load_safetensors(q3_speech_encoder* e, const char* path);
-/* frames for n samples: ceil over the four strides, then ceil(/2) */
+/* frames for n samples: ceil over the four strides, then ceil(/2). 0 for a null config, n_samples < 1 or a stride outside 1 .. 16
+ * (q3_mimi_create's range); -1 = no count for n_samples above 2^48 or a count beyond INT32_MAX. Host only. */
 int q3_mimi_frames(const q3_mimi_config* cfg, int64_t n_samples);
 /* Encoder12Hz::encode (encoder_12hz.rs:119-144): codes_host [T][n_q] u32 (frame-major, like q3_request.ref_codes);
  * codes_host == NULL: only *n_frames. sample_rate must be 24000 (q3_resample first). taps_host (test hook): NULL or 3 host

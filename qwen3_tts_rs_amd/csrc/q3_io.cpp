@@ -279,13 +279,25 @@ int dtype_size(const std::string& d) {
     return 0;
 }
 
+// element count of an entry's shape (dims are >= 0: st_open); false when the product leaves int64_t
+bool shape_count(const std::vector<int64_t>& shape, int64_t* n) {
+    int64_t p = 1;
+    for (int64_t d : shape) if (__builtin_mul_overflow(p, d, &p)) return false;
+    *n = p;
+    return true;
+}
+// does a count of `es`-byte elements fill the entry's byte range exactly (no product: it could wrap)
+bool fills_range(int64_t n, int es, const StEntry& e) { const uint64_t bytes = e.e - e.b; return bytes % (uint64_t)es == 0 && (uint64_t)n == bytes / (uint64_t)es; }
+// f16 elements of a mapped file, at any address
+inline uint16_t ld_u16(const uint8_t* p) { uint16_t v; memcpy(&v, p, 2); return v; }
+
 // upload entry `e` of file `f` under `name`; *n_expect = the element count the model wants
 q3_status st_upload(q3_model* m, const StFile& f, const char* path, const char* name, const StEntry& e, int64_t n_expect) {
-    int64_t n = 1;
-    for (int64_t d : e.shape) n *= d;
+    int64_t n = 0;
+    if (!shape_count(e.shape, &n)) return q3i_set_err(Q3_IO, "%s: tensor %s: shape overflows an element count", path, name);
     const int es = dtype_size(e.dtype);
     if (!es) return q3i_set_err(Q3_UNSUPPORTED, "%s: tensor %s has unsupported dtype %s", path, name, e.dtype.c_str());
-    if ((uint64_t)n * (uint64_t)es != e.e - e.b)
+    if (!fills_range(n, es, e))
         return q3i_set_err(Q3_IO, "%s: tensor %s: shape does not match its byte range", path, name);
     if (n != n_expect)
         return q3i_set_err(Q3_INVALID_ARG, "%s: tensor %s has %lld elements, expected %lld (shape mismatch with config.json?)", path,
@@ -295,8 +307,7 @@ q3_status st_upload(q3_model* m, const StFile& f, const char* path, const char* 
     if (e.dtype == "BF16") return q3_model_set_tensor(m, name, Q3_DTYPE_BF16, src, n);
     std::vector<float> tmp((size_t)n);
     if (e.dtype == "F16") {
-        const uint16_t* h = (const uint16_t*)src;
-        for (int64_t i = 0; i < n; ++i) tmp[(size_t)i] = f16_to_f32(h[i]);
+        for (int64_t i = 0; i < n; ++i) tmp[(size_t)i] = f16_to_f32(ld_u16(src + 2 * i));
     } else {   // F64
         for (int64_t i = 0; i < n; ++i) { double d; memcpy(&d, src + 8 * i, 8); tmp[(size_t)i] = (float)d; }
     }
@@ -447,11 +458,11 @@ extern "C" q3_status q3_spk_load_safetensors(q3_speaker_encoder* enc, const char
         Q3I_CHECK(q3_spk_tensor_info(enc, i, &name, &n_expect));
         const StEntry* e = f.find(name);
         if (!e) return q3i_set_err(Q3_MISSING_WEIGHT, "Missing weight: %s", name);
-        int64_t n = 1;
-        for (int64_t d : e->shape) n *= d;
+        int64_t n = 0;
+        if (!shape_count(e->shape, &n)) return q3i_set_err(Q3_IO, "%s: tensor %s: shape overflows an element count", path, name);
         const int es = dtype_size(e->dtype);
         if (!es) return q3i_set_err(Q3_UNSUPPORTED, "%s: tensor %s has unsupported dtype %s", path, name, e->dtype.c_str());
-        if ((uint64_t)n * (uint64_t)es != e->e - e->b) return q3i_set_err(Q3_IO, "%s: tensor %s: shape does not match its byte range", path, name);
+        if (!fills_range(n, es, *e)) return q3i_set_err(Q3_IO, "%s: tensor %s: shape does not match its byte range", path, name);
         if (n != n_expect)
             return q3i_set_err(Q3_INVALID_ARG, "%s: tensor %s has %lld elements, expected %lld (speaker_encoder_config mismatch?)", path, name,
                                (long long)n, (long long)n_expect);
@@ -460,8 +471,7 @@ extern "C" q3_status q3_spk_load_safetensors(q3_speaker_encoder* enc, const char
         if (e->dtype == "BF16") { Q3I_CHECK(q3_spk_set_tensor(enc, name, src, Q3_DTYPE_BF16, n)); continue; }
         std::vector<float> tmp((size_t)n);
         if (e->dtype == "F16") {
-            const uint16_t* h = (const uint16_t*)src;
-            for (int64_t j = 0; j < n; ++j) tmp[(size_t)j] = f16_to_f32(h[j]);
+            for (int64_t j = 0; j < n; ++j) tmp[(size_t)j] = f16_to_f32(ld_u16(src + 2 * j));
         } else {
             for (int64_t j = 0; j < n; ++j) { double d; memcpy(&d, src + 8 * j, 8); tmp[(size_t)j] = (float)d; }
         }
@@ -483,19 +493,18 @@ extern "C" q3_status q3_mimi_load_safetensors(q3_speech_encoder* enc, const char
         Q3I_CHECK(q3_mimi_tensor_info(enc, i, &name, &n_expect));
         const StEntry* e = f.find(name);
         if (!e) return q3i_set_err(Q3_MISSING_WEIGHT, "Missing weight: %s", name);
-        int64_t n = 1;
-        for (int64_t d : e->shape) n *= d;
+        int64_t n = 0;
+        if (!shape_count(e->shape, &n)) return q3i_set_err(Q3_IO, "%s: tensor %s: shape overflows an element count", path, name);
         const int es = dtype_size(e->dtype);
         if (!es) return q3i_set_err(Q3_UNSUPPORTED, "%s: tensor %s has unsupported dtype %s", path, name, e->dtype.c_str());
-        if ((uint64_t)n * (uint64_t)es != e->e - e->b) return q3i_set_err(Q3_IO, "%s: tensor %s: shape does not match its byte range", path, name);
+        if (!fills_range(n, es, *e)) return q3i_set_err(Q3_IO, "%s: tensor %s: shape does not match its byte range", path, name);
         if (n != n_expect) return q3i_set_err(Q3_INVALID_ARG, "%s: tensor %s has %lld elements, expected %lld", path, name, (long long)n, (long long)n_expect);
         const uint8_t* src = f.data + e->b;
         if (e->dtype == "F32") { Q3I_CHECK(q3_mimi_set_tensor(enc, name, src, Q3_DTYPE_F32, n)); continue; }
         if (e->dtype == "BF16") { Q3I_CHECK(q3_mimi_set_tensor(enc, name, src, Q3_DTYPE_BF16, n)); continue; }
         std::vector<float> tmp((size_t)n);
         if (e->dtype == "F16") {
-            const uint16_t* h = (const uint16_t*)src;
-            for (int64_t j = 0; j < n; ++j) tmp[(size_t)j] = f16_to_f32(h[j]);
+            for (int64_t j = 0; j < n; ++j) tmp[(size_t)j] = f16_to_f32(ld_u16(src + 2 * j));
         } else {
             for (int64_t j = 0; j < n; ++j) { double d; memcpy(&d, src + 8 * j, 8); tmp[(size_t)j] = (float)d; }
         }

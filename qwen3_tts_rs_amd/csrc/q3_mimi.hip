@@ -451,9 +451,12 @@ extern "C" q3_status q3_mimi_finalize(q3_speech_encoder* e) {
 static int m_ceil_div(int64_t a, int b) { return (int)((a + b - 1) / b); }
 extern "C" int q3_mimi_frames(const q3_mimi_config* c, int64_t n_samples) {
     if (!c || n_samples < 1) return 0;
+    for (int i = 0; i < 4; ++i) if (c->ratios[i] < 1 || c->ratios[i] > 16) return 0;      // (q3_mimi_create's range)
+    if (n_samples > ((int64_t)1 << 48)) return -1;                                       // no count
     int64_t L = n_samples;
     for (int i = 0; i < 4; ++i) L = (L + c->ratios[i] - 1) / c->ratios[i];
-    return (int)((L + 1) / 2);
+    L = (L + 1) / 2;
+    return L > 0x7fffffffLL ? -1 : (int)L;                                               // no count either: it does not fit
 }
 
 static hipError_t m_run_conv(q3_speech_encoder* e, const MConv& cv, const float* x, float* y, int L, int act = 0, const float* resid = nullptr,
@@ -626,6 +629,7 @@ extern "C" q3_status q3_mimi_pack_plan(const q3_mimi_config* cfg, const int64_t*
     for (int i = 0; i < n; ++i) {
         if (n_samples[i] < 1) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_pack_plan: clip %d: %lld samples", i, (long long)n_samples[i]);
         const int T = q3_mimi_frames(cfg, n_samples[i]);
+        if (T < 0) return q3i_set_err(Q3_INVALID_ARG, "q3_mimi_pack_plan: clip %d: %lld samples are more frames than a count holds", i, (long long)n_samples[i]);
         const int64_t slot = ((int64_t)T + 1) * S;
         if (at > 0 && at + slot > max_pass_samples) { ++pass; at = 0; }      // (a clip whose own slot is larger gets a pass to itself)
         clips[i].frames = T; clips[i].pass = pass; clips[i].start = at;

@@ -1061,21 +1061,31 @@ extern "C" q3_status q3_pcm_stage_taps(uint32_t sample_rate, float* taps_host, s
     return Q3_OK;
 }
 
-extern "C" q3_status q3_pcm_stage_bound(uint32_t sample_rate, size_t n_in, size_t* n_out_max) {
+// the resampler's cap for n samples that reach it. n is at most what chain_cap makes of 2^48 + a silence hold (below 2^52: the
+// stretcher and the pitch step at most double a count each); times L <= 320 that stays far inside 63 bits
+static q3_status resampler_bound(uint32_t sample_rate, size_t n, size_t* n_out_max) {
     Rate r;
     Q3C(rate_checked("q3_pcm_stage_bound", sample_rate, &r));
     if (!n_out_max) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound: null argument");
     // the most one push can return: its own samples and, with `last`, the 64 held back: llround(N L / M) - ceil((N - n - 64) L / M)
-    *n_out_max = sample_rate == PS_RATE_IN ? n_in : (size_t)(((long long)(n_in + PS_HALF) * r.L + r.M - 1) / r.M + 1);
+    *n_out_max = sample_rate == PS_RATE_IN ? n : (size_t)(((long long)(n + PS_HALF) * r.L + r.M - 1) / r.M + 1);
     return Q3_OK;
 }
 
+extern "C" q3_status q3_pcm_stage_bound(uint32_t sample_rate, size_t n_in, size_t* n_out_max) {
+    Rate r;
+    Q3C(rate_checked("q3_pcm_stage_bound", sample_rate, &r));
+    if (!n_out_max) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound: null argument");
+    if (n_in > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound: n_in above 2^48");
+    return resampler_bound(sample_rate, n_in, n_out_max);
+}
+
 // The _bound family: the caps of the steps a row with these settings has, in chain order (chain_cap), then the resampler's. hold: what
-// the row's silence step can retain (0: none). Each caller checks its own ranges first; tempo and cents are in range.
+// the row's silence step can retain (0: none). Each caller checks its own ranges first; tempo, cents and n_in (at most 2^48) are in range.
 static q3_status bound_through(uint32_t sample_rate, int tempo, int cents, int with_level, size_t hold, size_t n_in, size_t* n_out_max) {
     PsRow r;                                                       // (the settings alone; its silence step's cap is n_in + hold)
     r.pt.t = tempo; r.pt.te = r.tp.te = pitch_te(tempo, cents); r.lv.on = with_level != 0;
-    return q3_pcm_stage_bound(sample_rate, chain_cap(r, n_in + hold), n_out_max);
+    return resampler_bound(sample_rate, chain_cap(r, n_in + hold), n_out_max);
 }
 
 static q3_status tempo_checked(const char* who, int tempo) {
@@ -1859,7 +1869,7 @@ size_t pcm_stage_count(const q3_pcm_stage* ps, int row, size_t n, int last) {
     if (step_on(r, ST_SIL)) {
         // what comes is known after the pre-pass alone; the cap covers the a-priori bound: the caps of the row's steps, in a row
         size_t b = 0;
-        (void)q3_pcm_stage_bound(r.rs.sr, chain_cap(r, n), &b);
+        (void)resampler_bound(r.rs.sr, chain_cap(r, n), &b);
         return b;
     }
     SegWalk w{};

@@ -511,9 +511,13 @@ extern "C" q3_status q3_spk_tables(q3_speaker_encoder* e, float* win_host, float
     return Q3_OK;
 }
 
+// 0: a clip too short for one frame (n < 256, negative n included); -1: no count — above 2^38 samples (four months of audio)
+// the frames stop fitting the result long before n + 768 stops fitting its own type
 extern "C" int q3_spk_mel_frames(int64_t n) {
+    if (n < 1) return 0;
+    if (n > ((int64_t)1 << 38)) return -1;
     const int64_t padded = n + 2 * 384;
-    return (n < 1 || padded < 1024) ? 0 : (int)((padded - 1024) / 256 + 1);
+    return padded < 1024 ? 0 : (int)((padded - 1024) / 256 + 1);
 }
 
 static q3_status spk_reserve(q3_speaker_encoder* e, size_t floats) {
@@ -619,6 +623,7 @@ static size_t spk_ws_floats(const q3_speaker_encoder* e, int T) {
 static q3_status spk_check_T(const q3_speaker_encoder* e, int T) {
     int maxside = 0;
     for (int i = 0; i < 5; ++i) maxside = std::max(maxside, (e->cfg.dilations[i] * (e->cfg.kernel_sizes[i] - 1) + 1) / 2);
+    if (T < 0) return q3i_set_err(Q3_INVALID_ARG, "reference audio too long: more than 2^38 samples");
     if (T <= maxside) return q3i_set_err(Q3_INVALID_ARG, "reference audio too short: %d mel frames, reflect padding needs more than %d", T, maxside);
     return Q3_OK;
 }
@@ -627,6 +632,7 @@ extern "C" q3_status q3_spk_mel(q3_speaker_encoder* e, const float* samples, int
     if (!e || !samples || n < 1) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_mel: bad argument");
     if (!e->finalized) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_mel: encoder not finalized");
     const int T = q3_spk_mel_frames(n);
+    if (T < 0) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_mel: more than 2^38 samples");
     if (n_frames) *n_frames = T;
     if (!mel_host) return Q3_OK;
     if (T < 1 || cap < (int64_t)e->cfg.mel_dim * T) return q3i_set_err(Q3_INVALID_ARG, "q3_spk_mel: output buffer too small (%d frames)", T);

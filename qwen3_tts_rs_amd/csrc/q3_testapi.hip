@@ -607,10 +607,14 @@ extern "C" q3_status q3_kv_pages_to_bf16_ex(int device, int n_layers, int nkv, i
 }
 
 // ---- the vocoder conv family, one launch at a time (tests/test_gpu_conv_ops.py) ----
+// (L above 2^30 and a dilation beyond +-2^16 are refused here: the decision functions round L up to whole tiles and form
+// (k - 1) * dil in int)
 extern "C" int q3_conv_path(int cout, int cin, int L, int k, int dil, int phases, int packed, int has_resid, int planes, int aligned16) {
+    if (L > (1 << 30) || dil > (1 << 16) || dil < -(1 << 16)) return 0;
     return conv_path_code(conv_pick(cout, cin, L, k, dil, phases, packed != 0, has_resid != 0, planes, aligned16 != 0, phases > 1));
 }
 extern "C" int q3_resunit_path(int C, int L, int dil, int packed, int ya_is_xa, int planes) {
+    if (L > (1 << 30)) return 0;
     return conv_path_code(resunit_pick(C, L, dil, packed != 0, ya_is_xa != 0, planes));
 }
 extern "C" const char* q3_conv_path_name(int code) { return conv_path_name(code); }
@@ -796,7 +800,7 @@ static size_t gemm_ex_ws_bytes(int M, int N, int Kpad, int epi) {
 
 extern "C" int q3_gemm_path(int M, int N, int K, int epi, int norm, int w2, int planes, int* path) {
     if (path) path[0] = path[1] = path[2] = path[3] = 0;
-    if (M < 1 || N < 1 || K < 4) return -1;
+    if (M < 1 || N < 1 || K < 4 || M > (1 << 24) || N > (1 << 24) || K > (1 << 24)) return -1;      // (beyond 2^24 the paddings leave int)
     // nothing is dereferenced by the pick: the pointers only say what the caller has
     static float dummy[4];
     GemmArgs g;
@@ -900,8 +904,8 @@ extern "C" q3_status q3_attn_prefill_ex(int device, const q3_attn_prefill_ex_arg
     if (p->path) p->path[0] = p->path[1] = 0;
     const int n_seq = p->n_seq, rps = p->rps, nh = p->nh, nkv = p->nkv, base = p->base_pos, layout = p->layout, max_seq = p->max_seq;
     if (p->kernel < -1 || p->kernel > AP_X3 || p->halves < 1 || p->halves > 2) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: kernel -1..3, halves 1..2");
-    if (n_seq < 1 || n_seq > 64 || rps < 1 || rps > 8192 || nkv < 1 || nh < nkv || nh > 64 || nh % nkv || max_seq < 1 || base < 0 || base + rps > max_seq)
-        return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: bad shape (the chunk [base_pos, base_pos + rps) must lie inside max_seq)");
+    if (n_seq < 1 || n_seq > 64 || rps < 1 || rps > 8192 || nkv < 1 || nh < nkv || nh > 64 || nh % nkv || max_seq < 1 || max_seq > (1 << 20) || base < 0 || base > max_seq - rps)
+        return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: bad shape (the chunk [base_pos, base_pos + rps) must lie inside max_seq <= 2^20)");
     const int ld_qkv = p->ld_qkv, QD = nh * HEAD_DIM, rows = n_seq * rps;
     if (ld_qkv < (nh + 2 * nkv) * HEAD_DIM || ld_qkv % 4 || p->ld_out < QD || p->ld_out % 4) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: bad pitch");
     if (layout < 0 || layout > 2) return set_err(Q3_INVALID_ARG, "q3_attn_prefill_ex: layout 0..2");

@@ -193,6 +193,13 @@ def test_prefill_paths_are_host_only():
     assert q.gemm_path(4105, 2048, 2048) == (3, 8, 1, 1) and q.gemm_path(509, 2048, 6144) == (3, 8, 8, 1)
     assert q.gemm_path(130, 384, 128) == (2, 1, 1, 1) and q.gemm_path(130, 64, 40) == (1, 1, 1, 1) and q.gemm_path(130, 64, 36, planes=False) == (0, 1, 1, 1)
     assert q.gemm_path(130, 96, 128) is None and q.gemm_path(0, 64, 128) is None
+    # sizes whose tile roundings would leave int are refused at the entry (they used to overflow inside the decision functions)
+    L = _lib.lib
+    assert L.q3_gemm_path(1 << 24, 64, 128, 0, 0, 0, 1, None) >= 0 and L.q3_gemm_path(130, 64, (1 << 24) + 4, 0, 0, 0, 1, None) == -1
+    assert L.q3_gemm_path(130, 64, 2147483644, 0, 0, 0, 1, None) == -1 and L.q3_gemm_path(2147483647, 64, 128, 0, 0, 0, 1, None) == -1
+    assert L.q3_conv_path(64, 64, 1 << 30, 7, 1, 1, 1, 0, 3, 1) != 0 and L.q3_conv_path(64, 64, (1 << 30) + 1, 7, 1, 1, 1, 0, 3, 1) == 0
+    assert L.q3_conv_path(64, 64, 2147483647, 7, 1, 1, 1, 0, 3, 1) == 0 and L.q3_conv_path(64, 64, 640, 7, -2147483648, 1, 1, 0, 3, 1) == 0
+    assert L.q3_resunit_path(96, 1 << 30, 9, 1, 0, 3) != 0 and L.q3_resunit_path(96, 2147483647, 9, 1, 0, 3) == 0
     assert q.attn_prefill_path(16, 8, True, 2) == (3, 2) and q.attn_prefill_path(16, 8, False) == (2, 1) and q.attn_prefill_path(16, 2, False) is None
     assert ctypes.sizeof(_lib.CGemmEx) == 14 * 4 + 8 * 8 and ctypes.sizeof(_lib.CAttnPrefillEx) == 16 * 4 + 12 * 8 and \
         ctypes.sizeof(_lib.CPromptRowsEx) == 10 * 4 + 14 * 8

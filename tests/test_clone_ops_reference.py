@@ -285,3 +285,13 @@ def test_entry_points_refuse_bad_shapes_before_launching():
     enc.close()
     st = _lib.lib.q3_spk_tables(None, None, None)
     assert st == INVALID and len(_lib.lib.q3_last_error()) > 0
+
+
+def test_mel_frames_out_of_range():
+    """q3_spk_mel_frames: 0 for a clip too short for a frame (negative counts included), the closed form up to 2^38 samples, -1 (no
+    count) above — it used to add 768 to any n_samples, a signed overflow near INT64_MAX, and to truncate the count long before."""
+    f = _lib.lib.q3_spk_mel_frames
+    assert [f(n) for n in (-(1 << 63), -1, 0, 1, 255)] == [0] * 5
+    assert [f(n) for n in (256, 511, 512, 24000 * 120)] == [1, 1, 2, (24000 * 120 + 768 - 1024) // 256 + 1]
+    assert f(1 << 38) == ((1 << 38) + 768 - 1024) // 256 + 1 == (1 << 30)
+    assert [f(n) for n in ((1 << 38) + 1, 1 << 40, (1 << 63) - 768, (1 << 63) - 6, (1 << 63) - 1)] == [-1] * 5

@@ -113,3 +113,22 @@ def test_entry_points_refuse_before_the_device():
     assert L.q3_spk_encode_refs(spk._h, nulls, 1, None, None) == 1                             # nor is the output
     assert all(v == 0 for v in nf) and all(v == 0.0 for v in out)                              # a refusal writes nothing
     mimi.close(); spk.close()
+
+
+def test_frames_and_plan_out_of_range():
+    """q3_mimi_frames: 0 for a stride outside 1 .. 16 (a stride of 0 used to divide by zero), -1 (no count) for n_samples above 2^48
+    or a count beyond INT32_MAX (it used to add the stride to any n_samples and to truncate); q3_mimi_pack_plan refuses such a clip."""
+    L = _lib.lib
+    cfg = CONFIGS["production"]()
+    c = cfg.to_c()
+    assert L.q3_mimi_frames(ctypes.byref(c), 1 << 40) == ((1 << 40) + 1919) // 1920 and L.q3_mimi_frames(ctypes.byref(c), 1 << 48) == -1
+    assert [L.q3_mimi_frames(ctypes.byref(c), n) for n in ((1 << 48) + 1, (1 << 63) - 1)] == [-1, -1]
+    assert [L.q3_mimi_frames(ctypes.byref(c), n) for n in (0, -1, -(1 << 63))] == [0, 0, 0]
+    for bad in (0, -4, 17):
+        b = cfg.to_c(); b.ratios[2] = bad
+        assert L.q3_mimi_frames(ctypes.byref(b), 24000) == 0
+    one = cfg.to_c(); one.ratios[0] = one.ratios[1] = one.ratios[2] = one.ratios[3] = 1
+    assert L.q3_mimi_frames(ctypes.byref(one), (1 << 32) - 2) == (1 << 31) - 1 and L.q3_mimi_frames(ctypes.byref(one), (1 << 32) - 1) == -1
+    ns = (ctypes.c_int64 * 2)(24000, 1 << 48)
+    clips = (_lib.CMimiPackClip * 2)()
+    assert L.q3_mimi_pack_plan(ctypes.byref(c), ns, 2, 24000 * 120, clips, None, None, None) == 1 and b"clip 1" in L.q3_last_error()

@@ -267,3 +267,35 @@ def test_resample_accuracy(sr_in, sr_out):
     ref = 0.5 * np.sin(2 * np.pi * 440.0 * to) + 0.3 * np.sin(2 * np.pi * 3000.0 * to + 0.7)
     m = slice(200, len(r) - 200)
     assert np.abs(r.samples[m] - ref[m]).max() < 2e-3
+
+
+def test_safetensors_shape_product_is_checked(tmp_path):
+    """An entry whose shape product leaves int64 is refused with a message before anything is compared (it used to be a signed
+    overflow), one that wraps to the expected count included; an f16 entry at an odd address is read byte-wise. Through
+    q3_model_load_safetensors into a manifest-only handle, which runs every host check of an upload and then answers
+    Q3_UNSUPPORTED for the tensor itself."""
+    from common import manifest_handle
+    cfg = q.tiny()
+    h = manifest_handle(cfg)
+    L = _lib.lib
+    n = cfg.hidden                                           # talker.model.norm.weight: 64 = 2^6 elements
+    path = tmp_path / "m.safetensors"
+
+    def load(shape, dtype="F32", begin=0, es=4):
+        hdr = json.dumps({"talker.model.norm.weight": {"dtype": dtype, "shape": shape, "data_offsets": [begin, begin + n * es]}}).encode()
+        path.write_bytes(struct.pack("<Q", len(hdr)) + hdr + bytes(begin + n * es))
+        loaded = ctypes.c_int(-1)
+        st = L.q3_model_load_safetensors(h, str(path).encode(), ctypes.byref(loaded))
+        return st, L.q3_last_error().decode()
+    st, msg = load([n])
+    assert st == 7 and "manifest-only" in msg                # well formed: every check passed, the handle holds no weights
+    for shape in ([1 << 32, 1 << 32], [(1 << 63) - 1, 3], [64, (1 << 58) + 1], [3037000500, 3037000500], [n, (1 << 63) - 1]):
+        st, msg = load(shape)                                # 64 * (2^58 + 1) = 2^64 + 64: wraps to the expected count
+        assert st == 2 and "shape overflows" in msg, (shape, st, msg)
+    st, msg = load([n + 1])
+    assert st == 2 and "byte range" in msg
+    st, msg = load([n, 0])                                   # no overflow, no elements: the range does not match
+    assert st == 2 and "byte range" in msg
+    st, msg = load([n], "F16", begin=1, es=2)                # a well-formed f16 range at an odd address
+    assert st == 7 and "manifest-only" in msg
+    L.q3_model_free(h)

@@ -314,3 +314,28 @@ def test_resample_gpu_one_shot(pcm, oneshot):
     out = api.resample_gpu(api.AudioBuffer(pcm), 16000, pcm16=True)
     assert out.sample_rate == 16000 and out.samples.dtype == np.int16
     np.testing.assert_array_equal(out.samples, oneshot(16000, True))
+
+
+def test_bound_refuses_above_2_48():
+    """q3_pcm_stage_bound follows its siblings' rule: n_in above 2^48 is Q3_INVALID_ARG with a message (it used to multiply on,
+    into a signed overflow at 2^62); at and below 2^48 the value is the closed form, unchanged, and the siblings still answer
+    for 2^48 although their chains hand the resampler more than that."""
+    L = _lib.lib
+    n = ctypes.c_size_t()
+    for sr, (l, m) in {44100: (147, 80), 8000: (1, 3), 96000: (4, 1), 22050: (147, 160)}.items():
+        for n_in in (0, 1, 1920, (1 << 48) - 1, 1 << 48):
+            assert L.q3_pcm_stage_bound(sr, n_in, ctypes.byref(n)) == 0
+            assert n.value == ((n_in + 64) * l + m - 1) // m + 1, (sr, n_in)
+    assert L.q3_pcm_stage_bound(24000, 1 << 48, ctypes.byref(n)) == 0 and n.value == 1 << 48
+    for sr in (24000, 44100):
+        for n_in in ((1 << 48) + 1, 1 << 62, (1 << 63) - 1, (1 << 64) - 1):
+            n.value = 7
+            assert L.q3_pcm_stage_bound(sr, n_in, ctypes.byref(n)) == 1 and b"above 2^48" in L.q3_last_error(), (sr, n_in)
+            assert n.value == 7
+    for f in (lambda: L.q3_pcm_stage_bound_tempo(44100, 500, 1 << 48, ctypes.byref(n)),
+              lambda: L.q3_pcm_stage_bound_level(44100, 500, 1 << 48, ctypes.byref(n)),
+              lambda: L.q3_pcm_stage_bound_pitch(44100, 1000, 1200, 1, 1 << 48, ctypes.byref(n))):
+        n.value = 0
+        assert f() == 0 and n.value > (1 << 48), L.q3_last_error()
+    assert L.q3_pcm_stage_bound_tempo(44100, 500, 1 << 48, ctypes.byref(n)) == 0 and n.value > 2 * (1 << 48)
+    assert L.q3_pcm_stage_bound_tempo(44100, 500, (1 << 48) + 1, ctypes.byref(n)) == 1

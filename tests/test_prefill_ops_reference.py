@@ -246,3 +246,17 @@ def test_paged_entry_refuses_before_a_device_is_touched():
     # the contiguous form is untouched by all of this
     a = _lib.CAttnPrefillEx()
     assert _lib.lib.q3_attn_prefill_ex(0, a) == I
+
+
+def test_entry_refuses_a_chunk_beyond_int_range():
+    """base_pos + rps is checked without forming the sum (it used to overflow int for a base_pos near INT32_MAX), and max_seq stops at
+    2^20 (the page count used to round INT32_MAX up); both are Q3_INVALID_ARG before any array is read"""
+    from qwen3_tts_rs_amd import _lib
+    buf = np.zeros(16, np.float32)
+    a = _lib.CAttnPrefillEx()
+    for f in ("qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcache", "vcache", "out"):
+        setattr(a, f, buf.ctypes.data)
+    a.n_seq, a.rps, a.nh, a.nkv, a.ld_qkv, a.ld_out, a.kernel, a.halves = 1, 4, 2, 1, 512, 256, -1, 1
+    for base, max_seq in ((2**31 - 1, 256), (2**31 - 4, 256), (253, 256), (0, 2**31 - 1), (0, 2**20 + 1)):
+        a.base_pos, a.max_seq = base, max_seq
+        assert _lib.lib.q3_attn_prefill_ex(0, a) == 1 and b"bad shape" in _lib.lib.q3_last_error(), (base, max_seq)
