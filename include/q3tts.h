@@ -250,7 +250,10 @@ q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_host, const s
 q3_status q3_session_next_chunk(q3_session* s, float* pcm_host, size_t cap, size_t* n_samples, int* done);
 /* The same for sequence b of a session with several sequences (one StreamingSession per row, lib.rs:1484-1541): the rows
  * advance in lockstep, so the first row asked generates the chunk's frames for all of them and the others only run their
- * vocoder. An error leaves the row's position untouched: the call can be repeated (lib.rs:1775-1781). */
+ * vocoder. An error leaves the row's position untouched: the call can be repeated (lib.rs:1775-1781).
+ * A row has ONE streaming position (frames already handed out), and every streaming entry follows it: q3_session_next_chunk,
+ * q3_session_next_chunk_row, q3_session_next_chunks and q3_session_next_chunks_out may be mixed on a row, each continuing
+ * where the last one stopped. q3_session_replace and q3_session_resume_row set the row's position back to frame 0. */
 q3_status q3_session_next_chunk_row(q3_session* s, int b, float* pcm_host, size_t cap, size_t* n_samples, int* done);
 /* q3_session_next_chunk_row for every row in one call: generates until every live row has a chunk (or ends, or is held by
  * open text), then decodes all rows' chunks together. pcm_host / cap / n_samples / done are arrays of one entry per row.

@@ -265,6 +265,15 @@ class Session:
             self._row_limit[b] = max(self._row_limit[b], parked._row_limit)
         self._ref_frames[b] = parked._ref_frames
 
+    def next_chunk(self) -> Tuple[Optional[AudioBuffer], bool]:
+        """The next chunk of a one-row session, with read-ahead (q3_session_next_chunk): (chunk or None, done). A row has one
+        streaming position, so this may be mixed with `next_chunk_row` / `next_chunks` on the same row."""
+        chunk = self.options.chunk_frames if self.options.chunk_frames > 0 else 10      # the engine's default
+        buf = np.zeros(chunk * self.model.config.samples_per_frame, dtype=np.float32)
+        n = ctypes.c_size_t(); d = ctypes.c_int()
+        check(lib.q3_session_next_chunk(self._h, buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(n), ctypes.byref(d)))
+        return (AudioBuffer(buf[:n.value].copy()) if n.value else None), bool(d.value)
+
     def next_chunk_row(self, b: int) -> Tuple[Optional[AudioBuffer], bool]:
         """StreamingSession::next_chunk for row b of a multi-sequence session: (chunk or None, done)."""
         spf = self.model.config.samples_per_frame
@@ -796,20 +805,12 @@ class StreamingSession:
         if continuous:
             check(lib.q3_session_set_stream_mode(self._s._h, 1))
         self._done = False
-        self._spf = model.config.samples_per_frame
-        self._chunk = options.chunk_frames
 
     def next_chunk(self) -> Optional[AudioBuffer]:
         if self._done:
             return None
-        buf = np.zeros(self._chunk * self._spf, dtype=np.float32)
-        n = ctypes.c_size_t(); d = ctypes.c_int()
-        check(lib.q3_session_next_chunk(self._s._h, buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(n), ctypes.byref(d)))
-        if d.value:
-            self._done = True
-        if n.value == 0:
-            return None
-        return AudioBuffer(buf[:n.value].copy())
+        chunk, self._done = self._s.next_chunk()
+        return chunk
 
     def frames_generated(self) -> int:
         return self._s.frames(0)[0]
@@ -842,8 +843,6 @@ class TextStreamingSession:
         self._s.open_text(0)
         self._done = False
         self._finished = False
-        self._spf = model.config.samples_per_frame
-        self._chunk = options.chunk_frames if options.chunk_frames > 0 else 10
 
     def push(self, ids: Sequence[int]):
         self._s.append_text(0, ids, last=False)
@@ -856,14 +855,8 @@ class TextStreamingSession:
     def next_chunk(self) -> Optional[AudioBuffer]:
         if self._done:
             return None
-        buf = np.zeros(self._chunk * self._spf, dtype=np.float32)
-        n = ctypes.c_size_t(); d = ctypes.c_int()
-        check(lib.q3_session_next_chunk(self._s._h, buf.ctypes.data_as(ctypes.c_void_p), buf.size, ctypes.byref(n), ctypes.byref(d)))
-        if d.value:
-            self._done = True
-        if n.value == 0:
-            return None
-        return AudioBuffer(buf[:n.value].copy())
+        chunk, self._done = self._s.next_chunk()
+        return chunk
 
     def text_state(self) -> dict:
         return self._s.text_state(0)

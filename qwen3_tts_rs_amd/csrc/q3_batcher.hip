@@ -78,7 +78,6 @@ q3_status transplant_row(q3_session* s, int b, q3_session* side, int j, int limi
     if (sq.opened) { nq.committed = 0; nq.max_length_req = limit; }
     s->seq[(size_t)b] = nq;
     s->seq[(size_t)b].req = s->seq[(size_t)b].request();      // the request's arrays live in the row's own vectors (the caller's pointers need not outlive the call)
-    if (b == 0) s->stream_pos = 0;       // q3_session_next_chunk (the row-0 streaming call) starts over with the new utterance too
     if (s->cstream) codec_stream_reset(s->cstream, b);      // q3_session_next_chunks: the row's vocoder state belonged to the old utterance
     if (s->ostage) pcm_stage_reset(s->ostage, b);           // q3_session_next_chunks_out: so did its output row's
     s->codes_host_valid = false;

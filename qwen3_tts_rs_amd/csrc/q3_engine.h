@@ -500,8 +500,7 @@ struct q3_session {
     std::vector<CodecWS> par_ws; std::vector<hipStream_t> par_streams;     // q3_session_run: utterances vocoded side by side
     CodecWS seg_ws;                                          // q3_session_run: segments vocoded beside the frame loop
     std::vector<uint32_t> codes_host; bool codes_host_valid = false;
-    int stream_pos = 0;    // streaming: frames already decoded
-    int stream_mode = 0;   // 0 = context-free chunk decode (reference behaviour), 1 = continuous (left context re-run: seamless)
+    int stream_mode = 0;  // 0 = context-free chunk decode (reference behaviour), 1 = continuous (left context re-run: seamless)
     bool profile = false; ProfAcc prof_linear;
     bool legacy_attn = getenv("Q3_LEGACY_ATTN") != nullptr;   // A/B aid: three-kernel attention path
     bool proj_tables = getenv("Q3_NO_PROJ_TABLES") == nullptr;   // A/B aid: set to project the gathered embedding on every pass

@@ -133,7 +133,7 @@ extern "C" q3_status q3_session_park_row(q3_session* s, int b, q3_parked** out) 
     if (s->debug || s->profile) return set_err(Q3_UNSUPPORTED, "q3_session_park_row: not on debug / profiling sessions");
     if (s->kv_bf16 != s->kv_in_bf16) return set_err(Q3_UNSUPPORTED, "q3_session_park_row: the session's K/V conversion has not happened yet");
     if (s->seq[(size_t)b].idle) return set_err(Q3_INVALID_ARG, "q3_session_park_row: row %d is idle", b);
-    if (s->seq[(size_t)b].stream_pos > 0 || (b == 0 && s->stream_pos > 0))
+    if (s->seq[(size_t)b].stream_pos > 0)
         return set_err(Q3_UNSUPPORTED, "q3_session_park_row: row %d has delivered chunks (q3_session_next_chunk*): its stream position does not travel", b);
     q3_model* m = s->m; const q3_config& c = m->cfg;
     HIPC(hipSetDevice(m->device));
@@ -241,7 +241,6 @@ extern "C" q3_status q3_session_resume_row(q3_session* s, int b, q3_parked* p) {
     nq.start_run = s->frames_run - p->committed; nq.committed = p->committed;
     nq.idle = false; nq.stream_pos = 0;
     s->seq[(size_t)b] = nq; s->seq[(size_t)b].req = s->seq[(size_t)b].request();
-    if (b == 0) s->stream_pos = 0;
     if (s->cstream) codec_stream_reset(s->cstream, b);
     if (s->ostage) pcm_stage_reset(s->ostage, b);
     s->codes_host_valid = false;

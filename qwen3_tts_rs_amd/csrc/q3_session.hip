@@ -1890,8 +1890,72 @@ extern "C" q3_status q3_session_generate(q3_session* s, int n_frames, int use_gr
     return Q3_OK;
 }
 
-static q3_status decode_range_on(q3_session* s, int b, int f0, int f1, hipStream_t st, float* pcm_host, size_t cap, size_t* n_samples);
-static q3_status chunk_decode_row(q3_session* s, int b, int avail, float* pcm_host, size_t cap, size_t* n_samples);
+// ---- streaming: one fill, one cut, one vocoder enqueue under the four chunk entries ----
+// A row has ONE streaming position (SeqInfo::stream_pos: frames already handed out) and every entry follows it, so the entries
+// may be mixed on a row: q3_session_next_chunk (one row, with read-ahead), q3_session_next_chunk_row, q3_session_next_chunks[_out].
+static int chunk_frames_of(const q3_session* s) { return s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10; }
+// Fill: generate until row b has a chunk buffered behind its position or ends (lib.rs:1663-1748). An opened row waits for its
+// own text: it stops generating when it is held. (One row: session_remaining is max(row_capacity, 0), the same test.)
+static q3_status chunk_fill(q3_session* s, int b) {
+    const SeqInfo& q = s->seq[(size_t)b];
+    const int chunk = chunk_frames_of(s);
+    while (!q.done && q.n_frames - q.stream_pos < chunk && (q.opened ? row_capacity(s, q) : session_remaining(s)) > 0) {
+        Q3C(q3_session_generate(s, chunk - (q.n_frames - q.stream_pos), 1));
+        Q3C(refresh_codes(s));
+    }
+    return Q3_OK;
+}
+// Cut: what row b gets now. avail: frames (a chunk until the row ends, the rest then); held: an opened row whose text does not
+// reach a whole chunk yet gets nothing now (chunk boundaries stay those of the closed run); ends: what `done` will report.
+struct ChunkCut { int avail; bool held, ends; };
+static ChunkCut chunk_cut(const q3_session* s, int b) {
+    const SeqInfo& q = s->seq[(size_t)b];
+    const int chunk = chunk_frames_of(s);
+    int a = std::min(q.n_frames - q.stream_pos, chunk);
+    const bool held = q.opened && !q.done && a < chunk;
+    if (a < 0 || held) a = 0;
+    return {a, held, !held && (a <= 0 || (q.done && q.stream_pos + a >= q.n_frames))};
+}
+// Vocode: samples on the device (the session's codec workspace) once the stream they were enqueued on has drained
+struct ChunkPcm { const float* dev; size_t n; };
+// context-free: frames [f0, f0 + T) of row b decoded as an utterance of their own (the reference's per-chunk decode, lib.rs:1755-1758)
+static q3_status range_vocode_enqueue(q3_session* s, int b, int f0, int T, hipStream_t st, ChunkPcm* pcm) {
+    Q3C(codec_reserve(s->m, s->cws, T));
+    HIPC(hipMemcpyAsync(s->cws.frames, s->codes + ((size_t)b * s->max_frames + f0) * 16, (size_t)T * 16 * 4, hipMemcpyDeviceToDevice, st));
+    Q3C(codec_decode_dev(s->m, s->cws, T, st, nullptr));
+    *pcm = {s->cws.pcm, (size_t)T * samples_per_frame(s->m->cfg)};
+    return Q3_OK;
+}
+// frames [stream_pos, stream_pos + avail) of row b in the session's stream mode, enqueued on st; nothing is waited for
+static q3_status chunk_vocode_enqueue(q3_session* s, int b, int avail, hipStream_t st, ChunkPcm* pcm) {
+    const SeqInfo& q = s->seq[(size_t)b];
+    if (s->stream_mode != 1 || q.icl) return range_vocode_enqueue(s, b, q.stream_pos, avail, st, pcm);
+    // continuous mode (q3_session_set_stream_mode): the front runs over frames [0, end), the convolutional stack over
+    // [pos - CTX, end); the chunk's samples are identical to the same frames of a whole-utterance decode (codec_decode_dev)
+    const int spf = samples_per_frame(s->m->cfg);
+    const int a0 = q.stream_pos, e = q.stream_pos + avail, c0 = a0 > CODEC_CTX_FRAMES ? a0 - CODEC_CTX_FRAMES : 0;
+    Q3C(codec_reserve(s->m, s->cws, chunk_frames_of(s) + CODEC_CTX_FRAMES, s->max_frames));
+    HIPC(hipMemcpyAsync(s->cws.frames, s->codes + (size_t)b * s->max_frames * 16, (size_t)e * 16 * 4, hipMemcpyDeviceToDevice, st));
+    Q3C(codec_decode_dev(s->m, s->cws, e, st, nullptr, c0));
+    *pcm = {s->cws.pcm + (size_t)(a0 - c0) * spf, (size_t)avail * spf};
+    return Q3_OK;
+}
+// the caller's half, after its wait: the count, and the samples where a buffer was given
+static q3_status chunk_copy_out(const ChunkPcm& pcm, float* pcm_host, size_t cap, size_t* n_samples) {
+    if (n_samples) *n_samples = pcm.n;
+    if (pcm_host) {
+        if (cap < pcm.n) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
+        HIPC(q3_hipMemcpy(pcm_host, pcm.dev, pcm.n * 4, hipMemcpyDeviceToHost));
+    }
+    return Q3_OK;
+}
+// the vocoder pass of one row's chunk on the session's stream
+static q3_status chunk_decode_row(q3_session* s, int b, int avail, float* pcm_host, size_t cap, size_t* n_samples) {
+    ChunkPcm pcm;
+    Q3C(chunk_vocode_enqueue(s, b, avail, s->stream, &pcm));
+    HIPC(sync_frames(s));
+    return chunk_copy_out(pcm, pcm_host, cap, n_samples);
+}
 
 // Streaming with several sequences in one session: the next chunk of row b (StreamingSession::next_chunk, lib.rs:1650-1759,
 // one per row). Rows advance in lockstep, so asking row after row costs the frames once: the first call generates them for
@@ -1901,43 +1965,14 @@ extern "C" q3_status q3_session_next_chunk_row(q3_session* s, int b, float* pcm_
     HIPC(hipSetDevice(s->m->device));
     if (!s->prefilled) Q3C(q3_session_prefill(s));
     Q3C(refresh_codes(s));
-    SeqInfo& q = s->seq[b];
-    const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
-    // (an opened row waits for its own text: it stops generating when it is held)
-    while (!q.done && q.n_frames - q.stream_pos < chunk && (q.opened ? row_capacity(s, q) : session_remaining(s)) > 0) {
-        Q3C(q3_session_generate(s, chunk - (q.n_frames - q.stream_pos), 1));
-        Q3C(refresh_codes(s));
+    Q3C(chunk_fill(s, b));
+    const ChunkCut cut = chunk_cut(s, b);
+    if (n_samples) *n_samples = 0;
+    if (cut.avail > 0) {
+        Q3C(chunk_decode_row(s, b, cut.avail, pcm_host, cap, n_samples));
+        s->seq[(size_t)b].stream_pos += cut.avail;
     }
-    int avail = q.n_frames - q.stream_pos;
-    if (avail > chunk) avail = chunk;
-    // an opened row whose text does not reach a whole chunk yet: nothing now (chunk boundaries stay those of the closed run)
-    if (q.opened && !q.done && avail < chunk) { if (n_samples) *n_samples = 0; if (done) *done = 0; return Q3_OK; }
-    if (avail <= 0) { if (n_samples) *n_samples = 0; if (done) *done = 1; return Q3_OK; }
-    Q3C(chunk_decode_row(s, b, avail, pcm_host, cap, n_samples));
-    q.stream_pos += avail;
-    if (done) *done = (q.done && q.stream_pos >= q.n_frames) ? 1 : 0;
-    return Q3_OK;
-}
-// the vocoder pass of one row's chunk: frames [stream_pos, stream_pos + avail) of row b in the session's stream mode
-static q3_status chunk_decode_row(q3_session* s, int b, int avail, float* pcm_host, size_t cap, size_t* n_samples) {
-    SeqInfo& q = s->seq[b];
-    const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
-    const int spf = samples_per_frame(s->m->cfg);
-    if (s->stream_mode == 1 && !q.icl) {
-        // continuous mode (q3_session_set_stream_mode): left context re-run, sample-exact with the whole-utterance decode
-        const int a0 = q.stream_pos, e = q.stream_pos + avail, c0 = a0 > CODEC_CTX_FRAMES ? a0 - CODEC_CTX_FRAMES : 0;
-        Q3C(codec_reserve(s->m, s->cws, chunk + CODEC_CTX_FRAMES, s->max_frames));
-        HIPC(hipMemcpyAsync(s->cws.frames, s->codes + (size_t)b * s->max_frames * 16, (size_t)e * 16 * 4, hipMemcpyDeviceToDevice, s->stream));
-        Q3C(codec_decode_dev(s->m, s->cws, e, s->stream, nullptr, c0));
-        HIPC(sync_frames(s));
-        if (n_samples) *n_samples = (size_t)avail * spf;
-        if (pcm_host) {
-            if (cap < (size_t)avail * spf) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
-            HIPC(q3_hipMemcpy(pcm_host, s->cws.pcm + (size_t)(a0 - c0) * spf, (size_t)avail * spf * 4, hipMemcpyDeviceToHost));
-        }
-    } else {
-        Q3C(decode_range_on(s, b, q.stream_pos, q.stream_pos + avail, s->stream, pcm_host, cap, n_samples));
-    }
+    if (done) *done = cut.ends ? 1 : 0;
     return Q3_OK;
 }
 
@@ -1960,7 +1995,7 @@ extern "C" q3_status q3_session_set_output(q3_session* s, uint32_t sample_rate, 
     std::vector<OutSettings> next = s->out;
     for (OutSettings& o : next) Q3C(out_set_output("q3_session_set_output", o, sample_rate, format));
     if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_set_output: the model has no device");
-    bool started = s->out_started || s->stream_pos > 0;
+    bool started = s->out_started;
     for (const SeqInfo& q : s->seq) started = started || q.stream_pos > 0;
     if (started) return set_err(Q3_INVALID_ARG, "q3_session_set_output: the session has streamed its first chunk: the output is set before it");
     s->out = next;
@@ -1977,7 +2012,7 @@ static q3_status session_set_rows(q3_session* s, int b, const char* who, const c
     for (OutSettings& o : next) Q3C(edit(who, o));
     if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "%s: the model has no device", who);
     for (int r = b0; r < b1; ++r)
-        if ((r == 0 && s->stream_pos > 0) || s->seq[(size_t)r].stream_pos > 0)
+        if (s->seq[(size_t)r].stream_pos > 0)
             return set_err(Q3_INVALID_ARG, "%s: row %d has streamed its first chunk: the %s is set before it, or after q3_session_replace", who, r, what);
     for (int r = b0; r < b1; ++r) {
         if (s->ostage) Q3C(pcm_stage_apply(s->ostage, r, who, next[(size_t)(r - b0)]));
@@ -2023,8 +2058,7 @@ extern "C" q3_status q3_session_next_chunks_out(q3_session* s, void* const* out_
     if (!n_samples || !done || !out_host || !cap_samples) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: null argument");
     if (s->m->device < 0) return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: the model has no device");
     if (!s->ostage) {
-        const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
-        Q3C(q3_pcm_stage_create(s->m->device, s->B, (size_t)chunk * samples_per_frame(s->m->cfg), &s->ostage));
+        Q3C(q3_pcm_stage_create(s->m->device, s->B, (size_t)chunk_frames_of(s) * samples_per_frame(s->m->cfg), &s->ostage));
         for (int b = 0; b < s->B; ++b) Q3C(pcm_stage_apply(s->ostage, b, "q3_session_next_chunks_out", s->out[(size_t)b]));
     }
     s->out_started = true;
@@ -2034,79 +2068,56 @@ static q3_status next_chunks(q3_session* s, float* const* pcm_host, const size_t
     HIPC(hipSetDevice(s->m->device));
     if (!s->prefilled) Q3C(q3_session_prefill(s));
     Q3C(refresh_codes(s));
-    const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
     const int spf = samples_per_frame(s->m->cfg);
-    for (int b = 0; b < s->B; ++b) {
-        SeqInfo& q = s->seq[b];
-        while (!q.done && q.n_frames - q.stream_pos < chunk && (q.opened ? row_capacity(s, q) : session_remaining(s)) > 0) {
-            Q3C(q3_session_generate(s, chunk - (q.n_frames - q.stream_pos), 1));
-            Q3C(refresh_codes(s));
-        }
-    }
+    for (int b = 0; b < s->B; ++b) Q3C(chunk_fill(s, b));
     // what every row gets; refused as a whole before any row moves
-    std::vector<int> avail((size_t)s->B, 0);
-    std::vector<char> held((size_t)s->B, 0), ends((size_t)s->B, 0);
+    std::vector<ChunkCut> cuts;
     for (int b = 0; b < s->B; ++b) {
-        const SeqInfo& q = s->seq[b];
-        int a = std::min(q.n_frames - q.stream_pos, chunk);
-        held[(size_t)b] = q.opened && !q.done && a < chunk;          // an opened row whose text does not reach a whole chunk yet: nothing now
-        if (a < 0 || held[(size_t)b]) a = 0;
-        avail[(size_t)b] = a;
-        ends[(size_t)b] = held[(size_t)b] ? 0 : (a <= 0 || (q.done && q.stream_pos + a >= q.n_frames)) ? 1 : 0;      // what done[b] will say
+        const ChunkCut c = chunk_cut(s, b);
+        cuts.push_back(c);
         if (out) {
-            const size_t cnt = pcm_stage_count(s->ostage, b, (size_t)a * spf, ends[(size_t)b]);
+            const size_t cnt = pcm_stage_count(s->ostage, b, (size_t)c.avail * spf, c.ends);
             if (cnt > 0 && (!out_host[b] || cap[b] < cnt))
                 return set_err(Q3_INVALID_ARG, "q3_session_next_chunks_out: output buffer of row %d too small (%zu samples needed)", b, cnt);
-        } else if (a > 0 && pcm_host && pcm_host[b] && (!cap || cap[b] < (size_t)a * spf))
+        } else if (c.avail > 0 && pcm_host && pcm_host[b] && (!cap || cap[b] < (size_t)c.avail * spf))
             return set_err(Q3_INVALID_ARG, "q3_session_next_chunks: pcm buffer of row %d too small", b);
     }
     std::vector<CsPush> pushes;
     std::vector<float> tmp;
     for (int b = 0; b < s->B; ++b) {
-        SeqInfo& q = s->seq[b];
-        const int a = avail[(size_t)b];
+        const SeqInfo& q = s->seq[b];
+        const int a = cuts[(size_t)b].avail, last = cuts[(size_t)b].ends ? 1 : 0;
         n_samples[b] = out ? 0 : (size_t)a * spf;
-        if (out) {
-            const int last = ends[(size_t)b];
-            if (a <= 0 && !last) continue;
-            if (s->stream_mode == 1 && !q.icl) {
-                if (!s->cstream) Q3C(codec_stream_create(s->m, s->B, s->max_frames, s->stream, &s->cstream));
-                int n = 0, skip = 0, sp = 0;
-                if (a > 0) {
-                    if (codec_stream_pos(s->cstream, b) > q.stream_pos) codec_stream_reset(s->cstream, b);
-                    sp = codec_stream_pos(s->cstream, b);
-                    n = q.stream_pos + a - sp; skip = q.stream_pos - sp;
-                }
-                CsPush p{b, n, skip, nullptr, s->codes + ((size_t)b * s->max_frames + sp) * 16, nullptr};
-                p.ps = s->ostage; p.ps_row = b; p.last = last; p.out_host = out_host[b]; p.n_out = &n_samples[b];
-                pushes.push_back(p);
-            } else {
-                // ICL rows and stream mode 0 keep the per-row context-free decode; its samples take the stage's host entry
-                tmp.resize((size_t)a * spf);
-                if (a > 0) Q3C(chunk_decode_row(s, b, a, tmp.data(), tmp.size(), nullptr));
-                const float* in = tmp.data(); const size_t n_in = tmp.size();
-                Q3C(q3_pcm_stage_push(s->ostage, 1, &b, &in, &n_in, &last, &out_host[b], &cap[b], &n_samples[b]));
-            }
-            continue;
-        }
-        if (a <= 0) continue;
+        if (a <= 0 && !(out && last)) continue;          // (out: a == 0 but last flushes the stage row)
         if (s->stream_mode == 1 && !q.icl) {
             if (!s->cstream) Q3C(codec_stream_create(s->m, s->B, s->max_frames, s->stream, &s->cstream));
-            // the row's state follows the row: behind it (q3_session_next_chunk_row moved the row on) the push catches up,
-            // ahead of it (another utterance's) it starts over
-            if (codec_stream_pos(s->cstream, b) > q.stream_pos) codec_stream_reset(s->cstream, b);
-            const int sp = codec_stream_pos(s->cstream, b);
-            pushes.push_back({b, q.stream_pos + a - sp, q.stream_pos - sp, nullptr, s->codes + ((size_t)b * s->max_frames + sp) * 16,
-                              pcm_host ? pcm_host[b] : nullptr});
+            int sp = 0;
+            CsPush p{b, 0, 0, nullptr, nullptr, nullptr};
+            if (a > 0) {
+                // the row's state follows the row: behind it (q3_session_next_chunk[_row] moved the row on) the push catches up,
+                // ahead of it (another utterance's) it starts over
+                if (codec_stream_pos(s->cstream, b) > q.stream_pos) codec_stream_reset(s->cstream, b);
+                sp = codec_stream_pos(s->cstream, b);
+                p.n = q.stream_pos + a - sp; p.skip = q.stream_pos - sp;
+            }
+            p.dev = s->codes + ((size_t)b * s->max_frames + sp) * 16;
+            if (out) { p.ps = s->ostage; p.ps_row = b; p.last = last; p.out_host = out_host[b]; p.n_out = &n_samples[b]; }
+            else p.pcm_host = pcm_host ? pcm_host[b] : nullptr;
+            pushes.push_back(p);
+        } else if (out) {
+            // ICL rows and stream mode 0 keep the per-row context-free decode; its samples take the stage's host entry
+            tmp.resize((size_t)a * spf);
+            if (a > 0) Q3C(chunk_decode_row(s, b, a, tmp.data(), tmp.size(), nullptr));
+            const float* in = tmp.data(); const size_t n_in = tmp.size();
+            Q3C(q3_pcm_stage_push(s->ostage, 1, &b, &in, &n_in, &last, &out_host[b], &cap[b], &n_samples[b]));
         } else {
             Q3C(chunk_decode_row(s, b, a, pcm_host ? pcm_host[b] : nullptr, cap ? cap[b] : 0, nullptr));
         }
     }
     if (!pushes.empty()) Q3C(codec_stream_push(s->cstream, pushes));
     for (int b = 0; b < s->B; ++b) {
-        SeqInfo& q = s->seq[b];
-        q.stream_pos += avail[(size_t)b];
-        done[b] = held[(size_t)b] ? 0 : (avail[(size_t)b] <= 0 || (q.done && q.stream_pos >= q.n_frames)) ? 1 : 0;
+        s->seq[(size_t)b].stream_pos += cuts[(size_t)b].avail;
+        done[b] = cuts[(size_t)b].ends ? 1 : 0;
     }
     return Q3_OK;
 }
@@ -2133,20 +2144,14 @@ extern "C" q3_status q3_session_codes(q3_session* s, int b, uint32_t* codes_host
     return Q3_OK;
 }
 
-// context-free decode of frames [f0, f1) of sequence b on `st` (the reference's per-chunk decode, lib.rs:1755-1758)
+// context-free decode of frames [f0, f1) of sequence b on `st`, waited for and copied out
 static q3_status decode_range_on(q3_session* s, int b, int f0, int f1, hipStream_t st, float* pcm_host, size_t cap, size_t* n_samples) {
-    const int T = f1 - f0, spf = samples_per_frame(s->m->cfg);
-    if (n_samples) *n_samples = (size_t)T * spf;
-    if (T == 0) return Q3_OK;
-    Q3C(codec_reserve(s->m, s->cws, T));
-    HIPC(hipMemcpyAsync(s->cws.frames, s->codes + ((size_t)b * s->max_frames + f0) * 16, (size_t)T * 16 * 4, hipMemcpyDeviceToDevice, st));
-    Q3C(codec_decode_dev(s->m, s->cws, T, st, nullptr));
+    if (n_samples) *n_samples = 0;
+    if (f1 == f0) return Q3_OK;
+    ChunkPcm pcm;
+    Q3C(range_vocode_enqueue(s, b, f0, f1 - f0, st, &pcm));
     HIPC(hipStreamSynchronize(st));
-    if (pcm_host) {
-        if (cap < (size_t)T * spf) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
-        HIPC(q3_hipMemcpy(pcm_host, s->cws.pcm, (size_t)T * spf * 4, hipMemcpyDeviceToHost));
-    }
-    return Q3_OK;
+    return chunk_copy_out(pcm, pcm_host, cap, n_samples);
 }
 
 extern "C" q3_status q3_session_decode(q3_session* s, int b, int f0, int f1, float* pcm_host, size_t cap, size_t* n_samples) {
@@ -2410,36 +2415,30 @@ extern "C" q3_status q3_session_next_chunk(q3_session* s, float* pcm_host, size_
     if (s->B != 1) return set_err(Q3_UNSUPPORTED, "streaming sessions are batch 1 (StreamingSession, lib.rs:1484)");
     if (!s->prefilled) { s->precapture = true; Q3C(q3_session_prefill(s)); }
     Q3C(refresh_codes(s));
+    Q3C(chunk_fill(s, 0));
+    // (open text: the fill stopped at the held frame, and the read-ahead below never goes past what the text allows: session_remaining)
+    const ChunkCut cut = chunk_cut(s, 0);
+    if (cut.avail <= 0) { if (n_samples) *n_samples = 0; if (done) *done = cut.ends ? 1 : 0; return Q3_OK; }
     SeqInfo& q = s->seq[0];
-    const int chunk = s->opts.chunk_frames > 0 ? s->opts.chunk_frames : 10;
-    // generate until chunk_frames frames are buffered or the sequence ends (lib.rs:1663-1748)
-    while (!q.done && q.n_frames - s->stream_pos < chunk && session_remaining(s) > 0) {
-        int need = chunk - (q.n_frames - s->stream_pos);
-        Q3C(q3_session_generate(s, need, 1));
-        Q3C(refresh_codes(s));
-    }
-    int avail = q.n_frames - s->stream_pos;
-    if (avail > chunk) avail = chunk;
-    // open text that does not reach a whole chunk yet: nothing now (the loop above stopped at the held frame; chunk boundaries
-    // stay those of the closed run). Read-ahead below never goes past what the text allows (session_remaining).
-    if (q.opened && !q.done && avail < chunk) { if (n_samples) *n_samples = 0; if (done) *done = 0; return Q3_OK; }
-    if (avail <= 0) { if (n_samples) *n_samples = 0; if (done) *done = 1; return Q3_OK; }
-    const bool chunk_done = q.done && s->stream_pos + avail >= q.n_frames;
-    // Read-ahead: the frames of the NEXT chunk are enqueued (graph replays, no host wait) while this chunk is vocoded
-    // and handed over, so the frame loop keeps going while the host copies out, returns and plays the chunk. First
-    // chunk: its vocoder is enqueued first and the replays behind it on the same stream (time-to-first-audio is what it
-    // was; the host waits on an event, not on the stream). Later chunks: the replays go first and the chunk's vocoder
-    // runs beside them on its own stream — a chunk then costs max(generation, decode) instead of their sum (streaming
-    // RTF 0.046 -> 0.042 on the 1.7B model). After EOS the device-side done flag turns extra replays into no-ops.
-    // Q3_STREAM_NO_AHEAD=1 restores the serial schedule (A/B aid).
+    const int chunk = chunk_frames_of(s), avail = cut.avail;
+    // Read-ahead: the frames of the NEXT chunk are enqueued (no host wait for them) while this chunk is vocoded and handed
+    // over, so the frame loop keeps going while the host copies out, returns and plays the chunk.
+    // First chunk: its vocoder is enqueued first, on the session's stream, then the replays. As graph launches they queue behind
+    // it on the same stream and the host waits on an event, not on the stream. On the own (AQL) queue, which is not ordered
+    // with the stream, launch_ahead synchronises the stream before it submits: the first chunk is then serial — vocoder,
+    // wait, replays handed over, return — and time-to-first-audio is what it is without read-ahead.
+    // Later chunks: the replays go first and the chunk's vocoder runs beside them on its own stream — a chunk then costs
+    // max(generation, decode) instead of their sum (streaming RTF 0.046 -> 0.042 on the 1.7B model); on the AQL path the
+    // stream that launch_ahead synchronises holds only the K/V table updates then. After EOS the device-side done flag turns
+    // extra replays into no-ops. Q3_STREAM_NO_AHEAD=1 restores the serial schedule (A/B aid).
     static const bool no_ahead = getenv("Q3_STREAM_NO_AHEAD") != nullptr;
     int ahead = 0;
     if (!no_ahead && !q.done && (s->aql || s->graph_exec) && !s->aql_failed && !s->debug && !s->profile) {
-        ahead = chunk - (q.n_frames - (s->stream_pos + avail));
+        ahead = chunk - (q.n_frames - (q.stream_pos + avail));
         if (ahead > session_remaining(s)) ahead = session_remaining(s);
         if (ahead < 0) ahead = 0;
     }
-    const bool first = s->stream_pos == 0;
+    const bool first = q.stream_pos == 0;
     auto launch_ahead = [&]() -> q3_status {
         Q3C(kv_reserve_frames(s, ahead));                        // (its table updates ride s->stream)
         if (s->aql) HIPC(hipStreamSynchronize(s->stream));       // the own queue is not ordered with the stream
@@ -2451,25 +2450,8 @@ extern "C" q3_status q3_session_next_chunk(q3_session* s, float* pcm_host, size_
         Q3C(launch_ahead());
         dst = s->dec_stream;
     }
-    // enqueue this chunk's vocoder on dst
-    const int spf = samples_per_frame(s->m->cfg);
-    const float* src = nullptr;
-    if (s->stream_mode == 1 && !q.icl) {
-        // continuous mode: the front runs over frames [0, end), the convolutional stack over [pos - CTX, end); the chunk's
-        // samples are identical to the same frames of a whole-utterance decode (codec_decode_dev)
-        const int a0 = s->stream_pos, e = s->stream_pos + avail;
-        const int c0 = a0 > CODEC_CTX_FRAMES ? a0 - CODEC_CTX_FRAMES : 0;
-        Q3C(codec_reserve(s->m, s->cws, chunk + CODEC_CTX_FRAMES, s->max_frames));
-        HIPC(hipMemcpyAsync(s->cws.frames, s->codes, (size_t)e * 16 * 4, hipMemcpyDeviceToDevice, dst));
-        Q3C(codec_decode_dev(s->m, s->cws, e, dst, nullptr, c0));
-        src = s->cws.pcm + (size_t)(a0 - c0) * spf;
-    } else {
-        // the reference's schedule: the chunk decoded as an independent utterance (lib.rs:1755-1758)
-        Q3C(codec_reserve(s->m, s->cws, avail));
-        HIPC(hipMemcpyAsync(s->cws.frames, s->codes + (size_t)s->stream_pos * 16, (size_t)avail * 16 * 4, hipMemcpyDeviceToDevice, dst));
-        Q3C(codec_decode_dev(s->m, s->cws, avail, dst, nullptr));
-        src = s->cws.pcm;
-    }
+    ChunkPcm pcm;
+    Q3C(chunk_vocode_enqueue(s, 0, avail, dst, &pcm));
     if (ahead > 0 && first) {
         if (!s->dec_ev) HIPC(hipEventCreateWithFlags(&s->dec_ev, hipEventDisableTiming));
         HIPC(hipEventRecord(s->dec_ev, s->stream));
@@ -2478,13 +2460,9 @@ extern "C" q3_status q3_session_next_chunk(q3_session* s, float* pcm_host, size_
     } else {
         HIPC(hipStreamSynchronize(dst));
     }
-    if (n_samples) *n_samples = (size_t)avail * spf;
-    if (pcm_host) {
-        if (cap < (size_t)avail * spf) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
-        HIPC(q3_hipMemcpy(pcm_host, src, (size_t)avail * spf * 4, hipMemcpyDeviceToHost));
-    }
-    s->stream_pos += avail;
-    if (done) *done = chunk_done ? 1 : 0;
+    Q3C(chunk_copy_out(pcm, pcm_host, cap, n_samples));
+    q.stream_pos += avail;
+    if (done) *done = cut.ends ? 1 : 0;
     return Q3_OK;
 }
 

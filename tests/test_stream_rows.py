@@ -214,3 +214,40 @@ def test_alternating_with_next_chunk_row(gm):
     for b in range(3):
         np.testing.assert_array_equal(np.concatenate(got[b]), s.decode(b), err_msg=f"row {b}")
     s.close()
+
+
+def _take(s, call):
+    a, d = {"chunk": s.next_chunk, "row": lambda: s.next_chunk_row(0), "rows": lambda: s.next_chunks()[0]}[call]()
+    return (None if a is None else a.samples), d
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [1, 0])
+def test_one_position_under_every_entry(gm, mode):
+    """A row has one streaming position that every chunk entry follows. One row, limit 23, chunk 7 (the last chunk is the 2-frame
+    remainder): twin A is read through q3_session_next_chunk alone, twin B through next_chunk, next_chunk_row(0), next_chunks(),
+    next_chunk in turn — the same (samples, done) sequence, and in stream mode 1 the whole decode. While q3_session_next_chunk
+    kept a position of its own beside the row's, twin B delivered frames 0-6 a second time when it changed calls.
+    Parking row 0 between chunk 1 and chunk 2 is refused (a row's stream position does not travel with its record): the same
+    refusal whichever entry took the first chunk, and the rows stream on unharmed."""
+    opts = q.SynthesisOptions(max_length=23, seed=42, eos_token_id=None, chunk_frames=7)
+    a = _session(gm, _utts([23]), opts, mode); b = _session(gm, _utts([23]), opts, mode)
+    want = [_take(a, "chunk") for _ in range(4)]
+    got = [_take(b, call) for call in ("chunk", "row", "rows", "chunk")]
+    _same_rounds([[g] for g in got], [[w] for w in want])
+    assert [len(x) // SPF for x, _ in got] == [7, 7, 7, 2] and [d for _, d in got] == [False, False, False, True]
+    assert _take(a, "chunk") == (None, True) and _take(b, "row") == (None, True)
+    if mode == 1:
+        np.testing.assert_array_equal(np.concatenate([x for x, _ in got]), b.decode(0))
+    a.close(); b.close()
+
+    refusal = "q3_session_park_row: row 0 has delivered chunks (q3_session_next_chunk*): its stream position does not travel"
+    for first in ("chunk", "row"):
+        s = _session(gm, _utts([23]), opts, mode)
+        got = [_take(s, first)]
+        with pytest.raises(_lib.Q3Error) as e:
+            s.park_row(0)
+        assert refusal in str(e.value), first
+        got += [_take(s, "chunk") for _ in range(3)]
+        _same_rounds([[g] for g in got], [[w] for w in want])
+        s.close()
