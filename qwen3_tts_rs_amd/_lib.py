@@ -252,6 +252,14 @@ SYMBOLS = {
     "q3_session_silence": (c_int, [c_void_p, c_int] + [P(ctypes.c_int64)] * 5),
     "q3_batcher_ticket_silence": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int, c_int]),
     "q3_batcher_ticket_silence_read": (c_int, [c_void_p, ctypes.c_int64] + [P(ctypes.c_int64)] * 5),
+    "q3_pcm_stage_set_mark": (c_int, [c_void_p, c_int, ctypes.c_uint64, c_int]),
+    "q3_mark_carrier": (c_int, [ctypes.c_uint64, c_void_p]),
+    "q3_mark_embed": (c_int, [c_void_p, ctypes.c_size_t, ctypes.c_uint64, c_int, c_void_p]),
+    "q3_mark_score_detect": (ctypes.c_double, []),
+    "q3_mark_detect": (c_int, [c_void_p, ctypes.c_size_t, ctypes.c_uint64, P(ctypes.c_double), P(c_int)]),
+    "q3_session_set_mark": (c_int, [c_void_p, c_int, ctypes.c_uint64, c_int]),
+    "q3_batcher_ticket_mark": (c_int, [c_void_p, ctypes.c_int64, ctypes.c_uint64, c_int]),
+    "q3_ref_audio_mark_score": (c_int, [c_void_p, ctypes.c_uint64, P(ctypes.c_double), P(c_int)]),
     "q3_pcm_stage_set_level": (c_int, [c_void_p, c_int, c_int, c_int]),
     "q3_pcm_stage_level_coeffs": (c_int, [c_int, c_int, P(ctypes.c_float), P(ctypes.c_float)]),
     "q3_pcm_stage_level_count": (c_int, [ctypes.c_size_t, c_int, P(ctypes.c_size_t)]),

@@ -19,6 +19,10 @@ from ._lib import lib, check, COptions, CRequest, CTiming
 from .config import Q3Config
 from . import synth
 
+# the keyed watermark of the output stage
+MARK_DB_DEFAULT = -26.0                                  # Q3_MARK_STRENGTH_DEFAULT
+MARK_SCORE_DETECT = float(lib.q3_mark_score_detect())    # Q3_MARK_SCORE_DETECT: a clip carries the key's mark from this score on
+
 MAX_BATCH = 64                 # Q3_MAX_BATCH (include/q3tts.h): sequences per session
 CODEC_EOS_TOKEN_ID = 2150      # lib.rs:1466
 SAMPLES_PER_FRAME = 1920       # lib.rs:1469
@@ -327,6 +331,11 @@ class Session:
         check(lib.q3_session_set_silence(self._h, int(b), thr, int(edge_ms), int(pause_ms)))
         self._note_out(b, 3, (int(edge_ms), int(pause_ms)) if thr else None)
 
+    def set_mark(self, key, db: float = MARK_DB_DEFAULT, b: int = -1):
+        """The keyed watermark of row b (-1: every row) in `next_chunks_out` (q3_session_set_mark): key 0 or None = off; db: its
+        strength in dB re the local signal level, -40..-10. The window and the persistence of `set_tempo`."""
+        check(lib.q3_session_set_mark(self._h, int(b), mark_key(key), mark_mb(db)))
+
     def silence(self, b: int = 0) -> "Silence":
         """Row b's counts after its last streamed chunk (q3_session_silence)."""
         v = [ctypes.c_int64() for _ in range(5)]
@@ -584,14 +593,15 @@ class Batcher:
 
     def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False, tempo_permille: int = 1000,
                         fmt: Optional[str] = None, gain_mb: int = 0, ceiling_mb: int = 0, target_lufs: Optional[float] = None,
-                        prior_gain_db: float = 0.0, pitch_cents: int = 0, silence=None) -> int:
+                        prior_gain_db: float = 0.0, pitch_cents: int = 0, silence=None, mark=None) -> int:
         """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16 / fmt: the
         ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked, uint8 for
         fmt "ulaw" / "alaw". tempo_permille: its speaking rate (q3_batcher_ticket_tempo; 1250 = 1.25 x as fast, 1000 = off).
         gain_mb / ceiling_mb: its level (q3_batcher_ticket_level; millibel, (0, 0) = off). target_lufs: the loudness it is steered
         to, from the gain prior_gain_db (q3_batcher_ticket_loudness; `loudness(ticket)` reads the result). pitch_cents: its pitch
         (q3_batcher_ticket_pitch; -1200..1200, 0 = off). silence = (threshold_db, edge_ms, pause_ms): its silence step
-        (q3_batcher_ticket_silence; `silence(ticket)` reads the counts)."""
+        (q3_batcher_ticket_silence; `silence(ticket)` reads the counts). mark = (key, db) or key: its keyed watermark
+        (q3_batcher_ticket_mark)."""
         code = pcm_format(pcm16, fmt)
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
@@ -608,6 +618,12 @@ class Batcher:
         if silence is not None:
             try:
                 self.ticket_silence(int(t.value), *silence)
+            except _lib.Q3Error:
+                self.cancel(int(t.value)); self.fetch(int(t.value))
+                raise
+        if mark is not None:
+            try:
+                self.ticket_mark(int(t.value), *(mark if isinstance(mark, (tuple, list)) else (mark,)))
             except _lib.Q3Error:
                 self.cancel(int(t.value)); self.fetch(int(t.value))
                 raise
@@ -658,6 +674,12 @@ class Batcher:
         m = ctypes.c_float(); g = ctypes.c_float(); nb = ctypes.c_int(); cg = ctypes.c_int()
         check(lib.q3_batcher_ticket_loudness_read(self._h, int(ticket), ctypes.byref(m), ctypes.byref(g), ctypes.byref(nb), ctypes.byref(cg)))
         return Loudness.of(m.value, g.value, nb.value, cg.value)
+
+    def ticket_mark(self, ticket: int, key, db: float = MARK_DB_DEFAULT):
+        """A streamed ticket's keyed watermark (q3_batcher_ticket_mark): between its submission and the next `step`."""
+        check(lib.q3_batcher_ticket_mark(self._h, int(ticket), mark_key(key), mark_mb(db)))
+        if mark_key(key):
+            self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
 
     def ticket_silence(self, ticket: int, threshold_db, edge_ms: int = 50, pause_ms: int = 400):
         """A streamed ticket's silence step (q3_batcher_ticket_silence): between its submission and the next `step`."""
@@ -1501,6 +1523,59 @@ def silence_mb(threshold_db) -> int:
     return 0 if threshold_db is None else int(round(float(threshold_db) * 100.0))
 
 
+def mark_key(key) -> int:
+    """A watermark key as the library's uint64: an int, a hex string ("c0ffee" / "0xc0ffee"), None or 0 for off."""
+    if key is None:
+        return 0
+    k = int(key, 16) if isinstance(key, str) else int(key)
+    if not 0 <= k < (1 << 64):
+        raise ValueError(f"a watermark key is 64 bits, not {key!r}")
+    return k
+
+
+def mark_mb(db) -> int:
+    """A strength in dB re the local signal level as the stage's millibel."""
+    return int(round(float(db) * 100.0))
+
+
+def mark_carrier(key) -> np.ndarray:
+    """The carrier of a key (q3_mark_carrier): one period of 4096 samples at 24 kHz, float32, unit RMS."""
+    c = np.zeros(4096, np.float32)
+    check(lib.q3_mark_carrier(mark_key(key), c.ctypes.data_as(ctypes.c_void_p)))
+    return c
+
+
+def mark_embed(samples, key, db: float = MARK_DB_DEFAULT):
+    """The watermark step's definition on the CPU for one whole 24 kHz clip (q3_mark_embed), with the bits a stage row with
+    `set_mark` returns — what a caller of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their result.
+    AudioBuffer in, AudioBuffer out; an array gives an array."""
+    x = np.ascontiguousarray(samples.samples if isinstance(samples, AudioBuffer) else samples, dtype=np.float32).reshape(-1)
+    if isinstance(samples, AudioBuffer) and samples.sample_rate != 24000:
+        raise ValueError(f"mark_embed takes 24 kHz audio, not {samples.sample_rate} Hz")
+    y = np.zeros(x.size, np.float32)
+    check(lib.q3_mark_embed(x.ctypes.data_as(ctypes.c_void_p), x.size, mark_key(key), mark_mb(db), y.ctypes.data_as(ctypes.c_void_p)))
+    return AudioBuffer(y, 24000) if isinstance(samples, AudioBuffer) else y
+
+
+@dataclass
+class MarkScore:
+    """The detector's reading of a clip for one key: score in standard deviations of the correlation over the 4096 shifts, offset:
+    the carrier index of the clip's first sample, detected: score >= MARK_SCORE_DETECT."""
+    score: float
+    offset: int
+    detected: bool
+
+
+def mark_detect(samples, key) -> MarkScore:
+    """The watermark detector on the CPU, in float64 (q3_mark_detect), for a 24 kHz mono clip of at least 8192 samples."""
+    x = np.ascontiguousarray(samples.samples if isinstance(samples, AudioBuffer) else samples, dtype=np.float32).reshape(-1)
+    if isinstance(samples, AudioBuffer) and samples.sample_rate != 24000:
+        raise ValueError(f"mark_detect takes 24 kHz audio, not {samples.sample_rate} Hz (resample it first)")
+    sc = ctypes.c_double(); off = ctypes.c_int()
+    check(lib.q3_mark_detect(x.ctypes.data_as(ctypes.c_void_p), x.size, mark_key(key), ctypes.byref(sc), ctypes.byref(off)))
+    return MarkScore(sc.value, off.value, sc.value >= MARK_SCORE_DETECT)
+
+
 def pcm_stage_silence_hold(edge_ms: int, pause_ms: int) -> int:
     """The most samples a row's silence step retains (q3_pcm_stage_silence_hold)."""
     n = ctypes.c_size_t()
@@ -1579,6 +1654,11 @@ class PcmStage:
         check(lib.q3_pcm_stage_set_silence(self._h, int(row), thr, int(edge_ms), int(pause_ms)))
         self._silence[int(row)] = (int(edge_ms), int(pause_ms)) if thr else None
 
+    def set_mark(self, row: int, key, db: float = MARK_DB_DEFAULT):
+        """Row's keyed watermark (q3_pcm_stage_set_mark): key 0 or None = off; db: its strength in dB re the local signal level,
+        -40..-10; also restarts the row. `set`, `reset` and the other `set_*` keep it. No count or bound changes."""
+        check(lib.q3_pcm_stage_set_mark(self._h, int(row), mark_key(key), mark_mb(db)))
+
     def silence(self, row: int) -> "Silence":
         """The row's counts after its last successful push (q3_pcm_stage_silence)."""
         v = [ctypes.c_int64() for _ in range(5)]
@@ -1649,13 +1729,15 @@ class PcmStage:
 
 
 def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_permille: int = 1000, fmt: Optional[str] = None,
-                 gain_mb: int = 0, ceiling_mb: int = 0, target_mb: Optional[int] = None, prior_mb: int = 0, pitch_cents: int = 0, silence=None) -> AudioBuffer:
+                 gain_mb: int = 0, ceiling_mb: int = 0, target_mb: Optional[int] = None, prior_mb: int = 0, pitch_cents: int = 0, silence=None,
+                 mark=None) -> AudioBuffer:
     """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked (fmt: "f32" /
     "s16" / "ulaw" / "alaw") — what a caller of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their
     result. tempo_permille: the clip's speaking rate (1250 = 1.25 x as fast, 1000 = as it is). gain_mb / ceiling_mb: its level. target_mb / prior_mb: the loudness it is
     steered to (millibel of LUFS) and the gain it starts from — a causal normaliser: the first 400 ms leave at the prior.
     pitch_cents: its pitch (-1200..1200 cents, 0 = as it is; the duration stays that of the tempo). silence = (threshold_db, edge_ms,
-    pause_ms): its edges and pauses cut first, as `trim_silence` does."""
+    pause_ms): its edges and pauses cut first, as `trim_silence` does. mark = (key, db) or key: its keyed watermark, as `mark_embed`
+    adds it, behind the loudness and in front of the level."""
     code = pcm_format(pcm16, fmt)
     x = np.ascontiguousarray(audio.samples if isinstance(audio, AudioBuffer) else audio, dtype=np.float32).reshape(-1)
     if isinstance(audio, AudioBuffer) and audio.sample_rate != 24000:
@@ -1673,6 +1755,8 @@ def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_p
             ps.set_loudness(0, LOUD_NORMALIZE, target_mb, prior_mb)
         if silence is not None:
             ps.set_silence(0, *silence)
+        if mark is not None:
+            ps.set_mark(0, *(mark if isinstance(mark, (tuple, list)) else (mark,)))
         return AudioBuffer(ps.push({0: x}, last=(0,))[0], int(rate))
     finally:
         ps.close()
@@ -1853,6 +1937,13 @@ class RefAudio:
         out = np.empty(self.n_samples, np.float32); n = ctypes.c_int64()
         check(lib.q3_ref_audio_read(self._h, out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n)))
         return out
+
+    def mark_score(self, key) -> "MarkScore":
+        """The watermark detector on the device (q3_ref_audio_mark_score: k_mark_fold, k_mark_corr), on the clip where the intake
+        left it; `mark_detect`'s definition."""
+        sc = ctypes.c_double(); off = ctypes.c_int()
+        check(lib.q3_ref_audio_mark_score(self._h, mark_key(key), ctypes.byref(sc), ctypes.byref(off)))
+        return MarkScore(sc.value, off.value, sc.value >= MARK_SCORE_DETECT)
 
     def __len__(self) -> int:
         return self.n_samples

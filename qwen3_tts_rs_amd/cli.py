@@ -86,6 +86,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --trim-silence-db: the silence kept at the start and at the end, 0 .. 1000 ms in steps of 10")
     ap.add_argument("--max-pause-ms", type=int, default=400, metavar="MS", action=_Given,
                     help="with --trim-silence-db: the longest pause left inside the utterance, 20 .. 2000 ms in steps of 10")
+    ap.add_argument("--watermark-key", default=None, metavar="HEX",
+                    help="with --streaming: add an inaudible keyed watermark by the output stage (behind the loudness step, in front of "
+                         "the limiter); HEX: the 64-bit key, e.g. c0ffee")
+    ap.add_argument("--watermark-db", type=float, default=-26.0, metavar="X", action=_Given,
+                    help="with --watermark-key: the mark's level re the local signal level, -40 .. -10 dB (default -26)")
+    ap.add_argument("--detect-watermark", nargs=2, default=None, metavar=("HEX", "FILE.wav"),
+                    help="instead of synthesizing: score FILE.wav for the watermark of key HEX and print the score, the offset and the "
+                         "decision; with --ref-intake device the clip is converted and scored on the GPU")
     ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
                     help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
                          "first token to the first audio; writes the same WAV as without the flag)")
@@ -254,6 +262,49 @@ def silence_from_args(a):
     return a.trim_silence_db, a.edge_ms, a.max_pause_ms
 
 
+def mark_from_args(a):
+    """(key, db) of --watermark-key / --watermark-db, or None without --watermark-key; ValueError for a combination the CLI
+    refuses (before anything is loaded)."""
+    from qwen3_tts_rs_amd import api
+    if a.watermark_key is None:
+        if getattr(a, "watermark_db_given", False):
+            raise ValueError("--watermark-db applies to --watermark-key")
+        return None
+    if not a.streaming:
+        raise ValueError("--watermark-key applies to --streaming (mark a whole utterance with api.mark_embed)")
+    try:
+        key = api.mark_key(a.watermark_key)
+    except ValueError:
+        raise ValueError(f"--watermark-key {a.watermark_key!r} is not a 64-bit hexadecimal number")
+    if key == 0:
+        raise ValueError("--watermark-key 0 is off")
+    if not -40.0 <= a.watermark_db <= -10.0:
+        raise ValueError(f"--watermark-db {a.watermark_db} out of range (-40 .. -10)")
+    return key, a.watermark_db
+
+
+def detect_watermark(a, dev: int) -> int:
+    """--detect-watermark HEX FILE.wav: the score, the offset and the decision."""
+    from qwen3_tts_rs_amd import api
+    hexkey, path = a.detect_watermark
+    try:
+        key = api.mark_key(hexkey)
+        if a.ref_intake == "device":
+            ref = api.RefAudio.from_wav(path, device=dev)
+            r = ref.mark_score(key); dur = ref.duration(); ref.close()
+        else:
+            clip = api.AudioBuffer.load(path)
+            if clip.sample_rate != 24000:
+                clip = api.resample(clip, 24000)
+            r = api.mark_detect(clip, key); dur = clip.duration()
+    except (api._lib.Q3Error, OSError, ValueError) as e:
+        print(f"error: {e}", file=sys.stderr)
+        return 2
+    print(f"Watermark: score {r.score:.2f} (threshold {api.MARK_SCORE_DETECT:.2f}), offset {r.offset}, {dur:.2f}s scored on the "
+          f"{'device' if a.ref_intake == 'device' else 'host'}: {'DETECTED' if r.detected else 'not detected'}")
+    return 0
+
+
 def max_frames_from_args(a) -> int:
     return int(a.duration * 12.5) if a.duration is not None else a.frames
 
@@ -308,10 +359,13 @@ def main(argv=None) -> int:
     try:
         loud = loudness_from_args(a)
         sil = silence_from_args(a)
+        mark = mark_from_args(a)
     except ValueError as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
     dev = parse_device(a.device)
+    if a.detect_watermark:
+        return detect_watermark(a, dev)
     if a.tokenize:
         return tokenize_clips(a, dev)
     speaker, language = q.Speaker.from_str(a.speaker), q.Language.from_str(a.language)
@@ -401,7 +455,7 @@ def main(argv=None) -> int:
         print("error: --output-format / --gain-db / --ceiling-db apply to --streaming (convert a whole utterance with "
               "api.resample_gpu(..., fmt=, gain_mb=, ceiling_mb=))", file=sys.stderr)
         return 2
-    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None or sil is not None):
+    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None or sil is not None or mark is not None):
         # the chunks of the streaming session, each through the session's output stage as it leaves
         s = model.session([utt], opts)
         try:
@@ -416,6 +470,8 @@ def main(argv=None) -> int:
                 s.set_loudness(api.LOUD_NORMALIZE, loud[0], loud[1])
             if sil is not None:
                 s.set_silence(*sil)
+            if mark is not None:
+                s.set_mark(*mark)
         except api._lib.Q3Error as e:
             print(f"error: {e}", file=sys.stderr)
             return 2
@@ -466,6 +522,8 @@ def main(argv=None) -> int:
     if cuts is not None:
         print(f"Silence: {cuts.lead_cut} samples cut at the front, {cuts.pause_cut} in pauses, {cuts.trail_cut} at the end "
               f"({cuts.n_out} of {cuts.n_in} samples at 24 kHz kept; under {a.trim_silence_db:.1f} dBFS, edges {a.edge_ms} ms, pauses {a.max_pause_ms} ms)")
+    if mark is not None:
+        print(f"Watermark: key {mark[0]:x} at {mark[1]:.1f} dB re the local level")
     os.makedirs(a.output_dir, exist_ok=True)
     wav = a.output or os.path.join(a.output_dir, f"audio_seed{a.seed}_frames{n}.wav")
     if g711 is not None:

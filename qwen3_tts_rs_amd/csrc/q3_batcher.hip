@@ -1256,6 +1256,9 @@ extern "C" q3_status q3_batcher_ticket_loudness(q3_batcher* b, int64_t ticket, i
     out_loudness_at_rest(t.out, &t.lo_M, &t.lo_gain, &t.lo_blocks, &t.lo_gated);      // (until a part lands)
     return Q3_OK;
 }
+extern "C" q3_status q3_batcher_ticket_mark(q3_batcher* b, int64_t ticket, uint64_t key, int strength_mB) {
+    return ticket_set(b, ticket, "q3_batcher_ticket_mark", "mark", [&](const char* who, OutSettings& o) { return out_set_mark(who, o, key, strength_mB); });
+}
 extern "C" q3_status q3_batcher_ticket_silence(q3_batcher* b, int64_t ticket, int threshold_mB, int edge_ms, int pause_ms) {
     Q3C(ticket_set(b, ticket, "q3_batcher_ticket_silence", "silence step",
                    [&](const char* who, OutSettings& o) { return out_set_silence(who, o, threshold_mB, edge_ms, pause_ms); }));

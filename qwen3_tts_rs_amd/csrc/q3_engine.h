@@ -429,9 +429,11 @@ struct OutSettings {
     int gain_mB = 0, ceil_mB = 0;                             // the level; 0 / 0: off
     int loud = Q3_LOUD_OFF, target_mB = -1900, prior_mB = 0;
     int sil_mB = 0, edge_ms = 0, pause_ms = 20;               // the silence step's threshold, 0: off
+    uint64_t mark_key = 0; int mark_mB = Q3_MARK_STRENGTH_DEFAULT;               // the mark step's key, 0: off; its strength
     // 24 kHz f32 with every step off: the samples leave as they are, and no stage is needed
     bool plain() const {
-        return rate == 24000 && fmt == Q3_PCM_F32 && tempo == 1000 && cents == 0 && gain_mB == 0 && ceil_mB == 0 && loud == Q3_LOUD_OFF && sil_mB == 0;
+        return rate == 24000 && fmt == Q3_PCM_F32 && tempo == 1000 && cents == 0 && gain_mB == 0 && ceil_mB == 0 && loud == Q3_LOUD_OFF && sil_mB == 0 &&
+               mark_key == 0;
     }
     size_t sample_bytes() const { return fmt == Q3_PCM_F32 ? 4 : fmt == Q3_PCM_S16 ? 2 : 1; }
 };
@@ -579,6 +581,13 @@ struct PsPlan { std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t
 // q3_resample's filter as a table for output / input = L / M in lowest terms, out[L][128] (taps_of): the output stage's at
 // L / M = sr_out / 24000, the intake's (q3_intake.hip) at L / M = 24000 / sr_in
 Q3_HIDDEN void resampler_taps(int L, int M, std::vector<float>& out);
+// the counter hash of q3_synth_fill (q3_model.hip) and its hash of a name: the mark's carrier derives its phases from them
+Q3_HIDDEN uint64_t synth_hash(uint64_t x);
+Q3_HIDDEN uint64_t synth_name_hash(const char* s);
+// the mark's carrier of a key as q3_mark_carrier builds it, c[4096] (q3_pcm_stage.hip); the intake's detector stages it
+Q3_HIDDEN void mark_carrier(uint64_t key, float* c);
+// the detector's score and offset from the 4096 correlations (f64 on the host, whoever computed rho)
+Q3_HIDDEN q3_status mark_score_f32(const float* rho, double* score, int* offset);
 Q3_HIDDEN int pcm_stage_rows(const q3_pcm_stage* ps);
 Q3_HIDDEN void pcm_stage_reset(q3_pcm_stage* ps, int row);
 Q3_HIDDEN q3_status pcm_stage_check_rows(const q3_pcm_stage* ps, const char* who, int n_rows, const int* rows);
@@ -592,6 +601,7 @@ Q3_HIDDEN q3_status out_set_pitch(const char* who, OutSettings& o, int cents);
 Q3_HIDDEN q3_status out_set_level(const char* who, OutSettings& o, int gain_mB, int ceiling_mB);
 Q3_HIDDEN q3_status out_set_loudness(const char* who, OutSettings& o, int mode, int target_mB, int prior_mB);
 Q3_HIDDEN q3_status out_set_silence(const char* who, OutSettings& o, int threshold_mB, int edge_ms, int pause_ms);
+Q3_HIDDEN q3_status out_set_mark(const char* who, OutSettings& o, uint64_t key, int strength_mB);
 // The only writer of a row's step settings: what the steps that `o` turns on need on the device, the values derived from `o`,
 // and the row's restart. All or nothing (but see the silence step's state there). pcm_stage_settings: what the row was given last.
 Q3_HIDDEN q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutSettings& o);

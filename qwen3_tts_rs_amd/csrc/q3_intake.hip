@@ -121,6 +121,70 @@ __global__ __launch_bounds__(IN_TILE) void k_intake(const InDesc* __restrict__ d
     d.out[o0 + tid] = y;
 }
 
+// ---- the mark's detector: q3_mark_detect's definition on the clip where the intake left it ----
+constexpr int MD_P = 4096, MD_H = 240;                           // the carrier's period; hop (10 ms)
+constexpr int MD_THREADS = 256;
+constexpr int MD_FOLD_WGS = MD_P / MD_THREADS;                   // 16: a tile of 256 positions of the period each
+constexpr int MD_SHIFTS = 16, MD_CORR_WGS = MD_P / MD_SHIFTS;    // 16 shifts a workgroup, 256 workgroups: one per CU
+
+// F[m] = sum over k of z[k P + m] / max(r_h, 1e-4), r_h the root mean square of the sample's own hop, in ascending k. Per k a
+// workgroup's 256 samples lie in at most three hops: waves 0..2 take one each — lane q adds the squares of samples q, q + 64, ... of
+// the hop in ascending order (a non-finite one as 0, zeros behind the clip), the fold is the wave reduction d = 32 .. 1 — and post the
+// divisor; then every thread adds its sample's quotient. Every sum has one fixed order.
+// Bounds: z is read at indices below n alone; rh at (k P + m) / 240 - (k P + m0) / 240 <= (m0 + 255) / 240 - m0 / 240 <= 2.
+__global__ __launch_bounds__(MD_THREADS) void k_mark_fold(const float* __restrict__ z, long long n, float* __restrict__ F) {
+    __shared__ float rh[3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m0 = blockIdx.x * MD_THREADS;
+    float acc = 0.0f;
+    for (long long base = m0; base < n; base += MD_P) {          // (uniform over the block)
+        const long long h_lo = base / MD_H;
+        const long long h = h_lo + wave;
+        if (wave < 3 && h * MD_H < n) {
+            float part = 0.0f;
+            for (int j = lane; j < MD_H; j += 64) {
+                const long long i = h * MD_H + j;
+                float v = i < n ? z[i] : 0.0f;
+                v = __builtin_isfinite(v) ? v : 0.0f;
+                part = q3::add_rn(part, q3::mul_rn(v, v));
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) part = q3::add_rn(part, __shfl_down(part, o));
+            if (lane == 0) rh[wave] = fmaxf(sqrtf(q3::mul_rn(part, (float)(1.0 / 240.0))), 1e-4f);
+        }
+        __syncthreads();
+        const long long i = base + tid;
+        if (i < n) {
+            float v = z[i];
+            v = __builtin_isfinite(v) ? v : 0.0f;
+            acc = q3::add_rn(acc, __fdiv_rn(v, rh[(int)(i / MD_H - h_lo)]));
+        }
+        __syncthreads();                                         // (rh is written again)
+    }
+    F[m0 + tid] = acc;
+}
+
+// rho[d] = sum over m of F[m] c[(m + d) mod P]: a workgroup stages F and the carrier in LDS (32 KB) and takes 16 consecutive
+// shifts; thread (s, t) = (tid >> 4, tid & 15) sums m = t, t + 16, ... of shift d0 + s in four interleaved sums, joined pairwise, and
+// the 16 threads of a shift meet by four butterfly steps: one fixed order per shift. The 64 lanes of a wave read F at 16 consecutive
+// words (each by four lanes: a broadcast) and the carrier at 19 consecutive words: no pass meets a bank twice.
+__global__ __launch_bounds__(MD_THREADS) void k_mark_corr(const float* __restrict__ F, const float* __restrict__ c, float* __restrict__ rho) {
+    __shared__ float Fs[MD_P], cs[MD_P];
+    const int tid = threadIdx.x, t = tid & 15, d = blockIdx.x * MD_SHIFTS + (tid >> 4);
+    for (int i = tid; i < MD_P; i += MD_THREADS) { Fs[i] = F[i]; cs[i] = c[i]; }
+    __syncthreads();
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+#pragma unroll 4
+    for (int m = t; m < MD_P; m += 64) {
+        a0 = fmaf(Fs[m], cs[(m + d) & (MD_P - 1)], a0); a1 = fmaf(Fs[m + 16], cs[(m + 16 + d) & (MD_P - 1)], a1);
+        a2 = fmaf(Fs[m + 32], cs[(m + 32 + d) & (MD_P - 1)], a2); a3 = fmaf(Fs[m + 48], cs[(m + 48 + d) & (MD_P - 1)], a3);
+    }
+    float a = q3::add_rn(q3::add_rn(a0, a1), q3::add_rn(a2, a3));
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) a = q3::add_rn(a, __shfl_xor(a, o));
+    if (t == 0) rho[d] = a;
+}
+
 struct InRate { int L = 1, M = 1; };
 bool in_rate_of(uint32_t sr, InRate* r) {
     if (sr < IN_RATE_MIN || sr > IN_RATE_MAX) return false;
@@ -332,6 +396,37 @@ extern "C" q3_status q3_ref_audio_read(q3_ref_audio* r, float* host, int64_t cap
     HIPC(hipMemcpyAsync(host, r->dev, (size_t)r->n * 4, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     return Q3_OK;
+}
+
+// The detector on the device: the carrier up, the fold, the 4096 x 4096 correlation, the 16 KB of rho back, a wait; the score and
+// the offset from rho in f64 on the host (mark_score_f32). The scratch block goes back to the device-memory cache.
+extern "C" q3_status q3_ref_audio_mark_score(q3_ref_audio* r, uint64_t key, double* score, int* offset) {
+    const char* who = "q3_ref_audio_mark_score";
+    if (!r || (!score && !offset)) return set_err(Q3_INVALID_ARG, "%s: null argument", who);
+    if (key == 0) return set_err(Q3_INVALID_ARG, "%s: key 0 is off: there is no carrier", who);
+    if (r->n < 2 * (int64_t)MD_P) return set_err(Q3_INVALID_ARG, "%s: clip of %lld samples (at least %d: two periods at 24 kHz)", who, (long long)r->n, 2 * MD_P);
+    std::vector<float> host(2 * (size_t)MD_P);                   // the carrier up, rho back
+    mark_carrier(key, host.data());
+    HIPC(hipSetDevice(r->device));
+    hipStream_t st = nullptr;
+    Q3C(in_stream(r->device, &st));
+    float* dev = nullptr;                                        // c | F | rho
+    q3_relax_capture_mode();
+    HIPC(dev_malloc((void**)&dev, 3 * (size_t)MD_P * 4));
+    auto run = [&]() -> q3_status {
+        HIPC(hipMemcpyAsync(dev, host.data(), (size_t)MD_P * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_mark_fold, dim3(MD_FOLD_WGS), dim3(MD_THREADS), 0, st, (const float*)r->dev, (long long)r->n, dev + MD_P);
+        HIPC(hipGetLastError());
+        hipLaunchKernelGGL(k_mark_corr, dim3(MD_CORR_WGS), dim3(MD_THREADS), 0, st, (const float*)(dev + MD_P), (const float*)dev, dev + 2 * MD_P);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(host.data() + MD_P, dev + 2 * MD_P, (size_t)MD_P * 4, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        return Q3_OK;
+    };
+    const q3_status rs = run();
+    dev_free(dev);
+    Q3C(rs);
+    return mark_score_f32(host.data() + MD_P, score, offset);
 }
 
 extern "C" void q3_ref_audio_free(q3_ref_audio* r) {

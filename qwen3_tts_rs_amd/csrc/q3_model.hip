@@ -38,6 +38,9 @@ static inline uint64_t fnv1a64(const char* s) {
     for (; *s; ++s) { h ^= (unsigned char)*s; h *= 0x100000001b3ULL; }
     return h;
 }
+// the counter hash for the units that derive values from a seed and a name (q3_engine.h)
+uint64_t synth_hash(uint64_t x) { return splitmix64(x); }
+uint64_t synth_name_hash(const char* s) { return fnv1a64(s); }
 extern "C" q3_status q3_synth_fill(uint64_t seed, const char* name, int dtype, float scale, float offset, int64_t n,
                                    void* out_host) {
     if (!name || !out_host || n < 0) return set_err(Q3_INVALID_ARG, "q3_synth_fill: bad argument");

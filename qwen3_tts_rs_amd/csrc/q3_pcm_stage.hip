@@ -1,12 +1,12 @@
 // q3_pcm_stage.hip — the output stage: 24 kHz f32 from the vocoder -> per row a requested sample rate and format, through the
 // steps the row has asked for. (A unit of the engine: q3_engine.h says which holds what.)
 //
-// A row's stream passes a chain of six steps, front to back: silence -> stretcher -> pitch -> loudness -> level -> resampler /
-// format. The last one every row has; each of the others is on for the rows that ask for it, and a row whose step is off is not
+// A row's stream passes a chain of seven steps, front to back: silence -> stretcher -> pitch -> loudness -> mark -> level ->
+// resampler / format. The last one every row has; each of the others is on for the rows that ask for it, and a row whose step is off is not
 // touched by any of it: no launch, no buffer, no descriptor, no allocation. Every step counts the samples that have entered and
 // left it, keeps what the next push still needs on the device in two copies — a push reads one and writes the other, and they are
 // flipped when the push has succeeded: a push that fails or is refused leaves the row exactly where it was — and writes a push's
-// samples into the row's part of a buffer of its own (s, y, v, w, z), which the next step that is on takes as the row's input.
+// samples into the row's part of a buffer of its own (s, y, v, w, m, z), which the next step that is on takes as the row's input.
 // One launch per step serves every row of a push that has the step, a descriptor per row. The host side further down writes the
 // chain once (step_on, step_emitted, step_cap, chain_walk); the count, the plan and the commit of a push are three uses of it.
 //
@@ -36,6 +36,12 @@
 // would bring that loudness to a target, into w. A hop's gain depends on the hops that ended before it alone, so the step holds
 // nothing back: n samples leave for n that enter (a row that only meters hands its input on as it is). The row keeps its filter
 // states, partial sums, last energies and gains in two copies, its block values append-only.
+//
+// 4f. The mark step. k_mark adds a keyed carrier — a period of 4096 samples with unit magnitude and key-derived
+// phases in 500..3000 Hz — under a gain that follows the stream's own level: the root mean square of every 10 ms hop, ramped between
+// the two hops that ended before the sample's hop began, times a strength. Like the loudness step it holds nothing back; the row
+// keeps the partial sums of its open hop and two roots in two copies, and its carrier. It stands in front of the level step, so a
+// ceiling holds behind it. q3_mark_embed is its host twin, q3_mark_detect (and q3_intake.hip's kernels) the detector.
 //
 // 5. The level step. k_level multiplies the stream by a gain and by the mean, over 128 samples, of the minima, over
 // 128 samples, of the reduction each sample needs to stay under a ceiling: a look-ahead peak limiter whose output is a function of
@@ -91,6 +97,14 @@ struct LoDesc {
     long long base;
     int n_new, mode; float T, P, gate, a_lo, a_hi; int pad;
     float coef[10];
+};
+// k_mark: samples base .. base + n_new - 1 of the row's stream into the mark step
+// come from src and leave into y; st_in (null at the row's start) / st_out are the two copies of its small state, c the row's
+// carrier, s its strength
+struct MkDesc {
+    const float* src; float* y; const float* c; const float* st_in; float* st_out;
+    long long base;
+    int n_new; float s;
 };
 // k_level: the row's stream into the level step is tail_in (its last 254
 // samples) below `base`, the n_new samples of src from there, nothing from n_total on; outputs o_base .. o_base + n_z - 1 go to z
@@ -387,6 +401,63 @@ __global__ __launch_bounds__(LD_THREADS) void k_loud(const LoDesc* __restrict__ 
         d.st_out[LD_S_CG] = __int_as_float(cg); d.st_out[LD_S_EST] = __int_as_float(est);
     }
     if (tid < 64) d.st_out[4 + tid] = part;
+}
+
+// ---- the mark step ----
+constexpr int MK_P = 4096, MK_H = 240;                          // the carrier's period; hop (10 ms)
+constexpr int MK_THREADS = 256, MK_G = MK_THREADS / 64;         // hops of a round: one per wave
+constexpr int MK_STATE = 68;                                    // floats a copy of the small state: [partials 64 | r(h-1) r(h-2) | - -]
+constexpr int MK_S_R1 = 64, MK_S_R2 = 65;
+constexpr int MK_STRENGTH_MIN = -4000, MK_STRENGTH_MAX = -1000;
+constexpr int MK_BAND_LO = 500, MK_BAND_HI = 3000;              // Hz
+
+// One workgroup per row; the hops the push touches in rounds of four, one hop per wave. Per round: lane q of a wave adds the squares
+// of samples q, q + 64, ... of its hop that lie in the push (a non-finite one as 0; the hop the push opens in continues the row's
+// partials), the fold is the wave reduction d = 32 .. 1, and lane 0 posts the root of the hop's mean square; then every thread
+// writes samples of the round's hops: the sample plus the carrier under a gain that ramps between the roots of the two hops that
+// ended before the sample's hop began. The hop energies do not depend on each other, so a round needs the two roots before it alone.
+// Bounds: src and y hold n_new floats and i below is in [0, n_new); c holds MK_P floats; st_in / st_out MK_STATE.
+__global__ __launch_bounds__(MK_THREADS) void k_mark(const MkDesc* __restrict__ descs) {
+    __shared__ float rr[2 + MK_G];                               // r(h0 - 2), r(h0 - 1), then the round's own
+    const MkDesc d = descs[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long end = d.base + d.n_new;
+    const long long h_first = d.base / MK_H, h_end = (end + MK_H - 1) / MK_H;
+    float r1 = d.st_in ? d.st_in[MK_S_R1] : 0.0f, r2 = d.st_in ? d.st_in[MK_S_R2] : 0.0f;       // (thread 0's are the row's)
+    if (tid == 0) { rr[0] = r2; rr[1] = r1; }
+    for (long long h0 = h_first; h0 < h_end; h0 += MK_G) {
+        const long long h = h0 + wave;
+        if (h < h_end) {
+            float part = (h == h_first && d.st_in) ? d.st_in[lane] : 0.0f;
+            for (int j = lane; j < MK_H; j += 64) {
+                const long long n = h * MK_H + j;
+                if (n < d.base || n >= end) continue;
+                float v = d.src[n - d.base];
+                v = __builtin_isfinite(v) ? v : 0.0f;
+                part = q3::add_rn(part, q3::mul_rn(v, v));
+            }
+            const bool complete = (h + 1) * MK_H <= end;
+            if (h == h_end - 1) d.st_out[lane] = complete ? 0.0f : part;      // the partials of the hop still open
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) part = q3::add_rn(part, __shfl_down(part, o));
+            if (lane == 0) rr[2 + wave] = complete ? ld_sqrt_rn(q3::mul_rn(part, (float)(1.0 / 240.0))) : 0.0f;
+        }
+        __syncthreads();
+        for (int i = tid; i < MK_G * MK_H; i += MK_THREADS) {
+            const int w = i / MK_H, j = i - w * MK_H;
+            const long long n = (h0 + w) * MK_H + j;
+            if (n < d.base || n >= end) continue;
+            const float ra = rr[w], rb = rr[w + 1];              // r(h - 2), r(h - 1)
+            const float g = q3::add_rn(ra, q3::mul_rn(q3::sub_rn(rb, ra), __fdiv_rn((float)j, (float)MK_H)));
+            d.y[n - d.base] = q3::add_rn(d.src[n - d.base], q3::mul_rn(q3::mul_rn(d.s, g), d.c[n & (MK_P - 1)]));
+        }
+        const float n0 = rr[MK_G], n1 = rr[MK_G + 1];
+        if (tid == 0)
+            for (int w = 0; w < MK_G; ++w) if ((h0 + w + 1) * MK_H <= end) { r2 = r1; r1 = rr[2 + w]; }
+        __syncthreads();
+        if (tid == 0) { rr[0] = n0; rr[1] = n1; }                // (read again behind the next round's barrier)
+    }
+    if (tid == 0) { d.st_out[MK_S_R1] = r1; d.st_out[MK_S_R2] = r2; }
 }
 
 // ---- the time stretcher ----
@@ -907,6 +978,12 @@ struct LoudStep : Totals {                    // DESIGN 4.12c; out == in: the st
     float* state = nullptr; int cur = 0;      // two copies of LD_STATE floats, then the LD_HIST block values (one copy)
     void reset() { in = out = 0; }
 };
+struct MarkStep : Totals {                    // DESIGN 4.12f; key == 0: off; out == in: the step holds nothing back
+    uint64_t key = 0; float s = 0.0f;
+    float* tab = nullptr; uint64_t tab_key = 0;      // the row's carrier (MK_P floats, of key tab_key; 0: none), then two copies of MK_STATE floats
+    int cur = 0;
+    void reset() { in = out = 0; }
+};
 struct LevelStep : Totals {
     bool on = false; float g = 1.0f, c = 1.0f;
     float* tail = nullptr; int cur = 0;       // two copies of LV_TAIL_PITCH floats: the last 254 inputs
@@ -919,20 +996,21 @@ struct ResStep : Totals {                     // the resampler and 
 };
 struct PsRow {
     OutSettings asked;
-    SilStep sil; TempoStep tp; PitchStep pt; LoudStep ld; LevelStep lv; ResStep rs;
+    SilStep sil; TempoStep tp; PitchStep pt; LoudStep ld; MarkStep mk; LevelStep lv; ResStep rs;
     bool ended = false;                       // flushed by a push with `last`: restarted by pcm_stage_apply / reset only
-    void reset() { sil.reset(); tp.reset(); pt.reset(); ld.reset(); lv.reset(); rs.reset(); ended = false; }
+    void reset() { sil.reset(); tp.reset(); pt.reset(); ld.reset(); mk.reset(); lv.reset(); rs.reset(); ended = false; }
 };
 constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
 
 // ---- the chain, written once ----
-enum { ST_SIL, ST_TEMPO, ST_PITCH, ST_LOUD, ST_LEVEL, ST_RES, ST_N };
+enum { ST_SIL, ST_TEMPO, ST_PITCH, ST_LOUD, ST_MARK, ST_LEVEL, ST_RES, ST_N };
 static bool step_on(const PsRow& r, int s) {
     switch (s) {
     case ST_SIL: return r.sil.thr != 0;
     case ST_TEMPO: return r.tp.te != TP_OFF;
     case ST_PITCH: return r.pt.te != r.pt.t;
     case ST_LOUD: return r.ld.mode != Q3_LOUD_OFF;
+    case ST_MARK: return r.mk.key != 0;
     case ST_LEVEL: return r.lv.on;
     default: return true;
     }
@@ -943,6 +1021,7 @@ static const Totals& step_totals(const PsRow& r, int s) {
     case ST_TEMPO: return r.tp;
     case ST_PITCH: return r.pt;
     case ST_LOUD: return r.ld;
+    case ST_MARK: return r.mk;
     case ST_LEVEL: return r.lv;
     default: return r.rs;
     }
@@ -1001,7 +1080,7 @@ static void chain_walk(const PsRow& r, int first, long long n, bool last, SegWal
 struct StepPlan {
     std::vector<SegWalk> seg;
     std::vector<TrDesc> sdesc; std::vector<int> sseg; std::vector<long long> sres;      // the pre-pass: descriptors, their segments, the counters that came back
-    std::vector<TpDesc> tdesc; std::vector<PtDesc> pdesc; std::vector<LoDesc> odesc; std::vector<LvDesc> ldesc;
+    std::vector<TpDesc> tdesc; std::vector<PtDesc> pdesc; std::vector<LoDesc> odesc; std::vector<MkDesc> mdesc; std::vector<LvDesc> ldesc;
     int tiles[ST_N];
 };
 struct q3_pcm_stage {
@@ -1205,7 +1284,7 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
     for (auto& kv : ps->taps) dev_free(kv.second);
     dev_free(ps->tails); dev_free(ps->s_win); dev_free(ps->t_win); dev_free(ps->p_tab);
     for (PsRow& r : ps->rows) {
-        dev_free(r.sil.state); dev_free(r.tp.state); dev_free(r.pt.tail); dev_free(r.ld.state); dev_free(r.lv.tail);
+        dev_free(r.sil.state); dev_free(r.tp.state); dev_free(r.pt.tail); dev_free(r.ld.state); dev_free(r.mk.tab); dev_free(r.lv.tail);
         r.tp.lags[0].release(); r.tp.lags[1].release();
     }
     for (int s = 0; s < ST_N; ++s) { ps->buf[s].release(); ps->desc[s].release(); }
@@ -1389,6 +1468,121 @@ extern "C" q3_status q3_silence_trim(const float* x, size_t n, int threshold_mB,
     return Q3_OK;
 }
 
+// ---- the mark: carrier, host twin of k_mark, detector ----
+static inline float h_sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+static q3_status mark_checked(const char* who, int strength_mB) {
+    if (strength_mB < MK_STRENGTH_MIN || strength_mB > MK_STRENGTH_MAX)
+        return set_err(Q3_INVALID_ARG, "%s: strength %d mB out of range (%d..%d)", who, strength_mB, MK_STRENGTH_MIN, MK_STRENGTH_MAX);
+    return Q3_OK;
+}
+static inline float mark_strength(int strength_mB) { return (float)pow(10.0, (double)strength_mB / 2000.0); }
+
+// Unit magnitude and a key-derived phase in every bin of the period whose frequency lies in the band, zero elsewhere; the inverse
+// real DFT in f64 (the angle of bin k at sample n is 2 pi ((k n) mod P) / P, reduced in integers), scaled to unit RMS, rounded once
+void mark_carrier(uint64_t key, float* c) {
+    const double PI = 3.14159265358979323846;
+    const uint64_t kk = synth_hash(key ^ synth_name_hash("q3.mark.carrier"));
+    const int k_lo = (MK_BAND_LO * MK_P + (int)PS_RATE_IN - 1) / (int)PS_RATE_IN, k_hi = (MK_BAND_HI * MK_P) / (int)PS_RATE_IN;      // 86 .. 512
+    std::vector<double> ct((size_t)MK_P), sn((size_t)MK_P), acc((size_t)MK_P, 0.0);
+    for (int m = 0; m < MK_P; ++m) { const double a = 2.0 * PI * (double)m / (double)MK_P; ct[(size_t)m] = cos(a); sn[(size_t)m] = sin(a); }
+    for (int k = k_lo; k <= k_hi; ++k) {
+        const uint64_t z = synth_hash(kk + (uint64_t)k * 0x9E3779B97F4A7C15ULL);
+        const double phi = 2.0 * PI * (double)(z >> 11) * (1.0 / 9007199254740992.0);
+        const double cp = cos(phi), sp = sin(phi);
+        for (int n = 0; n < MK_P; ++n) { const size_t m = (size_t)((k * n) & (MK_P - 1)); acc[(size_t)n] += ct[m] * cp - sn[m] * sp; }
+    }
+    double ss = 0.0;
+    for (int n = 0; n < MK_P; ++n) ss += acc[(size_t)n] * acc[(size_t)n];
+    const double inv = 1.0 / sqrt(ss / (double)MK_P);
+    for (int n = 0; n < MK_P; ++n) c[n] = (float)(acc[(size_t)n] * inv);
+}
+
+extern "C" q3_status q3_mark_carrier(uint64_t key, float* c) {
+    if (key == 0) return set_err(Q3_INVALID_ARG, "q3_mark_carrier: key 0 is off: there is no carrier");
+    if (!c) return set_err(Q3_INVALID_ARG, "q3_mark_carrier: null argument");
+    mark_carrier(key, c);
+    return Q3_OK;
+}
+
+// the whole definition for one clip on the CPU: the same f32 operations in the same order as k_mark
+extern "C" q3_status q3_mark_embed(const float* x, size_t n, uint64_t key, int strength_mB, float* y) {
+    if (key == 0) return set_err(Q3_INVALID_ARG, "q3_mark_embed: key 0 is off: nothing to do");
+    Q3C(mark_checked("q3_mark_embed", strength_mB));
+    if (n > 0 && (!x || !y)) return set_err(Q3_INVALID_ARG, "q3_mark_embed: null argument");
+    if (n > ((size_t)1 << 40)) return set_err(Q3_INVALID_ARG, "q3_mark_embed: n above 2^40");
+    std::vector<float> c((size_t)MK_P);
+    mark_carrier(key, c.data());
+    const float s = mark_strength(strength_mB);
+    float ramp[MK_H];
+    for (int j = 0; j < MK_H; ++j) ramp[j] = (float)((double)j / 240.0);
+    float r1 = 0.0f, r2 = 0.0f;
+    for (size_t h0 = 0; h0 < n; h0 += MK_H) {
+        const size_t cnt = std::min((size_t)MK_H, n - h0);
+        float p[64];
+        for (int q = 0; q < 64; ++q) p[q] = 0.0f;
+        const float dg = h_sub_rn(r1, r2);
+        for (size_t j = 0; j < cnt; ++j) {
+            const float xv = x[h0 + j];
+            const float v = std::isfinite(xv) ? xv : 0.0f;
+            p[j & 63] = h_add_rn(p[j & 63], h_mul_rn(v, v));
+            const float g = h_add_rn(r2, h_mul_rn(dg, ramp[j]));
+            y[h0 + j] = h_add_rn(xv, h_mul_rn(h_mul_rn(s, g), c[(h0 + j) & (size_t)(MK_P - 1)]));
+        }
+        if (cnt < (size_t)MK_H) break;
+        for (int d = 32; d >= 1; d >>= 1) for (int q = 0; q < d; ++q) p[q] = h_add_rn(p[q], p[q + d]);
+        r2 = r1; r1 = sqrtf(h_mul_rn(p[0], (float)(1.0 / 240.0)));
+    }
+    return Q3_OK;
+}
+
+// rho[d] = sum_m F[m] c[(m + d) mod P] -> (max - mean) / std over the shifts and the shift of the maximum (the first of equals)
+static void mark_score_of(const double* rho, double* score, int* offset) {
+    double mean = 0.0, var = 0.0; int arg = 0;
+    for (int d = 0; d < MK_P; ++d) { mean += rho[d]; if (rho[d] > rho[arg]) arg = d; }
+    mean /= (double)MK_P;
+    for (int d = 0; d < MK_P; ++d) var += (rho[d] - mean) * (rho[d] - mean);
+    const double sd = sqrt(var / (double)MK_P);
+    if (score) *score = sd > 0.0 ? (rho[arg] - mean) / sd : 0.0;
+    if (offset) *offset = arg;
+}
+q3_status mark_score_f32(const float* rho, double* score, int* offset) {
+    std::vector<double> r((size_t)MK_P);
+    for (int d = 0; d < MK_P; ++d) r[(size_t)d] = (double)rho[d];
+    mark_score_of(r.data(), score, offset);
+    return Q3_OK;
+}
+
+extern "C" double q3_mark_score_detect(void) { return Q3_MARK_SCORE_DETECT; }
+
+extern "C" q3_status q3_mark_detect(const float* z, size_t n, uint64_t key, double* score, int* offset) {
+    if (key == 0) return set_err(Q3_INVALID_ARG, "q3_mark_detect: key 0 is off: there is no carrier");
+    if (!z || (!score && !offset)) return set_err(Q3_INVALID_ARG, "q3_mark_detect: null argument");
+    if (n < 2 * (size_t)MK_P) return set_err(Q3_INVALID_ARG, "q3_mark_detect: clip of %zu samples (at least %d: two periods at 24 kHz)", n, 2 * MK_P);
+    if (n > ((size_t)1 << 40)) return set_err(Q3_INVALID_ARG, "q3_mark_detect: n above 2^40");
+    std::vector<float> c((size_t)MK_P);
+    mark_carrier(key, c.data());
+    std::vector<double> F((size_t)MK_P, 0.0), c2(2 * (size_t)MK_P), rho((size_t)MK_P);
+    for (size_t h0 = 0; h0 < n; h0 += MK_H) {                      // (the clip's last, partial hop against zeros)
+        const size_t cnt = std::min((size_t)MK_H, n - h0);
+        double e = 0.0;
+        for (size_t j = 0; j < cnt; ++j) { const double v = std::isfinite(z[h0 + j]) ? (double)z[h0 + j] : 0.0; e += v * v; }
+        const double r = std::max(sqrt(e / 240.0), 1e-4);
+        for (size_t j = 0; j < cnt; ++j) { const double v = std::isfinite(z[h0 + j]) ? (double)z[h0 + j] : 0.0; F[(h0 + j) & (size_t)(MK_P - 1)] += v / r; }
+    }
+    for (int m = 0; m < 2 * MK_P; ++m) c2[(size_t)m] = (double)c[(size_t)(m & (MK_P - 1))];
+    for (int d = 0; d < MK_P; ++d) {
+        double a = 0.0;
+        const double* cd = c2.data() + d;
+        for (int m = 0; m < MK_P; ++m) a += F[(size_t)m] * cd[m];
+        rho[(size_t)d] = a;
+    }
+    mark_score_of(rho.data(), score, offset);
+    return Q3_OK;
+}
+
 // ---- settings (Settings) ----
 // The checked edits: every range of an output setting, and the rule that ties a tempo to a pitch, is in the *_checked functions
 // above and reaches every layer through these.
@@ -1422,6 +1616,11 @@ q3_status out_set_loudness(const char* who, OutSettings& o, int mode, int target
 q3_status out_set_silence(const char* who, OutSettings& o, int threshold_mB, int edge_ms, int pause_ms) {
     Q3C(silence_checked(who, threshold_mB, edge_ms, pause_ms));
     o.sil_mB = threshold_mB; o.edge_ms = edge_ms; o.pause_ms = pause_ms;
+    return Q3_OK;
+}
+q3_status out_set_mark(const char* who, OutSettings& o, uint64_t key, int strength_mB) {
+    Q3C(mark_checked(who, strength_mB));
+    o.mark_key = key; o.mark_mB = strength_mB;
     return Q3_OK;
 }
 
@@ -1478,6 +1677,20 @@ q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutS
         }
         Q3C(row_state(ps, &r.ld.state, (2 * (size_t)LD_STATE + LD_HIST) * 4, who, "state", row));
     }
+    if (o.mark_key != 0) {
+        // the row's table and state, then its carrier where the key is new to the table (no push is in flight: each ends with a wait).
+        // An upload that fails leaves the table without a carrier and the row with its mark step off, and otherwise untouched.
+        Q3C(mark_checked(who, o.mark_mB));
+        Q3C(row_state(ps, &r.mk.tab, ((size_t)MK_P + 2 * (size_t)MK_STATE) * 4, who, "carrier", row));
+        if (r.mk.tab_key != o.mark_key) {
+            std::vector<float> c((size_t)MK_P);
+            mark_carrier(o.mark_key, c.data());
+            r.mk.tab_key = 0;
+            const hipError_t e = q3_hipMemcpy(r.mk.tab, c.data(), (size_t)MK_P * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) { r.mk.key = 0; r.asked.mark_key = 0; return set_err(Q3_HIP_ERROR, "%s: carrier upload: %s", who, hipGetErrorString(e)); }
+            r.mk.tab_key = o.mark_key;
+        }
+    }
     const bool level = o.gain_mB != 0 || o.ceil_mB != 0;
     if (level) Q3C(row_state(ps, &r.lv.tail, 2 * (size_t)LV_TAIL_PITCH * 4, who, "state", row));
     const TrSet ts = tr_set(o.edge_ms, o.pause_ms);
@@ -1502,6 +1715,7 @@ q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutS
     (void)q3_pcm_stage_level_coeffs(o.gain_mB, o.ceil_mB, &r.lv.g, &r.lv.c);
     r.ld.mode = o.loud;
     (void)q3_pcm_stage_loudness_consts(o.target_mB, o.prior_mB, &r.ld.T, &r.ld.P, &r.ld.gate, &r.ld.lo, &r.ld.hi);
+    r.mk.key = o.mark_key; r.mk.s = mark_strength(o.mark_mB);
     r.sil.thr = o.sil_mB; r.sil.set = ts; r.sil.theta = tr_theta(o.sil_mB);
     if (o.sil_mB != 0) r.sil.copy = sil_copy;
     pcm_stage_reset(ps, row);
@@ -1530,6 +1744,9 @@ extern "C" q3_status q3_pcm_stage_set_level(q3_pcm_stage* ps, int row, int gain_
 }
 extern "C" q3_status q3_pcm_stage_set_loudness(q3_pcm_stage* ps, int row, int mode, int target_mB, int prior_mB) {
     return stage_set(ps, row, "q3_pcm_stage_set_loudness", [&](const char* who, OutSettings& o) { return out_set_loudness(who, o, mode, target_mB, prior_mB); });
+}
+extern "C" q3_status q3_pcm_stage_set_mark(q3_pcm_stage* ps, int row, uint64_t key, int strength_mB) {
+    return stage_set(ps, row, "q3_pcm_stage_set_mark", [&](const char* who, OutSettings& o) { return out_set_mark(who, o, key, strength_mB); });
 }
 extern "C" q3_status q3_pcm_stage_set_silence(q3_pcm_stage* ps, int row, int threshold_mB, int edge_ms, int pause_ms) {
     return stage_set(ps, row, "q3_pcm_stage_set_silence", [&](const char* who, OutSettings& o) { return out_set_silence(who, o, threshold_mB, edge_ms, pause_ms); });
@@ -1636,6 +1853,7 @@ static q3_status step_ready(const q3_pcm_stage* ps, const PsRow& r, int row, int
     case ST_TEMPO: if (!r.tp.state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tempo and no state", row); break;
     case ST_PITCH: if (!r.pt.tail || !ps->p_tab) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a pitch and no state", row); break;
     case ST_LOUD: if (!r.ld.state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a loudness step and no state", row); break;
+    case ST_MARK: if (!r.mk.tab || r.mk.tab_key != r.mk.key) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a mark and no carrier", row); break;
     case ST_LEVEL: if (!r.lv.tail) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a level and no state", row); break;
     default: break;
     }
@@ -1688,6 +1906,18 @@ static q3_status step_fill(q3_pcm_stage* ps, PsPlan& plan, const PsSeg& sg, cons
         if (!dst) return Q3_OK;
         break;
     }
+    case ST_MARK: {
+        if (n_in > 0) {                                            // (nothing passes: no descriptor, no flip)
+            const MarkStep& mk = r.mk;
+            float* st = mk.tab + MK_P;
+            MkDesc k{};
+            k.src = src; k.y = (float*)dst; k.c = mk.tab;
+            k.st_in = mk.in > 0 ? st + (size_t)mk.cur * MK_STATE : nullptr; k.st_out = st + (size_t)(mk.cur ^ 1) * MK_STATE;
+            k.base = mk.in; k.n_new = n_in; k.s = mk.s;
+            p.mdesc.push_back(k);
+        }
+        break;
+    }
     case ST_LEVEL: {
         const LevelStep& lv = r.lv;
         LvDesc l{};
@@ -1720,7 +1950,7 @@ static q3_status step_fill(q3_pcm_stage* ps, PsPlan& plan, const PsSeg& sg, cons
 static q3_status chain_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan) {
     StepPlan& p = ps->plan;
     plan.desc.clear(); plan.off.assign(segs.size(), 0); plan.count.assign(segs.size(), 0); plan.bytes = 0;
-    p.tdesc.clear(); p.pdesc.clear(); p.odesc.clear(); p.ldesc.clear();
+    p.tdesc.clear(); p.pdesc.clear(); p.odesc.clear(); p.mdesc.clear(); p.ldesc.clear();
     size_t floats[ST_N] = {0};
     for (int s = 0; s < ST_N; ++s) p.tiles[s] = 1;
     for (size_t i = 0; i < segs.size(); ++i) {
@@ -1761,6 +1991,7 @@ static hipError_t chain_launch(q3_pcm_stage* ps, const PsPlan& plan, const PsDes
     hipError_t e = step_launch<TpDesc, k_tempo>(ps->desc[ST_TEMPO], p.tdesc, dim3((unsigned)p.tdesc.size()), dim3(TP_THREADS), st);
     if (e == hipSuccess) e = step_launch<PtDesc, k_pitch>(ps->desc[ST_PITCH], p.pdesc, dim3((unsigned)p.tiles[ST_PITCH], (unsigned)p.pdesc.size()), dim3(PS_TILE), st);
     if (e == hipSuccess) e = step_launch<LoDesc, k_loud>(ps->desc[ST_LOUD], p.odesc, dim3((unsigned)p.odesc.size()), dim3(LD_THREADS), st);
+    if (e == hipSuccess) e = step_launch<MkDesc, k_mark>(ps->desc[ST_MARK], p.mdesc, dim3((unsigned)p.mdesc.size()), dim3(MK_THREADS), st);
     if (e == hipSuccess) e = step_launch<LvDesc, k_level>(ps->desc[ST_LEVEL], p.ldesc, dim3((unsigned)p.tiles[ST_LEVEL], (unsigned)p.ldesc.size()), dim3(PS_TILE), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_pcm_stage, dim3((unsigned)p.tiles[ST_RES], (unsigned)plan.desc.size()), dim3(PS_TILE), 0, st, desc_dev);
@@ -1782,6 +2013,7 @@ static void chain_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs) {
         }
         if (step_on(r, ST_PITCH)) { add(r.pt, ST_PITCH); if (!sg.last) r.pt.cur ^= 1; }
         if (step_on(r, ST_LOUD) && w.n_in[ST_LOUD] > 0) { add(r.ld, ST_LOUD); r.ld.cur ^= 1; }
+        if (step_on(r, ST_MARK) && w.n_in[ST_MARK] > 0) { add(r.mk, ST_MARK); r.mk.cur ^= 1; }
         if (step_on(r, ST_LEVEL)) { add(r.lv, ST_LEVEL); if (!sg.last) r.lv.cur ^= 1; }
         add(r.rs, ST_RES);
         if (r.rs.taps) { r.rs.cur ^= 1; r.rs.fresh = false; }

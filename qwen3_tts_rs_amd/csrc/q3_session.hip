@@ -2045,6 +2045,9 @@ extern "C" q3_status q3_session_set_silence(q3_session* s, int b, int threshold_
     return session_set_rows(s, b, "q3_session_set_silence", "silence step",
                             [&](const char* who, OutSettings& o) { return out_set_silence(who, o, threshold_mB, edge_ms, pause_ms); });
 }
+extern "C" q3_status q3_session_set_mark(q3_session* s, int b, uint64_t key, int strength_mB) {
+    return session_set_rows(s, b, "q3_session_set_mark", "mark", [&](const char* who, OutSettings& o) { return out_set_mark(who, o, key, strength_mB); });
+}
 extern "C" q3_status q3_session_silence(q3_session* s, int b, int64_t* n_in, int64_t* n_out, int64_t* lead_cut, int64_t* pause_cut, int64_t* trail_cut) {
     if (!s) return set_err(Q3_INVALID_ARG, "q3_session_silence: null session");
     if (b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "q3_session_silence: row %d out of range (%d rows)", b, s->B);

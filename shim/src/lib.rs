@@ -156,6 +156,15 @@ pub mod ffi {
         pub fn q3_session_silence(s: *mut c_void, b: i32, n_in: *mut i64, n_out: *mut i64, lead_cut: *mut i64, pause_cut: *mut i64, trail_cut: *mut i64) -> i32;
         pub fn q3_batcher_ticket_silence(b: *mut c_void, ticket: i64, threshold_mb: i32, edge_ms: i32, pause_ms: i32) -> i32;
         pub fn q3_batcher_ticket_silence_read(b: *mut c_void, ticket: i64, n_in: *mut i64, n_out: *mut i64, lead_cut: *mut i64, pause_cut: *mut i64, trail_cut: *mut i64) -> i32;
+        // the output stage's keyed watermark: a chain step between loudness and level; key 0 = off; and its detector
+        pub fn q3_pcm_stage_set_mark(ps: *mut c_void, row: i32, key: u64, strength_mb: i32) -> i32;
+        pub fn q3_mark_carrier(key: u64, c: *mut f32) -> i32;
+        pub fn q3_mark_embed(x: *const f32, n: usize, key: u64, strength_mb: i32, y: *mut f32) -> i32;
+        pub fn q3_mark_score_detect() -> f64;
+        pub fn q3_mark_detect(z: *const f32, n: usize, key: u64, score: *mut f64, offset: *mut i32) -> i32;
+        pub fn q3_ref_audio_mark_score(r: *mut c_void, key: u64, score: *mut f64, offset: *mut i32) -> i32;
+        pub fn q3_session_set_mark(s: *mut c_void, b: i32, key: u64, strength_mb: i32) -> i32;
+        pub fn q3_batcher_ticket_mark(b: *mut c_void, ticket: i64, key: u64, strength_mb: i32) -> i32;
     }
 }
 use ffi::*;
