@@ -303,11 +303,9 @@ static q3_status decoder_run(q3_batcher* b, BatTicket& t) {
     const q3_model* m = b->m;
     HIPC(hipSetDevice(m->device));
     if (!d.stream) HIPC(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-    const int n = t.n_frames;
-    Q3C(codec_reserve(m, d.ws, n));
-    HIPC(hipMemcpyAsync(d.ws.frames, t.codes.data(), (size_t)n * 16 * 4, hipMemcpyHostToDevice, d.stream));
-    Q3C(codec_decode_dev(m, d.ws, n, d.stream, nullptr));
-    HIPC(hipMemcpyAsync(t.pcm.data(), d.ws.pcm, t.pcm.size() * 4, hipMemcpyDeviceToHost, d.stream));
+    VocodePcm pcm;
+    Q3C(vocode_enqueue(m, d.ws, d.stream, VocodeSrc{nullptr, 0, t.codes.data(), true}, 0, t.n_frames, 0, 0, &pcm));
+    Q3C(vocode_copy_out(pcm, t.pcm.data(), t.pcm.size(), nullptr, d.stream));
     HIPC(hipStreamSynchronize(d.stream));
     return Q3_OK;
 }
@@ -1079,22 +1077,18 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
 }
 
 // the samples of a ticket's host codes on the session's stream and workspace, as q3_session_decode gives them for a whole row:
-// an ICL ticket's reference frames are prepended and their share of the samples cut (lib.rs:1022-1041)
+// an ICL ticket's reference frames go in front (vocode_enqueue cuts their samples)
 static q3_status decode_host_codes(q3_batcher* b, BatTicket& t) {
-    q3_session* s = b->s; const q3_model* m = b->m;
-    HIPC(hipSetDevice(m->device));
+    q3_session* s = b->s;
+    HIPC(hipSetDevice(b->m->device));
     HIPC(sync_frames(s));
-    const int spf = samples_per_frame(m->cfg), n = t.n_frames;
-    const int n_ref = t.req.r.mode == Q3_MODE_VOICE_CLONE ? (int)(t.req.ref_codes.size() / 16) : 0, total = n_ref + n;
-    const size_t all = (size_t)total * spf, cut = n_ref > 0 ? (size_t)n_ref * all / (size_t)total : 0;
-    Q3C(codec_reserve(m, s->cws, total));
-    if (n_ref > 0) HIPC(hipMemcpyAsync(s->cws.frames, t.req.ref_codes.data(), (size_t)n_ref * 64, hipMemcpyHostToDevice, s->stream));
-    HIPC(hipMemcpyAsync(s->cws.frames + (size_t)n_ref * 16, t.codes.data(), (size_t)n * 64, hipMemcpyHostToDevice, s->stream));
-    Q3C(codec_decode_dev(m, s->cws, total, s->stream, nullptr));
+    const bool icl = t.req.r.mode == Q3_MODE_VOICE_CLONE && !t.req.ref_codes.empty();
+    VocodePcm pcm;
+    Q3C(vocode_enqueue(b->m, s->cws, s->stream, VocodeSrc{icl ? t.req.ref_codes.data() : nullptr, (int)(t.req.ref_codes.size() / 16), t.codes.data(), true},
+                       0, t.n_frames, 0, 0, &pcm));
     HIPC(sync_frames(s));
-    t.pcm.resize(all - cut);
-    HIPC(q3_hipMemcpy(t.pcm.data(), s->cws.pcm + cut, (all - cut) * 4, hipMemcpyDeviceToHost));
-    return Q3_OK;
+    t.pcm.resize(pcm.n);
+    return vocode_copy_out(pcm, t.pcm.data(), t.pcm.size(), nullptr, nullptr);
 }
 // A ticket whose client went away gives its place back. Synchronous: between two steps nothing of the session is in flight.
 // Queued: it leaves the queue (a side session staged for it is dropped with its pages). Running: its row is collected with the

@@ -340,6 +340,33 @@ q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st
     return codec_stack_dev(m, ws, cur, L, st, taps, scope);
 }
 
+// How a row's frames become samples: the ONE range decode under every entry that vocodes (q3_session_run / _decode / _next_chunk*,
+// the batcher's worker and its cancel of a parked ticket, q3_decode_codes). The workspace gets [prefix ; codes[0, e)], the front
+// runs over all of it, the convolutional stack from frame c0 of the row, and `out` names the samples of the row's frames [a, e).
+// Exact for c0 = 0 and for c0 <= a - CODEC_CTX_FRAMES (vocode_ctx_start; see codec_decode_dev). Everything is enqueued on `st`
+// and nothing is waited for — but a workspace that has to grow synchronises the device, so a caller beside running work presizes.
+int vocode_ctx_start(int a) { return a > CODEC_CTX_FRAMES ? a - CODEC_CTX_FRAMES : 0; }
+q3_status vocode_enqueue(const q3_model* m, CodecWS& ws, hipStream_t st, const VocodeSrc& src, int a, int e, int c0, int resident, VocodePcm* out) {
+    const int P = src.prefix_host ? src.n_prefix : 0, T = P + e, spf = samples_per_frame(m->cfg);
+    const int start = c0 > 0 ? P + c0 : 0;                // of the stack, among the workspace's frames: a prefix is only cut whole
+    Q3C(codec_reserve(m, ws, T - start, T));
+    if (P > 0) HIPC(hipMemcpyAsync(ws.frames, src.prefix_host, (size_t)P * 16 * 4, hipMemcpyHostToDevice, st));
+    if (e > 0) HIPC(hipMemcpyAsync(ws.frames + (size_t)P * 16, src.codes, (size_t)e * 16 * 4, src.codes_on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    Q3C(codec_decode_dev(m, ws, T, st, nullptr, start, resident));
+    *out = {ws.pcm + (size_t)(P + a - start) * spf, (size_t)(e - a) * spf};
+    return Q3_OK;
+}
+// the caller's half: the count, and the samples where a buffer was given — after the caller's own wait (st null: a synchronous
+// copy), or behind the decode on its stream `st`
+q3_status vocode_copy_out(const VocodePcm& pcm, float* host, size_t cap, size_t* n, hipStream_t st) {
+    if (n) *n = pcm.n;
+    if (!host) return Q3_OK;
+    if (cap < pcm.n) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
+    if (st) HIPC(hipMemcpyAsync(host, pcm.dev, pcm.n * 4, hipMemcpyDeviceToHost, st));
+    else HIPC(q3_hipMemcpy(host, pcm.dev, pcm.n * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
 extern "C" q3_status q3_decode_codes(q3_model* m, const uint32_t* frames_host, int n_frames, float* pcm_host, float** taps_host) {
     if (!m || !m->finalized) return set_err(Q3_INVALID_ARG, "model not finalized");
     if (n_frames < 0 || (n_frames > 0 && (!frames_host || !pcm_host))) return set_err(Q3_INVALID_ARG, "q3_decode_codes: bad argument");
@@ -350,17 +377,23 @@ extern "C" q3_status q3_decode_codes(q3_model* m, const uint32_t* frames_host, i
                 return set_err(Q3_INVALID_ARG, "code %u out of range for codebook %d (frame %d)", frames_host[(size_t)f * 16 + g], g, f);
     HIPC(hipSetDevice(m->device));
     CodecWS ws;
-    q3_status st = codec_reserve(m, ws, n_frames);
-    if (st == Q3_OK) {
-        hipError_t e = q3_hipMemcpy(ws.frames, frames_host, (size_t)n_frames * 16 * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) st = set_err(Q3_HIP_ERROR, "hipMemcpy frames: %s", hipGetErrorString(e));
+    VocodePcm pcm{nullptr, 0};
+    q3_status st;
+    if (!taps_host) st = vocode_enqueue(m, ws, 0, VocodeSrc{nullptr, 0, frames_host, true}, 0, n_frames, 0, 0, &pcm);
+    else {                                                 // the range decode takes no taps: the pipeline itself
+        st = codec_reserve(m, ws, n_frames);
+        if (st == Q3_OK) {
+            hipError_t e = q3_hipMemcpy(ws.frames, frames_host, (size_t)n_frames * 16 * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) st = set_err(Q3_HIP_ERROR, "hipMemcpy frames: %s", hipGetErrorString(e));
+        }
+        if (st == Q3_OK) st = codec_decode_dev(m, ws, n_frames, 0, taps_host);
+        pcm = {ws.pcm, (size_t)n_frames * samples_per_frame(m->cfg)};
     }
-    if (st == Q3_OK) st = codec_decode_dev(m, ws, n_frames, 0, taps_host);
     if (st == Q3_OK) {
-        hipError_t e = q3_hipDeviceSynchronize();
-        if (e == hipSuccess) e = q3_hipMemcpy(pcm_host, ws.pcm, (size_t)n_frames * samples_per_frame(m->cfg) * 4, hipMemcpyDeviceToHost);
+        const hipError_t e = q3_hipDeviceSynchronize();
         if (e != hipSuccess) st = set_err(Q3_HIP_ERROR, "decode: %s", hipGetErrorString(e));
     }
+    if (st == Q3_OK) st = vocode_copy_out(pcm, pcm_host, pcm.n, nullptr, nullptr);
     ws.release();
     return st;
 }

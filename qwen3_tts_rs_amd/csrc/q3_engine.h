@@ -540,6 +540,15 @@ Q3_HIDDEN int samples_per_frame(const q3_config& c);
 // resident: residency cap of this decode's matrix-core launches (ConvArgs::resident): 0 = none; n >= 1 = at most n workgroups of a
 // launch per CU — for a decode that runs beside the frame loop (q3_session_run) and must leave every CU room for a frame workgroup
 Q3_HIDDEN q3_status codec_decode_dev(const q3_model* m, CodecWS& ws, int T, hipStream_t st, float** taps, int c0 = 0, int resident = 0);
+// The range decode every vocoding entry goes through: frames [a, e) of one row, the convolutional stack started at frame c0
+// (0, or vocode_ctx_start(a) = max(0, a - CODEC_CTX_FRAMES): the one statement of the rule). Enqueued on st, waits for nothing.
+struct VocodeSrc { const uint32_t* prefix_host; int n_prefix;      // frames in front of the row's own (ICL reference frames), or none
+                   const uint32_t* codes; bool codes_on_host; };   // the row's frames [0, e), from its first
+struct VocodePcm { const float* dev; size_t n; };                  // in the workspace; valid once st has drained
+Q3_HIDDEN int vocode_ctx_start(int a);
+Q3_HIDDEN q3_status vocode_enqueue(const q3_model* m, CodecWS& ws, hipStream_t st, const VocodeSrc& src, int a, int e, int c0, int resident, VocodePcm* out);
+// n: the count; host: the samples, "pcm buffer too small" below pcm.n. st null: a synchronous copy (after the caller's wait)
+Q3_HIDDEN q3_status vocode_copy_out(const VocodePcm& pcm, float* host, size_t cap, size_t* n, hipStream_t st);
 // the stages of codec_decode_dev, for the codec stream (q3_codec_stream.hip). A CodecScope must be alive on the calling thread
 // while they run: it names the model (packed weights), the bf16 planes (q3_model_set_codec_planes) and the residency cap of their launches.
 struct Q3_HIDDEN CodecScope { int planes, resident; explicit CodecScope(const q3_model* m, int resident = 0); ~CodecScope(); CodecScope(const CodecScope&) = delete; };

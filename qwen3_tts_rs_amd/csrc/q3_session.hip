@@ -1916,45 +1916,32 @@ static ChunkCut chunk_cut(const q3_session* s, int b) {
     if (a < 0 || held) a = 0;
     return {a, held, !held && (a <= 0 || (q.done && q.stream_pos + a >= q.n_frames))};
 }
-// Vocode: samples on the device (the session's codec workspace) once the stream they were enqueued on has drained
-struct ChunkPcm { const float* dev; size_t n; };
+// Vocode: the one range decode (vocode_enqueue, q3_codec_run.hip). A row's frames as it takes them: its codes on the device from frame f0; with_ref: behind the reference
+// frames of an ICL row that was prefilled, from the host copy (a row swapped in by q3_session_replace brings its own) — their
+// samples are cut (lib.rs:1022-1041)
+static VocodeSrc row_src(const q3_session* s, int b, int f0 = 0, bool with_ref = false) {
+    const SeqInfo& q = s->seq[(size_t)b];
+    const bool ref = with_ref && s->prefilled && !q.ref_codes.empty();
+    return {ref ? q.ref_codes.data() : nullptr, ref ? (int)(q.ref_codes.size() / 16) : 0, s->codes + ((size_t)b * s->max_frames + f0) * 16, false};
+}
 // context-free: frames [f0, f0 + T) of row b decoded as an utterance of their own (the reference's per-chunk decode, lib.rs:1755-1758)
-static q3_status range_vocode_enqueue(q3_session* s, int b, int f0, int T, hipStream_t st, ChunkPcm* pcm) {
-    Q3C(codec_reserve(s->m, s->cws, T));
-    HIPC(hipMemcpyAsync(s->cws.frames, s->codes + ((size_t)b * s->max_frames + f0) * 16, (size_t)T * 16 * 4, hipMemcpyDeviceToDevice, st));
-    Q3C(codec_decode_dev(s->m, s->cws, T, st, nullptr));
-    *pcm = {s->cws.pcm, (size_t)T * samples_per_frame(s->m->cfg)};
-    return Q3_OK;
+static q3_status range_vocode_enqueue(q3_session* s, int b, int f0, int T, hipStream_t st, VocodePcm* pcm) {
+    return vocode_enqueue(s->m, s->cws, st, row_src(s, b, f0), 0, T, 0, 0, pcm);
 }
 // frames [stream_pos, stream_pos + avail) of row b in the session's stream mode, enqueued on st; nothing is waited for
-static q3_status chunk_vocode_enqueue(q3_session* s, int b, int avail, hipStream_t st, ChunkPcm* pcm) {
+static q3_status chunk_vocode_enqueue(q3_session* s, int b, int avail, hipStream_t st, VocodePcm* pcm) {
     const SeqInfo& q = s->seq[(size_t)b];
     if (s->stream_mode != 1 || q.icl) return range_vocode_enqueue(s, b, q.stream_pos, avail, st, pcm);
-    // continuous mode (q3_session_set_stream_mode): the front runs over frames [0, end), the convolutional stack over
-    // [pos - CTX, end); the chunk's samples are identical to the same frames of a whole-utterance decode (codec_decode_dev)
-    const int spf = samples_per_frame(s->m->cfg);
-    const int a0 = q.stream_pos, e = q.stream_pos + avail, c0 = a0 > CODEC_CTX_FRAMES ? a0 - CODEC_CTX_FRAMES : 0;
+    // continuous mode (q3_session_set_stream_mode): the chunk's samples are identical to the same frames of a whole-utterance decode
     Q3C(codec_reserve(s->m, s->cws, chunk_frames_of(s) + CODEC_CTX_FRAMES, s->max_frames));
-    HIPC(hipMemcpyAsync(s->cws.frames, s->codes + (size_t)b * s->max_frames * 16, (size_t)e * 16 * 4, hipMemcpyDeviceToDevice, st));
-    Q3C(codec_decode_dev(s->m, s->cws, e, st, nullptr, c0));
-    *pcm = {s->cws.pcm + (size_t)(a0 - c0) * spf, (size_t)avail * spf};
-    return Q3_OK;
-}
-// the caller's half, after its wait: the count, and the samples where a buffer was given
-static q3_status chunk_copy_out(const ChunkPcm& pcm, float* pcm_host, size_t cap, size_t* n_samples) {
-    if (n_samples) *n_samples = pcm.n;
-    if (pcm_host) {
-        if (cap < pcm.n) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
-        HIPC(q3_hipMemcpy(pcm_host, pcm.dev, pcm.n * 4, hipMemcpyDeviceToHost));
-    }
-    return Q3_OK;
+    return vocode_enqueue(s->m, s->cws, st, row_src(s, b), q.stream_pos, q.stream_pos + avail, vocode_ctx_start(q.stream_pos), 0, pcm);
 }
 // the vocoder pass of one row's chunk on the session's stream
 static q3_status chunk_decode_row(q3_session* s, int b, int avail, float* pcm_host, size_t cap, size_t* n_samples) {
-    ChunkPcm pcm;
+    VocodePcm pcm;
     Q3C(chunk_vocode_enqueue(s, b, avail, s->stream, &pcm));
     HIPC(sync_frames(s));
-    return chunk_copy_out(pcm, pcm_host, cap, n_samples);
+    return vocode_copy_out(pcm, pcm_host, cap, n_samples, nullptr);
 }
 
 // Streaming with several sequences in one session: the next chunk of row b (StreamingSession::next_chunk, lib.rs:1650-1759,
@@ -2147,42 +2134,90 @@ extern "C" q3_status q3_session_codes(q3_session* s, int b, uint32_t* codes_host
     return Q3_OK;
 }
 
-// context-free decode of frames [f0, f1) of sequence b on `st`, waited for and copied out
-static q3_status decode_range_on(q3_session* s, int b, int f0, int f1, hipStream_t st, float* pcm_host, size_t cap, size_t* n_samples) {
-    if (n_samples) *n_samples = 0;
-    if (f1 == f0) return Q3_OK;
-    ChunkPcm pcm;
-    Q3C(range_vocode_enqueue(s, b, f0, f1 - f0, st, &pcm));
-    HIPC(hipStreamSynchronize(st));
-    return chunk_copy_out(pcm, pcm_host, cap, n_samples);
-}
-
 extern "C" q3_status q3_session_decode(q3_session* s, int b, int f0, int f1, float* pcm_host, size_t cap, size_t* n_samples) {
     if (!s || b < 0 || b >= s->B) return set_err(Q3_INVALID_ARG, "bad sequence index");
     HIPC(hipSetDevice(s->m->device));
     Q3C(refresh_codes(s));
     if (f0 < 0 || f1 < f0 || f1 > s->seq[b].n_frames) return set_err(Q3_INVALID_ARG, "bad frame range [%d,%d) of %d", f0, f1, s->seq[b].n_frames);
-    const int T = f1 - f0, spf = samples_per_frame(s->m->cfg);
-    const SeqInfo& q = s->seq[b];
-    if (!q.ref_codes.empty() && s->prefilled && f0 == 0 && f1 == q.n_frames) {
-        // ICL full-utterance decode (lib.rs:1022-1041): decode [ref_frames ; generated], then cut the first
-        // ref_len * samples / total_frames samples
-        const int n_ref = (int)(q.ref_codes.size() / 16), total = n_ref + T;
-        const size_t all = (size_t)total * spf, cut = (size_t)n_ref * all / (size_t)(total > 0 ? total : 1);
-        if (n_samples) *n_samples = all - cut;
-        Q3C(codec_reserve(s->m, s->cws, total));
-        // the row's reference frames from the host copy (a row swapped in by q3_session_replace brings its own)
-        HIPC(hipMemcpyAsync(s->cws.frames, q.ref_codes.data(), (size_t)n_ref * 16 * 4, hipMemcpyHostToDevice, s->stream));
-        if (T > 0) HIPC(hipMemcpyAsync(s->cws.frames + (size_t)n_ref * 16, s->codes + (size_t)b * s->max_frames * 16, (size_t)T * 16 * 4, hipMemcpyDeviceToDevice, s->stream));
-        Q3C(codec_decode_dev(s->m, s->cws, total, s->stream, nullptr));
-        HIPC(sync_frames(s));
-        if (pcm_host) {
-            if (cap < all - cut) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
-            HIPC(q3_hipMemcpy(pcm_host, s->cws.pcm + cut, (all - cut) * 4, hipMemcpyDeviceToHost));
-        }
+    if (n_samples) *n_samples = 0;
+    if (f1 == f0) return Q3_OK;
+    // a part of a row: context-free, an utterance of its own; the whole row: behind its reference frames where it is an ICL row
+    VocodePcm pcm;
+    Q3C(vocode_enqueue(s->m, s->cws, s->stream, row_src(s, b, f0, f0 == 0 && f1 == s->seq[b].n_frames), 0, f1 - f0, 0, 0, &pcm));
+    HIPC(sync_frames(s));
+    return vocode_copy_out(pcm, pcm_host, cap, n_samples, nullptr);
+}
+
+// ---- q3_session_run: the knobs, the lanes, the serial and the overlapped vocoder phase ----
+using run_clk = std::chrono::steady_clock;
+static double run_ms(run_clk::time_point a, run_clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+// The environment knobs of q3_session_run (A/B aids), clamped. overlap, resident, seg, tail and log are read on every call
+// (tests set them per test); pairs and cus once per process.
+struct RunKnobs {
+    int overlap;       // Q3_DECODE_OVERLAP: 0 the serial path, 1 overlap on, -1 (unset) DECODE_OVERLAP_DEFAULT below
+    int resident;      // Q3_DECODE_RESIDENT = 0|1|2 (1): the residency cap of the segments decoded beside the frames (0 = none: the unsplit overlap of round 6)
+    int seg, tail;     // Q3_DECODE_SEG (256) / Q3_DECODE_TAIL (32), 16 at least: the segment schedule (run_overlapped)
+    int pairs;         // Q3_DECODE_PAIRS = 1..8 (2): utterances vocoded at a time (run_serial)
+    int cus;           // Q3_DECODE_CUS (0 = off; 8..248 in eighths): the chip split while both run (run_overlapped)
+    bool log;          // Q3_DECODE_LOG: one line per overlapped run on stderr
+};
+static int env_int(const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; }
+static RunKnobs read_run_knobs() {
+    static const int pairs = std::min(std::max(env_int("Q3_DECODE_PAIRS", 2), 1), 8);
+    static const int cus = [] { const int v = env_int("Q3_DECODE_CUS", 0); return v <= 0 ? 0 : (v < 8 ? 8 : (v > 248 ? 248 : v & ~7)); }();
+    const char* overlap = getenv("Q3_DECODE_OVERLAP");
+    return {overlap ? (atoi(overlap) != 0 ? 1 : 0) : -1, std::min(std::max(env_int("Q3_DECODE_RESIDENT", 1), 0), 2),
+            std::max(env_int("Q3_DECODE_SEG", 256), 16), std::max(env_int("Q3_DECODE_TAIL", 32), 16), pairs, cus, getenv("Q3_DECODE_LOG") != nullptr};
+}
+// Utterances vocoded side by side, each on its own workspace and stream: lane 0 is the session's own pair, decode_lanes makes
+// the n - 1 others once (they live as long as the session)
+struct Lane { CodecWS& ws; hipStream_t st; };
+static q3_status decode_lanes(q3_session* s, int n) {
+    while ((int)s->par_ws.size() < n - 1) {
+        hipStream_t st = nullptr;
+        HIPC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        s->par_ws.emplace_back(); s->par_streams.push_back(st);
+    }
+    return Q3_OK;
+}
+static Lane lane(q3_session* s, int k) { return k == 0 ? Lane{s->cws, s->stream} : Lane{s->par_ws[(size_t)k - 1], s->par_streams[(size_t)k - 1]}; }
+
+// The serial path: every frame, then every row's vocoder. frames_done: when the frames were.
+static q3_status run_serial(q3_session* s, int use_graph, const RunKnobs& kn, float** pcm_host, const size_t* cap, run_clk::time_point* frames_done) {
+    Q3C(q3_session_generate(s, s->max_frames, use_graph));
+    Q3C(refresh_codes(s));
+    *frames_done = run_clk::now();
+    const int spf = samples_per_frame(s->m->cfg), conc = kn.pairs;
+    bool any_icl = false;
+    for (auto& q : s->seq) any_icl = any_icl || !q.ref_codes.empty();
+    if (conc == 1 || s->B == 1 || any_icl) {                 // one lane: row after row, as q3_session_decode gives them
+        for (int b = 0; b < s->B; ++b) Q3C(q3_session_decode(s, b, 0, s->seq[b].n_frames, pcm_host ? pcm_host[b] : nullptr, cap ? cap[b] : 0, nullptr));
         return Q3_OK;
     }
-    return decode_range_on(s, b, f0, f1, s->stream, pcm_host, cap, n_samples);
+    // Two utterances are vocoded at a time, each on its own stream and workspace: most of a decode saturates the
+    // chip, but its front (the pre-transformer's ~90 launches on 10-160 workgroups) is latency-bound and fills in beside
+    // the other utterance's convolutions. Q3_DECODE_PAIRS=n: n at a time (1 = serial; A/B aid). Re-measured in round 6
+    // (profiles/r6_decode_knobs_ab.txt): 8 x 640 frames 155.3 / 157.7 / 162.1 ms at 2 / 4 / 8 at a time, 64 x 640 frames
+    // 1261 / 1274 ms at 2 / 4 — four was the round-1 optimum, when the front was 4 of 28 ms; it is 2 of 19.8 now.
+    Q3C(decode_lanes(s, conc));
+    if (pcm_host)                                            // refused as a whole before any row's samples move
+        for (int b = 0; b < s->B; ++b)
+            if (pcm_host[b] && s->seq[b].n_frames && (!cap || cap[b] < (size_t)s->seq[b].n_frames * spf)) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
+    for (int b0 = 0; b0 < s->B; b0 += conc) {
+        const int nb = (s->B - b0) < conc ? (s->B - b0) : conc;
+        for (int k = 0; k < nb; ++k) {
+            const int b = b0 + k, T = s->seq[b].n_frames;
+            if (T == 0) continue;
+            const Lane ln = lane(s, k);
+            VocodePcm pcm;
+            Q3C(vocode_enqueue(s->m, ln.ws, ln.st, row_src(s, b), 0, T, 0, 0, &pcm));
+            // the samples leave for the host on the utterance's own stream, beside the other utterances' decodes
+            // (synthesize returns host samples, lib.rs:718-784); pinned caller buffers make this a true async copy
+            Q3C(vocode_copy_out(pcm, pcm_host ? pcm_host[b] : nullptr, cap ? cap[b] : 0, nullptr, ln.st));
+        }
+        for (int k = 0; k < nb; ++k) HIPC(hipStreamSynchronize(lane(s, k).st));
+    }
+    return Q3_OK;
 }
 
 // synthesize_with_timing for the whole batch. In the overlapped path (Q3_DECODE_OVERLAP=1, or unset: DECODE_OVERLAP_DEFAULT
@@ -2207,89 +2242,41 @@ extern "C" q3_status q3_session_decode(q3_session* s, int b, int f0, int f1, flo
 // A single row has 21 ms of vocoder to hide and ends in a tie (413.8-415.3 serial, 414.0-414.6 overlapped): serial. Wider sessions run
 // the k_wide* frame kernels with other register counts and lose 6.5-12.8 % with every overlap variant: serial. DESIGN 4.3 / 7a / 8.3.
 static constexpr bool DECODE_OVERLAP_DEFAULT = true;
-extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_host, const size_t* cap, size_t* n_samples, q3_timing* timing) {
-    if (!s) return set_err(Q3_INVALID_ARG, "null session");
-    if (any_open_text(s)) return set_err(Q3_UNSUPPORTED, "q3_session_run: a row's text is still open (q3_session_append_text with last != 0 closes it; or drive the session with q3_session_generate)");
-    using clk = std::chrono::steady_clock;
-    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t0 = clk::now();
-    s->precapture = use_graph != 0;
-    Q3C(q3_session_prefill(s));
-    const auto t1 = clk::now();
-    // read per call (tests set them per test): Q3_DECODE_OVERLAP=0 the serial path, =1 overlap on, unset the default below;
-    // Q3_DECODE_RESIDENT=0|1|2 the residency cap of the segments decoded beside the frames (0 = none: the unsplit overlap of round 6);
-    // Q3_DECODE_SEG / Q3_DECODE_TAIL (below) the segment schedule
-    const int overlap_env = [] { const char* e = getenv("Q3_DECODE_OVERLAP"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-    const int resident_env = [] { const char* e = getenv("Q3_DECODE_RESIDENT"); const int v = e ? atoi(e) : 1; return v < 0 ? 0 : (v > 2 ? 2 : v); }();
-    const int seg_env = [] { const char* e = getenv("Q3_DECODE_SEG"); const int v = e ? atoi(e) : 256; return v < 16 ? 16 : v; }();
-    const bool overlap_wanted = overlap_env >= 0 ? overlap_env != 0 : (DECODE_OVERLAP_DEFAULT && s->B >= 2 && s->B <= 16);
-    bool overlap = overlap_wanted && !s->debug && !s->profile && s->max_frames > seg_env;
-    for (auto& q : s->seq) if (!q.ref_codes.empty()) overlap = false;
-    const int spf = samples_per_frame(s->m->cfg);
-    if (!overlap) {
-        Q3C(q3_session_generate(s, s->max_frames, use_graph));
-        Q3C(refresh_codes(s));
-        const auto t2 = clk::now();
-        int total = 0;
-        // Two utterances are vocoded at a time, each on its own stream and workspace: most of a decode saturates the
-        // chip, but its front (the pre-transformer's ~90 launches on 10-160 workgroups) is latency-bound and fills in beside
-        // the other utterance's convolutions. Q3_DECODE_PAIRS=n: n at a time (1 = serial; A/B aid). Re-measured in round 6
-        // (profiles/r6_decode_knobs_ab.txt): 8 x 640 frames 155.3 / 157.7 / 162.1 ms at 2 / 4 / 8 at a time, 64 x 640 frames
-        // 1261 / 1274 ms at 2 / 4 — four was the round-1 optimum, when the front was 4 of 28 ms; it is 2 of 19.8 now.
-        static const int conc = [] { const char* e = getenv("Q3_DECODE_PAIRS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
-        bool any_icl = false;
-        for (auto& q : s->seq) any_icl = any_icl || !q.ref_codes.empty();
-        if (conc > 1 && s->B > 1 && !any_icl) {
-            while ((int)s->par_ws.size() < conc - 1) {
-                s->par_ws.emplace_back();
-                hipStream_t st = nullptr;
-                HIPC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-                s->par_streams.push_back(st);
-            }
-            auto ws_of = [&](int k) -> CodecWS& { return k == 0 ? s->cws : s->par_ws[(size_t)k - 1]; };
-            auto st_of = [&](int k) { return k == 0 ? s->stream : s->par_streams[(size_t)k - 1]; };
-            if (pcm_host)
-                for (int b = 0; b < s->B; ++b)
-                    if (pcm_host[b] && s->seq[b].n_frames && (!cap || cap[b] < (size_t)s->seq[b].n_frames * spf)) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
-            for (int b0 = 0; b0 < s->B; b0 += conc) {
-                const int nb = (s->B - b0) < conc ? (s->B - b0) : conc;
-                for (int k = 0; k < nb; ++k) {
-                    const int b = b0 + k, T = s->seq[b].n_frames;
-                    if (n_samples) n_samples[b] = (size_t)T * spf;
-                    total += T;
-                    if (T == 0) continue;
-                    Q3C(codec_reserve(s->m, ws_of(k), T));
-                    HIPC(hipMemcpyAsync(ws_of(k).frames, s->codes + (size_t)b * s->max_frames * 16, (size_t)T * 16 * 4, hipMemcpyDeviceToDevice, st_of(k)));
-                    Q3C(codec_decode_dev(s->m, ws_of(k), T, st_of(k), nullptr));
-                    // the samples leave for the host on the utterance's own stream, beside the other utterances' decodes
-                    // (synthesize returns host samples, lib.rs:718-784); pinned caller buffers make this a true async copy
-                    if (pcm_host && pcm_host[b])
-                        HIPC(hipMemcpyAsync(pcm_host[b], ws_of(k).pcm, (size_t)T * spf * 4, hipMemcpyDeviceToHost, st_of(k)));
-                }
-                for (int k = 0; k < nb; ++k) HIPC(hipStreamSynchronize(st_of(k)));
-            }
-        } else
-        for (int b = 0; b < s->B; ++b) {
-            size_t n = 0;
-            Q3C(q3_session_decode(s, b, 0, s->seq[b].n_frames, pcm_host ? pcm_host[b] : nullptr, cap ? cap[b] : 0, &n));
-            if (n_samples) n_samples[b] = n;
-            total += s->seq[b].n_frames;
+struct SegJob { int b, a, e; };
+// one segment: codes -> workspace, vocoder over [a - context, e), the samples of [a, e) straight to the caller's buffer
+// (resident: the residency cap of this decode's launches — the knob beside the frames, 0 for the tail on the whole chip)
+static q3_status seg_enqueue(q3_session* s, const SegJob& j, CodecWS& ws, hipStream_t st, int resident, float** pcm_host, const size_t* cap) {
+    const size_t at = (size_t)j.a * samples_per_frame(s->m->cfg);
+    float* host = pcm_host ? pcm_host[j.b] : nullptr;
+    VocodePcm pcm;
+    Q3C(vocode_enqueue(s->m, ws, st, row_src(s, j.b), j.a, j.e, vocode_ctx_start(j.a), resident, &pcm));
+    return vocode_copy_out(pcm, host ? host + at : nullptr, cap && cap[j.b] > at ? cap[j.b] - at : 0, nullptr, st);
+}
+// the segments that are ready behind dec_pos (final_pass: whatever is left), at most seg new frames each: every call stays within the workspace
+static std::vector<SegJob> seg_collect(const q3_session* s, std::vector<int>& dec_pos, int seg, bool final_pass) {
+    std::vector<SegJob> jobs;
+    for (int b = 0; b < s->B; ++b) {
+        const SeqInfo& q = s->seq[b];
+        const int e = (q.done || final_pass) ? q.n_frames : (q.n_frames < s->frames_run ? q.n_frames : s->frames_run);
+        if (e > dec_pos[(size_t)b] && (final_pass || q.done || e - dec_pos[(size_t)b] >= 16)) {
+            for (int a = dec_pos[(size_t)b]; a < e; a += seg) jobs.push_back({b, a, a + seg < e ? a + seg : e});
+            dec_pos[(size_t)b] = e;
         }
-        const auto t3 = clk::now();
-        if (timing) { timing->prefill_ms = ms(t0, t1); timing->generation_ms = ms(t1, t2); timing->decode_ms = ms(t2, t3); timing->generation_frames = total; }
-        return Q3_OK;
     }
+    return jobs;
+}
+struct OverlapMarks { run_clk::time_point frames_done; int n_dispatch = 0; double join_wait_ms = 0.0; };      // join_wait_ms: what the frame loop's thread spent waiting for the enqueue thread (Q3_DECODE_LOG)
+static q3_status run_overlapped(q3_session* s, int use_graph, const RunKnobs& kn, float** pcm_host, const size_t* cap, OverlapMarks* marks) {
     HIPC(hipSetDevice(s->m->device));
     // Q3_DECODE_CUS=n (measurement aid, default 0 = off) SPLITS the chip while both run: the frames keep the first 256 - n bits of the CU
     // mask on their own queue, the decode stream gets the last n (n / 8 CUs of every XCD, see aql_restrict_cus), so a frame kernel's
     // workgroups are never dealt onto a CU the vocoder holds. Measured in round 6 (profiles/r6_split_chip_overlap_ab.txt): the vocoder
     // beside the frames then costs them only 3 %, but the frames ALONE on 224 / 192 / 128 CUs are 16 / 15 / 23 % slower — their grids are
     // one workgroup per CU of the whole chip, and the slowest workgroup of every one of 549 dependent launches sets the pace.
-    static const int cus = [] { const char* e = getenv("Q3_DECODE_CUS"); const int v = e ? atoi(e) : 0; return v <= 0 ? 0 : (v < 8 ? 8 : (v > 248 ? 248 : v & ~7)); }();
     if (!s->dec_stream) {
-        if (cus) {
+        if (kn.cus) {
             uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int i = 256 - cus; i < 256; ++i) mask[i >> 5] |= 1u << (i & 31);
+            for (int i = 256 - kn.cus; i < 256; ++i) mask[i >> 5] |= 1u << (i & 31);
             HIPC(hipExtStreamCreateWithCUMask(&s->dec_stream, 8, mask));
         } else {
             int least = 0, greatest = 0;
@@ -2297,113 +2284,95 @@ extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_ho
             HIPC(hipStreamCreateWithPriority(&s->dec_stream, hipStreamNonBlocking, least));
         }
     }
-    Q3C(codec_reserve(s->m, s->seg_ws, seg_env + CODEC_CTX_FRAMES, s->max_frames));
+    Q3C(codec_reserve(s->m, s->seg_ws, kn.seg + CODEC_CTX_FRAMES, s->max_frames));
     struct Split {                                         // the whole chip goes back to the frames' queue on every way out
         q3::AqlProgram* p = nullptr;
         void release() { if (p) { std::string why; q3::aql_restrict_cus(p, 0, &why); p = nullptr; } }
         ~Split() { release(); }
     } split;
-    if (cus && s->aql && !s->aql_failed) { std::string why; if (q3::aql_restrict_cus(s->aql, 256 - cus, &why)) split.p = s->aql; }
+    if (kn.cus && s->aql && !s->aql_failed) { std::string why; if (q3::aql_restrict_cus(s->aql, 256 - kn.cus, &why)) split.p = s->aql; }
     std::vector<int> dec_pos((size_t)s->B, 0);
     std::thread worker; q3_status wst = Q3_OK; std::string werr;
-    double join_wait_ms = 0.0; int n_dispatch = 0;         // what the frame loop's thread spent waiting for the enqueue thread (Q3_DECODE_LOG)
     auto join = [&]() -> q3_status {
         if (worker.joinable()) worker.join();
         if (wst != Q3_OK) return set_err(wst, "%s", werr.c_str());
         return Q3_OK;
     };
-    struct Job { int b, a, e; };
-    // one segment: codes -> workspace, vocoder over [a - context, e), the samples of [a, e) straight to the caller's buffer
-    // (resident: the residency cap of this decode's launches — resident_env beside the frames, 0 for the tail on the whole chip)
-    auto seg_enqueue = [s, spf, pcm_host, cap](const Job& j, CodecWS& ws, hipStream_t st, int resident) -> q3_status {
-        const int c0 = j.a > CODEC_CTX_FRAMES ? j.a - CODEC_CTX_FRAMES : 0;
-        if (pcm_host && pcm_host[j.b] && (!cap || cap[j.b] < (size_t)j.e * spf)) return set_err(Q3_INVALID_ARG, "pcm buffer too small");
-        HIPC(hipMemcpyAsync(ws.frames, s->codes + (size_t)j.b * s->max_frames * 16, (size_t)j.e * 16 * 4, hipMemcpyDeviceToDevice, st));
-        Q3C(codec_decode_dev(s->m, ws, j.e, st, nullptr, c0, resident));
-        if (pcm_host && pcm_host[j.b])
-            HIPC(hipMemcpyAsync(pcm_host[j.b] + (size_t)j.a * spf, ws.pcm + (size_t)(j.a - c0) * spf, (size_t)(j.e - j.a) * spf * 4, hipMemcpyDeviceToHost, st));
-        return Q3_OK;
-    };
-    auto collect = [&](bool final_pass) {
-        std::vector<Job> jobs;
-        for (int b = 0; b < s->B; ++b) {
-            const SeqInfo& q = s->seq[b];
-            const int e = (q.done || final_pass) ? q.n_frames : (q.n_frames < s->frames_run ? q.n_frames : s->frames_run);
-            if (e > dec_pos[(size_t)b] && (final_pass || q.done || e - dec_pos[(size_t)b] >= 16)) {
-                // keep every call within the workspace: at most seg_env new frames per job
-                for (int a = dec_pos[(size_t)b]; a < e; a += seg_env) jobs.push_back({b, a, a + seg_env < e ? a + seg_env : e});
-                dec_pos[(size_t)b] = e;
-            }
-        }
-        return jobs;
-    };
     auto dispatch = [&]() -> q3_status {
-        std::vector<Job> jobs = collect(false);
+        std::vector<SegJob> jobs = seg_collect(s, dec_pos, kn.seg, false);
         if (jobs.empty()) return Q3_OK;
         {   // the previous segment's enqueue must be over: normally long since (its thread only enqueues; a segment of frames is ~0.3 s)
-            const auto j0 = clk::now();
+            const auto j0 = run_clk::now();
             Q3C(join());
-            join_wait_ms += ms(j0, clk::now()); ++n_dispatch;
+            marks->join_wait_ms += run_ms(j0, run_clk::now()); ++marks->n_dispatch;
         }
-        worker = std::thread([s, jobs, seg_enqueue, resident_env, &wst, &werr]() {
+        worker = std::thread([s, jobs, resident = kn.resident, pcm_host, cap, &wst, &werr]() {
             if (hipSetDevice(s->m->device) != hipSuccess) { wst = Q3_HIP_ERROR; werr = "hipSetDevice failed in the decode thread"; return; }
-            for (const Job& j : jobs) {
-                const q3_status st = seg_enqueue(j, s->seg_ws, s->dec_stream, resident_env);
+            for (const SegJob& j : jobs) {
+                const q3_status st = seg_enqueue(s, j, s->seg_ws, s->dec_stream, resident, pcm_host, cap);
                 if (st != Q3_OK) { wst = st; werr = q3_last_error(); return; }
             }
         });
         return Q3_OK;
     };
     // the last segment of a row is the only one nothing overlaps: it is kept short (Q3_DECODE_TAIL frames, default 32)
-    const int tail_env = [] { const char* e = getenv("Q3_DECODE_TAIL"); const int v = e ? atoi(e) : 32; return v < 16 ? 16 : v; }();
     q3_status st = Q3_OK;
     while (st == Q3_OK && session_remaining(s) > 0 && !all_done(s)) {
-        int n = seg_env;
+        int n = kn.seg;
         const int left = session_remaining(s);
-        if (left > tail_env && left - n < tail_env) n = left - tail_env;        // ... so the step before it stops tail_env frames short of the end
+        if (left > kn.tail && left - n < kn.tail) n = left - kn.tail;        // ... so the step before it stops kn.tail frames short of the end
         st = q3_session_generate(s, n, use_graph);
         if (st == Q3_OK) st = refresh_codes(s);
         if (st == Q3_OK && session_remaining(s) > 0 && !all_done(s)) st = dispatch();
     }
-    const auto t2 = clk::now();
+    marks->frames_done = run_clk::now();
     split.release();
     { const q3_status js = join(); if (st == Q3_OK) st = js; }
     if (st != Q3_OK) { hipStreamSynchronize(s->dec_stream); return st; }
     // what is left runs on the whole chip beside the confined stream's backlog: utterances side by side as in the plain path.
     // Whatever happens, nothing returns while a stream may still be copying samples into the caller's buffers.
-    {
-        const int conc = 2;
-        auto ws_of = [&](int k) -> CodecWS& { return k == 0 ? s->cws : s->par_ws[(size_t)k - 1]; };
-        auto st_of = [&](int k) { return k == 0 ? s->stream : s->par_streams[(size_t)k - 1]; };
-        auto tail = [&]() -> q3_status {
-            std::vector<Job> jobs = collect(true);
-            while ((int)s->par_ws.size() < conc - 1) {
-                hipStream_t pst = nullptr;
-                HIPC(hipStreamCreateWithFlags(&pst, hipStreamNonBlocking));
-                s->par_ws.emplace_back(); s->par_streams.push_back(pst);
-            }
-            for (int k = 0; k < conc; ++k) Q3C(codec_reserve(s->m, ws_of(k), seg_env + CODEC_CTX_FRAMES, s->max_frames));
-            for (size_t i = 0; i < jobs.size(); ++i) Q3C(seg_enqueue(jobs[i], ws_of((int)(i % conc)), st_of((int)(i % conc)), 0));
-            return Q3_OK;
-        };
-        st = tail();
-        hipError_t he = hipStreamSynchronize(s->dec_stream);
-        for (int k = 0; k < conc && k <= (int)s->par_streams.size(); ++k) { const hipError_t e2 = hipStreamSynchronize(st_of(k)); if (he == hipSuccess) he = e2; }
-        if (st != Q3_OK) return st;
-        HIPC(he);
-    }
+    const int conc = 2;
+    auto tail = [&]() -> q3_status {
+        std::vector<SegJob> jobs = seg_collect(s, dec_pos, kn.seg, true);
+        Q3C(decode_lanes(s, conc));
+        for (int k = 0; k < conc; ++k) Q3C(codec_reserve(s->m, lane(s, k).ws, kn.seg + CODEC_CTX_FRAMES, s->max_frames));
+        for (size_t i = 0; i < jobs.size(); ++i) { const Lane ln = lane(s, (int)(i % conc)); Q3C(seg_enqueue(s, jobs[i], ln.ws, ln.st, 0, pcm_host, cap)); }
+        return Q3_OK;
+    };
+    st = tail();
+    hipError_t he = hipStreamSynchronize(s->dec_stream);
+    for (int k = 0; k < conc && k <= (int)s->par_streams.size(); ++k) { const hipError_t e2 = hipStreamSynchronize(lane(s, k).st); if (he == hipSuccess) he = e2; }
+    if (st != Q3_OK) return st;
+    HIPC(he);
+    return Q3_OK;
+}
+
+// Open-text check, prefill, knobs, one of the two paths above, the counts and the timing
+extern "C" q3_status q3_session_run(q3_session* s, int use_graph, float** pcm_host, const size_t* cap, size_t* n_samples, q3_timing* timing) {
+    if (!s) return set_err(Q3_INVALID_ARG, "null session");
+    if (any_open_text(s)) return set_err(Q3_UNSUPPORTED, "q3_session_run: a row's text is still open (q3_session_append_text with last != 0 closes it; or drive the session with q3_session_generate)");
+    const auto t0 = run_clk::now();
+    s->precapture = use_graph != 0;
+    Q3C(q3_session_prefill(s));
+    const auto t1 = run_clk::now();
+    const RunKnobs kn = read_run_knobs();
+    const bool overlap_wanted = kn.overlap >= 0 ? kn.overlap != 0 : (DECODE_OVERLAP_DEFAULT && s->B >= 2 && s->B <= 16);
+    bool overlap = overlap_wanted && !s->debug && !s->profile && s->max_frames > kn.seg;
+    for (auto& q : s->seq) if (!q.ref_codes.empty()) overlap = false;
+    OverlapMarks marks;
+    Q3C(overlap ? run_overlapped(s, use_graph, kn, pcm_host, cap, &marks) : run_serial(s, use_graph, kn, pcm_host, cap, &marks.frames_done));
+    // (an ICL row's count too: its reference frames' samples are cut whole)
     int total = 0;
     for (int b = 0; b < s->B; ++b) {
-        if (n_samples) n_samples[b] = (size_t)s->seq[b].n_frames * spf;
+        if (n_samples) n_samples[b] = (size_t)s->seq[b].n_frames * samples_per_frame(s->m->cfg);
         total += s->seq[b].n_frames;
     }
-    const auto t3 = clk::now();
-    if (timing) { timing->prefill_ms = ms(t0, t1); timing->generation_ms = ms(t1, t2); timing->decode_ms = ms(t2, t3); timing->generation_frames = total; }
+    const auto t2 = marks.frames_done, t3 = run_clk::now();
+    if (timing) { timing->prefill_ms = run_ms(t0, t1); timing->generation_ms = run_ms(t1, t2); timing->decode_ms = run_ms(t2, t3); timing->generation_frames = total; }
     // Q3_DECODE_LOG=1 (A/B aid): one line per run on stderr — did the enqueue thread ever hold up the frame loop, how long was the exposed tail
-    const bool log_env = getenv("Q3_DECODE_LOG") != nullptr;
-    if (log_env)
+    if (overlap && kn.log)
         fprintf(stderr, "q3_session_run overlap: resident %d seg %d tail %d, %d dispatches, frame loop waited %.3f ms for the enqueue thread, frames %.1f ms, exposed decode %.1f ms\n",
-                resident_env, seg_env, tail_env, n_dispatch, join_wait_ms, ms(t1, t2), ms(t2, t3));
+                kn.resident, kn.seg, kn.tail, marks.n_dispatch, marks.join_wait_ms, run_ms(t1, t2), run_ms(t2, t3));
     return Q3_OK;
 }
 
@@ -2453,7 +2422,7 @@ extern "C" q3_status q3_session_next_chunk(q3_session* s, float* pcm_host, size_
         Q3C(launch_ahead());
         dst = s->dec_stream;
     }
-    ChunkPcm pcm;
+    VocodePcm pcm;
     Q3C(chunk_vocode_enqueue(s, 0, avail, dst, &pcm));
     if (ahead > 0 && first) {
         if (!s->dec_ev) HIPC(hipEventCreateWithFlags(&s->dec_ev, hipEventDisableTiming));
@@ -2463,7 +2432,7 @@ extern "C" q3_status q3_session_next_chunk(q3_session* s, float* pcm_host, size_
     } else {
         HIPC(hipStreamSynchronize(dst));
     }
-    Q3C(chunk_copy_out(pcm, pcm_host, cap, n_samples));
+    Q3C(vocode_copy_out(pcm, pcm_host, cap, n_samples, nullptr));
     q.stream_pos += avail;
     if (done) *done = cut.ends ? 1 : 0;
     return Q3_OK;
