@@ -1437,6 +1437,35 @@ q3_status q3_spk_encode_ref(q3_speaker_encoder* e, const q3_ref_audio* r, float*
 q3_status q3_mimi_encode_ref(q3_speech_encoder* e, const q3_ref_audio* r, uint32_t* codes_host, int cap_frames, int* n_frames,
                              float** taps_host);
 
+/* ---------------- spectral noise suppression of a reference clip (q3_denoise.hip) ----------------
+ * The step between the intake and the two encoders, on the device. No reference counterpart. The definition, for the samples
+ * x[0..n) of an object, 1 <= n <= 24000 * 120, and reduce_db in [0, 30] (default 12); N = 512, H = 128, K = 257, D = 94, c_bias = 4:
+ *  1. T = ceil(n / H) + 3 frames; frame m covers samples [m H - 384, m H + 128), zeros outside [0, n); w[i] = sqrt(0.5 - 0.5 cos(2 pi
+ *     i / N)) for analysis and synthesis; X[m][k] = the N-point DFT of w * frame, k = 0..256; P = |X|^2.
+ *  2. S[m][k] = the mean of P over frames m-2..m+2 and bins k-1..k+1, over the entries that exist.
+ *  3. Valid frames lo = 3 .. hi = T - 4. hi < lo (n <= 384): G = 1. Else M[m][k] = min of S[j][k] over a window of 2 D + 1 valid frames
+ *     centred on m and shifted, not shrunk, into [lo, hi]: a = max(lo, min(m - D, hi - 2 D)), b = a + 2 D; with fewer valid frames
+ *     the window is all of them. lambda = c_bias * M.
+ *  4. xi = max(S / max(lambda, 1e-30) - 1, 0); G = max(xi / (1 + xi), 10^(-reduce_db / 20)).
+ *  5. y = 1/2 of the overlap-add, in ascending frame order, of w * (the inverse N-point DFT of G X); y[0..n).
+ * Every sum on the device has one fixed order: a clip has the same bits alone and in any batch. */
+/* host arithmetic only: T, lo, hi of the definition and the bytes of X + P + G (16 T K); any out pointer may be NULL.
+ * n_samples outside 1 .. 24000 * 120: Q3_INVALID_ARG */
+q3_status q3_denoise_plan(int64_t n_samples, int* frames, int* valid_lo, int* valid_hi, size_t* workspace_bytes);
+/* n objects (1 .. 64) of one device through k_dn_analysis, k_dn_gain, k_dn_synthesis, one launch of each; out[i] receives a NEW
+ * object that remembers in[i]'s rate / format / channels (q3_spk_encode_ref(s) / q3_mimi_encode_ref(s) take it as they take
+ * in[i]); the inputs are untouched. reduce_db: [n] or NULL = 12 for all. All or nothing: every argument is checked before the
+ * device is touched, and on any refusal or device error no object is created and out is untouched. Q3_INVALID_ARG: a null pointer, n
+ * outside 1 .. 64, a reduce_db outside [0, 30] or NaN, objects on different devices. The workspace (q3_denoise_plan's bytes per
+ * clip) comes from the device-memory cache and goes back before the call returns; synchronises before it returns. */
+q3_status q3_ref_audio_denoise(q3_ref_audio* const* in, int n, const float* reduce_db /* [n] or NULL */, q3_ref_audio** out /* [n] */);
+/* the clip's estimated noise level and signal-to-noise ratio from the same floor (k_dn_analysis, k_dn_gain, k_dn_level): with
+ * Nbar / Pbar = the means over the valid frames of sum_k lambda[m][k] / sum_k P[m][k] (f32 sums in one fixed order on the device, the
+ * workgroups' sums joined in f64 on the host), nz = max(Nbar, 1e-30): noise_dbfs = 10 log10(nz / 65536) (65536 = N sum(w^2) / 2: a
+ * sine of amplitude 1 has -3 dBFS), snr_db = 10 log10(max(Pbar - nz, 1e-30) / nz). Either out pointer may be NULL. A clip with
+ * hi < lo (n <= 384): Q3_UNSUPPORTED. */
+q3_status q3_ref_audio_noise(q3_ref_audio* r, double* noise_dbfs, double* snr_db);
+
 /* ---------------- many reference clips in one packed pass of each encoder ----------------
  * n = 1 .. 64 objects of different lengths, laid side by side along the time axis of the encoders' [C][L] tensors, so every conv
  * launch covers all of them. Each clip's result is bit-equal to q3_spk_encode_ref / q3_mimi_encode_ref of that clip alone, whatever

@@ -427,6 +427,9 @@ SYMBOLS = {
     "q3_ref_audio_info": (c_int, [c_void_p, P(ctypes.c_int64), P(c_int), P(ctypes.c_uint32), P(c_int), P(c_int)]),
     "q3_ref_audio_read": (c_int, [c_void_p, c_void_p, ctypes.c_int64, P(ctypes.c_int64)]),
     "q3_ref_audio_free": (None, [c_void_p]),
+    "q3_denoise_plan": (c_int, [ctypes.c_int64, P(c_int), P(c_int), P(c_int), P(ctypes.c_size_t)]),
+    "q3_ref_audio_denoise": (c_int, [P(c_void_p), c_int, P(ctypes.c_float), P(c_void_p)]),
+    "q3_ref_audio_noise": (c_int, [c_void_p, P(ctypes.c_double), P(ctypes.c_double)]),
     "q3_spk_encode_ref": (c_int, [c_void_p, c_void_p, c_void_p]),
     "q3_mimi_encode_ref": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(c_int), P(c_void_p)]),
     "q3_mimi_pack_plan": (c_int, [P(CMimiConfig), P(ctypes.c_int64), c_int, ctypes.c_int64, P(CMimiPackClip), P(ctypes.c_int64), P(c_int), P(c_int)]),

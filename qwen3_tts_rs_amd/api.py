@@ -1881,6 +1881,20 @@ def intake_count(rate: int, n_in: int) -> int:
     return n.value
 
 
+class DenoisePlan(NamedTuple):
+    frames: int              # T
+    valid_lo: int
+    valid_hi: int
+    workspace_bytes: int     # X + P + G
+
+
+def denoise_plan(n_samples: int) -> DenoisePlan:
+    """Frames, valid frames and workspace of RefAudio.denoise for a clip of n_samples at 24 kHz (q3_denoise_plan; host only)."""
+    t = ctypes.c_int(); lo = ctypes.c_int(); hi = ctypes.c_int(); b = ctypes.c_size_t()
+    check(lib.q3_denoise_plan(int(n_samples), ctypes.byref(t), ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(b)))
+    return DenoisePlan(t.value, lo.value, hi.value, b.value)
+
+
 def _clip_of(data, sample_rate: int, fmt: str, channels: int, keep: list) -> "_lib.CClip":
     if fmt not in SRC_NAMES:
         raise ValueError(f"fmt must be one of {SRC_NAMES}, not {fmt!r}")
@@ -1937,6 +1951,28 @@ class RefAudio:
         out = np.empty(self.n_samples, np.float32); n = ctypes.c_int64()
         check(lib.q3_ref_audio_read(self._h, out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n)))
         return out
+
+    def denoise(self, reduce_db: float = 12.0) -> "RefAudio":
+        """A NEW RefAudio: this clip through the spectral noise suppressor on the device (q3_ref_audio_denoise: k_dn_analysis,
+        k_dn_gain, k_dn_synthesis). `reduce_db` in [0, 30]: the most any bin is turned down. This object is untouched."""
+        return RefAudio.denoise_many([self], reduce_db)[0]
+
+    @classmethod
+    def denoise_many(cls, refs: List["RefAudio"], reduce_db=12.0) -> List["RefAudio"]:
+        """`denoise` of many clips of one device with one launch per kernel; `reduce_db`: one value, or one per clip. All or nothing."""
+        n = len(refs)
+        db = np.ascontiguousarray(np.broadcast_to(np.asarray(reduce_db, np.float32), (n,)))
+        ins = (ctypes.c_void_p * max(1, n))(*[r._h for r in refs])
+        outs = (ctypes.c_void_p * max(1, n))()
+        check(lib.q3_ref_audio_denoise(ins, n, db.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), outs))
+        return [cls(ctypes.c_void_p(h)) for h in outs[:n]]
+
+    def noise(self) -> Tuple[float, float]:
+        """(noise_dbfs, snr_db): the clip's estimated noise level and signal-to-noise ratio from the suppressor's noise floor
+        (q3_ref_audio_noise). Clips of 384 samples or fewer are refused."""
+        nz = ctypes.c_double(); snr = ctypes.c_double()
+        check(lib.q3_ref_audio_noise(self._h, ctypes.byref(nz), ctypes.byref(snr)))
+        return nz.value, snr.value
 
     def mark_score(self, key) -> "MarkScore":
         """The watermark detector on the device (q3_ref_audio_mark_score: k_mark_fold, k_mark_corr), on the clip where the intake

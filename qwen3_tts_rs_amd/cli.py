@@ -51,6 +51,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--device", default="auto", help="auto | hip | hip:N | cuda:N (accepted as an alias)")
     # engine-specific
     ap.add_argument("--synthetic", choices=["tiny", "0.6b", "1.7b"], default=None, help="seeded random weights instead of --model-dir")
+    ap.add_argument("--ref-denoise", type=float, default=None, metavar="DB",
+                    help="with --ref-intake device: run the reference clip(s) through the spectral noise suppressor on the GPU before the "
+                         "encoders, turning no bin down by more than DB decibels (0 .. 30; RefAudio.denoise, DESIGN 4.14a)")
     ap.add_argument("--token-ids", default=None, help="comma-separated text token ids (bypasses the tokenizer)")
     ap.add_argument("--instruct-ids", default=None, help="comma-separated instruct token ids")
     ap.add_argument("--xvector-npy", default=None, help="speaker embedding [hidden] f32 (.npy) for voice cloning")
@@ -131,6 +134,10 @@ def tokenize_clips(a, dev: int) -> int:
                 raw = f.read()
             clips.append((raw[desc.data_offset:desc.data_offset + desc.data_bytes], desc.sample_rate, desc.fmt, desc.channels))
         refs = api.RefAudio.many(clips, device=dev)
+        if a.ref_denoise is not None:
+            raw_refs, refs = refs, api.RefAudio.denoise_many(refs, a.ref_denoise)
+            for r in raw_refs:
+                r.close()
         codes = enc.encode_refs(refs)
     except (api._lib.Q3Error, OSError) as e:
         print(f"error: {e}", file=sys.stderr)
@@ -356,6 +363,11 @@ def main(argv=None) -> int:
     if a.x_vector_only and a.ref_text:
         print("error: --x-vector-only and --ref-text are contradictory.\n  x_vector_only uses only the speaker embedding (no ICL).", file=sys.stderr)
         return 2
+    if a.ref_denoise is not None:
+        if a.ref_intake != "device":
+            build_parser().error("--ref-denoise requires --ref-intake device (the suppressor runs on the clip where the intake left it)")
+        if not 0.0 <= a.ref_denoise <= 30.0:
+            build_parser().error(f"--ref-denoise {a.ref_denoise}: 0 .. 30 dB")
     try:
         loud = loudness_from_args(a)
         sil = silence_from_args(a)
@@ -411,8 +423,18 @@ def main(argv=None) -> int:
             except api._lib.Q3Error as e:
                 print(f"error: {e}", file=sys.stderr)
                 return 2
+            snr = ""
+            if a.ref_denoise is not None:
+                try:
+                    if ref.n_samples > 384:      # (shorter clips have no noise estimate; the suppressor passes them through)
+                        snr = f", estimated SNR {ref.noise()[1]:.1f} dB before denoising by up to {a.ref_denoise:g} dB"
+                    raw_ref, ref = ref, ref.denoise(a.ref_denoise)
+                    raw_ref.close()
+                except api._lib.Q3Error as e:
+                    print(f"error: {e}", file=sys.stderr)
+                    return 2
             print(f"Reference audio: {a.ref_audio} ({ref.duration():.2f}s, {ref.source_rate} Hz, {ref.source_format}, "
-                  f"{ref.source_channels} ch)")
+                  f"{ref.source_channels} ch{snr})")
         else:
             ref = api.AudioBuffer.load(a.ref_audio)
             print(f"Reference audio: {a.ref_audio} ({ref.duration():.2f}s, {ref.sample_rate} Hz)")

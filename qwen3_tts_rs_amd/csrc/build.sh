@@ -37,6 +37,9 @@ done
 for f in q3_model q3_prefix_cache q3_codec_run q3_codec_stream q3_pcm_stage q3_intake q3_session q3_batcher q3_row_state q3_testapi; do
   compile "$HERE/$f.hip" "$BUILD/$f.o" "$DEV_FLAGS" "$HERE/q3_engine.h" "$HERE/q3_prefix_cache.h" "$HERE/q3_capture_lock.h" "$HERE/q3_kernels.h" "$HERE/q3_internal.h" "$HERE/q3_aql.h" "$API"
 done
+# q3_denoise: its butterflies are pairs of f32 operations, which this unit keeps as single instructions (no packed f32 forms;
+# the host pass does not know the feature and says that it ignores it)
+compile "$HERE/q3_denoise.hip" "$BUILD/q3_denoise.o" "$DEV_FLAGS -Xclang -target-feature -Xclang -packed-fp32-ops" "$HERE/q3_engine.h" "$HERE/q3_prefix_cache.h" "$HERE/q3_capture_lock.h" "$HERE/q3_kernels.h" "$HERE/q3_internal.h" "$HERE/q3_aql.h" "$API"
 compile "$HERE/q3_io.cpp" "$BUILD/q3_io.o" "$HOST_FLAGS" "$HERE/q3_internal.h" "$API"
 compile "$HERE/q3_dp.cpp" "$BUILD/q3_dp.o" "$HOST_FLAGS" "$HERE/q3_internal.h" "$API"
 compile "$HERE/q3_aql.cpp" "$BUILD/q3_aql.o" "$HOST_FLAGS" "$HERE/q3_aql.h" "$HERE/q3_capture_lock.h"

@@ -9,6 +9,8 @@
 //                    limiter) -> resampling to a requested rate as f32, PCM16 or G.711 bytes
 //   q3_intake.hip    the reference-audio intake: a clip in its on-disk sample format -> 24 kHz mono f32 on the device in one launch,
 //                    where both encoders read it
+//   q3_denoise.hip   spectral noise suppression of such a clip: STFT analysis, minimum-statistics gain, overlap-add synthesis
+//                    
 //   q3_session.hip   sessions: KV paging, the talker / code-predictor step, frame capture + own-queue submission, prefill, generate,
 //                    streaming chunks, q3_session_run / decode / get
 //   q3_batcher.hip   continuous batching: q3_session_replace (side prefill + transplant) and the native batcher q3_batcher_*
@@ -590,6 +592,13 @@ struct PsPlan { std::vector<PsDesc> desc; std::vector<size_t> off, count; size_t
 // q3_resample's filter as a table for output / input = L / M in lowest terms, out[L][128] (taps_of): the output stage's at
 // L / M = sr_out / 24000, the intake's (q3_intake.hip) at L / M = 24000 / sr_in
 Q3_HIDDEN void resampler_taps(int L, int M, std::vector<float>& out);
+// a reference clip on the device (q3_intake.hip creates it from a file's bytes, q3_denoise.hip from another one)
+struct q3_ref_audio {
+    float* dev = nullptr; int64_t n = 0; int device = 0;        // the 24 kHz samples
+    uint32_t sr_in = 0; int format = 0, channels = 0;           // what the clip was
+};
+// the intake's own stream, one per device, created by the first call there (q3_intake.hip)
+Q3_HIDDEN q3_status intake_stream(int device, hipStream_t* out);
 // the counter hash of q3_synth_fill (q3_model.hip) and its hash of a name: the mark's carrier derives its phases from them
 Q3_HIDDEN uint64_t synth_hash(uint64_t x);
 Q3_HIDDEN uint64_t synth_name_hash(const char* s);

@@ -25,11 +25,6 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-struct q3_ref_audio {
-    float* dev = nullptr; int64_t n = 0; int device = 0;        // the 24 kHz samples
-    uint32_t sr_in = 0; int format = 0, channels = 0;           // what the clip was
-};
-
 namespace {
 constexpr int IN_TILE = 256;                       // outputs per block, one per thread
 constexpr int IN_TAPS = 128, IN_HALF = 64;
@@ -297,6 +292,8 @@ q3_status intake_run(int device, int n, const q3_clip* clips, const std::vector<
     return Q3_OK;
 }
 }  // namespace
+
+q3_status intake_stream(int device, hipStream_t* out) { return in_stream(device, out); }
 
 extern "C" const float* q3i_ref_audio_dev(const q3_ref_audio* r, int64_t* n, int* device) {
     *n = r->n; *device = r->device;
