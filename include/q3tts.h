@@ -172,6 +172,16 @@ q3_status q3_model_kv_pool_trim(q3_model* m, size_t* bytes_freed);
  * (the path's tolerance is 1e-3), the 640-frame decode 20.6 -> 14.4 ms. Codec token ids never depend on it. Applies to
  * decodes started after the call; anything but 2 or 3 is Q3_INVALID_ARG. */
 q3_status q3_model_set_codec_planes(q3_model* m, int planes);
+/* Weight format of the decode GEMVs (opt-in; no reference counterpart: the reference streams the checkpoint's bf16). Q3_WEIGHTS_FP8:
+ * every talker / code-predictor projection also gets an OCP e4m3 image with one power-of-two scale per row and 128-wide K block
+ * (DESIGN 4.1a), built on the device from the resident bf16 weights, and sessions of up to 16 rows stream it wherever they ran the
+ * 16-row-tile kernels; everything else (4-row tiles, wide sessions, long-prompt prefill) keeps bf16. The quantisation of the weights is
+ * the only new rounding. HBM use goes UP by the FP8 images. A finalized device model only; Q3_UNSUPPORTED (nothing changed) while
+ * sessions of the model are alive; empties the prefix cache. A session keeps the format it was created under.
+ * q3_model_weight_info: the format, the matrices converted, and their bytes as bf16 tiles and as FP8 images (0 under BF16). */
+enum { Q3_WEIGHTS_BF16 = 0, Q3_WEIGHTS_FP8 = 1 };
+q3_status q3_model_set_weight_format(q3_model* m, int format);
+q3_status q3_model_weight_info(const q3_model* m, int* format, int* matrices, size_t* bf16_bytes, size_t* fp8_bytes);
 q3_status q3_model_kv_pool_info(q3_model* m, int* page_positions, size_t* page_bytes, int* pages_total, int* pages_in_use, int* pages_peak);
 /* Prefix cache (opt-in, off by default; no reference counterpart: the reference builds its KV cache per call, kv_cache.rs:234-310,
  * and prefills the whole VoiceDesign prompt [instruct N][role 3][codec 5][first text 1] every time, talker.rs:585-627). Under
@@ -503,6 +513,10 @@ typedef struct q3_linear_ex_args {
     float* y; float* zero_buf;
 } q3_linear_ex_args;
 q3_status q3_linear_ex(int device, const q3_linear_ex_args* args);
+/* tiled = 3 in q3_linear_ex: the FP8 kernels — the entry quantises the row-major bf16 it is given with the device quantiser first
+ * (M <= 16 only). Test API: that quantiser's result un-tiled — codes_out [N][K] e4m3fn bytes, exps_out [N][ceil(K / 128)] scale
+ * exponents (scale = 2^e); K a multiple of 8. */
+q3_status q3_w8_quantize(int device, const uint16_t* w_bf16, int N, int K, uint8_t* codes_out, int32_t* exps_out);
 /* Test API: one decode-attention step (per-head q/k RMSNorm, rotate-half RoPE at pos, K/V append, GQA attention) over a
  * contiguous cache. variant 0 = the one-launch kernel (+ the split merge when n_splits > 1), 1 = the three-launch path,
  * 2 = the code predictor's kernel (every pos equal, < 16; n_splits 1; Q3_UNSUPPORTED otherwise). pos [B]; qkv

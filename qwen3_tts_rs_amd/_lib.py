@@ -193,6 +193,8 @@ SYMBOLS = {
     "q3_model_arena": (c_int, [c_void_p, P(c_void_p), P(ctypes.c_size_t)]),
     "q3_model_kv_pool_limit": (c_int, [c_void_p, c_int]),
     "q3_model_set_codec_planes": (c_int, [c_void_p, c_int]),
+    "q3_model_set_weight_format": (c_int, [c_void_p, c_int]),
+    "q3_model_weight_info": (c_int, [c_void_p, P(c_int), P(c_int), P(ctypes.c_size_t), P(ctypes.c_size_t)]),
     "q3_model_kv_pool_trim": (c_int, [c_void_p, P(ctypes.c_size_t)]),
     "q3_model_kv_pool_info": (c_int, [c_void_p, P(c_int), P(ctypes.c_size_t), P(c_int), P(c_int), P(c_int)]),
     "q3_model_prefix_cache": (c_int, [c_void_p, c_int]),
@@ -317,6 +319,7 @@ SYMBOLS = {
     "q3_fused_residual_rmsnorm": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p]),
     "q3_linear": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "q3_linear_ex": (c_int, [c_int, P(CLinearEx)]),
+    "q3_w8_quantize": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "q3_attn_step": (c_int, [c_int, P(CAttnStep)]),
     "q3_attn_step_ex": (c_int, [c_int, P(CAttnStepEx)]),
     "q3_kv_pages_to_bf16_ex": (c_int, [c_int] * 4 + [c_void_p] * 6),

@@ -1085,6 +1085,25 @@ class Qwen3TTS:
         (default), 2 = hi + mid planes only (PCM within 1e-4 RMS of the reference instead of 2.5e-5; 30 % less vocoder time)."""
         check(lib.q3_model_set_codec_planes(self._h, int(planes)))
 
+    def set_weight_format(self, fmt: str):
+        """Weight format of the decode GEMVs (q3_model_set_weight_format): "bf16" (default) or "fp8" — e4m3 codes with one
+        power-of-two scale per row and 128-wide K block, built on the device, for sessions of up to 16 rows. Refused while
+        sessions of the model are alive; sessions created afterwards use it."""
+        if fmt not in ("bf16", "fp8"):
+            raise ValueError(f"weight format {fmt!r}: 'bf16' or 'fp8'")
+        check(lib.q3_model_set_weight_format(self._h, 1 if fmt == "fp8" else 0))
+
+    def weight_info(self) -> dict:
+        """q3_model_weight_info: the format, the matrices converted, their bytes as bf16 tiles and as FP8 images."""
+        f, n = ctypes.c_int(), ctypes.c_int()
+        b16, b8 = ctypes.c_size_t(), ctypes.c_size_t()
+        check(lib.q3_model_weight_info(self._h, ctypes.byref(f), ctypes.byref(n), ctypes.byref(b16), ctypes.byref(b8)))
+        return {"format": "fp8" if f.value == 1 else "bf16", "matrices": n.value, "bf16_bytes": b16.value, "fp8_bytes": b8.value}
+
+    @property
+    def weight_format(self) -> str:
+        return self.weight_info()["format"]
+
     def kv_pool_trim(self) -> int:
         """Slabs of the KV page pool that hold no page in use go back to the device (q3_model_kv_pool_trim); bytes freed."""
         n = ctypes.c_size_t()
@@ -2097,6 +2116,17 @@ def linear_ex(x: np.ndarray, w_bf16: np.ndarray, *, w2_bf16: Optional[np.ndarray
         a.zero_buf = ptr(zero_buf); a.zero_n = zero_n; a.zero_guard = zero_buf.size - zero_n
     check(lib.q3_linear_ex(device, ctypes.byref(a)))
     return y
+
+
+def w8_quantize(w_bf16: np.ndarray, device: int = 0):
+    """q3_w8_quantize: the device quantiser's FP8 image of a row-major bf16 matrix [N][K], un-tiled — (codes u8 [N][K] e4m3fn,
+    exps i32 [N][ceil(K / 128)], scale = 2^e per row and 128-wide K block)."""
+    w = np.ascontiguousarray(w_bf16, dtype=np.uint16); assert w.ndim == 2
+    N, K = w.shape
+    codes = np.zeros((N, K), dtype=np.uint8); exps = np.zeros((N, (K + 127) // 128), dtype=np.int32)
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    check(lib.q3_w8_quantize(device, ptr(w), N, K, ptr(codes), ptr(exps)))
+    return codes, exps
 
 
 def attn_step(variant: int, qkv: np.ndarray, pos, q_norm_w: np.ndarray, k_norm_w: np.ndarray, eps: float, rope_cos: np.ndarray,

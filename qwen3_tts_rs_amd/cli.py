@@ -100,6 +100,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
                     help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
                          "first token to the first audio; writes the same WAV as without the flag)")
+    ap.add_argument("--weight-format", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: e4m3 block-scaled weights in the decode GEMVs of sessions of up to 16 rows (opt-in; the default streams bf16)")
     ap.add_argument("--prefix-cache", type=int, default=0, metavar="PAGES",
                     help="keep up to PAGES KV pages (128 positions each) of prefilled --instruct prompts for later requests of this model (0 = off)")
     ap.add_argument("--no-eos", action="store_true", help="disable EOS (fixed-length runs on synthetic weights)")
@@ -406,6 +408,8 @@ def main(argv=None) -> int:
         model = q.Qwen3TTS.from_pretrained(a.model_dir, device=dev)
     print(f"Loaded model in {time.time() - t0:.2f}s ({model.config.name}, type {model.model_type.name if model.model_type else 'unknown'}, "
           f"tokenizer: {tok.kind if tok else 'none (--token-ids)'})")
+    if a.weight_format != "bf16":
+        model.set_weight_format(a.weight_format)
     if a.prefix_cache > 0:
         model.prefix_cache(a.prefix_cache)
     ids = [int(x) for x in a.token_ids.split(",")] if a.token_ids else tok.encode(a.text)

@@ -107,7 +107,8 @@ struct Slot {
     size_t offset2 = 0; bool dual = false;   // plus a 4-row-tile image at `offset2` when the projection is narrow
 };
 // a GEMV weight: 16-row-tile image (t1) and, for narrow projections, a 4-row-tile image (t2)
-struct TW { const uint16_t* t1 = nullptr; const uint16_t* t2 = nullptr; };
+// (+ while the model's weight format is FP8, q3_model_set_weight_format: the mode-3 image c3 and its scale bytes s3)
+struct TW { const uint16_t* t1 = nullptr; const uint16_t* t2 = nullptr; const uint8_t* c3 = nullptr; const uint8_t* s3 = nullptr; };
 struct LayerW {
     const float *in_ln, *q_norm, *k_norm, *post_ln;
     TW qkv, o, gate, up, down;
@@ -235,6 +236,10 @@ struct PrefixCache;
 struct q3_model {
     q3_config cfg{};
     int device = 0;
+    // q3_model_set_weight_format: Q3_WEIGHTS_FP8 = every talker / code-predictor GEMV matrix also has a mode-3 image (TW::c3 / s3) in
+    // w8_arena, built on the device from its 16-row-tile image; what the info call reports; sessions alive (the switch is refused then)
+    int weight_format = 0; uint8_t* w8_arena = nullptr; int w8_matrices = 0; size_t w8_bf16_bytes = 0, w8_fp8_bytes = 0;
+    std::atomic<int> n_sessions{0};
     int codec_planes = 3;  // q3_model_set_codec_planes: 3 = f32-exact bf16x3 products in the vocoder's convs, 2 = the two leading planes
     KvBudget kv_budget;    // one limit / occupancy for both pools below, in half-f32-page units
     KvPool kv_pool;
@@ -284,7 +289,7 @@ static inline int up128(int v) { return (v + 127) & ~127; }
 // constraint, launch latency is: the 4-row-tile kernel fills the chip for M <= 2 tokens (and for N <= 1024 up
 // to M = 8), the 16-row-tile kernel is cheaper per token for larger batches.
 static inline bool dual_tiled(int n_total) { return n_total < 4096; }
-static inline int kpad_for(int mode, int K) { return mode == 2 ? up128(K) : up32(K); }
+static inline int kpad_for(int mode, int K) { return mode >= 2 ? up128(K) : up32(K); }
 static inline size_t tiled_elems(int mode, int rows, int cols) {
     return mode == 2 ? (size_t)up4(rows) * up128(cols) : (size_t)up16(rows) * up32(cols);
 }
@@ -300,11 +305,21 @@ static inline int pick_mode(const TW& w, int M, int N, int K) {
     if (w.t2 && !short_k_wide(N, K) && (M <= 2 || (N <= 1024 && M <= 8))) return 2;
     return 1;
 }
-static inline void set_w(LinArgs& a, const TW& w, int M, int N, int K) {
-    a.tiled = pick_mode(w, M, N, K); a.W = a.tiled == 2 ? w.t2 : w.t1; a.Kpad = kpad_for(a.tiled, K);
+// fp8 (a session of a model in the FP8 weight format): mode 3 exactly where the pick is the 16-row tiles at M <= 16 and the matrix
+// has a mode-3 image; the 4-row tiles, wide sessions and everything else keep their bf16 images
+static inline bool use_w8(const TW& w, int mode, int M, bool fp8) { return fp8 && mode == 1 && M <= 16 && w.c3 != nullptr; }
+static inline void to_w8(LinArgs& a, const TW& w, const TW* w2, int K) {
+    a.tiled = 3; a.Kpad = kpad_for(3, K); a.W = reinterpret_cast<const uint16_t*>(w.c3); a.S = w.s3;
+    if (w2) { a.W2 = reinterpret_cast<const uint16_t*>(w2->c3); a.S2 = w2->s3; }
 }
-static inline void set_w2(LinArgs& a, const TW& w, const TW& w2, int M, int N, int K) {
+static inline void set_w(LinArgs& a, const TW& w, int M, int N, int K, bool fp8 = false) {
+    a.tiled = pick_mode(w, M, N, K); a.W = a.tiled == 2 ? w.t2 : w.t1; a.Kpad = kpad_for(a.tiled, K);
+    if (use_w8(w, a.tiled, M, fp8)) to_w8(a, w, nullptr, K);
+}
+static inline void set_w2(LinArgs& a, const TW& w, const TW& w2, int M, int N, int K, bool fp8 = false) {
     set_w(a, w, M, N, K); a.W2 = a.tiled == 2 ? w2.t2 : w2.t1;
+    if (use_w8(w, a.tiled, M, fp8) && w2.c3) to_w8(a, w, &w2, K);
+    else if (a.tiled == 3) { a.tiled = 1; a.W = w.t1; a.S = nullptr; a.Kpad = kpad_for(1, K); }      // (a pair converts together or not at all)
 }
 // session-lifetime device blocks from the per-device size-class cache (q3_codec_run.hip)
 Q3_HIDDEN hipError_t dev_malloc(void** p, size_t bytes);
@@ -468,6 +483,7 @@ struct q3_session {
     int kv_overflow_row = -1;             // the row whose page request the pool refused (kv_reserve_row): the batcher fails that row alone
     // bf16 K/V (opt-in, q3_session_set_kv_dtype; the reference GPU path's cache dtype): the prompt is prefilled into f32 pages
     // as always, converted once into pages of the bf16 pool (kv_in_bf16 from then on), and the decode attention reads / appends bf16
+    bool w_fp8 = false;      // the model's weight format when this session was created (q3_model_set_weight_format): read once, before any capture
     bool kv_bf16 = false, kv_in_bf16 = false; unsigned long long* kv_conv = nullptr;      // kv_conv: [2][B * KV_MAX_PAGES] page lists of the conversion launch
     float *rows = nullptr, *embeds = nullptr, *xvec = nullptr; int n_rows_total = 0;
     // prefill scratch, session-lifetime (no hipMalloc / hipFree and no extra stream syncs on the time-to-first-audio path)

@@ -63,7 +63,10 @@ struct LinArgs {
     int M = 1, N = 0, K = 0;
     int epi = EPI_NONE;
     int tiled = 0;                  // 1: 16-row MFMA tiles [N/16][Kpad/32][64 lanes][8 bf16]; 2: 4-row tiles [N/4][Kpad/128][64][8]
-    int Kpad = 0;                   // K rounded up to 32 (tiled == 1) or 128 (tiled == 2)
+                                    // 3: FP8 e4m3 codes in W / W2, 16 rows x 64 k per tile [N/16][Kpad/64][64 lanes][16 bytes] (q3_kernels_w8.hip; M <= 16)
+    int Kpad = 0;                   // K rounded up to 32 (tiled == 1) or 128 (tiled == 2, 3)
+    const uint8_t* S = nullptr;     // tiled == 3: E8M0 scale bytes of W, one per row and 128-k block [N/16][Kpad/128][16 rows]
+    const uint8_t* S2 = nullptr;    // ... of W2
     // Split-K in two (k_gemv_sk2: tiled == 1, no fused norm, epilogue none / resid): the K halves of a 16-row tile run as
     // two workgroups that ADD their results into y with f32 atomics. y MUST hold zeros when the launch starts; with exactly
     // two addends onto zero the sum does not depend on their order (f32 addition is commutative: 0 + a + b == 0 + b + a bit
@@ -84,6 +87,12 @@ size_t gemm_wide_ws_bytes(int M, int N, int K, int epi);
 hipError_t launch_gemv_tiled(const LinArgs& a, hipStream_t st);   // MFMA bf16x3 kernel (16-row tiles, tiled == 1)
 hipError_t launch_gemv_tiled4(const LinArgs& a, hipStream_t st);  // 4-row tiles on the 4x4x4 16-block MFMA (tiled == 2)
 hipError_t launch_linear_rowmajor(const LinArgs& a, hipStream_t st);   // first-generation VALU kernel
+// FP8 block-scaled weights (tiled == 3, M <= 16). hipErrorNotSupported: a combination outside the family — nothing is launched
+hipError_t launch_gemv_w8(const LinArgs& a, hipStream_t st);
+// the mode-3 image of a matrix from its mode-1 bf16 image t1, on the device: codes [w8_code_bytes], scales [w8_scale_bytes]
+size_t w8_code_bytes(int N, int K);
+size_t w8_scale_bytes(int N, int K);
+hipError_t launch_w8_build(const uint16_t* t1, int N, int K, uint8_t* codes, uint8_t* scales, hipStream_t st);
 
 // ---- long-prompt prefill (q3_kernels_prefill.hip): real GEMM over the same tiled weight image + query-blocked attention ----
 struct GemmArgs {

@@ -1401,3 +1401,6 @@ hipError_t launch_gemv_tiled(const LinArgs& a, hipStream_t st) {
 }
 
 }  // namespace q3
+
+// FP8 block-scaled weights (LinArgs::tiled == 3): the same B operand, so the same translation unit
+#include "q3_kernels_w8.hip"

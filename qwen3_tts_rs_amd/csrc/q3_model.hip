@@ -309,6 +309,7 @@ extern "C" void q3_model_free(q3_model* m) {
 void model_destroy(q3_model* m) {
     if (m->device < 0) { delete m; return; }
     hipSetDevice(m->device);
+    hipFree(m->w8_arena);
     hipFree(m->arena); hipFree(m->rope_cos); hipFree(m->rope_sin); hipFree(m->derived); hipFree(m->wpk_arena);
     hipFree((void*)m->rest_cbs_dev); hipFree((void*)m->cp_embs_dev); hipFree(m->proj_tabs); hipFree(m->qkv0_tabs);
     for (hipStream_t st : m->idle_streams) (void)hipStreamDestroy(st);
@@ -322,6 +323,69 @@ extern "C" q3_status q3_model_set_codec_planes(q3_model* m, int planes) {
     if (!m) return set_err(Q3_INVALID_ARG, "q3_model_set_codec_planes: null model");
     if (planes != 2 && planes != 3) return set_err(Q3_INVALID_ARG, "q3_model_set_codec_planes: %d (2 or 3)", planes);
     m->codec_planes = planes;
+    return Q3_OK;
+}
+
+// Weight format of the M <= 16 decode GEMVs. FP8: every talker / code-predictor GEMV matrix with a 16-row-tile image gets
+// a mode-3 image (e4m3 codes + E8M0 scale bytes) built ON THE DEVICE from that image — in one extra allocation; the bf16 images stay
+// (the 4-row tiles, wide sessions and the prefill GEMM read them). Refused while sessions are alive: a captured frame holds the
+// pointers of the format it was created under.
+struct W8Item { TW* w; int N, K; };
+static std::vector<W8Item> w8_items(q3_model* m) {
+    const q3_config& c = m->cfg;
+    std::vector<W8Item> v;
+    auto layer = [&](LayerW& L, int H, int I, int nh, int nkv) {
+        v.push_back({&L.qkv, (nh + 2 * nkv) * HEAD_DIM, H}); v.push_back({&L.o, H, nh * HEAD_DIM});
+        v.push_back({&L.gate, I, H}); v.push_back({&L.up, I, H}); v.push_back({&L.down, H, I});
+    };
+    for (auto& L : m->tl) layer(L, c.hidden, c.inter, c.n_heads, c.n_kv_heads);
+    for (auto& L : m->cl) layer(L, c.cp_hidden, c.cp_inter, c.cp_heads, c.cp_kv_heads);
+    v.push_back({&m->codec_head, c.codec_vocab, c.hidden});
+    v.push_back({&m->mtp_w, c.cp_hidden, c.hidden});
+    for (auto& h : m->cp_head) v.push_back({&h, c.cp_vocab, c.cp_hidden});
+    v.erase(std::remove_if(v.begin(), v.end(), [](const W8Item& i) { return i.w->t1 == nullptr; }), v.end());
+    return v;
+}
+extern "C" q3_status q3_model_set_weight_format(q3_model* m, int format) {
+    if (!m || m->device < 0) return set_err(Q3_INVALID_ARG, "q3_model_set_weight_format: no device model");
+    if (format != Q3_WEIGHTS_BF16 && format != Q3_WEIGHTS_FP8) return set_err(Q3_INVALID_ARG, "q3_model_set_weight_format: %d (Q3_WEIGHTS_BF16 or Q3_WEIGHTS_FP8)", format);
+    if (!m->finalized) return set_err(Q3_INVALID_ARG, "q3_model_set_weight_format: model not finalized");
+    if (m->n_sessions.load() > 0) return set_err(Q3_UNSUPPORTED, "q3_model_set_weight_format: %d session(s) of this model are alive (free them first)", m->n_sessions.load());
+    if (format == m->weight_format) return Q3_OK;
+    HIPC(hipSetDevice(m->device));
+    std::vector<W8Item> items = w8_items(m);
+    if (format == Q3_WEIGHTS_FP8) {
+        size_t total = 0, bf16 = 0;
+        std::vector<size_t> off;
+        for (const W8Item& i : items) {
+            off.push_back(total);
+            total += (w8_code_bytes(i.N, i.K) + w8_scale_bytes(i.N, i.K) + 255) & ~(size_t)255;
+            bf16 += tiled_elems(1, i.N, i.K) * 2;
+        }
+        uint8_t* arena = nullptr;
+        if (hipMalloc((void**)&arena, total ? total : 256) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "q3_model_set_weight_format: %zu bytes for the FP8 images", total); }
+        hipError_t e = hipSuccess;
+        for (size_t k = 0; k < items.size() && e == hipSuccess; ++k)
+            e = launch_w8_build(items[k].w->t1, items[k].N, items[k].K, arena + off[k], arena + off[k] + w8_code_bytes(items[k].N, items[k].K), 0);
+        if (e == hipSuccess) e = q3_hipDeviceSynchronize();
+        if (e != hipSuccess) { (void)hipFree(arena); HIPC(e); }
+        for (size_t k = 0; k < items.size(); ++k) { items[k].w->c3 = arena + off[k]; items[k].w->s3 = arena + off[k] + w8_code_bytes(items[k].N, items[k].K); }
+        m->w8_arena = arena; m->w8_matrices = (int)items.size(); m->w8_bf16_bytes = bf16; m->w8_fp8_bytes = total;
+    } else {
+        for (const W8Item& i : items) { i.w->c3 = nullptr; i.w->s3 = nullptr; }
+        HIPC(hipFree(m->w8_arena));
+        m->w8_arena = nullptr; m->w8_matrices = 0; m->w8_bf16_bytes = 0; m->w8_fp8_bytes = 0;
+    }
+    m->weight_format = format;
+    prefix_clear(m);      // cached K/V belongs to the format that produced it
+    return Q3_OK;
+}
+extern "C" q3_status q3_model_weight_info(const q3_model* m, int* format, int* matrices, size_t* bf16_bytes, size_t* fp8_bytes) {
+    if (!m) return set_err(Q3_INVALID_ARG, "q3_model_weight_info: null model");
+    if (format) *format = m->weight_format;
+    if (matrices) *matrices = m->w8_matrices;
+    if (bf16_bytes) *bf16_bytes = m->w8_bf16_bytes;
+    if (fp8_bytes) *fp8_bytes = m->w8_fp8_bytes;
     return Q3_OK;
 }
 

@@ -33,7 +33,7 @@ static hipError_t run_linear(q3_session* s, const LinArgs& a_in) {
     e = launch_linear(a, s->stream);
     hipError_t e2 = hipEventRecord(e1, s->stream);
     s->prof_events.push_back({e0, e1});
-    s->prof_event_bytes.push_back((double)a.N * a.K * 2.0 * (a.epi == EPI_SWIGLU ? 2.0 : 1.0));
+    s->prof_event_bytes.push_back((a.tiled == 3 ? (double)(w8_code_bytes(a.N, a.K) + w8_scale_bytes(a.N, a.K)) : (double)a.N * a.K * 2.0) * (a.epi == EPI_SWIGLU ? 2.0 : 1.0));
     {   // launch inventory (q3_session_profile_shapes): M, N, K, epilogue, fused input norm, reserved, tiling
         ProfShape ps{a.M, a.N, a.K, a.epi, a.norm_w ? 1 : 0, 0, a.ksplit == 2 ? 3 : a.tiled, 1};
         bool found = false;
@@ -124,7 +124,7 @@ q3_status lm_layer(q3_session* s, const LmDims& d, const LayerW& w, LmBuf& b, fl
     // sequence (chunked prefill, the code predictor's 2-token first pass)
     const int QD = d.nh * HEAD_DIM, KD = d.nkv * HEAD_DIM, B = s->B * rows_per_seq;
     LinArgs a;
-    a.N = QD + 2 * KD; a.K = d.H; set_w(a, w.qkv, B, a.N, a.K); a.x = b.X; a.ldx = d.H; a.norm_w = w.in_ln; a.eps = d.eps;
+    a.N = QD + 2 * KD; a.K = d.H; set_w(a, w.qkv, B, a.N, a.K, s->w_fp8); a.x = b.X; a.ldx = d.H; a.norm_w = w.in_ln; a.eps = d.eps;
     a.y = b.QKV; a.ldy = QD + 2 * KD; a.M = B; a.epi = EPI_NONE;
     // Wide sessions: the q|k|v GEMM hands its K-slice sums straight to the attention kernel, which adds them on the 3 x 128
     // values it needs (AttnArgs::qkv_part) — the slice-sum launch in between (93 per frame at 1.7B, 5.2 us + gap each) is gone.
@@ -209,18 +209,18 @@ q3_status lm_layer(q3_session* s, const LmDims& d, const LayerW& w, LmBuf& b, fl
             if (n_splits > 1) HIPC(launch_attn_merge(t, s->stream));
         }
     }
-    auto force16 = [&](LinArgs& l, const TW& tw) { l.tiled = 1; l.W = tw.t1; l.Kpad = kpad_for(1, l.K); l.ksplit = 2; };
+    auto force16 = [&](LinArgs& l, const TW& tw) { l.tiled = 1; l.W = tw.t1; l.Kpad = kpad_for(1, l.K); l.ksplit = 2; if (use_w8(tw, 1, l.M, s->w_fp8)) to_w8(l, tw, nullptr, l.K); };
     LinArgs o;
-    o.N = d.H; o.K = QD; set_w(o, w.o, B, o.N, o.K); o.x = b.ATT; o.ldx = QD; o.resid = b.X; o.ldr = d.H; o.y = b.SUM; o.ldy = d.H; o.M = B; o.epi = EPI_RESID;
+    o.N = d.H; o.K = QD; set_w(o, w.o, B, o.N, o.K, s->w_fp8); o.x = b.ATT; o.ldx = QD; o.resid = b.X; o.ldr = d.H; o.y = b.SUM; o.ldy = d.H; o.M = B; o.epi = EPI_RESID;
     if (o_sk) force16(o, w.o);
     HIPC(run_linear(s, o));
     LinArgs g;
-    g.N = d.I; g.K = d.H; set_w2(g, w.gate, w.up, B, g.N, g.K); g.x = b.SUM; g.ldx = d.H; g.norm_w = w.post_ln; g.eps = d.eps;
+    g.N = d.I; g.K = d.H; set_w2(g, w.gate, w.up, B, g.N, g.K, s->w_fp8); g.x = b.SUM; g.ldx = d.H; g.norm_w = w.post_ln; g.eps = d.eps;
     g.y = b.ACT; g.ldy = d.I; g.M = B; g.epi = EPI_SWIGLU;
     if (dn_sk) { g.zero = b.X; g.zero_n = B * d.H; }
     HIPC(run_linear(s, g));
     LinArgs dn;
-    dn.N = d.H; dn.K = d.I; set_w(dn, w.down, B, dn.N, dn.K); dn.x = b.ACT; dn.ldx = d.I; dn.resid = b.SUM; dn.ldr = d.H; dn.y = b.X; dn.ldy = d.H; dn.M = B; dn.epi = EPI_RESID;
+    dn.N = d.H; dn.K = d.I; set_w(dn, w.down, B, dn.N, dn.K, s->w_fp8); dn.x = b.ACT; dn.ldx = d.I; dn.resid = b.SUM; dn.ldr = d.H; dn.y = b.X; dn.ldy = d.H; dn.M = B; dn.epi = EPI_RESID;
     if (dn_sk) force16(dn, w.down);
     HIPC(run_linear(s, dn));
     return Q3_OK;
@@ -251,7 +251,7 @@ q3_status talker_step(q3_session* s, const int* pos_dev, int pos_static, bool wi
         HIPC(launch_rmsnorm(s->tb.X + (size_t)(rows_per_seq - 1) * c.hidden, rows_per_seq * c.hidden, m->norm, s->LASTH, c.hidden, s->B,
                             c.hidden, c.rms_eps, s->stream));
         LinArgs h;
-        h.N = c.codec_vocab; h.K = c.hidden; set_w(h, m->codec_head, s->B, h.N, h.K); h.x = s->LASTH; h.ldx = c.hidden; h.y = s->LOGITS; h.ldy = c.codec_vocab;
+        h.N = c.codec_vocab; h.K = c.hidden; set_w(h, m->codec_head, s->B, h.N, h.K, s->w_fp8); h.x = s->LASTH; h.ldx = c.hidden; h.y = s->LOGITS; h.ldy = c.codec_vocab;
         h.M = s->B; h.epi = EPI_NONE;
         HIPC(run_linear(s, h));
     }
@@ -284,7 +284,7 @@ static q3_status cp_run(q3_session* s) {
         const bool tabs = m->mtp_w.t1 && m->proj_tabs && s->proj_tables;
         auto project = [&](int M, int ldy, const float* x_in = nullptr) -> q3_status {
             LinArgs a;
-            a.N = CH; a.K = H; set_w(a, m->mtp_w, M, CH, H); a.x = x_in ? x_in : s->CP_IN; a.ldx = H; a.bias = m->mtp_b; a.y = s->cb.X; a.ldy = ldy;
+            a.N = CH; a.K = H; set_w(a, m->mtp_w, M, CH, H, s->w_fp8); a.x = x_in ? x_in : s->CP_IN; a.ldx = H; a.bias = m->mtp_b; a.y = s->cb.X; a.ldy = ldy;
             a.M = M; a.epi = EPI_NONE;
             HIPC(run_linear(s, a));
             return Q3_OK;
@@ -296,7 +296,7 @@ static q3_status cp_run(q3_session* s) {
         bool skip0 = false, fold0 = false;
         auto qkv_rows0 = [&](int ldx, int ldy) -> q3_status {      // run-time layer-0 qkv of the B pass-0 rows
             LinArgs a;
-            a.N = QKVD; a.K = CH; set_w(a, m->cl[0].qkv, B, QKVD, CH); a.x = s->cb.X; a.ldx = ldx; a.norm_w = m->cl[0].in_ln; a.eps = d.eps;
+            a.N = QKVD; a.K = CH; set_w(a, m->cl[0].qkv, B, QKVD, CH, s->w_fp8); a.x = s->cb.X; a.ldx = ldx; a.norm_w = m->cl[0].in_ln; a.eps = d.eps;
             a.y = s->cb.QKV; a.ldy = ldy; a.M = B; a.epi = EPI_NONE;
             HIPC(run_linear(s, a));
             return Q3_OK;
@@ -347,7 +347,7 @@ static q3_status cp_run(q3_session* s) {
                          n_pass + 1, nullptr, rows == 2 ? 0 : p, 1, rows, i == 0 && skip0, (i == 0 && fold0) ? &g : nullptr));
         if (p >= 1) {
             LinArgs h;
-            h.N = V; h.K = CH; set_w(h, m->cp_head[p - 1], B, V, CH); h.x = s->cb.X + (size_t)(rows - 1) * CH; h.ldx = rows * CH;
+            h.N = V; h.K = CH; set_w(h, m->cp_head[p - 1], B, V, CH, s->w_fp8); h.x = s->cb.X + (size_t)(rows - 1) * CH; h.ldx = rows * CH;
             h.norm_w = m->cp_norm; h.eps = c.rms_eps;
             h.y = s->CP_LOGITS + (size_t)(p - 1) * B * V; h.ldy = V; h.M = B; h.epi = EPI_NONE;
             HIPC(run_linear(s, h));
@@ -526,7 +526,8 @@ q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int fra
     std::unique_ptr<q3_session> s(new q3_session());
     s->m = m; s->B = batch; s->opts = reqs[0].opts;
     { static std::atomic<uint64_t> next_uid{1}; s->uid = next_uid.fetch_add(1); }
-    m->refs.fetch_add(1);
+    m->refs.fetch_add(1); m->n_sessions.fetch_add(1);
+    s->w_fp8 = m->weight_format == Q3_WEIGHTS_FP8;
     if (s->opts.max_length < 1) return set_err(Q3_INVALID_ARG, "max_length must be >= 1");
     s->seq.resize(batch); s->out.resize((size_t)batch);
     int rows = 0;
@@ -736,6 +737,7 @@ q3_session::~q3_session() {
     }
     if (stream && owns_stream) (void)hipStreamDestroy(stream);
     pool.release_all();                                          // the model's device must still be current for these
+    m->n_sessions.fetch_sub(1);
     if (m->refs.fetch_sub(1) == 1) model_destroy(m);          // the model handle was given up before its last session
 }
 
@@ -1124,7 +1126,7 @@ static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, i
             q3_session* sd = pk->side[j];
             HIPC(launch_rmsnorm(X + (size_t)(ps[j].row0 + ps[j].len - 1) * H, ps[j].len * H, m->norm, sd->LASTH, H, 1, H, c.rms_eps, s->stream));
             LinArgs h;
-            h.N = c.codec_vocab; h.K = H; set_w(h, m->codec_head, 1, h.N, h.K); h.x = sd->LASTH; h.ldx = H; h.y = sd->LOGITS; h.ldy = c.codec_vocab;
+            h.N = c.codec_vocab; h.K = H; set_w(h, m->codec_head, 1, h.N, h.K, s->w_fp8); h.x = sd->LASTH; h.ldx = H; h.y = sd->LOGITS; h.ldy = c.codec_vocab;
             h.M = 1; h.epi = EPI_NONE;
             HIPC(run_linear(sd, h));
         }
@@ -1134,7 +1136,7 @@ static q3_status prefill_gemm(q3_session* s, int S_all, int S, bool with_head, i
     // head on each sequence's last position (row b*ch + ch-1 of the last chunk): final norm -> LASTH, codec_head -> LOGITS
     HIPC(launch_rmsnorm(X + (size_t)(ch - 1) * H, ch * H, m->norm, s->LASTH, H, B, H, c.rms_eps, s->stream));
     LinArgs h;
-    h.N = c.codec_vocab; h.K = H; set_w(h, m->codec_head, B, h.N, h.K); h.x = s->LASTH; h.ldx = H; h.y = s->LOGITS; h.ldy = c.codec_vocab;
+    h.N = c.codec_vocab; h.K = H; set_w(h, m->codec_head, B, h.N, h.K, s->w_fp8); h.x = s->LASTH; h.ldx = H; h.y = s->LOGITS; h.ldy = c.codec_vocab;
     h.M = B; h.epi = EPI_NONE;
     HIPC(run_linear(s, h));
     HIPC(sync_frames(s));      // tmp buffers are freed on return
@@ -1736,7 +1738,7 @@ q3_status session_append_many(q3_session* s, const std::vector<TextPiece>& piece
 // the frame later is safe by default. Development switches: Q3_AQL_T_ACQ=0 / Q3_AQL_T_REL=0 keep that half of every boundary,
 // Q3_AQL_T_ONLY=<substring+substring> restricts the rule to kernels whose name holds one of the substrings (bisecting).
 static void frame_fence_policy(const char* name, int* acquire, int* release) {
-    static const char* const families[] = {"k_gemv_mfmaI", "k_gemv_sk2I", "k_gemv_gu24I", "k_gemv_ldsI", "k_gemv_mfma4I",
+    static const char* const families[] = {"k_gemv_mfmaI", "k_gemv_sk2I", "k_gemv_gu24I", "k_gemv_ldsI", "k_gemv_mfma4I", "k_gemv_w8I",
                                            "k_attn_cpI", "k_attn_fusedI", "k_attn_mergeI", "k_attn_first2I"};
     const bool drop_acq = !(getenv("Q3_AQL_T_ACQ") && atoi(getenv("Q3_AQL_T_ACQ")) == 0);
     const bool drop_rel = !(getenv("Q3_AQL_T_REL") && atoi(getenv("Q3_AQL_T_REL")) == 0);

@@ -193,7 +193,7 @@ extern "C" q3_status q3_linear_ex(int device, const q3_linear_ex_args* p) {
     const int M = p->M, N = p->N, K = p->K;
     if (M < 1 || M > Q3_MAX_BATCH || N < 1 || K < 8 || K % 8) return set_err(Q3_INVALID_ARG, "q3_linear_ex: bad shape (1 <= M <= %d, K a multiple of 8)", Q3_MAX_BATCH);
     if (p->ldx < K || p->ldx % 4 || p->ldy < N || p->M_alloc < M) return set_err(Q3_INVALID_ARG, "q3_linear_ex: bad pitch (ldx >= K, ldx %% 4 == 0, ldy >= N, M_alloc >= M)");
-    if (p->epi < EPI_NONE || p->epi > EPI_SWIGLU || p->tiled < -1 || p->tiled > 2 || p->ksplit < 1) return set_err(Q3_INVALID_ARG, "q3_linear_ex: epi 0..3, tiled -1..2, ksplit >= 1");
+    if (p->epi < EPI_NONE || p->epi > EPI_SWIGLU || p->tiled < -1 || p->tiled > 3 || p->ksplit < 1) return set_err(Q3_INVALID_ARG, "q3_linear_ex: epi 0..3, tiled -1..3, ksplit >= 1");
     if (p->epi == EPI_SWIGLU && !p->w2) return set_err(Q3_INVALID_ARG, "q3_linear_ex: SwiGLU needs a second matrix");
     if (p->epi == EPI_RESID && (!p->resid || p->ldr < N)) return set_err(Q3_INVALID_ARG, "q3_linear_ex: residual epilogue needs resid with ldr >= N");
     if (p->zero_n < 0 || p->zero_n % 4 || p->zero_guard < 0 || (p->zero_n > 0 && !p->zero_buf)) return set_err(Q3_INVALID_ARG, "q3_linear_ex: zero_n must be a multiple of 4 with a buffer");
@@ -203,17 +203,22 @@ extern "C" q3_status q3_linear_ex(int device, const q3_linear_ex_args* p) {
     HIPC(hipSetDevice(device));
     DevPool pool;
     const int nmat = p->epi == EPI_SWIGLU ? 2 : 1;
-    const size_t welems = mode == 0 ? (size_t)N * K : tiled_elems(mode, N, K);
+    const int img = mode == 3 ? 1 : mode;            // FP8 (3): the device quantiser builds its image from the 16-row-tile bf16 image
+    const size_t welems = mode == 0 ? (size_t)N * K : tiled_elems(img, N, K);
     uint16_t* w; float *x, *y, *b = nullptr, *nw = nullptr, *res = nullptr, *zb = nullptr, *ws = nullptr;
+    uint8_t* w8 = nullptr;                           // per matrix: codes, then scales
+    const size_t w8_bytes = (w8_code_bytes(N, K) + w8_scale_bytes(N, K) + 255) & ~(size_t)255;
     HIPC(pool.alloc(&w, welems * nmat));
+    if (mode == 3) HIPC(pool.alloc(&w8, w8_bytes * nmat));
     for (int i = 0; i < nmat; ++i) {
         const uint16_t* src = i ? p->w2 : p->w;
         if (mode == 0) HIPC(q3_hipMemcpy(w + (size_t)i * welems, src, welems * 2, hipMemcpyHostToDevice));
         else {
             std::vector<uint16_t> wt(welems);
-            retile_bf16(src, N, K, wt.data(), mode);
+            retile_bf16(src, N, K, wt.data(), img);
             HIPC(q3_hipMemcpy(w + (size_t)i * welems, wt.data(), welems * 2, hipMemcpyHostToDevice));
         }
+        if (mode == 3) HIPC(launch_w8_build(w + (size_t)i * welems, N, K, w8 + i * w8_bytes, w8 + i * w8_bytes + w8_code_bytes(N, K), 0));
     }
     const size_t xn = (size_t)M * p->ldx, yn = (size_t)p->M_alloc * p->ldy;
     HIPC(pool.alloc(&x, xn)); HIPC(q3_hipMemcpy(x, p->x, xn * 4, hipMemcpyHostToDevice));
@@ -234,6 +239,10 @@ extern "C" q3_status q3_linear_ex(int device, const q3_linear_ex_args* p) {
     a.W = w; a.W2 = nmat == 2 ? w + welems : nullptr; a.x = x; a.ldx = p->ldx; a.norm_w = nw; a.eps = p->eps; a.bias = b;
     a.resid = res; a.ldr = res ? p->ldr : 0; a.y = y; a.ldy = p->ldy; a.M = M; a.N = N; a.K = K; a.epi = p->epi;
     a.tiled = mode; a.Kpad = mode == 0 ? K : kpad_for(mode, K); a.ksplit = p->ksplit;
+    if (mode == 3) {
+        a.W = reinterpret_cast<const uint16_t*>(w8); a.S = w8 + w8_code_bytes(N, K);
+        if (nmat == 2) { a.W2 = reinterpret_cast<const uint16_t*>(w8 + w8_bytes); a.S2 = w8 + w8_bytes + w8_code_bytes(N, K); }
+    }
     a.zero = zb; a.zero_n = zb ? p->zero_n : 0; a.ws = ws; a.ws_bytes = ws_bytes;
     HIPC(q3_hipDeviceSynchronize());
     const hipError_t e = launch_linear(a, 0);
@@ -246,6 +255,34 @@ extern "C" q3_status q3_linear_ex(int device, const q3_linear_ex_args* p) {
     HIPC(q3_hipDeviceSynchronize());
     HIPC(q3_hipMemcpy(p->y, y, yn * 4, hipMemcpyDeviceToHost));
     if (zb) HIPC(q3_hipMemcpy(p->zero_buf, zb, zn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+// The device quantiser's result for a row-major bf16 matrix, un-tiled (tests/test_gpu_w8.py): codes [N][K] e4m3 bytes, exps
+// [N][ceil(K / 128)] — the weights take the loader's way (retile_bf16, upload), k_w8_build runs, and the host undoes the tile order.
+extern "C" q3_status q3_w8_quantize(int device, const uint16_t* w_bf16, int N, int K, uint8_t* codes_out, int32_t* exps_out) {
+    if (!w_bf16 || !codes_out || !exps_out) return set_err(Q3_INVALID_ARG, "q3_w8_quantize: null argument");
+    if (N < 1 || K < 8 || K % 8 || (int64_t)N * K > (1 << 28)) return set_err(Q3_INVALID_ARG, "q3_w8_quantize: bad shape (K a multiple of 8)");
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const size_t welems = tiled_elems(1, N, K), cb = w8_code_bytes(N, K), sb = w8_scale_bytes(N, K);
+    std::vector<uint16_t> wt(welems);
+    retile_bf16(w_bf16, N, K, wt.data(), 1);
+    uint16_t* w; uint8_t *c, *sc;
+    HIPC(pool.alloc(&w, welems)); HIPC(pool.alloc(&c, cb)); HIPC(pool.alloc(&sc, sb));
+    HIPC(q3_hipMemcpy(w, wt.data(), welems * 2, hipMemcpyHostToDevice));
+    HIPC(launch_w8_build(w, N, K, c, sc, 0));
+    HIPC(q3_hipDeviceSynchronize());
+    std::vector<uint8_t> hc(cb), hs(sb);
+    HIPC(q3_hipMemcpy(hc.data(), c, cb, hipMemcpyDeviceToHost)); HIPC(q3_hipMemcpy(hs.data(), sc, sb, hipMemcpyDeviceToHost));
+    const int NB = (K + 127) / 128;
+    for (int n = 0; n < N; ++n) {
+        for (int k = 0; k < K; ++k) {      // tile (n / 16, k / 64), slot (row n % 16, k-group (k % 32) / 8), byte 8 * ((k % 64) / 32) + k % 8
+            const size_t slot = ((size_t)(n / 16) * NB * 2 + k / 64) * 64 + ((k % 32) / 8) * 16 + n % 16;
+            codes_out[(size_t)n * K + k] = hc[slot * 16 + 8 * ((k % 64) / 32) + k % 8];
+        }
+        for (int j = 0; j < NB; ++j) exps_out[(size_t)n * NB + j] = (int32_t)hs[((size_t)(n / 16) * NB + j) * 16 + n % 16] - 127;
+    }
     return Q3_OK;
 }
 
@@ -1692,6 +1729,23 @@ extern "C" q3_status q3_session_frame_bytes(q3_session* s, int kv_len, double* w
     const double cp_pass = c.cp_layers * layer_params(c.cp_hidden, c.cp_inter, c.cp_heads, c.cp_kv_heads) + (double)c.cp_vocab * c.cp_hidden +
                            (c.hidden != c.cp_hidden ? (double)c.cp_hidden * c.hidden : 0.0);
     if (weight_bytes) *weight_bytes = 2.0 * (talker + 15.0 * cp_pass);          // bf16; SURVEY §8(d)
+    if (weight_bytes && s->w_fp8) {
+        // an FP8 session: every matrix its one-row-per-sequence steps take as mode 3 (set_w / the split-K pick of lm_layer) counts
+        // with its codes and scale bytes instead
+        const q3_model* m = s->m; const int B = s->B;
+        auto saved = [&](const TW& w, int N, int K, bool sk) {
+            const int mode = (sk && s->ksplit && B >= 3 && N <= 2048 && K >= 2048) ? 1 : pick_mode(w, B, N, K);
+            return use_w8(w, mode, B, true) ? 2.0 * N * K - (double)(w8_code_bytes(N, K) + w8_scale_bytes(N, K)) : 0.0;
+        };
+        auto layer = [&](const LayerW& L, int H, int I, int nh, int nkv) {
+            return saved(L.qkv, (nh + 2 * nkv) * HEAD_DIM, H, false) + saved(L.o, H, nh * HEAD_DIM, true) + saved(L.gate, I, H, false) + saved(L.up, I, H, false) + saved(L.down, H, I, true);
+        };
+        double t = saved(m->codec_head, c.codec_vocab, c.hidden, false), p = saved(m->cp_head[0], c.cp_vocab, c.cp_hidden, false);
+        if (m->mtp_w.t1) p += saved(m->mtp_w, c.cp_hidden, c.hidden, false);
+        for (const auto& L : m->tl) t += layer(L, c.hidden, c.inter, c.n_heads, c.n_kv_heads);
+        for (const auto& L : m->cl) p += layer(L, c.cp_hidden, c.cp_inter, c.cp_heads, c.cp_kv_heads);
+        *weight_bytes -= t + 15.0 * p;
+    }
     if (kv_bytes) {
         const double kv_tok = 2.0 * c.n_kv_heads * HEAD_DIM * (s->kv_bf16 ? 2.0 : 4.0) * c.n_layers;   // f32 K/V (default) or a bf16 session's
         const double cp_tok = 2.0 * c.cp_kv_heads * HEAD_DIM * 4.0 * c.cp_layers;
