@@ -91,7 +91,7 @@ typedef struct q3_options {
 } q3_options;
 
 enum { Q3_MODE_CUSTOM_VOICE = 0, Q3_MODE_VOICE_CLONE = 1, Q3_MODE_VOICE_DESIGN = 2 };
-enum { Q3_DTYPE_F32 = 0, Q3_DTYPE_BF16 = 1 };
+enum { Q3_DTYPE_F32 = 0, Q3_DTYPE_BF16 = 1, Q3_DTYPE_FP8_E4M3 = 2 };     /* FP8: a K/V cache dtype only (q3_session_set_kv_dtype) */
 
 /* One utterance. Replaces the argument lists of synthesize_with_voice (lib.rs:718-724),
  * synthesize_voice_design (lib.rs:802-808) and the x-vector-only branch of
@@ -156,7 +156,8 @@ q3_status q3_model_mark_loaded(q3_model* m);
  * q3_session_replace relinks the prefilled pages into the row instead of copying them.
  * q3_model_kv_pool_limit: the most pages the model's sessions may hold at once (0 = no limit but HBM); a session that
  * needs a page beyond it fails with Q3_KV_OVERFLOW before it runs (the reference's overflow bail). ONE budget covers f32 and
- * bf16 sessions (q3_session_set_kv_dtype): pages are counted in f32 equivalents, a bf16 page is half of one — the f32 pages a
+ * bf16 / KV8 sessions (q3_session_set_kv_dtype): pages are counted in f32 equivalents, a bf16 page is half of one, a KV8 page
+ * 33/128 of one (figures are rounded up) — the f32 pages a
  * bf16 session's prompt is prefilled into count in full until they are converted. The native batcher (q3_batcher_*) admits a
  * request only when its worst case (prompt + max_length) fits beside what the running rows may still take, so under a limit a
  * request waits in the queue instead of failing mid-generation; a request that cannot fit even alone fails on its ticket.
@@ -462,7 +463,11 @@ enum {
     Q3_GET_TOKEN = 7,           /* u32 current semantic token */
     Q3_GET_CP_LOGITS_HIST = 8   /* [frames][15][cp_vocab] (debug capture) */
 };
-/* K/V dtype of the talker cache, before q3_session_prefill: Q3_DTYPE_F32 (default — the parity contract is the reference's CPU
+/* K/V dtype of the talker cache, before q3_session_prefill (later: Q3_INVALID_ARG, as for any value but the three below).
+ * Q3_DTYPE_FP8_E4M3 ("KV8"): OCP e4m3fn codes with one power-of-two scale (an E8M0 byte) per cached row of 128 elements — 129/512
+ * of the f32 bytes; the prompt is prefilled into f32 pages and converted once, like bf16; the decode attention has a kernel of
+ * its own (k_attn_kv8). Not bit-comparable with the F32 oracle; needs the paged cache (Q3_UNSUPPORTED otherwise).
+ * Q3_DTYPE_F32 (default — the parity contract is the reference's CPU
  * F32 path) or Q3_DTYPE_BF16, the dtype of the reference GPU path's cache (kv_cache.rs:234-310; KVCache::new(..., dtype) at
  * lib.rs:450): the prompt is prefilled in f32 and converted once, decode steps append and read bf16 — half the K/V bytes per
  * frame; results are no longer bit-comparable with the F32 oracle. Needs the paged cache. */
@@ -570,6 +575,31 @@ q3_status q3_attn_step_ex(int device, const q3_attn_step_ex_args* args);
  * [2 (src, dst)][n_pages][nkv]. */
 q3_status q3_kv_pages_to_bf16_ex(int device, int n_layers, int nkv, int n_pages, const int* src_slots, const int* dst_slots,
                                  const float* src, uint16_t* dst, int* rot_used, long long* stray);
+/* Test API: one decode-attention step over KV8 pages (q3_session_set_kv_dtype(.., Q3_DTYPE_FP8_E4M3)) as a session runs it:
+ * launch_attn_kv8 (+ launch_attn_merge when n_splits > 1). The caller passes and receives the LOGICAL cache of the selected layer
+ * as e4m3 codes kcodes / vcodes [B][nkv][max_seq][128] and E8M0 scale bytes kscales / vscales [B][nkv][max_seq] (in and out: the
+ * row at pos[b] comes back as the step appended it). Slabs, page table, page_slots, kv_row_pages, rot_used and stray (in bytes)
+ * are q3_attn_step_ex's, in the KV8 pool's geometry. q|k|v from qkv [B][(nh + 2 nkv) * 128] or from slice sums; zero_buf as there.
+ * What launch_attn_kv8 refuses — g_logits set, rows_per_seq > 1, contiguous != 0 — is Q3_UNSUPPORTED with nothing launched. */
+typedef struct q3_attn_step_kv8_args {
+    int B, nh, nkv, n_splits, max_seq, rows_per_seq;
+    int n_layers, layer, n_slabs, kv_row_pages, contiguous;
+    int qkv_S, qkv_K, zero_n, zero_guard;
+    float eps, qkv_eps; int reserved;
+    const int* pos; const float* qkv; const float* q_norm_w; const float* k_norm_w;
+    const float* rope_cos; const float* rope_sin;
+    uint8_t* kcodes; uint8_t* vcodes; uint8_t* kscales; uint8_t* vscales; float* out;
+    const int* page_slots; int* rot_used; long long* stray;
+    const float* qkv_part; const float* qkv_ssq; const float* g_logits;
+    float* zero_buf;
+} q3_attn_step_kv8_args;
+q3_status q3_attn_step_kv8(int device, const q3_attn_step_kv8_args* args);
+/* Test API: launch_kv_pages_to_fp8 over n_pages pages: src [n_pages][n_layers][2 (K, V)][nkv][128][128] f32 is scattered into slots
+ * src_slots of pattern-filled f32 slabs, converted into slots dst_slots of pattern-filled KV8 slabs (n_slabs 1..2 of each, slots
+ * 0 .. 32 n_slabs - 1) and gathered in logical order: codes (uint8, src's shape), scales [n_pages][n_layers][2][nkv][128].
+ * stray (bytes of the destination slabs outside the pages' rows and scale bytes) and rot_used as in q3_kv_pages_to_bf16_ex. */
+q3_status q3_kv_pages_to_fp8_ex(int device, int n_layers, int nkv, int n_pages, int n_slabs, const int* src_slots, const int* dst_slots,
+                                const float* src, uint8_t* codes, uint8_t* scales, int* rot_used, long long* stray);
 /* Test API: which kernel instance the vocoder conv family runs for a shape — the launchers' own decision function, no GPU
  * needed. Returns a ConvPath code: low 5 bits the kernel (0 refused, 1 k_conv_out1, 2 k_conv_out1_v4, 3 / 4 k_lin_small_bf16x3
  * <4 | 8>, 5..11 the k_conv_bf16x3 geometries 96x128 T_M=4 / 4 waves x 32x128 / 4 waves x 32x256 / 64x128 / 64x64 / 128x128 /

@@ -74,6 +74,14 @@ class CAttnStepEx(ctypes.Structure):     # q3_attn_step_ex_args
                                                "g_codes", "g_frame_idx", "zero_buf")]
 
 
+class CAttnStepKv8(ctypes.Structure):    # q3_attn_step_kv8_args
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "nh", "nkv", "n_splits", "max_seq", "rows_per_seq", "n_layers", "layer", "n_slabs",
+                                              "kv_row_pages", "contiguous", "qkv_S", "qkv_K", "zero_n", "zero_guard")] + \
+               [("eps", ctypes.c_float), ("qkv_eps", ctypes.c_float), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("pos", "qkv", "q_norm_w", "k_norm_w", "rope_cos", "rope_sin", "kcodes", "vcodes", "kscales",
+                                               "vscales", "out", "page_slots", "rot_used", "stray", "qkv_part", "qkv_ssq", "g_logits", "zero_buf")]
+
+
 class CConvEx(ctypes.Structure):         # q3_conv_ex_args
     _fields_ = [(n, ctypes.c_int32) for n in ("kind", "cin", "cout", "L", "k", "dil", "stride", "act", "planes", "packed", "resid_in_place",
                                               "snake_raw", "y2_is_x", "y_front", "y_elems")] + [("path", ctypes.POINTER(ctypes.c_int32))] + \
@@ -323,6 +331,8 @@ SYMBOLS = {
     "q3_attn_step": (c_int, [c_int, P(CAttnStep)]),
     "q3_attn_step_ex": (c_int, [c_int, P(CAttnStepEx)]),
     "q3_kv_pages_to_bf16_ex": (c_int, [c_int] * 4 + [c_void_p] * 6),
+    "q3_attn_step_kv8": (c_int, [c_int, P(CAttnStepKv8)]),
+    "q3_kv_pages_to_fp8_ex": (c_int, [c_int] * 5 + [c_void_p] * 7),
     "q3_conv_path": (c_int, [c_int] * 10),
     "q3_resunit_path": (c_int, [c_int] * 6),
     "q3_conv_path_name": (c_char_p, [c_int]),

@@ -189,12 +189,26 @@ def fill_request(r, u: "Utterance", options: "SynthesisOptions", keep: list):
     r.opts = o
 
 
+KV_DTYPES = {"f32": 0, "bf16": 1, "fp8": 2}      # Q3_DTYPE_F32 / Q3_DTYPE_BF16 / Q3_DTYPE_FP8_E4M3
+
+
+def kv_dtype_code(kv_dtype: Optional[str], kv_bf16: bool = False) -> int:
+    if kv_dtype is None:
+        return 1 if kv_bf16 else 0
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype {kv_dtype!r}: one of {sorted(KV_DTYPES)}")
+    if kv_bf16 and kv_dtype != "bf16":
+        raise ValueError("kv_bf16=True contradicts kv_dtype=" + repr(kv_dtype))
+    return KV_DTYPES[kv_dtype]
+
+
 class Session:
     """A batch of utterances on one GPU (q3_session). Owns KV pages, RNG streams, penalty masks."""
 
     def __init__(self, model: "Qwen3TTS", utts: Sequence[Utterance], options: SynthesisOptions, debug: bool = False,
-                 frame_budget: int = 0, prompt_budget: int = 0, kv_bf16: bool = False):
-        """frame_budget / prompt_budget > 0: capacity (frames per row / prompt positions per row) for requests swapped in
+                 frame_budget: int = 0, prompt_budget: int = 0, kv_bf16: bool = False, kv_dtype: Optional[str] = None):
+        """kv_dtype: "f32" (default), "bf16" or "fp8" — the talker K/V cache (q3_session_set_kv_dtype); kv_bf16=True means "bf16".
+        frame_budget / prompt_budget > 0: capacity (frames per row / prompt positions per row) for requests swapped in
         later with a larger max_length or a longer prompt (q3_session_create_reserved); the rows of `utts` still end at
         their own limits."""
         self.model = model
@@ -215,8 +229,11 @@ class Session:
         else:
             check(lib.q3_session_create(model._h, reqs, self.B, ctypes.byref(h)))
         self._h = h
-        if kv_bf16:      # the reference GPU path's cache dtype (q3_session_set_kv_dtype): half the K/V bytes, not bit-comparable with the F32 oracle
-            check(lib.q3_session_set_kv_dtype(self._h, 1))
+        # bf16: the reference GPU path's cache dtype, half the K/V bytes; fp8: e4m3 codes + a scale byte per row, 129/512 of them.
+        # Neither is bit-comparable with the F32 oracle
+        self.kv_dtype = kv_dtype_code(kv_dtype, kv_bf16)
+        if self.kv_dtype:
+            check(lib.q3_session_set_kv_dtype(self._h, self.kv_dtype))
         if debug:
             check(lib.q3_session_set_debug(self._h, 1))
 
@@ -820,10 +837,10 @@ class StreamingSession:
     """StreamingSession (lib.rs:1484-1782): iterate to receive AudioBuffer chunks of up to
     chunk_frames*1920 samples; each chunk is decoded as an independent utterance (lib.rs:1755-1758)."""
 
-    def __init__(self, model: "Qwen3TTS", utt: Utterance, options: SynthesisOptions, continuous: bool = False):
+    def __init__(self, model: "Qwen3TTS", utt: Utterance, options: SynthesisOptions, continuous: bool = False, kv_dtype: Optional[str] = None):
         """continuous=True: chunks are decoded with left context and concatenate to exactly the non-streaming audio
         (q3_session_set_stream_mode 1); the default reproduces the reference's context-free chunk decode."""
-        self._s = Session(model, [utt], options)
+        self._s = Session(model, [utt], options, kv_dtype=kv_dtype)
         if continuous:
             check(lib.q3_session_set_stream_mode(self._s._h, 1))
         self._done = False
@@ -1141,8 +1158,9 @@ class Qwen3TTS:
         check(lib.q3_model_mark_loaded(self._h))
 
     # ---- synthesis API (lib.rs:416-501, 718-870, 1070-1110) ----
-    def session(self, utts: Sequence[Utterance], options: Optional[SynthesisOptions] = None, debug: bool = False, kv_bf16: bool = False) -> Session:
-        return Session(self, utts, options or SynthesisOptions(), debug, kv_bf16=kv_bf16)
+    def session(self, utts: Sequence[Utterance], options: Optional[SynthesisOptions] = None, debug: bool = False, kv_bf16: bool = False,
+                kv_dtype: Optional[str] = None) -> Session:
+        return Session(self, utts, options or SynthesisOptions(), debug, kv_bf16=kv_bf16, kv_dtype=kv_dtype)
 
     def synthesize(self, text_ids: Sequence[int], options: Optional[SynthesisOptions] = None) -> AudioBuffer:
         return self.synthesize_with_voice(text_ids, Speaker.Ryan, Language.English, options)
@@ -2243,6 +2261,70 @@ def kv_pages_to_bf16_ex(src: np.ndarray, src_slots, dst_slots, device: int = 0):
     ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
     check(lib.q3_kv_pages_to_bf16_ex(device, n_layers, nkv, n_pages, ptr(ss), ptr(ds), ptr(src), ptr(dst), ptr(rot), ptr(stray)))
     return dst, int(stray[0]), int(stray[1]), rot
+
+
+def attn_step_kv8(pos, q_norm_w: np.ndarray, k_norm_w: np.ndarray, eps: float, rope_cos: np.ndarray, rope_sin: np.ndarray, kcodes: np.ndarray,
+                  vcodes: np.ndarray, kscales: np.ndarray, vscales: np.ndarray, nh: int, nkv: int, n_splits: int = 1, *,
+                  qkv: Optional[np.ndarray] = None, rows_per_seq: int = 1, n_layers: int = 1, layer: int = 0, n_slabs: int = 1, kv_row_pages: int = 0,
+                  page_slots=None, contiguous: bool = False, qkv_part: Optional[np.ndarray] = None, qkv_ssq: Optional[np.ndarray] = None,
+                  qkv_K: int = 0, qkv_eps: float = 0.0, g_logits: Optional[np.ndarray] = None, zero_buf: Optional[np.ndarray] = None,
+                  zero_n: int = 0, device: int = 0) -> dict:
+    """q3_attn_step_kv8: one decode-attention step over KV8 pages (parity tests; include/q3tts.h describes the arguments). The
+    LOGICAL cache is codes [B][nkv][max_seq][128] uint8 + scale bytes [B][nkv][max_seq] uint8. Returns a dict: out [B][nh*128],
+    kcodes / vcodes / kscales / vscales (copies with the step's row appended), stray / stray_at, rot_used, zero_buf."""
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    f32 = lambda arr: np.ascontiguousarray(arr, dtype=np.float32)
+    kc, vc, ks, vs = (np.array(x, dtype=np.uint8, order="C") for x in (kcodes, vcodes, kscales, vscales))
+    assert kc.ndim == 4 and kc.shape[3] == 128 and kc.shape[1] == nkv and vc.shape == kc.shape and ks.shape == kc.shape[:3] and vs.shape == ks.shape
+    B, max_seq = kc.shape[0] * rows_per_seq, kc.shape[2]
+    ld = (nh + 2 * nkv) * 128
+    a = _lib.CAttnStepKv8()
+    if qkv is not None:
+        qkv = f32(qkv); assert qkv.shape == (B, ld)
+        a.qkv = ptr(qkv)
+    if qkv_part is not None:
+        qkv_part = f32(qkv_part); qkv_ssq = f32(qkv_ssq); assert qkv_part.ndim == 3 and qkv_part.shape[1:] == (B, ld) and qkv_ssq.shape == qkv_part.shape[:2]
+        a.qkv_part, a.qkv_ssq, a.qkv_S, a.qkv_K, a.qkv_eps = ptr(qkv_part), ptr(qkv_ssq), qkv_part.shape[0], qkv_K, qkv_eps
+    if g_logits is not None:
+        g_logits = f32(g_logits); a.g_logits = ptr(g_logits)
+    pos = np.ascontiguousarray(pos, dtype=np.int32); assert pos.shape == (kc.shape[0],)
+    qw = f32(q_norm_w); kw = f32(k_norm_w); rc = f32(rope_cos); rs = f32(rope_sin)
+    assert qw.shape == (128,) and kw.shape == (128,) and rc.shape == (max_seq, 64) and rs.shape == (max_seq, 64)
+    out = np.zeros((B, nh * 128), dtype=np.float32)
+    n_pg = (max_seq + 127) // 128
+    stray = np.array([0, -1], dtype=np.int64)
+    rot = np.full((kc.shape[0], n_pg, nkv), -1, dtype=np.int32)
+    a.B, a.nh, a.nkv, a.n_splits, a.max_seq, a.rows_per_seq = B, nh, nkv, n_splits, max_seq, rows_per_seq
+    a.n_layers, a.layer, a.n_slabs, a.kv_row_pages, a.contiguous, a.eps = n_layers, layer, n_slabs, kv_row_pages, int(contiguous), eps
+    a.pos, a.q_norm_w, a.k_norm_w, a.rope_cos, a.rope_sin = ptr(pos), ptr(qw), ptr(kw), ptr(rc), ptr(rs)
+    a.kcodes, a.vcodes, a.kscales, a.vscales, a.out, a.stray, a.rot_used = ptr(kc), ptr(vc), ptr(ks), ptr(vs), ptr(out), ptr(stray), ptr(rot)
+    if page_slots is not None:
+        page_slots = np.ascontiguousarray(page_slots, dtype=np.int32); assert page_slots.shape == (kc.shape[0], n_pg)
+        a.page_slots = ptr(page_slots)
+    res = dict(out=out, kcodes=kc, vcodes=vc, kscales=ks, vscales=vs, rot_used=rot)
+    if zero_buf is not None:
+        zb = np.array(zero_buf, dtype=np.float32, order="C"); assert zb.ndim == 1 and zb.size >= zero_n
+        a.zero_buf, a.zero_n, a.zero_guard = ptr(zb), zero_n, zb.size - zero_n
+        res["zero_buf"] = zb
+    check(lib.q3_attn_step_kv8(device, ctypes.byref(a)))
+    res["stray"], res["stray_at"] = int(stray[0]), int(stray[1])
+    return res
+
+
+def kv_pages_to_fp8_ex(src: np.ndarray, src_slots, dst_slots, n_slabs: int = 1, device: int = 0):
+    """q3_kv_pages_to_fp8_ex: launch_kv_pages_to_fp8 over src [n_pages][n_layers][2][nkv][128][128] f32, scattered into the f32
+    slots src_slots and converted into the KV8 slots dst_slots (parity tests). Returns (codes uint8 of src's shape, scale bytes
+    [n_pages][n_layers][2][nkv][128], stray, stray_at, rot_used [2 (src, dst)][n_pages][nkv])."""
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    assert src.ndim == 6 and src.shape[2] == 2 and src.shape[4:] == (128, 128)
+    n_pages, n_layers, nkv = src.shape[0], src.shape[1], src.shape[3]
+    ss = np.ascontiguousarray(src_slots, dtype=np.int32); ds = np.ascontiguousarray(dst_slots, dtype=np.int32)
+    assert ss.shape == (n_pages,) and ds.shape == (n_pages,)
+    codes = np.zeros(src.shape, dtype=np.uint8); scales = np.zeros(src.shape[:5], dtype=np.uint8)
+    rot = np.full((2, n_pages, nkv), -1, dtype=np.int32); stray = np.array([0, -1], dtype=np.int64)
+    ptr = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    check(lib.q3_kv_pages_to_fp8_ex(device, n_layers, nkv, n_pages, n_slabs, ptr(ss), ptr(ds), ptr(src), ptr(codes), ptr(scales), ptr(rot), ptr(stray)))
+    return codes, scales, int(stray[0]), int(stray[1]), rot
 
 
 def conv_path(cout: int, cin: int, L: int, k: int, dil: int = 1, phases: int = 1, packed: bool = True, has_resid: bool = False,

@@ -59,6 +59,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--xvector-npy", default=None, help="speaker embedding [hidden] f32 (.npy) for voice cloning")
     ap.add_argument("--ref-codes-bin", default=None, help="reference codec frames (codes_*.bin) for ICL voice cloning")
     ap.add_argument("--streaming", action="store_true", help="stream chunks (reports time to first audio)")
+    ap.add_argument("--kv-dtype", choices=["f32", "bf16", "fp8"], default="f32",
+                    help="talker K/V cache: f32 (default, the parity contract), bf16 (half the bytes) or fp8 (e4m3 codes + a scale byte per row)")
     ap.add_argument("--output-rate", type=int, default=24000, metavar="HZ",
                     help="with --streaming: the chunks leave through the output stage at this sample rate (8000, 16000, 44100, 48000, ...); "
                          "the WAV header carries it")
@@ -483,7 +485,7 @@ def main(argv=None) -> int:
         return 2
     if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None or sil is not None or mark is not None):
         # the chunks of the streaming session, each through the session's output stage as it leaves
-        s = model.session([utt], opts)
+        s = model.session([utt], opts, kv_dtype=a.kv_dtype)
         try:
             s.set_output(a.output_rate, fmt=a.output_format)
             if tempo != 1000:
@@ -520,7 +522,7 @@ def main(argv=None) -> int:
         elif a.output_format == "s16":
             samples = samples.astype(np.float32) / np.float32(32767.0)
     elif a.streaming:
-        ss = api.StreamingSession(model, utt, opts)
+        ss = api.StreamingSession(model, utt, opts, kv_dtype=a.kv_dtype)
         chunks = []
         for c in ss:
             if ttfa is None:
@@ -534,7 +536,7 @@ def main(argv=None) -> int:
         timing = None
         print(f"Fed {len(ids)} tokens {a.feed_tokens} at a time: first token to first audio {ttfa:.1f} ms")
     else:
-        s = model.session([utt], opts)
+        s = model.session([utt], opts, kv_dtype=a.kv_dtype)
         audio, timing = s.run()
         samples, codes = audio[0].samples, s.codes(0); s.close()
     wall = time.time() - t1

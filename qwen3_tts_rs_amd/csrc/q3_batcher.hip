@@ -91,7 +91,7 @@ static q3_status transplant_check(q3_session* s, q3_session* side, int j, int li
     if (sq.n_rows > s->row_cap) return set_err(Q3_UNSUPPORTED, "q3_session_replace: the request's %d text rows exceed the session's slot (%d rows: 1024, or the longest text of the original batch)", sq.n_rows, s->row_cap);
     if (sq.opened && sq.trailing_len + 1 > s->row_cap - 1) return set_err(Q3_UNSUPPORTED, "q3_session_replace: the open request's %d trailing text rows exceed the session's slot (%d rows)", sq.trailing_len + 1, s->row_cap - 1);
     if (s->paged != side->paged) return set_err(Q3_UNSUPPORTED, "q3_session_replace: the sessions disagree on KV paging");
-    if (s->kv_bf16 != s->kv_in_bf16) return set_err(Q3_UNSUPPORTED, "q3_session_replace: the session's K/V conversion has not happened yet");
+    if (s->kv_dtype != s->kv_in_dtype) return set_err(Q3_UNSUPPORTED, "q3_session_replace: the session's K/V conversion has not happened yet");
     // max_seq bounds a row in both layouts: the captured frame was specialised for it (key splits, the page-table form of the
     // attention kernel); with pages it reserves nothing — only the pages a row really reaches are taken from the pool
     if (sq.prefill_len + limit + 1 > s->max_seq) return set_err(Q3_KV_OVERFLOW, "q3_session_replace: prompt of %d positions + %d frames exceeds the row's KV extent (%d)", sq.prefill_len, limit, s->max_seq);
@@ -109,7 +109,7 @@ q3_status side_prefill(q3_session* host, const q3_request* reqs, const int* limi
     // (an open request: with the host's frame budget — an ICL row's length cap, which would size the side session, is not known yet)
     Q3C(session_create(host->m, rq.data(), n, open_text ? host->max_frames : 0, 0, &side_raw, borrow));
     std::unique_ptr<q3_session> side(side_raw);
-    side->kv_bf16 = host->kv_bf16;                      // the side session prefills in f32 and converts, as the host session did
+    side->kv_dtype = host->kv_dtype;                    // the side session prefills in f32 and converts, as the host session did
     side->prefix_common = prefix_common;
     if (open_text) Q3C(q3_session_open_text(side.get(), 0));       // the one request is taken with its text open
     if (open_text && closed) Q3C(q3_session_append_text(side.get(), 0, nullptr, 0, 1));      // ... and closed again: the close came before the prefill
@@ -464,15 +464,15 @@ static q3_status session_idle_row(q3_session* s, int b) {
         float* kept = row[keep];
         std::vector<float*> back;
         for (size_t i = 0; i < row.size(); ++i) if (i != keep) back.push_back(row[i]);
-        if (!back.empty()) (s->kv_in_bf16 ? s->m->kv_pool16 : s->m->kv_pool).give(back);
+        if (!back.empty()) s->m->kv_pool_of(s->kv_in_dtype).give(back);
         row.assign(1, kept);
         // EVERY entry of the row's table names the kept page (none keeps the address of a page that went back to the pool), and the
         // page is zero-filled: the frozen row goes on reading positions 0 .. pos through it, i.e. also slots this row never wrote
         // (a previous owner's bits, possibly NaN / Inf, which would then run through the sampler and the embedding gather of a row
-        // nobody reads); zeros are finite keys. One strided memset per K and V: n_layers runs of nkv * KV_PAGE_POS * HEAD_DIM elements.
+        // nobody reads); zeros are finite keys (KV8: zero codes under a zero scale byte). One strided memset per K and V: n_layers runs of nkv * KV_PAGE_POS * HEAD_DIM elements.
         std::vector<unsigned long long> ent((size_t)KV_MAX_PAGES, (unsigned long long)kept);
         HIPC(q3_hipMemcpy(s->kv_table + (size_t)b * KV_MAX_PAGES, ent.data(), ent.size() * 8, hipMemcpyHostToDevice));
-        const KvPool& pool = s->kv_in_bf16 ? s->m->kv_pool16 : s->m->kv_pool;
+        const KvPool& pool = s->m->kv_pool_of(s->kv_in_dtype);
         const size_t run_bytes = pool.run_floats * pool.elem_bytes, pitch = pool.layer_stride() * pool.elem_bytes;
         HIPC(hipMemset2DAsync(kept, pitch, 0, run_bytes, (size_t)pool.n_layers, s->stream));
         HIPC(hipMemset2DAsync((char*)kept + pool.v_delta() * pool.elem_bytes, pitch, 0, run_bytes, (size_t)pool.n_layers, s->stream));
@@ -801,13 +801,13 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
     // positions; row_worst_units) fits beside what the running rows may still come to hold and what everything else on the model
     // holds now — so a page shortage shows up here, as a request that waits in the queue (rows are running: room will come) or
     // fails on its ticket (it cannot fit even alone), never in the middle of a generation where it would stop every row.
-    auto held_units = [&](int r) -> long { return (long)b->s->kv_rows[(size_t)r].size() * (b->s->kv_in_bf16 ? 1 : 2); };
+    auto held_units = [&](int r) -> long { return (long)b->s->kv_rows[(size_t)r].size() * b->m->kv_pool_of(b->s->kv_in_dtype).unit; };
     auto admit = [&](const q3_request& rq, bool open, long* units_out, bool* wait, long extra = 0) -> bool {
         *wait = false; *units_out = 0;
         if (!b->s->paged) return true;
         const PromptShape sh = prompt_shape(rq);
         const int lim = open ? rq.opts.max_length : sh.limit;          // an open ICL ticket's length cap is not known before its text closes
-        const long units = row_worst_units(sh.prefill_len, lim, b->s->kv_bf16);
+        const long units = row_worst_units(sh.prefill_len, lim, b->m->kv_pool_of(b->s->kv_dtype).unit);
         *units_out = units;
         long mine = 0, claimed = 0; int running = 0;
         for (int r = 0; r < b->slots; ++r) {
@@ -818,7 +818,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
         // a parked ticket counts exactly as if it still sat in a row: the pages its record holds, and its worst case
         for (int64_t pid : b->parked) {
             const BatTicket& pt = *b->t[pid];
-            const long h = (long)parked_pages(pt.rec) * (b->s->kv_in_bf16 ? 1 : 2);
+            const long h = (long)parked_pages(pt.rec) * b->m->kv_pool_of(b->s->kv_in_dtype).unit;
             mine += h; claimed += std::max(pt.units, h);
             // (only a ticket that wants a row again makes a request WAIT for it: one the host holds parked may stay so for ever,
             // and a request that cannot fit beside it fails on its ticket, as it does when nothing runs)
@@ -826,7 +826,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
         }
         // pages only the prefix cache holds are reclaimable (kv_take evicts them before a row's request fails): they do not stand
         // in a request's way. A request is never discounted for the pages it hopes to find cached.
-        const long reclaim = 2L * prefix_reclaimable(b->m);
+        const long reclaim = KV_UNIT_F32 * prefix_reclaimable(b->m);
         std::lock_guard<std::mutex> g(b->m->kv_budget.mu);
         if (b->m->kv_budget.limit <= 0) return true;
         const long others = std::max(0L, b->m->kv_budget.used - mine - reclaim);
@@ -864,7 +864,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
                     if (b->stage.id == id) stage_drop(b);      // (a limit set after it was prefilled ahead) its side session goes with it
                     const PromptShape sh = prompt_shape(t.req.r);
                     bat_fail(t, set_err(Q3_KV_OVERFLOW, "KV page pool exhausted: the request's %d prompt positions + %d frames need %ld page(s) (f32 equivalents), more than the pool's limit leaves",
-                                        sh.prefill_len, sh.limit, (units + 1) / 2));
+                                        sh.prefill_len, sh.limit, kv_units_to_pages(units)));
                     finished++; continue;
                 }
                 b->queue.erase(b->queue.begin());
@@ -974,7 +974,7 @@ extern "C" q3_status q3_batcher_step(q3_batcher* b, int n_frames, int use_graph,
             {   // a fresh head that admission would keep waiting gains nothing from a free row (a parked ticket keeps its claim)
                 BatTicket& h = *b->t[b->queue.front()];
                 long units = 0; bool wait = false;
-                if (h.state != Q3_TICKET_PARKED && !admit(h.req.r, h.open, &units, &wait, b->s->kv_in_bf16 ? 1 : 2)) return Q3_OK;
+                if (h.state != Q3_TICKET_PARKED && !admit(h.req.r, h.open, &units, &wait, b->m->kv_pool_of(b->s->kv_in_dtype).unit)) return Q3_OK;
             }
             int victim = -1, most = -1;
             for (int r = 0; r < b->slots && victim < 0; ++r) {

@@ -128,9 +128,12 @@ struct UpW { const float *tw, *tb, *dww, *dwb, *nw, *nb, *p1w, *p1b, *p2w, *p2b,
 // prefilled pages of the side session into the row instead of copying extents. Pages are never cleared: the attention
 // kernels read a position only after it was written.
 // ------------------------------------------------------------------------------------------------
-// One page budget for both pools of a model (q3_model_kv_pool_limit), in UNITS of half an f32 page: an f32 page costs 2, a
-// bf16 page (same geometry, 2-byte elements) 1 — so the documented limit, the Q3_KV_OVERFLOW bail and the occupancy figures hold
-// for bf16 sessions and for the f32 pages their prompts are prefilled into alike.
+// One page budget for the pools of a model (q3_model_kv_pool_limit), in UNITS of 1/128 of an f32 page: an f32 page costs 128, a
+// bf16 page (same geometry, 2-byte elements) 64, a KV8 page (1-byte codes + one scale byte per row: 129/512 of the bytes) 33 — so
+// the documented limit, the Q3_KV_OVERFLOW bail and the occupancy figures hold for bf16 / KV8 sessions and for the f32 pages
+// their prompts are prefilled into alike. Public figures are f32-page equivalents, rounded up (kv_units_to_pages).
+constexpr long KV_UNIT_F32 = 128, KV_UNIT_BF16 = 64, KV_UNIT_FP8 = 33;
+inline long kv_units_to_pages(long units) { return (units + KV_UNIT_F32 - 1) / KV_UNIT_F32; }
 struct KvBudget {
     std::mutex mu;
     long limit = 0, used = 0, peak = 0;            // units; limit 0 = bounded by HBM only
@@ -145,11 +148,12 @@ struct KvPool {
     // V `v_delta()` floats behind K.
     static constexpr int SLAB_SLOTS = 32;
     std::mutex mu;
-    size_t run_floats = 0; int n_layers = 0;       // run = nkv * KV_PAGE_POS * HEAD_DIM ELEMENTS (one layer's K of one page)
-    size_t elem_bytes = sizeof(float);              // 4, or 2 for the pool of bf16 sessions (same geometry in elements)
+    size_t run_floats = 0; int n_layers = 0;       // run = nkv * KV_PAGE_POS * HEAD_DIM ELEMENTS (one layer's K of one page);
+                                                    // the KV8 pool: + nkv * KV_PAGE_POS scale bytes behind them (q3_kernels_kv8.hip)
+    size_t elem_bytes = sizeof(float);              // 4; 2 for the pool of bf16 sessions (same geometry in elements); 1 for KV8
     std::vector<void*> slabs; std::vector<float*> free_pages;
     int total = 0, in_use = 0;                      // pages of this pool
-    KvBudget* budget = nullptr; int unit = 2;       // the model's shared budget and what one page of this pool costs of it
+    KvBudget* budget = nullptr; long unit = KV_UNIT_F32;   // the model's shared budget and what one page of this pool costs of it
     // K -> V and layer -> layer distances are kept OFF powers of two (17 KB of padding behind every region): a lane asks for
     // the K row and the V row of a position together, and at exactly 16 MB apart the two requests meet in the same memory
     // channel (k_attn_fused 7.6 vs 6.9 us per launch at B = 8 against the contiguous caches, whose distance is arbitrary)
@@ -241,9 +245,11 @@ struct q3_model {
     int weight_format = 0; uint8_t* w8_arena = nullptr; int w8_matrices = 0; size_t w8_bf16_bytes = 0, w8_fp8_bytes = 0;
     std::atomic<int> n_sessions{0};
     int codec_planes = 3;  // q3_model_set_codec_planes: 3 = f32-exact bf16x3 products in the vocoder's convs, 2 = the two leading planes
-    KvBudget kv_budget;    // one limit / occupancy for both pools below, in half-f32-page units
+    KvBudget kv_budget;    // one limit / occupancy for the pools below, in KV_UNIT_* units
     KvPool kv_pool;
     KvPool kv_pool16;      // pages of bf16 sessions (q3_session_set_kv_dtype): the same geometry with 2-byte elements
+    KvPool kv_pool8;       // pages of KV8 sessions: 1-byte e4m3 codes, and a run's scale bytes behind its codes
+    KvPool& kv_pool_of(int dtype) { return dtype == Q3_DTYPE_FP8_E4M3 ? kv_pool8 : dtype == Q3_DTYPE_BF16 ? kv_pool16 : kv_pool; }
     PrefixCache* prefix = nullptr;      // prefilled instruct pages shared across requests (q3_prefix_cache.h; created with a device model, off until sized)
     // sessions hold pages, streams and weights of their model: the handle itself is ONE reference and every live session another;
     // whoever drops the count to zero destroys the model (q3_model_free with sessions still alive only gives up the handle's
@@ -481,10 +487,11 @@ struct q3_session {
     bool regrouped = false;              // prefix cache: a one-length session whose rows were prefilled in groups (prefix_regroup); transplant_row then also fills embeds
     bool prefix_common = false;           // prefix cache: rows that hit differently stay in this session (a group prefill_ragged formed)
     int kv_overflow_row = -1;             // the row whose page request the pool refused (kv_reserve_row): the batcher fails that row alone
-    // bf16 K/V (opt-in, q3_session_set_kv_dtype; the reference GPU path's cache dtype): the prompt is prefilled into f32 pages
-    // as always, converted once into pages of the bf16 pool (kv_in_bf16 from then on), and the decode attention reads / appends bf16
+    // bf16 / KV8 K/V (opt-in, q3_session_set_kv_dtype; bf16 is the reference GPU path's cache dtype): the prompt is prefilled into
+    // f32 pages as always, converted once into pages of the dtype's pool (kv_in_dtype == kv_dtype from then on), and the decode
+    // attention reads / appends that dtype. kv_dtype: what the session was asked for; kv_in_dtype: what its pages hold now
     bool w_fp8 = false;      // the model's weight format when this session was created (q3_model_set_weight_format): read once, before any capture
-    bool kv_bf16 = false, kv_in_bf16 = false; unsigned long long* kv_conv = nullptr;      // kv_conv: [2][B * KV_MAX_PAGES] page lists of the conversion launch
+    int kv_dtype = Q3_DTYPE_F32, kv_in_dtype = Q3_DTYPE_F32; unsigned long long* kv_conv = nullptr;      // kv_conv: [2][B * KV_MAX_PAGES] page lists of the conversion launch
     float *rows = nullptr, *embeds = nullptr, *xvec = nullptr; int n_rows_total = 0;
     // prefill scratch, session-lifetime (no hipMalloc / hipFree and no extra stream syncs on the time-to-first-audio path)
     uint32_t* ids_dev = nullptr; int *tr_dev = nullptr, *ci_dev = nullptr; float *proj_e = nullptr, *proj_h = nullptr;
@@ -675,7 +682,8 @@ Q3_HIDDEN PromptShape prompt_shape(const q3_request& r, int n_text);
 static inline PromptShape prompt_shape(const q3_request& r) { return prompt_shape(r, r.n_text); }
 // per prefill position of a row whose text rows start at row_base: the text row and the codec embedding (-1: none, -2: the x-vector, -3 - i: reference frame i)
 Q3_HIDDEN void prompt_positions(const PromptShape& sh, const q3_request& r, int row_base, int* text_row, int* codec_id);
-Q3_HIDDEN long row_worst_units(int prefill_len, int limit, bool bf16);
+inline const char* kv_dtype_name(int dtype) { return dtype == Q3_DTYPE_FP8_E4M3 ? "fp8" : dtype == Q3_DTYPE_BF16 ? "bf16" : "f32"; }
+Q3_HIDDEN long row_worst_units(int prefill_len, int limit, long unit);      // unit: what a page of the session's dtype costs (KvPool::unit)
 Q3_HIDDEN q3_request idle_request(int chunk_frames);
 Q3_HIDDEN q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int frame_budget, int prompt_budget, q3_session** out,
                                    hipStream_t borrow = nullptr);

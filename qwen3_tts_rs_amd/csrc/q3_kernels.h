@@ -164,7 +164,9 @@ struct AttnArgs {
     // a K row to its V row (both constants of the pool's slab layout)
     const unsigned long long* kv_pages = nullptr; size_t kv_layer_off = 0, kv_vdelta = 0;
     int kv_row_pages = 0;                   // most pages a row of this session can ever hold (0 = unknown: up to KV_MAX_PAGES)
-    int kv_bf16 = 0;                        // launch_attn_fused only: the pages hold bf16 (same geometry, 2-byte elements; q3_session_set_kv_dtype)
+    // what the pages hold (q3_session_set_kv_dtype): 0 = f32; 1 = bf16 (launch_attn_fused only: same geometry, 2-byte elements);
+    // 2 = KV8 (launch_attn_kv8 only: e4m3 codes + one scale byte per row, kv_layer_off / kv_vdelta in BYTES; q3_kernels_kv8.hip)
+    int kv_dtype = 0;
     float* qbuf;                            // [B][nh][128] normed+roped q
     float* part;                            // [B][nh][n_splits][PART_STRIDE]
     float* out; int ld_out;                 // [B][nh*128]
@@ -232,6 +234,10 @@ hipError_t launch_kv_planes(const AttnArgs& kv, int n_pairs, int n_pos, int tile
 // of page addresses [n_pages]; layer_stride / v_delta in ELEMENTS (the same counts in both pools)
 hipError_t launch_kv_pages_to_bf16(const unsigned long long* src_pages, const unsigned long long* dst_pages, int n_pages, int n_layers, int nkv,
                                    size_t layer_stride, size_t v_delta, hipStream_t st);
+// pages of f32 K/V -> KV8 pages (one E8M0 scale per row, RNE e4m3 codes): the strides of the source pool in floats, of the
+// destination pool in bytes
+hipError_t launch_kv_pages_to_fp8(const unsigned long long* src_pages, const unsigned long long* dst_pages, int n_pages, int n_layers, int nkv,
+                                  size_t src_layer_stride, size_t src_v_delta, size_t dst_layer_stride, size_t dst_v_delta, hipStream_t st);
 hipError_t launch_qknorm_rope_kv(const AttnArgs& a, hipStream_t st);
 hipError_t launch_attn_decode(const AttnArgs& a, hipStream_t st);
 hipError_t launch_attn_merge(const AttnArgs& a, hipStream_t st);
@@ -286,6 +292,9 @@ hipError_t launch_kv_planes_pack(const AttnArgs& kv, const PackTab& t, unsigned 
 hipError_t launch_attn_prefill_pack(const AttnArgs& a, const PackTab& t, int kernel, hipStream_t st);
 // fused q/k-norm + RoPE + KV append + attention (+ final normalisation when n_splits == 1)
 hipError_t launch_attn_fused(const AttnArgs& a, hipStream_t st);
+// the same over KV8 pages (kv_dtype == 2), partial records for launch_attn_merge when n_splits > 1. hipErrorNotSupported, nothing
+// launched: the folded gather (g_logits), rows_per_seq > 1, a contiguous cache
+hipError_t launch_attn_kv8(const AttnArgs& a, hipStream_t st);
 // the same for caches that never exceed 16 positions with the position known at launch (the code predictor's single-row
 // passes): one wave per (sequence, q head), one memory round trip; attn_cp_ok says whether the arguments qualify
 bool attn_cp_ok(const AttnArgs& a);

@@ -796,7 +796,8 @@ hipError_t launch_attn_fused(const AttnArgs& a, hipStream_t st) {
     if (a.kv_pages) {
         if (a.kv_vdelta > 0x7fffffffu) return hipErrorInvalidValue;
         const bool few = a.kv_row_pages > 0 && a.kv_row_pages <= 8;        // the session's rows never hold more than 8 pages
-        if (a.kv_bf16) {
+        if (a.kv_dtype == 2) return hipErrorInvalidValue;                  // KV8 pages have a kernel of their own (launch_attn_kv8)
+        if (a.kv_dtype == 1) {
 #define Q3_AFP16(R, P) hipLaunchKernelGGL((k_attn_fused<R, P, true>), grid, dim3(256), 0, st, a.pos_dev, reinterpret_cast<const float*>(a.kv_pages), reinterpret_cast<const float*>(a.kv_layer_off), \
                                           a.qkv, a.q_norm_w, a.k_norm_w, (int)a.kv_vdelta, pk, a)
             if (nrep == 1) { if (few) Q3_AFP16(1, 1); else Q3_AFP16(1, 2); }
@@ -1718,3 +1719,5 @@ hipError_t launch_sample(const SampleArgs& a, hipStream_t st) {
 }
 
 }  // namespace q3
+
+#include "q3_kernels_kv8.hip"

@@ -291,7 +291,10 @@ extern "C" q3_status q3_model_create(const q3_config* cfg, int device, q3_model*
     std::unique_ptr<q3_model> m(new q3_model());
     m->kv_pool.run_floats = (size_t)cfg->n_kv_heads * KV_PAGE_POS * HEAD_DIM; m->kv_pool.n_layers = cfg->n_layers;
     m->kv_pool16.run_floats = m->kv_pool.run_floats; m->kv_pool16.n_layers = cfg->n_layers; m->kv_pool16.elem_bytes = 2;
-    m->kv_pool.budget = &m->kv_budget; m->kv_pool.unit = 2; m->kv_pool16.budget = &m->kv_budget; m->kv_pool16.unit = 1;
+    // KV8: a run's scale bytes lie behind its codes, so the pool's run is 129/128 of the code bytes (q3_kernels_kv8.hip)
+    m->kv_pool8.run_floats = m->kv_pool.run_floats + (size_t)cfg->n_kv_heads * KV_PAGE_POS; m->kv_pool8.n_layers = cfg->n_layers; m->kv_pool8.elem_bytes = 1;
+    m->kv_pool.budget = &m->kv_budget; m->kv_pool.unit = KV_UNIT_F32; m->kv_pool16.budget = &m->kv_budget; m->kv_pool16.unit = KV_UNIT_BF16;
+    m->kv_pool8.budget = &m->kv_budget; m->kv_pool8.unit = KV_UNIT_FP8;
     m->cfg = *cfg; m->device = device;
     build_manifest(m.get());
     HIPC(hipMalloc((void**)&m->arena, m->arena_bytes));
@@ -393,33 +396,34 @@ extern "C" q3_status q3_model_kv_pool_limit(q3_model* m, int max_pages) {
     if (!m || m->device < 0) return set_err(Q3_INVALID_ARG, "q3_model_kv_pool_limit: no device model");
     if (max_pages < 0) return set_err(Q3_INVALID_ARG, "q3_model_kv_pool_limit: negative limit");
     std::lock_guard<std::mutex> g(m->kv_budget.mu);
-    if (max_pages > 0 && 2L * max_pages < m->kv_budget.used)
-        return set_err(Q3_INVALID_ARG, "q3_model_kv_pool_limit: %ld pages (f32 equivalents) are in use", (m->kv_budget.used + 1) / 2);
-    m->kv_budget.limit = 2L * max_pages;
+    if (max_pages > 0 && KV_UNIT_F32 * max_pages < m->kv_budget.used)
+        return set_err(Q3_INVALID_ARG, "q3_model_kv_pool_limit: %ld pages (f32 equivalents) are in use", kv_units_to_pages(m->kv_budget.used));
+    m->kv_budget.limit = KV_UNIT_F32 * max_pages;
     return Q3_OK;
 }
-// Pages are counted in f32 equivalents: a page of a bf16 session (q3_session_set_kv_dtype) is half of one, rounded up in the
-// totals below — one budget covers both pools.
+// Pages are counted in f32 equivalents: a page of a bf16 session (q3_session_set_kv_dtype) is half of one, a KV8 page 33/128 of
+// one, rounded up in the totals below — one budget covers the three pools.
 extern "C" q3_status q3_model_kv_pool_info(q3_model* m, int* page_positions, size_t* page_bytes, int* pages_total, int* pages_in_use, int* pages_peak) {
     if (!m || m->device < 0) return set_err(Q3_INVALID_ARG, "q3_model_kv_pool_info: no device model");
     int tot = 0;
     { std::lock_guard<std::mutex> g(m->kv_pool.mu); tot += m->kv_pool.total; }
     { std::lock_guard<std::mutex> g(m->kv_pool16.mu); tot += (m->kv_pool16.total + 1) / 2; }
+    { std::lock_guard<std::mutex> g(m->kv_pool8.mu); tot += (int)kv_units_to_pages(m->kv_pool8.total * KV_UNIT_FP8); }
     std::lock_guard<std::mutex> g(m->kv_budget.mu);
     if (page_positions) *page_positions = KV_PAGE_POS;
     if (page_bytes) *page_bytes = m->kv_pool.page_bytes();
     if (pages_total) *pages_total = tot;
-    if (pages_in_use) *pages_in_use = (int)((m->kv_budget.used + 1) / 2);
-    if (pages_peak) *pages_peak = (int)((m->kv_budget.peak + 1) / 2);
+    if (pages_in_use) *pages_in_use = (int)kv_units_to_pages(m->kv_budget.used);
+    if (pages_peak) *pages_peak = (int)kv_units_to_pages(m->kv_budget.peak);
     return Q3_OK;
 }
-// Slabs of either pool none of whose pages is held go back to the device (a server that has seen one very long prompt need not
+// Slabs of any pool none of whose pages is held go back to the device (a server that has seen one very long prompt need not
 // keep its ~1 GB slabs for the model's lifetime). Safe beside running sessions: held pages pin their slab.
 // Pages the prefix cache holds are held pages: they pin their slabs until the cache is cleared (q3_model_prefix_cache(m, 0)).
 extern "C" q3_status q3_model_kv_pool_trim(q3_model* m, size_t* bytes_freed) {
     if (!m || m->device < 0) return set_err(Q3_INVALID_ARG, "q3_model_kv_pool_trim: no device model");
     HIPC(hipSetDevice(m->device));
-    const size_t n = m->kv_pool.trim() + m->kv_pool16.trim();
+    const size_t n = m->kv_pool.trim() + m->kv_pool16.trim() + m->kv_pool8.trim();
     if (bytes_freed) *bytes_freed = n;
     return Q3_OK;
 }

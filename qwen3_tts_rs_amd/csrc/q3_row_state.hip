@@ -64,7 +64,7 @@ hipError_t launch_row_move(const RowSeg* segs_dev, int n_segs, size_t max_bytes,
 struct q3_parked {
     q3_model* m = nullptr; uint64_t session_uid = 0; int B = 0, max_frames = 0, H = 0, V = 0;
     SeqInfo seq; int committed = 0, n_frames = 0; bool done = false;
-    std::vector<float*> pages; bool pages_bf16 = false;
+    std::vector<float*> pages; int pages_dtype = Q3_DTYPE_F32;
     char* stash = nullptr; size_t stash_bytes = 0, block = 0; std::shared_ptr<ParkShelf> shelf;      // block: the stash's allocated size
     std::vector<uint32_t> codes_host;           // committed x 16 (q3_parked_codes: a parked ticket that is cancelled)
     // byte offsets of the parts within the stash (each a multiple of 16)
@@ -131,7 +131,7 @@ extern "C" q3_status q3_session_park_row(q3_session* s, int b, q3_parked** out) 
     if (s->aql_failed) return set_err(Q3_HIP_ERROR, "session unusable: an earlier frame submission on the AQL queue failed or timed out");
     if (!s->paged) return set_err(Q3_UNSUPPORTED, "q3_session_park_row: needs the paged K/V cache (Q3_KV_CONTIGUOUS is set)");
     if (s->debug || s->profile) return set_err(Q3_UNSUPPORTED, "q3_session_park_row: not on debug / profiling sessions");
-    if (s->kv_bf16 != s->kv_in_bf16) return set_err(Q3_UNSUPPORTED, "q3_session_park_row: the session's K/V conversion has not happened yet");
+    if (s->kv_dtype != s->kv_in_dtype) return set_err(Q3_UNSUPPORTED, "q3_session_park_row: the session's K/V conversion has not happened yet");
     if (s->seq[(size_t)b].idle) return set_err(Q3_INVALID_ARG, "q3_session_park_row: row %d is idle", b);
     if (s->seq[(size_t)b].stream_pos > 0)
         return set_err(Q3_UNSUPPORTED, "q3_session_park_row: row %d has delivered chunks (q3_session_next_chunk*): its stream position does not travel", b);
@@ -143,7 +143,7 @@ extern "C" q3_status q3_session_park_row(q3_session* s, int b, q3_parked** out) 
     std::unique_ptr<q3_parked> p(new q3_parked());
     p->session_uid = s->uid; p->B = s->B; p->max_frames = s->max_frames; p->H = c.hidden; p->V = c.codec_vocab;
     p->committed = session_row_committed(s, b); p->n_frames = q.n_frames; p->done = q.done;
-    p->n_text_rows = q.trailing_len; p->has_ready = s->text_ready != nullptr; p->pages_bf16 = s->kv_in_bf16;
+    p->n_text_rows = q.trailing_len; p->has_ready = s->text_ready != nullptr; p->pages_dtype = s->kv_in_dtype;
     size_t off = 0;
     auto part = [&](size_t bytes) { const size_t o = off; off += al16(bytes); return o; };
     p->o_lasth = part((size_t)p->H * 4); p->o_logits = part((size_t)p->V * 4); p->o_seen = part((size_t)p->V);
@@ -152,10 +152,10 @@ extern "C" q3_status q3_session_park_row(q3_session* s, int b, q3_parked** out) 
     p->o_scalars = part((size_t)16 * PS_SROW + sizeof(SampleRow));
     p->stash_bytes = off;
     // the vacated row's own page (below) and the stash: the two things that can be refused, before anything changes
-    KvPool& pool = s->kv_in_bf16 ? m->kv_pool16 : m->kv_pool;
+    KvPool& pool = m->kv_pool_of(s->kv_in_dtype);
     std::vector<float*> own;
     if (kv_take(m, pool, 1, own) != hipSuccess)
-        return set_err(Q3_KV_OVERFLOW, "q3_session_park_row: KV page pool exhausted: the vacated row needs one page of its own (budget: %ld of %ld half-pages in use)", m->kv_budget.used, m->kv_budget.limit);
+        return set_err(Q3_KV_OVERFLOW, "q3_session_park_row: KV page pool exhausted: the vacated row needs one page of its own (budget: %ld of %ld f32-equivalent pages in use)", kv_units_to_pages(m->kv_budget.used), kv_units_to_pages(m->kv_budget.limit));
     // (powers of two from 64 KB on, so that the blocks on the session's shelf fit the next record)
     size_t block = 65536; while (block < p->stash_bytes) block <<= 1;
     p->block = block; p->shelf = s->shelf;
@@ -265,7 +265,7 @@ extern "C" void q3_parked_free(q3_parked* p) {
     q3_model* m = p->m;
     if (m) {
         (void)hipSetDevice(m->device);
-        if (!p->pages.empty()) (p->pages_bf16 ? m->kv_pool16 : m->kv_pool).give(p->pages);
+        if (!p->pages.empty()) m->kv_pool_of(p->pages_dtype).give(p->pages);
         stash_give(p);
     }
     delete p;

@@ -53,12 +53,12 @@ q3_status kv_reserve_row(q3_session* s, int b, int n_pos) {
     std::vector<float*>& row = s->kv_rows[(size_t)b];
     const int need = (n_pos + KV_PAGE_POS - 1) / KV_PAGE_POS, have = (int)row.size();
     if (need <= have) return Q3_OK;
-    KvPool& pool = s->kv_in_bf16 ? s->m->kv_pool16 : s->m->kv_pool;
+    KvPool& pool = s->m->kv_pool_of(s->kv_in_dtype);
     if (kv_take(s->m, pool, need - have, row) != hipSuccess)      // (reclaims pages only the prefix cache holds before it gives up)
     {
         s->kv_overflow_row = b;
-        return set_err(Q3_KV_OVERFLOW, "KV page pool exhausted: row %d needs %d more %s page(s) of %d positions (budget: %ld of %ld half-pages in use)",
-                       b, need - have, s->kv_in_bf16 ? "bf16" : "f32", KV_PAGE_POS, s->m->kv_budget.used, s->m->kv_budget.limit);
+        return set_err(Q3_KV_OVERFLOW, "KV page pool exhausted: row %d needs %d more %s page(s) of %d positions (budget: %ld of %ld f32-equivalent pages in use)",
+                       b, need - have, kv_dtype_name(s->kv_in_dtype), KV_PAGE_POS, kv_units_to_pages(s->m->kv_budget.used), kv_units_to_pages(s->m->kv_budget.limit));
     }
     static_assert(sizeof(float*) == sizeof(unsigned long long), "page table entries are 64-bit pointers");
     HIPC(hipMemcpyAsync(s->kv_table + (size_t)b * KV_MAX_PAGES + have, row.data() + have, (size_t)(need - have) * 8, hipMemcpyHostToDevice, s->stream));
@@ -80,29 +80,35 @@ q3_status kv_reserve_frames(q3_session* s, int frames) {
     return Q3_OK;
 }
 void kv_release_row(q3_session* s, int b) {        // the caller has drained every stream that may still touch the row
-    if (s->paged && !s->kv_rows[(size_t)b].empty()) (s->kv_in_bf16 ? s->m->kv_pool16 : s->m->kv_pool).give(s->kv_rows[(size_t)b]);
+    if (s->paged && !s->kv_rows[(size_t)b].empty()) s->m->kv_pool_of(s->kv_in_dtype).give(s->kv_rows[(size_t)b]);
 }
 
-// bf16 sessions: every row's f32 pages -> as many pages of the bf16 pool (k_kv_pages_to_bf16), the table rewritten, the f32
-// pages returned (a page the prefix cache also holds stays the cache's: KvPool::give). The caller has drained the stream; this
-// drains it again before the f32 pages go back.
-static q3_status kv_convert_to_bf16(q3_session* s) {
-    if (!s->paged) return set_err(Q3_UNSUPPORTED, "bf16 K/V needs the paged cache");
+// bf16 / KV8 sessions: every row's f32 pages -> as many pages of the dtype's pool (k_kv_pages_to_bf16 / k_kv_pages_to_fp8), the
+// table rewritten, the f32 pages returned (a page the prefix cache also holds stays the cache's: KvPool::give). The caller has
+// drained the stream; this drains it again before the f32 pages go back.
+static q3_status kv_convert(q3_session* s) {
+    const char* name = kv_dtype_name(s->kv_dtype);
+    if (!s->paged) return set_err(Q3_UNSUPPORTED, "%s K/V needs the paged cache", name);
     const q3_config& c = s->m->cfg;
+    KvPool& to = s->m->kv_pool_of(s->kv_dtype);
     std::vector<unsigned long long> src, dst; std::vector<std::vector<float*>> fresh((size_t)s->B);
     q3_status st = Q3_OK;
     for (int b = 0; b < s->B && st == Q3_OK; ++b) {
         const int n = (int)s->kv_rows[(size_t)b].size();
-        if (kv_take(s->m, s->m->kv_pool16, n, fresh[(size_t)b]) != hipSuccess) { st = set_err(Q3_KV_OVERFLOW, "KV page pool (bf16) exhausted: row %d needs %d page(s)", b, n); break; }
+        if (kv_take(s->m, to, n, fresh[(size_t)b]) != hipSuccess) { st = set_err(Q3_KV_OVERFLOW, "KV page pool (%s) exhausted: row %d needs %d page(s)", name, b, n); break; }
         for (int i = 0; i < n; ++i) { src.push_back((unsigned long long)s->kv_rows[(size_t)b][(size_t)i]); dst.push_back((unsigned long long)fresh[(size_t)b][(size_t)i]); }
     }
-    if (st != Q3_OK) { for (auto& f : fresh) if (!f.empty()) s->m->kv_pool16.give(f); return st; }
+    if (st != Q3_OK) { for (auto& f : fresh) if (!f.empty()) to.give(f); return st; }
     const int n = (int)src.size();
     hipError_t e = hipMemcpyAsync(s->kv_conv, src.data(), (size_t)n * 8, hipMemcpyHostToDevice, s->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(s->kv_conv + (size_t)s->B * KV_MAX_PAGES, dst.data(), (size_t)n * 8, hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) e = launch_kv_pages_to_bf16(s->kv_conv, s->kv_conv + (size_t)s->B * KV_MAX_PAGES, n, c.n_layers, c.n_kv_heads, s->m->kv_pool.layer_stride(), s->m->kv_pool.v_delta(), s->stream);
+    const unsigned long long* dst_dev = s->kv_conv + (size_t)s->B * KV_MAX_PAGES;
+    const KvPool& from = s->m->kv_pool;
+    if (e == hipSuccess && s->kv_dtype == Q3_DTYPE_FP8_E4M3)
+        e = launch_kv_pages_to_fp8(s->kv_conv, dst_dev, n, c.n_layers, c.n_kv_heads, from.layer_stride(), from.v_delta(), to.layer_stride(), to.v_delta(), s->stream);
+    else if (e == hipSuccess) e = launch_kv_pages_to_bf16(s->kv_conv, dst_dev, n, c.n_layers, c.n_kv_heads, from.layer_stride(), from.v_delta(), s->stream);
     if (e == hipSuccess) e = sync_frames(s);
-    if (e != hipSuccess) { for (auto& f : fresh) if (!f.empty()) s->m->kv_pool16.give(f); return set_err(Q3_HIP_ERROR, "K/V conversion to bf16: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { for (auto& f : fresh) if (!f.empty()) to.give(f); return set_err(Q3_HIP_ERROR, "K/V conversion to %s: %s", name, hipGetErrorString(e)); }
     for (int b = 0; b < s->B; ++b) {
         s->m->kv_pool.give(s->kv_rows[(size_t)b]);
         s->kv_rows[(size_t)b].assign(fresh[(size_t)b].begin(), fresh[(size_t)b].end());
@@ -110,7 +116,7 @@ static q3_status kv_convert_to_bf16(q3_session* s) {
             HIPC(hipMemcpyAsync(s->kv_table + (size_t)b * KV_MAX_PAGES, s->kv_rows[(size_t)b].data(), s->kv_rows[(size_t)b].size() * 8, hipMemcpyHostToDevice, s->stream));
     }
     HIPC(sync_frames(s));
-    s->kv_in_bf16 = true;
+    s->kv_in_dtype = s->kv_dtype;
     return Q3_OK;
 }
 
@@ -148,10 +154,12 @@ q3_status lm_layer(q3_session* s, const LmDims& d, const LayerW& w, LmBuf& b, fl
     t.kcache = kc; t.vcache = vc; t.max_seq = max_seq; t.qbuf = b.Q; t.part = b.PART; t.out = b.ATT; t.ld_out = QD;
     t.B = B; t.nh = d.nh; t.nkv = d.nkv; t.n_splits = n_splits; t.rows_per_seq = rows_per_seq;
     if (paged_layer >= 0) {
-        t.kv_pages = s->kv_table; t.kv_layer_off = (size_t)paged_layer * s->m->kv_pool.layer_stride();
-        t.kv_vdelta = s->m->kv_pool.v_delta();
+        // (f32 and bf16 pools share one geometry in elements; the KV8 pool has its own, in bytes)
+        const KvPool& geo = s->kv_in_dtype == Q3_DTYPE_FP8_E4M3 ? s->m->kv_pool8 : s->m->kv_pool;
+        t.kv_pages = s->kv_table; t.kv_layer_off = (size_t)paged_layer * geo.layer_stride();
+        t.kv_vdelta = geo.v_delta();
         t.kv_row_pages = (max_seq + KV_PAGE_POS - 1) / KV_PAGE_POS;
-        t.kv_bf16 = s->kv_in_bf16 ? 1 : 0;
+        t.kv_dtype = s->kv_in_dtype;
     }
     if (wp.part) { t.qkv_part = wp.part; t.qkv_ssq = wp.ssq; t.qkv_S = wp.S; t.qkv_K = d.H; t.qkv_eps = d.eps; }
     // Split-K projections (LinArgs::ksplit, k_gemv_sk2): o-proj and down-proj with N <= 2048 and K >= 2048 at 3 .. 16 rows (wide
@@ -174,7 +182,7 @@ q3_status lm_layer(q3_session* s, const LmDims& d, const LayerW& w, LmBuf& b, fl
     // the GEMM pair — while the smaller matrices win: code predictor o 14.6 -> 6.8, down 15.7 -> 9.2, talker o 14.4 -> 11.7 us)
     const bool dn_big = B > 32 && (size_t)d.I * d.H * 2 > ((size_t)12 << 20);
     const bool dn_sk = sk_rows && !dn_big && w.down.t1 && w.gate.t1 && d.I >= 2048 && up32(d.I) / 32 >= 16;
-    if (t.kv_bf16 && (first2 || attn3)) return set_err(Q3_UNSUPPORTED, "multi-row talker steps are not available once a session's K/V is bf16");
+    if (t.kv_dtype != Q3_DTYPE_F32 && (first2 || attn3)) return set_err(Q3_UNSUPPORTED, "multi-row talker steps are not available once a session's K/V is %s", kv_dtype_name(t.kv_dtype));
     if (first2) {
         if (fold) {                                 // pass-1 gather folded: row 2b+1 = table row tok[b]
             t.g_tok = fold->tok; t.g_qkv_tab = fold->qkv_tab; t.g_proj_tab = fold->proj_tab; t.g_proj_dim = fold->proj_dim;
@@ -202,7 +210,11 @@ q3_status lm_layer(q3_session* s, const LmDims& d, const LayerW& w, LmBuf& b, fl
 #ifdef Q3_TRACE
             t.trace = s->trace_next(2, t.B, t.nh, n_splits, t.pos_static, t.g_logits ? 1 : 0);
 #endif
-            HIPC(launch_attn_fused(t, s->stream));
+            if (t.kv_dtype == Q3_DTYPE_FP8_E4M3) {
+                const hipError_t e8 = launch_attn_kv8(t, s->stream);
+                if (e8 == hipErrorNotSupported) { (void)hipGetLastError(); return set_err(Q3_UNSUPPORTED, "lm_layer: the KV8 decode attention takes one row per sequence of a paged cache and no folded gather"); }
+                HIPC(e8);
+            } else HIPC(launch_attn_fused(t, s->stream));
 #ifdef Q3_TRACE
             if (n_splits > 1) t.trace = s->trace_next(3, t.B, t.nh, n_splits, t.pos_static);
 #endif
@@ -459,10 +471,10 @@ void prompt_positions(const PromptShape& sh, const q3_request& r, int row_base, 
     }
 }
 // worst-case cost of a row against the model's KV budget (KvBudget units): every page prompt + limit + 1 positions can reach; a
-// bf16 row holds f32 pages for its prompt and, while they are converted, bf16 pages beside them
-long row_worst_units(int prefill_len, int limit, bool bf16) {
+// bf16 / KV8 row holds f32 pages for its prompt and, while they are converted, pages of its own dtype beside them
+long row_worst_units(int prefill_len, int limit, long unit) {
     const long full = (prefill_len + limit + 1 + KV_PAGE_POS - 1) / KV_PAGE_POS, pre = (prefill_len + 1 + KV_PAGE_POS - 1) / KV_PAGE_POS;
-    return bf16 ? std::max(3 * pre, full) : 2 * full;
+    return unit == KV_UNIT_F32 ? KV_UNIT_F32 * full : std::max((KV_UNIT_F32 + unit) * pre, unit * full);
 }
 // a request that only occupies a row: a one-token CustomVoice prompt with a one-frame limit, built from fixed, known-valid values
 // (ten prefill positions). Rows of the batcher's session before a ticket enters them; rows of a ragged first batch before prefill.
@@ -744,14 +756,15 @@ q3_session::~q3_session() {
 extern "C" void q3_session_free(q3_session* s) { delete s; }
 
 // K/V dtype of the talker cache (before q3_session_prefill): Q3_DTYPE_F32 (default: the parity contract is the reference's CPU
-// F32 path) or Q3_DTYPE_BF16 — the reference GPU path's cache dtype (kv_cache.rs:234-310): half the K/V bytes per frame, results
-// no longer bit-comparable with the F32 oracle. Needs the paged cache.
+// F32 path), Q3_DTYPE_BF16 — the reference GPU path's cache dtype (kv_cache.rs:234-310): half the K/V bytes per frame — or
+// Q3_DTYPE_FP8_E4M3 (KV8, DESIGN 4.2a: e4m3 codes + one power-of-two scale per row, 129/512 of the bytes). Results of the two
+// opt-in modes are not bit-comparable with the F32 oracle. Both need the paged cache.
 extern "C" q3_status q3_session_set_kv_dtype(q3_session* s, int dtype) {
     if (!s) return set_err(Q3_INVALID_ARG, "null session");
     if (s->prefilled) return set_err(Q3_INVALID_ARG, "q3_session_set_kv_dtype must be called before prefill");
-    if (dtype != Q3_DTYPE_F32 && dtype != Q3_DTYPE_BF16) return set_err(Q3_INVALID_ARG, "q3_session_set_kv_dtype: unknown dtype %d", dtype);
-    if (dtype == Q3_DTYPE_BF16 && !s->paged) return set_err(Q3_UNSUPPORTED, "bf16 K/V needs the paged cache (Q3_KV_CONTIGUOUS is set)");
-    s->kv_bf16 = dtype == Q3_DTYPE_BF16;
+    if (dtype != Q3_DTYPE_F32 && dtype != Q3_DTYPE_BF16 && dtype != Q3_DTYPE_FP8_E4M3) return set_err(Q3_INVALID_ARG, "q3_session_set_kv_dtype: unknown dtype %d", dtype);
+    if (dtype != Q3_DTYPE_F32 && !s->paged) return set_err(Q3_UNSUPPORTED, "%s K/V needs the paged cache (Q3_KV_CONTIGUOUS is set)", kv_dtype_name(dtype));
+    s->kv_dtype = dtype;
     return Q3_OK;
 }
 
@@ -1333,7 +1346,7 @@ static q3_status prefill_ragged(q3_session* s) {
     if (s->debug || s->profile) return set_err(Q3_UNSUPPORTED, "debug / profiling sessions need rows of one prefill length");
     const int B = s->B;
     for (int& v : s->prefill_info) v = 0;
-    s->kv_in_bf16 = s->kv_bf16;                          // the idle rows hold no pages: nothing to convert
+    s->kv_in_dtype = s->kv_dtype;                        // the idle rows hold no pages: nothing to convert
     s->prefilled = true; s->frames_run = 0; s->codes_host_valid = false;      // transplant_row stamps rows with start_run = frames_run
     std::vector<char> placed((size_t)B, 0);
     // prefix cache: rows of one length that would reuse different numbers of cached pages go into different groups (a batched
@@ -1570,8 +1583,8 @@ static q3_status prefill_finish(q3_session* s, const PrefillStaged& g) {
     HIPC(launch_sample(a, s->stream));
     // Callers that are going to replay the frame (q3_session_run, q3_session_next_chunk) have it captured and converted HERE, while
     // the prompt's kernels run: ~2 ms of host work that used to sit between the prefill and the first frame (time to first audio).
-    // (bf16-KV sessions capture later: which attention kernel the frame holds depends on the conversion below.)
-    if (s->precapture && !s->kv_bf16 && !s->debug && !s->profile) Q3C(frame_capture(s, true));
+    // (bf16- / KV8-KV sessions capture later: which attention kernel the frame holds depends on the conversion below.)
+    if (s->precapture && s->kv_dtype == Q3_DTYPE_F32 && !s->debug && !s->profile) Q3C(frame_capture(s, true));
     HIPC(sync_frames(s));
     if (cached) {      // the stream is drained: the rows' eligible pages that are not cached yet get a second holder, the cache (no copy)
         const PrefixRegime rg = prefix_regime(s);
@@ -1581,7 +1594,7 @@ static q3_status prefill_finish(q3_session* s, const PrefillStaged& g) {
             if (el > 0 && (int)s->kv_rows[(size_t)b].size() >= el) prefix_insert(s->m, rg, q.instruct.data(), el, s->kv_rows[(size_t)b].data());
         }
     }
-    if (s->kv_bf16 && !s->kv_in_bf16) Q3C(kv_convert_to_bf16(s));       // the prompt's K/V moves into pages of the bf16 pool, once
+    if (s->kv_dtype != s->kv_in_dtype) Q3C(kv_convert(s));       // the prompt's K/V moves into pages of the dtype's pool, once
     s->prefilled = true; s->frames_run = 0; s->codes_host_valid = false;
     return Q3_OK;
 }
@@ -1739,7 +1752,7 @@ q3_status session_append_many(q3_session* s, const std::vector<TextPiece>& piece
 // Q3_AQL_T_ONLY=<substring+substring> restricts the rule to kernels whose name holds one of the substrings (bisecting).
 static void frame_fence_policy(const char* name, int* acquire, int* release) {
     static const char* const families[] = {"k_gemv_mfmaI", "k_gemv_sk2I", "k_gemv_gu24I", "k_gemv_ldsI", "k_gemv_mfma4I", "k_gemv_w8I",
-                                           "k_attn_cpI", "k_attn_fusedI", "k_attn_mergeI", "k_attn_first2I"};
+                                           "k_attn_cpI", "k_attn_fusedI", "k_attn_mergeI", "k_attn_first2I", "k_attn_kv8I"};
     const bool drop_acq = !(getenv("Q3_AQL_T_ACQ") && atoi(getenv("Q3_AQL_T_ACQ")) == 0);
     const bool drop_rel = !(getenv("Q3_AQL_T_REL") && atoi(getenv("Q3_AQL_T_REL")) == 0);
     const std::string only = getenv("Q3_AQL_T_ONLY") ? getenv("Q3_AQL_T_ONLY") : "";

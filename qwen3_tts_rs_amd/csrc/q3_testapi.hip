@@ -539,7 +539,7 @@ extern "C" q3_status q3_attn_step_ex(int device, const q3_attn_step_ex_args* p) 
     t.B = B; t.nh = nh; t.nkv = nkv; t.n_splits = p->n_splits; t.rows_per_seq = rps;
     if (layout != 0) {
         t.kv_pages = table; t.kv_layer_off = (size_t)p->layer * slabs.geo.layer_stride(); t.kv_vdelta = slabs.geo.v_delta();
-        t.kv_row_pages = p->kv_row_pages; t.kv_bf16 = layout == 2 ? 1 : 0;
+        t.kv_row_pages = p->kv_row_pages; t.kv_dtype = layout == 2 ? Q3_DTYPE_BF16 : Q3_DTYPE_F32;
     } else { t.kcache = kv; t.vcache = kv + cn; }
     void* d = nullptr;
     const size_t gx_rows = variant == 3 ? (size_t)n_seq : (size_t)B, zn = (size_t)p->zero_n + p->zero_guard;
@@ -638,6 +638,187 @@ extern "C" q3_status q3_kv_pages_to_bf16_ex(int device, int n_layers, int nkv, i
         b.get_row(got, dst_slots[pg], elem, row.data());
         for (int dd = 0; dd < HEAD_DIM; ++dd) { uint32_t u; memcpy(&u, &row[(size_t)dd], 4); dst[at + dd] = (uint16_t)(u >> 16); }
         b.copy_row(b.img, got, dst_slots[pg], elem);
+    });
+    b.strays(got, stray);
+    return Q3_OK;
+}
+
+// ---- KV8 pages (tests/test_gpu_kv8.py): the decode attention over them and the f32 -> KV8 page conversion ----
+namespace {
+// byte offsets, within its slab, of the codes and of the scale byte of position p of (slot, layer, K | V, kv head) in a slab of the
+// KV8 pool's geometry (TestSlabs::shape_kv8)
+struct Kv8At { size_t codes, scale; };
+Kv8At kv8_at(const TestSlabs& t, int nkv, int slot, int layer, int is_v, int kvh, int p) {
+    const size_t run = (size_t)layer * t.geo.layer_stride() + (is_v ? t.geo.v_delta() : 0) + (size_t)(slot % KvPool::SLAB_SLOTS) * t.geo.run_floats;
+    const size_t row = (size_t)((p + kv_rot(t.page(slot), kvh)) & (KV_PAGE_POS - 1));
+    return {run + ((size_t)kvh * KV_PAGE_POS + row) * HEAD_DIM, run + ((size_t)nkv + 0) * KV_PAGE_POS * HEAD_DIM + (size_t)kvh * KV_PAGE_POS + row};
+}
+void shape_kv8(TestSlabs& t, int n_layers, int nkv) {      // q3_model_create's rule for kv_pool8
+    t.geo.n_layers = n_layers; t.geo.run_floats = (size_t)nkv * KV_PAGE_POS * (HEAD_DIM + 1); t.geo.elem_bytes = 1;
+}
+char* img_bytes(std::vector<std::vector<uint32_t>>& im, int slot) { return reinterpret_cast<char*>(im[(size_t)(slot / KvPool::SLAB_SLOTS)].data()); }
+}  // namespace
+
+// One decode-attention step over KV8 pages as lm_layer runs it for a KV8 session: launch_attn_kv8 (+ launch_attn_merge when
+// n_splits > 1). A launcher's refusal is a status — nothing else runs in its place.
+extern "C" q3_status q3_attn_step_kv8(int device, const q3_attn_step_kv8_args* p) {
+    if (!p || !p->pos || !p->q_norm_w || !p->k_norm_w || !p->rope_cos || !p->rope_sin || !p->kcodes || !p->vcodes || !p->kscales || !p->vscales || !p->out)
+        return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: null argument");
+    const int B = p->B, nh = p->nh, nkv = p->nkv, max_seq = p->max_seq;
+    if (B < 1 || B > Q3_MAX_BATCH || nkv < 1 || nh < nkv || nh > 64 || nh % nkv || max_seq < 1 || max_seq > KV_MAX_PAGES * KV_PAGE_POS || p->n_splits < 1 || p->n_splits > MAX_SPLITS)
+        return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: bad shape");
+    const int nrep = nh / nkv;
+    if (nrep != 1 && nrep != 2 && nrep != 4) return set_err(Q3_UNSUPPORTED, "q3_attn_step_kv8: heads / kv heads must be 1, 2 or 4");
+    const int rps = p->rows_per_seq <= 0 ? 1 : p->rows_per_seq;
+    if (rps > 8 || B % rps) return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: rows_per_seq 1..8, a divisor of B");
+    {   // what the launcher itself refuses, asked of the launcher (it decides before it touches a device)
+        AttnArgs r{};
+        r.B = B; r.nh = nh; r.nkv = nkv; r.n_splits = p->n_splits; r.rows_per_seq = rps; r.g_logits = p->g_logits;
+        r.kv_pages = p->contiguous ? nullptr : reinterpret_cast<const unsigned long long*>(p->pos);      // (only its being set is looked at)
+        if (p->g_logits || rps > 1 || p->contiguous) {
+            const hipError_t e = launch_attn_kv8(r, 0);
+            if (e == hipErrorNotSupported)
+                return set_err(Q3_UNSUPPORTED, "q3_attn_step_kv8: launch_attn_kv8 refused (g_logits %s, rows_per_seq %d, %s cache)", p->g_logits ? "set" : "unset", rps, p->contiguous ? "contiguous" : "paged");
+            return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: launch_attn_kv8 did not refuse what it cannot run");
+        }
+    }
+    const int n_seq = B;
+    for (int s = 0; s < n_seq; ++s)
+        if (p->pos[s] < 0 || p->pos[s] >= max_seq) return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: pos[%d] = %d outside the cache (%d)", s, p->pos[s], max_seq);
+    const int n_pg = (max_seq + KV_PAGE_POS - 1) / KV_PAGE_POS;
+    if (p->n_layers < 1 || p->n_layers > 4 || p->layer < 0 || p->layer >= p->n_layers || p->n_slabs < 1 || p->n_slabs > 2)
+        return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: n_layers 1..4, layer inside them, n_slabs 1..2");
+    if (!p->page_slots || !p->stray) return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: page_slots and stray are needed");
+    if (p->kv_row_pages < 0 || p->kv_row_pages > KV_MAX_PAGES || (p->kv_row_pages >= 1 && p->kv_row_pages <= 8 && p->kv_row_pages < n_pg))
+        return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: kv_row_pages 0..%d, and from 1 to 8 no fewer than the pages of max_seq (%d)", KV_MAX_PAGES, n_pg);
+    if (!slots_ok(p->page_slots, n_seq * n_pg, KvPool::SLAB_SLOTS * p->n_slabs))
+        return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: page_slots must be distinct slots of 0 .. %d", KvPool::SLAB_SLOTS * p->n_slabs - 1);
+    const bool slices = p->qkv_part != nullptr;
+    if (slices && (!p->qkv_ssq || p->qkv_S < 1 || p->qkv_S > 8 || p->qkv_K < 1)) return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: slice sums need qkv_ssq, qkv_S 1..8, qkv_K >= 1");
+    if (!p->qkv && !slices) return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: null argument (qkv)");
+    if (p->zero_n < 0 || p->zero_n % 4 || p->zero_guard < 0 || (p->zero_n > 0 && !p->zero_buf)) return set_err(Q3_INVALID_ARG, "q3_attn_step_kv8: zero_n must be a multiple of 4 with a buffer");
+
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    const int ld_qkv = (nh + 2 * nkv) * HEAD_DIM, QD = nh * HEAD_DIM;
+    const size_t rn = (size_t)max_seq * 64;
+    int* pos; float *qkv = nullptr, *qw, *kw, *rc, *rs, *part, *out;
+    unsigned long long* table = nullptr;
+    TestSlabs slabs;
+    shape_kv8(slabs, p->n_layers, nkv);
+    for (int s = 0; s < p->n_slabs; ++s) {          // (slab, table, slab: as q3_attn_step_ex)
+        if (s == 1) HIPC(pool.alloc(&table, (size_t)n_seq * KV_MAX_PAGES));
+        HIPC(slabs.add_slab(pool));
+    }
+    if (!table) HIPC(pool.alloc(&table, (size_t)n_seq * KV_MAX_PAGES));
+    HIPC(pool.alloc(&pos, (size_t)n_seq)); HIPC(pool.alloc(&qw, (size_t)HEAD_DIM)); HIPC(pool.alloc(&kw, (size_t)HEAD_DIM));
+    HIPC(pool.alloc(&rc, rn)); HIPC(pool.alloc(&rs, rn));
+    HIPC(pool.alloc(&part, (size_t)B * nh * p->n_splits * PART_STRIDE)); HIPC(pool.alloc(&out, (size_t)B * QD));
+    HIPC(q3_hipMemcpy(pos, p->pos, (size_t)n_seq * 4, hipMemcpyHostToDevice));
+    if (p->qkv) { HIPC(pool.alloc(&qkv, (size_t)B * ld_qkv)); HIPC(q3_hipMemcpy(qkv, p->qkv, (size_t)B * ld_qkv * 4, hipMemcpyHostToDevice)); }
+    HIPC(q3_hipMemcpy(qw, p->q_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(kw, p->k_norm_w, HEAD_DIM * 4, hipMemcpyHostToDevice));
+    HIPC(q3_hipMemcpy(rc, p->rope_cos, rn * 4, hipMemcpyHostToDevice)); HIPC(q3_hipMemcpy(rs, p->rope_sin, rn * 4, hipMemcpyHostToDevice));
+    auto each_row = [&](auto&& f) {             // every (sequence, kv head, position, K | V) of the logical cache: slot, offsets, logical row index
+        for (int s = 0; s < n_seq; ++s) for (int g = 0; g < nkv; ++g) for (int pp = 0; pp < max_seq; ++pp) for (int v = 0; v < 2; ++v) {
+            const int slot = p->page_slots[(size_t)s * n_pg + pp / KV_PAGE_POS];
+            f(slot, kv8_at(slabs, nkv, slot, p->layer, v, g, pp), v, ((size_t)s * nkv + g) * max_seq + pp);
+        }
+    };
+    slabs.fill_pattern();
+    each_row([&](int slot, Kv8At at, int v, size_t row) {
+        char* base = img_bytes(slabs.img, slot);
+        memcpy(base + at.codes, (v ? p->vcodes : p->kcodes) + row * HEAD_DIM, HEAD_DIM);
+        base[at.scale] = (char)(v ? p->vscales : p->kscales)[row];
+    });
+    HIPC(slabs.upload());
+    std::vector<unsigned long long> tab((size_t)n_seq * KV_MAX_PAGES);
+    for (int s = 0; s < n_seq; ++s)
+        for (int i = 0; i < KV_MAX_PAGES; ++i) tab[(size_t)s * KV_MAX_PAGES + i] = slabs.page(p->page_slots[(size_t)s * n_pg + (i < n_pg ? i : 0)]);
+    HIPC(q3_hipMemcpy(table, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    if (p->rot_used)
+        for (int s = 0; s < n_seq; ++s) for (int i = 0; i < n_pg; ++i) for (int g = 0; g < nkv; ++g)
+            p->rot_used[((size_t)s * n_pg + i) * nkv + g] = kv_rot(slabs.page(p->page_slots[(size_t)s * n_pg + i]), g);
+    auto up = [&](const void* h, size_t bytes, void** d) -> q3_status {
+        char* q; HIPC(pool.alloc(&q, bytes)); HIPC(q3_hipMemcpy(q, h, bytes, hipMemcpyHostToDevice)); *d = q;
+        return Q3_OK;
+    };
+    AttnArgs t{};
+    t.qkv = qkv; t.ld_qkv = ld_qkv; t.q_norm_w = qw; t.k_norm_w = kw; t.eps = p->eps; t.rope_cos = rc; t.rope_sin = rs;
+    t.pos_dev = pos; t.max_seq = max_seq; t.part = part; t.out = out; t.ld_out = QD;
+    t.B = B; t.nh = nh; t.nkv = nkv; t.n_splits = p->n_splits; t.rows_per_seq = 1;
+    t.kv_pages = table; t.kv_layer_off = (size_t)p->layer * slabs.geo.layer_stride(); t.kv_vdelta = slabs.geo.v_delta();
+    t.kv_row_pages = p->kv_row_pages; t.kv_dtype = Q3_DTYPE_FP8_E4M3;
+    void* d = nullptr;
+    const size_t zn = (size_t)p->zero_n + p->zero_guard;
+    if (slices) {
+        Q3C(up(p->qkv_part, (size_t)p->qkv_S * B * ld_qkv * 4, &d)); t.qkv_part = (const float*)d;
+        Q3C(up(p->qkv_ssq, (size_t)p->qkv_S * B * 4, &d)); t.qkv_ssq = (const float*)d;
+        t.qkv_S = p->qkv_S; t.qkv_K = p->qkv_K; t.qkv_eps = p->qkv_eps;
+    }
+    if (p->zero_n > 0) { Q3C(up(p->zero_buf, zn * 4, &d)); t.zero = (float*)d; t.zero_n = p->zero_n; }
+    HIPC(q3_hipDeviceSynchronize());
+    hipError_t e = launch_attn_kv8(t, 0);
+    if (e == hipSuccess && p->n_splits > 1) e = launch_attn_merge(t, 0);
+    if (e == hipErrorInvalidValue || e == hipErrorNotSupported) {
+        (void)hipGetLastError();
+        (void)q3_hipDeviceSynchronize();
+        return set_err(Q3_UNSUPPORTED, "q3_attn_step_kv8: the launcher refused nh=%d nkv=%d splits=%d (%s)", nh, nkv, p->n_splits, hipGetErrorString(e));
+    }
+    HIPC(e);
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(q3_hipMemcpy(p->out, out, (size_t)B * QD * 4, hipMemcpyDeviceToHost));
+    std::vector<std::vector<uint32_t>> got;
+    HIPC(slabs.download(got));
+    each_row([&](int slot, Kv8At at, int v, size_t row) {      // the cache as it stands; what is handed back no longer counts as stray
+        char* g = img_bytes(got, slot); char* im = img_bytes(slabs.img, slot);
+        memcpy((v ? p->vcodes : p->kcodes) + row * HEAD_DIM, g + at.codes, HEAD_DIM);
+        (v ? p->vscales : p->kscales)[row] = (uint8_t)g[at.scale];
+        memcpy(im + at.codes, g + at.codes, HEAD_DIM); im[at.scale] = g[at.scale];
+    });
+    slabs.strays(got, p->stray);
+    if (t.zero) HIPC(q3_hipMemcpy(p->zero_buf, t.zero, zn * 4, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+// launch_kv_pages_to_fp8 between slabs of the f32 pool's geometry and slabs of the KV8 pool's
+extern "C" q3_status q3_kv_pages_to_fp8_ex(int device, int n_layers, int nkv, int n_pages, int n_slabs, const int* src_slots, const int* dst_slots,
+                                           const float* src, uint8_t* codes, uint8_t* scales, int* rot_used, long long* stray) {
+    if (!src_slots || !dst_slots || !src || !codes || !scales || !stray) return set_err(Q3_INVALID_ARG, "q3_kv_pages_to_fp8_ex: null argument");
+    if (n_layers < 1 || n_layers > 4 || nkv < 1 || nkv > 8 || n_slabs < 1 || n_slabs > 2 || n_pages < 1 || n_pages > KvPool::SLAB_SLOTS * n_slabs)
+        return set_err(Q3_INVALID_ARG, "q3_kv_pages_to_fp8_ex: bad shape (n_layers 1..4, nkv 1..8, n_slabs 1..2, n_pages 1..%d)", KvPool::SLAB_SLOTS * (n_slabs > 0 ? n_slabs : 1));
+    if (!slots_ok(src_slots, n_pages, KvPool::SLAB_SLOTS * n_slabs) || !slots_ok(dst_slots, n_pages, KvPool::SLAB_SLOTS * n_slabs))
+        return set_err(Q3_INVALID_ARG, "q3_kv_pages_to_fp8_ex: the slots of a list must be distinct slots of 0 .. %d", KvPool::SLAB_SLOTS * n_slabs - 1);
+    HIPC(hipSetDevice(device));
+    DevPool pool;
+    TestSlabs a, b;
+    a.shape(n_layers, nkv, 4); shape_kv8(b, n_layers, nkv);
+    for (int s = 0; s < n_slabs; ++s) { HIPC(a.add_slab(pool)); HIPC(b.add_slab(pool)); }
+    a.fill_pattern(); b.fill_pattern();
+    auto each_row = [&](auto&& f) {
+        for (int pg = 0; pg < n_pages; ++pg) for (int l = 0; l < n_layers; ++l) for (int v = 0; v < 2; ++v) for (int g = 0; g < nkv; ++g) for (int pp = 0; pp < KV_PAGE_POS; ++pp)
+            f(pg, l, v, g, pp, ((((size_t)pg * n_layers + l) * 2 + v) * nkv + g) * KV_PAGE_POS + pp);
+    };
+    each_row([&](int pg, int l, int v, int g, int pp, size_t row) { a.put_row(a.img, src_slots[pg], a.row_elem(src_slots[pg], l, v, g, pp), src + row * HEAD_DIM); });
+    HIPC(a.upload()); HIPC(b.upload());
+    std::vector<unsigned long long> lists((size_t)2 * n_pages);
+    for (int pg = 0; pg < n_pages; ++pg) { lists[(size_t)pg] = a.page(src_slots[pg]); lists[(size_t)n_pages + pg] = b.page(dst_slots[pg]); }
+    if (rot_used)
+        for (int pg = 0; pg < n_pages; ++pg) for (int g = 0; g < nkv; ++g) {
+            rot_used[(size_t)pg * nkv + g] = kv_rot(lists[(size_t)pg], g);
+            rot_used[((size_t)n_pages + pg) * nkv + g] = kv_rot(lists[(size_t)n_pages + pg], g);
+        }
+    unsigned long long* dl; HIPC(pool.alloc(&dl, lists.size()));
+    HIPC(q3_hipMemcpy(dl, lists.data(), lists.size() * 8, hipMemcpyHostToDevice));
+    HIPC(q3_hipDeviceSynchronize());
+    HIPC(launch_kv_pages_to_fp8(dl, dl + n_pages, n_pages, n_layers, nkv, a.geo.layer_stride(), a.geo.v_delta(), b.geo.layer_stride(), b.geo.v_delta(), 0));
+    HIPC(q3_hipDeviceSynchronize());
+    std::vector<std::vector<uint32_t>> got;
+    HIPC(b.download(got));
+    each_row([&](int pg, int l, int v, int g, int pp, size_t row) {
+        const Kv8At at = kv8_at(b, nkv, dst_slots[pg], l, v, g, pp);
+        char* gb = img_bytes(got, dst_slots[pg]); char* im = img_bytes(b.img, dst_slots[pg]);
+        memcpy(codes + row * HEAD_DIM, gb + at.codes, HEAD_DIM); scales[row] = (uint8_t)gb[at.scale];
+        memcpy(im + at.codes, gb + at.codes, HEAD_DIM); im[at.scale] = gb[at.scale];
     });
     b.strays(got, stray);
     return Q3_OK;
@@ -1747,7 +1928,9 @@ extern "C" q3_status q3_session_frame_bytes(q3_session* s, int kv_len, double* w
         *weight_bytes -= t + 15.0 * p;
     }
     if (kv_bytes) {
-        const double kv_tok = 2.0 * c.n_kv_heads * HEAD_DIM * (s->kv_bf16 ? 2.0 : 4.0) * c.n_layers;   // f32 K/V (default) or a bf16 session's
+        // f32 K/V (default), a bf16 session's, or a KV8 session's (128 codes + one scale byte per row)
+        const double row_bytes = s->kv_dtype == Q3_DTYPE_FP8_E4M3 ? HEAD_DIM + 1.0 : HEAD_DIM * (s->kv_dtype == Q3_DTYPE_BF16 ? 2.0 : 4.0);
+        const double kv_tok = 2.0 * c.n_kv_heads * row_bytes * c.n_layers;
         const double cp_tok = 2.0 * c.cp_kv_heads * HEAD_DIM * 4.0 * c.cp_layers;
         *kv_bytes = s->B * (kv_tok * kv_len + cp_tok * 135.0);
     }
