@@ -1112,7 +1112,7 @@ q3_status q3_batcher_ticket_loudness_read(q3_batcher* b, int64_t ticket, float* 
  * The stretcher then runs at te in the place of t (not at all when te = 1000; q3_pcm_stage_tempo_lags reports the lags of te), and
  * where te != t its output y is resampled by te / t, which brings the duration back to t's and moves the pitch by t / te — within
  * 1.8 cents of the request. Varispeed compensated by time stretching: formants move with the pitch; +-300 cents is the useful
- * range for natural speech, +-1200 is accepted; a formant-preserving shifter is out of scope.
+ * range for natural speech, +-1200 is accepted; q3_pcm_stage_set_formant (below) brings the formants back.
  * The step is q3_resample's filter at sr_in = t, sr_out = te: output j sits at input time j t / te, cj = floor(j t / te),
  * r = (j t) mod te, taps over the inputs cj + k, k = -63 .. 64, at tau = r / te - k: h = fc sinc(fc tau) w^2(tau / 64),
  * fc = 0.95 min(1, te / t), w the Blackman-Harris window (0 from |tau| = 64 on). The taps come from two tables, f64 rounded to
@@ -1144,6 +1144,41 @@ q3_status q3_session_set_pitch(q3_session* s, int b, int cents);
 /* Batcher: a streamed ticket's pitch; the window and the read of q3_batcher_ticket_tempo. A slot's next owner gets its own setting,
  * off included; a parked streamed ticket keeps its stage row. */
 q3_status q3_batcher_ticket_pitch(q3_batcher* b, int64_t ticket, int cents);
+/* ---------------- output stage: the formants of a row (a spectral-envelope warp directly behind the pitch step) ----------------
+ * keep in 0 / 1 and fcents in -600..600, anything else Q3_INVALID_ARG before the device is touched. With the row's realised pitch
+ * ratio p' = t / te (above) and s = 2^(fcents / 1200) the warp is omega = (keep ? p' : 1) / s, computed in f64 and rounded once to
+ * f32. The step runs where omega != 1 alone: a row with keep = 0, fcents = 0 — and one with keep = 1 at 0 cents of pitch — takes the
+ * paths above and returns their bits and their launches, with no descriptor, launch or allocation. keep = 1 brings the formants
+ * that the pitch step moved by p' back to where the voice has them: the same speaker at another pitch; fcents moves them on their
+ * own, at any pitch. The step takes the pitch step's stream v (the stretcher's or the row's where no pitch step runs) and hands on
+ * as many samples as it takes, later.
+ * Frames of N = 1024 samples at hop H = 256: frame m covers samples [256 m - 768, 256 m + 256), zeros before sample 0 and, once the
+ * input has ended, behind its last sample; a non-finite sample enters as 0. w[n] = sqrt(0.5 - 0.5 cos(2 pi n / N)) for analysis and
+ * synthesis. Per frame: X = DFT(w x); L[k] = ln(max(|X[k]|^2, 1e-12)) / 2, k = 0..512, extended evenly; c = IDFT(L); the lifter
+ * keeps |n| <= 40 (600 Hz: above any speech f0, so the harmonics stay out) and E = Re DFT(c liftered) is the log envelope. With
+ * u = k omega, E_w[k] is E interpolated linearly between bins floor(u) and floor(u) + 1, E[512] for u >= 512;
+ * g[k] = exp(clamp(E_w[k] - E[k], +-ln 10^(18/20))); Y = g X; y_m = w IDFT(Y). The output is half the sum of the up to four frames
+ * over a sample, added in ascending m, each sum rounded once.
+ * Streaming rule: hop h is final once frames h .. h + 3 are done: after F final inputs 256 max(0, floor(F / 256) - 3) samples are
+ * out, and a push with `last` returns the rest, F in total. The row keeps at most 1023 inputs and 768 partial sums in two copies
+ * under the commit rule of the tails; since the frame grid and the order of the sums follow from the sample index alone, a row's
+ * output does not depend on how its input was cut into pushes, bit for bit. The table (12 KB a stage) and a row's state (14 KB) are
+ * allocated by the first setting whose omega is not 1. No reference counterpart. */
+q3_status q3_pcm_stage_set_formant(q3_pcm_stage* ps, int row, int keep, int fcents);       /* also restarts the row; kept by _set / _reset / every other _set_* */
+/* host only: omega as the row's descriptor carries it and whether the step runs (either may be NULL); q3_pcm_stage_pitch_plan's refusals */
+q3_status q3_pcm_stage_formant_plan(int tempo_permille, int cents, int keep, int fcents, float* omega, int* runs);
+/* host only: the streaming rule — samples that have left the step after n_in_total have entered it */
+q3_status q3_pcm_stage_formant_count(size_t n_in_total, int ended, size_t* n_out);
+/* host only (test hook): N, H and the tables as the stage uploads them: 1024 twiddles exp(-2 pi i t / 1024) as (re, im) pairs, 2048
+ * floats, and the 1024 floats of the window (either buffer may be NULL; both NULL: N / H alone) */
+q3_status q3_pcm_stage_formant_tables(float* twiddles, size_t cap1, float* window, size_t cap2, int* N, int* H);
+/* host only: q3_pcm_stage_bound_silence's cap and refusals for a row that also has the formant step, whose hold of 1023 samples
+ * stands behind the pitch step's; edge_ms < 0: a row without a silence step (pause_ms is then not read) */
+q3_status q3_pcm_stage_bound_formant(uint32_t sample_rate, int tempo_permille, int cents, int with_level, int edge_ms, int pause_ms, size_t n_in,
+                                     size_t* n_out_max);
+/* Sessions and the batcher: q3_session_set_pitch's / q3_batcher_ticket_pitch's window and persistence. */
+q3_status q3_session_set_formant(q3_session* s, int b, int keep, int fcents);
+q3_status q3_batcher_ticket_formant(q3_batcher* b, int64_t ticket, int keep, int fcents);
 /* ---------------- output stage: a silence trim and pause cap per row (at the very front of the row, before the stretcher) ----------------
  * threshold_mB: 0, the default, is off: such a row takes the paths above and returns their bits and their launches, and a push
  * without such a row has no launch, copy or wait it did not have. Otherwise -9000..-2000, millibel re full scale of a hop's mean

@@ -253,6 +253,13 @@ SYMBOLS = {
     "q3_pcm_stage_bound_pitch": (c_int, [ctypes.c_uint32, c_int, c_int, c_int, ctypes.c_size_t, P(ctypes.c_size_t)]),
     "q3_session_set_pitch": (c_int, [c_void_p, c_int, c_int]),
     "q3_batcher_ticket_pitch": (c_int, [c_void_p, ctypes.c_int64, c_int]),
+    "q3_pcm_stage_set_formant": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "q3_pcm_stage_formant_plan": (c_int, [c_int, c_int, c_int, c_int, P(ctypes.c_float), P(c_int)]),
+    "q3_pcm_stage_formant_count": (c_int, [ctypes.c_size_t, c_int, P(ctypes.c_size_t)]),
+    "q3_pcm_stage_formant_tables": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, P(c_int), P(c_int)]),
+    "q3_pcm_stage_bound_formant": (c_int, [ctypes.c_uint32, c_int, c_int, c_int, c_int, c_int, ctypes.c_size_t, P(ctypes.c_size_t)]),
+    "q3_session_set_formant": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "q3_batcher_ticket_formant": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int]),
     "q3_pcm_stage_set_silence": (c_int, [c_void_p, c_int, c_int, c_int, c_int]),
     "q3_pcm_stage_silence": (c_int, [c_void_p, c_int] + [P(ctypes.c_int64)] * 5),
     "q3_pcm_stage_silence_hold": (c_int, [c_int, c_int, P(ctypes.c_size_t)]),

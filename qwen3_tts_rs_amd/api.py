@@ -218,8 +218,8 @@ class Session:
         self._ref_frames = [0 if u.ref_codes is None else int(np.asarray(u.ref_codes).reshape(-1, 16).shape[0]) for u in utts]
         self._frame_budget = int(frame_budget)
         self._row_limit = [self._limit_of(u) for u in utts]       # frames a row can reach: sizes the PCM buffers of run()
-        # per row what sizes the buffers of next_chunks_out: [tempo, level on, pitch, silence (edge_ms, pause_ms) or None]
-        self._out_rows = [[1000, False, 0, None] for _ in utts]
+        # per row what sizes the buffers of next_chunks_out: [tempo, level on, pitch, silence (edge_ms, pause_ms) or None, formant step asked]
+        self._out_rows = [[1000, False, 0, None, False] for _ in utts]
         reqs = (CRequest * self.B)()
         for i, u in enumerate(utts):
             self._fill(reqs[i], u)
@@ -373,6 +373,13 @@ class Session:
         stretcher would leave 500..2000) is refused."""
         check(lib.q3_session_set_pitch(self._h, int(b), int(cents)))
         self._note_out(b, 2, int(cents))
+
+    def set_formant(self, keep: bool = True, shift_cents: int = 0, b: int = -1):
+        """The formant step of row b (-1: every row) in `next_chunks_out` (q3_session_set_formant): keep holds the formants where the
+        row's pitch moves them (the same speaker at another pitch), shift_cents (-600..600) moves them on their own; (False, 0) =
+        off. The window and the persistence of `set_pitch`."""
+        check(lib.q3_session_set_formant(self._h, int(b), 1 if keep else 0, int(shift_cents)))
+        self._note_out(b, 4, bool(keep) or bool(int(shift_cents)))
 
     def next_chunks_out(self) -> List[Tuple[Optional[AudioBuffer], bool]]:
         """`next_chunks` through the session's output stage (q3_session_next_chunks_out): one (chunk or None, done) per row, the
@@ -610,7 +617,7 @@ class Batcher:
 
     def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False, tempo_permille: int = 1000,
                         fmt: Optional[str] = None, gain_mb: int = 0, ceiling_mb: int = 0, target_lufs: Optional[float] = None,
-                        prior_gain_db: float = 0.0, pitch_cents: int = 0, silence=None, mark=None) -> int:
+                        prior_gain_db: float = 0.0, pitch_cents: int = 0, silence=None, mark=None, formant=None) -> int:
         """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16 / fmt: the
         ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked, uint8 for
         fmt "ulaw" / "alaw". tempo_permille: its speaking rate (q3_batcher_ticket_tempo; 1250 = 1.25 x as fast, 1000 = off).
@@ -618,7 +625,7 @@ class Batcher:
         to, from the gain prior_gain_db (q3_batcher_ticket_loudness; `loudness(ticket)` reads the result). pitch_cents: its pitch
         (q3_batcher_ticket_pitch; -1200..1200, 0 = off). silence = (threshold_db, edge_ms, pause_ms): its silence step
         (q3_batcher_ticket_silence; `silence(ticket)` reads the counts). mark = (key, db) or key: its keyed watermark
-        (q3_batcher_ticket_mark)."""
+        (q3_batcher_ticket_mark). formant = (keep, shift_cents): its formant step (q3_batcher_ticket_formant)."""
         code = pcm_format(pcm16, fmt)
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
@@ -641,6 +648,12 @@ class Batcher:
         if mark is not None:
             try:
                 self.ticket_mark(int(t.value), *(mark if isinstance(mark, (tuple, list)) else (mark,)))
+            except _lib.Q3Error:
+                self.cancel(int(t.value)); self.fetch(int(t.value))
+                raise
+        if formant is not None:
+            try:
+                self.ticket_formant(int(t.value), *formant)
             except _lib.Q3Error:
                 self.cancel(int(t.value)); self.fetch(int(t.value))
                 raise
@@ -722,6 +735,12 @@ class Batcher:
         """A streamed ticket's pitch in cents (q3_batcher_ticket_pitch): between its submission and the next `step`."""
         check(lib.q3_batcher_ticket_pitch(self._h, int(ticket), int(cents)))
         if int(cents):
+            self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
+
+    def ticket_formant(self, ticket: int, keep: bool = True, shift_cents: int = 0):
+        """A streamed ticket's formant step (q3_batcher_ticket_formant): between its submission and the next `step`."""
+        check(lib.q3_batcher_ticket_formant(self._h, int(ticket), 1 if keep else 0, int(shift_cents)))
+        if int(shift_cents):
             self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
 
     def submit_open(self, utt: Utterance, want: str = "stream", sample_rate: int = 24000, pcm16: bool = False,
@@ -1446,12 +1465,17 @@ def pcm_stage_taps(rate: int) -> Tuple[np.ndarray, int, int]:
     return t, L.value, M.value
 
 
-def pcm_stage_bound(rate: int, n_in: int, tempo_permille: int = 1000, level: bool = False, pitch_cents: int = 0, silence=None) -> int:
+def pcm_stage_bound(rate: int, n_in: int, tempo_permille: int = 1000, level: bool = False, pitch_cents: int = 0, silence=None,
+                    formant: bool = False) -> int:
     """The most samples one push of n_in 24 kHz samples returns at `rate` (q3_pcm_stage_bound), for a row at tempo_permille
     (q3_pcm_stage_bound_tempo), with `level` one that has a level (q3_pcm_stage_bound_level), with pitch_cents one that has a pitch
-    (q3_pcm_stage_bound_pitch), with silence = (edge_ms, pause_ms) one that has a silence step (q3_pcm_stage_bound_silence)."""
+    (q3_pcm_stage_bound_pitch), with silence = (edge_ms, pause_ms) one that has a silence step (q3_pcm_stage_bound_silence), with `formant` one that has a formant
+    step (q3_pcm_stage_bound_formant)."""
     n = ctypes.c_size_t()
-    if silence is not None:
+    if formant:
+        edge, pause = (int(silence[0]), int(silence[1])) if silence is not None else (-1, 0)
+        check(lib.q3_pcm_stage_bound_formant(int(rate), int(tempo_permille), int(pitch_cents), 1 if level else 0, edge, pause, int(n_in), ctypes.byref(n)))
+    elif silence is not None:
         check(lib.q3_pcm_stage_bound_silence(int(rate), int(tempo_permille), int(pitch_cents), 1 if level else 0, int(silence[0]), int(silence[1]),
                                              int(n_in), ctypes.byref(n)))
     elif int(pitch_cents):
@@ -1495,6 +1519,31 @@ def pcm_stage_pitch_count(tempo_permille: int, cents: int, n_in_total: int, ende
     n = ctypes.c_size_t()
     check(lib.q3_pcm_stage_pitch_count(int(tempo_permille), int(cents), int(n_in_total), 1 if ended else 0, ctypes.byref(n)))
     return int(n.value)
+
+
+def pcm_stage_formant_plan(tempo_permille: int, cents: int, keep: bool, shift_cents: int) -> Tuple[np.float32, bool]:
+    """(omega, runs): the warp a row at this tempo and pitch carries for (keep, shift_cents) and whether its formant step runs
+    (q3_pcm_stage_formant_plan)."""
+    om = ctypes.c_float(); runs = ctypes.c_int()
+    check(lib.q3_pcm_stage_formant_plan(int(tempo_permille), int(cents), int(keep), int(shift_cents), ctypes.byref(om), ctypes.byref(runs)))
+    return np.float32(om.value), bool(runs.value)
+
+
+def pcm_stage_formant_count(n_in_total: int, ended: bool = False) -> int:
+    """Samples that have left the formant step after n_in_total have entered it (q3_pcm_stage_formant_count)."""
+    n = ctypes.c_size_t()
+    check(lib.q3_pcm_stage_formant_count(int(n_in_total), 1 if ended else 0, ctypes.byref(n)))
+    return int(n.value)
+
+
+def pcm_stage_formant_tables() -> Tuple[np.ndarray, np.ndarray, int, int]:
+    """(twiddles [N] complex64, window [N] f32, N, H): the formant step's tables as the stage uploads them (q3_pcm_stage_formant_tables)."""
+    N = ctypes.c_int(); H = ctypes.c_int()
+    check(lib.q3_pcm_stage_formant_tables(None, 0, None, 0, ctypes.byref(N), ctypes.byref(H)))
+    tw = np.zeros(2 * N.value, np.float32); win = np.zeros(N.value, np.float32)
+    check(lib.q3_pcm_stage_formant_tables(tw.ctypes.data_as(ctypes.c_void_p), tw.size, win.ctypes.data_as(ctypes.c_void_p), win.size,
+                                          ctypes.byref(N), ctypes.byref(H)))
+    return tw.view(np.complex64), win, N.value, H.value
 
 
 def pcm_stage_level_coeffs(gain_mb: int, ceiling_mb: int) -> Tuple[np.float32, np.float32]:
@@ -1649,6 +1698,7 @@ class PcmStage:
         self._level = [False] * self.rows
         self._pitch = [0] * self.rows
         self._silence = [None] * self.rows
+        self._formant = [False] * self.rows
         self._h = ctypes.c_void_p()
         check(lib.q3_pcm_stage_create(self.device_index, self.rows, self.max_push_samples, ctypes.byref(self._h)))
 
@@ -1676,6 +1726,12 @@ class PcmStage:
         pitch. Refused where that tempo leaves 500..2000. `set`, `reset` and the other `set_*` keep it."""
         check(lib.q3_pcm_stage_set_pitch(self._h, int(row), int(cents)))
         self._pitch[int(row)] = int(cents)
+
+    def set_formant(self, row: int, keep: bool = True, shift_cents: int = 0):
+        """Row's formant step (q3_pcm_stage_set_formant): keep holds the formants where the row's pitch moves them, shift_cents
+        (-600..600) moves them on their own; (False, 0) = off; also restarts the row. `set`, `reset` and the other `set_*` keep it."""
+        check(lib.q3_pcm_stage_set_formant(self._h, int(row), int(keep), int(shift_cents)))
+        self._formant[int(row)] = bool(int(keep)) or bool(int(shift_cents))
 
     def set_loudness(self, row: int, mode: int, target_mb: int = -1900, prior_mb: int = 0):
         """Row's loudness step (q3_pcm_stage_set_loudness): LOUD_OFF, LOUD_METER (measure, the samples pass) or LOUD_NORMALIZE
@@ -1735,7 +1791,7 @@ class PcmStage:
 
     def bound(self, row: int, n_in: int) -> int:
         return pcm_stage_bound(self._fmt[int(row)][0], n_in, self._tempo[int(row)], self._level[int(row)], self._pitch[int(row)],
-                               self._silence[int(row)])
+                               self._silence[int(row)], self._formant[int(row)])
 
     def push(self, samples: dict, last=()) -> dict:
         """{row: 24 kHz f32 samples} -> {row: samples at the row's rate and format}, every row in one pass; rows in `last` are
@@ -1767,14 +1823,15 @@ class PcmStage:
 
 def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_permille: int = 1000, fmt: Optional[str] = None,
                  gain_mb: int = 0, ceiling_mb: int = 0, target_mb: Optional[int] = None, prior_mb: int = 0, pitch_cents: int = 0, silence=None,
-                 mark=None) -> AudioBuffer:
+                 mark=None, formant=None) -> AudioBuffer:
     """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked (fmt: "f32" /
     "s16" / "ulaw" / "alaw") — what a caller of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their
     result. tempo_permille: the clip's speaking rate (1250 = 1.25 x as fast, 1000 = as it is). gain_mb / ceiling_mb: its level. target_mb / prior_mb: the loudness it is
     steered to (millibel of LUFS) and the gain it starts from — a causal normaliser: the first 400 ms leave at the prior.
     pitch_cents: its pitch (-1200..1200 cents, 0 = as it is; the duration stays that of the tempo). silence = (threshold_db, edge_ms,
     pause_ms): its edges and pauses cut first, as `trim_silence` does. mark = (key, db) or key: its keyed watermark, as `mark_embed`
-    adds it, behind the loudness and in front of the level."""
+    adds it, behind the loudness and in front of the level. formant = (keep, shift_cents): keep holds the formants where pitch_cents
+    moves them, shift_cents moves them on their own (`PcmStage.set_formant`)."""
     code = pcm_format(pcm16, fmt)
     x = np.ascontiguousarray(audio.samples if isinstance(audio, AudioBuffer) else audio, dtype=np.float32).reshape(-1)
     if isinstance(audio, AudioBuffer) and audio.sample_rate != 24000:
@@ -1786,6 +1843,8 @@ def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_p
             ps.set_tempo(0, tempo_permille)
         if int(pitch_cents):
             ps.set_pitch(0, pitch_cents)
+        if formant is not None:
+            ps.set_formant(0, *formant)
         if int(gain_mb) or int(ceiling_mb):
             ps.set_level(0, gain_mb, ceiling_mb)
         if target_mb is not None:

@@ -69,7 +69,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "stretcher as the chunks leave")
     ap.add_argument("--pitch", type=float, default=0.0, metavar="SEMITONES",
                     help="with --streaming: the pitch, -12 .. +12 semitones, applied by the output stage (varispeed behind the time "
-                         "stretcher: the duration stays, formants move with the pitch; +-3 is the useful range for speech)")
+                         "stretcher: the duration stays, formants move with the pitch unless --keep-formants; +-3 is the useful range "
+                         "for speech without it)")
+    ap.add_argument("--keep-formants", action="store_true",
+                    help="with --streaming --pitch: keep the voice's formants where the pitch moves (the same speaker at another pitch)")
+    ap.add_argument("--formant-shift", type=float, default=0.0, metavar="SEMITONES",
+                    help="with --streaming: move the formants on their own, -6 .. +6 semitones, at any pitch")
     ap.add_argument("--output-format", choices=["f32", "s16", "ulaw", "alaw"], default="f32",
                     help="with --streaming: the format the chunks leave the output stage in; ulaw / alaw (ITU-T G.711, one byte per "
                          "sample) write a G.711 WAV (format tag 7 / 6)")
@@ -475,6 +480,11 @@ def main(argv=None) -> int:
     if cents != 0 and not a.streaming:
         print("error: --pitch applies to --streaming (shift a whole utterance with api.resample_gpu(..., pitch_cents=))", file=sys.stderr)
         return 2
+    fcents = int(round(a.formant_shift * 100.0))
+    formant = a.keep_formants or fcents != 0
+    if formant and not a.streaming:
+        print("error: --keep-formants / --formant-shift apply to --streaming (a whole utterance: api.resample_gpu(..., formant=(keep, cents)))", file=sys.stderr)
+        return 2
     gain_mb, ceiling_mb = int(round(a.gain_db * 100.0)), int(round(a.ceiling_db * 100.0))
     if loud is not None:
         ceiling_mb = loud[2]
@@ -483,7 +493,7 @@ def main(argv=None) -> int:
         print("error: --output-format / --gain-db / --ceiling-db apply to --streaming (convert a whole utterance with "
               "api.resample_gpu(..., fmt=, gain_mb=, ceiling_mb=))", file=sys.stderr)
         return 2
-    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None or sil is not None or mark is not None):
+    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None or sil is not None or mark is not None or formant):
         # the chunks of the streaming session, each through the session's output stage as it leaves
         s = model.session([utt], opts, kv_dtype=a.kv_dtype)
         try:
@@ -492,6 +502,8 @@ def main(argv=None) -> int:
                 s.set_tempo(tempo)
             if cents != 0:
                 s.set_pitch(cents)
+            if formant:
+                s.set_formant(a.keep_formants, fcents)
             if gain_mb or ceiling_mb:
                 s.set_level(gain_mb, ceiling_mb)
             if loud is not None:

@@ -4,9 +4,10 @@
 //   q3_prefix_cache.hip the prefix cache: prefilled instruct pages shared across requests (q3_prefix_cache.h)
 //   q3_codec_run.hip device-memory cache, the vocoder pipeline (codec_decode_dev) and q3_decode_codes
 //   q3_codec_stream.hip the codec stream: the vocoder with per-row state, many rows per pass
-//   q3_pcm_stage.hip the output stage, per row a chain of steps (DESIGN 4.12 - 4.12e): silence trim and pause cap -> speaking rate
-//                    (WSOLA) -> pitch in cents (varispeed) -> BS.1770 loudness meter / normaliser -> level (gain and look-ahead peak
-//                    limiter) -> resampling to a requested rate as f32, PCM16 or G.711 bytes
+//   q3_pcm_stage.hip the output stage, per row a chain of steps (DESIGN 4.12 - 4.12g): silence trim and pause cap -> speaking rate
+//                    (WSOLA) -> pitch in cents (varispeed) -> formants kept or shifted (a cepstral-envelope warp; its kernels are
+//                    q3_formant.hip, included at the unit's end) -> BS.1770 loudness meter / normaliser -> level (gain and look-ahead
+//                    peak limiter) -> resampling to a requested rate as f32, PCM16 or G.711 bytes
 //   q3_intake.hip    the reference-audio intake: a clip in its on-disk sample format -> 24 kHz mono f32 on the device in one launch,
 //                    where both encoders read it
 //   q3_denoise.hip   spectral noise suppression of such a clip: STFT analysis, minimum-statistics gain, overlap-add synthesis
@@ -453,10 +454,11 @@ struct OutSettings {
     int loud = Q3_LOUD_OFF, target_mB = -1900, prior_mB = 0;
     int sil_mB = 0, edge_ms = 0, pause_ms = 20;               // the silence step's threshold, 0: off
     uint64_t mark_key = 0; int mark_mB = Q3_MARK_STRENGTH_DEFAULT;               // the mark step's key, 0: off; its strength
+    int fm_keep = 0, fm_cents = 0;                            // the formant step: keep the formants where the pitch moves; their own shift in cents
     // 24 kHz f32 with every step off: the samples leave as they are, and no stage is needed
     bool plain() const {
         return rate == 24000 && fmt == Q3_PCM_F32 && tempo == 1000 && cents == 0 && gain_mB == 0 && ceil_mB == 0 && loud == Q3_LOUD_OFF && sil_mB == 0 &&
-               mark_key == 0;
+               mark_key == 0 && fm_cents == 0;                  // (fm_keep alone moves nothing while the pitch is 0)
     }
     size_t sample_bytes() const { return fmt == Q3_PCM_F32 ? 4 : fmt == Q3_PCM_S16 ? 2 : 1; }
 };
@@ -643,6 +645,7 @@ Q3_HIDDEN q3_status out_set_level(const char* who, OutSettings& o, int gain_mB, 
 Q3_HIDDEN q3_status out_set_loudness(const char* who, OutSettings& o, int mode, int target_mB, int prior_mB);
 Q3_HIDDEN q3_status out_set_silence(const char* who, OutSettings& o, int threshold_mB, int edge_ms, int pause_ms);
 Q3_HIDDEN q3_status out_set_mark(const char* who, OutSettings& o, uint64_t key, int strength_mB);
+Q3_HIDDEN q3_status out_set_formant(const char* who, OutSettings& o, int keep, int fcents);
 // The only writer of a row's step settings: what the steps that `o` turns on need on the device, the values derived from `o`,
 // and the row's restart. All or nothing (but see the silence step's state there). pcm_stage_settings: what the row was given last.
 Q3_HIDDEN q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutSettings& o);
@@ -663,6 +666,27 @@ Q3_HIDDEN q3_status pcm_stage_run(q3_pcm_stage* ps, const std::vector<PsSeg>& se
 Q3_HIDDEN void pcm_stage_finish(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, const PsPlan& plan, void* const* out_host, size_t* n_samples);
 // the three in a row, with the wait (st null: the stage's own stream)
 Q3_HIDDEN q3_status pcm_stage_push_dev(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, hipStream_t st, void* const* out_host, size_t* n_samples);
+// q3_formant.hip: the formant step of the output stage. q3_pcm_stage.hip owns the row's state and the chain.
+constexpr int FM_N = 1024, FM_H = 256;                      // frame and hop
+constexpr int FM_HOLD = FM_N - 1;                           // the most inputs a row holds back
+constexpr int FM_STATE_FLOATS = FM_N + (FM_N - FM_H);       // a copy of a row's state: [tail, at most 1023 inputs | 768 partial sums]
+constexpr int FM_TAB_FLOATS = 3 * FM_N;                     // the stage's table: 1024 twiddles (re, im), then the window
+constexpr int FM_CENTS_MAX = 600;
+// One row of a pass of k_fm_frame / k_fm_ola (device-visible, 8-byte aligned). The row's stream into the step is tail_in (from sample
+// 256 k0 - 768 on) below `base`, the n_new samples of src from there, zeros before 0 and from n_total on. Frames k0 .. k1 - 1 run into
+// fr[frame - k0][1024]; part_in holds the sums of samples o_base .. 256 k0 - 1 over the frames below k0; y takes n_y samples from
+// o_base on; tail_out (null with `last`) / part_out: the other copy of the row's state
+struct FmDesc {
+    const float* src; const float* tail_in; float* tail_out; const float* part_in; float* part_out; float* fr; float* y;
+    long long base, n_total, k0, k1, o_base;
+    int n_new, n_y, last; float omega;
+};
+Q3_HIDDEN long long formant_frames(long long F, bool ended);      // frames computed once F samples have entered
+Q3_HIDDEN long long formant_emitted(long long F, bool ended);     // the streaming rule: samples that have left
+Q3_HIDDEN float formant_omega(int t, int te, int keep, int fcents);      // the warp of a row at tempo t whose stretcher runs at te; 1: the step is off
+Q3_HIDDEN q3_status formant_checked(const char* who, int keep, int fcents);
+Q3_HIDDEN void formant_tables(std::vector<float>& tab);
+Q3_HIDDEN hipError_t formant_launch(const FmDesc* descs_dev, int n_rows, int max_frames, int max_tiles, const float* tab_dev, hipStream_t st);
 // q3_session.hip
 Q3_HIDDEN hipError_t sync_frames(q3_session* s);
 Q3_HIDDEN q3_status kv_reserve_row(q3_session* s, int b, int n_pos);

@@ -1,7 +1,7 @@
 // q3_pcm_stage.hip — the output stage: 24 kHz f32 from the vocoder -> per row a requested sample rate and format, through the
 // steps the row has asked for. (A unit of the engine: q3_engine.h says which holds what.)
 //
-// A row's stream passes a chain of seven steps, front to back: silence -> stretcher -> pitch -> loudness -> mark -> level ->
+// A row's stream passes a chain of eight steps, front to back: silence -> stretcher -> pitch -> formant -> loudness -> mark -> level ->
 // resampler / format. The last one every row has; each of the others is on for the rows that ask for it, and a row whose step is off is not
 // touched by any of it: no launch, no buffer, no descriptor, no allocation. Every step counts the samples that have entered and
 // left it, keeps what the next push still needs on the device in two copies — a push reads one and writes the other, and they are
@@ -29,6 +29,12 @@
 // points per zero crossing and the squared window at 64 points per tap, both interpolated linearly at positions that integer
 // arithmetic splits exactly into an index and a remainder. It holds 64 samples back like the resampler and keeps the row's last 128
 // inputs. A row whose te equals its t (0 cents) has no pitch step.
+//
+// 3g. The formant step (its kernels and rules are q3_formant.hip's). Frames of 1024 samples every 256 of the stream
+// behind the pitch step: the cepstral envelope of each is read at bin k * omega and the spectrum multiplied by the ratio, which
+// moves the formants back where the pitch step moved them (omega = t / te) or by a shift of their own; the frames are overlap-added
+// in ascending order into u. It is length-preserving and holds at most 1023 samples back; the row keeps those and 768 partial sums.
+// A row whose omega is 1 has no formant step.
 //
 // 4. The loudness step. k_loud K-weights the stream (ITU-R BS.1770-4: two biquads), keeps the energy of every 100 ms
 // hop and the mean square of every 400 ms block, gates the blocks the row has seen so far (absolute and relative gate) into its
@@ -973,6 +979,11 @@ struct PitchStep : Totals {                   // DESIGN 4.12d; the row's tempo t
     float* tail = nullptr; int cur = 0;       // two copies of 128 floats: the last 128 inputs
     void reset() { in = out = 0; }
 };
+struct FormantStep : Totals {                 // DESIGN 4.12g; omega: formant_omega of the row's tempo, pitch, keep and shift; 1: off
+    float omega = 1.0f;
+    float* state = nullptr; int cur = 0;      // two copies of FM_STATE_FLOATS floats: [tail | partial sums]
+    void reset() { in = out = 0; }
+};
 struct LoudStep : Totals {                    // DESIGN 4.12c; out == in: the step holds nothing back
     int mode = Q3_LOUD_OFF; float T = 0.0f, P = 1.0f, gate = 0.0f, lo = 0.0f, hi = 0.0f;
     float* state = nullptr; int cur = 0;      // two copies of LD_STATE floats, then the LD_HIST block values (one copy)
@@ -996,19 +1007,20 @@ struct ResStep : Totals {                     // the resampler and 
 };
 struct PsRow {
     OutSettings asked;
-    SilStep sil; TempoStep tp; PitchStep pt; LoudStep ld; MarkStep mk; LevelStep lv; ResStep rs;
+    SilStep sil; TempoStep tp; PitchStep pt; FormantStep fm; LoudStep ld; MarkStep mk; LevelStep lv; ResStep rs;
     bool ended = false;                       // flushed by a push with `last`: restarted by pcm_stage_apply / reset only
-    void reset() { sil.reset(); tp.reset(); pt.reset(); ld.reset(); mk.reset(); lv.reset(); rs.reset(); ended = false; }
+    void reset() { sil.reset(); tp.reset(); pt.reset(); fm.reset(); ld.reset(); mk.reset(); lv.reset(); rs.reset(); ended = false; }
 };
 constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
 
 // ---- the chain, written once ----
-enum { ST_SIL, ST_TEMPO, ST_PITCH, ST_LOUD, ST_MARK, ST_LEVEL, ST_RES, ST_N };
+enum { ST_SIL, ST_TEMPO, ST_PITCH, ST_FORMANT, ST_LOUD, ST_MARK, ST_LEVEL, ST_RES, ST_N };
 static bool step_on(const PsRow& r, int s) {
     switch (s) {
     case ST_SIL: return r.sil.thr != 0;
     case ST_TEMPO: return r.tp.te != TP_OFF;
     case ST_PITCH: return r.pt.te != r.pt.t;
+    case ST_FORMANT: return r.fm.omega != 1.0f;
     case ST_LOUD: return r.ld.mode != Q3_LOUD_OFF;
     case ST_MARK: return r.mk.key != 0;
     case ST_LEVEL: return r.lv.on;
@@ -1020,6 +1032,7 @@ static const Totals& step_totals(const PsRow& r, int s) {
     case ST_SIL: return r.sil;
     case ST_TEMPO: return r.tp;
     case ST_PITCH: return r.pt;
+    case ST_FORMANT: return r.fm;
     case ST_LOUD: return r.ld;
     case ST_MARK: return r.mk;
     case ST_LEVEL: return r.lv;
@@ -1038,6 +1051,7 @@ static long long step_emitted(const PsRow& r, int s, long long in, bool last, lo
         return y;
     }
     case ST_PITCH: return pitch_emitted(r.pt.t, r.pt.te, in, last);
+    case ST_FORMANT: return formant_emitted(in, last);
     case ST_LEVEL: return level_emitted(in, last);
     case ST_RES: return emitted(r.rs.sr, r.rs.r, in, last);
     default: return in;
@@ -1049,7 +1063,8 @@ static size_t step_cap(const PsRow& r, int s, size_t n) {
     case ST_SIL: return n + tr_hold(r.sil.set);                    // its own samples and what the row had retained
     case ST_TEMPO: return tempo_y_bound(r.tp.te, n);
     case ST_PITCH: return pitch_v_bound(r.pt.t, r.pt.te, n);
-    case ST_LEVEL: return n + LV_D;                                // with `last`, the 127 held back
+    case ST_FORMANT: return n + FM_HOLD;                           // with `last`, the at most 1023 held back
+    case ST_LEVEL: return n + LV_D;                               // with `last`, the 127 held back
     default: return n;
     }
 }
@@ -1063,6 +1078,7 @@ static size_t chain_cap(const PsRow& r, size_t n) {
 struct SegWalk {
     long long n_in[ST_N], n_out[ST_N], frames;
     size_t off[ST_N];
+    long long fm_k1; size_t fm_off;           // the formant step: the frame it reaches, its slice of the frame scratch (floats)
     const float* front; long long n_front;
     bool sil, runs;                           // the pre-pass ran for it; it passes the steps behind
 };
@@ -1080,8 +1096,10 @@ static void chain_walk(const PsRow& r, int first, long long n, bool last, SegWal
 struct StepPlan {
     std::vector<SegWalk> seg;
     std::vector<TrDesc> sdesc; std::vector<int> sseg; std::vector<long long> sres;      // the pre-pass: descriptors, their segments, the counters that came back
-    std::vector<TpDesc> tdesc; std::vector<PtDesc> pdesc; std::vector<LoDesc> odesc; std::vector<MkDesc> mdesc; std::vector<LvDesc> ldesc;
+    std::vector<TpDesc> tdesc; std::vector<PtDesc> pdesc; std::vector<FmDesc> fdesc; std::vector<LoDesc> odesc; std::vector<MkDesc> mdesc;
+    std::vector<LvDesc> ldesc;
     int tiles[ST_N];
+    int fm_frames;                            // the most frames a row's formant step runs in this push
 };
 struct q3_pcm_stage {
     int device = 0, R = 0; size_t max_push = 0;
@@ -1093,6 +1111,8 @@ struct q3_pcm_stage {
     float* s_win = nullptr;                                    // the seam's weights: w0, then w1, 240 floats each
     float* t_win = nullptr;                                    // the Hann window, 720 floats
     float* p_tab = nullptr;                                    // the sinc table, PT_SC_N floats, then the window's, PT_W2_N
+    float* f_tab = nullptr;                                    // the formant step's twiddles and window, FM_TAB_FLOATS floats
+    DevBuf f_fr;                                               // ... and its windowed frames of a push, [row][frame][1024]
     float o_coef[10] = {0}; bool o_coef_set = false;           // the K-weighting at 24 kHz, f32
     // per step, allocated by the first push of a row that has it: what it writes in a push, row after row (s: kept samples | kept
     // hops | flags; y, v, w, z: samples; the resampler's is `out`), and its descriptors (the silence step's: then the rows' counters
@@ -1161,9 +1181,11 @@ extern "C" q3_status q3_pcm_stage_bound(uint32_t sample_rate, size_t n_in, size_
 
 // The _bound family: the caps of the steps a row with these settings has, in chain order (chain_cap), then the resampler's. hold: what
 // the row's silence step can retain (0: none). Each caller checks its own ranges first; tempo, cents and n_in (at most 2^48) are in range.
-static q3_status bound_through(uint32_t sample_rate, int tempo, int cents, int with_level, size_t hold, size_t n_in, size_t* n_out_max) {
+static q3_status bound_through(uint32_t sample_rate, int tempo, int cents, int with_level, size_t hold, size_t n_in, size_t* n_out_max,
+                               bool with_formant = false) {
     PsRow r;                                                       // (the settings alone; its silence step's cap is n_in + hold)
     r.pt.t = tempo; r.pt.te = r.tp.te = pitch_te(tempo, cents); r.lv.on = with_level != 0;
+    if (with_formant) r.fm.omega = 2.0f;                           // (on: the cap does not depend on the warp)
     return resampler_bound(sample_rate, chain_cap(r, n_in + hold), n_out_max);
 }
 
@@ -1282,9 +1304,10 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
     (void)hipSetDevice(ps->device);
     if (ps->st) (void)hipStreamSynchronize(ps->st);
     for (auto& kv : ps->taps) dev_free(kv.second);
-    dev_free(ps->tails); dev_free(ps->s_win); dev_free(ps->t_win); dev_free(ps->p_tab);
+    dev_free(ps->tails); dev_free(ps->s_win); dev_free(ps->t_win); dev_free(ps->p_tab); dev_free(ps->f_tab);
+    ps->f_fr.release();
     for (PsRow& r : ps->rows) {
-        dev_free(r.sil.state); dev_free(r.tp.state); dev_free(r.pt.tail); dev_free(r.ld.state); dev_free(r.mk.tab); dev_free(r.lv.tail);
+        dev_free(r.sil.state); dev_free(r.tp.state); dev_free(r.pt.tail); dev_free(r.fm.state); dev_free(r.ld.state); dev_free(r.mk.tab); dev_free(r.lv.tail);
         r.tp.lags[0].release(); r.tp.lags[1].release();
     }
     for (int s = 0; s < ST_N; ++s) { ps->buf[s].release(); ps->desc[s].release(); }
@@ -1423,6 +1446,28 @@ extern "C" q3_status q3_pcm_stage_bound_silence(uint32_t sample_rate, int tempo_
     Q3C(pitch_checked("q3_pcm_stage_bound_pitch", tempo_permille, cents));
     if (n_in + hold > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_pitch: n_in above 2^48");
     return bound_through(sample_rate, tempo_permille, cents, with_level, hold, n_in, n_out_max);
+}
+
+extern "C" q3_status q3_pcm_stage_formant_plan(int tempo_permille, int cents, int keep, int fcents, float* omega, int* runs) {
+    Q3C(pitch_checked("q3_pcm_stage_formant_plan", tempo_permille, cents));
+    Q3C(formant_checked("q3_pcm_stage_formant_plan", keep, fcents));
+    const float w = formant_omega(tempo_permille, pitch_te(tempo_permille, cents), keep, fcents);
+    if (omega) *omega = w;
+    if (runs) *runs = w != 1.0f ? 1 : 0;
+    return Q3_OK;
+}
+
+extern "C" q3_status q3_pcm_stage_bound_formant(uint32_t sample_rate, int tempo_permille, int cents, int with_level, int edge_ms, int pause_ms, size_t n_in,
+                                                size_t* n_out_max) {
+    // q3_pcm_stage_bound_silence's chain and refusals with the formant step behind the pitch step; edge_ms < 0: no silence step
+    size_t hold = 0;
+    if (edge_ms >= 0) {
+        Q3C(silence_checked("q3_pcm_stage_bound_formant", 0, edge_ms, pause_ms));
+        hold = tr_hold(tr_set(edge_ms, pause_ms));
+    }
+    Q3C(pitch_checked("q3_pcm_stage_bound_formant", tempo_permille, cents));
+    if (n_in > ((size_t)1 << 48) || n_in + hold > ((size_t)1 << 48)) return set_err(Q3_INVALID_ARG, "q3_pcm_stage_bound_formant: n_in above 2^48");
+    return bound_through(sample_rate, tempo_permille, cents, with_level, hold, n_in, n_out_max, true);
 }
 
 // the whole definition for one clip on the CPU: the same f32 operations in the same order as k_trim
@@ -1623,6 +1668,11 @@ q3_status out_set_mark(const char* who, OutSettings& o, uint64_t key, int streng
     o.mark_key = key; o.mark_mB = strength_mB;
     return Q3_OK;
 }
+q3_status out_set_formant(const char* who, OutSettings& o, int keep, int fcents) {
+    Q3C(formant_checked(who, keep, fcents));
+    o.fm_keep = keep; o.fm_cents = fcents;
+    return Q3_OK;
+}
 
 // `o` (which came through the checked edits) onto a row. First everything that can fail — the tables and the row's states of the
 // steps that `o` turns on, each made by the first call that needs it and kept from then on —, then the step fields, then the
@@ -1665,6 +1715,15 @@ q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutS
             Q3C(table_upload(ps, &ps->p_tab, sc.data(), sc.size(), who, "tables", "table"));
         }
         Q3C(row_state(ps, &r.pt.tail, 2 * (size_t)PS_TAPS * 4, who, "tail", row));
+    }
+    const float omega = formant_omega(o.tempo, te, o.fm_keep, o.fm_cents);
+    if (omega != 1.0f) {
+        if (!ps->f_tab) {
+            std::vector<float> t;
+            formant_tables(t);
+            Q3C(table_upload(ps, &ps->f_tab, t.data(), t.size(), who, "formant tables", "table"));
+        }
+        Q3C(row_state(ps, &r.fm.state, 2 * (size_t)FM_STATE_FLOATS * 4, who, "formant state", row));
     }
     if (o.loud != Q3_LOUD_OFF) {
         if (!ps->o_coef_set) {
@@ -1711,6 +1770,7 @@ q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutS
     r.asked = o;
     r.rs.sr = o.rate; r.rs.fmt = o.fmt; r.rs.r = rate; r.rs.taps = taps;
     r.pt.t = o.tempo; r.pt.te = r.tp.te = te;
+    r.fm.omega = omega;
     r.lv.on = level;
     (void)q3_pcm_stage_level_coeffs(o.gain_mB, o.ceil_mB, &r.lv.g, &r.lv.c);
     r.ld.mode = o.loud;
@@ -1747,6 +1807,9 @@ extern "C" q3_status q3_pcm_stage_set_loudness(q3_pcm_stage* ps, int row, int mo
 }
 extern "C" q3_status q3_pcm_stage_set_mark(q3_pcm_stage* ps, int row, uint64_t key, int strength_mB) {
     return stage_set(ps, row, "q3_pcm_stage_set_mark", [&](const char* who, OutSettings& o) { return out_set_mark(who, o, key, strength_mB); });
+}
+extern "C" q3_status q3_pcm_stage_set_formant(q3_pcm_stage* ps, int row, int keep, int fcents) {
+    return stage_set(ps, row, "q3_pcm_stage_set_formant", [&](const char* who, OutSettings& o) { return out_set_formant(who, o, keep, fcents); });
 }
 extern "C" q3_status q3_pcm_stage_set_silence(q3_pcm_stage* ps, int row, int threshold_mB, int edge_ms, int pause_ms) {
     return stage_set(ps, row, "q3_pcm_stage_set_silence", [&](const char* who, OutSettings& o) { return out_set_silence(who, o, threshold_mB, edge_ms, pause_ms); });
@@ -1852,6 +1915,7 @@ static q3_status step_ready(const q3_pcm_stage* ps, const PsRow& r, int row, int
     switch (s) {
     case ST_TEMPO: if (!r.tp.state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tempo and no state", row); break;
     case ST_PITCH: if (!r.pt.tail || !ps->p_tab) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a pitch and no state", row); break;
+    case ST_FORMANT: if (!r.fm.state || !ps->f_tab) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a formant step and no state", row); break;
     case ST_LOUD: if (!r.ld.state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a loudness step and no state", row); break;
     case ST_MARK: if (!r.mk.tab || r.mk.tab_key != r.mk.key) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a mark and no carrier", row); break;
     case ST_LEVEL: if (!r.lv.tail) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a level and no state", row); break;
@@ -1890,6 +1954,24 @@ static q3_status step_fill(q3_pcm_stage* ps, PsPlan& plan, const PsSeg& sg, cons
         q.dq1 = (19 * PT_S1 * pt.te) / q.den1; q.dr1 = (19 * PT_S1 * pt.te) % q.den1;
         q.fc = (float)(0.95 * (pt.te < pt.t ? (double)pt.te / (double)pt.t : 1.0));
         p.pdesc.push_back(q);
+        break;
+    }
+    case ST_FORMANT: {
+        if (n_in > 0 || n_out > 0) {                               // (nothing passes: no descriptor, no flip)
+            const FormantStep& fm = r.fm;
+            const float* in = fm.state + (size_t)fm.cur * FM_STATE_FLOATS; float* out = fm.state + (size_t)(fm.cur ^ 1) * FM_STATE_FLOATS;
+            FmDesc f{};
+            f.src = src; f.tail_in = fm.in > 0 ? in : nullptr; f.part_in = fm.in > 0 ? in + FM_N : nullptr;
+            f.tail_out = sg.last ? nullptr : out; f.part_out = out + FM_N;
+            f.fr = (float*)ps->f_fr.dev + w.fm_off; f.y = (float*)dst;
+            f.base = fm.in; f.n_total = fm.in + n_in; f.k0 = formant_frames(fm.in, false); f.k1 = w.fm_k1; f.o_base = fm.out;
+            f.n_new = n_in; f.n_y = n_out; f.last = sg.last ? 1 : 0; f.omega = fm.omega;
+            p.fdesc.push_back(f);
+            p.fm_frames = std::max(p.fm_frames, (int)(f.k1 - f.k0));
+            // the hops k_fm_ola visits: the emitted ones and the ones whose partial sums it hands on
+            const long long pend = sg.last ? f.n_total : f.k1 * FM_H;
+            p.tiles[s] = std::max(p.tiles[s], (int)((pend - f.o_base + FM_H - 1) / FM_H));
+        }
         break;
     }
     case ST_LOUD: {
@@ -1950,9 +2032,10 @@ static q3_status step_fill(q3_pcm_stage* ps, PsPlan& plan, const PsSeg& sg, cons
 static q3_status chain_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan) {
     StepPlan& p = ps->plan;
     plan.desc.clear(); plan.off.assign(segs.size(), 0); plan.count.assign(segs.size(), 0); plan.bytes = 0;
-    p.tdesc.clear(); p.pdesc.clear(); p.odesc.clear(); p.mdesc.clear(); p.ldesc.clear();
-    size_t floats[ST_N] = {0};
+    p.tdesc.clear(); p.pdesc.clear(); p.fdesc.clear(); p.odesc.clear(); p.mdesc.clear(); p.ldesc.clear();
+    size_t floats[ST_N] = {0}, fr_floats = 0;
     for (int s = 0; s < ST_N; ++s) p.tiles[s] = 1;
+    p.fm_frames = 0;
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; const PsRow& r = ps->rows[(size_t)sg.row]; SegWalk& w = p.seg[i];
         w.runs = !r.ended && (w.n_front > 0 || sg.last);
@@ -1964,12 +2047,17 @@ static q3_status chain_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, Ps
             if (s == ST_LOUD && r.ld.mode != Q3_LOUD_NORMALIZE) continue;      // (a row that only meters writes no samples)
             w.off[s] = floats[s]; floats[s] += ((size_t)w.n_out[s] + 3) & ~(size_t)3;
         }
+        if (step_on(r, ST_FORMANT)) {                              // the frames the push reaches, and their place in the scratch
+            w.fm_k1 = formant_frames(r.fm.in + w.n_in[ST_FORMANT], sg.last != 0);
+            w.fm_off = fr_floats; fr_floats += (size_t)(w.fm_k1 - formant_frames(r.fm.in, false)) * FM_N;
+        }
         plan.count[i] = (size_t)w.n_out[ST_RES];
         plan.off[i] = w.off[ST_RES] = plan.bytes;
         plan.bytes = (plan.bytes + plan.count[i] * fmt_bytes(r.rs.fmt) + 15) & ~(size_t)15;
     }
     Q3C(buf_reserve(ps, ps->out, plan.bytes));
     for (int s = ST_TEMPO; s < ST_RES; ++s) if (floats[s] > 0) Q3C(buf_reserve(ps, ps->buf[s], floats[s] * 4));
+    if (fr_floats > 0) Q3C(buf_reserve(ps, ps->f_fr, fr_floats * 4));
     for (size_t i = 0; i < segs.size(); ++i) {
         const PsSeg& sg = segs[i]; PsRow& r = ps->rows[(size_t)sg.row]; const SegWalk& w = p.seg[i];
         if (!w.runs) continue;
@@ -1990,6 +2078,11 @@ static hipError_t chain_launch(q3_pcm_stage* ps, const PsPlan& plan, const PsDes
     const StepPlan& p = ps->plan;
     hipError_t e = step_launch<TpDesc, k_tempo>(ps->desc[ST_TEMPO], p.tdesc, dim3((unsigned)p.tdesc.size()), dim3(TP_THREADS), st);
     if (e == hipSuccess) e = step_launch<PtDesc, k_pitch>(ps->desc[ST_PITCH], p.pdesc, dim3((unsigned)p.tiles[ST_PITCH], (unsigned)p.pdesc.size()), dim3(PS_TILE), st);
+    if (e == hipSuccess && !p.fdesc.empty()) {                     // one descriptor block, k_fm_frame and k_fm_ola
+        PairBuf& b = ps->desc[ST_FORMANT];
+        e = b.upload(p.fdesc.data(), p.fdesc.size() * sizeof(FmDesc), st);
+        if (e == hipSuccess) e = formant_launch((const FmDesc*)b.dev, (int)p.fdesc.size(), p.fm_frames, p.tiles[ST_FORMANT], ps->f_tab, st);
+    }
     if (e == hipSuccess) e = step_launch<LoDesc, k_loud>(ps->desc[ST_LOUD], p.odesc, dim3((unsigned)p.odesc.size()), dim3(LD_THREADS), st);
     if (e == hipSuccess) e = step_launch<MkDesc, k_mark>(ps->desc[ST_MARK], p.mdesc, dim3((unsigned)p.mdesc.size()), dim3(MK_THREADS), st);
     if (e == hipSuccess) e = step_launch<LvDesc, k_level>(ps->desc[ST_LEVEL], p.ldesc, dim3((unsigned)p.tiles[ST_LEVEL], (unsigned)p.ldesc.size()), dim3(PS_TILE), st);
@@ -2012,6 +2105,7 @@ static void chain_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs) {
             add(tp, ST_TEMPO); tp.frames = w.frames; tp.cur ^= 1;
         }
         if (step_on(r, ST_PITCH)) { add(r.pt, ST_PITCH); if (!sg.last) r.pt.cur ^= 1; }
+        if (step_on(r, ST_FORMANT) && (w.n_in[ST_FORMANT] > 0 || w.n_out[ST_FORMANT] > 0)) { add(r.fm, ST_FORMANT); if (!sg.last) r.fm.cur ^= 1; }
         if (step_on(r, ST_LOUD) && w.n_in[ST_LOUD] > 0) { add(r.ld, ST_LOUD); r.ld.cur ^= 1; }
         if (step_on(r, ST_MARK) && w.n_in[ST_MARK] > 0) { add(r.mk, ST_MARK); r.mk.cur ^= 1; }
         if (step_on(r, ST_LEVEL)) { add(r.lv, ST_LEVEL); if (!sg.last) r.lv.cur ^= 1; }
@@ -2142,3 +2236,6 @@ extern "C" q3_status q3_pcm_stage_push(q3_pcm_stage* ps, int n_rows, const int* 
     if (total > 0) HIPC(hipMemcpyAsync(in.dev + db, in.host + db, total * 4, hipMemcpyHostToDevice, ps->st));
     return pcm_stage_push_dev(ps, segs, ps->st, out_host, n_samples);
 }
+
+// the formant step's kernels and rules: part of this unit
+#include "q3_formant.hip"

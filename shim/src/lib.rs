@@ -146,6 +146,14 @@ pub mod ffi {
         pub fn q3_pcm_stage_bound_pitch(sample_rate: u32, tempo_permille: i32, cents: i32, with_level: i32, n_in: usize, n_out_max: *mut usize) -> i32;
         pub fn q3_session_set_pitch(s: *mut c_void, b: i32, cents: i32) -> i32;
         pub fn q3_batcher_ticket_pitch(b: *mut c_void, ticket: i64, cents: i32) -> i32;
+        // the output stage's formant step: the spectral envelope kept where the pitch moves, or shifted on its own
+        pub fn q3_pcm_stage_set_formant(ps: *mut c_void, row: i32, keep: i32, fcents: i32) -> i32;
+        pub fn q3_pcm_stage_formant_plan(tempo_permille: i32, cents: i32, keep: i32, fcents: i32, omega: *mut f32, runs: *mut i32) -> i32;
+        pub fn q3_pcm_stage_formant_count(n_in_total: usize, ended: i32, n_out: *mut usize) -> i32;
+        pub fn q3_pcm_stage_formant_tables(twiddles: *mut f32, cap1: usize, window: *mut f32, cap2: usize, n: *mut i32, h: *mut i32) -> i32;
+        pub fn q3_pcm_stage_bound_formant(sample_rate: u32, tempo_permille: i32, cents: i32, with_level: i32, edge_ms: i32, pause_ms: i32, n_in: usize, n_out_max: *mut usize) -> i32;
+        pub fn q3_session_set_formant(s: *mut c_void, b: i32, keep: i32, fcents: i32) -> i32;
+        pub fn q3_batcher_ticket_formant(b: *mut c_void, ticket: i64, keep: i32, fcents: i32) -> i32;
         // the output stage's silence step: edges trimmed and pauses capped per row, at the very front; threshold 0 = off
         pub fn q3_pcm_stage_set_silence(ps: *mut c_void, row: i32, threshold_mb: i32, edge_ms: i32, pause_ms: i32) -> i32;
         pub fn q3_pcm_stage_silence(ps: *mut c_void, row: i32, n_in: *mut i64, n_out: *mut i64, lead_cut: *mut i64, pause_cut: *mut i64, trail_cut: *mut i64) -> i32;
