@@ -179,8 +179,13 @@ q3_status q3_model_set_codec_planes(q3_model* m, int planes);
  * 16-row-tile kernels; everything else (4-row tiles, wide sessions, long-prompt prefill) keeps bf16. The quantisation of the weights is
  * the only new rounding. HBM use goes UP by the FP8 images. A finalized device model only; Q3_UNSUPPORTED (nothing changed) while
  * sessions of the model are alive; empties the prefix cache. A session keeps the format it was created under.
- * q3_model_weight_info: the format, the matrices converted, and their bytes as bf16 tiles and as FP8 images (0 under BF16). */
-enum { Q3_WEIGHTS_BF16 = 0, Q3_WEIGHTS_FP8 = 1 };
+ * Q3_WEIGHTS_FP8_ALL: everything Q3_WEIGHTS_FP8 converts, plus the 4-row-tile launches of sessions of up to 8 rows (every narrow
+ * projection at 1-2 rows, the N <= 1024 ones up to 8): those matrices get a second FP8 image in 4-row tiles with the same codes and
+ * scales, so HBM use goes up by these images too. Sessions of 9-16 rows on the 4-row tiles, wide sessions, the text projection and
+ * prefill keep bf16. Any two of the three formats can be switched between; the images no longer needed are freed.
+ * q3_model_weight_info: the format, the matrices converted (each counted once), and the bytes of the converted images as bf16 tiles
+ * and as FP8 images (0 under BF16). */
+enum { Q3_WEIGHTS_BF16 = 0, Q3_WEIGHTS_FP8 = 1, Q3_WEIGHTS_FP8_ALL = 2 };
 q3_status q3_model_set_weight_format(q3_model* m, int format);
 q3_status q3_model_weight_info(const q3_model* m, int* format, int* matrices, size_t* bf16_bytes, size_t* fp8_bytes);
 q3_status q3_model_kv_pool_info(q3_model* m, int* page_positions, size_t* page_bytes, int* pages_total, int* pages_in_use, int* pages_peak);

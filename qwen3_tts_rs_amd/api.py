@@ -190,6 +190,7 @@ def fill_request(r, u: "Utterance", options: "SynthesisOptions", keep: list):
 
 
 KV_DTYPES = {"f32": 0, "bf16": 1, "fp8": 2}      # Q3_DTYPE_F32 / Q3_DTYPE_BF16 / Q3_DTYPE_FP8_E4M3
+WEIGHT_FORMATS = ("bf16", "fp8", "fp8-all")      # Q3_WEIGHTS_BF16 / Q3_WEIGHTS_FP8 / Q3_WEIGHTS_FP8_ALL
 
 
 def kv_dtype_code(kv_dtype: Optional[str], kv_bf16: bool = False) -> int:
@@ -1123,18 +1124,19 @@ class Qwen3TTS:
 
     def set_weight_format(self, fmt: str):
         """Weight format of the decode GEMVs (q3_model_set_weight_format): "bf16" (default) or "fp8" — e4m3 codes with one
-        power-of-two scale per row and 128-wide K block, built on the device, for sessions of up to 16 rows. Refused while
-        sessions of the model are alive; sessions created afterwards use it."""
-        if fmt not in ("bf16", "fp8"):
-            raise ValueError(f"weight format {fmt!r}: 'bf16' or 'fp8'")
-        check(lib.q3_model_set_weight_format(self._h, 1 if fmt == "fp8" else 0))
+        power-of-two scale per row and 128-wide K block, built on the device, for sessions of up to 16 rows — or "fp8-all",
+        which also converts the 4-row-tile launches of sessions of up to 8 rows. Refused while sessions of the model are
+        alive; sessions created afterwards use it."""
+        if fmt not in WEIGHT_FORMATS:
+            raise ValueError(f"weight format {fmt!r}: 'bf16', 'fp8' or 'fp8-all'")
+        check(lib.q3_model_set_weight_format(self._h, WEIGHT_FORMATS.index(fmt)))
 
     def weight_info(self) -> dict:
         """q3_model_weight_info: the format, the matrices converted, their bytes as bf16 tiles and as FP8 images."""
         f, n = ctypes.c_int(), ctypes.c_int()
         b16, b8 = ctypes.c_size_t(), ctypes.c_size_t()
         check(lib.q3_model_weight_info(self._h, ctypes.byref(f), ctypes.byref(n), ctypes.byref(b16), ctypes.byref(b8)))
-        return {"format": "fp8" if f.value == 1 else "bf16", "matrices": n.value, "bf16_bytes": b16.value, "fp8_bytes": b8.value}
+        return {"format": WEIGHT_FORMATS[f.value], "matrices": n.value, "bf16_bytes": b16.value, "fp8_bytes": b8.value}
 
     @property
     def weight_format(self) -> str:

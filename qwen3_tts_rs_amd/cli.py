@@ -107,8 +107,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--feed-tokens", type=int, default=0, metavar="N",
                     help="feed the text N tokens at a time through the open-text path, as an LLM would (reports the time from the "
                          "first token to the first audio; writes the same WAV as without the flag)")
-    ap.add_argument("--weight-format", choices=["bf16", "fp8"], default="bf16",
-                    help="fp8: e4m3 block-scaled weights in the decode GEMVs of sessions of up to 16 rows (opt-in; the default streams bf16)")
+    ap.add_argument("--weight-format", choices=["bf16", "fp8", "fp8-all"], default="bf16",
+                    help="fp8: e4m3 block-scaled weights in the decode GEMVs of sessions of up to 16 rows (opt-in; the default streams bf16); "
+                         "fp8-all: also in the 4-row-tile launches of sessions of up to 8 rows")
     ap.add_argument("--prefix-cache", type=int, default=0, metavar="PAGES",
                     help="keep up to PAGES KV pages (128 positions each) of prefilled --instruct prompts for later requests of this model (0 = off)")
     ap.add_argument("--no-eos", action="store_true", help="disable EOS (fixed-length runs on synthetic weights)")

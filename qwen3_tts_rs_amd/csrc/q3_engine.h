@@ -109,7 +109,11 @@ struct Slot {
 };
 // a GEMV weight: 16-row-tile image (t1) and, for narrow projections, a 4-row-tile image (t2)
 // (+ while the model's weight format is FP8, q3_model_set_weight_format: the mode-3 image c3 and its scale bytes s3)
-struct TW { const uint16_t* t1 = nullptr; const uint16_t* t2 = nullptr; const uint8_t* c3 = nullptr; const uint8_t* s3 = nullptr; };
+// (+ under Q3_WEIGHTS_FP8_ALL: the mode-4 image c4 / s4 of every matrix that keeps a 4-row-tile image)
+struct TW {
+    const uint16_t* t1 = nullptr; const uint16_t* t2 = nullptr; const uint8_t* c3 = nullptr; const uint8_t* s3 = nullptr;
+    const uint8_t* c4 = nullptr; const uint8_t* s4 = nullptr;
+};
 struct LayerW {
     const float *in_ln, *q_norm, *k_norm, *post_ln;
     TW qkv, o, gate, up, down;
@@ -314,19 +318,27 @@ static inline int pick_mode(const TW& w, int M, int N, int K) {
 }
 // fp8 (a session of a model in the FP8 weight format): mode 3 exactly where the pick is the 16-row tiles at M <= 16 and the matrix
 // has a mode-3 image; the 4-row tiles, wide sessions and everything else keep their bf16 images
-static inline bool use_w8(const TW& w, int mode, int M, bool fp8) { return fp8 && mode == 1 && M <= 16 && w.c3 != nullptr; }
+// fmt: the session's weight format (Q3_WEIGHTS_*). Under Q3_WEIGHTS_FP8_ALL a pick of the 4-row tiles at M <= 8 becomes mode 4 as
+// well, where the matrix has that image (k_gemv_w8r4); M > 8 on the 4-row tiles keeps bf16
+static inline bool use_w8(const TW& w, int mode, int M, int fmt) { return fmt != Q3_WEIGHTS_BF16 && mode == 1 && M <= 16 && w.c3 != nullptr; }
+static inline bool use_w8r4(const TW& w, int mode, int M, int fmt) { return fmt == Q3_WEIGHTS_FP8_ALL && mode == 2 && M <= 8 && w.c4 != nullptr; }
 static inline void to_w8(LinArgs& a, const TW& w, const TW* w2, int K) {
     a.tiled = 3; a.Kpad = kpad_for(3, K); a.W = reinterpret_cast<const uint16_t*>(w.c3); a.S = w.s3;
     if (w2) { a.W2 = reinterpret_cast<const uint16_t*>(w2->c3); a.S2 = w2->s3; }
 }
-static inline void set_w(LinArgs& a, const TW& w, int M, int N, int K, bool fp8 = false) {
-    a.tiled = pick_mode(w, M, N, K); a.W = a.tiled == 2 ? w.t2 : w.t1; a.Kpad = kpad_for(a.tiled, K);
-    if (use_w8(w, a.tiled, M, fp8)) to_w8(a, w, nullptr, K);
+static inline void to_w8r4(LinArgs& a, const TW& w, const TW* w2, int K) {
+    a.tiled = 4; a.Kpad = (K + 255) & ~255; a.W = reinterpret_cast<const uint16_t*>(w.c4); a.S = w.s4;
+    if (w2) { a.W2 = reinterpret_cast<const uint16_t*>(w2->c4); a.S2 = w2->s4; }
 }
-static inline void set_w2(LinArgs& a, const TW& w, const TW& w2, int M, int N, int K, bool fp8 = false) {
-    set_w(a, w, M, N, K); a.W2 = a.tiled == 2 ? w2.t2 : w2.t1;
-    if (use_w8(w, a.tiled, M, fp8) && w2.c3) to_w8(a, w, &w2, K);
-    else if (a.tiled == 3) { a.tiled = 1; a.W = w.t1; a.S = nullptr; a.Kpad = kpad_for(1, K); }      // (a pair converts together or not at all)
+static inline void set_w(LinArgs& a, const TW& w, int M, int N, int K, int fmt = Q3_WEIGHTS_BF16) {
+    a.tiled = pick_mode(w, M, N, K); a.W = a.tiled == 2 ? w.t2 : w.t1; a.Kpad = kpad_for(a.tiled, K);
+    if (use_w8(w, a.tiled, M, fmt)) to_w8(a, w, nullptr, K);
+    else if (use_w8r4(w, a.tiled, M, fmt)) to_w8r4(a, w, nullptr, K);
+}
+static inline void set_w2(LinArgs& a, const TW& w, const TW& w2, int M, int N, int K, int fmt = Q3_WEIGHTS_BF16) {
+    set_w(a, w, M, N, K); a.W2 = a.tiled == 2 ? w2.t2 : w2.t1;       // (a pair converts together or not at all)
+    if (use_w8(w, a.tiled, M, fmt) && w2.c3) to_w8(a, w, &w2, K);
+    else if (use_w8r4(w, a.tiled, M, fmt) && w2.c4) to_w8r4(a, w, &w2, K);
 }
 // session-lifetime device blocks from the per-device size-class cache (q3_codec_run.hip)
 Q3_HIDDEN hipError_t dev_malloc(void** p, size_t bytes);
@@ -492,7 +504,7 @@ struct q3_session {
     // bf16 / KV8 K/V (opt-in, q3_session_set_kv_dtype; bf16 is the reference GPU path's cache dtype): the prompt is prefilled into
     // f32 pages as always, converted once into pages of the dtype's pool (kv_in_dtype == kv_dtype from then on), and the decode
     // attention reads / appends that dtype. kv_dtype: what the session was asked for; kv_in_dtype: what its pages hold now
-    bool w_fp8 = false;      // the model's weight format when this session was created (q3_model_set_weight_format): read once, before any capture
+    int w_fp8 = Q3_WEIGHTS_BF16;      // the model's weight format (Q3_WEIGHTS_*) when this session was created (q3_model_set_weight_format): read once, before any capture
     int kv_dtype = Q3_DTYPE_F32, kv_in_dtype = Q3_DTYPE_F32; unsigned long long* kv_conv = nullptr;      // kv_conv: [2][B * KV_MAX_PAGES] page lists of the conversion launch
     float *rows = nullptr, *embeds = nullptr, *xvec = nullptr; int n_rows_total = 0;
     // prefill scratch, session-lifetime (no hipMalloc / hipFree and no extra stream syncs on the time-to-first-audio path)

@@ -64,8 +64,9 @@ struct LinArgs {
     int epi = EPI_NONE;
     int tiled = 0;                  // 1: 16-row MFMA tiles [N/16][Kpad/32][64 lanes][8 bf16]; 2: 4-row tiles [N/4][Kpad/128][64][8]
                                     // 3: FP8 e4m3 codes in W / W2, 16 rows x 64 k per tile [N/16][Kpad/64][64 lanes][16 bytes] (q3_kernels_w8.hip; M <= 16)
-    int Kpad = 0;                   // K rounded up to 32 (tiled == 1) or 128 (tiled == 2, 3)
-    const uint8_t* S = nullptr;     // tiled == 3: E8M0 scale bytes of W, one per row and 128-k block [N/16][Kpad/128][16 rows]
+                                    // 4: FP8 e4m3 codes in W / W2, 4 rows x 256 k per tile [N/4][Kpad/256][64 lanes][16 bytes] (q3_kernels_w8.hip; M <= 8)
+    int Kpad = 0;                   // K rounded up to 32 (tiled == 1), 128 (tiled == 2, 3) or 256 (tiled == 4)
+    const uint8_t* S = nullptr;     // tiled == 3: E8M0 scale bytes of W, one per row and 128-k block [N/16][Kpad/128][16 rows]; tiled == 4: [N/4][Kpad/128][4 rows]
     const uint8_t* S2 = nullptr;    // ... of W2
     // Split-K in two (k_gemv_sk2: tiled == 1, no fused norm, epilogue none / resid): the K halves of a 16-row tile run as
     // two workgroups that ADD their results into y with f32 atomics. y MUST hold zeros when the launch starts; with exactly
@@ -93,6 +94,11 @@ hipError_t launch_gemv_w8(const LinArgs& a, hipStream_t st);
 size_t w8_code_bytes(int N, int K);
 size_t w8_scale_bytes(int N, int K);
 hipError_t launch_w8_build(const uint16_t* t1, int N, int K, uint8_t* codes, uint8_t* scales, hipStream_t st);
+// the 4-row-tile form (tiled == 4, M <= 8, no split-K) and its image, built from the mode-2 bf16 image t2: the same codes and exponents
+hipError_t launch_gemv_w8r4(const LinArgs& a, hipStream_t st);
+size_t w8r4_code_bytes(int N, int K);
+size_t w8r4_scale_bytes(int N, int K);
+hipError_t launch_w8_build4(const uint16_t* t2, int N, int K, uint8_t* codes, uint8_t* scales, hipStream_t st);
 
 // ---- long-prompt prefill (q3_kernels_prefill.hip): real GEMM over the same tiled weight image + query-blocked attention ----
 struct GemmArgs {

@@ -346,39 +346,51 @@ static std::vector<W8Item> w8_items(q3_model* m) {
     v.push_back({&m->codec_head, c.codec_vocab, c.hidden});
     v.push_back({&m->mtp_w, c.cp_hidden, c.hidden});
     for (auto& h : m->cp_head) v.push_back({&h, c.cp_vocab, c.cp_hidden});
-    v.erase(std::remove_if(v.begin(), v.end(), [](const W8Item& i) { return i.w->t1 == nullptr; }), v.end());
+    v.erase(std::remove_if(v.begin(), v.end(), [](const W8Item& i) { return i.w->t1 == nullptr && i.w->t2 == nullptr; }), v.end());
     return v;
 }
+// Q3_WEIGHTS_FP8_ALL: on top of that, every matrix that keeps a 4-row-tile image gets a mode-4 image built from it (k_w8_build4), in the
+// same allocation. A switch builds the whole arena of the new format first and frees the old one after, so a failure changes nothing.
 extern "C" q3_status q3_model_set_weight_format(q3_model* m, int format) {
     if (!m || m->device < 0) return set_err(Q3_INVALID_ARG, "q3_model_set_weight_format: no device model");
-    if (format != Q3_WEIGHTS_BF16 && format != Q3_WEIGHTS_FP8) return set_err(Q3_INVALID_ARG, "q3_model_set_weight_format: %d (Q3_WEIGHTS_BF16 or Q3_WEIGHTS_FP8)", format);
+    if (format != Q3_WEIGHTS_BF16 && format != Q3_WEIGHTS_FP8 && format != Q3_WEIGHTS_FP8_ALL)
+        return set_err(Q3_INVALID_ARG, "q3_model_set_weight_format: %d (Q3_WEIGHTS_BF16, Q3_WEIGHTS_FP8 or Q3_WEIGHTS_FP8_ALL)", format);
     if (!m->finalized) return set_err(Q3_INVALID_ARG, "q3_model_set_weight_format: model not finalized");
     if (m->n_sessions.load() > 0) return set_err(Q3_UNSUPPORTED, "q3_model_set_weight_format: %d session(s) of this model are alive (free them first)", m->n_sessions.load());
     if (format == m->weight_format) return Q3_OK;
     HIPC(hipSetDevice(m->device));
     std::vector<W8Item> items = w8_items(m);
-    if (format == Q3_WEIGHTS_FP8) {
-        size_t total = 0, bf16 = 0;
-        std::vector<size_t> off;
-        for (const W8Item& i : items) {
-            off.push_back(total);
-            total += (w8_code_bytes(i.N, i.K) + w8_scale_bytes(i.N, i.K) + 255) & ~(size_t)255;
-            bf16 += tiled_elems(1, i.N, i.K) * 2;
+    uint8_t* arena = nullptr;
+    size_t total = 0, bf16 = 0;
+    int matrices = 0;
+    std::vector<size_t> off3(items.size(), 0), off4(items.size(), 0);
+    if (format != Q3_WEIGHTS_BF16) {
+        for (size_t k = 0; k < items.size(); ++k) {
+            const W8Item& i = items[k];
+            const bool m3 = i.w->t1 != nullptr, m4 = format == Q3_WEIGHTS_FP8_ALL && i.w->t2 != nullptr;
+            if (m3) { off3[k] = total; total += (w8_code_bytes(i.N, i.K) + w8_scale_bytes(i.N, i.K) + 255) & ~(size_t)255; bf16 += tiled_elems(1, i.N, i.K) * 2; }
+            if (m4) { off4[k] = total; total += (w8r4_code_bytes(i.N, i.K) + w8r4_scale_bytes(i.N, i.K) + 255) & ~(size_t)255; bf16 += tiled_elems(2, i.N, i.K) * 2; }
+            matrices += (m3 || m4) ? 1 : 0;
         }
-        uint8_t* arena = nullptr;
         if (hipMalloc((void**)&arena, total ? total : 256) != hipSuccess) { (void)hipGetLastError(); return set_err(Q3_OOM, "q3_model_set_weight_format: %zu bytes for the FP8 images", total); }
         hipError_t e = hipSuccess;
-        for (size_t k = 0; k < items.size() && e == hipSuccess; ++k)
-            e = launch_w8_build(items[k].w->t1, items[k].N, items[k].K, arena + off[k], arena + off[k] + w8_code_bytes(items[k].N, items[k].K), 0);
+        for (size_t k = 0; k < items.size() && e == hipSuccess; ++k) {
+            const W8Item& i = items[k];
+            if (i.w->t1) e = launch_w8_build(i.w->t1, i.N, i.K, arena + off3[k], arena + off3[k] + w8_code_bytes(i.N, i.K), 0);
+            if (e == hipSuccess && format == Q3_WEIGHTS_FP8_ALL && i.w->t2)
+                e = launch_w8_build4(i.w->t2, i.N, i.K, arena + off4[k], arena + off4[k] + w8r4_code_bytes(i.N, i.K), 0);
+        }
         if (e == hipSuccess) e = q3_hipDeviceSynchronize();
         if (e != hipSuccess) { (void)hipFree(arena); HIPC(e); }
-        for (size_t k = 0; k < items.size(); ++k) { items[k].w->c3 = arena + off[k]; items[k].w->s3 = arena + off[k] + w8_code_bytes(items[k].N, items[k].K); }
-        m->w8_arena = arena; m->w8_matrices = (int)items.size(); m->w8_bf16_bytes = bf16; m->w8_fp8_bytes = total;
-    } else {
-        for (const W8Item& i : items) { i.w->c3 = nullptr; i.w->s3 = nullptr; }
-        HIPC(hipFree(m->w8_arena));
-        m->w8_arena = nullptr; m->w8_matrices = 0; m->w8_bf16_bytes = 0; m->w8_fp8_bytes = 0;
     }
+    for (size_t k = 0; k < items.size(); ++k) {
+        TW& w = *items[k].w;
+        const bool m3 = arena && w.t1, m4 = arena && format == Q3_WEIGHTS_FP8_ALL && w.t2;
+        w.c3 = m3 ? arena + off3[k] : nullptr; w.s3 = m3 ? w.c3 + w8_code_bytes(items[k].N, items[k].K) : nullptr;
+        w.c4 = m4 ? arena + off4[k] : nullptr; w.s4 = m4 ? w.c4 + w8r4_code_bytes(items[k].N, items[k].K) : nullptr;
+    }
+    if (m->w8_arena) HIPC(hipFree(m->w8_arena));       // the images of the format that is left
+    m->w8_arena = arena; m->w8_matrices = matrices; m->w8_bf16_bytes = bf16; m->w8_fp8_bytes = total;
     m->weight_format = format;
     prefix_clear(m);      // cached K/V belongs to the format that produced it
     return Q3_OK;

@@ -33,7 +33,8 @@ static hipError_t run_linear(q3_session* s, const LinArgs& a_in) {
     e = launch_linear(a, s->stream);
     hipError_t e2 = hipEventRecord(e1, s->stream);
     s->prof_events.push_back({e0, e1});
-    s->prof_event_bytes.push_back((a.tiled == 3 ? (double)(w8_code_bytes(a.N, a.K) + w8_scale_bytes(a.N, a.K)) : (double)a.N * a.K * 2.0) * (a.epi == EPI_SWIGLU ? 2.0 : 1.0));
+    s->prof_event_bytes.push_back((a.tiled == 3 ? (double)(w8_code_bytes(a.N, a.K) + w8_scale_bytes(a.N, a.K)) : a.tiled == 4 ? (double)(w8r4_code_bytes(a.N, a.K) + w8r4_scale_bytes(a.N, a.K))
+                                                : (double)a.N * a.K * 2.0) * (a.epi == EPI_SWIGLU ? 2.0 : 1.0));
     {   // launch inventory (q3_session_profile_shapes): M, N, K, epilogue, fused input norm, reserved, tiling
         ProfShape ps{a.M, a.N, a.K, a.epi, a.norm_w ? 1 : 0, 0, a.ksplit == 2 ? 3 : a.tiled, 1};
         bool found = false;
@@ -221,7 +222,7 @@ q3_status lm_layer(q3_session* s, const LmDims& d, const LayerW& w, LmBuf& b, fl
             if (n_splits > 1) HIPC(launch_attn_merge(t, s->stream));
         }
     }
-    auto force16 = [&](LinArgs& l, const TW& tw) { l.tiled = 1; l.W = tw.t1; l.Kpad = kpad_for(1, l.K); l.ksplit = 2; if (use_w8(tw, 1, l.M, s->w_fp8)) to_w8(l, tw, nullptr, l.K); };
+    auto force16 = [&](LinArgs& l, const TW& tw) { l.tiled = 1; l.W = tw.t1; l.S = nullptr; l.Kpad = kpad_for(1, l.K); l.ksplit = 2; if (use_w8(tw, 1, l.M, s->w_fp8)) to_w8(l, tw, nullptr, l.K); };
     LinArgs o;
     o.N = d.H; o.K = QD; set_w(o, w.o, B, o.N, o.K, s->w_fp8); o.x = b.ATT; o.ldx = QD; o.resid = b.X; o.ldr = d.H; o.y = b.SUM; o.ldy = d.H; o.M = B; o.epi = EPI_RESID;
     if (o_sk) force16(o, w.o);
@@ -539,7 +540,7 @@ q3_status session_create(q3_model* m, const q3_request* reqs, int batch, int fra
     s->m = m; s->B = batch; s->opts = reqs[0].opts;
     { static std::atomic<uint64_t> next_uid{1}; s->uid = next_uid.fetch_add(1); }
     m->refs.fetch_add(1); m->n_sessions.fetch_add(1);
-    s->w_fp8 = m->weight_format == Q3_WEIGHTS_FP8;
+    s->w_fp8 = m->weight_format;
     if (s->opts.max_length < 1) return set_err(Q3_INVALID_ARG, "max_length must be >= 1");
     s->seq.resize(batch); s->out.resize((size_t)batch);
     int rows = 0;
@@ -1751,7 +1752,7 @@ q3_status session_append_many(q3_session* s, const std::vector<TextPiece>& piece
 // the frame later is safe by default. Development switches: Q3_AQL_T_ACQ=0 / Q3_AQL_T_REL=0 keep that half of every boundary,
 // Q3_AQL_T_ONLY=<substring+substring> restricts the rule to kernels whose name holds one of the substrings (bisecting).
 static void frame_fence_policy(const char* name, int* acquire, int* release) {
-    static const char* const families[] = {"k_gemv_mfmaI", "k_gemv_sk2I", "k_gemv_gu24I", "k_gemv_ldsI", "k_gemv_mfma4I", "k_gemv_w8I",
+    static const char* const families[] = {"k_gemv_mfmaI", "k_gemv_sk2I", "k_gemv_gu24I", "k_gemv_ldsI", "k_gemv_mfma4I", "k_gemv_w8I", "k_gemv_w8r4I",
                                            "k_attn_cpI", "k_attn_fusedI", "k_attn_mergeI", "k_attn_first2I", "k_attn_kv8I"};
     const bool drop_acq = !(getenv("Q3_AQL_T_ACQ") && atoi(getenv("Q3_AQL_T_ACQ")) == 0);
     const bool drop_rel = !(getenv("Q3_AQL_T_REL") && atoi(getenv("Q3_AQL_T_REL")) == 0);

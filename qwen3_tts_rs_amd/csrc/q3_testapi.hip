@@ -193,7 +193,7 @@ extern "C" q3_status q3_linear_ex(int device, const q3_linear_ex_args* p) {
     const int M = p->M, N = p->N, K = p->K;
     if (M < 1 || M > Q3_MAX_BATCH || N < 1 || K < 8 || K % 8) return set_err(Q3_INVALID_ARG, "q3_linear_ex: bad shape (1 <= M <= %d, K a multiple of 8)", Q3_MAX_BATCH);
     if (p->ldx < K || p->ldx % 4 || p->ldy < N || p->M_alloc < M) return set_err(Q3_INVALID_ARG, "q3_linear_ex: bad pitch (ldx >= K, ldx %% 4 == 0, ldy >= N, M_alloc >= M)");
-    if (p->epi < EPI_NONE || p->epi > EPI_SWIGLU || p->tiled < -1 || p->tiled > 3 || p->ksplit < 1) return set_err(Q3_INVALID_ARG, "q3_linear_ex: epi 0..3, tiled -1..3, ksplit >= 1");
+    if (p->epi < EPI_NONE || p->epi > EPI_SWIGLU || p->tiled < -1 || p->tiled > 4 || p->ksplit < 1) return set_err(Q3_INVALID_ARG, "q3_linear_ex: epi 0..3, tiled -1..4, ksplit >= 1");
     if (p->epi == EPI_SWIGLU && !p->w2) return set_err(Q3_INVALID_ARG, "q3_linear_ex: SwiGLU needs a second matrix");
     if (p->epi == EPI_RESID && (!p->resid || p->ldr < N)) return set_err(Q3_INVALID_ARG, "q3_linear_ex: residual epilogue needs resid with ldr >= N");
     if (p->zero_n < 0 || p->zero_n % 4 || p->zero_guard < 0 || (p->zero_n > 0 && !p->zero_buf)) return set_err(Q3_INVALID_ARG, "q3_linear_ex: zero_n must be a multiple of 4 with a buffer");
@@ -203,13 +203,14 @@ extern "C" q3_status q3_linear_ex(int device, const q3_linear_ex_args* p) {
     HIPC(hipSetDevice(device));
     DevPool pool;
     const int nmat = p->epi == EPI_SWIGLU ? 2 : 1;
-    const int img = mode == 3 ? 1 : mode;            // FP8 (3): the device quantiser builds its image from the 16-row-tile bf16 image
+    const int img = mode == 3 ? 1 : mode == 4 ? 2 : mode;      // FP8 (3 / 4): the device quantiser builds its image from the 16-row / 4-row-tile bf16 image
     const size_t welems = mode == 0 ? (size_t)N * K : tiled_elems(img, N, K);
     uint16_t* w; float *x, *y, *b = nullptr, *nw = nullptr, *res = nullptr, *zb = nullptr, *ws = nullptr;
     uint8_t* w8 = nullptr;                           // per matrix: codes, then scales
-    const size_t w8_bytes = (w8_code_bytes(N, K) + w8_scale_bytes(N, K) + 255) & ~(size_t)255;
+    const size_t w8_codes = mode == 4 ? w8r4_code_bytes(N, K) : w8_code_bytes(N, K);
+    const size_t w8_bytes = (w8_codes + (mode == 4 ? w8r4_scale_bytes(N, K) : w8_scale_bytes(N, K)) + 255) & ~(size_t)255;
     HIPC(pool.alloc(&w, welems * nmat));
-    if (mode == 3) HIPC(pool.alloc(&w8, w8_bytes * nmat));
+    if (mode >= 3) HIPC(pool.alloc(&w8, w8_bytes * nmat));
     for (int i = 0; i < nmat; ++i) {
         const uint16_t* src = i ? p->w2 : p->w;
         if (mode == 0) HIPC(q3_hipMemcpy(w + (size_t)i * welems, src, welems * 2, hipMemcpyHostToDevice));
@@ -218,7 +219,8 @@ extern "C" q3_status q3_linear_ex(int device, const q3_linear_ex_args* p) {
             retile_bf16(src, N, K, wt.data(), img);
             HIPC(q3_hipMemcpy(w + (size_t)i * welems, wt.data(), welems * 2, hipMemcpyHostToDevice));
         }
-        if (mode == 3) HIPC(launch_w8_build(w + (size_t)i * welems, N, K, w8 + i * w8_bytes, w8 + i * w8_bytes + w8_code_bytes(N, K), 0));
+        if (mode == 3) HIPC(launch_w8_build(w + (size_t)i * welems, N, K, w8 + i * w8_bytes, w8 + i * w8_bytes + w8_codes, 0));
+        if (mode == 4) HIPC(launch_w8_build4(w + (size_t)i * welems, N, K, w8 + i * w8_bytes, w8 + i * w8_bytes + w8_codes, 0));
     }
     const size_t xn = (size_t)M * p->ldx, yn = (size_t)p->M_alloc * p->ldy;
     HIPC(pool.alloc(&x, xn)); HIPC(q3_hipMemcpy(x, p->x, xn * 4, hipMemcpyHostToDevice));
@@ -238,10 +240,10 @@ extern "C" q3_status q3_linear_ex(int device, const q3_linear_ex_args* p) {
     LinArgs a;
     a.W = w; a.W2 = nmat == 2 ? w + welems : nullptr; a.x = x; a.ldx = p->ldx; a.norm_w = nw; a.eps = p->eps; a.bias = b;
     a.resid = res; a.ldr = res ? p->ldr : 0; a.y = y; a.ldy = p->ldy; a.M = M; a.N = N; a.K = K; a.epi = p->epi;
-    a.tiled = mode; a.Kpad = mode == 0 ? K : kpad_for(mode, K); a.ksplit = p->ksplit;
-    if (mode == 3) {
-        a.W = reinterpret_cast<const uint16_t*>(w8); a.S = w8 + w8_code_bytes(N, K);
-        if (nmat == 2) { a.W2 = reinterpret_cast<const uint16_t*>(w8 + w8_bytes); a.S2 = w8 + w8_bytes + w8_code_bytes(N, K); }
+    a.tiled = mode; a.Kpad = mode == 0 ? K : mode == 4 ? (K + 255) & ~255 : kpad_for(mode, K); a.ksplit = p->ksplit;
+    if (mode >= 3) {
+        a.W = reinterpret_cast<const uint16_t*>(w8); a.S = w8 + w8_codes;
+        if (nmat == 2) { a.W2 = reinterpret_cast<const uint16_t*>(w8 + w8_bytes); a.S2 = w8 + w8_bytes + w8_codes; }
     }
     a.zero = zb; a.zero_n = zb ? p->zero_n : 0; a.ws = ws; a.ws_bytes = ws_bytes;
     HIPC(q3_hipDeviceSynchronize());
@@ -1912,14 +1914,16 @@ extern "C" q3_status q3_session_frame_bytes(q3_session* s, int kv_len, double* w
     if (weight_bytes) *weight_bytes = 2.0 * (talker + 15.0 * cp_pass);          // bf16; SURVEY §8(d)
     if (weight_bytes && s->w_fp8) {
         // an FP8 session: every matrix its one-row-per-sequence steps take as mode 3 (set_w / the split-K pick of lm_layer) counts
-        // with its codes and scale bytes instead
+        // with its codes and scale bytes instead; under Q3_WEIGHTS_FP8_ALL likewise the ones they take as mode 4
         const q3_model* m = s->m; const int B = s->B;
-        auto saved = [&](const TW& w, int N, int K, bool sk) {
+        auto saved = [&](const TW& w, int N, int K, bool sk, const TW* pair = nullptr) {
             const int mode = (sk && s->ksplit && B >= 3 && N <= 2048 && K >= 2048) ? 1 : pick_mode(w, B, N, K);
-            return use_w8(w, mode, B, true) ? 2.0 * N * K - (double)(w8_code_bytes(N, K) + w8_scale_bytes(N, K)) : 0.0;
+            if (use_w8(w, mode, B, s->w_fp8) && (!pair || pair->c3)) return 2.0 * N * K - (double)(w8_code_bytes(N, K) + w8_scale_bytes(N, K));
+            if (use_w8r4(w, mode, B, s->w_fp8) && (!pair || pair->c4)) return 2.0 * N * K - (double)(w8r4_code_bytes(N, K) + w8r4_scale_bytes(N, K));
+            return 0.0;
         };
-        auto layer = [&](const LayerW& L, int H, int I, int nh, int nkv) {
-            return saved(L.qkv, (nh + 2 * nkv) * HEAD_DIM, H, false) + saved(L.o, H, nh * HEAD_DIM, true) + saved(L.gate, I, H, false) + saved(L.up, I, H, false) + saved(L.down, H, I, true);
+        auto layer = [&](const LayerW& L, int H, int I, int nh, int nkv) {      // (gate / up: a pair converts together or not at all)
+            return saved(L.qkv, (nh + 2 * nkv) * HEAD_DIM, H, false) + saved(L.o, H, nh * HEAD_DIM, true) + saved(L.gate, I, H, false, &L.up) + saved(L.up, I, H, false, &L.gate) + saved(L.down, H, I, true);
         };
         double t = saved(m->codec_head, c.codec_vocab, c.hidden, false), p = saved(m->cp_head[0], c.cp_vocab, c.cp_hidden, false);
         if (m->mtp_w.t1) p += saved(m->mtp_w, c.cp_hidden, c.hidden, false);
