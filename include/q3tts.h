@@ -1184,6 +1184,32 @@ q3_status q3_pcm_stage_bound_formant(uint32_t sample_rate, int tempo_permille, i
 /* Sessions and the batcher: q3_session_set_pitch's / q3_batcher_ticket_pitch's window and persistence. */
 q3_status q3_session_set_formant(q3_session* s, int b, int keep, int fcents);
 q3_status q3_batcher_ticket_formant(q3_batcher* b, int64_t ticket, int keep, int fcents);
+/* ---------------- output stage: the tone of a row (a cascade of up to 8 biquad sections, behind the formant step) ----------------
+ * n_bands in 0..8 (0, the default, is off: such a row takes the paths above and returns their bits and their launches, with no
+ * descriptor, launch or allocation); per band `kind` one of the five below, freq_hz in 20..11000, gain_mB in -2400..2400 (millibel;
+ * not read for the two pass kinds), q_milli in 100..10000 (Q x 1000; for the shelves the cookbook's alpha at that Q). Anything
+ * else is Q3_INVALID_ARG before the device is touched, and the message names the field. The step takes the stream behind the
+ * formant step at 24 kHz and hands on as many samples as it takes, at once: the loudness meter, the mark, the limiter and the
+ * resampler see the shaped signal.
+ * Each band is one second-order section of the Audio EQ Cookbook (R. Bristow-Johnson), designed once per setting by
+ * q3_tone_design(24000) in f64 and divided by a0; the sections run in the order given, in transposed direct form II:
+ * y = b0 x + s1; s1' = b1 x - a1 y + s2; s2' = b2 x - a2 y, the products and the two states in f64, the samples between sections
+ * f32 (a non-finite sample enters as 0). k_tone does not run the recursion sample after sample: the 64 lanes of a wave take 64
+ * samples each from zero state, an inclusive scan of the segments' affine state maps (A^64 per segment, A the section's 2 x 2
+ * state matrix, its powers made on the host in f64) gives every segment its true entry state, and each lane adds that state's
+ * free response. Where a segment begins depends on how the stream was cut into pushes, and so does the order of the sums: the
+ * same stream cut differently agrees to the rounding of f64 states and f32 samples, not bit for bit; the same cuts give the same
+ * bits. A row keeps 16 doubles of state in two copies (commit rule of the tails). No reference counterpart. */
+enum { Q3_TONE_PEAK = 0, Q3_TONE_LOWSHELF = 1, Q3_TONE_HIGHSHELF = 2, Q3_TONE_HIGHPASS = 3, Q3_TONE_LOWPASS = 4 };
+#define Q3_TONE_MAX_BANDS 8
+typedef struct { int32_t kind, freq_hz, gain_mB, q_milli; } q3_tone_band;
+q3_status q3_pcm_stage_set_tone(q3_pcm_stage* ps, int row, int n_bands, const q3_tone_band* bands);       /* also restarts the row; kept by _set / _reset / every other _set_* */
+/* host only: the cookbook section of one band at `rate` (8000..192000 Hz, freq_hz below rate / 2) as b0 b1 b2 a0 a1 a2 in f64, not
+ * normalised — the shape of q3_loudness_kweight */
+q3_status q3_tone_design(uint32_t rate, const q3_tone_band* band, double* ba);
+/* Sessions and the batcher: q3_session_set_pitch's / q3_batcher_ticket_pitch's window and persistence. */
+q3_status q3_session_set_tone(q3_session* s, int b, int n_bands, const q3_tone_band* bands);
+q3_status q3_batcher_ticket_tone(q3_batcher* b, int64_t ticket, int n_bands, const q3_tone_band* bands);
 /* ---------------- output stage: a silence trim and pause cap per row (at the very front of the row, before the stretcher) ----------------
  * threshold_mB: 0, the default, is off: such a row takes the paths above and returns their bits and their launches, and a push
  * without such a row has no launch, copy or wait it did not have. Otherwise -9000..-2000, millibel re full scale of a hop's mean

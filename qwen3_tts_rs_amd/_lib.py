@@ -180,6 +180,10 @@ class CWavDesc(ctypes.Structure):        # q3_wav_desc
                 ("frames", ctypes.c_int64), ("data_offset", ctypes.c_int64), ("data_bytes", ctypes.c_int64)]
 
 
+class CToneBand(ctypes.Structure):       # q3_tone_band
+    _fields_ = [("kind", ctypes.c_int32), ("freq_hz", ctypes.c_int32), ("gain_mB", ctypes.c_int32), ("q_milli", ctypes.c_int32)]
+
+
 class CTiming(ctypes.Structure):
     _fields_ = [("prefill_ms", ctypes.c_double), ("generation_ms", ctypes.c_double), ("decode_ms", ctypes.c_double),
                 ("generation_frames", ctypes.c_int32)]
@@ -260,6 +264,10 @@ SYMBOLS = {
     "q3_pcm_stage_bound_formant": (c_int, [ctypes.c_uint32, c_int, c_int, c_int, c_int, c_int, ctypes.c_size_t, P(ctypes.c_size_t)]),
     "q3_session_set_formant": (c_int, [c_void_p, c_int, c_int, c_int]),
     "q3_batcher_ticket_formant": (c_int, [c_void_p, ctypes.c_int64, c_int, c_int]),
+    "q3_pcm_stage_set_tone": (c_int, [c_void_p, c_int, c_int, P(CToneBand)]),
+    "q3_tone_design": (c_int, [ctypes.c_uint32, P(CToneBand), P(ctypes.c_double)]),
+    "q3_session_set_tone": (c_int, [c_void_p, c_int, c_int, P(CToneBand)]),
+    "q3_batcher_ticket_tone": (c_int, [c_void_p, ctypes.c_int64, c_int, P(CToneBand)]),
     "q3_pcm_stage_set_silence": (c_int, [c_void_p, c_int, c_int, c_int, c_int]),
     "q3_pcm_stage_silence": (c_int, [c_void_p, c_int] + [P(ctypes.c_int64)] * 5),
     "q3_pcm_stage_silence_hold": (c_int, [c_int, c_int, P(ctypes.c_size_t)]),

@@ -221,6 +221,7 @@ class Session:
         self._row_limit = [self._limit_of(u) for u in utts]       # frames a row can reach: sizes the PCM buffers of run()
         # per row what sizes the buffers of next_chunks_out: [tempo, level on, pitch, silence (edge_ms, pause_ms) or None, formant step asked]
         self._out_rows = [[1000, False, 0, None, False] for _ in utts]
+        self.tone = [() for _ in utts]                            # per row the bands of `set_tone`, as `tone_bands` returns them
         reqs = (CRequest * self.B)()
         for i, u in enumerate(utts):
             self._fill(reqs[i], u)
@@ -381,6 +382,15 @@ class Session:
         off. The window and the persistence of `set_pitch`."""
         check(lib.q3_session_set_formant(self._h, int(b), 1 if keep else 0, int(shift_cents)))
         self._note_out(b, 4, bool(keep) or bool(int(shift_cents)))
+
+    def set_tone(self, bands, b: int = -1):
+        """The tone of row b (-1: every row) in `next_chunks_out` (q3_session_set_tone): up to 8 bands (`tone_bands`: a string
+        "hp:120,peak:3000:+3:1.0" or (kind, freq_hz[, gain_db[, q]]) tuples) as a biquad cascade behind the formant step; None or
+        empty = off. The window and the persistence of `set_pitch`. `tone` holds what each row was given."""
+        t, n, arr = _tone_arg(bands)
+        check(lib.q3_session_set_tone(self._h, int(b), n, arr))
+        for r in (range(self.B) if b < 0 else [b]):
+            self.tone[r] = t
 
     def next_chunks_out(self) -> List[Tuple[Optional[AudioBuffer], bool]]:
         """`next_chunks` through the session's output stage (q3_session_next_chunks_out): one (chunk or None, done) per row, the
@@ -618,7 +628,7 @@ class Batcher:
 
     def submit_streamed(self, utt: Utterance, sample_rate: int = 24000, pcm16: bool = False, tempo_permille: int = 1000,
                         fmt: Optional[str] = None, gain_mb: int = 0, ceiling_mb: int = 0, target_lufs: Optional[float] = None,
-                        prior_gain_db: float = 0.0, pitch_cents: int = 0, silence=None, mark=None, formant=None) -> int:
+                        prior_gain_db: float = 0.0, pitch_cents: int = 0, silence=None, mark=None, formant=None, tone=None) -> int:
         """Queue one request whose audio is delivered while it runs (`read`); returns its ticket. sample_rate / pcm16 / fmt: the
         ticket's own output (q3_batcher_ticket_output) — `read` then returns samples at that rate, int16 when asked, uint8 for
         fmt "ulaw" / "alaw". tempo_permille: its speaking rate (q3_batcher_ticket_tempo; 1250 = 1.25 x as fast, 1000 = off).
@@ -626,7 +636,8 @@ class Batcher:
         to, from the gain prior_gain_db (q3_batcher_ticket_loudness; `loudness(ticket)` reads the result). pitch_cents: its pitch
         (q3_batcher_ticket_pitch; -1200..1200, 0 = off). silence = (threshold_db, edge_ms, pause_ms): its silence step
         (q3_batcher_ticket_silence; `silence(ticket)` reads the counts). mark = (key, db) or key: its keyed watermark
-        (q3_batcher_ticket_mark). formant = (keep, shift_cents): its formant step (q3_batcher_ticket_formant)."""
+        (q3_batcher_ticket_mark). formant = (keep, shift_cents): its formant step (q3_batcher_ticket_formant). tone:
+        its bands (`tone_bands`; q3_batcher_ticket_tone)."""
         code = pcm_format(pcm16, fmt)
         keep = []
         r = CRequest(); fill_request(r, utt, self.options, keep)
@@ -655,6 +666,12 @@ class Batcher:
         if formant is not None:
             try:
                 self.ticket_formant(int(t.value), *formant)
+            except _lib.Q3Error:
+                self.cancel(int(t.value)); self.fetch(int(t.value))
+                raise
+        if tone is not None:
+            try:
+                self.ticket_tone(int(t.value), tone)
             except _lib.Q3Error:
                 self.cancel(int(t.value)); self.fetch(int(t.value))
                 raise
@@ -742,6 +759,13 @@ class Batcher:
         """A streamed ticket's formant step (q3_batcher_ticket_formant): between its submission and the next `step`."""
         check(lib.q3_batcher_ticket_formant(self._h, int(ticket), 1 if keep else 0, int(shift_cents)))
         if int(shift_cents):
+            self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
+
+    def ticket_tone(self, ticket: int, bands):
+        """A streamed ticket's tone (q3_batcher_ticket_tone; `tone_bands`): between its submission and the next `step`."""
+        t, n, arr = _tone_arg(bands)
+        check(lib.q3_batcher_ticket_tone(self._h, int(ticket), n, arr))
+        if n:
             self._output.setdefault(int(ticket), (24000, PCM_F32))      # read through q3_batcher_read_out
 
     def submit_open(self, utt: Utterance, want: str = "stream", sample_rate: int = 24000, pcm16: bool = False,
@@ -1611,6 +1635,43 @@ def silence_mb(threshold_db) -> int:
     return 0 if threshold_db is None else int(round(float(threshold_db) * 100.0))
 
 
+TONE_PEAK, TONE_LOWSHELF, TONE_HIGHSHELF, TONE_HIGHPASS, TONE_LOWPASS = 0, 1, 2, 3, 4
+TONE_KINDS = {"peak": TONE_PEAK, "ls": TONE_LOWSHELF, "hs": TONE_HIGHSHELF, "hp": TONE_HIGHPASS, "lp": TONE_LOWPASS}
+TONE_Q_DEFAULT = 0.707
+
+
+def tone_bands(bands) -> Tuple[Tuple[int, int, int, int], ...]:
+    """The bands of a tone setting as the library's (kind, freq_hz, gain_mB, q_milli), in cascade order. `bands`: None (off), a
+    string "hp:120,peak:3000:+3:1.0,hs:8000:-2" or a sequence of (kind, freq_hz[, gain_db[, q]]) — kind a TONE_* value or "peak" /
+    "ls" / "hs" / "hp" / "lp", gain_db 0 and q 0.707 where left out. The ranges are the library's to refuse."""
+    if bands is None:
+        return ()
+    if isinstance(bands, str):
+        bands = [[f if i == 0 else float(f) for i, f in enumerate(b.strip().split(":"))] for b in bands.split(",") if b.strip()]
+    out = []
+    for b in bands:
+        b = list(b)
+        kind, freq, gain, qv = b + [0.0, TONE_Q_DEFAULT][len(b) - 2:] if 2 <= len(b) <= 4 else [None] * 4
+        if kind is None or (isinstance(kind, str) and kind not in TONE_KINDS):
+            raise ValueError(f"a tone band is kind:freq_hz[:gain_db[:q]] with kind one of {sorted(TONE_KINDS)}, not {b!r}")
+        out.append((TONE_KINDS[kind] if isinstance(kind, str) else int(kind), int(round(float(freq))), int(round(float(gain) * 100.0)),
+                    int(round(float(qv) * 1000.0))))
+    return tuple(out)
+
+
+def _tone_arg(bands):
+    t = tone_bands(bands)
+    return t, len(t), ((_lib.CToneBand * len(t))(*[_lib.CToneBand(*b) for b in t]) if t else None)
+
+
+def tone_design(band, rate: int = 24000) -> np.ndarray:
+    """The cookbook section of one band at `rate` as b0 b1 b2 a0 a1 a2 in float64 (q3_tone_design)."""
+    (b,) = tone_bands([band])
+    ba = np.zeros(6, np.float64)
+    check(lib.q3_tone_design(int(rate), ctypes.byref(_lib.CToneBand(*b)), ba.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return ba
+
+
 def mark_key(key) -> int:
     """A watermark key as the library's uint64: an int, a hex string ("c0ffee" / "0xc0ffee"), None or 0 for off."""
     if key is None:
@@ -1735,6 +1796,12 @@ class PcmStage:
         check(lib.q3_pcm_stage_set_formant(self._h, int(row), int(keep), int(shift_cents)))
         self._formant[int(row)] = bool(int(keep)) or bool(int(shift_cents))
 
+    def set_tone(self, row: int, bands):
+        """Row's tone (q3_pcm_stage_set_tone): up to 8 bands (`tone_bands`) as a biquad cascade behind the formant step, None or
+        empty = off; also restarts the row. `set`, `reset` and the other `set_*` keep it."""
+        _t, n, arr = _tone_arg(bands)
+        check(lib.q3_pcm_stage_set_tone(self._h, int(row), n, arr))
+
     def set_loudness(self, row: int, mode: int, target_mb: int = -1900, prior_mb: int = 0):
         """Row's loudness step (q3_pcm_stage_set_loudness): LOUD_OFF, LOUD_METER (measure, the samples pass) or LOUD_NORMALIZE
         (steer the row to target_mb, millibel of LUFS, from the gain prior_mb); also restarts the row. `set`, `reset`, `set_tempo`
@@ -1825,7 +1892,7 @@ class PcmStage:
 
 def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_permille: int = 1000, fmt: Optional[str] = None,
                  gain_mb: int = 0, ceiling_mb: int = 0, target_mb: Optional[int] = None, prior_mb: int = 0, pitch_cents: int = 0, silence=None,
-                 mark=None, formant=None) -> AudioBuffer:
+                 mark=None, formant=None, tone=None) -> AudioBuffer:
     """One-shot use of the output stage: a whole 24 kHz clip (AudioBuffer or array) at `rate`, int16 when asked (fmt: "f32" /
     "s16" / "ulaw" / "alaw") — what a caller of the whole-utterance paths (`run`, `decode`, `Batcher.fetch`) applies to their
     result. tempo_permille: the clip's speaking rate (1250 = 1.25 x as fast, 1000 = as it is). gain_mb / ceiling_mb: its level. target_mb / prior_mb: the loudness it is
@@ -1833,7 +1900,8 @@ def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_p
     pitch_cents: its pitch (-1200..1200 cents, 0 = as it is; the duration stays that of the tempo). silence = (threshold_db, edge_ms,
     pause_ms): its edges and pauses cut first, as `trim_silence` does. mark = (key, db) or key: its keyed watermark, as `mark_embed`
     adds it, behind the loudness and in front of the level. formant = (keep, shift_cents): keep holds the formants where pitch_cents
-    moves them, shift_cents moves them on their own (`PcmStage.set_formant`)."""
+    moves them, shift_cents moves them on their own (`PcmStage.set_formant`). tone: its bands (`tone_bands`), a biquad cascade in
+    front of the loudness and the level."""
     code = pcm_format(pcm16, fmt)
     x = np.ascontiguousarray(audio.samples if isinstance(audio, AudioBuffer) else audio, dtype=np.float32).reshape(-1)
     if isinstance(audio, AudioBuffer) and audio.sample_rate != 24000:
@@ -1847,6 +1915,8 @@ def resample_gpu(audio, rate: int, pcm16: bool = False, device: int = 0, tempo_p
             ps.set_pitch(0, pitch_cents)
         if formant is not None:
             ps.set_formant(0, *formant)
+        if tone is not None:
+            ps.set_tone(0, tone)
         if int(gain_mb) or int(ceiling_mb):
             ps.set_level(0, gain_mb, ceiling_mb)
         if target_mb is not None:

@@ -75,6 +75,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --streaming --pitch: keep the voice's formants where the pitch moves (the same speaker at another pitch)")
     ap.add_argument("--formant-shift", type=float, default=0.0, metavar="SEMITONES",
                     help="with --streaming: move the formants on their own, -6 .. +6 semitones, at any pitch")
+    ap.add_argument("--tone", default=None, metavar="BANDS",
+                    help="with --streaming: the tone, up to 8 comma-separated bands kind:freq_hz[:gain_db[:q]] with kind peak / ls / hs / "
+                         "hp / lp, e.g. \"hp:120,peak:3000:+3:1.0,hs:8000:-2\": a biquad cascade in the output stage, in front of the "
+                         "loudness, the level and the format")
     ap.add_argument("--output-format", choices=["f32", "s16", "ulaw", "alaw"], default="f32",
                     help="with --streaming: the format the chunks leave the output stage in; ulaw / alaw (ITU-T G.711, one byte per "
                          "sample) write a G.711 WAV (format tag 7 / 6)")
@@ -486,6 +490,14 @@ def main(argv=None) -> int:
     if formant and not a.streaming:
         print("error: --keep-formants / --formant-shift apply to --streaming (a whole utterance: api.resample_gpu(..., formant=(keep, cents)))", file=sys.stderr)
         return 2
+    try:
+        tone = api.tone_bands(a.tone)
+    except ValueError as e:
+        print(f"error: --tone: {e}", file=sys.stderr)
+        return 2
+    if tone and not a.streaming:
+        print("error: --tone applies to --streaming (a whole utterance: api.resample_gpu(..., tone=))", file=sys.stderr)
+        return 2
     gain_mb, ceiling_mb = int(round(a.gain_db * 100.0)), int(round(a.ceiling_db * 100.0))
     if loud is not None:
         ceiling_mb = loud[2]
@@ -494,7 +506,7 @@ def main(argv=None) -> int:
         print("error: --output-format / --gain-db / --ceiling-db apply to --streaming (convert a whole utterance with "
               "api.resample_gpu(..., fmt=, gain_mb=, ceiling_mb=))", file=sys.stderr)
         return 2
-    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None or sil is not None or mark is not None or formant):
+    if a.streaming and (a.output_rate != 24000 or tempo != 1000 or cents != 0 or a.output_format != "f32" or gain_mb or ceiling_mb or loud is not None or sil is not None or mark is not None or formant or tone):
         # the chunks of the streaming session, each through the session's output stage as it leaves
         s = model.session([utt], opts, kv_dtype=a.kv_dtype)
         try:
@@ -505,6 +517,8 @@ def main(argv=None) -> int:
                 s.set_pitch(cents)
             if formant:
                 s.set_formant(a.keep_formants, fcents)
+            if tone:
+                s.set_tone(a.tone)
             if gain_mb or ceiling_mb:
                 s.set_level(gain_mb, ceiling_mb)
             if loud is not None:

@@ -35,9 +35,9 @@ for f in q3_kernels_lm q3_kernels_gemv q3_kernels_wide q3_kernels_codec q3_kerne
   compile "$HERE/$f.hip" "$BUILD/$f.o" "$DEV_FLAGS" "$HERE/q3_kernels_w8.hip" "$HERE/q3_kernels_kv8.hip" "$HERE/q3_kernels.h" "$HERE/q3_internal.h" "$HERE/q3_capture_lock.h" "$API"
 done
 # the engine (host side of the hot path): ten units behind q3_engine.h
-# (q3_formant.hip is part of the q3_pcm_stage unit: included at its end)
+# (q3_formant.hip and q3_tone.hip are part of the q3_pcm_stage unit: included at its end)
 for f in q3_model q3_prefix_cache q3_codec_run q3_codec_stream q3_pcm_stage q3_intake q3_session q3_batcher q3_row_state q3_testapi; do
-  compile "$HERE/$f.hip" "$BUILD/$f.o" "$DEV_FLAGS" "$HERE/q3_formant.hip" "$HERE/q3_engine.h" "$HERE/q3_prefix_cache.h" "$HERE/q3_capture_lock.h" "$HERE/q3_kernels.h" "$HERE/q3_internal.h" "$HERE/q3_aql.h" "$API"
+  compile "$HERE/$f.hip" "$BUILD/$f.o" "$DEV_FLAGS" "$HERE/q3_formant.hip" "$HERE/q3_tone.hip" "$HERE/q3_engine.h" "$HERE/q3_prefix_cache.h" "$HERE/q3_capture_lock.h" "$HERE/q3_kernels.h" "$HERE/q3_internal.h" "$HERE/q3_aql.h" "$API"
 done
 # q3_denoise: its butterflies are pairs of f32 operations, which this unit keeps as single instructions (no packed f32 forms;
 # the host pass does not know the feature and says that it ignores it)

@@ -1243,6 +1243,9 @@ extern "C" q3_status q3_batcher_ticket_pitch(q3_batcher* b, int64_t ticket, int 
 extern "C" q3_status q3_batcher_ticket_formant(q3_batcher* b, int64_t ticket, int keep, int fcents) {
     return ticket_set(b, ticket, "q3_batcher_ticket_formant", "formant step", [&](const char* who, OutSettings& o) { return out_set_formant(who, o, keep, fcents); });
 }
+extern "C" q3_status q3_batcher_ticket_tone(q3_batcher* b, int64_t ticket, int n_bands, const q3_tone_band* bands) {
+    return ticket_set(b, ticket, "q3_batcher_ticket_tone", "tone", [&](const char* who, OutSettings& o) { return out_set_tone(who, o, n_bands, bands); });
+}
 extern "C" q3_status q3_batcher_ticket_level(q3_batcher* b, int64_t ticket, int gain_mB, int ceiling_mB) {
     return ticket_set(b, ticket, "q3_batcher_ticket_level", "level", [&](const char* who, OutSettings& o) { return out_set_level(who, o, gain_mB, ceiling_mB); });
 }

@@ -4,10 +4,11 @@
 //   q3_prefix_cache.hip the prefix cache: prefilled instruct pages shared across requests (q3_prefix_cache.h)
 //   q3_codec_run.hip device-memory cache, the vocoder pipeline (codec_decode_dev) and q3_decode_codes
 //   q3_codec_stream.hip the codec stream: the vocoder with per-row state, many rows per pass
-//   q3_pcm_stage.hip the output stage, per row a chain of steps (DESIGN 4.12 - 4.12g): silence trim and pause cap -> speaking rate
+//   q3_pcm_stage.hip the output stage, per row a chain of steps (DESIGN 4.12 - 4.12h): silence trim and pause cap -> speaking rate
 //                    (WSOLA) -> pitch in cents (varispeed) -> formants kept or shifted (a cepstral-envelope warp; its kernels are
-//                    q3_formant.hip, included at the unit's end) -> BS.1770 loudness meter / normaliser -> level (gain and look-ahead
-//                    peak limiter) -> resampling to a requested rate as f32, PCM16 or G.711 bytes
+//                    q3_formant.hip, included at the unit's end) -> tone (a biquad cascade by a block-parallel scan: q3_tone.hip,
+//                    included likewise) -> BS.1770 loudness meter / normaliser -> level (gain and look-ahead peak limiter) ->
+//                    resampling to a requested rate as f32, PCM16 or G.711 bytes
 //   q3_intake.hip    the reference-audio intake: a clip in its on-disk sample format -> 24 kHz mono f32 on the device in one launch,
 //                    where both encoders read it
 //   q3_denoise.hip   spectral noise suppression of such a clip: STFT analysis, minimum-statistics gain, overlap-add synthesis
@@ -467,10 +468,11 @@ struct OutSettings {
     int sil_mB = 0, edge_ms = 0, pause_ms = 20;               // the silence step's threshold, 0: off
     uint64_t mark_key = 0; int mark_mB = Q3_MARK_STRENGTH_DEFAULT;               // the mark step's key, 0: off; its strength
     int fm_keep = 0, fm_cents = 0;                            // the formant step: keep the formants where the pitch moves; their own shift in cents
+    int tone_n = 0; q3_tone_band tone[Q3_TONE_MAX_BANDS] = {};               // the tone step's bands in cascade order, 0: off
     // 24 kHz f32 with every step off: the samples leave as they are, and no stage is needed
     bool plain() const {
         return rate == 24000 && fmt == Q3_PCM_F32 && tempo == 1000 && cents == 0 && gain_mB == 0 && ceil_mB == 0 && loud == Q3_LOUD_OFF && sil_mB == 0 &&
-               mark_key == 0 && fm_cents == 0;                  // (fm_keep alone moves nothing while the pitch is 0)
+               mark_key == 0 && fm_cents == 0 && tone_n == 0;   // (fm_keep alone moves nothing while the pitch is 0)
     }
     size_t sample_bytes() const { return fmt == Q3_PCM_F32 ? 4 : fmt == Q3_PCM_S16 ? 2 : 1; }
 };
@@ -658,6 +660,7 @@ Q3_HIDDEN q3_status out_set_loudness(const char* who, OutSettings& o, int mode, 
 Q3_HIDDEN q3_status out_set_silence(const char* who, OutSettings& o, int threshold_mB, int edge_ms, int pause_ms);
 Q3_HIDDEN q3_status out_set_mark(const char* who, OutSettings& o, uint64_t key, int strength_mB);
 Q3_HIDDEN q3_status out_set_formant(const char* who, OutSettings& o, int keep, int fcents);
+Q3_HIDDEN q3_status out_set_tone(const char* who, OutSettings& o, int n_bands, const q3_tone_band* bands);
 // The only writer of a row's step settings: what the steps that `o` turns on need on the device, the values derived from `o`,
 // and the row's restart. All or nothing (but see the silence step's state there). pcm_stage_settings: what the row was given last.
 Q3_HIDDEN q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutSettings& o);
@@ -699,6 +702,24 @@ Q3_HIDDEN float formant_omega(int t, int te, int keep, int fcents);      // the 
 Q3_HIDDEN q3_status formant_checked(const char* who, int keep, int fcents);
 Q3_HIDDEN void formant_tables(std::vector<float>& tab);
 Q3_HIDDEN hipError_t formant_launch(const FmDesc* descs_dev, int n_rows, int max_frames, int max_tiles, const float* tab_dev, hipStream_t st);
+// q3_tone.hip: the tone step of the output stage. q3_pcm_stage.hip owns the row's state and the chain.
+constexpr int TN_MAX = Q3_TONE_MAX_BANDS;                   // sections of a row
+constexpr int TN_SEG = 64, TN_CHUNK = 64 * TN_SEG;          // samples of a lane's segment; of a wave's pass through LDS
+constexpr int TN_TAB = 5 + 4 * TN_SEG;                      // doubles a section has on the host: b0 b1 b2 a1 a2, then A^1 .. A^64
+constexpr int TN_FREQ_MIN = 20, TN_FREQ_MAX = 11000, TN_GAIN_MAX = 2400, TN_Q_MIN = 100, TN_Q_MAX = 10000;
+// One section as k_tone takes it: the coefficients over a0, A^64 and the power of the push's ragged last segment (row-major)
+struct TnSec { double b0, b1, b2, a1, a2, A64[4], Ar[4]; };
+// One row of a pass of k_tone (device-visible, 8-byte aligned): n_new samples of src pass n_sec sections into y; st_in (null at the
+// row's start) / st_out are the two copies of the row's state, (s1, s2) per section
+struct TnDesc {
+    const float* src; float* y; const double* st_in; double* st_out;
+    int n_new, n_sec;
+    TnSec sec[TN_MAX];
+};
+Q3_HIDDEN q3_status tone_checked(const char* who, int n_bands, const q3_tone_band* bands);
+Q3_HIDDEN void tone_plan(int n_bands, const q3_tone_band* bands, std::vector<double>& tab);      // a row's sections, TN_TAB doubles each
+Q3_HIDDEN void tone_fill(const std::vector<double>& tab, int n_new, TnDesc& d);
+Q3_HIDDEN hipError_t tone_launch(const TnDesc* descs_dev, int n_rows, hipStream_t st);
 // q3_session.hip
 Q3_HIDDEN hipError_t sync_frames(q3_session* s);
 Q3_HIDDEN q3_status kv_reserve_row(q3_session* s, int b, int n_pos);

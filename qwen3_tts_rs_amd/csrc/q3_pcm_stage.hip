@@ -1,12 +1,12 @@
 // q3_pcm_stage.hip — the output stage: 24 kHz f32 from the vocoder -> per row a requested sample rate and format, through the
 // steps the row has asked for. (A unit of the engine: q3_engine.h says which holds what.)
 //
-// A row's stream passes a chain of eight steps, front to back: silence -> stretcher -> pitch -> formant -> loudness -> mark -> level ->
+// A row's stream passes a chain of nine steps, front to back: silence -> stretcher -> pitch -> formant -> tone -> loudness -> mark -> level ->
 // resampler / format. The last one every row has; each of the others is on for the rows that ask for it, and a row whose step is off is not
 // touched by any of it: no launch, no buffer, no descriptor, no allocation. Every step counts the samples that have entered and
 // left it, keeps what the next push still needs on the device in two copies — a push reads one and writes the other, and they are
 // flipped when the push has succeeded: a push that fails or is refused leaves the row exactly where it was — and writes a push's
-// samples into the row's part of a buffer of its own (s, y, v, w, m, z), which the next step that is on takes as the row's input.
+// samples into the row's part of a buffer of its own (s, y, v, u, q, w, m, z), which the next step that is on takes as the row's input.
 // One launch per step serves every row of a push that has the step, a descriptor per row. The host side further down writes the
 // chain once (step_on, step_emitted, step_cap, chain_walk); the count, the plan and the commit of a push are three uses of it.
 //
@@ -35,6 +35,11 @@
 // moves the formants back where the pitch step moved them (omega = t / te) or by a shift of their own; the frames are overlap-added
 // in ascending order into u. It is length-preserving and holds at most 1023 samples back; the row keeps those and 768 partial sums.
 // A row whose omega is 1 has no formant step.
+//
+// 3h. The tone step (its kernel and rules are q3_tone.hip's). Up to 8 biquad sections per row, designed on the host in
+// f64 per setting; k_tone runs each over 64-sample segments in parallel and mends the segments' entry states by a scan of their
+// affine state maps across the wave. It holds nothing back; the row keeps two f64 states per section in two copies. A row with no
+// bands has no tone step.
 //
 // 4. The loudness step. k_loud K-weights the stream (ITU-R BS.1770-4: two biquads), keeps the energy of every 100 ms
 // hop and the mean square of every 400 ms block, gates the blocks the row has seen so far (absolute and relative gate) into its
@@ -984,6 +989,11 @@ struct FormantStep : Totals {                 // DESIGN 4.12g; omega: formant_om
     float* state = nullptr; int cur = 0;      // two copies of FM_STATE_FLOATS floats: [tail | partial sums]
     void reset() { in = out = 0; }
 };
+struct ToneStep : Totals {                    // DESIGN 4.12h; tab empty: off; out == in: the step holds nothing back
+    std::vector<double> tab;                  // tone_plan of the row's bands: TN_TAB doubles per section
+    double* state = nullptr; int cur = 0;     // two copies of 2 * TN_MAX doubles: (s1, s2) per section
+    void reset() { in = out = 0; }
+};
 struct LoudStep : Totals {                    // DESIGN 4.12c; out == in: the step holds nothing back
     int mode = Q3_LOUD_OFF; float T = 0.0f, P = 1.0f, gate = 0.0f, lo = 0.0f, hi = 0.0f;
     float* state = nullptr; int cur = 0;      // two copies of LD_STATE floats, then the LD_HIST block values (one copy)
@@ -1007,20 +1017,21 @@ struct ResStep : Totals {                     // the resampler and 
 };
 struct PsRow {
     OutSettings asked;
-    SilStep sil; TempoStep tp; PitchStep pt; FormantStep fm; LoudStep ld; MarkStep mk; LevelStep lv; ResStep rs;
+    SilStep sil; TempoStep tp; PitchStep pt; FormantStep fm; ToneStep tn; LoudStep ld; MarkStep mk; LevelStep lv; ResStep rs;
     bool ended = false;                       // flushed by a push with `last`: restarted by pcm_stage_apply / reset only
-    void reset() { sil.reset(); tp.reset(); pt.reset(); fm.reset(); ld.reset(); mk.reset(); lv.reset(); rs.reset(); ended = false; }
+    void reset() { sil.reset(); tp.reset(); pt.reset(); fm.reset(); tn.reset(); ld.reset(); mk.reset(); lv.reset(); rs.reset(); ended = false; }
 };
 constexpr size_t TP_STATE_BYTES = 16 + (size_t)TP_HIST * 4;
 
 // ---- the chain, written once ----
-enum { ST_SIL, ST_TEMPO, ST_PITCH, ST_FORMANT, ST_LOUD, ST_MARK, ST_LEVEL, ST_RES, ST_N };
+enum { ST_SIL, ST_TEMPO, ST_PITCH, ST_FORMANT, ST_TONE, ST_LOUD, ST_MARK, ST_LEVEL, ST_RES, ST_N };
 static bool step_on(const PsRow& r, int s) {
     switch (s) {
     case ST_SIL: return r.sil.thr != 0;
     case ST_TEMPO: return r.tp.te != TP_OFF;
     case ST_PITCH: return r.pt.te != r.pt.t;
     case ST_FORMANT: return r.fm.omega != 1.0f;
+    case ST_TONE: return !r.tn.tab.empty();
     case ST_LOUD: return r.ld.mode != Q3_LOUD_OFF;
     case ST_MARK: return r.mk.key != 0;
     case ST_LEVEL: return r.lv.on;
@@ -1033,6 +1044,7 @@ static const Totals& step_totals(const PsRow& r, int s) {
     case ST_TEMPO: return r.tp;
     case ST_PITCH: return r.pt;
     case ST_FORMANT: return r.fm;
+    case ST_TONE: return r.tn;
     case ST_LOUD: return r.ld;
     case ST_MARK: return r.mk;
     case ST_LEVEL: return r.lv;
@@ -1096,7 +1108,7 @@ static void chain_walk(const PsRow& r, int first, long long n, bool last, SegWal
 struct StepPlan {
     std::vector<SegWalk> seg;
     std::vector<TrDesc> sdesc; std::vector<int> sseg; std::vector<long long> sres;      // the pre-pass: descriptors, their segments, the counters that came back
-    std::vector<TpDesc> tdesc; std::vector<PtDesc> pdesc; std::vector<FmDesc> fdesc; std::vector<LoDesc> odesc; std::vector<MkDesc> mdesc;
+    std::vector<TpDesc> tdesc; std::vector<PtDesc> pdesc; std::vector<FmDesc> fdesc; std::vector<TnDesc> ndesc; std::vector<LoDesc> odesc; std::vector<MkDesc> mdesc;
     std::vector<LvDesc> ldesc;
     int tiles[ST_N];
     int fm_frames;                            // the most frames a row's formant step runs in this push
@@ -1307,7 +1319,7 @@ extern "C" void q3_pcm_stage_free(q3_pcm_stage* ps) {
     dev_free(ps->tails); dev_free(ps->s_win); dev_free(ps->t_win); dev_free(ps->p_tab); dev_free(ps->f_tab);
     ps->f_fr.release();
     for (PsRow& r : ps->rows) {
-        dev_free(r.sil.state); dev_free(r.tp.state); dev_free(r.pt.tail); dev_free(r.fm.state); dev_free(r.ld.state); dev_free(r.mk.tab); dev_free(r.lv.tail);
+        dev_free(r.sil.state); dev_free(r.tp.state); dev_free(r.pt.tail); dev_free(r.fm.state); dev_free(r.tn.state); dev_free(r.ld.state); dev_free(r.mk.tab); dev_free(r.lv.tail);
         r.tp.lags[0].release(); r.tp.lags[1].release();
     }
     for (int s = 0; s < ST_N; ++s) { ps->buf[s].release(); ps->desc[s].release(); }
@@ -1673,6 +1685,12 @@ q3_status out_set_formant(const char* who, OutSettings& o, int keep, int fcents)
     o.fm_keep = keep; o.fm_cents = fcents;
     return Q3_OK;
 }
+q3_status out_set_tone(const char* who, OutSettings& o, int n_bands, const q3_tone_band* bands) {
+    Q3C(tone_checked(who, n_bands, bands));
+    o.tone_n = n_bands;
+    for (int i = 0; i < TN_MAX; ++i) o.tone[i] = i < n_bands ? bands[i] : q3_tone_band{0, 0, 0, 0};
+    return Q3_OK;
+}
 
 // `o` (which came through the checked edits) onto a row. First everything that can fail — the tables and the row's states of the
 // steps that `o` turns on, each made by the first call that needs it and kept from then on —, then the step fields, then the
@@ -1725,6 +1743,7 @@ q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutS
         }
         Q3C(row_state(ps, &r.fm.state, 2 * (size_t)FM_STATE_FLOATS * 4, who, "formant state", row));
     }
+    if (o.tone_n > 0) Q3C(row_state(ps, &r.tn.state, 2 * 2 * (size_t)TN_MAX * sizeof(double), who, "tone state", row));
     if (o.loud != Q3_LOUD_OFF) {
         if (!ps->o_coef_set) {
             // the K-weighting at 24 kHz: in f64, rounded once
@@ -1771,6 +1790,7 @@ q3_status pcm_stage_apply(q3_pcm_stage* ps, int row, const char* who, const OutS
     r.rs.sr = o.rate; r.rs.fmt = o.fmt; r.rs.r = rate; r.rs.taps = taps;
     r.pt.t = o.tempo; r.pt.te = r.tp.te = te;
     r.fm.omega = omega;
+    tone_plan(o.tone_n, o.tone, r.tn.tab);                      // (the sections in f64, once per setting)
     r.lv.on = level;
     (void)q3_pcm_stage_level_coeffs(o.gain_mB, o.ceil_mB, &r.lv.g, &r.lv.c);
     r.ld.mode = o.loud;
@@ -1810,6 +1830,9 @@ extern "C" q3_status q3_pcm_stage_set_mark(q3_pcm_stage* ps, int row, uint64_t k
 }
 extern "C" q3_status q3_pcm_stage_set_formant(q3_pcm_stage* ps, int row, int keep, int fcents) {
     return stage_set(ps, row, "q3_pcm_stage_set_formant", [&](const char* who, OutSettings& o) { return out_set_formant(who, o, keep, fcents); });
+}
+extern "C" q3_status q3_pcm_stage_set_tone(q3_pcm_stage* ps, int row, int n_bands, const q3_tone_band* bands) {
+    return stage_set(ps, row, "q3_pcm_stage_set_tone", [&](const char* who, OutSettings& o) { return out_set_tone(who, o, n_bands, bands); });
 }
 extern "C" q3_status q3_pcm_stage_set_silence(q3_pcm_stage* ps, int row, int threshold_mB, int edge_ms, int pause_ms) {
     return stage_set(ps, row, "q3_pcm_stage_set_silence", [&](const char* who, OutSettings& o) { return out_set_silence(who, o, threshold_mB, edge_ms, pause_ms); });
@@ -1916,6 +1939,7 @@ static q3_status step_ready(const q3_pcm_stage* ps, const PsRow& r, int row, int
     case ST_TEMPO: if (!r.tp.state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tempo and no state", row); break;
     case ST_PITCH: if (!r.pt.tail || !ps->p_tab) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a pitch and no state", row); break;
     case ST_FORMANT: if (!r.fm.state || !ps->f_tab) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a formant step and no state", row); break;
+    case ST_TONE: if (!r.tn.state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a tone step and no state", row); break;
     case ST_LOUD: if (!r.ld.state) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a loudness step and no state", row); break;
     case ST_MARK: if (!r.mk.tab || r.mk.tab_key != r.mk.key) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a mark and no carrier", row); break;
     case ST_LEVEL: if (!r.lv.tail) return set_err(Q3_INVALID_ARG, "pcm stage: row %d has a level and no state", row); break;
@@ -1971,6 +1995,17 @@ static q3_status step_fill(q3_pcm_stage* ps, PsPlan& plan, const PsSeg& sg, cons
             // the hops k_fm_ola visits: the emitted ones and the ones whose partial sums it hands on
             const long long pend = sg.last ? f.n_total : f.k1 * FM_H;
             p.tiles[s] = std::max(p.tiles[s], (int)((pend - f.o_base + FM_H - 1) / FM_H));
+        }
+        break;
+    }
+    case ST_TONE: {
+        if (n_in > 0) {                                            // (nothing passes: no descriptor, no flip)
+            const ToneStep& tn = r.tn;
+            TnDesc t{};
+            t.src = src; t.y = (float*)dst;
+            t.st_in = tn.in > 0 ? tn.state + (size_t)tn.cur * 2 * TN_MAX : nullptr; t.st_out = tn.state + (size_t)(tn.cur ^ 1) * 2 * TN_MAX;
+            tone_fill(tn.tab, n_in, t);
+            p.ndesc.push_back(t);
         }
         break;
     }
@@ -2032,7 +2067,7 @@ static q3_status step_fill(q3_pcm_stage* ps, PsPlan& plan, const PsSeg& sg, cons
 static q3_status chain_plan(q3_pcm_stage* ps, const std::vector<PsSeg>& segs, PsPlan& plan) {
     StepPlan& p = ps->plan;
     plan.desc.clear(); plan.off.assign(segs.size(), 0); plan.count.assign(segs.size(), 0); plan.bytes = 0;
-    p.tdesc.clear(); p.pdesc.clear(); p.fdesc.clear(); p.odesc.clear(); p.mdesc.clear(); p.ldesc.clear();
+    p.tdesc.clear(); p.pdesc.clear(); p.fdesc.clear(); p.ndesc.clear(); p.odesc.clear(); p.mdesc.clear(); p.ldesc.clear();
     size_t floats[ST_N] = {0}, fr_floats = 0;
     for (int s = 0; s < ST_N; ++s) p.tiles[s] = 1;
     p.fm_frames = 0;
@@ -2083,6 +2118,11 @@ static hipError_t chain_launch(q3_pcm_stage* ps, const PsPlan& plan, const PsDes
         e = b.upload(p.fdesc.data(), p.fdesc.size() * sizeof(FmDesc), st);
         if (e == hipSuccess) e = formant_launch((const FmDesc*)b.dev, (int)p.fdesc.size(), p.fm_frames, p.tiles[ST_FORMANT], ps->f_tab, st);
     }
+    if (e == hipSuccess && !p.ndesc.empty()) {                     // a workgroup per row
+        PairBuf& b = ps->desc[ST_TONE];
+        e = b.upload(p.ndesc.data(), p.ndesc.size() * sizeof(TnDesc), st);
+        if (e == hipSuccess) e = tone_launch((const TnDesc*)b.dev, (int)p.ndesc.size(), st);
+    }
     if (e == hipSuccess) e = step_launch<LoDesc, k_loud>(ps->desc[ST_LOUD], p.odesc, dim3((unsigned)p.odesc.size()), dim3(LD_THREADS), st);
     if (e == hipSuccess) e = step_launch<MkDesc, k_mark>(ps->desc[ST_MARK], p.mdesc, dim3((unsigned)p.mdesc.size()), dim3(MK_THREADS), st);
     if (e == hipSuccess) e = step_launch<LvDesc, k_level>(ps->desc[ST_LEVEL], p.ldesc, dim3((unsigned)p.tiles[ST_LEVEL], (unsigned)p.ldesc.size()), dim3(PS_TILE), st);
@@ -2106,6 +2146,7 @@ static void chain_commit(q3_pcm_stage* ps, const std::vector<PsSeg>& segs) {
         }
         if (step_on(r, ST_PITCH)) { add(r.pt, ST_PITCH); if (!sg.last) r.pt.cur ^= 1; }
         if (step_on(r, ST_FORMANT) && (w.n_in[ST_FORMANT] > 0 || w.n_out[ST_FORMANT] > 0)) { add(r.fm, ST_FORMANT); if (!sg.last) r.fm.cur ^= 1; }
+        if (step_on(r, ST_TONE) && w.n_in[ST_TONE] > 0) { add(r.tn, ST_TONE); r.tn.cur ^= 1; }
         if (step_on(r, ST_LOUD) && w.n_in[ST_LOUD] > 0) { add(r.ld, ST_LOUD); r.ld.cur ^= 1; }
         if (step_on(r, ST_MARK) && w.n_in[ST_MARK] > 0) { add(r.mk, ST_MARK); r.mk.cur ^= 1; }
         if (step_on(r, ST_LEVEL)) { add(r.lv, ST_LEVEL); if (!sg.last) r.lv.cur ^= 1; }
@@ -2239,3 +2280,5 @@ extern "C" q3_status q3_pcm_stage_push(q3_pcm_stage* ps, int n_rows, const int* 
 
 // the formant step's kernels and rules: part of this unit
 #include "q3_formant.hip"
+// ... and the tone step's
+#include "q3_tone.hip"

@@ -2032,6 +2032,9 @@ extern "C" q3_status q3_session_set_pitch(q3_session* s, int b, int cents) {
 extern "C" q3_status q3_session_set_formant(q3_session* s, int b, int keep, int fcents) {
     return session_set_rows(s, b, "q3_session_set_formant", "formant step", [&](const char* who, OutSettings& o) { return out_set_formant(who, o, keep, fcents); });
 }
+extern "C" q3_status q3_session_set_tone(q3_session* s, int b, int n_bands, const q3_tone_band* bands) {
+    return session_set_rows(s, b, "q3_session_set_tone", "tone", [&](const char* who, OutSettings& o) { return out_set_tone(who, o, n_bands, bands); });
+}
 extern "C" q3_status q3_session_set_level(q3_session* s, int b, int gain_mB, int ceiling_mB) {
     return session_set_rows(s, b, "q3_session_set_level", "level", [&](const char* who, OutSettings& o) { return out_set_level(who, o, gain_mB, ceiling_mB); });
 }

@@ -23,6 +23,9 @@ pub mod ffi {
         pub dec_up_ratios: [i32; 2], pub dec_up_rates: [i32; 4], pub dec_eps: f32, pub dec_theta: f32 }
     #[repr(C)] #[derive(Default, Clone, Copy)]
     pub struct Q3Timing { pub prefill_ms: f64, pub generation_ms: f64, pub decode_ms: f64, pub generation_frames: i32 }
+    /// q3_tone_band: kind (0 peak, 1 low shelf, 2 high shelf, 3 high-pass, 4 low-pass), Hz, millibel, Q x 1000
+    #[repr(C)] #[derive(Clone, Copy, Default)]
+    pub struct Q3ToneBand { pub kind: i32, pub freq_hz: i32, pub gain_mb: i32, pub q_milli: i32 }
     #[repr(C)] #[derive(Clone, Copy, Default)]
     pub struct Q3SpkConfig { pub mel_dim: i32, pub enc_dim: i32, pub channels: [i32; 5], pub kernel_sizes: [i32; 5], pub dilations: [i32; 5],
         pub attention_channels: i32, pub res2net_scale: i32, pub se_channels: i32, pub sample_rate: i32 }
@@ -154,6 +157,11 @@ pub mod ffi {
         pub fn q3_pcm_stage_bound_formant(sample_rate: u32, tempo_permille: i32, cents: i32, with_level: i32, edge_ms: i32, pause_ms: i32, n_in: usize, n_out_max: *mut usize) -> i32;
         pub fn q3_session_set_formant(s: *mut c_void, b: i32, keep: i32, fcents: i32) -> i32;
         pub fn q3_batcher_ticket_formant(b: *mut c_void, ticket: i64, keep: i32, fcents: i32) -> i32;
+        // the output stage's tone step: up to 8 biquad bands per row behind the formant step; 0 bands = off
+        pub fn q3_pcm_stage_set_tone(ps: *mut c_void, row: i32, n_bands: i32, bands: *const Q3ToneBand) -> i32;
+        pub fn q3_tone_design(rate: u32, band: *const Q3ToneBand, ba: *mut f64) -> i32;
+        pub fn q3_session_set_tone(s: *mut c_void, b: i32, n_bands: i32, bands: *const Q3ToneBand) -> i32;
+        pub fn q3_batcher_ticket_tone(b: *mut c_void, ticket: i64, n_bands: i32, bands: *const Q3ToneBand) -> i32;
         // the output stage's silence step: edges trimmed and pauses capped per row, at the very front; threshold 0 = off
         pub fn q3_pcm_stage_set_silence(ps: *mut c_void, row: i32, threshold_mb: i32, edge_ms: i32, pause_ms: i32) -> i32;
         pub fn q3_pcm_stage_silence(ps: *mut c_void, row: i32, n_in: *mut i64, n_out: *mut i64, lead_cut: *mut i64, pause_cut: *mut i64, trail_cut: *mut i64) -> i32;
